@@ -38,7 +38,12 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W      (N > 1: l
     "timeout": true and the process ends with a non-zero status;
   * N = 1, --config 4k (the driver's command): behind the headline configuration the 8K (configs[2]) and all-intra (configs[4]) configurations run in short
     windows, each in a process of its own, and land in config.other_configs (fps, device only, pictures verified against the oracle); roofline carries the
-    dominant kernel, the dominant kernel of the B pictures and the I picture's intra kernel apart, and the VALU-issue utilisation from the counter pass.
+    dominant kernel, the dominant kernel of the B pictures and the I picture's intra kernel apart, and the VALU-issue utilisation from the counter pass;
+  * a plain run does only what `value` needs: set-up, the --repeats windows (pre-roll, warm-up, K timed pictures), the line.  Everything else above - the
+    look-ahead-0 windows, the device-only pass (N = 1), roofline, verification, cpu_baseline, other_configs, value_k64 - runs with --full only;
+  * --dump-outputs DIR: after the timed windows, the planes of the picture the last timed step reconstructed (what vvr_submit's caller reads back) are
+    written as DIR/y.npy, cb.npy, cr.npy in float32.  The inputs are seeded, so two builds run with the same arguments can be compared plane for plane.
+    Where the planes exceed 60 MB (8K) every plane keeps a fixed, seeded sample of its rows, and DIR/<plane>_rows.npy holds their indices.
 """
 import argparse
 import ctypes as C
@@ -266,6 +271,22 @@ def cpu_baseline(cfg_name, seed, gop, budget_s=20.0):
     return {"value": per_process["value"], "unit": "frames/s", "cores": cores, "kind": kind, "host_cores": os.cpu_count(), "sample": per_process["what"]}
 
 
+DUMP_BYTES = 60 * 10**6          # --dump-outputs writes at most this many bytes of planes
+
+
+def dump_outputs(path, planes, names=("y", "cb", "cr")):
+    """--dump-outputs: the planes of one reconstructed picture as float32 <path>/<name>.npy; above DUMP_BYTES a seeded sample of every plane's rows"""
+    os.makedirs(path, exist_ok=True)
+    total = 4 * sum(p.size for p in planes)
+    for name, p in zip(names, planes):
+        x = p.astype(np.float32)
+        if total > DUMP_BYTES:
+            rows = np.sort(np.random.default_rng(0).choice(p.shape[0], max(1, p.shape[0] * DUMP_BYTES // total), replace=False))
+            x = x[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float32))
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def kernel_source_hash():
     """MD5 over the kernel and host sources of the library (the files the Makefile lists): the counter / traffic summaries under profiles/ carry the hash of
     the sources they were measured with (tools/collect_profiles.py, tools/gpu_r6_counters.sh), and the line says "stale" when it differs"""
@@ -367,10 +388,12 @@ def main():
     ap.add_argument("--pageable-records", action="store_true", help="keep the host records in ordinary (pageable) memory: the library stages them through its pinned ring")
     ap.add_argument("--no-picture-sharding", action="store_true", help="N > 1: skip the additional pass that shards ONE stream by picture over the ranks")
     ap.add_argument("--picture-sharding-timeout", type=int, default=150, help="N > 1: seconds after which the picture-sharding pass is given up and the line is printed without it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1, --config 4k: do not run the 8K and all-intra configurations behind the headline one (config.other_configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, N = 1, --config 4k: do not run the 8K and all-intra configurations behind the headline one (config.other_configs)")
     ap.add_argument("--stop-after", type=int, default=0, help="developer: end the kernel chain after the reconstruction (1), deblocking (2) or SAO (3) stage, to see what a stage costs; needs --verify 0")
-    ap.add_argument("--verify", type=int, default=8, help="number of timed pictures re-checked against the CPU oracle after the run")
+    ap.add_argument("--verify", type=int, default=8, help="--full: number of timed pictures re-checked against the CPU oracle after the run")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: the look-ahead-0 windows, the device-only pass, roofline, verification, cpu_baseline, other_configs, value_k64")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the planes of the picture the last timed step reconstructed to DIR/<plane>.npy (float32)")
     a = ap.parse_args()
     if a.streams < 0:
         a.streams = 12 if a.config == "allintra" else 4       # (all-intra: 8 / 10 / 12 / 14 / 16 lanes: device only 900 / 1009 / 1199 / 1236 / 880, through vvr_submit 816 / 934 / 936 / 937 / 629)
@@ -464,18 +487,21 @@ def main():
 
     # ---- the timed runs.  One K-picture window is 10-20 ms of a pipeline with 16 host threads in it: a noisy instrument.  The window is therefore
     # run --repeats times, every time from the first picture of the stream (fresh pre-roll), and `value` is the MEDIAN; all samples are printed.
-    # The same stream in plain decoding order (no IRAP look-ahead: what a host without a reorder buffer submits) is timed next to it.
+    # With --full, the same stream in plain decoding order (no IRAP look-ahead: what a host without a reorder buffer submits) is timed next to it.
     dts = [window(order, first) for _ in range(max(1, a.repeats))]
     enq_host = enq["host"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rec.read_picture(plans[order[first + K - 1]].slot))
     tail_n = min(8, K)
-    keep = order[first + K - tail_n:first + K] + [i for i in order[first:first + K] if plans[i].slice_type == abi.SLICE_I]
-    later = {i: k for k, i in enumerate(order[:first + K])}
-    # (a timed picture can be checked if nothing submitted after it has overwritten its slot: the last pictures and, with a 48-slot DPB, the IRAP)
-    timed_out = {i: rec.read_picture(plans[i].slot) for i in dict.fromkeys(keep) if all(plans[j].slot != plans[i].slot for j in order[later[i] + 1:first + K])}
-    dts0 = []
-    if a.irap_lookahead and a.config != "allintra":
-        order0, first0 = orders[0]
-        dts0 = [window(order0, first0) for _ in range(max(1, min(3, a.repeats)))]
+    timed_out, dts0 = {}, []
+    if a.full:
+        keep = order[first + K - tail_n:first + K] + [i for i in order[first:first + K] if plans[i].slice_type == abi.SLICE_I]
+        later = {i: k for k, i in enumerate(order[:first + K])}
+        # (a timed picture can be checked if nothing submitted after it has overwritten its slot: the last pictures and, with a 48-slot DPB, the IRAP)
+        timed_out = {i: rec.read_picture(plans[i].slot) for i in dict.fromkeys(keep) if all(plans[j].slot != plans[i].slot for j in order[later[i] + 1:first + K])}
+        if a.irap_lookahead and a.config != "allintra":
+            order0, first0 = orders[0]
+            dts0 = [window(order0, first0) for _ in range(max(1, min(3, a.repeats)))]
     dt = float(np.median(dts))
 
     # ---- the same K pictures with records and work lists resident in HBM (the device pipeline alone)
@@ -494,17 +520,42 @@ def main():
         barrier(all_ranks)
         return time.perf_counter() - t0
 
-    window(order, first)                               # (the DPB as the headline order leaves it)
-    resident_pass(first - Wm, Wm)
-    dt_dev = resident_pass(first, K)
-    enq_dev = enq["device"]
-    if world > 1:
-        t = torch.tensor([dt_dev], device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_dev = float(t.item())
+    dt_dev = None
+    if a.full or world > 1:                            # (N > 1: the ceilings of the picture mode are drawn at the device-only time per picture)
+        window(order, first)                           # (the DPB as the headline order leaves it)
+        resident_pass(first - Wm, Wm)
+        dt_dev = resident_pass(first, K)
+        enq_dev = enq["device"]
+        if world > 1:
+            t = torch.tensor([dt_dev], device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_dev = float(t.item())
 
     out = None
     if rank == 0:
+        fps = world * K / dt
+        metric = {"4k": "decoded frames/sec (4K 10-bit RA) on MI355X, synthetic pre-parsed stream, bit-exact vs ref",
+                  "8k": "decoded frames/sec (8K 10-bit RA) on MI355X, synthetic pre-parsed stream, bit-exact vs ref",
+                  "allintra": "decoded frames/sec (4K 10-bit all-intra) on MI355X, synthetic pre-parsed stream, bit-exact vs ref"}[a.config]
+        out = {"metric": metric, "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wm,
+               "ms_per_step": round(1e3 * dt / K, 4), "higher_is_better": True, "scaling": "weak" if world > 1 else None, "vs_baseline": None,
+               "dtype": "int16", "data": "synthetic",
+               "config": {"workload": "%s, %dx%d, CTU 128%s; timed: K pictures through vvr_submit from host records (validation, work lists on %d library threads, H2D of %.1f MB per picture, all kernels); %d pre-roll + W warm-up pictures untimed; %d IRAP picture(s) in the timed window"
+                                      % (cfg_text, W, H, "" if a.config == "allintra" else ", hierarchical-B GOP %d, IRAP every %d pictures, submitted %d pictures ahead of its decoding-order position" % (a.gop, intra_period, a.irap_lookahead),
+                                         a.host_threads, upload_mb, first - Wm, n_irap),
+                          "conformance": "JVET set unpinned: no JVET bitstream exists offline; parser-fed parity is pinned on the streams tools/mini_vvenc.py writes (tests/bitstreams, reference decoder's MD5 / picture hashes)",
+                          "timed_path": "vvr_submit(host records)", "affine_sub_block_mvs": "spanned on the device from the control points (VVR_TOOL_AFFINE_MV_ON_DEVICE)" if a.affine_mv == "device" else "supplied by the host (motion field)", "lf_init": "k_lf_init (VVR_TOOL_LFP_ON_DEVICE: edge parameters derived on the device, no table uploaded)" if a.lf_init == "device" else "tables supplied by the host", "host_records_in": "pageable memory (staged by the library)" if a.pageable_records else "pinned host memory of the context (vvr_host_alloc): cu / tu / coef / lfp arrays are copied to HBM from where the generator wrote them", "host_threads": a.host_threads, "host_cores": os.cpu_count(),
+                          "value_is": "median of %d runs of the K-picture window, each from the first picture of the stream (pre-roll and warm-up untimed)" % len(dts),
+                          "value_samples_fps": [round(world * K / x, 1) for x in dts], "value_min_fps": round(world * K / max(dts), 2), "value_max_fps": round(world * K / min(dts), 2),
+                          "irap_in_window": n_irap, "irap_share_of_stream": "1/%d" % intra_period if a.config != "allintra" else "1/1",
+                          "tools": "intra planar/DC/angular/wide-angle + PDPC + MRL + reference smoothing + BDPCM + ISP, LFNST, inter uni/bi MC (8/4-tap DCTIF, alt half-pel, BCW), BDOF, DMVR, affine 4/6-parameter + PROF, GPM, CIIP, SbTMVP, CCLM/MDLM, MIP, LMCS luma mapping + chroma residual scaling, dequant + dep-quant, DCT2/DST7/DCT8 + transform skip, joint Cb-Cr, deblocking, SAO, ALF + CC-ALF",
+                          "mix": mix,
+                          "picture_sharding": None, "pictures_in_flight": a.streams, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "sharding": "closed-GOP segment per GPU, no data-path collective" if world > 1 else None}}
+        if dt_dev is not None:
+            out["config"].update({"device_only_fps": round(world * K / dt_dev, 2), "device_only_ms_per_step": round(1e3 * dt_dev / K, 4),
+                                  "submit_loop_ms": {"vvr_submit": round(1e3 * enq_host, 2), "vvr_submit_prepared": round(1e3 * enq_dev, 2), "what": "time the submitting thread spends in the K calls (of the timed K-picture passes: %.2f / %.2f ms)" % (1e3 * dt, 1e3 * dt_dev)},
+                                  "device_only_what": "same K pictures, records and work lists resident in HBM (vvr_prepare + vvr_submit_prepared)"})
+    if rank == 0 and a.full:
         # ---- roofline of the dominant kernel: a further pass over the K timed pictures only, HIP-event timing on the launch streams
         resident_pass(first - Wm, Wm, all_ranks=False)
         rec.enable_stats(True)
@@ -590,33 +641,12 @@ def main():
                         assert all(np.array_equal(g, w) for g, w in zip(got, want)), "bench: POC %d differs from the oracle" % pl.poc
                         verified += 1
             rec2.close()
-        fps = world * K / dt
         roof["frame_level"]["achieved_GBps_at_value"] = round(roof["frame_level"]["algorithmic_MB_per_picture"] * 1e6 * fps / world / 1e9, 1)
-        metric = {"4k": "decoded frames/sec (4K 10-bit RA) on MI355X, synthetic pre-parsed stream, bit-exact vs ref",
-                  "8k": "decoded frames/sec (8K 10-bit RA) on MI355X, synthetic pre-parsed stream, bit-exact vs ref",
-                  "allintra": "decoded frames/sec (4K 10-bit all-intra) on MI355X, synthetic pre-parsed stream, bit-exact vs ref"}[a.config]
-        out = {"metric": metric, "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wm,
-               "ms_per_step": round(1e3 * dt / K, 4), "higher_is_better": True, "scaling": "weak" if world > 1 else None, "vs_baseline": None,
-               "dtype": "int16", "data": "synthetic",
-               "config": {"workload": "%s, %dx%d, CTU 128%s; timed: K pictures through vvr_submit from host records (validation, work lists on %d library threads, H2D of %.1f MB per picture, all kernels); %d pre-roll + W warm-up pictures untimed; %d IRAP picture(s) in the timed window"
-                                      % (cfg_text, W, H, "" if a.config == "allintra" else ", hierarchical-B GOP %d, IRAP every %d pictures, submitted %d pictures ahead of its decoding-order position" % (a.gop, intra_period, a.irap_lookahead),
-                                         a.host_threads, upload_mb, first - Wm, n_irap),
-                          "conformance": "JVET set unpinned: no JVET bitstream exists offline; parser-fed parity is pinned on the streams tools/mini_vvenc.py writes (tests/bitstreams, reference decoder's MD5 / picture hashes)",
-                          "timed_path": "vvr_submit(host records)", "affine_sub_block_mvs": "spanned on the device from the control points (VVR_TOOL_AFFINE_MV_ON_DEVICE)" if a.affine_mv == "device" else "supplied by the host (motion field)", "lf_init": "k_lf_init (VVR_TOOL_LFP_ON_DEVICE: edge parameters derived on the device, no table uploaded)" if a.lf_init == "device" else "tables supplied by the host", "host_records_in": "pageable memory (staged by the library)" if a.pageable_records else "pinned host memory of the context (vvr_host_alloc): cu / tu / coef / lfp arrays are copied to HBM from where the generator wrote them", "host_threads": a.host_threads, "host_cores": os.cpu_count(),
-                          "value_is": "median of %d runs of the K-picture window, each from the first picture of the stream (pre-roll and warm-up untimed)" % len(dts),
-                          "value_samples_fps": [round(world * K / x, 1) for x in dts], "value_min_fps": round(world * K / max(dts), 2), "value_max_fps": round(world * K / min(dts), 2),
-                          "value_irap_lookahead_0": round(world * K / float(np.median(dts0)), 2) if dts0 else None,
-                          "value_irap_lookahead_0_samples_fps": [round(world * K / x, 1) for x in dts0],
-                          "value_irap_lookahead_0_what": "the same stream submitted in plain decoding order (a host without a reorder buffer): the IRAP arrives when its turn comes",
-                          "device_only_fps": round(world * K / dt_dev, 2), "device_only_ms_per_step": round(1e3 * dt_dev / K, 4),
-                          "submit_loop_ms": {"vvr_submit": round(1e3 * enq_host, 2), "vvr_submit_prepared": round(1e3 * enq_dev, 2), "what": "time the submitting thread spends in the K calls (of the timed K-picture passes: %.2f / %.2f ms)" % (1e3 * dt, 1e3 * dt_dev)},
-                          "device_only_what": "same K pictures, records and work lists resident in HBM (vvr_prepare + vvr_submit_prepared)",
-                          "irap_in_window": n_irap, "irap_share_of_stream": "1/%d" % intra_period if a.config != "allintra" else "1/1",
-                          "tools": "intra planar/DC/angular/wide-angle + PDPC + MRL + reference smoothing + BDPCM + ISP, LFNST, inter uni/bi MC (8/4-tap DCTIF, alt half-pel, BCW), BDOF, DMVR, affine 4/6-parameter + PROF, GPM, CIIP, SbTMVP, CCLM/MDLM, MIP, LMCS luma mapping + chroma residual scaling, dequant + dep-quant, DCT2/DST7/DCT8 + transform skip, joint Cb-Cr, deblocking, SAO, ALF + CC-ALF",
-                          "mix": mix,
-                          "picture_sharding": None, "pictures_in_flight": a.streams, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "sharding": "closed-GOP segment per GPU, no data-path collective" if world > 1 else None,
-                          "verified_timed_pictures_vs_oracle": verified, "timed_run_equals_serial_run": serial_equal},
-               "roofline": roof}
+        out["config"].update({"value_irap_lookahead_0": round(world * K / float(np.median(dts0)), 2) if dts0 else None,
+                              "value_irap_lookahead_0_samples_fps": [round(world * K / x, 1) for x in dts0],
+                              "value_irap_lookahead_0_what": "the same stream submitted in plain decoding order (a host without a reorder buffer): the IRAP arrives when its turn comes",
+                              "verified_timed_pictures_vs_oracle": verified, "timed_run_equals_serial_run": serial_equal})
+        out["roofline"] = roof
         if not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.config, seed, a.gop)
             if a.config != "allintra":
@@ -639,14 +669,14 @@ def main():
     rec.close()
     # ---- BASELINE configs[2] (8K RA QP27) and configs[4] (4K all-intra QP22) behind the headline configuration, each a run of this script in a process of its
     # own (short windows, no CPU baseline, the IRAP / one more picture against the oracle): config.other_configs.  The driver only ever runs the default command.
-    if rank == 0 and world == 1 and a.config == "4k" and not a.no_other_configs and not a.width:
+    if rank == 0 and world == 1 and a.full and a.config == "4k" and not a.no_other_configs and not a.width:
         import subprocess
         del descs, cpics
         others = {}
         for name, extra in (("8k", ["--steps", "16", "--warmup", "4", "--repeats", "3", "--verify", "1", "--intra-period", "32"]), ("allintra", ["--steps", "64", "--warmup", "16", "--repeats", "5", "--verify", "2"])):
             t0 = time.perf_counter()
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--no-cpu-baseline", "--no-other-configs"] + extra, capture_output=True, text=True, timeout=400)
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--full", "--no-cpu-baseline", "--no-other-configs"] + extra, capture_output=True, text=True, timeout=400)
                 o = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                 c = o["config"]
                 others[name] = {"fps": o["value"], "steps": o["steps"], "warmup": o["warmup"], "ms_per_step": o["ms_per_step"], "samples_fps": c["value_samples_fps"], "device_only_fps": c["device_only_fps"],
@@ -659,7 +689,7 @@ def main():
         # whose IRAP chain and fill weigh 3.2 times their share of the stream (round-5 verdict: a first-class field of the line, not only a file under profiles/)
         if K < 64:
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "64", "--warmup", "16", "--repeats", "3", "--verify", "0", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=300)
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "64", "--warmup", "16", "--repeats", "3", "--verify", "0", "--full", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=300)
                 o = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                 out["value_k64"] = {"fps": o["value"], "steps": 64, "warmup": 16, "ms_per_step": o["ms_per_step"], "samples_fps": o["config"]["value_samples_fps"], "device_only_fps": o["config"]["device_only_fps"],
                                     "what": "the same stream and path (vvr_submit from host records) over a 64-picture window with one IRAP: python bench.py --steps 64 --warmup 16"}

@@ -986,8 +986,8 @@ def test_bench_control_flow(stub, ranks):
     import sys
     tool = os.path.join(os.path.dirname(HERE), "tools", "bench_host_side.py")
     env = dict(os.environ, VVR_BENCH_BACKEND="gloo")
-    cmd = [sys.executable, tool] if ranks == 1 else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
-                                                    "--master-addr", "127.0.0.1", "--master-port", "29533", tool]
+    cmd = [sys.executable, tool, "--full"] if ranks == 1 else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
+                                                              "--master-addr", "127.0.0.1", "--master-port", "29533", tool, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1022,7 +1022,7 @@ def test_bench_line_survives_the_picture_sharding_pass(stub):
     import sys
     tool = os.path.join(os.path.dirname(HERE), "tools", "bench_host_side.py")
     env = dict(os.environ, VVR_BENCH_BACKEND="gloo", VVR_BENCH_EXTRA="--picture-sharding-timeout 0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29535", tool]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29535", tool, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, (r.returncode, r.stderr[-1500:])
@@ -1032,6 +1032,46 @@ def test_bench_line_survives_the_picture_sharding_pass(stub):
     # a pass that was given up is not a success: the line says so and the launch does not end with 0
     if out["config"]["picture_sharding"].get("timeout"):
         assert out.get("timeout") is True and r.returncode != 0
+
+
+def test_bench_plain_run_and_dump_outputs(stub, tmp_path):
+    """a plain bench.py run (no --full) prints the contract's keys and nothing that takes passes of its own; --dump-outputs writes the planes of the
+    picture the last timed step reconstructed as float32, and a second run with the same arguments writes the same arrays"""
+    import json
+    import sys
+    tool = os.path.join(os.path.dirname(HERE), "tools", "bench_host_side.py")
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("run%d" % run))
+        r = subprocess.run([sys.executable, tool, "--dump-outputs", d], capture_output=True, text=True, env=dict(os.environ, VVR_BENCH_BACKEND="gloo"), timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert k in out
+        assert out["steps"] == 6 and out["warmup"] == 4 and out["value"] > 0
+        assert abs(out["ms_per_step"] - 1e3 / out["value"]) < 0.01 * out["ms_per_step"]
+        assert "roofline" not in out and "cpu_baseline" not in out and "device_only_fps" not in out["config"] and "verified_timed_pictures_vs_oracle" not in out["config"]
+        planes = {n: np.load(os.path.join(d, n + ".npy")) for n in ("y", "cb", "cr")}
+        assert sorted(os.listdir(d)) == ["cb.npy", "cr.npy", "y.npy"]
+        assert planes["y"].dtype == np.float32 and planes["y"].shape == (128, 256) and planes["cb"].shape == planes["cr"].shape == (64, 128)
+        dumps.append(planes)
+    assert all(np.array_equal(dumps[0][n], dumps[1][n]) for n in dumps[0])
+
+
+def test_bench_dump_outputs_of_an_8k_picture_stay_under_64_mb(tmp_path):
+    """--dump-outputs of a picture too large for the budget (8K): every plane keeps the same seeded sample of its rows, the whole dump stays under 64 MB"""
+    import bench
+    H, W = 4320, 7680
+    planes = [np.arange(H * W, dtype=np.uint16).reshape(H, W)] + [np.full((H // 2, W // 2), c, np.uint16) for c in (1, 2)]
+    for run in range(2):
+        bench.dump_outputs(str(tmp_path / str(run)), planes)
+    assert sum(os.path.getsize(os.path.join(tmp_path, "0", f)) for f in os.listdir(tmp_path / "0")) <= 64 * 10**6
+    rows = np.load(tmp_path / "0" / "y_rows.npy")
+    y = np.load(tmp_path / "0" / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (len(rows), W) and np.array_equal(y, planes[0][rows.astype(np.int64)].astype(np.float32))
+    assert all(np.array_equal(np.load(tmp_path / "0" / f), np.load(tmp_path / "1" / f)) for f in os.listdir(tmp_path / "0"))
 
 
 def _submit_stream(stub, threads, W=416, H=240, frames=17, gop=8, lanes=3):

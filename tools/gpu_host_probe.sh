@@ -4,9 +4,9 @@
 out=gpurun_out/${1:-hostprobe}; mkdir -p $out
 A="--steps 20 --warmup 5 --repeats 3 --no-cpu-baseline --verify 0"
 for t in 8 10 20; do
-  timeout 300 python bench.py $A --host-threads $t > $out/bench_t$t.json 2> $out/bench_t$t.err
+  timeout 300 python bench.py --full $A --host-threads $t > $out/bench_t$t.json 2> $out/bench_t$t.err
 done
-VVDEC_AMD_LIB=$PWD/vvdec_amd/libvvdec_amd_wd.so VVR_SKIP_KERNELS=8175 timeout 300 python bench.py $A --host-threads 8 > $out/bench_nokernels_t8.json 2> $out/bench_nokernels_t8.err
+VVDEC_AMD_LIB=$PWD/vvdec_amd/libvvdec_amd_wd.so VVR_SKIP_KERNELS=8175 timeout 300 python bench.py --full $A --host-threads 8 > $out/bench_nokernels_t8.json 2> $out/bench_nokernels_t8.err
 for f in $out/bench_*.json; do python - "$f" <<'PY'
 import json,sys
 try:

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 A="--steps 6 --warmup 2 --verify 0 --no-cpu-baseline --streams 1 --host-threads 0 --repeats 1"
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_INST_ANY" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_ANY"; do
   tag=$(echo $set | tr ' ' '_' | cut -c1-40)
-  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $R/$out/ctr_$tag -o c -- python $R/bench.py $A > /dev/null 2> $R/$out/ctr_$tag.err) || echo "   (set '$set' failed)"
+  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $R/$out/ctr_$tag -o c -- python $R/bench.py --full $A > /dev/null 2> $R/$out/ctr_$tag.err) || echo "   (set '$set' failed)"
 done
 python - "$out" "$pat" <<'PY'
 import csv, glob, sys, collections, re

@@ -3,7 +3,7 @@
 out=gpurun_out/${1:-kalone}; mkdir -p $out
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof -o k -- python $R/bench.py --steps 16 --warmup 4 --verify 0 --no-cpu-baseline --streams 1 --host-threads 0 --repeats 1 > $R/$out/bench.json 2> $R/$out/err.txt)
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof -o k -- python $R/bench.py --full --steps 16 --warmup 4 --verify 0 --no-cpu-baseline --streams 1 --host-threads 0 --repeats 1 > $R/$out/bench.json 2> $R/$out/err.txt)
 python - "$out" <<'PY'
 import csv,glob,collections,sys
 f=glob.glob(sys.argv[1]+'/prof/**/*kernel_trace.csv',recursive=True)[0]

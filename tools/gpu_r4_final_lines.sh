@@ -1,9 +1,9 @@
 #!/bin/bash
 # developer helper: the bench lines of the final defaults (edge parameters and affine sub-block vectors derived on the device)
 out=gpurun_out/${1:-r4fin}; mkdir -p $out; export TMPDIR=/tmp
-timeout 400 python bench.py --steps 20 --warmup 5 > $out/bench_4k_steps20_warmup5.json 2> $out/bench_4k.err
-timeout 400 python bench.py --no-cpu-baseline > $out/bench_4k_steps64_warmup16.json 2> $out/bench_4k_64.err
-timeout 600 python bench.py --config 8k --steps 32 --warmup 8 --verify 1 --no-cpu-baseline > $out/bench_8k.json 2> $out/bench_8k.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $out/bench_4k_steps20_warmup5.json 2> $out/bench_4k.err
+timeout 400 python bench.py --full --no-cpu-baseline > $out/bench_4k_steps64_warmup16.json 2> $out/bench_4k_64.err
+timeout 600 python bench.py --full --config 8k --steps 32 --warmup 8 --verify 1 --no-cpu-baseline > $out/bench_8k.json 2> $out/bench_8k.err
 for f in $out/bench_4k_steps20_warmup5.json $out/bench_4k_steps64_warmup16.json $out/bench_8k.json; do python - "$f" <<'PY'
 import json,sys
 try:

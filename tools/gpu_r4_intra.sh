@@ -12,7 +12,7 @@ rm -f gpurun_out/intra_*poc*.bin
 grep -E "POC|blocks [0-9]+:|regular blocks|per unit|kernel span|alive" $out/btrace.txt
 echo "== intra probe (product build)"
 PROBE_PICTURES=3 timeout 300 python tools/intra_probe.py > $out/probe.txt 2>&1; cat $out/probe.txt
-if [ -n "$BENCH" ]; then timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench20.json 2> $out/bench20.err; python - $out/bench20.json <<'PY'
+if [ -n "$BENCH" ]; then timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench20.json 2> $out/bench20.err; python - $out/bench20.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); c=d['config']; r=d['roofline']
 print('value', d['value'], c.get('value_samples_fps'), 'dev', c['device_only_fps'], 'verified', c['verified_timed_pictures_vs_oracle'], 'dom', r['kernel'], r['frac'])

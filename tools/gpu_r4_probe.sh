@@ -11,4 +11,4 @@ rm -f gpurun_out/intra_*poc*.bin
 echo "== intra probe (product build)"
 PROBE_PICTURES=5 timeout 300 python tools/intra_probe.py > $out/probe.txt 2>&1; cat $out/probe.txt
 echo "== bench"
-timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench20.json 2> $out/bench20.err; tail -c 600 $out/bench20.json
+timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench20.json 2> $out/bench20.err; tail -c 600 $out/bench20.json

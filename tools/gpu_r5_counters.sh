@@ -9,8 +9,8 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 A="--config $cfg --steps 8 --warmup 4 --verify 0 --no-cpu-baseline --streams 1 --host-threads 0 --repeats 1"
 SET="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $R/$out/ctr_$cfg -o c -- python $R/bench.py $A > $R/$out/bench_under_pmc_$cfg.json 2> $R/$out/ctr_$cfg.err) || echo "   (counter pass failed)"
-python - "$out" "$cfg" "rocprofv3 --kernel-trace --pmc $SET -- python bench.py $A" <<'PY'
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $R/$out/ctr_$cfg -o c -- python $R/bench.py --full $A > $R/$out/bench_under_pmc_$cfg.json 2> $R/$out/ctr_$cfg.err) || echo "   (counter pass failed)"
+python - "$out" "$cfg" "rocprofv3 --kernel-trace --pmc $SET -- python bench.py --full $A" <<'PY'
 import csv, glob, sys, collections, json
 out, cfg, cmd = sys.argv[1], sys.argv[2], sys.argv[3]
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); disp = collections.defaultdict(set)

@@ -6,7 +6,7 @@ for k in "64 16" "32 8"; do set -- $k
   for l in r4 r5 cur; do
     lib=vvdec_amd/libvvdec_amd_$l.so; [ $l = cur ] && lib=vvdec_amd/libvvdec_amd.so
     [ -f $lib ] || continue
-    VVDEC_AMD_LIB=$PWD/$lib timeout 300 python bench.py --config allintra --steps $1 --warmup $2 --repeats 3 --verify 0 --no-cpu-baseline --no-other-configs > $out/allintra_${l}_k$1.json 2> $out/allintra_${l}_k$1.err
+    VVDEC_AMD_LIB=$PWD/$lib timeout 300 python bench.py --full --config allintra --steps $1 --warmup $2 --repeats 3 --verify 0 --no-cpu-baseline --no-other-configs > $out/allintra_${l}_k$1.json 2> $out/allintra_${l}_k$1.err
     python - $out/allintra_${l}_k$1.json $l $1 <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ for tag in "" $2; do
   lib=$R/vvdec_amd/libvvdec_amd${tag:+_$tag}.so; name=${tag:-product}
   echo "== $name"
   VVDEC_AMD_LIB=$lib bash tools/gpu_kstat_alone.sh $(basename $out)/alone_$name 2>&1 | grep -i "${3:-k_}" | head -${4:-6}
-  VVDEC_AMD_LIB=$lib timeout 300 python bench.py --config 4k --steps 64 --warmup 16 --verify 0 --no-cpu-baseline --no-other-configs --repeats 3 > $out/bench_k64_$name.json 2>/dev/null
+  VVDEC_AMD_LIB=$lib timeout 300 python bench.py --full --config 4k --steps 64 --warmup 16 --verify 0 --no-cpu-baseline --no-other-configs --repeats 3 > $out/bench_k64_$name.json 2>/dev/null
   python - $out/bench_k64_$name.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c=d["config"]

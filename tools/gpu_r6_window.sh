@@ -5,7 +5,7 @@ out=gpurun_out/${1:-r6win}; mkdir -p $out
 export TMPDIR=/tmp
 bash tools/gpu_r4_timeline.sh $(basename $out)/tl
 bash tools/gpu_r6_sweep.sh $(basename $out)/sweep
-timeout 300 python bench.py --config 4k --steps 64 --warmup 16 --verify 0 --no-cpu-baseline --no-other-configs --repeats 3 > $out/bench_k64.json 2>/dev/null
+timeout 300 python bench.py --full --config 4k --steps 64 --warmup 16 --verify 0 --no-cpu-baseline --no-other-configs --repeats 3 > $out/bench_k64.json 2>/dev/null
 python - $out/bench_k64.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c=d["config"]
