@@ -478,6 +478,14 @@ VVR_API int          vvr_read_plane(vvr_context* ctx, int slot, int comp, uint16
  * bytes_per_sample 2 = 16-bit samples, 1 = the low byte of every sample (8-bit streams; "only narrowing conversions", :853).  Crop and
  * narrowing run on the device: exactly w * h * bytes_per_sample bytes cross PCIe.  Waits for all work on the slot. */
 VVR_API int          vvr_read_output(vvr_context* ctx, int slot, int comp, int x, int y, int w, int h, int bytes_per_sample, void* dst, size_t dst_stride_bytes);
+/* the same window rescaled to out_w x out_h samples of the component, exactly as vvdec::rescalePlane does it (vvdecimpl.cpp:1620 ->
+ * sampleRateConvCore, Buffer.cpp:235-318: the regular 8-tap / 4-tap DCTIF, scale factors from the window's and the output's sizes, source taps
+ * clamped to the window), then stored like vvr_read_output.  collocated: bit 0 horizontal, bit 1 vertical chroma sample position
+ * (horCollocatedChromaFlag / verCollocatedChromaFlag; 4:2:0 default of vvdecapp: 1); ignored for luma.  Output sides 1..8192, each between 1/8
+ * and 8 times the window's; else VVR_ERR_PARAMETER.  The rescaling runs on the device: exactly out_w * out_h * bytes_per_sample bytes cross PCIe.
+ * Waits for all work on the slot. */
+VVR_API int          vvr_read_output_scaled(vvr_context* ctx, int slot, int comp, int x, int y, int w, int h, int out_w, int out_h,
+                                            int collocated, int bytes_per_sample, void* dst, size_t dst_stride_bytes);
 /* decoded picture hash of a slot, as the decoded-picture-hash SEI defines it and the reference checks it (calcMD5 / calcCRC / calcChecksum,
  * PicYuvMD5.cpp:99-221): one digest per component over the whole plane in raster order, samples as 1 byte (bit depth 8) or 2 bytes little
  * endian.  digest receives num_components x digest_len bytes (MD5 16, CRC 2, checksum 4), *digest_len the length of one.  CRC and checksum

@@ -68,6 +68,8 @@ def lib():
         L.vvr_picture_hash.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.vvr_read_output.restype = C.c_int
         L.vvr_read_output.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t]
+        L.vvr_read_output_scaled.restype = C.c_int
+        L.vvr_read_output_scaled.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t]
         L.vvr_read_dmvr.restype = C.c_int
         L.vvr_read_dmvr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.vvr_read_col_motion.restype = C.c_int
@@ -90,7 +92,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture"]
@@ -248,14 +250,21 @@ class Reconstructor:
         self._check(self.L.vvr_picture_hash(self.ctx, slot, method, buf, C.byref(n)))
         return [bytes(buf[k * n.value:(k + 1) * n.value]) for k in range(3 if self.chroma_format else 1)]
 
-    def read_output(self, slot, window=None, bytes_per_sample=2):
-        """the picture as the application gets it: conformance window (x, y, w, h in luma samples, even) applied, 8- or 16-bit samples"""
+    def read_output(self, slot, window=None, bytes_per_sample=2, size=None, collocated=(True, False)):
+        """the picture as the application gets it: conformance window (x, y, w, h in luma samples, even) applied, 8- or 16-bit samples.
+        size: (width, height) in luma samples to rescale the window to on the device, as vvdec::rescalePlane does (chroma planes get size >> 1,
+        vvdecapp's width / chromaSubX); collocated: horizontal, vertical chroma sample position (vvdecapp's 4:2:0 default: True, False)"""
         x, y, w, h = window or (0, 0, self.width, self.height)
         out = []
         for c in range(3 if self.chroma_format else 1):
             s = 1 if c else 0
-            a = np.zeros((h >> s, w >> s), np.uint8 if bytes_per_sample == 1 else np.uint16)
-            self._check(self.L.vvr_read_output(self.ctx, slot, c, x >> s, y >> s, w >> s, h >> s, bytes_per_sample, a.ctypes.data, a.strides[0]))
+            ow, oh = (w, h) if size is None else size
+            a = np.zeros((oh >> s, ow >> s), np.uint8 if bytes_per_sample == 1 else np.uint16)
+            if size is None:
+                self._check(self.L.vvr_read_output(self.ctx, slot, c, x >> s, y >> s, w >> s, h >> s, bytes_per_sample, a.ctypes.data, a.strides[0]))
+            else:
+                self._check(self.L.vvr_read_output_scaled(self.ctx, slot, c, x >> s, y >> s, w >> s, h >> s, ow >> s, oh >> s,
+                                                          int(bool(collocated[0])) | int(bool(collocated[1])) << 1, bytes_per_sample, a.ctypes.data, a.strides[0]))
             out.append(a)
         return out
 

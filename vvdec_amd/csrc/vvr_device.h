@@ -143,6 +143,15 @@ void launch_copy_planes( hipStream_t s, DevPlanes src, DevPlanes dst );
 void launch_copy_bytes( hipStream_t s, const void* src, void* dst, size_t bytes );
 void launch_output_window( hipStream_t s, const pel_t* src, int stride, int w, int h, int bytesPerSample, void* dst );      // window rows packed back to back, 1 or 2 bytes per sample
 void launch_plane_hash_rows( hipStream_t s, const pel_t* plane, int stride, int w, int h, int two, int crcMode, uint32_t* out );   // per row: checksum share / CRC piece
+// rescaled output (sampleRateConvCore, Buffer.cpp:235-318): a window of w x h samples resampled to outW x outH, packed like launch_output_window.
+// per direction refPos( i ) = ( i * step + add ) >> shift, step = scale << cs (vvr_output.inc, rescale_axis); luma: the 8-tap DCTIF, else the 4-tap one
+struct RescaleParams
+{
+  const pel_t* src; int stride, w, h, outW, outH;
+  int stepX, stepY, addX, addY, shiftX, shiftY;
+  int luma, maxVal, bytesPerSample;
+};
+void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst );
 void launch_mc_affine( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );
 void launch_mc_rpr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );      // tiles of CUs with a scaled reference picture
 void launch_mc_dmvr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems, int32_t* dmvrOut );

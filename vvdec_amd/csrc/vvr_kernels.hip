@@ -4713,6 +4713,85 @@ void launch_output_window( hipStream_t s, const pel_t* src, int stride, int w, i
   hipLaunchKernelGGL( k_output_window, dim3( ( w + 255 ) / 256, h ), dim3( 256 ), 0, s, src, stride, w, h, bytesPerSample, (uint8_t*) dst );
 }
 
+// k_rescale — rescaled output, sampleRateConvCore (Buffer.cpp:235-318) as vvdec::rescalePlane calls it (vvdecimpl.cpp:1620): the regular DCTIF
+// (8 taps, 16 phases for luma; 4 taps, 32 phases for chroma) whatever the ratio, the horizontal sums kept unnormalised, ( sum + 2048 ) >> 12 and
+// the clip after the vertical pass, source taps clamped to the window.  One workgroup per tile of 64 output columns x tileH output rows: each
+// lane owns a column (phase, coefficients and tap offsets computed once; the filter table is staged in LDS).  Horizontal pass: the four wavefronts take the tile's source rows in
+// turn; a wavefront stages the row's segment the tile reads (clamped to the window, coalesced loads) in an LDS row of its own and filters from
+// there, the sums go to LDS.  Vertical pass: one output row per wavefront at a time (the row's phase is uniform), taps read from the sums.  The
+// launcher sizes tileH so that the source rows of a tile fit RS_ROWS rows of sums at every accepted ratio (8x down: 16 output rows).
+#define RS_TW   64
+#define RS_ROWS 128      // LDS budget: 128 rows x 64 int32 sums = 32 KiB per workgroup
+#define RS_SEG  576      // source samples a row segment of 64 output columns can span: 63 * 8 + 1 + 8 at 8x down
+template<int TAPS>
+__global__ __launch_bounds__( 256 ) void k_rescale( RescaleParams p, int tileH, int rowsCap, uint8_t* __restrict__ dst )
+{
+  extern __shared__ int rs_sum[];      // [rowsCap][RS_TW]
+  __shared__ pel_t rs_seg[4][RS_SEG];
+  __shared__ int16_t rs_flt[128];      // the filter table (16 x 8 or 32 x 4): the vertical pass reads a row's coefficients from here, not through a global load per row
+  constexpr int fracShift = TAPS == 8 ? 4 : 5, fracMask = ( 1 << fracShift ) - 1, half = TAPS / 2 - 1;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * RS_TW, iOut = i0 + lane, iLast = min( i0 + RS_TW, p.outW ) - 1, i = min( iOut, iLast );
+  const int j0 = blockIdx.y * tileH, j1 = min( j0 + tileH, p.outH ) - 1;
+  // the source rows the tile's vertical taps reach (integer positions grow with j)
+  const int rowLo = max( 0, ( ( j0 * p.stepY + p.addY ) >> p.shiftY >> fracShift ) - half );
+  const int rowHi = min( min( p.h - 1, ( ( j1 * p.stepY + p.addY ) >> p.shiftY >> fracShift ) + TAPS - 1 - half ), rowLo + rowsCap - 1 );
+  if( threadIdx.x < 128 ) rs_flt[threadIdx.x] = TAPS == 8 ? ( &d_luma_filter[0][0] )[threadIdx.x] : ( &d_chroma_filter[0][0] )[threadIdx.x];
+  __syncthreads();
+  // the source columns the tile's horizontal taps reach: [xLo, xLo + segLen), staged clamped to the window
+  const int xLo = ( ( i0 * p.stepX + p.addX ) >> p.shiftX >> fracShift ) - half;
+  const int segLen = min( ( ( iLast * p.stepX + p.addX ) >> p.shiftX >> fracShift ) + TAPS - half - xLo, RS_SEG );
+  // the lane's column: phase, coefficients, tap offsets into the segment, once
+  const int refX = ( i * p.stepX + p.addX ) >> p.shiftX, tap0 = ( refX >> fracShift ) - half - xLo;
+  const int16_t* fh = rs_flt + ( refX & fracMask ) * TAPS;
+  int ch[TAPS], xo[TAPS];
+#pragma unroll
+  for( int k = 0; k < TAPS; k++ ) { ch[k] = fh[k]; xo[k] = min( tap0 + k, RS_SEG - 1 ); }
+  pel_t* seg = rs_seg[wave];
+  for( int r = rowLo + wave; r <= rowHi; r += 4 )
+  {
+    const pel_t* __restrict__ row = p.src + (size_t) r * p.stride;
+    for( int t = lane; t < segLen; t += 64 ) seg[t] = row[clip3( 0, p.w - 1, xLo + t )];
+    __builtin_amdgcn_wave_barrier();
+    int sum = 0;
+#pragma unroll
+    for( int k = 0; k < TAPS; k++ ) sum += ch[k] * seg[xo[k]];
+    rs_sum[( r - rowLo ) * RS_TW + lane] = sum;
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+  for( int j = j0 + wave; j <= j1; j += 4 )
+  {
+    const int refY = ( j * p.stepY + p.addY ) >> p.shiftY, intY = refY >> fracShift;
+    const int16_t* fv = rs_flt + ( refY & fracMask ) * TAPS;
+    int sum = 0;
+#pragma unroll
+    for( int k = 0; k < TAPS; k++ ) sum += fv[k] * rs_sum[( clip3( rowLo, rowHi, intY + k - half ) - rowLo ) * RS_TW + lane];     // (= the clamp to [0, h - 1])
+    const int v = clip3( 0, p.maxVal, ( sum + 2048 ) >> 12 );
+    if( iOut < p.outW )
+    {
+      if( p.bytesPerSample == 2 ) ( (uint16_t*) dst )[(size_t) j * p.outW + iOut] = (uint16_t) v;
+      else dst[(size_t) j * p.outW + iOut] = (uint8_t) v;
+    }
+  }
+}
+void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst )
+{
+  const int taps = p.luma ? 8 : 4, fracShift = p.luma ? 4 : 5;
+  // source rows of a tile of t output rows <= ceil( ( t - 1 ) * stepY / 2^( shiftY + fracShift ) ) + taps (stepY / 2^( shiftY + fracShift ): source rows per output row)
+  auto rows = [&]( int t ) { const int64_t den = (int64_t) 1 << ( p.shiftY + fracShift ); return (int) ( ( (int64_t) ( t - 1 ) * p.stepY + den - 1 ) / den ) + taps; };
+  int tileH = 64;
+  while( tileH > 1 && rows( tileH ) > RS_ROWS ) tileH--;
+  // (a small plane - the chroma of 1080p to 4K - in shorter tiles, so that every compute unit gets several workgroups)
+  const int tilesX = ( p.outW + RS_TW - 1 ) / RS_TW;
+  while( tileH > 16 && (int64_t) tilesX * ( ( p.outH + tileH - 1 ) / tileH ) < 1000 ) tileH >>= 1;
+  const int rowsCap = std::min( rows( tileH ), p.h );
+  const dim3 grid( tilesX, ( p.outH + tileH - 1 ) / tileH );
+  const size_t lds = (size_t) rowsCap * RS_TW * sizeof( int );
+  if( p.luma ) hipLaunchKernelGGL( k_rescale<8>, grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst );
+  else         hipLaunchKernelGGL( k_rescale<4>, grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst );
+}
+
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in
 __device__ __forceinline__ uint32_t crc_mul( uint32_t a, uint32_t b )
 {

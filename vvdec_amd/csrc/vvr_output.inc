@@ -59,7 +59,53 @@ int ensureOutputScratch( vvr_context* c, size_t devBytes, size_t hostBytes )
   if( hostBytes > c->outHostCap ) { if( c->outHost ) hipHostFree( c->outHost ); c->outHost = nullptr; c->outHostCap = 0; HIPCHK( c, hipHostMalloc( &c->outHost, hostBytes, hipHostMallocDefault ) ); c->outHostCap = hostBytes; }
   return VVR_OK;
 }
+
+// the positions of sampleRateConvCore (Buffer.cpp:249-255) for one direction: scale factor from the plane's own sizes ((src << 14) + dst / 2) / dst
+// (vvdecimpl.cpp:1633), refPos = ( ( i << cs ) * scale + add ) >> shift, integer part and phase from refPos.  With sides <= 8192 and src / dst in
+// [1/8, 8]: scale <= 8 << 14, ( 8191 << 1 ) * scale + add <= 2 147 279 360 < 2^31 - 1
+void rescale_axis( int src, int dst, int cs, int collocated, int fracShift, int& scale, int& add, int& shift )
+{
+  scale = ( ( src << 14 ) + ( dst >> 1 ) ) / dst;
+  shift = 14 - fracShift + cs;
+  add = ( 1 << ( shift - 1 ) ) + ( ( ( 1 - collocated ) * 8 * ( scale - ( 1 << 14 ) ) + ( 1 << ( 2 + cs ) ) ) >> ( 3 + cs ) );
+}
 }   // namespace
+
+#if !defined(__HIPCC__)
+// Host builds of this file (the CPU test harness compiles the host code against a stand-in runtime): the launcher as a plain loop restating
+// sampleRateConvCore (Buffer.cpp:235-318), so that the host half of vvr_read_output_scaled is checked without a GPU.  The product is always compiled
+// by hipcc and takes k_rescale (vvr_kernels.hip).
+namespace rescale_host_tbl {
+#include "../../tables/vvc_tables.inc"
+}
+void launch_rescale( hipStream_t, const RescaleParams& p, void* dst )
+{
+  const int taps = p.luma ? 8 : 4, fracShift = p.luma ? 4 : 5, fracMask = ( 1 << fracShift ) - 1;
+  auto coef = [&]( int frac, int k ) { return (int) ( p.luma ? rescale_host_tbl::vvc_luma_filter[frac][k] : rescale_host_tbl::vvc_chroma_filter[frac][k] ); };
+  std::vector<int> tmp( (size_t) p.h * p.outW );
+  for( int i = 0; i < p.outW; i++ )
+  {
+    const int refPos = ( i * p.stepX + p.addX ) >> p.shiftX, integer = refPos >> fracShift, frac = refPos & fracMask;
+    for( int j = 0; j < p.h; j++ )
+    {
+      int sum = 0;
+      for( int k = 0; k < taps; k++ ) sum += coef( frac, k ) * p.src[(size_t) j * p.stride + std::min( std::max( 0, integer + k - taps / 2 + 1 ), p.w - 1 )];
+      tmp[(size_t) j * p.outW + i] = sum;
+    }
+  }
+  for( int j = 0; j < p.outH; j++ )
+  {
+    const int refPos = ( j * p.stepY + p.addY ) >> p.shiftY, integer = refPos >> fracShift, frac = refPos & fracMask;
+    for( int i = 0; i < p.outW; i++ )
+    {
+      int sum = 0;
+      for( int k = 0; k < taps; k++ ) sum += coef( frac, k ) * tmp[(size_t) std::min( std::max( 0, integer + k - taps / 2 + 1 ), p.h - 1 ) * p.outW + i];
+      const int v = std::min( std::max( 0, ( sum + 2048 ) >> 12 ), p.maxVal );
+      if( p.bytesPerSample == 2 ) ( (uint16_t*) dst )[(size_t) j * p.outW + i] = (uint16_t) v; else ( (uint8_t*) dst )[(size_t) j * p.outW + i] = (uint8_t) v;
+    }
+  }
+}
+#endif
 
 extern "C" {
 
@@ -82,6 +128,45 @@ VVR_API int vvr_read_output( vvr_context* c, int slot, int comp, int x, int y, i
   HIPCHK( c, hipMemcpyAsync( c->outHost, c->outDev, rowBytes * h, hipMemcpyDeviceToHost, s ) );
   HIPCHK( c, hipStreamSynchronize( s ) );
   for( int r = 0; r < h; r++ ) memcpy( (uint8_t*) dst + (size_t) r * dstStrideBytes, (const uint8_t*) c->outHost + (size_t) r * rowBytes, rowBytes );
+  return VVR_OK;
+}
+
+VVR_API int vvr_read_output_scaled( vvr_context* c, int slot, int comp, int x, int y, int w, int h, int outW, int outH, int collocated, int bytesPerSample, void* dst, size_t dstStrideBytes )
+{
+  if( !c || slot < 0 || slot >= (int) c->slots.size() || comp < 0 || comp > 2 || !c->slots[slot].p[comp] || !dst ) return VVR_ERR_PARAMETER;
+  const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot: an RPR picture is smaller than the slot)
+  if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[comp] || y + h > d.h[comp] || ( bytesPerSample != 1 && bytesPerSample != 2 ) )
+  { c->setError( "vvr_read_output_scaled: window outside the picture's plane or bad sample size" ); return VVR_ERR_PARAMETER; }
+  if( outW <= 0 || outH <= 0 || outW > 8192 || outH > 8192 || w > 8 * outW || h > 8 * outH || outW > 8 * w || outH > 8 * h )
+  { c->setError( "vvr_read_output_scaled: output sides must be 1..8192 and within 1/8 .. 8 times the window's" ); return VVR_ERR_PARAMETER; }
+  if( dstStrideBytes < (size_t) outW * bytesPerSample ) { c->setError( "vvr_read_output_scaled: stride below the output's row" ); return VVR_ERR_PARAMETER; }
+  if( bytesPerSample == 1 && c->cfg.bit_depth > 8 ) { c->setError( "vvr_read_output_scaled: 8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" ); return VVR_ERR_PARAMETER; }
+  hipSetDevice( c->device );
+  int rc = vvr_sync( c ); if( rc != VVR_OK ) return rc;
+  // packed on the device, one copy into pinned memory, rows at the caller's stride from there (as vvr_read_output)
+  const size_t rowBytes = (size_t) outW * bytesPerSample, bytes = alignUp( rowBytes * outH, 256 );
+  if( ( rc = ensureOutputScratch( c, bytes, bytes ) ) != VVR_OK ) return rc;
+  hipStream_t s = c->streams[0];
+  const pel_t* src = d.p[comp] + (size_t) y * d.stride[comp] + x;
+  if( w == outW && h == outH )
+    launch_output_window( s, src, d.stride[comp], w, h, bytesPerSample, c->outDev );       // the reference copies (Buffer.cpp:243)
+  else
+  {
+    // the component's subsampling: 4:2:0 chroma is half size both ways; luma is always collocated (vvdecimpl.cpp:1651)
+    const bool luma = comp == 0;
+    const int cs = luma ? 0 : 1, colX = luma ? 1 : collocated & 1, colY = luma ? 1 : ( collocated >> 1 ) & 1, fracShift = luma ? 4 : 5;
+    RescaleParams p;
+    p.src = src; p.stride = d.stride[comp]; p.w = w; p.h = h; p.outW = outW; p.outH = outH;
+    p.luma = luma; p.maxVal = ( 1 << c->cfg.bit_depth ) - 1; p.bytesPerSample = bytesPerSample;
+    int scale;
+    rescale_axis( w, outW, cs, colX, fracShift, scale, p.addX, p.shiftX ); p.stepX = scale << cs;
+    rescale_axis( h, outH, cs, colY, fracShift, scale, p.addY, p.shiftY ); p.stepY = scale << cs;
+    launch_rescale( s, p, c->outDev );
+  }
+  HIPCHK( c, hipGetLastError() );
+  HIPCHK( c, hipMemcpyAsync( c->outHost, c->outDev, rowBytes * outH, hipMemcpyDeviceToHost, s ) );
+  HIPCHK( c, hipStreamSynchronize( s ) );
+  for( int r = 0; r < outH; r++ ) memcpy( (uint8_t*) dst + (size_t) r * dstStrideBytes, (const uint8_t*) c->outHost + (size_t) r * rowBytes, rowBytes );
   return VVR_OK;
 }
 
