@@ -486,6 +486,34 @@ VVR_API int          vvr_read_output(vvr_context* ctx, int slot, int comp, int x
  * Waits for all work on the slot. */
 VVR_API int          vvr_read_output_scaled(vvr_context* ctx, int slot, int comp, int x, int y, int w, int h, int out_w, int out_h,
                                             int collocated, int bytes_per_sample, void* dst, size_t dst_stride_bytes);
+
+/* Film grain synthesis at the output (the VFGS "hardware model" of the reference's FilmGrain, FilmGrainImpl.cpp:126-324, as
+ * VVDecImpl::xAddGrain applies it, vvdecimpl.cpp:897-956).  The bank is the model's state after FilmGrain::updateFGC, i.e. what the
+ * "firmware" derives from an FGC SEI; parsing the SEI, cancel, persistence and the reset at a CLVS start stay with the caller. */
+typedef struct vvr_film_grain_bank {
+  uint32_t struct_size;                /* sizeof( vvr_film_grain_bank )                                                  */
+  uint8_t  comp_present[3];            /* comp_model_present_flag[c]: absent components are copied unchanged             */
+  uint8_t  shift;                      /* log2_scale_factor - ( model_id ? 1 : 0 ), 2..7                                 */
+  uint8_t  scale_lut[3][256];          /* FilmGrainImpl::sLUT                                                            */
+  uint8_t  pattern_lut[3][256];        /* FilmGrainImpl::pLUT (pattern index << 4, < 0x80)                               */
+  int8_t   pattern[2][8][64][64];      /* [luma, chroma][index][row][col]; 4:2:0 chroma uses rows, cols < 32             */
+} vvr_film_grain_bank;
+/* the context's bank (copied; NULL: none).  A bank with a struct_size other than sizeof( vvr_film_grain_bank ), a shift outside 2..7 or a
+ * pattern_lut entry >= 0x80 is refused (VVR_ERR_PARAMETER) and the bank set before stays.  Does not touch the seed chain. */
+VVR_API int          vvr_set_film_grain(vvr_context* ctx, const vvr_film_grain_bank* bank);
+/* FilmGrain::set_seed: the state of the seed chain (a context starts at 0xdeadbeef) */
+VVR_API int          vvr_set_film_grain_seed(vvr_context* ctx, uint32_t seed);
+/* one frame, all components: the window (x, y, w, h in luma samples of the picture in the slot; even in 4:2:0) with the bank's grain added,
+ * stored like vvr_read_output into dst[c] at dst_stride_bytes[c] (dst[1], dst[2] unused in 4:0:0).  Per 16x16 block of the window (8x8 in
+ * 4:2:0 chroma) a random word from the seed chain, which advances exactly as FilmGrain::prepareBlockSeeds( w, h ) does, and only when the call
+ * succeeds; the output of a present component is clip( I + round( scale * grain, shift + 6 - ( bit_depth - 8 ) ), 0, 255 << ( bit_depth - 8 ) )
+ * (so 1020 is the 10-bit ceiling).  Refused (VVR_ERR_PARAMETER): no bank, bit depth other than 8 or 10, w <= 128 (the reference's limits),
+ * a window outside the picture or odd in 4:2:0, 1-byte output of a context with more than 8 bits.
+ * Where the reference reads past the frame (the deblocking of the last block edge when the luma width is 1 mod 16 or the 4:2:0 chroma width
+ * 1 mod 8: it takes the pattern index from the buffer's padding), the sample beyond the frame takes the pattern index of the frame's last
+ * sample in the row.  The synthesis runs on the device in the same pass that crops and packs the window.  Waits for all work on the slot. */
+VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, int y, int w, int h, int bytes_per_sample,
+                                           void* const dst[3], const size_t dst_stride_bytes[3]);
 /* decoded picture hash of a slot, as the decoded-picture-hash SEI defines it and the reference checks it (calcMD5 / calcCRC / calcChecksum,
  * PicYuvMD5.cpp:99-221): one digest per component over the whole plane in raster order, samples as 1 byte (bit depth 8) or 2 bytes little
  * endian.  digest receives num_components x digest_len bytes (MD5 16, CRC 2, checksum 4), *digest_len the length of one.  CRC and checksum

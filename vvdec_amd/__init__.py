@@ -70,6 +70,12 @@ def lib():
         L.vvr_read_output.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t]
         L.vvr_read_output_scaled.restype = C.c_int
         L.vvr_read_output_scaled.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t]
+        L.vvr_set_film_grain.restype = C.c_int
+        L.vvr_set_film_grain.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_set_film_grain_seed.restype = C.c_int
+        L.vvr_set_film_grain_seed.argtypes = [C.c_void_p, C.c_uint32]
+        L.vvr_read_output_grain.restype = C.c_int
+        L.vvr_read_output_grain.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.vvr_read_dmvr.restype = C.c_int
         L.vvr_read_dmvr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.vvr_read_col_motion.restype = C.c_int
@@ -92,7 +98,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture"]
@@ -250,11 +256,35 @@ class Reconstructor:
         self._check(self.L.vvr_picture_hash(self.ctx, slot, method, buf, C.byref(n)))
         return [bytes(buf[k * n.value:(k + 1) * n.value]) for k in range(3 if self.chroma_format else 1)]
 
-    def read_output(self, slot, window=None, bytes_per_sample=2, size=None, collocated=(True, False)):
+    def set_film_grain(self, bank):
+        """the film grain bank read_output(grain=True) applies: None, an abi.FilmGrainBank, or a dict of its fields as arrays (comp_present,
+        shift, scale_lut, pattern_lut, pattern; see abi.film_grain_bank).  Does not touch the seed chain."""
+        if bank is None:
+            self._check(self.L.vvr_set_film_grain(self.ctx, None))
+            return
+        if not isinstance(bank, abi.FilmGrainBank):
+            bank = abi.film_grain_bank(**bank)
+        self._check(self.L.vvr_set_film_grain(self.ctx, C.addressof(bank)))
+
+    def set_film_grain_seed(self, seed):
+        """the state of the film grain's seed chain (FilmGrain::set_seed; a context starts at 0xdeadbeef)"""
+        self._check(self.L.vvr_set_film_grain_seed(self.ctx, seed & 0xffffffff))
+
+    def read_output(self, slot, window=None, bytes_per_sample=2, size=None, collocated=(True, False), grain=False):
         """the picture as the application gets it: conformance window (x, y, w, h in luma samples, even) applied, 8- or 16-bit samples.
         size: (width, height) in luma samples to rescale the window to on the device, as vvdec::rescalePlane does (chroma planes get size >> 1,
-        vvdecapp's width / chromaSubX); collocated: horizontal, vertical chroma sample position (vvdecapp's 4:2:0 default: True, False)"""
+        vvdecapp's width / chromaSubX); collocated: horizontal, vertical chroma sample position (vvdecapp's 4:2:0 default: True, False).
+        grain: film grain of the bank set with set_film_grain added on the device, one frame of the seed chain (vvr_read_output_grain)"""
         x, y, w, h = window or (0, 0, self.width, self.height)
+        if grain:
+            if size is not None:
+                raise ValueError("read_output: grain and size together are not supported (the reference grains before it rescales)")
+            nc = 3 if self.chroma_format else 1
+            out = [np.zeros((h >> (1 if c else 0), w >> (1 if c else 0)), np.uint8 if bytes_per_sample == 1 else np.uint16) for c in range(nc)]
+            ptrs = (C.c_void_p * 3)(*[out[c].ctypes.data if c < nc else None for c in range(3)])
+            strides = (C.c_size_t * 3)(*[out[c].strides[0] if c < nc else 0 for c in range(3)])
+            self._check(self.L.vvr_read_output_grain(self.ctx, slot, x, y, w, h, bytes_per_sample, ptrs, strides))
+            return out
         out = []
         for c in range(3 if self.chroma_format else 1):
             s = 1 if c else 0

@@ -140,5 +140,25 @@ class Config(C.Structure):
                 ("read_buffers", u8), ("pad", u8 * 7), ("ext_planes", C.c_void_p)]
 
 
+class FilmGrainBank(C.Structure):
+    """vvr_film_grain_bank: the film grain model's state after the reference's FilmGrain::updateFGC (vvr.h)"""
+    _fields_ = [("struct_size", u32), ("comp_present", u8 * 3), ("shift", u8), ("scale_lut", (u8 * 256) * 3), ("pattern_lut", (u8 * 256) * 3),
+                ("pattern", (((C.c_int8 * 64) * 64) * 8) * 2)]
+
+
+def film_grain_bank(comp_present, shift, scale_lut, pattern_lut, pattern):
+    """a FilmGrainBank from its fields as arrays: comp_present (3,), shift, scale_lut and pattern_lut (3, 256) uint8, pattern (2, 8, 64, 64) int8"""
+    import numpy as np
+    b = FilmGrainBank()
+    b.struct_size = C.sizeof(FilmGrainBank)
+    b.shift = int(shift)
+    for name, arr, dt in (("comp_present", comp_present, np.uint8), ("scale_lut", scale_lut, np.uint8), ("pattern_lut", pattern_lut, np.uint8), ("pattern", pattern, np.int8)):
+        field = getattr(b, name)
+        a = np.ascontiguousarray(arr, dtype=dt)
+        assert a.nbytes == C.sizeof(field), name
+        C.memmove(C.addressof(field), a.ctypes.data, a.nbytes)
+    return b
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]

@@ -165,6 +165,9 @@ struct vvr_context {
   hipStream_t outStream = nullptr;                 // device-to-host copies of vvr_read_picture
   char*      prepStage = nullptr; size_t prepStageCap = 0;      // pinned staging of vvr_prepare
   std::vector<void*> stagePool;                    // pinned staging buffers of vvr_read_picture (one picture each), handed out under `mu`
+  // film grain at the output (vvr_set_film_grain): the bank, its device copy (uploaded on the stream of the first grain read after a change) and
+  // the seed chain (FilmGrain::m_line_rnd)
+  std::unique_ptr<vvr_film_grain_bank> grainBank; void* grainBankDev = nullptr; bool grainBankStale = false; uint32_t grainSeed = 0xdeadbeefu;
   // ---- job pipeline (everything below is guarded by mu)
   std::mutex mu, commitMu;              // commitMu: one committing thread at a time (it takes mu only around its bookkeeping)
   std::condition_variable cv;
@@ -1120,6 +1123,7 @@ VVR_API void vvr_destroy( vvr_context* c )
   if( c->planeMemOwned && c->planeMem ) hipFree( c->planeMem );
   if( c->scratchMem ) hipFree( c->scratchMem );
   if( c->outDev ) hipFree( c->outDev );
+  if( c->grainBankDev ) hipFree( c->grainBankDev );
   if( c->outHost ) hipHostFree( c->outHost );
   for( void* p : c->stagePool ) hipHostFree( p );
   if( c->prepStage ) hipHostFree( c->prepStage );

@@ -152,6 +152,16 @@ struct RescaleParams
   int luma, maxVal, bytesPerSample;
 };
 void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst );
+// film grain synthesis at the output (FilmGrainImpl::add_grain_block, FilmGrainImpl.cpp:126-324) over a window of every component, packed like
+// launch_output_window into dst + dstOff[c].  words: one random word per 16x16 luma block of the window, nbx per band (vvr_output.inc, grain_words);
+// bank: the device copy of the context's vvr_film_grain_bank
+struct FilmGrainParams
+{
+  const pel_t* src[3]; int stride[3], w[3], h[3]; size_t dstOff[3];
+  const vvr_film_grain_bank* bank; const uint32_t* words; int nbx;
+  int numComp, bs, scaleShift, bytesPerSample;
+};
+void launch_film_grain( hipStream_t s, const FilmGrainParams& p, void* dst );
 void launch_mc_affine( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );
 void launch_mc_rpr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );      // tiles of CUs with a scaled reference picture
 void launch_mc_dmvr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems, int32_t* dmvrOut );

@@ -4792,6 +4792,105 @@ void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst )
   else         hipLaunchKernelGGL( k_rescale<4>, grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst );
 }
 
+// k_film_grain — film grain synthesis at the output, the VFGS hardware model of the reference (FilmGrainImpl::add_grain_block ->
+// make_grain_pattern + scale_and_output, FilmGrainImpl.cpp:126-324, line by line as FilmGrain::add_grain_line drives it).  Every sample depends
+// only on its own intensity, on its 16x16 block's random word (8x8 in 4:2:0 chroma; the word of the block above for the overlap rows) and, at a
+// block edge, on the pre-deblock grain of the neighbour across it.  One lane per four consecutive samples of a row (a lane never straddles a
+// block: blocks are 16 or 8 wide), four rows per workgroup of 256, the tiles of all components in one grid.  A lane at a block edge recomputes
+// the neighbour's grain from the neighbour's intensity and word, so lanes exchange nothing.  The bank (66 KB) is read through the caches, not
+// staged in LDS: a copy per workgroup would move more bytes than the frame.
+struct FgTiles { int tilesX[3], first[3]; };
+struct FgOff { int neg, ox, oy; };
+// get_offset_y / get_offset_u / get_offset_v (FilmGrainImpl.cpp:85-124); chroma offsets are those of 4:2:0 (4 / csubx = 4 / csuby = 2)
+__device__ __forceinline__ FgOff fg_offset( uint32_t v, int c )
+{
+  FgOff o;
+  if( c == 0 )      { o.neg = v >> 31;        o.ox = ( ( ( v & 0x3ff ) * 13 ) >> 10 ) * 4;         o.oy = ( ( ( ( v >> 14 ) & 0x3ff ) * 12 ) >> 10 ) * 4; }
+  else if( c == 1 ) { o.neg = ( v >> 2 ) & 1; o.ox = ( ( ( ( v >> 10 ) & 0x3ff ) * 13 ) >> 10 ) * 2; o.oy = ( ( ( ( ( v >> 24 ) & 0xff ) | ( ( v << 8 ) & 0x300 ) ) * 12 ) >> 10 ) * 2; }
+  else              { o.neg = ( v >> 15 ) & 1; o.ox = ( ( ( ( v >> 20 ) & 0x3ff ) * 13 ) >> 10 ) * 2; o.oy = ( ( ( ( v >> 4 ) & 0x3ff ) * 12 ) >> 10 ) * 2; }
+  return o;
+}
+// make_grain_pattern for one sample: position i in a block with offsets cur (and up, in an overlap row: weights oc1 / oc2), pattern index from
+// the intensity
+__device__ __forceinline__ int fg_grain( const int8_t* __restrict__ pat, const uint8_t* __restrict__ plut, int intensity, int i, FgOff cur, FgOff up, int oc1, int oc2 )
+{
+  const int8_t* pp = pat + ( plut[intensity] >> 4 ) * 4096;
+  int P = pp[cur.oy * 64 + cur.ox + i];
+  if( cur.neg ) P = -P;
+  if( oc1 )
+  {
+    int U = pp[up.oy * 64 + up.ox + i];
+    if( up.neg ) U = -U;
+    P = ( P * oc1 + U * oc2 + 16 ) >> 5;
+  }
+  return P;
+}
+__global__ __launch_bounds__( 256 ) void k_film_grain( FilmGrainParams p, FgTiles t, uint8_t* __restrict__ dst )
+{
+  const int tile = blockIdx.x, c = tile >= t.first[2] && p.numComp > 2 ? 2 : ( tile >= t.first[1] && p.numComp > 1 ? 1 : 0 );
+  const int w = p.w[c], h = p.h[c], tileIdx = tile - t.first[c];
+  const int r = ( tileIdx / t.tilesX[c] ) * 4 + ( threadIdx.x >> 6 ), x0 = ( ( tileIdx % t.tilesX[c] ) * 64 + ( threadIdx.x & 63 ) ) * 4;
+  if( r >= h || x0 >= w ) return;
+  const vvr_film_grain_bank* __restrict__ bank = p.bank;
+  const pel_t* __restrict__ row = p.src[c] + (size_t) r * p.stride[c];
+  int I[4], g[4] = { 0, 0, 0, 0 };
+#pragma unroll
+  for( int k = 0; k < 4; k++ ) I[k] = row[min( x0 + k, w - 1 )];      // (beyond the frame: the row's last sample, see vvr.h)
+  const bool present = bank->comp_present[c];
+  if( present )
+  {
+    const int sub = c ? 1 : 0, bw = 16 >> sub, y = r << sub, j = y & 15, bx = x0 / bw, i0 = x0 - bx * bw;
+    const int oc1 = y > 15 && j == 0 ? ( sub ? 20 : 12 ) : ( y > 15 && j == 1 ? 24 : 0 ), oc2 = j == 0 ? ( sub ? 20 : 24 ) : 12;
+    const uint32_t* __restrict__ wrow = p.words + (size_t) ( y >> 4 ) * p.nbx;
+    const int8_t* __restrict__ pat = &bank->pattern[c ? 1 : 0][0][0][0];
+    const uint8_t* __restrict__ plut = bank->pattern_lut[c];
+    auto offs = [&]( int b, FgOff& cur, FgOff& up )
+    {
+      cur = fg_offset( wrow[b], c ); cur.oy += j >> sub;
+      up = cur;
+      if( oc1 ) { up = fg_offset( wrow[b - p.nbx], c ); up.oy += ( 16 + j ) >> sub; }
+    };
+    FgOff cur, up;
+    offs( bx, cur, up );
+#pragma unroll
+    for( int k = 0; k < 4; k++ ) g[k] = fg_grain( pat, plut, ( I[k] >> p.bs ) & 0xff, i0 + k, cur, up, oc1, oc2 );
+    // the horizontal deblocking across the block's left and right edges (scale_and_output), on the pre-deblock values
+    const int gl = i0 == 0 && bx > 0 ? 1 : 0, gr = i0 + 4 == bw && bx + 1 < p.nbx ? 1 : 0;
+    if( gl | gr )
+    {
+      FgOff ncur, nup;
+      offs( gl ? bx - 1 : bx + 1, ncur, nup );
+      const int n = fg_grain( pat, plut, ( row[gl ? x0 - 1 : x0 + 4] >> p.bs ) & 0xff, gl ? bw - 1 : 0, ncur, nup, oc1, oc2 );
+      if( gl ) g[0] = ( n + 3 * g[0] + g[1] + 2 ) >> 2;
+      else     g[3] = ( g[2] + 3 * g[3] + n + 2 ) >> 2;
+    }
+  }
+  const uint8_t* __restrict__ slut = bank->scale_lut[c];
+  const int maxVal = 255 << p.bs, half = 1 << ( p.scaleShift - 1 );
+  uint8_t* out = dst + p.dstOff[c] + ( (size_t) r * w + x0 ) * p.bytesPerSample;
+#pragma unroll
+  for( int k = 0; k < 4; k++ )
+  {
+    if( x0 + k >= w ) break;
+    const int v = present ? clip3( 0, maxVal, I[k] + ( ( slut[( I[k] >> p.bs ) & 0xff] * g[k] + half ) >> p.scaleShift ) ) : I[k];
+    if( p.bytesPerSample == 2 ) ( (uint16_t*) out )[k] = (uint16_t) v;
+    else out[k] = (uint8_t) v;
+  }
+}
+void launch_film_grain( hipStream_t s, const FilmGrainParams& p, void* dst )
+{
+  FgTiles t = { { 1, 1, 1 }, { 0, 0, 0 } };
+  int total = 0;
+  for( int c = 0; c < 3; c++ )
+  {
+    t.first[c] = total;
+    if( c >= p.numComp ) continue;
+    t.tilesX[c] = ( ( p.w[c] + 3 ) / 4 + 63 ) / 64;
+    total += t.tilesX[c] * ( ( p.h[c] + 3 ) / 4 );
+  }
+  hipLaunchKernelGGL( k_film_grain, dim3( total ), dim3( 256 ), 0, s, p, t, (uint8_t*) dst );
+}
+
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in
 __device__ __forceinline__ uint32_t crc_mul( uint32_t a, uint32_t b )
 {

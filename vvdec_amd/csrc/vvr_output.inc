@@ -69,6 +69,22 @@ void rescale_axis( int src, int dst, int cs, int collocated, int fracShift, int&
   shift = 14 - fracShift + cs;
   add = ( 1 << ( shift - 1 ) ) + ( ( ( 1 - collocated ) * 8 * ( scale - ( 1 << 14 ) ) + ( 1 << ( 2 + cs ) ) ) >> ( 3 + cs ) );
 }
+
+// the film grain's random generator (prng, FilmGrainImpl.h) and the words of a frame's blocks: FilmGrain::prepareBlockSeeds( w, h ) gives band
+// by (16 luma rows) the seed s[by], s[0] the chain's state and s[by + 1] = s[by] after nbx steps; add_grain_line gives block bx of the band s[by]
+// after bx steps.  words: nby x nbx.  Returns the chain's state after the frame, the seed of its last band (FilmGrain.cpp:794-820).
+uint32_t grain_prng( uint32_t x ) { return ( ( ( x << 30 ) ^ ( x << 2 ) ) & 0x80000000u ) | ( x >> 1 ); }
+uint32_t grain_words( uint32_t state, int nbx, int nby, uint32_t* words )
+{
+  uint32_t seed = state;
+  for( int by = 0; by < nby; by++ )
+  {
+    if( by ) seed = grain_prng( words[(size_t) by * nbx - 1] );
+    uint32_t r = seed;
+    for( int bx = 0; bx < nbx; bx++ ) { words[(size_t) by * nbx + bx] = r; r = grain_prng( r ); }
+  }
+  return seed;
+}
 }   // namespace
 
 #if !defined(__HIPCC__)
@@ -102,6 +118,57 @@ void launch_rescale( hipStream_t, const RescaleParams& p, void* dst )
       for( int k = 0; k < taps; k++ ) sum += coef( frac, k ) * tmp[(size_t) std::min( std::max( 0, integer + k - taps / 2 + 1 ), p.h - 1 ) * p.outW + i];
       const int v = std::min( std::max( 0, ( sum + 2048 ) >> 12 ), p.maxVal );
       if( p.bytesPerSample == 2 ) ( (uint16_t*) dst )[(size_t) j * p.outW + i] = (uint16_t) v; else ( (uint8_t*) dst )[(size_t) j * p.outW + i] = (uint8_t) v;
+    }
+  }
+}
+
+// ... and launch_film_grain as a plain loop restating FilmGrainImpl::add_grain_block (FilmGrainImpl.cpp:126-324) row by row: the pre-deblock grain
+// of every block of the row (make_grain_pattern), the horizontal deblocking across each block edge, scale, add and clip (scale_and_output)
+void launch_film_grain( hipStream_t, const FilmGrainParams& p, void* dst )
+{
+  const vvr_film_grain_bank& b = *p.bank;
+  for( int c = 0; c < p.numComp; c++ )
+  {
+    const int sub = c ? 2 : 1, bw = 16 / sub, w = p.w[c], n = p.nbx * bw;
+    std::vector<int> I( n ), g( n ), d( n );
+    for( int r = 0; r < p.h[c]; r++ )
+    {
+      const pel_t* row = p.src[c] + (size_t) r * p.stride[c];
+      for( int x = 0; x < n; x++ ) I[x] = row[std::min( x, w - 1 )];
+      std::fill( d.begin(), d.end(), 0 );
+      if( b.comp_present[c] )
+      {
+        const int y = r * sub, j = y & 15;
+        const int oc1 = y > 15 && j == 0 ? ( sub > 1 ? 20 : 12 ) : ( y > 15 && j == 1 ? 24 : 0 ), oc2 = y > 15 && j == 0 ? ( sub > 1 ? 20 : 24 ) : 12;
+        auto offset = [&]( uint32_t v, int& s, int& ox, int& oy )      // get_offset_y / _u / _v, 4:2:0 chroma
+        {
+          const uint32_t sx = c == 0 ? 31 : ( c == 1 ? 2 : 15 );
+          const uint32_t bx = c == 0 ? v & 0x3ff : ( c == 1 ? ( v >> 10 ) & 0x3ff : ( v >> 20 ) & 0x3ff );
+          const uint32_t by = c == 0 ? ( v >> 14 ) & 0x3ff : ( c == 1 ? ( ( v >> 24 ) & 0xff ) | ( ( v << 8 ) & 0x300 ) : ( v >> 4 ) & 0x3ff );
+          s = ( v >> sx ) & 1 ? -1 : 1; ox = (int) ( ( bx * 13 ) >> 10 ) * ( 4 / sub ); oy = (int) ( ( by * 12 ) >> 10 ) * ( 4 / sub );
+        };
+        for( int bx = 0; bx < p.nbx; bx++ )
+        {
+          int s, ox, oy, sUp = 1, oxUp = 0, oyUp = 0;
+          offset( p.words[(size_t) ( y / 16 ) * p.nbx + bx], s, ox, oy ); oy += j / sub;
+          if( oc1 ) { offset( p.words[(size_t) ( y / 16 - 1 ) * p.nbx + bx], sUp, oxUp, oyUp ); oyUp += ( 16 + j ) / sub; }
+          for( int i = 0; i < bw; i++ )
+          {
+            const int pi = b.pattern_lut[c][( I[bx * bw + i] >> ( p.bs ) ) & 0xff] >> 4;
+            int P = b.pattern[c ? 1 : 0][pi][oy][ox + i] * s;
+            if( oc1 ) P = ( P * oc1 + b.pattern[c ? 1 : 0][pi][oyUp][oxUp + i] * oc2 * sUp + 16 ) >> 5;
+            g[bx * bw + i] = P;
+          }
+        }
+        d = g;
+        for( int e = bw; e < n; e += bw ) { d[e - 1] = ( g[e - 2] + 3 * g[e - 1] + g[e] + 2 ) >> 2; d[e] = ( g[e - 1] + 3 * g[e] + g[e + 1] + 2 ) >> 2; }
+      }
+      for( int x = 0; x < w; x++ )
+      {
+        const int v = b.comp_present[c] ? std::min( std::max( 0, I[x] + ( ( b.scale_lut[c][( I[x] >> p.bs ) & 0xff] * d[x] + ( 1 << ( p.scaleShift - 1 ) ) ) >> p.scaleShift ) ), 255 << p.bs ) : I[x];
+        uint8_t* out = (uint8_t*) dst + p.dstOff[c] + ( (size_t) r * w + x ) * p.bytesPerSample;
+        if( p.bytesPerSample == 2 ) *(uint16_t*) out = (uint16_t) v; else *out = (uint8_t) v;
+      }
     }
   }
 }
@@ -167,6 +234,79 @@ VVR_API int vvr_read_output_scaled( vvr_context* c, int slot, int comp, int x, i
   HIPCHK( c, hipMemcpyAsync( c->outHost, c->outDev, rowBytes * outH, hipMemcpyDeviceToHost, s ) );
   HIPCHK( c, hipStreamSynchronize( s ) );
   for( int r = 0; r < outH; r++ ) memcpy( (uint8_t*) dst + (size_t) r * dstStrideBytes, (const uint8_t*) c->outHost + (size_t) r * rowBytes, rowBytes );
+  return VVR_OK;
+}
+
+VVR_API int vvr_set_film_grain( vvr_context* c, const vvr_film_grain_bank* bank )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  if( !bank ) { c->grainBank.reset(); return VVR_OK; }
+  if( bank->struct_size != sizeof( vvr_film_grain_bank ) ) { c->setError( "vvr_set_film_grain: struct_size is not sizeof( vvr_film_grain_bank )" ); return VVR_ERR_PARAMETER; }
+  if( bank->shift < 2 || bank->shift > 7 ) { c->setError( "vvr_set_film_grain: shift outside 2..7" ); return VVR_ERR_PARAMETER; }
+  for( int k = 0; k < 3; k++ )
+    for( int i = 0; i < 256; i++ )
+      if( bank->pattern_lut[k][i] >= 0x80 ) { c->setError( "vvr_set_film_grain: pattern_lut entry >= 0x80 (8 patterns)" ); return VVR_ERR_PARAMETER; }
+  if( !c->grainBank ) c->grainBank.reset( new vvr_film_grain_bank );
+  *c->grainBank = *bank;
+  c->grainBankStale = true;
+  return VVR_OK;
+}
+
+VVR_API int vvr_set_film_grain_seed( vvr_context* c, uint32_t seed )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  c->grainSeed = seed;
+  return VVR_OK;
+}
+
+VVR_API int vvr_read_output_grain( vvr_context* c, int slot, int x, int y, int w, int h, int bytesPerSample, void* const dst[3], const size_t dstStrideBytes[3] )
+{
+  if( !c || slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] || !dst || !dstStrideBytes ) return VVR_ERR_PARAMETER;
+  if( !c->grainBank ) { c->setError( "vvr_read_output_grain: no film grain bank set" ); return VVR_ERR_PARAMETER; }
+  const int bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1;
+  if( bd != 8 && bd != 10 ) { c->setError( "vvr_read_output_grain: film grain needs a bit depth of 8 or 10 (FilmGrainImpl::set_depth)" ); return VVR_ERR_PARAMETER; }
+  const DevPlanes d = pictureIn( c, slot );
+  if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) )
+  { c->setError( "vvr_read_output_grain: window outside the picture, or odd in 4:2:0" ); return VVR_ERR_PARAMETER; }
+  if( w <= 128 ) { c->setError( "vvr_read_output_grain: film grain needs a frame wider than 128 samples (FilmGrainImpl::add_grain_block)" ); return VVR_ERR_PARAMETER; }
+  if( bytesPerSample != 1 && bytesPerSample != 2 ) { c->setError( "vvr_read_output_grain: bad sample size" ); return VVR_ERR_PARAMETER; }
+  if( bytesPerSample == 1 && bd > 8 ) { c->setError( "vvr_read_output_grain: 8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" ); return VVR_ERR_PARAMETER; }
+  for( int k = 0; k < nc; k++ )
+    if( !dst[k] || dstStrideBytes[k] < (size_t) ( w >> ( k ? 1 : 0 ) ) * bytesPerSample ) { c->setError( "vvr_read_output_grain: missing plane or stride below the window's row" ); return VVR_ERR_PARAMETER; }
+  hipSetDevice( c->device );
+  int rc = vvr_sync( c ); if( rc != VVR_OK ) return rc;
+  // the scratch: the packed planes, then the blocks' random words (staged in the pinned half at the same offset)
+  FilmGrainParams p;
+  size_t total = 0;
+  for( int k = 0; k < 3; k++ )
+  {
+    const int s = k ? 1 : 0;
+    p.src[k] = k < nc ? d.p[k] + (size_t) ( y >> s ) * d.stride[k] + ( x >> s ) : nullptr;
+    p.stride[k] = d.stride[k]; p.w[k] = w >> s; p.h[k] = h >> s; p.dstOff[k] = total;
+    if( k < nc ) total = alignUp( total + (size_t) p.w[k] * p.h[k] * bytesPerSample, 256 );
+  }
+  const int nbx = ( w + 15 ) / 16, nby = ( h + 15 ) / 16;
+  const size_t wordsBytes = (size_t) nbx * nby * sizeof( uint32_t );
+  if( ( rc = ensureOutputScratch( c, total + wordsBytes, total + wordsBytes ) ) != VVR_OK ) return rc;
+  uint32_t* words = (uint32_t*) ( (char*) c->outHost + total );
+  const uint32_t nextSeed = grain_words( c->grainSeed, nbx, nby, words );
+  hipStream_t s = c->streams[0];
+  if( !c->grainBankDev ) HIPCHK( c, hipMalloc( &c->grainBankDev, sizeof( vvr_film_grain_bank ) ) );
+  if( c->grainBankStale ) HIPCHK( c, hipMemcpyAsync( c->grainBankDev, c->grainBank.get(), sizeof( vvr_film_grain_bank ), hipMemcpyHostToDevice, s ) );
+  HIPCHK( c, hipMemcpyAsync( (char*) c->outDev + total, words, wordsBytes, hipMemcpyHostToDevice, s ) );
+  p.bank = (const vvr_film_grain_bank*) c->grainBankDev; p.words = (const uint32_t*) ( (char*) c->outDev + total ); p.nbx = nbx;
+  p.numComp = nc; p.bs = bd - 8; p.scaleShift = c->grainBank->shift + 6 - p.bs; p.bytesPerSample = bytesPerSample;
+  launch_film_grain( s, p, c->outDev );
+  HIPCHK( c, hipGetLastError() );
+  HIPCHK( c, hipMemcpyAsync( c->outHost, c->outDev, total, hipMemcpyDeviceToHost, s ) );
+  HIPCHK( c, hipStreamSynchronize( s ) );
+  c->grainBankStale = false;
+  c->grainSeed = nextSeed;      // (only a frame that was grained advances the chain)
+  for( int k = 0; k < nc; k++ )
+  {
+    const size_t rowBytes = (size_t) p.w[k] * bytesPerSample;
+    for( int r = 0; r < p.h[k]; r++ ) memcpy( (uint8_t*) dst[k] + (size_t) r * dstStrideBytes[k], (const uint8_t*) c->outHost + p.dstOff[k] + (size_t) r * rowBytes, rowBytes );
+  }
   return VVR_OK;
 }
 
