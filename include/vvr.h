@@ -514,6 +514,47 @@ VVR_API int          vvr_set_film_grain_seed(vvr_context* ctx, uint32_t seed);
  * sample in the row.  The synthesis runs on the device in the same pass that crops and packs the window.  Waits for all work on the slot. */
 VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, int y, int w, int h, int bytes_per_sample,
                                            void* const dst[3], const size_t dst_stride_bytes[3]);
+/* Output queue: the three calls above as requests that are ordered behind the picture ON THE DEVICE and never drain the context (no
+ * vvr_sync): a request runs on the context's output stream behind its picture's completion event, leaves through one of 8 ring entries
+ * (device scratch + pinned staging, allocated on first use, grown on demand, freed by vvr_destroy) and is collected with its ticket.
+ *   formats  VVR_OUT_PLANAR16 / VVR_OUT_PLANAR8: the bytes vvr_read_output / _scaled / _grain give for bytes_per_sample 2 / 1, same refusals;
+ *            VVR_OUT_PACKED10: vvdecapp's packed output (--pyuv, _writeComponentToFile, vvdecHelper.h:106-145): every row of every plane is
+ *            w / 4 * 5 bytes, samples s0..s3 the little-endian 40-bit word s0 | s1 << 10 | s2 << 20 | s3 << 30; a context of 8 bits stores
+ *            s << 2 (:201-248).  Refused at bit depth 9 and when the output width of a plane is not a multiple of 4.
+ *   grain with out_w / out_h: the window is grained at its own size exactly as vvr_read_output_grain does it, the grained frame is then
+ *            rescaled exactly as vvr_read_output_scaled rescales a picture, taps clamped to the grained frame (the reference's order:
+ *            xAddGrain in xAddPicture, then the application's upscaleFrame).
+ *   seed chain: shared with vvr_read_output_grain; it advances in vvr_output_submit, in submission order, for accepted requests only.
+ *   slot     the request reads `slot` until its kernels have run (tens of microseconds; NOT until the copy to the host has finished): pictures
+ *            submitted (vvr_submit) after vvr_output_submit has returned a ticket that overwrite the slot are ordered behind that on the device.
+ *            The other way round is the caller's duty: a request is submitted BEFORE the next picture into its slot is (one that comes after that
+ *            picture has been handed to the device is refused; one that races with it gets whichever picture the slot holds).
+ *   dst      when every dst[c] lies in memory of vvr_host_alloc the device copies straight there at the caller's stride and vvr_output_wait
+ *            copies nothing; else the rows leave pinned staging inside vvr_output_wait, on the waiting thread.  Either way exactly the
+ *            output's bytes cross PCIe.  dst must stay valid until vvr_output_wait has returned.
+ * vvr_output_submit: a ticket (>= 2: never VVR_NOT_READY); VVR_ERR_PARAMETER (with a text) for a request that is refused; VVR_ERR_BUSY when 8 requests are in flight;
+ *   VVR_NOT_READY (blocking == 0) when `job` has not been handed to the device yet.  A request for a job that failed is accepted and fails with
+ *   the job's status from vvr_output_test / vvr_output_wait.  vvr_output_test: VVR_OK (vvr_output_wait returns at once) / VVR_NOT_READY / the
+ *   failure; the ticket stays.  vvr_output_wait blocks for THIS request only and retires the ticket.  An unknown or retired ticket:
+ *   VVR_ERR_PARAMETER.  vvr_sync also waits for the requests in flight but retires no ticket. */
+enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2 };
+typedef struct vvr_output_request {
+  uint32_t struct_size;        /* sizeof( vvr_output_request ) */
+  int32_t  slot;
+  int32_t  job;                /* >= 0: the picture this job reconstructs into `slot`, ordered behind it ON THE DEVICE;
+                                  -1: the slot as all work submitted so far leaves it (vvr_stream_wait_slot's rule) */
+  int32_t  x, y, w, h;         /* window, luma samples (even in 4:2:0) */
+  int32_t  out_w, out_h;       /* 0, 0: the window's size; else rescaled as vvr_read_output_scaled does it (chroma: >> 1) */
+  uint8_t  collocated;         /* as vvr_read_output_scaled */
+  uint8_t  format;             /* VVR_OUT_* */
+  uint8_t  grain;              /* 1: the context's bank is added first, one frame of the seed chain (vvr_read_output_grain's rules) */
+  uint8_t  blocking;           /* 0: VVR_NOT_READY instead of waiting on the host until `job` has been handed to the device */
+  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0 */
+  size_t   dst_stride_bytes[3];
+} vvr_output_request;
+VVR_API int          vvr_output_submit(vvr_context* ctx, const vvr_output_request* req);
+VVR_API int          vvr_output_test(vvr_context* ctx, int ticket);
+VVR_API int          vvr_output_wait(vvr_context* ctx, int ticket);
 /* decoded picture hash of a slot, as the decoded-picture-hash SEI defines it and the reference checks it (calcMD5 / calcCRC / calcChecksum,
  * PicYuvMD5.cpp:99-221): one digest per component over the whole plane in raster order, samples as 1 byte (bit depth 8) or 2 bytes little
  * endian.  digest receives num_components x digest_len bytes (MD5 16, CRC 2, checksum 4), *digest_len the length of one.  CRC and checksum

@@ -1,0 +1,144 @@
+"""Pictures per second DELIVERED TO THE HOST while a 10-bit 4:2:0 3840x2160 random-access stream is reconstructed (bench.py's 4k stream and window:
+K timed pictures behind pre-roll and warm-up, every window from the first picture of the stream), four ways in turn in one process:
+  A  the synchronous calls: vvr_wait, then three vvr_read_output (each drains the context) - the only way to output every picture before the queue
+  B  the output queue, VVR_OUT_PLANAR16 into pageable memory (the rows leave pinned staging in vvr_output_wait)
+  C  the output queue, VVR_OUT_PLANAR16 into memory of vvr_host_alloc (the device copies straight there)
+  D  the output queue, VVR_OUT_PACKED10 into memory of vvr_host_alloc
+and the decode-only rate of the same window (nothing leaves the device).  The ways alternate window by window; every way runs at least --windows
+windows and --min-seconds of timed work; median, minimum and maximum are reported.  Before the timed runs the outputs of A and B of the timed pictures
+are compared (they must be identical).  Requests are submitted without blocking behind their picture and collected when 8 are in flight.
+Kernel time: `rocprofv3 --kernel-trace --stats -- python tools/output_queue_probe.py --ways D --windows 2 --min-seconds 0` in a run of its own.
+Usage: python tools/output_queue_probe.py [--steps 64] [--warmup 16] [--windows 5] [--min-seconds 1.0] [--ways ABCDN] [--out FILE]"""
+import argparse
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--warmup", type=int, default=16)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--min-seconds", type=float, default=1.0)
+    ap.add_argument("--ways", default="ABCDN")
+    ap.add_argument("--config", default="4k")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import bench
+    import vvdec_amd
+    from vvdec_amd import abi, synth
+    from concurrent.futures import ThreadPoolExecutor
+    W, H, mix, intra_period, _ = bench.CONFIGS[a.config]
+    tools = bench._tools(abi) | abi.TOOL_LFP_ON_DEVICE | abi.TOOL_AFFINE_MV_ON_DEVICE
+    K, Wm = a.steps, a.warmup
+    plans, nslots, orders = bench.stream_plan(a.config, 32, intra_period, 8, 48, K, Wm)
+    order, first = orders[8]
+    rec = vvdec_amd.Reconstructor(W, H, num_slots=nslots, num_streams=4, host_threads=8)
+    L, ctx = rec.L, rec.ctx
+    needed = max(order[:first + K]) + 1
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as tp:
+        descs = list(tp.map(lambda pl: synth.picture_for_plan(pl, W, H, seed=1234, tool_flags=tools, alloc=rec.host_array, **mix), plans[:needed]))
+    cpics = [d.c() for d in descs]
+    timed = order[first:first + K]
+
+    # destinations: one set per ring entry and kind
+    def planes(fmt, pinned):
+        shapes, dt = abi.output_plane_shapes((0, 0, W, H), fmt, None, 3)
+        return [rec.host_array(r * n, dt).reshape(r, n) if pinned else np.zeros((r, n), dt) for r, n in shapes]
+    sets = {"B": ("planar16", [planes("planar16", False) for _ in range(8)]), "C": ("planar16", [planes("planar16", True) for _ in range(8)]),
+            "D": ("packed10", [planes("packed10", True) for _ in range(8)])}
+    reqs = {w: [abi.output_request(0, 0, (0, 0, W, H), fmt, None, (True, False), False, False, p) for p in ps] for w, (fmt, ps) in sets.items()}
+    sync_out = planes("planar16", False)
+    pcie = {"A": sum(p.nbytes for p in sync_out), "B": sum(p.nbytes for p in sets["B"][1][0]), "C": sum(p.nbytes for p in sets["C"][1][0]),
+            "D": sum(p.nbytes for p in sets["D"][1][0]), "N": 0}
+
+    def run(way, idx, digests=None):
+        """the pictures `idx` through vvr_submit, every one of them delivered the way `way` says"""
+        if way == "N":
+            for i in idx:
+                rec.submit_c(cpics[i])
+            rec.sync()
+            return
+        if way == "A":
+            for i in idx:
+                job = rec.submit_c(cpics[i])
+                rec._check(L.vvr_wait(ctx, job))
+                for c, o in enumerate(sync_out):
+                    rec._check(L.vvr_read_output(ctx, plans[i].slot, c, 0, 0, o.shape[1], o.shape[0], 2, o.ctypes.data, o.strides[0]))
+                if digests is not None:
+                    digests.append(hashlib.blake2b(b"".join(o.tobytes() for o in sync_out)).digest())
+            rec.sync()
+            return
+        pending, flight, free = [], [], list(range(8))
+
+        def collect():
+            t, e = flight.pop(0)
+            rec._check(L.vvr_output_wait(ctx, t))
+            if digests is not None:
+                digests.append(hashlib.blake2b(b"".join(o.tobytes() for o in sets[way][1][e])).digest())
+            free.append(e)
+
+        def drain(block):
+            while pending:
+                if not free:
+                    collect()
+                job, slot = pending[0]
+                r = reqs[way][free[0]]
+                r.job, r.slot, r.blocking = job, slot, 1 if block else 0
+                t = rec._check(L.vvr_output_submit(ctx, C.byref(r)))
+                if t == abi.VVR_NOT_READY:
+                    return
+                pending.pop(0)
+                flight.append((t, free.pop(0)))
+        for i in idx:
+            pending.append((rec.submit_c(cpics[i]), plans[i].slot))
+            drain(False)
+        drain(True)
+        while flight:
+            collect()
+        rec.sync()
+
+    def window(way, digests=None):
+        run("N", order[:first - Wm])
+        run(way, order[first - Wm:first])
+        t0 = time.perf_counter()
+        run(way, timed, digests)
+        return time.perf_counter() - t0
+
+    res = {"config": a.config, "size": [W, H], "steps": K, "warmup": Wm, "pcie_bytes_per_frame": pcie}
+    if "A" in a.ways and "B" in a.ways:
+        da, db = [], []
+        window("A", da)
+        window("B", db)
+        res["outputs_A_equal_B"] = len(da) == K and da == db
+    ways = [w for w in "ABCDN" if w in a.ways]
+    times = {w: [] for w in ways}
+    for w in ways:                                   # warm-up: every way once (ring entries, pinned staging)
+        window(w)
+    while any(len(times[w]) < a.windows or sum(times[w]) < a.min_seconds for w in ways):
+        for w in ways:
+            times[w].append(window(w))
+    for w in ways:
+        fps = sorted(K / t for t in times[w])
+        res["decode_only" if w == "N" else w] = {"pictures_per_s_median": round(float(np.median(fps)), 1), "min": round(fps[0], 1), "max": round(fps[-1], 1),
+                                                 "windows": len(fps), "timed_seconds": round(sum(times[w]), 3),
+                                                 "pcie_GB_per_s_at_median": round(float(np.median(fps)) * pcie[w] / 1e9, 2)}
+    rec.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -93,6 +93,12 @@ def lib():
         L.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.vvr_stream_wait_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.vvr_slot_external_event.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.vvr_output_submit.restype = C.c_int
+        L.vvr_output_submit.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_output_test.restype = C.c_int
+        L.vvr_output_test.argtypes = [C.c_void_p, C.c_int]
+        L.vvr_output_wait.restype = C.c_int
+        L.vvr_output_wait.argtypes = [C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -101,7 +107,8 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
-                    "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture"]
+                    "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
+                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait"]
 
 
 class Reconstructor:
@@ -120,6 +127,7 @@ class Reconstructor:
             raise VvrError("vvr_create failed with %d (%s)" % (rc, {abi.VVR_ERR_NO_DEVICE: "no gfx950 device; there is no CPU fallback"}.get(rc, "see include/vvr.h")))
         self.width, self.height, self.chroma_format = width, height, chroma_format
         self._keep = {}
+        self._out = {}
 
     # -- lifetime
     def close(self):
@@ -297,6 +305,40 @@ class Reconstructor:
                                                           int(bool(collocated[0])) | int(bool(collocated[1])) << 1, bytes_per_sample, a.ctypes.data, a.strides[0]))
             out.append(a)
         return out
+
+    # -- output queue: requests ordered behind their picture on the device; nothing here drains the context
+    def output_submit(self, slot, job=None, window=None, fmt="planar16", size=None, collocated=(True, False), grain=False, pinned=False, blocking=True):
+        """vvr_output_submit: the window of `slot` (as `job` leaves it; None: as all work submitted so far leaves it) in the application's form ->
+        ticket, or None when blocking=False and the job has not been handed to the device yet.  fmt: "planar16", "planar8" or "packed10"
+        (vvdecapp --pyuv: four samples in five bytes); size, collocated, grain as read_output - and grain with size is the reference's chain,
+        grain first, then the rescale of the grained frame.  pinned: the planes are allocated in memory of the context that the device writes
+        directly (vvr_host_alloc) - they belong to the context and are views valid until close().  At most 8 requests in flight (VvrError).
+        Ask for a picture's output before the next picture into its slot is submitted: that picture then waits for the request on the device."""
+        win = tuple(window or (0, 0, self.width, self.height))
+        shapes, dt = abi.output_plane_shapes(win, fmt, size, 3 if self.chroma_format else 1)
+        planes = [self.host_array(r * n, dt).reshape(r, n) if pinned else np.zeros((r, n), dt) for r, n in shapes]
+        req = abi.output_request(slot, job, win, fmt, size, collocated, grain, blocking, planes)
+        ticket = self._check(self.L.vvr_output_submit(self.ctx, C.byref(req)))
+        if not blocking and ticket == abi.VVR_NOT_READY:
+            return None
+        self._out[ticket] = planes
+        return ticket
+
+    def output_test(self, ticket):
+        """vvr_output_test: True when output_wait(ticket) returns at once; raises if the request (or its picture) failed"""
+        rc = self.L.vvr_output_test(self.ctx, ticket)
+        if rc == abi.VVR_NOT_READY:
+            return False
+        self._check(rc)
+        return True
+
+    def output_wait(self, ticket):
+        """vvr_output_wait: blocks for this request only and retires the ticket -> list of planes (packed10: uint8 arrays of (rows, w / 4 * 5))"""
+        try:
+            self._check(self.L.vvr_output_wait(self.ctx, ticket))
+            return self._out[ticket]
+        finally:
+            self._out.pop(ticket, None)
 
     def write_picture(self, slot, planes):
         for c, pl in enumerate(planes):

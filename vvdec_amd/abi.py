@@ -160,5 +160,40 @@ def film_grain_bank(comp_present, shift, scale_lut, pattern_lut, pattern):
     return b
 
 
+OUT_PLANAR16, OUT_PLANAR8, OUT_PACKED10 = 0, 1, 2
+OUT_FORMATS = {"planar16": OUT_PLANAR16, "planar8": OUT_PLANAR8, "packed10": OUT_PACKED10}
+
+
+class OutputRequest(C.Structure):
+    """vvr_output_request: one request of the output queue (vvr_output_submit, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("slot", i32), ("job", i32), ("x", i32), ("y", i32), ("w", i32), ("h", i32), ("out_w", i32), ("out_h", i32),
+                ("collocated", u8), ("format", u8), ("grain", u8), ("blocking", u8), ("dst", C.c_void_p * 3), ("dst_stride_bytes", C.c_size_t * 3)]
+
+
+def output_request(slot, job, window, fmt, size, collocated, grain, blocking, planes):
+    """an OutputRequest whose destinations are the numpy arrays `planes` (rows at their strides)"""
+    r = OutputRequest()
+    r.struct_size = C.sizeof(OutputRequest)
+    r.slot, r.job = slot, -1 if job is None else job
+    r.x, r.y, r.w, r.h = window
+    r.out_w, r.out_h = size or (0, 0)
+    r.collocated = int(bool(collocated[0])) | int(bool(collocated[1])) << 1
+    r.format, r.grain, r.blocking = OUT_FORMATS[fmt] if isinstance(fmt, str) else fmt, 1 if grain else 0, 1 if blocking else 0
+    for c, a in enumerate(planes):
+        r.dst[c] = a.ctypes.data
+        r.dst_stride_bytes[c] = a.strides[0]
+    return r
+
+
+def output_plane_shapes(window, fmt, size, ncomp):
+    """(rows, bytes or samples per row) of every plane a request produces, and the dtype: packed10 rows are w / 4 * 5 bytes"""
+    import numpy as np
+    w, h = size or (window[2], window[3])
+    shapes = [(h >> (1 if c else 0), w >> (1 if c else 0)) for c in range(ncomp)]
+    if fmt == "packed10":
+        return [(r, n // 4 * 5) for r, n in shapes], np.uint8
+    return shapes, np.uint8 if fmt == "planar8" else np.uint16
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]

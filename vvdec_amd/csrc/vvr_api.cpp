@@ -89,7 +89,7 @@ static double g_wdSum[6]; static uint64_t g_wdJobs; static double g_wdPart[4], g
 
 struct Stat { uint64_t launches = 0; double ms = 0, bytes = 0; };
 struct PendingTiming { hipEvent_t a, b; int kernel; double bytes; };
-const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes" };
+const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame" };
 
 // One slot of the upload ring: pinned staging memory and its image in HBM (grown on demand, never freed while the context lives), the device
 // pointers of the picture that currently sits in it, and the pinned landing area of its DMVR delta MVs.
@@ -163,6 +163,9 @@ struct vvr_context {
   void*      outDev = nullptr; size_t outDevCap = 0;
   void*      outHost = nullptr; size_t outHostCap = 0;
   hipStream_t outStream = nullptr;                 // device-to-host copies of vvr_read_picture
+  // the output queue (vvr_output_submit, vvr_output.inc): its stream and its ring; the entries are guarded by mu
+  hipStream_t outQStream = nullptr;
+  struct OutEntry* outRing = nullptr; int nextTicket = 2;      // (a ticket is never VVR_NOT_READY)
   char*      prepStage = nullptr; size_t prepStageCap = 0;      // pinned staging of vvr_prepare
   std::vector<void*> stagePool;                    // pinned staging buffers of vvr_read_picture (one picture each), handed out under `mu`
   // film grain at the output (vvr_set_film_grain): the bank, its device copy (uploaded on the stream of the first grain read after a change) and
@@ -1095,6 +1098,7 @@ VVR_API int vvr_create( const vvr_config* cfg, vvr_context** out )
 }
 
 VVR_API int vvr_sync( vvr_context* c );
+static void destroyOutputQueue( vvr_context* c );
 
 VVR_API void vvr_destroy( vvr_context* c )
 {
@@ -1104,6 +1108,7 @@ VVR_API void vvr_destroy( vvr_context* c )
   { std::lock_guard<std::mutex> lk( c->mu ); c->stop = true; c->cv.notify_all(); }
   for( auto& t : c->workers ) t.join();
   if( c->launcher.joinable() ) c->launcher.join();
+  if( c->outQStream ) hipStreamSynchronize( c->outQStream );      // (requests of the output queue still in flight read the DPB and write their ring entries)
 #ifdef VVR_WATCHDOG
   if( c->watchdog.joinable() ) c->watchdog.join();
   if( g_wdJobs ) fprintf( stderr, "[vvr] per streamed picture (ms): queued %.2f, work lists %.2f, wait for ring entry %.2f, pack %.2f, wait for commit %.2f, enqueue %.2f (%llu pictures)\n",
@@ -1128,6 +1133,7 @@ VVR_API void vvr_destroy( vvr_context* c )
   for( void* p : c->stagePool ) hipHostFree( p );
   if( c->prepStage ) hipHostFree( c->prepStage );
   if( c->outStream ) hipStreamDestroy( c->outStream );
+  destroyOutputQueue( c );
   for( auto p : c->syncBuf ) hipFree( p );
   for( auto p : c->leafMaps ) hipFree( p );
   if( c->errHost ) hipHostFree( c->errHost );
@@ -1383,6 +1389,7 @@ VVR_API int vvr_sync( vvr_context* c )
   for( int id : ids ) { const int r = finishJob( c, id ); if( r != VVR_OK && rc == VVR_OK ) rc = r; }
   if( rc != VVR_OK ) return rc;
   for( auto s : c->streams ) HIPCHK( c, hipStreamSynchronize( s ) );
+  if( c->outQStream ) HIPCHK( c, hipStreamSynchronize( c->outQStream ) );      // requests of the output queue in flight (their tickets stay)
   // (a wait of the intra stage that gave up fails the picture's own job: completeLocked reads the job's error word - vvr_wait, vvr_test, vvr_read_* and this call all see it)
   // external events that are complete are forgotten here (the caller may destroy them after this call, vvr.h)
   { std::lock_guard<std::mutex> lk( c->mu ); for( int slot = 0; slot < (int) c->slotExt.size(); slot++ ) pruneExternalEventsLocked( c, slot ); }

@@ -162,6 +162,16 @@ struct FilmGrainParams
   int numComp, bs, scaleShift, bytesPerSample;
 };
 void launch_film_grain( hipStream_t s, const FilmGrainParams& p, void* dst );
+// a frame of the output queue (vvr_output_submit): the windows of up to three planes, one launch, stored into dst + dstOff[c] (256-byte aligned) with
+// the rows back to back in `format` (VVR_OUT_*): 2 bytes or 1 byte per sample, or four samples in five bytes ( s << shift, 10 bits each;
+// w[c] a multiple of 4 then ).  A plane with w[c] == 0 is not part of the launch.  The launch may write up to 31 bytes of padding behind a plane.
+struct OutputFrameParams
+{
+  const pel_t* src[3]; int stride[3], w[3], h[3]; size_t dstOff[3];
+  int first[3];      // (set by the launcher: first workgroup of every plane)
+  int format, shift;
+};
+void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst );
 void launch_mc_affine( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );
 void launch_mc_rpr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );      // tiles of CUs with a scaled reference picture
 void launch_mc_dmvr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems, int32_t* dmvrOut );

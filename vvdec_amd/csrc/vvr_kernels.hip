@@ -4891,6 +4891,77 @@ void launch_film_grain( hipStream_t s, const FilmGrainParams& p, void* dst )
   hipLaunchKernelGGL( k_film_grain, dim3( total ), dim3( 256 ), 0, s, p, t, (uint8_t*) dst );
 }
 
+// k_output_frame — a frame of the output queue: crop and store of all planes of a request in one launch, in the application's form (16-bit,
+// 8-bit, or vvdecapp's packed 10-bit: _writeComponentToFile, vvdecHelper.h:106-145).  The output of a plane is one stream of samples, rows back to
+// back; a lane owns 16 consecutive samples of it, so that its store is whole and aligned whatever the width: 32 bytes (two 16-byte stores), 16 bytes,
+// or - packed - 5 dwords (four groups of 4 samples x 10 bits).  The 16 samples are one 32-byte piece of a source row (two 16-byte loads, consecutive
+// lanes consecutive pieces) unless the piece straddles the end of a row of a width that is no multiple of 16: those lanes gather sample by sample.
+// The last lane of a plane stores its whole piece: the planes are 256-byte aligned in dst, what lies behind a plane's last sample is padding.
+// No LDS, no scratch: the piece lives in registers.
+struct OfPiece { uint16_t s[16]; };
+typedef uint4 __attribute__(( aligned( 2 ) )) of_uint4_u;      // a 16-byte load from a 2-byte aligned address: one instruction (unaligned access mode)
+__global__ __launch_bounds__( 256 ) void k_output_frame( OutputFrameParams p, uint8_t* __restrict__ dst )
+{
+  const int blk = blockIdx.x, c = blk >= p.first[2] && p.w[2] ? 2 : ( blk >= p.first[1] && p.w[1] ? 1 : 0 );
+  const uint32_t w = p.w[c], n = w * (uint32_t) p.h[c], piece = (uint32_t) ( blk - p.first[c] ) * 256 + threadIdx.x, i0 = piece * 16;
+  if( i0 >= n ) return;
+  const uint32_t r = i0 / w, x = i0 - r * w;
+  const pel_t* __restrict__ row = p.src[c] + (size_t) r * p.stride[c];
+  OfPiece v;
+  if( x + 16 <= w )      // (2-byte aligned in general: the window starts anywhere)
+  {
+    const of_uint4_u* q = (const of_uint4_u*) ( row + x );
+    const uint4 q0 = q[0], q1 = q[1];
+    __builtin_memcpy( &v.s[0], &q0, 16 ); __builtin_memcpy( &v.s[8], &q1, 16 );
+  }
+  else
+  {
+    uint32_t xx = x;
+#pragma unroll
+    for( int k = 0; k < 16; k++ )
+    {
+      v.s[k] = i0 + k < n ? (uint16_t) row[xx] : 0;
+      if( ++xx == w ) { xx = 0; row += p.stride[c]; }
+    }
+  }
+  uint8_t* out = dst + p.dstOff[c];
+  if( p.format == VVR_OUT_PLANAR16 )
+  {
+    uint4 q[2]; __builtin_memcpy( q, &v, 32 );
+    uint4* o = (uint4*) ( out + (size_t) i0 * 2 );
+    o[0] = q[0]; o[1] = q[1];
+  }
+  else if( p.format == VVR_OUT_PLANAR8 )
+  {
+    uint32_t d[4];
+#pragma unroll
+    for( int k = 0; k < 4; k++ ) d[k] = ( v.s[4 * k] & 0xffu ) | ( v.s[4 * k + 1] & 0xffu ) << 8 | ( v.s[4 * k + 2] & 0xffu ) << 16 | (uint32_t) v.s[4 * k + 3] << 24;      // "only narrowing conversions" (vvdecimpl.cpp:853)
+    *(uint4*) ( out + i0 ) = make_uint4( d[0], d[1], d[2], d[3] );
+  }
+  else
+  {
+    uint64_t g[4];
+#pragma unroll
+    for( int k = 0; k < 4; k++ )
+    {
+      const uint64_t s0 = ( v.s[4 * k] << p.shift ) & 0x3ff, s1 = ( v.s[4 * k + 1] << p.shift ) & 0x3ff, s2 = ( v.s[4 * k + 2] << p.shift ) & 0x3ff, s3 = ( v.s[4 * k + 3] << p.shift ) & 0x3ff;
+      g[k] = s0 | s1 << 10 | s2 << 20 | s3 << 30;
+    }
+    uint32_t* o = (uint32_t*) ( out + (size_t) piece * 20 );
+    o[0] = (uint32_t) g[0];
+    o[1] = (uint32_t) ( g[0] >> 32 | g[1] << 8 );
+    o[2] = (uint32_t) ( g[1] >> 24 | g[2] << 16 );
+    o[3] = (uint32_t) ( g[2] >> 16 | g[3] << 24 );
+    o[4] = (uint32_t) ( g[3] >> 8 );
+  }
+}
+void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst )
+{
+  int total = 0;
+  for( int c = 0; c < 3; c++ ) { p.first[c] = total; total += (int) ( ( ( (size_t) p.w[c] * p.h[c] + 15 ) / 16 + 255 ) / 256 ); }
+  if( total ) hipLaunchKernelGGL( k_output_frame, dim3( total ), dim3( 256 ), 0, s, p, (uint8_t*) dst );
+}
+
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in
 __device__ __forceinline__ uint32_t crc_mul( uint32_t a, uint32_t b )
 {

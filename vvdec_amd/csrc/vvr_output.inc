@@ -172,6 +172,29 @@ void launch_film_grain( hipStream_t, const FilmGrainParams& p, void* dst )
     }
   }
 }
+
+// ... and launch_output_frame: the planes' windows row by row in the three formats (k_output_frame)
+void launch_output_frame( hipStream_t, OutputFrameParams p, void* dst )
+{
+  for( int c = 0; c < 3; c++ )
+    for( int r = 0; r < ( p.w[c] ? p.h[c] : 0 ); r++ )
+    {
+      const pel_t* row = p.src[c] + (size_t) r * p.stride[c];
+      uint8_t* out = (uint8_t*) dst + p.dstOff[c];
+      for( int x = 0; x < p.w[c]; x++ )
+      {
+        const size_t i = (size_t) r * p.w[c] + x;
+        if( p.format == VVR_OUT_PLANAR16 ) ( (uint16_t*) out )[i] = (uint16_t) row[x];
+        else if( p.format == VVR_OUT_PLANAR8 ) out[i] = (uint8_t) row[x];
+        else if( ( x & 3 ) == 0 )
+        {
+          uint64_t g = 0;
+          for( int k = 0; k < 4; k++ ) g |= (uint64_t) ( ( (uint16_t) row[x + k] << p.shift ) & 0x3ff ) << ( 10 * k );
+          for( int k = 0; k < 5; k++ ) out[i / 4 * 5 + k] = (uint8_t) ( g >> ( 8 * k ) );
+        }
+      }
+    }
+}
 #endif
 
 extern "C" {
@@ -419,6 +442,321 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
   }
   if( digestLen ) *digestLen = len;
   return VVR_OK;
+}
+
+}   // extern "C"
+
+// =====================================================================================================================
+// output queue: the output stage as a pipeline.  A request is ordered behind its picture's `done` event on the context's output stream,
+// runs there (k_film_grain, k_rescale, k_output_frame as the request needs them), leaves through a ring entry (device scratch + pinned
+// staging) and is collected with its ticket.  Nothing here calls vvr_sync.  The slot is protected the way an external reader's is
+// (vvr_slot_external_event): the entry's `read` event, recorded behind the last kernel of the request, is registered with the slot, so a
+// picture submitted afterwards that overwrites the slot waits for it on the device - not for the copy to the host.
+// k_rescale and k_film_grain reach the packed format and the chained case with at most one extra pass through HBM: they store 16-bit samples
+// into the entry's scratch (`tmp`) and k_output_frame packs from there; into the planar formats they store directly as ever.
+// =====================================================================================================================
+#define VVR_OUT_RING 8
+enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
+struct OutEntry {
+  int state = OQ_FREE, ticket = -1, job = -1, slot = -1, rc = VVR_OK;
+  char* dev = nullptr;  size_t devCap = 0;       // the output as it crosses PCIe: planes at off[], rows back to back
+  char* tmp = nullptr;  size_t tmpCap = 0;       // 16-bit intermediate planes (grained, rescaled) and the grain's random words
+  char* host = nullptr; size_t hostCap = 0;      // pinned: the output (unless it goes straight to the caller's pinned memory), then the words
+  hipEvent_t read = nullptr, done = nullptr;     // behind the last kernel; behind the last copy
+  bool direct = false, queued = false;           // queued: something was enqueued (done has been recorded)
+  int nc = 0, rows[3] = { 0, 0, 0 }; size_t off[3] = { 0, 0, 0 }, rowBytes[3] = { 0, 0, 0 }, dstStride[3] = { 0, 0, 0 }; void* dst[3] = { nullptr, nullptr, nullptr };
+  bool timed = false; PendingTiming timing;
+};
+
+static void destroyOutputQueue( vvr_context* c )
+{
+  if( c->outRing )
+    for( int i = 0; i < VVR_OUT_RING; i++ )
+    {
+      OutEntry& e = c->outRing[i];
+      if( e.dev ) hipFree( e.dev ); if( e.tmp ) hipFree( e.tmp ); if( e.host ) hipHostFree( e.host );
+      if( e.read ) hipEventDestroy( e.read ); if( e.done ) hipEventDestroy( e.done );
+      if( e.timed ) { hipEventDestroy( e.timing.a ); hipEventDestroy( e.timing.b ); }
+    }
+  delete[] c->outRing; c->outRing = nullptr;
+  if( c->outQStream ) { hipStreamDestroy( c->outQStream ); c->outQStream = nullptr; }
+}
+
+namespace {
+int outRefuse( vvr_context* c, const char* why ) { std::lock_guard<std::mutex> lk( c->mu ); c->setError( std::string( "vvr_output_submit: " ) + why ); return VVR_ERR_PARAMETER; }
+size_t outRegion( size_t bytes ) { return alignUp( bytes + 32, 256 ); }      // (k_output_frame stores whole pieces: up to 31 bytes behind a plane)
+int outGrow( char*& p, size_t& cap, size_t need, bool pinned )
+{
+  if( need <= cap ) return VVR_OK;
+  if( p ) { if( pinned ) hipHostFree( p ); else hipFree( p ); }
+  p = nullptr; cap = 0;
+  const size_t want = alignUp( need, 1 << 16 );
+  if( ( pinned ? hipHostMalloc( (void**) &p, want, hipHostMallocDefault ) : hipMalloc( (void**) &p, want ) ) != hipSuccess ) { p = nullptr; return VVR_ERR_DEVICE; }
+  cap = want;
+  return VVR_OK;
+}
+OutEntry* outFind( vvr_context* c, int ticket ) { if( c->outRing && ticket >= 0 ) for( int i = 0; i < VVR_OUT_RING; i++ ) if( c->outRing[i].state != OQ_FREE && c->outRing[i].ticket == ticket ) return &c->outRing[i]; return nullptr; }
+// the request's picture failed (an error that only showed when the picture completed: the intra stage's bounded waits)?  done: the request's own work
+// has finished, so the picture's has.  mu held (released while the picture's host event is waited for when `wait`).
+int outJobStatus( vvr_context* c, int job, std::unique_lock<std::mutex>& lk, bool wait )
+{
+  if( job < 0 ) return VVR_OK;
+  auto it = c->jobs.find( job );
+  if( it == c->jobs.end() ) return VVR_OK;
+  if( !it->second->completed && it->second->state == J_COMMITTED && it->second->doneHost )
+  {
+    hipEvent_t ev = it->second->doneHost;
+    if( wait ) { lk.unlock(); hipEventSynchronize( ev ); lk.lock(); }
+    else if( hipEventQuery( ev ) != hipSuccess ) return VVR_NOT_READY;
+    it = c->jobs.find( job );
+    if( it == c->jobs.end() ) return VVR_OK;
+    if( !it->second->completed ) completeLocked( c, *it->second );
+  }
+  if( it->second->state == J_FAILED ) { c->setError( it->second->err ); return it->second->rc; }
+  return VVR_OK;
+}
+}   // namespace
+
+extern "C" {
+
+VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  // ---- 1. the request
+  if( rq->struct_size != sizeof( vvr_output_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_output_request )" );
+  const int slot = rq->slot, bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
+  if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot" );
+  if( rq->format > VVR_OUT_PACKED10 ) return outRefuse( c, "unknown format" );
+  if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1" );
+  const bool packed = rq->format == VVR_OUT_PACKED10, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
+  const int bps = rq->format == VVR_OUT_PLANAR8 ? 1 : 2;
+  if( rq->format == VVR_OUT_PLANAR8 && bd > 8 ) return outRefuse( c, "8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" );
+  if( packed && bd != 8 && bd != 10 ) return outRefuse( c, "packed 10-bit output needs a bit depth of 8 or 10 (vvdecHelper.h:106-248)" );
+  const DevPlanes d = pictureIn( c, slot );
+  if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, or odd in 4:2:0" );
+  if( grain )
+  {
+    if( !c->grainBank ) return outRefuse( c, "no film grain bank set" );
+    if( bd != 8 && bd != 10 ) return outRefuse( c, "film grain needs a bit depth of 8 or 10 (FilmGrainImpl::set_depth)" );
+    if( w <= 128 ) return outRefuse( c, "film grain needs a frame wider than 128 samples (FilmGrainImpl::add_grain_block)" );
+  }
+  int pw[3], ph[3], ow[3], oh[3]; bool resc[3] = { false, false, false }, anyResc = false;
+  size_t rowBytes[3] = { 0, 0, 0 };
+  for( int k = 0; k < nc; k++ )
+  {
+    const int s = k ? 1 : 0;
+    pw[k] = w >> s; ph[k] = h >> s; ow[k] = scaled ? rq->out_w >> s : pw[k]; oh[k] = scaled ? rq->out_h >> s : ph[k];
+    if( scaled && ( ow[k] <= 0 || oh[k] <= 0 || ow[k] > 8192 || oh[k] > 8192 || pw[k] > 8 * ow[k] || ph[k] > 8 * oh[k] || ow[k] > 8 * pw[k] || oh[k] > 8 * ph[k] ) )
+      return outRefuse( c, "output sides must be 1..8192 and within 1/8 .. 8 times the window's" );
+    resc[k] = ow[k] != pw[k] || oh[k] != ph[k]; anyResc |= resc[k];
+    if( packed && ( ow[k] & 3 ) ) return outRefuse( c, "packed 10-bit output needs plane widths that are multiples of 4 (four samples in five bytes)" );
+    rowBytes[k] = packed ? (size_t) ow[k] / 4 * 5 : (size_t) ow[k] * bps;
+    if( !rq->dst[k] || rq->dst_stride_bytes[k] < rowBytes[k] ) return outRefuse( c, "missing plane or stride below the output's row" );
+  }
+  hipSetDevice( c->device );
+  // ---- 2. a ring entry; the picture has been handed to the device
+  OutEntry* e = nullptr;
+  hipEvent_t jobDone = nullptr; int jobFailed = VVR_OK;
+  std::unique_lock<std::mutex> lk( c->mu );
+  if( !c->outRing ) c->outRing = new OutEntry[VVR_OUT_RING];
+  for( int i = 0; i < VVR_OUT_RING && !e; i++ ) if( c->outRing[i].state == OQ_FREE ) e = &c->outRing[i];
+  if( !e ) { c->setError( "vvr_output_submit: 8 requests in flight (vvr_output_wait retires one)" ); return VVR_ERR_BUSY; }
+  if( !c->outQStream ) HIPCHK( c, hipStreamCreateWithFlags( &c->outQStream, hipStreamNonBlocking ) );
+  if( !e->read ) HIPCHK( c, hipEventCreateWithFlags( &e->read, hipEventDisableTiming ) );
+  if( !e->done ) HIPCHK( c, hipEventCreateWithFlags( &e->done, hipEventDisableTiming ) );
+  hipStream_t s = c->outQStream;
+  if( rq->job >= 0 )
+  {
+    auto it = c->jobs.find( rq->job );
+    if( it != c->jobs.end() )        // (else retired: finished long ago)
+    {
+      {
+        const Job& j = *it->second;
+        const vvr_pic_header* hd = j.q ? &j.q->hdr : ( j.pic.hdr.abi_version ? &j.pic.hdr : nullptr );
+        if( hd && hd->out_slot != slot ) { c->setError( "vvr_output_submit: the job does not reconstruct into this slot (hdr.out_slot)" ); return VVR_ERR_PARAMETER; }
+      }
+      if( !( it->second->state == J_COMMITTED || it->second->completed ) )
+      {
+        if( !rq->blocking ) return VVR_NOT_READY;
+        const int job = rq->job;
+        c->cv.wait( lk, [&]{ auto q = c->jobs.find( job ); return q == c->jobs.end() || q->second->state == J_COMMITTED || q->second->completed; } );
+        it = c->jobs.find( job );
+      }
+      if( it != c->jobs.end() )
+      {
+        if( it->second->state == J_FAILED ) jobFailed = it->second->rc;
+        else
+        {
+          // (the slot's writer is the first of its users: another one means that a later picture into the slot has been handed to the device already)
+          if( !c->slotUsers[slot].empty() && c->slotUsers[slot][0] != rq->job ) { c->setError( "vvr_output_submit: a later picture that overwrites the slot has been submitted already (request a picture's output before the slot's next picture is submitted)" ); return VVR_ERR_PARAMETER; }
+          if( !it->second->completed ) jobDone = it->second->done;
+        }
+      }
+    }
+  }
+  else if( !c->bySeq.empty() )       // pictures still with the workers: who uses the slot is only known once they are committed
+  {
+    if( !rq->blocking ) return VVR_NOT_READY;
+    c->cv.wait( lk, [&]{ return c->bySeq.empty(); } );
+  }
+  if( e->state != OQ_FREE ) { c->setError( "vvr_output_submit: called from two threads at once" ); return VVR_ERR_PARAMETER; }
+  e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
+  e->job = rq->job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->nc = nc;
+  if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
+  if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
+  // ---- the entry's buffers: the output's planes; the 16-bit planes of a grained frame that goes on (A) and of a rescaled plane that is packed (B); the words
+  const bool grainTmp = grain && ( packed || anyResc );
+  size_t total = 0, tmpBytes = 0, offA[3] = { 0, 0, 0 }, offB[3] = { 0, 0, 0 };
+  bool direct = true;
+  for( int k = 0; k < nc; k++ )
+  {
+    e->off[k] = total; e->rowBytes[k] = rowBytes[k]; e->rows[k] = oh[k]; e->dst[k] = rq->dst[k]; e->dstStride[k] = rq->dst_stride_bytes[k];
+    total += outRegion( rowBytes[k] * oh[k] );
+    if( grainTmp ) { offA[k] = tmpBytes; tmpBytes += outRegion( (size_t) pw[k] * ph[k] * 2 ); }
+    if( resc[k] && packed ) { offB[k] = tmpBytes; tmpBytes += outRegion( (size_t) ow[k] * oh[k] * 2 ); }
+    direct = direct && c->pinned.contains( rq->dst[k], (size_t) ( oh[k] - 1 ) * rq->dst_stride_bytes[k] + rowBytes[k] );
+  }
+  const int nbx = ( w + 15 ) / 16, nby = ( h + 15 ) / 16;
+  const size_t wordsBytes = grain ? (size_t) nbx * nby * sizeof( uint32_t ) : 0, wordsOff = tmpBytes, hostWordsOff = direct ? 0 : total;
+  tmpBytes += alignUp( wordsBytes, 256 );
+  const size_t hostBankOff = hostWordsOff + alignUp( wordsBytes, 256 );      // (a bank that changed travels through the entry's pinned memory: the context's copy may change while the upload is in flight)
+  if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostBankOff + ( grain && c->grainBankStale ? sizeof( vvr_film_grain_bank ) : 0 ), true ) != VVR_OK )
+  { c->setError( "vvr_output_submit: out of device or pinned memory" ); return VVR_ERR_DEVICE; }
+  e->direct = direct;
+  // ---- 3. behind the picture (or the slot's users) on the device, 4. the kernels.  mu stays held up to the registration of the `read` event: a
+  // picture committed meanwhile that overwrites the slot must find it
+#define OQCHK( call ) do { hipError_t e_ = ( call ); if( e_ != hipSuccess ) { c->setError( std::string( "vvr_output_submit: " #call ": " ) + hipGetErrorString( e_ ) ); hipStreamSynchronize( s ); return VVR_ERR_DEVICE; } } while( 0 )
+  if( jobDone ) OQCHK( hipStreamWaitEvent( s, jobDone, 0 ) );
+  if( rq->job < 0 )
+    for( int id : c->slotUsers[slot] )
+    {
+      auto it = c->jobs.find( id );
+      if( it != c->jobs.end() && !it->second->completed && it->second->state == J_COMMITTED && it->second->done ) OQCHK( hipStreamWaitEvent( s, it->second->done, 0 ) );
+    }
+  for( hipEvent_t ev : c->slotExt[slot] ) if( ev != e->read ) OQCHK( hipStreamWaitEvent( s, ev, 0 ) );      // (external writers of the slot; readers cost nothing)
+  struct Cur { const pel_t* p; int stride; bool inOut; } cur[3];
+  for( int k = 0; k < nc; k++ ) { const int sh = k ? 1 : 0; cur[k].p = d.p[k] + (size_t) ( y >> sh ) * d.stride[k] + ( x >> sh ); cur[k].stride = d.stride[k]; cur[k].inOut = false; }
+  uint32_t nextSeed = c->grainSeed;
+  if( grain )
+  {
+    uint32_t* words = (uint32_t*) ( e->host + hostWordsOff );
+    nextSeed = grain_words( c->grainSeed, nbx, nby, words );
+    if( !c->grainBankDev ) OQCHK( hipMalloc( &c->grainBankDev, sizeof( vvr_film_grain_bank ) ) );
+    if( c->grainBankStale )
+    {
+      memcpy( e->host + hostBankOff, c->grainBank.get(), sizeof( vvr_film_grain_bank ) );
+      OQCHK( hipMemcpyAsync( c->grainBankDev, e->host + hostBankOff, sizeof( vvr_film_grain_bank ), hipMemcpyHostToDevice, s ) );
+    }
+    OQCHK( hipMemcpyAsync( e->tmp + wordsOff, words, wordsBytes, hipMemcpyHostToDevice, s ) );
+    FilmGrainParams p;
+    for( int k = 0; k < 3; k++ )
+    {
+      p.src[k] = k < nc ? cur[k].p : nullptr; p.stride[k] = d.stride[k]; p.w[k] = w >> ( k ? 1 : 0 ); p.h[k] = h >> ( k ? 1 : 0 );
+      p.dstOff[k] = k < nc ? ( grainTmp ? offA[k] : e->off[k] ) : 0;
+    }
+    p.bank = (const vvr_film_grain_bank*) c->grainBankDev; p.words = (const uint32_t*) ( e->tmp + wordsOff ); p.nbx = nbx;
+    p.numComp = nc; p.bs = bd - 8; p.scaleShift = c->grainBank->shift + 6 - p.bs; p.bytesPerSample = grainTmp ? 2 : bps;
+    launch_film_grain( s, p, grainTmp ? e->tmp : e->dev );
+    for( int k = 0; k < nc; k++ )
+      if( grainTmp ) { cur[k].p = (const pel_t*) ( e->tmp + offA[k] ); cur[k].stride = pw[k]; } else cur[k].inOut = true;
+  }
+  for( int k = 0; k < nc; k++ )
+  {
+    if( !resc[k] ) continue;
+    // (as vvr_read_output_scaled: the component's subsampling, luma always collocated)
+    const bool luma = k == 0;
+    const int cs = luma ? 0 : 1, colX = luma ? 1 : rq->collocated & 1, colY = luma ? 1 : ( rq->collocated >> 1 ) & 1, fracShift = luma ? 4 : 5;
+    RescaleParams p;
+    p.src = cur[k].p; p.stride = cur[k].stride; p.w = pw[k]; p.h = ph[k]; p.outW = ow[k]; p.outH = oh[k];
+    p.luma = luma; p.maxVal = ( 1 << bd ) - 1; p.bytesPerSample = packed ? 2 : bps;
+    int scale;
+    rescale_axis( pw[k], ow[k], cs, colX, fracShift, scale, p.addX, p.shiftX ); p.stepX = scale << cs;
+    rescale_axis( ph[k], oh[k], cs, colY, fracShift, scale, p.addY, p.shiftY ); p.stepY = scale << cs;
+    launch_rescale( s, p, packed ? e->tmp + offB[k] : e->dev + e->off[k] );
+    if( packed ) { cur[k].p = (const pel_t*) ( e->tmp + offB[k] ); cur[k].stride = ow[k]; } else cur[k].inOut = true;
+  }
+  OutputFrameParams fp; memset( &fp, 0, sizeof( fp ) );
+  double frameBytes = 0;
+  for( int k = 0; k < nc; k++ )
+    if( !cur[k].inOut ) { fp.src[k] = cur[k].p; fp.stride[k] = cur[k].stride; fp.w[k] = ow[k]; fp.h[k] = oh[k]; fp.dstOff[k] = e->off[k]; frameBytes += (double) ow[k] * oh[k] * 2 + (double) rowBytes[k] * oh[k]; }
+  fp.format = rq->format; fp.shift = packed ? 10 - bd : 0;
+  if( frameBytes > 0 )
+  {
+    if( c->statsOn && hipEventCreate( &e->timing.a ) == hipSuccess )
+    {
+      if( hipEventCreate( &e->timing.b ) == hipSuccess ) { e->timed = true; e->timing.kernel = K_OUTPUT_FRAME; e->timing.bytes = frameBytes; hipEventRecord( e->timing.a, s ); }
+      else hipEventDestroy( e->timing.a );
+    }
+    launch_output_frame( s, fp, e->dev );
+    if( e->timed ) hipEventRecord( e->timing.b, s );
+  }
+  OQCHK( hipGetLastError() );
+  OQCHK( hipEventRecord( e->read, s ) );
+  c->slotExt[slot].push_back( e->read );
+  e->state = OQ_FLIGHT; e->queued = true;
+  if( grain ) { c->grainBankStale = false; c->grainSeed = nextSeed; }      // (the chain advances at submit, for an accepted request only)
+  const int ticket = e->ticket;
+  lk.unlock();
+  // ---- the result's way to the host: exactly the output's bytes
+  hipError_t ce = hipSuccess;
+  for( int k = 0; k < nc && ce == hipSuccess; k++ )
+  {
+    if( !direct ) ce = hipMemcpyAsync( e->host + e->off[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToHost, s );
+    else if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpyAsync( rq->dst[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToHost, s );
+    else ce = hipMemcpy2DAsync( rq->dst[k], rq->dst_stride_bytes[k], e->dev + e->off[k], rowBytes[k], rowBytes[k], oh[k], hipMemcpyDeviceToHost, s );
+  }
+  if( ce == hipSuccess ) ce = hipEventRecord( e->done, s );
+  if( ce != hipSuccess )
+  {
+    // (the request stays accepted - its kernels have run, the chain has advanced - and fails from vvr_output_test / vvr_output_wait)
+    hipStreamSynchronize( s );
+    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( "vvr_output_submit: copy to the host: " ) + hipGetErrorString( ce ) );
+  }
+#undef OQCHK
+  return ticket;
+}
+
+VVR_API int vvr_output_test( vvr_context* c, int ticket )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  hipSetDevice( c->device );
+  std::unique_lock<std::mutex> lk( c->mu );
+  OutEntry* e = outFind( c, ticket );
+  if( !e ) { c->setError( "vvr_output_test: unknown or retired ticket" ); return VVR_ERR_PARAMETER; }
+  if( e->rc != VVR_OK ) return e->rc;
+  if( e->queued && hipEventQuery( e->done ) != hipSuccess ) return VVR_NOT_READY;
+  return outJobStatus( c, e->job, lk, false );
+}
+
+VVR_API int vvr_output_wait( vvr_context* c, int ticket )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  hipSetDevice( c->device );
+  std::unique_lock<std::mutex> lk( c->mu );
+  OutEntry* e = outFind( c, ticket );
+  if( !e || e->state != OQ_FLIGHT ) { c->setError( "vvr_output_wait: unknown or retired ticket" ); return VVR_ERR_PARAMETER; }
+  e->state = OQ_WAITING;       // (the entry is this thread's now)
+  int rc = e->rc;
+  lk.unlock();
+  if( e->queued && hipEventSynchronize( e->done ) != hipSuccess ) rc = VVR_ERR_DEVICE;
+  lk.lock();
+  if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
+  if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
+  if( e->timed )
+  {
+    float ms = 0; hipEventElapsedTime( &ms, e->timing.a, e->timing.b );
+    c->stats[K_OUTPUT_FRAME].launches++; c->stats[K_OUTPUT_FRAME].ms += ms; c->stats[K_OUTPUT_FRAME].bytes += e->timing.bytes;
+    hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false;
+  }
+  // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
+  if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
+  lk.unlock();
+  if( rc == VVR_OK && e->queued && !e->direct )
+    for( int k = 0; k < e->nc; k++ )
+      for( int r = 0; r < e->rows[k]; r++ ) memcpy( (uint8_t*) e->dst[k] + (size_t) r * e->dstStride[k], e->host + e->off[k] + (size_t) r * e->rowBytes[k], e->rowBytes[k] );
+  lk.lock();
+  e->state = OQ_FREE; e->ticket = -1;
+  return rc;
 }
 
 }   // extern "C"
