@@ -128,7 +128,7 @@ struct Job {
   std::vector<vvr_motion> col;      // collocated motion (VVR_TOOL_COL_MOTION), likewise
   bool handled = false;             // committed (or failed) ahead of its turn: its bySeq entry stays until the commit front passes it
 #ifdef VVR_WATCHDOG
-  double tSubmit = 0, tPrep = 0, tBuilt = 0, tRing = 0, tReady = 0, tCommit0 = 0, tCommit1 = 0; hipEvent_t tlA = nullptr, tlB = nullptr; int tlPoc = 0, tlType = 0; unsigned long long tlSeq = 0;      // developer build: where a picture spends its time on the host
+  double tSubmit = 0, tPrep = 0, tBuilt = 0, tRing = 0, tReady = 0, tCommit0 = 0, tCommit1 = 0; hipEvent_t tlF = nullptr /* in front of the picture's front half (k_prep, k_lf_init) */, tlA = nullptr /* behind its waits */, tlB = nullptr; int tlPoc = 0, tlType = 0; unsigned long long tlSeq = 0;      // developer build: where a picture spends its time on the host
 #endif
 };
 
@@ -254,10 +254,10 @@ static void completeLocked( vvr_context* c, Job& j )
 #ifdef VVR_WATCHDOG
   if( j.tlA && j.tlB && c->tlBase )
   {
-    float a = 0, b = 0; hipEventElapsedTime( &a, c->tlBase, j.tlA ); hipEventElapsedTime( &b, c->tlBase, j.tlB );
-    fprintf( stderr, "[vvr timeline] device seq %3llu poc %4d type %d lane %d: %6.2f .. %6.2f  (base event recorded at host %6.2f)\n", j.tlSeq, j.tlPoc, j.tlType, j.lane, a, b, c->tlBaseHost - c->tl0 );
+    float f = 0, a = 0, b = 0; if( j.tlF ) hipEventElapsedTime( &f, c->tlBase, j.tlF ); hipEventElapsedTime( &a, c->tlBase, j.tlA ); hipEventElapsedTime( &b, c->tlBase, j.tlB );
+    fprintf( stderr, "[vvr timeline] device seq %3llu poc %4d type %d lane %d: front %6.2f  %6.2f .. %6.2f  (base event recorded at host %6.2f)\n", j.tlSeq, j.tlPoc, j.tlType, j.lane, f, a, b, c->tlBaseHost - c->tl0 );
   }
-  if( j.tlA ) { hipEventDestroy( j.tlA ); j.tlA = nullptr; } if( j.tlB ) { hipEventDestroy( j.tlB ); j.tlB = nullptr; }
+  if( j.tlF ) { hipEventDestroy( j.tlF ); j.tlF = nullptr; } if( j.tlA ) { hipEventDestroy( j.tlA ); j.tlA = nullptr; } if( j.tlB ) { hipEventDestroy( j.tlB ); j.tlB = nullptr; }
 #endif
   for( auto& t : j.timings )
   {
@@ -291,7 +291,8 @@ static void completeLocked( vvr_context* c, Job& j )
 // What the committer decides about a picture while it holds mu: its lane, the events of the pictures it has to be ordered behind, its
 // reference planes.  The HIP calls themselves (enqueuePicture) run WITHOUT mu: a launch blocks when the device's queues are full, and the
 // worker threads must be able to go on preparing pictures meanwhile.
-struct CommitPlan { int lane; std::vector<hipEvent_t> waits; RefSet refs; std::vector<int> waitInfo; std::vector<hipEvent_t> outExt /* external events of the output slot this picture waits for */; };
+struct CommitPlan { int lane; std::vector<hipEvent_t> waits; RefSet refs; std::vector<int> waitInfo; std::vector<hipEvent_t> outExt /* external events of the output slot this picture waits for */;
+                    std::vector<hipEvent_t> frontWaits /* what the picture's front half (k_prep, k_lf_init) is ordered behind: see enqueuePicture */; };
 
 // External events of a slot (vvr_slot_external_event) that the device has passed are dropped: nothing has to wait for them any more, and the caller
 // may destroy an event once it is complete and the back-end has been through vvr_sync (vvr.h).  Called with mu held - by vvr_sync ONLY: hipEventQuery says
@@ -344,6 +345,12 @@ static void planCommitLocked( vvr_context* c, Job& job, CommitPlan& plan )
       for( hipEvent_t ev : c->slotExt[slot] ) if( std::find( plan.waits.begin(), plan.waits.end(), ev ) == plan.waits.end() ) { plan.waits.push_back( ev ); plan.waitInfo.push_back( -2 ); plan.waitInfo.push_back( -1 ); }
       for( int k = 0; k < 3; k++ ) plan.refs.p[l * VVR_MAX_REFS + i][k] = c->slots[slot].p[k];
     }
+  // the front half of the picture is launched before these waits (enqueuePicture).  It writes tables of the prepared picture: a handle of vvr_prepare that an
+  // earlier, uncompleted job is still working from (vvr_submit_prepared twice) must not have them rewritten under that job - the front half waits for it, and for
+  // it alone.  (A ring entry has one job at a time.)
+  plan.frontWaits.clear();
+  if( !job.ring )
+    for( auto& kv : c->jobs ) { const Job& j = *kv.second; if( &j != &job && j.q == job.q && !j.completed && j.state == J_COMMITTED && j.lane != lane && j.done ) plan.frontWaits.push_back( j.done ); }
   job.done = takeEvent( c ); job.doneHost = takeEvent( c );
 }
 
@@ -374,48 +381,8 @@ static int enqueuePicture( vvr_context* c, Job& job, const CommitPlan& plan, std
 #ifdef VVR_WATCHDOG
   const double wdB = wdNow(); g_wdPart[0] += wdB - wdA; g_wdPartMax[0] = std::max( g_wdPartMax[0], wdB - wdA );
 #endif
-#ifdef VVR_WATCHDOG
-  for( size_t wi = 0; wi < plan.waits.size(); wi++ )
-  {
-    const double w0 = wdNow(); HIPCHK( c, hipStreamWaitEvent( s, plan.waits[wi], 0 ) ); const double w = wdNow() - w0;
-    if( w > 0.5 ) fprintf( stderr, "[vvr] slow wait: picture %d (type %d, lane %d) wait %zu of %zu on job %d (type %d, lane %d): %.2f ms\n", job.id, (int) h.slice_type, lane, wi, plan.waits.size(), plan.waitInfo[2 * wi] >> 4, ( plan.waitInfo[2 * wi] >> 2 ) & 3, plan.waitInfo[2 * wi + 1], w );
-  }
-#else
-  for( hipEvent_t ev : plan.waits ) HIPCHK( c, hipStreamWaitEvent( s, ev, 0 ) );      // (a picture that cannot be ordered behind its references must not run)
-#endif
-#ifdef VVR_WATCHDOG
-  const double wdC = wdNow(); g_wdPart[1] += wdC - wdB; g_wdPartMax[1] = std::max( g_wdPartMax[1], wdC - wdB );
-  // VVR_TIMELINE: when the picture's kernels start and end on the device, relative to an event recorded with the first commit of a burst
-  static const bool tlOn = getenv( "VVR_TIMELINE" ) != nullptr;
-  if( tlOn && job.ring )
-  {
-    if( job.tSubmit - c->tl0 > 50 )
-    {
-      static hipStream_t tlStream = nullptr; if( !tlStream ) hipStreamCreate( &tlStream );      // (an idle stream: the event completes when it is recorded)
-      c->tl0 = job.tSubmit; hipEventCreate( &c->tlBase ); hipEventRecord( c->tlBase, tlStream ); c->tlBaseHost = wdNow();
-      fprintf( stderr, "[vvr timeline] ---- (host: ms since the first submit of the burst; device: ms since the base event)\n" );
-    }
-    hipEventCreate( &job.tlA ); hipEventCreate( &job.tlB ); job.tlPoc = h.poc; job.tlType = h.slice_type; job.tlSeq = job.seq;
-    hipEventRecord( job.tlA, s );
-  }
-#endif
-  job.errWord = c->errHost + ( (unsigned) job.id % VVR_ERR_WORDS ); *job.errWord = 0;
-  const RefSet& refs = plan.refs;
-  DevPlanes A = c->slots[h.out_slot], B = c->scratchB[lane], R = c->scratchR[lane];
-  // the picture's own size (it may be smaller than the context's pictures: it lies in the top left corner of its slot and of the scratch planes)
-  for( int k = 0; k < 3; k++ ) { const int w = k ? h.width >> 1 : h.width, hh = k ? h.height >> 1 : h.height; A.w[k] = B.w[k] = R.w[k] = w; A.h[k] = B.h[k] = R.h[k] = hh; }
-  // SAO and ALF in one pass (k_sao_alf): the picture is reconstructed and deblocked in the lane's scratch picture, the pass writes the DPB slot; else
-  // everything up to SAO works in the slot, SAO writes the scratch picture and ALF the slot (the reference's m_fltBuf round trip)
   const int stopAfter = c->cfg.stop_after;       // conformance aid: vvr_config.stop_after
-  const bool sao = ( h.tool_flags & ( VVR_TOOL_SAO_LUMA | VVR_TOOL_SAO_CHROMA ) ) != 0 && stopAfter != 1 && stopAfter != 2;
-  const bool alf = ( h.tool_flags & VVR_TOOL_ALF ) != 0 && stopAfter == 0;
-  const bool fused = ( sao || alf ) && sao_alf_fused( q->pic );
-  // With the fused SAO + ALF pass (scratch -> slot) behind them the two deblocking passes run out of place, a tile per workgroup: vertical edges slot -> scratch
-  // picture (the inverse luma mapping in the load), horizontal edges scratch picture -> the residual planes (free once the picture is reconstructed), SAO + ALF from
-  // there into the slot.  Without deblocking: reconstructed in the scratch picture.
-  const bool dbOn = !( h.tool_flags & VVR_TOOL_DEBLOCK_OFF ) && stopAfter != 1;
-  const bool hop = fused && dbOn;
-  const DevPlanes P = ( fused && !hop ) ? B : A;
+  const bool dbOn = !( h.tool_flags & VVR_TOOL_DEBLOCK_OFF ) && stopAfter != 1;      // (deblocking: see below)
   auto timedOn = [&]( int k, hipStream_t st, double algoBytes, auto&& fn )
   {
 #ifdef VVR_WATCHDOG
@@ -432,10 +399,33 @@ static int enqueuePicture( vvr_context* c, Job& job, const CommitPlan& plan, std
 #endif
   };
   auto timed = [&]( int k, auto&& fn ) { timedOn( k, s, q->bytes[k], fn ); };
-  // INTER stage: prediction of every inter CU, then residual add (DecLibRecon.cpp:831-874)
-  // (the four launches write disjoint tiles.  Running them side by side on extra streams of the lane, forked and joined with events, was measured:
-  // device-only throughput fell from 1870 to 1240 pictures/s with 4 lanes, to 970 with 8 - the cross-stream waits cost more than the overlap gives)
-  // (the tiles of plain, BDOF and DMVR CUs are written on the device from the CU records: the host only counted them)
+#ifdef VVR_WATCHDOG
+  // VVR_TIMELINE: when the picture's kernels start and end on the device, relative to an event recorded with the first commit of a burst
+  static const bool tlOn = getenv( "VVR_TIMELINE" ) != nullptr;
+  if( tlOn && job.ring )
+  {
+    if( job.tSubmit - c->tl0 > 50 )
+    {
+      static hipStream_t tlStream = nullptr; if( !tlStream ) hipStreamCreate( &tlStream );      // (an idle stream: the event completes when it is recorded)
+      c->tl0 = job.tSubmit; hipEventCreate( &c->tlBase ); hipEventRecord( c->tlBase, tlStream ); c->tlBaseHost = wdNow();
+      fprintf( stderr, "[vvr timeline] ---- (host: ms since the first submit of the burst; device: ms since the base event)\n" );
+    }
+    hipEventCreate( &job.tlF ); hipEventCreate( &job.tlA ); hipEventCreate( &job.tlB ); job.tlPoc = h.poc; job.tlType = h.slice_type; job.tlSeq = job.seq;
+    hipEventRecord( job.tlF, s );         // (tlA: behind the waits, below)
+  }
+#endif
+  // ---- The front half of the picture, IN FRONT OF the waits for its references and slot hazards: k_prep and k_lf_init work from the picture's own uploaded
+  // records alone, so they run while the picture still waits - behind an IRAP every level of the B pyramid is alone on the device, and its 0.06 ms of
+  // tables were on the chain.  Checked in the kernels:
+  //   * written: q->lfCell, lfCellC, lfMv, lfRef, lfpDev[0..1] (prep_lf_maps, k_lf_init), q->mcDev, bdofItems, dmvrItems (prep_expand_mc) - room behind the
+  //     uploaded image in the ring entry's or the handle's blob - and c->leafMaps[lane] with its ticket (prep_intra_mark).  The lane's maps are only touched by
+  //     kernels of this lane (k_intra_leaf leaves them zero), which the stream orders.  A ring entry gets its next picture when its owner has completed.
+  //   * a vvr_prepare handle can be submitted again while an earlier job of it is in flight: the tables are that job's too.  plan.frontWaits holds the `done`
+  //     events of such jobs on other lanes (planCommitLocked) - the front half is ordered behind them, whatever the bytes it would write.
+  //   * read: pic.hdr, pic.cu, pic.tu, the host's lists (mcCus, lfSb, the intra and residual items), the CTU maps of slices / tiles / subpictures and the cell
+  //     records written just before - all inside the picture's own image.  No plane, no DPB slot, no collocated motion, no delta MV of another picture
+  //     (the filter sees the motion of the CU records, not the refined one).
+  for( hipEvent_t ev : plan.frontWaits ) HIPCHK( c, hipStreamWaitEvent( s, ev, 0 ) );
   {
     PrepWork w;
     if( q->numMcCus ) { w.mcCus = q->mcCus; w.numMcCus = q->numMcCus; w.plain = q->mcDev; w.bdof = q->bdofItems; w.dmvr = q->dmvrItems; }
@@ -445,6 +435,38 @@ static int enqueuePicture( vvr_context* c, Job& job, const CommitPlan& plan, std
   }
   // LF_INIT (DecLibRecon.cpp:807-829): the edge parameters of the deblocking passes from the CU / TU records, where the caller leaves them to the back-end
   if( q->lfpOnDevice && dbOn ) timed( K_LF_INIT, [&]{ launch_lf_init( s, q->pic, q->numCu, q->numTu, q->lfCell, q->lfCellC, q->lfMv, q->lfRef, q->lfSb, q->numLfSb, q->lfpDev[0], q->lfpDev[1] ); } );
+#ifdef VVR_WATCHDOG
+  for( size_t wi = 0; wi < plan.waits.size(); wi++ )
+  {
+    const double w0 = wdNow(); HIPCHK( c, hipStreamWaitEvent( s, plan.waits[wi], 0 ) ); const double w = wdNow() - w0;
+    if( w > 0.5 ) fprintf( stderr, "[vvr] slow wait: picture %d (type %d, lane %d) wait %zu of %zu on job %d (type %d, lane %d): %.2f ms\n", job.id, (int) h.slice_type, lane, wi, plan.waits.size(), plan.waitInfo[2 * wi] >> 4, ( plan.waitInfo[2 * wi] >> 2 ) & 3, plan.waitInfo[2 * wi + 1], w );
+  }
+#else
+  for( hipEvent_t ev : plan.waits ) HIPCHK( c, hipStreamWaitEvent( s, ev, 0 ) );      // (a picture that cannot be ordered behind its references must not run)
+#endif
+#ifdef VVR_WATCHDOG
+  const double wdC = wdNow(); g_wdPart[1] += wdC - wdB; g_wdPartMax[1] = std::max( g_wdPartMax[1], wdC - wdB );
+  if( job.tlA ) hipEventRecord( job.tlA, s );
+#endif
+  job.errWord = c->errHost + ( (unsigned) job.id % VVR_ERR_WORDS ); *job.errWord = 0;
+  const RefSet& refs = plan.refs;
+  DevPlanes A = c->slots[h.out_slot], B = c->scratchB[lane], R = c->scratchR[lane];
+  // the picture's own size (it may be smaller than the context's pictures: it lies in the top left corner of its slot and of the scratch planes)
+  for( int k = 0; k < 3; k++ ) { const int w = k ? h.width >> 1 : h.width, hh = k ? h.height >> 1 : h.height; A.w[k] = B.w[k] = R.w[k] = w; A.h[k] = B.h[k] = R.h[k] = hh; }
+  // SAO and ALF in one pass (k_sao_alf): the picture is reconstructed and deblocked in the lane's scratch picture, the pass writes the DPB slot; else
+  // everything up to SAO works in the slot, SAO writes the scratch picture and ALF the slot (the reference's m_fltBuf round trip)
+  const bool sao = ( h.tool_flags & ( VVR_TOOL_SAO_LUMA | VVR_TOOL_SAO_CHROMA ) ) != 0 && stopAfter != 1 && stopAfter != 2;
+  const bool alf = ( h.tool_flags & VVR_TOOL_ALF ) != 0 && stopAfter == 0;
+  const bool fused = ( sao || alf ) && sao_alf_fused( q->pic );
+  // With the fused SAO + ALF pass (scratch -> slot) behind them the two deblocking passes run out of place, a tile per workgroup: vertical edges slot -> scratch
+  // picture (the inverse luma mapping in the load), horizontal edges scratch picture -> the residual planes (free once the picture is reconstructed), SAO + ALF from
+  // there into the slot.  Without deblocking: reconstructed in the scratch picture.
+  const bool hop = fused && dbOn;
+  const DevPlanes P = ( fused && !hop ) ? B : A;
+  // INTER stage: prediction of every inter CU, then residual add (DecLibRecon.cpp:831-874)
+  // (the four launches write disjoint tiles.  Running them side by side on extra streams of the lane, forked and joined with events, was measured:
+  // device-only throughput fell from 1870 to 1240 pictures/s with 4 lanes, to 970 with 8 - the cross-stream waits cost more than the overlap gives)
+  // (the tiles of plain, BDOF and DMVR CUs are written on the device from the CU records: the host only counted them)
   if( q->numMc + q->numMcDev ) timedOn( K_MC, s, q->bytes[K_MC] - q->bytesBdof, [&]{ launch_mc( s, q->pic, refs, P, q->mcItems, q->numMc, q->mcDev, q->numMcDev, 0 ); } );
   if( q->numBdofItems ) timedOn( K_MC, s, q->bytesBdof, [&]{ launch_mc( s, q->pic, refs, P, nullptr, 0, q->bdofItems, q->numBdofItems, 1 ); } );
   if( q->numDmvrItems )
@@ -831,6 +853,8 @@ struct WorkerHelpers : HostHelpers
   bool announced = false;               // this worker counts in c->partsComing (it took an I picture and has not published the parts yet)
   WorkerHelpers( vvr_context* c_, PrepScratch*& spare_ ) : c( c_ ), spare( spare_ ) {}
   int width() const override { return c->cfg.host_threads; }
+  bool again = false;                   // partsFollow: this run() is not the picture's last
+  void partsFollow() override { again = true; }
   void notInParts() override { if( announced ) { std::lock_guard<std::mutex> lk( c->mu ); c->partsComing--; announced = false; c->cv.notify_all(); } }
   void run( int n, PrepScratch& own, const std::function<void( int, PrepScratch& )>& fn ) override
   {
@@ -844,7 +868,9 @@ struct WorkerHelpers : HostHelpers
         auto task = [&st, &fn, part]( PrepScratch& R ) { fn( part, R ); std::lock_guard<std::mutex> l2( st.mu ); st.remaining--; st.cv.notify_all(); };      // (notified under the lock: `st` lives on the caller's stack and is gone once the caller has seen remaining == 0)
         if( first ) c->subtasks.push_front( task ); else c->subtasks.push_back( task );
       }
-      if( announced ) { c->partsComing--; announced = false; }
+      // (an I picture's second phase follows its first after a join of a few microseconds: the others wait for its parts in between as they did for the first ones)
+      if( again ) { if( !announced ) { c->partsComing++; announced = true; } again = false; }
+      else if( announced ) { c->partsComing--; announced = false; }
       c->cv.notify_all();
     }
     fn( 0, own );

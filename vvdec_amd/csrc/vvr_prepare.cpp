@@ -50,6 +50,21 @@ struct UnitH { uint32_t comp, ctu, i0, i1, iA = 0; bool hasCs = false; BBox bb; 
 
 struct Part { const void* src; size_t n, off; bool direct; };
 
+// What one band of CTU rows of an I picture leaves with the picture's owner between the two parallel phases of buildIntraInParts: its lists (taken over
+// from the scratch that built them: that scratch may serve another band next), the per-block work of the unit and item tables done on them, its totals -
+// and, from the join, where its share of every table of the picture starts.  Kept from picture to picture (no allocation in the steady state).
+struct IntraPartOut
+{
+  int rc = VVR_OK; std::string err; uint64_t area[2] = { 0, 0 };
+  std::vector<IntraItem> intra[3];          // blocks per component, coding order
+  std::vector<TbItem> tb[3];
+  std::vector<UnitH> units[3];              // runs of equal CTU; i0 / i1 relative to the band's first block of the component
+  std::vector<uint32_t> im[3];              // block -> its first item, relative to the band's first item of the component (one entry more than blocks)
+  double bytes[K_NUM], bytesBdof = 0, bytesIntraLuma = 0, bytesTb[3];
+  uint32_t blockOff[3], itemOff[3], tbOff[3];
+  double tDone = 0;                         // (developer build) when the band's first phase ended
+};
+
 struct PrepScratch
 {
   // ---- the picture being prepared
@@ -99,6 +114,9 @@ struct PrepScratch
   std::vector<std::pair<uint32_t, uint32_t>> csProdRange;   // per VPDU: the luma blocks that produce that neighbourhood (range of csProdPool), looked up on first use
   std::vector<uint32_t> csProdPool;
   std::vector<IntraUnit> unitsDev;
+  std::vector<IntraPartOut> partOut;        // (buildIntraInParts) per band of CTU rows
+  bool fromParts = false;                   // (buildIntraInParts) the units are formed and the items written band by band: formUnits / emitUnitTable do the unit-level work only
+  double phaseT[4] = { 0, 0, 0, 0 };        // (developer builds, VVR_PHASES / VVR_TIMELINE) buildIntraInParts: start, last band through phase 1, joined, done
   int intraWorkgroups = 0, intraWorkgroupsChroma = 0, numLumaUnits = 0;
   std::vector<IntraItem> resiAdd;          // residual-add blocks (inter chroma blocks with LMCS chroma residual scaling): k_resi_add, outside the stage's dependency graph
   size_t intraChunk = (size_t) 1 << 30;      // blocks per unit of a long intra cluster (formUnits); off: measured, no gain
@@ -140,7 +158,7 @@ struct PrepScratch
     lfSb.clear(); lfpOnDevice = ( h.tool_flags & VVR_TOOL_LFP_ON_DEVICE ) && !( h.tool_flags & VVR_TOOL_DEBLOCK_OFF );
     mcCus.clear(); devTiles[0] = devTiles[1] = devTiles[2] = 0;
     for( int k = 0; k < 3; k++ ) { tb[k].clear(); intra[k].clear(); itemH[k].clear(); prodPool[k].clear(); }
-    resiAdd.clear(); intraAll.clear(); units.clear(); unitsDev.clear(); csVpduV.clear(); intraFine = false;
+    resiAdd.clear(); intraAll.clear(); units.clear(); unitsDev.clear(); csVpduV.clear(); intraFine = false; fromParts = false;
     ctuStartV.assign( 3 * (size_t) ( numCtu + 1 ), 0 );
     for( double& b : bytes ) b = 0;
     bytesBdof = bytesIntraLuma = 0; bytesTb[0] = bytesTb[1] = bytesTb[2] = 0;
@@ -234,6 +252,7 @@ struct PrepScratch
   int emitLeafItems( std::string& err );
   int buildWorkLists( std::string& err, uint32_t cu0 = 0, uint32_t cu1 = 0xffffffffu );
   int buildInParts( const vvr_config& cfg, HostHelpers& helpers, bool validate, std::string& err );
+  int buildIntraInParts( HostHelpers& helpers, bool validate, std::string& err );
   int formUnits();
   int groupUnits();
   int emitUnitTable( std::string& err );
@@ -1576,6 +1595,16 @@ int PrepScratch::groupUnits()
   return VVR_OK;
 }
 
+// the bands of rows a block of component k becomes (log2): see emitUnitTable
+static inline int bandsLog2( const IntraItem& src, int k )
+{
+  const int samples = 1 << ( src.lw + src.lh );
+  const bool split = samples > IT_SPLIT_SAMPLES && src.mode <= 66 && ( k || ( !( src.flags & IT_F_MIP ) && ( src.flags & IT_F_ISP ) != IT_F_ISP ) );
+  int lp = 0;
+  if( split ) while( lp < IT_MAX_LPARTS && ( samples >> lp ) > IT_SPLIT_SAMPLES ) lp++;
+  return lp;
+}
+
 int PrepScratch::emitUnitTable( std::string& err )
 {
   // one item array for the three components; active (component, CTU) pairs in raster order.  A block of more than IT_SPLIT_SAMPLES samples
@@ -1583,14 +1612,8 @@ int PrepScratch::emitUnitTable( std::string& err )
   // with one wavefront, the bands of a block with several at once (they read the same reference samples and write disjoint rows, so
   // band p is independent of the p items before it) - a band of 256 samples is one round of four samples per lane
   // (two passes: where every block's items start, then the items - written in place, no growing vector on the serial tail of an I picture's host stage)
-  auto bandsLog2 = [&]( const IntraItem& src, int k )
-  {
-    const int samples = 1 << ( src.lw + src.lh );
-    const bool split = samples > IT_SPLIT_SAMPLES && src.mode <= 66 && ( k || ( !( src.flags & IT_F_MIP ) && ( src.flags & IT_F_ISP ) != IT_F_ISP ) );
-    int lp = 0;
-    if( split ) while( lp < IT_MAX_LPARTS && ( samples >> lp ) > IT_SPLIT_SAMPLES ) lp++;
-    return lp;
-  };
+  // (an I picture built band by band has its items in place already - buildIntraInParts, the same two passes per band - and itemMap filled in where units begin and end)
+  if( !fromParts )
   {
     uint32_t at = (uint32_t) intraAll.size();
     for( int k = 0; k < 3; k++ )
@@ -1603,7 +1626,7 @@ int PrepScratch::emitUnitTable( std::string& err )
     }
     intraAll.resize( at );
   }
-  for( int k = 0; k < 3; k++ )
+  for( int k = 0; k < 3 && !fromParts; k++ )
   {
     const size_t n = intra[k].size();
     const uint32_t* im = itemMap[k].data(); const IntraItem* srcs = intra[k].data(); IntraItem* out = intraAll.data();
@@ -1841,6 +1864,7 @@ void PrepScratch::layout( PinnedRanges* pinned )
 int PrepScratch::buildInParts( const vvr_config& cfg, HostHelpers& helpers, bool validate, std::string& err )
 {
   (void) cfg;
+  if( allIntraCus && intraChunk == (size_t) 1 << 30 ) return buildIntraInParts( helpers, validate, err );      // (the developer's piece length keeps the general way through formUnits)
   const int n = std::min( helpers.width(), ctusY );
   struct Shared { std::mutex mu; std::condition_variable cv; int turn = 0; int rc = VVR_OK; std::string err; uint64_t area[2] = { 0, 0 }; } sh;
   const vvr_picture* pic = p;
@@ -1949,6 +1973,190 @@ int PrepScratch::buildInParts( const vvr_config& cfg, HostHelpers& helpers, bool
   return VVR_OK;
 }
 
+static inline double phaseNow() { return std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now().time_since_epoch() ).count(); }
+
+// An I picture without intra block copy (every CU an intra CU): the whole host stage in two parallel phases over the bands of CTU rows, with the per-block
+// work of the unit and item tables inside the bands.  The next GOP waits for this picture, and what one thread did behind the bands - a pass over all blocks
+// for the units, two for the items, the appending of every band's lists in band order under a mutex - was 0.9 ms of that chain at 4K (66 000 items).
+//   phase 1  a band builds its lists (buildWorkLists), forms the units of its CTUs - runs of equal CTU, as formUnits does it for such pictures: a band is
+//            whole CTU rows, no run crosses it - and counts the items of every block after the split into bands of rows; the lists stay with the owner
+//   join     one thread, per BAND not per block: where every band's share of every table starts, the units of all bands in picture-wide numbering
+//   phase 2  a band writes its items and transform blocks where they belong; meanwhile the caller does what needs the whole picture, on 1 500 units rather
+//            than 66 000 items: dependencies on the neighbouring CTUs, rank, order, workgroup count, the device's unit table (formUnits, emitUnitTable)
+// No band waits for another.  What the device is sent is byte for byte what one thread produces.
+int PrepScratch::buildIntraInParts( HostHelpers& helpers, bool validate, std::string& err )
+{
+  const int n = std::min( helpers.width(), ctusY );
+  const vvr_picture* pic = p;
+  PrepScratch* owner = this;
+  if( partOut.size() < (size_t) n ) partOut.resize( (size_t) n );
+#if defined( VVR_WATCHDOG ) || defined( VVR_DEV_ENV )
+  phaseT[0] = phaseNow();
+#endif
+  helpers.partsFollow();
+  helpers.run( n, *this, [&]( int part, PrepScratch& R )
+  {
+    PrepScratch& O = *owner;
+    IntraPartOut& PO = O.partOut[(size_t) part];
+    const int row0 = (int) ( (int64_t) O.ctusY * part / n ), row1 = (int) ( (int64_t) O.ctusY * ( part + 1 ) / n );
+    const uint32_t cu0 = pic->ctu_first_cu[(size_t) row0 * O.ctusX], cu1 = pic->ctu_first_cu[(size_t) row1 * O.ctusX];
+    int rc = VVR_OK; std::string e;
+    PO.area[0] = PO.area[1] = 0;
+    if( cu0 > cu1 || cu1 > pic->num_cu ) { rc = VVR_ERR_PARAMETER; e = "ctu_first_cu is not ascending"; }
+    if( rc == VVR_OK && validate ) rc = validate_records_range( pic, cu0, cu1, PO.area, e );
+    if( rc == VVR_OK )
+    {
+      if( &R != owner ) { R.begin( pic ); rc = R.beginMaps( owner ); }
+      R.partCtu0 = (uint32_t) row0 * O.ctusX; R.partCtu1 = (uint32_t) row1 * O.ctusX;
+      R.partTopY = 0; R.partBad = false; R.pending.clear();
+      if( rc == VVR_OK ) rc = R.buildWorkLists( e, cu0, cu1 );
+      R.partCtu0 = 0; R.partCtu1 = 0xffffffffu;
+      // (intra CUs only: nothing of the inter stage, no residual-add blocks)
+      if( rc == VVR_OK && !( R.mc.empty() && R.mcBdof.empty() && R.mcDmvr.empty() && R.mcAff.empty() && R.mcRpr.empty() && R.mcCus.empty() && R.lfSb.empty() && R.resiAdd.empty() ) )
+        { rc = VVR_ERR_UNSPECIFIED; e = "internal: inter-stage work in a picture of intra CUs"; }
+    }
+    if( rc == VVR_OK )
+    {
+      for( int k = 0; k < 3; k++ )
+      {
+        std::vector<UnitH>& U = PO.units[k]; U.clear();
+        std::vector<uint32_t>& im = PO.im[k];
+        const size_t nb = k < O.ncomp ? R.intra[k].size() : 0;
+        im.resize( nb + 1 );
+        const ItemH* IH = R.itemH[k].data(); const IntraItem* IT = R.intra[k].data();
+        // the runs of equal CTU with their bounding boxes (formUnits), and where every block's items start (emitUnitTable) while the block is at hand
+        uint32_t at = 0;
+        for( size_t i = 0; i < nb; )
+        {
+          UnitH u; u.comp = (uint32_t) k; u.ctu = IH[i].ctu; u.i0 = (uint32_t) i;
+          for( ; i < nb && IH[i].ctu == u.ctu; i++ )
+          {
+            const BBox& b = IH[i].bb;
+            u.bb.y0 = std::min( u.bb.y0, b.y0 ); u.bb.y1 = std::max( u.bb.y1, b.y1 ); u.bb.c0 = std::min( u.bb.c0, b.c0 ); u.bb.c1 = std::max( u.bb.c1, b.c1 );
+            if( k && ( IT[i].flags & IT_F_CSCALE ) ) u.hasCs = true;
+            im[i] = at; at += 1u << bandsLog2( IT[i], k );
+          }
+          u.i1 = (uint32_t) i; u.iA = u.i0;
+          U.push_back( std::move( u ) );
+        }
+        im[nb] = at;
+        // the lists change hands (the scratch gets the band's buffers of the picture before: cleared when it begins its next picture)
+        if( k < O.ncomp ) PO.intra[k].swap( R.intra[k] ); else PO.intra[k].clear();
+        PO.tb[k].swap( R.tb[k] );
+      }
+      memcpy( PO.bytes, R.bytes, sizeof( PO.bytes ) ); PO.bytesBdof = R.bytesBdof; PO.bytesIntraLuma = R.bytesIntraLuma; for( int k = 0; k < 3; k++ ) PO.bytesTb[k] = R.bytesTb[k];
+      // per CTU and per VPDU: every band has its own range of the owner's tables
+      if( &R != owner )
+      {
+        for( uint32_t c = (uint32_t) row0 * O.ctusX; c < (uint32_t) row1 * O.ctusX; c++ ) O.fastCtu[c] = R.fastCtu[c];
+        if( O.cscale )
+        {
+          const int nv = 1 << ( O.h.log2_ctu - O.vpduLog2 );
+          const size_t v0 = (size_t) row0 * nv * O.vpdusX, v1 = std::min( (size_t) row1 * nv, (size_t) O.vpdusY ) * O.vpdusX;
+          if( v1 > v0 ) memcpy( &O.csVpduV[v0], &R.csVpduV[v0], sizeof( uint32_t ) * ( v1 - v0 ) );
+        }
+      }
+    }
+    PO.rc = rc; PO.err.swap( e );
+#if defined( VVR_WATCHDOG ) || defined( VVR_DEV_ENV )
+    PO.tDone = phaseNow();
+#endif
+  } );
+  // ---- join: the first error in band order; where every band's share starts; the units in picture-wide numbering, component by component as formUnits lists them
+  uint64_t area[2] = { 0, 0 };
+  for( int part = 0; part < n; part++ )
+  {
+    IntraPartOut& PO = partOut[(size_t) part];
+    if( PO.rc != VVR_OK ) { helpers.notInParts(); err = PO.err; return PO.rc; }
+    area[0] += PO.area[0]; area[1] += PO.area[1];
+  }
+#if defined( VVR_WATCHDOG ) || defined( VVR_DEV_ENV )
+  phaseT[1] = phaseT[0]; for( int part = 0; part < n; part++ ) phaseT[1] = std::max( phaseT[1], partOut[(size_t) part].tDone );
+#endif
+  {
+    uint32_t items = 0;
+    for( int k = 0; k < 3; k++ )
+    {
+      uint32_t blocks = 0, tbs = 0;
+      for( int part = 0; part < n; part++ )
+      {
+        IntraPartOut& PO = partOut[(size_t) part];
+        PO.blockOff[k] = blocks; PO.itemOff[k] = items; PO.tbOff[k] = tbs;
+        blocks += (uint32_t) PO.intra[k].size(); items += PO.im[k].back(); tbs += (uint32_t) PO.tb[k].size();
+      }
+      intra[k].clear();                      // (the blocks stay with the bands: nothing behind this reads them; formUnits finds no block to form units of)
+      itemMap[k].resize( (size_t) blocks + 1 );
+      tb[k].resize( tbs );
+      for( int part = 0; part < n; part++ )
+      {
+        const IntraPartOut& PO = partOut[(size_t) part];
+        for( const UnitH& pu : PO.units[k] )
+        {
+          // (emitUnitTable asks for the first item of a unit's first block and of the block behind its last one: nothing else of the map is filled in)
+          itemMap[k][PO.blockOff[k] + pu.i0] = PO.itemOff[k] + PO.im[k][pu.i0]; itemMap[k][PO.blockOff[k] + pu.i1] = PO.itemOff[k] + PO.im[k][pu.i1];
+          units.push_back( pu );
+          UnitH& u = units.back(); u.i0 += PO.blockOff[k]; u.i1 += PO.blockOff[k]; u.iA = u.i0;
+        }
+      }
+    }
+    intraAll.resize( items );
+    // (in band order, the owner's own band first: the sums the single thread arrives at)
+    for( int part = 0; part < n; part++ )
+    {
+      const IntraPartOut& PO = partOut[(size_t) part];
+      for( int k = 0; k < K_NUM; k++ ) bytes[k] = part ? bytes[k] + PO.bytes[k] : PO.bytes[k];
+      bytesIntraLuma = part ? bytesIntraLuma + PO.bytesIntraLuma : PO.bytesIntraLuma; bytesBdof = part ? bytesBdof + PO.bytesBdof : PO.bytesBdof;
+      for( int k = 0; k < 3; k++ ) bytesTb[k] = part ? bytesTb[k] + PO.bytesTb[k] : PO.bytesTb[k];
+    }
+    fromParts = true;
+  }
+#if defined( VVR_WATCHDOG ) || defined( VVR_DEV_ENV )
+  phaseT[2] = phaseNow();
+#endif
+  // ---- phase 2: task 0 (the caller) the unit-level work, task 1 + b the items and transform blocks of band b
+  int rcUnits = VVR_OK; std::string errUnits;
+  helpers.run( n + 1, *this, [&]( int task, PrepScratch& )
+  {
+    PrepScratch& O = *owner;
+    if( task == 0 )
+    {
+      if( ( rcUnits = O.formUnits() ) == VVR_OK && ( rcUnits = O.groupUnits() ) == VVR_OK ) rcUnits = O.emitUnitTable( errUnits );
+      return;
+    }
+    IntraPartOut& PO = O.partOut[(size_t) task - 1];
+    for( int k = 0; k < 3; k++ )
+    {
+      const size_t nb = PO.intra[k].size();
+      const uint32_t* im = PO.im[k].data(); const IntraItem* srcs = PO.intra[k].data(); IntraItem* out = O.intraAll.data() + PO.itemOff[k];
+      for( size_t bi = 0; bi < nb; bi++ )
+      {
+        const IntraItem& src = srcs[bi];
+        // the blocks before this one that it does not read from, counted in items (emitUnitTable).  They are blocks of its own CTU (buildWorkLists: the CTU-local
+        // cell map), so the count never reaches back over the first block of a band of whole CTU rows.
+        uint32_t indepBlocks = src.comp >> 2;
+        if( indepBlocks > bi ) { if( PO.blockOff[k] ) { PO.rc = VVR_ERR_UNSPECIFIED; PO.err = "internal: a block's independent predecessors reach into the band above"; } indepBlocks = (uint32_t) bi; }
+        const uint32_t indepItems = im[bi] - im[bi - indepBlocks];
+        const int lp = ilog2i( (int) ( im[bi + 1] - im[bi] ) );
+        for( int part = 0; part < ( 1 << lp ); part++ )
+        {
+          IntraItem it = src;
+          it.nTL = (uint8_t) ( ( src.nTL & 1 ) | ( part << 1 ) | ( lp << 4 ) );
+          it.comp = (uint8_t) ( k | ( std::min<uint32_t>( 63, indepItems + part ) << 2 ) );
+          out[im[bi] + part] = it;
+        }
+      }
+      if( !PO.tb[k].empty() ) memcpy( O.tb[k].data() + PO.tbOff[k], PO.tb[k].data(), sizeof( TbItem ) * PO.tb[k].size() );
+    }
+  } );
+#if defined( VVR_WATCHDOG ) || defined( VVR_DEV_ENV )
+  phaseT[3] = phaseNow();
+#endif
+  for( int part = 0; part < n; part++ ) if( partOut[(size_t) part].rc != VVR_OK ) { err = partOut[(size_t) part].err; return partOut[(size_t) part].rc; }
+  if( rcUnits != VVR_OK ) { err = errUnits; return rcUnits; }
+  if( validate ) return validate_cover( p, area, err );
+  return VVR_OK;
+}
+
 int vvr_host_build( const vvr_picture* p, PrepScratch& S, size_t* totalBytes, std::string& err, PinnedRanges* pinned, HostHelpers* helpers, bool validateRecords )
 {
   S.begin( p );
@@ -1963,9 +2171,19 @@ int vvr_host_build( const vvr_picture* p, PrepScratch& S, size_t* totalBytes, st
     if( S.allIntraCus || anyInParts )
     {
       if( ( rc = S.buildInParts( vvr_config(), *helpers, validateRecords, err ) ) != VVR_OK ) return rc;
-      if( S.leaf ) { if( ( rc = S.emitLeafItems( err ) ) != VVR_OK ) return rc; }
+      if( S.fromParts ) {}                   // (an I picture: units and items were part of its two phases)
+      else if( S.leaf ) { if( ( rc = S.emitLeafItems( err ) ) != VVR_OK ) return rc; }
       else if( ( rc = S.formUnits() ) != VVR_OK || ( rc = S.groupUnits() ) != VVR_OK || ( rc = S.emitUnitTable( err ) ) != VVR_OK ) return rc;
       S.layout( pinned );
+#if defined( VVR_WATCHDOG ) || defined( VVR_DEV_ENV )
+      // developer builds: where the host stage of an I picture built in bands spends its time (tools/host_i_picture_stage.py)
+      if( S.fromParts && ( getenv( "VVR_PHASES" ) || getenv( "VVR_TIMELINE" ) ) )
+      {
+        const double t = phaseNow();
+        fprintf( stderr, "[vvr] I picture in bands (ms): phase 1 %.3f, join %.3f, phase 2 and units %.3f, layout %.3f; last band through phase 1 -> built %.3f; stage %.3f\n",
+                 S.phaseT[1] - S.phaseT[0], S.phaseT[2] - S.phaseT[1], S.phaseT[3] - S.phaseT[2], t - S.phaseT[3], t - S.phaseT[1], t - S.phaseT[0] );
+      }
+#endif
       *totalBytes = S.total;
       return VVR_OK;
     }
