@@ -521,6 +521,11 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *            VVR_OUT_PACKED10: vvdecapp's packed output (--pyuv, _writeComponentToFile, vvdecHelper.h:106-145): every row of every plane is
  *            w / 4 * 5 bytes, samples s0..s3 the little-endian 40-bit word s0 | s1 << 10 | s2 << 20 | s3 << 30; a context of 8 bits stores
  *            s << 2 (:201-248).  Refused at bit depth 9 and when the output width of a plane is not a multiple of 4.
+ *            VVR_OUT_NV12 / VVR_OUT_P010: the semi-planar forms display, encode and ML pipelines exchange.  Two planes leave the request: dst[0]
+ *            takes the luma rows, dst[1] the interleaved chroma rows Cb0, Cr0, Cb1, Cr1, ... of 2 * ( out_w >> 1 ) samples, out_h >> 1 of them
+ *            (dst_stride_bytes[1] covers that row; dst[2] and dst_stride_bytes[2] are ignored and may be NULL / 0).  NV12: one byte per sample,
+ *            the sample itself, 8-bit contexts only (VVR_OUT_PLANAR8's refusal).  P010: little-endian 16-bit words, sample << ( 16 - bit_depth ),
+ *            bit depths 8, 9 and 10.  Both are refused in a 4:0:0 context: there is no chroma to interleave.
  *   grain with out_w / out_h: the window is grained at its own size exactly as vvr_read_output_grain does it, the grained frame is then
  *            rescaled exactly as vvr_read_output_scaled rescales a picture, taps clamped to the grained frame (the reference's order:
  *            xAddGrain in xAddPicture, then the application's upscaleFrame).
@@ -532,12 +537,20 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *   dst      when every dst[c] lies in memory of vvr_host_alloc the device copies straight there at the caller's stride and vvr_output_wait
  *            copies nothing; else the rows leave pinned staging inside vvr_output_wait, on the waiting thread.  Either way exactly the
  *            output's bytes cross PCIe.  dst must stay valid until vvr_output_wait has returned.
+ *   dst on the device   when every plane the request uses (dst[0], dst[1] of the semi-planar formats, else all planes) lies wholly inside a
+ *            range of vvr_device_alloc / vvr_device_register, the request is a device request: nothing crosses PCIe, every format is accepted,
+ *            vvr_output_wait copies nothing.  A plane whose rows are back to back (dst_stride_bytes[k] equal to the row's bytes) at a base
+ *            aligned to 32 bytes is stored by the last kernel itself, exactly its bytes; any other plane is laid out at the caller's stride by
+ *            one device-to-device copy.  No byte outside the rows changes.  A plane partly inside a range, and device planes mixed with host
+ *            planes, are refused.  The caller's duty: the destination is memory of the context's device, it is idle when the request is
+ *            submitted, and nothing touches it before the request has completed (vvr_output_wait / vvr_output_test on the host,
+ *            vvr_output_stream_wait on the device).
  * vvr_output_submit: a ticket (>= 2: never VVR_NOT_READY); VVR_ERR_PARAMETER (with a text) for a request that is refused; VVR_ERR_BUSY when 8 requests are in flight;
  *   VVR_NOT_READY (blocking == 0) when `job` has not been handed to the device yet.  A request for a job that failed is accepted and fails with
  *   the job's status from vvr_output_test / vvr_output_wait.  vvr_output_test: VVR_OK (vvr_output_wait returns at once) / VVR_NOT_READY / the
  *   failure; the ticket stays.  vvr_output_wait blocks for THIS request only and retires the ticket.  An unknown or retired ticket:
  *   VVR_ERR_PARAMETER.  vvr_sync also waits for the requests in flight but retires no ticket. */
-enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2 };
+enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2, VVR_OUT_NV12 = 16, VVR_OUT_P010 = 17 };
 typedef struct vvr_output_request {
   uint32_t struct_size;        /* sizeof( vvr_output_request ) */
   int32_t  slot;
@@ -549,12 +562,28 @@ typedef struct vvr_output_request {
   uint8_t  format;             /* VVR_OUT_* */
   uint8_t  grain;              /* 1: the context's bank is added first, one frame of the seed chain (vvr_read_output_grain's rules) */
   uint8_t  blocking;           /* 0: VVR_NOT_READY instead of waiting on the host until `job` has been handed to the device */
-  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0 */
+  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0; dst[2] unused by VVR_OUT_NV12 / VVR_OUT_P010 */
   size_t   dst_stride_bytes[3];
 } vvr_output_request;
 VVR_API int          vvr_output_submit(vvr_context* ctx, const vvr_output_request* req);
 VVR_API int          vvr_output_test(vvr_context* ctx, int ticket);
 VVR_API int          vvr_output_wait(vvr_context* ctx, int ticket);
+/* Destinations of the output queue in device memory, for a consumer on the same GPU (an encoder, a torch model, the sender of a collective).
+ * vvr_device_alloc: hipMalloc on the context's device, owned by the context (freed by vvr_destroy at the latest); vvr_device_free gives it back
+ * (an unknown pointer: nothing is freed, the text says so; a range a request in flight writes is freed behind that request).
+ * vvr_device_register: device memory of the caller's (a torch tensor's storage) on the context's device - the caller's word, nothing is
+ * queried.  A range that overlaps a known one, a NULL pointer or 0 bytes: VVR_ERR_PARAMETER.  vvr_device_unregister: VVR_ERR_PARAMETER for a
+ * pointer that was not registered (memory of vvr_device_alloc is freed, not unregistered), VVR_ERR_BUSY while a request whose ticket has not been
+ * retired writes into the range. */
+VVR_API void*        vvr_device_alloc(vvr_context* ctx, size_t bytes);
+VVR_API void         vvr_device_free(vvr_context* ctx, void* p);
+VVR_API int          vvr_device_register(vvr_context* ctx, void* p, size_t bytes);
+VVR_API int          vvr_device_unregister(vvr_context* ctx, void* p);
+/* the caller's stream (a hipStream_t) waits ON THE DEVICE for the completion of request `ticket` - behind its last kernel or copy; the host does
+ * not wait (vvr_stream_wait_job's counterpart for outputs).  For a host destination it means "the copy has landed" (pageable destinations still
+ * get their rows in vvr_output_wait).  The ticket stays and is retired by vvr_output_wait as ever.  An unknown or retired ticket:
+ * VVR_ERR_PARAMETER; a request whose job had failed when it was submitted: the job's status, nothing is enqueued. */
+VVR_API int          vvr_output_stream_wait(vvr_context* ctx, int ticket, void* stream);
 /* decoded picture hash of a slot, as the decoded-picture-hash SEI defines it and the reference checks it (calcMD5 / calcCRC / calcChecksum,
  * PicYuvMD5.cpp:99-221): one digest per component over the whole plane in raster order, samples as 1 byte (bit depth 8) or 2 bytes little
  * endian.  digest receives num_components x digest_len bytes (MD5 16, CRC 2, checksum 4), *digest_len the length of one.  CRC and checksum

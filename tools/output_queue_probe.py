@@ -4,11 +4,18 @@ K timed pictures behind pre-roll and warm-up, every window from the first pictur
   B  the output queue, VVR_OUT_PLANAR16 into pageable memory (the rows leave pinned staging in vvr_output_wait)
   C  the output queue, VVR_OUT_PLANAR16 into memory of vvr_host_alloc (the device copies straight there)
   D  the output queue, VVR_OUT_PACKED10 into memory of vvr_host_alloc
+  E  the output queue, VVR_OUT_P010 into memory of vvr_host_alloc
+  F  the output queue, VVR_OUT_P010 into device memory (vvr_device_alloc): nothing crosses PCIe
 and the decode-only rate of the same window (nothing leaves the device).  The ways alternate window by window; every way runs at least --windows
 windows and --min-seconds of timed work; median, minimum and maximum are reported.  Before the timed runs the outputs of A and B of the timed pictures
 are compared (they must be identical).  Requests are submitted without blocking behind their picture and collected when 8 are in flight.
 Kernel time: `rocprofv3 --kernel-trace --stats -- python tools/output_queue_probe.py --ways D --windows 2 --min-seconds 0` in a run of its own.
-Usage: python tools/output_queue_probe.py [--steps 64] [--warmup 16] [--windows 5] [--min-seconds 1.0] [--ways ABCDN] [--out FILE]"""
+--frame N: one 3840x2160 10-bit frame instead of a stream, N repeats of every configuration in turn (planar16 and p010 into memory of
+vvr_host_alloc and into device memory): the time of k_output_frame (HIP events around the launch, vvr_get_stats) and the time from
+vvr_output_submit to the return of vvr_output_wait, median / minimum / maximum.  --root DIR measures the package of another checkout of the project
+(the parent commit, say) with this script, so that both can run in one call on one box; configurations that checkout does not have are left out.
+Usage: python tools/output_queue_probe.py [--steps 64] [--warmup 16] [--windows 5] [--min-seconds 1.0] [--ways ABCDEFN] [--out FILE]
+       python tools/output_queue_probe.py --frame 50 [--root DIR] [--out FILE]"""
 import argparse
 import ctypes as C
 import hashlib
@@ -20,7 +27,50 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+
+
+def frame_mode(a):
+    """one 4K 10-bit frame: kernel time and submit-to-completion time per configuration"""
+    import vvdec_amd
+    from vvdec_amd import abi
+    W, H = 3840, 2160
+    rec = vvdec_amd.Reconstructor(W, H, bit_depth=10, num_slots=1, num_streams=1)
+    rng = np.random.default_rng(7)
+    rec.write_picture(0, [rng.integers(0, 1024, (H >> s, W >> s), dtype=np.uint16) for s in (0, 1, 1)])
+    rec.enable_stats()
+    win = (0, 0, W, H)
+
+    def kernel_ms():
+        return sum(s["total_ms"] for s in rec.stats() if s["name"] == "k_output_frame")
+    configs = {}
+    for fmt in ("planar16", "p010"):
+        for where in ("pinned", "device"):
+            if fmt not in abi.OUT_FORMATS or (where == "device" and not hasattr(rec, "device_array")):
+                continue
+            shapes, dt = abi.output_plane_shapes(win, fmt, None, 3)
+            item = np.dtype(dt).itemsize
+            if where == "pinned":
+                planes = [rec.host_array(r * n, dt).reshape(r, n) for r, n in shapes]
+            else:
+                import torch
+                planes = [rec.device_array(r * n * item).view(torch.int16).view(r, n) for r, n in shapes]
+            configs[fmt + "_" + where] = abi.output_request(0, None, win, fmt, None, (True, False), False, True, planes), planes
+    times = {name: ([], []) for name in configs}
+    for n in range(3 + a.frame):                  # (the first three rounds warm up: ring entries, scratch)
+        for name, (req, _) in configs.items():
+            k0, t0 = kernel_ms(), time.perf_counter()
+            t = rec._check(rec.L.vvr_output_submit(rec.ctx, C.byref(req)))
+            rec._check(rec.L.vvr_output_wait(rec.ctx, t))
+            t1 = time.perf_counter()
+            if n >= 3:
+                times[name][0].append(kernel_ms() - k0)
+                times[name][1].append((t1 - t0) * 1e3)
+    res = {"mode": "frame", "size": [W, H], "bit_depth": 10, "repeats": a.frame, "root": os.path.abspath(a.root or ROOT)}
+    for name, (k, t) in times.items():
+        res[name] = {"k_output_frame_ms": {"median": round(float(np.median(k)), 4), "min": round(min(k), 4), "max": round(max(k), 4)},
+                     "submit_to_completion_ms": {"median": round(float(np.median(t)), 4), "min": round(min(t), 4), "max": round(max(t), 4)}}
+    rec.close()
+    return res
 
 
 def main():
@@ -29,10 +79,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--min-seconds", type=float, default=1.0)
-    ap.add_argument("--ways", default="ABCDN")
+    ap.add_argument("--ways", default="ABCDEFN")
     ap.add_argument("--config", default="4k")
     ap.add_argument("--out", default="")
+    ap.add_argument("--frame", type=int, default=0)
+    ap.add_argument("--root", default="")
     a = ap.parse_args()
+    import torch  # noqa: F401  (first: torch brings its own HIP runtime, which has to be the one the process initialises - way F and --frame use tensors)
+    sys.path.insert(0, a.root or ROOT)
+    if a.frame:
+        line = json.dumps(frame_mode(a))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     import bench
     import vvdec_amd
     from vvdec_amd import abi, synth
@@ -51,15 +112,22 @@ def main():
     timed = order[first:first + K]
 
     # destinations: one set per ring entry and kind
-    def planes(fmt, pinned):
+    def planes(fmt, pinned, device=False):
         shapes, dt = abi.output_plane_shapes((0, 0, W, H), fmt, None, 3)
+        if device:
+            import torch
+            return [rec.device_array(r * n * 2).view(torch.int16).view(r, n) for r, n in shapes]
         return [rec.host_array(r * n, dt).reshape(r, n) if pinned else np.zeros((r, n), dt) for r, n in shapes]
     sets = {"B": ("planar16", [planes("planar16", False) for _ in range(8)]), "C": ("planar16", [planes("planar16", True) for _ in range(8)]),
             "D": ("packed10", [planes("packed10", True) for _ in range(8)])}
+    if "E" in a.ways:
+        sets["E"] = ("p010", [planes("p010", True) for _ in range(8)])
+    if "F" in a.ways:
+        sets["F"] = ("p010", [planes("p010", False, True) for _ in range(8)])
     reqs = {w: [abi.output_request(0, 0, (0, 0, W, H), fmt, None, (True, False), False, False, p) for p in ps] for w, (fmt, ps) in sets.items()}
     sync_out = planes("planar16", False)
     pcie = {"A": sum(p.nbytes for p in sync_out), "B": sum(p.nbytes for p in sets["B"][1][0]), "C": sum(p.nbytes for p in sets["C"][1][0]),
-            "D": sum(p.nbytes for p in sets["D"][1][0]), "N": 0}
+            "D": sum(p.nbytes for p in sets["D"][1][0]), "E": W * H * 3, "F": 0, "N": 0}
 
     def run(way, idx, digests=None):
         """the pictures `idx` through vvr_submit, every one of them delivered the way `way` says"""
@@ -120,7 +188,7 @@ def main():
         window("A", da)
         window("B", db)
         res["outputs_A_equal_B"] = len(da) == K and da == db
-    ways = [w for w in "ABCDN" if w in a.ways]
+    ways = [w for w in "ABCDEFN" if w in a.ways]
     times = {w: [] for w in ways}
     for w in ways:                                   # warm-up: every way once (ring entries, pinned staging)
         window(w)

@@ -99,6 +99,16 @@ def lib():
         L.vvr_output_test.argtypes = [C.c_void_p, C.c_int]
         L.vvr_output_wait.restype = C.c_int
         L.vvr_output_wait.argtypes = [C.c_void_p, C.c_int]
+        L.vvr_output_stream_wait.restype = C.c_int
+        L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.vvr_device_alloc.restype = C.c_void_p
+        L.vvr_device_alloc.argtypes = [C.c_void_p, C.c_size_t]
+        L.vvr_device_free.restype = None
+        L.vvr_device_free.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_device_register.restype = C.c_int
+        L.vvr_device_register.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.vvr_device_unregister.restype = C.c_int
+        L.vvr_device_unregister.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -108,7 +118,8 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
-                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait"]
+                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait",
+                    "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
 
 
 class Reconstructor:
@@ -128,6 +139,8 @@ class Reconstructor:
         self.width, self.height, self.chroma_format = width, height, chroma_format
         self._keep = {}
         self._out = {}
+        self._reg = {}      # ticket -> addresses registered for the life of the request (output_submit(into=...))
+        self._dev = []      # (address, bytes) of device_array memory: known to the context already
 
     # -- lifetime
     def close(self):
@@ -196,6 +209,22 @@ class Reconstructor:
         if not ptr:
             raise VvrError("vvr_host_alloc(%d) failed" % nbytes)
         return np.frombuffer((C.c_char * nbytes).from_address(ptr), dt, count=max(1, int(n)))[:int(n)]
+
+    def device_array(self, nbytes):
+        """uint8 torch tensor of nbytes in device memory of the context (vvr_device_alloc): a destination for output_submit(into=...) that
+        needs no registration.  The memory belongs to the context: the tensor is a view valid until close().  A process that uses torch tensors
+        with a context imports torch before it creates the first context (torch brings its own HIP runtime, which has to be the first one the
+        process initialises - the order bench.py uses); otherwise torch finds no device."""
+        import torch
+        nbytes = max(1, int(nbytes))
+        ptr = self.L.vvr_device_alloc(self.ctx, nbytes)
+        if not ptr:
+            raise VvrError("vvr_device_alloc(%d) failed" % nbytes)
+        self._dev.append((ptr, nbytes))
+
+        class _Mem:
+            __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
+        return torch.as_tensor(_Mem(), device="cuda:%d" % self.cfg.device)
 
     def copy_bandwidth(self, iters=20):
         """practical HBM ceiling: bytes/s (read + written) of the library's copy kernel over one DPB slot"""
@@ -307,22 +336,60 @@ class Reconstructor:
         return out
 
     # -- output queue: requests ordered behind their picture on the device; nothing here drains the context
-    def output_submit(self, slot, job=None, window=None, fmt="planar16", size=None, collocated=(True, False), grain=False, pinned=False, blocking=True):
+    def output_submit(self, slot, job=None, window=None, fmt="planar16", size=None, collocated=(True, False), grain=False, pinned=False, blocking=True, into=None):
         """vvr_output_submit: the window of `slot` (as `job` leaves it; None: as all work submitted so far leaves it) in the application's form ->
-        ticket, or None when blocking=False and the job has not been handed to the device yet.  fmt: "planar16", "planar8" or "packed10"
-        (vvdecapp --pyuv: four samples in five bytes); size, collocated, grain as read_output - and grain with size is the reference's chain,
+        ticket, or None when blocking=False and the job has not been handed to the device yet.  fmt: "planar16", "planar8", "packed10"
+        (vvdecapp --pyuv: four samples in five bytes), "nv12" or "p010" (two planes: luma, interleaved CbCr; p010: sample << (16 - bit depth));
+        size, collocated, grain as read_output - and grain with size is the reference's chain,
         grain first, then the rescale of the grained frame.  pinned: the planes are allocated in memory of the context that the device writes
-        directly (vvr_host_alloc) - they belong to the context and are views valid until close().  At most 8 requests in flight (VvrError).
+        directly (vvr_host_alloc) - they belong to the context and are views valid until close().
+        into: the destination planes as 2-D torch tensors on the context's device (row-major, any row stride, element size that of the
+        format: abi.output_plane_shapes): the device writes them, nothing crosses PCIe; they are registered with the context for the life of
+        the request and output_wait returns them.  The tensors must be idle now and stay untouched until the request has completed
+        (output_wait, output_test, or output_stream_wait on the stream that uses them).  At most 8 requests in flight (VvrError).
         Ask for a picture's output before the next picture into its slot is submitted: that picture then waits for the request on the device."""
         win = tuple(window or (0, 0, self.width, self.height))
         shapes, dt = abi.output_plane_shapes(win, fmt, size, 3 if self.chroma_format else 1)
-        planes = [self.host_array(r * n, dt).reshape(r, n) if pinned else np.zeros((r, n), dt) for r, n in shapes]
+        registered = []
+        if into is not None:
+            planes = list(into)
+            if len(planes) != len(shapes):
+                raise ValueError("output_submit: %s needs %d planes" % (fmt, len(shapes)))
+            for t, shape in zip(planes, shapes):
+                if not t.is_cuda or t.device.index != self.cfg.device or t.dim() != 2 or tuple(t.shape) != tuple(shape) or t.element_size() != np.dtype(dt).itemsize or (t.shape[1] > 1 and t.stride(1) != 1):
+                    raise ValueError("output_submit: into needs row-major 2-D tensors on the context's device, here of shape %r and %d-byte elements" % (shape, np.dtype(dt).itemsize))
+            try:
+                for t in planes:
+                    ptr, n = t.data_ptr(), ((t.shape[0] - 1) * t.stride(0) + t.shape[1]) * t.element_size()
+                    if any(a <= ptr and ptr + n <= a + m for a, m in self._dev):
+                        continue
+                    self._check(self.L.vvr_device_register(self.ctx, ptr, n))
+                    registered.append(ptr)
+            except VvrError:
+                for ptr in registered:
+                    self.L.vvr_device_unregister(self.ctx, ptr)
+                raise
+        else:
+            planes = [self.host_array(r * n, dt).reshape(r, n) if pinned else np.zeros((r, n), dt) for r, n in shapes]
         req = abi.output_request(slot, job, win, fmt, size, collocated, grain, blocking, planes)
-        ticket = self._check(self.L.vvr_output_submit(self.ctx, C.byref(req)))
+        ticket = self.L.vvr_output_submit(self.ctx, C.byref(req))
+        if ticket < 0 or ticket == abi.VVR_NOT_READY:
+            for ptr in registered:
+                self.L.vvr_device_unregister(self.ctx, ptr)
+        self._check(ticket)
         if not blocking and ticket == abi.VVR_NOT_READY:
             return None
         self._out[ticket] = planes
+        self._reg[ticket] = registered
         return ticket
+
+    def output_stream_wait(self, ticket, stream=None):
+        """vvr_output_stream_wait: `stream` (a torch.cuda.Stream, or a hipStream_t as an int; None: torch's current stream) waits on the device
+        for the completion of the request; the host does not wait.  The ticket stays for output_wait."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.cfg.device)
+        self._check(self.L.vvr_output_stream_wait(self.ctx, ticket, getattr(stream, "cuda_stream", stream)))
 
     def output_test(self, ticket):
         """vvr_output_test: True when output_wait(ticket) returns at once; raises if the request (or its picture) failed"""
@@ -333,12 +400,15 @@ class Reconstructor:
         return True
 
     def output_wait(self, ticket):
-        """vvr_output_wait: blocks for this request only and retires the ticket -> list of planes (packed10: uint8 arrays of (rows, w / 4 * 5))"""
+        """vvr_output_wait: blocks for this request only and retires the ticket -> list of planes (packed10: uint8 arrays of (rows, w / 4 * 5); the
+        tensors of output_submit(into=...), which are unregistered here)"""
         try:
             self._check(self.L.vvr_output_wait(self.ctx, ticket))
             return self._out[ticket]
         finally:
             self._out.pop(ticket, None)
+            for ptr in self._reg.pop(ticket, []):
+                self.L.vvr_device_unregister(self.ctx, ptr)
 
     def write_picture(self, slot, planes):
         for c, pl in enumerate(planes):

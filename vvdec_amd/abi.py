@@ -160,8 +160,8 @@ def film_grain_bank(comp_present, shift, scale_lut, pattern_lut, pattern):
     return b
 
 
-OUT_PLANAR16, OUT_PLANAR8, OUT_PACKED10 = 0, 1, 2
-OUT_FORMATS = {"planar16": OUT_PLANAR16, "planar8": OUT_PLANAR8, "packed10": OUT_PACKED10}
+OUT_PLANAR16, OUT_PLANAR8, OUT_PACKED10, OUT_NV12, OUT_P010 = 0, 1, 2, 16, 17
+OUT_FORMATS = {"planar16": OUT_PLANAR16, "planar8": OUT_PLANAR8, "packed10": OUT_PACKED10, "nv12": OUT_NV12, "p010": OUT_P010}
 
 
 class OutputRequest(C.Structure):
@@ -171,7 +171,7 @@ class OutputRequest(C.Structure):
 
 
 def output_request(slot, job, window, fmt, size, collocated, grain, blocking, planes):
-    """an OutputRequest whose destinations are the numpy arrays `planes` (rows at their strides)"""
+    """an OutputRequest whose destinations are `planes` (rows at their strides): numpy arrays, or 2-D torch tensors on the context's device"""
     r = OutputRequest()
     r.struct_size = C.sizeof(OutputRequest)
     r.slot, r.job = slot, -1 if job is None else job
@@ -180,16 +180,21 @@ def output_request(slot, job, window, fmt, size, collocated, grain, blocking, pl
     r.collocated = int(bool(collocated[0])) | int(bool(collocated[1])) << 1
     r.format, r.grain, r.blocking = OUT_FORMATS[fmt] if isinstance(fmt, str) else fmt, 1 if grain else 0, 1 if blocking else 0
     for c, a in enumerate(planes):
-        r.dst[c] = a.ctypes.data
-        r.dst_stride_bytes[c] = a.strides[0]
+        if hasattr(a, "data_ptr"):
+            r.dst[c], r.dst_stride_bytes[c] = a.data_ptr(), a.stride(0) * a.element_size()
+        else:
+            r.dst[c], r.dst_stride_bytes[c] = a.ctypes.data, a.strides[0]
     return r
 
 
 def output_plane_shapes(window, fmt, size, ncomp):
-    """(rows, bytes or samples per row) of every plane a request produces, and the dtype: packed10 rows are w / 4 * 5 bytes"""
+    """(rows, bytes or samples per row) of every plane a request produces, and the dtype: packed10 rows are w / 4 * 5 bytes; the semi-planar
+    formats have two planes, luma and the interleaved CbCr rows of 2 * (w >> 1) samples (nv12: uint8, p010: uint16)"""
     import numpy as np
     w, h = size or (window[2], window[3])
     shapes = [(h >> (1 if c else 0), w >> (1 if c else 0)) for c in range(ncomp)]
+    if fmt in ("nv12", "p010"):
+        return [(h, w), (h >> 1, 2 * (w >> 1))], np.uint8 if fmt == "nv12" else np.uint16
     if fmt == "packed10":
         return [(r, n // 4 * 5) for r, n in shapes], np.uint8
     return shapes, np.uint8 if fmt == "planar8" else np.uint16

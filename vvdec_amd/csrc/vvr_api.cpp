@@ -198,6 +198,7 @@ struct vvr_context {
   bool       stop = false;
   PrepScratch* inlineScratch = nullptr; // host_threads == 0, and vvr_prepare
   PinnedRanges pinned;                  // vvr_host_alloc
+  std::vector<DevRange> devRanges;      // vvr_device_alloc / vvr_device_register: where the output queue may store on the device (under mu)
   bool       statsOn = false;
   int        partsPolicy = 2;              // pictures with inter CUs built in bands by the workers together: 0 never, 1 always, 2 while the device is short of work (VVR_PARTS)
 #ifdef VVR_WATCHDOG
@@ -1165,6 +1166,7 @@ VVR_API void vvr_destroy( vvr_context* c )
   if( c->errHost ) hipHostFree( c->errHost );
   if( c->inlineScratch ) vvr_scratch_destroy( c->inlineScratch );
   for( auto& e : c->pinned.r ) hipHostFree( (void*) e.first );
+  for( auto& r : c->devRanges ) if( r.owned ) hipFree( r.p );
   delete c;
 }
 

@@ -165,9 +165,15 @@ void launch_film_grain( hipStream_t s, const FilmGrainParams& p, void* dst );
 // a frame of the output queue (vvr_output_submit): the windows of up to three planes, one launch, stored into dst + dstOff[c] (256-byte aligned) with
 // the rows back to back in `format` (VVR_OUT_*): 2 bytes or 1 byte per sample, or four samples in five bytes ( s << shift, 10 bits each;
 // w[c] a multiple of 4 then ).  A plane with w[c] == 0 is not part of the launch.  The launch may write up to 31 bytes of padding behind a plane.
+// The semi-planar formats (VVR_OUT_NV12: 1 byte per sample; VVR_OUT_P010: 2 bytes, s << shift) have two output planes: plane 0 the luma window,
+// plane 1 the chroma windows src[1], src[2] (w[1] / 2 samples wide each, stride[1], stride[2]) interleaved Cb0, Cr0, Cb1, ... into rows of w[1]
+// samples, h[1] of them; w[2] is 0.
+// direct[c] != NULL: plane c is stored there (32-byte aligned memory of the caller's) instead of dst + dstOff[c], and not a byte behind the
+// plane's last sample is written.
 struct OutputFrameParams
 {
   const pel_t* src[3]; int stride[3], w[3], h[3]; size_t dstOff[3];
+  uint8_t* direct[3];
   int first[3];      // (set by the launcher: first workgroup of every plane)
   int format, shift;
 };

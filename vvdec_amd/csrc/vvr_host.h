@@ -61,6 +61,8 @@ struct PinnedRanges {
   }
 };
 struct DirectCopy { const void* src; size_t n, off; };
+// Device memory the output queue may store into: the context's own (vvr_device_alloc) or the caller's (vvr_device_register)
+struct DevRange { char* p; size_t n; bool owned; };
 
 // Reusable scratch of one preparing thread: the lists are built here (no allocation in the steady state), then packed into pinned memory.
 struct PrepScratch;

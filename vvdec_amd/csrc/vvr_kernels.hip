@@ -4892,51 +4892,112 @@ void launch_film_grain( hipStream_t s, const FilmGrainParams& p, void* dst )
 }
 
 // k_output_frame — a frame of the output queue: crop and store of all planes of a request in one launch, in the application's form (16-bit,
-// 8-bit, or vvdecapp's packed 10-bit: _writeComponentToFile, vvdecHelper.h:106-145).  The output of a plane is one stream of samples, rows back to
-// back; a lane owns 16 consecutive samples of it, so that its store is whole and aligned whatever the width: 32 bytes (two 16-byte stores), 16 bytes,
-// or - packed - 5 dwords (four groups of 4 samples x 10 bits).  The 16 samples are one 32-byte piece of a source row (two 16-byte loads, consecutive
-// lanes consecutive pieces) unless the piece straddles the end of a row of a width that is no multiple of 16: those lanes gather sample by sample.
-// The last lane of a plane stores its whole piece: the planes are 256-byte aligned in dst, what lies behind a plane's last sample is padding.
-// No LDS, no scratch: the piece lives in registers.
+// 8-bit, vvdecapp's packed 10-bit: _writeComponentToFile, vvdecHelper.h:106-145, or semi-planar: NV12, P010).  The output of a plane is one
+// stream of samples, rows back to back; a lane owns 16 consecutive samples of it, so that its store is whole and aligned whatever the width:
+// 32 bytes (two 16-byte stores), 16 bytes, or - packed - 5 dwords (four groups of 4 samples x 10 bits).  The 16 samples are one 32-byte piece
+// of a source row (two 16-byte loads, consecutive lanes consecutive pieces) unless the piece straddles the end of a row of a width that is no
+// multiple of 16: those lanes gather sample by sample.
+// The CbCr plane of the semi-planar formats: a lane's 16 samples are 8 ( Cb, Cr ) pairs - one 16-byte load from each chroma plane, interleaved
+// in registers (v_perm_b32 picks the halves of a Cb and a Cr dword), one 32-byte (P010) or 16-byte (NV12) store; lanes whose 8 pairs straddle
+// the end of a chroma row gather pair by pair.  P010's shift is one v_and + v_lshl per dword (two samples), the 8-bit narrowing one v_perm
+// per four samples.
+// The last lane of a plane stores its whole piece: the planes are 256-byte aligned in dst, what lies behind a plane's last sample is padding -
+// except in the caller's device memory (direct[c]), where it stores exactly the samples that exist.
+// No LDS, no scratch: the piece lives in registers (8 dwords, two samples each).
 struct OfPiece { uint16_t s[16]; };
 typedef uint4 __attribute__(( aligned( 2 ) )) of_uint4_u;      // a 16-byte load from a 2-byte aligned address: one instruction (unaligned access mode)
+#define OF_PERM_LO16 0x05040100u      /* __builtin_amdgcn_perm( b, a, . ): a.lo16 | b.lo16 << 16 */
+#define OF_PERM_HI16 0x07060302u      /*                                   a.hi16 | b.hi16 << 16 */
+#define OF_PERM_NARROW 0x06040200u    /* the low bytes of the four 16-bit samples of a ( 0, 1 ) and b ( 2, 3 ) */
 __global__ __launch_bounds__( 256 ) void k_output_frame( OutputFrameParams p, uint8_t* __restrict__ dst )
 {
   const int blk = blockIdx.x, c = blk >= p.first[2] && p.w[2] ? 2 : ( blk >= p.first[1] && p.w[1] ? 1 : 0 );
   const uint32_t w = p.w[c], n = w * (uint32_t) p.h[c], piece = (uint32_t) ( blk - p.first[c] ) * 256 + threadIdx.x, i0 = piece * 16;
   if( i0 >= n ) return;
   const uint32_t r = i0 / w, x = i0 - r * w;
-  const pel_t* __restrict__ row = p.src[c] + (size_t) r * p.stride[c];
-  OfPiece v;
-  if( x + 16 <= w )      // (2-byte aligned in general: the window starts anywhere)
+  uint32_t d[8];
+  if( p.format >= VVR_OUT_NV12 && c == 1 )
   {
-    const of_uint4_u* q = (const of_uint4_u*) ( row + x );
-    const uint4 q0 = q[0], q1 = q[1];
-    __builtin_memcpy( &v.s[0], &q0, 16 ); __builtin_memcpy( &v.s[8], &q1, 16 );
+    // (w and i0 are even, so x is: the piece starts with a Cb)
+    const uint32_t cw = w >> 1, px = x >> 1;
+    const pel_t* __restrict__ rowB = p.src[1] + (size_t) r * p.stride[1] + px;
+    const pel_t* __restrict__ rowR = p.src[2] + (size_t) r * p.stride[2] + px;
+    if( px + 8 <= cw )
+    {
+      const uint4 a = *(const of_uint4_u*) rowB, b = *(const of_uint4_u*) rowR;
+      d[0] = __builtin_amdgcn_perm( b.x, a.x, OF_PERM_LO16 ); d[1] = __builtin_amdgcn_perm( b.x, a.x, OF_PERM_HI16 );
+      d[2] = __builtin_amdgcn_perm( b.y, a.y, OF_PERM_LO16 ); d[3] = __builtin_amdgcn_perm( b.y, a.y, OF_PERM_HI16 );
+      d[4] = __builtin_amdgcn_perm( b.z, a.z, OF_PERM_LO16 ); d[5] = __builtin_amdgcn_perm( b.z, a.z, OF_PERM_HI16 );
+      d[6] = __builtin_amdgcn_perm( b.w, a.w, OF_PERM_LO16 ); d[7] = __builtin_amdgcn_perm( b.w, a.w, OF_PERM_HI16 );
+    }
+    else
+    {
+      uint32_t xx = px;
+#pragma unroll
+      for( int k = 0; k < 8; k++ )
+      {
+        d[k] = i0 + 2 * k < n ? (uint32_t) (uint16_t) *rowB | (uint32_t) (uint16_t) *rowR << 16 : 0;
+        rowB++; rowR++;
+        if( ++xx == cw ) { xx = 0; rowB += p.stride[1] - (int) cw; rowR += p.stride[2] - (int) cw; }
+      }
+    }
   }
   else
   {
-    uint32_t xx = x;
-#pragma unroll
-    for( int k = 0; k < 16; k++ )
+    const pel_t* __restrict__ row = p.src[c] + (size_t) r * p.stride[c];
+    if( x + 16 <= w )      // (2-byte aligned in general: the window starts anywhere)
     {
-      v.s[k] = i0 + k < n ? (uint16_t) row[xx] : 0;
-      if( ++xx == w ) { xx = 0; row += p.stride[c]; }
+      const of_uint4_u* q = (const of_uint4_u*) ( row + x );
+      const uint4 q0 = q[0], q1 = q[1];
+      __builtin_memcpy( &d[0], &q0, 16 ); __builtin_memcpy( &d[4], &q1, 16 );
+    }
+    else
+    {
+      OfPiece v;
+      uint32_t xx = x;
+#pragma unroll
+      for( int k = 0; k < 16; k++ )
+      {
+        v.s[k] = i0 + k < n ? (uint16_t) row[xx] : 0;
+        if( ++xx == w ) { xx = 0; row += p.stride[c]; }
+      }
+      __builtin_memcpy( d, &v, 32 );
     }
   }
-  uint8_t* out = dst + p.dstOff[c];
-  if( p.format == VVR_OUT_PLANAR16 )
+  uint8_t* out = p.direct[c] ? p.direct[c] : dst + p.dstOff[c];
+  const uint32_t left = n - i0;
+  const bool partial = p.direct[c] && left < 16;      // (the caller's memory ends with the plane)
+  if( p.format == VVR_OUT_PLANAR16 || p.format == VVR_OUT_P010 )
   {
-    uint4 q[2]; __builtin_memcpy( q, &v, 32 );
-    uint4* o = (uint4*) ( out + (size_t) i0 * 2 );
-    o[0] = q[0]; o[1] = q[1];
-  }
-  else if( p.format == VVR_OUT_PLANAR8 )
-  {
-    uint32_t d[4];
+    if( p.format == VVR_OUT_P010 )
+    {
+      const uint32_t m = ( 0xffffu >> p.shift ) * 0x10001u;      // ( s << shift ) as a 16-bit word, two samples per dword
 #pragma unroll
-    for( int k = 0; k < 4; k++ ) d[k] = ( v.s[4 * k] & 0xffu ) | ( v.s[4 * k + 1] & 0xffu ) << 8 | ( v.s[4 * k + 2] & 0xffu ) << 16 | (uint32_t) v.s[4 * k + 3] << 24;      // "only narrowing conversions" (vvdecimpl.cpp:853)
-    *(uint4*) ( out + i0 ) = make_uint4( d[0], d[1], d[2], d[3] );
+      for( int k = 0; k < 8; k++ ) d[k] = ( d[k] & m ) << p.shift;
+    }
+    if( !partial )
+    {
+      uint4* o = (uint4*) ( out + (size_t) i0 * 2 );
+      o[0] = make_uint4( d[0], d[1], d[2], d[3] ); o[1] = make_uint4( d[4], d[5], d[6], d[7] );
+    }
+    else
+    {
+      uint16_t* o = (uint16_t*) ( out + (size_t) i0 * 2 );
+#pragma unroll
+      for( int k = 0; k < 16; k++ ) if( (uint32_t) k < left ) o[k] = (uint16_t) ( d[k >> 1] >> ( 16 * ( k & 1 ) ) );
+    }
+  }
+  else if( p.format == VVR_OUT_PLANAR8 || p.format == VVR_OUT_NV12 )
+  {
+    uint32_t b[4];
+#pragma unroll
+    for( int k = 0; k < 4; k++ ) b[k] = __builtin_amdgcn_perm( d[2 * k + 1], d[2 * k], OF_PERM_NARROW );      // "only narrowing conversions" (vvdecimpl.cpp:853)
+    if( !partial ) *(uint4*) ( out + i0 ) = make_uint4( b[0], b[1], b[2], b[3] );
+    else
+    {
+#pragma unroll
+      for( int k = 0; k < 16; k++ ) if( (uint32_t) k < left ) out[i0 + k] = (uint8_t) ( b[k >> 2] >> ( 8 * ( k & 3 ) ) );
+    }
   }
   else
   {
@@ -4944,15 +5005,23 @@ __global__ __launch_bounds__( 256 ) void k_output_frame( OutputFrameParams p, ui
 #pragma unroll
     for( int k = 0; k < 4; k++ )
     {
-      const uint64_t s0 = ( v.s[4 * k] << p.shift ) & 0x3ff, s1 = ( v.s[4 * k + 1] << p.shift ) & 0x3ff, s2 = ( v.s[4 * k + 2] << p.shift ) & 0x3ff, s3 = ( v.s[4 * k + 3] << p.shift ) & 0x3ff;
+      const uint32_t lo = d[2 * k], hi = d[2 * k + 1];
+      const uint64_t s0 = ( ( lo & 0xffff ) << p.shift ) & 0x3ff, s1 = ( ( lo >> 16 ) << p.shift ) & 0x3ff, s2 = ( ( hi & 0xffff ) << p.shift ) & 0x3ff, s3 = ( ( hi >> 16 ) << p.shift ) & 0x3ff;
       g[k] = s0 | s1 << 10 | s2 << 20 | s3 << 30;
     }
-    uint32_t* o = (uint32_t*) ( out + (size_t) piece * 20 );
-    o[0] = (uint32_t) g[0];
-    o[1] = (uint32_t) ( g[0] >> 32 | g[1] << 8 );
-    o[2] = (uint32_t) ( g[1] >> 24 | g[2] << 16 );
-    o[3] = (uint32_t) ( g[2] >> 16 | g[3] << 24 );
-    o[4] = (uint32_t) ( g[3] >> 8 );
+    const uint32_t q[5] = { (uint32_t) g[0], (uint32_t) ( g[0] >> 32 | g[1] << 8 ), (uint32_t) ( g[1] >> 24 | g[2] << 16 ), (uint32_t) ( g[2] >> 16 | g[3] << 24 ), (uint32_t) ( g[3] >> 8 ) };
+    if( !partial )
+    {
+      uint32_t* o = (uint32_t*) ( out + (size_t) piece * 20 );
+      o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3]; o[4] = q[4];
+    }
+    else
+    {
+      uint8_t* o = out + (size_t) piece * 20;
+      const uint32_t bytes = left / 4 * 5;      // (the plane's width is a multiple of 4)
+#pragma unroll
+      for( int k = 0; k < 20; k++ ) if( (uint32_t) k < bytes ) o[k] = (uint8_t) ( q[k >> 2] >> ( 8 * ( k & 3 ) ) );
+    }
   }
 }
 void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst )

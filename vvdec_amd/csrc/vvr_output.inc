@@ -173,23 +173,26 @@ void launch_film_grain( hipStream_t, const FilmGrainParams& p, void* dst )
   }
 }
 
-// ... and launch_output_frame: the planes' windows row by row in the three formats (k_output_frame)
+// ... and launch_output_frame: the planes' windows row by row in the five formats (k_output_frame); plane 1 of the semi-planar ones takes its
+// samples from the two chroma windows in turn
 void launch_output_frame( hipStream_t, OutputFrameParams p, void* dst )
 {
+  const bool semi = p.format == VVR_OUT_NV12 || p.format == VVR_OUT_P010;
   for( int c = 0; c < 3; c++ )
     for( int r = 0; r < ( p.w[c] ? p.h[c] : 0 ); r++ )
     {
-      const pel_t* row = p.src[c] + (size_t) r * p.stride[c];
-      uint8_t* out = (uint8_t*) dst + p.dstOff[c];
+      uint8_t* out = p.direct[c] ? p.direct[c] : (uint8_t*) dst + p.dstOff[c];
+      auto sample = [&]( int x ) { const int k = semi && c == 1 ? 1 + ( x & 1 ) : c, col = semi && c == 1 ? x >> 1 : x; return (uint16_t) p.src[k][(size_t) r * p.stride[k] + col]; };
       for( int x = 0; x < p.w[c]; x++ )
       {
         const size_t i = (size_t) r * p.w[c] + x;
-        if( p.format == VVR_OUT_PLANAR16 ) ( (uint16_t*) out )[i] = (uint16_t) row[x];
-        else if( p.format == VVR_OUT_PLANAR8 ) out[i] = (uint8_t) row[x];
+        if( p.format == VVR_OUT_PLANAR16 ) ( (uint16_t*) out )[i] = sample( x );
+        else if( p.format == VVR_OUT_P010 ) ( (uint16_t*) out )[i] = (uint16_t) ( sample( x ) << p.shift );
+        else if( p.format == VVR_OUT_PLANAR8 || p.format == VVR_OUT_NV12 ) out[i] = (uint8_t) sample( x );
         else if( ( x & 3 ) == 0 )
         {
           uint64_t g = 0;
-          for( int k = 0; k < 4; k++ ) g |= (uint64_t) ( ( (uint16_t) row[x + k] << p.shift ) & 0x3ff ) << ( 10 * k );
+          for( int k = 0; k < 4; k++ ) g |= (uint64_t) ( ( sample( x + k ) << p.shift ) & 0x3ff ) << ( 10 * k );
           for( int k = 0; k < 5; k++ ) out[i / 4 * 5 + k] = (uint8_t) ( g >> ( 8 * k ) );
         }
       }
@@ -453,7 +456,12 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // (vvr_slot_external_event): the entry's `read` event, recorded behind the last kernel of the request, is registered with the slot, so a
 // picture submitted afterwards that overwrites the slot waits for it on the device - not for the copy to the host.
 // k_rescale and k_film_grain reach the packed format and the chained case with at most one extra pass through HBM: they store 16-bit samples
-// into the entry's scratch (`tmp`) and k_output_frame packs from there; into the planar formats they store directly as ever.
+// into the entry's scratch (`tmp`) and k_output_frame packs (or interleaves: NV12, P010) from there; into the planar formats they store directly
+// as ever.
+// A request whose destination planes lie in device memory the context knows (vvr_device_alloc / vvr_device_register) moves nothing over PCIe:
+// k_output_frame stores a plane whose rows are back to back at a 32-byte aligned base straight into it, exactly its bytes; every other plane
+// (padded rows, odd bases, the planes k_film_grain / k_rescale store themselves) goes through the entry's scratch and one device-to-device
+// hipMemcpy2DAsync at the caller's stride.  `done` is recorded behind the last kernel or copy; vvr_output_stream_wait hands it to a stream.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -463,7 +471,8 @@ struct OutEntry {
   char* tmp = nullptr;  size_t tmpCap = 0;       // 16-bit intermediate planes (grained, rescaled) and the grain's random words
   char* host = nullptr; size_t hostCap = 0;      // pinned: the output (unless it goes straight to the caller's pinned memory), then the words
   hipEvent_t read = nullptr, done = nullptr;     // behind the last kernel; behind the last copy
-  bool direct = false, queued = false;           // queued: something was enqueued (done has been recorded)
+  bool direct = false, queued = false;           // direct: vvr_output_wait copies nothing (pinned or device destinations); queued: something was enqueued (done has been recorded)
+  bool devDst = false; size_t extent[3] = { 0, 0, 0 };      // the destination planes lie in device memory: dst[k] .. dst[k] + extent[k]
   int nc = 0, rows[3] = { 0, 0, 0 }; size_t off[3] = { 0, 0, 0 }, rowBytes[3] = { 0, 0, 0 }, dstStride[3] = { 0, 0, 0 }; void* dst[3] = { nullptr, nullptr, nullptr };
   bool timed = false; PendingTiming timing;
 };
@@ -526,11 +535,15 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( rq->struct_size != sizeof( vvr_output_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_output_request )" );
   const int slot = rq->slot, bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot" );
-  if( rq->format > VVR_OUT_PACKED10 ) return outRefuse( c, "unknown format" );
+  if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 ) return outRefuse( c, "unknown format" );
   if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1" );
-  const bool packed = rq->format == VVR_OUT_PACKED10, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
-  const int bps = rq->format == VVR_OUT_PLANAR8 ? 1 : 2;
-  if( rq->format == VVR_OUT_PLANAR8 && bd > 8 ) return outRefuse( c, "8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" );
+  const bool packed = rq->format == VVR_OUT_PACKED10, semi = rq->format == VVR_OUT_NV12 || rq->format == VVR_OUT_P010, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
+  const bool viaTmp = packed || semi;      // k_output_frame makes the format: the stages before it store 16-bit samples into `tmp`
+  const bool narrow = rq->format == VVR_OUT_PLANAR8 || rq->format == VVR_OUT_NV12;
+  const int bps = narrow ? 1 : 2, nOut = semi ? 2 : nc;
+  if( semi && nc == 1 ) return outRefuse( c, "semi-planar output of a 4:0:0 context: there is no chroma to interleave" );
+  if( rq->format == VVR_OUT_P010 && ( bd < 8 || bd > 10 ) ) return outRefuse( c, "P010 output needs a bit depth of 8, 9 or 10" );
+  if( narrow && bd > 8 ) return outRefuse( c, "8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" );
   if( packed && bd != 8 && bd != 10 ) return outRefuse( c, "packed 10-bit output needs a bit depth of 8 or 10 (vvdecHelper.h:106-248)" );
   const DevPlanes d = pictureIn( c, slot );
   if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, or odd in 4:2:0" );
@@ -550,8 +563,8 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
       return outRefuse( c, "output sides must be 1..8192 and within 1/8 .. 8 times the window's" );
     resc[k] = ow[k] != pw[k] || oh[k] != ph[k]; anyResc |= resc[k];
     if( packed && ( ow[k] & 3 ) ) return outRefuse( c, "packed 10-bit output needs plane widths that are multiples of 4 (four samples in five bytes)" );
-    rowBytes[k] = packed ? (size_t) ow[k] / 4 * 5 : (size_t) ow[k] * bps;
-    if( !rq->dst[k] || rq->dst_stride_bytes[k] < rowBytes[k] ) return outRefuse( c, "missing plane or stride below the output's row" );
+    rowBytes[k] = packed ? (size_t) ow[k] / 4 * 5 : (size_t) ow[k] * bps * ( semi && k ? 2 : 1 );      // (semi-planar plane 1: Cb and Cr interleaved)
+    if( k < nOut && ( !rq->dst[k] || rq->dst_stride_bytes[k] < rowBytes[k] ) ) return outRefuse( c, "missing plane or stride below the output's row" );
   }
   hipSetDevice( c->device );
   // ---- 2. a ring entry; the picture has been handed to the device
@@ -600,21 +613,40 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     c->cv.wait( lk, [&]{ return c->bySeq.empty(); } );
   }
   if( e->state != OQ_FREE ) { c->setError( "vvr_output_submit: called from two threads at once" ); return VVR_ERR_PARAMETER; }
+  // ---- where the planes go: device memory the context knows (every plane wholly inside a range), or the host
+  size_t extent[3] = { 0, 0, 0 }; int devPlanes = 0;
+  for( int k = 0; k < nOut; k++ )
+  {
+    extent[k] = (size_t) ( oh[k] - 1 ) * rq->dst_stride_bytes[k] + rowBytes[k];
+    const char* b = (const char*) rq->dst[k];
+    for( const DevRange& r : c->devRanges )
+    {
+      if( b >= r.p && b + extent[k] <= r.p + r.n ) { devPlanes++; break; }
+      if( b < r.p + r.n && b + extent[k] > r.p ) { c->setError( "vvr_output_submit: a destination plane lies partly inside a device range (vvr_device_alloc / vvr_device_register)" ); return VVR_ERR_PARAMETER; }
+    }
+  }
+  if( devPlanes && devPlanes != nOut ) { c->setError( "vvr_output_submit: destination planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
+  const bool devDst = devPlanes != 0;
   e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
-  e->job = rq->job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->nc = nc;
+  e->job = rq->job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = nOut;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
   if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
   // ---- the entry's buffers: the output's planes; the 16-bit planes of a grained frame that goes on (A) and of a rescaled plane that is packed (B); the words
-  const bool grainTmp = grain && ( packed || anyResc );
+  const bool grainTmp = grain && ( viaTmp || anyResc );
   size_t total = 0, tmpBytes = 0, offA[3] = { 0, 0, 0 }, offB[3] = { 0, 0, 0 };
-  bool direct = true;
+  bool direct = true, kdirect[3] = { false, false, false };      // kdirect: k_output_frame stores the plane straight into the caller's device memory
+  for( int k = 0; k < nOut; k++ )
+  {
+    const bool frameStores = viaTmp || !( ( grain && !grainTmp ) || resc[k] );      // (else k_film_grain / k_rescale store the plane themselves)
+    kdirect[k] = devDst && frameStores && rq->dst_stride_bytes[k] == rowBytes[k] && ( (uintptr_t) rq->dst[k] & 31 ) == 0;
+    e->off[k] = total; e->rowBytes[k] = rowBytes[k]; e->rows[k] = oh[k]; e->dst[k] = rq->dst[k]; e->dstStride[k] = rq->dst_stride_bytes[k]; e->extent[k] = extent[k];
+    if( !kdirect[k] ) total += outRegion( rowBytes[k] * oh[k] );
+    direct = direct && ( devDst || c->pinned.contains( rq->dst[k], extent[k] ) );
+  }
   for( int k = 0; k < nc; k++ )
   {
-    e->off[k] = total; e->rowBytes[k] = rowBytes[k]; e->rows[k] = oh[k]; e->dst[k] = rq->dst[k]; e->dstStride[k] = rq->dst_stride_bytes[k];
-    total += outRegion( rowBytes[k] * oh[k] );
     if( grainTmp ) { offA[k] = tmpBytes; tmpBytes += outRegion( (size_t) pw[k] * ph[k] * 2 ); }
-    if( resc[k] && packed ) { offB[k] = tmpBytes; tmpBytes += outRegion( (size_t) ow[k] * oh[k] * 2 ); }
-    direct = direct && c->pinned.contains( rq->dst[k], (size_t) ( oh[k] - 1 ) * rq->dst_stride_bytes[k] + rowBytes[k] );
+    if( resc[k] && viaTmp ) { offB[k] = tmpBytes; tmpBytes += outRegion( (size_t) ow[k] * oh[k] * 2 ); }
   }
   const int nbx = ( w + 15 ) / 16, nby = ( h + 15 ) / 16;
   const size_t wordsBytes = grain ? (size_t) nbx * nby * sizeof( uint32_t ) : 0, wordsOff = tmpBytes, hostWordsOff = direct ? 0 : total;
@@ -622,7 +654,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   const size_t hostBankOff = hostWordsOff + alignUp( wordsBytes, 256 );      // (a bank that changed travels through the entry's pinned memory: the context's copy may change while the upload is in flight)
   if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostBankOff + ( grain && c->grainBankStale ? sizeof( vvr_film_grain_bank ) : 0 ), true ) != VVR_OK )
   { c->setError( "vvr_output_submit: out of device or pinned memory" ); return VVR_ERR_DEVICE; }
-  e->direct = direct;
+  e->direct = direct; e->devDst = devDst;
   // ---- 3. behind the picture (or the slot's users) on the device, 4. the kernels.  mu stays held up to the registration of the `read` event: a
   // picture committed meanwhile that overwrites the slot must find it
 #define OQCHK( call ) do { hipError_t e_ = ( call ); if( e_ != hipSuccess ) { c->setError( std::string( "vvr_output_submit: " #call ": " ) + hipGetErrorString( e_ ) ); hipStreamSynchronize( s ); return VVR_ERR_DEVICE; } } while( 0 )
@@ -668,18 +700,22 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     const int cs = luma ? 0 : 1, colX = luma ? 1 : rq->collocated & 1, colY = luma ? 1 : ( rq->collocated >> 1 ) & 1, fracShift = luma ? 4 : 5;
     RescaleParams p;
     p.src = cur[k].p; p.stride = cur[k].stride; p.w = pw[k]; p.h = ph[k]; p.outW = ow[k]; p.outH = oh[k];
-    p.luma = luma; p.maxVal = ( 1 << bd ) - 1; p.bytesPerSample = packed ? 2 : bps;
+    p.luma = luma; p.maxVal = ( 1 << bd ) - 1; p.bytesPerSample = viaTmp ? 2 : bps;
     int scale;
     rescale_axis( pw[k], ow[k], cs, colX, fracShift, scale, p.addX, p.shiftX ); p.stepX = scale << cs;
     rescale_axis( ph[k], oh[k], cs, colY, fracShift, scale, p.addY, p.shiftY ); p.stepY = scale << cs;
-    launch_rescale( s, p, packed ? e->tmp + offB[k] : e->dev + e->off[k] );
-    if( packed ) { cur[k].p = (const pel_t*) ( e->tmp + offB[k] ); cur[k].stride = ow[k]; } else cur[k].inOut = true;
+    launch_rescale( s, p, viaTmp ? e->tmp + offB[k] : e->dev + e->off[k] );
+    if( viaTmp ) { cur[k].p = (const pel_t*) ( e->tmp + offB[k] ); cur[k].stride = ow[k]; } else cur[k].inOut = true;
   }
   OutputFrameParams fp; memset( &fp, 0, sizeof( fp ) );
   double frameBytes = 0;
   for( int k = 0; k < nc; k++ )
-    if( !cur[k].inOut ) { fp.src[k] = cur[k].p; fp.stride[k] = cur[k].stride; fp.w[k] = ow[k]; fp.h[k] = oh[k]; fp.dstOff[k] = e->off[k]; frameBytes += (double) ow[k] * oh[k] * 2 + (double) rowBytes[k] * oh[k]; }
-  fp.format = rq->format; fp.shift = packed ? 10 - bd : 0;
+    if( !cur[k].inOut )
+    {
+      fp.src[k] = cur[k].p; fp.stride[k] = cur[k].stride; frameBytes += (double) ow[k] * oh[k] * 2 + ( k < nOut ? (double) rowBytes[k] * oh[k] : 0. );
+      if( k < nOut ) { fp.w[k] = semi && k ? 2 * ow[k] : ow[k]; fp.h[k] = oh[k]; fp.dstOff[k] = e->off[k]; fp.direct[k] = kdirect[k] ? (uint8_t*) rq->dst[k] : nullptr; }
+    }
+  fp.format = rq->format; fp.shift = packed ? 10 - bd : ( rq->format == VVR_OUT_P010 ? 16 - bd : 0 );
   if( frameBytes > 0 )
   {
     if( c->statsOn && hipEventCreate( &e->timing.a ) == hipSuccess )
@@ -699,9 +735,15 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   lk.unlock();
   // ---- the result's way to the host: exactly the output's bytes
   hipError_t ce = hipSuccess;
-  for( int k = 0; k < nc && ce == hipSuccess; k++ )
+  for( int k = 0; k < nOut && ce == hipSuccess; k++ )
   {
-    if( !direct ) ce = hipMemcpyAsync( e->host + e->off[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToHost, s );
+    if( devDst )      // (what k_output_frame has not stored itself: rows out of the entry's scratch at the caller's stride, on the device)
+    {
+      if( kdirect[k] ) continue;
+      if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpyAsync( rq->dst[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToDevice, s );
+      else ce = hipMemcpy2DAsync( rq->dst[k], rq->dst_stride_bytes[k], e->dev + e->off[k], rowBytes[k], rowBytes[k], oh[k], hipMemcpyDeviceToDevice, s );
+    }
+    else if( !direct ) ce = hipMemcpyAsync( e->host + e->off[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToHost, s );
     else if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpyAsync( rq->dst[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToHost, s );
     else ce = hipMemcpy2DAsync( rq->dst[k], rq->dst_stride_bytes[k], e->dev + e->off[k], rowBytes[k], rowBytes[k], oh[k], hipMemcpyDeviceToHost, s );
   }
@@ -710,7 +752,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   {
     // (the request stays accepted - its kernels have run, the chain has advanced - and fails from vvr_output_test / vvr_output_wait)
     hipStreamSynchronize( s );
-    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( "vvr_output_submit: copy to the host: " ) + hipGetErrorString( ce ) );
+    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( "vvr_output_submit: copy to the destination: " ) + hipGetErrorString( ce ) );
   }
 #undef OQCHK
   return ticket;
@@ -757,6 +799,86 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   lk.lock();
   e->state = OQ_FREE; e->ticket = -1;
   return rc;
+}
+
+VVR_API int vvr_output_stream_wait( vvr_context* c, int ticket, void* stream )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  hipSetDevice( c->device );
+  std::unique_lock<std::mutex> lk( c->mu );
+  OutEntry* e = outFind( c, ticket );
+  if( !e || e->state != OQ_FLIGHT ) { c->setError( "vvr_output_stream_wait: unknown or retired ticket" ); return VVR_ERR_PARAMETER; }
+  if( e->rc != VVR_OK ) return e->rc;      // (the request's job had failed, or its copy could not be enqueued: nothing to wait for)
+  if( e->queued ) HIPCHK( c, hipStreamWaitEvent( (hipStream_t) stream, e->done, 0 ) );
+  return VVR_OK;
+}
+
+VVR_API void* vvr_device_alloc( vvr_context* c, size_t bytes )
+{
+  if( !c || !bytes ) return nullptr;
+  hipSetDevice( c->device );
+  void* p = nullptr;
+  if( hipMalloc( &p, bytes ) != hipSuccess ) return nullptr;
+  std::lock_guard<std::mutex> lk( c->mu );
+  c->devRanges.push_back( DevRange{ (char*) p, bytes, true } );
+  return p;
+}
+
+VVR_API int vvr_device_register( vvr_context* c, void* p, size_t bytes )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  if( !p || !bytes ) { c->setError( "vvr_device_register: no pointer or no bytes" ); return VVR_ERR_PARAMETER; }
+  for( const DevRange& r : c->devRanges )
+    if( (char*) p < r.p + r.n && (char*) p + bytes > r.p ) { c->setError( "vvr_device_register: the range overlaps one that is registered or allocated already" ); return VVR_ERR_PARAMETER; }
+  c->devRanges.push_back( DevRange{ (char*) p, bytes, false } );
+  return VVR_OK;
+}
+
+namespace {
+// the range that starts at p, and whether a request whose ticket has not been retired writes into it.  mu held.
+int devRangeAt( vvr_context* c, const void* p, bool& busy )
+{
+  busy = false;
+  int at = -1;
+  for( size_t i = 0; i < c->devRanges.size(); i++ ) if( c->devRanges[i].p == (const char*) p ) at = (int) i;
+  if( at < 0 || !c->outRing ) return at;
+  const DevRange& r = c->devRanges[at];
+  for( int i = 0; i < VVR_OUT_RING; i++ )
+  {
+    const OutEntry& e = c->outRing[i];
+    if( e.state == OQ_FREE || !e.devDst ) continue;
+    for( int k = 0; k < e.nc; k++ ) if( (const char*) e.dst[k] >= r.p && (const char*) e.dst[k] + e.extent[k] <= r.p + r.n ) busy = true;
+  }
+  return at;
+}
+}   // namespace
+
+VVR_API int vvr_device_unregister( vvr_context* c, void* p )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  bool busy;
+  const int at = devRangeAt( c, p, busy );
+  if( at < 0 || c->devRanges[at].owned ) { c->setError( at < 0 ? "vvr_device_unregister: unknown pointer" : "vvr_device_unregister: memory of vvr_device_alloc (vvr_device_free gives it back)" ); return VVR_ERR_PARAMETER; }
+  if( busy ) { c->setError( "vvr_device_unregister: a request in flight writes into the range (vvr_output_wait retires it)" ); return VVR_ERR_BUSY; }
+  c->devRanges.erase( c->devRanges.begin() + at );
+  return VVR_OK;
+}
+
+VVR_API void vvr_device_free( vvr_context* c, void* p )
+{
+  if( !c ) return;
+  hipSetDevice( c->device );
+  std::unique_lock<std::mutex> lk( c->mu );
+  bool busy;
+  const int at = devRangeAt( c, p, busy );
+  if( at < 0 || !c->devRanges[at].owned ) { c->setError( at < 0 ? "vvr_device_free: unknown pointer" : "vvr_device_free: registered memory of the caller's (vvr_device_unregister)" ); return; }
+  c->devRanges.erase( c->devRanges.begin() + at );
+  hipStream_t s = c->outQStream;
+  lk.unlock();
+  if( busy && s ) hipStreamSynchronize( s );      // (behind the request that writes it; its ticket stays)
+  hipFree( p );
 }
 
 }   // extern "C"
