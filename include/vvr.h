@@ -526,6 +526,26 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *            (dst_stride_bytes[1] covers that row; dst[2] and dst_stride_bytes[2] are ignored and may be NULL / 0).  NV12: one byte per sample,
  *            the sample itself, 8-bit contexts only (VVR_OUT_PLANAR8's refusal).  P010: little-endian 16-bit words, sample << ( 16 - bit_depth ),
  *            bit depths 8, 9 and 10.  Both are refused in a 4:0:0 context: there is no chroma to interleave.
+ *            VVR_OUT_RGB8 / VVR_OUT_RGB16 / VVR_OUT_RGBF16: planar R'G'B' for a model on the same GPU.  Three planes of out_w x out_h samples
+ *            (or w x h) leave the request, dst[0], dst[1], dst[2] = R, G, B, rows of out_w * 1 (RGB8) or out_w * 2 bytes.  The frame that is
+ *            converted is the one the other formats would store: the window, grained, rescaled.  The arithmetic is defined here to the bit:
+ *              chroma to the luma grid: the 4-tap chroma DCTIF of vvr_read_output_scaled (1/32-sample table), its two passes and rounding.  Per
+ *              direction, output position i reads the chroma plane at refPos = 16 * i - ( collocated ? 0 : 8 ) in 1/32 chroma samples (`collocated`
+ *              of the request: bit 0 horizontal, bit 1 vertical), integer = refPos >> 5, frac = refPos & 31 (0 and 16, or 24 and 8), taps at
+ *              integer - 1 .. integer + 2, each clamped to the chroma plane OF THE FRAME BEING CONVERTED; the horizontal sums are not normalised,
+ *              the vertical pass runs over them, then ( sum + 2048 ) >> 12, clipped to [0, 2^bd - 1].
+ *              matrix: od = 8 (RGB8) or bd; m = 2^od - 1, s = 2^( bd - 8 ); ( Kr, Kb ) from vvr_set_output_colour; Kg = 1 - Kr - Kb; limited
+ *              range: ys = m / ( 219 s ), cs = m / ( 224 s ), yoff = 16 s; full range: ys = cs = m / ( 2^bd - 1 ), yoff = 0; coff = 2^( bd - 1 ).
+ *              Five Q14 coefficients, computed once in double with q( v ) = floor( v * 16384 + 0.5 ): cy = q( ys ), rv = q( 2 ( 1 - Kr ) cs ),
+ *              gu = -q( 2 Kb ( 1 - Kb ) / Kg * cs ), gv = -q( 2 Kr ( 1 - Kr ) / Kg * cs ), bu = q( 2 ( 1 - Kb ) cs ).  With y = Y - yoff,
+ *              u = Cb' - coff, v = Cr' - coff in int32 and arithmetic shifts: R = clip( ( cy y + rv v + 8192 ) >> 14, 0, m ),
+ *              G = clip( ( cy y + gu u + gv v + 8192 ) >> 14, 0, m ), B = clip( ( cy y + bu u + 8192 ) >> 14, 0, m ): within 0.5625 of the
+ *              real-valued H.273 equations; 10 -> 8 bits is a rounding through the coefficients, not a truncation.
+ *              RGB8: uint8.  RGB16: little-endian uint16, od = bd.  RGBF16: IEEE half, the RGB16 value v as half( float32( v ) * inv ) with
+ *              inv = float32( 1 ) / float32( 2^bd - 1 ): one correctly rounded float32 multiply, one conversion rounding to nearest even.
+ *            Refused: no colour description set, a 4:0:0 context (no chroma), a bit depth outside 8..10, an odd out_w or out_h, a missing plane
+ *            among the three or a stride below the row.  Not offered: interleaved or packed RGB(A), BGR, float32; primaries or transfer
+ *            conversion; constant-luminance BT.2020, ICtCp, YCgCo, the identity matrix; 4:0:0 as grey; the synchronous vvr_read_output* calls.
  *   grain with out_w / out_h: the window is grained at its own size exactly as vvr_read_output_grain does it, the grained frame is then
  *            rescaled exactly as vvr_read_output_scaled rescales a picture, taps clamped to the grained frame (the reference's order:
  *            xAddGrain in xAddPicture, then the application's upscaleFrame).
@@ -550,7 +570,7 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *   the job's status from vvr_output_test / vvr_output_wait.  vvr_output_test: VVR_OK (vvr_output_wait returns at once) / VVR_NOT_READY / the
  *   failure; the ticket stays.  vvr_output_wait blocks for THIS request only and retires the ticket.  An unknown or retired ticket:
  *   VVR_ERR_PARAMETER.  vvr_sync also waits for the requests in flight but retires no ticket. */
-enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2, VVR_OUT_NV12 = 16, VVR_OUT_P010 = 17 };
+enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2, VVR_OUT_NV12 = 16, VVR_OUT_P010 = 17, VVR_OUT_RGB8 = 32, VVR_OUT_RGB16 = 33, VVR_OUT_RGBF16 = 34 };
 typedef struct vvr_output_request {
   uint32_t struct_size;        /* sizeof( vvr_output_request ) */
   int32_t  slot;
@@ -562,9 +582,15 @@ typedef struct vvr_output_request {
   uint8_t  format;             /* VVR_OUT_* */
   uint8_t  grain;              /* 1: the context's bank is added first, one frame of the seed chain (vvr_read_output_grain's rules) */
   uint8_t  blocking;           /* 0: VVR_NOT_READY instead of waiting on the host until `job` has been handed to the device */
-  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0; dst[2] unused by VVR_OUT_NV12 / VVR_OUT_P010 */
+  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0; dst[2] unused by VVR_OUT_NV12 / VVR_OUT_P010; R, G, B for VVR_OUT_RGB* */
   size_t   dst_stride_bytes[3];
 } vvr_output_request;
+/* the colour description the RGB formats convert with - context state, like the film grain bank; a new context has none.  matrix_coefficients
+ * is the H.273 code point: 1 (BT.709), 5 or 6 (BT.601), 9 (BT.2020 non-constant luminance); full_range is video_full_range_flag, 0 or 1.
+ * Anything else - 0 (identity / GBR), 2 (unspecified: the caller decides), 14, ... - is VVR_ERR_PARAMETER with a text, and the value set before
+ * stays.  A request takes the value that is set when vvr_output_submit accepts it: the coefficients travel as kernel arguments, a later call
+ * never changes a request in flight. */
+VVR_API int          vvr_set_output_colour(vvr_context* ctx, int matrix_coefficients, int full_range);
 VVR_API int          vvr_output_submit(vvr_context* ctx, const vvr_output_request* req);
 VVR_API int          vvr_output_test(vvr_context* ctx, int ticket);
 VVR_API int          vvr_output_wait(vvr_context* ctx, int ticket);

@@ -1,20 +1,23 @@
 """Pictures per second DELIVERED TO THE HOST while a 10-bit 4:2:0 3840x2160 random-access stream is reconstructed (bench.py's 4k stream and window:
-K timed pictures behind pre-roll and warm-up, every window from the first picture of the stream), four ways in turn in one process:
+K timed pictures behind pre-roll and warm-up, every window from the first picture of the stream), these ways in turn in one process:
   A  the synchronous calls: vvr_wait, then three vvr_read_output (each drains the context) - the only way to output every picture before the queue
   B  the output queue, VVR_OUT_PLANAR16 into pageable memory (the rows leave pinned staging in vvr_output_wait)
   C  the output queue, VVR_OUT_PLANAR16 into memory of vvr_host_alloc (the device copies straight there)
   D  the output queue, VVR_OUT_PACKED10 into memory of vvr_host_alloc
   E  the output queue, VVR_OUT_P010 into memory of vvr_host_alloc
   F  the output queue, VVR_OUT_P010 into device memory (vvr_device_alloc): nothing crosses PCIe
+  G  the output queue, VVR_OUT_RGB16 into device memory: one (3, H, W) tensor per request, BT.709 limited range (k_output_rgb)
+  H  the output queue, VVR_OUT_RGBF16 into device memory, likewise
 and the decode-only rate of the same window (nothing leaves the device).  The ways alternate window by window; every way runs at least --windows
 windows and --min-seconds of timed work; median, minimum and maximum are reported.  Before the timed runs the outputs of A and B of the timed pictures
 are compared (they must be identical).  Requests are submitted without blocking behind their picture and collected when 8 are in flight.
-Kernel time: `rocprofv3 --kernel-trace --stats -- python tools/output_queue_probe.py --ways D --windows 2 --min-seconds 0` in a run of its own.
+Kernel time: `rocprofv3 --kernel-trace --stats -- python tools/output_queue_probe.py --ways D --windows 2 --min-seconds 0` in a run of its own
+(--ways FG: k_output_frame storing P010 and k_output_rgb on the same frames in one trace).
 --frame N: one 3840x2160 10-bit frame instead of a stream, N repeats of every configuration in turn (planar16 and p010 into memory of
-vvr_host_alloc and into device memory): the time of k_output_frame (HIP events around the launch, vvr_get_stats) and the time from
+vvr_host_alloc and into device memory, rgb8 / rgb16 / rgbf16 into device memory): the time of k_output_frame or k_output_rgb (HIP events around the launch, vvr_get_stats) and the time from
 vvr_output_submit to the return of vvr_output_wait, median / minimum / maximum.  --root DIR measures the package of another checkout of the project
 (the parent commit, say) with this script, so that both can run in one call on one box; configurations that checkout does not have are left out.
-Usage: python tools/output_queue_probe.py [--steps 64] [--warmup 16] [--windows 5] [--min-seconds 1.0] [--ways ABCDEFN] [--out FILE]
+Usage: python tools/output_queue_probe.py [--steps 64] [--warmup 16] [--windows 5] [--min-seconds 1.0] [--ways ABCDEFGHN] [--out FILE]
        python tools/output_queue_probe.py --frame 50 [--root DIR] [--out FILE]"""
 import argparse
 import ctypes as C
@@ -41,11 +44,13 @@ def frame_mode(a):
     win = (0, 0, W, H)
 
     def kernel_ms():
-        return sum(s["total_ms"] for s in rec.stats() if s["name"] == "k_output_frame")
+        return sum(s["total_ms"] for s in rec.stats() if s["name"] in ("k_output_frame", "k_output_rgb"))
     configs = {}
-    for fmt in ("planar16", "p010"):
+    if "rgb16" in abi.OUT_FORMATS:
+        rec.set_output_colour(1, False)
+    for fmt in ("planar16", "p010", "rgb8", "rgb16", "rgbf16"):
         for where in ("pinned", "device"):
-            if fmt not in abi.OUT_FORMATS or (where == "device" and not hasattr(rec, "device_array")):
+            if fmt not in abi.OUT_FORMATS or (where == "device" and not hasattr(rec, "device_array")) or (fmt.startswith("rgb") and where == "pinned"):
                 continue
             shapes, dt = abi.output_plane_shapes(win, fmt, None, 3)
             item = np.dtype(dt).itemsize
@@ -53,7 +58,7 @@ def frame_mode(a):
                 planes = [rec.host_array(r * n, dt).reshape(r, n) for r, n in shapes]
             else:
                 import torch
-                planes = [rec.device_array(r * n * item).view(torch.int16).view(r, n) for r, n in shapes]
+                planes = [rec.device_array(r * n * item).view(torch.uint8 if item == 1 else torch.int16).view(r, n) for r, n in shapes]
             configs[fmt + "_" + where] = abi.output_request(0, None, win, fmt, None, (True, False), False, True, planes), planes
     times = {name: ([], []) for name in configs}
     for n in range(3 + a.frame):                  # (the first three rounds warm up: ring entries, scratch)
@@ -67,7 +72,7 @@ def frame_mode(a):
                 times[name][1].append((t1 - t0) * 1e3)
     res = {"mode": "frame", "size": [W, H], "bit_depth": 10, "repeats": a.frame, "root": os.path.abspath(a.root or ROOT)}
     for name, (k, t) in times.items():
-        res[name] = {"k_output_frame_ms": {"median": round(float(np.median(k)), 4), "min": round(min(k), 4), "max": round(max(k), 4)},
+        res[name] = {("k_output_rgb_ms" if name.startswith("rgb") else "k_output_frame_ms"): {"median": round(float(np.median(k)), 4), "min": round(min(k), 4), "max": round(max(k), 4)},
                      "submit_to_completion_ms": {"median": round(float(np.median(t)), 4), "min": round(min(t), 4), "max": round(max(t), 4)}}
     rec.close()
     return res
@@ -79,7 +84,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--min-seconds", type=float, default=1.0)
-    ap.add_argument("--ways", default="ABCDEFN")
+    ap.add_argument("--ways", default="ABCDEFGHN")
     ap.add_argument("--config", default="4k")
     ap.add_argument("--out", default="")
     ap.add_argument("--frame", type=int, default=0)
@@ -116,6 +121,8 @@ def main():
         shapes, dt = abi.output_plane_shapes((0, 0, W, H), fmt, None, 3)
         if device:
             import torch
+            if fmt.startswith("rgb"):      # (as a model takes it: the planes of one contiguous (3, H, W) tensor)
+                return list(rec.device_array(3 * H * W * 2).view(torch.int16).view(3, H, W))
             return [rec.device_array(r * n * 2).view(torch.int16).view(r, n) for r, n in shapes]
         return [rec.host_array(r * n, dt).reshape(r, n) if pinned else np.zeros((r, n), dt) for r, n in shapes]
     sets = {"B": ("planar16", [planes("planar16", False) for _ in range(8)]), "C": ("planar16", [planes("planar16", True) for _ in range(8)]),
@@ -124,10 +131,14 @@ def main():
         sets["E"] = ("p010", [planes("p010", True) for _ in range(8)])
     if "F" in a.ways:
         sets["F"] = ("p010", [planes("p010", False, True) for _ in range(8)])
+    for way, fmt in (("G", "rgb16"), ("H", "rgbf16")):
+        if way in a.ways and fmt in abi.OUT_FORMATS:      # (--root of a checkout without the RGB formats: the ways are left out)
+            rec.set_output_colour(1, False)
+            sets[way] = (fmt, [planes(fmt, False, True) for _ in range(8)])
     reqs = {w: [abi.output_request(0, 0, (0, 0, W, H), fmt, None, (True, False), False, False, p) for p in ps] for w, (fmt, ps) in sets.items()}
     sync_out = planes("planar16", False)
     pcie = {"A": sum(p.nbytes for p in sync_out), "B": sum(p.nbytes for p in sets["B"][1][0]), "C": sum(p.nbytes for p in sets["C"][1][0]),
-            "D": sum(p.nbytes for p in sets["D"][1][0]), "E": W * H * 3, "F": 0, "N": 0}
+            "D": sum(p.nbytes for p in sets["D"][1][0]), "E": W * H * 3, "F": 0, "G": 0, "H": 0, "N": 0}
 
     def run(way, idx, digests=None):
         """the pictures `idx` through vvr_submit, every one of them delivered the way `way` says"""
@@ -188,7 +199,7 @@ def main():
         window("A", da)
         window("B", db)
         res["outputs_A_equal_B"] = len(da) == K and da == db
-    ways = [w for w in "ABCDEFN" if w in a.ways]
+    ways = [w for w in "ABCDEFGHN" if w in a.ways and (w in "AN" or w in sets)]
     times = {w: [] for w in ways}
     for w in ways:                                   # warm-up: every way once (ring entries, pinned staging)
         window(w)

@@ -74,6 +74,8 @@ def lib():
         L.vvr_set_film_grain.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_set_film_grain_seed.restype = C.c_int
         L.vvr_set_film_grain_seed.argtypes = [C.c_void_p, C.c_uint32]
+        L.vvr_set_output_colour.restype = C.c_int
+        L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.vvr_read_output_grain.restype = C.c_int
         L.vvr_read_output_grain.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.vvr_read_dmvr.restype = C.c_int
@@ -114,7 +116,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
@@ -307,6 +309,12 @@ class Reconstructor:
         """the state of the film grain's seed chain (FilmGrain::set_seed; a context starts at 0xdeadbeef)"""
         self._check(self.L.vvr_set_film_grain_seed(self.ctx, seed & 0xffffffff))
 
+    def set_output_colour(self, matrix, full_range=False):
+        """the colour description the "rgb8" / "rgb16" / "rgbf16" formats of output_submit convert with (vvr_set_output_colour): H.273
+        matrix_coefficients 1 (BT.709), 5 or 6 (BT.601) or 9 (BT.2020 non-constant luminance) and video_full_range_flag.  A request takes the
+        value that is set when it is submitted."""
+        self._check(self.L.vvr_set_output_colour(self.ctx, int(matrix), 1 if full_range else 0))
+
     def read_output(self, slot, window=None, bytes_per_sample=2, size=None, collocated=(True, False), grain=False):
         """the picture as the application gets it: conformance window (x, y, w, h in luma samples, even) applied, 8- or 16-bit samples.
         size: (width, height) in luma samples to rescale the window to on the device, as vvdec::rescalePlane does (chroma planes get size >> 1,
@@ -339,7 +347,8 @@ class Reconstructor:
     def output_submit(self, slot, job=None, window=None, fmt="planar16", size=None, collocated=(True, False), grain=False, pinned=False, blocking=True, into=None):
         """vvr_output_submit: the window of `slot` (as `job` leaves it; None: as all work submitted so far leaves it) in the application's form ->
         ticket, or None when blocking=False and the job has not been handed to the device yet.  fmt: "planar16", "planar8", "packed10"
-        (vvdecapp --pyuv: four samples in five bytes), "nv12" or "p010" (two planes: luma, interleaved CbCr; p010: sample << (16 - bit depth));
+        (vvdecapp --pyuv: four samples in five bytes), "nv12" or "p010" (two planes: luma, interleaved CbCr; p010: sample << (16 - bit depth)),
+        "rgb8", "rgb16" or "rgbf16" (three planes R, G, B at the luma size, converted on the device with the matrix of set_output_colour: vvr.h);
         size, collocated, grain as read_output - and grain with size is the reference's chain,
         grain first, then the rescale of the grained frame.  pinned: the planes are allocated in memory of the context that the device writes
         directly (vvr_host_alloc) - they belong to the context and are views valid until close().
@@ -347,11 +356,18 @@ class Reconstructor:
         format: abi.output_plane_shapes): the device writes them, nothing crosses PCIe; they are registered with the context for the life of
         the request and output_wait returns them.  The tensors must be idle now and stay untouched until the request has completed
         (output_wait, output_test, or output_stream_wait on the stream that uses them).  At most 8 requests in flight (VvrError).
+        The RGB formats also take one 3-D tensor of shape (3, h, w) whose last dimension is contiguous (planes and rows may be padded or
+        sliced); output_wait returns that tensor.
         Ask for a picture's output before the next picture into its slot is submitted: that picture then waits for the request on the device."""
         win = tuple(window or (0, 0, self.width, self.height))
         shapes, dt = abi.output_plane_shapes(win, fmt, size, 3 if self.chroma_format else 1)
         registered = []
+        whole = None
         if into is not None:
+            if hasattr(into, "dim") and into.dim() == 3:      # (3, h, w): its planes, registered as one range
+                if len(shapes) != 3 or into.shape[0] != 3 or min(into.stride()) < 0:
+                    raise ValueError("output_submit: a 3-D tensor serves the RGB formats, as (3, h, w)")
+                whole = into
             planes = list(into)
             if len(planes) != len(shapes):
                 raise ValueError("output_submit: %s needs %d planes" % (fmt, len(shapes)))
@@ -359,8 +375,8 @@ class Reconstructor:
                 if not t.is_cuda or t.device.index != self.cfg.device or t.dim() != 2 or tuple(t.shape) != tuple(shape) or t.element_size() != np.dtype(dt).itemsize or (t.shape[1] > 1 and t.stride(1) != 1):
                     raise ValueError("output_submit: into needs row-major 2-D tensors on the context's device, here of shape %r and %d-byte elements" % (shape, np.dtype(dt).itemsize))
             try:
-                for t in planes:
-                    ptr, n = t.data_ptr(), ((t.shape[0] - 1) * t.stride(0) + t.shape[1]) * t.element_size()
+                for t in [whole] if whole is not None else planes:
+                    ptr, n = t.data_ptr(), (sum((d - 1) * st for d, st in zip(t.shape, t.stride())) + 1) * t.element_size()
                     if any(a <= ptr and ptr + n <= a + m for a, m in self._dev):
                         continue
                     self._check(self.L.vvr_device_register(self.ctx, ptr, n))
@@ -379,7 +395,7 @@ class Reconstructor:
         self._check(ticket)
         if not blocking and ticket == abi.VVR_NOT_READY:
             return None
-        self._out[ticket] = planes
+        self._out[ticket] = planes if whole is None else whole
         self._reg[ticket] = registered
         return ticket
 
@@ -401,7 +417,7 @@ class Reconstructor:
 
     def output_wait(self, ticket):
         """vvr_output_wait: blocks for this request only and retires the ticket -> list of planes (packed10: uint8 arrays of (rows, w / 4 * 5); the
-        tensors of output_submit(into=...), which are unregistered here)"""
+        tensors - or the one (3, h, w) tensor - of output_submit(into=...), which are unregistered here)"""
         try:
             self._check(self.L.vvr_output_wait(self.ctx, ticket))
             return self._out[ticket]

@@ -160,8 +160,9 @@ def film_grain_bank(comp_present, shift, scale_lut, pattern_lut, pattern):
     return b
 
 
-OUT_PLANAR16, OUT_PLANAR8, OUT_PACKED10, OUT_NV12, OUT_P010 = 0, 1, 2, 16, 17
-OUT_FORMATS = {"planar16": OUT_PLANAR16, "planar8": OUT_PLANAR8, "packed10": OUT_PACKED10, "nv12": OUT_NV12, "p010": OUT_P010}
+OUT_PLANAR16, OUT_PLANAR8, OUT_PACKED10, OUT_NV12, OUT_P010, OUT_RGB8, OUT_RGB16, OUT_RGBF16 = 0, 1, 2, 16, 17, 32, 33, 34
+OUT_FORMATS = {"planar16": OUT_PLANAR16, "planar8": OUT_PLANAR8, "packed10": OUT_PACKED10, "nv12": OUT_NV12, "p010": OUT_P010,
+               "rgb8": OUT_RGB8, "rgb16": OUT_RGB16, "rgbf16": OUT_RGBF16}
 
 
 class OutputRequest(C.Structure):
@@ -189,9 +190,12 @@ def output_request(slot, job, window, fmt, size, collocated, grain, blocking, pl
 
 def output_plane_shapes(window, fmt, size, ncomp):
     """(rows, bytes or samples per row) of every plane a request produces, and the dtype: packed10 rows are w / 4 * 5 bytes; the semi-planar
-    formats have two planes, luma and the interleaved CbCr rows of 2 * (w >> 1) samples (nv12: uint8, p010: uint16)"""
+    formats have two planes, luma and the interleaved CbCr rows of 2 * (w >> 1) samples (nv12: uint8, p010: uint16); the RGB formats three
+    planes at the luma size (rgb8: uint8, rgb16: uint16, rgbf16: float16)"""
     import numpy as np
     w, h = size or (window[2], window[3])
+    if fmt in ("rgb8", "rgb16", "rgbf16"):
+        return [(h, w)] * 3, {"rgb8": np.uint8, "rgb16": np.uint16, "rgbf16": np.float16}[fmt]
     shapes = [(h >> (1 if c else 0), w >> (1 if c else 0)) for c in range(ncomp)]
     if fmt in ("nv12", "p010"):
         return [(h, w), (h >> 1, 2 * (w >> 1))], np.uint8 if fmt == "nv12" else np.uint16

@@ -20,6 +20,7 @@
 // There is NO CPU fallback: without a gfx950 device every entry point fails with VVR_ERR_NO_DEVICE.
 #include "vvr_host.h"
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -89,7 +90,7 @@ static double g_wdSum[6]; static uint64_t g_wdJobs; static double g_wdPart[4], g
 
 struct Stat { uint64_t launches = 0; double ms = 0, bytes = 0; };
 struct PendingTiming { hipEvent_t a, b; int kernel; double bytes; };
-const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame" };
+const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame", "k_output_rgb" };
 
 // One slot of the upload ring: pinned staging memory and its image in HBM (grown on demand, never freed while the context lives), the device
 // pointers of the picture that currently sits in it, and the pinned landing area of its DMVR delta MVs.
@@ -171,6 +172,8 @@ struct vvr_context {
   // film grain at the output (vvr_set_film_grain): the bank, its device copy (uploaded on the stream of the first grain read after a change) and
   // the seed chain (FilmGrain::m_line_rnd)
   std::unique_ptr<vvr_film_grain_bank> grainBank; void* grainBankDev = nullptr; bool grainBankStale = false; uint32_t grainSeed = 0xdeadbeefu;
+  // colour description of the RGB formats of the output queue (vvr_set_output_colour): H.273 matrix_coefficients (0: none set) and the range flag
+  int        outMatrix = 0, outFullRange = 0;
   // ---- job pipeline (everything below is guarded by mu)
   std::mutex mu, commitMu;              // commitMu: one committing thread at a time (it takes mu only around its bookkeeping)
   std::condition_variable cv;

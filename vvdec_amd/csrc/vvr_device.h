@@ -178,6 +178,20 @@ struct OutputFrameParams
   int format, shift;
 };
 void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst );
+// a frame of the output queue as planar R'G'B' (VVR_OUT_RGB8 / _RGB16 / _RGBF16, the definition: vvr.h): one 4:2:0 frame of w x h luma samples
+// (even; the chroma planes w / 2 x h / 2), chroma brought to the luma grid by the 4-tap DCTIF at the two phases `collocated` selects per direction
+// (taps clamped to the frame), then the Q14 matrix.  Three planes of w x h samples leave, rows back to back, into dst + dstOff[c] (256-byte
+// aligned) or direct[c] (32-byte aligned memory of the caller's); nothing behind a plane's last sample is written in either.
+struct OutputRgbParams
+{
+  const pel_t* src[3]; int stride[3], w, h; size_t dstOff[3];
+  uint8_t* direct[3];
+  int format, collocated;
+  int maxVal, yoff, coff;      // 2^bd - 1; 16 << ( bd - 8 ) or 0; 2^( bd - 1 )
+  int cy, rv, gu, gv, bu, maxOut;      // the Q14 coefficients (vvr_output.inc, rgb_coefficients), 2^od - 1
+  float inv;                   // VVR_OUT_RGBF16: float32( 1 ) / float32( 2^bd - 1 )
+};
+void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
 void launch_mc_affine( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );
 void launch_mc_rpr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );      // tiles of CUs with a scaled reference picture
 void launch_mc_dmvr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems, int32_t* dmvrOut );

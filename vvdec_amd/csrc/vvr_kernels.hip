@@ -5031,6 +5031,174 @@ void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst )
   if( total ) hipLaunchKernelGGL( k_output_frame, dim3( total ), dim3( 256 ), 0, s, p, (uint8_t*) dst );
 }
 
+// k_output_rgb — a 4:2:0 frame of the output queue as planar R'G'B' (the definition: vvr.h): chroma to the luma grid with the 4-tap DCTIF in
+// sampleRateConvCore's two passes (horizontal sums unnormalised, ( sum + 2048 ) >> 12 and the clip after the vertical pass), then the Q14 matrix,
+// the clip and the store as bytes, 16-bit words or halves - one launch, every source sample read from HBM once, nothing at 4:4:4 written but the result.
+// A workgroup owns 64 x 32 output samples.  It stages the tile's 32 x 16 chroma samples of both planes with their halo of two columns / rows on
+// every side (taps clamped to the frame) in LDS, then writes the horizontal sums of the 20 staged rows at the tile's 64 columns there as int32.
+// With 2:1 the positions are 16 * i - ( collocated ? 0 : 8 ) in 1/32 samples: a direction has two phases, 0 and 16 or 24 and 8, for even and odd
+// i - fixed tap sets (rows 0, 16, 24 and 8 of vvc_chroma_filter), no table; the chroma positions, the format and the store are template parameters.  A lane owns 8 consecutive samples of one row: its luma is one
+// 16-byte load issued before the staging, the vertical pass over the sums, the matrix and the conversion run in registers, its store per plane is
+// whole (8 or 16 bytes) when the width is a multiple of 8 - every lane's address is aligned then - and goes pair by pair otherwise (the width is even).
+#define RGB_TW 64
+#define RGB_TH 32
+#define RGB_CW ( RGB_TW / 2 + 4 )
+#define RGB_CH ( RGB_TH / 2 + 4 )
+#define RGB_SW ( RGB_TW + 4 )      // a row of sums, padded: rows that differ by one do not meet in the same LDS banks
+// VVR_OUT_RGBF16: one float32 multiply, one conversion that rounds to nearest even (v_mul_f32, v_cvt_f16_f32 in the default rounding mode).  The
+// empty asm keeps the product in a register of its own: without it the two fold into one v_fma_mixlo_f16, which is not the operation vvr.h defines
+__device__ __forceinline__ uint32_t rgb_half( int v, float inv )
+{
+  float f = (float) v * inv;
+  asm volatile( "" : "+v"( f ) );
+  return __builtin_bit_cast( uint16_t, (_Float16) f );
+}
+typedef uint32_t __attribute__(( aligned( 2 ) )) rgb_uint_u;
+// the lane's 8 samples of one plane, stored at sample i0 of it: WHOLE - 8 bytes, or 16 of words or halves; every lane's address is aligned when the
+// width is a multiple of 8 - or the n samples that exist, pair by pair.  (WHOLE is a template parameter: with both paths in one kernel the compiler
+// shares a dword store between them and splits the whole one.)
+template<int FMT, bool WHOLE>
+__device__ __forceinline__ void rgb_store( uint8_t* __restrict__ plane, size_t i0, const int ( &v )[8], float inv, int n )
+{
+  if( FMT == VVR_OUT_RGB8 )
+  {
+    const uint32_t lo = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24, hi = v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24;
+    uint8_t* o = plane + i0;
+    if( WHOLE ) *(uint2*) o = make_uint2( lo, hi );
+    else
+    {
+      *(uint16_t*) o = (uint16_t) lo;
+      if( n > 2 ) *(uint16_t*) ( o + 2 ) = (uint16_t) ( lo >> 16 );
+      if( n > 4 ) *(uint16_t*) ( o + 4 ) = (uint16_t) hi;
+      if( n > 6 ) *(uint16_t*) ( o + 6 ) = (uint16_t) ( hi >> 16 );
+    }
+  }
+  else
+  {
+    uint32_t d0, d1, d2, d3;
+    if( FMT == VVR_OUT_RGB16 ) { d0 = v[0] | v[1] << 16; d1 = v[2] | v[3] << 16; d2 = v[4] | v[5] << 16; d3 = v[6] | v[7] << 16; }
+    else
+    {
+      d0 = rgb_half( v[0], inv ) | rgb_half( v[1], inv ) << 16; d1 = rgb_half( v[2], inv ) | rgb_half( v[3], inv ) << 16;
+      d2 = rgb_half( v[4], inv ) | rgb_half( v[5], inv ) << 16; d3 = rgb_half( v[6], inv ) | rgb_half( v[7], inv ) << 16;
+    }
+    uint32_t* o = (uint32_t*) ( plane + i0 * 2 );
+    if( WHOLE ) *(uint4*) o = make_uint4( d0, d1, d2, d3 );
+    else
+    {
+      o[0] = d0;
+      if( n > 2 ) o[1] = d1;
+      if( n > 4 ) o[2] = d2;
+      if( n > 6 ) o[3] = d3;
+    }
+  }
+}
+template<int COL, int FMT, bool WHOLE>
+__global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_t* __restrict__ dst )
+{
+  __shared__ uint16_t rgb_raw[2][RGB_CH][RGB_CW];
+  __shared__ __attribute__(( aligned( 16 ) )) int rgb_sum[2][RGB_CH][RGB_SW];
+  constexpr bool COLX = ( COL & 1 ) != 0, COLY = ( COL & 2 ) != 0;
+  const int tid = threadIdx.x, X0 = blockIdx.x * RGB_TW, Y0 = blockIdx.y * RGB_TH;
+  // the lane's 8 luma samples (2-byte aligned in general, as k_output_frame's piece); a row that ends inside them: pair by pair
+  const int jj = tid >> 3, xl = ( tid & 7 ) * 8, x = X0 + xl, y = Y0 + jj, n = WHOLE ? 8 : min( 8, p.w - x );
+  const bool live = x < p.w && y < p.h;
+  uint4 yy = make_uint4( 0, 0, 0, 0 );
+  if( live )
+  {
+    const pel_t* __restrict__ row = p.src[0] + (size_t) y * p.stride[0] + x;
+    if( n == 8 ) __builtin_memcpy( &yy, row, 16 );      // (one 16-byte load: unaligned access mode)
+    else
+    {
+      yy.x = *(const rgb_uint_u*) row;
+      if( n > 2 ) yy.y = *(const rgb_uint_u*) ( row + 2 );
+      if( n > 4 ) yy.z = *(const rgb_uint_u*) ( row + 4 );
+    }
+  }
+  // chroma columns cx0 .. cx0 + 35 and rows cy0 .. cy0 + 19 of both planes, clamped to the frame
+  const int cw = p.w >> 1, ch = p.h >> 1, cx0 = ( X0 >> 1 ) - 2, cy0 = ( Y0 >> 1 ) - 2;
+  constexpr int STAGED = 2 * RGB_CH * RGB_CW, PER_LANE = ( STAGED + 255 ) / 256;
+  uint16_t staged[PER_LANE];
+#pragma unroll
+  for( int i = 0; i < PER_LANE; i++ )      // (all loads in flight before the first LDS store)
+  {
+    const int t = min( tid + 256 * i, STAGED - 1 ), pl = t / ( RGB_CH * RGB_CW ), rem = t - pl * ( RGB_CH * RGB_CW ), r = rem / RGB_CW, cc = rem - r * RGB_CW;
+    const pel_t* __restrict__ s = pl ? p.src[2] : p.src[1];
+    staged[i] = (uint16_t) s[(size_t) clip3( 0, ch - 1, cy0 + r ) * ( pl ? p.stride[2] : p.stride[1] ) + clip3( 0, cw - 1, cx0 + cc )];
+  }
+#pragma unroll
+  for( int i = 0; i < PER_LANE; i++ ) if( tid + 256 * i < STAGED ) ( &rgb_raw[0][0][0] )[tid + 256 * i] = staged[i];
+  __syncthreads();
+  // horizontal pass: output columns 2 k (phase 0 or 24) and 2 k + 1 (phase 16 or 8) of a staged row; c[2] is the chroma sample at column k of the tile
+  for( int u = tid; u < 2 * RGB_CH * ( RGB_TW / 2 ); u += 256 )
+  {
+    const int k = u & ( RGB_TW / 2 - 1 ), rr = u / ( RGB_TW / 2 ), pl = rr / RGB_CH, r = rr - pl * RGB_CH;
+    const uint16_t* c = &rgb_raw[pl][r][k];
+    int ev, od;
+    if( COLX ) { ev = 64 * c[2];                                  od = -4 * c[1] + 36 * c[2] + 36 * c[3] - 4 * c[4]; }
+    else       { ev = -2 * c[0] + 16 * c[1] + 54 * c[2] - 4 * c[3]; od = -4 * c[1] + 54 * c[2] + 16 * c[3] - 2 * c[4]; }
+    *(int2*) &rgb_sum[pl][r][2 * k] = make_int2( ev, od );
+  }
+  __syncthreads();
+  if( !live ) return;
+  // vertical pass: row y = Y0 + jj takes the staged rows f .. f + 3 with the taps of its phase
+  const bool odd = jj & 1;
+  const int f = ( jj >> 1 ) + ( COLY || odd ? 1 : 0 );
+  const int c0 = COLY ? ( odd ? -4 : 0 ) : ( odd ? -4 : -2 ), c1 = COLY ? ( odd ? 36 : 64 ) : ( odd ? 54 : 16 );
+  const int c2 = COLY ? ( odd ? 36 : 0 ) : ( odd ? 16 : 54 ), c3 = COLY ? ( odd ? -4 : 0 ) : ( odd ? -2 : -4 );
+  int uv[2][8];
+#pragma unroll
+  for( int pl = 0; pl < 2; pl++ )
+  {
+    int4 a[4][2];
+#pragma unroll
+    for( int t = 0; t < 4; t++ ) { a[t][0] = *(const int4*) &rgb_sum[pl][f + t][xl]; a[t][1] = *(const int4*) &rgb_sum[pl][f + t][xl + 4]; }
+#pragma unroll
+    for( int hlf = 0; hlf < 2; hlf++ )
+    {
+      uv[pl][4 * hlf + 0] = c0 * a[0][hlf].x + c1 * a[1][hlf].x + c2 * a[2][hlf].x + c3 * a[3][hlf].x;
+      uv[pl][4 * hlf + 1] = c0 * a[0][hlf].y + c1 * a[1][hlf].y + c2 * a[2][hlf].y + c3 * a[3][hlf].y;
+      uv[pl][4 * hlf + 2] = c0 * a[0][hlf].z + c1 * a[1][hlf].z + c2 * a[2][hlf].z + c3 * a[3][hlf].z;
+      uv[pl][4 * hlf + 3] = c0 * a[0][hlf].w + c1 * a[1][hlf].w + c2 * a[2][hlf].w + c3 * a[3][hlf].w;
+    }
+  }
+  int R[8], G[8], B[8];
+#pragma unroll
+  for( int i = 0; i < 8; i++ )
+  {
+    const uint32_t y2 = i < 2 ? yy.x : ( i < 4 ? yy.y : ( i < 6 ? yy.z : yy.w ) );
+    const int Y = (int) ( ( y2 >> ( 16 * ( i & 1 ) ) ) & 0xffff ) - p.yoff;
+    const int u = clip3( 0, p.maxVal, ( uv[0][i] + 2048 ) >> 12 ) - p.coff, v = clip3( 0, p.maxVal, ( uv[1][i] + 2048 ) >> 12 ) - p.coff;
+    const int l = p.cy * Y + 8192;
+    R[i] = clip3( 0, p.maxOut, ( l + p.rv * v ) >> 14 );
+    G[i] = clip3( 0, p.maxOut, ( l + p.gu * u + p.gv * v ) >> 14 );
+    B[i] = clip3( 0, p.maxOut, ( l + p.bu * u ) >> 14 );
+  }
+  const size_t i0 = (size_t) y * p.w + x;
+  rgb_store<FMT, WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, p.inv, n );
+  rgb_store<FMT, WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, G, p.inv, n );
+  rgb_store<FMT, WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, B, p.inv, n );
+}
+template<int FMT, bool WHOLE>
+static void launch_output_rgb_as( hipStream_t s, const OutputRgbParams& p, void* dst )
+{
+  const dim3 grid( ( p.w + RGB_TW - 1 ) / RGB_TW, ( p.h + RGB_TH - 1 ) / RGB_TH );
+  switch( p.collocated & 3 )
+  {
+  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  default: hipLaunchKernelGGL( ( k_output_rgb<3, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  }
+}
+void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst )
+{
+  const bool whole = ( p.w & 7 ) == 0;      // (rows of a multiple of 8 samples: every lane has 8, at an aligned address)
+  if( p.format == VVR_OUT_RGB8 )       { if( whole ) launch_output_rgb_as<VVR_OUT_RGB8, true>( s, p, dst );   else launch_output_rgb_as<VVR_OUT_RGB8, false>( s, p, dst ); }
+  else if( p.format == VVR_OUT_RGB16 ) { if( whole ) launch_output_rgb_as<VVR_OUT_RGB16, true>( s, p, dst );  else launch_output_rgb_as<VVR_OUT_RGB16, false>( s, p, dst ); }
+  else                                 { if( whole ) launch_output_rgb_as<VVR_OUT_RGBF16, true>( s, p, dst ); else launch_output_rgb_as<VVR_OUT_RGBF16, false>( s, p, dst ); }
+}
+
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in
 __device__ __forceinline__ uint32_t crc_mul( uint32_t a, uint32_t b )
 {

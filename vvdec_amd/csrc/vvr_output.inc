@@ -85,6 +85,29 @@ uint32_t grain_words( uint32_t state, int nbx, int nby, uint32_t* words )
   }
   return seed;
 }
+
+// the colour description of the RGB formats (vvr.h): Kr, Kb of an H.273 matrix_coefficients code point the queue accepts, and the five Q14
+// coefficients cy, rv, gu, gv, bu of a conversion from bd to od bits, q( v ) = floor( v * 16384 + 0.5 ) in double
+bool rgb_matrix( int matrix, double& kr, double& kb )
+{
+  switch( matrix )
+  {
+  case 1:         kr = 0.2126; kb = 0.0722; return true;      // BT.709
+  case 5: case 6: kr = 0.299;  kb = 0.114;  return true;      // BT.601 (625 and 525 lines)
+  case 9:         kr = 0.2627; kb = 0.0593; return true;      // BT.2020 non-constant luminance
+  }
+  return false;
+}
+void rgb_coefficients( int matrix, int fullRange, int bd, int od, OutputRgbParams& p )
+{
+  double kr = 0, kb = 0; rgb_matrix( matrix, kr, kb );
+  const double kg = 1 - kr - kb, m = ( 1 << od ) - 1, s = 1 << ( bd - 8 );
+  const double ys = fullRange ? m / ( ( 1 << bd ) - 1 ) : m / ( 219 * s ), cs = fullRange ? ys : m / ( 224 * s );
+  auto q = []( double v ) { return (int) std::floor( v * 16384 + 0.5 ); };
+  p.cy = q( ys ); p.rv = q( 2 * ( 1 - kr ) * cs ); p.gu = -q( 2 * kb * ( 1 - kb ) / kg * cs ); p.gv = -q( 2 * kr * ( 1 - kr ) / kg * cs ); p.bu = q( 2 * ( 1 - kb ) * cs );
+  p.maxVal = ( 1 << bd ) - 1; p.maxOut = ( 1 << od ) - 1; p.yoff = fullRange ? 0 : 16 << ( bd - 8 ); p.coff = 1 << ( bd - 1 );
+  p.inv = 1.0f / (float) ( ( 1 << bd ) - 1 );
+}
 }   // namespace
 
 #if !defined(__HIPCC__)
@@ -198,6 +221,64 @@ void launch_output_frame( hipStream_t, OutputFrameParams p, void* dst )
       }
     }
 }
+
+// ... and launch_output_rgb (k_output_rgb): the definition of vvr.h sample by sample - positions, phases and taps from the table as launch_rescale
+// takes them (step 16, add 0 / -8, shift 0, the chroma filter), the matrix, the three stores
+namespace {
+uint16_t rgb_half_rne( float f )      // 0 or 1 / 1023 <= f <= 1: zero or a normal half; round to nearest even (a carry out of the mantissa raises the exponent)
+{
+  uint32_t b; memcpy( &b, &f, 4 );
+  if( !b ) return 0;
+  uint32_t h = ( ( b >> 23 ) - 127 + 15 ) << 10 | ( b & 0x7fffff ) >> 13;
+  const uint32_t rem = b & 0x1fff;
+  if( rem > 0x1000 || ( rem == 0x1000 && ( h & 1 ) ) ) h++;
+  return (uint16_t) h;
+}
+}
+void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
+{
+  const int cw = p.w / 2, ch = p.h / 2;
+  std::vector<int> sums( (size_t) ch * p.w ), up[2];
+  for( int pl = 0; pl < 2; pl++ )
+  {
+    const pel_t* src = p.src[1 + pl];
+    up[pl].resize( (size_t) p.w * p.h );
+    for( int i = 0; i < p.w; i++ )
+    {
+      const int refPos = 16 * i - ( p.collocated & 1 ? 0 : 8 ), integer = refPos >> 5, frac = refPos & 31;
+      for( int j = 0; j < ch; j++ )
+      {
+        int sum = 0;
+        for( int k = 0; k < 4; k++ ) sum += rescale_host_tbl::vvc_chroma_filter[frac][k] * src[(size_t) j * p.stride[1 + pl] + std::min( std::max( 0, integer + k - 1 ), cw - 1 )];
+        sums[(size_t) j * p.w + i] = sum;
+      }
+    }
+    for( int j = 0; j < p.h; j++ )
+    {
+      const int refPos = 16 * j - ( p.collocated & 2 ? 0 : 8 ), integer = refPos >> 5, frac = refPos & 31;
+      for( int i = 0; i < p.w; i++ )
+      {
+        int sum = 0;
+        for( int k = 0; k < 4; k++ ) sum += rescale_host_tbl::vvc_chroma_filter[frac][k] * sums[(size_t) std::min( std::max( 0, integer + k - 1 ), ch - 1 ) * p.w + i];
+        up[pl][(size_t) j * p.w + i] = std::min( std::max( 0, ( sum + 2048 ) >> 12 ), p.maxVal );
+      }
+    }
+  }
+  for( int j = 0; j < p.h; j++ )
+    for( int i = 0; i < p.w; i++ )
+    {
+      const size_t at = (size_t) j * p.w + i;
+      const int y = p.src[0][(size_t) j * p.stride[0] + i] - p.yoff, u = up[0][at] - p.coff, v = up[1][at] - p.coff;
+      const int rgb[3] = { ( p.cy * y + p.rv * v + 8192 ) >> 14, ( p.cy * y + p.gu * u + p.gv * v + 8192 ) >> 14, ( p.cy * y + p.bu * u + 8192 ) >> 14 };
+      for( int c = 0; c < 3; c++ )
+      {
+        const int val = std::min( std::max( 0, rgb[c] ), p.maxOut );
+        uint8_t* out = p.direct[c] ? p.direct[c] : (uint8_t*) dst + p.dstOff[c];
+        if( p.format == VVR_OUT_RGB8 ) out[at] = (uint8_t) val;
+        else ( (uint16_t*) out )[at] = p.format == VVR_OUT_RGB16 ? (uint16_t) val : rgb_half_rne( (float) val * p.inv );
+      }
+    }
+}
 #endif
 
 extern "C" {
@@ -282,6 +363,17 @@ VVR_API int vvr_set_film_grain_seed( vvr_context* c, uint32_t seed )
 {
   if( !c ) return VVR_ERR_PARAMETER;
   c->grainSeed = seed;
+  return VVR_OK;
+}
+
+VVR_API int vvr_set_output_colour( vvr_context* c, int matrixCoefficients, int fullRange )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  double kr, kb;
+  if( !rgb_matrix( matrixCoefficients, kr, kb ) ) { c->setError( "vvr_set_output_colour: matrix_coefficients must be 1 (BT.709), 5 or 6 (BT.601) or 9 (BT.2020 non-constant luminance)" ); return VVR_ERR_PARAMETER; }
+  if( fullRange != 0 && fullRange != 1 ) { c->setError( "vvr_set_output_colour: full_range must be 0 or 1" ); return VVR_ERR_PARAMETER; }
+  c->outMatrix = matrixCoefficients; c->outFullRange = fullRange;
   return VVR_OK;
 }
 
@@ -451,13 +543,13 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 
 // =====================================================================================================================
 // output queue: the output stage as a pipeline.  A request is ordered behind its picture's `done` event on the context's output stream,
-// runs there (k_film_grain, k_rescale, k_output_frame as the request needs them), leaves through a ring entry (device scratch + pinned
+// runs there (k_film_grain, k_rescale, k_output_frame or k_output_rgb as the request needs them), leaves through a ring entry (device scratch + pinned
 // staging) and is collected with its ticket.  Nothing here calls vvr_sync.  The slot is protected the way an external reader's is
 // (vvr_slot_external_event): the entry's `read` event, recorded behind the last kernel of the request, is registered with the slot, so a
 // picture submitted afterwards that overwrites the slot waits for it on the device - not for the copy to the host.
 // k_rescale and k_film_grain reach the packed format and the chained case with at most one extra pass through HBM: they store 16-bit samples
-// into the entry's scratch (`tmp`) and k_output_frame packs (or interleaves: NV12, P010) from there; into the planar formats they store directly
-// as ever.
+// into the entry's scratch (`tmp`) and k_output_frame packs (or interleaves: NV12, P010) from there, or k_output_rgb converts from there (the RGB
+// formats; a plain request converts straight from the slot); into the planar formats they store directly as ever.
 // A request whose destination planes lie in device memory the context knows (vvr_device_alloc / vvr_device_register) moves nothing over PCIe:
 // k_output_frame stores a plane whose rows are back to back at a 32-byte aligned base straight into it, exactly its bytes; every other plane
 // (padded rows, odd bases, the planes k_film_grain / k_rescale store themselves) goes through the entry's scratch and one device-to-device
@@ -535,12 +627,22 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( rq->struct_size != sizeof( vvr_output_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_output_request )" );
   const int slot = rq->slot, bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot" );
-  if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 ) return outRefuse( c, "unknown format" );
+  const bool rgb = rq->format == VVR_OUT_RGB8 || rq->format == VVR_OUT_RGB16 || rq->format == VVR_OUT_RGBF16;
+  if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 && !rgb ) return outRefuse( c, "unknown format" );
   if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1" );
   const bool packed = rq->format == VVR_OUT_PACKED10, semi = rq->format == VVR_OUT_NV12 || rq->format == VVR_OUT_P010, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
-  const bool viaTmp = packed || semi;      // k_output_frame makes the format: the stages before it store 16-bit samples into `tmp`
+  const bool viaTmp = packed || semi || rgb;      // k_output_frame / k_output_rgb makes the format: the stages before it store 16-bit samples into `tmp`
   const bool narrow = rq->format == VVR_OUT_PLANAR8 || rq->format == VVR_OUT_NV12;
-  const int bps = narrow ? 1 : 2, nOut = semi ? 2 : nc;
+  const int bps = narrow || rq->format == VVR_OUT_RGB8 ? 1 : 2, nOut = semi ? 2 : nc;
+  int outMatrix = 0, outFullRange = 0;      // (the colour description: looked at here for the refusal, taken under mu where the request is accepted)
+  if( rgb )
+  {
+    { std::lock_guard<std::mutex> lk( c->mu ); outMatrix = c->outMatrix; outFullRange = c->outFullRange; }
+    if( nc == 1 ) return outRefuse( c, "RGB output of a 4:0:0 context: there is no chroma to convert" );
+    if( !outMatrix ) return outRefuse( c, "RGB output with no colour description set (vvr_set_output_colour)" );
+    if( bd < 8 || bd > 10 ) return outRefuse( c, "RGB output needs a bit depth of 8, 9 or 10" );
+    if( scaled && ( ( rq->out_w | rq->out_h ) & 1 ) ) return outRefuse( c, "RGB output needs an even out_w and out_h (one 4:2:0 frame is converted)" );
+  }
   if( semi && nc == 1 ) return outRefuse( c, "semi-planar output of a 4:0:0 context: there is no chroma to interleave" );
   if( rq->format == VVR_OUT_P010 && ( bd < 8 || bd > 10 ) ) return outRefuse( c, "P010 output needs a bit depth of 8, 9 or 10" );
   if( narrow && bd > 8 ) return outRefuse( c, "8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" );
@@ -553,7 +655,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     if( bd != 8 && bd != 10 ) return outRefuse( c, "film grain needs a bit depth of 8 or 10 (FilmGrainImpl::set_depth)" );
     if( w <= 128 ) return outRefuse( c, "film grain needs a frame wider than 128 samples (FilmGrainImpl::add_grain_block)" );
   }
-  int pw[3], ph[3], ow[3], oh[3]; bool resc[3] = { false, false, false }, anyResc = false;
+  int pw[3], ph[3], ow[3], oh[3], outRows[3]; bool resc[3] = { false, false, false }, anyResc = false;
   size_t rowBytes[3] = { 0, 0, 0 };
   for( int k = 0; k < nc; k++ )
   {
@@ -563,7 +665,8 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
       return outRefuse( c, "output sides must be 1..8192 and within 1/8 .. 8 times the window's" );
     resc[k] = ow[k] != pw[k] || oh[k] != ph[k]; anyResc |= resc[k];
     if( packed && ( ow[k] & 3 ) ) return outRefuse( c, "packed 10-bit output needs plane widths that are multiples of 4 (four samples in five bytes)" );
-    rowBytes[k] = packed ? (size_t) ow[k] / 4 * 5 : (size_t) ow[k] * bps * ( semi && k ? 2 : 1 );      // (semi-planar plane 1: Cb and Cr interleaved)
+    rowBytes[k] = packed ? (size_t) ow[k] / 4 * 5 : (size_t) ow[rgb ? 0 : k] * bps * ( semi && k ? 2 : 1 );      // (semi-planar plane 1: Cb and Cr interleaved; RGB: every plane at the luma size)
+    outRows[k] = oh[rgb ? 0 : k];
     if( k < nOut && ( !rq->dst[k] || rq->dst_stride_bytes[k] < rowBytes[k] ) ) return outRefuse( c, "missing plane or stride below the output's row" );
   }
   hipSetDevice( c->device );
@@ -617,7 +720,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   size_t extent[3] = { 0, 0, 0 }; int devPlanes = 0;
   for( int k = 0; k < nOut; k++ )
   {
-    extent[k] = (size_t) ( oh[k] - 1 ) * rq->dst_stride_bytes[k] + rowBytes[k];
+    extent[k] = (size_t) ( outRows[k] - 1 ) * rq->dst_stride_bytes[k] + rowBytes[k];
     const char* b = (const char*) rq->dst[k];
     for( const DevRange& r : c->devRanges )
     {
@@ -627,6 +730,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   }
   if( devPlanes && devPlanes != nOut ) { c->setError( "vvr_output_submit: destination planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
   const bool devDst = devPlanes != 0;
+  if( rgb ) { outMatrix = c->outMatrix; outFullRange = c->outFullRange; }      // (what is set now, behind the waits above: a description cannot be unset)
   e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
   e->job = rq->job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = nOut;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
@@ -639,8 +743,8 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   {
     const bool frameStores = viaTmp || !( ( grain && !grainTmp ) || resc[k] );      // (else k_film_grain / k_rescale store the plane themselves)
     kdirect[k] = devDst && frameStores && rq->dst_stride_bytes[k] == rowBytes[k] && ( (uintptr_t) rq->dst[k] & 31 ) == 0;
-    e->off[k] = total; e->rowBytes[k] = rowBytes[k]; e->rows[k] = oh[k]; e->dst[k] = rq->dst[k]; e->dstStride[k] = rq->dst_stride_bytes[k]; e->extent[k] = extent[k];
-    if( !kdirect[k] ) total += outRegion( rowBytes[k] * oh[k] );
+    e->off[k] = total; e->rowBytes[k] = rowBytes[k]; e->rows[k] = outRows[k]; e->dst[k] = rq->dst[k]; e->dstStride[k] = rq->dst_stride_bytes[k]; e->extent[k] = extent[k];
+    if( !kdirect[k] ) total += outRegion( rowBytes[k] * outRows[k] );
     direct = direct && ( devDst || c->pinned.contains( rq->dst[k], extent[k] ) );
   }
   for( int k = 0; k < nc; k++ )
@@ -709,7 +813,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   }
   OutputFrameParams fp; memset( &fp, 0, sizeof( fp ) );
   double frameBytes = 0;
-  for( int k = 0; k < nc; k++ )
+  for( int k = 0; k < nc && !rgb; k++ )
     if( !cur[k].inOut )
     {
       fp.src[k] = cur[k].p; fp.stride[k] = cur[k].stride; frameBytes += (double) ow[k] * oh[k] * 2 + ( k < nOut ? (double) rowBytes[k] * oh[k] : 0. );
@@ -726,6 +830,21 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     launch_output_frame( s, fp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
   }
+  if( rgb )
+  {
+    // the frame as it stands - the slot's window, or the grained / rescaled planes in `tmp` - converted in one launch
+    OutputRgbParams rp; memset( &rp, 0, sizeof( rp ) );
+    for( int k = 0; k < 3; k++ ) { rp.src[k] = cur[k].p; rp.stride[k] = cur[k].stride; rp.dstOff[k] = e->off[k]; rp.direct[k] = kdirect[k] ? (uint8_t*) rq->dst[k] : nullptr; }
+    rp.w = ow[0]; rp.h = oh[0]; rp.format = rq->format; rp.collocated = rq->collocated & 3;
+    rgb_coefficients( outMatrix, outFullRange, bd, rq->format == VVR_OUT_RGB8 ? 8 : bd, rp );
+    if( c->statsOn && hipEventCreate( &e->timing.a ) == hipSuccess )
+    {
+      if( hipEventCreate( &e->timing.b ) == hipSuccess ) { e->timed = true; e->timing.kernel = K_OUTPUT_RGB; e->timing.bytes = (double) rp.w * rp.h * ( 3. + 3. * bps ); hipEventRecord( e->timing.a, s ); }
+      else hipEventDestroy( e->timing.a );
+    }
+    launch_output_rgb( s, rp, e->dev );
+    if( e->timed ) hipEventRecord( e->timing.b, s );
+  }
   OQCHK( hipGetLastError() );
   OQCHK( hipEventRecord( e->read, s ) );
   c->slotExt[slot].push_back( e->read );
@@ -740,12 +859,12 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     if( devDst )      // (what k_output_frame has not stored itself: rows out of the entry's scratch at the caller's stride, on the device)
     {
       if( kdirect[k] ) continue;
-      if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpyAsync( rq->dst[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToDevice, s );
-      else ce = hipMemcpy2DAsync( rq->dst[k], rq->dst_stride_bytes[k], e->dev + e->off[k], rowBytes[k], rowBytes[k], oh[k], hipMemcpyDeviceToDevice, s );
+      if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpyAsync( rq->dst[k], e->dev + e->off[k], rowBytes[k] * outRows[k], hipMemcpyDeviceToDevice, s );
+      else ce = hipMemcpy2DAsync( rq->dst[k], rq->dst_stride_bytes[k], e->dev + e->off[k], rowBytes[k], rowBytes[k], outRows[k], hipMemcpyDeviceToDevice, s );
     }
-    else if( !direct ) ce = hipMemcpyAsync( e->host + e->off[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToHost, s );
-    else if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpyAsync( rq->dst[k], e->dev + e->off[k], rowBytes[k] * oh[k], hipMemcpyDeviceToHost, s );
-    else ce = hipMemcpy2DAsync( rq->dst[k], rq->dst_stride_bytes[k], e->dev + e->off[k], rowBytes[k], rowBytes[k], oh[k], hipMemcpyDeviceToHost, s );
+    else if( !direct ) ce = hipMemcpyAsync( e->host + e->off[k], e->dev + e->off[k], rowBytes[k] * outRows[k], hipMemcpyDeviceToHost, s );
+    else if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpyAsync( rq->dst[k], e->dev + e->off[k], rowBytes[k] * outRows[k], hipMemcpyDeviceToHost, s );
+    else ce = hipMemcpy2DAsync( rq->dst[k], rq->dst_stride_bytes[k], e->dev + e->off[k], rowBytes[k], rowBytes[k], outRows[k], hipMemcpyDeviceToHost, s );
   }
   if( ce == hipSuccess ) ce = hipEventRecord( e->done, s );
   if( ce != hipSuccess )
@@ -787,7 +906,8 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   if( e->timed )
   {
     float ms = 0; hipEventElapsedTime( &ms, e->timing.a, e->timing.b );
-    c->stats[K_OUTPUT_FRAME].launches++; c->stats[K_OUTPUT_FRAME].ms += ms; c->stats[K_OUTPUT_FRAME].bytes += e->timing.bytes;
+    Stat& st = c->stats[e->timing.kernel];      // (K_OUTPUT_FRAME or K_OUTPUT_RGB)
+    st.launches++; st.ms += ms; st.bytes += e->timing.bytes;
     hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false;
   }
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
