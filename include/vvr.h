@@ -614,9 +614,44 @@ VVR_API int          vvr_output_stream_wait(vvr_context* ctx, int ticket, void* 
  * PicYuvMD5.cpp:99-221): one digest per component over the whole plane in raster order, samples as 1 byte (bit depth 8) or 2 bytes little
  * endian.  digest receives num_components x digest_len bytes (MD5 16, CRC 2, checksum 4), *digest_len the length of one.  CRC and checksum
  * are computed on the device (only per-row partial results cross PCIe); for MD5, a serial chain over the bytes of a plane, the device packs
- * the plane to exactly those bytes and the host hashes them. */
+ * the plane to exactly those bytes and the host hashes them.  Waits for all work of the context (vvr_sync); vvr_hash_submit below does not. */
 enum { VVR_HASH_MD5 = 0, VVR_HASH_CRC = 1, VVR_HASH_CHECKSUM = 2 };
 VVR_API int          vvr_picture_hash(vvr_context* ctx, int slot, int method, uint8_t* digest, int* digest_len);
+/* vvr_picture_hash as a request of the output queue: what a decoder that verifies every picture against its decoded-picture-hash SEI submits
+ * next to the picture's output request (the reference: vvdecParams.verifyPictureHash, vvdecPicAttributes.picHashError).  vvr_picture_hash
+ * drains the context (vvr_sync); this does not.  Everything said about an output request above holds for a hash request:
+ *   ticket and ring   the ticket comes from the same ticket space and the same 8 ring entries as vvr_output_submit's (VVR_ERR_BUSY counts both
+ *            kinds); it is collected with vvr_output_test / vvr_output_wait; vvr_output_stream_wait is accepted and means "the digest bytes
+ *            (MD5: the picture's bytes) have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing.
+ *   ordering the request runs on the context's output stream behind the picture's completion event ON THE DEVICE; pictures submitted after the
+ *            ticket was returned that overwrite the slot wait for the request's kernels on the device; submit the request BEFORE the next
+ *            picture into the slot.  blocking == 0: VVR_NOT_READY while `job` has not been handed to the device yet - that hand-over is the
+ *            only thing vvr_hash_submit ever waits for on the host (no vvr_sync, no device or stream synchronise).  A request for a job
+ *            that failed is accepted and fails with the job's status from vvr_output_test / vvr_output_wait.
+ *   hashed   exactly what vvr_picture_hash hashes: the picture in the slot at the picture's size (vvr_slot_picture_size), every component
+ *            of the context, samples as 1 byte at bit depth 8, else 2 bytes little endian; digest bytes in vvr_picture_hash's order
+ *            (num_components x 16 / 2 / 4 bytes).  The film grain's seed chain and the colour description are not touched.
+ *   cost     CRC and checksum are finished on the device (one launch over the rows of all planes, one that combines them): 4 bytes per
+ *            component cross PCIe and the host does nothing.  MD5 is a serial chain: the device packs the planes to their bytes, the
+ *            picture's bytes cross PCIe into pinned memory, vvr_output_test reports VVR_OK once they have landed and vvr_output_wait
+ *            hashes them on the calling thread - about one pass of host hashing over the picture per request.
+ *   result   vvr_output_wait, when it returns VVR_OK, writes `digest` (unless NULL) and - with `expected`, the SEI's digests in the same
+ *            layout, copied inside vvr_hash_submit - *mismatch: bit c set when component c differs, 0 = the picture is verified.
+ *            digest and mismatch must stay valid until vvr_output_wait has returned.
+ * Refused (VVR_ERR_PARAMETER with a text, no ring entry taken): a struct_size other than sizeof( vvr_hash_request ), no such slot, an unknown
+ * method, job < -1, digest and expected both NULL, expected without mismatch. */
+typedef struct vvr_hash_request {
+  uint32_t struct_size;      /* sizeof( vvr_hash_request ) */
+  int32_t  slot;
+  int32_t  job;              /* as vvr_output_request.job: >= 0 ordered behind that picture ON THE DEVICE, -1 the slot as submitted work leaves it */
+  uint8_t  method;           /* VVR_HASH_MD5 / _CRC / _CHECKSUM */
+  uint8_t  blocking;         /* as vvr_output_request.blocking */
+  uint8_t  pad[2];
+  uint8_t* digest;           /* nc * len bytes (len 16 / 2 / 4), written by vvr_output_wait; may be NULL when `expected` is given */
+  const uint8_t* expected;   /* NULL, or nc * len bytes of the SEI's digests: copied inside vvr_hash_submit */
+  uint32_t* mismatch;        /* required with `expected`: bit c set when component c differs (what picHashError reports), 0 = verified */
+} vvr_hash_request;
+VVR_API int          vvr_hash_submit(vvr_context* ctx, const vvr_hash_request* req);
 /* the finished picture in `slot` (every plane, at the picture's size) into the caller's buffers - what a decoder does with each picture it hands to
  * the application (the planes of a vvdecFrame live in the Picture's own buffers, vvdecimpl.cpp:1058).  Waits for NOTHING: the caller has waited for
  * the picture (vvr_wait); other pictures in flight are not held up (vvr_read_plane drains the context).  Each plane crosses PCIe in one transfer

@@ -101,6 +101,8 @@ def lib():
         L.vvr_output_test.argtypes = [C.c_void_p, C.c_int]
         L.vvr_output_wait.restype = C.c_int
         L.vvr_output_wait.argtypes = [C.c_void_p, C.c_int]
+        L.vvr_hash_submit.restype = C.c_int
+        L.vvr_hash_submit.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_output_stream_wait.restype = C.c_int
         L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vvr_device_alloc.restype = C.c_void_p
@@ -120,7 +122,7 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
-                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait",
+                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
 
 
@@ -425,6 +427,35 @@ class Reconstructor:
             self._out.pop(ticket, None)
             for ptr in self._reg.pop(ticket, []):
                 self.L.vvr_device_unregister(self.ctx, ptr)
+
+    def hash_submit(self, slot, job=None, method=0, expected=None, blocking=True):
+        """vvr_hash_submit: the decoded picture hash of `slot` (as `job` leaves it; None: as all work submitted so far leaves it) as a request of
+        the output queue -> ticket, or None when blocking=False and the job has not been handed to the device yet.  method: 0 MD5, 1 CRC,
+        2 checksum (CRC and checksum are finished on the device; for MD5 the picture's bytes come to the host and hash_wait hashes them).
+        expected: the SEI's digests (a list of bytes per component, or their concatenation) to compare with.  The ticket shares the 8 entries of
+        output_submit; output_test and output_stream_wait take it.  Nothing here drains the context (picture_hash does)."""
+        nc, n = 3 if self.chroma_format else 1, abi.HASH_LEN[method]
+        r = abi.HashRequest()
+        r.struct_size, r.slot, r.job, r.method, r.blocking = C.sizeof(abi.HashRequest), slot, -1 if job is None else job, method, 1 if blocking else 0
+        digest, mismatch, want = (C.c_uint8 * (nc * n))(), C.c_uint32(0xffffffff), None
+        r.digest = C.addressof(digest)
+        if expected is not None:
+            raw = expected if isinstance(expected, (bytes, bytearray)) else b"".join(expected)
+            if len(raw) != nc * n:
+                raise ValueError("hash_submit: expected needs %d digests of %d bytes" % (nc, n))
+            want = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
+            r.expected, r.mismatch = C.addressof(want), C.addressof(mismatch)
+        ticket = self._check(self.L.vvr_hash_submit(self.ctx, C.byref(r)))
+        if not blocking and ticket == abi.VVR_NOT_READY:
+            return None
+        self._out[ticket] = (digest, mismatch if expected is not None else None, nc, n)
+        return ticket
+
+    def hash_wait(self, ticket):
+        """vvr_output_wait for a ticket of hash_submit -> (list of per-component digests as bytes, mismatch mask or None when nothing was
+        expected): bit c of the mask is set when component c differs from the expected digest, 0 means the picture is verified"""
+        digest, mismatch, nc, n = self.output_wait(ticket)
+        return [bytes(digest[k * n:(k + 1) * n]) for k in range(nc)], None if mismatch is None else mismatch.value
 
     def write_picture(self, slot, planes):
         for c, pl in enumerate(planes):

@@ -204,5 +204,15 @@ def output_plane_shapes(window, fmt, size, ncomp):
     return shapes, np.uint8 if fmt == "planar8" else np.uint16
 
 
+HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2
+HASH_LEN = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
+
+
+class HashRequest(C.Structure):
+    """vvr_hash_request: a decoded picture hash as a request of the output queue (vvr_hash_submit, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("slot", i32), ("job", i32), ("method", u8), ("blocking", u8), ("pad", u8 * 2),
+                ("digest", C.c_void_p), ("expected", C.c_void_p), ("mismatch", C.c_void_p)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]

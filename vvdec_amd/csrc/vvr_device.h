@@ -192,6 +192,20 @@ struct OutputRgbParams
   float inv;                   // VVR_OUT_RGBF16: float32( 1 ) / float32( 2^bd - 1 )
 };
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
+// decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.
+// launch_hash_rows: one launch over the rows of all planes, rows[g] = the CRC piece (the row's bytes mod P, register from 0) or the checksum share
+// of row g (the planes' rows one after the other).  launch_hash_combine: out[c] = the component's digest as a number - the checksum, or the CRC
+// register after chaining the rows from 0xffff and the 16 appended zero bits.  The powers of x (mod P) the kernels multiply by come from the
+// host (vvr_output.inc, hash_params): bits = 8 or 16 per sample, a lane folds chunks of 8 samples
+struct HashParams
+{
+  const pel_t* src[3]; int stride[3], w[3], h[3];
+  int numComp, two, crc;
+  uint32_t xIter, xTree[6], xTail[3];            // rows: x^( 64 chunks ); x^( chunk << s ); x^( ( w[c] & 7 ) * bits )
+  uint32_t xRowIter[3], xRowTree[3][7];          // combine: x^( 256 rows of component c ); x^( row << s )
+};
+void launch_hash_rows( hipStream_t s, const HashParams& p, uint32_t* rows );
+void launch_hash_combine( hipStream_t s, const HashParams& p, const uint32_t* rows, uint32_t* out );
 void launch_mc_affine( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );
 void launch_mc_rpr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems );      // tiles of CUs with a scaled reference picture
 void launch_mc_dmvr( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems, int32_t* dmvrOut );

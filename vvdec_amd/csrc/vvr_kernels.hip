@@ -5249,6 +5249,147 @@ void launch_plane_hash_rows( hipStream_t s, const pel_t* plane, int stride, int 
   hipLaunchKernelGGL( k_plane_hash_rows, dim3( h ), dim3( 64 ), 0, s, plane, stride, w, two, crcMode, out );
 }
 
+// k_hash_rows / k_hash_combine — the hash requests of the output queue (vvr_hash_submit): CRC and checksum of a whole picture in two launches,
+// the digests finished on the device.
+// k_hash_rows: one wavefront per row, the rows of all planes in one grid (four per workgroup).  A lane takes 8 samples with one 16-byte load
+// (rows start 128-byte aligned and a chunk index is whole, so every load is aligned; a wavefront's loads are 1 KiB back to back).  CRC: the
+// chunk's 8 or 16 message bytes are reduced mod P with one table look-up per byte - tbl[k][b] = b * x^( 8 ( k + 2 ) ) mod P, built in LDS by
+// the workgroup; the look-ups are independent - and a lane chains its chunks by Horner's rule with ONE multiplication per chunk
+// ( acc = acc * x^( 64 chunks ) + chunk ).  The chunks are numbered from the END of the row's whole chunks (the missing ones in front are
+// zeros, which a polynomial does not see), so every lane ends 63 - lane chunks before that end and six multiply-and-shuffle steps join the
+// lanes; lane 0 adds the row's last w & 7 samples.  Every power of x is a kernel argument (the host computes them once per request).
+// k_hash_combine: one workgroup per component chains the rows' pieces the same way (the register's initial 0xffff is one more piece in front,
+// the 16 appended zero bits a last multiplication by x^16 = 0x1021), or adds the checksum shares.
+template<int K> __device__ __forceinline__ uint32_t crc_term( const uint16_t ( *tbl )[256], uint32_t byte )      // byte * x^( 8 K ) mod P
+{
+  return K == 0 ? byte : K == 1 ? byte << 8 : (uint32_t) tbl[K >= 2 ? K - 2 : 0][byte];
+}
+template<bool TWO, int I> __device__ __forceinline__ uint32_t crc_sample( const uint16_t ( *tbl )[256], uint32_t v )      // sample I of a chunk of 8: low byte first
+{
+  if( TWO ) return crc_term<15 - 2 * I>( tbl, v & 0xff ) ^ crc_term<14 - 2 * I>( tbl, v >> 8 );
+  return crc_term<7 - I>( tbl, v & 0xff );
+}
+template<bool TWO> __device__ __forceinline__ uint32_t crc_chunk( const uint16_t ( *tbl )[256], uint4 q )
+{
+  return crc_sample<TWO, 0>( tbl, q.x & 0xffff ) ^ crc_sample<TWO, 1>( tbl, q.x >> 16 ) ^ crc_sample<TWO, 2>( tbl, q.y & 0xffff ) ^ crc_sample<TWO, 3>( tbl, q.y >> 16 )
+       ^ crc_sample<TWO, 4>( tbl, q.z & 0xffff ) ^ crc_sample<TWO, 5>( tbl, q.z >> 16 ) ^ crc_sample<TWO, 6>( tbl, q.w & 0xffff ) ^ crc_sample<TWO, 7>( tbl, q.w >> 16 );
+}
+template<bool TWO> __device__ __forceinline__ uint32_t checksum_sample( uint32_t v, int x, int y )
+{
+  const uint32_t mask = ( ( x & 0xff ) ^ ( y & 0xff ) ^ ( x >> 8 ) ^ ( y >> 8 ) ) & 0xff;
+  return ( ( v & 0xff ) ^ mask ) + ( TWO ? ( v >> 8 ) ^ mask : 0u );
+}
+template<bool TWO> __device__ __forceinline__ uint32_t checksum_pair( uint32_t pair, int x, int y ) { return checksum_sample<TWO>( pair & 0xffff, x, y ) + checksum_sample<TWO>( pair >> 16, x + 1, y ); }
+
+template<bool TWO, bool CRC>
+__global__ __launch_bounds__( 256 ) void k_hash_rows( HashParams p, int rowsTotal, uint32_t* __restrict__ rows )
+{
+  __shared__ uint16_t tbl[CRC ? 14 : 1][256];      // (the CRC's byte tables; the checksum has none)
+  if constexpr( CRC )
+  {
+    uint32_t a = threadIdx.x << 8;      // t * x^8
+#pragma unroll 1
+    for( int k = 0; k < ( TWO ? 14 : 6 ); k++ )
+    {
+#pragma unroll
+      for( int i = 0; i < 8; i++ ) { a <<= 1; a ^= ( ( a >> 16 ) & 1 ) * 0x11021u; }
+      tbl[k][threadIdx.x] = (uint16_t) a;
+    }
+    __syncthreads();
+  }
+  const int lane = threadIdx.x & 63, g = blockIdx.x * 4 + ( threadIdx.x >> 6 );
+  if( g >= rowsTotal ) return;
+  int c = 0, y = g;
+  if( y >= p.h[0] ) { y -= p.h[0]; c = 1; if( y >= p.h[1] ) { y -= p.h[1]; c = 2; } }
+  const int w = c == 0 ? p.w[0] : c == 1 ? p.w[1] : p.w[2], stride = c == 0 ? p.stride[0] : c == 1 ? p.stride[1] : p.stride[2];
+  const pel_t* __restrict__ row = ( c == 0 ? p.src[0] : c == 1 ? p.src[1] : p.src[2] ) + (size_t) y * stride;
+  const int nFull = w >> 3, rem = w & 7;
+  uint32_t acc = 0;
+  if constexpr( !CRC )
+  {
+    for( int ci = lane; ci < nFull; ci += 64 )
+    {
+      const uint4 q = *(const uint4*) ( row + 8 * ci );
+      acc += checksum_pair<TWO>( q.x, 8 * ci, y ) + checksum_pair<TWO>( q.y, 8 * ci + 2, y ) + checksum_pair<TWO>( q.z, 8 * ci + 4, y ) + checksum_pair<TWO>( q.w, 8 * ci + 6, y );
+    }
+    if( lane < rem ) acc += checksum_sample<TWO>( (uint16_t) row[8 * nFull + lane], 8 * nFull + lane, y );
+    for( int o = 32; o; o >>= 1 ) acc += __shfl_down( acc, o, 64 );
+  }
+  else
+  {
+    const int nIter = ( nFull + 63 ) >> 6, pad = nIter * 64 - nFull;
+    for( int it = 0; it < nIter; it++ )
+    {
+      const int ci = it * 64 + lane - pad;
+      uint32_t v = 0;
+      if( ci >= 0 ) v = crc_chunk<TWO>( tbl, *(const uint4*) ( row + 8 * ci ) );
+      acc = crc_mul( acc, p.xIter ) ^ v;
+    }
+#pragma unroll
+    for( int s = 0; s < 6; s++ ) { const uint32_t next = __shfl_down( acc, 1 << s, 64 ); acc = crc_mul( acc, p.xTree[s] ) ^ next; }      // (lane 0 ends with the 64 lanes' chunks in order)
+    if( lane == 0 && rem )
+    {
+      // the last w & 7 samples as the end of a chunk whose front is zeros
+      uint4 q;
+      uint32_t t[8];
+#pragma unroll
+      for( int i = 0; i < 8; i++ ) t[i] = i >= 8 - rem ? (uint32_t) (uint16_t) row[w - 8 + i] : 0u;
+      q.x = t[0] | t[1] << 16; q.y = t[2] | t[3] << 16; q.z = t[4] | t[5] << 16; q.w = t[6] | t[7] << 16;
+      acc = crc_mul( acc, c == 0 ? p.xTail[0] : c == 1 ? p.xTail[1] : p.xTail[2] ) ^ crc_chunk<TWO>( tbl, q );
+    }
+  }
+  if( lane == 0 ) rows[g] = acc;
+}
+void launch_hash_rows( hipStream_t s, const HashParams& p, uint32_t* rows )
+{
+  int rowsTotal = 0; for( int c = 0; c < p.numComp; c++ ) rowsTotal += p.h[c];
+  const dim3 grid( ( rowsTotal + 3 ) / 4 ), block( 256 );
+  if( p.crc ) { if( p.two ) hipLaunchKernelGGL( ( k_hash_rows<true, true> ), grid, block, 0, s, p, rowsTotal, rows ); else hipLaunchKernelGGL( ( k_hash_rows<false, true> ), grid, block, 0, s, p, rowsTotal, rows ); }
+  else        { if( p.two ) hipLaunchKernelGGL( ( k_hash_rows<true, false> ), grid, block, 0, s, p, rowsTotal, rows ); else hipLaunchKernelGGL( ( k_hash_rows<false, false> ), grid, block, 0, s, p, rowsTotal, rows ); }
+}
+
+__global__ __launch_bounds__( 256 ) void k_hash_combine( HashParams p, const uint32_t* __restrict__ rows, uint32_t* __restrict__ out )
+{
+  __shared__ uint32_t part[4];
+  const int c = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const int h = c == 0 ? p.h[0] : c == 1 ? p.h[1] : p.h[2];
+  rows += c == 0 ? 0 : c == 1 ? p.h[0] : p.h[0] + p.h[1];
+  uint32_t acc = 0;
+  if( !p.crc )
+  {
+    for( int r = t; r < h; r += 256 ) acc += rows[r];
+    for( int o = 32; o; o >>= 1 ) acc += __shfl_down( acc, o, 64 );
+  }
+  else
+  {
+    // h + 1 pieces (0xffff, then the rows), numbered from the end like the chunks of a row
+    const int n = h + 1, nIter = ( n + 255 ) >> 8, pad = nIter * 256 - n;
+    const uint32_t xIter = c == 0 ? p.xRowIter[0] : c == 1 ? p.xRowIter[1] : p.xRowIter[2];
+    for( int it = 0; it < nIter; it++ )
+    {
+      const int i = it * 256 + t - pad;
+      acc = crc_mul( acc, xIter ) ^ ( i < 0 ? 0u : i == 0 ? 0xffffu : rows[i - 1] & 0xffffu );
+    }
+#pragma unroll
+    for( int s = 0; s < 6; s++ ) { const uint32_t next = __shfl_down( acc, 1 << s, 64 ); acc = crc_mul( acc, c == 0 ? p.xRowTree[0][s] : c == 1 ? p.xRowTree[1][s] : p.xRowTree[2][s] ) ^ next; }
+  }
+  if( lane == 0 ) part[t >> 6] = acc;
+  __syncthreads();
+  if( t ) return;
+  if( !p.crc ) acc = part[0] + part[1] + part[2] + part[3];
+  else
+  {
+    const uint32_t x64 = c == 0 ? p.xRowTree[0][6] : c == 1 ? p.xRowTree[1][6] : p.xRowTree[2][6];
+    for( int k = 1; k < 4; k++ ) acc = crc_mul( acc, x64 ) ^ part[k];
+    acc = crc_mul( acc, 0x1021u );      // the 16 zero bits appended at the end: x^16 mod P
+  }
+  out[c] = acc;
+}
+void launch_hash_combine( hipStream_t s, const HashParams& p, const uint32_t* rows, uint32_t* out )
+{
+  hipLaunchKernelGGL( k_hash_combine, dim3( p.numComp ), dim3( 256 ), 0, s, p, rows, out );
+}
+
 #include "vvr_intra_cells.inc"
 
 // =====================================================================================================================

@@ -52,12 +52,48 @@ uint32_t crcMul( uint32_t a, uint32_t b )
   return r;
 }
 uint32_t crcXPow( uint64_t n ) { uint32_t r = 1, base = 2; while( n ) { if( n & 1 ) r = crcMul( r, base ); base = crcMul( base, base ); n >>= 1; } return r; }
+// what k_hash_rows / k_hash_combine get of a picture: its planes and, for the CRC, the powers of x they multiply by (vvr_device.h).  A row of
+// 7680 10-bit samples has 122 880 bits: the exponents are 64-bit here and never formed on the device
+HashParams hash_params( const DevPlanes& d, int nc, bool two, bool crc )
+{
+  HashParams p; memset( &p, 0, sizeof( p ) );
+  const uint64_t bits = two ? 16 : 8, chunk = 8 * bits;
+  for( int k = 0; k < nc; k++ ) { p.src[k] = d.p[k]; p.stride[k] = d.stride[k]; p.w[k] = d.w[k]; p.h[k] = d.h[k]; }
+  p.numComp = nc; p.two = two; p.crc = crc;
+  if( !crc ) return p;
+  p.xIter = crcXPow( 64 * chunk );
+  for( int s = 0; s < 6; s++ ) p.xTree[s] = crcXPow( chunk << s );
+  for( int k = 0; k < nc; k++ )
+  {
+    const uint64_t row = (uint64_t) d.w[k] * bits;
+    p.xTail[k] = crcXPow( ( d.w[k] & 7 ) * bits ); p.xRowIter[k] = crcXPow( row * 256 );
+    for( int s = 0; s < 7; s++ ) p.xRowTree[k][s] = crcXPow( row << s );
+  }
+  return p;
+}
 
 int ensureOutputScratch( vvr_context* c, size_t devBytes, size_t hostBytes )
 {
   if( devBytes > c->outDevCap ) { if( c->outDev ) hipFree( c->outDev ); c->outDev = nullptr; c->outDevCap = 0; HIPCHK( c, hipMalloc( &c->outDev, devBytes ) ); c->outDevCap = devBytes; }
   if( hostBytes > c->outHostCap ) { if( c->outHost ) hipHostFree( c->outHost ); c->outHost = nullptr; c->outHostCap = 0; HIPCHK( c, hipHostMalloc( &c->outHost, hostBytes, hipHostMallocDefault ) ); c->outHostCap = hostBytes; }
   return VVR_OK;
+}
+
+// the kernels of the output stage between two events of their own when statistics are on: outTimeBegin before the launch, t.b recorded behind it,
+// outTimeEnd once both are complete
+void outTimeBegin( vvr_context* c, hipStream_t s, bool& timed, PendingTiming& t, int kernel, double bytes )
+{
+  if( !c->statsOn || hipEventCreate( &t.a ) != hipSuccess ) return;
+  if( hipEventCreate( &t.b ) != hipSuccess ) { hipEventDestroy( t.a ); return; }
+  timed = true; t.kernel = kernel; t.bytes = bytes; hipEventRecord( t.a, s );
+}
+void outTimeEnd( vvr_context* c, bool& timed, PendingTiming& t, int launches = 1 )
+{
+  if( !timed ) return;
+  float ms = 0; hipEventElapsedTime( &ms, t.a, t.b );
+  Stat& st = c->stats[t.kernel];
+  st.launches += launches; st.ms += ms; st.bytes += t.bytes;
+  hipEventDestroy( t.a ); hipEventDestroy( t.b ); timed = false;
 }
 
 // the positions of sampleRateConvCore (Buffer.cpp:249-255) for one direction: scale factor from the plane's own sizes ((src << 14) + dst / 2) / dst
@@ -278,6 +314,41 @@ void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
         else ( (uint16_t*) out )[at] = p.format == VVR_OUT_RGB16 ? (uint16_t) val : rgb_half_rne( (float) val * p.inv );
       }
     }
+}
+
+// ... and launch_hash_rows / launch_hash_combine (k_hash_rows, k_hash_combine): per row the CRC register reached from 0 bit by bit (compCRC,
+// PicYuvMD5.cpp:99-137) or the checksum share (compChecksum, :152-176); the rows chained with the request's power of x, or added
+void launch_hash_rows( hipStream_t, const HashParams& p, uint32_t* rows )
+{
+  for( int c = 0; c < p.numComp; c++ )
+  {
+    for( int y = 0; y < p.h[c]; y++ )
+    {
+      uint32_t acc = 0;
+      for( int x = 0; x < p.w[c]; x++ )
+      {
+        const uint32_t v = (uint16_t) p.src[c][(size_t) y * p.stride[c] + x];
+        if( !p.crc ) { const uint32_t mask = ( ( x & 0xff ) ^ ( y & 0xff ) ^ ( x >> 8 ) ^ ( y >> 8 ) ) & 0xff; acc += ( v & 0xff ) ^ mask; if( p.two ) acc += ( v >> 8 ) ^ mask; }
+        else for( int b = 0; b < ( p.two ? 2 : 1 ); b++ ) for( int bit = 7; bit >= 0; bit-- )
+        {
+          const uint32_t byte = b ? v >> 8 : v & 0xff, msb = ( acc >> 15 ) & 1;
+          acc = ( ( ( acc << 1 ) + ( ( byte >> bit ) & 1 ) ) & 0xffff ) ^ ( msb * 0x1021 );
+        }
+      }
+      rows[y] = acc;
+    }
+    rows += p.h[c];
+  }
+}
+void launch_hash_combine( hipStream_t, const HashParams& p, const uint32_t* rows, uint32_t* out )
+{
+  for( int c = 0; c < p.numComp; c++ )
+  {
+    uint32_t acc = p.crc ? 0xffff : 0;
+    for( int r = 0; r < p.h[c]; r++ ) acc = p.crc ? crcMul( acc, p.xRowTree[c][0] ) ^ ( rows[r] & 0xffff ) : acc + rows[r];
+    out[c] = p.crc ? crcMul( acc, 0x1021 ) : acc;
+    rows += p.h[c];
+  }
 }
 #endif
 
@@ -510,10 +581,21 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
     if( ( rc = ensureOutputScratch( c, bytes, bytes ) ) != VVR_OK ) return rc;
     uint32_t* dev = (uint32_t*) c->outDev; const uint32_t* host = (const uint32_t*) c->outHost;
     size_t off = 0;
+    bool timed = false; PendingTiming t; double planesBytes = 0;
+    for( int k = 0; k < nc; k++ ) planesBytes += (double) d.w[k] * d.h[k] * sizeof( pel_t );
+    outTimeBegin( c, s, timed, t, K_PLANE_HASH_ROWS, planesBytes + sizeof( uint32_t ) * rowsTotal );      // (one entry for the planes' launches together)
     for( int k = 0; k < nc; k++ ) { launch_plane_hash_rows( s, d.p[k], d.stride[k], d.w[k], d.h[k], two ? 1 : 0, method == VVR_HASH_CRC ? 1 : 0, dev + off ); off += d.h[k]; }
-    HIPCHK( c, hipGetLastError() );
-    HIPCHK( c, hipMemcpyAsync( c->outHost, c->outDev, sizeof( uint32_t ) * rowsTotal, hipMemcpyDeviceToHost, s ) );
-    HIPCHK( c, hipStreamSynchronize( s ) );
+    if( timed ) hipEventRecord( t.b, s );
+    hipError_t he = hipGetLastError();
+    if( he == hipSuccess ) he = hipMemcpyAsync( c->outHost, c->outDev, sizeof( uint32_t ) * rowsTotal, hipMemcpyDeviceToHost, s );
+    if( he == hipSuccess ) he = hipStreamSynchronize( s );
+    if( he != hipSuccess )
+    {
+      if( timed ) { hipEventDestroy( t.a ); hipEventDestroy( t.b ); }      // (nothing is counted for a call that failed)
+      c->setError( std::string( "vvr_picture_hash: " ) + hipGetErrorString( he ) );
+      return VVR_ERR_DEVICE;
+    }
+    { std::lock_guard<std::mutex> lk( c->mu ); outTimeEnd( c, timed, t, nc ); }
     off = 0;
     for( int k = 0; k < nc; k++ )
     {
@@ -554,6 +636,9 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // k_output_frame stores a plane whose rows are back to back at a 32-byte aligned base straight into it, exactly its bytes; every other plane
 // (padded rows, odd bases, the planes k_film_grain / k_rescale store themselves) goes through the entry's scratch and one device-to-device
 // hipMemcpy2DAsync at the caller's stride.  `done` is recorded behind the last kernel or copy; vvr_output_stream_wait hands it to a stream.
+// A hash request (vvr_hash_submit) is an entry with no destination planes: k_hash_rows and k_hash_combine leave one word per component in the
+// entry's scratch and that is all that crosses PCIe (CRC, checksum), or k_output_window packs the planes and their bytes cross (MD5: hashed by
+// the thread that calls vvr_output_wait); the digest bytes and the comparison with the SEI's are made in vvr_output_wait.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -567,6 +652,10 @@ struct OutEntry {
   bool devDst = false; size_t extent[3] = { 0, 0, 0 };      // the destination planes lie in device memory: dst[k] .. dst[k] + extent[k]
   int nc = 0, rows[3] = { 0, 0, 0 }; size_t off[3] = { 0, 0, 0 }, rowBytes[3] = { 0, 0, 0 }, dstStride[3] = { 0, 0, 0 }; void* dst[3] = { nullptr, nullptr, nullptr };
   bool timed = false; PendingTiming timing;
+  // a hash request: method + 1 (0: an output request); planes of planeBytes[] at off[] in `host` (MD5) or one word per component at its start
+  int hash = 0, hashNc = 0; size_t planeBytes[3] = { 0, 0, 0 };
+  uint8_t* digest = nullptr; uint32_t* mismatch = nullptr; bool verify = false; uint8_t expected[48];
+  bool timed2 = false; PendingTiming timing2;      // (k_hash_combine; `timing` is k_hash_rows then)
 };
 
 static void destroyOutputQueue( vvr_context* c )
@@ -578,13 +667,14 @@ static void destroyOutputQueue( vvr_context* c )
       if( e.dev ) hipFree( e.dev ); if( e.tmp ) hipFree( e.tmp ); if( e.host ) hipHostFree( e.host );
       if( e.read ) hipEventDestroy( e.read ); if( e.done ) hipEventDestroy( e.done );
       if( e.timed ) { hipEventDestroy( e.timing.a ); hipEventDestroy( e.timing.b ); }
+      if( e.timed2 ) { hipEventDestroy( e.timing2.a ); hipEventDestroy( e.timing2.b ); }
     }
   delete[] c->outRing; c->outRing = nullptr;
   if( c->outQStream ) { hipStreamDestroy( c->outQStream ); c->outQStream = nullptr; }
 }
 
 namespace {
-int outRefuse( vvr_context* c, const char* why ) { std::lock_guard<std::mutex> lk( c->mu ); c->setError( std::string( "vvr_output_submit: " ) + why ); return VVR_ERR_PARAMETER; }
+int outRefuse( vvr_context* c, const char* why, const char* who = "vvr_output_submit" ) { std::lock_guard<std::mutex> lk( c->mu ); c->setError( std::string( who ) + ": " + why ); return VVR_ERR_PARAMETER; }
 size_t outRegion( size_t bytes ) { return alignUp( bytes + 32, 256 ); }      // (k_output_frame stores whole pieces: up to 31 bytes behind a plane)
 int outGrow( char*& p, size_t& cap, size_t need, bool pinned )
 {
@@ -616,13 +706,88 @@ int outJobStatus( vvr_context* c, int job, std::unique_lock<std::mutex>& lk, boo
   if( it->second->state == J_FAILED ) { c->setError( it->second->err ); return it->second->rc; }
   return VVR_OK;
 }
+// A request's way into the ring, shared by vvr_output_submit and vvr_hash_submit (`who`); mu held in all three.
+// outAcquire: a free entry, the output stream, the entry's events; the picture `job` reconstructs into `slot` has been handed to the device - the
+// only host wait of a submit call, only when `blocking`, mu released meanwhile.  VVR_OK: jobDone is the event the request waits for on the device
+// (NULL: the picture has finished), jobFailed the status of a picture that failed; anything else is what the submit call returns.
+int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blocking, std::unique_lock<std::mutex>& lk, OutEntry*& e, hipEvent_t& jobDone, int& jobFailed )
+{
+  const std::string w = std::string( who ) + ": ";
+  e = nullptr; jobDone = nullptr; jobFailed = VVR_OK;
+  if( !c->outRing ) c->outRing = new OutEntry[VVR_OUT_RING];
+  for( int i = 0; i < VVR_OUT_RING && !e; i++ ) if( c->outRing[i].state == OQ_FREE ) e = &c->outRing[i];
+  if( !e ) { c->setError( w + "8 requests in flight (vvr_output_wait retires one)" ); return VVR_ERR_BUSY; }
+  if( !c->outQStream ) HIPCHK( c, hipStreamCreateWithFlags( &c->outQStream, hipStreamNonBlocking ) );
+  if( !e->read ) HIPCHK( c, hipEventCreateWithFlags( &e->read, hipEventDisableTiming ) );
+  if( !e->done ) HIPCHK( c, hipEventCreateWithFlags( &e->done, hipEventDisableTiming ) );
+  if( job >= 0 )
+  {
+    auto it = c->jobs.find( job );
+    if( it != c->jobs.end() )        // (else retired: finished long ago)
+    {
+      {
+        const Job& j = *it->second;
+        const vvr_pic_header* hd = j.q ? &j.q->hdr : ( j.pic.hdr.abi_version ? &j.pic.hdr : nullptr );
+        if( hd && hd->out_slot != slot ) { c->setError( w + "the job does not reconstruct into this slot (hdr.out_slot)" ); return VVR_ERR_PARAMETER; }
+      }
+      if( !( it->second->state == J_COMMITTED || it->second->completed ) )
+      {
+        if( !blocking ) return VVR_NOT_READY;
+        c->cv.wait( lk, [&]{ auto q = c->jobs.find( job ); return q == c->jobs.end() || q->second->state == J_COMMITTED || q->second->completed; } );
+        it = c->jobs.find( job );
+      }
+      if( it != c->jobs.end() )
+      {
+        if( it->second->state == J_FAILED ) jobFailed = it->second->rc;
+        else
+        {
+          // (the slot's writer is the first of its users: another one means that a later picture into the slot has been handed to the device already)
+          if( !c->slotUsers[slot].empty() && c->slotUsers[slot][0] != job ) { c->setError( w + "a later picture that overwrites the slot has been submitted already (request a picture's output before the slot's next picture is submitted)" ); return VVR_ERR_PARAMETER; }
+          if( !it->second->completed ) jobDone = it->second->done;
+        }
+      }
+    }
+  }
+  else if( !c->bySeq.empty() )       // pictures still with the workers: who uses the slot is only known once they are committed
+  {
+    if( !blocking ) return VVR_NOT_READY;
+    c->cv.wait( lk, [&]{ return c->bySeq.empty(); } );
+  }
+  if( e->state != OQ_FREE ) { c->setError( w + "called from two threads at once" ); return VVR_ERR_PARAMETER; }
+  return VVR_OK;
+}
+// outTake: the entry gets its ticket (the caller sets OQ_FLIGHT when the request is accepted)
+void outTake( vvr_context* c, OutEntry* e, int slot, int job, int jobFailed )
+{
+  e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
+  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0;
+  if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
+  if( e->timed2 ) { hipEventDestroy( e->timing2.a ); hipEventDestroy( e->timing2.b ); e->timed2 = false; }
+}
+// outOrder: the output stream behind the picture (or, job < 0, behind the slot's users) and behind the external writers of the slot (readers cost nothing)
+hipError_t outOrder( vvr_context* c, const OutEntry* e, int slot, int job, hipEvent_t jobDone )
+{
+  hipError_t rc = jobDone ? hipStreamWaitEvent( c->outQStream, jobDone, 0 ) : hipSuccess;
+  if( job < 0 )
+    for( int id : c->slotUsers[slot] )
+    {
+      auto it = c->jobs.find( id );
+      if( rc == hipSuccess && it != c->jobs.end() && !it->second->completed && it->second->state == J_COMMITTED && it->second->done ) rc = hipStreamWaitEvent( c->outQStream, it->second->done, 0 );
+    }
+  for( hipEvent_t ev : c->slotExt[slot] ) if( rc == hipSuccess && ev != e->read ) rc = hipStreamWaitEvent( c->outQStream, ev, 0 );
+  return rc;
+}
 }   // namespace
 
 extern "C" {
 
+// (a call that fails while a request is being enqueued: `who` is the submit call, s the output stream - drained, the entry's buffers may be reused at once)
+#define OQCHK( call ) do { hipError_t e_ = ( call ); if( e_ != hipSuccess ) { c->setError( std::string( who ) + ": " #call ": " + hipGetErrorString( e_ ) ); hipStreamSynchronize( s ); return VVR_ERR_DEVICE; } } while( 0 )
+
 VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
 {
   if( !c || !rq ) return VVR_ERR_PARAMETER;
+  const char* const who = "vvr_output_submit";
   // ---- 1. the request
   if( rq->struct_size != sizeof( vvr_output_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_output_request )" );
   const int slot = rq->slot, bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
@@ -674,48 +839,8 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   OutEntry* e = nullptr;
   hipEvent_t jobDone = nullptr; int jobFailed = VVR_OK;
   std::unique_lock<std::mutex> lk( c->mu );
-  if( !c->outRing ) c->outRing = new OutEntry[VVR_OUT_RING];
-  for( int i = 0; i < VVR_OUT_RING && !e; i++ ) if( c->outRing[i].state == OQ_FREE ) e = &c->outRing[i];
-  if( !e ) { c->setError( "vvr_output_submit: 8 requests in flight (vvr_output_wait retires one)" ); return VVR_ERR_BUSY; }
-  if( !c->outQStream ) HIPCHK( c, hipStreamCreateWithFlags( &c->outQStream, hipStreamNonBlocking ) );
-  if( !e->read ) HIPCHK( c, hipEventCreateWithFlags( &e->read, hipEventDisableTiming ) );
-  if( !e->done ) HIPCHK( c, hipEventCreateWithFlags( &e->done, hipEventDisableTiming ) );
+  { const int rc = outAcquire( c, who, slot, rq->job, rq->blocking != 0, lk, e, jobDone, jobFailed ); if( rc != VVR_OK ) return rc; }
   hipStream_t s = c->outQStream;
-  if( rq->job >= 0 )
-  {
-    auto it = c->jobs.find( rq->job );
-    if( it != c->jobs.end() )        // (else retired: finished long ago)
-    {
-      {
-        const Job& j = *it->second;
-        const vvr_pic_header* hd = j.q ? &j.q->hdr : ( j.pic.hdr.abi_version ? &j.pic.hdr : nullptr );
-        if( hd && hd->out_slot != slot ) { c->setError( "vvr_output_submit: the job does not reconstruct into this slot (hdr.out_slot)" ); return VVR_ERR_PARAMETER; }
-      }
-      if( !( it->second->state == J_COMMITTED || it->second->completed ) )
-      {
-        if( !rq->blocking ) return VVR_NOT_READY;
-        const int job = rq->job;
-        c->cv.wait( lk, [&]{ auto q = c->jobs.find( job ); return q == c->jobs.end() || q->second->state == J_COMMITTED || q->second->completed; } );
-        it = c->jobs.find( job );
-      }
-      if( it != c->jobs.end() )
-      {
-        if( it->second->state == J_FAILED ) jobFailed = it->second->rc;
-        else
-        {
-          // (the slot's writer is the first of its users: another one means that a later picture into the slot has been handed to the device already)
-          if( !c->slotUsers[slot].empty() && c->slotUsers[slot][0] != rq->job ) { c->setError( "vvr_output_submit: a later picture that overwrites the slot has been submitted already (request a picture's output before the slot's next picture is submitted)" ); return VVR_ERR_PARAMETER; }
-          if( !it->second->completed ) jobDone = it->second->done;
-        }
-      }
-    }
-  }
-  else if( !c->bySeq.empty() )       // pictures still with the workers: who uses the slot is only known once they are committed
-  {
-    if( !rq->blocking ) return VVR_NOT_READY;
-    c->cv.wait( lk, [&]{ return c->bySeq.empty(); } );
-  }
-  if( e->state != OQ_FREE ) { c->setError( "vvr_output_submit: called from two threads at once" ); return VVR_ERR_PARAMETER; }
   // ---- where the planes go: device memory the context knows (every plane wholly inside a range), or the host
   size_t extent[3] = { 0, 0, 0 }; int devPlanes = 0;
   for( int k = 0; k < nOut; k++ )
@@ -731,9 +856,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( devPlanes && devPlanes != nOut ) { c->setError( "vvr_output_submit: destination planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
   const bool devDst = devPlanes != 0;
   if( rgb ) { outMatrix = c->outMatrix; outFullRange = c->outFullRange; }      // (what is set now, behind the waits above: a description cannot be unset)
-  e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
-  e->job = rq->job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = nOut;
-  if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
+  outTake( c, e, slot, rq->job, jobFailed ); e->nc = nOut;
   if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
   // ---- the entry's buffers: the output's planes; the 16-bit planes of a grained frame that goes on (A) and of a rescaled plane that is packed (B); the words
   const bool grainTmp = grain && ( viaTmp || anyResc );
@@ -761,15 +884,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   e->direct = direct; e->devDst = devDst;
   // ---- 3. behind the picture (or the slot's users) on the device, 4. the kernels.  mu stays held up to the registration of the `read` event: a
   // picture committed meanwhile that overwrites the slot must find it
-#define OQCHK( call ) do { hipError_t e_ = ( call ); if( e_ != hipSuccess ) { c->setError( std::string( "vvr_output_submit: " #call ": " ) + hipGetErrorString( e_ ) ); hipStreamSynchronize( s ); return VVR_ERR_DEVICE; } } while( 0 )
-  if( jobDone ) OQCHK( hipStreamWaitEvent( s, jobDone, 0 ) );
-  if( rq->job < 0 )
-    for( int id : c->slotUsers[slot] )
-    {
-      auto it = c->jobs.find( id );
-      if( it != c->jobs.end() && !it->second->completed && it->second->state == J_COMMITTED && it->second->done ) OQCHK( hipStreamWaitEvent( s, it->second->done, 0 ) );
-    }
-  for( hipEvent_t ev : c->slotExt[slot] ) if( ev != e->read ) OQCHK( hipStreamWaitEvent( s, ev, 0 ) );      // (external writers of the slot; readers cost nothing)
+  OQCHK( outOrder( c, e, slot, rq->job, jobDone ) );
   struct Cur { const pel_t* p; int stride; bool inOut; } cur[3];
   for( int k = 0; k < nc; k++ ) { const int sh = k ? 1 : 0; cur[k].p = d.p[k] + (size_t) ( y >> sh ) * d.stride[k] + ( x >> sh ); cur[k].stride = d.stride[k]; cur[k].inOut = false; }
   uint32_t nextSeed = c->grainSeed;
@@ -822,11 +937,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   fp.format = rq->format; fp.shift = packed ? 10 - bd : ( rq->format == VVR_OUT_P010 ? 16 - bd : 0 );
   if( frameBytes > 0 )
   {
-    if( c->statsOn && hipEventCreate( &e->timing.a ) == hipSuccess )
-    {
-      if( hipEventCreate( &e->timing.b ) == hipSuccess ) { e->timed = true; e->timing.kernel = K_OUTPUT_FRAME; e->timing.bytes = frameBytes; hipEventRecord( e->timing.a, s ); }
-      else hipEventDestroy( e->timing.a );
-    }
+    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_FRAME, frameBytes );
     launch_output_frame( s, fp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
   }
@@ -837,11 +948,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     for( int k = 0; k < 3; k++ ) { rp.src[k] = cur[k].p; rp.stride[k] = cur[k].stride; rp.dstOff[k] = e->off[k]; rp.direct[k] = kdirect[k] ? (uint8_t*) rq->dst[k] : nullptr; }
     rp.w = ow[0]; rp.h = oh[0]; rp.format = rq->format; rp.collocated = rq->collocated & 3;
     rgb_coefficients( outMatrix, outFullRange, bd, rq->format == VVR_OUT_RGB8 ? 8 : bd, rp );
-    if( c->statsOn && hipEventCreate( &e->timing.a ) == hipSuccess )
-    {
-      if( hipEventCreate( &e->timing.b ) == hipSuccess ) { e->timed = true; e->timing.kernel = K_OUTPUT_RGB; e->timing.bytes = (double) rp.w * rp.h * ( 3. + 3. * bps ); hipEventRecord( e->timing.a, s ); }
-      else hipEventDestroy( e->timing.a );
-    }
+    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + 3. * bps ) );
     launch_output_rgb( s, rp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
   }
@@ -871,11 +978,79 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   {
     // (the request stays accepted - its kernels have run, the chain has advanced - and fails from vvr_output_test / vvr_output_wait)
     hipStreamSynchronize( s );
-    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( "vvr_output_submit: copy to the destination: " ) + hipGetErrorString( ce ) );
+    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( who ) + ": copy to the destination: " + hipGetErrorString( ce ) );
   }
-#undef OQCHK
   return ticket;
 }
+
+VVR_API int vvr_hash_submit( vvr_context* c, const vvr_hash_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  const char* const who = "vvr_hash_submit";
+  // ---- 1. the request
+  if( rq->struct_size != sizeof( vvr_hash_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_hash_request )", who );
+  const int slot = rq->slot, method = rq->method, nc = c->cfg.chroma_format ? 3 : 1, len = method == VVR_HASH_MD5 ? 16 : method == VVR_HASH_CRC ? 2 : 4;
+  if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot", who );
+  if( method > VVR_HASH_CHECKSUM ) return outRefuse( c, "unknown method", who );
+  if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1", who );
+  if( !rq->digest && !rq->expected ) return outRefuse( c, "neither digest nor expected given", who );
+  if( rq->expected && !rq->mismatch ) return outRefuse( c, "expected without mismatch", who );
+  const bool two = c->cfg.bit_depth > 8;
+  const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot, not the slot)
+  hipSetDevice( c->device );
+  // ---- 2. a ring entry; the picture has been handed to the device
+  OutEntry* e = nullptr;
+  hipEvent_t jobDone = nullptr; int jobFailed = VVR_OK;
+  std::unique_lock<std::mutex> lk( c->mu );
+  { const int rc = outAcquire( c, who, slot, rq->job, rq->blocking != 0, lk, e, jobDone, jobFailed ); if( rc != VVR_OK ) return rc; }
+  hipStream_t s = c->outQStream;
+  outTake( c, e, slot, rq->job, jobFailed );
+  e->hash = method + 1; e->hashNc = nc; e->digest = rq->digest; e->mismatch = rq->mismatch; e->verify = rq->expected != nullptr;
+  if( rq->expected ) memcpy( e->expected, rq->expected, (size_t) nc * len );
+  if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
+  // ---- the entry's buffers.  MD5: the planes' bytes, on the device and pinned; else a word per row on the device, a word per component on both sides
+  size_t total = 0, rowsTotal = 0; double planesBytes = 0;
+  for( int k = 0; k < nc; k++ )
+  {
+    e->off[k] = total; e->planeBytes[k] = (size_t) d.w[k] * d.h[k] * ( two ? 2 : 1 );
+    total += alignUp( e->planeBytes[k], 256 ); rowsTotal += d.h[k]; planesBytes += (double) d.w[k] * d.h[k] * sizeof( pel_t );
+  }
+  const size_t wordsOff = alignUp( sizeof( uint32_t ) * rowsTotal, 256 );
+  if( outGrow( e->dev, e->devCap, method == VVR_HASH_MD5 ? total : wordsOff + 256, false ) != VVR_OK || outGrow( e->host, e->hostCap, method == VVR_HASH_MD5 ? total : 256, true ) != VVR_OK )
+  { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
+  // ---- 3. behind the picture (or the slot's users) on the device, 4. the kernels.  mu stays held up to the registration of the `read` event (as vvr_output_submit)
+  OQCHK( outOrder( c, e, slot, rq->job, jobDone ) );
+  if( method == VVR_HASH_MD5 )
+    for( int k = 0; k < nc; k++ ) launch_output_window( s, d.p[k], d.stride[k], d.w[k], d.h[k], two ? 2 : 1, e->dev + e->off[k] );
+  else
+  {
+    const HashParams p = hash_params( d, nc, two, method == VVR_HASH_CRC );
+    outTimeBegin( c, s, e->timed, e->timing, K_HASH_ROWS, planesBytes + sizeof( uint32_t ) * rowsTotal );
+    launch_hash_rows( s, p, (uint32_t*) e->dev );
+    if( e->timed ) hipEventRecord( e->timing.b, s );
+    outTimeBegin( c, s, e->timed2, e->timing2, K_HASH_COMBINE, (double) sizeof( uint32_t ) * ( rowsTotal + nc ) );
+    launch_hash_combine( s, p, (const uint32_t*) e->dev, (uint32_t*) ( e->dev + wordsOff ) );
+    if( e->timed2 ) hipEventRecord( e->timing2.b, s );
+  }
+  OQCHK( hipGetLastError() );
+  OQCHK( hipEventRecord( e->read, s ) );
+  c->slotExt[slot].push_back( e->read );
+  e->state = OQ_FLIGHT; e->queued = true;
+  const int ticket = e->ticket;
+  lk.unlock();
+  // ---- the result's way to the host: nc words, or the planes' bytes
+  hipError_t ce = hipSuccess;
+  if( method != VVR_HASH_MD5 ) ce = hipMemcpyAsync( e->host, e->dev + wordsOff, sizeof( uint32_t ) * nc, hipMemcpyDeviceToHost, s );
+  else for( int k = 0; k < nc && ce == hipSuccess; k++ ) ce = hipMemcpyAsync( e->host + e->off[k], e->dev + e->off[k], e->planeBytes[k], hipMemcpyDeviceToHost, s );
+  if( ce == hipSuccess ) ce = hipEventRecord( e->done, s );
+  if( ce != hipSuccess )
+  {
+    hipStreamSynchronize( s );
+    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( who ) + ": copy to the host: " + hipGetErrorString( ce ) );
+  }
+  return ticket;
+}
+#undef OQCHK
 
 VVR_API int vvr_output_test( vvr_context* c, int ticket )
 {
@@ -903,19 +1078,29 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   lk.lock();
   if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
   if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
-  if( e->timed )
-  {
-    float ms = 0; hipEventElapsedTime( &ms, e->timing.a, e->timing.b );
-    Stat& st = c->stats[e->timing.kernel];      // (K_OUTPUT_FRAME or K_OUTPUT_RGB)
-    st.launches++; st.ms += ms; st.bytes += e->timing.bytes;
-    hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false;
-  }
+  outTimeEnd( c, e->timed, e->timing );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS ...
+  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE)
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
   if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
   lk.unlock();
   if( rc == VVR_OK && e->queued && !e->direct )
     for( int k = 0; k < e->nc; k++ )
       for( int r = 0; r < e->rows[k]; r++ ) memcpy( (uint8_t*) e->dst[k] + (size_t) r * e->dstStride[k], e->host + e->off[k] + (size_t) r * e->rowBytes[k], e->rowBytes[k] );
+  if( rc == VVR_OK && e->queued && e->hash )
+  {
+    // the digests in vvr_picture_hash's byte order (MD5: the planes' bytes are hashed here, on the waiting thread), then the comparison with the SEI's
+    const int method = e->hash - 1, len = method == VVR_HASH_MD5 ? 16 : method == VVR_HASH_CRC ? 2 : 4;
+    uint8_t dg[48];
+    for( int k = 0; k < e->hashNc; k++ )
+    {
+      uint8_t* out = dg + k * len;
+      if( method == VVR_HASH_MD5 ) { Md5 m; m.update( (const uint8_t*) e->host + e->off[k], e->planeBytes[k] ); m.finish( out ); continue; }
+      const uint32_t v = ( (const uint32_t*) e->host )[k];
+      for( int i = 0; i < len; i++ ) out[i] = (uint8_t) ( v >> ( 8 * ( len - 1 - i ) ) );
+    }
+    if( e->digest ) memcpy( e->digest, dg, (size_t) e->hashNc * len );
+    if( e->verify ) { uint32_t m = 0; for( int k = 0; k < e->hashNc; k++ ) if( memcmp( dg + k * len, e->expected + k * len, len ) ) m |= 1u << k; *e->mismatch = m; }
+  }
   lk.lock();
   e->state = OQ_FREE; e->ticket = -1;
   return rc;
