@@ -544,8 +544,9 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *              RGB8: uint8.  RGB16: little-endian uint16, od = bd.  RGBF16: IEEE half, the RGB16 value v as half( float32( v ) * inv ) with
  *              inv = float32( 1 ) / float32( 2^bd - 1 ): one correctly rounded float32 multiply, one conversion rounding to nearest even.
  *            Refused: no colour description set, a 4:0:0 context (no chroma), a bit depth outside 8..10, an odd out_w or out_h, a missing plane
- *            among the three or a stride below the row.  Not offered: interleaved or packed RGB(A), BGR, float32; primaries or transfer
- *            conversion; constant-luminance BT.2020, ICtCp, YCgCo, the identity matrix; 4:0:0 as grey; the synchronous vvr_read_output* calls.
+ *            among the three or a stride below the row.  Primaries and transfer conversion: vvr_set_output_transform below.  Not offered:
+ *            interleaved or packed RGB(A), BGR, float32; constant-luminance BT.2020, ICtCp, YCgCo, the identity matrix; 3-D LUTs and
+ *            luminance-based tone mapping; 4:0:0 as grey; the synchronous vvr_read_output* calls.
  *   grain with out_w / out_h: the window is grained at its own size exactly as vvr_read_output_grain does it, the grained frame is then
  *            rescaled exactly as vvr_read_output_scaled rescales a picture, taps clamped to the grained frame (the reference's order:
  *            xAddGrain in xAddPicture, then the application's upscaleFrame).
@@ -591,6 +592,62 @@ typedef struct vvr_output_request {
  * stays.  A request takes the value that is set when vvr_output_submit accepts it: the coefficients travel as kernel arguments, a later call
  * never changes a request in flight. */
 VVR_API int          vvr_set_output_colour(vvr_context* ctx, int matrix_coefficients, int full_range);
+/* Linear-light colour transform of the RGB formats: 1-D table -> 3x3 matrix -> 1-D table, the shaper / matrix / shaper of colour management and the
+ * degamma / CTM / gamma of a display controller - what brings PQ- or HLG-coded BT.2020 R'G'B' to sRGB or BT.709 for a model, a display path or a
+ * thumbnailer.  Context state like the colour description (copied; NULL: none; a new context has none).  It runs inside the RGB request's one
+ * kernel, in registers, between the Y'CbCr matrix above and the store.  The integer pipeline is defined here to the bit; the floating-point
+ * colour science lives only in how the tables are filled (vvr_output_transform_preset fills them for the standard cases, the caller keeps the
+ * choice of any other tone curve).
+ *   which requests   a VVR_OUT_RGB8 / _RGB16 / _RGBF16 request takes the transform that is set when vvr_output_submit accepts it (the rule of the
+ *            colour description): the tables are refreshed on the output stream ahead of the request's kernel, the matrix travels as kernel
+ *            arguments, so a later vvr_set_output_transform never changes a request in flight.  Every other format ignores the transform, and so
+ *            does every synchronous call.
+ *   input    ( r, g, b ): the three values of the definition above computed at od = bd - also for VVR_OUT_RGB8, whose Y'CbCr matrix runs at
+ *            od = bd under a transform - each 0 .. 2^bd - 1.
+ *   stage 1  Lc = lin[c] for c in r, g, b.  lin[v] belongs to the R'G'B' value v (what a plain VVR_OUT_RGB16 request stores); the first 2^bd
+ *            entries are read.
+ *   stage 2  in int64 with an arithmetic shift: Tk = clip( ( m[k][0] * Lr + m[k][1] * Lg + m[k][2] * Lb + 8192 ) >> 14, 0, 65535 ), k = 0, 1, 2.
+ *            m is Q14, every | m[k][j] | <= 65536 (4.0).  Three products of 65536 x 65535 do not fit 32 bits: the sum is 64 bits wide.
+ *   stage 3  i = Tk >> 6, f = Tk & 63, Ek = ( enc[i] * ( 64 - f ) + enc[i + 1] * f + 32 ) >> 6, 0 .. 65535: enc[i] belongs to the stage-2 value
+ *            64 * i (enc[1024] to 65536, which is never reached: it only closes the last interval), linear interpolation between entries.
+ *   store    RGB8: ( Ek + 128 ) / 257, the correctly rounded 16 -> 8 bit reduction (65535 = 255 x 257).  RGB16: Ek itself - under a transform
+ *            VVR_OUT_RGB16 is full-scale 16 bits, not bd bits.  RGBF16: half( float32( Ek ) * inv ) with inv = float32( 1 ) / float32( 65535 ):
+ *            one correctly rounded float32 multiply, one conversion rounding to nearest even, as without a transform.
+ * Refused (VVR_ERR_PARAMETER with a text, the value set before stays in force): a struct_size other than sizeof( vvr_output_transform ), a matrix
+ * entry beyond +-65536.  A transform may be set in any context: it only ever meets RGB requests, and a 4:0:0 context refuses those. */
+typedef struct vvr_output_transform {
+  uint32_t struct_size;      /* sizeof( vvr_output_transform ) */
+  uint32_t pad;
+  uint16_t lin[1024];        /* stage 1: entry v for the R'G'B' value v at od = bd (what VVR_OUT_RGB16 stores); the first 2^bd entries are read */
+  int32_t  m[3][3];          /* stage 2: Q14, every |m| <= 65536 (4.0) */
+  uint16_t enc[1025];        /* stage 3: entry i belongs to the stage-2 value 64 * i */
+  uint16_t pad2[3];
+} vvr_output_transform;
+VVR_API int          vvr_set_output_transform(vvr_context* ctx, const vvr_output_transform* t);
+/* The tables for HDR video to BT.709 primaries (D65), filled in double precision; a pure host function, no context.  q16( v ) = floor( v * 65535 + 0.5 ).
+ *   transfer_characteristics (H.273)  16: PQ, 18: HLG.  colour_primaries (H.273), the source gamut  9: BT.2020, 1: BT.709.
+ *   target   VVR_XFORM_TO_SRGB, VVR_XFORM_TO_BT709 (the BT.709 OETF) or VVR_XFORM_TO_LINEAR; the target gamut is always BT.709's.
+ *   bit_depth  8, 9 or 10: the context's; lin[v] is filled for v <= 2^bit_depth - 1 with E' = v / ( 2^bit_depth - 1 ), the rest is 0.
+ *   PQ: lin[v] = q16( min( EOTF( EETF( E' ) ) / dst_peak_nits, 1 ) ).
+ *            EOTF (SMPTE ST 2084, BT.2100-2 table 4): 10000 * ( max( E'^( 1 / m2 ) - c1, 0 ) / ( c2 - c3 * E'^( 1 / m2 ) ) )^( 1 / m1 ) cd/m2, m1 = 2610 / 16384,
+ *            m2 = 2523 / 4096 * 128, c1 = 3424 / 4096, c2 = 2413 / 4096 * 32, c3 = 2392 / 4096 * 32; its inverse I( L ) = ( ( c1 + c2 Y ) / ( 1 + c3 Y ) )^m2, Y = ( L / 10000 )^m1.
+ *            EETF (BT.2390-10 section 5.4.1, per channel, mastering black and target black 0): lo = I( 0 ), hi = I( src_peak_nits ),
+ *            E1 = clip( ( E' - lo ) / ( hi - lo ), 0, 1 ), maxLum = ( I( dst_peak_nits ) - lo ) / ( hi - lo ), KS = 1.5 maxLum - 0.5; E2 = E1 when
+ *            E1 < KS or KS >= 1, else the Hermite spline ( 2 T^3 - 3 T^2 + 1 ) KS + ( T^3 - 2 T^2 + T ) ( 1 - KS ) + ( -2 T^3 + 3 T^2 ) maxLum with
+ *            T = ( E1 - KS ) / ( 1 - KS ); the black lift b ( 1 - E2 )^4 is 0; EETF = E2 ( hi - lo ) + lo.  Both peaks in ( 0, 10000 ].
+ *   HLG: lin[v] = q16( inverse OETF( E' ) ) (BT.2100-2 table 5): E'^2 / 3 for E' <= 1/2, else ( exp( ( E' - c ) / a ) + b ) / 12, a = 0.17883277,
+ *            b = 1 - 4 a, c = 0.5 - a ln( 4 a ): scene light 0 .. 1.  The two peaks are ignored: this is the scene-referred conversion of
+ *            BT.2408 (section 5.1 of BT.2408-7: no OOTF, no system gamma), not a display-referred one.
+ *   m[k][j] = floor( M[k][j] * 16384 + 0.5 ), M = inverse( N709 ) * Nsrc, N the normalised primary matrix RGB -> XYZ of a gamut (SMPTE RP 177: the
+ *            columns x / y, 1, ( 1 - x - y ) / y of R, G, B scaled so that R = G = B = 1 gives the white point with Y = 1) from the chromaticities of
+ *            BT.2020-2 table 3 (0.708, 0.292; 0.170, 0.797; 0.131, 0.046) and BT.709-6 item 1.3 (0.640, 0.330; 0.300, 0.600; 0.150, 0.060), D65 =
+ *            (0.3127, 0.3290).  Source primaries 1: the identity.  BT.2020: 27205 -9628 -1194 / -2041 18561 -137 / -297 -1648 18329 (the matrix of BT.2407 section 2.2, the inverse of BT.2087's M2).
+ *   enc[i] = q16( OETF( min( 64 i, 65535 ) / 65535 ) ).  sRGB (IEC 61966-2-1): 12.92 L for L <= 0.0031308, else 1.055 L^( 1 / 2.4 ) - 0.055.
+ *            BT.709 (BT.709-6 item 1.2): 4.5 L for L < 0.018, else 1.099 L^0.45 - 0.099.  Linear: min( 64 i, 65535 ).
+ * struct_size and the pads are set.  Any other code point, target, bit depth or peak: VVR_ERR_PARAMETER, *out untouched. */
+enum { VVR_XFORM_TO_SRGB = 0, VVR_XFORM_TO_BT709 = 1, VVR_XFORM_TO_LINEAR = 2 };
+VVR_API int          vvr_output_transform_preset(vvr_output_transform* out, int transfer_characteristics, int colour_primaries, int target,
+                                                 double src_peak_nits, double dst_peak_nits, int bit_depth);
 VVR_API int          vvr_output_submit(vvr_context* ctx, const vvr_output_request* req);
 VVR_API int          vvr_output_test(vvr_context* ctx, int ticket);
 VVR_API int          vvr_output_wait(vvr_context* ctx, int ticket);

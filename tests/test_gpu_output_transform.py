@@ -1,0 +1,47 @@
+"""GPU: the colour transform of the RGB formats of the output queue on the device (k_output_rgb with its transform stage; vvr_set_output_transform,
+vvr_output_transform_preset).  The cases of tests/test_output_transform_host.py at 10 and 8 bits, each request into host memory and into a
+(3, h, w) torch tensor; three pictures of a GOP as rgbf16 under the PQ preset, consumed on the GPU behind vvr_output_stream_wait without the
+host waiting for any of them; and the statistics entry: one k_output_rgb launch per request.
+
+The cases themselves are in tests/output_transform_on_the_device.py, which runs in a process of its own, once for all of them (torch brings its own
+HIP runtime, which has to be the first one the process initialises); the tests here read what it printed."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+DEPTHS = [10, 8]
+KINDS = ["identity", "random", "extremes", "snapshot"]
+
+
+@pytest.fixture(scope="module")
+def on_the_device(built):
+    here = os.path.dirname(os.path.abspath(__file__))
+    cases = ["%s-%d" % (kind, bd) for kind in KINDS for bd in DEPTHS] + ["gop", "stats"]
+    r = subprocess.run([sys.executable, os.path.join(here, "output_transform_on_the_device.py")] + cases, capture_output=True, text=True, timeout=300)
+    return r.stdout.splitlines(), r.stdout[-3000:] + r.stderr[-3000:]
+
+
+def _passed(on_the_device, case):
+    lines, tail = on_the_device
+    assert "ok " + case in lines, "%s did not pass (the cases run in order and stop at the first failure):\n%s" % (case, tail)
+
+
+@pytest.mark.parametrize("bd", DEPTHS)
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_host_cases_on_the_device(on_the_device, kind, bd):
+    """identity: rgb16 under the identity is plain rgb16; random: seeded tables and matrices, every format and chroma position, whole and
+    pair-by-pair stores, behind a rescale (the transform reads `tmp` planes) and behind grain and a rescale; extremes: the 64-bit sum; snapshot:
+    two transforms in flight, the formats that ignore them, NULL"""
+    _passed(on_the_device, "%s-%d" % (kind, bd))
+
+
+def test_a_gop_under_the_pq_preset_consumed_on_the_gpu(on_the_device):
+    _passed(on_the_device, "gop")
+
+
+def test_statistics_count_one_launch_per_request(on_the_device):
+    """vvr_get_stats: k_output_rgb with one launch per RGB request, with a transform or without"""
+    _passed(on_the_device, "stats")

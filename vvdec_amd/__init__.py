@@ -76,6 +76,10 @@ def lib():
         L.vvr_set_film_grain_seed.argtypes = [C.c_void_p, C.c_uint32]
         L.vvr_set_output_colour.restype = C.c_int
         L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.vvr_set_output_transform.restype = C.c_int
+        L.vvr_set_output_transform.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_output_transform_preset.restype = C.c_int
+        L.vvr_output_transform_preset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
         L.vvr_read_output_grain.restype = C.c_int
         L.vvr_read_output_grain.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.vvr_read_dmvr.restype = C.c_int
@@ -118,12 +122,24 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
                     "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
+
+
+def output_transform(transfer, primaries, target, src_peak=1000., dst_peak=100., bit_depth=10):
+    """vvr_output_transform_preset: the tables that bring HDR video to BT.709 primaries -> an abi.OutputTransform for
+    Reconstructor.set_output_transform.  transfer: H.273 transfer_characteristics 16 (PQ) or 18 (HLG); primaries: colour_primaries 9 (BT.2020)
+    or 1 (BT.709); target: "srgb", "bt709" (the BT.709 OETF) or "linear" (or abi.XFORM_TO_*); src_peak, dst_peak: cd/m2, the peaks the
+    BT.2390 EETF maps between (PQ only); bit_depth: the context's, 8 .. 10.  A pure host function: no context, no device."""
+    t = abi.OutputTransform()
+    rc = lib().vvr_output_transform_preset(C.byref(t), int(transfer), int(primaries), abi.XFORM_TARGETS.get(target, target), float(src_peak), float(dst_peak), int(bit_depth))
+    if rc != abi.VVR_OK:
+        raise VvrError("vvr_output_transform_preset: transfer 16 or 18, primaries 1 or 9, a target of abi.XFORM_TARGETS, peaks in (0, 10000], bit depth 8 .. 10 (rc %d)" % rc)
+    return t
 
 
 class Reconstructor:
@@ -316,6 +332,18 @@ class Reconstructor:
         matrix_coefficients 1 (BT.709), 5 or 6 (BT.601) or 9 (BT.2020 non-constant luminance) and video_full_range_flag.  A request takes the
         value that is set when it is submitted."""
         self._check(self.L.vvr_set_output_colour(self.ctx, int(matrix), 1 if full_range else 0))
+
+    def set_output_transform(self, t):
+        """the colour transform the "rgb8" / "rgb16" / "rgbf16" formats of output_submit run between the Y'CbCr matrix and the store
+        (vvr_set_output_transform): None (none), an abi.OutputTransform (vvdec_amd.output_transform( ... ) makes the standard ones) or a tuple
+        (lin, m, enc) of arrays (abi.output_transform).  Under a transform "rgb16" is full-scale 16 bits.  A request takes the transform that is
+        set when it is submitted."""
+        if t is None:
+            self._check(self.L.vvr_set_output_transform(self.ctx, None))
+            return
+        if not isinstance(t, abi.OutputTransform):
+            t = abi.output_transform(*t)
+        self._check(self.L.vvr_set_output_transform(self.ctx, C.addressof(t)))
 
     def read_output(self, slot, window=None, bytes_per_sample=2, size=None, collocated=(True, False), grain=False):
         """the picture as the application gets it: conformance window (x, y, w, h in luma samples, even) applied, 8- or 16-bit samples.

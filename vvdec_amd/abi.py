@@ -204,6 +204,34 @@ def output_plane_shapes(window, fmt, size, ncomp):
     return shapes, np.uint8 if fmt == "planar8" else np.uint16
 
 
+XFORM_TO_SRGB, XFORM_TO_BT709, XFORM_TO_LINEAR = 0, 1, 2
+XFORM_TARGETS = {"srgb": XFORM_TO_SRGB, "bt709": XFORM_TO_BT709, "linear": XFORM_TO_LINEAR}
+
+
+class OutputTransform(C.Structure):
+    """vvr_output_transform: the colour transform of the RGB formats, 1-D table -> Q14 3x3 matrix -> 1-D table (vvr_set_output_transform, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("pad", u32), ("lin", u16 * 1024), ("m", (i32 * 3) * 3), ("enc", u16 * 1025), ("pad2", u16 * 3)]
+
+
+def output_transform(lin, m, enc):
+    """an OutputTransform from its fields as arrays: lin (1024,) and enc (1025,) uint16, m (3, 3) int32 in Q14"""
+    import numpy as np
+    t = OutputTransform()
+    t.struct_size = C.sizeof(OutputTransform)
+    for name, arr, dt in (("lin", lin, np.uint16), ("m", m, np.int32), ("enc", enc, np.uint16)):
+        field = getattr(t, name)
+        a = np.ascontiguousarray(arr, dtype=dt)
+        assert a.nbytes == C.sizeof(field), name
+        C.memmove(C.addressof(field), a.ctypes.data, a.nbytes)
+    return t
+
+
+def output_transform_arrays(t):
+    """(lin, m, enc) of an OutputTransform as numpy arrays (copies)"""
+    import numpy as np
+    return np.array(t.lin, np.uint16), np.array([list(r) for r in t.m], np.int32), np.array(t.enc, np.uint16)
+
+
 HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2
 HASH_LEN = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
 

@@ -174,6 +174,9 @@ struct vvr_context {
   std::unique_ptr<vvr_film_grain_bank> grainBank; void* grainBankDev = nullptr; bool grainBankStale = false; uint32_t grainSeed = 0xdeadbeefu;
   // colour description of the RGB formats of the output queue (vvr_set_output_colour): H.273 matrix_coefficients (0: none set) and the range flag
   int        outMatrix = 0, outFullRange = 0;
+  // ... and their colour transform (vvr_set_output_transform): the context's copy (NULL: none), its device copy - the struct as it is, k_output_rgb reads
+  // lin and enc out of it - refreshed on the output stream ahead of the first RGB request after a change (xformStale), as the grain bank is
+  std::unique_ptr<vvr_output_transform> xform; void* xformDev = nullptr; bool xformStale = false;
   // ---- job pipeline (everything below is guarded by mu)
   std::mutex mu, commitMu;              // commitMu: one committing thread at a time (it takes mu only around its bookkeeping)
   std::condition_variable cv;
@@ -1159,6 +1162,7 @@ VVR_API void vvr_destroy( vvr_context* c )
   if( c->scratchMem ) hipFree( c->scratchMem );
   if( c->outDev ) hipFree( c->outDev );
   if( c->grainBankDev ) hipFree( c->grainBankDev );
+  if( c->xformDev ) hipFree( c->xformDev );
   if( c->outHost ) hipHostFree( c->outHost );
   for( void* p : c->stagePool ) hipHostFree( p );
   if( c->prepStage ) hipHostFree( c->prepStage );

@@ -189,7 +189,11 @@ struct OutputRgbParams
   int format, collocated;
   int maxVal, yoff, coff;      // 2^bd - 1; 16 << ( bd - 8 ) or 0; 2^( bd - 1 )
   int cy, rv, gu, gv, bu, maxOut;      // the Q14 coefficients (vvr_output.inc, rgb_coefficients), 2^od - 1
-  float inv;                   // VVR_OUT_RGBF16: float32( 1 ) / float32( 2^bd - 1 )
+  float inv;                   // VVR_OUT_RGBF16: float32( 1 ) / float32( 2^bd - 1 ); under a transform float32( 1 ) / float32( 65535 )
+  // the colour transform (vvr_set_output_transform, the definition: vvr.h); xform == NULL: none.  xform: the device copy of the context's
+  // vvr_output_transform (lin and enc are read from it; 8-byte aligned); xm: its matrix, as kernel arguments.  The matrix above runs at od = bd
+  // then, whatever the format.
+  const vvr_output_transform* xform; int xm[3][3];
 };
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.

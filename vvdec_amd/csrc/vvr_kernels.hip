@@ -5093,11 +5093,18 @@ __device__ __forceinline__ void rgb_store( uint8_t* __restrict__ plane, size_t i
     }
   }
 }
-template<int COL, int FMT, bool WHOLE>
+// XF: the colour transform of vvr_set_output_transform (the definition: vvr.h) between the clip of R, G, B and the store, in registers.  The workgroup
+// brings the two tables into LDS with the staging (their loads are issued with the chroma window's, ahead of the first barrier): lin as it is (2 KB),
+// enc as 1024 pairs enc[i] | enc[i + 1] << 16 (4 KB), so that stage 3 is one 4-byte LDS read per value instead of two 2-byte ones; a sample costs three
+// reads of lin and three of the pairs.  Stage 2 is nine 64-bit multiply-adds (v_mad_i64_i32) per sample: | m | <= 2^16 times a 16-bit value, three
+// of them summed, needs 35 bits.  The instantiations without XF are the code they were (no table in LDS, no branch).
+template<int COL, int FMT, bool WHOLE, bool XF>
 __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_t* __restrict__ dst )
 {
   __shared__ uint16_t rgb_raw[2][RGB_CH][RGB_CW];
   __shared__ __attribute__(( aligned( 16 ) )) int rgb_sum[2][RGB_CH][RGB_SW];
+  __shared__ __attribute__(( aligned( 16 ) )) uint16_t xf_lin[XF ? 1024 : 4];
+  __shared__ __attribute__(( aligned( 16 ) )) uint32_t xf_enc[XF ? 1024 : 4];
   constexpr bool COLX = ( COL & 1 ) != 0, COLY = ( COL & 2 ) != 0;
   const int tid = threadIdx.x, X0 = blockIdx.x * RGB_TW, Y0 = blockIdx.y * RGB_TH;
   // the lane's 8 luma samples (2-byte aligned in general, as k_output_frame's piece); a row that ends inside them: pair by pair
@@ -5126,8 +5133,25 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
     const pel_t* __restrict__ s = pl ? p.src[2] : p.src[1];
     staged[i] = (uint16_t) s[(size_t) clip3( 0, ch - 1, cy0 + r ) * ( pl ? p.stride[2] : p.stride[1] ) + clip3( 0, cw - 1, cx0 + cc )];
   }
+  // the tables: lane t brings lin[4 t .. 4 t + 3] and the pairs 2 j, 2 j + 1 for j = t, t + 256 (dwords j and j + 1 of enc; dword 512 is
+  // enc[1024] and the struct's padding).  lin lies 8 bytes, enc 2092 bytes into the struct
+  uint2 xli = make_uint2( 0, 0 ); uint32_t xe[2][2] = { { 0, 0 }, { 0, 0 } };
+  if( XF )
+  {
+    const uint8_t* __restrict__ t = (const uint8_t*) p.xform;
+    xli = *(const uint2*) ( t + offsetof( vvr_output_transform, lin ) + 8 * tid );
+    const uint32_t* __restrict__ ge = (const uint32_t*) ( t + offsetof( vvr_output_transform, enc ) );
+#pragma unroll
+    for( int k = 0; k < 2; k++ ) { xe[k][0] = ge[tid + 256 * k]; xe[k][1] = ge[tid + 256 * k + 1]; }
+  }
 #pragma unroll
   for( int i = 0; i < PER_LANE; i++ ) if( tid + 256 * i < STAGED ) ( &rgb_raw[0][0][0] )[tid + 256 * i] = staged[i];
+  if( XF )
+  {
+    *(uint2*) &xf_lin[4 * tid] = xli;
+#pragma unroll
+    for( int k = 0; k < 2; k++ ) *(uint2*) &xf_enc[2 * ( tid + 256 * k )] = make_uint2( xe[k][0], xe[k][0] >> 16 | xe[k][1] << 16 );
+  }
   __syncthreads();
   // horizontal pass: output columns 2 k (phase 0 or 24) and 2 k + 1 (phase 16 or 8) of a staged row; c[2] is the chroma sample at column k of the tile
   for( int u = tid; u < 2 * RGB_CH * ( RGB_TW / 2 ); u += 256 )
@@ -5174,29 +5198,54 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
     G[i] = clip3( 0, p.maxOut, ( l + p.gu * u + p.gv * v ) >> 14 );
     B[i] = clip3( 0, p.maxOut, ( l + p.bu * u ) >> 14 );
   }
+  if( XF )
+  {
+#pragma unroll
+    for( int i = 0; i < 8; i++ )
+    {
+      const int lr = xf_lin[R[i] & 1023], lg = xf_lin[G[i] & 1023], lb = xf_lin[B[i] & 1023];      // (maxOut is 2^bd - 1 <= 1023)
+      int o[3];
+#pragma unroll
+      for( int k = 0; k < 3; k++ )
+      {
+        const int64_t acc = (int64_t) p.xm[k][0] * lr + (int64_t) p.xm[k][1] * lg + (int64_t) p.xm[k][2] * lb + 8192;
+        const int t = clip3( 0, 65535, (int) ( acc >> 14 ) );      // (| acc >> 14 | < 2^20)
+        const uint32_t e2 = xf_enc[t >> 6], f = t & 63;
+        const uint32_t ev = ( ( e2 & 0xffff ) * ( 64 - f ) + ( e2 >> 16 ) * f + 32 ) >> 6;
+        o[k] = (int) ( FMT == VVR_OUT_RGB8 ? ( ev + 128 ) / 257 : ev );
+      }
+      R[i] = o[0]; G[i] = o[1]; B[i] = o[2];
+    }
+  }
   const size_t i0 = (size_t) y * p.w + x;
   rgb_store<FMT, WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, p.inv, n );
   rgb_store<FMT, WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, G, p.inv, n );
   rgb_store<FMT, WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, B, p.inv, n );
 }
-template<int FMT, bool WHOLE>
+template<int FMT, bool WHOLE, bool XF>
 static void launch_output_rgb_as( hipStream_t s, const OutputRgbParams& p, void* dst )
 {
   const dim3 grid( ( p.w + RGB_TW - 1 ) / RGB_TW, ( p.h + RGB_TH - 1 ) / RGB_TH );
   switch( p.collocated & 3 )
   {
-  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  default: hipLaunchKernelGGL( ( k_output_rgb<3, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  default: hipLaunchKernelGGL( ( k_output_rgb<3, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
   }
+}
+template<int FMT>
+static void launch_output_rgb_fmt( hipStream_t s, const OutputRgbParams& p, void* dst )
+{
+  const bool whole = ( p.w & 7 ) == 0;      // (rows of a multiple of 8 samples: every lane has 8, at an aligned address)
+  if( p.xform ) { if( whole ) launch_output_rgb_as<FMT, true, true>( s, p, dst );  else launch_output_rgb_as<FMT, false, true>( s, p, dst ); }
+  else          { if( whole ) launch_output_rgb_as<FMT, true, false>( s, p, dst ); else launch_output_rgb_as<FMT, false, false>( s, p, dst ); }
 }
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst )
 {
-  const bool whole = ( p.w & 7 ) == 0;      // (rows of a multiple of 8 samples: every lane has 8, at an aligned address)
-  if( p.format == VVR_OUT_RGB8 )       { if( whole ) launch_output_rgb_as<VVR_OUT_RGB8, true>( s, p, dst );   else launch_output_rgb_as<VVR_OUT_RGB8, false>( s, p, dst ); }
-  else if( p.format == VVR_OUT_RGB16 ) { if( whole ) launch_output_rgb_as<VVR_OUT_RGB16, true>( s, p, dst );  else launch_output_rgb_as<VVR_OUT_RGB16, false>( s, p, dst ); }
-  else                                 { if( whole ) launch_output_rgb_as<VVR_OUT_RGBF16, true>( s, p, dst ); else launch_output_rgb_as<VVR_OUT_RGBF16, false>( s, p, dst ); }
+  if( p.format == VVR_OUT_RGB8 )       launch_output_rgb_fmt<VVR_OUT_RGB8>( s, p, dst );
+  else if( p.format == VVR_OUT_RGB16 ) launch_output_rgb_fmt<VVR_OUT_RGB16>( s, p, dst );
+  else                                 launch_output_rgb_fmt<VVR_OUT_RGBF16>( s, p, dst );
 }
 
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in

@@ -261,11 +261,20 @@ void launch_output_frame( hipStream_t, OutputFrameParams p, void* dst )
 // ... and launch_output_rgb (k_output_rgb): the definition of vvr.h sample by sample - positions, phases and taps from the table as launch_rescale
 // takes them (step 16, add 0 / -8, shift 0, the chroma filter), the matrix, the three stores
 namespace {
-uint16_t rgb_half_rne( float f )      // 0 or 1 / 1023 <= f <= 1: zero or a normal half; round to nearest even (a carry out of the mantissa raises the exponent)
+uint16_t rgb_half_rne( float f )      // 0 or 1 / 65535 <= f <= 1: zero, a subnormal (below 2^-14: under a transform) or a normal half; round to nearest even (a carry out of the mantissa raises the exponent)
 {
   uint32_t b; memcpy( &b, &f, 4 );
   if( !b ) return 0;
-  uint32_t h = ( ( b >> 23 ) - 127 + 15 ) << 10 | ( b & 0x7fffff ) >> 13;
+  const int e = (int) ( b >> 23 ) - 127;
+  if( e < -14 )      // in units of 2^-24
+  {
+    const uint32_t man = ( b & 0x7fffff ) | 0x800000; const int sh = -e - 1;
+    if( sh > 24 ) return 0;
+    uint32_t q = man >> sh; const uint32_t rem = man & ( ( 1u << sh ) - 1 ), half = 1u << ( sh - 1 );
+    if( rem > half || ( rem == half && ( q & 1 ) ) ) q++;
+    return (uint16_t) q;
+  }
+  uint32_t h = (uint32_t) ( e + 15 ) << 10 | ( b & 0x7fffff ) >> 13;
   const uint32_t rem = b & 0x1fff;
   if( rem > 0x1000 || ( rem == 0x1000 && ( h & 1 ) ) ) h++;
   return (uint16_t) h;
@@ -306,9 +315,19 @@ void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
       const size_t at = (size_t) j * p.w + i;
       const int y = p.src[0][(size_t) j * p.stride[0] + i] - p.yoff, u = up[0][at] - p.coff, v = up[1][at] - p.coff;
       const int rgb[3] = { ( p.cy * y + p.rv * v + 8192 ) >> 14, ( p.cy * y + p.gu * u + p.gv * v + 8192 ) >> 14, ( p.cy * y + p.bu * u + 8192 ) >> 14 };
+      int L[3] = { 0, 0, 0 };
+      for( int c = 0; c < 3 && p.xform; c++ ) L[c] = p.xform->lin[std::min( std::max( 0, rgb[c] ), p.maxOut )];      // (stage 1)
       for( int c = 0; c < 3; c++ )
       {
-        const int val = std::min( std::max( 0, rgb[c] ), p.maxOut );
+        int val = std::min( std::max( 0, rgb[c] ), p.maxOut );
+        if( p.xform )
+        {
+          // stages 2 and 3, the 16 -> 8 bit reduction of RGB8 (vvr.h)
+          const int64_t acc = (int64_t) p.xm[c][0] * L[0] + (int64_t) p.xm[c][1] * L[1] + (int64_t) p.xm[c][2] * L[2] + 8192;
+          const int t = (int) std::min<int64_t>( std::max<int64_t>( 0, acc >> 14 ), 65535 ), i = t >> 6, f = t & 63;
+          val = ( p.xform->enc[i] * ( 64 - f ) + p.xform->enc[i + 1] * f + 32 ) >> 6;
+          if( p.format == VVR_OUT_RGB8 ) val = ( val + 128 ) / 257;
+        }
         uint8_t* out = p.direct[c] ? p.direct[c] : (uint8_t*) dst + p.dstOff[c];
         if( p.format == VVR_OUT_RGB8 ) out[at] = (uint8_t) val;
         else ( (uint16_t*) out )[at] = p.format == VVR_OUT_RGB16 ? (uint16_t) val : rgb_half_rne( (float) val * p.inv );
@@ -445,6 +464,84 @@ VVR_API int vvr_set_output_colour( vvr_context* c, int matrixCoefficients, int f
   if( !rgb_matrix( matrixCoefficients, kr, kb ) ) { c->setError( "vvr_set_output_colour: matrix_coefficients must be 1 (BT.709), 5 or 6 (BT.601) or 9 (BT.2020 non-constant luminance)" ); return VVR_ERR_PARAMETER; }
   if( fullRange != 0 && fullRange != 1 ) { c->setError( "vvr_set_output_colour: full_range must be 0 or 1" ); return VVR_ERR_PARAMETER; }
   c->outMatrix = matrixCoefficients; c->outFullRange = fullRange;
+  return VVR_OK;
+}
+
+VVR_API int vvr_set_output_transform( vvr_context* c, const vvr_output_transform* t )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  if( !t ) { c->xform.reset(); return VVR_OK; }
+  if( t->struct_size != sizeof( vvr_output_transform ) ) { c->setError( "vvr_set_output_transform: struct_size is not sizeof( vvr_output_transform )" ); return VVR_ERR_PARAMETER; }
+  for( int k = 0; k < 3; k++ )
+    for( int j = 0; j < 3; j++ )
+      if( t->m[k][j] < -65536 || t->m[k][j] > 65536 ) { c->setError( "vvr_set_output_transform: matrix entry beyond +-65536 (4.0 in Q14)" ); return VVR_ERR_PARAMETER; }
+  if( !c->xform ) c->xform.reset( new vvr_output_transform );
+  *c->xform = *t;
+  c->xformStale = true;
+  return VVR_OK;
+}
+
+// the tables of the standard cases, every formula as vvr.h gives it, in double
+VVR_API int vvr_output_transform_preset( vvr_output_transform* out, int transfer, int primaries, int target, double srcPeak, double dstPeak, int bitDepth )
+{
+  if( !out || ( transfer != 16 && transfer != 18 ) || ( primaries != 1 && primaries != 9 ) || target < VVR_XFORM_TO_SRGB || target > VVR_XFORM_TO_LINEAR || bitDepth < 8 || bitDepth > 10 ) return VVR_ERR_PARAMETER;
+  if( transfer == 16 && !( srcPeak > 0 && srcPeak <= 10000 && dstPeak > 0 && dstPeak <= 10000 ) ) return VVR_ERR_PARAMETER;
+  auto q16 = []( double v ) { return (uint16_t) std::floor( v * 65535 + 0.5 ); };
+  // stage 1: PQ EOTF behind the BT.2390 EETF, or the inverse HLG OETF
+  const double m1 = 2610. / 16384, m2 = 2523. / 4096 * 128, c1 = 3424. / 4096, c2 = 2413. / 4096 * 32, c3 = 2392. / 4096 * 32;
+  auto pqEotf = [&]( double e ) { const double p = std::pow( e, 1 / m2 ); return 10000 * std::pow( std::max( p - c1, 0. ) / ( c2 - c3 * p ), 1 / m1 ); };
+  auto pqInv = [&]( double nits ) { const double y = std::pow( nits / 10000, m1 ); return std::pow( ( c1 + c2 * y ) / ( 1 + c3 * y ), m2 ); };
+  const double lo = pqInv( 0 ), hi = pqInv( srcPeak ), maxLum = ( pqInv( dstPeak ) - lo ) / ( hi - lo ), ks = 1.5 * maxLum - 0.5;
+  auto eetf = [&]( double e )
+  {
+    const double e1 = std::min( std::max( ( e - lo ) / ( hi - lo ), 0. ), 1. );
+    double e2 = e1;
+    if( ks < 1 && e1 >= ks )
+    {
+      const double t = ( e1 - ks ) / ( 1 - ks ), t2 = t * t, t3 = t2 * t;
+      e2 = ( 2 * t3 - 3 * t2 + 1 ) * ks + ( t3 - 2 * t2 + t ) * ( 1 - ks ) + ( -2 * t3 + 3 * t2 ) * maxLum;
+    }
+    return e2 * ( hi - lo ) + lo;
+  };
+  const double ha = 0.17883277, hb = 1 - 4 * ha, hc = 0.5 - ha * std::log( 4 * ha );
+  vvr_output_transform t; memset( &t, 0, sizeof( t ) );
+  t.struct_size = sizeof( t );
+  const int top = ( 1 << bitDepth ) - 1;
+  for( int v = 0; v <= top; v++ )
+  {
+    const double e = (double) v / top;
+    t.lin[v] = q16( transfer == 16 ? std::min( pqEotf( eetf( e ) ) / dstPeak, 1. ) : ( e <= 0.5 ? e * e / 3 : ( std::exp( ( e - hc ) / ha ) + hb ) / 12 ) );
+  }
+  // stage 2: inverse( N709 ) * Nsrc, the normalised primary matrices from the chromaticities
+  auto npm = []( const double xy[3][2], double n[3][3] )
+  {
+    const double wx = 0.3127, wy = 0.3290, w[3] = { wx / wy, 1, ( 1 - wx - wy ) / wy };
+    double p[3][3], inv[3][3];
+    for( int j = 0; j < 3; j++ ) { p[0][j] = xy[j][0] / xy[j][1]; p[1][j] = 1; p[2][j] = ( 1 - xy[j][0] - xy[j][1] ) / xy[j][1]; }
+    const double det = p[0][0] * ( p[1][1] * p[2][2] - p[1][2] * p[2][1] ) - p[0][1] * ( p[1][0] * p[2][2] - p[1][2] * p[2][0] ) + p[0][2] * ( p[1][0] * p[2][1] - p[1][1] * p[2][0] );
+    for( int i = 0; i < 3; i++ ) for( int j = 0; j < 3; j++ )
+      inv[j][i] = ( p[( i + 1 ) % 3][( j + 1 ) % 3] * p[( i + 2 ) % 3][( j + 2 ) % 3] - p[( i + 1 ) % 3][( j + 2 ) % 3] * p[( i + 2 ) % 3][( j + 1 ) % 3] ) / det;
+    for( int j = 0; j < 3; j++ ) { const double sc = inv[j][0] * w[0] + inv[j][1] * w[1] + inv[j][2] * w[2]; for( int i = 0; i < 3; i++ ) n[i][j] = p[i][j] * sc; }
+  };
+  if( primaries == 1 ) for( int k = 0; k < 3; k++ ) t.m[k][k] = 16384;
+  else
+  {
+    const double xy709[3][2] = { { 0.640, 0.330 }, { 0.300, 0.600 }, { 0.150, 0.060 } }, xy2020[3][2] = { { 0.708, 0.292 }, { 0.170, 0.797 }, { 0.131, 0.046 } };
+    double a[3][3], b[3][3], ai[3][3];
+    npm( xy709, a ); npm( xy2020, b );
+    const double det = a[0][0] * ( a[1][1] * a[2][2] - a[1][2] * a[2][1] ) - a[0][1] * ( a[1][0] * a[2][2] - a[1][2] * a[2][0] ) + a[0][2] * ( a[1][0] * a[2][1] - a[1][1] * a[2][0] );
+    for( int i = 0; i < 3; i++ ) for( int j = 0; j < 3; j++ )
+      ai[j][i] = ( a[( i + 1 ) % 3][( j + 1 ) % 3] * a[( i + 2 ) % 3][( j + 2 ) % 3] - a[( i + 1 ) % 3][( j + 2 ) % 3] * a[( i + 2 ) % 3][( j + 1 ) % 3] ) / det;
+    for( int k = 0; k < 3; k++ ) for( int j = 0; j < 3; j++ ) t.m[k][j] = (int32_t) std::floor( ( ai[k][0] * b[0][j] + ai[k][1] * b[1][j] + ai[k][2] * b[2][j] ) * 16384 + 0.5 );
+  }
+  // stage 3: the target's OETF
+  for( int i = 0; i <= 1024; i++ )
+  {
+    const double x = std::min( 64 * i, 65535 ) / 65535.;
+    t.enc[i] = q16( target == VVR_XFORM_TO_SRGB ? ( x <= 0.0031308 ? 12.92 * x : 1.055 * std::pow( x, 1 / 2.4 ) - 0.055 ) : target == VVR_XFORM_TO_BT709 ? ( x < 0.018 ? 4.5 * x : 1.099 * std::pow( x, 0.45 ) - 0.099 ) : x );
+  }
+  *out = t;
   return VVR_OK;
 }
 
@@ -856,6 +953,11 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( devPlanes && devPlanes != nOut ) { c->setError( "vvr_output_submit: destination planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
   const bool devDst = devPlanes != 0;
   if( rgb ) { outMatrix = c->outMatrix; outFullRange = c->outFullRange; }      // (what is set now, behind the waits above: a description cannot be unset)
+  // the colour transform the request takes: the one that is set now.  Its matrix goes with the request as kernel arguments; its tables, when
+  // they have changed, are refreshed on the output stream ahead of the request's kernel - behind the kernels of the requests in flight
+  const bool xf = rgb && c->xform, xfUpload = xf && c->xformStale;
+  int xm[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+  if( xf ) memcpy( xm, c->xform->m, sizeof( xm ) );
   outTake( c, e, slot, rq->job, jobFailed ); e->nc = nOut;
   if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
   // ---- the entry's buffers: the output's planes; the 16-bit planes of a grained frame that goes on (A) and of a rescaled plane that is packed (B); the words
@@ -879,7 +981,8 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   const size_t wordsBytes = grain ? (size_t) nbx * nby * sizeof( uint32_t ) : 0, wordsOff = tmpBytes, hostWordsOff = direct ? 0 : total;
   tmpBytes += alignUp( wordsBytes, 256 );
   const size_t hostBankOff = hostWordsOff + alignUp( wordsBytes, 256 );      // (a bank that changed travels through the entry's pinned memory: the context's copy may change while the upload is in flight)
-  if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostBankOff + ( grain && c->grainBankStale ? sizeof( vvr_film_grain_bank ) : 0 ), true ) != VVR_OK )
+  const size_t hostXformOff = hostBankOff + ( grain && c->grainBankStale ? alignUp( sizeof( vvr_film_grain_bank ), 256 ) : 0 );      // (... and so do the tables of a transform that changed)
+  if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostXformOff + ( xfUpload ? sizeof( vvr_output_transform ) : 0 ), true ) != VVR_OK )
   { c->setError( "vvr_output_submit: out of device or pinned memory" ); return VVR_ERR_DEVICE; }
   e->direct = direct; e->devDst = devDst;
   // ---- 3. behind the picture (or the slot's users) on the device, 4. the kernels.  mu stays held up to the registration of the `read` event: a
@@ -947,7 +1050,18 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     OutputRgbParams rp; memset( &rp, 0, sizeof( rp ) );
     for( int k = 0; k < 3; k++ ) { rp.src[k] = cur[k].p; rp.stride[k] = cur[k].stride; rp.dstOff[k] = e->off[k]; rp.direct[k] = kdirect[k] ? (uint8_t*) rq->dst[k] : nullptr; }
     rp.w = ow[0]; rp.h = oh[0]; rp.format = rq->format; rp.collocated = rq->collocated & 3;
-    rgb_coefficients( outMatrix, outFullRange, bd, rq->format == VVR_OUT_RGB8 ? 8 : bd, rp );
+    rgb_coefficients( outMatrix, outFullRange, bd, rq->format == VVR_OUT_RGB8 && !xf ? 8 : bd, rp );
+    if( xf )
+    {
+      if( !c->xformDev ) OQCHK( hipMalloc( &c->xformDev, sizeof( vvr_output_transform ) ) );
+      if( xfUpload )
+      {
+        memcpy( e->host + hostXformOff, c->xform.get(), sizeof( vvr_output_transform ) );
+        OQCHK( hipMemcpyAsync( c->xformDev, e->host + hostXformOff, sizeof( vvr_output_transform ), hipMemcpyHostToDevice, s ) );
+      }
+      rp.xform = (const vvr_output_transform*) c->xformDev; memcpy( rp.xm, xm, sizeof( xm ) );
+      rp.inv = 1.0f / 65535.0f;
+    }
     outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + 3. * bps ) );
     launch_output_rgb( s, rp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
@@ -957,6 +1071,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   c->slotExt[slot].push_back( e->read );
   e->state = OQ_FLIGHT; e->queued = true;
   if( grain ) { c->grainBankStale = false; c->grainSeed = nextSeed; }      // (the chain advances at submit, for an accepted request only)
+  if( xfUpload ) c->xformStale = false;
   const int ticket = e->ticket;
   lk.unlock();
   // ---- the result's way to the host: exactly the output's bytes
