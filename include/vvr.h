@@ -544,9 +544,24 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *              RGB8: uint8.  RGB16: little-endian uint16, od = bd.  RGBF16: IEEE half, the RGB16 value v as half( float32( v ) * inv ) with
  *              inv = float32( 1 ) / float32( 2^bd - 1 ): one correctly rounded float32 multiply, one conversion rounding to nearest even.
  *            Refused: no colour description set, a 4:0:0 context (no chroma), a bit depth outside 8..10, an odd out_w or out_h, a missing plane
- *            among the three or a stride below the row.  Primaries and transfer conversion: vvr_set_output_transform below.  Not offered:
- *            interleaved or packed RGB(A), BGR, float32; constant-luminance BT.2020, ICtCp, YCgCo, the identity matrix; 3-D LUTs and
- *            luminance-based tone mapping; 4:0:0 as grey; the synchronous vvr_read_output* calls.
+ *            among the three or a stride below the row.  Primaries and transfer conversion: vvr_set_output_transform below.
+ *            VVR_OUT_RGBF32: the three planes as IEEE float32, rows of out_w * 4 bytes, for a model that takes ( 3, H, W ) float32 with a mean and a
+ *            standard deviation per channel applied (vvr_set_output_normalisation below, where the value is defined to the bit).
+ *            VVR_OUT_RGBA8 / _BGRA8 / _RGB24 / _BGR24 / _RGB10A2 / _RGBA16F: the same pixels interleaved, for a display surface, a compositor, an
+ *            encoder's RGB input, an HDR swap chain, OpenCV- or PIL-style code.  One plane leaves the request, dst[0]; dst[1], dst[2] and their
+ *            strides are ignored and may be NULL / 0.  A pixel in memory order, a row of out_w pixels:
+ *              RGBA8   4 bytes  R, G, B, 255        BGRA8   4 bytes  B, G, R, 255        - the bytes VVR_OUT_RGB8 stores
+ *              RGB24   3 bytes  R, G, B             BGR24   3 bytes  B, G, R             - the bytes VVR_OUT_RGB8 stores
+ *              RGBA16F 8 bytes  four little-endian halves R, G, B, 0x3C00 (1.0)          - the halves VVR_OUT_RGBF16 stores
+ *              RGB10A2 4 bytes  the little-endian dword R | G << 10 | B << 20 | 3 << 30.  Without a transform the matrix runs at od = 10
+ *                      (m = 1023) for every bit depth 8, 9 and 10: the widening is a rounding through the coefficients, as the narrowing of RGB8 is.
+ *                      Under a transform: ( Ek * 1023 + 32767 ) / 65535 in integer division, the correctly rounded 16 -> 10 bit reduction (65535
+ *                      is odd: no ties).
+ *            "the bytes X stores": the definition of X above and below, with or without a transform - RGB8's od = 8 without one and od = bd,
+ *            ( Ek + 128 ) / 257 with one included.  The refusals are those of the three planar formats, a missing plane or a stride below the
+ *            row among the planes the format uses.
+ *            Not offered: interleaved float32; 4:0:0 as grey; RGB from the synchronous vvr_read_output* calls; constant-luminance BT.2020,
+ *            ICtCp, YCgCo, the identity matrix; 3-D LUTs and luminance-based tone mapping.
  *   grain with out_w / out_h: the window is grained at its own size exactly as vvr_read_output_grain does it, the grained frame is then
  *            rescaled exactly as vvr_read_output_scaled rescales a picture, taps clamped to the grained frame (the reference's order:
  *            xAddGrain in xAddPicture, then the application's upscaleFrame).
@@ -571,7 +586,8 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *   the job's status from vvr_output_test / vvr_output_wait.  vvr_output_test: VVR_OK (vvr_output_wait returns at once) / VVR_NOT_READY / the
  *   failure; the ticket stays.  vvr_output_wait blocks for THIS request only and retires the ticket.  An unknown or retired ticket:
  *   VVR_ERR_PARAMETER.  vvr_sync also waits for the requests in flight but retires no ticket. */
-enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2, VVR_OUT_NV12 = 16, VVR_OUT_P010 = 17, VVR_OUT_RGB8 = 32, VVR_OUT_RGB16 = 33, VVR_OUT_RGBF16 = 34 };
+enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2, VVR_OUT_NV12 = 16, VVR_OUT_P010 = 17, VVR_OUT_RGB8 = 32, VVR_OUT_RGB16 = 33, VVR_OUT_RGBF16 = 34,
+       VVR_OUT_RGBF32 = 36, VVR_OUT_RGBA8 = 48, VVR_OUT_BGRA8 = 49, VVR_OUT_RGB24 = 50, VVR_OUT_BGR24 = 51, VVR_OUT_RGB10A2 = 52, VVR_OUT_RGBA16F = 53 };
 typedef struct vvr_output_request {
   uint32_t struct_size;        /* sizeof( vvr_output_request ) */
   int32_t  slot;
@@ -583,7 +599,7 @@ typedef struct vvr_output_request {
   uint8_t  format;             /* VVR_OUT_* */
   uint8_t  grain;              /* 1: the context's bank is added first, one frame of the seed chain (vvr_read_output_grain's rules) */
   uint8_t  blocking;           /* 0: VVR_NOT_READY instead of waiting on the host until `job` has been handed to the device */
-  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0; dst[2] unused by VVR_OUT_NV12 / VVR_OUT_P010; R, G, B for VVR_OUT_RGB* */
+  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0; dst[2] unused by VVR_OUT_NV12 / VVR_OUT_P010; R, G, B for the planar VVR_OUT_RGB*; dst[0] alone for the interleaved ones */
   size_t   dst_stride_bytes[3];
 } vvr_output_request;
 /* the colour description the RGB formats convert with - context state, like the film grain bank; a new context has none.  matrix_coefficients
@@ -592,13 +608,25 @@ typedef struct vvr_output_request {
  * stays.  A request takes the value that is set when vvr_output_submit accepts it: the coefficients travel as kernel arguments, a later call
  * never changes a request in flight. */
 VVR_API int          vvr_set_output_colour(vvr_context* ctx, int matrix_coefficients, int full_range);
+/* Normalisation of VVR_OUT_RGBF32: a mean and a standard deviation per channel (R, G, B), as a vision model takes them.  Context state like the
+ * colour description (copied; NULL, NULL: none; a new context has none): a VVR_OUT_RGBF32 request takes the value that is set when
+ * vvr_output_submit accepts it, it travels as kernel arguments, a later call never changes a request in flight.  Every other format -
+ * VVR_OUT_RGBF16 and VVR_OUT_RGBA16F too - ignores it.  Defined to the bit:
+ *   v        the value VVR_OUT_RGB16 stores for the channel, 0 .. M: M = 2^bd - 1 without a transform, 65535 with one.
+ *   scale[c] = (float)( 1.0 / ( (double) M * (double) std[c] ) ), bias[c] = (float)( -(double) mean[c] / (double) std[c] ): computed on the host in
+ *            double, rounded once.  None set: scale[c] = (float)( 1.0 / M ), bias[c] = +0.
+ *   t = float32( v ) * scale[c], one correctly rounded float32 multiply; out = t + bias[c], one correctly rounded float32 add; never an FMA.
+ * Refused (VVR_ERR_PARAMETER with a text, the value set before stays in force): one of the two pointers NULL, an entry that is not finite, a
+ * std[c] outside [ 2^-20, 2^20 ], a | mean[c] | above 2^20.  Within these bounds no product, sum or result is subnormal: the result does not
+ * depend on a denormal mode. */
+VVR_API int          vvr_set_output_normalisation(vvr_context* ctx, const float mean[3], const float std[3]);
 /* Linear-light colour transform of the RGB formats: 1-D table -> 3x3 matrix -> 1-D table, the shaper / matrix / shaper of colour management and the
  * degamma / CTM / gamma of a display controller - what brings PQ- or HLG-coded BT.2020 R'G'B' to sRGB or BT.709 for a model, a display path or a
  * thumbnailer.  Context state like the colour description (copied; NULL: none; a new context has none).  It runs inside the RGB request's one
  * kernel, in registers, between the Y'CbCr matrix above and the store.  The integer pipeline is defined here to the bit; the floating-point
  * colour science lives only in how the tables are filled (vvr_output_transform_preset fills them for the standard cases, the caller keeps the
  * choice of any other tone curve).
- *   which requests   a VVR_OUT_RGB8 / _RGB16 / _RGBF16 request takes the transform that is set when vvr_output_submit accepts it (the rule of the
+ *   which requests   a request of any RGB format (planar or interleaved) takes the transform that is set when vvr_output_submit accepts it (the rule of the
  *            colour description): the tables are refreshed on the output stream ahead of the request's kernel, the matrix travels as kernel
  *            arguments, so a later vvr_set_output_transform never changes a request in flight.  Every other format ignores the transform, and so
  *            does every synchronous call.

@@ -8,16 +8,21 @@ K timed pictures behind pre-roll and warm-up, every window from the first pictur
   F  the output queue, VVR_OUT_P010 into device memory (vvr_device_alloc): nothing crosses PCIe
   G  the output queue, VVR_OUT_RGB16 into device memory: one (3, H, W) tensor per request, BT.709 limited range (k_output_rgb)
   H  the output queue, VVR_OUT_RGBF16 into device memory, likewise
+  I  the output queue, VVR_OUT_BGRA8 into device memory: one (H, W, 4) tensor of bytes per request
+  J  the output queue, VVR_OUT_RGB24 into device memory: one (H, W, 3) tensor of bytes
+  K  the output queue, VVR_OUT_RGBA16F into device memory: one (H, W, 4) tensor of halves
+  L  the output queue, VVR_OUT_RGBF32 into device memory: one (3, H, W) tensor of float32, ImageNet mean and standard deviation applied
 and the decode-only rate of the same window (nothing leaves the device).  The ways alternate window by window; every way runs at least --windows
 windows and --min-seconds of timed work; median, minimum and maximum are reported.  Before the timed runs the outputs of A and B of the timed pictures
 are compared (they must be identical).  Requests are submitted without blocking behind their picture and collected when 8 are in flight.
 Kernel time: `rocprofv3 --kernel-trace --stats -- python tools/output_queue_probe.py --ways D --windows 2 --min-seconds 0` in a run of its own
 (--ways FG: k_output_frame storing P010 and k_output_rgb on the same frames in one trace).
 --frame N: one 3840x2160 10-bit frame instead of a stream, N repeats of every configuration in turn (planar16 and p010 into memory of
-vvr_host_alloc and into device memory, rgb8 / rgb16 / rgbf16 into device memory): the time of k_output_frame or k_output_rgb (HIP events around the launch, vvr_get_stats) and the time from
-vvr_output_submit to the return of vvr_output_wait, median / minimum / maximum.  --root DIR measures the package of another checkout of the project
+vvr_host_alloc and into device memory, every RGB format into device memory): the time of k_output_frame or k_output_rgb (HIP events around the launch, vvr_get_stats) and the time from
+vvr_output_submit to the return of vvr_output_wait, median / minimum / maximum; and what a caller without the interleaved and float32 formats does
+behind a planar request, timed with torch events: torch.stack( rgb8 planes, dim = -1 ), and rgbf16 .float() with mean and standard deviation.  --root DIR measures the package of another checkout of the project
 (the parent commit, say) with this script, so that both can run in one call on one box; configurations that checkout does not have are left out.
-Usage: python tools/output_queue_probe.py [--steps 64] [--warmup 16] [--windows 5] [--min-seconds 1.0] [--ways ABCDEFGHN] [--out FILE]
+Usage: python tools/output_queue_probe.py [--steps 64] [--warmup 16] [--windows 5] [--min-seconds 1.0] [--ways ABCDEFGHIJKLN] [--out FILE]
        python tools/output_queue_probe.py --frame 50 [--root DIR] [--out FILE]"""
 import argparse
 import ctypes as C
@@ -30,6 +35,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # (ImageNet's, as torchvision documents them)
 
 
 def frame_mode(a):
@@ -48,9 +54,11 @@ def frame_mode(a):
     configs = {}
     if "rgb16" in abi.OUT_FORMATS:
         rec.set_output_colour(1, False)
-    for fmt in ("planar16", "p010", "rgb8", "rgb16", "rgbf16"):
+    if hasattr(rec, "set_output_normalisation"):
+        rec.set_output_normalisation(MEAN, STD)
+    for fmt in ("planar16", "p010", "rgb8", "rgb16", "rgbf16", "rgbf32", "rgba8", "bgra8", "rgb24", "bgr24", "rgb10a2", "rgba16f"):
         for where in ("pinned", "device"):
-            if fmt not in abi.OUT_FORMATS or (where == "device" and not hasattr(rec, "device_array")) or (fmt.startswith("rgb") and where == "pinned"):
+            if fmt not in abi.OUT_FORMATS or (where == "device" and not hasattr(rec, "device_array")) or (fmt[:3] in ("rgb", "bgr") and where == "pinned"):
                 continue
             shapes, dt = abi.output_plane_shapes(win, fmt, None, 3)
             item = np.dtype(dt).itemsize
@@ -58,7 +66,7 @@ def frame_mode(a):
                 planes = [rec.host_array(r * n, dt).reshape(r, n) for r, n in shapes]
             else:
                 import torch
-                planes = [rec.device_array(r * n * item).view(torch.uint8 if item == 1 else torch.int16).view(r, n) for r, n in shapes]
+                planes = [rec.device_array(r * n * item).view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[item]).view(r, n) for r, n in shapes]
             configs[fmt + "_" + where] = abi.output_request(0, None, win, fmt, None, (True, False), False, True, planes), planes
     times = {name: ([], []) for name in configs}
     for n in range(3 + a.frame):                  # (the first three rounds warm up: ring entries, scratch)
@@ -72,8 +80,26 @@ def frame_mode(a):
                 times[name][1].append((t1 - t0) * 1e3)
     res = {"mode": "frame", "size": [W, H], "bit_depth": 10, "repeats": a.frame, "root": os.path.abspath(a.root or ROOT)}
     for name, (k, t) in times.items():
-        res[name] = {("k_output_rgb_ms" if name.startswith("rgb") else "k_output_frame_ms"): {"median": round(float(np.median(k)), 4), "min": round(min(k), 4), "max": round(max(k), 4)},
+        res[name] = {("k_output_rgb_ms" if name[:3] in ("rgb", "bgr") else "k_output_frame_ms"): {"median": round(float(np.median(k)), 4), "min": round(min(k), 4), "max": round(max(k), 4)},
                      "submit_to_completion_ms": {"median": round(float(np.median(t)), 4), "min": round(min(t), 4), "max": round(max(t), 4)}}
+    # what a caller does today behind the planar request (the planes are in device memory already): the extra passes, torch events around them
+    if "rgb8_device" in configs and "rgbf16_device" in configs:
+        import torch
+        p8 = configs["rgb8_device"][1]
+        pf = [p.view(torch.float16) for p in configs["rgbf16_device"][1]]
+        mean, std = [torch.tensor(v, dtype=torch.float32, device=p8[0].device).view(3, 1, 1) for v in (MEAN, STD)]
+        todays = {"torch_stack_of_rgb8": lambda: torch.stack(p8, dim=-1), "float_and_normalise_of_rgbf16": lambda: (torch.stack(pf).float() - mean) / std}
+        for name, fn in todays.items():
+            ms = []
+            for n in range(3 + a.frame):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if n >= 3:
+                    ms.append(e0.elapsed_time(e1))
+            res[name] = {"torch_ms": {"median": round(float(np.median(ms)), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}}
     rec.close()
     return res
 
@@ -84,7 +110,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--min-seconds", type=float, default=1.0)
-    ap.add_argument("--ways", default="ABCDEFGHN")
+    ap.add_argument("--ways", default="ABCDEFGHIJKLN")
     ap.add_argument("--config", default="4k")
     ap.add_argument("--out", default="")
     ap.add_argument("--frame", type=int, default=0)
@@ -121,9 +147,11 @@ def main():
         shapes, dt = abi.output_plane_shapes((0, 0, W, H), fmt, None, 3)
         if device:
             import torch
-            if fmt.startswith("rgb"):      # (as a model takes it: the planes of one contiguous (3, H, W) tensor)
-                return list(rec.device_array(3 * H * W * 2).view(torch.int16).view(3, H, W))
-            return [rec.device_array(r * n * 2).view(torch.int16).view(r, n) for r, n in shapes]
+            item = np.dtype(dt).itemsize
+            tdt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[item]
+            if len(shapes) == 3 and fmt.startswith("rgb"):      # (as a model takes it: the planes of one contiguous (3, H, W) tensor)
+                return list(rec.device_array(3 * H * W * item).view(tdt).view(3, H, W))
+            return [rec.device_array(r * n * item).view(tdt).view(r, n) for r, n in shapes]      # (an interleaved format: the (H, W, C) tensor as its one plane of rows)
         return [rec.host_array(r * n, dt).reshape(r, n) if pinned else np.zeros((r, n), dt) for r, n in shapes]
     sets = {"B": ("planar16", [planes("planar16", False) for _ in range(8)]), "C": ("planar16", [planes("planar16", True) for _ in range(8)]),
             "D": ("packed10", [planes("packed10", True) for _ in range(8)])}
@@ -131,14 +159,16 @@ def main():
         sets["E"] = ("p010", [planes("p010", True) for _ in range(8)])
     if "F" in a.ways:
         sets["F"] = ("p010", [planes("p010", False, True) for _ in range(8)])
-    for way, fmt in (("G", "rgb16"), ("H", "rgbf16")):
+    if "L" in a.ways and hasattr(rec, "set_output_normalisation"):
+        rec.set_output_normalisation(MEAN, STD)
+    for way, fmt in (("G", "rgb16"), ("H", "rgbf16"), ("I", "bgra8"), ("J", "rgb24"), ("K", "rgba16f"), ("L", "rgbf32")):
         if way in a.ways and fmt in abi.OUT_FORMATS:      # (--root of a checkout without the RGB formats: the ways are left out)
             rec.set_output_colour(1, False)
             sets[way] = (fmt, [planes(fmt, False, True) for _ in range(8)])
     reqs = {w: [abi.output_request(0, 0, (0, 0, W, H), fmt, None, (True, False), False, False, p) for p in ps] for w, (fmt, ps) in sets.items()}
     sync_out = planes("planar16", False)
     pcie = {"A": sum(p.nbytes for p in sync_out), "B": sum(p.nbytes for p in sets["B"][1][0]), "C": sum(p.nbytes for p in sets["C"][1][0]),
-            "D": sum(p.nbytes for p in sets["D"][1][0]), "E": W * H * 3, "F": 0, "G": 0, "H": 0, "N": 0}
+            "D": sum(p.nbytes for p in sets["D"][1][0]), "E": W * H * 3, "F": 0, "G": 0, "H": 0, "I": 0, "J": 0, "K": 0, "L": 0, "N": 0}
 
     def run(way, idx, digests=None):
         """the pictures `idx` through vvr_submit, every one of them delivered the way `way` says"""
@@ -199,7 +229,7 @@ def main():
         window("A", da)
         window("B", db)
         res["outputs_A_equal_B"] = len(da) == K and da == db
-    ways = [w for w in "ABCDEFGHN" if w in a.ways and (w in "AN" or w in sets)]
+    ways = [w for w in "ABCDEFGHIJKLN" if w in a.ways and (w in "AN" or w in sets)]
     times = {w: [] for w in ways}
     for w in ways:                                   # warm-up: every way once (ring entries, pinned staging)
         window(w)

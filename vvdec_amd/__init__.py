@@ -76,6 +76,8 @@ def lib():
         L.vvr_set_film_grain_seed.argtypes = [C.c_void_p, C.c_uint32]
         L.vvr_set_output_colour.restype = C.c_int
         L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.vvr_set_output_normalisation.restype = C.c_int
+        L.vvr_set_output_normalisation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vvr_set_output_transform.restype = C.c_int
         L.vvr_set_output_transform.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_output_transform_preset.restype = C.c_int
@@ -122,7 +124,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
@@ -333,6 +335,17 @@ class Reconstructor:
         value that is set when it is submitted."""
         self._check(self.L.vvr_set_output_colour(self.ctx, int(matrix), 1 if full_range else 0))
 
+    def set_output_normalisation(self, mean=None, std=None):
+        """the per-channel mean and standard deviation the "rgbf32" format of output_submit applies (vvr_set_output_normalisation): three floats
+        each for R, G, B, in units of full scale (0 .. 1) - out = v / (M * std) - mean / std in two float32 roundings (vvr.h); None: none.  A
+        request takes the value that is set when it is submitted; every other format ignores it."""
+        if mean is None and std is None:
+            self._check(self.L.vvr_set_output_normalisation(self.ctx, None, None))
+            return
+        m = None if mean is None else (C.c_float * 3)(*[float(v) for v in mean])
+        s = None if std is None else (C.c_float * 3)(*[float(v) for v in std])
+        self._check(self.L.vvr_set_output_normalisation(self.ctx, m, s))
+
     def set_output_transform(self, t):
         """the colour transform the "rgb8" / "rgb16" / "rgbf16" formats of output_submit run between the Y'CbCr matrix and the store
         (vvr_set_output_transform): None (none), an abi.OutputTransform (vvdec_amd.output_transform( ... ) makes the standard ones) or a tuple
@@ -379,6 +392,8 @@ class Reconstructor:
         ticket, or None when blocking=False and the job has not been handed to the device yet.  fmt: "planar16", "planar8", "packed10"
         (vvdecapp --pyuv: four samples in five bytes), "nv12" or "p010" (two planes: luma, interleaved CbCr; p010: sample << (16 - bit depth)),
         "rgb8", "rgb16" or "rgbf16" (three planes R, G, B at the luma size, converted on the device with the matrix of set_output_colour: vvr.h);
+        "rgbf32" (the three planes as float32 with set_output_normalisation applied), "rgba8", "bgra8", "rgb24", "bgr24", "rgb10a2" or "rgba16f"
+        (one plane of interleaved pixels: abi.output_plane_shapes);
         size, collocated, grain as read_output - and grain with size is the reference's chain,
         grain first, then the rescale of the grained frame.  pinned: the planes are allocated in memory of the context that the device writes
         directly (vvr_host_alloc) - they belong to the context and are views valid until close().
@@ -386,19 +401,32 @@ class Reconstructor:
         format: abi.output_plane_shapes): the device writes them, nothing crosses PCIe; they are registered with the context for the life of
         the request and output_wait returns them.  The tensors must be idle now and stay untouched until the request has completed
         (output_wait, output_test, or output_stream_wait on the stream that uses them).  At most 8 requests in flight (VvrError).
-        The RGB formats also take one 3-D tensor of shape (3, h, w) whose last dimension is contiguous (planes and rows may be padded or
-        sliced); output_wait returns that tensor.
+        The planar RGB formats also take one 3-D tensor of shape (3, h, w) whose last dimension is contiguous (planes and rows may be padded or
+        sliced) - float32 for "rgbf32"; the interleaved formats "rgba8", "bgra8", "rgb24", "bgr24" (uint8) and "rgba16f" (float16) one tensor of
+        shape (h, w, C) with stride(2) == 1 and stride(1) == C at any row stride, "rgb10a2" one (h, w) tensor of int32; output_wait returns
+        that tensor.
         Ask for a picture's output before the next picture into its slot is submitted: that picture then waits for the request on the device."""
         win = tuple(window or (0, 0, self.width, self.height))
         shapes, dt = abi.output_plane_shapes(win, fmt, size, 3 if self.chroma_format else 1)
         registered = []
         whole = None
         if into is not None:
-            if hasattr(into, "dim") and into.dim() == 3:      # (3, h, w): its planes, registered as one range
-                if len(shapes) != 3 or into.shape[0] != 3 or min(into.stride()) < 0:
-                    raise ValueError("output_submit: a 3-D tensor serves the RGB formats, as (3, h, w)")
+            inter = abi.OUT_INTERLEAVED.get(fmt) if isinstance(fmt, str) else None
+            if inter is not None and hasattr(into, "dim"):      # one tensor of pixels: (h, w, C), or (h, w) of 4-byte elements for rgb10a2
+                h, n = shapes[0]
+                ok = (tuple(into.shape) == (h, n) and into.element_size() == 4) if fmt == "rgb10a2" else \
+                     (into.dim() == 3 and tuple(into.shape) == (h, n // inter, inter) and into.stride(2) == 1 and into.stride(1) == inter)
+                if not ok or min(into.stride()) < 0:
+                    raise ValueError("output_submit: %s takes one tensor of shape %r" % (fmt, (h, n) if fmt == "rgb10a2" else (h, n // inter, inter)))
                 whole = into
-            planes = list(into)
+                planes = [into if into.dim() == 2 else into.as_strided((h, n), (into.stride(0), 1))]      # (the plane the request sees: rows of w * C elements)
+            elif hasattr(into, "dim") and into.dim() == 3:      # (3, h, w): its planes, registered as one range
+                if len(shapes) != 3 or into.shape[0] != 3 or min(into.stride()) < 0:
+                    raise ValueError("output_submit: a 3-D tensor serves the planar RGB formats, as (3, h, w)")
+                whole = into
+                planes = list(into)
+            else:
+                planes = list(into)
             if len(planes) != len(shapes):
                 raise ValueError("output_submit: %s needs %d planes" % (fmt, len(shapes)))
             for t, shape in zip(planes, shapes):

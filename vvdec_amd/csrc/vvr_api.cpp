@@ -174,6 +174,8 @@ struct vvr_context {
   std::unique_ptr<vvr_film_grain_bank> grainBank; void* grainBankDev = nullptr; bool grainBankStale = false; uint32_t grainSeed = 0xdeadbeefu;
   // colour description of the RGB formats of the output queue (vvr_set_output_colour): H.273 matrix_coefficients (0: none set) and the range flag
   int        outMatrix = 0, outFullRange = 0;
+  // ... and the normalisation of VVR_OUT_RGBF32 (vvr_set_output_normalisation): mean and standard deviation per channel as they were given
+  bool       outNorm = false; float outMean[3] = { 0, 0, 0 }, outStd[3] = { 1, 1, 1 };
   // ... and their colour transform (vvr_set_output_transform): the context's copy (NULL: none), its device copy - the struct as it is, k_output_rgb reads
   // lin and enc out of it - refreshed on the output stream ahead of the first RGB request after a change (xformStale), as the grain bank is
   std::unique_ptr<vvr_output_transform> xform; void* xformDev = nullptr; bool xformStale = false;

@@ -178,9 +178,9 @@ struct OutputFrameParams
   int format, shift;
 };
 void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst );
-// a frame of the output queue as planar R'G'B' (VVR_OUT_RGB8 / _RGB16 / _RGBF16, the definition: vvr.h): one 4:2:0 frame of w x h luma samples
+// a frame of the output queue as R'G'B' (planar VVR_OUT_RGB8 / _RGB16 / _RGBF16 / _RGBF32 or one interleaved plane, the definition: vvr.h): one 4:2:0 frame of w x h luma samples
 // (even; the chroma planes w / 2 x h / 2), chroma brought to the luma grid by the 4-tap DCTIF at the two phases `collocated` selects per direction
-// (taps clamped to the frame), then the Q14 matrix.  Three planes of w x h samples leave, rows back to back, into dst + dstOff[c] (256-byte
+// (taps clamped to the frame), then the Q14 matrix.  Three planes of w x h samples (or one of w x h pixels) leave, rows back to back, into dst + dstOff[c] (256-byte
 // aligned) or direct[c] (32-byte aligned memory of the caller's); nothing behind a plane's last sample is written in either.
 struct OutputRgbParams
 {
@@ -194,6 +194,11 @@ struct OutputRgbParams
   // vvr_output_transform (lin and enc are read from it; 8-byte aligned); xm: its matrix, as kernel arguments.  The matrix above runs at od = bd
   // then, whatever the format.
   const vvr_output_transform* xform; int xm[3][3];
+  // the interleaved formats (VVR_OUT_RGBA8 ... _RGBA16F: one plane of pixels, dstOff[0] / direct[0]) and VVR_OUT_RGBF32 (three planes).  format is
+  // the class the kernel is compiled for - VVR_OUT_RGBA8 also serves _BGRA8, VVR_OUT_RGB24 also _BGR24 - and swapRB exchanges R and B ahead of
+  // the store.  nscale, nbias: the normalisation of VVR_OUT_RGBF32 (vvr_set_output_normalisation, the definition: vvr.h), out = v * nscale[c] + nbias[c]
+  // in two roundings.  (Behind the fields above: the kernel arguments of the three planar formats stay where they were.)
+  int swapRB; float nscale[3], nbias[3];
 };
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.

@@ -5033,7 +5033,8 @@ void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst )
 
 // k_output_rgb — a 4:2:0 frame of the output queue as planar R'G'B' (the definition: vvr.h): chroma to the luma grid with the 4-tap DCTIF in
 // sampleRateConvCore's two passes (horizontal sums unnormalised, ( sum + 2048 ) >> 12 and the clip after the vertical pass), then the Q14 matrix,
-// the clip and the store as bytes, 16-bit words or halves - one launch, every source sample read from HBM once, nothing at 4:4:4 written but the result.
+// the clip and the store as bytes, 16-bit words, halves or floats in three planes, or as pixels of one interleaved plane (RGBA8 / BGRA8, RGB24 / BGR24,
+// RGB10A2, RGBA16F) - one launch, every source sample read from HBM once, nothing at 4:4:4 written but the result.
 // A workgroup owns 64 x 32 output samples.  It stages the tile's 32 x 16 chroma samples of both planes with their halo of two columns / rows on
 // every side (taps clamped to the frame) in LDS, then writes the horizontal sums of the 20 staged rows at the tile's 64 columns there as int32.
 // With 2:1 the positions are 16 * i - ( collocated ? 0 : 8 ) in 1/32 samples: a direction has two phases, 0 and 16 or 24 and 8, for even and odd
@@ -5090,6 +5091,89 @@ __device__ __forceinline__ void rgb_store( uint8_t* __restrict__ plane, size_t i
       if( n > 2 ) o[1] = d1;
       if( n > 4 ) o[2] = d2;
       if( n > 6 ) o[3] = d3;
+    }
+  }
+}
+// VVR_OUT_RGBF32: v * scale + bias in two roundings (vvr.h).  The product is kept in a register of its own, as rgb_half keeps it: hipcc
+// contracts a * b + c into v_fma_f32 by default, which rounds once
+__device__ __forceinline__ uint32_t rgb_f32( int v, float scale, float bias )
+{
+  float t = (float) v * scale;
+  asm volatile( "" : "+v"( t ) );
+  return __builtin_bit_cast( uint32_t, t + bias );
+}
+// ... and one plane of it: the lane's 8 floats, 32 bytes - two 16-byte stores, or the pairs that exist (8 bytes each: the width is even)
+template<bool WHOLE>
+__device__ __forceinline__ void rgb_store_f32( uint8_t* __restrict__ plane, size_t i0, const int ( &v )[8], float scale, float bias, int n )
+{
+  uint32_t d[8];
+#pragma unroll
+  for( int i = 0; i < 8; i++ ) d[i] = rgb_f32( v[i], scale, bias );
+  uint2* o = (uint2*) ( plane + i0 * 4 );
+  if( WHOLE ) { *(uint4*) o = make_uint4( d[0], d[1], d[2], d[3] ); *(uint4*) ( o + 2 ) = make_uint4( d[4], d[5], d[6], d[7] ); }
+  else
+  {
+    o[0] = make_uint2( d[0], d[1] );
+    if( n > 2 ) o[1] = make_uint2( d[2], d[3] );
+    if( n > 4 ) o[2] = make_uint2( d[4], d[5] );
+    if( n > 6 ) o[3] = make_uint2( d[6], d[7] );
+  }
+}
+// The interleaved formats: the lane's 8 pixels of the one plane, at pixel i0 of it (the base is aligned to 32 bytes: the entry's scratch, or a
+// destination the request path found aligned).  FMT is the class: VVR_OUT_RGBA8 (BGRA8: r and b arrive exchanged) and VVR_OUT_RGB10A2 - a dword
+// per pixel, 32 bytes per lane, two 16-byte stores or 8 bytes per pair; VVR_OUT_RGB24 (BGR24) - 24 bytes per lane at an 8-byte aligned address
+// when the width is a multiple of 8, one 8- and one 16-byte store, else pair by pair, 6 bytes as three 2-byte stores (rows are 2-byte aligned
+// then); VVR_OUT_RGBA16F - 8 bytes per pixel, 64 bytes per lane, four 16-byte stores or one per pair.
+template<int FMT, bool WHOLE>
+__device__ __forceinline__ void rgb_store_px( uint8_t* __restrict__ plane, size_t i0, const int ( &r )[8], const int ( &g )[8], const int ( &b )[8], float inv, int n )
+{
+  if( FMT == VVR_OUT_RGB24 )
+  {
+    uint32_t d[6];
+#pragma unroll
+    for( int k = 0; k < 2; k++ )      // (four pixels in three dwords)
+    {
+      const int i = 4 * k;
+      d[3 * k + 0] = (uint32_t) r[i] | (uint32_t) g[i] << 8 | (uint32_t) b[i] << 16 | (uint32_t) r[i + 1] << 24;
+      d[3 * k + 1] = (uint32_t) g[i + 1] | (uint32_t) b[i + 1] << 8 | (uint32_t) r[i + 2] << 16 | (uint32_t) g[i + 2] << 24;
+      d[3 * k + 2] = (uint32_t) b[i + 2] | (uint32_t) r[i + 3] << 8 | (uint32_t) g[i + 3] << 16 | (uint32_t) b[i + 3] << 24;
+    }
+    uint8_t* o = plane + i0 * 3;
+    if( WHOLE ) { *(uint2*) o = make_uint2( d[0], d[1] ); __builtin_memcpy( o + 8, &d[2], 16 ); }      // (the second at 8 bytes: unaligned access mode)
+    else
+    {
+#pragma unroll
+      for( int k = 0; k < 4; k++ )
+        if( 2 * k < n )
+        {
+          uint16_t* q = (uint16_t*) ( o + 6 * k );
+          q[0] = (uint16_t) ( r[2 * k] | g[2 * k] << 8 ); q[1] = (uint16_t) ( b[2 * k] | r[2 * k + 1] << 8 ); q[2] = (uint16_t) ( g[2 * k + 1] | b[2 * k + 1] << 8 );
+        }
+    }
+  }
+  else if( FMT == VVR_OUT_RGBA16F )
+  {
+    uint4* o = (uint4*) ( plane + i0 * 8 );
+#pragma unroll
+    for( int k = 0; k < 4; k++ )
+      if( WHOLE || 2 * k < n )
+        o[k] = make_uint4( rgb_half( r[2 * k], inv ) | rgb_half( g[2 * k], inv ) << 16, rgb_half( b[2 * k], inv ) | 0x3c000000u,
+                           rgb_half( r[2 * k + 1], inv ) | rgb_half( g[2 * k + 1], inv ) << 16, rgb_half( b[2 * k + 1], inv ) | 0x3c000000u );
+  }
+  else
+  {
+    uint32_t d[8];
+#pragma unroll
+    for( int i = 0; i < 8; i++ )
+      d[i] = FMT == VVR_OUT_RGB10A2 ? (uint32_t) r[i] | (uint32_t) g[i] << 10 | (uint32_t) b[i] << 20 | 3u << 30 : (uint32_t) r[i] | (uint32_t) g[i] << 8 | (uint32_t) b[i] << 16 | 255u << 24;
+    uint2* o = (uint2*) ( plane + i0 * 4 );
+    if( WHOLE ) { *(uint4*) o = make_uint4( d[0], d[1], d[2], d[3] ); *(uint4*) ( o + 2 ) = make_uint4( d[4], d[5], d[6], d[7] ); }
+    else
+    {
+      o[0] = make_uint2( d[0], d[1] );
+      if( n > 2 ) o[1] = make_uint2( d[2], d[3] );
+      if( n > 4 ) o[2] = make_uint2( d[4], d[5] );
+      if( n > 6 ) o[3] = make_uint2( d[6], d[7] );
     }
   }
 }
@@ -5212,12 +5296,30 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
         const int t = clip3( 0, 65535, (int) ( acc >> 14 ) );      // (| acc >> 14 | < 2^20)
         const uint32_t e2 = xf_enc[t >> 6], f = t & 63;
         const uint32_t ev = ( ( e2 & 0xffff ) * ( 64 - f ) + ( e2 >> 16 ) * f + 32 ) >> 6;
-        o[k] = (int) ( FMT == VVR_OUT_RGB8 ? ( ev + 128 ) / 257 : ev );
+        o[k] = (int) ( FMT == VVR_OUT_RGB8 || FMT == VVR_OUT_RGBA8 || FMT == VVR_OUT_RGB24 ? ( ev + 128 ) / 257 : FMT == VVR_OUT_RGB10A2 ? ( ev * 1023 + 32767 ) / 65535 : ev );
       }
       R[i] = o[0]; G[i] = o[1]; B[i] = o[2];
     }
   }
   const size_t i0 = (size_t) y * p.w + x;
+  if( FMT == VVR_OUT_RGBF32 )
+  {
+    rgb_store_f32<WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, p.nscale[0], p.nbias[0], n );
+    rgb_store_f32<WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, G, p.nscale[1], p.nbias[1], n );
+    rgb_store_f32<WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, B, p.nscale[2], p.nbias[2], n );
+    return;
+  }
+  if( FMT >= VVR_OUT_RGBA8 )
+  {
+    // BGRA8 / BGR24: the same code with the two arrays exchanged - uniform, not an instantiation of its own
+    if( ( FMT == VVR_OUT_RGBA8 || FMT == VVR_OUT_RGB24 ) && p.swapRB )
+    {
+#pragma unroll
+      for( int i = 0; i < 8; i++ ) { const int t = R[i]; R[i] = B[i]; B[i] = t; }
+    }
+    rgb_store_px<FMT, WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, G, B, p.inv, n );
+    return;
+  }
   rgb_store<FMT, WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, p.inv, n );
   rgb_store<FMT, WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, G, p.inv, n );
   rgb_store<FMT, WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, B, p.inv, n );
@@ -5243,9 +5345,18 @@ static void launch_output_rgb_fmt( hipStream_t s, const OutputRgbParams& p, void
 }
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst )
 {
-  if( p.format == VVR_OUT_RGB8 )       launch_output_rgb_fmt<VVR_OUT_RGB8>( s, p, dst );
-  else if( p.format == VVR_OUT_RGB16 ) launch_output_rgb_fmt<VVR_OUT_RGB16>( s, p, dst );
-  else                                 launch_output_rgb_fmt<VVR_OUT_RGBF16>( s, p, dst );
+  switch( p.format )
+  {
+  case VVR_OUT_RGB8:    launch_output_rgb_fmt<VVR_OUT_RGB8>( s, p, dst ); break;
+  case VVR_OUT_RGB16:   launch_output_rgb_fmt<VVR_OUT_RGB16>( s, p, dst ); break;
+  case VVR_OUT_RGBF16:  launch_output_rgb_fmt<VVR_OUT_RGBF16>( s, p, dst ); break;
+  case VVR_OUT_RGBF32:  launch_output_rgb_fmt<VVR_OUT_RGBF32>( s, p, dst ); break;
+  case VVR_OUT_RGBA8:   launch_output_rgb_fmt<VVR_OUT_RGBA8>( s, p, dst ); break;      // (and BGRA8: p.swapRB)
+  case VVR_OUT_RGB24:   launch_output_rgb_fmt<VVR_OUT_RGB24>( s, p, dst ); break;      // (and BGR24)
+  case VVR_OUT_RGB10A2: launch_output_rgb_fmt<VVR_OUT_RGB10A2>( s, p, dst ); break;
+  case VVR_OUT_RGBA16F: launch_output_rgb_fmt<VVR_OUT_RGBA16F>( s, p, dst ); break;
+  default: break;      // (the request path hands over one of the eight classes)
+  }
 }
 
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in

@@ -259,7 +259,7 @@ void launch_output_frame( hipStream_t, OutputFrameParams p, void* dst )
 }
 
 // ... and launch_output_rgb (k_output_rgb): the definition of vvr.h sample by sample - positions, phases and taps from the table as launch_rescale
-// takes them (step 16, add 0 / -8, shift 0, the chroma filter), the matrix, the three stores
+// takes them (step 16, add 0 / -8, shift 0, the chroma filter), the matrix, the transform, the stores of the planar and the interleaved formats
 namespace {
 uint16_t rgb_half_rne( float f )      // 0 or 1 / 65535 <= f <= 1: zero, a subnormal (below 2^-14: under a transform) or a normal half; round to nearest even (a carry out of the mantissa raises the exponent)
 {
@@ -315,7 +315,7 @@ void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
       const size_t at = (size_t) j * p.w + i;
       const int y = p.src[0][(size_t) j * p.stride[0] + i] - p.yoff, u = up[0][at] - p.coff, v = up[1][at] - p.coff;
       const int rgb[3] = { ( p.cy * y + p.rv * v + 8192 ) >> 14, ( p.cy * y + p.gu * u + p.gv * v + 8192 ) >> 14, ( p.cy * y + p.bu * u + 8192 ) >> 14 };
-      int L[3] = { 0, 0, 0 };
+      int L[3] = { 0, 0, 0 }, px[3] = { 0, 0, 0 };
       for( int c = 0; c < 3 && p.xform; c++ ) L[c] = p.xform->lin[std::min( std::max( 0, rgb[c] ), p.maxOut )];      // (stage 1)
       for( int c = 0; c < 3; c++ )
       {
@@ -328,9 +328,31 @@ void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
           val = ( p.xform->enc[i] * ( 64 - f ) + p.xform->enc[i + 1] * f + 32 ) >> 6;
           if( p.format == VVR_OUT_RGB8 ) val = ( val + 128 ) / 257;
         }
+        if( p.xform && ( p.format == VVR_OUT_RGBA8 || p.format == VVR_OUT_RGB24 ) ) val = ( val + 128 ) / 257;
+        if( p.xform && p.format == VVR_OUT_RGB10A2 ) val = ( val * 1023 + 32767 ) / 65535;      // (the 16 -> 10 bit reduction)
+        px[c] = val;
+        if( p.format >= VVR_OUT_RGBA8 ) continue;      // (one plane of pixels: below)
         uint8_t* out = p.direct[c] ? p.direct[c] : (uint8_t*) dst + p.dstOff[c];
         if( p.format == VVR_OUT_RGB8 ) out[at] = (uint8_t) val;
+        else if( p.format == VVR_OUT_RGBF32 )
+        {
+          // two roundings: the product is a float32 of its own (volatile: no contraction into an FMA whatever the compiler's mode)
+          volatile float t = (float) val * p.nscale[c];
+          ( (float*) out )[at] = t + p.nbias[c];
+        }
         else ( (uint16_t*) out )[at] = p.format == VVR_OUT_RGB16 ? (uint16_t) val : rgb_half_rne( (float) val * p.inv );
+      }
+      if( p.format < VVR_OUT_RGBA8 ) continue;
+      // the interleaved formats: a pixel of the one plane in memory order (vvr.h); BGRA8 / BGR24 arrive as their class with swapRB set
+      uint8_t* out = p.direct[0] ? p.direct[0] : (uint8_t*) dst + p.dstOff[0];
+      const int r = p.swapRB ? px[2] : px[0], g = px[1], b = p.swapRB ? px[0] : px[2];
+      if( p.format == VVR_OUT_RGBA8 )        { uint8_t* o = out + at * 4; o[0] = (uint8_t) r; o[1] = (uint8_t) g; o[2] = (uint8_t) b; o[3] = 255; }
+      else if( p.format == VVR_OUT_RGB24 )   { uint8_t* o = out + at * 3; o[0] = (uint8_t) r; o[1] = (uint8_t) g; o[2] = (uint8_t) b; }
+      else if( p.format == VVR_OUT_RGB10A2 ) { const uint32_t d = (uint32_t) r | (uint32_t) g << 10 | (uint32_t) b << 20 | 3u << 30; memcpy( out + at * 4, &d, 4 ); }
+      else      // VVR_OUT_RGBA16F
+      {
+        const uint16_t hq[4] = { rgb_half_rne( (float) r * p.inv ), rgb_half_rne( (float) g * p.inv ), rgb_half_rne( (float) b * p.inv ), 0x3c00 };
+        memcpy( out + at * 8, hq, 8 );
       }
     }
 }
@@ -464,6 +486,24 @@ VVR_API int vvr_set_output_colour( vvr_context* c, int matrixCoefficients, int f
   if( !rgb_matrix( matrixCoefficients, kr, kb ) ) { c->setError( "vvr_set_output_colour: matrix_coefficients must be 1 (BT.709), 5 or 6 (BT.601) or 9 (BT.2020 non-constant luminance)" ); return VVR_ERR_PARAMETER; }
   if( fullRange != 0 && fullRange != 1 ) { c->setError( "vvr_set_output_colour: full_range must be 0 or 1" ); return VVR_ERR_PARAMETER; }
   c->outMatrix = matrixCoefficients; c->outFullRange = fullRange;
+  return VVR_OK;
+}
+
+VVR_API int vvr_set_output_normalisation( vvr_context* c, const float mean[3], const float stdDev[3] )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  if( !mean && !stdDev ) { c->outNorm = false; return VVR_OK; }
+  if( !mean || !stdDev ) { c->setError( "vvr_set_output_normalisation: mean and std are given together, or both NULL" ); return VVR_ERR_PARAMETER; }
+  const float lim = 1048576.f;      // 2^20
+  for( int k = 0; k < 3; k++ )
+  {
+    if( !std::isfinite( mean[k] ) || !std::isfinite( stdDev[k] ) ) { c->setError( "vvr_set_output_normalisation: an entry is not finite" ); return VVR_ERR_PARAMETER; }
+    if( stdDev[k] < 1 / lim || stdDev[k] > lim ) { c->setError( "vvr_set_output_normalisation: std outside [ 2^-20, 2^20 ]" ); return VVR_ERR_PARAMETER; }
+    if( std::fabs( mean[k] ) > lim ) { c->setError( "vvr_set_output_normalisation: | mean | above 2^20" ); return VVR_ERR_PARAMETER; }
+  }
+  for( int k = 0; k < 3; k++ ) { c->outMean[k] = mean[k]; c->outStd[k] = stdDev[k]; }
+  c->outNorm = true;
   return VVR_OK;
 }
 
@@ -889,13 +929,17 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( rq->struct_size != sizeof( vvr_output_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_output_request )" );
   const int slot = rq->slot, bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot" );
-  const bool rgb = rq->format == VVR_OUT_RGB8 || rq->format == VVR_OUT_RGB16 || rq->format == VVR_OUT_RGBF16;
+  // the RGB formats: three planes (RGB8, RGB16, RGBF16, RGBF32) or one plane of pixels (`inter`); px: bytes of a sample of a plane, or of a pixel
+  const bool inter = rq->format >= VVR_OUT_RGBA8 && rq->format <= VVR_OUT_RGBA16F;
+  const bool rgb = rq->format == VVR_OUT_RGB8 || rq->format == VVR_OUT_RGB16 || rq->format == VVR_OUT_RGBF16 || rq->format == VVR_OUT_RGBF32 || inter;
+  const bool rgb8 = rq->format == VVR_OUT_RGB8 || rq->format == VVR_OUT_RGBA8 || rq->format == VVR_OUT_BGRA8 || rq->format == VVR_OUT_RGB24 || rq->format == VVR_OUT_BGR24;      // (the values VVR_OUT_RGB8 stores)
+  const int px = rq->format == VVR_OUT_RGB8 ? 1 : rq->format == VVR_OUT_RGB24 || rq->format == VVR_OUT_BGR24 ? 3 : rq->format == VVR_OUT_RGBA16F ? 8 : rq->format == VVR_OUT_RGB16 || rq->format == VVR_OUT_RGBF16 ? 2 : 4;
   if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 && !rgb ) return outRefuse( c, "unknown format" );
   if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1" );
   const bool packed = rq->format == VVR_OUT_PACKED10, semi = rq->format == VVR_OUT_NV12 || rq->format == VVR_OUT_P010, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
   const bool viaTmp = packed || semi || rgb;      // k_output_frame / k_output_rgb makes the format: the stages before it store 16-bit samples into `tmp`
   const bool narrow = rq->format == VVR_OUT_PLANAR8 || rq->format == VVR_OUT_NV12;
-  const int bps = narrow || rq->format == VVR_OUT_RGB8 ? 1 : 2, nOut = semi ? 2 : nc;
+  const int bps = narrow ? 1 : rgb ? px : 2, nOut = semi ? 2 : inter ? 1 : nc;
   int outMatrix = 0, outFullRange = 0;      // (the colour description: looked at here for the refusal, taken under mu where the request is accepted)
   if( rgb )
   {
@@ -956,6 +1000,14 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   // the colour transform the request takes: the one that is set now.  Its matrix goes with the request as kernel arguments; its tables, when
   // they have changed, are refreshed on the output stream ahead of the request's kernel - behind the kernels of the requests in flight
   const bool xf = rgb && c->xform, xfUpload = xf && c->xformStale;
+  // the normalisation a VVR_OUT_RGBF32 request takes: the one that is set now, as scale and bias computed in double and rounded once (vvr.h)
+  float nscale[3], nbias[3];
+  for( int k = 0; k < 3; k++ )
+  {
+    const double M = xf ? 65535. : (double) ( ( 1 << bd ) - 1 );
+    nscale[k] = c->outNorm ? (float) ( 1.0 / ( M * (double) c->outStd[k] ) ) : (float) ( 1.0 / M );
+    nbias[k] = c->outNorm ? (float) ( -(double) c->outMean[k] / (double) c->outStd[k] ) : 0.f;
+  }
   int xm[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
   if( xf ) memcpy( xm, c->xform->m, sizeof( xm ) );
   outTake( c, e, slot, rq->job, jobFailed ); e->nc = nOut;
@@ -1048,9 +1100,12 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   {
     // the frame as it stands - the slot's window, or the grained / rescaled planes in `tmp` - converted in one launch
     OutputRgbParams rp; memset( &rp, 0, sizeof( rp ) );
-    for( int k = 0; k < 3; k++ ) { rp.src[k] = cur[k].p; rp.stride[k] = cur[k].stride; rp.dstOff[k] = e->off[k]; rp.direct[k] = kdirect[k] ? (uint8_t*) rq->dst[k] : nullptr; }
-    rp.w = ow[0]; rp.h = oh[0]; rp.format = rq->format; rp.collocated = rq->collocated & 3;
-    rgb_coefficients( outMatrix, outFullRange, bd, rq->format == VVR_OUT_RGB8 && !xf ? 8 : bd, rp );
+    for( int k = 0; k < 3; k++ ) { rp.src[k] = cur[k].p; rp.stride[k] = cur[k].stride; rp.dstOff[k] = k < nOut ? e->off[k] : 0; rp.direct[k] = k < nOut && kdirect[k] ? (uint8_t*) rq->dst[k] : nullptr; }
+    rp.w = ow[0]; rp.h = oh[0]; rp.collocated = rq->collocated & 3;
+    rp.format = rq->format == VVR_OUT_BGRA8 ? VVR_OUT_RGBA8 : rq->format == VVR_OUT_BGR24 ? VVR_OUT_RGB24 : rq->format;      // (the class the kernel is compiled for)
+    rp.swapRB = rq->format == VVR_OUT_BGRA8 || rq->format == VVR_OUT_BGR24;
+    rgb_coefficients( outMatrix, outFullRange, bd, xf ? bd : rgb8 ? 8 : rq->format == VVR_OUT_RGB10A2 ? 10 : bd, rp );
+    for( int k = 0; k < 3; k++ ) { rp.nscale[k] = nscale[k]; rp.nbias[k] = nbias[k]; }
     if( xf )
     {
       if( !c->xformDev ) OQCHK( hipMalloc( &c->xformDev, sizeof( vvr_output_transform ) ) );
@@ -1062,7 +1117,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
       rp.xform = (const vvr_output_transform*) c->xformDev; memcpy( rp.xm, xm, sizeof( xm ) );
       rp.inv = 1.0f / 65535.0f;
     }
-    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + 3. * bps ) );
+    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + (double) nOut * px ) );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma; written: the planes, or the pixel)
     launch_output_rgb( s, rp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
   }
