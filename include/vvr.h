@@ -561,7 +561,7 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *            ( Ek + 128 ) / 257 with one included.  The refusals are those of the three planar formats, a missing plane or a stride below the
  *            row among the planes the format uses.
  *            Not offered: interleaved float32; 4:0:0 as grey; RGB from the synchronous vvr_read_output* calls; constant-luminance BT.2020,
- *            ICtCp, YCgCo, the identity matrix; 3-D LUTs and luminance-based tone mapping.
+ *            ICtCp, YCgCo, the identity matrix; dynamic metadata; a 3-D LUT for the synchronous calls.
  *   grain with out_w / out_h: the window is grained at its own size exactly as vvr_read_output_grain does it, the grained frame is then
  *            rescaled exactly as vvr_read_output_scaled rescales a picture, taps clamped to the grained frame (the reference's order:
  *            xAddGrain in xAddPicture, then the application's upscaleFrame).
@@ -612,7 +612,7 @@ VVR_API int          vvr_set_output_colour(vvr_context* ctx, int matrix_coeffici
  * colour description (copied; NULL, NULL: none; a new context has none): a VVR_OUT_RGBF32 request takes the value that is set when
  * vvr_output_submit accepts it, it travels as kernel arguments, a later call never changes a request in flight.  Every other format -
  * VVR_OUT_RGBF16 and VVR_OUT_RGBA16F too - ignores it.  Defined to the bit:
- *   v        the value VVR_OUT_RGB16 stores for the channel, 0 .. M: M = 2^bd - 1 without a transform, 65535 with one.
+ *   v        the value VVR_OUT_RGB16 stores for the channel, 0 .. M: M = 2^bd - 1 without a transform or a 3-D LUT, 65535 with either.
  *   scale[c] = (float)( 1.0 / ( (double) M * (double) std[c] ) ), bias[c] = (float)( -(double) mean[c] / (double) std[c] ): computed on the host in
  *            double, rounded once.  None set: scale[c] = (float)( 1.0 / M ), bias[c] = +0.
  *   t = float32( v ) * scale[c], one correctly rounded float32 multiply; out = t + bias[c], one correctly rounded float32 add; never an FMA.
@@ -676,6 +676,46 @@ VVR_API int          vvr_set_output_transform(vvr_context* ctx, const vvr_output
 enum { VVR_XFORM_TO_SRGB = 0, VVR_XFORM_TO_BT709 = 1, VVR_XFORM_TO_LINEAR = 2 };
 VVR_API int          vvr_output_transform_preset(vvr_output_transform* out, int transfer_characteristics, int colour_primaries, int target,
                                                  double src_peak_nits, double dst_peak_nits, int bit_depth);
+/* 3-D LUT of the RGB formats, tetrahedral interpolation: what a per-channel transform cannot express - a tone curve on luminance that keeps hue
+ * and saturation (the BT.2390 EETF on Y, the HLG OOTF with its system gamma), or any grade a colour tool exports as a .cube file.  Context state
+ * like the transform (copied inside the call; NULL with n = 0: none; a new context has none).  It runs inside the RGB request's one kernel, last
+ * before the store, behind the transform if one is set.  Defined to the bit:
+ *   nodes    n = 17, 33 or 65 per axis; n^3 x 3 values in .cube order, R fastest: node ( jr, jg, jb ) at 3 * ( ( jb * n + jg ) * n + jr ), as R, G, B.
+ *   which requests   a request of any RGB format (planar or interleaved) takes the LUT that is set when vvr_output_submit accepts it: the nodes
+ *            are refreshed on the output stream ahead of the request's kernel, the size travels as a kernel argument, so a later
+ *            vvr_set_output_lut3d never changes a request in flight.  Every other format ignores the LUT, and so does every synchronous call.
+ *            The refresh travels through the ring entry's pinned staging, as the transform's tables do: the first RGB request behind a changed
+ *            LUT may grow its entry's staging by the nodes (8 n^3 bytes: 39 KB, 287 KB, 2.2 MB) inside vvr_output_submit, once per entry -
+ *            what a request with a larger output than the entry has seen does too.  A caller that changes a 65-point LUT per frame pays that
+ *            once for each of the 8 entries, and the upload of 2.2 MB each time.
+ *   input    with a transform: the three Ek of stage 3, each 0 .. 65535.  Without one: the Y'CbCr matrix runs at od = bd - also for VVR_OUT_RGB8 and
+ *            VVR_OUT_RGB10A2, as it does under a transform - and each value v is widened to ( v * 65535 + ( M >> 1 ) ) / M, M = 2^bd - 1, in
+ *            integer division: the correctly rounded widening.
+ *   cell     s = 16 - log2( n - 1 ) (12, 11, 10), S = 2^s; per channel i = v >> s (0 .. n - 2), f = v & ( S - 1 ).  Node j belongs to the value
+ *            j * S (node n - 1 to 65536, which is never reached: it only closes the last cell - the convention of enc[1024]).
+ *   interpolation    order the three fractions f1 >= f2 >= f3.  c0 = node ( ir, ig, ib ); c1 = c0 stepped by one along the axis of f1; c2 = c1
+ *            stepped along the axis of f2; c3 = node ( ir + 1, ig + 1, ib + 1 ).  Per output channel k:
+ *            Ok = ( c0[k] * ( S - f1 ) + c1[k] * ( f1 - f2 ) + c2[k] * ( f2 - f3 ) + c3[k] * f3 + ( S >> 1 ) ) >> s.  The weights sum to S: the sum
+ *            stays below 2^28.  Equal fractions need no rule: the vertex that differs has weight 0.
+ *   store    exactly the stores under a transform with Ek := Ok: RGB8 / RGBA8 / RGB24 (and the BGR orders) ( Ok + 128 ) / 257, RGB10A2
+ *            ( Ok * 1023 + 32767 ) / 65535, RGB16 full-scale 16 bits, the halves and float32 with M = 65535.
+ * Refused (VVR_ERR_PARAMETER with a text, the LUT set before stays in force): an n other than 17, 33, 65; nodes == NULL with n != 0.  A LUT may be
+ * set in any context. */
+enum { VVR_LUT3D_MAX = 65 };
+VVR_API int          vvr_set_output_lut3d(vvr_context* ctx, int n, const uint16_t* nodes);
+/* The nodes for HDR video to BT.709 primaries with the tone curve on luminance; a pure host function, no context, everything in double.  Meant
+ * for use WITHOUT a transform: the LUT's input is the coded R'G'B'.  Code points, targets and the PQ peaks: those of vvr_output_transform_preset,
+ * whose q16, EOTF, I, EETF, OETFs and gamut matrix M these are; n = 17, 33 or 65.  Per node E'c = min( jc * S, 65535 ) / 65535, c in R, G, B.
+ *   PQ:   Lc = EOTF( E'c ); Y = sum of w_c * Lc, w the middle row of the source gamut's normalised primary matrix; if Y > 0:
+ *         Lc *= EOTF( EETF( I( Y ) ) ) / Y - the BT.2390 curve on luminance, hue and saturation kept; Lc /= dst_peak_nits.
+ *   HLG:  Ec = inverse OETF( E'c ); Ys = sum of w_c * Ec; Fc = Ys^( gamma - 1 ) * Ec (0 at Ys = 0), gamma = 1.2 + 0.42 log10( Lw / 1000 ) for
+ *         400 <= Lw <= 2000, else 1.2 * 1.111^log2( Lw / 1000 ) (BT.2100-2 note 5f, BT.2390-10 section 6.2), Lw = dst_peak_nits;
+ *         src_peak_nits is ignored.  One difference from vvr_output_transform_preset, which ignores both peaks for HLG: here dst_peak_nits
+ *         is the display's peak and must lie in ( 0, 10000 ] - the system gamma has no value at Lw <= 0.
+ *   both: T = M * L (or F), clipped to [ 0, 1 ]; node[k] = q16( OETF( Tk ) ).
+ * Anything else: VVR_ERR_PARAMETER, nodes untouched. */
+VVR_API int          vvr_output_lut3d_preset(uint16_t* nodes, int n, int transfer_characteristics, int colour_primaries, int target,
+                                             double src_peak_nits, double dst_peak_nits);
 VVR_API int          vvr_output_submit(vvr_context* ctx, const vvr_output_request* req);
 VVR_API int          vvr_output_test(vvr_context* ctx, int ticket);
 VVR_API int          vvr_output_wait(vvr_context* ctx, int ticket);

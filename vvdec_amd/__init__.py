@@ -82,6 +82,10 @@ def lib():
         L.vvr_set_output_transform.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_output_transform_preset.restype = C.c_int
         L.vvr_output_transform_preset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
+        L.vvr_set_output_lut3d.restype = C.c_int
+        L.vvr_set_output_lut3d.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.vvr_output_lut3d_preset.restype = C.c_int
+        L.vvr_output_lut3d_preset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
         L.vvr_read_output_grain.restype = C.c_int
         L.vvr_read_output_grain.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.vvr_read_dmvr.restype = C.c_int
@@ -124,7 +128,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_set_output_lut3d", "vvr_output_lut3d_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
@@ -142,6 +146,68 @@ def output_transform(transfer, primaries, target, src_peak=1000., dst_peak=100.,
     if rc != abi.VVR_OK:
         raise VvrError("vvr_output_transform_preset: transfer 16 or 18, primaries 1 or 9, a target of abi.XFORM_TARGETS, peaks in (0, 10000], bit depth 8 .. 10 (rc %d)" % rc)
     return t
+
+
+def output_lut3d(n, transfer, primaries, target, src_peak=1000., dst_peak=100.):
+    """vvr_output_lut3d_preset: the 3-D LUT that brings HDR video to BT.709 primaries with the tone curve on luminance (the BT.2390 EETF on Y for
+    PQ, the HLG OOTF with the system gamma of a dst_peak display) -> (n, uint16 nodes of n^3 x 3 values in .cube order) for
+    Reconstructor.set_output_lut3d, used without a transform.  n: 17, 33 or 65; the other arguments as output_transform's.  A pure host function."""
+    import numpy as np
+    nodes = np.zeros(3 * int(n) ** 3 if n in abi.LUT3D_SIZES else 3, np.uint16)
+    rc = lib().vvr_output_lut3d_preset(nodes.ctypes.data, int(n), int(transfer), int(primaries), abi.XFORM_TARGETS.get(target, target), float(src_peak), float(dst_peak))
+    if rc != abi.VVR_OK:
+        raise VvrError("vvr_output_lut3d_preset: n 17, 33 or 65, transfer 16 or 18, primaries 1 or 9, a target of abi.XFORM_TARGETS, peaks in (0, 10000] (rc %d)" % rc)
+    return int(n), nodes
+
+
+def _cube_tokens(path):
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0].strip()
+            if line:
+                yield line.split()
+
+
+def read_cube(path):
+    """a .cube 3-D LUT file -> (n, uint16 nodes) for Reconstructor.set_output_lut3d: LUT_3D_SIZE 17, 33 or 65 with the default domain (0 .. 1;
+    a DOMAIN_MIN / DOMAIN_MAX line must say just that), n^3 rows of R G B with R changing fastest; TITLE and comments are skipped.  Values are
+    clipped to [0, 1] and quantised as q16( v ) = floor( v * 65535 + 0.5 ).  Nodes are taken as they are: the file's node j belongs to the input
+    j / ( n - 1 ), ours to j * S / 65535 with S = 65536 / ( n - 1 ) - the two grids differ by j / ( ( n - 1 ) * 65535 ), a domain error below
+    2^-16 of the range, which is not resampled away."""
+    import numpy as np
+    n, rows = None, []
+    for tok in _cube_tokens(path):
+        key = tok[0].upper()
+        if key == "LUT_3D_SIZE":
+            n = int(tok[1])
+        elif key in ("DOMAIN_MIN", "DOMAIN_MAX"):
+            if [float(v) for v in tok[1:4]] != [0. if key == "DOMAIN_MIN" else 1.] * 3:
+                raise ValueError("read_cube: %s: only the default domain 0 .. 1 is supported" % path)
+        elif key == "LUT_1D_SIZE" or key.startswith("LUT_1D") or key.startswith("LUT_3D_INPUT_RANGE"):
+            raise ValueError("read_cube: %s: %s is not supported" % (path, tok[0]))
+        elif key == "TITLE":
+            continue
+        else:
+            rows.append([float(v) for v in tok[:3]])
+            if len(tok) != 3:
+                raise ValueError("read_cube: %s: a row of %d values" % (path, len(tok)))
+    if n not in abi.LUT3D_SIZES:
+        raise ValueError("read_cube: %s: LUT_3D_SIZE %r, not 17, 33 or 65" % (path, n))
+    if len(rows) != n ** 3:
+        raise ValueError("read_cube: %s: %d rows for a %d-point LUT" % (path, len(rows), n))
+    v = np.clip(np.array(rows, np.float64), 0, 1)
+    return n, np.floor(v * 65535 + 0.5).astype(np.uint16).reshape(-1)
+
+
+def write_cube(path, n, nodes, title=None):
+    """(n, uint16 nodes) -> a .cube file with the default domain: node values as v / 65535 with 10 decimals, which read_cube brings back exactly"""
+    a = abi.lut3d_nodes(n, nodes).reshape(-1, 3)
+    with open(path, "w") as f:
+        if title:
+            f.write('TITLE "%s"\n' % title)
+        f.write("LUT_3D_SIZE %d\n" % n)
+        for r, g, b in a.tolist():
+            f.write("%.10f %.10f %.10f\n" % (r / 65535, g / 65535, b / 65535))
 
 
 class Reconstructor:
@@ -357,6 +423,17 @@ class Reconstructor:
         if not isinstance(t, abi.OutputTransform):
             t = abi.output_transform(*t)
         self._check(self.L.vvr_set_output_transform(self.ctx, C.addressof(t)))
+
+    def set_output_lut3d(self, lut):
+        """the 3-D LUT the RGB formats of output_submit run last before the store, behind the transform if one is set (vvr_set_output_lut3d): None
+        (none) or (n, nodes) - n 17, 33 or 65, nodes n^3 x 3 uint16 values in .cube order, as vvdec_amd.output_lut3d( ... ) and
+        vvdec_amd.read_cube( path ) give them.  Under a LUT "rgb16" is full-scale 16 bits.  A request takes the LUT that is set when it is submitted."""
+        if lut is None:
+            self._check(self.L.vvr_set_output_lut3d(self.ctx, 0, None))
+            return
+        n, nodes = lut
+        a = abi.lut3d_nodes(n, nodes)
+        self._check(self.L.vvr_set_output_lut3d(self.ctx, int(n), a.ctypes.data))      # (copied inside the call)
 
     def read_output(self, slot, window=None, bytes_per_sample=2, size=None, collocated=(True, False), grain=False):
         """the picture as the application gets it: conformance window (x, y, w, h in luma samples, even) applied, 8- or 16-bit samples.

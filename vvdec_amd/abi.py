@@ -239,6 +239,18 @@ def output_transform_arrays(t):
     return np.array(t.lin, np.uint16), np.array([list(r) for r in t.m], np.int32), np.array(t.enc, np.uint16)
 
 
+LUT3D_SIZES = (17, 33, 65)
+
+
+def lut3d_nodes(n, nodes):
+    """the nodes of a 3-D LUT as vvr_set_output_lut3d takes them: a contiguous uint16 array of n^3 x 3 values in .cube order (R fastest);
+    `nodes` may have any shape with that many elements, (n, n, n, 3) indexed [jb, jg, jr] included"""
+    import numpy as np
+    a = np.ascontiguousarray(nodes, dtype=np.uint16).reshape(-1)
+    assert a.size == 3 * int(n) ** 3, "a %d-point LUT has %d values, not %d" % (n, 3 * int(n) ** 3, a.size)
+    return a
+
+
 HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2
 HASH_LEN = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
 

@@ -179,6 +179,10 @@ struct vvr_context {
   // ... and their colour transform (vvr_set_output_transform): the context's copy (NULL: none), its device copy - the struct as it is, k_output_rgb reads
   // lin and enc out of it - refreshed on the output stream ahead of the first RGB request after a change (xformStale), as the grain bank is
   std::unique_ptr<vvr_output_transform> xform; void* xformDev = nullptr; bool xformStale = false;
+  // ... and their 3-D LUT (vvr_set_output_lut3d): the context's copy as the device takes it - four 16-bit words per node, R, G, B, 0 - with its
+  // size (lutN == 0: none), its device copy - one buffer for VVR_LUT3D_MAX, allocated on first use and kept until vvr_destroy: a hipFree in the
+  // request path would drain the device - refreshed like the transform's tables (lutStale)
+  std::vector<uint16_t> lut; int lutN = 0; void* lutDev = nullptr; bool lutStale = false;
   // ---- job pipeline (everything below is guarded by mu)
   std::mutex mu, commitMu;              // commitMu: one committing thread at a time (it takes mu only around its bookkeeping)
   std::condition_variable cv;
@@ -1165,6 +1169,7 @@ VVR_API void vvr_destroy( vvr_context* c )
   if( c->outDev ) hipFree( c->outDev );
   if( c->grainBankDev ) hipFree( c->grainBankDev );
   if( c->xformDev ) hipFree( c->xformDev );
+  if( c->lutDev ) hipFree( c->lutDev );
   if( c->outHost ) hipHostFree( c->outHost );
   for( void* p : c->stagePool ) hipHostFree( p );
   if( c->prepStage ) hipHostFree( c->prepStage );

@@ -199,6 +199,11 @@ struct OutputRgbParams
   // the store.  nscale, nbias: the normalisation of VVR_OUT_RGBF32 (vvr_set_output_normalisation, the definition: vvr.h), out = v * nscale[c] + nbias[c]
   // in two roundings.  (Behind the fields above: the kernel arguments of the three planar formats stay where they were.)
   int swapRB; float nscale[3], nbias[3];
+  // the 3-D LUT (vvr_set_output_lut3d, the definition: vvr.h), last before the store; lut == NULL: none.  lut: the device copy, one 8-byte node
+  // R, G, B, 0 (16-bit words) at ( jb * lutN + jg ) * lutN + jr; lutN: 17, 33 or 65; lutShift: s = 16 - log2( lutN - 1 ).  Its input is Ek under a
+  // transform, else the value of the matrix above at od = bd widened to 16 bits: ( v * 65535 + ( M >> 1 ) ) / M, M = 2^bd - 1 = maxOut - which
+  // the kernel takes as ( x * lutWiden ) >> 39 with lutWiden = 2^39 / M + 1 (exact for x < 2^26: the error x / 2^39 stays below 1 / M)
+  const uint16_t* lut; int lutN, lutShift; uint32_t lutWiden;
 };
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.

@@ -5182,7 +5182,14 @@ __device__ __forceinline__ void rgb_store_px( uint8_t* __restrict__ plane, size_
 // enc as 1024 pairs enc[i] | enc[i + 1] << 16 (4 KB), so that stage 3 is one 4-byte LDS read per value instead of two 2-byte ones; a sample costs three
 // reads of lin and three of the pairs.  Stage 2 is nine 64-bit multiply-adds (v_mad_i64_i32) per sample: | m | <= 2^16 times a 16-bit value, three
 // of them summed, needs 35 bits.  The instantiations without XF are the code they were (no table in LDS, no branch).
-template<int COL, int FMT, bool WHOLE, bool XF>
+// XF == 2: the 3-D LUT of vvr_set_output_lut3d (the definition: vvr.h) last before the store; whether the transform runs ahead of it is a uniform
+// branch on p.xform inside these instantiations (the tables' place in LDS is theirs either way), so the LUT adds half the instantiations, not as
+// many again.  The LUT stays in global memory (39 KB / 287 KB / 2.2 MB: L2).  A pixel reads the four vertices of its tetrahedron, 8 bytes each:
+// c0 = the cell's corner, c3 = the opposite corner, c1 = c0 stepped along the axis of the largest fraction, c2 = c3 stepped back along the axis of
+// the smallest (with equal fractions the choice among the tied axes moves weight 0).  The lane's 8 pixels go in two batches of four: the 16
+// loads of a batch are issued back to back (32 VGPRs of results in flight), then the twelve multiply-adds per pixel; one batch of eight would
+// hold 64 VGPRs, and load-wait-load four dependent round trips to L2 per pixel.
+template<int COL, int FMT, bool WHOLE, int XF>
 __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_t* __restrict__ dst )
 {
   __shared__ uint16_t rgb_raw[2][RGB_CH][RGB_CW];
@@ -5220,7 +5227,8 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
   // the tables: lane t brings lin[4 t .. 4 t + 3] and the pairs 2 j, 2 j + 1 for j = t, t + 256 (dwords j and j + 1 of enc; dword 512 is
   // enc[1024] and the struct's padding).  lin lies 8 bytes, enc 2092 bytes into the struct
   uint2 xli = make_uint2( 0, 0 ); uint32_t xe[2][2] = { { 0, 0 }, { 0, 0 } };
-  if( XF )
+  const bool xf = XF == 1 || ( XF == 2 && p.xform );
+  if( xf )
   {
     const uint8_t* __restrict__ t = (const uint8_t*) p.xform;
     xli = *(const uint2*) ( t + offsetof( vvr_output_transform, lin ) + 8 * tid );
@@ -5230,7 +5238,7 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
   }
 #pragma unroll
   for( int i = 0; i < PER_LANE; i++ ) if( tid + 256 * i < STAGED ) ( &rgb_raw[0][0][0] )[tid + 256 * i] = staged[i];
-  if( XF )
+  if( xf )
   {
     *(uint2*) &xf_lin[4 * tid] = xli;
 #pragma unroll
@@ -5282,7 +5290,7 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
     G[i] = clip3( 0, p.maxOut, ( l + p.gu * u + p.gv * v ) >> 14 );
     B[i] = clip3( 0, p.maxOut, ( l + p.bu * u ) >> 14 );
   }
-  if( XF )
+  if( xf )
   {
 #pragma unroll
     for( int i = 0; i < 8; i++ )
@@ -5296,9 +5304,56 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
         const int t = clip3( 0, 65535, (int) ( acc >> 14 ) );      // (| acc >> 14 | < 2^20)
         const uint32_t e2 = xf_enc[t >> 6], f = t & 63;
         const uint32_t ev = ( ( e2 & 0xffff ) * ( 64 - f ) + ( e2 >> 16 ) * f + 32 ) >> 6;
-        o[k] = (int) ( FMT == VVR_OUT_RGB8 || FMT == VVR_OUT_RGBA8 || FMT == VVR_OUT_RGB24 ? ( ev + 128 ) / 257 : FMT == VVR_OUT_RGB10A2 ? ( ev * 1023 + 32767 ) / 65535 : ev );
+        o[k] = (int) ( XF == 2 ? ev : FMT == VVR_OUT_RGB8 || FMT == VVR_OUT_RGBA8 || FMT == VVR_OUT_RGB24 ? ( ev + 128 ) / 257 : FMT == VVR_OUT_RGB10A2 ? ( ev * 1023 + 32767 ) / 65535 : ev );
       }
       R[i] = o[0]; G[i] = o[1]; B[i] = o[2];
+    }
+  }
+  else if( XF == 2 )
+  {
+#pragma unroll
+    for( int i = 0; i < 8; i++ )      // (no transform: the correctly rounded widening of 0 .. maxOut to 16 bits)
+    {
+      R[i] = (int) ( __umulhi( (uint32_t) R[i] * 65535u + ( (uint32_t) p.maxOut >> 1 ), p.lutWiden ) >> 7 );
+      G[i] = (int) ( __umulhi( (uint32_t) G[i] * 65535u + ( (uint32_t) p.maxOut >> 1 ), p.lutWiden ) >> 7 );
+      B[i] = (int) ( __umulhi( (uint32_t) B[i] * 65535u + ( (uint32_t) p.maxOut >> 1 ), p.lutWiden ) >> 7 );
+    }
+  }
+  if( XF == 2 )
+  {
+    const uint2* __restrict__ lut = (const uint2*) p.lut;
+    const int s = p.lutShift, S = 1 << s, ln = p.lutN, ln2 = ln * ln, far = 1 + ln + ln2;
+#pragma unroll
+    for( int h4 = 0; h4 < 2; h4++ )
+    {
+      uint2 c[4][4]; int w[4][4];
+#pragma unroll
+      for( int j = 0; j < 4; j++ )
+      {
+        const int i = 4 * h4 + j;
+        const int fr = R[i] & ( S - 1 ), fg = G[i] & ( S - 1 ), fb = B[i] & ( S - 1 );
+        const int at = ( ( B[i] >> s ) * ln + ( G[i] >> s ) ) * ln + ( R[i] >> s );      // (values are 0 .. 65535: indices 0 .. lutN - 2, at + far inside the table)
+        const bool rg = fr >= fg, gb = fg >= fb, rb = fr >= fb;
+        const int s1 = rg && rb ? 1 : ( !rg && gb ? ln : ln2 ), s3 = gb && rb ? ln2 : ( rg && !gb ? ln : 1 );      // (never the same axis, ties included)
+        const int f1 = max( fr, max( fg, fb ) ), f3 = min( fr, min( fg, fb ) ), f2 = fr + fg + fb - f1 - f3;
+        c[j][0] = lut[at]; c[j][1] = lut[at + s1]; c[j][2] = lut[at + far - s3]; c[j][3] = lut[at + far];
+        w[j][0] = S - f1; w[j][1] = f1 - f2; w[j][2] = f2 - f3; w[j][3] = f3;
+      }
+#pragma unroll
+      for( int j = 0; j < 4; j++ )
+      {
+        const int i = 4 * h4 + j;
+        uint32_t o[3] = { (uint32_t) S >> 1, (uint32_t) S >> 1, (uint32_t) S >> 1 };      // (the weights sum to S <= 2^12: the sums stay below 2^28)
+#pragma unroll
+        for( int v = 0; v < 4; v++ ) { o[0] += ( c[j][v].x & 0xffff ) * w[j][v]; o[1] += ( c[j][v].x >> 16 ) * w[j][v]; o[2] += ( c[j][v].y & 0xffff ) * w[j][v]; }
+#pragma unroll
+        for( int k = 0; k < 3; k++ )
+        {
+          const uint32_t ev = o[k] >> s;
+          o[k] = FMT == VVR_OUT_RGB8 || FMT == VVR_OUT_RGBA8 || FMT == VVR_OUT_RGB24 ? ( ev + 128 ) / 257 : FMT == VVR_OUT_RGB10A2 ? ( ev * 1023 + 32767 ) / 65535 : ev;
+        }
+        R[i] = (int) o[0]; G[i] = (int) o[1]; B[i] = (int) o[2];
+      }
     }
   }
   const size_t i0 = (size_t) y * p.w + x;
@@ -5324,7 +5379,7 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
   rgb_store<FMT, WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, G, p.inv, n );
   rgb_store<FMT, WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, B, p.inv, n );
 }
-template<int FMT, bool WHOLE, bool XF>
+template<int FMT, bool WHOLE, int XF>
 static void launch_output_rgb_as( hipStream_t s, const OutputRgbParams& p, void* dst )
 {
   const dim3 grid( ( p.w + RGB_TW - 1 ) / RGB_TW, ( p.h + RGB_TH - 1 ) / RGB_TH );
@@ -5340,8 +5395,9 @@ template<int FMT>
 static void launch_output_rgb_fmt( hipStream_t s, const OutputRgbParams& p, void* dst )
 {
   const bool whole = ( p.w & 7 ) == 0;      // (rows of a multiple of 8 samples: every lane has 8, at an aligned address)
-  if( p.xform ) { if( whole ) launch_output_rgb_as<FMT, true, true>( s, p, dst );  else launch_output_rgb_as<FMT, false, true>( s, p, dst ); }
-  else          { if( whole ) launch_output_rgb_as<FMT, true, false>( s, p, dst ); else launch_output_rgb_as<FMT, false, false>( s, p, dst ); }
+  if( p.lut )        { if( whole ) launch_output_rgb_as<FMT, true, 2>( s, p, dst ); else launch_output_rgb_as<FMT, false, 2>( s, p, dst ); }
+  else if( p.xform ) { if( whole ) launch_output_rgb_as<FMT, true, 1>( s, p, dst ); else launch_output_rgb_as<FMT, false, 1>( s, p, dst ); }
+  else               { if( whole ) launch_output_rgb_as<FMT, true, 0>( s, p, dst ); else launch_output_rgb_as<FMT, false, 0>( s, p, dst ); }
 }
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst )
 {

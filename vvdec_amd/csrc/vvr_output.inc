@@ -315,21 +315,38 @@ void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
       const size_t at = (size_t) j * p.w + i;
       const int y = p.src[0][(size_t) j * p.stride[0] + i] - p.yoff, u = up[0][at] - p.coff, v = up[1][at] - p.coff;
       const int rgb[3] = { ( p.cy * y + p.rv * v + 8192 ) >> 14, ( p.cy * y + p.gu * u + p.gv * v + 8192 ) >> 14, ( p.cy * y + p.bu * u + 8192 ) >> 14 };
-      int L[3] = { 0, 0, 0 }, px[3] = { 0, 0, 0 };
+      int L[3] = { 0, 0, 0 }, px[3] = { 0, 0, 0 }, E[3];
       for( int c = 0; c < 3 && p.xform; c++ ) L[c] = p.xform->lin[std::min( std::max( 0, rgb[c] ), p.maxOut )];      // (stage 1)
       for( int c = 0; c < 3; c++ )
       {
-        int val = std::min( std::max( 0, rgb[c] ), p.maxOut );
+        E[c] = std::min( std::max( 0, rgb[c] ), p.maxOut );
         if( p.xform )
         {
-          // stages 2 and 3, the 16 -> 8 bit reduction of RGB8 (vvr.h)
+          // stages 2 and 3 (vvr.h)
           const int64_t acc = (int64_t) p.xm[c][0] * L[0] + (int64_t) p.xm[c][1] * L[1] + (int64_t) p.xm[c][2] * L[2] + 8192;
           const int t = (int) std::min<int64_t>( std::max<int64_t>( 0, acc >> 14 ), 65535 ), i = t >> 6, f = t & 63;
-          val = ( p.xform->enc[i] * ( 64 - f ) + p.xform->enc[i + 1] * f + 32 ) >> 6;
-          if( p.format == VVR_OUT_RGB8 ) val = ( val + 128 ) / 257;
+          E[c] = ( p.xform->enc[i] * ( 64 - f ) + p.xform->enc[i + 1] * f + 32 ) >> 6;
         }
-        if( p.xform && ( p.format == VVR_OUT_RGBA8 || p.format == VVR_OUT_RGB24 ) ) val = ( val + 128 ) / 257;
-        if( p.xform && p.format == VVR_OUT_RGB10A2 ) val = ( val * 1023 + 32767 ) / 65535;      // (the 16 -> 10 bit reduction)
+        else if( p.lut ) E[c] = ( E[c] * 65535 + ( p.maxOut >> 1 ) ) / p.maxOut;      // (the widening to the LUT's 16 bits)
+      }
+      if( p.lut )
+      {
+        // the 3-D LUT: the cell, the fractions in descending order, the four vertices of the tetrahedron (vvr.h)
+        const int s = p.lutShift, S = 1 << s, n = p.lutN, step[3] = { 1, n, n * n };
+        int idx[3], order[3] = { 0, 1, 2 }, f[3];
+        for( int c = 0; c < 3; c++ ) { idx[c] = E[c] >> s; f[c] = E[c] & ( S - 1 ); }
+        std::stable_sort( order, order + 3, [&]( int a, int b ) { return f[a] > f[b]; } );
+        const int c0 = ( idx[2] * n + idx[1] ) * n + idx[0], c1 = c0 + step[order[0]], c2 = c1 + step[order[1]], c3 = c2 + step[order[2]];
+        const int f1 = f[order[0]], f2 = f[order[1]], f3 = f[order[2]];
+        for( int c = 0; c < 3; c++ )
+          E[c] = ( p.lut[4 * c0 + c] * ( S - f1 ) + p.lut[4 * c1 + c] * ( f1 - f2 ) + p.lut[4 * c2 + c] * ( f2 - f3 ) + p.lut[4 * c3 + c] * f3 + ( S >> 1 ) ) >> s;
+      }
+      for( int c = 0; c < 3; c++ )
+      {
+        int val = E[c];
+        // the 16 -> 8 and 16 -> 10 bit reductions under a transform or a LUT (vvr.h)
+        if( ( p.xform || p.lut ) && ( p.format == VVR_OUT_RGB8 || p.format == VVR_OUT_RGBA8 || p.format == VVR_OUT_RGB24 ) ) val = ( val + 128 ) / 257;
+        if( ( p.xform || p.lut ) && p.format == VVR_OUT_RGB10A2 ) val = ( val * 1023 + 32767 ) / 65535;
         px[c] = val;
         if( p.format >= VVR_OUT_RGBA8 ) continue;      // (one plane of pixels: below)
         uint8_t* out = p.direct[c] ? p.direct[c] : (uint8_t*) dst + p.dstOff[c];
@@ -522,18 +539,33 @@ VVR_API int vvr_set_output_transform( vvr_context* c, const vvr_output_transform
   return VVR_OK;
 }
 
-// the tables of the standard cases, every formula as vvr.h gives it, in double
-VVR_API int vvr_output_transform_preset( vvr_output_transform* out, int transfer, int primaries, int target, double srcPeak, double dstPeak, int bitDepth )
+VVR_API int vvr_set_output_lut3d( vvr_context* c, int n, const uint16_t* nodes )
 {
-  if( !out || ( transfer != 16 && transfer != 18 ) || ( primaries != 1 && primaries != 9 ) || target < VVR_XFORM_TO_SRGB || target > VVR_XFORM_TO_LINEAR || bitDepth < 8 || bitDepth > 10 ) return VVR_ERR_PARAMETER;
-  if( transfer == 16 && !( srcPeak > 0 && srcPeak <= 10000 && dstPeak > 0 && dstPeak <= 10000 ) ) return VVR_ERR_PARAMETER;
-  auto q16 = []( double v ) { return (uint16_t) std::floor( v * 65535 + 0.5 ); };
-  // stage 1: PQ EOTF behind the BT.2390 EETF, or the inverse HLG OETF
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  if( !nodes && n == 0 ) { c->lutN = 0; c->lut.clear(); return VVR_OK; }
+  if( !nodes ) { c->setError( "vvr_set_output_lut3d: nodes is NULL with a size other than 0" ); return VVR_ERR_PARAMETER; }
+  if( n != 17 && n != 33 && n != 65 ) { c->setError( "vvr_set_output_lut3d: the size is 17, 33 or 65 nodes per axis" ); return VVR_ERR_PARAMETER; }
+  // the copy as the device takes it: a node is R, G, B, 0 - one 8-byte load per vertex
+  const size_t count = (size_t) n * n * n;
+  c->lut.assign( count * 4, 0 );
+  for( size_t j = 0; j < count; j++ ) for( int k = 0; k < 3; k++ ) c->lut[4 * j + k] = nodes[3 * j + k];
+  c->lutN = n; c->lutStale = true;
+  return VVR_OK;
+}
+
+// the colour science of the presets, every formula as vvr.h gives it, in double
+namespace {
+struct PresetMath
+{
   const double m1 = 2610. / 16384, m2 = 2523. / 4096 * 128, c1 = 3424. / 4096, c2 = 2413. / 4096 * 32, c3 = 2392. / 4096 * 32;
-  auto pqEotf = [&]( double e ) { const double p = std::pow( e, 1 / m2 ); return 10000 * std::pow( std::max( p - c1, 0. ) / ( c2 - c3 * p ), 1 / m1 ); };
-  auto pqInv = [&]( double nits ) { const double y = std::pow( nits / 10000, m1 ); return std::pow( ( c1 + c2 * y ) / ( 1 + c3 * y ), m2 ); };
-  const double lo = pqInv( 0 ), hi = pqInv( srcPeak ), maxLum = ( pqInv( dstPeak ) - lo ) / ( hi - lo ), ks = 1.5 * maxLum - 0.5;
-  auto eetf = [&]( double e )
+  const double ha = 0.17883277, hb = 1 - 4 * ha, hc = 0.5 - ha * std::log( 4 * ha );
+  double lo = 0, hi = 1, maxLum = 1, ks = 1;
+  PresetMath( double srcPeak, double dstPeak ) { lo = pqInv( 0 ); hi = pqInv( srcPeak ); maxLum = ( pqInv( dstPeak ) - lo ) / ( hi - lo ); ks = 1.5 * maxLum - 0.5; }
+  static uint16_t q16( double v ) { return (uint16_t) std::floor( v * 65535 + 0.5 ); }
+  double pqEotf( double e ) const { const double p = std::pow( e, 1 / m2 ); return 10000 * std::pow( std::max( p - c1, 0. ) / ( c2 - c3 * p ), 1 / m1 ); }
+  double pqInv( double nits ) const { const double y = std::pow( nits / 10000, m1 ); return std::pow( ( c1 + c2 * y ) / ( 1 + c3 * y ), m2 ); }
+  double eetf( double e ) const
   {
     const double e1 = std::min( std::max( ( e - lo ) / ( hi - lo ), 0. ), 1. );
     double e2 = e1;
@@ -543,19 +575,17 @@ VVR_API int vvr_output_transform_preset( vvr_output_transform* out, int transfer
       e2 = ( 2 * t3 - 3 * t2 + 1 ) * ks + ( t3 - 2 * t2 + t ) * ( 1 - ks ) + ( -2 * t3 + 3 * t2 ) * maxLum;
     }
     return e2 * ( hi - lo ) + lo;
-  };
-  const double ha = 0.17883277, hb = 1 - 4 * ha, hc = 0.5 - ha * std::log( 4 * ha );
-  vvr_output_transform t; memset( &t, 0, sizeof( t ) );
-  t.struct_size = sizeof( t );
-  const int top = ( 1 << bitDepth ) - 1;
-  for( int v = 0; v <= top; v++ )
-  {
-    const double e = (double) v / top;
-    t.lin[v] = q16( transfer == 16 ? std::min( pqEotf( eetf( e ) ) / dstPeak, 1. ) : ( e <= 0.5 ? e * e / 3 : ( std::exp( ( e - hc ) / ha ) + hb ) / 12 ) );
   }
-  // stage 2: inverse( N709 ) * Nsrc, the normalised primary matrices from the chromaticities
-  auto npm = []( const double xy[3][2], double n[3][3] )
+  double hlgInv( double e ) const { return e <= 0.5 ? e * e / 3 : ( std::exp( ( e - hc ) / ha ) + hb ) / 12; }
+  static double oetf( int target, double x )
   {
+    return target == VVR_XFORM_TO_SRGB ? ( x <= 0.0031308 ? 12.92 * x : 1.055 * std::pow( x, 1 / 2.4 ) - 0.055 ) : target == VVR_XFORM_TO_BT709 ? ( x < 0.018 ? 4.5 * x : 1.099 * std::pow( x, 0.45 ) - 0.099 ) : x;
+  }
+  // the normalised primary matrix RGB -> XYZ of a gamut from its chromaticities (SMPTE RP 177), D65
+  static void npm( int primaries, double n[3][3] )
+  {
+    const double xy709[3][2] = { { 0.640, 0.330 }, { 0.300, 0.600 }, { 0.150, 0.060 } }, xy2020[3][2] = { { 0.708, 0.292 }, { 0.170, 0.797 }, { 0.131, 0.046 } };
+    const double ( *xy )[2] = primaries == 1 ? xy709 : xy2020;
     const double wx = 0.3127, wy = 0.3290, w[3] = { wx / wy, 1, ( 1 - wx - wy ) / wy };
     double p[3][3], inv[3][3];
     for( int j = 0; j < 3; j++ ) { p[0][j] = xy[j][0] / xy[j][1]; p[1][j] = 1; p[2][j] = ( 1 - xy[j][0] - xy[j][1] ) / xy[j][1]; }
@@ -563,25 +593,79 @@ VVR_API int vvr_output_transform_preset( vvr_output_transform* out, int transfer
     for( int i = 0; i < 3; i++ ) for( int j = 0; j < 3; j++ )
       inv[j][i] = ( p[( i + 1 ) % 3][( j + 1 ) % 3] * p[( i + 2 ) % 3][( j + 2 ) % 3] - p[( i + 1 ) % 3][( j + 2 ) % 3] * p[( i + 2 ) % 3][( j + 1 ) % 3] ) / det;
     for( int j = 0; j < 3; j++ ) { const double sc = inv[j][0] * w[0] + inv[j][1] * w[1] + inv[j][2] * w[2]; for( int i = 0; i < 3; i++ ) n[i][j] = p[i][j] * sc; }
-  };
-  if( primaries == 1 ) for( int k = 0; k < 3; k++ ) t.m[k][k] = 16384;
-  else
+  }
+  // M = inverse( N709 ) * Nsrc; source primaries 1: the identity
+  static void gamut( int primaries, double M[3][3] )
   {
-    const double xy709[3][2] = { { 0.640, 0.330 }, { 0.300, 0.600 }, { 0.150, 0.060 } }, xy2020[3][2] = { { 0.708, 0.292 }, { 0.170, 0.797 }, { 0.131, 0.046 } };
+    for( int k = 0; k < 3; k++ ) for( int j = 0; j < 3; j++ ) M[k][j] = k == j;
+    if( primaries == 1 ) return;
     double a[3][3], b[3][3], ai[3][3];
-    npm( xy709, a ); npm( xy2020, b );
+    npm( 1, a ); npm( primaries, b );
     const double det = a[0][0] * ( a[1][1] * a[2][2] - a[1][2] * a[2][1] ) - a[0][1] * ( a[1][0] * a[2][2] - a[1][2] * a[2][0] ) + a[0][2] * ( a[1][0] * a[2][1] - a[1][1] * a[2][0] );
     for( int i = 0; i < 3; i++ ) for( int j = 0; j < 3; j++ )
       ai[j][i] = ( a[( i + 1 ) % 3][( j + 1 ) % 3] * a[( i + 2 ) % 3][( j + 2 ) % 3] - a[( i + 1 ) % 3][( j + 2 ) % 3] * a[( i + 2 ) % 3][( j + 1 ) % 3] ) / det;
-    for( int k = 0; k < 3; k++ ) for( int j = 0; j < 3; j++ ) t.m[k][j] = (int32_t) std::floor( ( ai[k][0] * b[0][j] + ai[k][1] * b[1][j] + ai[k][2] * b[2][j] ) * 16384 + 0.5 );
+    for( int k = 0; k < 3; k++ ) for( int j = 0; j < 3; j++ ) M[k][j] = ai[k][0] * b[0][j] + ai[k][1] * b[1][j] + ai[k][2] * b[2][j];
   }
-  // stage 3: the target's OETF
-  for( int i = 0; i <= 1024; i++ )
+};
+bool presetKnown( int transfer, int primaries, int target, double srcPeak, double dstPeak )
+{
+  if( ( transfer != 16 && transfer != 18 ) || ( primaries != 1 && primaries != 9 ) || target < VVR_XFORM_TO_SRGB || target > VVR_XFORM_TO_LINEAR ) return false;
+  return transfer != 16 || ( srcPeak > 0 && srcPeak <= 10000 && dstPeak > 0 && dstPeak <= 10000 );
+}
+}   // namespace
+
+VVR_API int vvr_output_transform_preset( vvr_output_transform* out, int transfer, int primaries, int target, double srcPeak, double dstPeak, int bitDepth )
+{
+  if( !out || !presetKnown( transfer, primaries, target, srcPeak, dstPeak ) || bitDepth < 8 || bitDepth > 10 ) return VVR_ERR_PARAMETER;
+  const PresetMath pm( srcPeak, dstPeak );
+  vvr_output_transform t; memset( &t, 0, sizeof( t ) );
+  t.struct_size = sizeof( t );
+  // stage 1: PQ EOTF behind the BT.2390 EETF, or the inverse HLG OETF
+  const int top = ( 1 << bitDepth ) - 1;
+  for( int v = 0; v <= top; v++ )
   {
-    const double x = std::min( 64 * i, 65535 ) / 65535.;
-    t.enc[i] = q16( target == VVR_XFORM_TO_SRGB ? ( x <= 0.0031308 ? 12.92 * x : 1.055 * std::pow( x, 1 / 2.4 ) - 0.055 ) : target == VVR_XFORM_TO_BT709 ? ( x < 0.018 ? 4.5 * x : 1.099 * std::pow( x, 0.45 ) - 0.099 ) : x );
+    const double e = (double) v / top;
+    t.lin[v] = pm.q16( transfer == 16 ? std::min( pm.pqEotf( pm.eetf( e ) ) / dstPeak, 1. ) : pm.hlgInv( e ) );
   }
+  // stage 2: inverse( N709 ) * Nsrc, the normalised primary matrices from the chromaticities
+  double M[3][3];
+  pm.gamut( primaries, M );
+  for( int k = 0; k < 3; k++ ) for( int j = 0; j < 3; j++ ) t.m[k][j] = (int32_t) std::floor( M[k][j] * 16384 + 0.5 );
+  // stage 3: the target's OETF
+  for( int i = 0; i <= 1024; i++ ) t.enc[i] = pm.q16( pm.oetf( target, std::min( 64 * i, 65535 ) / 65535. ) );
   *out = t;
+  return VVR_OK;
+}
+
+// the 3-D LUT of the same cases with the tone curve on luminance: BT.2390's EETF on Y (PQ), the HLG OOTF with its system gamma (vvr.h)
+VVR_API int vvr_output_lut3d_preset( uint16_t* nodes, int n, int transfer, int primaries, int target, double srcPeak, double dstPeak )
+{
+  if( !nodes || ( n != 17 && n != 33 && n != 65 ) || !presetKnown( transfer, primaries, target, srcPeak, dstPeak ) ) return VVR_ERR_PARAMETER;
+  if( transfer == 18 && !( dstPeak > 0 && dstPeak <= 10000 ) ) return VVR_ERR_PARAMETER;      // (Lw of the system gamma)
+  const PresetMath pm( srcPeak, dstPeak );
+  double M[3][3], N[3][3];
+  pm.gamut( primaries, M ); pm.npm( primaries, N );
+  const double* w = N[1];      // (luminance of the source's R, G, B)
+  const double gamma = dstPeak >= 400 && dstPeak <= 2000 ? 1.2 + 0.42 * std::log10( dstPeak / 1000 ) : 1.2 * std::pow( 1.111, std::log2( dstPeak / 1000 ) );
+  const int S = 65536 / ( n - 1 );
+  std::vector<double> lin( n );      // per node of an axis: display light in cd/m2 (PQ) or scene light 0 .. 1 (HLG)
+  for( int j = 0; j < n; j++ ) { const double e = std::min( j * S, 65535 ) / 65535.; lin[j] = transfer == 16 ? pm.pqEotf( e ) : pm.hlgInv( e ); }
+  for( int jb = 0; jb < n; jb++ )
+    for( int jg = 0; jg < n; jg++ )
+      for( int jr = 0; jr < n; jr++ )
+      {
+        double L[3] = { lin[jr], lin[jg], lin[jb] };
+        const double Y = w[0] * L[0] + w[1] * L[1] + w[2] * L[2];
+        double scale;
+        if( transfer == 16 ) scale = ( Y > 0 ? pm.pqEotf( pm.eetf( pm.pqInv( Y ) ) ) / Y : 1. ) / dstPeak;
+        else scale = Y > 0 ? std::pow( Y, gamma - 1 ) : 0.;
+        uint16_t* o = nodes + 3 * ( ( (size_t) jb * n + jg ) * n + jr );
+        for( int k = 0; k < 3; k++ )
+        {
+          const double t = M[k][0] * ( L[0] * scale ) + M[k][1] * ( L[1] * scale ) + M[k][2] * ( L[2] * scale );
+          o[k] = pm.q16( pm.oetf( target, std::min( std::max( t, 0. ), 1. ) ) );
+        }
+      }
   return VVR_OK;
 }
 
@@ -1000,11 +1084,15 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   // the colour transform the request takes: the one that is set now.  Its matrix goes with the request as kernel arguments; its tables, when
   // they have changed, are refreshed on the output stream ahead of the request's kernel - behind the kernels of the requests in flight
   const bool xf = rgb && c->xform, xfUpload = xf && c->xformStale;
+  // ... and the 3-D LUT, by the same rule: its size goes with the request, its nodes are refreshed on the output stream when they have changed
+  const int lutN = rgb ? c->lutN : 0;
+  const bool lutUpload = lutN && c->lutStale;
+  const size_t lutBytes = (size_t) lutN * lutN * lutN * 8;
   // the normalisation a VVR_OUT_RGBF32 request takes: the one that is set now, as scale and bias computed in double and rounded once (vvr.h)
   float nscale[3], nbias[3];
   for( int k = 0; k < 3; k++ )
   {
-    const double M = xf ? 65535. : (double) ( ( 1 << bd ) - 1 );
+    const double M = xf || lutN ? 65535. : (double) ( ( 1 << bd ) - 1 );
     nscale[k] = c->outNorm ? (float) ( 1.0 / ( M * (double) c->outStd[k] ) ) : (float) ( 1.0 / M );
     nbias[k] = c->outNorm ? (float) ( -(double) c->outMean[k] / (double) c->outStd[k] ) : 0.f;
   }
@@ -1034,7 +1122,10 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   tmpBytes += alignUp( wordsBytes, 256 );
   const size_t hostBankOff = hostWordsOff + alignUp( wordsBytes, 256 );      // (a bank that changed travels through the entry's pinned memory: the context's copy may change while the upload is in flight)
   const size_t hostXformOff = hostBankOff + ( grain && c->grainBankStale ? alignUp( sizeof( vvr_film_grain_bank ), 256 ) : 0 );      // (... and so do the tables of a transform that changed)
-  if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostXformOff + ( xfUpload ? sizeof( vvr_output_transform ) : 0 ), true ) != VVR_OK )
+  // (... and the nodes of a LUT that changed: up to 2.2 MB more of the entry's pinned staging, grown below once per entry like the staging of a
+  // larger output - the device copy is never reallocated, the staging is only ever enlarged)
+  const size_t hostLutOff = hostXformOff + ( xfUpload ? alignUp( sizeof( vvr_output_transform ), 256 ) : 0 );
+  if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostLutOff + ( lutUpload ? lutBytes : 0 ), true ) != VVR_OK )
   { c->setError( "vvr_output_submit: out of device or pinned memory" ); return VVR_ERR_DEVICE; }
   e->direct = direct; e->devDst = devDst;
   // ---- 3. behind the picture (or the slot's users) on the device, 4. the kernels.  mu stays held up to the registration of the `read` event: a
@@ -1104,7 +1195,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     rp.w = ow[0]; rp.h = oh[0]; rp.collocated = rq->collocated & 3;
     rp.format = rq->format == VVR_OUT_BGRA8 ? VVR_OUT_RGBA8 : rq->format == VVR_OUT_BGR24 ? VVR_OUT_RGB24 : rq->format;      // (the class the kernel is compiled for)
     rp.swapRB = rq->format == VVR_OUT_BGRA8 || rq->format == VVR_OUT_BGR24;
-    rgb_coefficients( outMatrix, outFullRange, bd, xf ? bd : rgb8 ? 8 : rq->format == VVR_OUT_RGB10A2 ? 10 : bd, rp );
+    rgb_coefficients( outMatrix, outFullRange, bd, xf || lutN ? bd : rgb8 ? 8 : rq->format == VVR_OUT_RGB10A2 ? 10 : bd, rp );
     for( int k = 0; k < 3; k++ ) { rp.nscale[k] = nscale[k]; rp.nbias[k] = nbias[k]; }
     if( xf )
     {
@@ -1117,6 +1208,18 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
       rp.xform = (const vvr_output_transform*) c->xformDev; memcpy( rp.xm, xm, sizeof( xm ) );
       rp.inv = 1.0f / 65535.0f;
     }
+    if( lutN )
+    {
+      if( !c->lutDev ) OQCHK( hipMalloc( &c->lutDev, (size_t) VVR_LUT3D_MAX * VVR_LUT3D_MAX * VVR_LUT3D_MAX * 8 ) );
+      if( lutUpload )
+      {
+        memcpy( e->host + hostLutOff, c->lut.data(), lutBytes );
+        OQCHK( hipMemcpyAsync( c->lutDev, e->host + hostLutOff, lutBytes, hipMemcpyHostToDevice, s ) );
+      }
+      rp.lut = (const uint16_t*) c->lutDev; rp.lutN = lutN; rp.lutShift = lutN == 17 ? 12 : lutN == 33 ? 11 : 10;
+      rp.lutWiden = (uint32_t) ( ( 1ull << 39 ) / (unsigned) ( ( 1 << bd ) - 1 ) + 1 );
+      rp.inv = 1.0f / 65535.0f;
+    }
     outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + (double) nOut * px ) );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma; written: the planes, or the pixel)
     launch_output_rgb( s, rp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
@@ -1127,6 +1230,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   e->state = OQ_FLIGHT; e->queued = true;
   if( grain ) { c->grainBankStale = false; c->grainSeed = nextSeed; }      // (the chain advances at submit, for an accepted request only)
   if( xfUpload ) c->xformStale = false;
+  if( lutUpload ) c->lutStale = false;
   const int ticket = e->ticket;
   lk.unlock();
   // ---- the result's way to the host: exactly the output's bytes
