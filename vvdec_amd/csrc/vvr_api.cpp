@@ -430,12 +430,12 @@ static int enqueuePicture( vvr_context* c, Job& job, const CommitPlan& plan, std
   // ---- The front half of the picture, IN FRONT OF the waits for its references and slot hazards: k_prep and k_lf_init work from the picture's own uploaded
   // records alone, so they run while the picture still waits - behind an IRAP every level of the B pyramid is alone on the device, and its 0.06 ms of
   // tables were on the chain.  Checked in the kernels:
-  //   * written: q->lfCell, lfCellC, lfMv, lfRef, lfpDev[0..1] (prep_lf_maps, k_lf_init), q->mcDev, bdofItems, dmvrItems (prep_expand_mc) - room behind the
+  //   * written: q->lfCell, lfCellC, lfMv, lfRef, lfpDev[0..1] (prep_lf_maps, k_lf_init), q->mcDev, bdofItems, dmvrItems (prep_expand_mc), q->tbRecs[0..2] (prep_tb_records) - room behind the
   //     uploaded image in the ring entry's or the handle's blob - and c->leafMaps[lane] with its ticket (prep_intra_mark).  The lane's maps are only touched by
   //     kernels of this lane (k_intra_leaf leaves them zero), which the stream orders.  A ring entry gets its next picture when its owner has completed.
   //   * a vvr_prepare handle can be submitted again while an earlier job of it is in flight: the tables are that job's too.  plan.frontWaits holds the `done`
   //     events of such jobs on other lanes (planCommitLocked) - the front half is ordered behind them, whatever the bytes it would write.
-  //   * read: pic.hdr, pic.cu, pic.tu, the host's lists (mcCus, lfSb, the intra and residual items), the CTU maps of slices / tiles / subpictures and the cell
+  //   * read: pic.hdr, pic.cu, pic.tu, the host's lists (mcCus, lfSb, the intra and residual items, the transform-block items), the slice headers, the CTU maps of slices / tiles / subpictures and the cell
   //     records written just before - all inside the picture's own image.  No plane, no DPB slot, no collocated motion, no delta MV of another picture
   //     (the filter sees the motion of the CU records, not the refined one).
   for( hipEvent_t ev : plan.frontWaits ) HIPCHK( c, hipStreamWaitEvent( s, ev, 0 ) );
@@ -444,6 +444,7 @@ static int enqueuePicture( vvr_context* c, Job& job, const CommitPlan& plan, std
     if( q->numMcCus ) { w.mcCus = q->mcCus; w.numMcCus = q->numMcCus; w.plain = q->mcDev; w.bdof = q->bdofItems; w.dmvr = q->dmvrItems; }
     if( q->lfpOnDevice && dbOn ) { w.lfMaps = true; w.numCu = q->numCu; w.numTu = q->numTu; w.cell = q->lfCell; w.cellC = q->lfCellC; w.mv = q->lfMv; w.ref = q->lfRef; w.sb = q->lfSb; w.numSb = q->numLfSb; }
     if( q->intraLeaf && q->numIntra ) { w.items = q->intraItems; w.numItems = q->numIntra; w.resi = q->resiItems; w.numResi = q->numResi; w.maps = c->leafMaps[lane]; w.mapInts = c->leafMapInts; w.mapW4 = c->leafW4; w.mapH4 = c->leafH4; }
+    for( int k = 0; k < 3; k++ ) { w.tbItems[k] = q->tbItems[k]; w.tbRecs[k] = q->tbRecs[k]; w.numTb[k] = q->numTb[k]; }
     launch_prep( s, q->pic, w );
   }
   // LF_INIT (DecLibRecon.cpp:807-829): the edge parameters of the deblocking passes from the CU / TU records, where the caller leaves them to the back-end

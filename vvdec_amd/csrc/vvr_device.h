@@ -54,6 +54,77 @@ enum { TB_ADD = 0, TB_STORE = 1 };
 enum { TB_P_CUGEOM = 1 /* chroma block of an ISP CU: position and size are the CU's */, TB_P_BDPCM = 2 /* BDPCM: every level of the block is coded */,
        TB_P_LFNST = 4 /* the CU applies LFNST to this component: cu.lfnst_idx > 0 && ( cu.tree != VVR_TREE_JOINT || comp == 0 ) */ };
 
+// Everything k_itrans needs to know of a transform block, in one 16-byte record per TbItem (same index, an array of its own per size class): what the kernel used to
+// chase item -> TU record -> CU record -> slice map at the head of every block.  A pure function of the picture's own records (tb_record below), written on the
+// device by prep_tb_records (a section of k_prep, the picture's first launch, in front of the waits for the reference pictures) into room behind the uploaded image.
+struct TbRec {
+  uint32_t coef;       // offset of the block's level corner in the coefficient stream
+  uint16_t x, y;       // position in samples of the component (chroma of an ISP CU: the CU's)
+  uint32_t a;          // log2 width (3 bits) | log2 height << 3 | comp << 6 | mode << 8 | ict << 9 (as TbItem) | mts_idx << 12 | tr_type << 15 (4 bits) | BDPCM direction << 19 (2)
+                       // | slice: dependent quantisation << 21 | slice: scaling lists on << 22 | scaling-list type << 23 (3) | TB_P_LFNST << 26
+                       // | LFNST set << 27 (2) | LFNST index - 1 << 29 | LFNST output transposed << 30
+  uint32_t b;          // max_scan_x (8 bits) | max_scan_y << 8 | QP << 16 (8 bits, signed)
+};
+__host__ __device__ inline int tbr_lw( const TbRec& r )        { return (int) ( r.a & 7 ); }
+__host__ __device__ inline int tbr_lh( const TbRec& r )        { return (int) ( ( r.a >> 3 ) & 7 ); }
+__host__ __device__ inline int tbr_comp( const TbRec& r )      { return (int) ( ( r.a >> 6 ) & 3 ); }
+__host__ __device__ inline int tbr_mode( const TbRec& r )      { return (int) ( ( r.a >> 8 ) & 1 ); }
+__host__ __device__ inline int tbr_ict( const TbRec& r )       { return (int) ( ( r.a >> 9 ) & 7 ); }
+__host__ __device__ inline int tbr_mts( const TbRec& r )       { return (int) ( ( r.a >> 12 ) & 7 ); }
+__host__ __device__ inline int tbr_tr_type( const TbRec& r )   { return (int) ( ( r.a >> 15 ) & 15 ); }
+__host__ __device__ inline int tbr_bdpcm( const TbRec& r )     { return (int) ( ( r.a >> 19 ) & 3 ); }
+__host__ __device__ inline bool tbr_dep_quant( const TbRec& r ) { return ( r.a >> 21 ) & 1; }
+__host__ __device__ inline bool tbr_sl_on( const TbRec& r )    { return ( r.a >> 22 ) & 1; }
+__host__ __device__ inline int tbr_list_type( const TbRec& r ) { return (int) ( ( r.a >> 23 ) & 7 ); }
+__host__ __device__ inline bool tbr_lfnst( const TbRec& r )    { return ( r.a >> 26 ) & 1; }
+__host__ __device__ inline int tbr_lfnst_set( const TbRec& r ) { return (int) ( ( r.a >> 27 ) & 3 ); }
+__host__ __device__ inline int tbr_lfnst_idx( const TbRec& r ) { return (int) ( ( r.a >> 29 ) & 1 ); }
+__host__ __device__ inline bool tbr_lfnst_transposed( const TbRec& r ) { return ( r.a >> 30 ) & 1; }
+__host__ __device__ inline int tbr_scan_x( const TbRec& r )    { return (int) ( r.b & 0xff ); }
+__host__ __device__ inline int tbr_scan_y( const TbRec& r )    { return (int) ( ( r.b >> 8 ) & 0xff ); }
+__host__ __device__ inline int tbr_qp( const TbRec& r )        { return (int) (int8_t) ( ( r.b >> 16 ) & 0xff ); }
+
+__host__ __device__ inline int tbr_ilog2( int v ) { int l = 0; while( v > 1 ) { v >>= 1; l++; } return l; }
+// the record of item `it`; sliceFlags: the tool switches that hold in the slice of the TU's top-left luma sample (the picture's where it has no slice headers)
+__host__ __device__ inline TbRec tb_record( const TbItem& it, const vvr_tu& tu, const vvr_cu& cu, uint32_t sliceFlags )
+{
+  const int comp = it.comp, csh = comp ? 1 : 0;
+  int bw = tu.w >> csh, bh = tu.h >> csh, bx = tu.x >> csh, by = tu.y >> csh;
+  if( it.pad & TB_P_CUGEOM ) { bw = cu.w >> 1; bh = cu.h >> 1; bx = cu.x >> 1; by = cu.y >> 1; }      // (chroma of an ISP CU)
+  const int bdpcm = ( it.pad & TB_P_BDPCM ) ? ( comp ? cu.bdpcm[1] : cu.bdpcm[0] ) : 0;
+  const int listType = ( cu.pred_mode == VVR_PRED_INTRA ? 0 : 3 ) + comp;          // (getScalingListType: intra / inter x component)
+  uint32_t lf = 0;
+  if( it.pad & TB_P_LFNST )
+  {
+    // the LFNST set and whether its output is transposed, from the intra mode (TrQuant.cpp:201-237): planar for MIP, the luma mode for a chroma block
+    // predicted from luma, wide angles mapped by the block's shape (PU::getWideAngIntraMode, UnitTools.cpp:617 - the CU's shape for the partitions of an ISP CU)
+    int mode;
+    if( ( cu.flags & VVR_CU_MIP ) && comp == 0 ) mode = 0;
+    else if( comp && cu.intra_dir[1] >= 67 ) mode = cu.lfnst_intra_mode;
+    else mode = cu.intra_dir[comp ? 1 : 0];
+    const int w = ( cu.isp_mode && !comp ) ? cu.w : bw, h = ( cu.isp_mode && !comp ) ? cu.h : bh;
+    if( mode >= 2 )
+    {
+      const int dl = tbr_ilog2( w ) - tbr_ilog2( h ), d = dl < 0 ? -dl : dl;
+      const int modeShift = d == 0 ? 0 : d == 1 ? 6 : d == 2 ? 10 : d == 3 ? 12 : d == 4 ? 14 : 15;
+      if( w > h && mode < 2 + modeShift ) mode += 65;
+      else if( h > w && mode > 66 - modeShift ) mode -= 67;
+    }
+    const int lm = mode < 0 ? mode + 14 + 67 : mode >= 67 ? mode + 14 : mode;
+    const bool transpose = ( lm >= 67 && lm >= 67 + 14 ) || ( lm < 67 && lm > 34 );
+    // g_lfnstLut (Rom.cpp): 0 for planar / DC and the LM modes, 1 / 2 / 3 / 2 / 1 over the angles
+    const int set = lm < 2 ? 0 : lm < 13 ? 1 : lm < 24 ? 2 : lm < 45 ? 3 : lm < 56 ? 2 : lm < 95 ? 1 : 0;
+    lf = 1u | ( (uint32_t) set << 1 ) | ( (uint32_t) ( ( cu.lfnst_idx - 1 ) & 1 ) << 3 ) | ( transpose ? 16u : 0u );
+  }
+  TbRec r;
+  r.coef = tu.coef_off[comp]; r.x = (uint16_t) bx; r.y = (uint16_t) by;
+  r.a = (uint32_t) tbr_ilog2( bw ) | ( (uint32_t) tbr_ilog2( bh ) << 3 ) | ( (uint32_t) comp << 6 ) | ( (uint32_t) ( it.mode & 1 ) << 8 ) | ( (uint32_t) ( it.ict & 7 ) << 9 )
+      | ( (uint32_t) ( tu.mts_idx[comp] & 7 ) << 12 ) | ( (uint32_t) ( tu.tr_type[comp] & 15 ) << 15 ) | ( (uint32_t) bdpcm << 19 )
+      | ( ( sliceFlags & VVR_TOOL_DEP_QUANT ) ? 1u << 21 : 0u ) | ( ( sliceFlags & VVR_TOOL_SCALING_LIST ) ? 1u << 22 : 0u ) | ( (uint32_t) listType << 23 ) | ( lf << 26 );
+  r.b = (uint32_t) tu.max_scan_x[comp] | ( (uint32_t) tu.max_scan_y[comp] << 8 ) | ( (uint32_t) (uint8_t) tu.qp[comp] << 16 );
+  return r;
+}
+
 // One intra-predicted transform block (decode order inside its CTU).  The reference-sample availability counts are the
 // m_neighborSize[] values IntraPrediction::xFillReferenceSamples derives by walking the CU/TU tree (IntraPrediction.cpp:1104-1139);
 // that walk is host glue here (vvr_prepare), the kernel only consumes the counts.
@@ -123,6 +194,7 @@ struct PicDev {         // everything a kernel needs about one picture (passed b
   int                colStride;      // records per row = ( w4 + 1 ) / 2
   int                vpdusX, vpduLog2;
   int                w4, h4, ctus_x, ctus_y;
+  const TbRec*       tbRec[3];       // the records of the transform blocks, one per TbItem of the size class (written by k_prep: launch_itrans hands its class's to the kernel)
 };
 
 struct RefSet { const pel_t* p[2 * VVR_MAX_REFS][3]; };   // reference planes indexed [list * 16 + refIdx][comp]; geometry = the current picture's
@@ -238,6 +310,7 @@ struct PrepWork
   const McCuRef* mcCus = nullptr; int numMcCus = 0; McItem *plain = nullptr, *bdof = nullptr, *dmvr = nullptr;
   bool lfMaps = false; uint32_t numCu = 0, numTu = 0; struct LfCell *cell = nullptr, *cellC = nullptr; struct LfMv* mv = nullptr; uint32_t* ref = nullptr; const struct LfSbCell* sb = nullptr; int numSb = 0;
   const IntraItem *items = nullptr, *resi = nullptr; int numItems = 0, numResi = 0; uint32_t* maps = nullptr; size_t mapInts = 0; int mapW4 = 0, mapH4 = 0;
+  const TbItem* tbItems[3] = { nullptr, nullptr, nullptr }; TbRec* tbRecs[3] = { nullptr, nullptr, nullptr }; int numTb[3] = { 0, 0, 0 };      // the transform blocks' records (prep_tb_records)
 };
 void launch_prep( hipStream_t s, const PicDev& pic, const PrepWork& w );
 void launch_intra_leaf( hipStream_t s, const PicDev& pic, DevPlanes reco, DevPlanes resi, const IntraItem* items, int numItems, const IntraItem* resiItems, int numResi /* residual-add blocks grouped by VPDU: done by the VPDU's IT_MODE_CSFAC item */,

@@ -28,6 +28,7 @@ struct vvr_prepared {
   McItem*  rprItems = nullptr; int numRprItems = 0;        // tiles of CUs that predict from a scaled reference picture
   uint32_t numDmvr = 0;                                    // delta-MV entries the DMVR kernel writes (pairs of ints)
   TbItem*  tbItems[3] = { nullptr, nullptr, nullptr }; int numTb[3] = { 0, 0, 0 };   // size classes 16 / 32 / 64
+  TbRec*   tbRecs[3] = { nullptr, nullptr, nullptr };                                 // one record per item, written by k_prep (room reserved behind the uploaded image)
   IntraItem* intraItems = nullptr; IntraUnit* units = nullptr; int numActive = 0, numIntra = 0;
   bool     intraFine = false;                              // (tile path) every unit is a whole CTU of intra CUs: the CTU wavefront may be resolved block by block (k_intra<.., FINE>)
   bool     intraLeaf = false;                              // the items are those of k_intra_leaf (one wavefront per block, no units): a picture with scattered intra blocks

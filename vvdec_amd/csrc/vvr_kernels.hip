@@ -35,7 +35,7 @@ __device__ TR_ALIGN int16_t d_dct2_2[4], d_dct2_4[16], d_dct2_8[64], d_dct2_16[2
 __device__ TR_ALIGN int16_t d_dct8_4[16], d_dct8_8[64], d_dct8_16[256], d_dct8_32[1024];
 __device__ TR_ALIGN int16_t d_dst7_4[16], d_dst7_8[64], d_dst7_16[256], d_dst7_32[1024];
 __device__ int8_t  d_lfnst8x8[4][2][48][16], d_lfnst4x4[4][2][16][16];
-__device__ uint8_t d_lfnst_lut[97], d_lfnst_scan8x8_xy[16][2], d_lfnst_scan4x4_xy[16][2];
+__device__ uint8_t d_lfnst_scan8x8_xy[16][2], d_lfnst_scan4x4_xy[16][2];      // (the LFNST set of an intra mode - g_lfnstLut - is part of tb_record, vvr_device.h)
 __device__ int32_t d_inv_quant_scales[2][6];
 __device__ uint8_t d_mip_matrix_4x4[16][16][4], d_mip_matrix_8x8[8][16][8], d_mip_matrix_16x16[6][64][7];
 __device__ int16_t d_geo_params[64][2], d_geo_weight_offset[64][4][4][2];
@@ -55,7 +55,7 @@ int vvr_upload_tables()
   UPLOAD( dct2_2 ); UPLOAD( dct2_4 ); UPLOAD( dct2_8 ); UPLOAD( dct2_16 ); UPLOAD( dct2_32 ); UPLOAD( dct2_64 );
   UPLOAD( dct8_4 ); UPLOAD( dct8_8 ); UPLOAD( dct8_16 ); UPLOAD( dct8_32 );
   UPLOAD( dst7_4 ); UPLOAD( dst7_8 ); UPLOAD( dst7_16 ); UPLOAD( dst7_32 );
-  UPLOAD( lfnst8x8 ); UPLOAD( lfnst4x4 ); UPLOAD( lfnst_lut ); UPLOAD( lfnst_scan8x8_xy ); UPLOAD( lfnst_scan4x4_xy );
+  UPLOAD( lfnst8x8 ); UPLOAD( lfnst4x4 ); UPLOAD( lfnst_scan8x8_xy ); UPLOAD( lfnst_scan4x4_xy );
   UPLOAD( inv_quant_scales ); UPLOAD( luma_filter ); UPLOAD( luma_filter_4x4 ); UPLOAD( luma_alt_hpel ); UPLOAD( chroma_filter );
   UPLOAD( bcw_weights ); UPLOAD( db_tc_table ); UPLOAD( db_beta_table ); UPLOAD( alf_fixed_coeff ); UPLOAD( alf_class_to_filter );
   UPLOAD( mip_matrix_4x4 ); UPLOAD( mip_matrix_8x8 ); UPLOAD( mip_matrix_16x16 );
@@ -2192,16 +2192,6 @@ __device__ __forceinline__ const int16_t* tr_matrix( int type, int n )
   switch( n ) { case 4: return d_dst7_4; case 8: return d_dst7_8; case 16: return d_dst7_16; default: return d_dst7_32; }
 }
 
-__device__ __forceinline__ int wide_angle_mode( int w, int h, int mode )   // PU::getWideAngIntraMode (UnitTools.cpp:617)
-{
-  const int modeShift[6] = { 0, 6, 10, 12, 14, 15 };
-  if( mode < 2 ) return mode;
-  const int d = iabs( ilog2( w ) - ilog2( h ) );
-  if( w > h && mode < 2 + modeShift[d] ) mode += 65;
-  else if( h > w && mode > 66 - modeShift[d] ) mode -= 67;
-  return mode;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // LMCS chroma residual scaling: Reshape::calculateChromaAdjVpduNei (Reshape.cpp:192-274) — the factor of a VPDU is looked up from
 // the mean of the reconstructed (mapped-domain) luma samples left of and above the CU at the VPDU origin; AreaBuf::scaleSignal
@@ -2305,34 +2295,51 @@ __device__ __forceinline__ int scaling_entry( const vvr_scaling_list* __restrict
 
 // NT threads per transform block: 64 for the <= 16x16 class (one wavefront per block: four times as many blocks resident, no
 // cross-wave barrier), 256 for the larger classes.
-// Round 6: three memory round trips per block - the item; its TU record; then EVERYTHING else at once: the CU record, the coded levels, the basis rows of both
-// passes and, for a block that is added onto the prediction, the prediction samples its lanes are going to change - instead of seven one after the other (item, TU,
-// CU, levels, basis rows, and at the very end a read of the prediction for every group of stores).  What the loads depend on of the CU - a chroma block that takes
-// its geometry from an ISP CU, BDPCM, LFNST - the host says in the item (TbItem::pad), so that only such a block waits for the CU record before it asks for the rest.
+// Two memory round trips per block: its record (TbRec, 16 bytes: position, size, levels, QP, transform, BDPCM, the slice's switches, the LFNST set - written by
+// k_prep from the item, the TU and CU records and the slice map, in front of the picture's waits); then EVERYTHING else at once: the coded levels, the basis rows of
+// both passes and, for a block that is added onto the prediction, the prediction samples its lanes are going to change.  (Round 6 had three - item, TU record, the
+// rest with the CU record - and seven before that.)
+// Packed passes: every operand of the two 1-D passes is a 16-bit value by construction (the dequantised level, the LFNST output and the intermediate are clipped
+// to int16, the basis is int16), so LDS holds them two per dword, PAIRED ALONG THE SUMMATION INDEX k:
+//   dqP [kp * dqW + x]  = ( dq[2kp][x],  dq[2kp+1][x] )       the coefficients (row y = k of column x), dqW = min( bw, CUT )
+//   mvP [kp * bh  + y]  = ( Mv[2kp][y],  Mv[2kp+1][y] )       basis of the vertical pass
+//   tmpP[kp * bh  + y]  = ( tmp[2kp][y], tmp[2kp+1][y] )      the intermediate (column x = k of row y)
+//   mhP [kp * bw  + x]  = ( Mh[2kp][x],  Mh[2kp+1][x] )       basis of the horizontal pass
+// and the inner step is v_dot2_i32_i16 (two products and the accumulate, full rate) on a 16-byte read of four neighbouring columns / rows and one dword of the basis.
+// The sum is exact in any order: at most 64 terms of |level| <= 32768 times |basis| <= 90 stay below 2^31.  An odd count of rows (cutH) or columns (redW) that take
+// part: the upper half of the last basis pair is zero (where the rows are staged), whatever the other operand holds there.
+// Only a CUT x CUT corner of a block can carry coefficients (CUT = 32 in the 64 class: blocks above 32 are DCT-2 with zero-out; transform skip and BDPCM stop
+// at 32, which vvr_prepare checks), so dqP is CUT x CUT, tmpP CUT x MAXN and each basis CUT x MAXN 16-bit values: 14 KB in the 64 class.
+constexpr int itr_cut( int maxn ) { return maxn > 32 ? 32 : maxn; }
+// element (k, j) of a buffer paired along k with row length n (in 16-bit units)
+__device__ __forceinline__ int itr_at( int k, int j, int n ) { return ( ( ( k >> 1 ) * n + j ) << 1 ) + ( k & 1 ); }
+__device__ __forceinline__ uint32_t itr_pack( int lo, int hi ) { return ( (uint32_t) lo & 0xffffu ) | ( (uint32_t) hi << 16 ); }
+
 template<int MAXN, int NT>
-__global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 32 ? 3 : 8, 8 ) ) ) void k_itrans( PicDev pic, DevPlanes reco, DevPlanes resi, const TbItem* __restrict__ items, int numItems )
+__global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 32 ? 5 : 8, 8 ) ) ) void k_itrans( PicDev pic, DevPlanes reco, DevPlanes resi, const TbRec* __restrict__ recs, int numItems )
 {
-  __shared__ __attribute__( ( aligned( 16 ) ) ) int32_t dq[MAXN * MAXN];      // (16-byte reads in the two passes)
-  __shared__ __attribute__( ( aligned( 16 ) ) ) int32_t tmp[MAXN * MAXN];
-  __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t mvS[MAXN * MAXN], mhS[MAXN * MAXN];
+  constexpr int CUT = itr_cut( MAXN );
+  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t dqP[CUT * CUT / 2];      // (16-byte reads in the two passes)
+  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t tmpP[CUT * MAXN / 2];
+  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t mvP[CUT * MAXN / 2], mhP[CUT * MAXN / 2];
   __shared__ int32_t lf_in[16], lf_out[48];
+  int16_t* const dq16 = reinterpret_cast<int16_t*>( dqP ); int16_t* const tmp16 = reinterpret_cast<int16_t*>( tmpP );
+  const int16_t* const mv16 = reinterpret_cast<const int16_t*>( mvP ); const int16_t* const mh16 = reinterpret_cast<const int16_t*>( mhP );
   const int item = blockIdx.x;
   if( item >= numItems ) return;
-  const TbItem it = items[item];
-  const vvr_tu& tu = pic.tu[it.tu];
-  const int comp = it.comp, bd = pic.hdr.bit_depth, tid = threadIdx.x;
-  const int csh = comp ? 1 : 0;
-  // ---- the TU record: every field the block needs, asked for together
-  const int tuX = tu.x, tuY = tu.y, tuW = tu.w, tuH = tu.h, mts = tu.mts_idx[comp], trt = tu.tr_type[comp];
-  const int scanX = tu.max_scan_x[comp], scanY = tu.max_scan_y[comp], tuQp = tu.qp[comp];
-  const int16_t* __restrict__ lev = pic.coef + tu.coef_off[comp];
-  const vvr_cu& cu = pic.cu[tu.cu];
-  int bw = tuW >> csh, bh = tuH >> csh, bx = tuX >> csh, by = tuY >> csh;
-  if( it.pad & TB_P_CUGEOM ) { bw = cu.w >> 1; bh = cu.h >> 1; bx = cu.x >> 1; by = cu.y >> 1; }      // (chroma of an ISP CU)
-  const int lw = ilog2( bw ), lh = ilog2( bh ), n = bw * bh;
+  // ---- the block's record (one 16-byte load): every field the block needs - the item, its TU and CU records and the slice map are not touched
+  TbRec rec;
+  { const uint4 q = *reinterpret_cast<const uint4*>( &recs[item] ); rec.coef = q.x; rec.x = (uint16_t) ( q.y & 0xffff ); rec.y = (uint16_t) ( q.y >> 16 ); rec.a = q.z; rec.b = q.w; }
+  const int comp = tbr_comp( rec ), bd = pic.hdr.bit_depth, tid = threadIdx.x;
+  const int mts = tbr_mts( rec ), trt = tbr_tr_type( rec );
+  const int scanX = tbr_scan_x( rec ), scanY = tbr_scan_y( rec ), tuQp = tbr_qp( rec );
+  const int16_t* __restrict__ lev = pic.coef + rec.coef;
+  const int lw = tbr_lw( rec ), lh = tbr_lh( rec ), bw = 1 << lw, bh = 1 << lh, bx = rec.x, by = rec.y, n = bw * bh;
+  const int itMode = tbr_mode( rec );
   const bool isTS = mts == VVR_MTS_SKIP;
-  const bool bdpcmOn = ( it.pad & TB_P_BDPCM ) != 0;
-  const bool lfnstBit = ( it.pad & TB_P_LFNST ) != 0;                // cu.lfnst_idx > 0 && ( cu.tree != VVR_TREE_JOINT || comp == 0 )
+  const int bdpcm = tbr_bdpcm( rec );
+  const bool bdpcmOn = bdpcm != 0;
+  const bool lfnstBit = tbr_lfnst( rec );                            // cu.lfnst_idx > 0 && ( cu.tree != VVR_TREE_JOINT || comp == 0 )
   const bool lfnstOn = ( pic.hdr.tool_flags & VVR_TOOL_LFNST ) && lfnstBit && !isTS;
   // the corner that carries coefficients when the passes start: the coded one, the whole block under BDPCM, at least the LFNST output region
   const int cw = scanX + 1, codedRows = scanY + 1;
@@ -2346,7 +2353,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
   const bool twoD = !isTS && !dcOnly && !oneD;
   const bool fourRows = bh >= 4 && !oneD;                   // four neighbouring rows of a column per work item in the output stage
   // basis rows the passes touch (zero-out of the high frequencies: TrQuant_EMT.cpp:389)
-  int redW = 0, cutH = 0, cntV = 0, cntH = 0;
+  int redW = 0, cutH = 0, cntH = 0;
   const int16_t* __restrict__ Mv = nullptr; const int16_t* __restrict__ Mh = nullptr;
   if( oneD )
   {
@@ -2360,32 +2367,52 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
     const int skipW = max( ( trHor != 0 && bw == 32 ) ? 16 : bw > 32 ? bw - 32 : 0, bw - maxX - 1 );
     const int skipH = max( ( trVer != 0 && bh == 32 ) ? 16 : bh > 32 ? bh - 32 : 0, bh - maxY - 1 );
     cutH = bh - skipH; redW = bw - skipW;
-    Mv = tr_matrix( trVer, bh ); Mh = tr_matrix( trHor, bw ); cntV = cutH * bh; cntH = redW * bw;
+    Mv = tr_matrix( trVer, bh ); Mh = tr_matrix( trHor, bw ); cntH = redW * bw;
   }
-  // ---- the loads: levels (one per lane and step over the whole block: zero outside the coded corner), basis rows as dwords, prediction samples
-  constexpr int ITER_C = MAXN * MAXN / NT, ITER_M = ( MAXN > 32 ? 32 : MAXN ) * MAXN / 2 / NT, ITER_E = MAXN * MAXN / 4 / NT;
-  int lv[ITER_C];
+  // ---- the loads: levels (a pair of rows of one column per lane and step over the corner that can be non-zero: zero outside the coded one), basis rows as dwords, prediction samples
+  // a work item of the level loop owns a pair of rows of one column of the CUT x CUT corner (one dword of dqP), one of the basis loop two neighbouring
+  // columns of a pair of basis rows (two dwords of mvP / mhP)
+  constexpr int ITER_P = CUT * CUT / 2 / NT, ITER_M = CUT * MAXN / 4 / NT, ITER_E = MAXN * MAXN / 4 / NT;
+  const int dqW = min( bw, CUT ), dqH = min( bh, CUT ), ldW = min( lw, ilog2( CUT ) ), dqHp = ( dqH + 1 ) >> 1;
+  int lv[ITER_P][2];
   if( !bdpcmOn )
   {
 #pragma unroll
-    for( int k = 0; k < ITER_C; k++ )
+    for( int k = 0; k < ITER_P; k++ )
     {
-      const int i = tid + k * NT, y = i >> lw, x = i & ( bw - 1 );
-      lv[k] = 0;
-      if( i < n && x < cw && y < codedRows ) lv[k] = lev[y * cw + x];
+      const int i = tid + k * NT, yp = i >> ldW, x = i & ( dqW - 1 );
+#pragma unroll
+      for( int e = 0; e < 2; e++ )
+      {
+        const int y = 2 * yp + e;
+        lv[k][e] = 0;
+        if( y < dqH && x < cw && y < codedRows ) lv[k][e] = lev[y * cw + x];
+      }
     }
   }
-  uint32_t mvR[ITER_M], mhR[ITER_M];
+  const int nV = bh, nH = oneD ? ( bw == 1 ? bh : bw ) : bw, lnV2 = max( lh - 1, 0 ), lnH2 = ilog2( nH ) - 1;          // (rows of the basis are nV / nH long; both are even)
+  const int unitsV = ( ( cutH + 1 ) >> 1 ) << lnV2, unitsH = cntH ? ( ( redW + 1 ) >> 1 ) << lnH2 : 0;       // (cutH = 0 unless both passes run)
+  uint32_t mvR[ITER_M][2], mhR[ITER_M][2];
 #pragma unroll
   for( int k = 0; k < ITER_M; k++ )
   {
     const int j = tid + k * NT;
-    mvR[k] = 0; mhR[k] = 0;
-    if( 2 * j < cntV ) mvR[k] = reinterpret_cast<const uint32_t*>( Mv )[j];
-    if( 2 * j < cntH ) mhR[k] = reinterpret_cast<const uint32_t*>( Mh )[j];
+    mvR[k][0] = mvR[k][1] = 0; mhR[k][0] = mhR[k][1] = 0;
+    if( j < unitsV )
+    {
+      const int kp = j >> lnV2, jp = j & ( ( nV >> 1 ) - 1 );
+      mvR[k][0] = reinterpret_cast<const uint32_t*>( Mv )[( ( 2 * kp ) << lnV2 ) + jp];
+      if( 2 * kp + 1 < cutH ) mvR[k][1] = reinterpret_cast<const uint32_t*>( Mv )[( ( 2 * kp + 1 ) << lnV2 ) + jp];
+    }
+    if( j < unitsH )
+    {
+      const int kp = j >> lnH2, jp = j & ( ( nH >> 1 ) - 1 );
+      mhR[k][0] = reinterpret_cast<const uint32_t*>( Mh )[( ( 2 * kp ) << lnH2 ) + jp];
+      if( 2 * kp + 1 < redW ) mhR[k][1] = reinterpret_cast<const uint32_t*>( Mh )[( ( 2 * kp + 1 ) << lnH2 ) + jp];
+    }
   }
-  const int ict = it.ict ? (int) it.ict - 4 : 0;
-  const bool havePred = it.mode == TB_ADD && !ict && fourRows;
+  const int ict = tbr_ict( rec ) ? tbr_ict( rec ) - 4 : 0;
+  const bool havePred = itMode == TB_ADD && !ict && fourRows;
   int predv[ITER_E][4];
   {
     const pel_t* __restrict__ P = reco.p[comp]; const int stride = reco.stride[comp];
@@ -2402,13 +2429,13 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
   for( int k = 0; k < ITER_M; k++ )
   {
     const int j = tid + k * NT;
-    if( 2 * j < cntV ) reinterpret_cast<uint32_t*>( mvS )[j] = mvR[k];
-    if( 2 * j < cntH ) reinterpret_cast<uint32_t*>( mhS )[j] = mhR[k];
+    // rows 2kp and 2kp+1 of two neighbouring columns -> the pairs of the two columns (an odd count of rows: the missing row is zero)
+    if( j < unitsV ) reinterpret_cast<uint2*>( mvP )[j] = make_uint2( ( mvR[k][0] & 0xffffu ) | ( mvR[k][1] << 16 ), ( mvR[k][0] >> 16 ) | ( mvR[k][1] & 0xffff0000u ) );
+    if( j < unitsH ) reinterpret_cast<uint2*>( mhP )[j] = make_uint2( ( mhR[k][0] & 0xffffu ) | ( mhR[k][1] << 16 ), ( mhR[k][0] >> 16 ) | ( mhR[k][1] & 0xffff0000u ) );
   }
   // ---- dequantisation
   {
-    const uint32_t sliceFlags = flags_at( pic, tuX, tuY );      // dependent quantisation and the scaling lists are switches of the block's slice (Quant.cpp:306,336)
-    const bool depQuant = ( sliceFlags & VVR_TOOL_DEP_QUANT ) && !isTS;
+    const bool depQuant = tbr_dep_quant( rec ) && !isTS;         // (dependent quantisation and the scaling lists are switches of the block's slice: the record has the slice's)
     int qp = tuQp;
     if( isTS ) qp = max( qp, (int) pic.hdr.min_qp_ts );
     const int per = depQuant ? ( qp + 1 ) / 6 : qp / 6;
@@ -2416,7 +2443,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
     const bool needSqrt = !isTS && ( ( lw + lh ) & 1 );
     const int trShift = 15 - bd - ( ( lw + lh ) >> 1 ) - ( needSqrt ? 1 : 0 );
     // explicit scaling list (getUseScalingList, Quant.h:103): not for transform skip, optionally not for LFNST blocks
-    const bool useSL = pic.scaling && ( sliceFlags & VVR_TOOL_SCALING_LIST ) && !isTS && !( lfnstBit && ( pic.hdr.tool_flags & VVR_TOOL_SCALING_LIST_NO_LFNST ) );
+    const bool useSL = pic.scaling && tbr_sl_on( rec ) && !isTS && !( lfnstBit && ( pic.hdr.tool_flags & VVR_TOOL_SCALING_LIST_NO_LFNST ) );
     const int rightShift = 6 + ( depQuant ? 1 : 0 ) - ( ( isTS ? 0 : trShift ) + per ) + ( useSL ? 4 : 0 );
     const int scaleQP = d_inv_quant_scales[needSqrt ? 1 : 0][rem];
     int targetBits = 32 + rightShift - 7; if( targetBits > 16 ) targetBits = 16;
@@ -2424,51 +2451,53 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
     if( bdpcmOn )
     {
       // invResDPCM (Quant.cpp:239): running sums along rows (mode 1) / columns (mode 2); one thread per line
-      const int bdpcm = comp ? cu.bdpcm[1] : cu.bdpcm[0];
       const int lines = bdpcm == 1 ? bh : bw, len = bdpcm == 1 ? bw : bh;
       for( int l = tid; l < lines; l += NT )
       {
         int acc = 0;
         for( int k = 0; k < len; k++ )
         {
-          const int idx = bdpcm == 1 ? l * bw + k : k * bw + l;
-          const int v = lev[idx];
+          const int y = bdpcm == 1 ? l : k, x = bdpcm == 1 ? k : l;
+          const int v = lev[y * bw + x];
           acc = k == 0 ? v : clip3( -32768, 32767, acc + v );
-          dq[idx] = acc;
+          if( y < dqH && x < dqW ) dq16[itr_at( y, x, dqW )] = (int16_t) acc;      // (a 16-bit value: a level, or clipped)
         }
       }
       __syncthreads();
-      for( int i = tid; i < n; i += NT )
+      for( int i = tid; i < dqH * dqW; i += NT )
       {
-        const int level = dq[i];
+        const int at = itr_at( i >> ldW, i & ( dqW - 1 ), dqW );
+        const int level = dq16[at];
         if( level )
         {
           const long long c = clip3( inMin, inMax, level );
           const long long v = rightShift > 0 ? ( c * scaleQP + ( 1ll << ( rightShift - 1 ) ) ) >> rightShift : ( c * scaleQP ) * ( 1ll << -rightShift );
-          dq[i] = clip3( -32768, 32767, (int) v );
+          dq16[at] = (int16_t) clip3( -32768, 32767, (int) v );
         }
       }
     }
     else
     {
-      const int listType = useSL ? ( cu.pred_mode == VVR_PRED_INTRA ? 0 : 3 ) + comp : 0;
+      const int listType = useSL ? tbr_list_type( rec ) : 0;
 #pragma unroll
-      for( int k = 0; k < ITER_C; k++ )
+      for( int k = 0; k < ITER_P; k++ )
       {
-        const int i = tid + k * NT;
-        if( i < n )
+        const int i = tid + k * NT, yp = i >> ldW, x = i & ( dqW - 1 );
+        int out[2];
+#pragma unroll
+        for( int e = 0; e < 2; e++ )
         {
-          const int level = lv[k];
-          int out = 0;
+          const int level = lv[k][e];
+          out[e] = 0;
           if( level )
           {
             const long long c = clip3( inMin, inMax, level );
-            const int scale = useSL ? scaling_entry( pic.scaling, listType, lw, lh, i & ( bw - 1 ), i >> lw ) * scaleQP : scaleQP;
+            const int scale = useSL ? scaling_entry( pic.scaling, listType, lw, lh, x, 2 * yp + e ) * scaleQP : scaleQP;
             const long long v = rightShift > 0 ? ( c * scale + ( 1ll << ( rightShift - 1 ) ) ) >> rightShift : ( c * scale ) * ( 1ll << -rightShift );
-            out = clip3( -32768, 32767, (int) v );
+            out[e] = clip3( -32768, 32767, (int) v );
           }
-          dq[i] = out;
         }
+        if( yp < dqHp ) dqP[i] = itr_pack( out[0], out[1] );      // (the whole corner is written: zero outside the coded one)
       }
     }
   }
@@ -2477,18 +2506,12 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
   if( lfnstOn )
   {
     const bool whge3 = bw >= 8 && bh >= 8;
-    int mode;
-    if( ( cu.flags & VVR_CU_MIP ) && comp == 0 ) mode = 0;
-    else if( comp && cu.intra_dir[1] >= 67 ) mode = cu.lfnst_intra_mode;
-    else mode = cu.intra_dir[comp ? 1 : 0];
-    mode = wide_angle_mode( ( cu.isp_mode && !comp ) ? cu.w : bw, ( cu.isp_mode && !comp ) ? cu.h : bh, mode );
-    const int lm = mode < 0 ? mode + 14 + 67 : mode >= 67 ? mode + 14 : mode;
-    const bool transpose = ( lm >= 67 && lm >= 67 + 14 ) || ( lm < 67 && lm > 34 );
+    const bool transpose = tbr_lfnst_transposed( rec );         // (set, index and transposition: derived from the CU's intra mode by tb_record)
     const int sb = whge3 ? 8 : 4;
     const int zeroOut = ( ( bw == 4 && bh == 4 ) || ( bw == 8 && bh == 8 ) ) ? 8 : 16;
-    if( tid < 16 ) { const uint8_t* xy = whge3 ? d_lfnst_scan8x8_xy[tid] : d_lfnst_scan4x4_xy[tid]; lf_in[tid] = dq[xy[1] * bw + xy[0]]; }
+    if( tid < 16 ) { const uint8_t* xy = whge3 ? d_lfnst_scan8x8_xy[tid] : d_lfnst_scan4x4_xy[tid]; lf_in[tid] = dq16[itr_at( xy[1], xy[0], dqW )]; }
     __syncthreads();
-    const int set = d_lfnst_lut[lm], idx = cu.lfnst_idx - 1, trSize = sb == 8 ? 48 : 16;
+    const int set = tbr_lfnst_set( rec ), idx = tbr_lfnst_idx( rec ), trSize = sb == 8 ? 48 : 16;
     if( tid < trSize )
     {
       int r = 0;
@@ -2499,16 +2522,17 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
     if( tid < sb * sb )
     {
       const int y = tid / sb, x = tid % sb;
-      if( sb == 4 ) dq[y * bw + x] = transpose ? lf_out[x * 4 + y] : lf_out[y * 4 + x];
+      int16_t* d = &dq16[itr_at( y, x, dqW )];       // (lf_out is clipped to 16 bits)
+      if( sb == 4 ) *d = (int16_t) ( transpose ? lf_out[x * 4 + y] : lf_out[y * 4 + x] );
       else if( transpose )
       {
-        if( x < 4 ) dq[y * bw + x] = lf_out[x * 8 + y];
-        else if( y < 4 ) dq[y * bw + x] = lf_out[32 + ( x - 4 ) * 4 + y];
+        if( x < 4 ) *d = (int16_t) lf_out[x * 8 + y];
+        else if( y < 4 ) *d = (int16_t) lf_out[32 + ( x - 4 ) * 4 + y];
       }
       else
       {
-        if( y < 4 ) dq[y * bw + x] = lf_out[y * 8 + x];
-        else if( x < 4 ) dq[y * bw + x] = lf_out[32 + ( y - 4 ) * 4 + x];
+        if( y < 4 ) *d = (int16_t) lf_out[y * 8 + x];
+        else if( x < 4 ) *d = (int16_t) lf_out[32 + ( y - 4 ) * 4 + x];
       }
     }
     __syncthreads();
@@ -2517,34 +2541,37 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
   int dcVal = 0;
   if( dcOnly )
   {
-    if( oneD ) dcVal = (int16_t) ( ( dq[0] * 64 + ( 1 << shift2 ) ) >> ( shift2 + 1 ) );
+    const int dc = dq16[0];
+    if( oneD ) dcVal = (int16_t) ( ( dc * 64 + ( 1 << shift2 ) ) >> ( shift2 + 1 ) );
     else
     {
-      dcVal = ( dq[0] * 64 + ( 1 << ( shift1 - 1 ) ) ) >> shift1;
+      dcVal = ( dc * 64 + ( 1 << ( shift1 - 1 ) ) ) >> shift1;
       dcVal = (int16_t) ( ( dcVal * 64 + ( 1 << ( shift2 - 1 ) ) ) >> shift2 );
     }
   }
   else if( twoD )
   {
-    // pass 1 (vertical): tmp[x*bh + y] = clip16( ( sum_k dq[k*bw + x] * Mv[k*bh + y] + 64 ) >> 7 ), x < redW
-    // Four neighbouring columns per work item: one 16-byte read of dq and one basis value per step instead of a read of each per multiply-add
-    // (the kernel lives on the LDS pipe: 512 + 1024 scalar reads per thread for a 64x64 block with a 32x32 corner before this)
+    // pass 1 (vertical): tmp[x][y] = clip16( ( sum_k dq[k][x] * Mv[k][y] + 64 ) >> 7 ), x < redW
+    // Four neighbouring columns per work item: one 16-byte read of dqP (a pair of rows of the four columns) and one dword of the basis per step, four v_dot2 = eight
+    // multiply-adds; the four results are two dwords of tmpP, already paired for pass 2 (columns from redW up to the end of the group: zero)
     if( bw >= 4 )
     {
-      const int grpX = ( redW + 3 ) >> 2;
+      const int grpX = ( redW + 3 ) >> 2, kp1 = ( cutH + 1 ) >> 1;
       for( int i = tid; i < grpX * bh; i += NT )
       {
         const int xg = i >> lh, y = i & ( bh - 1 ), x0 = xg << 2;
         int s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-        for( int k = 0; k < cutH; k++ )
+        for( int kp = 0; kp < kp1; kp++ )
         {
-          const int m = mvS[k * bh + y];
-          const int4 d = *reinterpret_cast<const int4*>( &dq[k * bw + x0] );
-          s0 += d.x * m; s1 += d.y * m; s2 += d.z * m; s3 += d.w * m;
+          const uint32_t m = mvP[kp * bh + y];
+          const uint4 d = *reinterpret_cast<const uint4*>( &dqP[kp * dqW + x0] );
+          s0 = mc_dot2( d.x, m, s0 ); s1 = mc_dot2( d.y, m, s1 ); s2 = mc_dot2( d.z, m, s2 ); s3 = mc_dot2( d.w, m, s3 );
         }
         const int sv[4] = { s0, s1, s2, s3 };
+        int tv[4];
 #pragma unroll
-        for( int r = 0; r < 4; r++ ) if( x0 + r < redW ) tmp[( x0 + r ) * bh + y] = clip3( -32768, 32767, ( sv[r] + ( 1 << ( shift1 - 1 ) ) ) >> shift1 );
+        for( int r = 0; r < 4; r++ ) tv[r] = x0 + r < redW ? clip3( -32768, 32767, ( sv[r] + ( 1 << ( shift1 - 1 ) ) ) >> shift1 ) : 0;
+        tmpP[( xg * 2 ) * bh + y] = itr_pack( tv[0], tv[1] ); tmpP[( xg * 2 + 1 ) * bh + y] = itr_pack( tv[2], tv[3] );
       }
     }
     else
@@ -2552,8 +2579,8 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
     {
       const int x = i >> lh, y = i & ( bh - 1 );
       int sum = 0;
-      for( int k = 0; k < cutH; k++ ) sum += dq[k * bw + x] * mvS[k * bh + y];
-      tmp[x * bh + y] = clip3( -32768, 32767, ( sum + ( 1 << ( shift1 - 1 ) ) ) >> shift1 );
+      for( int k = 0; k < cutH; k++ ) sum += __mul24( dq16[itr_at( k, x, dqW )], mv16[itr_at( k, y, bh )] );
+      tmp16[itr_at( x, y, bh )] = (int16_t) clip3( -32768, 32767, ( sum + ( 1 << ( shift1 - 1 ) ) ) >> shift1 );
     }
     __syncthreads();
   }
@@ -2574,7 +2601,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
       else                 { rOther = -r >> 1; cOther = 1; }
       rOther = (int16_t) rOther;
     }
-    if( it.mode == TB_ADD )
+    if( itMode == TB_ADD )
     {
       pel_t* d = &reco.p[cSelf][(size_t) ( by + y ) * reco.stride[cSelf] + bx + x];
       *d = (pel_t) clip_pel( *d + r, bd );
@@ -2603,11 +2630,11 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
         if( twoD )
         {
           int s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-          for( int k = 0; k < redW; k++ )
+          for( int kp = 0; kp < ( ( redW + 1 ) >> 1 ); kp++ )
           {
-            const int m = mhS[k * bw + x];
-            const int4 t = *reinterpret_cast<const int4*>( &tmp[k * bh + y0] );
-            s0 += t.x * m; s1 += t.y * m; s2 += t.z * m; s3 += t.w * m;
+            const uint32_t m = mhP[kp * bw + x];
+            const uint4 t = *reinterpret_cast<const uint4*>( &tmpP[kp * bh + y0] );
+            s0 = mc_dot2( t.x, m, s0 ); s1 = mc_dot2( t.y, m, s1 ); s2 = mc_dot2( t.z, m, s2 ); s3 = mc_dot2( t.w, m, s3 );
           }
           const int sv[4] = { s0, s1, s2, s3 };
 #pragma unroll
@@ -2616,7 +2643,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
         else
         {
 #pragma unroll
-          for( int r = 0; r < 4; r++ ) rv[r] = isTS ? (int) (int16_t) dq[( y0 + r ) * bw + x] : dcVal;
+          for( int r = 0; r < 4; r++ ) rv[r] = isTS ? (int) dq16[itr_at( y0 + r, x, dqW )] : dcVal;
         }
         if( havePred )
         {
@@ -2637,20 +2664,20 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
   {
     const int y = i >> lw, x = i & ( bw - 1 );
     int r;
-    if( isTS ) r = (int16_t) dq[i];
+    if( isTS ) r = dq16[itr_at( y, x, dqW )];
     else if( dcOnly ) r = dcVal;
     else if( oneD )
     {
       const int n1 = bw == 1 ? bh : bw;
       int sum = 0;
-      for( int k = 0; k < redW; k++ ) sum += dq[k] * mhS[k * n1 + i];        // (i runs along the only dimension)
+      for( int k = 0; k < redW; k++ ) sum += __mul24( dq16[bw == 1 ? itr_at( k, 0, 1 ) : itr_at( 0, k, dqW )], mh16[itr_at( k, i, n1 )] );        // (i runs along the only dimension)
       r = clip3( -32768, 32767, ( sum + ( 1 << shift2 ) ) >> ( shift2 + 1 ) );
     }
     else
     {
       // out[y*bw + x] = clip16( ( sum_{k<redW} tmp[k*bh + y] * Mh[k*bw + x] + rnd ) >> shift2 )
       int sum = 0;
-      for( int k = 0; k < redW; k++ ) sum += tmp[k * bh + y] * mhS[k * bw + x];
+      for( int k = 0; k < redW; k++ ) sum += __mul24( tmp16[itr_at( k, y, bh )], mh16[itr_at( k, x, bw )] );
       r = clip3( -32768, 32767, ( sum + ( 1 << ( shift2 - 1 ) ) ) >> shift2 );
     }
     emit( x, y, r );
@@ -2660,9 +2687,12 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
 void launch_itrans( hipStream_t s, const PicDev& pic, DevPlanes reco, DevPlanes resi, const TbItem* items, int numItems, int sizeClass )
 {
   if( !numItems ) return;
-  if( sizeClass <= 16 )      hipLaunchKernelGGL( ( k_itrans<16, 64> ),  dim3( numItems ), dim3( 64 ),  0, s, pic, reco, resi, items, numItems );
-  else if( sizeClass <= 32 ) hipLaunchKernelGGL( ( k_itrans<32, 128> ), dim3( numItems ), dim3( 128 ), 0, s, pic, reco, resi, items, numItems );
-  else                       hipLaunchKernelGGL( ( k_itrans<64, 256> ), dim3( numItems ), dim3( 256 ), 0, s, pic, reco, resi, items, numItems );
+  // (the kernel reads the records k_prep wrote from the items, one per item of the class: pic.tbRec.  `items` stays in the signature, which the stand-in runtime of
+  // the host tests - tests/hoststub - defines too: the caller hands over the list the records were made from)
+  (void) items;
+  if( sizeClass <= 16 )      hipLaunchKernelGGL( ( k_itrans<16, 64> ),  dim3( numItems ), dim3( 64 ),  0, s, pic, reco, resi, pic.tbRec[0], numItems );
+  else if( sizeClass <= 32 ) hipLaunchKernelGGL( ( k_itrans<32, 128> ), dim3( numItems ), dim3( 128 ), 0, s, pic, reco, resi, pic.tbRec[1], numItems );
+  else                       hipLaunchKernelGGL( ( k_itrans<64, 256> ), dim3( numItems ), dim3( 256 ), 0, s, pic, reco, resi, pic.tbRec[2], numItems );
 }
 
 // =====================================================================================================================
@@ -7001,13 +7031,29 @@ static IntraPic intra_pic( const PicDev& pic, const DevPlanes& reco, const DevPl
 //   * prep_expand_mc   the motion-compensation tiles of plain, BDOF and DMVR CUs from the CU records
 //   * prep_lf_maps     the per-cell records and motion of the deblocking edge derivation (k_lf_init, the next launch of that stage, reads them)
 //   * prep_intra_mark  the cells the scattered intra blocks of the picture are going to produce, and their ticket (k_intra_leaf)
+//   * prep_tb_records  the records of the transform blocks (k_itrans): item -> TU -> CU -> slice, chased here instead of at the head of every block of the three launches
 // =====================================================================================================================
+// one thread per transform block of the three size classes: tb_record (vvr_device.h) of its item
+__device__ __forceinline__ void prep_tb_records( int bid, const PicDev& pic, const TbItem* const ( &items )[3], TbRec* const ( &recs )[3], const int ( &num )[3] )
+{
+  int i = bid * 256 + threadIdx.x, cls = 0;
+  if( i >= num[0] ) { i -= num[0]; cls = 1; if( i >= num[1] ) { i -= num[1]; cls = 2; if( i >= num[2] ) return; } }
+  const TbItem* __restrict__ its = cls == 0 ? items[0] : cls == 1 ? items[1] : items[2];
+  TbRec* __restrict__ out = cls == 0 ? recs[0] : cls == 1 ? recs[1] : recs[2];
+  const TbItem it = its[i];
+  const vvr_tu& tu = pic.tu[it.tu];        // (a reference: a copy indexed by the component would be placed in LDS)
+  const vvr_cu& cu = pic.cu[tu.cu];
+  const TbRec r = tb_record( it, tu, cu, flags_at( pic, tu.x, tu.y ) );      // dependent quantisation and the scaling lists are switches of the block's slice (Quant.cpp:306,336)
+  *reinterpret_cast<uint4*>( &out[i] ) = make_uint4( r.coef, (uint32_t) r.x | ( (uint32_t) r.y << 16 ), r.a, r.b );
+}
+
 struct PrepArgs
 {
   const McCuRef* mcCus; int numMcCus; McItem *plain, *bdof, *dmvr;
   int numCu, numTu, numSb, dbg; LfCell *cell, *cellC; LfMv* mv; uint32_t* ref; const LfSbCell* sb;
   const IntraItem *items, *resi; int numItems, numResi; LeafMaps M; int* sync;
-  int blocksExpand, blocksMaps;
+  const TbItem* tbItems[3]; TbRec* tbRecs[3]; int numTb[3];
+  int blocksExpand, blocksMaps, blocksTb;
 };
 __global__ __launch_bounds__( 256 ) void k_prep( PicDev pic, PrepArgs a )
 {
@@ -7017,6 +7063,8 @@ __global__ __launch_bounds__( 256 ) void k_prep( PicDev pic, PrepArgs a )
   bid -= a.blocksMaps;
   if( bid < a.blocksExpand ) { prep_expand_mc( bid, pic.cu, a.mcCus, a.numMcCus, a.plain, a.bdof, a.dmvr ); return; }
   bid -= a.blocksExpand;
+  if( bid < a.blocksTb ) { prep_tb_records( bid, pic, a.tbItems, a.tbRecs, a.numTb ); return; }
+  bid -= a.blocksTb;
   prep_intra_mark( bid, a.items, a.numItems, a.resi, a.numResi, a.M, a.sync );
 }
 
@@ -7040,7 +7088,9 @@ void launch_prep( hipStream_t s, const PicDev& pic, const PrepWork& w )
     a.M = leaf_maps_of( pic, w.maps, w.mapW4, w.mapH4 ); a.sync = reinterpret_cast<int*>( w.maps + w.mapInts - 64 );
     blocksMark = ( w.numItems + w.numResi + 15 ) / 16;
   }
-  const int blocks = a.blocksMaps + a.blocksExpand + blocksMark;
+  for( int k = 0; k < 3; k++ ) { a.tbItems[k] = w.tbItems[k]; a.tbRecs[k] = w.tbRecs[k]; a.numTb[k] = w.tbRecs[k] ? w.numTb[k] : 0; }
+  a.blocksTb = ( a.numTb[0] + a.numTb[1] + a.numTb[2] + 255 ) / 256;
+  const int blocks = a.blocksMaps + a.blocksExpand + a.blocksTb + blocksMark;
   if( blocks ) hipLaunchKernelGGL( k_prep, dim3( blocks ), dim3( 256 ), 0, s, pic, a );
 }
 

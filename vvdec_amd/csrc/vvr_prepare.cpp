@@ -129,7 +129,7 @@ struct PrepScratch
   std::vector<Part> parts;
   size_t total = 0, numDirect = 0;          // parts [0, numDirect) are copied from the caller's pinned arrays
   int iLfSb, iLfTu, iLfTuC, iLfMotion;
-  int iCu, iTu, iCoef, iAffMv, iL0, iL1, iSao, iAlf, iAlfP, iSlices, iLmcs, iSl, iCtuSlice, iCtuTile, iSubpics, iCtuSubpic, iWp, iCsVpdu, iMc, iMcB, iMcD, iMcA, iTb[3], iIntra, iResi, iUnits, iMcCus, iMcDev[3], iRpr, iMcR;
+  int iCu, iTu, iCoef, iAffMv, iL0, iL1, iSao, iAlf, iAlfP, iSlices, iLmcs, iSl, iCtuSlice, iCtuTile, iSubpics, iCtuSubpic, iWp, iCsVpdu, iMc, iMcB, iMcD, iMcA, iTb[3], iTbRec[3], iIntra, iResi, iUnits, iMcCus, iMcDev[3], iRpr, iMcR;
   size_t stagedEndOff = 0;                  // end of the uploaded part of the image
 
   void begin( const vvr_picture* pic )
@@ -467,6 +467,8 @@ static int validate_records_range( const vvr_picture* p, uint32_t cu0, uint32_t 
         if( tu.mts_idx[c] > VVR_MTS_DCT8_DCT8 || ( tu.tr_type[c] & 3 ) > 2 || ( tu.tr_type[c] >> 2 ) > 2 ) FAIL( VVR_ERR_PARAMETER, "TU: transform type out of range" );
         const int bdp = c ? cu.bdpcm[1] : cu.bdpcm[0];
         if( !bdp && ( tu.max_scan_x[c] >= bw || tu.max_scan_y[c] >= bh ) ) FAIL( VVR_ERR_PARAMETER, "TU: last significant position outside the block" );
+        // (k_itrans keeps the 32 x 32 corner of a block above 32: the DCT-2 zero-out; transform skip and BDPCM carry levels everywhere and stop at 32 - MaxTsSize)
+        if( ( bdp || tu.mts_idx[c] == VVR_MTS_SKIP ) && ( bw > 32 || bh > 32 ) ) FAIL( VVR_ERR_PARAMETER, "TU: transform skip / BDPCM block larger than 32 samples" );
         const uint64_t n = bdp ? (uint64_t) bw * bh : (uint64_t) ( tu.max_scan_x[c] + 1 ) * ( tu.max_scan_y[c] + 1 );
         if( (uint64_t) tu.coef_off[c] + n > p->num_coef ) FAIL( VVR_ERR_PARAMETER, "TU: coded corner outside the level stream" );
       }
@@ -1845,6 +1847,7 @@ void PrepScratch::layout( PinnedRanges* pinned )
   // behind everything that is uploaded: room for what the device writes itself (k_expand_mc, k_lf_init)
   stagedEndOff = total;
   for( int k = 0; k < 3; k++ ) iMcDev[k] = add( nullptr, sizeof( McItem ) * devTiles[k] );
+  for( int k = 0; k < 3; k++ ) iTbRec[k] = add( nullptr, sizeof( TbRec ) * tb[k].size() );
   iLfTu = iLfTuC = iLfMotion = -1;
   if( lfpOnDevice )
   {
@@ -2286,7 +2289,7 @@ void vvr_host_bind( const PrepScratch& S, vvr_prepared& q, char* base )
   q.affItems = (McItem*) at( S.iMcA ); q.numAffItems = (int) S.mcAff.size();
   q.rprItems = (McItem*) at( S.iMcR ); q.numRprItems = (int) S.mcRpr.size();
   q.numDmvr = S.numDmvr;
-  for( int k = 0; k < 3; k++ ) { q.tbItems[k] = (TbItem*) at( S.iTb[k] ); q.numTb[k] = (int) S.tb[k].size(); }
+  for( int k = 0; k < 3; k++ ) { q.tbItems[k] = (TbItem*) at( S.iTb[k] ); q.numTb[k] = (int) S.tb[k].size(); q.tbRecs[k] = (TbRec*) at( S.iTbRec[k] ); d.tbRec[k] = q.tbRecs[k]; }
   q.intraItems = (IntraItem*) at( S.iIntra ); q.numIntra = (int) S.intraAll.size(); q.intraLeaf = S.leaf; q.intraFine = !S.leaf && S.intraFine && !S.unitsDev.empty();
   q.units = (IntraUnit*) at( S.iUnits ); q.numActive = (int) S.unitsDev.size(); q.intraWorkgroups = S.intraWorkgroups;
   q.resiItems = (IntraItem*) at( S.iResi ); q.numResi = (int) S.resiAdd.size(); q.numLumaUnits = S.numLumaUnits; q.intraWorkgroupsChroma = S.intraWorkgroupsChroma;
