@@ -561,7 +561,8 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *            ( Ek + 128 ) / 257 with one included.  The refusals are those of the three planar formats, a missing plane or a stride below the
  *            row among the planes the format uses.
  *            Not offered: interleaved float32; 4:0:0 as grey; RGB from the synchronous vvr_read_output* calls; constant-luminance BT.2020,
- *            ICtCp, YCgCo, the identity matrix; dynamic metadata; a 3-D LUT for the synchronous calls.
+ *            ICtCp, YCgCo, the identity matrix; a 3-D LUT for the synchronous calls.  Dynamic metadata: the per-frame measurements exist
+ *            (vvr_stats_submit, vvr_light_level below); parsing ST 2094 / CLL SEIs, smoothing over time and scene logic do not.
  *   grain with out_w / out_h: the window is grained at its own size exactly as vvr_read_output_grain does it, the grained frame is then
  *            rescaled exactly as vvr_read_output_scaled rescales a picture, taps clamped to the grained frame (the reference's order:
  *            xAddGrain in xAddPicture, then the application's upscaleFrame).
@@ -777,6 +778,78 @@ typedef struct vvr_hash_request {
   uint32_t* mismatch;        /* required with `expected`: bit c set when component c differs (what picHashError reports), 0 = verified */
 } vvr_hash_request;
 VVR_API int          vvr_hash_submit(vvr_context* ctx, const vvr_hash_request* req);
+/* Light-level statistics of a picture as a request of the output queue: the per-frame measurements dynamic HDR metadata is made of - what a
+ * player that tone-maps by scene (peak detection), a transcoder that writes MaxCLL / MaxFALL (CTA-861.3) or the ST 2094-40 fields (maxscl,
+ * average_maxrgb, the maxRGB percentiles) and anything that watches luma histograms would otherwise pull a whole RGB frame over PCIe for.  The
+ * reduction runs where the pixels are; 8216 bytes cross PCIe; nothing drains.  The result is integers, defined here to the bit:
+ *   window   x, y, w, h in luma samples of the picture in the slot (vvr_slot_picture_size), even in 4:2:0.  Film grain and rescaling are not
+ *            offered: content metadata is measured on the decoded picture.  The seed chain is never touched.
+ *   hist_y   hist_y[v]: the luma samples of the window, as they lie in the slot, with value v (a slot holds values below 2^bd; a sample above 1023
+ *            written from outside counts in bin 1023).  Both modes.
+ *   VVR_STATS_RGB   R, G, B of a pixel are the three values of the definition above (VVR_OUT_RGB16) computed at od = bd - the input of the transform
+ *            stage: chroma to the luma grid by the 4-tap filter, taps clamped to the WINDOW's chroma, `collocated` of the request, the Q14 matrix of
+ *            the colour description that is set when vvr_stats_submit accepts the request (the coefficients travel as kernel arguments: a later
+ *            vvr_set_output_colour never changes a request in flight).  hist_maxrgb[v]: pixels with max( R, G, B ) == v.  max_c[c], min_c[c]: the
+ *            largest and the smallest value of channel c = R, G, B over the window (max_c: ST 2094-40 maxscl as code values).  The context's
+ *            transform, 3-D LUT and normalisation are ignored: the statistics describe the coded signal, not a rendering of it.
+ *   VVR_STATS_LUMA  hist_y alone; hist_maxrgb, max_c and min_c are 0.  Works in every context, 4:0:0 included.
+ *   bins     at 2^bd and above: 0.  samples = width * height; both histograms sum to it (hist_maxrgb in RGB mode).
+ *   ticket and ring, ordering   everything said about a hash request above holds: the ticket comes from the same ticket space and the same 8 ring
+ *            entries (VVR_ERR_BUSY counts all three kinds of request); vvr_output_test / vvr_output_wait collect it; vvr_output_stream_wait means
+ *            "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the request runs on the output
+ *            stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1); pictures submitted afterwards
+ *            that overwrite the slot wait for the request's kernels on the device; blocking == 0: VVR_NOT_READY while `job` has not been handed
+ *            to the device; a request for a job that failed is accepted and fails with that job's status, *stats untouched.
+ *   result   vvr_output_wait, when it returns VVR_OK, writes *stats: every field, struct_size included.  It must stay valid until then.
+ * Refused (VVR_ERR_PARAMETER with a text, no ring entry taken): a struct_size other than sizeof( vvr_stats_request ), no such slot, job < -1, an
+ * unknown mode, stats == NULL, a window outside the picture, empty, or odd in a 4:2:0 context, RGB mode in a 4:0:0 context or without a colour
+ * description.
+ * The intended loop of a player: vvr_stats_submit -> vvr_output_wait -> vvr_light_level -> vvr_output_lut3d_preset( src_peak_nits = the measured
+ * pct_nits or max_nits ) -> vvr_set_output_lut3d -> the RGB request of the same picture.  Smoothing over time and scene logic stay with the caller;
+ * ST 2094 / CLL SEIs are not parsed here. */
+enum { VVR_STATS_LUMA = 0, VVR_STATS_RGB = 1 };
+typedef struct vvr_frame_stats {
+  uint32_t struct_size;        /* sizeof( vvr_frame_stats ), written with the rest */
+  uint32_t mode;               /* VVR_STATS_* of the request */
+  uint32_t bit_depth;          /* the context's: bins 0 .. 2^bit_depth - 1 are in use */
+  uint32_t pad;
+  uint32_t width, height;      /* the window */
+  uint64_t samples;            /* width * height */
+  uint32_t hist_y[1024];       /* hist_y[v]: luma samples of the window with value v */
+  uint32_t hist_maxrgb[1024];  /* RGB mode: pixels with max( R, G, B ) == v */
+  uint32_t max_c[3], min_c[3]; /* RGB mode: per channel R, G, B over the window (max_c = ST 2094-40 maxscl as code values) */
+} vvr_frame_stats;
+typedef struct vvr_stats_request {
+  uint32_t struct_size;        /* sizeof( vvr_stats_request ) */
+  int32_t  slot;
+  int32_t  job;                /* as vvr_output_request.job */
+  int32_t  x, y, w, h;         /* window, luma samples (even in 4:2:0) */
+  uint8_t  collocated;         /* RGB mode: as vvr_output_request.collocated */
+  uint8_t  mode;               /* VVR_STATS_LUMA / VVR_STATS_RGB */
+  uint8_t  blocking;           /* as vvr_output_request.blocking */
+  uint8_t  pad;
+  vvr_frame_stats* stats;      /* written by vvr_output_wait; must stay valid until it has returned */
+} vvr_stats_request;
+VVR_API int          vvr_stats_submit(vvr_context* ctx, const vvr_stats_request* req);
+/* Light levels from RGB-mode statistics; a pure host function, no context, everything in double.  M = 2^bit_depth - 1.
+ *   max_code   the highest non-empty bin of hist_maxrgb.
+ *   pct_code   the smallest v with cum( v ) * 10000 >= percentile_e4 * samples, cum( v ) = hist_maxrgb[0] + ... + hist_maxrgb[v], in uint64;
+ *              percentile_e4 in 1 .. 10000 (9995: 99.95 %).
+ *   transfer_characteristics 16 (PQ): with EOTF the ST 2084 EOTF of vvr_output_transform_preset, in cd/m2: max_nits = EOTF( max_code / M ),
+ *              pct_nits = EOTF( pct_code / M ), maxscl_nits[c] = EOTF( max_c[c] / M ), avg_nits = ( sum over v, ascending, of hist_maxrgb[v] *
+ *              EOTF( v / M ) ) / samples - the frame average of maxRGB, the quantity MaxFALL is the maximum of (max_nits: MaxCLL's).
+ *   transfer_characteristics 0: the code fields alone; the nits fields are 0.
+ * struct_size, transfer and the pad are set.  Refused (VVR_ERR_PARAMETER, *out untouched): a NULL pointer, statistics whose struct_size is not
+ * sizeof( vvr_frame_stats ), whose mode is not VVR_STATS_RGB, whose bit depth is outside 8..10 or whose hist_maxrgb does not sum to `samples`
+ * (or samples == 0), a percentile outside 1 .. 10000, any other transfer (HLG is relative: the presets ignore its source peak). */
+struct vvr_light_level {       /* (a tag, no typedef: the function has the name) */
+  uint32_t struct_size;        /* sizeof( struct vvr_light_level ) */
+  uint32_t transfer;           /* the transfer_characteristics the nits fields were computed with, or 0 */
+  uint32_t max_code, pct_code;
+  double   max_nits, pct_nits, avg_nits;
+  double   maxscl_nits[3];
+};
+VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_characteristics, uint32_t percentile_e4, struct vvr_light_level* out);
 /* the finished picture in `slot` (every plane, at the picture's size) into the caller's buffers - what a decoder does with each picture it hands to
  * the application (the planes of a vvdecFrame live in the Picture's own buffers, vvdecimpl.cpp:1058).  Waits for NOTHING: the caller has waited for
  * the picture (vvr_wait); other pictures in flight are not held up (vvr_read_plane drains the context).  Each plane crosses PCIe in one transfer

@@ -113,6 +113,10 @@ def lib():
         L.vvr_output_wait.argtypes = [C.c_void_p, C.c_int]
         L.vvr_hash_submit.restype = C.c_int
         L.vvr_hash_submit.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_stats_submit.restype = C.c_int
+        L.vvr_stats_submit.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_light_level.restype = C.c_int
+        L.vvr_light_level.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
         L.vvr_output_stream_wait.restype = C.c_int
         L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vvr_device_alloc.restype = C.c_void_p
@@ -132,7 +136,7 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
-                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit",
+                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit", "vvr_stats_submit", "vvr_light_level",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
 
 
@@ -158,6 +162,30 @@ def output_lut3d(n, transfer, primaries, target, src_peak=1000., dst_peak=100.):
     if rc != abi.VVR_OK:
         raise VvrError("vvr_output_lut3d_preset: n 17, 33 or 65, transfer 16 or 18, primaries 1 or 9, a target of abi.XFORM_TARGETS, peaks in (0, 10000] (rc %d)" % rc)
     return int(n), nodes
+
+
+class FrameStats:
+    """the result of Reconstructor.stats_wait: numpy views of the arrays of an abi.FrameStats (`raw`, which light_level takes) and its header
+    fields"""
+    def __init__(self, raw):
+        import numpy as np
+        self.raw = raw
+        self.mode, self.bit_depth, self.width, self.height, self.samples = raw.mode, raw.bit_depth, raw.width, raw.height, raw.samples
+        self.hist_y, self.hist_maxrgb = np.ctypeslib.as_array(raw.hist_y), np.ctypeslib.as_array(raw.hist_maxrgb)
+        self.max_c, self.min_c = np.ctypeslib.as_array(raw.max_c), np.ctypeslib.as_array(raw.min_c)
+
+
+def light_level(stats, transfer=16, percentile=9995):
+    """vvr_light_level: the light levels of a frame from its RGB-mode statistics (a FrameStats of stats_wait, or an abi.FrameStats) -> an
+    abi.LightLevel: max_code and pct_code (the highest non-empty bin of max( R, G, B ) and its percentile; `percentile` is in units of 0.01 %,
+    1 .. 10000, 9995 meaning 99.95 %), and for transfer 16 (PQ) max_nits, pct_nits, avg_nits (the frame average of maxRGB: what MaxFALL is the
+    maximum of) and maxscl_nits per channel in cd/m2; transfer 0: the codes alone.  pct_nits is what output_lut3d takes as src_peak for this
+    frame.  A pure host function; nothing is computed here."""
+    out = abi.LightLevel()
+    rc = lib().vvr_light_level(C.byref(getattr(stats, "raw", stats)), int(transfer), int(percentile), C.byref(out))
+    if rc != abi.VVR_OK:
+        raise VvrError("vvr_light_level: RGB-mode statistics, transfer 16 (PQ) or 0 (codes only), a percentile of 1 .. 10000 (rc %d)" % rc)
+    return out
 
 
 def _cube_tokens(path):
@@ -589,6 +617,25 @@ class Reconstructor:
         expected): bit c of the mask is set when component c differs from the expected digest, 0 means the picture is verified"""
         digest, mismatch, nc, n = self.output_wait(ticket)
         return [bytes(digest[k * n:(k + 1) * n]) for k in range(nc)], None if mismatch is None else mismatch.value
+
+    def stats_submit(self, slot, job=None, window=None, mode="rgb", collocated=(True, False), blocking=True):
+        """vvr_stats_submit: light-level statistics of the window of `slot` (as `job` leaves it; None: as all work submitted so far leaves it),
+        reduced on the device -> ticket, or None when blocking=False and the job has not been handed to the device yet.  mode "rgb": the luma
+        histogram, the histogram of max( R, G, B ) and the channels' extremes of the coded R'G'B' (the matrix of set_output_colour at the
+        context's bit depth; transform, LUT and normalisation are ignored); "luma": the luma histogram alone, in any context.  The ticket
+        shares the 8 entries of output_submit; output_test and output_stream_wait take it.  Nothing here drains the context."""
+        raw = abi.FrameStats()
+        req = abi.stats_request(slot, job, tuple(window or (0, 0, self.width, self.height)), mode, collocated, blocking, raw)
+        ticket = self._check(self.L.vvr_stats_submit(self.ctx, C.byref(req)))
+        if not blocking and ticket == abi.VVR_NOT_READY:
+            return None
+        self._out[ticket] = raw
+        return ticket
+
+    def stats_wait(self, ticket):
+        """vvr_output_wait for a ticket of stats_submit -> FrameStats (numpy views hist_y, hist_maxrgb, max_c, min_c; vvdec_amd.light_level
+        turns it into light levels)"""
+        return FrameStats(self.output_wait(ticket))
 
     def write_picture(self, slot, planes):
         for c, pl in enumerate(planes):

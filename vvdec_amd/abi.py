@@ -261,5 +261,39 @@ class HashRequest(C.Structure):
                 ("digest", C.c_void_p), ("expected", C.c_void_p), ("mismatch", C.c_void_p)]
 
 
+STATS_LUMA, STATS_RGB = 0, 1
+STATS_MODES = {"luma": STATS_LUMA, "rgb": STATS_RGB}
+
+
+class FrameStats(C.Structure):
+    """vvr_frame_stats: what vvr_output_wait writes for a statistics request (vvr_stats_submit, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("mode", u32), ("bit_depth", u32), ("pad", u32), ("width", u32), ("height", u32), ("samples", u64),
+                ("hist_y", u32 * 1024), ("hist_maxrgb", u32 * 1024), ("max_c", u32 * 3), ("min_c", u32 * 3)]
+
+
+class StatsRequest(C.Structure):
+    """vvr_stats_request: light-level statistics of a picture as a request of the output queue (vvr_stats_submit, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("slot", i32), ("job", i32), ("x", i32), ("y", i32), ("w", i32), ("h", i32),
+                ("collocated", u8), ("mode", u8), ("blocking", u8), ("pad", u8), ("stats", C.c_void_p)]
+
+
+class LightLevel(C.Structure):
+    """vvr_light_level: the light levels vvr_light_level derives from RGB-mode statistics (vvr.h)"""
+    _fields_ = [("struct_size", u32), ("transfer", u32), ("max_code", u32), ("pct_code", u32),
+                ("max_nits", C.c_double), ("pct_nits", C.c_double), ("avg_nits", C.c_double), ("maxscl_nits", C.c_double * 3)]
+
+
+def stats_request(slot, job, window, mode, collocated, blocking, stats):
+    """a StatsRequest that writes into `stats` (a FrameStats the caller keeps alive until the request has been waited for)"""
+    r = StatsRequest()
+    r.struct_size = C.sizeof(StatsRequest)
+    r.slot, r.job = slot, -1 if job is None else job
+    r.x, r.y, r.w, r.h = window
+    r.collocated = int(bool(collocated[0])) | int(bool(collocated[1])) << 1
+    r.mode, r.blocking = STATS_MODES[mode] if isinstance(mode, str) else mode, 1 if blocking else 0
+    r.stats = C.addressof(stats)
+    return r
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]

@@ -278,6 +278,17 @@ struct OutputRgbParams
   const uint16_t* lut; int lutN, lutShift; uint32_t lutWiden;
 };
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
+// light-level statistics of the output queue (vvr_stats_submit, the definition: vvr.h).  launch_output_stats: the window src / stride / w / h of p
+// (rgb != 0: the 4:2:0 frame with collocated and the matrix at od = bd, as launch_output_rgb takes it; else src[0] alone) accumulated into
+// `shards`: STATS_SHARDS copies of STATS_WORDS words, all zero before the launch - hist_y[1024], hist_maxrgb[1024], max_c[3], then maxVal - min_c[3]
+// (a maximum too, so that zero is the start of every word).  A workgroup adds into the copy its index selects: the workgroups of a flat frame all
+// add to one bin, and adds to one address take their turn at the memory side.  launch_output_stats_sum: out[i] = the sum (the last six words: the
+// maximum) over the copies.
+#define STATS_SHARDS 16
+#define STATS_WORDS 2054
+#define RGB_FMT_STATS 255      /* the store class of k_output_rgb that accumulates where the others store */
+void launch_output_stats( hipStream_t s, const OutputRgbParams& p, int rgb, uint32_t* shards );
+void launch_output_stats_sum( hipStream_t s, const uint32_t* shards, uint32_t* out );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.
 // launch_hash_rows: one launch over the rows of all planes, rows[g] = the CRC piece (the row's bytes mod P, register from 0) or the checksum share
 // of row g (the planes' rows one after the other).  launch_hash_combine: out[c] = the component's digest as a number - the checksum, or the CRC

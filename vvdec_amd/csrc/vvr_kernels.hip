@@ -5207,6 +5207,63 @@ __device__ __forceinline__ void rgb_store_px( uint8_t* __restrict__ plane, size_
     }
   }
 }
+// Light-level statistics (vvr_stats_submit, the definition: vvr.h): histograms of luma and of max( R, G, B ), the channels' extremes.  RGB mode is
+// one more store class of k_output_rgb, RGB_FMT_STATS - its staging, its sums, its lane of 8 samples, XF = 0 - with an accumulation where the store
+// is; luma mode is the row kernel k_output_stats below.  A workgroup keeps its histograms in LDS (stats_lds: 2 x 1024 counters and the six extremes,
+// beside the 14 KB of the tile) and adds its non-zero bins - a few dozen of 2048 for a natural tile - to the request's words in global memory
+// afterwards.  All sums are integers: the result does not depend on the order.
+// The hard case is flat content - sky, letterbox bars, a black frame: every lane adds to one bin, and adds to one address take their turn, in LDS
+// as at the memory side.  Three measures: a lane merges equal neighbours among its 8 values in registers (a run is one add of its length); when
+// every lane of a wavefront holds eight times one and the same value, one lane adds 512; and the workgroups spread over STATS_SHARDS copies of
+// the words in global memory (vvr_device.h), which k_output_stats_sum folds.  The extremes are reduced across the wavefront in registers - two
+// channels to a dword, max( M - v ) for the minimum so that zero starts every word - and one lane per wavefront touches LDS.
+__device__ __forceinline__ uint32_t* stats_lds()
+{
+  __shared__ uint32_t stats_words[STATS_WORDS + 2];      // (only kernels that call this hold it)
+  return stats_words;
+}
+__device__ __forceinline__ void stats_hist8( uint32_t* __restrict__ hist, const int ( &v )[8], int n, bool live )      // values 0 .. 1023; n of them exist in a live lane
+{
+  bool one = live && n == 8;
+#pragma unroll
+  for( int i = 1; i < 8; i++ ) one = one && v[i] == v[0];
+  const int first = __builtin_amdgcn_readfirstlane( v[0] );
+  if( __all( one && v[0] == first ) )      // (uniform: every lane of the wavefront is here)
+  {
+    if( ( threadIdx.x & 63 ) == 0 ) atomicAdd( &hist[first], 512u );
+    return;
+  }
+  if( !live ) return;
+  int cur = v[0]; uint32_t run = 1;
+#pragma unroll
+  for( int i = 1; i < 8; i++ )
+    if( i < n )
+    {
+      if( v[i] == cur ) run++;
+      else { atomicAdd( &hist[cur], run ); cur = v[i]; run = 1; }
+    }
+  atomicAdd( &hist[cur], run );
+}
+typedef unsigned short stats_us2 __attribute__(( ext_vector_type( 2 ) ));
+__device__ __forceinline__ uint32_t stats_wave_max2( uint32_t v )      // both halves of the dword, over the wavefront
+{
+#pragma unroll
+  for( int d = 1; d < 64; d <<= 1 )
+  {
+    const uint32_t o = (uint32_t) __shfl_xor( (int) v, d );
+    v = __builtin_bit_cast( uint32_t, __builtin_elementwise_max( __builtin_bit_cast( stats_us2, v ), __builtin_bit_cast( stats_us2, o ) ) );
+  }
+  return v;
+}
+__device__ __forceinline__ void stats_flush( const uint32_t* __restrict__ words, uint32_t* __restrict__ shards )
+{
+  uint32_t* __restrict__ out = shards + (size_t) ( ( blockIdx.x + blockIdx.y * gridDim.x ) & ( STATS_SHARDS - 1 ) ) * STATS_WORDS;
+  for( int i = threadIdx.x; i < STATS_WORDS; i += 256 )
+  {
+    const uint32_t v = words[i];
+    if( v ) { if( i < 2048 ) atomicAdd( &out[i], v ); else atomicMax( &out[i], v ); }
+  }
+}
 // XF: the colour transform of vvr_set_output_transform (the definition: vvr.h) between the clip of R, G, B and the store, in registers.  The workgroup
 // brings the two tables into LDS with the staging (their loads are issued with the chroma window's, ahead of the first barrier): lin as it is (2 KB),
 // enc as 1024 pairs enc[i] | enc[i + 1] << 16 (4 KB), so that stage 3 is one 4-byte LDS read per value instead of two 2-byte ones; a sample costs three
@@ -5274,6 +5331,11 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
 #pragma unroll
     for( int k = 0; k < 2; k++ ) *(uint2*) &xf_enc[2 * ( tid + 256 * k )] = make_uint2( xe[k][0], xe[k][0] >> 16 | xe[k][1] << 16 );
   }
+  if constexpr( FMT == RGB_FMT_STATS )
+  {
+    uint32_t* __restrict__ words = stats_lds();
+    for( int i = tid; i < STATS_WORDS; i += 256 ) words[i] = 0;
+  }
   __syncthreads();
   // horizontal pass: output columns 2 k (phase 0 or 24) and 2 k + 1 (phase 16 or 8) of a staged row; c[2] is the chroma sample at column k of the tile
   for( int u = tid; u < 2 * RGB_CH * ( RGB_TW / 2 ); u += 256 )
@@ -5286,7 +5348,7 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
     *(int2*) &rgb_sum[pl][r][2 * k] = make_int2( ev, od );
   }
   __syncthreads();
-  if( !live ) return;
+  if( FMT != RGB_FMT_STATS && !live ) return;      // (the statistics end on a barrier: their lanes outside the frame stay, and count nothing)
   // vertical pass: row y = Y0 + jj takes the staged rows f .. f + 3 with the taps of its phase
   const bool odd = jj & 1;
   const int f = ( jj >> 1 ) + ( COLY || odd ? 1 : 0 );
@@ -5319,6 +5381,37 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
     R[i] = clip3( 0, p.maxOut, ( l + p.rv * v ) >> 14 );
     G[i] = clip3( 0, p.maxOut, ( l + p.gu * u + p.gv * v ) >> 14 );
     B[i] = clip3( 0, p.maxOut, ( l + p.bu * u ) >> 14 );
+  }
+  if constexpr( FMT == RGB_FMT_STATS )
+  {
+    // the accumulation where the store is (maxOut is maxVal: od = bd): the lane's luma and its max( R, G, B ) into the two histograms, the extremes
+    // of its samples that exist across the wavefront, then the workgroup's non-zero words to the request's
+    uint32_t* __restrict__ words = stats_lds();
+    int ys[8], mx[8];
+    uint32_t hi[3] = { 0, 0, 0 }, lo[3] = { 0, 0, 0 };      // max( v ), max( maxVal - v )
+#pragma unroll
+    for( int i = 0; i < 8; i++ )
+    {
+      const uint32_t y2 = i < 2 ? yy.x : ( i < 4 ? yy.y : ( i < 6 ? yy.z : yy.w ) );
+      ys[i] = min( (int) ( ( y2 >> ( 16 * ( i & 1 ) ) ) & 0xffff ), 1023 );
+      mx[i] = max( R[i], max( G[i], B[i] ) );
+      if( live && i < n )
+      {
+        hi[0] = max( hi[0], (uint32_t) R[i] ); hi[1] = max( hi[1], (uint32_t) G[i] ); hi[2] = max( hi[2], (uint32_t) B[i] );
+        lo[0] = max( lo[0], (uint32_t) ( p.maxVal - R[i] ) ); lo[1] = max( lo[1], (uint32_t) ( p.maxVal - G[i] ) ); lo[2] = max( lo[2], (uint32_t) ( p.maxVal - B[i] ) );
+      }
+    }
+    stats_hist8( words, ys, n, live );
+    stats_hist8( words + 1024, mx, n, live );
+    const uint32_t e0 = stats_wave_max2( hi[0] | hi[1] << 16 ), e1 = stats_wave_max2( hi[2] | lo[0] << 16 ), e2 = stats_wave_max2( lo[1] | lo[2] << 16 );
+    if( ( tid & 63 ) == 0 )
+    {
+      atomicMax( &words[2048], e0 & 0xffff ); atomicMax( &words[2049], e0 >> 16 ); atomicMax( &words[2050], e1 & 0xffff );
+      atomicMax( &words[2051], e1 >> 16 ); atomicMax( &words[2052], e2 & 0xffff ); atomicMax( &words[2053], e2 >> 16 );
+    }
+    __syncthreads();
+    stats_flush( words, (uint32_t*) dst );
+    return;
   }
   if( xf )
   {
@@ -5443,6 +5536,74 @@ void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst )
   case VVR_OUT_RGBA16F: launch_output_rgb_fmt<VVR_OUT_RGBA16F>( s, p, dst ); break;
   default: break;      // (the request path hands over one of the eight classes)
   }
+}
+
+// k_output_stats — luma mode of the statistics: the window's rows in pieces of 8 samples, a lane one piece (one 16-byte load, sample by sample
+// at a row's end), a workgroup STATS_ITER x 256 consecutive pieces into one histogram in LDS - 16 K samples for each clear and each flush
+#define STATS_ITER 8
+__global__ __launch_bounds__( 256 ) void k_output_stats( const pel_t* __restrict__ src, int stride, int w, int h, uint32_t* __restrict__ shards )
+{
+  uint32_t* __restrict__ words = stats_lds();
+  const int tid = threadIdx.x, pieces = ( w + 7 ) >> 3, total = pieces * h;      // (sides <= 8192: below 2^23)
+  for( int i = tid; i < STATS_WORDS; i += 256 ) words[i] = 0;
+  __syncthreads();
+  for( int it = 0; it < STATS_ITER; it++ )
+  {
+    const int item = ( blockIdx.x * STATS_ITER + it ) * 256 + tid;
+    const bool live = item < total;
+    int v[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, n = 8;
+    if( live )
+    {
+      const int row = item / pieces, x = ( item - row * pieces ) * 8;
+      const pel_t* __restrict__ s = src + (size_t) row * stride + x;
+      n = min( 8, w - x );
+      if( n == 8 )
+      {
+        uint4 q; __builtin_memcpy( &q, s, 16 );      // (unaligned access mode)
+        v[0] = q.x & 0xffff; v[1] = q.x >> 16; v[2] = q.y & 0xffff; v[3] = q.y >> 16; v[4] = q.z & 0xffff; v[5] = q.z >> 16; v[6] = q.w & 0xffff; v[7] = q.w >> 16;
+      }
+      else
+      {
+#pragma unroll
+        for( int i = 0; i < 7; i++ ) if( i < n ) v[i] = (uint16_t) s[i];
+      }
+#pragma unroll
+      for( int i = 0; i < 8; i++ ) v[i] = min( v[i], 1023 );
+    }
+    stats_hist8( words, v, n, live );
+  }
+  __syncthreads();
+  stats_flush( words, shards );
+}
+__global__ __launch_bounds__( 256 ) void k_output_stats_sum( const uint32_t* __restrict__ shards, uint32_t* __restrict__ out )
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if( i >= STATS_WORDS ) return;
+  uint32_t acc = 0;
+  for( int k = 0; k < STATS_SHARDS; k++ ) { const uint32_t v = shards[(size_t) k * STATS_WORDS + i]; acc = i < 2048 ? acc + v : max( acc, v ); }
+  out[i] = acc;
+}
+template<bool WHOLE>
+static void launch_output_stats_as( hipStream_t s, const OutputRgbParams& p, uint32_t* shards )
+{
+  const dim3 grid( ( p.w + RGB_TW - 1 ) / RGB_TW, ( p.h + RGB_TH - 1 ) / RGB_TH );
+  switch( p.collocated & 3 )
+  {
+  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
+  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
+  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
+  default: hipLaunchKernelGGL( ( k_output_rgb<3, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
+  }
+}
+void launch_output_stats( hipStream_t s, const OutputRgbParams& p, int rgb, uint32_t* shards )
+{
+  if( rgb ) { if( ( p.w & 7 ) == 0 ) launch_output_stats_as<true>( s, p, shards ); else launch_output_stats_as<false>( s, p, shards ); return; }
+  const int items = ( ( p.w + 7 ) >> 3 ) * p.h;
+  hipLaunchKernelGGL( k_output_stats, dim3( ( items + 256 * STATS_ITER - 1 ) / ( 256 * STATS_ITER ) ), dim3( 256 ), 0, s, p.src[0], p.stride[0], p.w, p.h, shards );
+}
+void launch_output_stats_sum( hipStream_t s, const uint32_t* shards, uint32_t* out )
+{
+  hipLaunchKernelGGL( k_output_stats_sum, dim3( ( STATS_WORDS + 255 ) / 256 ), dim3( 256 ), 0, s, shards, out );
 }
 
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in

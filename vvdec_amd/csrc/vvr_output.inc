@@ -408,6 +408,42 @@ void launch_hash_combine( hipStream_t, const HashParams& p, const uint32_t* rows
     rows += p.h[c];
   }
 }
+
+// ... and launch_output_stats / launch_output_stats_sum (k_output_stats, the statistics class of k_output_rgb, k_output_stats_sum): the definition
+// of vvr.h sample by sample - the luma as it lies there, R, G, B as launch_output_rgb above stores them for VVR_OUT_RGB16 at od = bd with no
+// transform and no LUT - counted into the first copy of the words; the copies folded
+void launch_output_stats( hipStream_t, const OutputRgbParams& p, int rgb, uint32_t* shards )
+{
+  for( int j = 0; j < p.h; j++ )
+    for( int i = 0; i < p.w; i++ ) shards[std::min<int>( (uint16_t) p.src[0][(size_t) j * p.stride[0] + i], 1023 )]++;
+  if( !rgb ) return;
+  const size_t count = (size_t) p.w * p.h;
+  std::vector<uint16_t> planes( 3 * count );
+  OutputRgbParams q = p;
+  q.format = VVR_OUT_RGB16; q.xform = nullptr; q.lut = nullptr; q.lutN = 0;
+  for( int k = 0; k < 3; k++ ) { q.direct[k] = nullptr; q.dstOff[k] = k * count * sizeof( uint16_t ); }
+  launch_output_rgb( nullptr, q, planes.data() );
+  for( size_t at = 0; at < count; at++ )
+  {
+    uint32_t top = 0;
+    for( int k = 0; k < 3; k++ )
+    {
+      const uint32_t v = planes[k * count + at];
+      top = std::max( top, v );
+      shards[2048 + k] = std::max( shards[2048 + k], v ); shards[2051 + k] = std::max( shards[2051 + k], (uint32_t) p.maxVal - v );
+    }
+    shards[1024 + top]++;
+  }
+}
+void launch_output_stats_sum( hipStream_t, const uint32_t* shards, uint32_t* out )
+{
+  for( int i = 0; i < STATS_WORDS; i++ )
+  {
+    uint32_t acc = 0;
+    for( int k = 0; k < STATS_SHARDS; k++ ) { const uint32_t v = shards[(size_t) k * STATS_WORDS + i]; acc = i < 2048 ? acc + v : std::max( acc, v ); }
+    out[i] = acc;
+  }
+}
 #endif
 
 extern "C" {
@@ -669,6 +705,38 @@ VVR_API int vvr_output_lut3d_preset( uint16_t* nodes, int n, int transfer, int p
   return VVR_OK;
 }
 
+// light levels from the statistics of a frame (vvr_stats_submit), every formula as vvr.h gives it, in double
+VVR_API int vvr_light_level( const vvr_frame_stats* st, int transfer, uint32_t percentileE4, struct vvr_light_level* out )
+{
+  if( !st || !out || st->struct_size != sizeof( vvr_frame_stats ) || st->mode != VVR_STATS_RGB || st->bit_depth < 8 || st->bit_depth > 10 || !st->samples ) return VVR_ERR_PARAMETER;
+  if( percentileE4 < 1 || percentileE4 > 10000 || ( transfer != 0 && transfer != 16 ) ) return VVR_ERR_PARAMETER;
+  const int M = ( 1 << st->bit_depth ) - 1;
+  uint64_t total = 0;
+  for( int v = 0; v < 1024; v++ ) total += st->hist_maxrgb[v];
+  if( total != st->samples ) return VVR_ERR_PARAMETER;
+  struct vvr_light_level r; memset( &r, 0, sizeof( r ) );
+  r.struct_size = sizeof( r ); r.transfer = (uint32_t) transfer;
+  uint64_t cum = 0; bool found = false;
+  for( int v = 0; v < 1024; v++ )
+  {
+    if( st->hist_maxrgb[v] ) r.max_code = (uint32_t) v;
+    cum += st->hist_maxrgb[v];
+    if( !found && cum * 10000 >= (uint64_t) percentileE4 * st->samples ) { r.pct_code = (uint32_t) v; found = true; }
+  }
+  if( transfer == 16 )
+  {
+    const PresetMath pm( 10000, 10000 );
+    auto nits = [&]( uint32_t code ) { return pm.pqEotf( (double) std::min<uint32_t>( code, M ) / M ); };
+    r.max_nits = nits( r.max_code ); r.pct_nits = nits( r.pct_code );
+    for( int k = 0; k < 3; k++ ) r.maxscl_nits[k] = nits( st->max_c[k] );
+    double sum = 0;
+    for( int v = 0; v <= M; v++ ) if( st->hist_maxrgb[v] ) sum += (double) st->hist_maxrgb[v] * nits( (uint32_t) v );
+    r.avg_nits = sum / (double) st->samples;
+  }
+  *out = r;
+  return VVR_OK;
+}
+
 VVR_API int vvr_read_output_grain( vvr_context* c, int slot, int x, int y, int w, int h, int bytesPerSample, void* const dst[3], const size_t dstStrideBytes[3] )
 {
   if( !c || slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] || !dst || !dstStrideBytes ) return VVR_ERR_PARAMETER;
@@ -860,6 +928,9 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // A hash request (vvr_hash_submit) is an entry with no destination planes: k_hash_rows and k_hash_combine leave one word per component in the
 // entry's scratch and that is all that crosses PCIe (CRC, checksum), or k_output_window packs the planes and their bytes cross (MD5: hashed by
 // the thread that calls vvr_output_wait); the digest bytes and the comparison with the SEI's are made in vvr_output_wait.
+// A statistics request (vvr_stats_submit) is an entry with no destination planes either: its scratch holds the copies of the words the workgroups
+// add into - cleared on the output stream ahead of the launch - and the words k_output_stats_sum folds them to, which are all that crosses PCIe;
+// vvr_output_wait writes the caller's vvr_frame_stats from them.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -877,6 +948,8 @@ struct OutEntry {
   int hash = 0, hashNc = 0; size_t planeBytes[3] = { 0, 0, 0 };
   uint8_t* digest = nullptr; uint32_t* mismatch = nullptr; bool verify = false; uint8_t expected[48];
   bool timed2 = false; PendingTiming timing2;      // (k_hash_combine; `timing` is k_hash_rows then)
+  // a statistics request: mode + 1 (0: none); STATS_WORDS words at the start of `host`; what vvr_output_wait writes besides them
+  int stats = 0, statsW = 0, statsH = 0; vvr_frame_stats* statsOut = nullptr;
 };
 
 static void destroyOutputQueue( vvr_context* c )
@@ -981,7 +1054,7 @@ int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blockin
 void outTake( vvr_context* c, OutEntry* e, int slot, int job, int jobFailed )
 {
   e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
-  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0;
+  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
   if( e->timed2 ) { hipEventDestroy( e->timing2.a ); hipEventDestroy( e->timing2.b ); e->timed2 = false; }
 }
@@ -1324,6 +1397,73 @@ VVR_API int vvr_hash_submit( vvr_context* c, const vvr_hash_request* rq )
   }
   return ticket;
 }
+
+VVR_API int vvr_stats_submit( vvr_context* c, const vvr_stats_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  const char* const who = "vvr_stats_submit";
+  // ---- 1. the request
+  if( rq->struct_size != sizeof( vvr_stats_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_stats_request )", who );
+  const int slot = rq->slot, bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
+  if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot", who );
+  if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1", who );
+  if( rq->mode > VVR_STATS_RGB ) return outRefuse( c, "unknown mode", who );
+  if( !rq->stats ) return outRefuse( c, "stats is NULL", who );
+  const bool rgb = rq->mode == VVR_STATS_RGB;
+  int outMatrix = 0, outFullRange = 0;      // (looked at here for the refusal, taken under mu where the request is accepted: as vvr_output_submit)
+  if( rgb )
+  {
+    { std::lock_guard<std::mutex> lk( c->mu ); outMatrix = c->outMatrix; }
+    if( nc == 1 ) return outRefuse( c, "RGB statistics of a 4:0:0 context: there is no chroma to convert", who );
+    if( !outMatrix ) return outRefuse( c, "RGB statistics with no colour description set (vvr_set_output_colour)", who );
+  }
+  const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot, not the slot)
+  if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, empty, or odd in 4:2:0", who );
+  hipSetDevice( c->device );
+  // ---- 2. a ring entry; the picture has been handed to the device
+  OutEntry* e = nullptr;
+  hipEvent_t jobDone = nullptr; int jobFailed = VVR_OK;
+  std::unique_lock<std::mutex> lk( c->mu );
+  { const int rc = outAcquire( c, who, slot, rq->job, rq->blocking != 0, lk, e, jobDone, jobFailed ); if( rc != VVR_OK ) return rc; }
+  hipStream_t s = c->outQStream;
+  if( rgb ) { outMatrix = c->outMatrix; outFullRange = c->outFullRange; }      // (what is set now, behind the waits above)
+  outTake( c, e, slot, rq->job, jobFailed );
+  e->stats = rq->mode + 1; e->statsW = w; e->statsH = h; e->statsOut = rq->stats;
+  if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
+  // ---- the entry's buffers: the copies of the words the workgroups add into, the folded words behind them; the folded words pinned
+  const size_t shardBytes = alignUp( sizeof( uint32_t ) * STATS_SHARDS * STATS_WORDS, 256 ), wordBytes = sizeof( uint32_t ) * STATS_WORDS;
+  if( outGrow( e->dev, e->devCap, shardBytes + wordBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, wordBytes, true ) != VVR_OK )
+  { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
+  // ---- 3. behind the picture (or the slot's users) on the device, 4. the clear and the kernels.  mu stays held up to the registration of the `read` event (as vvr_output_submit)
+  OQCHK( outOrder( c, e, slot, rq->job, jobDone ) );
+  OQCHK( hipMemsetAsync( e->dev, 0, shardBytes, s ) );
+  OutputRgbParams p; memset( &p, 0, sizeof( p ) );
+  for( int k = 0; k < nc; k++ ) { const int sh = k ? 1 : 0; p.src[k] = d.p[k] + (size_t) ( y >> sh ) * d.stride[k] + ( x >> sh ); p.stride[k] = d.stride[k]; }
+  p.w = w; p.h = h; p.collocated = rq->collocated & 3; p.format = RGB_FMT_STATS; p.maxVal = ( 1 << bd ) - 1;
+  if( rgb ) rgb_coefficients( outMatrix, outFullRange, bd, bd, p );      // (od = bd: the input of the transform stage)
+  outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_STATS, (double) w * h * ( rgb ? 3. : 2. ) );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma)
+  launch_output_stats( s, p, rgb ? 1 : 0, (uint32_t*) e->dev );
+  if( e->timed ) hipEventRecord( e->timing.b, s );
+  OQCHK( hipGetLastError() );
+  OQCHK( hipEventRecord( e->read, s ) );      // (the slot's reader ends here: the fold reads the entry's scratch)
+  c->slotExt[slot].push_back( e->read );
+  e->state = OQ_FLIGHT; e->queued = true;
+  outTimeBegin( c, s, e->timed2, e->timing2, K_OUTPUT_STATS_SUM, (double) wordBytes * ( STATS_SHARDS + 1 ) );
+  launch_output_stats_sum( s, (const uint32_t*) e->dev, (uint32_t*) ( e->dev + shardBytes ) );
+  if( e->timed2 ) hipEventRecord( e->timing2.b, s );
+  const int ticket = e->ticket;
+  lk.unlock();
+  // ---- the result's way to the host: the words
+  hipError_t ce = hipGetLastError();
+  if( ce == hipSuccess ) ce = hipMemcpyAsync( e->host, e->dev + shardBytes, wordBytes, hipMemcpyDeviceToHost, s );
+  if( ce == hipSuccess ) ce = hipEventRecord( e->done, s );
+  if( ce != hipSuccess )
+  {
+    hipStreamSynchronize( s );
+    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( who ) + ": copy to the host: " + hipGetErrorString( ce ) );
+  }
+  return ticket;
+}
 #undef OQCHK
 
 VVR_API int vvr_output_test( vvr_context* c, int ticket )
@@ -1353,7 +1493,7 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
   if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
   outTimeEnd( c, e->timed, e->timing );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS ...
-  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE)
+  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM)
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
   if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
   lk.unlock();
@@ -1374,6 +1514,21 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
     }
     if( e->digest ) memcpy( e->digest, dg, (size_t) e->hashNc * len );
     if( e->verify ) { uint32_t m = 0; for( int k = 0; k < e->hashNc; k++ ) if( memcmp( dg + k * len, e->expected + k * len, len ) ) m |= 1u << k; *e->mismatch = m; }
+  }
+  if( rc == VVR_OK && e->queued && e->stats )
+  {
+    // the caller's vvr_frame_stats: the header fields and the words (the minimum was accumulated as the maximum of M - v)
+    const uint32_t* w = (const uint32_t*) e->host;
+    vvr_frame_stats& st = *e->statsOut;
+    memset( &st, 0, sizeof( st ) );
+    st.struct_size = sizeof( st ); st.mode = (uint32_t) ( e->stats - 1 ); st.bit_depth = (uint32_t) c->cfg.bit_depth;
+    st.width = (uint32_t) e->statsW; st.height = (uint32_t) e->statsH; st.samples = (uint64_t) e->statsW * e->statsH;
+    memcpy( st.hist_y, w, sizeof( st.hist_y ) );
+    if( st.mode == VVR_STATS_RGB )
+    {
+      memcpy( st.hist_maxrgb, w + 1024, sizeof( st.hist_maxrgb ) );
+      for( int k = 0; k < 3; k++ ) { st.max_c[k] = w[2048 + k]; st.min_c[k] = ( ( 1u << c->cfg.bit_depth ) - 1 ) - w[2051 + k]; }
+    }
   }
   lk.lock();
   e->state = OQ_FREE; e->ticket = -1;
