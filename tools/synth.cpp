@@ -385,7 +385,7 @@ struct Gen {
     const uint32_t cuIdx = B.num_cu++;
     cu.x = x; cu.y = y; cu.w = w; cu.h = h; cu.tree = (uint8_t) curTree;
     const bool treeL = curTree == VVR_TREE_LUMA, treeC = curTree == VVR_TREE_CHROMA;
-    cu.qp = (int8_t) std::min( 63, std::max( 0, P.base_qp + (int) rng.u( 7 ) - 3 ) );
+    cu.qp = (int8_t) std::min( 63, std::max( -6 * ( bd - 8 ), P.base_qp + (int) rng.u( 7 ) - 3 ) );      // slice QP + CU deltas: -QpBdOffset .. 63
     cu.bcw_idx = 2; cu.ref_idx[0] = cu.ref_idx[1] = -1;
     const bool isI = curI;
     // (a 4x4 CU is never inter predicted: pred_mode is inferred; it only gets here in 4:0:0 pictures, where no chroma constraint forces a mode)

@@ -187,6 +187,94 @@ def vary_slices(d, seed, alf_sets=2, wp_sets=2, intra_slices=0):
     return d
 
 
+def _alf_tables(d):
+    return list(getattr(d, "alf_sets", None) or [d.alf_params])
+
+
+def alf_to_limits(d, seed, clip=None):
+    """Push the ALF tables of a generated description to the limits of the syntax: every luma / chroma coefficient drawn from {-128, 127}, every
+    CC-ALF tap at +-64 (the largest power of two the syntax codes), and the clipping values at index 0 (1 << bit depth: no clipping) in the even
+    classes / chroma alternatives and at index 3 (the tightest) in the odd ones - or, with clip = 0 or 3, at that index everywhere"""
+    rng = np.random.default_rng(seed)
+    bd = int(d.hdr.bit_depth)
+    cv = {0: 1 << bd, 3: 1 << (bd - 7)}                       # AlfClippingValues: index 0 and index 3 (8 bit: 256, 2; 10 bit: 1024, 8)
+    for a in _alf_tables(d):
+        lc, lk = np.ctypeslib.as_array(a.luma_coeff), np.ctypeslib.as_array(a.luma_clip)
+        lc[..., :12] = rng.choice(np.array([-128, 127], np.int16), lc[..., :12].shape)
+        for c in range(abi.VVR_ALF_CLASSES):
+            lk[:, c, :12] = cv[clip if clip is not None else (3 if c & 1 else 0)]
+        cc, ck = np.ctypeslib.as_array(a.chroma_coeff), np.ctypeslib.as_array(a.chroma_clip)
+        cc[:, :6] = rng.choice(np.array([-128, 127], np.int16), cc[:, :6].shape)
+        for alt in range(abi.VVR_ALF_MAX_CHR_ALT):
+            ck[alt, :6] = cv[clip if clip is not None else (3 if alt & 1 else 0)]
+        x = np.ctypeslib.as_array(a.ccalf_coeff)
+        x[..., :abi.VVR_CCALF_TAPS] = rng.choice(np.array([-64, 64], np.int16), x[..., :abi.VVR_CCALF_TAPS].shape)
+    return d
+
+
+def wp_to_limits(d, seed):
+    """Push the explicit prediction weights of a generated description to the limits of pred_weight_table(): the denominators from {0, 7} (luma and chroma
+    differ), the weight of every entry that is `present` at ( 1 << denominator ) - 128 or + 127, its offset at -128 or 127.  `present` is left as generated,
+    so the CUs' mc_mode and the BDOF / DMVR conditions stay valid"""
+    rng = np.random.default_rng(seed)
+    for k, w in enumerate(list(getattr(d, "wp_sets", None) or [d.wp])):
+        w.log2_denom[0] = 7 if (seed + k) & 1 else 0
+        w.log2_denom[1] = 7 - w.log2_denom[0]
+        for l in range(2):
+            for i in range(abi.VVR_MAX_REFS):
+                for c in range(3):
+                    e = w.e[l][i][c]
+                    den = w.log2_denom[1 if c else 0]
+                    if e.present:
+                        e.weight = (1 << den) + (127 if rng.integers(2) else -128)
+                        e.offset = 127 if rng.integers(2) else -128
+                    else:
+                        e.weight, e.offset = 1 << den, 0
+    return d
+
+
+def deblock_offsets_to_limits(d, sign):
+    """pps / ph / sh _beta_offset_div2 and _tc_offset_div2 of every component at +6 (sign > 0) or -6: the ends of the syntax range (+-12 once doubled), in the
+    picture header and in the slice headers.  (The edge tables of a description hold QPs, boundary strengths and filter lengths only: nothing to regenerate.)"""
+    v = 6 if sign > 0 else -6
+    for c in range(3):
+        d.hdr.deblock_beta_offset_div2[c] = v
+        d.hdr.deblock_tc_offset_div2[c] = v
+    if getattr(d, "slices", None) is not None:
+        d.slices["deblock_beta_offset_div2"][...] = v
+        d.slices["deblock_tc_offset_div2"][...] = v
+    return d
+
+
+def rewrite_qp(d, qps):
+    """Give the CUs of a generated single-tree description the luma QPs `qps` (one per CU, -QpBdOffset .. 63) and keep everything that follows from them
+    consistent, the way the generator derives it: TU.qp (luma: QP + QpBdOffset; chroma: identity mapping of the QP clipped to -QpBdOffset .. 63) and the QPs of
+    the edge tables (rounded mean of the two sides, LoopFilter.cpp:1363 / 1180)"""
+    qps = np.asarray(qps, np.int32)
+    assert len(qps) == len(d.cu) and not (d.cu["tree"] == abi.TREE_CHROMA).any(), "one QP per CU of a single-tree picture"
+    qpbd = 6 * (int(d.hdr.bit_depth) - 8)
+    assert qps.min() >= -qpbd and qps.max() <= 63
+    d.cu["qp"] = qps
+    t = qps[d.tu["cu"]]
+    d.tu["qp"][:, 0] = t + qpbd
+    d.tu["qp"][:, 1] = d.tu["qp"][:, 2] = np.clip(t, -qpbd, 63) + qpbd
+    q4 = np.zeros((d.h4, d.w4), np.int32)
+    for cu, q in zip(d.cu, qps):
+        q4[int(cu["y"]) >> 2:(int(cu["y"]) + int(cu["h"]) + 3) >> 2, int(cu["x"]) >> 2:(int(cu["x"]) + int(cu["w"]) + 3) >> 2] = q
+    for dr in range(2):
+        p4 = np.roll(q4, 1, axis=1 - dr)                      # the P side: the unit to the left (vertical edges) / above (horizontal edges)
+        mean = ((q4 + p4 + 1) >> 1).astype(np.int8)
+        valid = np.ones_like(q4, bool)
+        if dr == 0:
+            valid[:, 0] = False
+        else:
+            valid[0, :] = False
+        lq = d.lfp[dr]["qp"].reshape(d.h4, d.w4, 3)
+        for c in range(3):
+            lq[:, :, c][valid] = mean[valid]
+    return d
+
+
 def attach_rpr(d, refs, win=(0, 0), colloc=(1, 1)):
     """Reference picture resampling: give a generated description its vvr_rpr_params.  refs: {(list, idx): dict(ratio=(rx, ry), size=(w, h), win=(left, top))}
     names the scaled reference pictures (the description must have been generated with Params.scaled_refs naming the same ones); every other reference
@@ -228,3 +316,50 @@ def natural_picture(width, height, seed, bit_depth=10):
     cb = np.clip(y[::2, ::2].astype(np.int32) // 2 + mx // 4 + rng.integers(-6, 7, (height // 2, width // 2)), 0, mx).astype(np.uint16)
     cr = np.clip(mx - y[::2, ::2].astype(np.int32) // 2 - mx // 4 + rng.integers(-6, 7, (height // 2, width // 2)), 0, mx).astype(np.uint16)
     return [y, cb, cr]
+
+
+EXTREME_KINDS = ("checker", "steps", "flat_max", "flat_zero", "noise", "taps")
+
+
+def extreme_picture(width, height, seed, bit_depth=10, kind="checker"):
+    """A test picture at the ends of the sample range, [y, cb, cr] like natural_picture; every plane follows the rule of its kind with draws of its own
+    (chroma is never derived from luma).
+      checker    0 / max alternating from sample to sample; phase and orientation (per sample, per row, per column) drawn anew for every 16x16 block, so
+                 that fractional MVs see every alignment
+      steps      0 / max blocks of 4, 8 or 16 samples, the size and a shift of 0 or 4 samples drawn per 64x64 region: edges on and off the 8-sample grid
+      flat_max, flat_zero
+      noise      uniform over the whole range, 0 and max present in every plane
+      taps       max where the eight-tap interpolation filters are positive, 0 where they are negative (- + - + + - + - along a row, the rows that meet
+                 negative taps of the second stage inverted), shifted and inverted per 32x32 block: where an MV lines up with a block, both filter stages
+                 reach their largest over- and undershoot - more than on a checker, which the two centre taps see as + -"""
+    assert kind in EXTREME_KINDS, kind
+    rng = np.random.default_rng([seed, EXTREME_KINDS.index(kind)])
+    mx = (1 << bit_depth) - 1
+    out = []
+    for (h, w) in ((height, width), (height // 2, width // 2), (height // 2, width // 2)):
+        gy, gx = np.mgrid[0:h, 0:w]
+        if kind == "checker":
+            shape = (h // 16 + 1, w // 16 + 1)
+            up = lambda a: a.repeat(16, 0).repeat(16, 1)[:h, :w]
+            phase, orient = up(rng.integers(0, 2, shape)), up(rng.integers(0, 3, shape))
+            bit = (np.where(orient == 0, gx + gy, np.where(orient == 1, gy, gx)) + phase) & 1
+        elif kind == "steps":
+            shape = (h // 64 + 1, w // 64 + 1)
+            up = lambda a: a.repeat(64, 0).repeat(64, 1)[:h, :w]
+            l2, sx, sy, phase = up(rng.integers(2, 5, shape)), up(rng.integers(0, 2, shape)) * 4, up(rng.integers(0, 2, shape)) * 4, up(rng.integers(0, 2, shape))
+            bit = (((gx + sx) >> l2) + ((gy + sy) >> l2) + phase) & 1
+        elif kind == "taps":
+            shape = (h // 32 + 1, w // 32 + 1)
+            up = lambda a: a.repeat(32, 0).repeat(32, 1)[:h, :w]
+            sign = np.array([0, 1, 0, 1, 1, 0, 1, 0])
+            sx, sy, phase = up(rng.integers(0, 8, shape)), up(rng.integers(0, 8, shape)), up(rng.integers(0, 2, shape))
+            bit = sign[(gx + sx) & 7] ^ sign[(gy + sy) & 7] ^ phase
+        elif kind == "noise":
+            a = rng.integers(0, mx + 1, (h, w))
+            a[0, 0], a[-1, -1] = 0, mx
+            out.append(a.astype(np.uint16))
+            continue
+        else:
+            bit = np.full((h, w), 1 if kind == "flat_max" else 0)
+        out.append((bit * mx).astype(np.uint16))
+    return out
