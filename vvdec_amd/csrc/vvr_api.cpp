@@ -481,6 +481,8 @@ static int enqueuePicture( vvr_context* c, Job& job, const CommitPlan& plan, std
   // (the four launches write disjoint tiles.  Running them side by side on extra streams of the lane, forked and joined with events, was measured:
   // device-only throughput fell from 1870 to 1240 pictures/s with 4 lanes, to 970 with 8 - the cross-stream waits cost more than the overlap gives)
   // (the tiles of plain, BDOF and DMVR CUs are written on the device from the CU records: the host only counted them)
+  // (the BDOF tiles as workgroups of the DMVR launch, behind its sub-blocks, were measured as well: that launch grew from 37 to 65 us for tiles that take 21 us in a
+  // launch of their own, device-only throughput fell by 2 % - profiles/shared_launches_4k.txt)
   if( q->numMc + q->numMcDev ) timedOn( K_MC, s, q->bytes[K_MC] - q->bytesBdof, [&]{ launch_mc( s, q->pic, refs, P, q->mcItems, q->numMc, q->mcDev, q->numMcDev, 0 ); } );
   if( q->numBdofItems ) timedOn( K_MC, s, q->bytesBdof, [&]{ launch_mc( s, q->pic, refs, P, nullptr, 0, q->bdofItems, q->numBdofItems, 1 ); } );
   if( q->numDmvrItems )
@@ -496,7 +498,9 @@ static int enqueuePicture( vvr_context* c, Job& job, const CommitPlan& plan, std
   const bool lmcsOn = ( h.tool_flags & VVR_TOOL_LMCS ) != 0;
   // LMCS: the inter prediction is forward-mapped before any residual is added (DecCu.cpp:458-476) - by the motion-compensation kernels themselves
   // where they store their luma samples (lmcs_fwd_luma): no pass over the picture
-  for( int k = 0; k < 3; k++ ) if( q->numTb[k] ) timedOn( K_ITRANS, s, q->bytesTb[k], [&]{ launch_itrans( s, q->pic, P, R, q->tbItems[k], q->numTb[k], 16 << k ); } );
+  // (VVR_SHARED_ITRANS_LAUNCH: the launch of the 16 class runs the blocks of the 32 class too, where the picture has both; their bytes are counted with it)
+  const bool tbShared = itrans_shared_launch( q->pic );
+  for( int k = 0; k < 3; k++ ) if( q->numTb[k] && !( tbShared && k == 1 ) ) timedOn( K_ITRANS, s, q->bytesTb[k] + ( tbShared && k == 0 ? q->bytesTb[1] : 0 ), [&]{ launch_itrans( s, q->pic, P, R, q->tbItems[k], q->numTb[k], 16 << k ); } );
   // INTRA stage: wavefront over the CTUs that contain intra blocks (DecLibRecon.cpp:876-911)
   {
     // ticket + one flag per unit: a picture with more units than the lane's buffer holds gets a larger one; work queued on the lane may

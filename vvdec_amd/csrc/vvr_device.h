@@ -195,13 +195,22 @@ struct PicDev {         // everything a kernel needs about one picture (passed b
   int                vpdusX, vpduLog2;
   int                w4, h4, ctus_x, ctus_y;
   const TbRec*       tbRec[3];       // the records of the transform blocks, one per TbItem of the size class (written by k_prep: launch_itrans hands its class's to the kernel)
+  int                numTb[3];       // transform blocks per size class (the records of tbRec): the launch of the 16 class takes the 32 class along (VVR_SHARED_ITRANS_LAUNCH)
 };
+
+// Build-time switch: 1 - a picture with transform blocks of the 16 and of the 32 class runs both in ONE launch (launch_itrans for the 16 class; the caller makes no
+// call for the 32 class); 0 - a launch per class, as before (-DVVR_SHARED_ITRANS_LAUNCH=0: to measure one against the other from one tree).  A picture with one of
+// the two classes only takes that class's kernel either way.
+#ifndef VVR_SHARED_ITRANS_LAUNCH
+#define VVR_SHARED_ITRANS_LAUNCH 1
+#endif
 
 struct RefSet { const pel_t* p[2 * VVR_MAX_REFS][3]; };   // reference planes indexed [list * 16 + refIdx][comp]; geometry = the current picture's
 
 // kernel launchers (vvr_kernels.hip) ----------------------------------------------------------------------------------
 void launch_mc     ( hipStream_t s, const PicDev& pic, const RefSet& refs, DevPlanes reco, const McItem* items, int numItems, const McItem* items2, int numItems2, int bdof );      // tiles of two arrays (host-written, device-written) in one launch
 void launch_itrans ( hipStream_t s, const PicDev& pic, DevPlanes reco, DevPlanes resi, const TbItem* items, int numItems, int sizeClass );
+inline bool itrans_shared_launch( const PicDev& pic ) { return VVR_SHARED_ITRANS_LAUNCH && pic.numTb[0] > 0 && pic.numTb[1] > 0; }      // the call for the 16 class launches the 32 class too
 // the deblocking edge parameters of the picture from its CU / TU records (vvr_lf_init.h): cell maps, motion of sub-block CUs, one thread per cell and direction
 void launch_lf_init( hipStream_t s, const PicDev& pic, uint32_t numCu, uint32_t numTu, struct LfCell* cell, struct LfCell* cellC, struct LfMv* mv, uint32_t* ref, const struct LfSbCell* sbCells, int numSbCells, vvr_lfp* out0, vvr_lfp* out1 );
 void launch_deblock( hipStream_t s, const PicDev& pic, DevPlanes reco, int dir );

@@ -2315,22 +2315,24 @@ constexpr int itr_cut( int maxn ) { return maxn > 32 ? 32 : maxn; }
 __device__ __forceinline__ int itr_at( int k, int j, int n ) { return ( ( ( k >> 1 ) * n + j ) << 1 ) + ( k & 1 ); }
 __device__ __forceinline__ uint32_t itr_pack( int lo, int hi ) { return ( (uint32_t) lo & 0xffffu ) | ( (uint32_t) hi << 16 ); }
 
-template<int MAXN, int NT>
-__global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 32 ? 5 : 8, 8 ) ) ) void k_itrans( PicDev pic, DevPlanes reco, DevPlanes resi, const TbRec* __restrict__ recs, int numItems )
+// The body of a block is a function of its own: k_itrans runs it with a workgroup per block, k_itrans_16_32 with a workgroup per block of the 32 class and a WAVEFRONT
+// per block of the 16 class.  tid: the lane's index among the NT lanes of the block; dqP .. lf_out: the block's own LDS (as k_itrans lays it out).  WAVE: the NT = 64
+// lanes are one wavefront of a larger workgroup - what one lane stores to LDS and another reads is ordered by the wavefront itself (its LDS operations execute in
+// order), and the body executes NO workgroup barrier: the other wavefronts of the workgroup hold blocks that take other paths and never reach the same ones.
+__device__ __forceinline__ void itr_wave_sync() { asm volatile( "s_waitcnt lgkmcnt(0)" ::: "memory" ); }
+template<int MAXN, int NT, bool WAVE>
+__device__ __forceinline__ void itrans_block( const PicDev& pic, const DevPlanes& reco, const DevPlanes& resi, const TbRec* __restrict__ recs, const int item, const int tid,
+                                              uint32_t* const dqP, uint32_t* const tmpP, uint32_t* const mvP, uint32_t* const mhP, int32_t* const lf_in, int32_t* const lf_out )
 {
+  static_assert( !WAVE || NT == 64, "a block without workgroup barriers is one wavefront" );
   constexpr int CUT = itr_cut( MAXN );
-  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t dqP[CUT * CUT / 2];      // (16-byte reads in the two passes)
-  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t tmpP[CUT * MAXN / 2];
-  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t mvP[CUT * MAXN / 2], mhP[CUT * MAXN / 2];
-  __shared__ int32_t lf_in[16], lf_out[48];
+  auto sync = [&]{ if constexpr( WAVE ) itr_wave_sync(); else __syncthreads(); };
   int16_t* const dq16 = reinterpret_cast<int16_t*>( dqP ); int16_t* const tmp16 = reinterpret_cast<int16_t*>( tmpP );
   const int16_t* const mv16 = reinterpret_cast<const int16_t*>( mvP ); const int16_t* const mh16 = reinterpret_cast<const int16_t*>( mhP );
-  const int item = blockIdx.x;
-  if( item >= numItems ) return;
   // ---- the block's record (one 16-byte load): every field the block needs - the item, its TU and CU records and the slice map are not touched
   TbRec rec;
   { const uint4 q = *reinterpret_cast<const uint4*>( &recs[item] ); rec.coef = q.x; rec.x = (uint16_t) ( q.y & 0xffff ); rec.y = (uint16_t) ( q.y >> 16 ); rec.a = q.z; rec.b = q.w; }
-  const int comp = tbr_comp( rec ), bd = pic.hdr.bit_depth, tid = threadIdx.x;
+  const int comp = tbr_comp( rec ), bd = pic.hdr.bit_depth;
   const int mts = tbr_mts( rec ), trt = tbr_tr_type( rec );
   const int scanX = tbr_scan_x( rec ), scanY = tbr_scan_y( rec ), tuQp = tbr_qp( rec );
   const int16_t* __restrict__ lev = pic.coef + rec.coef;
@@ -2463,7 +2465,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
           if( y < dqH && x < dqW ) dq16[itr_at( y, x, dqW )] = (int16_t) acc;      // (a 16-bit value: a level, or clipped)
         }
       }
-      __syncthreads();
+      sync();
       for( int i = tid; i < dqH * dqW; i += NT )
       {
         const int at = itr_at( i >> ldW, i & ( dqW - 1 ), dqW );
@@ -2501,7 +2503,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
       }
     }
   }
-  __syncthreads();
+  sync();
   // ---- LFNST
   if( lfnstOn )
   {
@@ -2510,7 +2512,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
     const int sb = whge3 ? 8 : 4;
     const int zeroOut = ( ( bw == 4 && bh == 4 ) || ( bw == 8 && bh == 8 ) ) ? 8 : 16;
     if( tid < 16 ) { const uint8_t* xy = whge3 ? d_lfnst_scan8x8_xy[tid] : d_lfnst_scan4x4_xy[tid]; lf_in[tid] = dq16[itr_at( xy[1], xy[0], dqW )]; }
-    __syncthreads();
+    sync();
     const int set = tbr_lfnst_set( rec ), idx = tbr_lfnst_idx( rec ), trSize = sb == 8 ? 48 : 16;
     if( tid < trSize )
     {
@@ -2518,7 +2520,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
       for( int i = 0; i < zeroOut; i++ ) r += lf_in[i] * ( sb == 8 ? d_lfnst8x8[set][idx][tid][i] : d_lfnst4x4[set][idx][tid][i] );
       lf_out[tid] = clip3( -32768, 32767, ( r + 64 ) >> 7 );
     }
-    __syncthreads();
+    sync();
     if( tid < sb * sb )
     {
       const int y = tid / sb, x = tid % sb;
@@ -2535,7 +2537,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
         else if( x < 4 ) *d = (int16_t) lf_out[32 + ( y - 4 ) * 4 + x];
       }
     }
-    __syncthreads();
+    sync();
   }
   // ---- inverse transform; every thread produces the final residual of its samples and emits it right away
   int dcVal = 0;
@@ -2582,7 +2584,7 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
       for( int k = 0; k < cutH; k++ ) sum += __mul24( dq16[itr_at( k, x, dqW )], mv16[itr_at( k, y, bh )] );
       tmp16[itr_at( x, y, bh )] = (int16_t) clip3( -32768, 32767, ( sum + ( 1 << ( shift1 - 1 ) ) ) >> shift1 );
     }
-    __syncthreads();
+    sync();
   }
   // ---- pass 2 (horizontal) + output
   // the residual r of sample (x, y) goes where it belongs: onto the prediction (inter blocks) or into the residual plane; joint Cb-Cr derives the second one
@@ -2684,12 +2686,56 @@ __global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 
   }
 }
 
+template<int MAXN, int NT>
+__global__ __launch_bounds__( NT ) __attribute__( ( amdgpu_waves_per_eu( MAXN > 32 ? 5 : 8, 8 ) ) ) void k_itrans( PicDev pic, DevPlanes reco, DevPlanes resi, const TbRec* __restrict__ recs, int numItems )
+{
+  constexpr int CUT = itr_cut( MAXN );
+  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t dqP[CUT * CUT / 2];      // (16-byte reads in the two passes)
+  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t tmpP[CUT * MAXN / 2];
+  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t mvP[CUT * MAXN / 2], mhP[CUT * MAXN / 2];
+  __shared__ int32_t lf_in[16], lf_out[48];
+  const int item = blockIdx.x;
+  if( item >= numItems ) return;
+  itrans_block<MAXN, NT, false>( pic, reco, resi, recs, item, threadIdx.x, dqP, tmpP, mvP, mhP, lf_in, lf_out );
+}
+
+#if VVR_SHARED_ITRANS_LAUNCH
+// The 16 and the 32 class of a picture in one launch of 128-thread workgroups: first the blocks of the 32 class, one per workgroup as in k_itrans<32, 128>; then
+// the blocks of the 16 class, two per workgroup, one per wavefront, each in its own slice of the LDS (2 x 2304 bytes inside the 8448 of a 32-class block).  Which
+// kind a workgroup is follows from its index.  The two wavefronts of a 16-class workgroup never meet at a barrier (itrans_block<.., true>); with an odd count of
+// blocks the last workgroup's second wavefront returns at once.
+__global__ __launch_bounds__( 128 ) __attribute__( ( amdgpu_waves_per_eu( 8, 8 ) ) ) void k_itrans_16_32( PicDev pic, DevPlanes reco, DevPlanes resi, int num32, int num16 )
+{
+  constexpr int D32 = 32 * 32 / 2, D16 = 16 * 16 / 2, SLICE16 = 4 * D16 + 64;      // dwords of one buffer of either class; of a 16-class block's LDS
+  __shared__ __attribute__( ( aligned( 16 ) ) ) uint32_t lds[4 * D32 + 64];
+  static_assert( 2 * SLICE16 <= 4 * D32 + 64 && ( SLICE16 * 4 ) % 16 == 0, "two 16-class blocks lie inside the LDS of a 32-class block, 16-byte aligned" );
+  const int wg = blockIdx.x;
+  if( wg < num32 )
+  {
+    itrans_block<32, 128, false>( pic, reco, resi, pic.tbRec[1], wg, threadIdx.x, lds, lds + D32, lds + 2 * D32, lds + 3 * D32, reinterpret_cast<int32_t*>( lds + 4 * D32 ), reinterpret_cast<int32_t*>( lds + 4 * D32 + 16 ) );
+    return;
+  }
+  const int wave = __builtin_amdgcn_readfirstlane( (int) ( threadIdx.x >> 6 ) ), item = 2 * ( wg - num32 ) + wave;
+  if( item >= num16 ) return;
+  uint32_t* const l = lds + wave * SLICE16;
+  itrans_block<16, 64, true>( pic, reco, resi, pic.tbRec[0], item, threadIdx.x & 63, l, l + D16, l + 2 * D16, l + 3 * D16, reinterpret_cast<int32_t*>( l + 4 * D16 ), reinterpret_cast<int32_t*>( l + 4 * D16 + 16 ) );
+}
+#endif
+
 void launch_itrans( hipStream_t s, const PicDev& pic, DevPlanes reco, DevPlanes resi, const TbItem* items, int numItems, int sizeClass )
 {
   if( !numItems ) return;
   // (the kernel reads the records k_prep wrote from the items, one per item of the class: pic.tbRec.  `items` stays in the signature, which the stand-in runtime of
   // the host tests - tests/hoststub - defines too: the caller hands over the list the records were made from)
   (void) items;
+#if VVR_SHARED_ITRANS_LAUNCH
+  // the 16 class of a picture that has blocks of the 32 class too: both in one launch (the caller then makes no call for the 32 class: itrans_shared_launch)
+  if( sizeClass <= 16 && itrans_shared_launch( pic ) )
+  {
+    hipLaunchKernelGGL( k_itrans_16_32, dim3( pic.numTb[1] + ( ( numItems + 1 ) >> 1 ) ), dim3( 128 ), 0, s, pic, reco, resi, pic.numTb[1], numItems );
+    return;
+  }
+#endif
   if( sizeClass <= 16 )      hipLaunchKernelGGL( ( k_itrans<16, 64> ),  dim3( numItems ), dim3( 64 ),  0, s, pic, reco, resi, pic.tbRec[0], numItems );
   else if( sizeClass <= 32 ) hipLaunchKernelGGL( ( k_itrans<32, 128> ), dim3( numItems ), dim3( 128 ), 0, s, pic, reco, resi, pic.tbRec[1], numItems );
   else                       hipLaunchKernelGGL( ( k_itrans<64, 256> ), dim3( numItems ), dim3( 256 ), 0, s, pic, reco, resi, pic.tbRec[2], numItems );

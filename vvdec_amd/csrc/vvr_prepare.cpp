@@ -2289,7 +2289,7 @@ void vvr_host_bind( const PrepScratch& S, vvr_prepared& q, char* base )
   q.affItems = (McItem*) at( S.iMcA ); q.numAffItems = (int) S.mcAff.size();
   q.rprItems = (McItem*) at( S.iMcR ); q.numRprItems = (int) S.mcRpr.size();
   q.numDmvr = S.numDmvr;
-  for( int k = 0; k < 3; k++ ) { q.tbItems[k] = (TbItem*) at( S.iTb[k] ); q.numTb[k] = (int) S.tb[k].size(); q.tbRecs[k] = (TbRec*) at( S.iTbRec[k] ); d.tbRec[k] = q.tbRecs[k]; }
+  for( int k = 0; k < 3; k++ ) { q.tbItems[k] = (TbItem*) at( S.iTb[k] ); q.numTb[k] = (int) S.tb[k].size(); q.tbRecs[k] = (TbRec*) at( S.iTbRec[k] ); d.tbRec[k] = q.tbRecs[k]; d.numTb[k] = q.tbRecs[k] ? q.numTb[k] : 0; }
   q.intraItems = (IntraItem*) at( S.iIntra ); q.numIntra = (int) S.intraAll.size(); q.intraLeaf = S.leaf; q.intraFine = !S.leaf && S.intraFine && !S.unitsDev.empty();
   q.units = (IntraUnit*) at( S.iUnits ); q.numActive = (int) S.unitsDev.size(); q.intraWorkgroups = S.intraWorkgroups;
   q.resiItems = (IntraItem*) at( S.iResi ); q.numResi = (int) S.resiAdd.size(); q.numLumaUnits = S.numLumaUnits; q.intraWorkgroupsChroma = S.intraWorkgroupsChroma;
