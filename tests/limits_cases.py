@@ -1,4 +1,5 @@
-"""The cases of the range-limit tests: pictures whose QPs, samples, weights and filter taps sit at the ends of what the syntax allows.
+"""The cases of the range-limit tests: pictures whose QPs, samples, weights, filter taps, reference indices and motion vectors sit at the ends of what the
+syntax allows.
 
 One table, two users: tests/test_oracle_vs_ref_limits.py pins every input on the CPU (oracle against the reference classes), tests/test_gpu_limits.py
 then runs the same inputs through the back-end against the oracle.  Nothing here touches a GPU or the reference build: a case is a builder
@@ -66,16 +67,21 @@ def holds_both_ends(planes, bd):
 
 
 class Case:
-    def __init__(self, id, family, make, present, derive_lfp=False, bd=10, cf=1, l2=7):
+    """middle: what make(extreme=False) is asserted to change - "picture": the oracle reconstructs another picture; "vectors": the stored motion vectors differ
+    and every other record is byte-identical (the decoder's clip is idempotent: the picture need not change, the case exercises the clip and nothing else).
+    found: the numbers `present` counted, for the record (a later change to the generator that empties a case shows there first)"""
+
+    def __init__(self, id, family, make, present, derive_lfp=False, bd=10, cf=1, l2=7, middle="picture"):
         self.id, self.family, self.make, self.present, self.derive_lfp, self.bd, self.cf, self.l2 = id, family, make, present, derive_lfp, bd, cf, l2
+        self.middle, self.found = middle, {}
 
 
 CASES = []
 
 
-def case(id, family, present, derive_lfp=False, bd=10, cf=1, l2=7):
+def case(id, family, present, derive_lfp=False, bd=10, cf=1, l2=7, middle="picture"):
     def reg(make):
-        CASES.append(Case(id, family, make, present, derive_lfp, bd, cf, l2))
+        CASES.append(Case(id, family, make, present, derive_lfp, bd, cf, l2, middle))
         return make
     return reg
 
@@ -483,6 +489,375 @@ _mc_case("mc_checker_noise_8bit", "mono_8bit", _mc_present, no_filters(TOOLS_I),
 _mc_case("mc_taps_8bit", "mono_8bit", _mc_present, no_filters(TOOLS_I), 3137, ("taps",), bd=8, l2=6, **MC)
 _alf_case("sao_alf_fused_ctu128_checker_400", "mono_8bit", 3133, ("checker",), None, cf=0)
 _alf_case("sao_alf_fused_ctu64_steps_8bit", "mono_8bit", 3134, ("steps", "checker"), None, l2=6, bd=8)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+# reference picture lists of up to 16 entries (VVR_MAX_REFS): indices of 2 and more, a picture at several indices of one list
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+LIST_POC = 16
+LIST_DISTS = (2, 8, 4)
+POOL_KINDS = {2: "checker", 4: "noise", 6: "steps"}      # the pool: slots 1 .. 6, the odd ones natural pictures, the even ones extreme pictures of these kinds
+
+
+def paired_lists(seed, n0, n1):
+    """two lists over six pictures, drawn with repetition: slots 1 .. 3 lie 2, 8 and 4 pictures before the current one, slots 4 .. 6 as many after it.  At every
+    index the two lists hold the two pictures of one distance, one before and one after: CUs with the same index in both lists are BDOF / DMVR candidates at
+    every index, not only at 0 and 1"""
+    rng = np.random.default_rng(seed)
+    past = {dist: (1 + k, LIST_POC - dist) for k, dist in enumerate(LIST_DISTS)}
+    future = {dist: (4 + k, LIST_POC + dist) for k, dist in enumerate(LIST_DISTS)}
+    l0, l1 = [], []
+    for i in range(abi.VVR_MAX_REFS):
+        dist = LIST_DISTS[i] if i < 3 else LIST_DISTS[int(rng.integers(3))]
+        a, b = past[dist], future[dist]
+        if i >= 3 and rng.random() < 0.4:
+            a, b = b, a
+        l0.append(a)
+        l1.append(b)
+    return l0[:n0], l1[:n1]
+
+
+def list_picture(W, H, l2, seed, tools, n0, n1, slice_type=B, bd=10, cf=1, scaled=None, **kw):
+    """one picture at POC 16 in slot 0 with the lists of paired_lists; scaled: {slot: dict(ratio=, size=)} - the pictures of the pool that have another size
+    (tests/test_oracle_vs_ref.py::rpr_case's way of attaching the table, for lists of any length)"""
+    import ctypes as C
+    l0, l1 = paired_lists(seed, n0, 0 if slice_type == P else n1)
+    scaled = scaled or {}
+    if scaled:
+        kw["scaled_refs"] = (C.c_uint16 * 2)(*[sum(1 << i for i, (slot, _) in enumerate(lst) if slot in scaled) for lst in (l0, l1)])
+    p = synth.default_params(width=W, height=H, seed=seed, tool_flags=tools, slice_type=slice_type, log2_ctu=l2, bit_depth=bd, chroma_format=cf, **kw)
+    p.poc, p.out_slot = LIST_POC, 0
+    synth.set_refs(p, l0, l1)
+    d = synth.generate(p)
+    if scaled:
+        synth.attach_rpr(d, {(l, i): scaled[slot] for l, lst in enumerate((l0, l1)) for i, (slot, _) in enumerate(lst) if slot in scaled})
+    refs = {}
+    for slot in range(1, 7):
+        w, h = scaled.get(slot, {}).get("size", (W, H))
+        pic = synth.extreme_picture(w, h, seed * 10 + slot, bit_depth=bd, kind=POOL_KINDS[slot]) if slot in POOL_KINDS else synth.natural_picture(w, h, seed * 10 + slot, bit_depth=bd)
+        refs[slot] = pic[:3 if cf else 1]
+    return d, refs
+
+
+def fold_indices(d):
+    """every reference index to index & 1 over the same lists - CU records, GPM partitions, motion field - and the loop filters off (the edge tables were drawn
+    for the other indices)"""
+    r = d.cu["ref_idx"]
+    d.cu["ref_idx"] = np.where(r >= 0, r & 1, r)
+    g = d.cu["geo_dir_ref"]
+    d.cu["geo_dir_ref"] = (g & 0xF0) | (g & 1)
+    m = d.motion["ref_idx"]
+    d.motion["ref_idx"] = np.where(m >= 0, m & 1, m)
+    d.hdr.tool_flags = no_filters(int(d.hdr.tool_flags))
+    return d
+
+
+def cu_cells(d, cu):
+    x4, y4, w4, h4 = int(cu["x"]) >> 2, int(cu["y"]) >> 2, int(cu["w"]) >> 2, int(cu["h"]) >> 2
+    return d.motion.reshape(d.h4, d.w4)[y4:y4 + h4, x4:x4 + w4]
+
+
+def cu_indices(d, cu):
+    """the (list, reference index) pairs the prediction of a CU reads: its own, those of its GPM partitions, those of its SbTMVP sub-blocks in the motion field"""
+    m = int(cu["mc_mode"])
+    if m == abi.MC_GEO:
+        return [((int(g) >> 4) - 1, int(g) & 15) for g in cu["geo_dir_ref"]]
+    if m == abi.MC_SBTMVP:
+        cells = cu_cells(d, cu)["ref_idx"].reshape(-1, 2)
+        return sorted({(l, int(v)) for l in range(2) for v in cells[:, l] if v >= 0})
+    return [(l, int(cu["ref_idx"][l])) for l in range(2) if cu["ref_idx"][l] >= 0]
+
+
+def same_picture_other_index(d):
+    """pairs of neighbouring 4x4 cells across a CU edge that refer, in one list, to the same picture through different indices: the deblocking compares pictures,
+    so these are the edges an index comparison would filter (or not) wrongly"""
+    owner = np.full((d.h4, d.w4), -1, np.int32)
+    for k, cu in enumerate(d.cu):
+        if cu["tree"] != abi.TREE_CHROMA:
+            owner[int(cu["y"]) >> 2:(int(cu["y"]) + int(cu["h"])) >> 2, int(cu["x"]) >> 2:(int(cu["x"]) + int(cu["w"])) >> 2] = k
+    idx = d.motion.reshape(d.h4, d.w4)["ref_idx"].astype(np.int32)
+    n = 0
+    for l in range(2):
+        il = idx[:, :, l]
+        poc = np.array(list(d.hdr.ref_poc[l]), np.int64)[np.maximum(il, 0)]
+        for a, b in ((np.s_[:, 1:], np.s_[:, :-1]), (np.s_[1:, :], np.s_[:-1, :])):
+            n += int(((owner[a] != owner[b]) & (il[a] >= 0) & (il[b] >= 0) & (il[a] != il[b]) & (poc[a] == poc[b])).sum())
+    return n
+
+
+MODE_NAMES = {abi.MC_UNI: "uni", abi.MC_BI: "bi", abi.MC_BDOF: "bdof", abi.MC_DMVR: "dmvr", abi.MC_DMVR_BDOF: "dmvr_bdof", abi.MC_AFFINE: "affine", abi.MC_SBTMVP: "sbtmvp", abi.MC_GEO: "gpm"}
+
+
+def _lists_present(c, d, refs, st):
+    cu = _inter(d)
+    used, high = set(), {}
+    for u in cu:
+        ix = cu_indices(d, u)
+        used.update(ix)
+        m = int(u["mc_mode"])
+        high[m] = high.get(m, 0) + (1 if max(i for _, i in ix) >= 2 else 0)
+    for l in range(2):
+        if int(d.hdr.num_ref[l]) == abi.VVR_MAX_REFS:
+            assert (l, abi.VVR_MAX_REFS - 1) in used, "index 15 of list %d is not used" % l
+    assert set(c.modes) <= set(high), (sorted(c.modes), sorted(high))
+    assert all(n > 0 for n in high.values()), "a mode without an index of 2 or more: %r" % high
+    edges = same_picture_other_index(d)
+    assert edges > 0, "no CU edge between cells that reach one picture through different indices"
+    c.found = dict(inter_cus=len(cu), cus_with_index_2_or_more=sum(1 for u in cu if max(i for _, i in cu_indices(d, u)) >= 2), highest_index=max(i for _, i in used),
+                   high_index_cus_by_mode={MODE_NAMES[m]: n for m, n in sorted(high.items())}, edges_same_picture_other_index=edges)
+    if d.wp is not None:       # one picture at two indices of a list, both used, with different weights
+        n = 0
+        for l in range(2):
+            for i in range(int(d.hdr.num_ref[l])):
+                for j in range(i):
+                    if d.hdr.ref_poc[l][i] == d.hdr.ref_poc[l][j] and (l, i) in used and (l, j) in used:
+                        n += any((int(d.wp.e[l][i][k].present), int(d.wp.e[l][i][k].weight), int(d.wp.e[l][i][k].offset)) != (int(d.wp.e[l][j][k].present), int(d.wp.e[l][j][k].weight), int(d.wp.e[l][j][k].offset)) for k in range(3))
+        assert n > 0, "no picture with two sets of weights"
+        c.found["index_pairs_one_picture_two_weights"] = n
+    if d.rpr is not None:
+        n = sum(1 for u in cu if any(i >= 2 and d.rpr.ref[l][i].scaled for l, i in cu_indices(d, u)))
+        ratios = {int(d.rpr.ref[l][i].ratio[0]) for l, i in used if i >= 2 and d.rpr.ref[l][i].scaled}
+        assert n > 0 and ratios == {1 << 13, 1 << 15}, (n, sorted(ratios))
+        c.found["cus_with_a_scaled_picture_at_index_2_or_more"] = n
+    # the high indices decide the prediction itself (before any filter): the same records with every index folded to index & 1
+    d2, refs2 = c.make(extreme=False)
+    assert differ(st(refdrv.STOP_AFTER_RECO), refdrv.oracle_reconstruct(d2, refs2, flags=refdrv.STOP_AFTER_RECO)), "the prediction does not depend on the high indices"
+
+
+def _list_case(id, tools, seed, n0, n1, modes, W=256, H=128, l2=7, bd=10, cf=1, slice_type=B, derive_lfp=False, post=None, **kw):
+    @case(id, "reference_lists", _lists_present, derive_lfp=derive_lfp, bd=bd, cf=cf, l2=l2)
+    def make(extreme=True):
+        d, refs = list_picture(W, H, l2, seed, tools, n0, n1, slice_type=slice_type, bd=bd, cf=cf, **kw)
+        if post:
+            post(d, extreme)
+        return (d if extreme else fold_indices(d)), refs
+    CASES[-1].modes = modes
+
+
+EVERY_MODE = (abi.MC_UNI, abi.MC_BI, abi.MC_BDOF, abi.MC_DMVR_BDOF, abi.MC_AFFINE, abi.MC_SBTMVP, abi.MC_GEO)
+LISTS = dict(p_intra=0.1, p_affine=0.2, p_sbtmvp=0.15, p_ciip=0.1, p_geo=0.15, p_bcw=0.2, p_bi=0.7, p_coded=0.3, p_coded_chroma=0.2, p_split_scale=1.2)
+_list_case("lists_16_16_every_inter_tool", TOOLS_A, 3401, 16, 16, EVERY_MODE, derive_lfp=True, **LISTS)
+_list_case("lists_16_9_wp_lmcs", TOOLS_A | abi.TOOL_WP | abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE, 3402, 16, 9, (abi.MC_UNI, abi.MC_BI, abi.MC_AFFINE, abi.MC_SBTMVP, abi.MC_GEO), l2=6, **LISTS)
+_list_case("lists_16_p_wp", TOOLS_A | abi.TOOL_WP, 3403, 16, 0, (abi.MC_UNI, abi.MC_AFFINE, abi.MC_SBTMVP), slice_type=P, l2=6, **LISTS)
+_list_case("lists_5_16_bdof_dmvr_small_cus", no_filters(TOOLS_DB), 3404, 5, 16, (abi.MC_BDOF, abi.MC_DMVR_BDOF), p_intra=0.0, p_bi=1.0, mv_sigma=3.0, min_cu_log2=2, p_split_scale=1.3, p_coded=0.0, p_coded_chroma=0.0)
+_list_case("lists_16_16_8bit_ctu32", TOOLS_A, 3603, 16, 16, EVERY_MODE, W=200, H=136, l2=5, bd=8, derive_lfp=True, **LISTS)
+_list_case("lists_16_16_400", TOOLS_A, 3613, 16, 16, EVERY_MODE, l2=6, cf=0, **LISTS)
+_list_case("lists_16_16_scaled_pictures_at_high_indices", no_filters(TOOLS_A), 3407, 16, 16, (abi.MC_UNI, abi.MC_BI, abi.MC_AFFINE, abi.MC_SBTMVP, abi.MC_GEO), l2=6,
+           scaled={3: dict(ratio=(1 << 13, 1 << 13), size=(128, 64)), 6: dict(ratio=(1 << 15, 1 << 15), size=(512, 256))}, **dict(LISTS, p_coded=0.0, p_coded_chroma=0.0))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+# motion vectors over the 18-bit range: beyond the window an encoder's clip leaves them in (Mv.cpp:64), up to the ends of the storage range.
+# What this family can show: for a plain block the decoder's clip and a clamped read give the same samples wherever the vector points.  The vector's size and
+# the clip's position change the result where DMVR start vectors are clipped against the CU, SbTMVP vectors against the sub-block, affine vectors per
+# sub-block and chroma at the halved vector; with scaled reference pictures (no clip at all); in the refined vectors handed back as collocated motion; in the
+# edge parameters derived on the device; and in every integer that holds position * 16 + vector on the way.
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+MV_MIN, MV_MAX = -(1 << 17), (1 << 17) - 1
+
+
+def cu_vectors(d, cu):
+    """(x, y, mvx, mvy) of the vectors the prediction of a CU starts from, with the position the clip window is taken at: the CU's own (affine: its first control
+    point), its GPM partitions', its SbTMVP sub-blocks' in the motion field"""
+    x, y, m = int(cu["x"]), int(cu["y"]), int(cu["mc_mode"])
+    if m == abi.MC_GEO:
+        return [(x, y, int(v[0]), int(v[1])) for v in cu["geo_mv"]]
+    if m == abi.MC_SBTMVP:
+        cells = cu_cells(d, cu)
+        return [(x + 4 * i, y + 4 * j, int(cells["mv"][j, i, l, 0]), int(cells["mv"][j, i, l, 1])) for j in range(0, cells.shape[0], 2) for i in range(0, cells.shape[1], 2)
+                for l in range(2) if cells["ref_idx"][j, i, l] >= 0]
+    return [(x, y, int(cu["mv"][l, 0, 0]), int(cu["mv"][l, 0, 1])) for l in range(2) if cu["ref_idx"][l] >= 0]
+
+
+def window_sides(d, x, y, mvx, mvy):
+    """through which sides a vector leaves the window of clipMvInPic (Mv.cpp:64): (left, right, top, bottom)"""
+    W, H, ctu, off = int(d.hdr.width), int(d.hdr.height), 1 << int(d.hdr.log2_ctu), 8
+    return (mvx < (-ctu - off - x + 1) * 16, mvx > (W + off - x - 1) * 16, mvy < (-ctu - off - y + 1) * 16, mvy > (H + off - y - 1) * 16)
+
+
+def _tally(d, keys):
+    """per key of `keys(cu)`: [vectors inside the window, vectors outside], and the vectors leaving per side"""
+    sides, by = [0, 0, 0, 0], {}
+    for cu in _inter(d):
+        for v in cu_vectors(d, cu):
+            s = window_sides(d, *v)
+            for k in range(4):
+                sides[k] += int(s[k])
+            for key in keys(cu):
+                by.setdefault(key, [0, 0])[1 if any(s) else 0] += 1
+    return sides, by
+
+
+def _mode_keys(cu):
+    keys = [MODE_NAMES[int(cu["mc_mode"])]]
+    if cu["flags"] & abi.CU_CIIP:
+        keys.append("ciip")
+    if cu["flags"] & abi.CU_AFFINE:
+        keys.append("affine_6p" if cu["flags"] & abi.CU_AFFINE_6P else "affine_4p")
+    return keys
+
+
+def _mv_mix_present(c, d, refs, st):
+    sides, by = _tally(d, _mode_keys)
+    assert all(n > 0 for n in sides), "no vector leaves through one of the sides (left, right, top, bottom): %r" % sides
+    for key in c.modes:
+        assert key in by and by[key][0] > 0 and by[key][1] > 0, "%s: [inside, outside] = %r" % (key, by.get(key))
+    if d.wp is not None:
+        assert any(d.wp.e[l][i][k].present for l in range(2) for i in range(2) for k in range(3))
+    if d.hdr.wrap_offset:
+        assert sides[2] > 0 and sides[3] > 0
+    c.found = dict(vectors_leaving_left_right_top_bottom=sides, inside_outside_by_mode={k: by[k] for k in sorted(by)})
+
+
+def _mv_limits_present(c, d, refs, st):
+    """each of -2^17, -2^17 + k, 2^17 - 1 - k, 2^17 - 1 (0 < k < 32) among the used vectors, horizontally and vertically"""
+    n = np.zeros((2, 4), np.int64)
+    for cu in _inter(d):
+        for v in cu_vectors(d, cu):
+            for comp in range(2):
+                m = v[2 + comp]
+                for k, hit in enumerate((m == MV_MIN, MV_MIN < m < MV_MIN + 32, MV_MAX - 32 < m < MV_MAX, m == MV_MAX)):
+                    n[comp, k] += int(hit)
+    assert (n > 0).all(), n.tolist()
+    c.found = dict(x_at_min_nearmin_nearmax_max=n[0].tolist(), y_at_min_nearmin_nearmax_max=n[1].tolist())
+
+
+def near_limit(v):
+    return v <= MV_MIN + 32 or v >= MV_MAX - 32
+
+
+def _mv_dmvr_present(c, d, refs, st):
+    """a refined vector that the clamp to the storage range can reach: a sub-block with a non-zero delta in a direction in which one of its lists starts within
+    32 units of the limit"""
+    st(0)
+    assert st.dmvr is not None and len(st.dmvr) == d.num_dmvr
+    n = moved = 0
+    for cu in _inter(d):
+        if int(cu["mc_mode"]) not in (abi.MC_DMVR, abi.MC_DMVR_BDOF):
+            continue
+        nsb = ((int(cu["w"]) + 15) // 16) * ((int(cu["h"]) + 15) // 16)
+        for dm in st.dmvr[int(cu["dmvr_off"]):int(cu["dmvr_off"]) + nsb]:
+            moved += int(dm.any())
+            n += sum(1 for comp in range(2) if dm[comp] != 0 and any(near_limit(int(cu["mv"][l, 0, comp])) for l in range(2)))
+    assert n > 0, "no refined sub-block next to the limit (%d refined at all)" % moved
+    c.found = dict(dmvr_sub_blocks=int(d.num_dmvr), refined=moved, refined_in_a_direction_next_to_the_limit=n)
+
+
+def dmvr_to_the_limit(d):
+    """one component of one list of every DMVR CU to within 32 units of an end of the range (a whole sample, the step of the integer search, more often than not), in the CU record and in its cells of the motion field; the other list
+    stays inside the picture, so the search has something to match and the refined vector can run into the clamp"""
+    k = 0
+    for i in np.nonzero((d.cu["pred_mode"] == abi.PRED_INTER) & ((d.cu["mc_mode"] == abi.MC_DMVR) | (d.cu["mc_mode"] == abi.MC_DMVR_BDOF)))[0]:
+        l, comp, neg, r = k & 1, (k >> 1) & 1, (k >> 2) & 1, (16, 1, 16, 2, 16, 4, 16, 8, 16, 32)[(k >> 3) % 10]
+        v = MV_MIN + r if neg else MV_MAX - r
+        d.cu["mv"][i, l, 0, comp] = v
+        cu_cells(d, d.cu[i])["mv"][:, :, l, comp] = v
+        k += 1
+    return d
+
+
+def _mv_rpr_present(c, d, refs, st):
+    n = out = at_end = 0
+    for cu in _inter(d):
+        if not any(d.rpr.ref[l][i].scaled for l, i in cu_indices(d, cu)):
+            continue
+        n += 1
+        vs = cu_vectors(d, cu)
+        out += int(any(any(window_sides(d, *v)) for v in vs))
+        at_end += int(any(m in (MV_MIN, MV_MAX) for v in vs for m in v[2:]))
+    assert out > 0 and at_end > 0, (n, out, at_end)
+    c.found = dict(cus_with_a_scaled_picture=n, of_those_outside_the_window=out, of_those_at_an_end_of_the_range=at_end)
+
+
+def only_the_vectors_differ(d, d2):
+    """two descriptions whose stored vectors differ and whose other records are the same bytes.  (The edge tables are left out: the generator derives the
+    boundary strengths from the stored vectors.)"""
+    def but(a, *fields):
+        b = a.copy()
+        for f in fields:
+            b[f] = 0
+        return b.tobytes()
+    assert d.cu["mv"].tobytes() != d2.cu["mv"].tobytes() or d.motion["mv"].tobytes() != d2.motion["mv"].tobytes(), "the stored vectors are the same"
+    assert but(d.cu, "mv", "geo_mv") == but(d2.cu, "mv", "geo_mv"), "CU records differ in more than their vectors"
+    assert but(d.motion, "mv") == but(d2.motion, "mv"), "the motion field differs in more than its vectors"
+    for name in ("tu", "coef", "sao", "alf", "ctu_first_cu"):
+        assert getattr(d, name).tobytes() == getattr(d2, name).tobytes(), name
+    for name in ("hdr", "alf_params", "lmcs", "wp"):
+        a, b = getattr(d, name, None), getattr(d2, name, None)
+        assert (a is None) == (b is None) and (a is None or bytes(a) == bytes(b)), name
+
+
+def _mv_case(id, present, tools, seed, modes=(), kinds=("noise", "checker"), W=256, H=128, l2=7, bd=10, cf=1, middle="vectors", derive_lfp=False, post=None, far=None, **kw):
+    far = dict(mv_sigma=300.0, mv_window=500, mv_window_ver=500) if far is None else far
+
+    @case(id, "motion_vectors", present, derive_lfp=derive_lfp, bd=bd, cf=cf, l2=l2, middle=middle)
+    def make(extreme=True):
+        k2 = dict(kw, **far)
+        if not extreme:
+            k2.update(mv_window=0, mv_window_ver=0, p_mv_limit=0.0)
+        d, refs = one_picture(W, H, l2, seed, tools, kinds, bd=bd, cf=cf, **k2)
+        if post and extreme:
+            post(d)
+        return d, refs
+    CASES[-1].modes = modes
+
+
+PLAIN = dict(p_coded=0.0, p_coded_chroma=0.0, p_intra=0.0, p_bi=0.7, p_split_scale=1.2)
+MIXED = dict(PLAIN, p_intra=0.1, p_affine=0.25, p_sbtmvp=0.15, p_ciip=0.15, p_geo=0.15, p_bi=0.6)
+MIXED_MODES = ("affine_4p", "affine_6p", "gpm", "ciip", "sbtmvp")
+_mv_case("mv_in_and_out_uni_bi_bdof_dmvr", _mv_mix_present, TOOLS_DB, 3604, ("uni", "bi", "bdof", "dmvr_bdof"), derive_lfp=True, **dict(PLAIN, p_coded=0.3, p_coded_chroma=0.2))
+_mv_case("mv_in_and_out_affine_gpm_ciip_sbtmvp_wp_ctu32", _mv_mix_present, TOOLS_A | abi.TOOL_WP, 3502, MIXED_MODES, W=200, H=136, l2=5, derive_lfp=True, **dict(MIXED, p_coded=0.3, p_coded_chroma=0.2))
+_mv_case("mv_in_and_out_affine_gpm_ciip_sbtmvp_wp_8bit", _mv_mix_present, no_filters(TOOLS_A | abi.TOOL_WP), 3503, MIXED_MODES, bd=8, l2=6, **MIXED)
+_mv_case("mv_in_and_out_affine_gpm_ciip_sbtmvp_400", _mv_mix_present, no_filters(TOOLS_A), 3602, MIXED_MODES, cf=0, l2=6, **MIXED)
+_mv_case("mv_components_at_the_limits", _mv_limits_present, no_filters(TOOLS_A), 3505, far=dict(mv_sigma=300.0, mv_window=500, mv_window_ver=500, p_mv_limit=0.2), l2=6, p_imv_hpel=0.0, **MIXED)
+_mv_case("mv_dmvr_refined_into_the_limit", _mv_dmvr_present, no_filters(TOOLS_DB), 3627, kinds=("noise", "noise"), far=dict(mv_sigma=3.0), post=dmvr_to_the_limit, p_imv_hpel=0.0,
+         **dict(PLAIN, p_bi=1.0))
+_mv_case("mv_wrap_around_vertical_lift", _mv_mix_present, no_filters(TOOLS_A), 3507, ("uni", "bi", "bdof", "dmvr_bdof"), far=dict(mv_sigma=300.0, mv_window=500, mv_window_ver=500), l2=6, wrap_offset=256,
+         **dict(PLAIN, p_affine=0.15, p_sbtmvp=0.1, p_geo=0.1))
+
+
+def _mv_rpr(name, seed, spec):
+    @case("mv_scaled_picture_%s" % name, "motion_vectors", _mv_rpr_present, l2=6)
+    def make(extreme=True):
+        from test_oracle_vs_ref import rpr_case, ALL
+        far = dict(mv_window=8200, mv_window_ver=8200) if extreme else {}
+        return rpr_case(256, 128, 6, 2, seed, [spec], tools=no_filters(ALL), p_coded=0.0, p_coded_chroma=0.0, p_intra=0.1, p_affine=0.25, p_geo=0.1, p_sbtmvp=0.15, mv_sigma=4000.0, **far)
+    CASES[-1].modes = ()
+
+
+_mv_rpr("0_5x", 3511, dict(ratio=(1 << 13, 1 << 13), size=(128, 64)))
+_mv_rpr("2x", 3512, dict(ratio=(1 << 15, 1 << 15), size=(512, 256)))
+
+def col_motion_at_the_limit():
+    """the DMVR case as a picture that stays a reference (the reference finishes the motion of such pictures only): (description, reference pictures)"""
+    d, refs = [c for c in CASES if c.id == "mv_dmvr_refined_into_the_limit"][0].make()
+    d.hdr.tool_flags |= abi.TOOL_STILL_REF
+    return d, refs
+
+
+def handed_out_on_the_limit(d, final):
+    """cells of a final motion field (4x4 raster, abi.Motion) with a component on an end of the range whose start vector in the description was not there: refined
+    vectors the clamp to the storage range caught"""
+    start = d.motion["mv"]
+    return int((np.isin(final["mv"], (MV_MIN, MV_MAX)) & ~np.isin(start, (MV_MIN, MV_MAX))).any(axis=(1, 2)).sum())
+
+
+def handed_out_beyond_the_limit(final):
+    """cells of a final motion field with a component outside the 18-bit range.  The reference clamps the refined vector it predicts with (InterPrediction.cpp:1956)
+    and not the one DecCu::TaskFinishMotionInfo stores (DecCu.cpp:191): what is handed out as collocated motion is the unclamped sum, and the back-end's is the same"""
+    return int(((final["mv"] < MV_MIN) | (final["mv"] > MV_MAX)).any(axis=(1, 2)).sum())
+
+
+def long_lists_plan(pictures=24, slots=18):
+    """a low-delay stream after an uploaded POC 0: picture k lists pictures k - 1 .. k - 16 in list 0 and the same in reverse in list 1; slots are taken round-robin,
+    so a slot is written again while up to 16 pictures in flight still read it -> (plans, number of slots)"""
+    from vvdec_amd import stream
+    plans = []
+    for k in range(1, pictures + 1):
+        past = [(j % slots, j) for j in range(k - 1, max(-1, k - 1 - abi.VVR_MAX_REFS), -1)]
+        plans.append(stream.PicPlan(poc=k, layer=0, slice_type=B, l0=[poc for _, poc in past], l1=[poc for _, poc in past[::-1]], slot=k % slots, ref_slots=(past, past[::-1])))
+    return plans, slots
+
 
 FAMILIES = sorted({c.family for c in CASES})
 

@@ -71,6 +71,27 @@ API int vvr_submit( vvr_context* c, const vvr_picture* pic )
   std::lock_guard<std::mutex> lk( c->mu );
   const vvr_pic_header& h = pic->hdr;
   if( h.out_slot < 0 || h.out_slot >= (int) c->slots.size() ) { c->err = "bad output slot"; return VVR_ERR_PARAMETER; }
+  // motion vectors are 18-bit quantities: what vvr_prepare refuses (vvdec_amd/csrc/vvr_prepare.cpp, "18-bit range") is refused here, vector for vector
+  {
+    auto out = []( int32_t v ) { return v < -( 1 << 17 ) || v > ( 1 << 17 ) - 1; };
+    const int w4 = ( h.width + 3 ) >> 2;
+    for( uint32_t k = 0; k < pic->num_cu; k++ )
+    {
+      const vvr_cu& u = pic->cu[k];
+      if( u.pred_mode != VVR_PRED_INTER ) continue;
+      const bool geo = u.mc_mode == VVR_MC_GEO, sbt = u.mc_mode == VVR_MC_SBTMVP, aff = u.mc_mode == VVR_MC_AFFINE;
+      bool bad = false;
+      for( int l = 0; l < 2; l++ ) if( u.ref_idx[l] >= 0 && !geo && !sbt ) for( int cp = 0; cp < ( aff ? ( ( u.flags & VVR_CU_AFFINE_6P ) ? 3 : 2 ) : 1 ); cp++ ) bad |= out( u.mv[l][cp][0] ) || out( u.mv[l][cp][1] );
+      if( geo ) for( int i = 0; i < 2; i++ ) bad |= out( u.geo_mv[i][0] ) || out( u.geo_mv[i][1] );
+      if( pic->motion && ( sbt || ( aff && !( h.tool_flags & VVR_TOOL_AFFINE_MV_ON_DEVICE ) ) ) )
+        for( int y = 0; y < u.h; y += 4 ) for( int x = 0; x < u.w; x += 4 )
+        {
+          const vvr_motion& m = pic->motion[(size_t) ( ( u.y + y ) >> 2 ) * w4 + ( ( u.x + x ) >> 2 )];
+          for( int l = 0; l < 2; l++ ) if( ( sbt ? m.ref_idx[l] : u.ref_idx[l] ) >= 0 ) bad |= out( m.mv[l][0] ) || out( m.mv[l][1] );
+        }
+      if( bad ) { c->err = "motion vector outside the 18-bit range"; return VVR_ERR_PARAMETER; }
+    }
+  }
   vvr_picture P = *pic;
   std::vector<vvr_cu> cuCopy;
   if( const char* e = getenv( "VVR_ORACLE_NO_DMVR" ) )      // developer aid: 1 = every DMVR CU predicted without the refinement; 2 = only those whose MVs leave the picture by more than a CTU

@@ -104,6 +104,7 @@ def a_4k_frame_direct_and_laid_out():
             full = [torch.full((r, n + pad), -1, dtype=torch.int16, device="cuda") for r, n in shapes]
             into = [f[:, :n] for f, (r, n) in zip(full, shapes)]
             assert all(t.is_contiguous() == (pad == 0) for t in into)
+            torch.cuda.synchronize()       # (the fill runs on torch's stream, the request on the context's: a destination must be idle when it is submitted)
             got = rec.output_wait(rec.output_submit(0, window=win, fmt="p010", into=into))
             for k in range(2):
                 host = full[k].cpu().numpy().view(np.uint16)

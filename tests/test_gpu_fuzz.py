@@ -1,8 +1,9 @@
 """GPU (-m gpu): the RANDOMISED leg of the parity suite.  Every other GPU case is a fixed seed; here the seeds change with every build of the kernels, so that
 each run of the suite covers pictures and streams no run before it has seen:
   * generated pictures from the parameter space of tools/fuzz_oracle_vs_ref.py (tool switches, picture and CTU sizes, sample formats, split / residual densities,
-    MV spreads incl. the `far` mode with vectors of thousands of samples and reference wrap-around), reconstructed through the C ABI on the HIP path and compared
-    with the CPU oracle on the same reference pictures;
+    MV spreads incl. the `far` mode - vectors up to thousands of samples beyond the encoder's clip window in both directions, with and without reference
+    wrap-around, sometimes with components at the ends of the 18-bit range - and, for a quarter of the pictures, reference lists of 3 .. 16 entries),
+    reconstructed through the C ABI on the HIP path and compared with the CPU oracle on the same reference pictures;
   * bitstreams written by tools/mini_vvenc.py with mutated tool mixes, decoded by the reference's application on the DROP-IN library with the HIP back-end behind
     vvdec::DecLibRecon: output MD5 == the reference decoder's (oracle/_ref/vvdecapp_ref).
 The seed is the MD5 of the kernel sources (VVR_FUZZ_SEED overrides it: a failure prints the seed it ran with)."""
@@ -63,6 +64,10 @@ def _case(rnd, far):
         off = W - 8 * rnd.randrange(5)
         if rnd.random() < 0.6 and off >= (1 << l2) + 16 and not (tools & abi.TOOL_IBC):
             kw["wrap_offset"] = off
+        kw["mv_window_ver"] = rnd.choice([0, 500, 2000, 7000])         # (( H + window ) * 16 stays inside the 18-bit MV range)
+        if rnd.random() < 0.3:
+            kw["p_mv_limit"] = rnd.choice([0.05, 0.3])                  # components at the ends of that range
+    lists = (rnd.randrange(3, abi.VVR_MAX_REFS + 1), rnd.randrange(3, abi.VVR_MAX_REFS + 1)) if rnd.random() < 0.25 else None       # reference lists of 3 .. 16 entries
     bd = rnd.choice([8, 10, 10]); cf = rnd.choice([1, 1, 1, 0])
     if not cf:
         tools &= ~abi.TOOL_LMCS_CSCALE
@@ -70,7 +75,7 @@ def _case(rnd, far):
         tools |= abi.TOOL_LMCS
     if (tools & abi.TOOL_AFFINE_MV_ON_DEVICE) and not (tools & abi.TOOL_LFP_ON_DEVICE):
         tools &= ~abi.TOOL_AFFINE_MV_ON_DEVICE
-    return dict(W=W, H=H, l2=l2, idx=idx, seed=seed, tools=tools, bd=bd, cf=cf, kw=kw)
+    return dict(W=W, H=H, l2=l2, idx=idx, seed=seed, tools=tools, bd=bd, cf=cf, kw=kw, lists=lists)
 
 
 def test_gpu_fuzz_slice(built):
@@ -86,9 +91,11 @@ def test_gpu_fuzz_slice(built):
     while n < int(os.environ.get("VVR_FUZZ_PICTURES", "300")) and time.time() - t0 < budget:
         c = _case(rnd, far=(n % 3 == 2))
         pl = plans[c["idx"]]
+        if c["lists"] and pl.slice_type != abi.SLICE_I:
+            pl = stream.with_longer_lists(pl, c["lists"][0], c["lists"][1], nslots, random.Random(c["seed"]))
         key = (c["W"], c["H"], c["l2"], c["bd"], c["cf"])
         if key not in ctxs:
-            ctxs[key] = vvdec_amd.Reconstructor(c["W"], c["H"], num_slots=nslots, num_streams=1, host_threads=0, log2_ctu=c["l2"], bit_depth=c["bd"], chroma_format=c["cf"])
+            ctxs[key] = vvdec_amd.Reconstructor(c["W"], c["H"], num_slots=nslots + stream.LONGER_LISTS_POOL, num_streams=1, host_threads=0, log2_ctu=c["l2"], bit_depth=c["bd"], chroma_format=c["cf"])
         rec = ctxs[key]
         ncomp = 3 if c["cf"] else 1
         try:

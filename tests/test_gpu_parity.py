@@ -14,11 +14,12 @@ pytestmark = pytest.mark.gpu
 TOOLS = abi.TOOL_SAO_LUMA | abi.TOOL_SAO_CHROMA | abi.TOOL_ALF | abi.TOOL_CCALF | abi.TOOL_DEP_QUANT | abi.TOOL_MTS
 
 
-def _run_stream(W, H, frames, gop, seed, tools, streams=2, log2_ctu=7, check=True, intra=False, bit_depth=10, chroma_format=1, post=None, kernels=None, seed_picture=None, **kw):
+def _run_stream(W, H, frames, gop, seed, tools, streams=2, log2_ctu=7, check=True, intra=False, bit_depth=10, chroma_format=1, post=None, kernels=None, seed_picture=None, plan=None, **kw):
     """intra=False: POC 0 is an uploaded picture and all CUs are inter; intra=True: POC 0 is an I picture reconstructed by the
-    back-end and the B pictures contain intra CUs (p_intra).  seed_picture: the uploaded picture ([y, cb, cr]; default: synth.natural_picture of the seed)."""
+    back-end and the B pictures contain intra CUs (p_intra).  seed_picture: the uploaded picture ([y, cb, cr]; default: synth.natural_picture of the seed).
+    plan: (plans, number of slots) of the caller's making instead of the random-access plan of `frames` and `gop`."""
     import vvdec_amd
-    plans, nslots = stream.ra_plan(frames, gop=gop, seed_poc0_is_external=not intra)
+    plans, nslots = plan if plan is not None else stream.ra_plan(frames, gop=gop, seed_poc0_is_external=not intra)
     ncomp = 3 if chroma_format else 1
     geo = dict(log2_ctu=log2_ctu, bit_depth=bit_depth, chroma_format=chroma_format)
     rec = vvdec_amd.Reconstructor(W, H, num_slots=nslots, num_streams=streams, host_threads=3, **geo)     # pictures prepared by worker threads

@@ -742,6 +742,16 @@ def test_malformed_descriptions_are_rejected(stub):
     _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, "ref_idx")
     d = mk(plans[1], p_intra=0.0); k = int(np.nonzero(d.cu["ref_idx"][:, 0] >= 0)[0][0]); d.cu["mv"][k][0][0] = (1 << 17, 0)
     _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, "18-bit range")
+    AFF = dict(tools=TOOLS | abi.TOOL_PROF, p_intra=0.0, p_affine=0.5, p_geo=0.3, p_sbtmvp=0.3)
+    first = lambda d, mode, extra=True: int(np.nonzero((d.cu["mc_mode"] == mode) & extra)[0][0])
+    d = mk(plans[1], **AFF); k = first(d, abi.MC_AFFINE, (d.cu["flags"] & abi.CU_AFFINE_6P) != 0); l = 0 if d.cu["ref_idx"][k][0] >= 0 else 1; d.cu["mv"][k][l][2] = (0, -(1 << 17) - 1)
+    _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, "control-point vector outside the 18-bit range")
+    d = mk(plans[1], **AFF); k = first(d, abi.MC_GEO); d.cu["geo_mv"][k][1] = (1 << 17, 0)
+    _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, "partition vector outside the 18-bit range")
+    for mode, text in ((abi.MC_SBTMVP, "SbTMVP CU: sub-block vector"), (abi.MC_AFFINE, "affine CU: sub-block vector")):      # the last cell of the CU, in a list the cell uses
+        d = mk(plans[1], **AFF); k = first(d, mode); cell = d.motion.reshape(d.h4, d.w4)[(int(d.cu["y"][k]) + int(d.cu["h"][k]) - 4) >> 2, (int(d.cu["x"][k]) + int(d.cu["w"][k]) - 4) >> 2]
+        l = 0 if cell["ref_idx"][0] >= 0 else 1; cell["mv"][l] = (0, 1 << 17)
+        _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, text)
     d = mk(plans[1], p_intra=0.0); d.cu["mc_mode"][0] = 77
     _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, "mc_mode")
     d = mk(plans[1], p_intra=0.0); d.cu["w"][0] = 4; d.cu["h"][0] = 4

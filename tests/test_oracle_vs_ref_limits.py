@@ -1,5 +1,6 @@
 """CPU: the plain-C oracle against the real reference classes at the ends of the value ranges - QPs from -QpBdOffset to 63, reference pictures that alternate
-between 0 and the largest sample value, prediction weights, ALF / CC-ALF taps and deblocking offsets at the limits of their syntax (tests/limits_cases.py).
+between 0 and the largest sample value, prediction weights, ALF / CC-ALF taps and deblocking offsets at the limits of their syntax, reference lists of 16 entries,
+motion vectors over the 18-bit range (tests/limits_cases.py).
 Every input of tests/test_gpu_limits.py is pinned here first, so a GPU failure there says that the kernel is wrong, not the oracle.  Skipped where oracle/_ref
 is not built, like tests/test_oracle_vs_ref.py."""
 import numpy as np
@@ -39,12 +40,33 @@ def test_oracle_equals_reference_at_the_limits(built, case):
 @pytest.mark.parametrize("case", lc.CASES, ids=[c.id for c in lc.CASES])
 def test_the_limits_matter(built, case):
     """every case can fail: with its subject moved back to the middle of the range - reference pictures clamped to the middle half, the table as the generator
-    drew it, QP 32, levels as drawn - the oracle reconstructs another picture"""
+    drew it, QP 32, levels as drawn, reference indices folded to 0 and 1, vectors inside the encoder's clip window - the oracle reconstructs another picture.
+    Where the decoder clips the vectors the clip is idempotent and the picture need not change (Case.middle == "vectors"): there the stored vectors differ and
+    every other record is the same byte for byte - the case exercises the clip, not another picture"""
     d, refs = case.make()
-    final = refdrv.oracle_reconstruct(d, refs)
     d2, refs2 = case.make(extreme=False)
+    if case.middle == "vectors":
+        lc.only_the_vectors_differ(d, d2)
+        return
+    final = refdrv.oracle_reconstruct(d, refs)
     other = refdrv.oracle_reconstruct(d2, refs2)
     assert lc.differ(final, other), "the picture does not depend on its extreme"
+
+
+def test_collocated_motion_at_the_limit_on_the_cpu(built):
+    """the input of tests/test_gpu_limits.py::test_limits_collocated_motion_at_the_limit: the oracle's planes and DMVR delta MVs are the reference's, and the
+    reference's final motion field alone holds refined vectors that arrive on an end of the 18-bit range from a start vector beside it - and vectors beyond it:
+    the reference clamps the refined vector it predicts with, not the one it stores (limits_cases.handed_out_beyond_the_limit)"""
+    d, refs = lc.col_motion_at_the_limit()
+    nd = d.num_dmvr
+    planes, motion = refdrv.reconstruct_with_motion(d, refs, flags=0)
+    got = refdrv.oracle_reconstruct(d, refs)
+    assert not lc.differ(got, planes)
+    assert np.array_equal(refdrv.oracle_dmvr(nd), refdrv.reconstruct(d, refs, want_dmvr=nd)["dmvr"][:nd])
+    n = lc.handed_out_on_the_limit(d, motion)
+    beyond = lc.handed_out_beyond_the_limit(motion)
+    print("cells of the final motion field on the limit whose start vector was not: %d; beyond the limit (stored unclamped by the reference): %d" % (n, beyond))
+    assert n > 0 and beyond > 0
 
 
 @pytest.mark.parametrize("name,kind,tools,seed", lc.STREAMS, ids=[x[0] for x in lc.STREAMS])

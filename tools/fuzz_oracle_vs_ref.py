@@ -1,5 +1,5 @@
 """developer helper: randomised sweep of the generator's parameter space (tools, sizes, CTU sizes, sample formats, stage) comparing the
-plain-C oracle with the reference decoder's own classes (oracle/_ref).  Usage: tools/fuzz_oracle_vs_ref.py <seed> <seconds> [far]   (far: motion vectors up to thousands of samples, reference wrap-around in 6 pictures of 10).
+plain-C oracle with the reference decoder's own classes (oracle/_ref).  Usage: tools/fuzz_oracle_vs_ref.py <seed> <seconds> [far]   (far: motion vectors up to thousands of samples beyond the clip window in both directions, components at the ends of the 18-bit range, reference wrap-around in 6 pictures of 10; a quarter of the pictures have reference lists of 3 .. 16 entries).
 Round 1: 4 x 200 s = 33 800 pictures, no mismatch.  Round 4 (after the two wrap-around findings): 2 x 600 s `far` = 54 811 pictures and 600 s without = 26 173
 pictures, no mismatch (2 pictures refused by the reference: an 8-bit LMCS model of the generator that breaks the LmcsPivot constraint, Reshape.cpp:363)."""
 import sys, random, time
@@ -11,7 +11,7 @@ from vvdec_amd import abi, synth, stream
 BASE = (abi.TOOL_SAO_LUMA | abi.TOOL_SAO_CHROMA | abi.TOOL_ALF | abi.TOOL_CCALF | abi.TOOL_DEP_QUANT | abi.TOOL_MTS | abi.TOOL_LFNST | abi.TOOL_BDOF | abi.TOOL_DMVR | abi.TOOL_PROF)
 OPT = [abi.TOOL_LMCS, abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE, abi.TOOL_JCCR_SIGN, abi.TOOL_CCLM_COLLOC, abi.TOOL_WP, abi.TOOL_SCALING_LIST, abi.TOOL_SCALING_LIST | abi.TOOL_SCALING_LIST_NO_LFNST,
        abi.TOOL_IMPLICIT_MTS, abi.TOOL_IBC, abi.TOOL_STILL_REF]
-plans, _ = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
+plans, NSLOTS = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
 def sweep(seed, seconds=None, cases=None):
   rnd = random.Random(seed)
   t_end = time.time() + (seconds or 1e9)
@@ -37,10 +37,14 @@ def sweep(seed, seconds=None, cases=None):
           kw["mv_sigma"] = rnd.choice([300.0, 1500.0, 6000.0]); kw["mv_window"] = rnd.choice([500, 2000, 7000])          # ((W + window) * 16 stays inside the 18-bit MV range)
           off = W - 8 * rnd.randrange(5)
           if rnd.random() < 0.6 and off >= (1 << l2) + 16 and not (tools & abi.TOOL_IBC): kw["wrap_offset"] = off
+          kw["mv_window_ver"] = rnd.choice([0, 500, 2000, 7000])         # (without wrap-around mv_window lifts the horizontal clip too; this one the vertical clip)
+          if rnd.random() < 0.3: kw["p_mv_limit"] = rnd.choice([0.05, 0.3])      # components at the ends of the 18-bit range
+      lists = (rnd.randrange(3, abi.VVR_MAX_REFS + 1), rnd.randrange(3, abi.VVR_MAX_REFS + 1)) if rnd.random() < 0.25 else None       # reference lists of 3 .. 16 entries
       bd = rnd.choice([8, 10, 10]); cf = rnd.choice([1, 1, 1, 0])
       if not cf: tools &= ~abi.TOOL_LMCS_CSCALE
       if (tools & abi.TOOL_LMCS_CSCALE) and not (tools & abi.TOOL_LMCS): tools |= abi.TOOL_LMCS
       pl = plans[idx]
+      if lists and pl.slice_type != abi.SLICE_I: pl = stream.with_longer_lists(pl, lists[0], lists[1], NSLOTS, random.Random(seed))
       try:
           d = synth.picture_for_plan(pl, W, H, seed=seed, tool_flags=tools, log2_ctu=l2, bit_depth=bd, chroma_format=cf, **kw)
           refs = {}
@@ -53,10 +57,10 @@ def sweep(seed, seconds=None, cases=None):
           n += 1
           if any(diff):
               bad += 1
-              print("MISMATCH", dict(W=W, H=H, l2=l2, idx=idx, seed=seed, tools=hex(tools), bd=bd, cf=cf, fl=fl, kw=kw), diff, flush=True)
+              print("MISMATCH", dict(W=W, H=H, l2=l2, idx=idx, seed=seed, tools=hex(tools), bd=bd, cf=cf, fl=fl, kw=kw, lists=lists), diff, flush=True)
       except Exception as e:
           n += 1; bad += 1
-          print("EXC", repr(e)[:300], dict(W=W, H=H, l2=l2, idx=idx, seed=seed, tools=hex(tools), bd=bd, cf=cf, kw=kw), flush=True)
+          print("EXC", repr(e)[:300], dict(W=W, H=H, l2=l2, idx=idx, seed=seed, tools=hex(tools), bd=bd, cf=cf, kw=kw, lists=lists), flush=True)
   return n, bad
 
 

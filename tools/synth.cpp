@@ -83,7 +83,11 @@ typedef struct vvs_params {
   uint16_t scaled_refs[2];      // reference picture resampling: bit i of [l] = reference picture i of list l is a scaled one (vvr_rpr_ref.scaled; the caller attaches
                                 // the table): CUs predicting from it take no BDOF / DMVR (InterPrediction.cpp:1431-1435) and their MVs are left as drawn
   uint16_t mv_window;           // with wrap_offset: how many luma samples an MV may point beyond the window clipMv leaves it in (0: two CTUs + 64, within one wrap period of
-                                // the margins); a parsed stream may carry vectors several periods out - e.g. 2000 to generate those
+                                // the margins); a parsed stream may carry vectors several periods out - e.g. 2000 to generate those.  Without wrap_offset: how many
+                                // luma samples an MV may point beyond clipMv's window to the left / right (0: none - the vectors a conforming encoder's clip leaves)
+  uint16_t mv_window_ver;       // the same above / below, with and without wrap_offset (0: none)
+  float    p_mv_limit;          // of the components of a drawn vector (per list, per direction): replaced by one of -2^17, -2^17 + k, 2^17 - 1 - k, 2^17 - 1 with k < 32, the
+                                // ends of the 18-bit MV storage range; draws of a generator of its own, so the rest of the picture stays as it is without them
 } vvs_params;
 
 typedef struct vvs_buffers {     // caller-allocated, sized with vvs_bounds()
@@ -131,7 +135,7 @@ void vvs_default_params( vvs_params* P )
 namespace {
 
 struct Gen {
-  const vvs_params& P; vvs_buffers& B; Rng rng;
+  const vvs_params& P; vvs_buffers& B; Rng rng; Rng rngLim;      // rngLim: the draws of p_mv_limit only
   int W, H, w4, h4, ctu, bd;
   std::vector<int32_t> cuOf4;      // per 4x4: CU index
   std::vector<int32_t> tuOf4;      // per 4x4: TU index
@@ -140,7 +144,7 @@ struct Gen {
   bool curI = false;               // the CTU being generated lies in an I slice (or the picture is an I picture)
   int modeType = 0;                // mode constraint of the current sub-tree (SCIPU): 0 all, 1 inter only, 2 intra only (local dual tree)
   bool cclmOk = true;              // CCLM allowed for the chroma CUs being added (CU::checkCCLMAllowed, UnitTools.cpp:3439)
-  Gen( const vvs_params& p, vvs_buffers& b ) : P( p ), B( b ), rng( p.seed ) {}
+  Gen( const vvs_params& p, vvs_buffers& b ) : P( p ), B( b ), rng( p.seed ), rngLim( p.seed ^ 0x6C696D6974ull ) {}
 
   // slices and tiles: index of every CTU; two positions see each other (intra availability, CIIP neighbours: CodingStructure::getCURestricted)
   // only inside one slice and one tile; the loop filters additionally obey the pps_loop_filter_across_* flags
@@ -321,14 +325,23 @@ struct Gen {
     if( x < 2 * ctu ) mv[0] -= (int32_t) rng.u( (uint32_t) reach );
     else if( x + w > W - 2 * ctu ) mv[0] += (int32_t) rng.u( (uint32_t) reach );
   }
-  void clipMv( int32_t mv[2], int x, int y ) const   // clipMvInPic, Mv.cpp:64 (with wrap-around the stream may carry MVs beyond it: kept inside a wider window)
+  static int32_t storageMv( int32_t v ) { return std::min( ( 1 << 17 ) - 1, std::max( -( 1 << 17 ), v ) ); }     // Mv::clipToStorageBitDepth
+  // clipMvInPic, Mv.cpp:64.  The stream may carry MVs beyond it - the decoder clips, or with wrap-around and scaled references takes them as they are: mv_window /
+  // mv_window_ver keep them inside a wider window, p_mv_limit puts components at the ends of the 18-bit storage range, which bounds every vector
+  void clipMv( int32_t mv[2], int x, int y )
   {
     const int off = 8;
-    const int beyond = P.wrap_offset ? ( P.mv_window ? P.mv_window : 2 * ctu + 64 ) : 0;
+    const int beyond = P.wrap_offset ? ( P.mv_window ? P.mv_window : 2 * ctu + 64 ) : P.mv_window, beyondV = P.mv_window_ver;
     const int horMax = ( W + off - x - 1 + beyond ) * 16, horMin = ( -ctu - off - x + 1 - beyond ) * 16;
-    const int verMax = ( H + off - y - 1 ) * 16, verMin = ( -ctu - off - y + 1 ) * 16;
+    const int verMax = ( H + off - y - 1 + beyondV ) * 16, verMin = ( -ctu - off - y + 1 - beyondV ) * 16;
     mv[0] = std::min( horMax, std::max( horMin, mv[0] ) );
     mv[1] = std::min( verMax, std::max( verMin, mv[1] ) );
+    if( P.p_mv_limit > 0 ) for( int k = 0; k < 2; k++ ) if( rngLim.p( P.p_mv_limit ) )
+    {
+      const int which = (int) rngLim.u( 4 ), d = 1 + (int) rngLim.u( 31 );
+      mv[k] = which == 0 ? -( 1 << 17 ) : which == 1 ? -( 1 << 17 ) + d : which == 2 ? ( 1 << 17 ) - 1 - d : ( 1 << 17 ) - 1;
+    }
+    mv[0] = storageMv( mv[0] ); mv[1] = storageMv( mv[1] );
   }
 
   void genLevels( vvr_tu& tu, int c, int bw, int bh, bool ts, bool bdpcm, bool lfnst )
@@ -481,7 +494,7 @@ struct Gen {
         for( int l = 0; l < 2; l++ )
         {
           if( cu.ref_idx[l] < 0 ) continue;
-          for( int k = 1; k < 3; k++ ) { cu.mv[l][k][0] = cu.mv[l][0][0] + rng.laplace( spread ); cu.mv[l][k][1] = cu.mv[l][0][1] + rng.laplace( spread ); }
+          for( int k = 1; k < 3; k++ ) { cu.mv[l][k][0] = storageMv( cu.mv[l][0][0] + rng.laplace( spread ) ); cu.mv[l][k][1] = storageMv( cu.mv[l][0][1] + rng.laplace( spread ) ); }
           if( rng.p( 0.05 ) ) for( int k = 1; k < 3; k++ ) { cu.mv[l][k][0] = cu.mv[l][0][0]; cu.mv[l][k][1] = cu.mv[l][0][1]; }    // all equal: PROF off
         }
       }

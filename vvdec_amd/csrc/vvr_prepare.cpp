@@ -426,6 +426,7 @@ int vvr_host_validate_header( const vvr_config& cfg, const vvr_picture* p, std::
   return VVR_OK;
 }
 
+static inline bool mvInRange( int32_t v ) { return v >= -( 1 << 17 ) && v <= ( 1 << 17 ) - 1; }      // Mv::clipToStorageBitDepth
 // the CU / TU records (0.3 ms for a 4K picture): by the thread that builds the picture's work lists
 // the CU / TU records [cu0, cu1) (a picture's records are checked in one go, or in parts by the threads that build its work lists in parts);
 // area[0 / 1]: luma / chroma area the CUs of the range cover
@@ -525,7 +526,20 @@ static int validate_records_range( const vvr_picture* p, uint32_t cu0, uint32_t 
       // motion vectors are 18-bit quantities (Mv::clipToStorageBitDepth, Mv.h; the refined vectors of DMVR are clamped to that range and the padded local
       // copy holds +-2 samples around the START vector: beyond the range the reference itself stops, InterPrediction.cpp:1768)
       for( int l = 0; l < 2; l++ ) if( cu.ref_idx[l] >= 0 && !isGeo && !isSbt ) for( int k = 0; k < 2; k++ )
-        if( cu.mv[l][0][k] < -( 1 << 17 ) || cu.mv[l][0][k] > ( 1 << 17 ) - 1 ) FAIL( VVR_ERR_PARAMETER, "motion vector outside the 18-bit range" );
+        if( !mvInRange( cu.mv[l][0][k] ) ) FAIL( VVR_ERR_PARAMETER, "motion vector outside the 18-bit range" );
+      // the same for every other vector the prediction or the edge derivation reads: control points 1 and 2 of affine CUs (2: six-parameter models), the vectors
+      // of the GPM partitions, and the motion field where the kernels take the sub-block vectors from it (SbTMVP; affine unless the device spans them)
+      if( isAff ) for( int l = 0; l < 2; l++ ) if( cu.ref_idx[l] >= 0 ) for( int cp = 1; cp < ( ( cu.flags & VVR_CU_AFFINE_6P ) ? 3 : 2 ); cp++ )
+        if( !mvInRange( cu.mv[l][cp][0] ) || !mvInRange( cu.mv[l][cp][1] ) ) FAIL( VVR_ERR_PARAMETER, "affine CU: control-point vector outside the 18-bit range" );
+      if( isGeo ) for( int k = 0; k < 2; k++ )
+        if( !mvInRange( cu.geo_mv[k][0] ) || !mvInRange( cu.geo_mv[k][1] ) ) FAIL( VVR_ERR_PARAMETER, "GPM CU: partition vector outside the 18-bit range" );
+      if( isSbt || ( isAff && !( h.tool_flags & VVR_TOOL_AFFINE_MV_ON_DEVICE ) ) )
+        for( int y = 0; y < cu.h; y += 4 ) for( int x = 0; x < cu.w; x += 4 )
+        {
+          const vvr_motion& m = p->motion[(size_t) ( ( cu.y + y ) >> 2 ) * ( ( h.width + 3 ) >> 2 ) + ( ( cu.x + x ) >> 2 )];
+          for( int l = 0; l < 2; l++ ) if( ( isSbt ? m.ref_idx[l] : cu.ref_idx[l] ) >= 0 && ( !mvInRange( m.mv[l][0] ) || !mvInRange( m.mv[l][1] ) ) )
+            FAIL( VVR_ERR_PARAMETER, isSbt ? "SbTMVP CU: sub-block vector in the motion field outside the 18-bit range" : "affine CU: sub-block vector in the motion field outside the 18-bit range" );
+        }
       // (the switch and the table are those of the CU's slice)
       const vvr_slice_header* sh = p->slices ? &p->slices[p->ctu_slice[( cu.y >> h.log2_ctu ) * ( ( h.width + ( 1 << h.log2_ctu ) - 1 ) >> h.log2_ctu ) + ( cu.x >> h.log2_ctu )]] : nullptr;
       if( ( sh ? ( sh->tool_flags & VVR_TOOL_WP ) != 0 : wpOn ) && cu.ref_idx[0] >= 0 && cu.ref_idx[1] >= 0 )

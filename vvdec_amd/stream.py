@@ -107,6 +107,25 @@ def ra_plan(num_frames, gop=16, seed_poc0_is_external=True, pool=0, intra_period
     return plans, max_slots
 
 
+LONGER_LISTS_POOL = 4      # with_longer_lists: further reference pictures, in the slots after the plan's own
+
+
+def with_longer_lists(pl, n0, n1, first_free_slot, rnd):
+    """A copy of the PicPlan `pl` (a P / B picture with slots assigned) whose reference lists hold n0 / n1 entries (up to 16; a list the plan leaves empty stays
+    empty): the entries it has keep their indices, the further ones are drawn with rnd (random.Random) from the pictures it lists and from
+    LONGER_LISTS_POOL pictures of the caller's in the slots first_free_slot .., at POCs before every POC of a stream that starts at 0 - a picture may appear at
+    several indices of one list.  The caller provides a picture for every (slot, POC) of the new ref_slots."""
+    from dataclasses import replace
+    pool = []
+    for lst in pl.ref_slots:
+        for e in lst:
+            if e not in pool:
+                pool.append(e)
+    pool += [(first_free_slot + k, -4 * (k + 1)) for k in range(LONGER_LISTS_POOL)]
+    lists = tuple(list(lst) + ([pool[rnd.randrange(len(pool))] for _ in range(n - len(lst))] if lst else []) for lst, n in zip(pl.ref_slots, (n0, n1)))
+    return replace(pl, l0=[poc for _, poc in lists[0]], l1=[poc for _, poc in lists[1]], ref_slots=lists)
+
+
 def submission_order(plans, irap_lookahead):
     """Order in which a host that parses `irap_lookahead` pictures ahead hands the pictures of `plans` (decoding order, slots assigned, i.e. what
     ra_plan(..., irap_lookahead=0) returns) to the back-end: an IRAP picture depends on nothing, so it is submitted that many positions before its
