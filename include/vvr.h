@@ -795,7 +795,7 @@ VVR_API int          vvr_hash_submit(vvr_context* ctx, const vvr_hash_request* r
  *   VVR_STATS_LUMA  hist_y alone; hist_maxrgb, max_c and min_c are 0.  Works in every context, 4:0:0 included.
  *   bins     at 2^bd and above: 0.  samples = width * height; both histograms sum to it (hist_maxrgb in RGB mode).
  *   ticket and ring, ordering   everything said about a hash request above holds: the ticket comes from the same ticket space and the same 8 ring
- *            entries (VVR_ERR_BUSY counts all three kinds of request); vvr_output_test / vvr_output_wait collect it; vvr_output_stream_wait means
+ *            entries (VVR_ERR_BUSY counts every kind of request: output, hash, statistics, comparison); vvr_output_test / vvr_output_wait collect it; vvr_output_stream_wait means
  *            "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the request runs on the output
  *            stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1); pictures submitted afterwards
  *            that overwrite the slot wait for the request's kernels on the device; blocking == 0: VVR_NOT_READY while `job` has not been handed
@@ -850,6 +850,78 @@ struct vvr_light_level {       /* (a tag, no typedef: the function has the name)
   double   maxscl_nits[3];
 };
 VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_characteristics, uint32_t percentile_e4, struct vvr_light_level* out);
+/* A picture compared with a reference frame as a request of the output queue: what a transcoder's quality loop (PSNR against the source, which lies
+ * on the same GPU), a conformance check against a .yuv of expected frames (a digest says "differs", not where or by how much) and a parity test
+ * would otherwise pull whole planes over PCIe for.  The reduction runs where the pixels are; about a hundred bytes cross PCIe, and one word per
+ * block of 64 x 64 luma samples with `map`; nothing drains.  The result is integers, defined here to the bit:
+ *   d        ( int32 ) slot sample - ( int32 ) reference sample, both read as unsigned values exactly as they lie: the slot's 16-bit word, the
+ *            reference's byte or little-endian 16-bit word.  A reference may hold any value up to 65535; nothing is clipped or masked.  One d * d
+ *            reaches 4 294 836 225: every sum is exact in 64 bits for every input.
+ *   window   x, y, w, h in luma samples of the picture in the slot (vvr_slot_picture_size), even in 4:2:0; component c of a 4:2:0 context is compared
+ *            over ( x >> 1, y >> 1, w >> 1, h >> 1 ) of its plane.  Every component of the context is compared.  The reference planes ARE the window:
+ *            their sample ( 0, 0 ) is the window's, ref[c] + j * ref_stride_bytes[c] is row j of component c.  With ref_slot >= 0 the reference is the
+ *            same window of the picture in that slot; both pictures must be of the same size.
+ *   per component c   samples = width * height; differing: samples with d != 0; sse: the sum of d * d; sad: the sum of |d|; max_abs: the largest |d|;
+ *            first_x, first_y: the first differing sample in raster order of the component's window (rows top to bottom, a row left to right), in that
+ *            window's coordinates, both 0xffffffff when differing == 0.  The entries of the components a 4:0:0 context lacks are 0 (first: 0xffffffff).
+ *   map      NULL, or ceil( w / 64 ) * ceil( h / 64 ) words, row-major: map[by * ceil( w / 64 ) + bx] is the number of differing samples, over all
+ *            components, inside the block of 64 x 64 luma samples at ( 64 bx, 64 by ) of the window; a chroma sample ( i, j ) belongs to the block of
+ *            ( 2 i, 2 j ).  The map sums to differing[0] + differing[1] + differing[2].
+ *   where the reference may lie (ref_slot == -1), as `dst` of an output request:
+ *            every plane wholly inside a range of vvr_device_alloc / vvr_device_register: read in place, nothing crosses PCIe; the caller sees to it
+ *            that the memory is idle, as for a device destination.  Every plane in memory of vvr_host_alloc: copied to the device straight from it on
+ *            the output stream; it must stay untouched until vvr_output_wait has returned.  Any other host memory: copied inside vvr_compare_submit
+ *            into the entry's pinned staging, as `expected` of a hash request is: the caller's buffers are free again when the call returns.
+ *   ticket and ring, ordering   everything said about a hash or statistics request above holds: the ticket comes from the same ticket space and the
+ *            same 8 ring entries (VVR_ERR_BUSY counts all four kinds of request); vvr_output_test / vvr_output_wait collect it;
+ *            vvr_output_stream_wait means "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the
+ *            request runs on the output stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1);
+ *            ref_slot is taken as all work submitted so far leaves it (the job == -1 rule, whatever `job` is); the request is a reader of both slots:
+ *            a picture submitted afterwards into either waits for the request's first kernel on the device; blocking == 0: VVR_NOT_READY while `job`
+ *            (with ref_slot: any picture) has not been handed to the device; a request for a job that failed is accepted and fails with that job's
+ *            status, *result and map untouched.  The film grain seed chain and the colour description are not touched.
+ *   result   vvr_output_wait, when it returns VVR_OK, writes *result - every field, struct_size included - and map.  Both must stay valid until then.
+ * Refused (VVR_ERR_PARAMETER with a text, no ring entry taken): a struct_size other than sizeof( vvr_compare_request ), no such slot or ref_slot,
+ * ref_slot == slot, job < -1, result == NULL, a window outside the picture, empty, or odd in a 4:2:0 context, pictures of different sizes in the two
+ * slots; without ref_slot: ref_bytes_per_sample other than 1 or 2, a NULL plane among those the context has, a stride below the row, device planes
+ * mixed with host planes, a plane partly inside a device range.
+ * Not offered: SSIM and other windowed measures; grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
+ * a reference of another size than the window. */
+typedef struct vvr_frame_compare {
+  uint32_t struct_size;            /* sizeof( vvr_frame_compare ), written with the rest */
+  uint32_t bit_depth;              /* the context's */
+  uint32_t num_components;         /* 1 (4:0:0) or 3 */
+  uint32_t pad;
+  uint32_t width[3], height[3];    /* the window per component (chroma: >> 1 in 4:2:0) */
+  uint64_t samples[3];             /* width * height */
+  uint64_t differing[3];           /* samples with d != 0 */
+  uint64_t sse[3];                 /* sum of d * d */
+  uint64_t sad[3];                 /* sum of |d| */
+  uint32_t max_abs[3];             /* largest |d| */
+  uint32_t first_x[3], first_y[3]; /* the first differing sample in raster order of the component's window; 0xffffffff both when differing == 0 */
+  uint32_t pad2;
+} vvr_frame_compare;
+typedef struct vvr_compare_request {
+  uint32_t struct_size;            /* sizeof( vvr_compare_request ) */
+  int32_t  slot;
+  int32_t  job;                    /* as vvr_output_request.job */
+  int32_t  x, y, w, h;             /* window, luma samples (even in 4:2:0) */
+  int32_t  ref_slot;               /* >= 0: the reference is the same window of that slot; -1: ref[] below */
+  uint8_t  ref_bytes_per_sample;   /* 1 or 2 (little endian); ignored with ref_slot */
+  uint8_t  blocking;               /* as vvr_output_request.blocking */
+  uint8_t  pad[2];
+  uint32_t pad2;
+  const void* ref[3];              /* planes of the WINDOW's size (not the picture's); ref[1], ref[2] unused in 4:0:0 */
+  size_t   ref_stride_bytes[3];
+  vvr_frame_compare* result;       /* written by vvr_output_wait; must stay valid until it has returned */
+  uint32_t* map;                   /* NULL, or ceil( w / 64 ) * ceil( h / 64 ) words, written by vvr_output_wait */
+} vvr_compare_request;
+VVR_API int          vvr_compare_submit(vvr_context* ctx, const vvr_compare_request* req);
+/* PSNR from the sums of a comparison; a pure host function, no context, everything in double.  peak <= 0 means 2^bit_depth - 1 (HM-style callers
+ * pass 255 << ( bit_depth - 8 )).  psnr[c] = 10 log10( peak^2 * samples[c] / sse[c] ) for the components that exist, 0 for those that do not;
+ * psnr[3]: the same formula from the sums of samples and of sse over the components.  HUGE_VAL where the sse is 0.  Refused (VVR_ERR_PARAMETER, psnr
+ * untouched): a NULL pointer, a struct_size other than sizeof( vvr_frame_compare ), a bit depth outside 8..10, samples[0] == 0. */
+VVR_API int          vvr_compare_psnr(const vvr_frame_compare* cmp, double peak, double psnr[4]);
 /* the finished picture in `slot` (every plane, at the picture's size) into the caller's buffers - what a decoder does with each picture it hands to
  * the application (the planes of a vvdecFrame live in the Picture's own buffers, vvdecimpl.cpp:1058).  Waits for NOTHING: the caller has waited for
  * the picture (vvr_wait); other pictures in flight are not held up (vvr_read_plane drains the context).  Each plane crosses PCIe in one transfer

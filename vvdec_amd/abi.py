@@ -295,5 +295,49 @@ def stats_request(slot, job, window, mode, collocated, blocking, stats):
     return r
 
 
+class FrameCompare(C.Structure):
+    """vvr_frame_compare: what vvr_output_wait writes for a comparison request (vvr_compare_submit, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("bit_depth", u32), ("num_components", u32), ("pad", u32), ("width", u32 * 3), ("height", u32 * 3),
+                ("samples", u64 * 3), ("differing", u64 * 3), ("sse", u64 * 3), ("sad", u64 * 3),
+                ("max_abs", u32 * 3), ("first_x", u32 * 3), ("first_y", u32 * 3), ("pad2", u32)]
+
+
+class CompareRequest(C.Structure):
+    """vvr_compare_request: a picture compared with a reference frame as a request of the output queue (vvr_compare_submit, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("slot", i32), ("job", i32), ("x", i32), ("y", i32), ("w", i32), ("h", i32), ("ref_slot", i32),
+                ("ref_bytes_per_sample", u8), ("blocking", u8), ("pad", u8 * 2), ("pad2", u32),
+                ("ref", C.c_void_p * 3), ("ref_stride_bytes", C.c_size_t * 3), ("result", C.c_void_p), ("map", C.c_void_p)]
+
+
+def compare_map_shape(window):
+    """(rows, columns) of the map of a comparison: one word per block of 64 x 64 luma samples of the window"""
+    return (window[3] + 63) // 64, (window[2] + 63) // 64
+
+
+def compare_request(slot, job, window, ref, result, map_=None, blocking=True, ref_bytes_per_sample=2):
+    """a CompareRequest that writes into `result` (a FrameCompare) and, when given, `map_` (a C-contiguous uint32 array of compare_map_shape),
+    both kept alive by the caller until the request has been waited for.  ref: a slot number, or per component a numpy plane (uint8 / uint16,
+    rows contiguous), an object with data_ptr() / stride() / element_size() (a torch tensor), or an (address, stride in bytes) pair with
+    ref_bytes_per_sample"""
+    r = CompareRequest()
+    r.struct_size = C.sizeof(CompareRequest)
+    r.slot, r.job, r.blocking = slot, -1 if job is None else job, 1 if blocking else 0
+    r.x, r.y, r.w, r.h = window
+    r.ref_slot, r.ref_bytes_per_sample = -1, ref_bytes_per_sample
+    if isinstance(ref, int):
+        r.ref_slot = ref
+    else:
+        for k, pl in enumerate(ref):
+            if isinstance(pl, tuple):
+                r.ref[k], r.ref_stride_bytes[k] = pl
+            elif hasattr(pl, "data_ptr"):
+                r.ref[k], r.ref_stride_bytes[k], r.ref_bytes_per_sample = pl.data_ptr(), pl.stride(0) * pl.element_size(), pl.element_size()
+            else:
+                r.ref[k], r.ref_stride_bytes[k], r.ref_bytes_per_sample = pl.ctypes.data, pl.strides[0], pl.itemsize
+    r.result = C.addressof(result)
+    r.map = None if map_ is None else map_.ctypes.data
+    return r
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]

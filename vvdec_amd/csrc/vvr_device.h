@@ -298,6 +298,24 @@ void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
 #define RGB_FMT_STATS 255      /* the store class of k_output_rgb that accumulates where the others store */
 void launch_output_stats( hipStream_t s, const OutputRgbParams& p, int rgb, uint32_t* shards );
 void launch_output_stats_sum( hipStream_t s, const uint32_t* shards, uint32_t* out );
+// a picture compared with a reference frame (vvr_compare_submit, the definition: vvr.h).  The window is cut into blocks of 64 x 64 luma samples
+// (with them the 32 x 32 chroma samples of each chroma component), nbx x nby of them, row-major.  launch_output_compare: recs[( c * nbx * nby + b ) *
+// CMP_REC_WORDS ..] = the record of component c in block b - sse (low word, high word), sad, the number of differing samples, the largest |d|, the
+// smallest j * w[c] + i of a differing sample ( i, j ) of the component's window (0xffffffff: none) - and map[b] = the differing samples of the
+// block over the components; every word is stored, nothing has to be cleared.  launch_output_compare_sum: out[c * CMP_OUT_WORDS ..] = sse, sad and
+// the count as 64-bit sums (low word first), the maximum, the minimum of the first indices, over the blocks.
+#define CMP_REC_WORDS 6
+#define CMP_OUT_WORDS 8
+struct CompareParams
+{
+  const pel_t* src[3]; int stride[3];            // the window's origin in the slot's planes; samples
+  const uint8_t* ref[3]; size_t refStride[3];    // the reference window; bytes
+  int w[3], h[3];                                // the window per component
+  int numComp, refBytes, nbx, nby;               // refBytes: 1 or 2 per reference sample
+  int bySample;                                  // no wide loads: an origin, a base or a stride does not allow them (chosen by the caller)
+};
+void launch_output_compare( hipStream_t s, const CompareParams& p, uint32_t* recs, uint32_t* map );
+void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks, int numComp, uint32_t* out );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.
 // launch_hash_rows: one launch over the rows of all planes, rows[g] = the CRC piece (the row's bytes mod P, register from 0) or the checksum share
 // of row g (the planes' rows one after the other).  launch_hash_combine: out[c] = the component's digest as a number - the checksum, or the CRC

@@ -5652,6 +5652,146 @@ void launch_output_stats_sum( hipStream_t s, const uint32_t* shards, uint32_t* o
   hipLaunchKernelGGL( k_output_stats_sum, dim3( ( STATS_WORDS + 255 ) / 256 ), dim3( 256 ), 0, s, shards, out );
 }
 
+// k_output_compare — a picture compared with a reference frame (vvr_compare_submit, the definition: vvr.h).  A workgroup owns one block of 64 x 64
+// luma samples of the window and with it the 32 x 32 samples of both chroma components; a lane owns pieces of 8 samples of a row: two of luma
+// (piece tid and tid + 256 of the block's 64 rows x 8) and one of chroma (wavefronts 0 and 1: Cb, 2 and 3: Cr - uniform in a wavefront, so each
+// wavefront reduces one luma and one chroma set).  A whole piece is one 16-byte load of the slot and one 16- or 8-byte load of the reference
+// (unaligned access mode, as k_output_stats), a piece at a row's end - and every piece of the class the host selects for origins, bases and
+// strides that do not allow wide loads, BYSAMPLE - sample by sample, the reference byte by byte.  The three pieces are loaded into registers
+// before the first of them is looked at.  Per lane: count, sad (16 samples x 65535), maximum and smallest index in 32 bits, sse
+// in 64 ( one d * d fills 32).  Across the wavefront in registers, across the four wavefronts through 48 words of LDS; lane 0 stores the block's
+// records and its map word.  No atomics, nothing cleared beforehand: every word of the output is stored exactly once.
+struct CmpAcc { uint32_t n, sad, top, first; uint64_t sse; };
+struct CmpPiece { uint4 a, b; int n; uint32_t at; };      // 8 slot samples and 8 reference samples, two to a dword (RB == 1: the bytes in b.x, b.y); how many exist; the index of the first
+template<int RB, bool BYSAMPLE>
+__device__ __forceinline__ CmpPiece cmp_load( const CompareParams& p, int c, int i0, int j )
+{
+  CmpPiece q; q.a = make_uint4( 0, 0, 0, 0 ); q.b = make_uint4( 0, 0, 0, 0 ); q.n = 0; q.at = 0;
+  if( c >= p.numComp || j >= p.h[c] || i0 >= p.w[c] ) return q;
+  q.n = min( 8, p.w[c] - i0 ); q.at = (uint32_t) ( j * p.w[c] + i0 );      // (sides <= 8192: below 2^26)
+  const pel_t* __restrict__ s = p.src[c] + (size_t) j * p.stride[c] + i0;
+  const uint8_t* __restrict__ r = p.ref[c] + (size_t) j * p.refStride[c] + (size_t) i0 * RB;
+  if( !BYSAMPLE && q.n == 8 )
+  {
+    __builtin_memcpy( &q.a, s, 16 );
+    if( RB == 2 ) __builtin_memcpy( &q.b, r, 16 ); else { uint2 t; __builtin_memcpy( &t, r, 8 ); q.b.x = t.x; q.b.y = t.y; }
+    return q;
+  }
+  uint32_t va[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, vb[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+  for( int i = 0; i < 8; i++ )
+    if( i < q.n ) { va[i] = (uint16_t) s[i]; vb[i] = RB == 1 ? (uint32_t) r[i] : (uint32_t) r[2 * i] | (uint32_t) r[2 * i + 1] << 8; }
+  q.a = make_uint4( va[0] | va[1] << 16, va[2] | va[3] << 16, va[4] | va[5] << 16, va[6] | va[7] << 16 );
+  if( RB == 2 ) q.b = make_uint4( vb[0] | vb[1] << 16, vb[2] | vb[3] << 16, vb[4] | vb[5] << 16, vb[6] | vb[7] << 16 );
+  else { q.b.x = vb[0] | vb[1] << 8 | vb[2] << 16 | vb[3] << 24; q.b.y = vb[4] | vb[5] << 8 | vb[6] << 16 | vb[7] << 24; }
+  return q;
+}
+template<int RB>
+__device__ __forceinline__ void cmp_add( CmpAcc& acc, const CmpPiece& q )
+{
+  const uint32_t wa[4] = { q.a.x, q.a.y, q.a.z, q.a.w }, wb[4] = { q.b.x, q.b.y, q.b.z, q.b.w };
+#pragma unroll
+  for( int i = 0; i < 8; i++ )
+  {
+    const int a = (int) ( ( wa[i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffff );
+    const int b = RB == 2 ? (int) ( ( wb[i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffff ) : (int) ( ( wb[i >> 2] >> ( 8 * ( i & 3 ) ) ) & 0xff );
+    const uint32_t ad = i < q.n ? (uint32_t) abs( a - b ) : 0u;      // (below 2^16: ad * ad fits 32 bits)
+    if( ad ) { acc.n++; acc.first = min( acc.first, q.at + i ); }
+    acc.sad += ad; acc.top = max( acc.top, ad ); acc.sse += (uint64_t) ( ad * ad );
+  }
+}
+__device__ __forceinline__ CmpAcc cmp_wave( CmpAcc v )      // over the wavefront, in every lane
+{
+#pragma unroll
+  for( int d = 1; d < 64; d <<= 1 )
+  {
+    v.n += (uint32_t) __shfl_xor( (int) v.n, d ); v.sad += (uint32_t) __shfl_xor( (int) v.sad, d );
+    v.top = max( v.top, (uint32_t) __shfl_xor( (int) v.top, d ) ); v.first = min( v.first, (uint32_t) __shfl_xor( (int) v.first, d ) );
+    const uint32_t lo = (uint32_t) __shfl_xor( (int) (uint32_t) v.sse, d ), hi = (uint32_t) __shfl_xor( (int) (uint32_t) ( v.sse >> 32 ), d );
+    v.sse += lo | (uint64_t) hi << 32;
+  }
+  return v;
+}
+template<int RB, bool BYSAMPLE>
+__global__ __launch_bounds__( 256 ) void k_output_compare( CompareParams p, uint32_t* __restrict__ recs, uint32_t* __restrict__ map )
+{
+  __shared__ uint32_t part[4][2][CMP_REC_WORDS];
+  const int tid = threadIdx.x, wave = tid >> 6, cc = 1 + ( tid >> 7 ), ct = tid & 127;
+  const int X0 = blockIdx.x * 64, Y0 = blockIdx.y * 64;
+  const CmpPiece q0 = cmp_load<RB, BYSAMPLE>( p, 0, X0 + ( tid & 7 ) * 8, Y0 + ( tid >> 3 ) );
+  const CmpPiece q1 = cmp_load<RB, BYSAMPLE>( p, 0, X0 + ( tid & 7 ) * 8, Y0 + 32 + ( tid >> 3 ) );
+  const CmpPiece q2 = cmp_load<RB, BYSAMPLE>( p, cc, ( X0 >> 1 ) + ( ct & 3 ) * 8, ( Y0 >> 1 ) + ( ct >> 2 ) );
+  CmpAcc luma = { 0, 0, 0, 0xffffffffu, 0 }, chroma = { 0, 0, 0, 0xffffffffu, 0 };
+  cmp_add<RB>( luma, q0 ); cmp_add<RB>( luma, q1 ); cmp_add<RB>( chroma, q2 );
+  luma = cmp_wave( luma ); chroma = cmp_wave( chroma );
+  if( ( tid & 63 ) == 0 )
+  {
+    uint32_t* l = part[wave][0]; uint32_t* k = part[wave][1];
+    l[0] = (uint32_t) luma.sse; l[1] = (uint32_t) ( luma.sse >> 32 ); l[2] = luma.sad; l[3] = luma.n; l[4] = luma.top; l[5] = luma.first;
+    k[0] = (uint32_t) chroma.sse; k[1] = (uint32_t) ( chroma.sse >> 32 ); k[2] = chroma.sad; k[3] = chroma.n; k[4] = chroma.top; k[5] = chroma.first;
+  }
+  __syncthreads();
+  if( tid >= p.numComp ) return;
+  // lane c folds component c: luma from the four wavefronts, Cb from wavefronts 0 and 1, Cr from 2 and 3 (sad of a block: 4096 x 65535 < 2^32)
+  const int w0 = tid == 2 ? 2 : 0, w1 = tid == 1 ? 2 : 4, set = tid ? 1 : 0;
+  uint64_t sse = 0; uint32_t sad = 0, n = 0, top = 0, first = 0xffffffffu;
+  for( int w = w0; w < w1; w++ )
+  {
+    const uint32_t* v = part[w][set];
+    sse += v[0] | (uint64_t) v[1] << 32; sad += v[2]; n += v[3]; top = max( top, v[4] ); first = min( first, v[5] );
+  }
+  const int b = blockIdx.y * gridDim.x + blockIdx.x, blocks = gridDim.x * gridDim.y;
+  uint32_t* __restrict__ rec = recs + ( (size_t) tid * blocks + b ) * CMP_REC_WORDS;
+  rec[0] = (uint32_t) sse; rec[1] = (uint32_t) ( sse >> 32 ); rec[2] = sad; rec[3] = n; rec[4] = top; rec[5] = first;
+  // the map word: the three counts meet in lane 0 (lanes 0 .. 2 are of one wavefront, all three here in 4:2:0)
+  const uint32_t all = n + ( p.numComp > 1 ? (uint32_t) __shfl( (int) n, 1 ) + (uint32_t) __shfl( (int) n, 2 ) : 0u );
+  if( tid == 0 ) map[b] = all;
+}
+// k_output_compare_sum — workgroup c folds the records of component c into its CMP_OUT_WORDS words: 64-bit sums, the maximum, the minimum of the
+// first indices - which are indices into the component's window, so that the minimum is the first in raster order whatever block holds it
+__global__ __launch_bounds__( 256 ) void k_output_compare_sum( const uint32_t* __restrict__ recs, int blocks, uint32_t* __restrict__ out )
+{
+  __shared__ uint32_t part[4][CMP_OUT_WORDS];
+  const int tid = threadIdx.x, c = blockIdx.x;
+  uint64_t sse = 0, sad = 0, n = 0; uint32_t top = 0, first = 0xffffffffu;
+  for( int b = tid; b < blocks; b += 256 )
+  {
+    const uint2* __restrict__ r = (const uint2*) ( recs + ( (size_t) c * blocks + b ) * CMP_REC_WORDS );      // (24 bytes a record: 8-byte aligned)
+    const uint2 v0 = r[0], v1 = r[1], v2 = r[2];
+    sse += v0.x | (uint64_t) v0.y << 32; sad += v1.x; n += v1.y; top = max( top, v2.x ); first = min( first, v2.y );
+  }
+  CmpAcc a = { 0, 0, top, first, sse }, k = { 0, 0, 0, 0xffffffffu, sad }, m = { 0, 0, 0, 0xffffffffu, n };      // (three 64-bit sums ride in the sse field)
+  a = cmp_wave( a ); k = cmp_wave( k ); m = cmp_wave( m );
+  if( ( tid & 63 ) == 0 )
+  {
+    uint32_t* v = part[tid >> 6];
+    v[0] = (uint32_t) a.sse; v[1] = (uint32_t) ( a.sse >> 32 ); v[2] = (uint32_t) k.sse; v[3] = (uint32_t) ( k.sse >> 32 );
+    v[4] = (uint32_t) m.sse; v[5] = (uint32_t) ( m.sse >> 32 ); v[6] = a.top; v[7] = a.first;
+  }
+  __syncthreads();
+  if( tid ) return;
+  sse = sad = n = 0; top = 0; first = 0xffffffffu;
+  for( int w = 0; w < 4; w++ )
+  {
+    const uint32_t* v = part[w];
+    sse += v[0] | (uint64_t) v[1] << 32; sad += v[2] | (uint64_t) v[3] << 32; n += v[4] | (uint64_t) v[5] << 32; top = max( top, v[6] ); first = min( first, v[7] );
+  }
+  uint32_t* __restrict__ o = out + c * CMP_OUT_WORDS;
+  o[0] = (uint32_t) sse; o[1] = (uint32_t) ( sse >> 32 ); o[2] = (uint32_t) sad; o[3] = (uint32_t) ( sad >> 32 ); o[4] = (uint32_t) n; o[5] = (uint32_t) ( n >> 32 );
+  o[6] = top; o[7] = first;
+}
+void launch_output_compare( hipStream_t s, const CompareParams& p, uint32_t* recs, uint32_t* map )
+{
+  const dim3 grid( p.nbx, p.nby );
+  if( p.bySample ) { if( p.refBytes == 1 ) hipLaunchKernelGGL( ( k_output_compare<1, true> ), grid, dim3( 256 ), 0, s, p, recs, map ); else hipLaunchKernelGGL( ( k_output_compare<2, true> ), grid, dim3( 256 ), 0, s, p, recs, map ); }
+  else if( p.refBytes == 1 ) hipLaunchKernelGGL( ( k_output_compare<1, false> ), grid, dim3( 256 ), 0, s, p, recs, map );
+  else hipLaunchKernelGGL( ( k_output_compare<2, false> ), grid, dim3( 256 ), 0, s, p, recs, map );
+}
+void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks, int numComp, uint32_t* out )
+{
+  hipLaunchKernelGGL( k_output_compare_sum, dim3( numComp ), dim3( 256 ), 0, s, recs, blocks, out );
+}
+
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in
 __device__ __forceinline__ uint32_t crc_mul( uint32_t a, uint32_t b )
 {

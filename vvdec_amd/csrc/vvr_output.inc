@@ -444,6 +444,49 @@ void launch_output_stats_sum( hipStream_t, const uint32_t* shards, uint32_t* out
     out[i] = acc;
   }
 }
+
+// ... and launch_output_compare / launch_output_compare_sum (k_output_compare, k_output_compare_sum): the definition of vvr.h sample by sample, a
+// record per block and component as vvr_device.h lays them out; the records folded
+void launch_output_compare( hipStream_t, const CompareParams& p, uint32_t* recs, uint32_t* map )
+{
+  const int blocks = p.nbx * p.nby;
+  for( int b = 0; b < blocks; b++ )
+  {
+    map[b] = 0;
+    for( int c = 0; c < p.numComp; c++ )
+    {
+      const int side = c ? 32 : 64, i0 = ( b % p.nbx ) * side, j0 = ( b / p.nbx ) * side;
+      uint64_t sse = 0; uint32_t sad = 0, count = 0, top = 0, first = 0xffffffffu;
+      for( int j = j0; j < std::min( j0 + side, p.h[c] ); j++ )
+        for( int i = i0; i < std::min( i0 + side, p.w[c] ); i++ )
+        {
+          const uint8_t* r = p.ref[c] + (size_t) j * p.refStride[c] + (size_t) i * p.refBytes;
+          const int32_t d = (int32_t) (uint16_t) p.src[c][(size_t) j * p.stride[c] + i] - (int32_t) ( p.refBytes == 1 ? r[0] : r[0] | r[1] << 8 );
+          if( !d ) continue;
+          const uint32_t a = (uint32_t) std::abs( d );
+          sse += (uint64_t) a * a; sad += a; count++; top = std::max( top, a ); first = std::min( first, (uint32_t) ( j * p.w[c] + i ) );
+        }
+      uint32_t* rec = recs + ( (size_t) c * blocks + b ) * CMP_REC_WORDS;
+      rec[0] = (uint32_t) sse; rec[1] = (uint32_t) ( sse >> 32 ); rec[2] = sad; rec[3] = count; rec[4] = top; rec[5] = first;
+      map[b] += count;
+    }
+  }
+}
+void launch_output_compare_sum( hipStream_t, const uint32_t* recs, int blocks, int numComp, uint32_t* out )
+{
+  for( int c = 0; c < numComp; c++ )
+  {
+    uint64_t sse = 0, sad = 0, count = 0; uint32_t top = 0, first = 0xffffffffu;
+    for( int b = 0; b < blocks; b++ )
+    {
+      const uint32_t* rec = recs + ( (size_t) c * blocks + b ) * CMP_REC_WORDS;
+      sse += rec[0] | (uint64_t) rec[1] << 32; sad += rec[2]; count += rec[3]; top = std::max( top, rec[4] ); first = std::min( first, rec[5] );
+    }
+    uint32_t* o = out + c * CMP_OUT_WORDS;
+    o[0] = (uint32_t) sse; o[1] = (uint32_t) ( sse >> 32 ); o[2] = (uint32_t) sad; o[3] = (uint32_t) ( sad >> 32 ); o[4] = (uint32_t) count; o[5] = (uint32_t) ( count >> 32 );
+    o[6] = top; o[7] = first;
+  }
+}
 #endif
 
 extern "C" {
@@ -737,6 +780,23 @@ VVR_API int vvr_light_level( const vvr_frame_stats* st, int transfer, uint32_t p
   return VVR_OK;
 }
 
+// PSNR from the sums of a comparison (vvr_compare_submit), the formula as vvr.h gives it, in double
+VVR_API int vvr_compare_psnr( const vvr_frame_compare* cmp, double peak, double psnr[4] )
+{
+  if( !cmp || !psnr || cmp->struct_size != sizeof( vvr_frame_compare ) || cmp->bit_depth < 8 || cmp->bit_depth > 10 || !cmp->samples[0] ) return VVR_ERR_PARAMETER;
+  if( !( peak > 0 ) ) peak = (double) ( ( 1u << cmp->bit_depth ) - 1 );
+  auto db = [&]( double samples, double sse ) { return sse == 0 ? HUGE_VAL : 10.0 * std::log10( peak * peak * samples / sse ); };
+  const int nc = cmp->num_components == 1 ? 1 : 3;
+  double samples = 0, sse = 0;
+  for( int k = 0; k < 3; k++ )
+  {
+    psnr[k] = k < nc ? db( (double) cmp->samples[k], (double) cmp->sse[k] ) : 0.0;
+    if( k < nc ) { samples += (double) cmp->samples[k]; sse += (double) cmp->sse[k]; }
+  }
+  psnr[3] = db( samples, sse );
+  return VVR_OK;
+}
+
 VVR_API int vvr_read_output_grain( vvr_context* c, int slot, int x, int y, int w, int h, int bytesPerSample, void* const dst[3], const size_t dstStrideBytes[3] )
 {
   if( !c || slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] || !dst || !dstStrideBytes ) return VVR_ERR_PARAMETER;
@@ -931,6 +991,10 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // A statistics request (vvr_stats_submit) is an entry with no destination planes either: its scratch holds the copies of the words the workgroups
 // add into - cleared on the output stream ahead of the launch - and the words k_output_stats_sum folds them to, which are all that crosses PCIe;
 // vvr_output_wait writes the caller's vvr_frame_stats from them.
+// A comparison request (vvr_compare_submit) reads two sources: the slot and a second slot, the caller's device memory in place, or the entry's
+// `tmp`, where a reference from the host is packed (copied from the caller's pinned memory, or through the entry's pinned staging).  Its scratch
+// holds a record per block and component, every word of which k_output_compare stores - nothing is cleared - then the words
+// k_output_compare_sum folds them to and the map; the words (with `map` the map too) are all that crosses PCIe back.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -950,7 +1014,11 @@ struct OutEntry {
   bool timed2 = false; PendingTiming timing2;      // (k_hash_combine; `timing` is k_hash_rows then)
   // a statistics request: mode + 1 (0: none); STATS_WORDS words at the start of `host`; what vvr_output_wait writes besides them
   int stats = 0, statsW = 0, statsH = 0; vvr_frame_stats* statsOut = nullptr;
+  // a comparison request: its number of components (0: none); CMP_OUT_WORDS words per component at the start of `host`, the map's words from
+  // word CMP_HEAD_WORDS on; the second slot it reads (-1: none); what vvr_output_wait writes
+  int cmp = 0, cmpW = 0, cmpH = 0, cmpBlocks = 0, refSlot = -1; vvr_frame_compare* cmpOut = nullptr; uint32_t* cmpMap = nullptr;
 };
+#define CMP_HEAD_WORDS 32      /* 3 x CMP_OUT_WORDS, rounded up: the map starts at a multiple of 128 bytes */
 
 static void destroyOutputQueue( vvr_context* c )
 {
@@ -1000,14 +1068,14 @@ int outJobStatus( vvr_context* c, int job, std::unique_lock<std::mutex>& lk, boo
   if( it->second->state == J_FAILED ) { c->setError( it->second->err ); return it->second->rc; }
   return VVR_OK;
 }
-// A request's way into the ring, shared by vvr_output_submit and vvr_hash_submit (`who`); mu held in all three.
+// A request's way into the ring, shared by the four submit calls (`who`); mu held in all three helpers.
 // outAcquire: a free entry, the output stream, the entry's events; the picture `job` reconstructs into `slot` has been handed to the device - the
 // only host wait of a submit call, only when `blocking`, mu released meanwhile.  VVR_OK: jobDone is the event the request waits for on the device
 // (NULL: the picture has finished), jobFailed the status of a picture that failed; anything else is what the submit call returns.
-int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blocking, std::unique_lock<std::mutex>& lk, OutEntry*& e, hipEvent_t& jobDone, int& jobFailed )
+int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blocking, std::unique_lock<std::mutex>& lk, OutEntry*& e, hipEvent_t& jobDone, int& jobFailed, OutEntry* take = nullptr )
 {
   const std::string w = std::string( who ) + ": ";
-  e = nullptr; jobDone = nullptr; jobFailed = VVR_OK;
+  e = take; jobDone = nullptr; jobFailed = VVR_OK;      // (take: a free entry the caller has chosen - vvr_compare_submit, which has staged a reference in its pinned memory)
   if( !c->outRing ) c->outRing = new OutEntry[VVR_OUT_RING];
   for( int i = 0; i < VVR_OUT_RING && !e; i++ ) if( c->outRing[i].state == OQ_FREE ) e = &c->outRing[i];
   if( !e ) { c->setError( w + "8 requests in flight (vvr_output_wait retires one)" ); return VVR_ERR_BUSY; }
@@ -1054,7 +1122,7 @@ int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blockin
 void outTake( vvr_context* c, OutEntry* e, int slot, int job, int jobFailed )
 {
   e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
-  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0;
+  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0; e->cmp = 0; e->refSlot = -1;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
   if( e->timed2 ) { hipEventDestroy( e->timing2.a ); hipEventDestroy( e->timing2.b ); e->timed2 = false; }
 }
@@ -1464,6 +1532,145 @@ VVR_API int vvr_stats_submit( vvr_context* c, const vvr_stats_request* rq )
   }
   return ticket;
 }
+
+VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  const char* const who = "vvr_compare_submit";
+  // ---- 1. the request
+  if( rq->struct_size != sizeof( vvr_compare_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_compare_request )", who );
+  const int slot = rq->slot, refSlot = rq->ref_slot, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
+  if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot", who );
+  if( refSlot < -1 || refSlot >= (int) c->slots.size() || ( refSlot >= 0 && !c->slots[refSlot].p[0] ) ) return outRefuse( c, "no such ref_slot", who );
+  if( refSlot == slot ) return outRefuse( c, "ref_slot is the slot itself", who );
+  if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1", who );
+  if( !rq->result ) return outRefuse( c, "result is NULL", who );
+  const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot, not the slot)
+  if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, empty, or odd in 4:2:0", who );
+  const int rb = refSlot >= 0 ? 2 : rq->ref_bytes_per_sample;
+  CompareParams p; memset( &p, 0, sizeof( p ) );
+  size_t rowBytes[3] = { 0, 0, 0 }, extent[3] = { 0, 0, 0 };
+  for( int k = 0; k < nc; k++ ) { const int sh = k ? 1 : 0; p.w[k] = w >> sh; p.h[k] = h >> sh; p.src[k] = d.p[k] + (size_t) ( y >> sh ) * d.stride[k] + ( x >> sh ); p.stride[k] = d.stride[k]; }
+  p.numComp = nc; p.refBytes = rb; p.nbx = ( w + 63 ) / 64; p.nby = ( h + 63 ) / 64;
+  if( refSlot >= 0 )
+  {
+    const DevPlanes r = pictureIn( c, refSlot );
+    if( r.w[0] != d.w[0] || r.h[0] != d.h[0] ) return outRefuse( c, "the pictures in slot and ref_slot are of different sizes", who );
+    for( int k = 0; k < nc; k++ ) { const int sh = k ? 1 : 0; p.ref[k] = (const uint8_t*) ( r.p[k] + (size_t) ( y >> sh ) * r.stride[k] + ( x >> sh ) ); p.refStride[k] = (size_t) r.stride[k] * sizeof( pel_t ); }
+  }
+  else
+  {
+    if( rb != 1 && rb != 2 ) return outRefuse( c, "ref_bytes_per_sample must be 1 or 2", who );
+    for( int k = 0; k < nc; k++ )
+    {
+      rowBytes[k] = (size_t) p.w[k] * rb; extent[k] = (size_t) ( p.h[k] - 1 ) * rq->ref_stride_bytes[k] + rowBytes[k];
+      if( !rq->ref[k] || rq->ref_stride_bytes[k] < rowBytes[k] ) return outRefuse( c, "missing reference plane or stride below the window's row", who );
+    }
+  }
+  hipSetDevice( c->device );
+  std::unique_lock<std::mutex> lk( c->mu );
+  // ---- where the reference lies: device memory the context knows (every plane wholly inside a range), or the host
+  int devPlanes = 0;
+  for( int k = 0; k < nc && refSlot < 0; k++ )
+  {
+    const char* b = (const char*) rq->ref[k];
+    for( const DevRange& r : c->devRanges )
+    {
+      if( b >= r.p && b + extent[k] <= r.p + r.n ) { devPlanes++; break; }
+      if( b < r.p + r.n && b + extent[k] > r.p ) { c->setError( std::string( who ) + ": a reference plane lies partly inside a device range (vvr_device_alloc / vvr_device_register)" ); return VVR_ERR_PARAMETER; }
+    }
+  }
+  if( devPlanes && devPlanes != nc ) { c->setError( std::string( who ) + ": reference planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
+  const bool devRef = devPlanes != 0, staged = refSlot < 0 && !devRef;
+  bool pinnedRef = staged;
+  for( int k = 0; k < nc && pinnedRef; k++ ) pinnedRef = c->pinned.contains( rq->ref[k], extent[k] );
+  // ---- the entry's buffers: the blocks' records, the folded words and the map behind them; a reference from the host packed in `tmp`, rows at a
+  // multiple of 16 bytes; pinned: the folded words and the map, then the staging of a reference in pageable memory
+  const int blocks = p.nbx * p.nby;
+  const size_t recBytes = alignUp( sizeof( uint32_t ) * CMP_REC_WORDS * nc * blocks, 256 ), wordBytes = sizeof( uint32_t ) * ( CMP_HEAD_WORDS + blocks );
+  const size_t crossBytes = sizeof( uint32_t ) * ( rq->map ? CMP_HEAD_WORDS + blocks : 3 * CMP_OUT_WORDS ), hostStageOff = alignUp( wordBytes, 256 );
+  size_t stageOff[3] = { 0, 0, 0 }, stageStride[3] = { 0, 0, 0 }, stageBytes = 0;
+  for( int k = 0; k < nc && staged; k++ ) { stageOff[k] = stageBytes; stageStride[k] = alignUp( rowBytes[k], 16 ); stageBytes += alignUp( stageStride[k] * p.h[k], 256 ); }
+  // ---- a reference in pageable memory goes into an entry's pinned memory BEFORE the request is ordered: from outAcquire to the registration of the
+  // `read` event mu stays held (a picture committed in between that overwrites the slot has to find the event), and a frame's worth of memcpy
+  // does not belong under mu.  The entry is this thread's meanwhile and is handed to outAcquire as the one to take
+  OutEntry* mine = nullptr;
+  if( staged && !pinnedRef )
+  {
+    if( !c->outRing ) c->outRing = new OutEntry[VVR_OUT_RING];
+    for( int i = 0; i < VVR_OUT_RING && !mine; i++ ) if( c->outRing[i].state == OQ_FREE ) mine = &c->outRing[i];
+    if( !mine ) { c->setError( std::string( who ) + ": 8 requests in flight (vvr_output_wait retires one)" ); return VVR_ERR_BUSY; }
+    if( outGrow( mine->host, mine->hostCap, hostStageOff + stageBytes, true ) != VVR_OK ) { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
+    mine->state = OQ_WAITING; mine->ticket = -1; mine->devDst = false;
+    lk.unlock();
+    for( int k = 0; k < nc; k++ )
+      for( int r = 0; r < p.h[k]; r++ ) memcpy( mine->host + hostStageOff + stageOff[k] + (size_t) r * stageStride[k], (const char*) rq->ref[k] + (size_t) r * rq->ref_stride_bytes[k], rowBytes[k] );
+    lk.lock();
+    mine->state = OQ_FREE;
+  }
+  // ---- 2. a ring entry; the picture has been handed to the device - and with ref_slot every picture: who uses that slot is only known then
+  if( refSlot >= 0 && !c->bySeq.empty() )
+  {
+    if( !rq->blocking ) return VVR_NOT_READY;
+    c->cv.wait( lk, [&]{ return c->bySeq.empty(); } );
+  }
+  OutEntry* e = nullptr;
+  hipEvent_t jobDone = nullptr; int jobFailed = VVR_OK;
+  { const int rc = outAcquire( c, who, slot, rq->job, rq->blocking != 0, lk, e, jobDone, jobFailed, mine ); if( rc != VVR_OK ) return rc; }
+  hipStream_t s = c->outQStream;
+  outTake( c, e, slot, rq->job, jobFailed );
+  e->cmp = nc; e->cmpW = w; e->cmpH = h; e->cmpBlocks = blocks; e->cmpOut = rq->result; e->cmpMap = rq->map;
+  if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
+  if( outGrow( e->dev, e->devCap, recBytes + wordBytes, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, stageBytes, false ) != VVR_OK ||
+      outGrow( e->host, e->hostCap, hostStageOff, true ) != VVR_OK )      // (a staged reference: grown above, beyond this)
+  { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
+  for( int k = 0; k < nc && refSlot < 0; k++ )
+  {
+    p.ref[k] = staged ? (const uint8_t*) ( e->tmp + stageOff[k] ) : (const uint8_t*) rq->ref[k];
+    p.refStride[k] = staged ? stageStride[k] : rq->ref_stride_bytes[k];
+  }
+  // wide loads (vvr_device.h): not from an odd origin of a 4:0:0 window, not from reference planes whose base or stride is odd
+  p.bySample = nc == 1 && ( x & 1 );
+  for( int k = 0; k < nc; k++ ) if( ( (uintptr_t) p.ref[k] | p.refStride[k] ) & 1 ) p.bySample = 1;
+  if( devRef )      // (vvr_device_free / vvr_device_unregister see a request in flight that uses the range)
+  {
+    e->direct = true; e->devDst = true; e->nc = nc;
+    for( int k = 0; k < nc; k++ ) { e->dst[k] = const_cast<void*>( rq->ref[k] ); e->extent[k] = extent[k]; }
+  }
+  // ---- 3. behind the picture (or the slot's users) and behind all that uses ref_slot on the device, 4. the reference's copy and the kernels.
+  // mu stays held up to the registration of the `read` event (as vvr_output_submit)
+  OQCHK( outOrder( c, e, slot, rq->job, jobDone ) );
+  if( refSlot >= 0 ) OQCHK( outOrder( c, e, refSlot, -1, nullptr ) );
+  if( staged && !pinnedRef ) OQCHK( hipMemcpyAsync( e->tmp, e->host + hostStageOff, stageBytes, hipMemcpyHostToDevice, s ) );
+  for( int k = 0; k < nc && staged && pinnedRef; k++ )
+    OQCHK( hipMemcpy2DAsync( e->tmp + stageOff[k], stageStride[k], rq->ref[k], rq->ref_stride_bytes[k], rowBytes[k], p.h[k], hipMemcpyHostToDevice, s ) );
+  uint32_t* recs = (uint32_t*) e->dev; uint32_t* words = (uint32_t*) ( e->dev + recBytes );
+  double samples = 0;
+  for( int k = 0; k < nc; k++ ) samples += (double) p.w[k] * p.h[k];
+  outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_COMPARE, samples * ( 2 + rb ) );
+  launch_output_compare( s, p, recs, words + CMP_HEAD_WORDS );
+  if( e->timed ) hipEventRecord( e->timing.b, s );
+  OQCHK( hipGetLastError() );
+  OQCHK( hipEventRecord( e->read, s ) );      // (the slots' reader ends here: the fold reads the entry's scratch)
+  c->slotExt[slot].push_back( e->read );
+  if( refSlot >= 0 ) { c->slotExt[refSlot].push_back( e->read ); e->refSlot = refSlot; }
+  e->state = OQ_FLIGHT; e->queued = true;
+  outTimeBegin( c, s, e->timed2, e->timing2, K_OUTPUT_COMPARE_SUM, (double) sizeof( uint32_t ) * ( CMP_REC_WORDS * blocks + CMP_OUT_WORDS ) * nc );
+  launch_output_compare_sum( s, recs, blocks, nc, words );
+  if( e->timed2 ) hipEventRecord( e->timing2.b, s );
+  const int ticket = e->ticket;
+  lk.unlock();
+  // ---- the result's way to the host: the folded words, with `map` a word per block behind them
+  hipError_t ce = hipGetLastError();
+  if( ce == hipSuccess ) ce = hipMemcpyAsync( e->host, words, crossBytes, hipMemcpyDeviceToHost, s );
+  if( ce == hipSuccess ) ce = hipEventRecord( e->done, s );
+  if( ce != hipSuccess )
+  {
+    hipStreamSynchronize( s );
+    lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( who ) + ": copy to the host: " + hipGetErrorString( ce ) );
+  }
+  return ticket;
+}
 #undef OQCHK
 
 VVR_API int vvr_output_test( vvr_context* c, int ticket )
@@ -1493,9 +1700,10 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
   if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
   outTimeEnd( c, e->timed, e->timing );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS ...
-  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM)
+  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM; K_OUTPUT_COMPARE and K_OUTPUT_COMPARE_SUM)
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
   if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
+  if( e->refSlot >= 0 ) { auto& v = c->slotExt[e->refSlot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }      // (a comparison reads two slots)
   lk.unlock();
   if( rc == VVR_OK && e->queued && !e->direct )
     for( int k = 0; k < e->nc; k++ )
@@ -1529,6 +1737,24 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
       memcpy( st.hist_maxrgb, w + 1024, sizeof( st.hist_maxrgb ) );
       for( int k = 0; k < 3; k++ ) { st.max_c[k] = w[2048 + k]; st.min_c[k] = ( ( 1u << c->cfg.bit_depth ) - 1 ) - w[2051 + k]; }
     }
+  }
+  if( rc == VVR_OK && e->queued && e->cmp )
+  {
+    // the caller's vvr_frame_compare: the header fields, the folded words, the first index as a position in the component's window; the map
+    const uint32_t* w = (const uint32_t*) e->host;
+    vvr_frame_compare& r = *e->cmpOut;
+    memset( &r, 0, sizeof( r ) );
+    r.struct_size = sizeof( r ); r.bit_depth = (uint32_t) c->cfg.bit_depth; r.num_components = (uint32_t) e->cmp;
+    for( int k = 0; k < 3; k++ )
+    {
+      r.first_x[k] = r.first_y[k] = 0xffffffffu;
+      if( k >= e->cmp ) continue;
+      const uint32_t* o = w + k * CMP_OUT_WORDS;
+      r.width[k] = (uint32_t) ( e->cmpW >> ( k ? 1 : 0 ) ); r.height[k] = (uint32_t) ( e->cmpH >> ( k ? 1 : 0 ) ); r.samples[k] = (uint64_t) r.width[k] * r.height[k];
+      r.sse[k] = o[0] | (uint64_t) o[1] << 32; r.sad[k] = o[2] | (uint64_t) o[3] << 32; r.differing[k] = o[4] | (uint64_t) o[5] << 32; r.max_abs[k] = o[6];
+      if( o[7] != 0xffffffffu ) { r.first_x[k] = o[7] % r.width[k]; r.first_y[k] = o[7] / r.width[k]; }
+    }
+    if( e->cmpMap ) memcpy( e->cmpMap, w + CMP_HEAD_WORDS, sizeof( uint32_t ) * e->cmpBlocks );
   }
   lk.lock();
   e->state = OQ_FREE; e->ticket = -1;
