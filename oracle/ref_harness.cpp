@@ -232,6 +232,12 @@ struct ThreadedRun { int threads; double ms; };
 static ThreadedRun* g_threaded = nullptr;
 static int g_extraFlags = 0;      // VVREF_* flags for the entry points that have no flags argument (vvref_run_binding / vvref_run_dropin)
 extern "C" __attribute__((visibility("default"))) void vvref_set_extra_flags( int f ) { g_extraFlags = f; }
+// side channel of the harness: the chroma QP model of a generated picture (tools/synth.cpp, vvs_chroma_qp - the description holds the resulting TU QPs only).
+// Installed into the SPS mapping tables, the PPS / slice offsets, the PPS offset list and CodingUnit::chromaQpAdj; TransformUnit::chromaQp then comes from
+// the reference's own QpParam, and a value that differs from the description's TU QP is an error.  nullptr: identity tables, zero offsets (the default)
+struct ChromaQpModel { int8_t table[3][76]; int8_t pps_offset[3], slice_offset[3]; int8_t list[6][3]; uint32_t num_cu; const uint8_t* cu_idx; };
+static const ChromaQpModel* g_cqp = nullptr;
+extern "C" __attribute__((visibility("default"))) void vvref_set_chroma_qp_model( const void* m ) { g_cqp = (const ChromaQpModel*) m; }
 
 int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes, uint16_t* const* out_planes,
                        vvr_lfp* const* lfp_out, int32_t* dmvr_out, int flags, double* stage_ms )
@@ -316,12 +322,13 @@ int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes,
     {
       ChromaQpMappingTable& t = sps.m_chromaQpMappingTable;
       t.m_qpBdOffset = sps.getQpBDOffset();
-      t.m_sameCQPTableForAllChromaFlag = true;
+      t.m_sameCQPTableForAllChromaFlag = !g_cqp;
       for( int i = 0; i < MAX_NUM_CQP_MAPPING_TABLES; i++ )
       {
         t.m_chromaQpMappingTables[i].resize( MAX_QP + t.m_qpBdOffset + 1 );
-        for( int q = -t.m_qpBdOffset; q <= MAX_QP; q++ ) t.m_chromaQpMappingTables[i][q + t.m_qpBdOffset] = q;   // identity
+        for( int q = -t.m_qpBdOffset; q <= MAX_QP; q++ ) t.m_chromaQpMappingTables[i][q + t.m_qpBdOffset] = g_cqp ? g_cqp->table[i][q + t.m_qpBdOffset] : q;   // the model's, or identity
       }
+      if( g_cqp && g_cqp->num_cu != vp->num_cu ) THROW_FATAL( "chroma QP model: made for another number of CUs" );
     }
 
     auto ppsP = std::make_shared<PPS>(); PPS& pps = *ppsP;
@@ -330,6 +337,11 @@ int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes,
     pps.setPicWidthInLumaSamples( W );
     pps.setPicHeightInLumaSamples( Hh );
     pps.setLog2CtuSize( H.log2_ctu );
+    if( g_cqp )
+    {
+      pps.setQpOffset( COMPONENT_Cb, g_cqp->pps_offset[0] ); pps.setQpOffset( COMPONENT_Cr, g_cqp->pps_offset[1] ); pps.setQpOffset( JOINT_CbCr, g_cqp->pps_offset[2] );
+      for( int k = 0; k < 6; k++ ) pps.setChromaQpOffsetListEntry( k + 1, g_cqp->list[k][0], g_cqp->list[k][1], g_cqp->list[k][2] );
+    }
     {
       // tile grid as the description's CTU -> tile map says (uniform grids only differ in where the columns / rows are cut)
       const int cX = ( W + ctuSize - 1 ) / ctuSize, cY = ( Hh + ctuSize - 1 ) / ctuSize;
@@ -610,6 +622,7 @@ int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes,
     slice->setSliceType( SliceType( SH.slice_type ) );
     slice->setPOC( H.poc );
     slice->setSliceQp( 32 );
+    if( g_cqp ) { slice->setSliceChromaQpDelta( COMPONENT_Cb, g_cqp->slice_offset[0] ); slice->setSliceChromaQpDelta( COMPONENT_Cr, g_cqp->slice_offset[1] ); slice->setSliceChromaQpDelta( JOINT_CbCr, g_cqp->slice_offset[2] ); slice->setUseChromaQpAdj( true ); }
     slice->setDefaultClpRng( sps );
     slice->setDepQuantEnabledFlag( !!( SH.tool_flags & VVR_TOOL_DEP_QUANT ) );
     slice->setDeblockingFilterDisable( !!( H.tool_flags & VVR_TOOL_DEBLOCK_OFF ) );
@@ -770,7 +783,7 @@ int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes,
       CodingUnit& cu = cs.addCU( ua, chType, tt, MODE_TYPE_ALL, cuL, cuA );
       cuPtrs[i] = &cu;
       cu.slice = cuSlice; cu.pps = &pps; cu.sps = &sps; cu.tileIdx = tileOfCtu( ctuOfCu );
-      cu.qp = c.qp; cu.chromaQpAdj = 0;
+      cu.qp = c.qp; cu.chromaQpAdj = g_cqp ? g_cqp->cu_idx[i] : 0;
       cu.setPredMode( c.pred_mode == VVR_PRED_INTRA ? MODE_INTRA : c.pred_mode == VVR_PRED_IBC ? MODE_IBC : MODE_INTER );
       cu.setRootCbf( !!( c.flags & VVR_CU_ROOT_CBF ) );
       cu.setSkip( !!( c.flags & VVR_CU_SKIP ) );
@@ -831,6 +844,17 @@ int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes,
         tu.cbf = vt.cbf;
         tu.jointCbCr = vt.joint_cbcr;
         tu.chromaQp[0] = vt.qp[1]; tu.chromaQp[1] = vt.qp[2];   // CABACReader.cpp:612-618: QpParam( tu, Cb/Cr ).Qp( false )
+        if( g_cqp )
+        {   // with a model installed: the reference's own QpParam, as the parser calls it - and the description must hold the same
+          for( int k = 1; k < 3 && cf != CHROMA_400; k++ )
+          {
+            if( !tu.blocks[k].valid() ) continue;
+            QpParam cQP( tu, ComponentID( k ), false );
+            tu.chromaQp[k - 1] = cQP.Qp( false );
+            if( tu.chromaQp[k - 1] != vt.qp[k] )
+              THROW_FATAL( "chroma QP model: QpParam gives " << (int) tu.chromaQp[k - 1] << ", the description " << (int) vt.qp[k] << " (TU " << t << ", component " << k << ", joint Cb-Cr mode " << (int) vt.joint_cbcr << ")" );
+          }
+        }
         for( int k = 0; k < 3; k++ )
         {
           tu.setMtsIdx( k, vt.mts_idx[k] );

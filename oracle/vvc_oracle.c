@@ -344,7 +344,7 @@ int vvo_reconstruct( const vvr_picture* pic, const uint16_t* const* ref_planes, 
     else { vvo_set_error( "unknown prediction mode" ); goto done; }
   }
 
-  if( pic->lmcs )
+  if( pic->lmcs && !( ( flags & VVO_STOP_AFTER_RECO ) && ( flags & VVO_MAPPED_LUMA ) ) )
   {   /* inverse luma mapping, CTU by CTU: where the CTU's slice uses LMCS (Reshape::rspCtuBcw :376-392, applyLutCore Buffer.cpp:200) */
     for( int y = 0; y < reco.h[0]; y++ ) for( int x = 0; x < reco.w[0]; x++ )
       if( vvo_flags_at( pic, x, y ) & VVR_TOOL_LMCS ) { pel* d = &reco.p[0][(size_t) y * reco.stride[0] + x]; *d = pic->lmcs->inv_lut[*d & 4095]; }

@@ -18,6 +18,7 @@ extern "C" {
 #endif
 
 enum { VVO_STOP_AFTER_RECO = 4, VVO_STOP_AFTER_DBK = 8, VVO_STOP_AFTER_SAO = 16 };   /* same values as the VVREF_* flags */
+enum { VVO_MAPPED_LUMA = 1 << 8 };   /* with VVO_STOP_AFTER_RECO: the luma plane as the intra stage leaves it, before the inverse LMCS map (the samples the chroma-scale search averages) */
 
 /* whole picture: same calling convention as vvref_reconstruct (tight planes, ref_planes[slot*3+comp]) */
 int vvo_reconstruct( const vvr_picture* pic, const uint16_t* const* ref_planes, uint16_t* const* out_planes, int flags );

@@ -1,5 +1,5 @@
-"""The cases of the range-limit tests: pictures whose QPs, samples, weights, filter taps, reference indices and motion vectors sit at the ends of what the
-syntax allows.
+"""The cases of the range-limit tests: pictures whose QPs, samples, weights, filter taps, reference indices, motion vectors and side tables (LMCS model,
+chroma QP mapping and offsets, min_qp_ts) sit at the ends of what the syntax allows.
 
 One table, two users: tests/test_oracle_vs_ref_limits.py pins every input on the CPU (oracle against the reference classes), tests/test_gpu_limits.py
 then runs the same inputs through the back-end against the oracle.  Nothing here touches a GPU or the reference build: a case is a builder
@@ -857,6 +857,269 @@ def long_lists_plan(pictures=24, slots=18):
         past = [(j % slots, j) for j in range(k - 1, max(-1, k - 1 - abi.VVR_MAX_REFS), -1)]
         plans.append(stream.PicPlan(poc=k, layer=0, slice_type=B, l0=[poc for _, poc in past], l1=[poc for _, poc in past[::-1]], slot=k % slots, ref_slots=(past, past[::-1])))
     return plans, slots
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+# LMCS models at the ends of lmcs_data(): one bin, few bins, slopes of 1 / 8 next to 8, lmcsDeltaCrs at -7 and +7 (vvdec_amd.synth.LMCS_SHAPES)
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+LM = abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE
+
+
+def cscale_indices(d, mapped):
+    """Reshape::calculateChromaAdjVpduNei / getPWLIdxInv (Reshape.cpp:192-280) restated for a picture of one slice and one tile: per transform unit whose chroma
+    residual is scaled, the index of the search BEFORE the clamp to 15 (min_bin .. max_bin + 1), from the luma plane `mapped` (the oracle's, before the inverse
+    map) -> {TU index: search index}"""
+    L, W, H = d.lmcs, int(d.hdr.width), int(d.hdr.height)
+    l2 = int(d.hdr.log2_ctu)
+    n = min(1 << l2, 64)
+    nlog = n.bit_length() - 1
+    cu_at = np.full((d.h4, d.w4), -1, np.int64)
+    for k, cu in enumerate(d.cu):
+        if cu["tree"] != abi.TREE_CHROMA:
+            cu_at[int(cu["y"]) >> 2:(int(cu["y"]) + int(cu["h"]) + 3) >> 2, int(cu["x"]) >> 2:(int(cu["x"]) + int(cu["w"]) + 3) >> 2] = k
+    Y = mapped.astype(np.int64)
+    pivot = [int(v) for v in L.pivot]
+    out, memo = {}, {}
+    for t, tu in enumerate(d.tu):
+        cu = d.cu[int(tu["cu"])]
+        if not (int(tu["comp_mask"]) & 6) or not (int(cu["flags"]) & abi.CU_ROOT_CBF) or not ((int(tu["cbf"]) & 6) or int(tu["joint_cbcr"])):
+            continue
+        w, h = (int(cu["w"]), int(cu["h"])) if int(cu["isp_mode"]) else (int(tu["w"]), int(tu["h"]))
+        if (w >> 1) * (h >> 1) <= 4:
+            continue
+        key = (int(tu["x"]) & ~(n - 1), int(tu["y"]) & ~(n - 1))
+        if key not in memo:
+            tl = int(cu_at[key[1] >> 2, key[0] >> 2])
+            x, y = int(d.cu["x"][tl]), int(d.cu["y"][tl])
+            left = x > 0 and not (((x - 1) >> l2) == (x >> l2) and cu_at[y >> 2, (x - 1) >> 2] > tl)
+            above = y > 0 and not (((y - 1) >> l2) == (y >> l2) and cu_at[(y - 1) >> 2, x >> 2] > tl)
+            s = 0
+            if left:
+                s += int(Y[np.minimum(y + np.arange(n), H - 1), x - 1].sum())
+            if above:
+                s += int(Y[y - 1, np.minimum(x + np.arange(n), W - 1)].sum())
+            v = (s + (1 << nlog)) >> (nlog + 1) if left and above else (s + (1 << (nlog - 1))) >> nlog if left or above else 1 << (int(d.hdr.bit_depth) - 1)
+            idx = int(L.min_bin)
+            while idx <= int(L.max_bin) and v >= pivot[idx + 1]:
+                idx += 1
+            memo[key] = idx
+        out[t] = memo[key]
+    return out
+
+
+def longest_flat_run(a):
+    a = np.asarray(a, np.int64)
+    edges = np.flatnonzero(np.diff(a) != 0)
+    return int(np.diff(np.concatenate([[-1], edges, [len(a) - 1]])).max())
+
+
+def _lmcs_present(c, d, refs, st):
+    L, bd = d.lmcs, c.bd
+    lo, hi = int(L.min_bin), int(L.max_bin)
+    org = (1 << bd) // 16
+    cw = [int(L.pivot[i + 1]) - int(L.pivot[i]) for i in range(16)]
+    assert d.hdr.tool_flags & LM == LM
+    mapped = refdrv.oracle_reconstruct(d, refs, flags=refdrv.STOP_AFTER_RECO | refdrv.ORACLE_MAPPED_LUMA)
+    idx = cscale_indices(d, mapped[0])
+    n_fall, n_min, n_15 = (sum(1 for v in idx.values() if cond(v)) for cond in (lambda v: v == hi + 1, lambda v: v == lo, lambda v: min(v, 15) == 15))
+    factors = {int(L.chroma_scale[min(v, 15)]) for v in idx.values()}
+    fwd, inv = np.ctypeslib.as_array(L.fwd_lut)[:1 << bd], np.ctypeslib.as_array(L.inv_lut)[:1 << bd]
+    c.found = dict(scaled_tus=len(idx), index_max_bin_plus_1=n_fall, index_min_bin=n_min, index_15=n_15, factors=sorted(factors),
+                   fwd_flat_run=longest_flat_run(fwd), fwd_step=int(np.diff(fwd.astype(int)).max()), inv_flat_run=longest_flat_run(inv), inv_step=int(np.diff(inv.astype(int)).max()))
+    shape = c.shape
+    assert len(idx) > 20
+    if shape in ("single_bin_low", "single_bin_high", "late_early"):      # few bins: the search starts above 0, and falls through to the zero bin
+        assert lo > 0 and hi < 15 and n_fall > 0 and n_min > 0, c.found
+        assert 1 << 11 in factors and int(L.chroma_scale[hi + 1]) == 1 << 11, "the zero-code-word bin's entry is not used"
+    if shape in ("single_bin_low", "single_bin_high"):
+        assert lo == hi and cw[lo] == 8 * org - 1
+    if shape in ("single_bin_low", "single_bin_high"):      # forward slope 8 inside the bin and 0 outside, inverse slope 1 / 8
+        assert c.found["fwd_step"] >= 8 and c.found["fwd_flat_run"] >= 8 and c.found["inv_flat_run"] >= 8, c.found
+    if shape == "sawtooth":      # slopes of 8 and of 1 / 8 next to each other: steps and flat stretches in both tables
+        assert c.found["fwd_step"] >= 8 and c.found["inv_step"] >= 8 and c.found["fwd_flat_run"] >= 8 and c.found["inv_flat_run"] >= 8, c.found
+    if shape == "sawtooth":
+        assert hi == 15 and n_15 > 0 and min(cw) == org >> 3 and max(cw) >= 7 * org, c.found
+        assert any(cw[i] == org >> 3 and cw[i + 1] >= 7 * org for i in range(15))
+    if shape == "crs_low":       # lmcsCW + lmcsDeltaCrs at OrgCW >> 3: the largest factor there is
+        assert int(L.model_delta_crs) == -7 and 16384 in factors and max(int(v) for v in L.chroma_scale) == 16384, c.found
+        # |residual| is clipped to 1 << bd before the factor (AreaBuf::scaleSignal, Buffer.cpp:412): 8 << bd at most comes out, which the +-32768 clip
+        # behind it never sees; what saturated levels at this factor do reach is the sample clip on both sides, in both chroma planes
+        assert int(np.abs(d.coef).max()) == 32767 and holds_both_ends(st(refdrv.STOP_AFTER_RECO)[1:], bd)
+    if shape == "crs_high":      # lmcsCW + lmcsDeltaCrs at ( OrgCW << 3 ) - 1: the smallest
+        assert int(L.model_delta_crs) == 7 and min(int(v) for v in L.chroma_scale) == 256 and 256 in factors, c.found
+        assert int(np.abs(d.coef).max()) == 32767
+    if shape == "nearly_identity_full":
+        assert (lo, hi) == (0, 15) and int(L.pivot[16]) == (1 << bd) - 1 and cw == [org] * 15 + [org - 1]
+    if c.slice_type == B:
+        assert int(((d.cu["flags"] & abi.CU_CIIP) != 0).sum()) > 0 and int((d.cu["pred_mode"] == abi.PRED_INTRA).sum()) > 0
+        assert min(int(r[0].min()) for r in refs.values()) == 0 and max(int(r[0].max()) for r in refs.values()) == (1 << bd) - 1
+    if not (int(d.hdr.tool_flags) & abi.TOOL_DEBLOCK_OFF):
+        assert differ(st(refdrv.STOP_AFTER_DBK), st(refdrv.STOP_AFTER_RECO)), "deblocking changes nothing"
+
+
+LMCS_MIX = dict(RESI, p_jccr=0.2, p_cclm=0.2)
+LMCS_MIX_B = dict(LMCS_MIX, p_ciip=0.3, p_intra=0.3, p_bi=0.6)
+
+
+def _lmcs_case(id, shape, seed, slice_type, tools, W=256, H=128, l2=7, bd=10, saturate=False, kinds=("noise", "checker"), **kw):
+    @case(id, "lmcs_model", _lmcs_present, bd=bd, l2=l2)
+    def make(extreme=True):
+        d, refs = one_picture(W, H, l2, seed, tools | LM, kinds, slice_type=slice_type, bd=bd, lmcs_shape=synth.LMCS_SHAPES[shape] if extreme else 0,
+                              **dict(LMCS_MIX if slice_type == I else LMCS_MIX_B, **kw))
+        if saturate and extreme:
+            _saturate(d)
+        return d, refs
+    CASES[-1].shape, CASES[-1].slice_type = shape, slice_type
+
+
+_lmcs_case("lmcs_single_bin_low_i", "single_bin_low", 3701, I, TOOLS_I)
+_lmcs_case("lmcs_single_bin_high_b_ctu64", "single_bin_high", 3702, B, TOOLS_A, l2=6)
+_lmcs_case("lmcs_late_early_b_ctu64", "late_early", 3704, B, TOOLS_A, l2=6, kinds=("flat_max", "flat_zero"), p_bi=0.2)    # (flat pictures: the mean of 128 neighbouring samples reaches both ends)
+_lmcs_case("lmcs_sawtooth_i", "sawtooth", 3704, I, TOOLS_I)
+_lmcs_case("lmcs_sawtooth_b_8bit_ctu64", "sawtooth", 3705, B, no_filters(TOOLS_A), l2=6, bd=8)
+_lmcs_case("lmcs_crs_low_i_saturated_levels", "crs_low", 3706, I, TOOLS_I, saturate=True)
+_lmcs_case("lmcs_crs_high_b_saturated_levels_ctu32", "crs_high", 3707, B, no_filters(TOOLS_A), W=200, H=136, l2=5, saturate=True)
+_lmcs_case("lmcs_nearly_identity_full_b", "nearly_identity_full", 3708, B, no_filters(TOOLS_A), l2=6)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+# chroma QPs that are not the luma QP: mapping tables, PPS / slice / CU-level offsets, the joint Cb-Cr table (vvdec_amd.synth.ChromaQpModel)
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+def chroma_qp_cells(d):
+    """per 4x4 luma cell the [Cb, Cr] QP of the transform unit that owns its chroma (ISP: the last one of the CU), -1 where there is none"""
+    q = np.full((d.h4, d.w4, 2), -1, np.int32)
+    for tu in d.tu:
+        if not int(tu["comp_mask"]) & 6:
+            continue
+        cu = d.cu[int(tu["cu"])]
+        x, y, w, h = (int(cu[k]) for k in "xywh") if int(cu["isp_mode"]) else (int(tu[k]) for k in "xywh")
+        q[y >> 2:(y + h + 3) >> 2, x >> 2:(x + w + 3) >> 2] = tu["qp"][1:3]
+    return q
+
+
+def _cqp_present(c, d, refs, st):
+    m = d.chroma_qp_model
+    qpbd = 6 * (c.bd - 8)
+    own, joint = synth.model_chroma_qps(d)
+    ch = (d.tu["comp_mask"] & 6) != 0
+    j3 = d.tu["joint_cbcr"] == 3
+    q = d.tu["qp"].astype(np.int32)
+    # the description holds what the model gives (the generator's own restatement of QpParam, once more in Python; the reference's QpParam is asked on the CPU leg)
+    assert np.array_equal(q[ch & ~j3][:, 1:3], own[ch & ~j3]) and np.array_equal(q[ch & j3][:, 1], joint[ch & j3]) and np.array_equal(q[ch & j3][:, 2], joint[ch & j3])
+    cu_of = d.tu["cu"].astype(np.int64)
+    n_cb_cr = int((ch & (q[:, 1] != q[:, 2])).sum())
+    n_not_luma = int((ch & ((q[:, 1] != q[:, 0]) | (q[:, 2] != q[:, 0]))).sum())
+    n_joint = int((ch & j3 & (joint != own[:, 0]) & (joint != own[:, 1])).sum())
+    modes = {int(v) for v in d.tu["joint_cbcr"][ch]}
+    apart = ch & (np.abs(own[:, 0] - own[:, 1]) >= 6) & (np.abs(own[:, 0] - joint) >= 6) & (np.abs(own[:, 1] - joint) >= 6)
+    n_isp = int((ch & (q[:, 1] != q[:, 0]) & (d.cu["isp_mode"][cu_of] != 0)).sum())
+    n_tree = int((ch & (q[:, 1] != q[:, 0]) & (d.cu["tree"][cu_of] == abi.TREE_CHROMA)).sum())
+    cells = chroma_qp_cells(d)
+    far = 0
+    for dr in range(2):
+        a, b = (cells[:, 1:], cells[:, :-1]) if dr == 0 else (cells[1:, :], cells[:-1, :])
+        bs = d.lfp[dr]["bs"].reshape(d.h4, d.w4)
+        bs = bs[:, 1:] if dr == 0 else bs[1:, :]
+        for k in range(2):
+            far += int(((a[..., k] >= 0) & (b[..., k] >= 0) & (np.abs(a[..., k] - b[..., k]) >= 12) & (((bs >> (2 * (k + 1))) & 3) > 0)).sum())
+    c.found = dict(chroma_tus=int(ch.sum()), cb_differs_from_cr=n_cb_cr, chroma_differs_from_luma=n_not_luma, joint_mode_3_differs_from_both=n_joint,
+                   cb_cr_joint_pairwise_6_apart=int(apart.sum()), isp_tus_among_them=n_isp, chroma_tree_tus_among_them=n_tree, filtered_chroma_edges_12_apart=far,
+                   chroma_qp_min_max=[int(q[ch][:, 1:3].min()), int(q[ch][:, 1:3].max())])
+    assert n_cb_cr > 0 and n_not_luma > 0, c.found
+    want = c.want
+    if "jccr" in want:
+        assert modes >= {0, 1, 2, 3} and n_joint > 0, (sorted(modes), c.found)
+        assert 2 * int(apart.sum()) > int(ch.sum()), "Cb, Cr and joint QPs are not 6 apart on most transform units: %r" % c.found
+        b = _blocks(d)
+        assert {abi.MTS_SKIP, abi.MTS_DCT2} <= {int(tu["mts_idx"][comp]) for w, h, comp, tu, cu in b if comp} and any(int(cu["bdpcm"][1]) for w, h, comp, tu, cu in b if comp)
+        assert any(int(cu["lfnst_idx"]) for w, h, comp, tu, cu in b) and far > 0
+    if "clip" in want:
+        lum = q[ch][:, 0] - qpbd
+        assert int(lum.min()) >= 24 and int(lum.max()) <= 40
+        for k in (1, 2):
+            assert int(q[ch][:, k].min()) == 0 and int(q[ch][:, k].max()) == 63 + qpbd, c.found
+        assert far > 0
+    if "dual_tree" in want:
+        assert n_tree > 0 and int((d.cu["tree"] == abi.TREE_LUMA).sum()) > 0, c.found
+    if "isp" in want:
+        assert n_isp > 0, c.found
+    if "deblock" in want:
+        # luma QPs at which tc = 0 (below 18 with the offsets at 0: tcTable, LoopFilter.cpp:73), chroma QPs at which the chroma filters run
+        assert int(d.cu["qp"].max()) <= 17 and int(q[ch][:, 1:3].min()) - qpbd >= 40 and all(int(v) == 0 for v in d.hdr.deblock_tc_offset_div2)
+        a, bb = st(refdrv.STOP_AFTER_RECO), st(refdrv.STOP_AFTER_DBK)
+        assert not differ(a[:1], bb[:1]), "the luma deblocking is not off at these QPs"
+        for k in (1, 2):
+            chc = a[k] != bb[k]
+            gy, gx = np.mgrid[0:chc.shape[0], 0:chc.shape[1]]
+            one_dir = (((gx & 7) == 1) | ((gx & 7) == 2) | ((gx & 7) == 5) | ((gx & 7) == 6)) & ((gy & 7) >= 3) & ((gy & 7) <= 4)
+            assert int((chc & one_dir).sum()) > 0, "no strong chroma filter in component %d" % k
+
+
+CQP_MIX = dict(RESI, p_coded_chroma=0.9, p_jccr=0.5, p_cclm=0.2)
+
+
+def _cqp_case(id, want, seed, model, slice_type, tools, flavour=0, W=256, H=128, l2=7, bd=10, kinds=("noise", "checker"), post=None, **kw):
+    @case(id, "chroma_qp", _cqp_present, derive_lfp=True, bd=bd, l2=l2)
+    def make(extreme=True):
+        d, refs = one_picture(W, H, l2, seed, tools, kinds, slice_type=slice_type, bd=bd, chroma_qp_model=model if extreme else 0, chroma_qp_flavour=flavour if extreme else 0,
+                              **dict(CQP_MIX, **kw))
+        if post:
+            post(d, extreme)
+        return d, refs
+    CASES[-1].want = want
+
+
+def _zero_tc_offsets(d, extreme):
+    for k in range(3):
+        d.hdr.deblock_tc_offset_div2[k] = d.hdr.deblock_beta_offset_div2[k] = 0
+
+
+_cqp_case("chroma_qp_every_residual_tool_jccr_b", ("jccr",), 3801, 41, B, TOOLS_A, p_sbt=0.2, p_intra=0.4)
+_cqp_case("chroma_qp_8bit_ctu64_no_dep_quant_scaling_lists", ("jccr",), 3802, 42, B, (TOOLS_A & ~abi.TOOL_DEP_QUANT) | abi.TOOL_SCALING_LIST, l2=6, bd=8, p_sbt=0.2, p_intra=0.4)
+_cqp_case("chroma_qp_both_clips_luma_in_the_middle", ("clip",), 3803, 43, I, TOOLS_I, flavour=synth.CQP_CLIP)
+_cqp_case("chroma_qp_dual_tree", ("dual_tree",), 3804, 44, I, TOOLS_I, l2=6, dual_tree=1.0)
+_cqp_case("chroma_qp_isp_last_tu_ctu32", ("isp",), 3805, 45, I, TOOLS_I, W=200, H=136, l2=5, p_isp=0.6, p_mrl=0.0, p_bdpcm=0.0, p_mip=0.0)
+_cqp_case("chroma_qp_deblock_steps_luma_off_chroma_strong", ("deblock",), 3808, 46, B, TOOLS, flavour=synth.CQP_LIFTED, kinds=("steps",), post=_zero_tc_offsets, base_qp=14,
+          **dict(COPY, p_coded=0.5, p_coded_chroma=0.4, p_split_scale=0.45, p_small_corner=1.0, p_jccr=0.1))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+# min_qp_ts above 4: transform-skip and BDPCM blocks below, on and above the bound (per / rem of the raised QP)
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+def _ts_present(c, d, refs, st):
+    bound = int(d.hdr.min_qp_ts)
+    assert bound == c.min_qp_ts
+    n = {(ch, g): 0 for ch in ("luma", "chroma") for g in ("below", "on", "above")}
+    bdpcm = {"luma": 0, "chroma": 0}
+    for w, h, comp, tu, cu in _blocks(d):
+        if int(tu["mts_idx"][comp]) != abi.MTS_SKIP:
+            continue
+        qp, ch = int(tu["qp"][comp]), "chroma" if comp else "luma"
+        n[(ch, "below" if qp < bound else "on" if qp == bound else "above")] += 1
+        bdpcm[ch] += int(cu["bdpcm"][1 if comp else 0] != 0)
+    c.found = dict({"%s_%s" % k: v for k, v in n.items()}, bdpcm_luma=bdpcm["luma"], bdpcm_chroma=bdpcm["chroma"])
+    assert all(v > 0 for v in n.values()) and bdpcm["luma"] > 0 and bdpcm["chroma"] > 0, c.found
+
+
+def _whole_range(d, bound):
+    """CU QPs over -QpBdOffset .. 63, every third one on the bound (identity chroma mapping: TU.qp of all three components is QP + QpBdOffset)"""
+    qpbd = 6 * (int(d.hdr.bit_depth) - 8)
+    k = np.arange(len(d.cu))
+    synth.rewrite_qp(d, np.where(k % 3 == 0, bound - qpbd, (k * 7) % (64 + qpbd) - qpbd))
+
+
+def _ts_case(id, seed, min_qp_ts, bd, tools, l2=7, **kw):
+    @case(id, "ts_min_qp", _ts_present, bd=bd, l2=l2)
+    def make(extreme=True):
+        d, refs = one_picture(256, 128, l2, seed, tools, slice_type=I, bd=bd, min_qp_ts=min_qp_ts if extreme else 4, **dict(RESI, p_ts=0.5, p_bdpcm=0.4, p_split_scale=1.4, **kw))
+        _whole_range(d, min_qp_ts)
+        return d, refs
+    CASES[-1].min_qp_ts = min_qp_ts
+
+
+_ts_case("ts_min_qp_16_10bit", 3901, 16, 10, TOOLS_I)
+_ts_case("ts_min_qp_52_10bit_ctu64_no_dep_quant", 3902, 52, 10, TOOLS_I & ~abi.TOOL_DEP_QUANT, l2=6)
+_ts_case("ts_min_qp_10_8bit_scaling_lists", 3903, 10, 8, TOOLS_I | abi.TOOL_SCALING_LIST)
 
 
 FAMILIES = sorted({c.family for c in CASES})

@@ -92,6 +92,30 @@ API int vvr_submit( vvr_context* c, const vvr_picture* pic )
       if( bad ) { c->err = "motion vector outside the 18-bit range"; return VVR_ERR_PARAMETER; }
     }
   }
+  // QPs, min_qp_ts and the LMCS tables: what vvr_prepare refuses (vvdec_amd/csrc/vvr_prepare.cpp) is refused here, with the same words
+  {
+    const int bd = h.bit_depth, qpBd = 6 * ( bd - 8 );
+    uint32_t tools = h.tool_flags;
+    if( pic->slices ) for( uint32_t i = 0; i < pic->num_slices; i++ ) tools |= pic->slices[i].tool_flags & VVR_TOOL_LMCS;
+    if( h.min_qp_ts < 4 || h.min_qp_ts > 52 || ( h.min_qp_ts - 4 ) % 6 ) { c->err = "min_qp_ts: 4 + 6k with k in 0 .. 8"; return VVR_ERR_PARAMETER; }
+    if( ( tools & VVR_TOOL_LMCS ) && pic->lmcs )
+    {
+      const vvr_lmcs_params& L = *pic->lmcs;
+      for( int v = 0; v < ( 1 << bd ); v++ ) if( ( L.fwd_lut[v] | L.inv_lut[v] ) < 0 || ( L.fwd_lut[v] | L.inv_lut[v] ) >= ( 1 << bd ) ) { c->err = "LMCS: fwd_lut / inv_lut entry outside 0 .. ( 1 << bit depth ) - 1"; return VVR_ERR_PARAMETER; }
+      if( L.min_bin < 0 || L.min_bin > 15 || L.max_bin < 0 || L.max_bin > 15 ) { c->err = "LMCS: min_bin / max_bin outside 0 .. 15"; return VVR_ERR_PARAMETER; }
+      if( L.min_bin > L.max_bin ) { c->err = "LMCS: min_bin above max_bin"; return VVR_ERR_PARAMETER; }
+      for( int i = 0; i < 17; i++ ) if( L.pivot[i] < 0 || L.pivot[i] > ( 1 << bd ) || ( i && L.pivot[i] < L.pivot[i - 1] ) ) { c->err = "LMCS: pivot decreasing or outside 0 .. 1 << bit depth"; return VVR_ERR_PARAMETER; }
+      for( int i = 0; i < 16; i++ ) if( L.chroma_scale[i] <= 0 ) { c->err = "LMCS: chroma_scale entry not positive"; return VVR_ERR_PARAMETER; }
+    }
+    for( uint32_t k = 0; k < pic->num_cu && pic->cu && pic->tu; k++ )
+    {
+      const vvr_cu& u = pic->cu[k];
+      if( u.qp < -qpBd || u.qp > 63 ) { c->err = "cu.qp outside -QpBdOffset .. 63"; return VVR_ERR_PARAMETER; }
+      for( uint32_t t = u.first_tu; t < u.first_tu + u.num_tu && t < pic->num_tu; t++ )
+        for( int comp = 0; comp < ( h.chroma_format ? 3 : 1 ); comp++ )
+          if( ( pic->tu[t].comp_mask & ( 1 << comp ) ) && ( pic->tu[t].qp[comp] < 0 || pic->tu[t].qp[comp] > 63 + qpBd ) ) { c->err = "tu.qp outside 0 .. 63 + QpBdOffset"; return VVR_ERR_PARAMETER; }
+    }
+  }
   vvr_picture P = *pic;
   std::vector<vvr_cu> cuCopy;
   if( const char* e = getenv( "VVR_ORACLE_NO_DMVR" ) )      // developer aid: 1 = every DMVR CU predicted without the refinement; 2 = only those whose MVs leave the picture by more than a CTU

@@ -9,7 +9,8 @@ from vvdec_amd import abi
 
 _LIB = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "libvvref.so")
 SIMD, DERIVE_LFP, STOP_AFTER_RECO, STOP_AFTER_DBK, STOP_AFTER_SAO, SPAN_AFFINE = 1, 2, 4, 8, 16, 32
-ROTATE_REF_LISTS = 64      # VVREF_ROTATE_REF_LISTS: every slice holds the description's reference lists rotated by its index (the extractor merges them again)
+ORACLE_MAPPED_LUMA = 256   # VVO_MAPPED_LUMA (oracle_reconstruct with STOP_AFTER_RECO only): the luma plane before the inverse LMCS map
+ROTATE_REF_LISTS = 64     # VVREF_ROTATE_REF_LISTS: every slice holds the description's reference lists rotated by its index (the extractor merges them again)
 _lib = None
 
 
@@ -24,6 +25,13 @@ def lib():
         _lib.vvref_reconstruct.restype = C.c_int
         _lib.vvref_last_error.restype = C.c_char_p
     return _lib
+
+
+def _install_model(L, desc):
+    """the chroma QP model a picture was generated with (vvdec_amd.synth.ChromaQpModel, beside the description) into the harness, or none: with one, the
+    harness fills the reference's parameter sets from it, lets QpParam derive every TransformUnit::chromaQp and fails where the description holds another"""
+    m = getattr(desc, "chroma_qp_model", None)
+    L.vvref_set_chroma_qp_model(C.byref(m) if m is not None else None)
 
 
 def reconstruct(desc, refs=None, flags=0, want_lfp=False, want_dmvr=0):
@@ -51,6 +59,7 @@ def reconstruct(desc, refs=None, flags=0, want_lfp=False, want_dmvr=0):
             lfp_ptrs[d] = lfps[d].ctypes.data_as(C.POINTER(abi.Lfp))
     dmvr = np.zeros((max(1, want_dmvr), 2), np.int32)
     ms = (C.c_double * 8)()
+    _install_model(L, desc)
     rc = L.vvref_reconstruct(C.byref(p), ref_ptrs, out_ptrs, lfp_ptrs if want_lfp else None,
                              dmvr.ctypes.data_as(C.POINTER(C.c_int32)) if want_dmvr else None, flags, ms)
     if rc != 0:
@@ -72,6 +81,7 @@ def reconstruct_threaded(desc, refs=None, threads=4):
         out_ptrs[c] = outs[c].ctypes.data_as(C.POINTER(C.c_uint16))
     ms = C.c_double()
     L.vvref_reconstruct_threaded.restype = C.c_int
+    _install_model(L, desc)
     rc = L.vvref_reconstruct_threaded(C.byref(p), ref_ptrs, out_ptrs, int(threads), C.byref(ms))
     if rc != 0:
         raise RuntimeError("vvref_reconstruct_threaded failed: " + L.vvref_last_error().decode())
@@ -102,6 +112,7 @@ def reconstruct_with_motion(desc, refs=None, flags=0):
         out_ptrs[c] = outs[c].ctypes.data_as(C.POINTER(C.c_uint16))
     motion = np.zeros(desc.w4 * desc.h4, np.dtype(abi.Motion))
     L.vvref_reconstruct_with_motion.restype = C.c_int
+    _install_model(L, desc)
     rc = L.vvref_reconstruct_with_motion(C.byref(p), ref_ptrs, out_ptrs, motion.ctypes.data_as(C.c_void_p), flags)
     if rc != 0:
         raise RuntimeError("vvref_reconstruct_with_motion failed: " + L.vvref_last_error().decode())
@@ -135,6 +146,7 @@ def run_binding(desc, refs, backend_path, num_slots=8, flags=0):
     motion = np.zeros(desc.w4 * desc.h4, np.dtype(abi.Motion))
     _bind.vvref_set_extra_flags(flags)
     try:
+        _install_model(_bind, desc)
         rc = _bind.vvref_run_binding(C.byref(p), ref_ptrs, out_ptrs, motion.ctypes.data_as(C.c_void_p), max(num_slots, nslots + 2))
     finally:
         _bind.vvref_set_extra_flags(0)
@@ -172,6 +184,7 @@ def run_dropin(desc, refs, backend_path, threads=2, flags=0):
     motion = np.zeros(desc.w4 * desc.h4, np.dtype(abi.Motion))
     _dropin.vvref_set_extra_flags(flags)              # (e.g. ROTATE_REF_LISTS: what the harness builds, not what the drop-in does)
     try:
+        _install_model(_dropin, desc)
         rc = _dropin.vvref_run_dropin(C.byref(p), ref_ptrs, out_ptrs, motion.ctypes.data_as(C.c_void_p), threads)
     finally:
         _dropin.vvref_set_extra_flags(0)
@@ -195,6 +208,7 @@ def extract(desc, refs=None, flags=0):
             keep.append(a)
             ref_ptrs[slot * 3 + c] = a.ctypes.data_as(C.POINTER(C.c_uint16))
     nd = C.c_uint32()
+    _install_model(L, desc)
     r = L.vvref_extract(C.byref(p), ref_ptrs, C.byref(nd), flags)      # flags: DERIVE_LFP = the reference derives the edge parameters itself
     if not r:
         raise RuntimeError("vvref_extract failed: " + L.vvref_last_error().decode())

@@ -175,6 +175,29 @@ def test_p_slice(built):
     assert not bad, "\n".join(bad)
 
 
+@pytest.mark.parametrize("case_id", ["lmcs_sawtooth_b_8bit_ctu64", "lmcs_crs_low_i_saturated_levels", "chroma_qp_every_residual_tool_jccr_b", "chroma_qp_isp_last_tu_ctu32"])
+def test_side_tables_at_their_limits_survive_the_reference_objects(built, case_id):
+    """cases of tests/limits_cases.py: an LMCS model at the ends of lmcs_data() comes back as the tables Reshape built from it; with a chroma QP model installed
+    TransformUnit::chromaQp is the reference's own QpParam, so the t.qp[1..2] the extractor writes are checked against the model, not against a copy"""
+    import limits_cases as lc
+    case = [c for c in lc.CASES if c.id == case_id][0]
+    d, refs = case.make()
+    e = refdrv.extract(d, refs)
+    bad = _compare(d, e)
+    assert not bad, "\n".join(bad)
+    if case.family == "chroma_qp":
+        own, joint = synth.model_chroma_qps(d)
+        ch, j3 = (d.tu["comp_mask"] & 6) != 0, d.tu["joint_cbcr"] == 3
+        want = np.where(j3[:, None], np.stack([joint, joint], axis=1), own)
+        assert int((want[ch] != d.cu["qp"][d.tu["cu"]][ch, None] + 6 * (case.bd - 8)).sum()) > 0
+        assert np.array_equal(e["tu"]["qp"][ch][:, 1:3], want[ch])
+        # the reference's own derivation of the edge parameters from these TUs (the last TU of an ISP CU owns its chroma QPs)
+        derived = refdrv.extract(d, refs, flags=refdrv.DERIVE_LFP)["lfp"]
+        for k in range(2):
+            edge = (d.lfp[k]["bs"] >> 2) != 0         # where a chroma edge is filtered (the raw tables of the reference hold values elsewhere that no filter reads)
+            assert int(edge.sum()) > 0 and np.array_equal(d.lfp[k]["qp"][edge][:, 1:3], derived[k]["qp"][edge][:, 1:3]), "direction %d: other chroma edge QPs" % k
+
+
 @pytest.mark.parametrize("name,W,H,l2,idx,seed,tools,kw", CASES, ids=[c[0] for c in CASES])
 def test_edge_tables_of_the_reference_drive_the_oracle(built, name, W, H, l2, idx, seed, tools, kw):
     """the way a real integration runs: the reference derives the edge parameters itself (LF_INIT, calcFilterStrengthsCTU), the extractor

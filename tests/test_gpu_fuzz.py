@@ -67,6 +67,13 @@ def _case(rnd, far):
         kw["mv_window_ver"] = rnd.choice([0, 500, 2000, 7000])         # (( H + window ) * 16 stays inside the 18-bit MV range)
         if rnd.random() < 0.3:
             kw["p_mv_limit"] = rnd.choice([0.05, 0.3])                  # components at the ends of that range
+    # the side tables: LMCS models at the ends of lmcs_data(), chroma QPs from mapping tables and offsets, min_qp_ts above 4
+    if rnd.random() < 0.3:
+        kw["lmcs_shape"] = rnd.randrange(1, len(synth.LMCS_SHAPES))
+    if rnd.random() < 0.3:
+        kw["chroma_qp_model"] = rnd.randrange(1, 1 << 30); kw["chroma_qp_flavour"] = rnd.choice([synth.CQP_GENERAL, synth.CQP_GENERAL, synth.CQP_CLIP, synth.CQP_LIFTED])
+    if rnd.random() < 0.3:
+        kw["min_qp_ts"] = 4 + 6 * rnd.randrange(9)
     lists = (rnd.randrange(3, abi.VVR_MAX_REFS + 1), rnd.randrange(3, abi.VVR_MAX_REFS + 1)) if rnd.random() < 0.25 else None       # reference lists of 3 .. 16 entries
     bd = rnd.choice([8, 10, 10]); cf = rnd.choice([1, 1, 1, 0])
     if not cf:

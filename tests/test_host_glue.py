@@ -790,6 +790,49 @@ def test_malformed_descriptions_are_rejected(stub):
     ctx.close()
 
 
+def _first_chroma_tu(d):
+    return int(np.nonzero((d.tu["comp_mask"] & 6) != 0)[0][0])
+
+
+QP_LMCS_REFUSALS = [
+    # QPs index the dequantisation tables and give the shift counts; min_qp_ts replaces the QP of transform-skip blocks
+    ("cu_qp_below_minus_qp_bd_offset", lambda d: d.cu["qp"].__setitem__(0, -13), "cu.qp outside"),
+    ("cu_qp_above_63", lambda d: d.cu["qp"].__setitem__(len(d.cu) - 1, 64), "cu.qp outside"),
+    ("tu_luma_qp_negative", lambda d: d.tu["qp"].__setitem__((0, 0), -1), "tu.qp outside"),
+    ("tu_cb_qp_above_63_plus_qp_bd_offset", lambda d: d.tu["qp"].__setitem__((_first_chroma_tu(d), 1), 76), "tu.qp outside"),
+    ("tu_cr_qp_negative", lambda d: d.tu["qp"].__setitem__((_first_chroma_tu(d), 2), -1), "tu.qp outside"),
+    ("min_qp_ts_0", lambda d: setattr(d.hdr, "min_qp_ts", 0), "min_qp_ts"),
+    ("min_qp_ts_5", lambda d: setattr(d.hdr, "min_qp_ts", 5), "min_qp_ts"),
+    ("min_qp_ts_58", lambda d: setattr(d.hdr, "min_qp_ts", 58), "min_qp_ts"),
+    # the LMCS tables: what the chroma-scale search walks and indexes
+    ("lmcs_min_bin_above_max_bin", lambda d: (setattr(d.lmcs, "min_bin", 9), setattr(d.lmcs, "max_bin", 8)), "LMCS: min_bin above max_bin"),
+    ("lmcs_max_bin_16", lambda d: setattr(d.lmcs, "max_bin", 16), "LMCS: min_bin / max_bin outside"),
+    ("lmcs_min_bin_negative", lambda d: setattr(d.lmcs, "min_bin", -1), "LMCS: min_bin / max_bin outside"),
+    ("lmcs_pivot_decreasing", lambda d: d.lmcs.pivot.__setitem__(8, d.lmcs.pivot[7] - 1), "LMCS: pivot"),
+    ("lmcs_pivot_above_1_shl_bit_depth", lambda d: d.lmcs.pivot.__setitem__(16, 1025), "LMCS: pivot"),
+    ("lmcs_chroma_scale_zero", lambda d: d.lmcs.chroma_scale.__setitem__(15, 0), "LMCS: chroma_scale"),
+    ("lmcs_chroma_scale_negative", lambda d: d.lmcs.chroma_scale.__setitem__(0, -2048), "LMCS: chroma_scale"),
+    ("lmcs_fwd_lut_entry_1024", lambda d: d.lmcs.fwd_lut.__setitem__(1023, 1024), "LMCS: fwd_lut / inv_lut"),
+    ("lmcs_inv_lut_entry_negative", lambda d: d.lmcs.inv_lut.__setitem__(0, -1), "LMCS: fwd_lut / inv_lut"),
+]
+
+
+@pytest.mark.parametrize("name,mutate,text", QP_LMCS_REFUSALS, ids=[r[0] for r in QP_LMCS_REFUSALS])
+def test_qp_and_lmcs_fields_out_of_range_are_rejected(stub, name, mutate, text):
+    """a QP outside its range gives a negative rem / per in the dequantisation (an index before the scale table, a negative shift count), an LMCS table that
+    Reshape::constructReshaper could not have built an index beyond chroma_scale[16] or the LUTs: refused with VVR_ERR_PARAMETER and the field's name, and the
+    same description without the one change is accepted"""
+    W, H = 128, 64
+    plans, nslots = stream.ra_plan(1, gop=1, seed_poc0_is_external=False)
+    ctx = Ctx(stub, W, H, nslots)
+    mk = lambda: synth.picture_for_plan(plans[0], W, H, seed=611, tool_flags=TOOLS | abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE, p_coded=0.8, p_coded_chroma=0.8)
+    d = mk()
+    mutate(d)
+    _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, text)
+    stub.vvr_free_prepared(ctx.ctx, ctx.prepare(mk()))
+    ctx.close()
+
+
 def test_slice_headers_in_the_host_glue(stub):
     """slices with headers of their own: the chroma blocks' residual-scaling flag follows the slice of the CTU, the intra tables stay valid, and
     headers that do not fit the picture are refused"""

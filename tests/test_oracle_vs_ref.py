@@ -224,7 +224,9 @@ def test_edge_parameters_match_reference_derivation(built):
 
 
 def test_oracle_equals_reference_random_sweep(built):
-    """a fixed-seed slice of tools/fuzz_oracle_vs_ref.py: random tool combinations, sizes, CTU sizes, sample formats and stages"""
+    """a fixed-seed slice of tools/fuzz_oracle_vs_ref.py: random tool combinations, sizes, CTU sizes, sample formats and stages - and, for about a third of
+    the pictures each, an LMCS model at the ends of lmcs_data(), a chroma QP model (tests/refdrv.py installs it into the reference's parameter sets, whose own
+    QpParam then derives the chroma QPs; without that the reference would see the identity mapping) and min_qp_ts above 4"""
     import importlib.util, os
     spec = importlib.util.spec_from_file_location("fuzz_oracle_vs_ref", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "fuzz_oracle_vs_ref.py"))
     fz = importlib.util.module_from_spec(spec)

@@ -1,6 +1,7 @@
 """CPU: the plain-C oracle against the real reference classes at the ends of the value ranges - QPs from -QpBdOffset to 63, reference pictures that alternate
 between 0 and the largest sample value, prediction weights, ALF / CC-ALF taps and deblocking offsets at the limits of their syntax, reference lists of 16 entries,
-motion vectors over the 18-bit range (tests/limits_cases.py).
+motion vectors over the 18-bit range, LMCS models at the ends of lmcs_data(), chroma QPs from mapping tables and offsets (installed into the reference's parameter
+sets, so that its own QpParam derives them), min_qp_ts above 4 (tests/limits_cases.py).
 Every input of tests/test_gpu_limits.py is pinned here first, so a GPU failure there says that the kernel is wrong, not the oracle.  Skipped where oracle/_ref
 is not built, like tests/test_oracle_vs_ref.py."""
 import numpy as np
@@ -51,6 +52,46 @@ def test_the_limits_matter(built, case):
     final = refdrv.oracle_reconstruct(d, refs)
     other = refdrv.oracle_reconstruct(d2, refs2)
     assert lc.differ(final, other), "the picture does not depend on its extreme"
+
+
+LMCS_CASES = [c for c in lc.CASES if c.family == "lmcs_model"]
+CQP_CASES = [c for c in lc.CASES if c.family == "chroma_qp"]
+
+
+@pytest.mark.parametrize("case", LMCS_CASES, ids=[c.id for c in LMCS_CASES])
+def test_lmcs_tables_of_the_shapes_are_the_references(built, case):
+    """the tables the generator builds from each named model are the ones the reference's Reshape builds from the same model (integration/vvr_extract.h reads
+    them out of the Reshape object): forward and inverse map, chroma scale factors, pivots, the two bin indices"""
+    d, refs = case.make()
+    got, want, n = refdrv.extract(d, refs)["lmcs"], d.lmcs, 1 << case.bd
+    for name, count in (("fwd_lut", n), ("inv_lut", n), ("chroma_scale", 16), ("pivot", 17)):
+        a, b = np.ctypeslib.as_array(getattr(got, name))[:count], np.ctypeslib.as_array(getattr(want, name))[:count]
+        assert np.array_equal(a, b), "%s: %d entries differ, the first at %d" % (name, int((a != b).sum()), int(np.flatnonzero(a != b)[0]))
+    assert (int(got.min_bin), int(got.max_bin)) == (int(want.min_bin), int(want.max_bin))
+
+
+@pytest.mark.parametrize("case", CQP_CASES, ids=[c.id for c in CQP_CASES])
+def test_chroma_qps_of_the_model_are_qp_params(built, case):
+    """with the model installed the harness asks the reference's QpParam for every TransformUnit::chromaQp and refuses a description that holds another value:
+    the generator's restatement of QpParam is pinned TU by TU, and the QPs the reference dequantises with are the description's.  The glue hands them back."""
+    d, refs = case.make()
+    e = refdrv.extract(d, refs)
+    ch = (d.tu["comp_mask"] & 6) != 0
+    assert len(e["tu"]) == len(d.tu) and np.array_equal(e["tu"]["qp"][ch], d.tu["qp"][ch])
+    t = int(np.flatnonzero(ch)[len(np.flatnonzero(ch)) // 2])
+    for comp, delta in ((1, 1), (2, -1)):
+        keep = int(d.tu["qp"][t, comp])
+        d.tu["qp"][t, comp] = keep + delta if 0 <= keep + delta <= 63 + 6 * (case.bd - 8) else keep - delta
+        with pytest.raises(RuntimeError, match="chroma QP model: QpParam gives %d" % keep):
+            refdrv.reconstruct(d, refs, flags=refdrv.STOP_AFTER_RECO)
+        d.tu["qp"][t, comp] = keep
+    # and without the model the reference sees the identity mapping: another picture
+    model, d.chroma_qp_model = d.chroma_qp_model, None
+    try:
+        other = refdrv.reconstruct(d, refs, flags=refdrv.STOP_AFTER_RECO)["planes"]
+    finally:
+        d.chroma_qp_model = model
+    assert lc.differ(other[1:], refdrv.oracle_reconstruct(d, refs, flags=refdrv.STOP_AFTER_RECO)[1:]), "the reference's dequantisation does not see the chroma QPs"
 
 
 def test_collocated_motion_at_the_limit_on_the_cpu(built):

@@ -88,7 +88,23 @@ typedef struct vvs_params {
   uint16_t mv_window_ver;       // the same above / below, with and without wrap_offset (0: none)
   float    p_mv_limit;          // of the components of a drawn vector (per list, per direction): replaced by one of -2^17, -2^17 + k, 2^17 - 1 - k, 2^17 - 1 with k < 32, the
                                 // ends of the 18-bit MV storage range; draws of a generator of its own, so the rest of the picture stays as it is without them
+  uint8_t  lmcs_shape;          // 0: the LMCS model as drawn; else one of the named models at the ends of lmcs_data() (VVS_LMCS_*), built from the syntax-level model like the drawn one
+  uint8_t  min_qp_ts;           // header field of the same name (4 + 6 * sps_internal_bit_depth_minus_input_bit_depth): 4 + 6k, k in 0 .. 8
+  uint8_t  chroma_qp_flavour;   // with chroma_qp_model: 0 mapping tables of three kinds (the 4:2:0 default shape, a steep one, a plateau) and offsets that keep Cb, Cr and joint apart;
+                                // 1 tables of slope 16 and offsets of +-12: chroma QPs run into both clips from luma QPs in the middle; 2 tables lifted by 28 .. 36: high chroma QPs from low luma QPs
+  uint32_t chroma_qp_model;     // 0: identity chroma QP mapping, zero offsets; else the seed of a model (vvs_chroma_qp, draws of a generator of its own) applied the way QpParam does (Quant.cpp:65-91)
 } vvs_params;
+
+enum { VVS_LMCS_DRAWN = 0, VVS_LMCS_SINGLE_BIN_LOW, VVS_LMCS_SINGLE_BIN_HIGH, VVS_LMCS_LATE_EARLY, VVS_LMCS_SAWTOOTH, VVS_LMCS_CRS_LOW, VVS_LMCS_CRS_HIGH, VVS_LMCS_NEARLY_IDENTITY_FULL, VVS_LMCS_NUM_SHAPES };
+
+// what the SPS / PPS / slice header / CUs of a stream would carry about chroma QPs; generator-side only (the description holds the resulting TU QPs)
+typedef struct vvs_chroma_qp {
+  int8_t   table[3][76];        // Cb, Cr, joint Cb-Cr: mapped QP of luma QP q at [q + QpBdOffset], q = -QpBdOffset .. 63, non-decreasing, values in -QpBdOffset .. 63
+  int8_t   pps_offset[3], slice_offset[3];      // per table; the sum of the two lies in -12 .. 12
+  int8_t   list[6][3];          // pps_cb / cr / joint_cbcr_qp_offset_list, entries in -12 .. 12
+  uint32_t num_cu;
+  uint8_t* cu_idx;              // [max_cu], caller-allocated: per CU 0 (no entry of the list) or 1 + index into the list (CodingUnit::chromaQpAdj)
+} vvs_chroma_qp;
 
 typedef struct vvs_buffers {     // caller-allocated, sized with vvs_bounds()
   vvr_cu*      cu;      uint32_t max_cu;
@@ -106,6 +122,7 @@ typedef struct vvs_buffers {     // caller-allocated, sized with vvs_bounds()
   uint16_t*    ctu_slice;         // [num_ctu], filled when the parameters ask for more than one slice (else left alone)
   uint16_t*    ctu_tile;          // [num_ctu], likewise for tiles
   vvr_subpic*  subpics;           // [up to 255], filled when the parameters ask for sub-pictures
+  vvs_chroma_qp* cqp;             // filled when the parameters ask for a chroma QP model
   // outputs
   uint32_t     num_cu, num_tu; uint64_t num_coef; uint32_t num_dmvr; uint32_t num_subpics;
   vvr_pic_header hdr;
@@ -126,7 +143,7 @@ void vvs_default_params( vvs_params* P )
 {
   memset( P, 0, sizeof( *P ) );
   P->seed = 1234; P->width = 3840; P->height = 2160; P->bit_depth = 10; P->log2_ctu = 7; P->chroma_format = 1; P->slice_type = 0;
-  P->base_qp = 32; P->min_cu_log2 = 3;
+  P->base_qp = 32; P->min_cu_log2 = 3; P->min_qp_ts = 4;
   P->p_intra = 0.15f; P->p_bi = 0.6f; P->p_coded = 0.35f; P->p_coded_chroma = 0.2f; P->p_small_corner = 0.8f; P->p_mts = 0.15f; P->p_ts = 0.03f; P->p_lfnst = 0.2f;
   P->p_split_scale = 1.0f; P->mv_sigma = 8.0f; P->p_sao = 0.4f; P->p_alf_luma = 0.8f; P->p_alf_chroma = 0.5f; P->p_ccalf = 0.3f; P->p_imv_hpel = 0.1f; P->p_jccr = 0.1f; P->p_mrl = 0.15f; P->p_bdpcm = 0.03f;
   P->p_affine = 0.0f; P->p_geo = 0.0f; P->p_ciip = 0.0f; P->p_sbtmvp = 0.0f; P->p_bcw = 0.05f; P->p_cclm = 0.0f; P->p_mip = 0.0f; P->p_sbt = 0.0f; P->p_isp = 0.0f; P->dual_tree = 0.0f; P->p_ibc = 0.0f;
@@ -947,8 +964,10 @@ struct Gen {
         // an edge on a slice / tile boundary the loop filters must not cross is not filtered (m_stLFCUParam.leftEdge / topEdge, LoopFilter.cpp:1078,1088)
         if( !lfMayCross( ctuOfPos( x4 << 2, y4 << 2 ), ctuOfPos( px4 << 2, py4 << 2 ) ) || onVirtualBoundary( d, x4, y4 ) ) { L.bs = 0; L.flags &= (uint8_t) ~3; }
         L.qp[0] = (int8_t) ( ( CQ.qp + CP.qp + 1 ) >> 1 );
-        L.qp[1] = (int8_t) ( ( TQc.qp[1] + TPc.qp[1] - 2 * qpBd + 1 ) >> 1 );
-        L.qp[2] = (int8_t) ( ( TQc.qp[2] + TPc.qp[2] - 2 * qpBd + 1 ) >> 1 );
+        // the chroma QPs of an ISP CU are those of its last transform unit, the one that holds the chroma blocks (LoopFilter.cpp:1120-1123)
+        const vvr_tu& TQq = CQc.isp_mode ? B.tu[CQc.first_tu + CQc.num_tu - 1] : TQc; const vvr_tu& TPq = CPc.isp_mode ? B.tu[CPc.first_tu + CPc.num_tu - 1] : TPc;
+        L.qp[1] = (int8_t) ( ( TQq.qp[1] + TPq.qp[1] - 2 * qpBd + 1 ) >> 1 );
+        L.qp[2] = (int8_t) ( ( TQq.qp[2] + TPq.qp[2] - 2 * qpBd + 1 ) >> 1 );
         if( !L.bs ) { /* edge without any filtering keeps its length info, like the reference table */ }
       }
       // sub-block edges of affine and SbTMVP CUs (8x8 grid; xSetEdgeFilterInsidePu :1032, xSetMaxFilterLengthPQForCodingSubBlocks :707):
@@ -1035,7 +1054,7 @@ struct Gen {
 
   // LMCS model (lmcs_data()) + the tables Reshape::constructReshaper (Reshape.cpp:318-374) derives from it: this is host glue
   // (the parser side owns it), the back-end consumes the two LUTs
-  void genLmcs()
+  bool genLmcs()
   {
     vvr_lmcs_params& L = *B.lmcs; memset( &L, 0, sizeof( L ) );
     const int lutSize = 1 << bd, orgCW = lutSize / 16, l2cw = ilog2( orgCW );
@@ -1043,8 +1062,50 @@ struct Gen {
     int binCW[16] = { 0 };
     for( int i = L.min_bin; i <= L.max_bin; i++ ) binCW[i] = orgCW + (int) rng.u( 2 * ( orgCW / 3 ) + 1 ) - orgCW / 3;     // well inside [OrgCW >> 3, OrgCW << 3) and >= 1 << (bd - 5)
     for( ;; ) { int sum = 0; for( int i = 0; i < 16; i++ ) sum += binCW[i]; if( sum <= lutSize - 1 ) break; binCW[L.min_bin + rng.u( L.max_bin - L.min_bin + 1 )] -= 1; }
-    for( int i = 0; i < 16; i++ ) L.model_delta_cw[i] = (int16_t) ( ( i >= L.min_bin && i <= L.max_bin ) ? binCW[i] - orgCW : 0 );
     L.model_delta_crs = (int16_t) ( (int) rng.u( 5 ) - 2 );
+    const int cwMin = orgCW >> 3, cwMax = ( orgCW << 3 ) - 1, unit = 1 << ( bd - 5 );
+    if( P.lmcs_shape )
+    {
+      // the named models (the draws above are made all the same: the rest of the picture does not depend on the shape)
+      int lo = 0, hi = 15, crs = 0;
+      for( int i = 0; i < 16; i++ ) binCW[i] = 0;
+      switch( P.lmcs_shape )
+      {
+      case VVS_LMCS_SINGLE_BIN_LOW:  lo = hi = 2;  binCW[2]  = cwMax; break;       // one bin of slope ~8 forward, 1 / 8 inverse; flat forward map on both sides of it
+      case VVS_LMCS_SINGLE_BIN_HIGH: lo = hi = 13; binCW[13] = cwMax; break;
+      // five bins of slope ~2.4 that end at three quarters of the range: the prediction maps to pivot[10] at most, and what a residual adds on top lies in no bin
+      case VVS_LMCS_LATE_EARLY:      lo = 5; hi = 9; for( int i = lo; i <= hi; i++ ) binCW[i] = ( 3 * lutSize / 4 - 1 ) / 5; break;
+      case VVS_LMCS_SAWTOOTH:
+        // smallest legal bins next to large ones, the largest last (slopes 1 / 8 and ~8 side by side, and mapped luma beyond pivot[16]); a pivot inside a unit
+        // of 1 << (bd - 5) needs the next one in a later unit: small + ( unit - small ) seven times, then small + ( 8 * OrgCW - small )
+        for( int i = 0; i < 16; i++ ) binCW[i] = !( i & 1 ) ? cwMin : i == 15 ? 8 * orgCW - cwMin : unit - cwMin;
+        break;
+      case VVS_LMCS_CRS_LOW:
+        // lmcsCW + lmcsDeltaCrs at the smallest legal value in the even bins: scale OrgCW * 2048 / ( OrgCW >> 3 ) = 16384; the odd bins fill pairs of 2 * OrgCW - 1
+        crs = -7;
+        for( int i = 0; i < 16; i++ ) binCW[i] = ( i & 1 ) ? 2 * orgCW - 1 - ( cwMin + 7 ) : cwMin + 7;
+        break;
+      case VVS_LMCS_CRS_HIGH:        lo = 7; hi = 8; crs = 7; binCW[7] = binCW[8] = cwMax - 7; break;       // lmcsCW + lmcsDeltaCrs at the largest: the smallest scale
+      case VVS_LMCS_NEARLY_IDENTITY_FULL: for( int i = 0; i < 16; i++ ) binCW[i] = orgCW - ( i == 15 ); crs = L.model_delta_crs; break;      // the sum is exactly ( 1 << bd ) - 1
+      }
+      L.min_bin = (int16_t) lo; L.max_bin = (int16_t) hi; L.model_delta_crs = (int16_t) crs;
+    }
+    {
+      // lmcs_data() semantics: what a conforming stream guarantees (and Reshape::constructReshaper relies on)
+      int sum = 0, piv = 0;
+      if( L.min_bin < 0 || L.max_bin > 15 || L.min_bin > L.max_bin || L.model_delta_crs < -7 || L.model_delta_crs > 7 ) return false;
+      for( int i = 0; i < 16; i++ )
+      {
+        const bool in = i >= L.min_bin && i <= L.max_bin;
+        if( !in && binCW[i] ) return false;
+        if( in && ( binCW[i] < cwMin || binCW[i] > cwMax || binCW[i] + L.model_delta_crs < cwMin || binCW[i] + L.model_delta_crs > cwMax ) ) return false;
+        // LmcsPivot[i] inside a unit of 1 << (bd - 5): LmcsPivot[i + 1] lies in a later unit
+        if( in && piv % unit && ( piv / unit ) == ( ( piv + binCW[i] ) / unit ) ) return false;
+        piv += binCW[i]; sum += binCW[i];
+      }
+      if( sum > lutSize - 1 ) return false;
+    }
+    for( int i = 0; i < 16; i++ ) L.model_delta_cw[i] = (int16_t) ( ( i >= L.min_bin && i <= L.max_bin ) ? binCW[i] - orgCW : 0 );
     int pivot[17] = { 0 }, inPivot[17] = { 0 }, fwdCoef[16], invCoef[16];
     for( int i = 0; i < 16; i++ )
     {
@@ -1062,6 +1123,49 @@ struct Gen {
       L.inv_lut[v] = (int16_t) std::min( lutSize - 1, std::max( 0, (int) (int16_t) inv ) );
       const int fi = v >> l2cw;                                                                        // rspFwdCore (Buffer.cpp:321)
       L.fwd_lut[v] = (int16_t) std::min( lutSize - 1, std::max( 0, pivot[fi] + ( ( (int16_t) fwdCoef[fi] * ( v - inPivot[fi] ) + ( 1 << 10 ) ) >> 11 ) ) );
+    }
+    return true;
+  }
+
+  // chroma QP model: mapping tables, PPS + slice offsets, the CU-level offset list and its per-CU index, then the TU QPs the way QpParam derives them
+  // (Quant.cpp:65-91): joint_cbcr == 3 (ICT mode 2) takes the joint table and offsets for both components
+  void genChromaQp()
+  {
+    vvs_chroma_qp& M = *B.cqp; uint8_t* cuIdx = M.cu_idx; memset( &M, 0, sizeof( M ) ); M.cu_idx = cuIdx;
+    Rng r( (uint64_t) P.chroma_qp_model ^ 0x6371706D6F64ull );
+    const int qpBd = 6 * ( bd - 8 ), fl = P.chroma_qp_flavour;
+    static const int dflt[14] = { 29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37 };      // the 4:2:0 table of earlier standards: flattens above 30
+    const int rot = (int) r.u( 3 ), base[3] = { -9, 0, 9 };
+    for( int t = 0; t < 3; t++ )
+    {
+      const int kind = ( P.chroma_qp_model + t ) % 3, a = 24 + (int) r.u( 8 ), len = 8 + (int) r.u( 8 ), sh = (int) r.u( 5 ) - 2;
+      for( int q = -qpBd; q <= 63; q++ )
+      {
+        int v;
+        if( fl == 1 ) v = 32 + 16 * ( q - 32 + t - 1 );
+        else if( fl == 2 ) v = q + 28 + 4 * t;
+        else if( kind == 0 ) v = q < 30 ? q : q >= 44 ? q - 6 : dflt[q - 30];
+        else if( kind == 1 ) v = 32 + 2 * ( q - 32 ) + sh;
+        else v = q < a ? q : q < a + len ? a : q - len;
+        M.table[t][q + qpBd] = (int8_t) std::min( 63, std::max( -qpBd, v ) );
+      }
+      const int tot = fl == 1 ? ( t == 0 ? -12 : t == 1 ? 12 : 0 ) : fl == 2 ? (int) r.u( 5 ) - 2 : base[( t + rot ) % 3] + (int) r.u( 7 ) - 3;
+      M.pps_offset[t] = (int8_t) ( tot / 2 + (int) r.u( 5 ) - 2 ); M.slice_offset[t] = (int8_t) ( tot - M.pps_offset[t] );
+    }
+    for( int k = 0; k < 6; k++ ) for( int c = 0; c < 3; c++ ) M.list[k][c] = (int8_t) ( fl == 1 ? ( ( ( k + c ) & 1 ) ? 12 : -12 ) : fl == 2 ? (int) r.u( 9 ) - 4 : (int) r.u( 25 ) - 12 );
+    M.num_cu = B.num_cu;
+    for( uint32_t i = 0; i < B.num_cu; i++ ) M.cu_idx[i] = (uint8_t) r.u( 7 );
+    for( uint32_t t = 0; t < B.num_tu; t++ )
+    {
+      vvr_tu& tu = B.tu[t];
+      if( !( tu.comp_mask & 6 ) ) continue;
+      const int qpi = std::min( 63, std::max( -qpBd, (int) B.cu[tu.cu].qp ) ), idx = M.cu_idx[tu.cu];
+      for( int c = 1; c < 3; c++ )
+      {
+        const int j = tu.joint_cbcr == 3 ? 2 : c - 1;
+        const int off = M.pps_offset[j] + M.slice_offset[j] + ( idx ? M.list[idx - 1][j] : 0 );
+        tu.qp[c] = (int8_t) std::min( 63 + qpBd, std::max( 0, M.table[j][qpi + qpBd] + off + qpBd ) );
+      }
     }
   }
 
@@ -1097,7 +1201,7 @@ struct Gen {
     for( size_t i = 0; i < (size_t) w4 * h4; i++ ) { memset( &B.motion[i], 0, sizeof( vvr_motion ) ); B.motion[i].ref_idx[0] = B.motion[i].ref_idx[1] = -1; }
     vvr_pic_header& h = B.hdr; memset( &h, 0, sizeof( h ) );
     h.abi_version = VVR_ABI_VERSION; h.tool_flags = P.tool_flags; h.width = W; h.height = H; h.chroma_format = P.chroma_format; h.bit_depth = bd;
-    h.log2_ctu = P.log2_ctu; h.slice_type = P.slice_type; h.poc = P.poc; h.out_slot = P.out_slot; h.min_qp_ts = 4;
+    h.log2_ctu = P.log2_ctu; h.slice_type = P.slice_type; h.poc = P.poc; h.out_slot = P.out_slot; h.min_qp_ts = P.min_qp_ts;
     for( int l = 0; l < 2; l++ ) { h.num_ref[l] = P.slice_type == 2 ? 0 : P.num_ref[l]; for( int i = 0; i < VVR_MAX_REFS; i++ ) { h.ref_slot[l][i] = P.ref_slot[l][i]; h.ref_poc[l][i] = P.ref_poc[l][i]; } }
     for( int c = 0; c < 3; c++ ) { h.deblock_beta_offset_div2[c] = (int8_t) ( (int) rng.u( 5 ) - 2 ); h.deblock_tc_offset_div2[c] = (int8_t) ( (int) rng.u( 5 ) - 2 ); }
     h.wrap_offset = P.wrap_offset;
@@ -1161,8 +1265,9 @@ struct Gen {
       curTree = VVR_TREE_JOINT; cclmOk = true;
     }
     B.ctu_first_cu[a] = B.num_cu;
+    if( P.chroma_qp_model && B.cqp && P.chroma_format ) genChromaQp();      // (before the edge tables: they average the TU QPs)
     if( dual ) deriveLfpDual(); else deriveLfp();       // (deriveLfp handles the chroma-tree CUs of local dual trees through the chroma owner maps)
-    if( ( P.tool_flags & VVR_TOOL_LMCS ) && B.lmcs ) genLmcs();
+    if( ( P.tool_flags & VVR_TOOL_LMCS ) && B.lmcs && !genLmcs() ) return -2;
     genAlfParams();
     genLoopFilterParams();
     return 0;
@@ -1175,6 +1280,7 @@ __attribute__((visibility("default")))
 int vvs_generate( const vvs_params* P, vvs_buffers* B )
 {
   if( P->min_cu_log2 < 2 || P->chroma_format > 1 || P->bit_depth < 8 || P->bit_depth > 10 ) return -1;
+  if( P->min_qp_ts < 4 || P->min_qp_ts > 52 || ( P->min_qp_ts - 4 ) % 6 || P->lmcs_shape >= VVS_LMCS_NUM_SHAPES || P->chroma_qp_flavour > 2 ) return -1;
   Gen g( *P, *B );
   return g.run();
 }

@@ -379,6 +379,20 @@ int vvr_host_validate_header( const vvr_config& cfg, const vvr_picture* p, std::
     if( p->wp[k].log2_denom[0] > 7 || p->wp[k].log2_denom[1] > 7 ) FAIL( VVR_ERR_PARAMETER, "weighted prediction: log2 denominator out of range" );
   if( ( h.tool_flags & VVR_TOOL_LMCS_CSCALE ) && !( h.tool_flags & VVR_TOOL_LMCS ) ) FAIL( VVR_ERR_PARAMETER, "LMCS chroma residual scaling without LMCS" );
   if( ( h.tool_flags & VVR_TOOL_LMCS ) && !p->lmcs ) FAIL( VVR_ERR_PARAMETER, "LMCS enabled without tables" );
+  // min_qp_ts = 4 + 6 * sps_internal_bit_depth_minus_input_bit_depth (0 .. 8): k_itrans takes per / rem of max( qp, min_qp_ts )
+  if( h.min_qp_ts < 4 || h.min_qp_ts > 52 || ( h.min_qp_ts - 4 ) % 6 ) FAIL( VVR_ERR_PARAMETER, "min_qp_ts: 4 + 6k with k in 0 .. 8" );
+  if( h.tool_flags & VVR_TOOL_LMCS )
+  {
+    // what Reshape::constructReshaper guarantees about its tables: the chroma-scale search walks pivot[min_bin + 1 .. max_bin + 1] and indexes chroma_scale[16] with
+    // the result.  The two LUTs hold samples: constructReshaper (Reshape.cpp:369) and rspFwdCore (Buffer.cpp:321) clip every entry to 0 .. ( 1 << bd ) - 1, so a
+    // table of the reference never holds another value, and forward-mapped samples index the inverse table
+    const vvr_lmcs_params& L = *p->lmcs;
+    for( int v = 0; v < ( 1 << h.bit_depth ); v++ ) if( ( L.fwd_lut[v] | L.inv_lut[v] ) < 0 || ( L.fwd_lut[v] | L.inv_lut[v] ) >= ( 1 << h.bit_depth ) ) FAIL( VVR_ERR_PARAMETER, "LMCS: fwd_lut / inv_lut entry outside 0 .. ( 1 << bit depth ) - 1" );
+    if( L.min_bin < 0 || L.min_bin > 15 || L.max_bin < 0 || L.max_bin > 15 ) FAIL( VVR_ERR_PARAMETER, "LMCS: min_bin / max_bin outside 0 .. 15" );
+    if( L.min_bin > L.max_bin ) FAIL( VVR_ERR_PARAMETER, "LMCS: min_bin above max_bin" );
+    for( int i = 0; i < 17; i++ ) if( L.pivot[i] < 0 || L.pivot[i] > ( 1 << h.bit_depth ) || ( i && L.pivot[i] < L.pivot[i - 1] ) ) FAIL( VVR_ERR_PARAMETER, "LMCS: pivot decreasing or outside 0 .. 1 << bit depth" );
+    for( int i = 0; i < 16; i++ ) if( L.chroma_scale[i] <= 0 ) FAIL( VVR_ERR_PARAMETER, "LMCS: chroma_scale entry not positive" );
+  }
   const bool wpOn = ( h.tool_flags & VVR_TOOL_WP ) && h.slice_type != 2;
   if( wpOn && !p->wp ) FAIL( VVR_ERR_PARAMETER, "weighted prediction enabled without the weight table" );
 
@@ -443,6 +457,8 @@ static int validate_records_range( const vvr_picture* p, uint32_t cu0, uint32_t 
   {
     const vvr_cu& cu = p->cu[i];
     if( !cu.w || !cu.h || cu.x + cu.w > h.width || cu.y + cu.h > h.height || cu.first_tu + cu.num_tu > p->num_tu ) FAIL( VVR_ERR_PARAMETER, "CU outside the picture / bad TU range" );
+    // QPs index the dequantisation tables ( rem ) and shift ( per ), and the tc / beta tables of the deblocking: the luma QP of a CU lies in -QpBdOffset .. 63
+    if( cu.qp < -6 * ( h.bit_depth - 8 ) || cu.qp > 63 ) FAIL( VVR_ERR_PARAMETER, "cu.qp outside -QpBdOffset .. 63" );
     if( cu.tree != VVR_TREE_CHROMA ) areaLuma += (uint64_t) cu.w * cu.h;
     if( cu.tree != VVR_TREE_LUMA ) areaChroma += (uint64_t) cu.w * cu.h;
     // ---- the CU's transform units: inside the CU, owned by it, tiling it, coded corners inside the level stream
@@ -461,6 +477,7 @@ static int validate_records_range( const vvr_picture* p, uint32_t cu0, uint32_t 
       for( int c = 0; c < ncomp; c++ )
       {
         if( !( tu.comp_mask & ( 1 << c ) ) ) continue;
+        if( tu.qp[c] < 0 || tu.qp[c] > 63 + 6 * ( h.bit_depth - 8 ) ) FAIL( VVR_ERR_PARAMETER, "tu.qp outside 0 .. 63 + QpBdOffset" );
         // (joint Cb-Cr: the levels belong to Cb for modes 2 / 3, to Cr for mode 1)
         const bool coded = ( c && tu.joint_cbcr ) ? c == ( ( tu.joint_cbcr >> 1 ) ? 1 : 2 ) : ( ( tu.cbf >> c ) & 1 ) != 0;
         if( !coded || !( cu.flags & VVR_CU_ROOT_CBF ) ) continue;

@@ -35,13 +35,26 @@ class Params(C.Structure):
                 ("p_imv_hpel", C.c_float), ("p_jccr", C.c_float), ("p_mrl", C.c_float), ("p_bdpcm", C.c_float),
                 ("p_affine", C.c_float), ("p_geo", C.c_float), ("p_ciip", C.c_float), ("p_sbtmvp", C.c_float), ("p_bcw", C.c_float), ("p_cclm", C.c_float), ("p_mip", C.c_float), ("p_sbt", C.c_float), ("p_isp", C.c_float), ("dual_tree", C.c_float), ("p_ibc", C.c_float),
                 ("num_slices", C.c_uint8), ("tile_cols", C.c_uint8), ("tile_rows", C.c_uint8), ("wrap_offset", C.c_uint16), ("subpics", C.c_uint8), ("intra_slices", C.c_uint8), ("virtual_boundaries", C.c_uint8), ("scaled_refs", C.c_uint16 * 2), ("mv_window", C.c_uint16),
-                ("mv_window_ver", C.c_uint16), ("p_mv_limit", C.c_float)]
+                ("mv_window_ver", C.c_uint16), ("p_mv_limit", C.c_float),
+                ("lmcs_shape", C.c_uint8), ("min_qp_ts", C.c_uint8), ("chroma_qp_flavour", C.c_uint8), ("chroma_qp_model", C.c_uint32)]
+
+
+# Params.lmcs_shape: LMCS models at the ends of what lmcs_data() allows (tools/synth.cpp, genLmcs)
+LMCS_SHAPES = {"drawn": 0, "single_bin_low": 1, "single_bin_high": 2, "late_early": 3, "sawtooth": 4, "crs_low": 5, "crs_high": 6, "nearly_identity_full": 7}
+CQP_GENERAL, CQP_CLIP, CQP_LIFTED = 0, 1, 2       # Params.chroma_qp_flavour
+
+
+class ChromaQpModel(C.Structure):
+    """what a stream's SPS / PPS / slice header / CUs would carry about chroma QPs (tools/synth.cpp, vvs_chroma_qp): the generator fills it beside the
+    description, whose TU records hold the resulting QPs; the checkers install it into the parameter sets of a reference decoder"""
+    _fields_ = [("table", C.c_int8 * 76 * 3), ("pps_offset", C.c_int8 * 3), ("slice_offset", C.c_int8 * 3), ("list", C.c_int8 * 3 * 6),
+                ("num_cu", C.c_uint32), ("cu_idx", C.c_void_p)]
 
 
 class Buffers(C.Structure):
     _fields_ = [("cu", C.c_void_p), ("max_cu", C.c_uint32), ("tu", C.c_void_p), ("max_tu", C.c_uint32),
                 ("coef", C.c_void_p), ("max_coef", C.c_uint64), ("ctu_first_cu", C.c_void_p),
-                ("motion", C.c_void_p), ("lfp", C.c_void_p * 2), ("sao", C.c_void_p), ("alf", C.c_void_p), ("alf_params", C.c_void_p), ("lmcs", C.c_void_p), ("wp", C.c_void_p), ("scaling", C.c_void_p), ("ctu_slice", C.c_void_p), ("ctu_tile", C.c_void_p), ("subpics", C.c_void_p),
+                ("motion", C.c_void_p), ("lfp", C.c_void_p * 2), ("sao", C.c_void_p), ("alf", C.c_void_p), ("alf_params", C.c_void_p), ("lmcs", C.c_void_p), ("wp", C.c_void_p), ("scaling", C.c_void_p), ("ctu_slice", C.c_void_p), ("ctu_tile", C.c_void_p), ("subpics", C.c_void_p), ("cqp", C.c_void_p),
                 ("num_cu", C.c_uint32), ("num_tu", C.c_uint32), ("num_coef", C.c_uint64), ("num_dmvr", C.c_uint32), ("num_subpics", C.c_uint32),
                 ("hdr", abi.PicHeader)]
 
@@ -124,9 +137,18 @@ def generate(p, alloc=None):
         if d.ctu_slice is None:                      # one slice per sub-picture
             d.ctu_slice = np.zeros(d.num_ctu, np.uint16)
             b.ctu_slice = d.ctu_slice.ctypes.data
+    model = cu_idx = None
+    if p.chroma_qp_model and p.chroma_format:
+        model, cu_idx = ChromaQpModel(), np.zeros(mcu.value, np.uint8)
+        model.cu_idx = cu_idx.ctypes.data
+        b.cqp = C.addressof(model)
     rc = L.vvs_generate(C.byref(p), C.byref(b))
     if rc != 0:
         raise RuntimeError("vvs_generate failed (%d)" % rc)
+    if model is not None:       # beside the description, not in it: the ABI carries TU QPs only
+        model.cu_idx_array = cu_idx[:b.num_cu].copy()
+        model.cu_idx = model.cu_idx_array.ctypes.data
+        d.chroma_qp_model = model
     d.hdr = abi.PicHeader.from_buffer_copy(b.hdr)
     d.cu = _compact(cu, b.num_cu, alloc)
     d.tu = _compact(tu, b.num_tu, alloc)
@@ -253,6 +275,7 @@ def rewrite_qp(d, qps):
     the edge tables (rounded mean of the two sides, LoopFilter.cpp:1363 / 1180)"""
     qps = np.asarray(qps, np.int32)
     assert len(qps) == len(d.cu) and not (d.cu["tree"] == abi.TREE_CHROMA).any(), "one QP per CU of a single-tree picture"
+    assert getattr(d, "chroma_qp_model", None) is None, "identity chroma QP mapping only (the edge tables of a model are the generator's)"
     qpbd = 6 * (int(d.hdr.bit_depth) - 8)
     assert qps.min() >= -qpbd and qps.max() <= 63
     d.cu["qp"] = qps
@@ -274,6 +297,21 @@ def rewrite_qp(d, qps):
         for c in range(3):
             lq[:, :, c][valid] = mean[valid]
     return d
+
+
+def model_chroma_qps(d, model=None):
+    """TU.qp[1..2] restated from a chroma QP model the way QpParam derives them (Quant.cpp:65-91) -> (per TU [Cb, Cr] with each component's own table,
+    per TU the QP of the joint table): a joint_cbcr == 3 TU holds the joint QP in both components, every other TU the components' own"""
+    m = model or d.chroma_qp_model
+    qpbd = 6 * (int(d.hdr.bit_depth) - 8)
+    table = np.ctypeslib.as_array(m.table).astype(np.int32)
+    tot = np.array([m.pps_offset[t] + m.slice_offset[t] for t in range(3)], np.int32)
+    lst = np.concatenate([np.zeros((1, 3), np.int32), np.ctypeslib.as_array(m.list).astype(np.int32)])
+    cu = d.tu["cu"].astype(np.int64)
+    qpi = np.clip(d.cu["qp"].astype(np.int32)[cu], -qpbd, 63)
+    idx = m.cu_idx_array[cu]
+    q = np.stack([np.clip(table[t][qpi + qpbd] + tot[t] + lst[idx, t] + qpbd, 0, 63 + qpbd) for t in range(3)], axis=1)
+    return q[:, :2], q[:, 2]
 
 
 def attach_rpr(d, refs, win=(0, 0), colloc=(1, 1)):
