@@ -795,7 +795,7 @@ VVR_API int          vvr_hash_submit(vvr_context* ctx, const vvr_hash_request* r
  *   VVR_STATS_LUMA  hist_y alone; hist_maxrgb, max_c and min_c are 0.  Works in every context, 4:0:0 included.
  *   bins     at 2^bd and above: 0.  samples = width * height; both histograms sum to it (hist_maxrgb in RGB mode).
  *   ticket and ring, ordering   everything said about a hash request above holds: the ticket comes from the same ticket space and the same 8 ring
- *            entries (VVR_ERR_BUSY counts every kind of request: output, hash, statistics, comparison); vvr_output_test / vvr_output_wait collect it; vvr_output_stream_wait means
+ *            entries (VVR_ERR_BUSY counts every kind of request: output, hash, statistics, comparison, SSIM); vvr_output_test / vvr_output_wait collect it; vvr_output_stream_wait means
  *            "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the request runs on the output
  *            stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1); pictures submitted afterwards
  *            that overwrite the slot wait for the request's kernels on the device; blocking == 0: VVR_NOT_READY while `job` has not been handed
@@ -873,7 +873,7 @@ VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_
  *            the output stream; it must stay untouched until vvr_output_wait has returned.  Any other host memory: copied inside vvr_compare_submit
  *            into the entry's pinned staging, as `expected` of a hash request is: the caller's buffers are free again when the call returns.
  *   ticket and ring, ordering   everything said about a hash or statistics request above holds: the ticket comes from the same ticket space and the
- *            same 8 ring entries (VVR_ERR_BUSY counts all four kinds of request); vvr_output_test / vvr_output_wait collect it;
+ *            same 8 ring entries (VVR_ERR_BUSY counts all five kinds of request); vvr_output_test / vvr_output_wait collect it;
  *            vvr_output_stream_wait means "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the
  *            request runs on the output stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1);
  *            ref_slot is taken as all work submitted so far leaves it (the job == -1 rule, whatever `job` is); the request is a reader of both slots:
@@ -885,7 +885,7 @@ VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_
  * ref_slot == slot, job < -1, result == NULL, a window outside the picture, empty, or odd in a 4:2:0 context, pictures of different sizes in the two
  * slots; without ref_slot: ref_bytes_per_sample other than 1 or 2, a NULL plane among those the context has, a stride below the row, device planes
  * mixed with host planes, a plane partly inside a device range.
- * Not offered: SSIM and other windowed measures; grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
+ * Not offered here: SSIM is a request of its own (vvr_ssim_submit, below); grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
  * a reference of another size than the window. */
 typedef struct vvr_frame_compare {
   uint32_t struct_size;            /* sizeof( vvr_frame_compare ), written with the rest */
@@ -922,6 +922,72 @@ VVR_API int          vvr_compare_submit(vvr_context* ctx, const vvr_compare_requ
  * psnr[3]: the same formula from the sums of samples and of sse over the components.  HUGE_VAL where the sse is 0.  Refused (VVR_ERR_PARAMETER, psnr
  * untouched): a NULL pointer, a struct_size other than sizeof( vvr_frame_compare ), a bit depth outside 8..10, samples[0] == 0. */
 VVR_API int          vvr_compare_psnr(const vvr_frame_compare* cmp, double peak, double psnr[4]);
+/* SSIM of a picture against a reference frame as a request of the output queue: the second number of a transcoder's quality loop.  It is windowed and
+ * not linear per window, so it does not follow from the sums of a comparison; it has a kernel of its own and the comparison's plumbing.  The result is
+ * integers, defined here to the bit:
+ *   samples  L = 2^bit_depth - 1 with the context's bit depth (8 .. 10).  x: the slot's 16-bit word, y: the reference's byte or little-endian 16-bit
+ *            word, both read as unsigned values and both clamped: min( value, L ).  (A reference may hold anything up to 65535 and vvr_write_plane can
+ *            put anything into a slot: the clamp keeps every intermediate below inside 64 bits.)
+ *   window   x, y, w, h, the components' windows ( x >> 1, y >> 1, w >> 1, h >> 1 ) in 4:2:0, the reference planes that ARE the window, ref_slot:
+ *            exactly as for vvr_compare_request.
+ *   SSIM windows   8 x 8 samples at a stride of 4 in both directions: origins ( 4 i, 4 j ) of the component's window ( w_c x h_c ) for all
+ *            4 i + 8 <= w_c and 4 j + 8 <= h_c.  windows_x = w_c >= 8 ? ( w_c - 8 ) / 4 + 1 : 0, windows_y likewise; samples right of or below the
+ *            last whole window are not covered; a component narrower or lower than 8 has no windows.
+ *   per SSIM window   with N = 64, in int64_t:  s1 = sum x, s2 = sum y, sxx = sum x * x, syy = sum y * y, sxy = sum x * y;
+ *            C1 = ( L * L * 4096 + 5000 ) / 10000, C2 = ( 9 * L * L * 4096 + 5000 ) / 10000  (K1 = 0.01, K2 = 0.03 of Wang et al. at N * N: 26634 and
+ *            239708 at 8 bits, 428658 and 3857925 at 10);
+ *            A1 = 2 * s1 * s2 + C1,  B1 = s1 * s1 + s2 * s2 + C1,
+ *            A2 = 2 * ( N * sxy - s1 * s2 ) + C2,  B2 = ( N * sxx - s1 * s1 ) + ( N * syy - s2 * s2 ) + C2,
+ *            l = ( A1 << 24 ) / B1,  c = ( A2 * 16777216 ) / B2,  v = ( l * c ) / 16777216; every / is C's division on
+ *            int64_t, which truncates toward zero; A2, c and v may be negative.  This is textbook SSIM - uniform 8 x 8 window, population variance
+ *            - as a Q24 number: 0 < A1 <= B1 and |A2| <= B2, so |v| <= 2^24; identical windows give exactly 2^24; A1 << 24 and |A2| << 24 stay
+ *            below 2^58; | v / 2^24 - the real-valued SSIM with these constants, C1 / N^2 and C2 / N^2 | < 3 * 2^-24.
+ *   per component c   width, height: the component's window; windows_x, windows_y; windows = windows_x * windows_y; sum: the sum of v; min: the
+ *            smallest v; min_x, min_y: the origin, in samples of the component's window, of the first window in raster order of the window grid that
+ *            has that v.  A component without windows has sum 0, min 0x7fffffff, min_x = min_y = 0xffffffff, and so have the two components a
+ *            4:0:0 context lacks (their other fields are 0).
+ *   map      NULL, or ceil( w / 64 ) * ceil( h / 64 ) words, row-major: the smallest v over the windows of all components whose ORIGIN sample lies in
+ *            that block of 64 x 64 luma samples; a chroma origin ( i, j ) belongs to the block of ( 2 i, 2 j ); 0x7fffffff where no origin falls into
+ *            the block (a last block 4 samples wide, for one).
+ *   where the reference may lie, ticket and ring, ordering, result   everything said for a comparison request above holds (VVR_ERR_BUSY counts all five
+ *            kinds of request); the film grain seed chain and the colour description are not touched.
+ * Refused (VVR_ERR_PARAMETER with a text that names vvr_ssim_submit, no ring entry taken): everything vvr_compare_submit refuses, struct_size being
+ * sizeof( vvr_ssim_request ), and a window with w < 8 or h < 8.
+ * Not offered: MS-SSIM, Gaussian windows; grained or rescaled frames; results left in device memory; a reference of another size than the window. */
+typedef struct vvr_frame_ssim {
+  uint32_t struct_size;            /* sizeof( vvr_frame_ssim ), written with the rest */
+  uint32_t bit_depth;              /* the context's */
+  uint32_t num_components;         /* 1 (4:0:0) or 3 */
+  uint32_t pad;
+  uint32_t width[3], height[3];    /* the window per component (chroma: >> 1 in 4:2:0) */
+  uint32_t windows_x[3], windows_y[3];
+  uint64_t windows[3];             /* windows_x * windows_y */
+  int64_t  sum[3];                 /* sum of v */
+  int32_t  min[3];                 /* smallest v; 0x7fffffff without windows */
+  uint32_t min_x[3], min_y[3];     /* origin of the first window in raster order that has it; 0xffffffff both without windows */
+  uint32_t pad2;
+} vvr_frame_ssim;
+typedef struct vvr_ssim_request {  /* field by field a vvr_compare_request, but for the types of result and map */
+  uint32_t struct_size;            /* sizeof( vvr_ssim_request ) */
+  int32_t  slot;
+  int32_t  job;                    /* as vvr_output_request.job */
+  int32_t  x, y, w, h;             /* window, luma samples (even in 4:2:0), w >= 8 and h >= 8 */
+  int32_t  ref_slot;               /* >= 0: the reference is the same window of that slot; -1: ref[] below */
+  uint8_t  ref_bytes_per_sample;   /* 1 or 2 (little endian); ignored with ref_slot */
+  uint8_t  blocking;               /* as vvr_output_request.blocking */
+  uint8_t  pad[2];
+  uint32_t pad2;
+  const void* ref[3];              /* planes of the WINDOW's size (not the picture's); ref[1], ref[2] unused in 4:0:0 */
+  size_t   ref_stride_bytes[3];
+  vvr_frame_ssim* result;          /* written by vvr_output_wait; must stay valid until it has returned */
+  int32_t* map;                    /* NULL, or ceil( w / 64 ) * ceil( h / 64 ) words, written by vvr_output_wait */
+} vvr_ssim_request;
+VVR_API int          vvr_ssim_submit(vvr_context* ctx, const vvr_ssim_request* req);
+/* mean SSIM from the sums of an SSIM request; a pure host function, no context, in double.  ssim[c] = sum[c] / ( windows[c] * 2^24 ) for the
+ * components that have windows, 0 for the others; ssim[3]: the same formula from the sums of `sum` and of `windows` over the components.  Refused
+ * (VVR_ERR_PARAMETER, ssim untouched): a NULL pointer, a struct_size other than sizeof( vvr_frame_ssim ), a bit depth outside 8..10,
+ * windows[0] == 0. */
+VVR_API int          vvr_compare_ssim(const vvr_frame_ssim* s, double ssim[4]);
 /* the finished picture in `slot` (every plane, at the picture's size) into the caller's buffers - what a decoder does with each picture it hands to
  * the application (the planes of a vvdecFrame live in the Picture's own buffers, vvdecimpl.cpp:1058).  Waits for NOTHING: the caller has waited for
  * the picture (vvr_wait); other pictures in flight are not held up (vvr_read_plane drains the context).  Each plane crosses PCIe in one transfer

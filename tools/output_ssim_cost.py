@@ -1,0 +1,131 @@
+"""What an SSIM request of the output queue costs (vvr_ssim_submit): on the 3840x2160 window of one 10-bit picture, the device time of
+k_output_ssim and k_output_ssim_sum with the reference in device memory (torch tensors, read in place; 16-bit and 8-bit planes) and in another
+slot - next to the comparison request of the same frame in the same process (k_output_compare, which reads the same bytes without the halo, the
+cell stage and the divisions: the yardstick).
+The configurations take turns inside a round (--repeats requests of each behind three of warm-up); the process runs --rounds rounds and reports,
+per configuration, the median of every round, the median of those medians and their spread.  The kernel time is the library's (HIP events around
+the launch, vvr_enable_stats / vvr_get_stats); the wall time is vvr_ssim_submit .. vvr_output_wait on the host.  Bytes read per second - the
+slot's and the reference's samples over the kernel's time - stand against vvr_measure_copy_bandwidth of the same run (bytes read + written per
+second of the library's copy kernel).
+--table FILE: the compiler's resource table (tools/kernel_resources.sh); the lines of the kernels measured here are quoted in the note.
+--table-only: no GPU: the note holds the compiler's table and says that the times are NOT YET measured.
+Usage: python tools/output_ssim_cost.py [--repeats 30] [--rounds 5] [--table FILE] [--table-only] [--out profiles/output_ssim_4k.txt] [--json FILE]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from output_compare_cost import W, H, picture, summary      # noqa: E402  (the same frame and the same reduction of the rounds)
+
+KERNELS = ("k_output_ssim", "k_output_ssim_sum", "k_output_compare", "k_output_compare_sum")
+YARDSTICK = "comparison request of the same frame (k_output_compare), reference in device memory, 16-bit"
+
+
+def measure(a):
+    import torch                      # first: its HIP runtime is the one the process initialises
+    sys.path.insert(0, ROOT)
+    import vvdec_amd
+    rng = np.random.default_rng(7)
+    planes = picture(rng)
+    # the reference: the picture with coding-noise-like differences in a quarter of the samples
+    other = [np.where(rng.random(p.shape) < 0.25, (p.astype(np.int64) + rng.integers(-3, 4, p.shape)).clip(0, 1023), p).astype(np.uint16) for p in planes]
+    rec = vvdec_amd.Reconstructor(W, H, bit_depth=10, num_slots=2, num_streams=1)
+    rec.write_picture(0, planes)
+    rec.write_picture(1, other)
+    ceiling = rec.copy_bandwidth(20)
+    rec.enable_stats()
+    dev16 = [torch.from_numpy(p.view(np.int16)).cuda() for p in other]
+    dev8 = [torch.from_numpy((p >> 2).astype(np.uint8)).cuda() for p in other]
+    torch.cuda.synchronize()
+    configs = [("reference in device memory, 16-bit", dev16, 4, True), ("reference in device memory, 8-bit", dev8, 3, True), ("reference in another slot", 1, 4, True),
+               (YARDSTICK, dev16, 4, False)]
+    samples = W * H * 3 // 2
+
+    def kernel_ms():
+        st = {s["name"]: s["total_ms"] for s in rec.stats()}
+        return [st.get(k, 0.) for k in KERNELS]
+
+    medians = {c[0]: [] for c in configs}
+    for _ in range(a.rounds):
+        times = {c[0]: [] for c in configs}
+        for k in range(3 + a.repeats):
+            for name, ref, _b, ssim in configs:
+                k0, t0 = kernel_ms(), time.perf_counter()
+                (rec.ssim if ssim else rec.compare)(0, ref, window=(0, 0, W, H), with_map=True)
+                wall = time.perf_counter() - t0
+                if k >= 3:
+                    times[name].append([y - x for x, y in zip(k0, kernel_ms())] + [wall * 1000])
+        for c in configs:
+            medians[c[0]].append([float(v) for v in np.median(np.array(times[c[0]]), axis=0)])
+    first = rec.ssim(0, dev16, window=(0, 0, W, H))
+    rec.close()
+    res = {"size": [W, H], "bit_depth": 10, "repeats": a.repeats, "rounds": a.rounds, "library": vvdec_amd.lib().vvr_version().decode(),
+           "copy_bandwidth_GBps": round(ceiling / 1e9, 1), "ssim": [round(v, 6) for v in first["ssim"]], "windows": first["windows"], "configs": {}}
+    for name, ref, bps, ssim in configs:
+        m = np.array(medians[name]) * 1000      # microseconds
+        main, fold = (m[:, 0], m[:, 1]) if ssim else (m[:, 2], m[:, 3])
+        nbytes = samples * bps
+        res["configs"][name] = {"kernel_us": summary(main), "fold_us": summary(fold), "request_wall_us": summary(m[:, 4]), "bytes_read": nbytes,
+                                "read_GBps": round(nbytes / (float(np.median(main)) * 1e-6) / 1e9, 1)}
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    return res
+
+
+def compose(res, table):
+    out = ["SSIM of a picture against a reference frame through the output queue (vvr_ssim_submit): the compiler's resource lines of the two kernels and",
+           "their time on the 3840x2160 window of one 10-bit 4:2:0 picture (a structured synthetic picture; the reference differs from it in a quarter",
+           "of the samples)." + (" %r windows per component, mean SSIM %r (Y, Cb, Cr, all)." % (res["windows"], res["ssim"]) if res else ""), ""]
+    if table:
+        out += ["== Compiler table (tools/kernel_resources.sh: hipcc -Rpass-analysis=kernel-resource-usage, gfx950; no GPU needed) =="]
+        out += [l.rstrip() for l in open(table) if "k_output_ssim" in l or "k_output_compare" in l] + [""]
+    if not res:
+        return "\n".join(out + ["== Kernel time at 4K ==", "NOT YET measured: no run on the device has been made with this library (tools/output_ssim_cost.py writes this section).", ""])
+    out += ["== Kernel time at 4K ==",
+            "One MI355X, one process (%s).  %d rounds; in a round the configurations take turns, %d timed requests of each behind three of" % (res["library"], res["rounds"], res["repeats"]),
+            "warm-up.  Kernel time: HIP events around the launch (vvr_enable_stats) - k_output_ssim, its fold k_output_ssim_sum apart.  Wall time:",
+            "vvr_ssim_submit .. vvr_output_wait on the host, with the map (8 KB more over PCIe), registration of the tensors included.  Per",
+            "configuration the median of the round medians, their spread (largest - smallest) and the round medians, in microseconds; bytes read: the",
+            "slot's and the reference's samples, the halo of 4 samples to the right of and below every block (13 % more, from the cache for the most",
+            "part) not counted; GB/s: those bytes over the kernel's median.  vvr_measure_copy_bandwidth of this run: %.1f GB/s (read + written by the" % res["copy_bandwidth_GBps"],
+            "library's copy kernel), i.e. the ceiling for a kernel that only reads is that many bytes per second.", ""]
+    for name, c in res["configs"].items():
+        k, f, w_ = c["kernel_us"], c["fold_us"], c["request_wall_us"]
+        floor = c["bytes_read"] / (res["copy_bandwidth_GBps"] * 1e9) * 1e6
+        out += ["-- %s" % name,
+                "   kernel  median %8.2f  spread %6.2f  %r" % (k["median"], k["spread"], k["round_medians"]),
+                "   fold    median %8.2f  spread %6.2f  %r" % (f["median"], f["spread"], f["round_medians"]),
+                "   request median %8.2f  spread %6.2f  (host wall time)" % (w_["median"], w_["spread"]),
+                "   %.1f MB read, %.1f GB/s; the copy ceiling implies %.2f us for these bytes: the kernel takes %.2f times that" % (c["bytes_read"] / 1e6, c["read_GBps"], floor, k["median"] / floor), ""]
+    yard = res["configs"][YARDSTICK]["kernel_us"]["median"]
+    out += ["== Against k_output_compare =="]
+    for name, c in res["configs"].items():
+        if name != YARDSTICK:
+            out += ["k_output_ssim, %s: %.2f us = %.2f x k_output_compare (%.2f us in this process)" % (name, c["kernel_us"]["median"], c["kernel_us"]["median"] / yard, yard)]
+    return "\n".join(out) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--table", default="")
+    ap.add_argument("--table-only", action="store_true")
+    ap.add_argument("--out", default="")
+    ap.add_argument("--json", default="")
+    a = ap.parse_args()
+    text = compose(None if a.table_only else measure(a), a.table)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -121,6 +121,10 @@ def lib():
         L.vvr_compare_submit.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_compare_psnr.restype = C.c_int
         L.vvr_compare_psnr.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.vvr_ssim_submit.restype = C.c_int
+        L.vvr_ssim_submit.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_compare_ssim.restype = C.c_int
+        L.vvr_compare_ssim.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_output_stream_wait.restype = C.c_int
         L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vvr_device_alloc.restype = C.c_void_p
@@ -141,7 +145,7 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
                     "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit", "vvr_stats_submit", "vvr_light_level",
-                    "vvr_compare_submit", "vvr_compare_psnr",
+                    "vvr_compare_submit", "vvr_compare_psnr", "vvr_ssim_submit", "vvr_compare_ssim",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
 
 
@@ -642,6 +646,41 @@ class Reconstructor:
         turns it into light levels)"""
         return FrameStats(self.output_wait(ticket))
 
+    def _against_reference(self, what, slot, ref, win, job, request, submit, raw, blocks):
+        """the part compare() and ssim() share: the reference looked at (a slot number, numpy planes, or torch tensors on the device, which are
+        registered with the context for the call's duration), the request made by `request`, submitted with `submit` and waited for; `raw` and
+        `blocks` are written"""
+        nc = 3 if self.chroma_format else 1
+        registered = []
+        if not isinstance(ref, int):
+            ref = list(ref)[:nc]
+            shapes = [(win[3] >> (1 if c else 0), win[2] >> (1 if c else 0)) for c in range(nc)]
+            if len(ref) != nc or any(tuple(p.shape) != s for p, s in zip(ref, shapes)):
+                raise ValueError("%s: the reference needs %d planes of the window's size, %r" % (what, nc, shapes))
+            if all(hasattr(p, "data_ptr") for p in ref):
+                if any(not p.is_cuda or p.device.index != self.cfg.device or p.element_size() not in (1, 2) or p.element_size() != ref[0].element_size() or
+                       (p.shape[1] > 1 and p.stride(1) != 1) or p.stride(0) < 0 for p in ref):
+                    raise ValueError(what + ": reference tensors are row-major 2-D tensors of 1- or 2-byte elements on the context's device")
+            else:
+                ref = [np.asarray(p) for p in ref]
+                if ref[0].dtype not in (np.uint8, np.uint16) or any(p.dtype != ref[0].dtype for p in ref):
+                    raise ValueError(what + ": reference planes are uint8 or uint16 arrays")
+                ref = [p if p.strides[1] == p.itemsize and p.strides[0] > 0 else np.ascontiguousarray(p) for p in ref]
+        try:
+            if not isinstance(ref, int) and hasattr(ref[0], "data_ptr"):
+                for t in ref:
+                    ptr, n = t.data_ptr(), (sum((d - 1) * st for d, st in zip(t.shape, t.stride())) + 1) * t.element_size()
+                    if any(a <= ptr and ptr + n <= a + m for a, m in self._dev) or ptr in registered:
+                        continue
+                    self._check(self.L.vvr_device_register(self.ctx, ptr, n))
+                    registered.append(ptr)
+            req = request(slot, job, win, ref, raw, blocks)
+            ticket = self._check(submit(self.ctx, C.byref(req)))
+            self._check(self.L.vvr_output_wait(self.ctx, ticket))
+        finally:
+            for ptr in registered:
+                self.L.vvr_device_unregister(self.ctx, ptr)
+
     def compare(self, slot, ref, window=None, job=None, with_map=False):
         """vvr_compare_submit and vvr_output_wait: the window of `slot` (as `job` leaves it; None: as all work submitted so far leaves it)
         compared sample by sample with a reference frame, reduced on the device -> dict of per-component lists (width, height, samples,
@@ -654,35 +693,7 @@ class Reconstructor:
         nc = 3 if self.chroma_format else 1
         raw = abi.FrameCompare()
         blocks = np.zeros(abi.compare_map_shape(win), np.uint32) if with_map else None
-        registered = []
-        if not isinstance(ref, int):
-            ref = list(ref)[:nc]
-            shapes = [(win[3] >> (1 if c else 0), win[2] >> (1 if c else 0)) for c in range(nc)]
-            if len(ref) != nc or any(tuple(p.shape) != s for p, s in zip(ref, shapes)):
-                raise ValueError("compare: the reference needs %d planes of the window's size, %r" % (nc, shapes))
-            if all(hasattr(p, "data_ptr") for p in ref):
-                if any(not p.is_cuda or p.device.index != self.cfg.device or p.element_size() not in (1, 2) or p.element_size() != ref[0].element_size() or
-                       (p.shape[1] > 1 and p.stride(1) != 1) or p.stride(0) < 0 for p in ref):
-                    raise ValueError("compare: reference tensors are row-major 2-D tensors of 1- or 2-byte elements on the context's device")
-            else:
-                ref = [np.asarray(p) for p in ref]
-                if ref[0].dtype not in (np.uint8, np.uint16) or any(p.dtype != ref[0].dtype for p in ref):
-                    raise ValueError("compare: reference planes are uint8 or uint16 arrays")
-                ref = [p if p.strides[1] == p.itemsize and p.strides[0] > 0 else np.ascontiguousarray(p) for p in ref]
-        try:
-            if not isinstance(ref, int) and hasattr(ref[0], "data_ptr"):
-                for t in ref:
-                    ptr, n = t.data_ptr(), (sum((d - 1) * st for d, st in zip(t.shape, t.stride())) + 1) * t.element_size()
-                    if any(a <= ptr and ptr + n <= a + m for a, m in self._dev) or ptr in registered:
-                        continue
-                    self._check(self.L.vvr_device_register(self.ctx, ptr, n))
-                    registered.append(ptr)
-            req = abi.compare_request(slot, job, win, ref, raw, blocks)
-            ticket = self._check(self.L.vvr_compare_submit(self.ctx, C.byref(req)))
-            self._check(self.L.vvr_output_wait(self.ctx, ticket))
-        finally:
-            for ptr in registered:
-                self.L.vvr_device_unregister(self.ctx, ptr)
+        self._against_reference("compare", slot, ref, win, job, abi.compare_request, self.L.vvr_compare_submit, raw, blocks)
         out = dict(raw=raw, bit_depth=raw.bit_depth, num_components=raw.num_components)
         for name in ("width", "height", "samples", "differing", "sse", "sad", "max_abs"):
             out[name] = [int(v) for v in getattr(raw, name)][:nc]
@@ -699,6 +710,28 @@ class Reconstructor:
         if self.L.vvr_compare_psnr(C.byref(raw), float(peak), out) != abi.VVR_OK:
             raise VvrError("vvr_compare_psnr: a result of compare() at 8 to 10 bits")
         return list(out)
+
+    def ssim(self, slot, ref, window=None, job=None, with_map=False):
+        """vvr_ssim_submit and vvr_output_wait: SSIM of the window of `slot` against a reference frame, reduced on the device (8 x 8 windows at a
+        stride of 4, integers defined in vvr.h) -> dict: `ssim` [Y, Cb, Cr, all components together] as floats (vvr_compare_ssim), per-component
+        lists sum, windows, min (Q24 integers) and min_at ((x, y) of the first window in raster order that has the smallest value, or None),
+        width, height, bit_depth, num_components, `raw` (the abi.FrameSsim) and, with_map, `map`: an int32 array with the smallest value of every
+        block of 64 x 64 luma samples (0x7fffffff: no window starts there).  slot, ref, window, job: as compare()."""
+        win = tuple(window or (0, 0, self.width, self.height))
+        nc = 3 if self.chroma_format else 1
+        raw = abi.FrameSsim()
+        blocks = np.zeros(abi.ssim_map_shape(win), np.int32) if with_map else None
+        self._against_reference("ssim", slot, ref, win, job, abi.ssim_request, self.L.vvr_ssim_submit, raw, blocks)
+        mean = (C.c_double * 4)()
+        if self.L.vvr_compare_ssim(C.byref(raw), mean) != abi.VVR_OK:
+            raise VvrError("vvr_compare_ssim: a result of vvr_ssim_submit at 8 to 10 bits")
+        out = dict(raw=raw, bit_depth=raw.bit_depth, num_components=raw.num_components, ssim=list(mean))
+        for name in ("width", "height", "sum", "windows", "min"):
+            out[name] = [int(v) for v in getattr(raw, name)][:nc]
+        out["min_at"] = [(raw.min_x[c], raw.min_y[c]) if raw.windows[c] else None for c in range(nc)]
+        if with_map:
+            out["map"] = blocks
+        return out
 
     def write_picture(self, slot, planes):
         for c, pl in enumerate(planes):

@@ -339,5 +339,32 @@ def compare_request(slot, job, window, ref, result, map_=None, blocking=True, re
     return r
 
 
+class FrameSsim(C.Structure):
+    """vvr_frame_ssim: what vvr_output_wait writes for an SSIM request (vvr_ssim_submit, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("bit_depth", u32), ("num_components", u32), ("pad", u32), ("width", u32 * 3), ("height", u32 * 3),
+                ("windows_x", u32 * 3), ("windows_y", u32 * 3), ("windows", u64 * 3), ("sum", C.c_int64 * 3), ("min", i32 * 3),
+                ("min_x", u32 * 3), ("min_y", u32 * 3), ("pad2", u32)]
+
+
+class SsimRequest(C.Structure):
+    """vvr_ssim_request: SSIM of a picture against a reference frame as a request of the output queue (vvr_ssim_submit, vvr.h); field by field a
+    CompareRequest"""
+    _fields_ = list(CompareRequest._fields_)
+
+
+def ssim_map_shape(window):
+    """(rows, columns) of the map of an SSIM request: one word per block of 64 x 64 luma samples of the window"""
+    return compare_map_shape(window)
+
+
+def ssim_request(slot, job, window, ref, result, map_=None, blocking=True, ref_bytes_per_sample=2):
+    """an SsimRequest that writes into `result` (a FrameSsim) and, when given, `map_` (a C-contiguous int32 array of ssim_map_shape); everything
+    else as compare_request"""
+    c = compare_request(slot, job, window, ref, result, map_, blocking, ref_bytes_per_sample)
+    r = SsimRequest.from_buffer_copy(bytes(c))
+    r.struct_size = C.sizeof(SsimRequest)
+    return r
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]

@@ -316,6 +316,18 @@ struct CompareParams
 };
 void launch_output_compare( hipStream_t s, const CompareParams& p, uint32_t* recs, uint32_t* map );
 void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks, int numComp, uint32_t* out );
+// SSIM of a picture against a reference frame (vvr_ssim_submit, the definition: vvr.h), on the comparison's parameters and blocks: a block owns the
+// SSIM windows (8 x 8 samples at a stride of 4) whose ORIGIN lies in it.  launch_output_ssim: recs[( c * nbx * nby + b ) * SSIM_REC_WORDS ..] = the
+// record of component c in block b - the sum of v (low word, high word), then the smallest v with the first window that has it as ONE 64-bit key,
+// low word first: ( (uint32_t) v ^ 0x80000000 ) << 32 | gj * windows_x + gi for window ( gi, gj ) of the component's grid, so that the smaller key is
+// the smaller v and, among equals, the earlier window in raster order; all ones: no window - and map[b] = the smallest v of the block over the
+// components (0x7fffffff: none); every word is stored, nothing has to be cleared.  launch_output_ssim_sum: out[c * SSIM_OUT_WORDS ..] = the sum and
+// the smallest key over the blocks, in the same four words.
+#define SSIM_REC_WORDS 4
+#define SSIM_OUT_WORDS 4
+#define SSIM_NO_WINDOW 0xffffffffffffffffull
+void launch_output_ssim( hipStream_t s, const CompareParams& p, int bitDepth, uint32_t* recs, int32_t* map );
+void launch_output_ssim_sum( hipStream_t s, const uint32_t* recs, int blocks, int numComp, uint32_t* out );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.
 // launch_hash_rows: one launch over the rows of all planes, rows[g] = the CRC piece (the row's bytes mod P, register from 0) or the checksum share
 // of row g (the planes' rows one after the other).  launch_hash_combine: out[c] = the component's digest as a number - the checksum, or the CRC

@@ -5792,6 +5792,219 @@ void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks,
   hipLaunchKernelGGL( k_output_compare_sum, dim3( numComp ), dim3( 256 ), 0, s, recs, blocks, out );
 }
 
+// k_output_ssim — SSIM of a picture against a reference frame (vvr_ssim_submit, the definition: vvr.h), on the blocks of k_output_compare: a workgroup
+// owns the SSIM windows (8 x 8 samples at a stride of 4) whose origin lies in its block of 64 x 64 luma samples and in the 32 x 32 samples of both
+// chroma components.  Such a window reaches 4 samples into the blocks to the right and below, so the workgroup reads 68 x 68 luma and 36 x 36 chroma
+// samples, clipped to the window of the request, as cells of 4 x 4 samples: 17 x 17 luma cells and 9 x 9 per chroma component.  Stage 1: a lane owns
+// two cells side by side - 4 rows of 8 samples, each one 16-byte load of the slot and one 16- or 8-byte load of the reference as cmp_load reads a
+// piece; the ninth (fifth) pair of a row of cells is the halo's single cell, half as wide.  17 x 9 luma pairs and 2 x 9 x 5 chroma pairs are 243
+// tasks: one per lane, all eight loads in registers before the first is looked at.  Only cells that lie wholly inside the
+// request's window are loaded - no SSIM window uses another - and the class the host selects (CompareParams::bySample) reads them sample by sample.
+// The lane clamps both sides to 2^bd - 1, forms the five sums of its cells (16 samples x 1023^2 < 2^24) and stores them in LDS, one array per sum:
+// a lane's two cells are neighbouring words, so each of the ten stores puts two lanes on a bank; in stage 2 the four 17-word rows a wavefront reads
+// are 67 all but consecutive words, one or two of which meet another lane's bank (32 lanes form a group of ds_read_b32).  Stage 2: a lane evaluates the luma window ( tid & 15, tid >> 4 ) of the block from four cells, and the lanes of wavefront 0 (Cb) and
+// 1 (Cr) one chroma window each; sums of 64 samples stay below 2^27, the products and both quotients are 64-bit integers exactly as vvr.h writes
+// them.  The sum of v (64 bits) and the key ( v biased to unsigned << 32 | the window's raster index in the component's grid ) - whose minimum is the
+// smallest v and among equals the first window - go across the wavefront in registers, across the wavefronts through 32 words of LDS; lane c stores
+// the record of component c, lane 0 the map word.  No atomics, nothing cleared beforehand: every word of the output is stored exactly once.
+#define SSIM_LUMA_CELLS 289      /* 17 x 17 */
+#define SSIM_CHROMA_CELLS 81     /* 9 x 9 */
+#define SSIM_CELLS ( SSIM_LUMA_CELLS + 2 * SSIM_CHROMA_CELLS )
+struct SsimRows { uint4 a[4], b[4]; };      // 4 rows of 8 slot samples and 8 reference samples, two to a dword (RB == 1: the bytes in b.x, b.y)
+struct SsimAcc { int64_t sum; uint64_t key; };
+template<int RB, bool BYSAMPLE>
+__device__ __forceinline__ SsimRows ssim_load( const CompareParams& p, int c, int i0, int j0, int cells )      // cells: how many of the two are wanted
+{
+  SsimRows q;
+#pragma unroll
+  for( int r = 0; r < 4; r++ ) { q.a[r] = make_uint4( 0, 0, 0, 0 ); q.b[r] = make_uint4( 0, 0, 0, 0 ); }
+  if( c >= p.numComp || j0 + 4 > p.h[c] ) return q;
+  cells = min( cells, ( p.w[c] - i0 ) >> 2 );      // whole cells inside the window
+  if( cells <= 0 ) return q;
+#pragma unroll
+  for( int r = 0; r < 4; r++ )
+  {
+    const pel_t* __restrict__ s = p.src[c] + (size_t) ( j0 + r ) * p.stride[c] + i0;
+    const uint8_t* __restrict__ y = p.ref[c] + (size_t) ( j0 + r ) * p.refStride[c] + (size_t) i0 * RB;
+    if( !BYSAMPLE && cells == 2 )
+    {
+      __builtin_memcpy( &q.a[r], s, 16 );
+      if( RB == 2 ) __builtin_memcpy( &q.b[r], y, 16 ); else { uint2 t; __builtin_memcpy( &t, y, 8 ); q.b[r].x = t.x; q.b[r].y = t.y; }
+    }
+    else if( !BYSAMPLE )
+    {
+      uint2 t; __builtin_memcpy( &t, s, 8 ); q.a[r].x = t.x; q.a[r].y = t.y;
+      if( RB == 2 ) { __builtin_memcpy( &t, y, 8 ); q.b[r].x = t.x; q.b[r].y = t.y; } else { uint32_t u; __builtin_memcpy( &u, y, 4 ); q.b[r].x = u; }
+    }
+    else
+    {
+      uint32_t va[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, vb[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+      for( int i = 0; i < 8; i++ )
+        if( i < 4 * cells ) { va[i] = (uint16_t) s[i]; vb[i] = RB == 1 ? (uint32_t) y[i] : (uint32_t) y[2 * i] | (uint32_t) y[2 * i + 1] << 8; }
+      q.a[r] = make_uint4( va[0] | va[1] << 16, va[2] | va[3] << 16, va[4] | va[5] << 16, va[6] | va[7] << 16 );
+      if( RB == 2 ) q.b[r] = make_uint4( vb[0] | vb[1] << 16, vb[2] | vb[3] << 16, vb[4] | vb[5] << 16, vb[6] | vb[7] << 16 );
+      else { q.b[r].x = vb[0] | vb[1] << 8 | vb[2] << 16 | vb[3] << 24; q.b[r].y = vb[4] | vb[5] << 8 | vb[6] << 16 | vb[7] << 24; }
+    }
+  }
+  return q;
+}
+// the five sums - x, y, x * x, y * y, x * y - of the two cells, both sides clamped to `top` (cells that were not loaded are zeros: so are their sums)
+template<int RB>
+__device__ __forceinline__ void ssim_cells( const SsimRows& q, uint32_t top, uint32_t s[2][5] )
+{
+#pragma unroll
+  for( int k = 0; k < 2; k++ )
+#pragma unroll
+    for( int n = 0; n < 5; n++ ) s[k][n] = 0;
+#pragma unroll
+  for( int r = 0; r < 4; r++ )
+  {
+    const uint32_t wa[4] = { q.a[r].x, q.a[r].y, q.a[r].z, q.a[r].w }, wb[4] = { q.b[r].x, q.b[r].y, q.b[r].z, q.b[r].w };
+#pragma unroll
+    for( int i = 0; i < 8; i++ )
+    {
+      const uint32_t a = min( ( wa[i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffffu, top );
+      const uint32_t b = min( RB == 2 ? ( wb[i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffffu : ( wb[i >> 2] >> ( 8 * ( i & 3 ) ) ) & 0xffu, top );
+      uint32_t* t = s[i >> 2];
+      t[0] += a; t[1] += b; t[2] += a * a; t[3] += b * b; t[4] += a * b;
+    }
+  }
+}
+// v of the window whose top left cell is `at` in a grid of `pitch` cells a row: vvr.h line by line
+__device__ __forceinline__ int64_t ssim_window( const uint32_t ( *cell )[SSIM_CELLS], int at, int pitch, int64_t C1, int64_t C2 )
+{
+  uint32_t t[5];
+#pragma unroll
+  for( int n = 0; n < 5; n++ ) t[n] = cell[n][at] + cell[n][at + 1] + cell[n][at + pitch] + cell[n][at + pitch + 1];
+  const int64_t s1 = t[0], s2 = t[1], sxx = t[2], syy = t[3], sxy = t[4];
+  const int64_t A1 = 2 * s1 * s2 + C1, B1 = s1 * s1 + s2 * s2 + C1;
+  const int64_t A2 = 2 * ( 64 * sxy - s1 * s2 ) + C2, B2 = ( 64 * sxx - s1 * s1 ) + ( 64 * syy - s2 * s2 ) + C2;
+  const int64_t l = ( A1 * 16777216 ) / B1, c = ( A2 * 16777216 ) / B2;
+  return ( l * c ) / 16777216;
+}
+__device__ __forceinline__ uint64_t ssim_key( int64_t v, uint32_t index ) { return (uint64_t) ( (uint32_t) (int32_t) v ^ 0x80000000u ) << 32 | index; }
+__device__ __forceinline__ SsimAcc ssim_wave( SsimAcc v )      // over the wavefront, in every lane
+{
+#pragma unroll
+  for( int d = 1; d < 64; d <<= 1 )
+  {
+    const uint64_t u = (uint64_t) v.sum;
+    const uint32_t slo = (uint32_t) __shfl_xor( (int) (uint32_t) u, d ), shi = (uint32_t) __shfl_xor( (int) (uint32_t) ( u >> 32 ), d );
+    const uint32_t klo = (uint32_t) __shfl_xor( (int) (uint32_t) v.key, d ), khi = (uint32_t) __shfl_xor( (int) (uint32_t) ( v.key >> 32 ), d );
+    v.sum = (int64_t) ( u + ( slo | (uint64_t) shi << 32 ) ); v.key = min( v.key, klo | (uint64_t) khi << 32 );
+  }
+  return v;
+}
+template<int RB, bool BYSAMPLE>
+__global__ __launch_bounds__( 256 ) void k_output_ssim( CompareParams p, int bitDepth, uint32_t* __restrict__ recs, int32_t* __restrict__ map )
+{
+  __shared__ uint32_t cell[5][SSIM_CELLS];
+  __shared__ uint32_t part[4][2][SSIM_REC_WORDS];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int X0 = blockIdx.x * 64, Y0 = blockIdx.y * 64;
+  // ---- stage 1: the lane's pair of cells.  Lanes 0 .. 152: luma, 9 pairs a row of cells; 153 .. 197: Cb, 198 .. 242: Cr, 5 pairs a row
+  const bool luma = tid < 153;
+  const int t = luma ? tid : ( tid - 153 ) % 45, perRow = luma ? 9 : 5, pitch = luma ? 17 : 9;
+  const int c = luma ? 0 : tid < 198 ? 1 : tid < 243 ? 2 : 3, sh = luma ? 0 : 1;      // (3: no task)
+  const int cr = t / perRow, pp = t % perRow, wanted = pp == perRow - 1 ? 1 : 2;
+  const SsimRows q = ssim_load<RB, BYSAMPLE>( p, c, ( X0 >> sh ) + pp * 8, ( Y0 >> sh ) + cr * 4, wanted );
+  uint32_t s[2][5];
+  ssim_cells<RB>( q, ( 1u << bitDepth ) - 1, s );
+  if( c < 3 )
+  {
+    const int at = ( luma ? 0 : SSIM_LUMA_CELLS + ( c - 1 ) * SSIM_CHROMA_CELLS ) + cr * pitch + 2 * pp;
+#pragma unroll
+    for( int n = 0; n < 5; n++ ) { cell[n][at] = s[0][n]; if( wanted == 2 ) cell[n][at + 1] = s[1][n]; }
+  }
+  __syncthreads();
+  // ---- stage 2: a luma window per lane, a chroma window per lane of wavefronts 0 (Cb) and 1 (Cr)
+  const int64_t top = ( 1 << bitDepth ) - 1, C1 = ( top * top * 4096 + 5000 ) / 10000, C2 = ( 9 * top * top * 4096 + 5000 ) / 10000;
+  SsimAcc lum = { 0, SSIM_NO_WINDOW }, chr = { 0, SSIM_NO_WINDOW };
+  {
+    const int wi = tid & 15, wj = tid >> 4, gx = X0 + 4 * wi, gy = Y0 + 4 * wj;
+    if( gx + 8 <= p.w[0] && gy + 8 <= p.h[0] )
+    {
+      lum.sum = ssim_window( cell, wj * 17 + wi, 17, C1, C2 );
+      lum.key = ssim_key( lum.sum, (uint32_t) ( ( gy >> 2 ) * ( ( p.w[0] - 8 ) / 4 + 1 ) + ( gx >> 2 ) ) );      // (sides <= 8192: below 2^22)
+    }
+  }
+  if( wave < 2 && p.numComp > 1 )
+  {
+    const int k = 1 + wave, wi = tid & 7, wj = ( tid >> 3 ) & 7, gx = ( X0 >> 1 ) + 4 * wi, gy = ( Y0 >> 1 ) + 4 * wj;
+    if( gx + 8 <= p.w[k] && gy + 8 <= p.h[k] )
+    {
+      chr.sum = ssim_window( cell, SSIM_LUMA_CELLS + wave * SSIM_CHROMA_CELLS + wj * 9 + wi, 9, C1, C2 );
+      chr.key = ssim_key( chr.sum, (uint32_t) ( ( gy >> 2 ) * ( ( p.w[k] - 8 ) / 4 + 1 ) + ( gx >> 2 ) ) );
+    }
+  }
+  lum = ssim_wave( lum ); chr = ssim_wave( chr );
+  if( ( tid & 63 ) == 0 )
+  {
+    uint32_t* l = part[wave][0]; uint32_t* k = part[wave][1];
+    l[0] = (uint32_t) (uint64_t) lum.sum; l[1] = (uint32_t) ( (uint64_t) lum.sum >> 32 ); l[2] = (uint32_t) lum.key; l[3] = (uint32_t) ( lum.key >> 32 );
+    k[0] = (uint32_t) (uint64_t) chr.sum; k[1] = (uint32_t) ( (uint64_t) chr.sum >> 32 ); k[2] = (uint32_t) chr.key; k[3] = (uint32_t) ( chr.key >> 32 );
+  }
+  __syncthreads();
+  if( tid >= p.numComp ) return;
+  // lane c folds component c: luma from the four wavefronts, Cb from wavefront 0, Cr from wavefront 1
+  const int w0 = tid == 2 ? 1 : 0, w1 = tid == 0 ? 4 : w0 + 1, set = tid ? 1 : 0;
+  uint64_t sum = 0, key = SSIM_NO_WINDOW;      // (the sum in two's complement)
+  for( int w = w0; w < w1; w++ )
+  {
+    const uint32_t* v = part[w][set];
+    sum += v[0] | (uint64_t) v[1] << 32; key = min( key, v[2] | (uint64_t) v[3] << 32 );
+  }
+  const int b = blockIdx.y * gridDim.x + blockIdx.x, blocks = gridDim.x * gridDim.y;
+  uint32_t* __restrict__ rec = recs + ( (size_t) tid * blocks + b ) * SSIM_REC_WORDS;
+  rec[0] = (uint32_t) sum; rec[1] = (uint32_t) ( sum >> 32 ); rec[2] = (uint32_t) key; rec[3] = (uint32_t) ( key >> 32 );
+  // the map word: the three smallest v, still biased, meet in lane 0 (lanes 0 .. 2 are of one wavefront, all three here in 4:2:0)
+  uint32_t low = (uint32_t) ( key >> 32 );
+  if( p.numComp > 1 ) low = min( low, min( (uint32_t) __shfl( (int) low, 1 ), (uint32_t) __shfl( (int) low, 2 ) ) );
+  if( tid == 0 ) map[b] = (int32_t) ( low ^ 0x80000000u );
+}
+// k_output_ssim_sum — workgroup c folds the records of component c into its SSIM_OUT_WORDS words: the 64-bit sum and the smallest key - the keys
+// carry the window's index in the component's grid, so that the minimum is the first in raster order whatever block holds it
+__global__ __launch_bounds__( 256 ) void k_output_ssim_sum( const uint32_t* __restrict__ recs, int blocks, uint32_t* __restrict__ out )
+{
+  __shared__ uint32_t part[4][SSIM_OUT_WORDS];
+  const int tid = threadIdx.x, c = blockIdx.x;
+  uint64_t sum = 0, key = SSIM_NO_WINDOW;
+  for( int b = tid; b < blocks; b += 256 )
+  {
+    const uint4 v = *(const uint4*) ( recs + ( (size_t) c * blocks + b ) * SSIM_REC_WORDS );      // (16 bytes a record, the base is a hipMalloc's)
+    sum += v.x | (uint64_t) v.y << 32; key = min( key, v.z | (uint64_t) v.w << 32 );
+  }
+  SsimAcc a = { (int64_t) sum, key };
+  a = ssim_wave( a );
+  if( ( tid & 63 ) == 0 )
+  {
+    uint32_t* v = part[tid >> 6];
+    v[0] = (uint32_t) (uint64_t) a.sum; v[1] = (uint32_t) ( (uint64_t) a.sum >> 32 ); v[2] = (uint32_t) a.key; v[3] = (uint32_t) ( a.key >> 32 );
+  }
+  __syncthreads();
+  if( tid ) return;
+  sum = 0; key = SSIM_NO_WINDOW;
+  for( int w = 0; w < 4; w++ )
+  {
+    const uint32_t* v = part[w];
+    sum += v[0] | (uint64_t) v[1] << 32; key = min( key, v[2] | (uint64_t) v[3] << 32 );
+  }
+  uint32_t* __restrict__ o = out + c * SSIM_OUT_WORDS;
+  o[0] = (uint32_t) sum; o[1] = (uint32_t) ( sum >> 32 ); o[2] = (uint32_t) key; o[3] = (uint32_t) ( key >> 32 );
+}
+void launch_output_ssim( hipStream_t s, const CompareParams& p, int bitDepth, uint32_t* recs, int32_t* map )
+{
+  const dim3 grid( p.nbx, p.nby );
+  if( p.bySample ) { if( p.refBytes == 1 ) hipLaunchKernelGGL( ( k_output_ssim<1, true> ), grid, dim3( 256 ), 0, s, p, bitDepth, recs, map ); else hipLaunchKernelGGL( ( k_output_ssim<2, true> ), grid, dim3( 256 ), 0, s, p, bitDepth, recs, map ); }
+  else if( p.refBytes == 1 ) hipLaunchKernelGGL( ( k_output_ssim<1, false> ), grid, dim3( 256 ), 0, s, p, bitDepth, recs, map );
+  else hipLaunchKernelGGL( ( k_output_ssim<2, false> ), grid, dim3( 256 ), 0, s, p, bitDepth, recs, map );
+}
+void launch_output_ssim_sum( hipStream_t s, const uint32_t* recs, int blocks, int numComp, uint32_t* out )
+{
+  hipLaunchKernelGGL( k_output_ssim_sum, dim3( numComp ), dim3( 256 ), 0, s, recs, blocks, out );
+}
+
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in
 __device__ __forceinline__ uint32_t crc_mul( uint32_t a, uint32_t b )
 {

@@ -487,6 +487,56 @@ void launch_output_compare_sum( hipStream_t, const uint32_t* recs, int blocks, i
     o[6] = top; o[7] = first;
   }
 }
+
+// ... and launch_output_ssim / launch_output_ssim_sum (k_output_ssim, k_output_ssim_sum): the definition of vvr.h window by window and sample by
+// sample, a record per block and component as vvr_device.h lays them out; the records folded
+void launch_output_ssim( hipStream_t, const CompareParams& p, int bitDepth, uint32_t* recs, int32_t* map )
+{
+  const int blocks = p.nbx * p.nby;
+  const int64_t L = ( 1 << bitDepth ) - 1, N = 64, C1 = ( L * L * 4096 + 5000 ) / 10000, C2 = ( 9 * L * L * 4096 + 5000 ) / 10000;
+  for( int b = 0; b < blocks; b++ )
+  {
+    map[b] = 0x7fffffff;
+    for( int c = 0; c < p.numComp; c++ )
+    {
+      const int side = c ? 32 : 64, i0 = ( b % p.nbx ) * side, j0 = ( b / p.nbx ) * side, windowsX = p.w[c] >= 8 ? ( p.w[c] - 8 ) / 4 + 1 : 0;
+      int64_t sum = 0; uint64_t key = SSIM_NO_WINDOW;
+      for( int j = j0; j < j0 + side && j + 8 <= p.h[c]; j += 4 )
+        for( int i = i0; i < i0 + side && i + 8 <= p.w[c]; i += 4 )
+        {
+          int64_t s1 = 0, s2 = 0, sxx = 0, syy = 0, sxy = 0;
+          for( int jj = j; jj < j + 8; jj++ )
+            for( int ii = i; ii < i + 8; ii++ )
+            {
+              const uint8_t* r = p.ref[c] + (size_t) jj * p.refStride[c] + (size_t) ii * p.refBytes;
+              const int64_t x = std::min<int64_t>( (uint16_t) p.src[c][(size_t) jj * p.stride[c] + ii], L ), y = std::min<int64_t>( p.refBytes == 1 ? r[0] : r[0] | r[1] << 8, L );
+              s1 += x; s2 += y; sxx += x * x; syy += y * y; sxy += x * y;
+            }
+          const int64_t A1 = 2 * s1 * s2 + C1, B1 = s1 * s1 + s2 * s2 + C1, A2 = 2 * ( N * sxy - s1 * s2 ) + C2, B2 = ( N * sxx - s1 * s1 ) + ( N * syy - s2 * s2 ) + C2;
+          const int64_t l = ( A1 * 16777216 ) / B1, cs = ( A2 * 16777216 ) / B2, v = ( l * cs ) / 16777216;
+          sum += v;
+          key = std::min( key, (uint64_t) ( (uint32_t) (int32_t) v ^ 0x80000000u ) << 32 | (uint32_t) ( ( j / 4 ) * windowsX + i / 4 ) );
+        }
+      uint32_t* rec = recs + ( (size_t) c * blocks + b ) * SSIM_REC_WORDS;
+      rec[0] = (uint32_t) (uint64_t) sum; rec[1] = (uint32_t) ( (uint64_t) sum >> 32 ); rec[2] = (uint32_t) key; rec[3] = (uint32_t) ( key >> 32 );
+      map[b] = std::min( map[b], (int32_t) ( (uint32_t) ( key >> 32 ) ^ 0x80000000u ) );
+    }
+  }
+}
+void launch_output_ssim_sum( hipStream_t, const uint32_t* recs, int blocks, int numComp, uint32_t* out )
+{
+  for( int c = 0; c < numComp; c++ )
+  {
+    uint64_t sum = 0, key = SSIM_NO_WINDOW;      // (the sum in two's complement)
+    for( int b = 0; b < blocks; b++ )
+    {
+      const uint32_t* rec = recs + ( (size_t) c * blocks + b ) * SSIM_REC_WORDS;
+      sum += rec[0] | (uint64_t) rec[1] << 32; key = std::min( key, rec[2] | (uint64_t) rec[3] << 32 );
+    }
+    uint32_t* o = out + c * SSIM_OUT_WORDS;
+    o[0] = (uint32_t) sum; o[1] = (uint32_t) ( sum >> 32 ); o[2] = (uint32_t) key; o[3] = (uint32_t) ( key >> 32 );
+  }
+}
 #endif
 
 extern "C" {
@@ -797,6 +847,22 @@ VVR_API int vvr_compare_psnr( const vvr_frame_compare* cmp, double peak, double 
   return VVR_OK;
 }
 
+// mean SSIM from the sums of an SSIM request (vvr_ssim_submit), the formula as vvr.h gives it, in double
+VVR_API int vvr_compare_ssim( const vvr_frame_ssim* sm, double ssim[4] )
+{
+  if( !sm || !ssim || sm->struct_size != sizeof( vvr_frame_ssim ) || sm->bit_depth < 8 || sm->bit_depth > 10 || !sm->windows[0] ) return VVR_ERR_PARAMETER;
+  auto mean = [&]( double sum, double windows ) { return windows == 0 ? 0.0 : sum / ( windows * 16777216.0 ); };
+  const int nc = sm->num_components == 1 ? 1 : 3;
+  double sum = 0, windows = 0;
+  for( int k = 0; k < 3; k++ )
+  {
+    ssim[k] = k < nc ? mean( (double) sm->sum[k], (double) sm->windows[k] ) : 0.0;
+    if( k < nc ) { sum += (double) sm->sum[k]; windows += (double) sm->windows[k]; }
+  }
+  ssim[3] = mean( sum, windows );
+  return VVR_OK;
+}
+
 VVR_API int vvr_read_output_grain( vvr_context* c, int slot, int x, int y, int w, int h, int bytesPerSample, void* const dst[3], const size_t dstStrideBytes[3] )
 {
   if( !c || slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] || !dst || !dstStrideBytes ) return VVR_ERR_PARAMETER;
@@ -995,6 +1061,8 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // `tmp`, where a reference from the host is packed (copied from the caller's pinned memory, or through the entry's pinned staging).  Its scratch
 // holds a record per block and component, every word of which k_output_compare stores - nothing is cleared - then the words
 // k_output_compare_sum folds them to and the map; the words (with `map` the map too) are all that crosses PCIe back.
+// An SSIM request (vvr_ssim_submit) is a comparison request with other kernels (k_output_ssim, k_output_ssim_sum), records and words: both calls
+// go through compareSubmit.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -1017,6 +1085,9 @@ struct OutEntry {
   // a comparison request: its number of components (0: none); CMP_OUT_WORDS words per component at the start of `host`, the map's words from
   // word CMP_HEAD_WORDS on; the second slot it reads (-1: none); what vvr_output_wait writes
   int cmp = 0, cmpW = 0, cmpH = 0, cmpBlocks = 0, refSlot = -1; vvr_frame_compare* cmpOut = nullptr; uint32_t* cmpMap = nullptr;
+  // ... or an SSIM request, which is a comparison request with records and words of its own (SSIM_OUT_WORDS per component) and with cmpOut and
+  // cmpMap pointing to a vvr_frame_ssim and to int32_t words
+  bool cmpSsim = false;
 };
 #define CMP_HEAD_WORDS 32      /* 3 x CMP_OUT_WORDS, rounded up: the map starts at a multiple of 128 bytes */
 
@@ -1533,12 +1604,14 @@ VVR_API int vvr_stats_submit( vvr_context* c, const vvr_stats_request* rq )
   return ticket;
 }
 
-VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
+// vvr_compare_submit and vvr_ssim_submit (`who`): one path for the window, the reference's home and staging, the ring entry, the ordering behind
+// both slots and the result's way back; `ssim` selects the refusal of windows below 8 x 8, the size of a record, the kernels and what
+// vvr_output_wait writes.  A vvr_ssim_request is a vvr_compare_request field by field (result and map are pointers to other types)
+static_assert( sizeof( vvr_ssim_request ) == sizeof( vvr_compare_request ) && offsetof( vvr_ssim_request, ref ) == offsetof( vvr_compare_request, ref ) &&
+               offsetof( vvr_ssim_request, result ) == offsetof( vvr_compare_request, result ) && offsetof( vvr_ssim_request, map ) == offsetof( vvr_compare_request, map ), "vvr_ssim_request mirrors vvr_compare_request" );
+static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const char* who, bool ssim )
 {
-  if( !c || !rq ) return VVR_ERR_PARAMETER;
-  const char* const who = "vvr_compare_submit";
-  // ---- 1. the request
-  if( rq->struct_size != sizeof( vvr_compare_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_compare_request )", who );
+  // ---- 1. the request (its struct_size has been looked at)
   const int slot = rq->slot, refSlot = rq->ref_slot, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot", who );
   if( refSlot < -1 || refSlot >= (int) c->slots.size() || ( refSlot >= 0 && !c->slots[refSlot].p[0] ) ) return outRefuse( c, "no such ref_slot", who );
@@ -1547,6 +1620,7 @@ VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
   if( !rq->result ) return outRefuse( c, "result is NULL", who );
   const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot, not the slot)
   if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, empty, or odd in 4:2:0", who );
+  if( ssim && ( w < 8 || h < 8 ) ) return outRefuse( c, "a window below 8 x 8 holds no SSIM window", who );
   const int rb = refSlot >= 0 ? 2 : rq->ref_bytes_per_sample;
   CompareParams p; memset( &p, 0, sizeof( p ) );
   size_t rowBytes[3] = { 0, 0, 0 }, extent[3] = { 0, 0, 0 };
@@ -1586,9 +1660,9 @@ VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
   for( int k = 0; k < nc && pinnedRef; k++ ) pinnedRef = c->pinned.contains( rq->ref[k], extent[k] );
   // ---- the entry's buffers: the blocks' records, the folded words and the map behind them; a reference from the host packed in `tmp`, rows at a
   // multiple of 16 bytes; pinned: the folded words and the map, then the staging of a reference in pageable memory
-  const int blocks = p.nbx * p.nby;
-  const size_t recBytes = alignUp( sizeof( uint32_t ) * CMP_REC_WORDS * nc * blocks, 256 ), wordBytes = sizeof( uint32_t ) * ( CMP_HEAD_WORDS + blocks );
-  const size_t crossBytes = sizeof( uint32_t ) * ( rq->map ? CMP_HEAD_WORDS + blocks : 3 * CMP_OUT_WORDS ), hostStageOff = alignUp( wordBytes, 256 );
+  const int blocks = p.nbx * p.nby, recWords = ssim ? SSIM_REC_WORDS : CMP_REC_WORDS, outWords = ssim ? SSIM_OUT_WORDS : CMP_OUT_WORDS;
+  const size_t recBytes = alignUp( sizeof( uint32_t ) * recWords * nc * blocks, 256 ), wordBytes = sizeof( uint32_t ) * ( CMP_HEAD_WORDS + blocks );
+  const size_t crossBytes = sizeof( uint32_t ) * ( rq->map ? CMP_HEAD_WORDS + blocks : 3 * outWords ), hostStageOff = alignUp( wordBytes, 256 );
   size_t stageOff[3] = { 0, 0, 0 }, stageStride[3] = { 0, 0, 0 }, stageBytes = 0;
   for( int k = 0; k < nc && staged; k++ ) { stageOff[k] = stageBytes; stageStride[k] = alignUp( rowBytes[k], 16 ); stageBytes += alignUp( stageStride[k] * p.h[k], 256 ); }
   // ---- a reference in pageable memory goes into an entry's pinned memory BEFORE the request is ordered: from outAcquire to the registration of the
@@ -1619,7 +1693,7 @@ VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
   { const int rc = outAcquire( c, who, slot, rq->job, rq->blocking != 0, lk, e, jobDone, jobFailed, mine ); if( rc != VVR_OK ) return rc; }
   hipStream_t s = c->outQStream;
   outTake( c, e, slot, rq->job, jobFailed );
-  e->cmp = nc; e->cmpW = w; e->cmpH = h; e->cmpBlocks = blocks; e->cmpOut = rq->result; e->cmpMap = rq->map;
+  e->cmp = nc; e->cmpW = w; e->cmpH = h; e->cmpBlocks = blocks; e->cmpOut = rq->result; e->cmpMap = rq->map; e->cmpSsim = ssim;
   if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
   if( outGrow( e->dev, e->devCap, recBytes + wordBytes, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, stageBytes, false ) != VVR_OK ||
       outGrow( e->host, e->hostCap, hostStageOff, true ) != VVR_OK )      // (a staged reference: grown above, beyond this)
@@ -1647,16 +1721,18 @@ VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
   uint32_t* recs = (uint32_t*) e->dev; uint32_t* words = (uint32_t*) ( e->dev + recBytes );
   double samples = 0;
   for( int k = 0; k < nc; k++ ) samples += (double) p.w[k] * p.h[k];
-  outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_COMPARE, samples * ( 2 + rb ) );
-  launch_output_compare( s, p, recs, words + CMP_HEAD_WORDS );
+  outTimeBegin( c, s, e->timed, e->timing, ssim ? K_OUTPUT_SSIM : K_OUTPUT_COMPARE, samples * ( 2 + rb ) );
+  if( ssim ) launch_output_ssim( s, p, c->cfg.bit_depth, recs, (int32_t*) ( words + CMP_HEAD_WORDS ) );
+  else launch_output_compare( s, p, recs, words + CMP_HEAD_WORDS );
   if( e->timed ) hipEventRecord( e->timing.b, s );
   OQCHK( hipGetLastError() );
   OQCHK( hipEventRecord( e->read, s ) );      // (the slots' reader ends here: the fold reads the entry's scratch)
   c->slotExt[slot].push_back( e->read );
   if( refSlot >= 0 ) { c->slotExt[refSlot].push_back( e->read ); e->refSlot = refSlot; }
   e->state = OQ_FLIGHT; e->queued = true;
-  outTimeBegin( c, s, e->timed2, e->timing2, K_OUTPUT_COMPARE_SUM, (double) sizeof( uint32_t ) * ( CMP_REC_WORDS * blocks + CMP_OUT_WORDS ) * nc );
-  launch_output_compare_sum( s, recs, blocks, nc, words );
+  outTimeBegin( c, s, e->timed2, e->timing2, ssim ? K_OUTPUT_SSIM_SUM : K_OUTPUT_COMPARE_SUM, (double) sizeof( uint32_t ) * ( recWords * blocks + outWords ) * nc );
+  if( ssim ) launch_output_ssim_sum( s, recs, blocks, nc, words );
+  else launch_output_compare_sum( s, recs, blocks, nc, words );
   if( e->timed2 ) hipEventRecord( e->timing2.b, s );
   const int ticket = e->ticket;
   lk.unlock();
@@ -1670,6 +1746,20 @@ VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
     lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( who ) + ": copy to the host: " + hipGetErrorString( ce ) );
   }
   return ticket;
+}
+VVR_API int vvr_compare_submit( vvr_context* c, const vvr_compare_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  if( rq->struct_size != sizeof( vvr_compare_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_compare_request )", "vvr_compare_submit" );
+  return compareSubmit( c, rq, "vvr_compare_submit", false );
+}
+VVR_API int vvr_ssim_submit( vvr_context* c, const vvr_ssim_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  if( rq->struct_size != sizeof( vvr_ssim_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_ssim_request )", "vvr_ssim_submit" );
+  vvr_compare_request q;
+  memcpy( &q, rq, sizeof( q ) );
+  return compareSubmit( c, &q, "vvr_ssim_submit", true );
 }
 #undef OQCHK
 
@@ -1700,7 +1790,7 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
   if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
   outTimeEnd( c, e->timed, e->timing );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS ...
-  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM; K_OUTPUT_COMPARE and K_OUTPUT_COMPARE_SUM)
+  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM; K_OUTPUT_COMPARE and K_OUTPUT_COMPARE_SUM; K_OUTPUT_SSIM and K_OUTPUT_SSIM_SUM)
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
   if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
   if( e->refSlot >= 0 ) { auto& v = c->slotExt[e->refSlot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }      // (a comparison reads two slots)
@@ -1738,7 +1828,30 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
       for( int k = 0; k < 3; k++ ) { st.max_c[k] = w[2048 + k]; st.min_c[k] = ( ( 1u << c->cfg.bit_depth ) - 1 ) - w[2051 + k]; }
     }
   }
-  if( rc == VVR_OK && e->queued && e->cmp )
+  if( rc == VVR_OK && e->queued && e->cmp && e->cmpSsim )
+  {
+    // the caller's vvr_frame_ssim: the header fields, the grid of windows, the folded words - the key taken apart into the smallest v and the
+    // origin of the first window that has it; the map
+    const uint32_t* w = (const uint32_t*) e->host;
+    vvr_frame_ssim r;
+    memset( &r, 0, sizeof( r ) );
+    r.struct_size = sizeof( r ); r.bit_depth = (uint32_t) c->cfg.bit_depth; r.num_components = (uint32_t) e->cmp;
+    for( int k = 0; k < 3; k++ )
+    {
+      r.min[k] = 0x7fffffff; r.min_x[k] = r.min_y[k] = 0xffffffffu;
+      if( k >= e->cmp ) continue;
+      const uint32_t* o = w + k * SSIM_OUT_WORDS;
+      r.width[k] = (uint32_t) ( e->cmpW >> ( k ? 1 : 0 ) ); r.height[k] = (uint32_t) ( e->cmpH >> ( k ? 1 : 0 ) );
+      r.windows_x[k] = r.width[k] >= 8 ? ( r.width[k] - 8 ) / 4 + 1 : 0; r.windows_y[k] = r.height[k] >= 8 ? ( r.height[k] - 8 ) / 4 + 1 : 0;
+      r.windows[k] = (uint64_t) r.windows_x[k] * r.windows_y[k];
+      if( !r.windows[k] ) continue;
+      r.sum[k] = (int64_t) ( o[0] | (uint64_t) o[1] << 32 ); r.min[k] = (int32_t) ( o[3] ^ 0x80000000u );
+      r.min_x[k] = 4 * ( o[2] % r.windows_x[k] ); r.min_y[k] = 4 * ( o[2] / r.windows_x[k] );
+    }
+    memcpy( (void*) e->cmpOut, &r, sizeof( r ) );
+    if( e->cmpMap ) memcpy( e->cmpMap, w + CMP_HEAD_WORDS, sizeof( uint32_t ) * e->cmpBlocks );
+  }
+  else if( rc == VVR_OK && e->queued && e->cmp )
   {
     // the caller's vvr_frame_compare: the header fields, the folded words, the first index as a position in the component's window; the map
     const uint32_t* w = (const uint32_t*) e->host;
