@@ -357,6 +357,18 @@ int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes,
       for( int w : colW ) pps.addTileColumnWidth( w );
       for( int h : rowH ) pps.addTileRowHeight( h );
       pps.initTiles();
+      // pps_rect_slice_flag as the layout says: a slice that is no rectangle of CTUs can only be a raster-scan slice (a run of tiles that starts or ends inside a
+      // tile row); every other layout can be written as rectangular slices and is (the description does not say which
+      // mode the stream used, and no class the harness drives reads the flag: the filters work from the slice objects)
+      bool rect = true;
+      if( vp->ctu_slice )
+      {
+        int ns = 0; for( int a = 0; a < cX * cY; a++ ) ns = std::max( ns, vp->ctu_slice[a] + 1 );
+        std::vector<int> x0( ns, cX ), y0( ns, cY ), x1( ns, -1 ), y1( ns, -1 ), cnt( ns, 0 );
+        for( int a = 0; a < cX * cY; a++ ) { const int k = vp->ctu_slice[a], x = a % cX, y = a / cX; x0[k] = std::min( x0[k], x ); y0[k] = std::min( y0[k], y ); x1[k] = std::max( x1[k], x ); y1[k] = std::max( y1[k], y ); cnt[k]++; }
+        for( int k = 0; k < ns; k++ ) if( cnt[k] && cnt[k] != ( x1[k] - x0[k] + 1 ) * ( y1[k] - y0[k] + 1 ) ) rect = false;
+      }
+      pps.setRectSliceFlag( rect );
     }
     // horizontal reference wrap-around (sps_ref_wraparound_enabled_flag / pps_ref_wraparound_enabled_flag + offset)
     sps.setUseWrapAround( H.wrap_offset != 0 ); pps.setUseWrapAround( H.wrap_offset != 0 ); pps.setWrapAroundOffset( H.wrap_offset );
@@ -641,7 +653,17 @@ int vvref_reconstruct( const vvr_picture* vp, const uint16_t* const* ref_planes,
     slice->setIndependentSliceIdx( si );
     slice->resetSliceMap();
     if( !vp->ctu_slice ) slice->addCtusToSlice( 0, pps.pcv->widthInCtus, 0, pps.pcv->heightInCtus, pps.pcv->widthInCtus );
-    else for( int a = 0; a < numCtuAll; a++ ) if( vp->ctu_slice[a] == si ) { const int cx = a % (int) pps.pcv->widthInCtus, cy = a / (int) pps.pcv->widthInCtus; slice->addCtusToSlice( cx, cx + 1, cy, cy + 1, pps.pcv->widthInCtus ); }
+    else
+    {
+      // the CTUs of a slice in the order a stream carries them: tile by tile, raster scan inside a tile (a slice of several tiles; nothing the harness drives
+      // reads the order of this list, but it is the parser's)
+      const int numTilesAll = vp->ctu_tile ? (int) pps.getNumTiles() : 1;
+      for( int t = 0; t < numTilesAll; t++ ) for( int a = 0; a < numCtuAll; a++ ) if( vp->ctu_slice[a] == si && ( !vp->ctu_tile || vp->ctu_tile[a] == t ) )
+      {
+        const int cx = a % (int) pps.pcv->widthInCtus, cy = a / (int) pps.pcv->widthInCtus;
+        slice->addCtusToSlice( cx, cx + 1, cy, cy + 1, pps.pcv->widthInCtus );
+      }
+    }
     // reference picture lists: the description holds the union of the slices' lists and its CUs index that union, so every non-I slice is
     // given the union (a decoder's slices hold their own lists; whoever flattens a picture renumbers the indices, integration/vvr_extract.h)
     for( int l = 0; l < 2; l++ )

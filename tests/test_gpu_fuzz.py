@@ -2,7 +2,8 @@
 each run of the suite covers pictures and streams no run before it has seen:
   * generated pictures from the parameter space of tools/fuzz_oracle_vs_ref.py (tool switches, picture and CTU sizes, sample formats, split / residual densities,
     MV spreads incl. the `far` mode - vectors up to thousands of samples beyond the encoder's clip window in both directions, with and without reference
-    wrap-around, sometimes with components at the ends of the 18-bit range - and, for a quarter of the pictures, reference lists of 3 .. 16 entries),
+    wrap-around, sometimes with components at the ends of the 18-bit range - and, for a quarter of the pictures, reference lists of 3 .. 16 entries, for a third
+    a picture partitioning: tile grids, raster-scan and rectangular slices, sub-pictures, virtual boundaries),
     reconstructed through the C ABI on the HIP path and compared with the CPU oracle on the same reference pictures;
   * bitstreams written by tools/mini_vvenc.py with mutated tool mixes, decoded by the reference's application on the DROP-IN library with the HIP back-end behind
     vvdec::DecLibRecon: output MD5 == the reference decoder's (oracle/_ref/vvdecapp_ref).
@@ -82,6 +83,13 @@ def _case(rnd, far):
         tools |= abi.TOOL_LMCS
     if (tools & abi.TOOL_AFFINE_MV_ON_DEVICE) and not (tools & abi.TOOL_LFP_ON_DEVICE):
         tools &= ~abi.TOOL_AFFINE_MV_ON_DEVICE
+    # the picture partitioning, for a third of the pictures, from a generator of its own (the draws above stay what they were): the generator's layouts and explicit ones -
+    # random tile grids, raster-scan and rectangular slices, sub-pictures, virtual boundaries at legal spacing (synth.random_partition)
+    part = random.Random(seed ^ 0x70617274)
+    if part.random() < 1 / 3:
+        flags, pkw = synth.random_partition(part, W, H, l2, subpics_ok="wrap_offset" not in kw)
+        tools |= flags
+        kw.update(pkw)
     return dict(W=W, H=H, l2=l2, idx=idx, seed=seed, tools=tools, bd=bd, cf=cf, kw=kw, lists=lists)
 
 
@@ -107,8 +115,10 @@ def test_gpu_fuzz_slice(built):
         ncomp = 3 if c["cf"] else 1
         try:
             d = synth.picture_for_plan(pl, c["W"], c["H"], seed=c["seed"], tool_flags=c["tools"], log2_ctu=c["l2"], bit_depth=c["bd"], chroma_format=c["cf"], **c["kw"])
-        except Exception:
-            refused += 1            # (a parameter combination the generator does not make)
+        except Exception as e:
+            # (a parameter combination the generator does not make - but never a partitioning: synth.random_partition draws legal ones only)
+            assert "partitioning" not in str(e) and "virtual boundaries" not in str(e), "fuzz seed %d, case %d %r: %s" % (seed0, n, c, e)
+            refused += 1
             continue
         refs = {}
         for lst in pl.ref_slots:

@@ -1702,3 +1702,47 @@ def test_transform_block_items_say_what_the_kernel_must_know_of_the_cu(stub):
         stub.vvr_free_prepared(ctx.ctx, h)
         ctx.close()
     assert seen[1] and seen[2] and seen[4], seen        # (chroma blocks of ISP coding units, BDPCM blocks and LFNST blocks were among them)
+
+
+def test_partition_layouts_in_the_host_glue(stub):
+    """the layouts of tests/partition_cases.py - tiles of one CTU, a last tile column 8 samples wide, 20 tile columns, raster-scan slices from the middle of a tile
+    row, rectangular slices inside tiles, 256 slices - through vvr_prepare: the intra stage's units and blocks stay a valid order (no block reads one it does not
+    wait for, across tile and slice edges included), and a block never counts reference samples in another slice or tile as available"""
+    import partition_cases as pc
+    checked = 0
+    for case in pc.PARTITION_CASES:
+        if case.family == "virtual_boundaries":       # (nothing of the host tables depends on them)
+            continue
+        d, refs = case.make()
+        l2, S, cx, cy = pc.geometry(d)
+        ctx = Ctx(stub, int(d.hdr.width), int(d.hdr.height), 3, log2_ctu=l2)
+        hnd = ctx.prepare(d)
+        units, items = ctx.tables(hnd)
+        checked += _check_tables(d, units, items)
+        _check_resi_add(d, units, *ctx.resi_tables(hnd))
+        tile, slc = pc.ctu_maps(d)
+        it = items[(items["mode"] <= 69) & ((items["flags"] & 6) != 6)]           # intra predicted blocks (not the partitions of ISP CUs: their CU's line)
+        sh = (it["comp"] & 3 != 0).astype(int)
+        x, y = it["x"].astype(int) << sh, it["y"].astype(int) << sh
+        own = (tile[y >> l2, x >> l2], slc[y >> l2, x >> l2])
+        up, left = np.maximum(y - 1, 0) >> l2, np.maximum(x - 1, 0) >> l2
+        closed_above = (y > 0) & ((tile[up, x >> l2] != own[0]) | (slc[up, x >> l2] != own[1]))
+        closed_left = (x > 0) & ((tile[y >> l2, left] != own[0]) | (slc[y >> l2, left] != own[1]))
+        assert closed_above.any() and closed_left.any(), case.id
+        assert not it["nA"][closed_above].any() and not it["nL"][closed_left].any() and not (it["nTL"][closed_above | closed_left] & 1).any(), case.id
+        stub.vvr_free_prepared(ctx.ctx, hnd)
+        ctx.close()
+    assert checked > 0
+
+
+def test_more_than_256_slice_headers_are_refused(stub):
+    """vvr_prepare takes 1 .. 256 slice headers: 256 pass (tests/partition_cases.py: slices_256), 257 are refused"""
+    import partition_cases as pc
+    case = [c for c in pc.PARTITION_CASES if c.id == "slices_256_i"][0]
+    d, refs = case.make()
+    ctx = Ctx(stub, int(d.hdr.width), int(d.hdr.height), 3, log2_ctu=case.l2)
+    stub.vvr_free_prepared(ctx.ctx, ctx.prepare(d))
+    d.slices = np.concatenate([d.slices, d.slices[:1]])
+    assert len(d.slices) == 257
+    _expect_error(ctx, d, abi.VVR_ERR_PARAMETER, "slice headers: 1..256")
+    ctx.close()

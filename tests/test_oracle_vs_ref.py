@@ -264,7 +264,7 @@ SLICE_TILE_CASES = [
     (512, 384, 6, 0, 262, 0, dict(num_slices=3, p_cclm=0.3)),                                                    # slices, loop filters cross them
     (512, 384, 6, 2, 263, abi.TOOL_NO_LF_ACROSS_TILES, dict(tile_cols=2, tile_rows=2, p_intra=0.3, p_ciip=0.2, p_cclm=0.3)),
     (512, 384, 6, 2, 264, abi.TOOL_NO_LF_ACROSS_SLICES | abi.TOOL_NO_LF_ACROSS_TILES, dict(num_slices=3, tile_cols=2, tile_rows=2, p_intra=0.3, p_affine=0.2)),
-    (512, 384, 6, 3, 265, abi.TOOL_NO_LF_ACROSS_SLICES, dict(num_slices=3, tile_cols=2, tile_rows=2, p_intra=0.2)),   # raster slices over tiles: the ALF corner padding
+    (512, 384, 6, 3, 265, abi.TOOL_NO_LF_ACROSS_SLICES, dict(num_slices=3, tile_cols=2, tile_rows=2, p_intra=0.2)),   # raster slices over tiles, slice flag alone (no CTU of this layout gets the ALF corner padding: partition_cases.py, raster_slices_start_mid_row)
     (640, 256, 5, 0, 266, abi.TOOL_NO_LF_ACROSS_SLICES | abi.TOOL_NO_LF_ACROSS_TILES | abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE, dict(num_slices=4, tile_cols=3, tile_rows=2, p_cclm=0.4, p_coded_chroma=0.6)),
     (384, 256, 7, 2, 267, abi.TOOL_NO_LF_ACROSS_TILES | abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE, dict(tile_cols=3, tile_rows=1, p_intra=0.3, p_coded_chroma=0.6, p_cclm=0.3)),
     (512, 384, 6, 0, 268, abi.TOOL_NO_LF_ACROSS_SLICES | abi.TOOL_NO_LF_ACROSS_TILES, dict(num_slices=2, tile_cols=2, tile_rows=2, dual_tree=1.0, p_cclm=0.4)),

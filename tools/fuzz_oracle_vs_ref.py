@@ -2,7 +2,10 @@
 plain-C oracle with the reference decoder's own classes (oracle/_ref).  Usage: tools/fuzz_oracle_vs_ref.py <seed> <seconds> [far]   (far: motion vectors up to thousands of samples beyond the clip window in both directions, components at the ends of the 18-bit range, reference wrap-around in 6 pictures of 10; a quarter of the pictures have reference lists of 3 .. 16 entries).
 Round 1: 4 x 200 s = 33 800 pictures, no mismatch.  Round 4 (after the two wrap-around findings): 2 x 600 s `far` = 54 811 pictures and 600 s without = 26 173
 pictures, no mismatch (2 pictures refused by the reference: an 8-bit LMCS model of the generator that breaks the LmcsPivot constraint, Reshape.cpp:363).
-With the side tables drawn as well (lmcs_shape, chroma_qp_model, min_qp_ts): 150 s = 2 759 pictures and 150 s `far` = 2 436, no mismatch, none refused."""
+With the side tables drawn as well (lmcs_shape, chroma_qp_model, min_qp_ts): 150 s = 2 759 pictures and 150 s `far` = 2 436, no mismatch, none refused.
+With a picture partitioning drawn for a third of the pictures (synth.random_partition: tile grids, raster-scan and rectangular slices, sub-pictures, virtual
+boundaries): 150 s = 3 202 pictures and 150 s `far` = 3 110, no mismatch, 41 refused (40 by the reference: three old-style drawn boundaries at one CTU, "Too many
+virtual boundaries"; one LMCS model); with at most two old-style boundaries per direction 120 s = 2 337 and 120 s `far` = 2 391, no mismatch, none refused."""
 import sys, random, time
 import os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,6 +51,11 @@ def sweep(seed, seconds=None, cases=None):
       bd = rnd.choice([8, 10, 10]); cf = rnd.choice([1, 1, 1, 0])
       if not cf: tools &= ~abi.TOOL_LMCS_CSCALE
       if (tools & abi.TOOL_LMCS_CSCALE) and not (tools & abi.TOOL_LMCS): tools |= abi.TOOL_LMCS
+      # the picture partitioning, for a third of the pictures, from a generator of its own (the draws above stay what they were)
+      part = random.Random(seed ^ 0x70617274)
+      if part.random() < 1 / 3:
+          flags, pkw = synth.random_partition(part, W, H, l2, subpics_ok="wrap_offset" not in kw)
+          tools |= flags; kw.update(pkw)
       pl = plans[idx]
       if lists and pl.slice_type != abi.SLICE_I: pl = stream.with_longer_lists(pl, lists[0], lists[1], NSLOTS, random.Random(seed))
       try:

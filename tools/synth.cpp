@@ -33,6 +33,8 @@ struct Rng {   // splitmix64
 
 extern "C" {
 
+enum { VVS_MAX_TILE_COLS = 20, VVS_MAX_TILE_ROWS = 32 };      // MAX_TILE_COLS of the syntax; rows: what the test pictures need
+
 typedef struct vvs_params {
   uint64_t seed;
   uint16_t width, height;
@@ -93,7 +95,24 @@ typedef struct vvs_params {
   uint8_t  chroma_qp_flavour;   // with chroma_qp_model: 0 mapping tables of three kinds (the 4:2:0 default shape, a steep one, a plateau) and offsets that keep Cb, Cr and joint apart;
                                 // 1 tables of slope 16 and offsets of +-12: chroma QPs run into both clips from luma QPs in the middle; 2 tables lifted by 28 .. 36: high chroma QPs from low luma QPs
   uint32_t chroma_qp_model;     // 0: identity chroma QP mapping, zero offsets; else the seed of a model (vvs_chroma_qp, draws of a generator of its own) applied the way QpParam does (Quant.cpp:65-91)
+  // explicit picture partitioning (all empty: the layouts of tile_cols / tile_rows / num_slices / virtual_boundaries above).  A layout that no PPS / picture header can
+  // express is refused: vvs_generate returns VVS_ERR_LAYOUT / VVS_ERR_BOUNDARIES
+  uint8_t  tile_col_w[VVS_MAX_TILE_COLS + 1], tile_row_h[VVS_MAX_TILE_ROWS + 1];   // tile column widths / row heights in CTUs, zero-terminated; an empty one of the two: one column / row.
+                                // The sums are the picture's size in CTUs.  With subpics bit 0: one sub-picture per tile of this grid
+  uint8_t  slice_mode;          // with slice_map: VVS_SLICES_RASTER (pps_rect_slice_flag = 0: every slice a run of complete tiles in tile raster order) or VVS_SLICES_RECT (a rectangle of
+                                // complete tiles, or consecutive complete CTU rows of one tile), numbered by the tile of the slice's first CTU in tile raster order, inside a tile from
+                                // the top: the order of a PPS whose slices step through the tiles forwards (where the default step does not reach the next slice's tile - e.g. behind a
+                                // slice two tiles high in the first column - with a positive pps_tile_idx_delta)
+  const uint16_t* slice_map;    // [slice_map_len = number of CTUs]: slice index of every CTU in picture raster order (synth.py builds it from a short description); replaces num_slices
+  uint32_t slice_map_len;
+  uint16_t vb_x[4], vb_y[4];    // virtual boundary positions (luma samples), zero-terminated, at most three per direction; if either is given, `virtual_boundaries` is not looked at.
+                                // Multiples of 8 inside the picture, ascending, at least one CTU size apart (ph_virtual_boundary_pos_x/y_minus1 and the spacing rule of its semantics)
+  float    p_boundary_bt;       // of the square nodes (at most 64 x 64) that cross the right or the bottom picture boundary, not both: split in two in the crossing direction instead of in
+                                // four (both are legal implicit splits) - CUs of 8 x 16 and more in a last column 8 samples wide, where the quad split leaves 8 x 8 only.  0: quad, as before
 } vvs_params;
+
+enum { VVS_SLICES_RASTER = 1, VVS_SLICES_RECT = 2 };
+enum { VVS_ERR_LAYOUT = -3, VVS_ERR_BOUNDARIES = -4 };
 
 enum { VVS_LMCS_DRAWN = 0, VVS_LMCS_SINGLE_BIN_LOW, VVS_LMCS_SINGLE_BIN_HIGH, VVS_LMCS_LATE_EARLY, VVS_LMCS_SAWTOOTH, VVS_LMCS_CRS_LOW, VVS_LMCS_CRS_HIGH, VVS_LMCS_NEARLY_IDENTITY_FULL, VVS_LMCS_NUM_SHAPES };
 
@@ -178,6 +197,7 @@ struct Gen {
     return false;
   }
   std::vector<uint16_t> subpicOfCtu; std::vector<vvr_subpic> subpicV;
+  std::vector<int> explicitGrid[2];       // tile column widths / row heights of vvs_params::tile_col_w / tile_row_h
   bool lfMayCross( int a, int b ) const
   {
     if( ( P.tool_flags & VVR_TOOL_NO_LF_ACROSS_SLICES ) && sliceOfCtu[a] != sliceOfCtu[b] ) return false;
@@ -186,15 +206,99 @@ struct Gen {
     if( !subpicV.empty() && subpicOfCtu[a] != subpicOfCtu[b] && !( subpicV[subpicOfCtu[a]].lf_across && subpicV[subpicOfCtu[b]].lf_across ) ) return false;
     return true;
   }
-  void layoutSlicesAndTiles()
+  // the slice map of the caller: complete, and a layout a PPS can express (vvs_params::slice_mode)
+  bool sliceMapLegal( const std::vector<int>& colW, const std::vector<int>& rowH, int ns ) const
+  {
+    const int tc = (int) colW.size(), numTiles = tc * (int) rowH.size();
+    struct Box { int x0, y0, x1, y1, n, t0, t1, nt; };
+    std::vector<Box> box( ns, Box{ 1 << 30, 1 << 30, -1, -1, 0, 1 << 30, -1, 0 } );
+    std::vector<Box> tbox( numTiles, Box{ 1 << 30, 1 << 30, -1, -1, 0, 0, 0, 0 } );
+    std::vector<int> sliceOfTile( numTiles, -1 ); std::vector<char> tileSplit( numTiles, 0 );
+    for( int a = 0; a < ctusX * ctusY; a++ )
+    {
+      const int cx = a % ctusX, cy = a / ctusX, t = tileOfCtu[a], k = sliceOfCtu[a];
+      Box& b = box[k]; b.x0 = std::min( b.x0, cx ); b.y0 = std::min( b.y0, cy ); b.x1 = std::max( b.x1, cx ); b.y1 = std::max( b.y1, cy ); b.n++; b.t0 = std::min( b.t0, t ); b.t1 = std::max( b.t1, t );
+      Box& q = tbox[t]; q.x0 = std::min( q.x0, cx ); q.y0 = std::min( q.y0, cy ); q.x1 = std::max( q.x1, cx ); q.y1 = std::max( q.y1, cy ); q.n++;
+      if( sliceOfTile[t] < 0 ) sliceOfTile[t] = k; else if( sliceOfTile[t] != k ) tileSplit[t] = 1;
+    }
+    for( int k = 0; k < ns; k++ ) if( !box[k].n ) return false;                                   // every index up to the largest names a slice
+    if( P.slice_mode == VVS_SLICES_RASTER )
+    {
+      // runs of complete tiles in tile raster order, numbered along it
+      for( int t = 0; t < numTiles; t++ ) if( tileSplit[t] || sliceOfTile[t] != ( t ? sliceOfTile[t - 1] : 0 ) + ( t && sliceOfTile[t] != sliceOfTile[t - 1] ? 1 : 0 ) ) return false;
+      return true;
+    }
+    if( P.slice_mode != VVS_SLICES_RECT ) return false;
+    int prevKey = -1;
+    for( int k = 0; k < ns; k++ )
+    {
+      const Box& b = box[k];
+      if( b.n != ( b.x1 - b.x0 + 1 ) * ( b.y1 - b.y0 + 1 ) ) return false;                        // a rectangle of CTUs
+      if( b.t0 == b.t1 && tileSplit[b.t0] )
+      {
+        // part of one tile: complete CTU rows of it (consecutive, as the rectangle is filled)
+        if( b.x0 != tbox[b.t0].x0 || b.x1 != tbox[b.t0].x1 ) return false;
+      }
+      else
+      {
+        // complete tiles: the rectangle ends on tile edges, and no tile in it is shared with another slice
+        int area = 0;
+        for( int t = 0; t < numTiles; t++ ) if( sliceOfTile[t] == k ) { if( tileSplit[t] ) return false; area += tbox[t].n; }
+        if( area != b.n ) return false;
+      }
+      const int key = b.t0 * ( ctusY + 1 ) + ( b.y0 - tbox[b.t0].y0 );                            // t0: the tile of the first CTU (the rectangle's top-left one)
+      if( key <= prevKey ) return false;
+      prevKey = key;
+    }
+    return true;
+  }
+  bool layoutSlicesAndTiles()
   {
     ctusX = ( W + ctu - 1 ) / ctu; ctusY = ( H + ctu - 1 ) / ctu;
     const int n = ctusX * ctusY;
     sliceOfCtu.assign( n, 0 ); tileOfCtu.assign( n, 0 );
-    const int tc = std::max<int>( 1, std::min<int>( P.tile_cols, ctusX ) ), tr = std::max<int>( 1, std::min<int>( P.tile_rows, ctusY ) );
-    for( int cy = 0; cy < ctusY; cy++ ) for( int cx = 0; cx < ctusX; cx++ ) tileOfCtu[cy * ctusX + cx] = (uint16_t) ( ( cy * tr / ctusY ) * tc + cx * tc / ctusX );
-    const int numTiles = tc * tr, ns = std::max<int>( 1, P.num_slices );
-    if( ns > 1 )
+    int numTiles, ns = std::max<int>( 1, P.num_slices );
+    if( P.tile_col_w[0] || P.tile_row_h[0] )
+    {
+      // explicit grid
+      std::vector<int> colW, rowH;
+      for( int i = 0; i < VVS_MAX_TILE_COLS && P.tile_col_w[i]; i++ ) colW.push_back( P.tile_col_w[i] );
+      for( int i = 0; i < VVS_MAX_TILE_ROWS && P.tile_row_h[i]; i++ ) rowH.push_back( P.tile_row_h[i] );
+      if( P.tile_col_w[VVS_MAX_TILE_COLS] || P.tile_row_h[VVS_MAX_TILE_ROWS] ) return false;
+      if( colW.empty() ) colW.push_back( ctusX );
+      if( rowH.empty() ) rowH.push_back( ctusY );
+      int sx = 0, sy = 0; for( int w : colW ) sx += w; for( int h : rowH ) sy += h;
+      if( sx != ctusX || sy != ctusY ) return false;
+      std::vector<int> colOf, rowOf;
+      for( size_t i = 0; i < colW.size(); i++ ) colOf.insert( colOf.end(), colW[i], (int) i );
+      for( size_t i = 0; i < rowH.size(); i++ ) rowOf.insert( rowOf.end(), rowH[i], (int) i );
+      for( int cy = 0; cy < ctusY; cy++ ) for( int cx = 0; cx < ctusX; cx++ ) tileOfCtu[cy * ctusX + cx] = (uint16_t) ( rowOf[cy] * (int) colW.size() + colOf[cx] );
+      numTiles = (int) ( colW.size() * rowH.size() );
+      explicitGrid[0] = colW; explicitGrid[1] = rowH;
+    }
+    else
+    {
+      const int tc = std::max<int>( 1, std::min<int>( P.tile_cols, ctusX ) ), tr = std::max<int>( 1, std::min<int>( P.tile_rows, ctusY ) );
+      for( int cy = 0; cy < ctusY; cy++ ) for( int cx = 0; cx < ctusX; cx++ ) tileOfCtu[cy * ctusX + cx] = (uint16_t) ( ( cy * tr / ctusY ) * tc + cx * tc / ctusX );
+      numTiles = tc * tr;
+    }
+    if( P.slice_map )
+    {
+      // explicit slices
+      if( (int) P.slice_map_len != n ) return false;
+      ns = 0;
+      for( int a = 0; a < n; a++ ) { sliceOfCtu[a] = P.slice_map[a]; ns = std::max<int>( ns, P.slice_map[a] + 1 ); }
+      if( ns > n ) return false;
+      std::vector<int> colW, rowH;
+      if( !explicitGrid[0].empty() ) { colW = explicitGrid[0]; rowH = explicitGrid[1]; }
+      else
+      {
+        int run = 1; for( int x = 1; x <= ctusX; x++ ) { if( x == ctusX || tileOfCtu[x] != tileOfCtu[x - 1] ) { colW.push_back( run ); run = 1; } else run++; }
+        run = 1; for( int y = 1; y <= ctusY; y++ ) { if( y == ctusY || tileOfCtu[y * ctusX] != tileOfCtu[( y - 1 ) * ctusX] ) { rowH.push_back( run ); run = 1; } else run++; }
+      }
+      if( !sliceMapLegal( colW, rowH, ns ) ) return false;
+    }
+    else if( ns > 1 )
     {
       if( numTiles > 1 )
       {
@@ -233,6 +337,7 @@ struct Gen {
     }
     if( B.ctu_slice && ns > 1 && subpicV.empty() ) memcpy( B.ctu_slice, sliceOfCtu.data(), sizeof( uint16_t ) * n );
     if( B.ctu_tile && numTiles > 1 ) memcpy( B.ctu_tile, tileOfCtu.data(), sizeof( uint16_t ) * n );
+    return true;
   }
 
   // intra block copy: what the IBC virtual buffer of every CTU row holds (CodingStructure::fillIBCbuffer, CodingStructure.cpp:550): per
@@ -241,11 +346,12 @@ struct Gen {
   bool ibcOn = false;
   int ibcW4 = 0;
   std::vector<int32_t> vbL, vbC;
-  bool ibcCellsValid( const std::vector<int32_t>& vb, int rx, int ry, int w, int h, int ctuY0 ) const
+  // (curCtu: the CTU of the CU that copies.  The buffer is reset at the first CTU of every CTU row of a tile and of a slice: nothing of another tile or slice is in it)
+  bool ibcCellsValid( const std::vector<int32_t>& vb, int rx, int ry, int w, int h, int ctuY0, int curCtu ) const
   {
     if( rx < 0 || ry < ctuY0 || rx + w > W || ry + h > std::min( H, ctuY0 + ctu ) ) return false;
     for( int cy = ry >> 2; cy <= ( ry + h - 1 ) >> 2; cy++ ) for( int cx = rx >> 2; cx <= ( rx + w - 1 ) >> 2; cx++ )
-      if( vb[(size_t) cy * ibcW4 + ( cx % ibcW4 )] != cx ) return false;
+      if( vb[(size_t) cy * ibcW4 + ( cx % ibcW4 )] != cx || !sameSliceTile( ctuOfPos( cx << 2, cy << 2 ), curCtu ) ) return false;
     return true;
   }
   // a block vector whose reference block is completely valid in the virtual buffer (luma, and chroma at the halved vector for CUs
@@ -262,8 +368,8 @@ struct Gen {
       else { rx = x - (int) rng.u( std::min( x, 4 * ibcW4 - ctu ) + 1 ); ry = ctuY0 + (int) rng.u( ctu - h + 1 ); }   // anywhere in the buffer
       if( rng.p( 0.3 ) ) { rx &= ~3; ry &= ~3; }
       const int vx = rx - x, vy = ry - y;
-      if( !ibcCellsValid( vbL, rx, ry, w, h, ctuY0 ) ) continue;
-      if( withChroma && !ibcCellsValid( vbC, x + 2 * ( vx >> 1 ), y + 2 * ( vy >> 1 ), w, h, ctuY0 ) ) continue;
+      if( !ibcCellsValid( vbL, rx, ry, w, h, ctuY0, ctuOfPos( x, y ) ) ) continue;
+      if( withChroma && !ibcCellsValid( vbC, x + 2 * ( vx >> 1 ), y + 2 * ( vy >> 1 ), w, h, ctuY0, ctuOfPos( x, y ) ) ) continue;
       bvx = vx; bvy = vy;
       return true;
     }
@@ -767,7 +873,8 @@ struct Gen {
     {
       const int minS = std::max( 8, 1 << P.min_cu_log2 );       // (implicit splits at the picture boundary stop at 8x8: picture sizes are multiples of 8)
       // implicit boundary split: quad when possible, else binary in the crossing direction
-      if( w > minS && h > minS && ( ( crossX && crossY ) || w == h ) ) { const int hw = w >> 1, hh = h >> 1; split( x, y, hw, hh ); split( x + hw, y, hw, hh ); split( x, y + hh, hw, hh ); split( x + hw, y + hh, hw, hh ); }
+      const bool binary = P.p_boundary_bt > 0 && w == h && w <= 64 && crossX != crossY && rng.p( P.p_boundary_bt );
+      if( w > minS && h > minS && ( ( crossX && crossY ) || w == h ) && !binary ) { const int hw = w >> 1, hh = h >> 1; split( x, y, hw, hh ); split( x + hw, y, hw, hh ); split( x, y + hh, hw, hh ); split( x + hw, y + hh, hw, hh ); }
       else if( w <= 64 && h > 64 ) { split( x, y, w, h >> 1 ); split( x, y + ( h >> 1 ), w, h >> 1 ); }                 // (VPDU rule first)
       else if( w > 64 && h <= 64 ) { split( x, y, w >> 1, h ); split( x + ( w >> 1 ), y, w >> 1, h ); }
       else if( crossX && w > minS ) { split( x, y, w >> 1, h ); split( x + ( w >> 1 ), y, w >> 1, h ); }
@@ -1195,7 +1302,7 @@ struct Gen {
   int run()
   {
     W = P.width; H = P.height; w4 = ( W + 3 ) >> 2; h4 = ( H + 3 ) >> 2; ctu = 1 << P.log2_ctu; bd = P.bit_depth;
-    layoutSlicesAndTiles();
+    if( !layoutSlicesAndTiles() ) return VVS_ERR_LAYOUT;
     cuOf4.assign( (size_t) w4 * h4, -1 ); tuOf4.assign( (size_t) w4 * h4, -1 );
     B.num_cu = B.num_tu = 0; B.num_coef = 0; B.num_dmvr = 0;
     for( size_t i = 0; i < (size_t) w4 * h4; i++ ) { memset( &B.motion[i], 0, sizeof( vvr_motion ) ); B.motion[i].ref_idx[0] = B.motion[i].ref_idx[1] = -1; }
@@ -1205,7 +1312,22 @@ struct Gen {
     for( int l = 0; l < 2; l++ ) { h.num_ref[l] = P.slice_type == 2 ? 0 : P.num_ref[l]; for( int i = 0; i < VVR_MAX_REFS; i++ ) { h.ref_slot[l][i] = P.ref_slot[l][i]; h.ref_poc[l][i] = P.ref_poc[l][i]; } }
     for( int c = 0; c < 3; c++ ) { h.deblock_beta_offset_div2[c] = (int8_t) ( (int) rng.u( 5 ) - 2 ); h.deblock_tc_offset_div2[c] = (int8_t) ( (int) rng.u( 5 ) - 2 ); }
     h.wrap_offset = P.wrap_offset;
-    for( int d = 0; d < 2; d++ )
+    const bool vbExplicit = P.vb_x[0] || P.vb_y[0];
+    for( int d = 0; d < 2 && vbExplicit; d++ )
+    {
+      // the caller's positions: multiples of 8 inside the picture, ascending, at least one CTU size apart (the semantics of ph_virtual_boundary_pos_x/y_minus1)
+      const uint16_t* in = d ? P.vb_y : P.vb_x; uint16_t* pos = d ? h.vb_pos_y : h.vb_pos_x;
+      const int lim = d ? H : W;
+      if( in[3] ) return VVS_ERR_BOUNDARIES;
+      int got = 0;
+      for( ; got < 3 && in[got]; got++ )
+      {
+        if( ( in[got] & 7 ) || in[got] >= lim || ( got && (int) in[got] - (int) in[got - 1] < ctu ) ) return VVS_ERR_BOUNDARIES;
+        pos[got] = in[got];
+      }
+      if( d ) h.num_hor_vb = (uint8_t) got; else h.num_ver_vb = (uint8_t) got;
+    }
+    for( int d = 0; d < 2 && !vbExplicit; d++ )
     {
       // virtual boundaries: distinct multiples of 8 inside the picture, ascending (ph_virtual_boundary_pos_x/y_minus1)
       const int n = ( P.virtual_boundaries >> ( 2 * d ) ) & 3, lim = d ? H : W;
@@ -1245,7 +1367,7 @@ struct Gen {
     for( int y = 0; y < H; y += ctu ) for( int x = 0; x < W; x += ctu, a++ )
     {
       B.ctu_first_cu[a] = B.num_cu;
-      curI = P.slice_type == 2 || ( P.num_slices > 1 && ( ( P.intra_slices >> ( sliceOfCtu[a] & 7 ) ) & 1 ) );
+      curI = P.slice_type == 2 || ( ( P.num_slices > 1 || P.slice_map ) && ( ( P.intra_slices >> ( sliceOfCtu[a] & 7 ) ) & 1 ) );
       if( !dual ) { split( x, y, ctu, ctu ); continue; }
       // dual tree: the CTU is split down to 64x64 implicitly; every such node carries its luma tree, then its chroma tree.
       // Inside the picture the node is either not split or quad-split in both trees, which keeps CCLM legal (checkCCLMAllowed)

@@ -22,6 +22,11 @@ def build(force=False):
     return _LIB
 
 
+MAX_TILE_COLS, MAX_TILE_ROWS = 20, 32                  # VVS_MAX_TILE_COLS / _ROWS
+SLICES_RASTER, SLICES_RECT = 1, 2                      # Params.slice_mode
+ERRORS = {-3: "a partitioning no PPS can express (tile grid / slice map)", -4: "virtual boundaries the picture header cannot carry (multiples of 8 inside the picture, ascending, one CTU apart)"}
+
+
 class Params(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("width", C.c_uint16), ("height", C.c_uint16),
                 ("bit_depth", C.c_uint8), ("log2_ctu", C.c_uint8), ("chroma_format", C.c_uint8), ("slice_type", C.c_uint8),
@@ -36,7 +41,9 @@ class Params(C.Structure):
                 ("p_affine", C.c_float), ("p_geo", C.c_float), ("p_ciip", C.c_float), ("p_sbtmvp", C.c_float), ("p_bcw", C.c_float), ("p_cclm", C.c_float), ("p_mip", C.c_float), ("p_sbt", C.c_float), ("p_isp", C.c_float), ("dual_tree", C.c_float), ("p_ibc", C.c_float),
                 ("num_slices", C.c_uint8), ("tile_cols", C.c_uint8), ("tile_rows", C.c_uint8), ("wrap_offset", C.c_uint16), ("subpics", C.c_uint8), ("intra_slices", C.c_uint8), ("virtual_boundaries", C.c_uint8), ("scaled_refs", C.c_uint16 * 2), ("mv_window", C.c_uint16),
                 ("mv_window_ver", C.c_uint16), ("p_mv_limit", C.c_float),
-                ("lmcs_shape", C.c_uint8), ("min_qp_ts", C.c_uint8), ("chroma_qp_flavour", C.c_uint8), ("chroma_qp_model", C.c_uint32)]
+                ("lmcs_shape", C.c_uint8), ("min_qp_ts", C.c_uint8), ("chroma_qp_flavour", C.c_uint8), ("chroma_qp_model", C.c_uint32),
+                ("tile_col_w", C.c_uint8 * (MAX_TILE_COLS + 1)), ("tile_row_h", C.c_uint8 * (MAX_TILE_ROWS + 1)), ("slice_mode", C.c_uint8),
+                ("slice_map", C.c_void_p), ("slice_map_len", C.c_uint32), ("vb_x", C.c_uint16 * 4), ("vb_y", C.c_uint16 * 4), ("p_boundary_bt", C.c_float)]
 
 
 # Params.lmcs_shape: LMCS models at the ends of what lmcs_data() allows (tools/synth.cpp, genLmcs)
@@ -74,8 +81,54 @@ def default_params(**kw):
     p = Params()
     lib().vvs_default_params(C.byref(p))
     for k, v in kw.items():
-        setattr(p, k, v)
+        if k == "slice_map":      # (mode, per-CTU slice indices): raster_slices() / rect_slices(); the array lives as long as the parameters
+            p.slice_mode, p._slice_map = v[0], np.ascontiguousarray(v[1], np.uint16)
+            p.slice_map, p.slice_map_len = p._slice_map.ctypes.data, len(p._slice_map)
+        elif k in ("tile_col_w", "tile_row_h", "vb_x", "vb_y"):      # zero-terminated lists
+            a = getattr(p, k)
+            assert len(v) <= len(a), k                # (the generator refuses a list that fills the array: no terminator)
+            for i in range(len(a)):
+                a[i] = v[i] if i < len(v) else 0
+        else:
+            setattr(p, k, v)
     return p
+
+
+def tile_of_ctu(col_w, row_h):
+    """tile index of every CTU (picture raster order) of the grid with these column widths / row heights in CTUs -> array [sum(row_h), sum(col_w)]"""
+    col, row = np.repeat(np.arange(len(col_w)), col_w), np.repeat(np.arange(len(row_h)), row_h)
+    return (row[:, None] * len(col_w) + col[None, :]).astype(np.uint16)
+
+
+def raster_slices(col_w, row_h, runs):
+    """Params.slice_map of raster-scan slices over a tile grid: `runs` tiles each, in tile raster order"""
+    assert sum(runs) == len(col_w) * len(row_h) and min(runs) > 0
+    return SLICES_RASTER, np.repeat(np.arange(len(runs)), runs).astype(np.uint16)[tile_of_ctu(col_w, row_h)].reshape(-1)
+
+
+def rect_slices(col_w, row_h, tiles):
+    """Params.slice_map of rectangular slices over a tile grid.  `tiles` says per tile (raster order) what becomes of it: "whole" - a slice of its own (or the first tile
+    of a slice that later tiles join); a tuple of heights in CTU rows - cut into that many slices, top to bottom; ("join", k) - part of the slice tile k belongs to.
+    Slices are numbered in the order their first tile comes.  The generator checks that every slice is something a PPS can express; this only numbers them"""
+    t = tile_of_ctu(col_w, row_h)
+    m = np.zeros(t.shape, np.uint16)
+    first, n = {}, 0
+    assert len(tiles) == len(col_w) * len(row_h)
+    for k, what in enumerate(tiles):
+        ys, xs = np.nonzero(t == k)
+        if what == "whole":
+            first[k], n = n, n + 1
+            m[t == k] = first[k]
+        elif what[0] == "join":
+            first[k] = first[what[1]]
+            m[t == k] = first[k]
+        else:
+            assert sum(what) == ys.max() - ys.min() + 1, "bands of tile %d" % k
+            y = int(ys.min())
+            for hgt in what:
+                m[y:y + hgt, xs.min():xs.max() + 1] = n
+                y, n = y + hgt, n + 1
+    return SLICES_RECT, m.reshape(-1)
 
 
 def set_refs(p, l0, l1=()):
@@ -124,10 +177,10 @@ def generate(p, alloc=None):
     if p.tool_flags & abi.TOOL_SCALING_LIST:
         d.scaling = abi.ScalingList()
         b.scaling = C.addressof(d.scaling)
-    if p.num_slices > 1:
+    if p.num_slices > 1 or p.slice_map:
         d.ctu_slice = np.zeros(d.num_ctu, np.uint16)
         b.ctu_slice = d.ctu_slice.ctypes.data
-    if p.tile_cols > 1 or p.tile_rows > 1:
+    if p.tile_cols > 1 or p.tile_rows > 1 or p.tile_col_w[0] or p.tile_row_h[0]:
         d.ctu_tile = np.zeros(d.num_ctu, np.uint16)
         b.ctu_tile = d.ctu_tile.ctypes.data
     subpics = None
@@ -144,7 +197,7 @@ def generate(p, alloc=None):
         b.cqp = C.addressof(model)
     rc = L.vvs_generate(C.byref(p), C.byref(b))
     if rc != 0:
-        raise RuntimeError("vvs_generate failed (%d)" % rc)
+        raise RuntimeError("vvs_generate failed (%d)%s" % (rc, ": " + ERRORS[rc] if rc in ERRORS else ""))
     if model is not None:       # beside the description, not in it: the ABI carries TU QPs only
         model.cu_idx_array = cu_idx[:b.num_cu].copy()
         model.cu_idx = model.cu_idx_array.ctypes.data
@@ -402,3 +455,71 @@ def extreme_picture(width, height, seed, bit_depth=10, kind="checker"):
             bit = np.full((h, w), 1 if kind == "flat_max" else 0)
         out.append((bit * mx).astype(np.uint16))
     return out
+
+
+def random_partition(rnd, W, H, log2_ctu, subpics_ok=True):
+    """A random picture partitioning for the randomised test legs -> (tool flags to add, generator parameters).  `rnd`: a random.Random of the caller's, kept apart
+    from the one that draws the rest of the picture.  Half of the draws use the generator's own layouts (num_slices / tile_cols / tile_rows / virtual_boundaries /
+    subpics), half the explicit ones: a random tile grid (up to 20 columns), raster-scan slices of random runs or rectangular slices (a tile whole, cut into bands
+    of CTU rows, or joined with the tile to its left), virtual boundaries at random legal positions (multiples of 8, one CTU apart)"""
+    S = 1 << log2_ctu
+    cx, cy = (W + S - 1) >> log2_ctu, (H + S - 1) >> log2_ctu
+    tools = (abi.TOOL_NO_LF_ACROSS_SLICES if rnd.random() < 0.5 else 0) | (abi.TOOL_NO_LF_ACROSS_TILES if rnd.random() < 0.5 else 0)
+    kw = {}
+    if rnd.random() < 0.5:
+        if rnd.random() < 0.7:
+            kw["tile_cols"], kw["tile_rows"] = rnd.randrange(1, 4), rnd.randrange(1, 4)
+        if rnd.random() < 0.6:
+            kw["num_slices"] = rnd.randrange(2, 6)
+        if rnd.random() < 0.5:
+            # (at most two per direction: the drawn positions ignore the one-CTU spacing, and three that touch one CTU are more than the reference's filters take)
+            kw["virtual_boundaries"] = rnd.randrange(3) | (rnd.randrange(3) << 2) | (16 if rnd.random() < 0.5 else 0)
+        if subpics_ok and rnd.random() < 0.25 and kw.get("tile_cols", 1) * kw.get("tile_rows", 1) > 1:
+            kw["subpics"] = 1 | (rnd.randrange(3) << 1) | (rnd.randrange(3) << 3)
+        return tools, kw
+
+    def cut(n, most):
+        parts = []
+        while n:
+            parts.append(rnd.randrange(1, n + 1) if len(parts) + 1 < most else n)
+            if rnd.random() < 0.5:
+                parts[-1] = min(parts[-1], 1 + rnd.randrange(2))
+            n -= parts[-1]
+        return tuple(parts)
+    cols, rows = cut(cx, MAX_TILE_COLS), cut(cy, MAX_TILE_ROWS)
+    kw["tile_col_w"], kw["tile_row_h"] = cols, rows
+    nt = len(cols) * len(rows)
+    how = rnd.randrange(4)
+    if how == 0 and subpics_ok and 1 < nt <= 255:
+        kw["subpics"] = 1 | (rnd.randrange(3) << 1) | (rnd.randrange(3) << 3)
+    elif how == 1 and nt > 1:
+        runs = []
+        while sum(runs) < nt:
+            runs.append(rnd.randrange(1, min(nt - sum(runs), 2 * len(cols)) + 1))
+        if len(runs) > 1:
+            kw["slice_map"] = raster_slices(cols, rows, runs)
+    elif how == 2:
+        tiles = []
+        for k in range(nt):
+            hgt = rows[k // len(cols)]
+            r = rnd.random()
+            if r < 0.3 and k % len(cols) and (tiles[k - 1] == "whole" or tiles[k - 1][0] == "join"):       # (a run of tiles inside one tile row: a rectangle)
+                tiles.append(("join", k - 1))
+            elif r < 0.6 and hgt > 1:
+                bands = cut(hgt, hgt)
+                tiles.append(bands if len(bands) > 1 else "whole")
+            else:
+                tiles.append("whole")
+        mode, m = rect_slices(cols, rows, tiles)
+        if m.max() > 0:
+            kw["slice_map"] = (mode, m)
+    for name, lim in (("vb_x", W), ("vb_y", H)):
+        pos, v = [], 8 * rnd.randrange(1, max(2, lim // 8))
+        for _ in range(rnd.randrange(4)):
+            if v >= lim:
+                break
+            pos.append(v)
+            v += S + 8 * rnd.randrange(0, max(1, lim // 16))
+        if pos and rnd.random() < 0.6:
+            kw[name] = tuple(pos)
+    return tools, kw
