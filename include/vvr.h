@@ -560,6 +560,43 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *            "the bytes X stores": the definition of X above and below, with or without a transform - RGB8's od = 8 without one and od = bd,
  *            ( Ek + 128 ) / 257 with one included.  The refusals are those of the three planar formats, a missing plane or a stride below the
  *            row among the planes the format uses.
+ *            VVR_OUT_YUV444P8 / _YUV444P16 / _YUV422P8 / _YUV422P16 / _UYVY / _YUY2 / _Y210 / _V210 / _Y410: Y'CbCr with the chroma brought to
+ *            4:4:4 or 4:2:2 on the device, for playout and capture hardware (packed 4:2:2), an encoder of a 4:2:2 / 4:4:4 transcode, a model or
+ *            a filter that works in Y'CbCr on one grid.  The frame that is converted is the one every other format would store: the window,
+ *            grained, rescaled, in that order.  No colour description is needed; transform, 3-D LUT and normalisation are ignored.  Y is the
+ *            frame's luma unchanged.  With W = out_w (or w), H = out_h (or h):
+ *              YUV444P8   dst[0..2] = Y, Cb', Cr', each W x H   rows of W bytes        the sample, 8-bit contexts only (VVR_OUT_PLANAR8's refusal)
+ *              YUV444P16  the same                              rows of W * 2 bytes    the sample as a little-endian 16-bit word
+ *              YUV422P8   Y W x H; Cb', Cr' ( W >> 1 ) x H      rows of W, W >> 1      as YUV444P8
+ *              YUV422P16  the same                              W * 2, ( W >> 1 ) * 2  as YUV444P16
+ *              UYVY       dst[0] alone, rows of W * 2 bytes     bytes Cb, Y0, Cr, Y1 per pixel pair; 8-bit contexts only
+ *              YUY2       dst[0] alone, rows of W * 2 bytes     bytes Y0, Cb, Y1, Cr per pixel pair; 8-bit contexts only
+ *              Y210       dst[0] alone, rows of W * 4 bytes     little-endian words Y0, Cb, Y1, Cr, each sample << ( 16 - bit_depth ) (P010's rule)
+ *              V210       dst[0] alone, rows of ( ( W + 5 ) / 6 ) * 16 bytes: six pixels in four little-endian dwords.  With s' = sample <<
+ *                         ( 10 - bit_depth ) (VVR_OUT_PACKED10's widening) and Cbk, Crk the chroma of pixel pair k of the group:
+ *                           d0 = Cb0 | Y0 << 10 | Cr0 << 20      d1 = Y1 | Cb1 << 10 | Y2 << 20
+ *                           d2 = Cr1 | Y3 << 10 | Cb2 << 20      d3 = Y4 | Cr2 << 10 | Y5 << 20
+ *                         bits 30 and 31 are 0.  W is even: the last group of a row holds 2, 4 or 6 pixels; the fields of pixels that do not
+ *                         exist are 0 and the whole 16-byte group is stored.  The conventional padding of a line to 128 bytes is the caller's
+ *                         dst_stride_bytes[0]: the request only requires the stride to cover the row above.
+ *              Y410       dst[0] alone, rows of W * 4 bytes     the little-endian dword Cb' | Y << 10 | Cr' << 20 | 3 << 30 per pixel, 4:4:4,
+ *                         values sample << ( 10 - bit_depth )
+ *            For the one-plane formats dst[1], dst[2] and their strides are ignored and may be NULL / 0.  The chroma is the arithmetic of the
+ *            RGB formats, not a new one:
+ *              4:4:4 (YUV444P8, YUV444P16, Y410): Cb' and Cr' are exactly the "chroma to the luma grid" planes above - the same positions
+ *              16 * i - ( collocated ? 0 : 8 ) per direction, the same taps clamped to the chroma plane of the frame being converted, the
+ *              horizontal sums not normalised, the vertical pass over them, then ( sum + 2048 ) >> 12 clipped to [0, 2^bd - 1].  The matrix
+ *              of VVR_OUT_RGB16 applied to ( Y, Cb', Cr' ) gives the planes VVR_OUT_RGB16 stores.
+ *              4:2:2 (YUV422P8 ... V210): the same two passes with the horizontal position 32 * i - phase 0 at every i, tap set ( 0, 64, 0, 0 ),
+ *              so the horizontal sum is 64 times the sample - and the vertical pass as above with bit 1 of `collocated`.  That is
+ *              clip( ( c0 s0 + c1 s1 + c2 s2 + c3 s3 + 32 ) >> 6, 0, 2^bd - 1 ) with the four taps of the row's phase over the chroma rows
+ *              integer - 1 .. integer + 2 of the same column, clamped to the plane: what the kernel computes.  Bit 0 of `collocated` is
+ *              ignored: the horizontal chroma grid is the stream's.  With a collocated vertical position every second row is the source row.
+ *            Refused, each with its text, before a ring entry is taken: a 4:0:0 context (no chroma to upsample); an 8-bit format in a context
+ *            of more than 8 bits (bit-depth reduction of Y'CbCr is not offered); a bit depth outside 8..10; an odd out_w or out_h; a missing
+ *            plane or a stride below the row among the planes the format uses.
+ *            Not offered: semi-planar 4:2:2 / 4:4:4 (P210, NV16), AYUV / VUYA, Y216 / Y416; 10 -> 8 bit reduction of Y'CbCr; 4:0:0 with neutral
+ *            chroma; these formats from the synchronous vvr_read_output* calls; decoding 4:2:2 / 4:4:4 streams.
  *            Not offered: interleaved float32; 4:0:0 as grey; RGB from the synchronous vvr_read_output* calls; constant-luminance BT.2020,
  *            ICtCp, YCgCo, the identity matrix; a 3-D LUT for the synchronous calls.  Dynamic metadata: the per-frame measurements exist
  *            (vvr_stats_submit, vvr_light_level below); parsing ST 2094 / CLL SEIs, smoothing over time and scene logic do not.
@@ -588,7 +625,9 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *   failure; the ticket stays.  vvr_output_wait blocks for THIS request only and retires the ticket.  An unknown or retired ticket:
  *   VVR_ERR_PARAMETER.  vvr_sync also waits for the requests in flight but retires no ticket. */
 enum { VVR_OUT_PLANAR16 = 0, VVR_OUT_PLANAR8 = 1, VVR_OUT_PACKED10 = 2, VVR_OUT_NV12 = 16, VVR_OUT_P010 = 17, VVR_OUT_RGB8 = 32, VVR_OUT_RGB16 = 33, VVR_OUT_RGBF16 = 34,
-       VVR_OUT_RGBF32 = 36, VVR_OUT_RGBA8 = 48, VVR_OUT_BGRA8 = 49, VVR_OUT_RGB24 = 50, VVR_OUT_BGR24 = 51, VVR_OUT_RGB10A2 = 52, VVR_OUT_RGBA16F = 53 };
+       VVR_OUT_RGBF32 = 36, VVR_OUT_RGBA8 = 48, VVR_OUT_BGRA8 = 49, VVR_OUT_RGB24 = 50, VVR_OUT_BGR24 = 51, VVR_OUT_RGB10A2 = 52, VVR_OUT_RGBA16F = 53,
+       VVR_OUT_YUV444P8 = 64, VVR_OUT_YUV444P16 = 65, VVR_OUT_YUV422P8 = 66, VVR_OUT_YUV422P16 = 67, VVR_OUT_UYVY = 68, VVR_OUT_YUY2 = 69, VVR_OUT_Y210 = 70,
+       VVR_OUT_V210 = 71, VVR_OUT_Y410 = 72 };
 typedef struct vvr_output_request {
   uint32_t struct_size;        /* sizeof( vvr_output_request ) */
   int32_t  slot;
@@ -600,7 +639,7 @@ typedef struct vvr_output_request {
   uint8_t  format;             /* VVR_OUT_* */
   uint8_t  grain;              /* 1: the context's bank is added first, one frame of the seed chain (vvr_read_output_grain's rules) */
   uint8_t  blocking;           /* 0: VVR_NOT_READY instead of waiting on the host until `job` has been handed to the device */
-  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0; dst[2] unused by VVR_OUT_NV12 / VVR_OUT_P010; R, G, B for the planar VVR_OUT_RGB*; dst[0] alone for the interleaved ones */
+  void*    dst[3];             /* dst[1], dst[2] unused in 4:0:0; dst[2] unused by VVR_OUT_NV12 / VVR_OUT_P010; R, G, B for the planar VVR_OUT_RGB*; Y, Cb, Cr for VVR_OUT_YUV4*P*; dst[0] alone for the interleaved and the packed Y'CbCr ones */
   size_t   dst_stride_bytes[3];
 } vvr_output_request;
 /* the colour description the RGB formats convert with - context state, like the film grain bank; a new context has none.  matrix_coefficients

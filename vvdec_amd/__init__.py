@@ -507,7 +507,9 @@ class Reconstructor:
         (vvdecapp --pyuv: four samples in five bytes), "nv12" or "p010" (two planes: luma, interleaved CbCr; p010: sample << (16 - bit depth)),
         "rgb8", "rgb16" or "rgbf16" (three planes R, G, B at the luma size, converted on the device with the matrix of set_output_colour: vvr.h);
         "rgbf32" (the three planes as float32 with set_output_normalisation applied), "rgba8", "bgra8", "rgb24", "bgr24", "rgb10a2" or "rgba16f"
-        (one plane of interleaved pixels: abi.output_plane_shapes);
+        (one plane of interleaved pixels: abi.output_plane_shapes); "yuv444p8", "yuv444p16" (Y, Cb, Cr at the luma size), "yuv422p8", "yuv422p16"
+        (Y, and Cb, Cr of w >> 1 samples on every luma row), "uyvy", "yuy2", "y210", "v210" (packed 4:2:2, one plane) or "y410" (packed 4:4:4,
+        one plane): Y'CbCr with the chroma upsampled on the device by the filter of the RGB formats, no colour description needed (vvr.h);
         size, collocated, grain as read_output - and grain with size is the reference's chain,
         grain first, then the rescale of the grained frame.  pinned: the planes are allocated in memory of the context that the device writes
         directly (vvr_host_alloc) - they belong to the context and are views valid until close().
@@ -518,7 +520,9 @@ class Reconstructor:
         The planar RGB formats also take one 3-D tensor of shape (3, h, w) whose last dimension is contiguous (planes and rows may be padded or
         sliced) - float32 for "rgbf32"; the interleaved formats "rgba8", "bgra8", "rgb24", "bgr24" (uint8) and "rgba16f" (float16) one tensor of
         shape (h, w, C) with stride(2) == 1 and stride(1) == C at any row stride, "rgb10a2" one (h, w) tensor of int32; output_wait returns
-        that tensor.
+        that tensor.  "yuv444p8" / "yuv444p16" take a (3, h, w) tensor like planar RGB, "yuv422p8" / "yuv422p16" a list of three 2-D tensors, the
+        packed Y'CbCr formats one 2-D tensor of the plane's shape and element size (abi.output_plane_shapes; uint32 planes as int32), which
+        output_wait returns.
         Ask for a picture's output before the next picture into its slot is submitted: that picture then waits for the request on the device."""
         win = tuple(window or (0, 0, self.width, self.height))
         shapes, dt = abi.output_plane_shapes(win, fmt, size, 3 if self.chroma_format else 1)
@@ -534,9 +538,14 @@ class Reconstructor:
                     raise ValueError("output_submit: %s takes one tensor of shape %r" % (fmt, (h, n) if fmt == "rgb10a2" else (h, n // inter, inter)))
                 whole = into
                 planes = [into if into.dim() == 2 else into.as_strided((h, n), (into.stride(0), 1))]      # (the plane the request sees: rows of w * C elements)
+            elif fmt in abi.OUT_YUV_PACKED and hasattr(into, "dim"):      # one 2-D tensor: the packed plane
+                if into.dim() != 2 or min(into.stride()) < 0:
+                    raise ValueError("output_submit: %s takes one 2-D tensor of shape %r" % (fmt, tuple(shapes[0])))
+                whole = into
+                planes = [into]
             elif hasattr(into, "dim") and into.dim() == 3:      # (3, h, w): its planes, registered as one range
-                if len(shapes) != 3 or into.shape[0] != 3 or min(into.stride()) < 0:
-                    raise ValueError("output_submit: a 3-D tensor serves the planar RGB formats, as (3, h, w)")
+                if len(shapes) != 3 or len(set(shapes)) != 1 or into.shape[0] != 3 or min(into.stride()) < 0:
+                    raise ValueError("output_submit: a 3-D tensor serves the planar RGB formats and 4:4:4 Y'CbCr, as (3, h, w)")
                 whole = into
                 planes = list(into)
             else:
@@ -766,6 +775,6 @@ class Reconstructor:
         self._check(self.L.vvr_enable_stats(self.ctx, 1 if on else 0))
 
     def stats(self):
-        arr = (abi.KernelStat * 32)()
-        n = self._check(self.L.vvr_get_stats(self.ctx, arr, 32))
+        arr = (abi.KernelStat * 64)()
+        n = self._check(self.L.vvr_get_stats(self.ctx, arr, 64))
         return [dict(name=arr[i].name.decode(), launches=arr[i].launches, total_ms=arr[i].total_ms, algo_bytes=arr[i].algo_bytes) for i in range(n)]

@@ -162,9 +162,14 @@ def film_grain_bank(comp_present, shift, scale_lut, pattern_lut, pattern):
 
 OUT_PLANAR16, OUT_PLANAR8, OUT_PACKED10, OUT_NV12, OUT_P010, OUT_RGB8, OUT_RGB16, OUT_RGBF16 = 0, 1, 2, 16, 17, 32, 33, 34
 OUT_RGBF32, OUT_RGBA8, OUT_BGRA8, OUT_RGB24, OUT_BGR24, OUT_RGB10A2, OUT_RGBA16F = 36, 48, 49, 50, 51, 52, 53
+OUT_YUV444P8, OUT_YUV444P16, OUT_YUV422P8, OUT_YUV422P16, OUT_UYVY, OUT_YUY2, OUT_Y210, OUT_V210, OUT_Y410 = 64, 65, 66, 67, 68, 69, 70, 71, 72
 OUT_FORMATS = {"planar16": OUT_PLANAR16, "planar8": OUT_PLANAR8, "packed10": OUT_PACKED10, "nv12": OUT_NV12, "p010": OUT_P010,
                "rgb8": OUT_RGB8, "rgb16": OUT_RGB16, "rgbf16": OUT_RGBF16, "rgbf32": OUT_RGBF32, "rgba8": OUT_RGBA8, "bgra8": OUT_BGRA8,
-               "rgb24": OUT_RGB24, "bgr24": OUT_BGR24, "rgb10a2": OUT_RGB10A2, "rgba16f": OUT_RGBA16F}
+               "rgb24": OUT_RGB24, "bgr24": OUT_BGR24, "rgb10a2": OUT_RGB10A2, "rgba16f": OUT_RGBA16F,
+               "yuv444p8": OUT_YUV444P8, "yuv444p16": OUT_YUV444P16, "yuv422p8": OUT_YUV422P8, "yuv422p16": OUT_YUV422P16, "uyvy": OUT_UYVY, "yuy2": OUT_YUY2,
+               "y210": OUT_Y210, "v210": OUT_V210, "y410": OUT_Y410}
+# Y'CbCr at 4:4:4 / 4:2:2: the packed formats are one plane, elements of the plane's dtype per row as a function of the width
+OUT_YUV_PACKED = {"uyvy": lambda w: 2 * w, "yuy2": lambda w: 2 * w, "y210": lambda w: 2 * w, "v210": lambda w: (w + 5) // 6 * 4, "y410": lambda w: w}
 # the interleaved formats: elements of the plane's dtype per pixel (rgb10a2: one uint32)
 OUT_INTERLEAVED = {"rgba8": 4, "bgra8": 4, "rgb24": 3, "bgr24": 3, "rgba16f": 4, "rgb10a2": 1}
 
@@ -196,11 +201,19 @@ def output_plane_shapes(window, fmt, size, ncomp):
     """(rows, bytes or samples per row) of every plane a request produces, and the dtype: packed10 rows are w / 4 * 5 bytes; the semi-planar
     formats have two planes, luma and the interleaved CbCr rows of 2 * (w >> 1) samples (nv12: uint8, p010: uint16); the RGB formats three
     planes at the luma size (rgb8: uint8, rgb16: uint16, rgbf16: float16, rgbf32: float32); the interleaved formats one plane of (h, w * C)
-    uint8 (rgba8, bgra8: C = 4; rgb24, bgr24: C = 3) or float16 (rgba16f: C = 4), rgb10a2 one plane of (h, w) uint32"""
+    uint8 (rgba8, bgra8: C = 4; rgb24, bgr24: C = 3) or float16 (rgba16f: C = 4), rgb10a2 one plane of (h, w) uint32; Y'CbCr at 4:4:4 three planes
+    at the luma size (yuv444p8: uint8, yuv444p16: uint16), at 4:2:2 Y (h, w) and Cb, Cr (h, w >> 1) (yuv422p8, yuv422p16), or one packed plane:
+    uyvy, yuy2 (h, 2 w) uint8, y210 (h, 2 w) uint16, v210 (h, (w + 5) // 6 * 4) uint32 - six pixels in four dwords - and y410 (h, w) uint32"""
     import numpy as np
     w, h = size or (window[2], window[3])
     if fmt in ("rgb8", "rgb16", "rgbf16", "rgbf32"):
         return [(h, w)] * 3, {"rgb8": np.uint8, "rgb16": np.uint16, "rgbf16": np.float16, "rgbf32": np.float32}[fmt]
+    if fmt in ("yuv444p8", "yuv444p16"):
+        return [(h, w)] * 3, np.uint8 if fmt == "yuv444p8" else np.uint16
+    if fmt in ("yuv422p8", "yuv422p16"):
+        return [(h, w), (h, w >> 1), (h, w >> 1)], np.uint8 if fmt == "yuv422p8" else np.uint16
+    if fmt in OUT_YUV_PACKED:
+        return [(h, OUT_YUV_PACKED[fmt](w))], np.uint8 if fmt in ("uyvy", "yuy2") else np.uint16 if fmt == "y210" else np.uint32
     if fmt in OUT_INTERLEAVED:
         return [(h, w * OUT_INTERLEAVED[fmt])], np.uint32 if fmt == "rgb10a2" else np.float16 if fmt == "rgba16f" else np.uint8
     shapes = [(h >> (1 if c else 0), w >> (1 if c else 0)) for c in range(ncomp)]

@@ -287,6 +287,18 @@ struct OutputRgbParams
   const uint16_t* lut; int lutN, lutShift; uint32_t lutWiden;
 };
 void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
+// a frame of the output queue as Y'CbCr at 4:4:4 or 4:2:2 (VVR_OUT_YUV444P8 ... VVR_OUT_Y410, the definition: vvr.h): one 4:2:0 frame of w x h luma
+// samples (even), the luma as it is, the chroma brought to the luma grid as launch_output_rgb brings it there (4:4:4: bits 0 and 1 of collocated)
+// or to every luma row of its own columns (4:2:2: the vertical 4-tap alone, bit 1 of collocated).  Three planes or one leave, rows back to back,
+// into dst + dstOff[c] (256-byte aligned) or direct[c] (32-byte aligned memory of the caller's); nothing behind a plane's last row is written
+// (a V210 row is ( ( w + 5 ) / 6 ) * 16 bytes, stored whole).  shift: the widening of the sample - 16 - bd (Y210), 10 - bd (V210, Y410), else 0.
+struct OutputYuvParams
+{
+  const pel_t* src[3]; int stride[3], w, h; size_t dstOff[3];
+  uint8_t* direct[3];
+  int format, collocated, maxVal, shift;
+};
+void launch_output_yuv( hipStream_t s, const OutputYuvParams& p, void* dst );
 // light-level statistics of the output queue (vvr_stats_submit, the definition: vvr.h).  launch_output_stats: the window src / stride / w / h of p
 // (rgb != 0: the 4:2:0 frame with collocated and the matrix at od = bd, as launch_output_rgb takes it; else src[0] alone) accumulated into
 // `shards`: STATS_SHARDS copies of STATS_WORDS words, all zero before the launch - hist_y[1024], hist_maxrgb[1024], max_c[3], then maxVal - min_c[3]

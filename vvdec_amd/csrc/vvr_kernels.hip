@@ -5584,6 +5584,325 @@ void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst )
   }
 }
 
+// k_output_yuv — a 4:2:0 frame of the output queue as Y'CbCr at 4:4:4 or 4:2:2 (VVR_OUT_YUV444P8 ... VVR_OUT_Y410, the definition: vvr.h): the luma as
+// it is, the chroma upsampled with the 4-tap DCTIF of k_output_rgb, the store of the format - one launch, every source sample read from HBM once,
+// nothing written but the result.  Three classes, each with its own tile in LDS (k_output_rgb itself is not touched: the staging and the vertical
+// taps are restated in helpers of this kernel):
+//   4:4:4 (YUV444P8, YUV444P16, Y410)  k_output_rgb's tile and passes up to the matrix: 64 x 32 samples, the 20 x 36 chroma samples of both planes
+//          staged, their horizontal sums as int32 (13 760 bytes of LDS, as k_output_rgb), a lane 8 samples of a row; the four chroma positions.
+//   4:2:2 (YUV422P8, YUV422P16, UYVY, YUY2, Y210)  no horizontal pass and no int32 sums: the tile's 32 chroma columns x 20 rows of both planes are
+//          staged as they are (2560 bytes; rows of 64 bytes, a lane reads its 4 samples of a row as one ds_read_b64 - the 32 lanes of a half-wavefront
+//          read at most three consecutive rows, 192 bytes: no bank is met twice), the vertical taps run over them as ( sum + 32 ) >> 6; the two
+//          vertical chroma positions.
+//   V210   six pixels are one 16-byte group: a lane owns one group of each of two rows (jj and jj + 16), the tile is 96 x 32.  The 48 chroma
+//          columns x 20 rows are staged three samples to an 8-byte cell (5120 bytes; rows of 128 bytes, a group's three samples one aligned
+//          ds_read_b64, two rows per half-wavefront: 256 bytes, no bank met twice).  The last group of a row holds 2, 4 or 6 pixels; the
+//          fields of the others are 0 and the group is stored whole - always one aligned 16-byte store, so the class has one kind of store.
+// The stores of the other formats are whole when the width is a multiple of 8 - every lane has 8 samples and its address is aligned: 8 or 16
+// bytes per plane (planar luma, 4:4:4 chroma), 4 or 8 (4:2:2 chroma), 16 (UYVY, YUY2), 2 x 16 (Y210, Y410) - and go pixel pair by pixel pair
+// otherwise (the width is even).  rgb_store / rgb_store_px of k_output_rgb serve the planar and the Y410 stores as they are.
+__host__ __device__ constexpr bool yuv_is_444( int f ) { return f == VVR_OUT_YUV444P8 || f == VVR_OUT_YUV444P16 || f == VVR_OUT_Y410; }
+// the lane's n = 2, 4, 6 or 8 luma samples at a 2-byte aligned address
+__device__ __forceinline__ uint4 yuv_luma8( const pel_t* __restrict__ row, int n )
+{
+  uint4 yy = make_uint4( 0, 0, 0, 0 );
+  if( n == 8 ) __builtin_memcpy( &yy, row, 16 );      // (one 16-byte load: unaligned access mode)
+  else
+  {
+    yy.x = *(const rgb_uint_u*) row;
+    if( n > 2 ) yy.y = *(const rgb_uint_u*) ( row + 2 );
+    if( n > 4 ) yy.z = *(const rgb_uint_u*) ( row + 4 );
+  }
+  return yy;
+}
+// row jj of a tile whose staged chroma rows begin two rows above the tile's first: the first of the four staged rows and the taps of the row's phase
+template<bool COLY>
+__device__ __forceinline__ int yuv_vtaps( int jj, int ( &c )[4] )
+{
+  const bool odd = jj & 1;
+  c[0] = COLY ? ( odd ? -4 : 0 ) : ( odd ? -4 : -2 ); c[1] = COLY ? ( odd ? 36 : 64 ) : ( odd ? 54 : 16 );
+  c[2] = COLY ? ( odd ? 36 : 0 ) : ( odd ? 16 : 54 ); c[3] = COLY ? ( odd ? -4 : 0 ) : ( odd ? -2 : -4 );
+  return ( jj >> 1 ) + ( COLY || odd ? 1 : 0 );
+}
+template<int COL, int FMT, bool WHOLE>
+__device__ __forceinline__ void yuv_tile_444( const OutputYuvParams& p, uint8_t* __restrict__ dst )
+{
+  __shared__ uint16_t yuv_raw[2][RGB_CH][RGB_CW];
+  __shared__ __attribute__(( aligned( 16 ) )) int yuv_sum[2][RGB_CH][RGB_SW];
+  constexpr bool COLX = ( COL & 1 ) != 0, COLY = ( COL & 2 ) != 0;
+  const int tid = threadIdx.x, X0 = blockIdx.x * RGB_TW, Y0 = blockIdx.y * RGB_TH;
+  const int jj = tid >> 3, xl = ( tid & 7 ) * 8, x = X0 + xl, y = Y0 + jj, n = WHOLE ? 8 : min( 8, p.w - x );
+  const bool live = x < p.w && y < p.h;
+  uint4 yy = make_uint4( 0, 0, 0, 0 );
+  if( live ) yy = yuv_luma8( p.src[0] + (size_t) y * p.stride[0] + x, n );
+  // chroma columns cx0 .. cx0 + 35 and rows cy0 .. cy0 + 19 of both planes, clamped to the frame
+  const int cw = p.w >> 1, ch = p.h >> 1, cx0 = ( X0 >> 1 ) - 2, cy0 = ( Y0 >> 1 ) - 2;
+  constexpr int STAGED = 2 * RGB_CH * RGB_CW, PER_LANE = ( STAGED + 255 ) / 256;
+  uint16_t staged[PER_LANE];
+#pragma unroll
+  for( int i = 0; i < PER_LANE; i++ )      // (all loads in flight before the first LDS store)
+  {
+    const int t = min( tid + 256 * i, STAGED - 1 ), pl = t / ( RGB_CH * RGB_CW ), rem = t - pl * ( RGB_CH * RGB_CW ), r = rem / RGB_CW, cc = rem - r * RGB_CW;
+    const pel_t* __restrict__ s = pl ? p.src[2] : p.src[1];
+    staged[i] = (uint16_t) s[(size_t) clip3( 0, ch - 1, cy0 + r ) * ( pl ? p.stride[2] : p.stride[1] ) + clip3( 0, cw - 1, cx0 + cc )];
+  }
+#pragma unroll
+  for( int i = 0; i < PER_LANE; i++ ) if( tid + 256 * i < STAGED ) ( &yuv_raw[0][0][0] )[tid + 256 * i] = staged[i];
+  __syncthreads();
+  // horizontal pass: output columns 2 k (phase 0 or 24) and 2 k + 1 (phase 16 or 8) of a staged row; c[2] is the chroma sample at column k of the tile
+  for( int u = tid; u < 2 * RGB_CH * ( RGB_TW / 2 ); u += 256 )
+  {
+    const int k = u & ( RGB_TW / 2 - 1 ), rr = u / ( RGB_TW / 2 ), pl = rr / RGB_CH, r = rr - pl * RGB_CH;
+    const uint16_t* c = &yuv_raw[pl][r][k];
+    int ev, od;
+    if( COLX ) { ev = 64 * c[2];                                  od = -4 * c[1] + 36 * c[2] + 36 * c[3] - 4 * c[4]; }
+    else       { ev = -2 * c[0] + 16 * c[1] + 54 * c[2] - 4 * c[3]; od = -4 * c[1] + 54 * c[2] + 16 * c[3] - 2 * c[4]; }
+    *(int2*) &yuv_sum[pl][r][2 * k] = make_int2( ev, od );
+  }
+  __syncthreads();
+  if( !live ) return;
+  int c[4];
+  const int f = yuv_vtaps<COLY>( jj, c );
+  int Y[8], UV[2][8];
+#pragma unroll
+  for( int pl = 0; pl < 2; pl++ )
+  {
+    int4 a[4][2];
+#pragma unroll
+    for( int t = 0; t < 4; t++ ) { a[t][0] = *(const int4*) &yuv_sum[pl][f + t][xl]; a[t][1] = *(const int4*) &yuv_sum[pl][f + t][xl + 4]; }
+#pragma unroll
+    for( int hlf = 0; hlf < 2; hlf++ )
+    {
+      UV[pl][4 * hlf + 0] = c[0] * a[0][hlf].x + c[1] * a[1][hlf].x + c[2] * a[2][hlf].x + c[3] * a[3][hlf].x;
+      UV[pl][4 * hlf + 1] = c[0] * a[0][hlf].y + c[1] * a[1][hlf].y + c[2] * a[2][hlf].y + c[3] * a[3][hlf].y;
+      UV[pl][4 * hlf + 2] = c[0] * a[0][hlf].z + c[1] * a[1][hlf].z + c[2] * a[2][hlf].z + c[3] * a[3][hlf].z;
+      UV[pl][4 * hlf + 3] = c[0] * a[0][hlf].w + c[1] * a[1][hlf].w + c[2] * a[2][hlf].w + c[3] * a[3][hlf].w;
+    }
+  }
+#pragma unroll
+  for( int i = 0; i < 8; i++ )
+  {
+    const uint32_t y2 = i < 2 ? yy.x : ( i < 4 ? yy.y : ( i < 6 ? yy.z : yy.w ) );
+    Y[i] = (int) ( ( y2 >> ( 16 * ( i & 1 ) ) ) & 0xffff ) << p.shift;
+    UV[0][i] = clip3( 0, p.maxVal, ( UV[0][i] + 2048 ) >> 12 ) << p.shift; UV[1][i] = clip3( 0, p.maxVal, ( UV[1][i] + 2048 ) >> 12 ) << p.shift;
+  }
+  const size_t i0 = (size_t) y * p.w + x;
+  uint8_t* __restrict__ o0 = p.direct[0] ? p.direct[0] : dst + p.dstOff[0];
+  if( FMT == VVR_OUT_Y410 ) { rgb_store_px<VVR_OUT_RGB10A2, WHOLE>( o0, i0, UV[0], Y, UV[1], 0.f, n ); return; }      // (Cb | Y << 10 | Cr << 20 | 3 << 30)
+  constexpr int ST = FMT == VVR_OUT_YUV444P8 ? VVR_OUT_RGB8 : VVR_OUT_RGB16;
+  rgb_store<ST, WHOLE>( o0, i0, Y, 0.f, n );
+  rgb_store<ST, WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, UV[0], 0.f, n );
+  rgb_store<ST, WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, UV[1], 0.f, n );
+}
+// 4:2:2 chroma: rows cy0 .. cy0 + 19 (clamped to the plane) of CW columns from column cx0 of both planes into LDS, CELL samples to a cell of
+// ROW / ( CW / CELL ) samples (V210: three samples in a cell of four)
+template<int CW, int CELL, int PITCH>
+__device__ __forceinline__ void yuv_stage_422( const OutputYuvParams& p, int cx0, int cy0, uint16_t* __restrict__ raw )
+{
+  const int tid = threadIdx.x, cw = p.w >> 1, ch = p.h >> 1;
+  constexpr int STAGED = 2 * RGB_CH * CW, PER_LANE = ( STAGED + 255 ) / 256, ROW = CW / CELL * PITCH;
+  uint16_t staged[PER_LANE];
+#pragma unroll
+  for( int i = 0; i < PER_LANE; i++ )      // (all loads in flight before the first LDS store)
+  {
+    const int t = min( tid + 256 * i, STAGED - 1 ), pl = t / ( RGB_CH * CW ), rem = t - pl * ( RGB_CH * CW ), r = rem / CW, cc = rem - r * CW;
+    const pel_t* __restrict__ s = pl ? p.src[2] : p.src[1];
+    staged[i] = (uint16_t) s[(size_t) clip3( 0, ch - 1, cy0 + r ) * ( pl ? p.stride[2] : p.stride[1] ) + min( cw - 1, cx0 + cc )];
+  }
+#pragma unroll
+  for( int i = 0; i < PER_LANE; i++ )
+  {
+    const int t = tid + 256 * i, rr = t / CW, cc = t - rr * CW;
+    if( t < STAGED ) raw[rr * ROW + cc / CELL * PITCH + cc % CELL] = staged[i];
+  }
+}
+// the vertical taps over four cells of up to four samples, one above the other ROW samples apart: ( sum + 32 ) >> 6, clipped, widened
+template<int ROW>
+__device__ __forceinline__ void yuv_vertical_422( const uint16_t* __restrict__ cell, const int ( &c )[4], int maxVal, int shift, int ( &out )[4] )
+{
+  uint2 a[4];
+#pragma unroll
+  for( int t = 0; t < 4; t++ ) a[t] = *(const uint2*) ( cell + t * ROW );
+#pragma unroll
+  for( int i = 0; i < 4; i++ )
+  {
+    int sum = 32;
+#pragma unroll
+    for( int t = 0; t < 4; t++ ) sum += c[t] * (int) ( ( ( i < 2 ? a[t].x : a[t].y ) >> ( 16 * ( i & 1 ) ) ) & 0xffff );
+    out[i] = clip3( 0, maxVal, sum >> 6 ) << shift;
+  }
+}
+template<bool COLY, int FMT, bool WHOLE>
+__device__ __forceinline__ void yuv_tile_422( const OutputYuvParams& p, uint8_t* __restrict__ dst )
+{
+  constexpr int CW = RGB_TW / 2;
+  __shared__ __attribute__(( aligned( 8 ) )) uint16_t yuv_raw[2][RGB_CH][CW];
+  const int tid = threadIdx.x, X0 = blockIdx.x * RGB_TW, Y0 = blockIdx.y * RGB_TH;
+  const int jj = tid >> 3, xl = ( tid & 7 ) * 8, x = X0 + xl, y = Y0 + jj, n = WHOLE ? 8 : min( 8, p.w - x );
+  const bool live = x < p.w && y < p.h;
+  uint4 yy = make_uint4( 0, 0, 0, 0 );
+  if( live ) yy = yuv_luma8( p.src[0] + (size_t) y * p.stride[0] + x, n );
+  yuv_stage_422<CW, 4, 4>( p, X0 >> 1, ( Y0 >> 1 ) - 2, &yuv_raw[0][0][0] );
+  __syncthreads();
+  if( !live ) return;
+  int c[4], Y[8], U[4], V[4];
+  const int f = yuv_vtaps<COLY>( jj, c );
+  yuv_vertical_422<CW>( &yuv_raw[0][f][xl >> 1], c, p.maxVal, p.shift, U );
+  yuv_vertical_422<CW>( &yuv_raw[1][f][xl >> 1], c, p.maxVal, p.shift, V );
+#pragma unroll
+  for( int i = 0; i < 8; i++ )
+  {
+    const uint32_t y2 = i < 2 ? yy.x : ( i < 4 ? yy.y : ( i < 6 ? yy.z : yy.w ) );
+    Y[i] = (int) ( ( y2 >> ( 16 * ( i & 1 ) ) ) & 0xffff ) << p.shift;
+  }
+  const size_t i0 = (size_t) y * p.w + x;
+  uint8_t* __restrict__ o0 = p.direct[0] ? p.direct[0] : dst + p.dstOff[0];
+  if( FMT == VVR_OUT_YUV422P8 || FMT == VVR_OUT_YUV422P16 )
+  {
+    rgb_store<FMT == VVR_OUT_YUV422P8 ? VVR_OUT_RGB8 : VVR_OUT_RGB16, WHOLE>( o0, i0, Y, 0.f, n );
+    const size_t ci = ( (size_t) y * p.w + x ) >> 1;      // (w and x are even)
+#pragma unroll
+    for( int pl = 0; pl < 2; pl++ )
+    {
+      const int ( &C )[4] = pl ? V : U;
+      uint8_t* __restrict__ o = p.direct[1 + pl] ? p.direct[1 + pl] : dst + p.dstOff[1 + pl];
+      if( FMT == VVR_OUT_YUV422P8 )
+      {
+        if( WHOLE ) *(uint32_t*) ( o + ci ) = (uint32_t) C[0] | (uint32_t) C[1] << 8 | (uint32_t) C[2] << 16 | (uint32_t) C[3] << 24;
+        else
+        {
+#pragma unroll
+          for( int k = 0; k < 4; k++ ) if( 2 * k < n ) o[ci + k] = (uint8_t) C[k];
+        }
+      }
+      else
+      {
+        if( WHOLE ) *(uint2*) ( o + 2 * ci ) = make_uint2( (uint32_t) C[0] | (uint32_t) C[1] << 16, (uint32_t) C[2] | (uint32_t) C[3] << 16 );
+        else
+        {
+#pragma unroll
+          for( int k = 0; k < 4; k++ ) if( 2 * k < n ) ( (uint16_t*) o )[ci + k] = (uint16_t) C[k];
+        }
+      }
+    }
+    return;
+  }
+  if( FMT == VVR_OUT_Y210 )      // a pixel pair: the words Y0, Cb, Y1, Cr
+  {
+    uint2 d[4];
+#pragma unroll
+    for( int k = 0; k < 4; k++ ) d[k] = make_uint2( (uint32_t) Y[2 * k] | (uint32_t) U[k] << 16, (uint32_t) Y[2 * k + 1] | (uint32_t) V[k] << 16 );
+    uint2* o = (uint2*) ( o0 + i0 * 4 );
+    if( WHOLE ) { *(uint4*) o = make_uint4( d[0].x, d[0].y, d[1].x, d[1].y ); *(uint4*) ( o + 2 ) = make_uint4( d[2].x, d[2].y, d[3].x, d[3].y ); }
+    else
+    {
+      o[0] = d[0];
+      if( n > 2 ) o[1] = d[1];
+      if( n > 4 ) o[2] = d[2];
+      if( n > 6 ) o[3] = d[3];
+    }
+    return;
+  }
+  uint32_t d[4];      // UYVY: the bytes Cb, Y0, Cr, Y1; YUY2: Y0, Cb, Y1, Cr
+#pragma unroll
+  for( int k = 0; k < 4; k++ )
+    d[k] = FMT == VVR_OUT_UYVY ? (uint32_t) U[k] | (uint32_t) Y[2 * k] << 8 | (uint32_t) V[k] << 16 | (uint32_t) Y[2 * k + 1] << 24
+                               : (uint32_t) Y[2 * k] | (uint32_t) U[k] << 8 | (uint32_t) Y[2 * k + 1] << 16 | (uint32_t) V[k] << 24;
+  uint32_t* o = (uint32_t*) ( o0 + i0 * 2 );
+  if( WHOLE ) *(uint4*) o = make_uint4( d[0], d[1], d[2], d[3] );
+  else
+  {
+    o[0] = d[0];
+    if( n > 2 ) o[1] = d[1];
+    if( n > 4 ) o[2] = d[2];
+    if( n > 6 ) o[3] = d[3];
+  }
+}
+#define YUV_V210_TW 96
+template<bool COLY>
+__device__ __forceinline__ void yuv_tile_v210( const OutputYuvParams& p, uint8_t* __restrict__ dst )
+{
+  constexpr int CW = YUV_V210_TW / 2, ROW = CW / 3 * 4;
+  __shared__ __attribute__(( aligned( 8 ) )) uint16_t yuv_raw[2][RGB_CH][ROW];
+  const int tid = threadIdx.x, X0 = blockIdx.x * YUV_V210_TW, Y0 = blockIdx.y * RGB_TH;
+  const int g = tid & 15, x = X0 + 6 * g, n = min( 6, p.w - x );      // (n: 2, 4 or 6 in a lane that has a group)
+  uint32_t yy[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } };
+#pragma unroll
+  for( int it = 0; it < 2; it++ )
+  {
+    const int y = Y0 + ( tid >> 4 ) + 16 * it;
+    if( x < p.w && y < p.h )
+    {
+      const pel_t* __restrict__ row = p.src[0] + (size_t) y * p.stride[0] + x;
+      yy[it][0] = *(const rgb_uint_u*) row;
+      if( n > 2 ) yy[it][1] = *(const rgb_uint_u*) ( row + 2 );
+      if( n > 4 ) yy[it][2] = *(const rgb_uint_u*) ( row + 4 );
+    }
+  }
+  yuv_stage_422<CW, 3, 4>( p, X0 >> 1, ( Y0 >> 1 ) - 2, &yuv_raw[0][0][0] );
+  __syncthreads();
+  uint8_t* __restrict__ out = p.direct[0] ? p.direct[0] : dst + p.dstOff[0];
+  const size_t rowBytes = (size_t) ( ( p.w + 5 ) / 6 ) * 16;
+#pragma unroll
+  for( int it = 0; it < 2; it++ )
+  {
+    const int jj = ( tid >> 4 ) + 16 * it, y = Y0 + jj;
+    if( x >= p.w || y >= p.h ) continue;
+    int c[4], U[4], V[4];
+    const int f = yuv_vtaps<COLY>( jj, c );
+    yuv_vertical_422<ROW>( &yuv_raw[0][f][4 * g], c, p.maxVal, p.shift, U );
+    yuv_vertical_422<ROW>( &yuv_raw[1][f][4 * g], c, p.maxVal, p.shift, V );
+    if( n < 6 ) { U[2] = 0; V[2] = 0; }
+    if( n < 4 ) { U[1] = 0; V[1] = 0; }
+    const uint32_t s = p.shift, y0 = ( yy[it][0] & 0xffff ) << s, y1 = ( yy[it][0] >> 16 ) << s, y2 = ( yy[it][1] & 0xffff ) << s, y3 = ( yy[it][1] >> 16 ) << s;
+    const uint32_t y4 = ( yy[it][2] & 0xffff ) << s, y5 = ( yy[it][2] >> 16 ) << s;
+    *(uint4*) ( out + (size_t) y * rowBytes + (size_t) ( blockIdx.x * ( YUV_V210_TW / 6 ) + g ) * 16 ) =
+      make_uint4( (uint32_t) U[0] | y0 << 10 | (uint32_t) V[0] << 20, y1 | (uint32_t) U[1] << 10 | y2 << 20, (uint32_t) V[1] | y3 << 10 | (uint32_t) U[2] << 20, y4 | (uint32_t) V[2] << 10 | y5 << 20 );
+  }
+}
+// COL: the chroma position (4:2:2 and V210: bit 1 alone, instantiated with bit 0 clear); WHOLE: the kind of store (V210: true)
+template<int COL, int FMT, bool WHOLE>
+__global__ __launch_bounds__( 256 ) void k_output_yuv( OutputYuvParams p, uint8_t* __restrict__ dst )
+{
+  if constexpr( yuv_is_444( FMT ) ) yuv_tile_444<COL, FMT, WHOLE>( p, dst );
+  else if constexpr( FMT == VVR_OUT_V210 ) yuv_tile_v210<( COL & 2 ) != 0>( p, dst );
+  else yuv_tile_422<( COL & 2 ) != 0, FMT, WHOLE>( p, dst );
+}
+template<int FMT, bool WHOLE>
+static void launch_output_yuv_as( hipStream_t s, const OutputYuvParams& p, void* dst )
+{
+  const dim3 grid( ( p.w + ( FMT == VVR_OUT_V210 ? YUV_V210_TW : RGB_TW ) - 1 ) / ( FMT == VVR_OUT_V210 ? YUV_V210_TW : RGB_TW ), ( p.h + RGB_TH - 1 ) / RGB_TH );
+  switch( p.collocated & ( yuv_is_444( FMT ) ? 3 : 2 ) )
+  {
+  case 0:  hipLaunchKernelGGL( ( k_output_yuv<0, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 2:  hipLaunchKernelGGL( ( k_output_yuv<2, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 1:  if constexpr( yuv_is_444( FMT ) ) hipLaunchKernelGGL( ( k_output_yuv<1, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  default: if constexpr( yuv_is_444( FMT ) ) hipLaunchKernelGGL( ( k_output_yuv<3, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  }
+}
+template<int FMT>
+static void launch_output_yuv_fmt( hipStream_t s, const OutputYuvParams& p, void* dst )
+{
+  if( FMT == VVR_OUT_V210 || ( p.w & 7 ) == 0 ) launch_output_yuv_as<FMT, true>( s, p, dst );      // (rows of a multiple of 8 samples: every lane has 8, at an aligned address)
+  else if constexpr( FMT != VVR_OUT_V210 ) launch_output_yuv_as<FMT, false>( s, p, dst );
+}
+void launch_output_yuv( hipStream_t s, const OutputYuvParams& p, void* dst )
+{
+  switch( p.format )
+  {
+  case VVR_OUT_YUV444P8:  launch_output_yuv_fmt<VVR_OUT_YUV444P8>( s, p, dst ); break;
+  case VVR_OUT_YUV444P16: launch_output_yuv_fmt<VVR_OUT_YUV444P16>( s, p, dst ); break;
+  case VVR_OUT_YUV422P8:  launch_output_yuv_fmt<VVR_OUT_YUV422P8>( s, p, dst ); break;
+  case VVR_OUT_YUV422P16: launch_output_yuv_fmt<VVR_OUT_YUV422P16>( s, p, dst ); break;
+  case VVR_OUT_UYVY:      launch_output_yuv_fmt<VVR_OUT_UYVY>( s, p, dst ); break;
+  case VVR_OUT_YUY2:      launch_output_yuv_fmt<VVR_OUT_YUY2>( s, p, dst ); break;
+  case VVR_OUT_Y210:      launch_output_yuv_fmt<VVR_OUT_Y210>( s, p, dst ); break;
+  case VVR_OUT_V210:      launch_output_yuv_fmt<VVR_OUT_V210>( s, p, dst ); break;
+  case VVR_OUT_Y410:      launch_output_yuv_fmt<VVR_OUT_Y410>( s, p, dst ); break;
+  default: break;      // (the request path hands over one of the nine formats)
+  }
+}
+
 // k_output_stats — luma mode of the statistics: the window's rows in pieces of 8 samples, a lane one piece (one 16-byte load, sample by sample
 // at a row's end), a workgroup STATS_ITER x 256 consecutive pieces into one histogram in LDS - 16 K samples for each clear and each flush
 #define STATS_ITER 8

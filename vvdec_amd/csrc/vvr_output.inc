@@ -374,6 +374,77 @@ void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
     }
 }
 
+// ... and launch_output_yuv (k_output_yuv): the definition of vvr.h sample by sample - the two passes of launch_output_rgb above with the table's
+// taps, the horizontal position 16 * i - ( 0 or 8 ) (4:4:4) or 32 * i (4:2:2: every phase is 0), then the sample, the word or the packed group
+void launch_output_yuv( hipStream_t, const OutputYuvParams& p, void* dst )
+{
+  const int f = p.format;
+  const bool full = f == VVR_OUT_YUV444P8 || f == VVR_OUT_YUV444P16 || f == VVR_OUT_Y410, bytes = f == VVR_OUT_YUV444P8 || f == VVR_OUT_YUV422P8;
+  const int cw = p.w / 2, ch = p.h / 2, uw = full ? p.w : cw;      // (uw: the samples of a chroma row that leaves)
+  std::vector<int> sums( (size_t) ch * uw ), up[2];
+  for( int pl = 0; pl < 2; pl++ )
+  {
+    const pel_t* src = p.src[1 + pl];
+    up[pl].resize( (size_t) uw * p.h );
+    for( int i = 0; i < uw; i++ )
+    {
+      const int refPos = full ? 16 * i - ( p.collocated & 1 ? 0 : 8 ) : 32 * i, integer = refPos >> 5, frac = refPos & 31;
+      for( int j = 0; j < ch; j++ )
+      {
+        int sum = 0;
+        for( int k = 0; k < 4; k++ ) sum += rescale_host_tbl::vvc_chroma_filter[frac][k] * src[(size_t) j * p.stride[1 + pl] + std::min( std::max( 0, integer + k - 1 ), cw - 1 )];
+        sums[(size_t) j * uw + i] = sum;
+      }
+    }
+    for( int j = 0; j < p.h; j++ )
+    {
+      const int refPos = 16 * j - ( p.collocated & 2 ? 0 : 8 ), integer = refPos >> 5, frac = refPos & 31;
+      for( int i = 0; i < uw; i++ )
+      {
+        int sum = 0;
+        for( int k = 0; k < 4; k++ ) sum += rescale_host_tbl::vvc_chroma_filter[frac][k] * sums[(size_t) std::min( std::max( 0, integer + k - 1 ), ch - 1 ) * uw + i];
+        up[pl][(size_t) j * uw + i] = std::min( std::max( 0, ( sum + 2048 ) >> 12 ), p.maxVal );
+      }
+    }
+  }
+  uint8_t* out[3];
+  for( int c = 0; c < 3; c++ ) out[c] = p.direct[c] ? p.direct[c] : (uint8_t*) dst + p.dstOff[c];
+  auto luma = [&]( int i, int j ) { return (uint32_t) (uint16_t) p.src[0][(size_t) j * p.stride[0] + i]; };
+  const size_t v210Row = (size_t) ( p.w + 5 ) / 6 * 16;
+  for( int j = 0; j < p.h; j++ )
+  {
+    if( f == VVR_OUT_V210 ) memset( out[0] + j * v210Row, 0, v210Row );      // (the fields of pixels that do not exist)
+    for( int i = 0; i < p.w; i++ )
+    {
+      const uint32_t y = luma( i, j ) << p.shift, u = (uint32_t) up[0][(size_t) j * uw + ( full ? i : i / 2 )] << p.shift, v = (uint32_t) up[1][(size_t) j * uw + ( full ? i : i / 2 )] << p.shift;
+      const size_t at = (size_t) j * p.w + i, cat = (size_t) j * uw + i / 2;
+      switch( f )
+      {
+      case VVR_OUT_YUV444P8: case VVR_OUT_YUV422P8:
+        out[0][at] = (uint8_t) y;
+        if( full ) { out[1][at] = (uint8_t) u; out[2][at] = (uint8_t) v; } else if( !( i & 1 ) ) { out[1][cat] = (uint8_t) u; out[2][cat] = (uint8_t) v; }
+        break;
+      case VVR_OUT_YUV444P16: case VVR_OUT_YUV422P16:
+        ( (uint16_t*) out[0] )[at] = (uint16_t) y;
+        if( full ) { ( (uint16_t*) out[1] )[at] = (uint16_t) u; ( (uint16_t*) out[2] )[at] = (uint16_t) v; } else if( !( i & 1 ) ) { ( (uint16_t*) out[1] )[cat] = (uint16_t) u; ( (uint16_t*) out[2] )[cat] = (uint16_t) v; }
+        break;
+      case VVR_OUT_UYVY: out[0][2 * at + 1] = (uint8_t) y; if( !( i & 1 ) ) { out[0][2 * at] = (uint8_t) u; out[0][2 * at + 2] = (uint8_t) v; } break;
+      case VVR_OUT_YUY2: out[0][2 * at] = (uint8_t) y; if( !( i & 1 ) ) { out[0][2 * at + 1] = (uint8_t) u; out[0][2 * at + 3] = (uint8_t) v; } break;
+      case VVR_OUT_Y210: ( (uint16_t*) out[0] )[2 * at] = (uint16_t) y; if( !( i & 1 ) ) { ( (uint16_t*) out[0] )[2 * at + 1] = (uint16_t) u; ( (uint16_t*) out[0] )[2 * at + 3] = (uint16_t) v; } break;
+      case VVR_OUT_Y410: { const uint32_t d = u | y << 10 | v << 20 | 3u << 30; memcpy( out[0] + at * 4, &d, 4 ); } break;
+      default:      // VVR_OUT_V210: the 10-bit fields of a group in order Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5, three to a dword
+      {
+        uint32_t* g = (uint32_t*) ( out[0] + j * v210Row ) + i / 6 * 4;
+        static const int yField[6] = { 1, 3, 5, 7, 9, 11 }, uField[3] = { 0, 4, 8 }, vField[3] = { 2, 6, 10 };
+        const int k = i % 6;
+        g[yField[k] / 3] |= y << ( 10 * ( yField[k] % 3 ) );
+        if( !( k & 1 ) ) { g[uField[k / 2] / 3] |= u << ( 10 * ( uField[k / 2] % 3 ) ); g[vField[k / 2] / 3] |= v << ( 10 * ( vField[k / 2] % 3 ) ); }
+      }
+      }
+    }
+  }
+}
+
 // ... and launch_hash_rows / launch_hash_combine (k_hash_rows, k_hash_combine): per row the CRC register reached from 0 bit by bit (compCRC,
 // PicYuvMD5.cpp:99-137) or the checksum share (compChecksum, :152-176); the rows chained with the request's power of x, or added
 void launch_hash_rows( hipStream_t, const HashParams& p, uint32_t* rows )
@@ -1040,7 +1111,7 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 
 // =====================================================================================================================
 // output queue: the output stage as a pipeline.  A request is ordered behind its picture's `done` event on the context's output stream,
-// runs there (k_film_grain, k_rescale, k_output_frame or k_output_rgb as the request needs them), leaves through a ring entry (device scratch + pinned
+// runs there (k_film_grain, k_rescale, k_output_frame, k_output_rgb or k_output_yuv as the request needs them), leaves through a ring entry (device scratch + pinned
 // staging) and is collected with its ticket.  Nothing here calls vvr_sync.  The slot is protected the way an external reader's is
 // (vvr_slot_external_event): the entry's `read` event, recorded behind the last kernel of the request, is registered with the slot, so a
 // picture submitted afterwards that overwrites the slot waits for it on the device - not for the copy to the host.
@@ -1230,12 +1301,16 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   const bool rgb = rq->format == VVR_OUT_RGB8 || rq->format == VVR_OUT_RGB16 || rq->format == VVR_OUT_RGBF16 || rq->format == VVR_OUT_RGBF32 || inter;
   const bool rgb8 = rq->format == VVR_OUT_RGB8 || rq->format == VVR_OUT_RGBA8 || rq->format == VVR_OUT_BGRA8 || rq->format == VVR_OUT_RGB24 || rq->format == VVR_OUT_BGR24;      // (the values VVR_OUT_RGB8 stores)
   const int px = rq->format == VVR_OUT_RGB8 ? 1 : rq->format == VVR_OUT_RGB24 || rq->format == VVR_OUT_BGR24 ? 3 : rq->format == VVR_OUT_RGBA16F ? 8 : rq->format == VVR_OUT_RGB16 || rq->format == VVR_OUT_RGBF16 ? 2 : 4;
-  if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 && !rgb ) return outRefuse( c, "unknown format" );
+  // the Y'CbCr formats at 4:4:4 / 4:2:2 (k_output_yuv): three planes, or one packed plane (`yuvOne`); yuv8: the sample as a byte
+  const bool yuv = rq->format >= VVR_OUT_YUV444P8 && rq->format <= VVR_OUT_Y410;
+  const bool yuv444 = rq->format == VVR_OUT_YUV444P8 || rq->format == VVR_OUT_YUV444P16 || rq->format == VVR_OUT_Y410, yuvOne = yuv && rq->format >= VVR_OUT_UYVY;
+  const bool yuv8 = rq->format == VVR_OUT_YUV444P8 || rq->format == VVR_OUT_YUV422P8 || rq->format == VVR_OUT_UYVY || rq->format == VVR_OUT_YUY2;
+  if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 && !rgb && !yuv ) return outRefuse( c, "unknown format" );
   if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1" );
   const bool packed = rq->format == VVR_OUT_PACKED10, semi = rq->format == VVR_OUT_NV12 || rq->format == VVR_OUT_P010, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
-  const bool viaTmp = packed || semi || rgb;      // k_output_frame / k_output_rgb makes the format: the stages before it store 16-bit samples into `tmp`
-  const bool narrow = rq->format == VVR_OUT_PLANAR8 || rq->format == VVR_OUT_NV12;
-  const int bps = narrow ? 1 : rgb ? px : 2, nOut = semi ? 2 : inter ? 1 : nc;
+  const bool viaTmp = packed || semi || rgb || yuv;      // k_output_frame / k_output_rgb / k_output_yuv makes the format: the stages before it store 16-bit samples into `tmp`
+  const bool narrow = rq->format == VVR_OUT_PLANAR8 || rq->format == VVR_OUT_NV12 || yuv8;
+  const int bps = narrow ? 1 : rgb ? px : 2, nOut = semi ? 2 : inter || yuvOne ? 1 : yuv ? 3 : nc;
   int outMatrix = 0, outFullRange = 0;      // (the colour description: looked at here for the refusal, taken under mu where the request is accepted)
   if( rgb )
   {
@@ -1246,9 +1321,12 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     if( scaled && ( ( rq->out_w | rq->out_h ) & 1 ) ) return outRefuse( c, "RGB output needs an even out_w and out_h (one 4:2:0 frame is converted)" );
   }
   if( semi && nc == 1 ) return outRefuse( c, "semi-planar output of a 4:0:0 context: there is no chroma to interleave" );
+  if( yuv && nc == 1 ) return outRefuse( c, "4:2:2 / 4:4:4 output of a 4:0:0 context: there is no chroma to upsample" );
   if( rq->format == VVR_OUT_P010 && ( bd < 8 || bd > 10 ) ) return outRefuse( c, "P010 output needs a bit depth of 8, 9 or 10" );
   if( narrow && bd > 8 ) return outRefuse( c, "8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" );
   if( packed && bd != 8 && bd != 10 ) return outRefuse( c, "packed 10-bit output needs a bit depth of 8 or 10 (vvdecHelper.h:106-248)" );
+  if( yuv && ( bd < 8 || bd > 10 ) ) return outRefuse( c, "4:2:2 / 4:4:4 output needs a bit depth of 8, 9 or 10" );
+  if( yuv && scaled && ( ( rq->out_w | rq->out_h ) & 1 ) ) return outRefuse( c, "4:2:2 / 4:4:4 output needs an even out_w and out_h (one 4:2:0 frame is upsampled)" );
   const DevPlanes d = pictureIn( c, slot );
   if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, or odd in 4:2:0" );
   if( grain )
@@ -1269,6 +1347,12 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     if( packed && ( ow[k] & 3 ) ) return outRefuse( c, "packed 10-bit output needs plane widths that are multiples of 4 (four samples in five bytes)" );
     rowBytes[k] = packed ? (size_t) ow[k] / 4 * 5 : (size_t) ow[rgb ? 0 : k] * bps * ( semi && k ? 2 : 1 );      // (semi-planar plane 1: Cb and Cr interleaved; RGB: every plane at the luma size)
     outRows[k] = oh[rgb ? 0 : k];
+    if( yuv )      // (every plane has the luma rows; the chroma planes of the planar 4:2:2 formats half the luma samples of a row)
+    {
+      const size_t W0 = (size_t) ow[0];
+      rowBytes[k] = rq->format == VVR_OUT_V210 ? ( W0 + 5 ) / 6 * 16 : rq->format == VVR_OUT_Y210 || rq->format == VVR_OUT_Y410 ? W0 * 4 : yuvOne ? W0 * 2 : ( yuv444 || !k ? W0 : W0 >> 1 ) * ( yuv8 ? 1 : 2 );
+      outRows[k] = oh[0];
+    }
     if( k < nOut && ( !rq->dst[k] || rq->dst_stride_bytes[k] < rowBytes[k] ) ) return outRefuse( c, "missing plane or stride below the output's row" );
   }
   hipSetDevice( c->device );
@@ -1386,7 +1470,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   }
   OutputFrameParams fp; memset( &fp, 0, sizeof( fp ) );
   double frameBytes = 0;
-  for( int k = 0; k < nc && !rgb; k++ )
+  for( int k = 0; k < nc && !rgb && !yuv; k++ )
     if( !cur[k].inOut )
     {
       fp.src[k] = cur[k].p; fp.stride[k] = cur[k].stride; frameBytes += (double) ow[k] * oh[k] * 2 + ( k < nOut ? (double) rowBytes[k] * oh[k] : 0. );
@@ -1434,6 +1518,19 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     }
     outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + (double) nOut * px ) );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma; written: the planes, or the pixel)
     launch_output_rgb( s, rp, e->dev );
+    if( e->timed ) hipEventRecord( e->timing.b, s );
+  }
+  if( yuv )
+  {
+    // the frame as it stands, as the RGB formats take it, with the chroma upsampled and the format's store in one launch
+    OutputYuvParams yp; memset( &yp, 0, sizeof( yp ) );
+    double written = 0;
+    for( int k = 0; k < 3; k++ ) { yp.src[k] = cur[k].p; yp.stride[k] = cur[k].stride; yp.dstOff[k] = k < nOut ? e->off[k] : 0; yp.direct[k] = k < nOut && kdirect[k] ? (uint8_t*) rq->dst[k] : nullptr; }
+    for( int k = 0; k < nOut; k++ ) written += (double) rowBytes[k] * outRows[k];
+    yp.w = ow[0]; yp.h = oh[0]; yp.collocated = rq->collocated & 3; yp.format = rq->format; yp.maxVal = ( 1 << bd ) - 1;
+    yp.shift = rq->format == VVR_OUT_Y210 ? 16 - bd : rq->format == VVR_OUT_V210 || rq->format == VVR_OUT_Y410 ? 10 - bd : 0;
+    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_YUV, (double) yp.w * yp.h * 3. + written );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma; written: the planes)
+    launch_output_yuv( s, yp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
   }
   OQCHK( hipGetLastError() );
