@@ -524,7 +524,7 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *            VVR_OUT_NV12 / VVR_OUT_P010: the semi-planar forms display, encode and ML pipelines exchange.  Two planes leave the request: dst[0]
  *            takes the luma rows, dst[1] the interleaved chroma rows Cb0, Cr0, Cb1, Cr1, ... of 2 * ( out_w >> 1 ) samples, out_h >> 1 of them
  *            (dst_stride_bytes[1] covers that row; dst[2] and dst_stride_bytes[2] are ignored and may be NULL / 0).  NV12: one byte per sample,
- *            the sample itself, 8-bit contexts only (VVR_OUT_PLANAR8's refusal).  P010: little-endian 16-bit words, sample << ( 16 - bit_depth ),
+ *            the sample itself in an 8-bit context; at 9 / 10 bits refused unless a narrowing is set (vvr_set_output_narrowing below).  P010: little-endian 16-bit words, sample << ( 16 - bit_depth ),
  *            bit depths 8, 9 and 10.  Both are refused in a 4:0:0 context: there is no chroma to interleave.
  *            VVR_OUT_RGB8 / VVR_OUT_RGB16 / VVR_OUT_RGBF16: planar R'G'B' for a model on the same GPU.  Three planes of out_w x out_h samples
  *            (or w x h) leave the request, dst[0], dst[1], dst[2] = R, G, B, rows of out_w * 1 (RGB8) or out_w * 2 bytes.  The frame that is
@@ -565,12 +565,12 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *            a filter that works in Y'CbCr on one grid.  The frame that is converted is the one every other format would store: the window,
  *            grained, rescaled, in that order.  No colour description is needed; transform, 3-D LUT and normalisation are ignored.  Y is the
  *            frame's luma unchanged.  With W = out_w (or w), H = out_h (or h):
- *              YUV444P8   dst[0..2] = Y, Cb', Cr', each W x H   rows of W bytes        the sample, 8-bit contexts only (VVR_OUT_PLANAR8's refusal)
+ *              YUV444P8   dst[0..2] = Y, Cb', Cr', each W x H   rows of W bytes        the sample; above 8 bits: vvr_set_output_narrowing
  *              YUV444P16  the same                              rows of W * 2 bytes    the sample as a little-endian 16-bit word
  *              YUV422P8   Y W x H; Cb', Cr' ( W >> 1 ) x H      rows of W, W >> 1      as YUV444P8
  *              YUV422P16  the same                              W * 2, ( W >> 1 ) * 2  as YUV444P16
- *              UYVY       dst[0] alone, rows of W * 2 bytes     bytes Cb, Y0, Cr, Y1 per pixel pair; 8-bit contexts only
- *              YUY2       dst[0] alone, rows of W * 2 bytes     bytes Y0, Cb, Y1, Cr per pixel pair; 8-bit contexts only
+ *              UYVY       dst[0] alone, rows of W * 2 bytes     bytes Cb, Y0, Cr, Y1 per pixel pair; above 8 bits as YUV444P8
+ *              YUY2       dst[0] alone, rows of W * 2 bytes     bytes Y0, Cb, Y1, Cr per pixel pair; above 8 bits as YUV444P8
  *              Y210       dst[0] alone, rows of W * 4 bytes     little-endian words Y0, Cb, Y1, Cr, each sample << ( 16 - bit_depth ) (P010's rule)
  *              V210       dst[0] alone, rows of ( ( W + 5 ) / 6 ) * 16 bytes: six pixels in four little-endian dwords.  With s' = sample <<
  *                         ( 10 - bit_depth ) (VVR_OUT_PACKED10's widening) and Cbk, Crk the chroma of pixel pair k of the group:
@@ -593,9 +593,9 @@ VVR_API int          vvr_read_output_grain(vvr_context* ctx, int slot, int x, in
  *              integer - 1 .. integer + 2 of the same column, clamped to the plane: what the kernel computes.  Bit 0 of `collocated` is
  *              ignored: the horizontal chroma grid is the stream's.  With a collocated vertical position every second row is the source row.
  *            Refused, each with its text, before a ring entry is taken: a 4:0:0 context (no chroma to upsample); an 8-bit format in a context
- *            of more than 8 bits (bit-depth reduction of Y'CbCr is not offered); a bit depth outside 8..10; an odd out_w or out_h; a missing
+ *            of more than 8 bits with no narrowing set (vvr_set_output_narrowing below); a bit depth outside 8..10; an odd out_w or out_h; a missing
  *            plane or a stride below the row among the planes the format uses.
- *            Not offered: semi-planar 4:2:2 / 4:4:4 (P210, NV16), AYUV / VUYA, Y216 / Y416; 10 -> 8 bit reduction of Y'CbCr; 4:0:0 with neutral
+ *            Not offered: semi-planar 4:2:2 / 4:4:4 (P210, NV16), AYUV / VUYA, Y216 / Y416; 4:0:0 with neutral
  *            chroma; these formats from the synchronous vvr_read_output* calls; decoding 4:2:2 / 4:4:4 streams.
  *            Not offered: interleaved float32; 4:0:0 as grey; RGB from the synchronous vvr_read_output* calls; constant-luminance BT.2020,
  *            ICtCp, YCgCo, the identity matrix; a 3-D LUT for the synchronous calls.  Dynamic metadata: the per-frame measurements exist
@@ -648,6 +648,31 @@ typedef struct vvr_output_request {
  * stays.  A request takes the value that is set when vvr_output_submit accepts it: the coefficients travel as kernel arguments, a later call
  * never changes a request in flight. */
 VVR_API int          vvr_set_output_colour(vvr_context* ctx, int matrix_coefficients, int full_range);
+/* 8-bit Y'CbCr frames from 9- and 10-bit pictures - context state, like the colour description.  mode: VVR_NARROW_REFUSE (a new context: the
+ * byte-per-sample formats are refused above 8 bits, as ever), _TRUNCATE, _ROUND or _DITHER; phase: 0 .. 3.  A mode outside 0 .. 3 or a phase
+ * outside 0 .. 3 is VVR_ERR_PARAMETER with a text, and the value set before stays.  A request takes the value that is set when
+ * vvr_output_submit accepts it: the values travel as kernel arguments, a later call never changes a request in flight.
+ *   The mode is looked at only for the six byte-per-sample Y'CbCr formats - VVR_OUT_PLANAR8, _NV12, _YUV444P8, _YUV422P8, _UYVY, _YUY2 - and only
+ *   in a context of 9 or 10 bits.  In an 8-bit context, and for every other format, a request stores exactly the bytes it stores with mode 0.
+ *   Defined to the bit.  s = bit_depth - 8 (1 or 2); v: the 16-bit word the 16-bit sibling format would store for the sample - VVR_OUT_PLANAR16
+ *   for PLANAR8 and NV12, _YUV444P16 for YUV444P8, _YUV422P16 for YUV422P8, UYVY and YUY2 - that is the window, grained, rescaled, with the
+ *   chroma upsampled, in that order; the reduction is the very last step before the store.  In 32-bit arithmetic:
+ *     byte = min( 255, ( v + a ) >> s )
+ *     TRUNCATE  a = 0                     (at 10 bits what vvdecapp writes for an 8-bit file of a 10-bit stream, vvdecHelper.h:90)
+ *     ROUND     a = 1 << ( s - 1 )
+ *     DITHER    a = M[ ( j + ( phase >> 1 & 1 ) ) & 1 ][ ( i + ( phase & 1 ) ) & 1 ] >> ( 2 - s ),   M = { { 0, 2 }, { 3, 1 } }
+ *   ( i, j ): the sample's column and row IN ITS OWN OUTPUT PLANE - the stored frame's, not the picture's.  Luma: ( x, y ).  A chroma plane of
+ *   PLANAR8 / NV12: its own 4:2:0 coordinates; the Cb and the Cr of NV12's pair k in row j both use ( k, j ).  YUV444P8 chroma: ( x, y ).
+ *   YUV422P8 / UYVY / YUY2 chroma of pixel pair k: ( k, y ).  The min matters in every mode but TRUNCATE on in-range samples:
+ *   ( 1023 + 3 ) >> 2 = 256.  v is read as it lies (vvr_write_plane can put anything into a slot); clamping v to 2^bit_depth - 1 first gives
+ *   the same byte for every input, and the packed 16-bit arithmetic of the device relies on it.  `phase` lets a caller move the pattern per
+ *   frame; nothing in the library advances it.
+ *   Everything vvr_output_submit refuses stays refused under a mode: the 4:0:0 refusals of NV12 and the 4:2:2 / 4:4:4 formats, grain at depths
+ *   other than 8 and 10, odd sizes, ...  PLANAR8 of a 4:0:0 context at 9 / 10 bits is accepted, luma alone.
+ *   Not offered: the synchronous vvr_read_output* calls with bytes_per_sample == 1 keep their refusal above 8 bits; error diffusion and
+ *   blue-noise masks; dither for the RGB formats; P210 / NV16. */
+enum { VVR_NARROW_REFUSE = 0, VVR_NARROW_TRUNCATE = 1, VVR_NARROW_ROUND = 2, VVR_NARROW_DITHER = 3 };
+VVR_API int          vvr_set_output_narrowing(vvr_context* ctx, int mode, int phase);
 /* Normalisation of VVR_OUT_RGBF32: a mean and a standard deviation per channel (R, G, B), as a vision model takes them.  Context state like the
  * colour description (copied; NULL, NULL: none; a new context has none): a VVR_OUT_RGBF32 request takes the value that is set when
  * vvr_output_submit accepts it, it travels as kernel arguments, a later call never changes a request in flight.  Every other format -

@@ -76,6 +76,7 @@ def lib():
         L.vvr_set_film_grain_seed.argtypes = [C.c_void_p, C.c_uint32]
         L.vvr_set_output_colour.restype = C.c_int
         L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        abi.bind_output_narrowing(L)
         L.vvr_set_output_normalisation.restype = C.c_int
         L.vvr_set_output_normalisation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vvr_set_output_transform.restype = C.c_int
@@ -140,7 +141,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_set_output_lut3d", "vvr_output_lut3d_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_narrowing", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_set_output_lut3d", "vvr_output_lut3d_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
@@ -438,6 +439,18 @@ class Reconstructor:
         value that is set when it is submitted."""
         self._check(self.L.vvr_set_output_colour(self.ctx, int(matrix), 1 if full_range else 0))
 
+    def set_output_narrowing(self, mode, phase=0):
+        """how the byte-per-sample Y'CbCr formats of output_submit ("planar8", "nv12", "yuv444p8", "yuv422p8", "uyvy", "yuy2") leave a context of
+        9 or 10 bits (vvr_set_output_narrowing, the arithmetic: vvr.h): 0 / "refuse" (a new context: such a request is refused), 1 / "truncate"
+        (v >> s), 2 / "round", 3 / "dither" (ordered, a 2 x 2 cell; phase 0 .. 3 moves it by a column and / or a row - nothing advances it).
+        The planes are uint8 arrays or tensors of the shapes the formats have in an 8-bit context (abi.output_plane_shapes), `into=` included.  A
+        request takes the value that is set when it is submitted; 8-bit contexts and every other format ignore it."""
+        if isinstance(mode, str):
+            if mode not in abi.NARROW_MODES:
+                raise ValueError("set_output_narrowing: mode is 0 .. 3 or one of %s" % ", ".join(abi.NARROW_MODES))
+            mode = abi.NARROW_MODES[mode]
+        self._check(self.L.vvr_set_output_narrowing(self.ctx, int(mode), int(phase)))
+
     def set_output_normalisation(self, mean=None, std=None):
         """the per-channel mean and standard deviation the "rgbf32" format of output_submit applies (vvr_set_output_normalisation): three floats
         each for R, G, B, in units of full scale (0 .. 1) - out = v / (M * std) - mean / std in two float32 roundings (vvr.h); None: none.  A
@@ -504,7 +517,8 @@ class Reconstructor:
     def output_submit(self, slot, job=None, window=None, fmt="planar16", size=None, collocated=(True, False), grain=False, pinned=False, blocking=True, into=None):
         """vvr_output_submit: the window of `slot` (as `job` leaves it; None: as all work submitted so far leaves it) in the application's form ->
         ticket, or None when blocking=False and the job has not been handed to the device yet.  fmt: "planar16", "planar8", "packed10"
-        (vvdecapp --pyuv: four samples in five bytes), "nv12" or "p010" (two planes: luma, interleaved CbCr; p010: sample << (16 - bit depth)),
+        (vvdecapp --pyuv: four samples in five bytes), "nv12" or "p010" (two planes: luma, interleaved CbCr; p010: sample << (16 - bit depth);
+        the byte formats - "planar8", "nv12", "yuv444p8", "yuv422p8", "uyvy", "yuy2" - in a context of 9 or 10 bits: set_output_narrowing),
         "rgb8", "rgb16" or "rgbf16" (three planes R, G, B at the luma size, converted on the device with the matrix of set_output_colour: vvr.h);
         "rgbf32" (the three planes as float32 with set_output_normalisation applied), "rgba8", "bgra8", "rgb24", "bgr24", "rgb10a2" or "rgba16f"
         (one plane of interleaved pixels: abi.output_plane_shapes); "yuv444p8", "yuv444p16" (Y, Cb, Cr at the luma size), "yuv422p8", "yuv422p16"

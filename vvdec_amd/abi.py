@@ -172,6 +172,17 @@ OUT_FORMATS = {"planar16": OUT_PLANAR16, "planar8": OUT_PLANAR8, "packed10": OUT
 OUT_YUV_PACKED = {"uyvy": lambda w: 2 * w, "yuy2": lambda w: 2 * w, "y210": lambda w: 2 * w, "v210": lambda w: (w + 5) // 6 * 4, "y410": lambda w: w}
 # the interleaved formats: elements of the plane's dtype per pixel (rgb10a2: one uint32)
 OUT_INTERLEAVED = {"rgba8": 4, "bgra8": 4, "rgb24": 3, "bgr24": 3, "rgba16f": 4, "rgb10a2": 1}
+# vvr_set_output_narrowing: how the byte-per-sample Y'CbCr formats leave a context of 9 or 10 bits (VVR_NARROW_*); OUT_NARROWED: the formats it is looked at for
+NARROW_REFUSE, NARROW_TRUNCATE, NARROW_ROUND, NARROW_DITHER = 0, 1, 2, 3
+NARROW_MODES = {"refuse": NARROW_REFUSE, "truncate": NARROW_TRUNCATE, "round": NARROW_ROUND, "dither": NARROW_DITHER}
+OUT_NARROWED = ("planar8", "nv12", "yuv444p8", "yuv422p8", "uyvy", "yuy2")
+
+
+def bind_output_narrowing(L):
+    """the ctypes signature of vvr_set_output_narrowing on a loaded library (the product's, or the host build of the tests)"""
+    L.vvr_set_output_narrowing.restype = C.c_int
+    L.vvr_set_output_narrowing.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    return L
 
 
 class OutputRequest(C.Structure):

@@ -90,7 +90,7 @@ static double g_wdSum[6]; static uint64_t g_wdJobs; static double g_wdPart[4], g
 
 struct Stat { uint64_t launches = 0; double ms = 0, bytes = 0; };
 struct PendingTiming { hipEvent_t a, b; int kernel; double bytes; };
-const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame", "k_output_rgb", "k_hash_rows", "k_hash_combine", "k_plane_hash_rows", "k_output_stats", "k_output_stats_sum", "k_output_compare", "k_output_compare_sum", "k_output_ssim", "k_output_ssim_sum", "k_output_yuv" };
+const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame", "k_output_rgb", "k_hash_rows", "k_hash_combine", "k_plane_hash_rows", "k_output_stats", "k_output_stats_sum", "k_output_compare", "k_output_compare_sum", "k_output_ssim", "k_output_ssim_sum", "k_output_yuv", "k_output_narrow" };
 
 // One slot of the upload ring: pinned staging memory and its image in HBM (grown on demand, never freed while the context lives), the device
 // pointers of the picture that currently sits in it, and the pinned landing area of its DMVR delta MVs.
@@ -174,6 +174,8 @@ struct vvr_context {
   std::unique_ptr<vvr_film_grain_bank> grainBank; void* grainBankDev = nullptr; bool grainBankStale = false; uint32_t grainSeed = 0xdeadbeefu;
   // colour description of the RGB formats of the output queue (vvr_set_output_colour): H.273 matrix_coefficients (0: none set) and the range flag
   int        outMatrix = 0, outFullRange = 0;
+  // ... and the narrowing of the byte-per-sample Y'CbCr formats in a context of 9 or 10 bits (vvr_set_output_narrowing): VVR_NARROW_*, the dither's phase
+  int        outNarrow = 0, outNarrowPhase = 0;
   // ... and the normalisation of VVR_OUT_RGBF32 (vvr_set_output_normalisation): mean and standard deviation per channel as they were given
   bool       outNorm = false; float outMean[3] = { 0, 0, 0 }, outStd[3] = { 1, 1, 1 };
   // ... and their colour transform (vvr_set_output_transform): the context's copy (NULL: none), its device copy - the struct as it is, k_output_rgb reads
@@ -1611,6 +1613,16 @@ VVR_API uint8_t vvr_resolve_tr_type( const vvr_pic_header* hdr, const vvr_cu* cu
     ver = ( ( tu->mts_idx[comp] - 2 ) >> 1 ) ? 1 : 2;
   }
   return (uint8_t) ( ( ver << 2 ) | hor );
+}
+
+VVR_API int vvr_set_output_narrowing( vvr_context* c, int mode, int phase )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  if( mode < VVR_NARROW_REFUSE || mode > VVR_NARROW_DITHER ) { c->setError( "vvr_set_output_narrowing: mode must be 0 (refuse), 1 (truncate), 2 (round) or 3 (dither)" ); return VVR_ERR_PARAMETER; }
+  if( phase < 0 || phase > 3 ) { c->setError( "vvr_set_output_narrowing: phase must be 0 .. 3" ); return VVR_ERR_PARAMETER; }
+  c->outNarrow = mode; c->outNarrowPhase = phase;
+  return VVR_OK;
 }
 
 }   // extern "C"

@@ -259,6 +259,12 @@ struct OutputFrameParams
   int format, shift;
 };
 void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst );
+// the 9 / 10 -> 8 bit reduction of the byte-per-sample Y'CbCr formats (vvr_set_output_narrowing, the definition: vvr.h): byte =
+// min( 255, ( min( v, maxVal ) + a ) >> s ).  cell[r]: the additive constants of row parity r of the 2 x 2 cell with the phase folded in, the one of
+// an even column in the low, of an odd column in the high 16 bits (TRUNCATE: 0; ROUND: ( 1 << ( s - 1 ) ) * 0x10001; DITHER: the matrix)
+struct NarrowArgs { int s, maxVal; uint32_t cell[2]; };
+// VVR_OUT_PLANAR8 / VVR_OUT_NV12 of a context of 9 or 10 bits (k_output_narrow): p as launch_output_frame takes it, the reduction at the store
+void launch_output_narrow( hipStream_t s, OutputFrameParams p, NarrowArgs na, void* dst );
 // a frame of the output queue as R'G'B' (planar VVR_OUT_RGB8 / _RGB16 / _RGBF16 / _RGBF32 or one interleaved plane, the definition: vvr.h): one 4:2:0 frame of w x h luma samples
 // (even; the chroma planes w / 2 x h / 2), chroma brought to the luma grid by the 4-tap DCTIF at the two phases `collocated` selects per direction
 // (taps clamped to the frame), then the Q14 matrix.  Three planes of w x h samples (or one of w x h pixels) leave, rows back to back, into dst + dstOff[c] (256-byte
@@ -297,6 +303,9 @@ struct OutputYuvParams
   const pel_t* src[3]; int stride[3], w, h; size_t dstOff[3];
   uint8_t* direct[3];
   int format, collocated, maxVal, shift;
+  // the four byte formats in a context of 9 or 10 bits: the reduction at the store (narrow.s != 0; the kernel's NARROW variants).  (Behind the
+  // fields above: the kernel arguments of the instantiations that serve every other request stay where they were.)
+  NarrowArgs narrow;
 };
 void launch_output_yuv( hipStream_t s, const OutputYuvParams& p, void* dst );
 // light-level statistics of the output queue (vvr_stats_submit, the definition: vvr.h).  launch_output_stats: the window src / stride / w / h of p

@@ -5107,6 +5107,109 @@ void launch_output_frame( hipStream_t s, OutputFrameParams p, void* dst )
   if( total ) hipLaunchKernelGGL( k_output_frame, dim3( total ), dim3( 256 ), 0, s, p, (uint8_t*) dst );
 }
 
+// k_output_narrow — VVR_OUT_PLANAR8 / VVR_OUT_NV12 of a context of 9 or 10 bits (vvr_set_output_narrowing, the definition: vvr.h): k_output_frame's
+// decomposition - a plane's output one stream of samples, a lane 16 consecutive ones (NV12's CbCr plane: 8 pairs from one 16-byte load per
+// chroma plane, interleaved by v_perm_b32), one whole 16-byte store, lanes whose piece straddles the end of a row gather, partial stores only
+// into the caller's device memory - with the reduction on the packed dwords (two samples each) ahead of the OF_PERM_NARROW permute: packed min
+// with 2^bd - 1 (so that the 16-bit sum cannot wrap: the same byte for every input, vvr.h), packed add of the thresholds, packed shift, packed
+// min with 255.  The three modes are one path: the four constants of the 2 x 2 cell arrive as kernel arguments (NarrowArgs).
+// The thresholds go by column and row of the sample in its plane, not by its index in the stream: a piece of a narrow or odd-width plane
+// (chroma widths are odd for w = 2 mod 4) spans several rows, and the column parity flips where a row of odd length ends.  A lane whose piece
+// lies in one row has one threshold dword for all eight (halves swapped when it starts at an odd column), or - CbCr - two in turn, a pair's Cb
+// and Cr sharing the pair's column; a lane that gathers builds its thresholds beside its samples.  No LDS, no scratch.
+typedef unsigned short of_ushort2 __attribute__(( ext_vector_type( 2 ) ));
+__device__ __forceinline__ uint32_t of_narrow2( uint32_t d, uint32_t a, const NarrowArgs& na )
+{
+  of_ushort2 v = __builtin_bit_cast( of_ushort2, d );
+  v = __builtin_elementwise_min( v, (of_ushort2) (unsigned short) na.maxVal );
+  v = v + __builtin_bit_cast( of_ushort2, a );
+  v = v >> (of_ushort2) (unsigned short) na.s;
+  v = __builtin_elementwise_min( v, (of_ushort2) (unsigned short) 255 );
+  return __builtin_bit_cast( uint32_t, v );
+}
+__global__ __launch_bounds__( 256 ) void k_output_narrow( OutputFrameParams p, NarrowArgs na, uint8_t* __restrict__ dst )
+{
+  const int blk = blockIdx.x, c = blk >= p.first[2] && p.w[2] ? 2 : ( blk >= p.first[1] && p.w[1] ? 1 : 0 );
+  const uint32_t w = p.w[c], n = w * (uint32_t) p.h[c], piece = (uint32_t) ( blk - p.first[c] ) * 256 + threadIdx.x, i0 = piece * 16;
+  if( i0 >= n ) return;
+  const uint32_t r = i0 / w, x = i0 - r * w;
+  const uint32_t cellR = r & 1 ? na.cell[1] : na.cell[0];      // (the lane's first row: low half the even columns', high half the odd columns')
+  uint32_t d[8], a[8];
+  if( p.format == VVR_OUT_NV12 && c == 1 )
+  {
+    // (w and i0 are even, so x is: the piece starts with a Cb; pair k of the row has column k of the plane's cell)
+    const uint32_t cw = w >> 1, px = x >> 1;
+    const pel_t* __restrict__ rowB = p.src[1] + (size_t) r * p.stride[1] + px;
+    const pel_t* __restrict__ rowR = p.src[2] + (size_t) r * p.stride[2] + px;
+    if( px + 8 <= cw )
+    {
+      const uint4 u = *(const of_uint4_u*) rowB, v = *(const of_uint4_u*) rowR;
+      d[0] = __builtin_amdgcn_perm( v.x, u.x, OF_PERM_LO16 ); d[1] = __builtin_amdgcn_perm( v.x, u.x, OF_PERM_HI16 );
+      d[2] = __builtin_amdgcn_perm( v.y, u.y, OF_PERM_LO16 ); d[3] = __builtin_amdgcn_perm( v.y, u.y, OF_PERM_HI16 );
+      d[4] = __builtin_amdgcn_perm( v.z, u.z, OF_PERM_LO16 ); d[5] = __builtin_amdgcn_perm( v.z, u.z, OF_PERM_HI16 );
+      d[6] = __builtin_amdgcn_perm( v.w, u.w, OF_PERM_LO16 ); d[7] = __builtin_amdgcn_perm( v.w, u.w, OF_PERM_HI16 );
+      const uint32_t first = __builtin_amdgcn_perm( cellR, cellR, OF_PERM_LO16 ), second = __builtin_amdgcn_perm( cellR, cellR, OF_PERM_HI16 );      // (both halves the even column's; the odd column's)
+#pragma unroll
+      for( int k = 0; k < 8; k++ ) a[k] = ( ( px + k ) & 1 ) ? second : first;
+    }
+    else
+    {
+      uint32_t xx = px, cell = cellR;
+#pragma unroll
+      for( int k = 0; k < 8; k++ )
+      {
+        d[k] = i0 + 2 * k < n ? (uint32_t) (uint16_t) *rowB | (uint32_t) (uint16_t) *rowR << 16 : 0;
+        a[k] = __builtin_amdgcn_perm( cell, cell, xx & 1 ? OF_PERM_HI16 : OF_PERM_LO16 );
+        rowB++; rowR++;
+        if( ++xx == cw ) { xx = 0; rowB += p.stride[1] - (int) cw; rowR += p.stride[2] - (int) cw; cell ^= na.cell[0] ^ na.cell[1]; }      // (the next row: the other half of the cell)
+      }
+    }
+  }
+  else
+  {
+    const pel_t* __restrict__ row = p.src[c] + (size_t) r * p.stride[c];
+    if( x + 16 <= w )      // (2-byte aligned in general: the window starts anywhere)
+    {
+      const of_uint4_u* q = (const of_uint4_u*) ( row + x );
+      const uint4 q0 = q[0], q1 = q[1];
+      __builtin_memcpy( &d[0], &q0, 16 ); __builtin_memcpy( &d[4], &q1, 16 );
+      const uint32_t pair = x & 1 ? __builtin_amdgcn_alignbit( cellR, cellR, 16 ) : cellR;      // (an odd first column: the halves change places)
+#pragma unroll
+      for( int k = 0; k < 8; k++ ) a[k] = pair;
+    }
+    else
+    {
+      OfPiece v, t;
+      uint32_t xx = x, cell = cellR;
+#pragma unroll
+      for( int k = 0; k < 16; k++ )
+      {
+        v.s[k] = i0 + k < n ? (uint16_t) row[xx] : 0;
+        t.s[k] = (uint16_t) ( xx & 1 ? cell >> 16 : cell );
+        if( ++xx == w ) { xx = 0; row += p.stride[c]; cell ^= na.cell[0] ^ na.cell[1]; }
+      }
+      __builtin_memcpy( d, &v, 32 ); __builtin_memcpy( a, &t, 32 );
+    }
+  }
+  uint32_t b[4];
+#pragma unroll
+  for( int k = 0; k < 4; k++ ) b[k] = __builtin_amdgcn_perm( of_narrow2( d[2 * k + 1], a[2 * k + 1], na ), of_narrow2( d[2 * k], a[2 * k], na ), OF_PERM_NARROW );
+  uint8_t* out = p.direct[c] ? p.direct[c] : dst + p.dstOff[c];
+  const uint32_t left = n - i0;
+  if( !( p.direct[c] && left < 16 ) ) *(uint4*) ( out + i0 ) = make_uint4( b[0], b[1], b[2], b[3] );
+  else      // (the caller's memory ends with the plane)
+  {
+#pragma unroll
+    for( int k = 0; k < 16; k++ ) if( (uint32_t) k < left ) out[i0 + k] = (uint8_t) ( b[k >> 2] >> ( 8 * ( k & 3 ) ) );
+  }
+}
+void launch_output_narrow( hipStream_t s, OutputFrameParams p, NarrowArgs na, void* dst )
+{
+  int total = 0;
+  for( int c = 0; c < 3; c++ ) { p.first[c] = total; total += (int) ( ( ( (size_t) p.w[c] * p.h[c] + 15 ) / 16 + 255 ) / 256 ); }
+  if( total ) hipLaunchKernelGGL( k_output_narrow, dim3( total ), dim3( 256 ), 0, s, p, na, (uint8_t*) dst );
+}
+
 // k_output_rgb — a 4:2:0 frame of the output queue as planar R'G'B' (the definition: vvr.h): chroma to the luma grid with the 4-tap DCTIF in
 // sampleRateConvCore's two passes (horizontal sums unnormalised, ( sum + 2048 ) >> 12 and the clip after the vertical pass), then the Q14 matrix,
 // the clip and the store as bytes, 16-bit words, halves or floats in three planes, or as pixels of one interleaved plane (RGBA8 / BGRA8, RGB24 / BGR24,
@@ -5624,7 +5727,10 @@ __device__ __forceinline__ int yuv_vtaps( int jj, int ( &c )[4] )
   c[2] = COLY ? ( odd ? 36 : 0 ) : ( odd ? 16 : 54 ); c[3] = COLY ? ( odd ? -4 : 0 ) : ( odd ? -2 : -4 );
   return ( jj >> 1 ) + ( COLY || odd ? 1 : 0 );
 }
-template<int COL, int FMT, bool WHOLE>
+// the reduction of the four byte formats in a context of 9 or 10 bits (the NARROW variants; vvr_set_output_narrowing, the definition: vvr.h) on the
+// lane's unpacked samples, last before the store: v at an even and at an odd column of its plane in the row whose half of the cell is `cell`
+__device__ __forceinline__ int yuv_narrow( int v, bool odd, uint32_t cell, int s ) { return min( 255, ( v + (int) ( odd ? cell >> 16 : cell & 0xffff ) ) >> s ); }
+template<int COL, int FMT, bool WHOLE, bool NARROW>
 __device__ __forceinline__ void yuv_tile_444( const OutputYuvParams& p, uint8_t* __restrict__ dst )
 {
   __shared__ uint16_t yuv_raw[2][RGB_CH][RGB_CW];
@@ -5686,6 +5792,12 @@ __device__ __forceinline__ void yuv_tile_444( const OutputYuvParams& p, uint8_t*
     Y[i] = (int) ( ( y2 >> ( 16 * ( i & 1 ) ) ) & 0xffff ) << p.shift;
     UV[0][i] = clip3( 0, p.maxVal, ( UV[0][i] + 2048 ) >> 12 ) << p.shift; UV[1][i] = clip3( 0, p.maxVal, ( UV[1][i] + 2048 ) >> 12 ) << p.shift;
   }
+  if constexpr( NARROW )      // (x is a multiple of 8: sample i of the lane lies at a column of the parity of i, in all three planes)
+  {
+    const uint32_t cell = y & 1 ? p.narrow.cell[1] : p.narrow.cell[0];
+#pragma unroll
+    for( int i = 0; i < 8; i++ ) { Y[i] = yuv_narrow( Y[i], i & 1, cell, p.narrow.s ); UV[0][i] = yuv_narrow( UV[0][i], i & 1, cell, p.narrow.s ); UV[1][i] = yuv_narrow( UV[1][i], i & 1, cell, p.narrow.s ); }
+  }
   const size_t i0 = (size_t) y * p.w + x;
   uint8_t* __restrict__ o0 = p.direct[0] ? p.direct[0] : dst + p.dstOff[0];
   if( FMT == VVR_OUT_Y410 ) { rgb_store_px<VVR_OUT_RGB10A2, WHOLE>( o0, i0, UV[0], Y, UV[1], 0.f, n ); return; }      // (Cb | Y << 10 | Cr << 20 | 3 << 30)
@@ -5732,7 +5844,7 @@ __device__ __forceinline__ void yuv_vertical_422( const uint16_t* __restrict__ c
     out[i] = clip3( 0, maxVal, sum >> 6 ) << shift;
   }
 }
-template<bool COLY, int FMT, bool WHOLE>
+template<bool COLY, int FMT, bool WHOLE, bool NARROW>
 __device__ __forceinline__ void yuv_tile_422( const OutputYuvParams& p, uint8_t* __restrict__ dst )
 {
   constexpr int CW = RGB_TW / 2;
@@ -5754,6 +5866,14 @@ __device__ __forceinline__ void yuv_tile_422( const OutputYuvParams& p, uint8_t*
   {
     const uint32_t y2 = i < 2 ? yy.x : ( i < 4 ? yy.y : ( i < 6 ? yy.z : yy.w ) );
     Y[i] = (int) ( ( y2 >> ( 16 * ( i & 1 ) ) ) & 0xffff ) << p.shift;
+  }
+  if constexpr( NARROW )      // (x is a multiple of 8: luma sample i at a column of the parity of i, the chroma of pixel pair k at column ( x >> 1 ) + k of its plane)
+  {
+    const uint32_t cell = y & 1 ? p.narrow.cell[1] : p.narrow.cell[0];
+#pragma unroll
+    for( int i = 0; i < 8; i++ ) Y[i] = yuv_narrow( Y[i], i & 1, cell, p.narrow.s );
+#pragma unroll
+    for( int k = 0; k < 4; k++ ) { U[k] = yuv_narrow( U[k], k & 1, cell, p.narrow.s ); V[k] = yuv_narrow( V[k], k & 1, cell, p.narrow.s ); }
   }
   const size_t i0 = (size_t) y * p.w + x;
   uint8_t* __restrict__ o0 = p.direct[0] ? p.direct[0] : dst + p.dstOff[0];
@@ -5860,29 +5980,51 @@ __device__ __forceinline__ void yuv_tile_v210( const OutputYuvParams& p, uint8_t
       make_uint4( (uint32_t) U[0] | y0 << 10 | (uint32_t) V[0] << 20, y1 | (uint32_t) U[1] << 10 | y2 << 20, (uint32_t) V[1] | y3 << 10 | (uint32_t) U[2] << 20, y4 | (uint32_t) V[2] << 10 | y5 << 20 );
   }
 }
-// COL: the chroma position (4:2:2 and V210: bit 1 alone, instantiated with bit 0 clear); WHOLE: the kind of store (V210: true)
+// COL: the chroma position (4:2:2 and V210: bit 1 alone, instantiated with bit 0 clear); WHOLE: the kind of store (V210: true); NARROW: the four
+// byte formats in a context of 9 or 10 bits, the reduction at the store (the instantiations without it are what they were)
+__host__ __device__ constexpr bool yuv_is_bytes( int f ) { return f == VVR_OUT_YUV444P8 || f == VVR_OUT_YUV422P8 || f == VVR_OUT_UYVY || f == VVR_OUT_YUY2; }
 template<int COL, int FMT, bool WHOLE>
 __global__ __launch_bounds__( 256 ) void k_output_yuv( OutputYuvParams p, uint8_t* __restrict__ dst )
 {
-  if constexpr( yuv_is_444( FMT ) ) yuv_tile_444<COL, FMT, WHOLE>( p, dst );
+  if constexpr( yuv_is_444( FMT ) ) yuv_tile_444<COL, FMT, WHOLE, false>( p, dst );
   else if constexpr( FMT == VVR_OUT_V210 ) yuv_tile_v210<( COL & 2 ) != 0>( p, dst );
-  else yuv_tile_422<( COL & 2 ) != 0, FMT, WHOLE>( p, dst );
+  else yuv_tile_422<( COL & 2 ) != 0, FMT, WHOLE, false>( p, dst );
 }
-template<int FMT, bool WHOLE>
+// ... and the NARROW variants: an overload with the further parameter, so that the kernels above keep their names as well as their code
+template<int COL, int FMT, bool WHOLE, bool NARROW>
+__global__ __launch_bounds__( 256 ) void k_output_yuv( OutputYuvParams p, uint8_t* __restrict__ dst )
+{
+  static_assert( NARROW && yuv_is_bytes( FMT ), "the byte formats alone are narrowed" );
+  if constexpr( yuv_is_444( FMT ) ) yuv_tile_444<COL, FMT, WHOLE, true>( p, dst );
+  else yuv_tile_422<( COL & 2 ) != 0, FMT, WHOLE, true>( p, dst );
+}
+template<int COL, int FMT, bool WHOLE, bool NARROW>
+static void launch_output_yuv_at( hipStream_t s, dim3 grid, const OutputYuvParams& p, void* dst )
+{
+  if constexpr( NARROW ) hipLaunchKernelGGL( ( k_output_yuv<COL, FMT, WHOLE, true> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst );
+  else hipLaunchKernelGGL( ( k_output_yuv<COL, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst );
+}
+template<int FMT, bool WHOLE, bool NARROW = false>
 static void launch_output_yuv_as( hipStream_t s, const OutputYuvParams& p, void* dst )
 {
   const dim3 grid( ( p.w + ( FMT == VVR_OUT_V210 ? YUV_V210_TW : RGB_TW ) - 1 ) / ( FMT == VVR_OUT_V210 ? YUV_V210_TW : RGB_TW ), ( p.h + RGB_TH - 1 ) / RGB_TH );
   switch( p.collocated & ( yuv_is_444( FMT ) ? 3 : 2 ) )
   {
-  case 0:  hipLaunchKernelGGL( ( k_output_yuv<0, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  case 2:  hipLaunchKernelGGL( ( k_output_yuv<2, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  case 1:  if constexpr( yuv_is_444( FMT ) ) hipLaunchKernelGGL( ( k_output_yuv<1, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  default: if constexpr( yuv_is_444( FMT ) ) hipLaunchKernelGGL( ( k_output_yuv<3, FMT, WHOLE> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 0:  launch_output_yuv_at<0, FMT, WHOLE, NARROW>( s, grid, p, dst ); break;
+  case 2:  launch_output_yuv_at<2, FMT, WHOLE, NARROW>( s, grid, p, dst ); break;
+  case 1:  if constexpr( yuv_is_444( FMT ) ) launch_output_yuv_at<1, FMT, WHOLE, NARROW>( s, grid, p, dst ); break;
+  default: if constexpr( yuv_is_444( FMT ) ) launch_output_yuv_at<3, FMT, WHOLE, NARROW>( s, grid, p, dst ); break;
   }
 }
 template<int FMT>
 static void launch_output_yuv_fmt( hipStream_t s, const OutputYuvParams& p, void* dst )
 {
+  if constexpr( yuv_is_bytes( FMT ) )
+    if( p.narrow.s )
+    {
+      if( ( p.w & 7 ) == 0 ) launch_output_yuv_as<FMT, true, true>( s, p, dst ); else launch_output_yuv_as<FMT, false, true>( s, p, dst );
+      return;
+    }
   if( FMT == VVR_OUT_V210 || ( p.w & 7 ) == 0 ) launch_output_yuv_as<FMT, true>( s, p, dst );      // (rows of a multiple of 8 samples: every lane has 8, at an aligned address)
   else if constexpr( FMT != VVR_OUT_V210 ) launch_output_yuv_as<FMT, false>( s, p, dst );
 }

@@ -258,6 +258,26 @@ void launch_output_frame( hipStream_t, OutputFrameParams p, void* dst )
     }
 }
 
+// ... and launch_output_narrow (k_output_narrow): the definition of vvr_set_output_narrowing (vvr.h) sample by sample, in 32 bits - the word as it
+// lies, the constant of the cell at the sample's column and row in its own output plane (the Cb and the Cr of NV12's pair k: column k)
+namespace {
+uint8_t narrow_byte( uint32_t v, int i, int j, const NarrowArgs& na ) { return (uint8_t) std::min<uint32_t>( 255, ( v + ( i & 1 ? na.cell[j & 1] >> 16 : na.cell[j & 1] & 0xffff ) ) >> na.s ); }
+}
+void launch_output_narrow( hipStream_t, OutputFrameParams p, NarrowArgs na, void* dst )
+{
+  const bool semi = p.format == VVR_OUT_NV12;
+  for( int c = 0; c < 3; c++ )
+    for( int r = 0; r < ( p.w[c] ? p.h[c] : 0 ); r++ )
+    {
+      uint8_t* out = p.direct[c] ? p.direct[c] : (uint8_t*) dst + p.dstOff[c];
+      for( int x = 0; x < p.w[c]; x++ )
+      {
+        const int k = semi && c == 1 ? 1 + ( x & 1 ) : c, col = semi && c == 1 ? x >> 1 : x;
+        out[(size_t) r * p.w[c] + x] = narrow_byte( (uint16_t) p.src[k][(size_t) r * p.stride[k] + col], col, r, na );
+      }
+    }
+}
+
 // ... and launch_output_rgb (k_output_rgb): the definition of vvr.h sample by sample - positions, phases and taps from the table as launch_rescale
 // takes them (step 16, add 0 / -8, shift 0, the chroma filter), the matrix, the transform, the stores of the planar and the interleaved formats
 namespace {
@@ -416,7 +436,12 @@ void launch_output_yuv( hipStream_t, const OutputYuvParams& p, void* dst )
     if( f == VVR_OUT_V210 ) memset( out[0] + j * v210Row, 0, v210Row );      // (the fields of pixels that do not exist)
     for( int i = 0; i < p.w; i++ )
     {
-      const uint32_t y = luma( i, j ) << p.shift, u = (uint32_t) up[0][(size_t) j * uw + ( full ? i : i / 2 )] << p.shift, v = (uint32_t) up[1][(size_t) j * uw + ( full ? i : i / 2 )] << p.shift;
+      uint32_t y = luma( i, j ) << p.shift, u = (uint32_t) up[0][(size_t) j * uw + ( full ? i : i / 2 )] << p.shift, v = (uint32_t) up[1][(size_t) j * uw + ( full ? i : i / 2 )] << p.shift;
+      if( p.narrow.s )      // (the byte formats in a context of 9 or 10 bits: the chroma at its own column - of the pixel pair at 4:2:2)
+      {
+        const int ci = full ? i : i / 2;
+        y = narrow_byte( y, i, j, p.narrow ); u = narrow_byte( u, ci, j, p.narrow ); v = narrow_byte( v, ci, j, p.narrow );
+      }
       const size_t at = (size_t) j * p.w + i, cat = (size_t) j * uw + i / 2;
       switch( f )
       {
@@ -1111,13 +1136,14 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 
 // =====================================================================================================================
 // output queue: the output stage as a pipeline.  A request is ordered behind its picture's `done` event on the context's output stream,
-// runs there (k_film_grain, k_rescale, k_output_frame, k_output_rgb or k_output_yuv as the request needs them), leaves through a ring entry (device scratch + pinned
+// runs there (k_film_grain, k_rescale, k_output_frame, k_output_narrow, k_output_rgb or k_output_yuv as the request needs them), leaves through a ring entry (device scratch + pinned
 // staging) and is collected with its ticket.  Nothing here calls vvr_sync.  The slot is protected the way an external reader's is
 // (vvr_slot_external_event): the entry's `read` event, recorded behind the last kernel of the request, is registered with the slot, so a
 // picture submitted afterwards that overwrites the slot waits for it on the device - not for the copy to the host.
 // k_rescale and k_film_grain reach the packed format and the chained case with at most one extra pass through HBM: they store 16-bit samples
 // into the entry's scratch (`tmp`) and k_output_frame packs (or interleaves: NV12, P010) from there, or k_output_rgb converts from there (the RGB
-// formats; a plain request converts straight from the slot); into the planar formats they store directly as ever.
+// formats; a plain request converts straight from the slot); into the planar formats they store directly as ever - but for VVR_OUT_PLANAR8 of a
+// context of 9 or 10 bits (vvr_set_output_narrowing), which goes through 16-bit samples and k_output_narrow like VVR_OUT_NV12.
 // A request whose destination planes lie in device memory the context knows (vvr_device_alloc / vvr_device_register) moves nothing over PCIe:
 // k_output_frame stores a plane whose rows are back to back at a 32-byte aligned base straight into it, exactly its bytes; every other plane
 // (padded rows, odd bases, the planes k_film_grain / k_rescale store themselves) goes through the entry's scratch and one device-to-device
@@ -1308,8 +1334,9 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 && !rgb && !yuv ) return outRefuse( c, "unknown format" );
   if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1" );
   const bool packed = rq->format == VVR_OUT_PACKED10, semi = rq->format == VVR_OUT_NV12 || rq->format == VVR_OUT_P010, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
-  const bool viaTmp = packed || semi || rgb || yuv;      // k_output_frame / k_output_rgb / k_output_yuv makes the format: the stages before it store 16-bit samples into `tmp`
   const bool narrow = rq->format == VVR_OUT_PLANAR8 || rq->format == VVR_OUT_NV12 || yuv8;
+  const bool reduce = narrow && bd > 8;      // (accepted under a mode of vvr_set_output_narrowing alone: k_output_narrow or k_output_yuv reduces at its store)
+  const bool viaTmp = packed || semi || rgb || yuv || reduce;      // k_output_frame / k_output_narrow / k_output_rgb / k_output_yuv makes the format: the stages before it store 16-bit samples into `tmp`
   const int bps = narrow ? 1 : rgb ? px : 2, nOut = semi ? 2 : inter || yuvOne ? 1 : yuv ? 3 : nc;
   int outMatrix = 0, outFullRange = 0;      // (the colour description: looked at here for the refusal, taken under mu where the request is accepted)
   if( rgb )
@@ -1323,7 +1350,13 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( semi && nc == 1 ) return outRefuse( c, "semi-planar output of a 4:0:0 context: there is no chroma to interleave" );
   if( yuv && nc == 1 ) return outRefuse( c, "4:2:2 / 4:4:4 output of a 4:0:0 context: there is no chroma to upsample" );
   if( rq->format == VVR_OUT_P010 && ( bd < 8 || bd > 10 ) ) return outRefuse( c, "P010 output needs a bit depth of 8, 9 or 10" );
-  if( narrow && bd > 8 ) return outRefuse( c, "8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)" );
+  static const char* const noNarrowing = "8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)";
+  int outNarrow = 0, outNarrowPhase = 0;      // (the narrowing: looked at here for the refusal, taken under mu where the request is accepted)
+  if( reduce )
+  {
+    { std::lock_guard<std::mutex> lk( c->mu ); outNarrow = c->outNarrow; }
+    if( !outNarrow || bd > 10 ) return outRefuse( c, noNarrowing );
+  }
   if( packed && bd != 8 && bd != 10 ) return outRefuse( c, "packed 10-bit output needs a bit depth of 8 or 10 (vvdecHelper.h:106-248)" );
   if( yuv && ( bd < 8 || bd > 10 ) ) return outRefuse( c, "4:2:2 / 4:4:4 output needs a bit depth of 8, 9 or 10" );
   if( yuv && scaled && ( ( rq->out_w | rq->out_h ) & 1 ) ) return outRefuse( c, "4:2:2 / 4:4:4 output needs an even out_w and out_h (one 4:2:0 frame is upsampled)" );
@@ -1377,6 +1410,23 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( devPlanes && devPlanes != nOut ) { c->setError( "vvr_output_submit: destination planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
   const bool devDst = devPlanes != 0;
   if( rgb ) { outMatrix = c->outMatrix; outFullRange = c->outFullRange; }      // (what is set now, behind the waits above: a description cannot be unset)
+  // the narrowing the request takes: the one that is set now (it can be unset: the request is refused then, no entry has been taken); the four
+  // constants of the 2 x 2 cell, the phase folded in, go with the request as kernel arguments - the three modes are one kernel path
+  NarrowArgs na; memset( &na, 0, sizeof( na ) );
+  if( reduce )
+  {
+    outNarrow = c->outNarrow; outNarrowPhase = c->outNarrowPhase;
+    if( !outNarrow ) { c->setError( std::string( who ) + ": " + noNarrowing ); return VVR_ERR_PARAMETER; }
+    static const int M[2][2] = { { 0, 2 }, { 3, 1 } };
+    na.s = bd - 8; na.maxVal = ( 1 << bd ) - 1;
+    for( int j = 0; j < 2; j++ )
+    {
+      uint32_t a[2];
+      for( int i = 0; i < 2; i++ )
+        a[i] = outNarrow == VVR_NARROW_TRUNCATE ? 0 : outNarrow == VVR_NARROW_ROUND ? 1u << ( na.s - 1 ) : (uint32_t) M[( j + ( outNarrowPhase >> 1 & 1 ) ) & 1][( i + ( outNarrowPhase & 1 ) ) & 1] >> ( 2 - na.s );
+      na.cell[j] = a[0] | a[1] << 16;
+    }
+  }
   // the colour transform the request takes: the one that is set now.  Its matrix goes with the request as kernel arguments; its tables, when
   // they have changed, are refreshed on the output stream ahead of the request's kernel - behind the kernels of the requests in flight
   const bool xf = rgb && c->xform, xfUpload = xf && c->xformStale;
@@ -1479,8 +1529,8 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   fp.format = rq->format; fp.shift = packed ? 10 - bd : ( rq->format == VVR_OUT_P010 ? 16 - bd : 0 );
   if( frameBytes > 0 )
   {
-    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_FRAME, frameBytes );
-    launch_output_frame( s, fp, e->dev );
+    outTimeBegin( c, s, e->timed, e->timing, reduce ? K_OUTPUT_NARROW : K_OUTPUT_FRAME, frameBytes );
+    if( reduce ) launch_output_narrow( s, fp, na, e->dev ); else launch_output_frame( s, fp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
   }
   if( rgb )
@@ -1529,6 +1579,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     for( int k = 0; k < nOut; k++ ) written += (double) rowBytes[k] * outRows[k];
     yp.w = ow[0]; yp.h = oh[0]; yp.collocated = rq->collocated & 3; yp.format = rq->format; yp.maxVal = ( 1 << bd ) - 1;
     yp.shift = rq->format == VVR_OUT_Y210 ? 16 - bd : rq->format == VVR_OUT_V210 || rq->format == VVR_OUT_Y410 ? 10 - bd : 0;
+    yp.narrow = na;      // (s == 0 unless a byte format leaves a context of 9 or 10 bits: the kernel's NARROW variants, counted under k_output_yuv)
     outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_YUV, (double) yp.w * yp.h * 3. + written );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma; written: the planes)
     launch_output_yuv( s, yp, e->dev );
     if( e->timed ) hipEventRecord( e->timing.b, s );
