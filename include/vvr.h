@@ -859,7 +859,7 @@ VVR_API int          vvr_hash_submit(vvr_context* ctx, const vvr_hash_request* r
  *   VVR_STATS_LUMA  hist_y alone; hist_maxrgb, max_c and min_c are 0.  Works in every context, 4:0:0 included.
  *   bins     at 2^bd and above: 0.  samples = width * height; both histograms sum to it (hist_maxrgb in RGB mode).
  *   ticket and ring, ordering   everything said about a hash request above holds: the ticket comes from the same ticket space and the same 8 ring
- *            entries (VVR_ERR_BUSY counts every kind of request: output, hash, statistics, comparison, SSIM); vvr_output_test / vvr_output_wait collect it; vvr_output_stream_wait means
+ *            entries (VVR_ERR_BUSY counts every kind of request: output, hash, statistics, comparison, SSIM, MS-SSIM); vvr_output_test / vvr_output_wait collect it; vvr_output_stream_wait means
  *            "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the request runs on the output
  *            stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1); pictures submitted afterwards
  *            that overwrite the slot wait for the request's kernels on the device; blocking == 0: VVR_NOT_READY while `job` has not been handed
@@ -937,7 +937,7 @@ VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_
  *            the output stream; it must stay untouched until vvr_output_wait has returned.  Any other host memory: copied inside vvr_compare_submit
  *            into the entry's pinned staging, as `expected` of a hash request is: the caller's buffers are free again when the call returns.
  *   ticket and ring, ordering   everything said about a hash or statistics request above holds: the ticket comes from the same ticket space and the
- *            same 8 ring entries (VVR_ERR_BUSY counts all five kinds of request); vvr_output_test / vvr_output_wait collect it;
+ *            same 8 ring entries (VVR_ERR_BUSY counts all six kinds of request); vvr_output_test / vvr_output_wait collect it;
  *            vvr_output_stream_wait means "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the
  *            request runs on the output stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1);
  *            ref_slot is taken as all work submitted so far leaves it (the job == -1 rule, whatever `job` is); the request is a reader of both slots:
@@ -949,7 +949,7 @@ VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_
  * ref_slot == slot, job < -1, result == NULL, a window outside the picture, empty, or odd in a 4:2:0 context, pictures of different sizes in the two
  * slots; without ref_slot: ref_bytes_per_sample other than 1 or 2, a NULL plane among those the context has, a stride below the row, device planes
  * mixed with host planes, a plane partly inside a device range.
- * Not offered here: SSIM is a request of its own (vvr_ssim_submit, below); grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
+ * Not offered here: SSIM and MS-SSIM are requests of their own (vvr_ssim_submit, vvr_msssim_submit, below); grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
  * a reference of another size than the window. */
 typedef struct vvr_frame_compare {
   uint32_t struct_size;            /* sizeof( vvr_frame_compare ), written with the rest */
@@ -1013,11 +1013,11 @@ VVR_API int          vvr_compare_psnr(const vvr_frame_compare* cmp, double peak,
  *   map      NULL, or ceil( w / 64 ) * ceil( h / 64 ) words, row-major: the smallest v over the windows of all components whose ORIGIN sample lies in
  *            that block of 64 x 64 luma samples; a chroma origin ( i, j ) belongs to the block of ( 2 i, 2 j ); 0x7fffffff where no origin falls into
  *            the block (a last block 4 samples wide, for one).
- *   where the reference may lie, ticket and ring, ordering, result   everything said for a comparison request above holds (VVR_ERR_BUSY counts all five
+ *   where the reference may lie, ticket and ring, ordering, result   everything said for a comparison request above holds (VVR_ERR_BUSY counts all six
  *            kinds of request); the film grain seed chain and the colour description are not touched.
  * Refused (VVR_ERR_PARAMETER with a text that names vvr_ssim_submit, no ring entry taken): everything vvr_compare_submit refuses, struct_size being
  * sizeof( vvr_ssim_request ), and a window with w < 8 or h < 8.
- * Not offered: MS-SSIM, Gaussian windows; grained or rescaled frames; results left in device memory; a reference of another size than the window. */
+ * Not offered here: MS-SSIM is a request of its own (vvr_msssim_submit, below).  Not offered: Gaussian windows; grained or rescaled frames; results left in device memory; a reference of another size than the window. */
 typedef struct vvr_frame_ssim {
   uint32_t struct_size;            /* sizeof( vvr_frame_ssim ), written with the rest */
   uint32_t bit_depth;              /* the context's */
@@ -1052,6 +1052,68 @@ VVR_API int          vvr_ssim_submit(vvr_context* ctx, const vvr_ssim_request* r
  * (VVR_ERR_PARAMETER, ssim untouched): a NULL pointer, a struct_size other than sizeof( vvr_frame_ssim ), a bit depth outside 8..10,
  * windows[0] == 0. */
 VVR_API int          vvr_compare_ssim(const vvr_frame_ssim* s, double ssim[4]);
+/* MS-SSIM of a picture against a reference frame as a request of the output queue: the third number of a transcoder's quality loop.  The pyramid
+ * is built and every level is reduced on the device; scales x components x 4 words cross PCIe.  Everything not said here is exactly as for
+ * vvr_ssim_submit: the window and the components' windows in 4:2:0, the reference planes that ARE the window, ref_slot, where the reference may lie,
+ * ticket and ring (VVR_ERR_BUSY counts all six kinds of request), ordering, the reader of both slots; a failed job fails the request and leaves
+ * *result untouched.  The result is integers, defined here to the bit:
+ *   level 0  x_0 = min( slot word, L ), y_0 = min( reference byte or little-endian word, L ), L = 2^bit_depth - 1; its size is the component's
+ *            window, w_0 x h_0.
+ *   level k + 1 from level k, for both images alike: its size is ( w_k >> 1 ) x ( h_k >> 1 ), and the sample ( i, j ) is
+ *            ( a( 2 i, 2 j ) + a( 2 i + 1, 2 j ) + a( 2 i, 2 j + 1 ) + a( 2 i + 1, 2 j + 1 ) + 2 ) >> 2: the rounded mean of 2 x 2 samples.  A last odd
+ *            column or row is dropped.  The clamp happens once, at level 0, before any averaging; level samples never exceed L.
+ *   per level k and component c   SSIM windows of 8 x 8 samples at a stride of 4 over the level's plane: windows_x, windows_y by vvr_ssim_submit's
+ *            formula applied to w_k, h_k; per window l, c and v are vvr_ssim_submit's, unchanged - the same C1, C2, N = 64, the same truncating
+ *            64-bit divisions, the same bounds on every intermediate.  Reported: width, height (w_k, h_k), windows_x, windows_y,
+ *            windows = windows_x * windows_y, sum_cs: the sum of c, the contrast-structure quotient ( A2 * 16777216 ) / B2 in Q24, and sum_v: the
+ *            sum of v.  Indices are [level][component]; the entries of levels >= scales and of the components a 4:0:0 context lacks are 0.
+ *   Two consequences.  (a) With scales == 1, sum_v[0] and windows[0] equal `sum` and `windows` of a vvr_ssim_submit request of the same window,
+ *            exactly.  (b) A sample of a level that lies outside the whole 4 x 4 cells of its plane (column >= 4 * ( w_k / 4 ) or row
+ *            >= 4 * ( h_k / 4 )) reaches neither a window of that level nor a window of any deeper level: the windows of a level cover a multiple
+ *            of 4 columns that does not exceed w_k, and 8 * ( w_{k+1} / 4 ) <= 4 * ( w_k / 4 ).  (An implementation may build level k + 1 from
+ *            whole cells of level k only and leave the never-read last samples of its scratch planes unwritten.)
+ * Refused (VVR_ERR_PARAMETER with a text that names vvr_msssim_submit, no ring entry taken): everything vvr_compare_submit refuses, struct_size being
+ * sizeof( vvr_msssim_request ); scales outside 1 .. VVR_MSSSIM_MAX_SCALES; a request in which some component of the context has no window at the
+ * last level: ( w_c >> ( scales - 1 ) ) < 8 or ( h_c >> ( scales - 1 ) ) < 8, with w_c = w >> 1, h_c = h >> 1 for chroma in 4:2:0.  So five scales need
+ * a window of 256 x 256 in 4:2:0 and of 128 x 128 in 4:0:0; a smaller window takes fewer scales.
+ * Not offered: a map or a minimum (where a picture is worst is vvr_ssim_submit's answer); Gaussian windows; another pyramid filter than the 2 x 2
+ * mean; grained or rescaled frames; results left in device memory; a reference of another size than the window. */
+#define VVR_MSSSIM_MAX_SCALES 5
+typedef struct vvr_frame_msssim {
+  uint32_t struct_size;            /* sizeof( vvr_frame_msssim ), written with the rest */
+  uint32_t bit_depth;              /* the context's */
+  uint32_t num_components;         /* 1 (4:0:0) or 3 */
+  uint32_t scales;                 /* the request's */
+  uint32_t width[VVR_MSSSIM_MAX_SCALES][3], height[VVR_MSSSIM_MAX_SCALES][3];      /* the level's plane per component */
+  uint32_t windows_x[VVR_MSSSIM_MAX_SCALES][3], windows_y[VVR_MSSSIM_MAX_SCALES][3];
+  uint64_t windows[VVR_MSSSIM_MAX_SCALES][3];      /* windows_x * windows_y */
+  int64_t  sum_cs[VVR_MSSSIM_MAX_SCALES][3];       /* sum of c */
+  int64_t  sum_v[VVR_MSSSIM_MAX_SCALES][3];        /* sum of v */
+} vvr_frame_msssim;                /* 616 bytes */
+typedef struct vvr_msssim_request { /* a vvr_ssim_request with `scales` where pad[0] was, and no map */
+  uint32_t struct_size;            /* sizeof( vvr_msssim_request ) */
+  int32_t  slot;
+  int32_t  job;                    /* as vvr_output_request.job */
+  int32_t  x, y, w, h;             /* window, luma samples (even in 4:2:0) */
+  int32_t  ref_slot;               /* >= 0: the reference is the same window of that slot; -1: ref[] below */
+  uint8_t  ref_bytes_per_sample;   /* 1 or 2 (little endian); ignored with ref_slot */
+  uint8_t  blocking;               /* as vvr_output_request.blocking */
+  uint8_t  scales;                 /* 1 .. VVR_MSSSIM_MAX_SCALES */
+  uint8_t  pad;
+  uint32_t pad2;
+  const void* ref[3];              /* planes of the WINDOW's size (not the picture's); ref[1], ref[2] unused in 4:0:0 */
+  size_t   ref_stride_bytes[3];
+  vvr_frame_msssim* result;        /* written by vvr_output_wait; must stay valid until it has returned */
+} vvr_msssim_request;              /* 96 bytes */
+VVR_API int          vvr_msssim_submit(vvr_context* ctx, const vvr_msssim_request* req);
+/* MS-SSIM from the sums of an MS-SSIM request; a pure host function, no context, in double.  Per component c: m_k = sum_cs[k][c] /
+ * ( windows[k][c] * 2^24 ) for k < scales - 1, m_last = sum_v[scales - 1][c] / ( windows[scales - 1][c] * 2^24 ); msssim[c] = the product over k, in
+ * ascending order, of pow( max( m_k, 0 ), weights[k] ).  msssim[3]: the same formula on sum_cs, sum_v and windows summed over the components, per
+ * level.  Components that do not exist (or, in sums built by hand, lack windows at one of the levels) give 0.  weights == NULL: the first `scales` of 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 (Wang et al. 2003)
+ * divided by their sum; a caller's weights are used as given, `scales` of them.  Refused (VVR_ERR_PARAMETER, msssim untouched): a NULL s or msssim,
+ * a struct_size other than sizeof( vvr_frame_msssim ), a bit depth outside 8..10, scales outside 1 .. 5, windows[k][0] == 0 for some k < scales,
+ * a weight that is negative or not finite. */
+VVR_API int          vvr_compare_msssim(const vvr_frame_msssim* s, const double* weights, double msssim[4]);
 /* the finished picture in `slot` (every plane, at the picture's size) into the caller's buffers - what a decoder does with each picture it hands to
  * the application (the planes of a vvdecFrame live in the Picture's own buffers, vvdecimpl.cpp:1058).  Waits for NOTHING: the caller has waited for
  * the picture (vvr_wait); other pictures in flight are not held up (vvr_read_plane drains the context).  Each plane crosses PCIe in one transfer

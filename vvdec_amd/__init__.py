@@ -126,6 +126,10 @@ def lib():
         L.vvr_ssim_submit.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_compare_ssim.restype = C.c_int
         L.vvr_compare_ssim.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_msssim_submit.restype = C.c_int
+        L.vvr_msssim_submit.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_compare_msssim.restype = C.c_int
+        L.vvr_compare_msssim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vvr_output_stream_wait.restype = C.c_int
         L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vvr_device_alloc.restype = C.c_void_p
@@ -146,7 +150,7 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
                     "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit", "vvr_stats_submit", "vvr_light_level",
-                    "vvr_compare_submit", "vvr_compare_psnr", "vvr_ssim_submit", "vvr_compare_ssim",
+                    "vvr_compare_submit", "vvr_compare_psnr", "vvr_ssim_submit", "vvr_compare_ssim", "vvr_msssim_submit", "vvr_compare_msssim",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
 
 
@@ -754,6 +758,28 @@ class Reconstructor:
         out["min_at"] = [(raw.min_x[c], raw.min_y[c]) if raw.windows[c] else None for c in range(nc)]
         if with_map:
             out["map"] = blocks
+        return out
+
+    def msssim(self, slot, ref, window=None, job=None, scales=5, weights=None):
+        """vvr_msssim_submit and vvr_output_wait: MS-SSIM of the window of `slot` against a reference frame over `scales` levels (1 .. 5), the
+        pyramid of 2 x 2 rounded means built and every level reduced on the device (integers defined in vvr.h) -> dict: `msssim` [Y, Cb, Cr,
+        all components together] as floats (vvr_compare_msssim with `weights`: None, Wang et al.'s normalised to the scales taken, or `scales`
+        non-negative numbers), per-level lists of per-component lists width, height, windows, sum_cs, sum_v (Q24 sums), scales, bit_depth,
+        num_components, `raw` (the abi.FrameMsssim).  slot, ref, window, job: as compare()."""
+        win = tuple(window or (0, 0, self.width, self.height))
+        nc = 3 if self.chroma_format else 1
+        raw = abi.FrameMsssim()
+        self._against_reference("msssim", slot, ref, win, job, lambda s, j, w, r, res, _: abi.msssim_request(s, j, w, r, res, scales), self.L.vvr_msssim_submit, raw, None)
+        if weights is not None:
+            if len(weights) != scales:
+                raise ValueError("msssim: %d weights for %d scales" % (len(weights), scales))
+            weights = (C.c_double * scales)(*weights)
+        value = (C.c_double * 4)()
+        if self.L.vvr_compare_msssim(C.byref(raw), weights, value) != abi.VVR_OK:
+            raise VvrError("vvr_compare_msssim: a result of vvr_msssim_submit, and weights that are finite and not negative")
+        out = dict(raw=raw, bit_depth=raw.bit_depth, num_components=raw.num_components, scales=raw.scales, msssim=list(value))
+        for name in ("width", "height", "windows", "sum_cs", "sum_v"):
+            out[name] = [[int(v) for v in getattr(raw, name)[k]][:nc] for k in range(raw.scales)]
         return out
 
     def write_picture(self, slot, planes):

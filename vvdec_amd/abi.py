@@ -390,5 +390,32 @@ def ssim_request(slot, job, window, ref, result, map_=None, blocking=True, ref_b
     return r
 
 
+MSSSIM_MAX_SCALES = 5
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang et al. 2003; vvr_compare_msssim divides the first `scales` by their sum
+
+
+class FrameMsssim(C.Structure):
+    """vvr_frame_msssim: what vvr_output_wait writes for an MS-SSIM request (vvr_msssim_submit, vvr.h); indices are [level][component]"""
+    _fields_ = [("struct_size", u32), ("bit_depth", u32), ("num_components", u32), ("scales", u32),
+                ("width", u32 * 3 * 5), ("height", u32 * 3 * 5), ("windows_x", u32 * 3 * 5), ("windows_y", u32 * 3 * 5),
+                ("windows", u64 * 3 * 5), ("sum_cs", C.c_int64 * 3 * 5), ("sum_v", C.c_int64 * 3 * 5)]
+
+
+class MsssimRequest(C.Structure):
+    """vvr_msssim_request: MS-SSIM of a picture against a reference frame as a request of the output queue (vvr_msssim_submit, vvr.h): an
+    SsimRequest with `scales` where its first pad byte was, and no map"""
+    _fields_ = [("struct_size", u32), ("slot", i32), ("job", i32), ("x", i32), ("y", i32), ("w", i32), ("h", i32), ("ref_slot", i32),
+                ("ref_bytes_per_sample", u8), ("blocking", u8), ("scales", u8), ("pad", u8), ("pad2", u32),
+                ("ref", C.c_void_p * 3), ("ref_stride_bytes", C.c_size_t * 3), ("result", C.c_void_p)]
+
+
+def msssim_request(slot, job, window, ref, result, scales=5, blocking=True, ref_bytes_per_sample=2):
+    """an MsssimRequest of `scales` levels that writes into `result` (a FrameMsssim); everything else as compare_request"""
+    c = compare_request(slot, job, window, ref, result, None, blocking, ref_bytes_per_sample)
+    r = MsssimRequest.from_buffer_copy(bytes(c)[:C.sizeof(MsssimRequest)])
+    r.struct_size, r.scales = C.sizeof(MsssimRequest), scales
+    return r
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]

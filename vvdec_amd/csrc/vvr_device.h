@@ -349,6 +349,22 @@ void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks,
 #define SSIM_NO_WINDOW 0xffffffffffffffffull
 void launch_output_ssim( hipStream_t s, const CompareParams& p, int bitDepth, uint32_t* recs, int32_t* map );
 void launch_output_ssim_sum( hipStream_t s, const uint32_t* recs, int blocks, int numComp, uint32_t* out );
+// MS-SSIM of a picture against a reference frame (vvr_msssim_submit, the definition: vvr.h): a launch per level on the SSIM request's blocks, then
+// one fold.  launch_output_msssim: p describes ONE level - level 0 as launch_output_ssim takes it, a deeper level with src and ref pointing to the
+// level's two scratch planes (16-bit words, refBytes 2, rows a multiple of 16 bytes: the wide class) - and recs[( c * nbx * nby + b ) *
+// MSSSIM_REC_WORDS ..] = the record of component c in block b: the sum of c, the contrast-structure quotient, then the sum of v, both 64 bits, low
+// word first; every word is stored, nothing has to be cleared.  next != NULL: the launch also writes level k + 1 of both images, the 2 x 2 rounded
+// means of the clamped samples, into next->x[c] (the slot's side) and next->y[c] (the reference's), rows of next->stride[c] samples (a multiple of
+// 8, the bases at a multiple of 16 bytes) - from the whole 4 x 4 cells of level k only: sample ( i, j ) of level k + 1 is written for
+// i < 2 * ( w_k / 4 ) and j < 2 * ( h_k / 4 ), which is all a window of level k + 1 or deeper reads.  launch_output_msssim_sum: a launch for all
+// levels, out[( k * numComp + c ) * MSSSIM_OUT_WORDS ..] = the two sums over the blocks[k] blocks of level k, whose records start at recs + recOff[k].
+#define MSSSIM_REC_WORDS 4
+#define MSSSIM_OUT_WORDS 4
+#define MSSSIM_MAX_SCALES 5
+struct MsssimNext { uint16_t* x[3]; uint16_t* y[3]; int stride[3]; };
+struct MsssimFold { int scales, recOff[MSSSIM_MAX_SCALES], blocks[MSSSIM_MAX_SCALES]; };      // recOff: in words, a multiple of 64
+void launch_output_msssim( hipStream_t s, const CompareParams& p, int bitDepth, uint32_t* recs, const MsssimNext* next );
+void launch_output_msssim_sum( hipStream_t s, const uint32_t* recs, const MsssimFold& f, int numComp, uint32_t* out );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.
 // launch_hash_rows: one launch over the rows of all planes, rows[g] = the CRC piece (the row's bytes mod P, register from 0) or the checksum share
 // of row g (the planes' rows one after the other).  launch_hash_combine: out[c] = the component's digest as a number - the checksum, or the CRC

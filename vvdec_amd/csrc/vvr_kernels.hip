@@ -6466,6 +6466,176 @@ void launch_output_ssim_sum( hipStream_t s, const uint32_t* recs, int blocks, in
   hipLaunchKernelGGL( k_output_ssim_sum, dim3( numComp ), dim3( 256 ), 0, s, recs, blocks, out );
 }
 
+// k_output_msssim — one level of an MS-SSIM request (vvr_msssim_submit, the definition: vvr.h) on k_output_ssim's decomposition: the same blocks,
+// the same 243 stage-1 tasks and ssim_load's loading rule (whole cells inside the level's plane only), the same window per lane in stage 2.  Two
+// differences.  Stage 2 keeps the contrast-structure quotient c beside v and the workgroup stores, per component, ONE record of two 64-bit sums
+// (the sum of c, the sum of v, low words first): no key, no map word, every word stored once, no atomics.  And with EMIT (every level but the
+// last) the lane that holds a pair of the block's OWN cells in registers - never a halo cell: the neighbouring block stores that one - forms the
+// 2 x 2 rounded means of both images, clamped first, and stores them as 16-bit words into the next level's two planes: two rows of four samples,
+// 8 bytes each, at ( i0 / 2, j0 / 2 ) - i0 is a multiple of 8 and the planes' rows a multiple of 16 bytes, so the stores are aligned; a lane whose
+// second cell is not wholly inside the plane stores 4 bytes.  By consequence (b) of the definition the samples that no whole cell gives are never
+// read.  The deeper levels read both images from those planes as 16-bit words: always the wide class with RB == 2.
+struct MsAcc { int64_t cs, v; };
+template<int RB>
+__device__ __forceinline__ void msssim_emit( const SsimRows& q, uint32_t top, uint16_t* __restrict__ x, uint16_t* __restrict__ y, int stride, int cells )
+{
+#pragma unroll
+  for( int r = 0; r < 4; r += 2 )
+  {
+    uint32_t ma[4], mb[4];
+#pragma unroll
+    for( int i = 0; i < 4; i++ )
+    {
+      uint32_t sa = 2, sb = 2;
+#pragma unroll
+      for( int n = 0; n < 4; n++ )
+      {
+        const int rr = r + ( n >> 1 ), ii = 2 * i + ( n & 1 );
+        const uint32_t wa[4] = { q.a[rr].x, q.a[rr].y, q.a[rr].z, q.a[rr].w }, wb[4] = { q.b[rr].x, q.b[rr].y, q.b[rr].z, q.b[rr].w };
+        sa += min( ( wa[ii >> 1] >> ( 16 * ( ii & 1 ) ) ) & 0xffffu, top );
+        sb += min( RB == 2 ? ( wb[ii >> 1] >> ( 16 * ( ii & 1 ) ) ) & 0xffffu : ( wb[ii >> 2] >> ( 8 * ( ii & 3 ) ) ) & 0xffu, top );
+      }
+      ma[i] = sa >> 2; mb[i] = sb >> 2;
+    }
+    uint16_t* __restrict__ dx = x + (size_t) ( r >> 1 ) * stride; uint16_t* __restrict__ dy = y + (size_t) ( r >> 1 ) * stride;
+    const uint2 vx = make_uint2( ma[0] | ma[1] << 16, ma[2] | ma[3] << 16 ), vy = make_uint2( mb[0] | mb[1] << 16, mb[2] | mb[3] << 16 );
+    if( cells == 2 ) { *(uint2*) dx = vx; *(uint2*) dy = vy; }
+    else { *(uint32_t*) dx = vx.x; *(uint32_t*) dy = vy.x; }
+  }
+}
+// c and v of the window whose top left cell is `at` in a grid of `pitch` cells a row: vvr.h line by line (ssim_window, keeping c)
+__device__ __forceinline__ MsAcc msssim_window( const uint32_t ( *cell )[SSIM_CELLS], int at, int pitch, int64_t C1, int64_t C2 )
+{
+  uint32_t t[5];
+#pragma unroll
+  for( int n = 0; n < 5; n++ ) t[n] = cell[n][at] + cell[n][at + 1] + cell[n][at + pitch] + cell[n][at + pitch + 1];
+  const int64_t s1 = t[0], s2 = t[1], sxx = t[2], syy = t[3], sxy = t[4];
+  const int64_t A1 = 2 * s1 * s2 + C1, B1 = s1 * s1 + s2 * s2 + C1;
+  const int64_t A2 = 2 * ( 64 * sxy - s1 * s2 ) + C2, B2 = ( 64 * sxx - s1 * s1 ) + ( 64 * syy - s2 * s2 ) + C2;
+  const int64_t l = ( A1 * 16777216 ) / B1, c = ( A2 * 16777216 ) / B2;
+  const MsAcc a = { c, ( l * c ) / 16777216 };
+  return a;
+}
+__device__ __forceinline__ int64_t msssim_wave( int64_t v )      // the sum over the wavefront, in every lane
+{
+  uint64_t u = (uint64_t) v;
+#pragma unroll
+  for( int d = 1; d < 64; d <<= 1 )
+  {
+    const uint32_t lo = (uint32_t) __shfl_xor( (int) (uint32_t) u, d ), hi = (uint32_t) __shfl_xor( (int) (uint32_t) ( u >> 32 ), d );
+    u += lo | (uint64_t) hi << 32;
+  }
+  return (int64_t) u;
+}
+template<int RB, bool BYSAMPLE, bool EMIT>
+__global__ __launch_bounds__( 256 ) void k_output_msssim( CompareParams p, MsssimNext nx, int bitDepth, uint32_t* __restrict__ recs )
+{
+  __shared__ uint32_t cell[5][SSIM_CELLS];
+  __shared__ uint32_t part[4][2][MSSSIM_REC_WORDS];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int X0 = blockIdx.x * 64, Y0 = blockIdx.y * 64;
+  // ---- stage 1: the lane's pair of cells, as k_output_ssim assigns them
+  const bool luma = tid < 153;
+  const int t = luma ? tid : ( tid - 153 ) % 45, perRow = luma ? 9 : 5, pitch = luma ? 17 : 9;
+  const int c = luma ? 0 : tid < 198 ? 1 : tid < 243 ? 2 : 3, sh = luma ? 0 : 1;      // (3: no task)
+  const int cr = t / perRow, pp = t % perRow, wanted = pp == perRow - 1 ? 1 : 2;
+  const int i0 = ( X0 >> sh ) + pp * 8, j0 = ( Y0 >> sh ) + cr * 4;
+  const SsimRows q = ssim_load<RB, BYSAMPLE>( p, c, i0, j0, wanted );
+  const uint32_t top = ( 1u << bitDepth ) - 1;
+  if( EMIT && c < p.numComp && wanted == 2 && cr < perRow * 2 - 2 && j0 + 4 <= p.h[c] )      // (the block's own 16 x 16 or 8 x 8 cells, wholly inside the plane)
+  {
+    const int inside = min( 2, ( p.w[c] - i0 ) >> 2 );
+    if( inside > 0 ) msssim_emit<RB>( q, top, nx.x[c] + (size_t) ( j0 >> 1 ) * nx.stride[c] + ( i0 >> 1 ), nx.y[c] + (size_t) ( j0 >> 1 ) * nx.stride[c] + ( i0 >> 1 ), nx.stride[c], inside );
+  }
+  uint32_t s[2][5];
+  ssim_cells<RB>( q, top, s );
+  if( c < 3 )
+  {
+    const int at = ( luma ? 0 : SSIM_LUMA_CELLS + ( c - 1 ) * SSIM_CHROMA_CELLS ) + cr * pitch + 2 * pp;
+#pragma unroll
+    for( int n = 0; n < 5; n++ ) { cell[n][at] = s[0][n]; if( wanted == 2 ) cell[n][at + 1] = s[1][n]; }
+  }
+  __syncthreads();
+  // ---- stage 2: a luma window per lane, a chroma window per lane of wavefronts 0 (Cb) and 1 (Cr)
+  const int64_t L = top, C1 = ( L * L * 4096 + 5000 ) / 10000, C2 = ( 9 * L * L * 4096 + 5000 ) / 10000;
+  MsAcc lum = { 0, 0 }, chr = { 0, 0 };
+  {
+    const int wi = tid & 15, wj = tid >> 4, gx = X0 + 4 * wi, gy = Y0 + 4 * wj;
+    if( gx + 8 <= p.w[0] && gy + 8 <= p.h[0] ) lum = msssim_window( cell, wj * 17 + wi, 17, C1, C2 );
+  }
+  if( wave < 2 && p.numComp > 1 )
+  {
+    const int k = 1 + wave, wi = tid & 7, wj = ( tid >> 3 ) & 7, gx = ( X0 >> 1 ) + 4 * wi, gy = ( Y0 >> 1 ) + 4 * wj;
+    if( gx + 8 <= p.w[k] && gy + 8 <= p.h[k] ) chr = msssim_window( cell, SSIM_LUMA_CELLS + wave * SSIM_CHROMA_CELLS + wj * 9 + wi, 9, C1, C2 );
+  }
+  lum.cs = msssim_wave( lum.cs ); lum.v = msssim_wave( lum.v ); chr.cs = msssim_wave( chr.cs ); chr.v = msssim_wave( chr.v );
+  if( ( tid & 63 ) == 0 )
+  {
+    uint32_t* l = part[wave][0]; uint32_t* k = part[wave][1];
+    l[0] = (uint32_t) (uint64_t) lum.cs; l[1] = (uint32_t) ( (uint64_t) lum.cs >> 32 ); l[2] = (uint32_t) (uint64_t) lum.v; l[3] = (uint32_t) ( (uint64_t) lum.v >> 32 );
+    k[0] = (uint32_t) (uint64_t) chr.cs; k[1] = (uint32_t) ( (uint64_t) chr.cs >> 32 ); k[2] = (uint32_t) (uint64_t) chr.v; k[3] = (uint32_t) ( (uint64_t) chr.v >> 32 );
+  }
+  __syncthreads();
+  if( tid >= p.numComp ) return;
+  // lane c folds component c: luma from the four wavefronts, Cb from wavefront 0, Cr from wavefront 1
+  const int w0 = tid == 2 ? 1 : 0, w1 = tid == 0 ? 4 : w0 + 1, set = tid ? 1 : 0;
+  uint64_t cs = 0, v = 0;      // (two's complement)
+  for( int w = w0; w < w1; w++ )
+  {
+    const uint32_t* u = part[w][set];
+    cs += u[0] | (uint64_t) u[1] << 32; v += u[2] | (uint64_t) u[3] << 32;
+  }
+  const int b = blockIdx.y * gridDim.x + blockIdx.x, blocks = gridDim.x * gridDim.y;
+  uint32_t* __restrict__ rec = recs + ( (size_t) tid * blocks + b ) * MSSSIM_REC_WORDS;
+  rec[0] = (uint32_t) cs; rec[1] = (uint32_t) ( cs >> 32 ); rec[2] = (uint32_t) v; rec[3] = (uint32_t) ( v >> 32 );
+}
+// k_output_msssim_sum — workgroup ( c, k ) folds the records of component c at level k into the level's MSSSIM_OUT_WORDS words of that component
+__global__ __launch_bounds__( 256 ) void k_output_msssim_sum( const uint32_t* __restrict__ recs, MsssimFold f, uint32_t* __restrict__ out )
+{
+  __shared__ uint32_t part[4][MSSSIM_OUT_WORDS];
+  const int tid = threadIdx.x, c = blockIdx.x, k = blockIdx.y, blocks = f.blocks[k];
+  const uint32_t* __restrict__ level = recs + f.recOff[k];
+  uint64_t cs = 0, v = 0;
+  for( int b = tid; b < blocks; b += 256 )
+  {
+    const uint4 u = *(const uint4*) ( level + ( (size_t) c * blocks + b ) * MSSSIM_REC_WORDS );      // (16 bytes a record, a level's records start at a multiple of 256 bytes)
+    cs += u.x | (uint64_t) u.y << 32; v += u.z | (uint64_t) u.w << 32;
+  }
+  cs = (uint64_t) msssim_wave( (int64_t) cs ); v = (uint64_t) msssim_wave( (int64_t) v );
+  if( ( tid & 63 ) == 0 )
+  {
+    uint32_t* u = part[tid >> 6];
+    u[0] = (uint32_t) cs; u[1] = (uint32_t) ( cs >> 32 ); u[2] = (uint32_t) v; u[3] = (uint32_t) ( v >> 32 );
+  }
+  __syncthreads();
+  if( tid ) return;
+  cs = 0; v = 0;
+  for( int w = 0; w < 4; w++ )
+  {
+    const uint32_t* u = part[w];
+    cs += u[0] | (uint64_t) u[1] << 32; v += u[2] | (uint64_t) u[3] << 32;
+  }
+  uint32_t* __restrict__ o = out + ( k * gridDim.x + c ) * MSSSIM_OUT_WORDS;
+  o[0] = (uint32_t) cs; o[1] = (uint32_t) ( cs >> 32 ); o[2] = (uint32_t) v; o[3] = (uint32_t) ( v >> 32 );
+}
+template<bool EMIT>
+static void launch_output_msssim_class( hipStream_t s, const CompareParams& p, const MsssimNext& nx, int bitDepth, uint32_t* recs )
+{
+  const dim3 grid( p.nbx, p.nby );
+  if( p.bySample ) { if( p.refBytes == 1 ) hipLaunchKernelGGL( ( k_output_msssim<1, true, EMIT> ), grid, dim3( 256 ), 0, s, p, nx, bitDepth, recs ); else hipLaunchKernelGGL( ( k_output_msssim<2, true, EMIT> ), grid, dim3( 256 ), 0, s, p, nx, bitDepth, recs ); }
+  else if( p.refBytes == 1 ) hipLaunchKernelGGL( ( k_output_msssim<1, false, EMIT> ), grid, dim3( 256 ), 0, s, p, nx, bitDepth, recs );
+  else hipLaunchKernelGGL( ( k_output_msssim<2, false, EMIT> ), grid, dim3( 256 ), 0, s, p, nx, bitDepth, recs );
+}
+void launch_output_msssim( hipStream_t s, const CompareParams& p, int bitDepth, uint32_t* recs, const MsssimNext* next )
+{
+  const MsssimNext none = { { nullptr, nullptr, nullptr }, { nullptr, nullptr, nullptr }, { 0, 0, 0 } };
+  if( next ) launch_output_msssim_class<true>( s, p, *next, bitDepth, recs ); else launch_output_msssim_class<false>( s, p, none, bitDepth, recs );
+}
+void launch_output_msssim_sum( hipStream_t s, const uint32_t* recs, const MsssimFold& f, int numComp, uint32_t* out )
+{
+  hipLaunchKernelGGL( k_output_msssim_sum, dim3( numComp, f.scales ), dim3( 256 ), 0, s, recs, f, out );
+}
+
 // multiplication in GF(2)[x] / (x^16 + x^12 + x^5 + 1), the ring the CRC of the decoded picture hash lives in
 __device__ __forceinline__ uint32_t crc_mul( uint32_t a, uint32_t b )
 {

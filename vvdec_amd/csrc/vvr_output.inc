@@ -633,6 +633,62 @@ void launch_output_ssim_sum( hipStream_t, const uint32_t* recs, int blocks, int 
     o[0] = (uint32_t) sum; o[1] = (uint32_t) ( sum >> 32 ); o[2] = (uint32_t) key; o[3] = (uint32_t) ( key >> 32 );
   }
 }
+
+// ... and launch_output_msssim / launch_output_msssim_sum (k_output_msssim, k_output_msssim_sum): one level of the definition of vvr.h window by
+// window and sample by sample, a record per block and component as vvr_device.h lays them out; with `next` the whole next level, every sample
+// ( i, j ) with i < w >> 1 and j < h >> 1 as the rounded mean of the 2 x 2 clamped samples above it; the records of all levels folded
+void launch_output_msssim( hipStream_t, const CompareParams& p, int bitDepth, uint32_t* recs, const MsssimNext* next )
+{
+  const int blocks = p.nbx * p.nby;
+  const int64_t L = ( 1 << bitDepth ) - 1, N = 64, C1 = ( L * L * 4096 + 5000 ) / 10000, C2 = ( 9 * L * L * 4096 + 5000 ) / 10000;
+  auto sampleX = [&]( int c, int i, int j ) { return std::min<int64_t>( (uint16_t) p.src[c][(size_t) j * p.stride[c] + i], L ); };
+  auto sampleY = [&]( int c, int i, int j ) { const uint8_t* r = p.ref[c] + (size_t) j * p.refStride[c] + (size_t) i * p.refBytes; return std::min<int64_t>( p.refBytes == 1 ? r[0] : r[0] | r[1] << 8, L ); };
+  for( int c = 0; c < p.numComp; c++ )
+  {
+    for( int b = 0; b < blocks; b++ )
+    {
+      const int side = c ? 32 : 64, i0 = ( b % p.nbx ) * side, j0 = ( b / p.nbx ) * side;
+      int64_t sumCs = 0, sumV = 0;
+      for( int j = j0; j < j0 + side && j + 8 <= p.h[c]; j += 4 )
+        for( int i = i0; i < i0 + side && i + 8 <= p.w[c]; i += 4 )
+        {
+          int64_t s1 = 0, s2 = 0, sxx = 0, syy = 0, sxy = 0;
+          for( int jj = j; jj < j + 8; jj++ )
+            for( int ii = i; ii < i + 8; ii++ )
+            {
+              const int64_t x = sampleX( c, ii, jj ), y = sampleY( c, ii, jj );
+              s1 += x; s2 += y; sxx += x * x; syy += y * y; sxy += x * y;
+            }
+          const int64_t A1 = 2 * s1 * s2 + C1, B1 = s1 * s1 + s2 * s2 + C1, A2 = 2 * ( N * sxy - s1 * s2 ) + C2, B2 = ( N * sxx - s1 * s1 ) + ( N * syy - s2 * s2 ) + C2;
+          const int64_t l = ( A1 * 16777216 ) / B1, cs = ( A2 * 16777216 ) / B2, v = ( l * cs ) / 16777216;
+          sumCs += cs; sumV += v;
+        }
+      uint32_t* rec = recs + ( (size_t) c * blocks + b ) * MSSSIM_REC_WORDS;
+      rec[0] = (uint32_t) (uint64_t) sumCs; rec[1] = (uint32_t) ( (uint64_t) sumCs >> 32 ); rec[2] = (uint32_t) (uint64_t) sumV; rec[3] = (uint32_t) ( (uint64_t) sumV >> 32 );
+    }
+    for( int j = 0; next && j < p.h[c] >> 1; j++ )
+      for( int i = 0; i < p.w[c] >> 1; i++ )
+      {
+        next->x[c][(size_t) j * next->stride[c] + i] = (uint16_t) ( ( sampleX( c, 2 * i, 2 * j ) + sampleX( c, 2 * i + 1, 2 * j ) + sampleX( c, 2 * i, 2 * j + 1 ) + sampleX( c, 2 * i + 1, 2 * j + 1 ) + 2 ) >> 2 );
+        next->y[c][(size_t) j * next->stride[c] + i] = (uint16_t) ( ( sampleY( c, 2 * i, 2 * j ) + sampleY( c, 2 * i + 1, 2 * j ) + sampleY( c, 2 * i, 2 * j + 1 ) + sampleY( c, 2 * i + 1, 2 * j + 1 ) + 2 ) >> 2 );
+      }
+  }
+}
+void launch_output_msssim_sum( hipStream_t, const uint32_t* recs, const MsssimFold& f, int numComp, uint32_t* out )
+{
+  for( int k = 0; k < f.scales; k++ )
+    for( int c = 0; c < numComp; c++ )
+    {
+      uint64_t cs = 0, v = 0;      // (two's complement)
+      for( int b = 0; b < f.blocks[k]; b++ )
+      {
+        const uint32_t* rec = recs + f.recOff[k] + ( (size_t) c * f.blocks[k] + b ) * MSSSIM_REC_WORDS;
+        cs += rec[0] | (uint64_t) rec[1] << 32; v += rec[2] | (uint64_t) rec[3] << 32;
+      }
+      uint32_t* o = out + ( k * numComp + c ) * MSSSIM_OUT_WORDS;
+      o[0] = (uint32_t) cs; o[1] = (uint32_t) ( cs >> 32 ); o[2] = (uint32_t) v; o[3] = (uint32_t) ( v >> 32 );
+    }
+}
 #endif
 
 extern "C" {
@@ -959,6 +1015,40 @@ VVR_API int vvr_compare_ssim( const vvr_frame_ssim* sm, double ssim[4] )
   return VVR_OK;
 }
 
+// MS-SSIM from the sums of an MS-SSIM request (vvr_msssim_submit), the formula as vvr.h gives it, in double
+VVR_API int vvr_compare_msssim( const vvr_frame_msssim* ms, const double* weights, double msssim[4] )
+{
+  if( !ms || !msssim || ms->struct_size != sizeof( vvr_frame_msssim ) || ms->bit_depth < 8 || ms->bit_depth > 10 || ms->scales < 1 || ms->scales > VVR_MSSSIM_MAX_SCALES ) return VVR_ERR_PARAMETER;
+  static const double wang[VVR_MSSSIM_MAX_SCALES] = { 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 };
+  const int scales = (int) ms->scales, nc = ms->num_components == 1 ? 1 : 3;
+  double wt[VVR_MSSSIM_MAX_SCALES], total = 0;
+  for( int k = 0; k < scales; k++ ) total += wang[k];
+  for( int k = 0; k < scales; k++ )
+  {
+    if( !ms->windows[k][0] ) return VVR_ERR_PARAMETER;
+    wt[k] = weights ? weights[k] : wang[k] / total;
+    if( !std::isfinite( wt[k] ) || wt[k] < 0 ) return VVR_ERR_PARAMETER;
+  }
+  double out[4] = { 0, 0, 0, 0 };
+  for( int c = 0; c < 4; c++ )
+  {
+    bool exists = c == 3 || c < nc;      // (a component that does not exist, or lacks windows at one of the levels: 0)
+    for( int k = 0; k < scales && c < 3 && exists; k++ ) exists = ms->windows[k][c] != 0;
+    if( !exists ) continue;
+    double product = 1;
+    for( int k = 0; k < scales; k++ )
+    {
+      double sum = 0, windows = 0;
+      for( int q = ( c < 3 ? c : 0 ); q < ( c < 3 ? c + 1 : nc ); q++ ) { sum += (double) ( k < scales - 1 ? ms->sum_cs[k][q] : ms->sum_v[k][q] ); windows += (double) ms->windows[k][q]; }
+      const double m = sum / ( windows * 16777216.0 );
+      product *= pow( m > 0 ? m : 0.0, wt[k] );
+    }
+    out[c] = product;
+  }
+  memcpy( msssim, out, sizeof( out ) );
+  return VVR_OK;
+}
+
 VVR_API int vvr_read_output_grain( vvr_context* c, int slot, int x, int y, int w, int h, int bytesPerSample, void* const dst[3], const size_t dstStrideBytes[3] )
 {
   if( !c || slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] || !dst || !dstStrideBytes ) return VVR_ERR_PARAMETER;
@@ -1159,7 +1249,9 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // holds a record per block and component, every word of which k_output_compare stores - nothing is cleared - then the words
 // k_output_compare_sum folds them to and the map; the words (with `map` the map too) are all that crosses PCIe back.
 // An SSIM request (vvr_ssim_submit) is a comparison request with other kernels (k_output_ssim, k_output_ssim_sum), records and words: both calls
-// go through compareSubmit.
+// go through compareSubmit.  So does an MS-SSIM request (vvr_msssim_submit): a k_output_msssim per scale, each but the last writing the next
+// level of both images into the pyramid that lies behind the records and words in the entry's `dev`, and one k_output_msssim_sum; only level 0
+// reads the slots and the reference, so `read` is recorded behind it.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -1185,6 +1277,9 @@ struct OutEntry {
   // ... or an SSIM request, which is a comparison request with records and words of its own (SSIM_OUT_WORDS per component) and with cmpOut and
   // cmpMap pointing to a vvr_frame_ssim and to int32_t words
   bool cmpSsim = false;
+  // ... or an MS-SSIM request (msScales > 0: its number of scales), a comparison request too: MSSSIM_OUT_WORDS words per level and component at the
+  // start of `host`, cmpOut pointing to a vvr_frame_msssim, no map; `dev` holds the records of all levels, the words, then the pyramid
+  int msScales = 0;
 };
 #define CMP_HEAD_WORDS 32      /* 3 x CMP_OUT_WORDS, rounded up: the map starts at a multiple of 128 bytes */
 
@@ -1290,7 +1385,7 @@ int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blockin
 void outTake( vvr_context* c, OutEntry* e, int slot, int job, int jobFailed )
 {
   e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
-  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0; e->cmp = 0; e->refSlot = -1;
+  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0; e->cmp = 0; e->msScales = 0; e->refSlot = -1;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
   if( e->timed2 ) { hipEventDestroy( e->timing2.a ); hipEventDestroy( e->timing2.b ); e->timed2 = false; }
 }
@@ -1757,8 +1852,9 @@ VVR_API int vvr_stats_submit( vvr_context* c, const vvr_stats_request* rq )
 // vvr_output_wait writes.  A vvr_ssim_request is a vvr_compare_request field by field (result and map are pointers to other types)
 static_assert( sizeof( vvr_ssim_request ) == sizeof( vvr_compare_request ) && offsetof( vvr_ssim_request, ref ) == offsetof( vvr_compare_request, ref ) &&
                offsetof( vvr_ssim_request, result ) == offsetof( vvr_compare_request, result ) && offsetof( vvr_ssim_request, map ) == offsetof( vvr_compare_request, map ), "vvr_ssim_request mirrors vvr_compare_request" );
-static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const char* who, bool ssim )
+static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const char* who, bool ssim, int scales = 0 )      // scales > 0: vvr_msssim_submit
 {
+  const bool ms = scales > 0;
   // ---- 1. the request (its struct_size has been looked at)
   const int slot = rq->slot, refSlot = rq->ref_slot, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot", who );
@@ -1769,6 +1865,8 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot, not the slot)
   if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, empty, or odd in 4:2:0", who );
   if( ssim && ( w < 8 || h < 8 ) ) return outRefuse( c, "a window below 8 x 8 holds no SSIM window", who );
+  for( int k = 0; k < nc && ms; k++ )
+    if( ( ( w >> ( k ? 1 : 0 ) ) >> ( scales - 1 ) ) < 8 || ( ( h >> ( k ? 1 : 0 ) ) >> ( scales - 1 ) ) < 8 ) return outRefuse( c, "a component has no 8 x 8 window at the last level: the window takes fewer scales", who );
   const int rb = refSlot >= 0 ? 2 : rq->ref_bytes_per_sample;
   CompareParams p; memset( &p, 0, sizeof( p ) );
   size_t rowBytes[3] = { 0, 0, 0 }, extent[3] = { 0, 0, 0 };
@@ -1809,8 +1907,28 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   // ---- the entry's buffers: the blocks' records, the folded words and the map behind them; a reference from the host packed in `tmp`, rows at a
   // multiple of 16 bytes; pinned: the folded words and the map, then the staging of a reference in pageable memory
   const int blocks = p.nbx * p.nby, recWords = ssim ? SSIM_REC_WORDS : CMP_REC_WORDS, outWords = ssim ? SSIM_OUT_WORDS : CMP_OUT_WORDS;
-  const size_t recBytes = alignUp( sizeof( uint32_t ) * recWords * nc * blocks, 256 ), wordBytes = sizeof( uint32_t ) * ( CMP_HEAD_WORDS + blocks );
-  const size_t crossBytes = sizeof( uint32_t ) * ( rq->map ? CMP_HEAD_WORDS + blocks : 3 * outWords ), hostStageOff = alignUp( wordBytes, 256 );
+  size_t recBytes = alignUp( sizeof( uint32_t ) * recWords * nc * blocks, 256 ), wordBytes = sizeof( uint32_t ) * ( CMP_HEAD_WORDS + blocks );
+  size_t crossBytes = sizeof( uint32_t ) * ( rq->map ? CMP_HEAD_WORDS + blocks : 3 * outWords );
+  // MS-SSIM: the records of every level one after the other, each at a multiple of 256 bytes, the words of all levels, then the pyramid - per level
+  // k >= 1 and component the slot's side and the reference's, 16-bit words, rows a multiple of 16 bytes, each plane at a multiple of 256 bytes
+  MsssimFold fold; memset( &fold, 0, sizeof( fold ) );
+  size_t pyrOff[MSSSIM_MAX_SCALES][3][2]; int pyrStride[MSSSIM_MAX_SCALES][3]; size_t pyrBytes = 0;
+  if( ms )
+  {
+    fold.scales = scales; recBytes = 0;
+    for( int k = 0; k < scales; k++ )
+    {
+      fold.recOff[k] = (int) ( recBytes / sizeof( uint32_t ) ); fold.blocks[k] = ( ( ( w >> k ) + 63 ) / 64 ) * ( ( ( h >> k ) + 63 ) / 64 );
+      recBytes += alignUp( sizeof( uint32_t ) * MSSSIM_REC_WORDS * nc * fold.blocks[k], 256 );
+      for( int q = 0; q < nc && k > 0; q++ )
+      {
+        pyrStride[k][q] = (int) alignUp( (size_t) ( p.w[q] >> k ), 8 );
+        for( int side = 0; side < 2; side++ ) { pyrOff[k][q][side] = pyrBytes; pyrBytes += alignUp( sizeof( uint16_t ) * pyrStride[k][q] * ( p.h[q] >> k ), 256 ); }
+      }
+    }
+    wordBytes = sizeof( uint32_t ) * MSSSIM_OUT_WORDS * 3 * MSSSIM_MAX_SCALES; crossBytes = sizeof( uint32_t ) * MSSSIM_OUT_WORDS * nc * scales;
+  }
+  const size_t hostStageOff = alignUp( wordBytes, 256 ), pyrBase = alignUp( recBytes + wordBytes, 256 );
   size_t stageOff[3] = { 0, 0, 0 }, stageStride[3] = { 0, 0, 0 }, stageBytes = 0;
   for( int k = 0; k < nc && staged; k++ ) { stageOff[k] = stageBytes; stageStride[k] = alignUp( rowBytes[k], 16 ); stageBytes += alignUp( stageStride[k] * p.h[k], 256 ); }
   // ---- a reference in pageable memory goes into an entry's pinned memory BEFORE the request is ordered: from outAcquire to the registration of the
@@ -1841,9 +1959,9 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   { const int rc = outAcquire( c, who, slot, rq->job, rq->blocking != 0, lk, e, jobDone, jobFailed, mine ); if( rc != VVR_OK ) return rc; }
   hipStream_t s = c->outQStream;
   outTake( c, e, slot, rq->job, jobFailed );
-  e->cmp = nc; e->cmpW = w; e->cmpH = h; e->cmpBlocks = blocks; e->cmpOut = rq->result; e->cmpMap = rq->map; e->cmpSsim = ssim;
+  e->cmp = nc; e->cmpW = w; e->cmpH = h; e->cmpBlocks = blocks; e->cmpOut = rq->result; e->cmpMap = rq->map; e->cmpSsim = ssim; e->msScales = scales;
   if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
-  if( outGrow( e->dev, e->devCap, recBytes + wordBytes, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, stageBytes, false ) != VVR_OK ||
+  if( outGrow( e->dev, e->devCap, ms ? pyrBase + pyrBytes : recBytes + wordBytes, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, stageBytes, false ) != VVR_OK ||
       outGrow( e->host, e->hostCap, hostStageOff, true ) != VVR_OK )      // (a staged reference: grown above, beyond this)
   { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
   for( int k = 0; k < nc && refSlot < 0; k++ )
@@ -1869,17 +1987,37 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   uint32_t* recs = (uint32_t*) e->dev; uint32_t* words = (uint32_t*) ( e->dev + recBytes );
   double samples = 0;
   for( int k = 0; k < nc; k++ ) samples += (double) p.w[k] * p.h[k];
-  outTimeBegin( c, s, e->timed, e->timing, ssim ? K_OUTPUT_SSIM : K_OUTPUT_COMPARE, samples * ( 2 + rb ) );
-  if( ssim ) launch_output_ssim( s, p, c->cfg.bit_depth, recs, (int32_t*) ( words + CMP_HEAD_WORDS ) );
+  // (MS-SSIM: level k reads 2 + rb or 4 bytes a sample and, but for the last, writes 4 bytes for every four samples; level l holds samples / 4^l)
+  auto level = [&]( int k, MsssimNext& nx )      // the planes of level k >= 1 of the pyramid
+  {
+    for( int q = 0; q < nc; q++ ) { nx.x[q] = (uint16_t*) ( e->dev + pyrBase + pyrOff[k][q][0] ); nx.y[q] = (uint16_t*) ( e->dev + pyrBase + pyrOff[k][q][1] ); nx.stride[q] = pyrStride[k][q]; }
+  };
+  double msBytes = 0;
+  for( int k = 0; k < scales; k++ ) msBytes += samples / (double) ( 1 << 2 * k ) * ( ( k ? 4 : 2 + rb ) + ( k + 1 < scales ? 1 : 0 ) );
+  outTimeBegin( c, s, e->timed, e->timing, ms ? K_OUTPUT_MSSSIM : ssim ? K_OUTPUT_SSIM : K_OUTPUT_COMPARE, ms ? msBytes : samples * ( 2 + rb ) );
+  MsssimNext nx; memset( &nx, 0, sizeof( nx ) );
+  if( ms ) { if( scales > 1 ) level( 1, nx ); launch_output_msssim( s, p, c->cfg.bit_depth, recs, scales > 1 ? &nx : nullptr ); }
+  else if( ssim ) launch_output_ssim( s, p, c->cfg.bit_depth, recs, (int32_t*) ( words + CMP_HEAD_WORDS ) );
   else launch_output_compare( s, p, recs, words + CMP_HEAD_WORDS );
-  if( e->timed ) hipEventRecord( e->timing.b, s );
+  if( e->timed && scales <= 1 ) hipEventRecord( e->timing.b, s );
   OQCHK( hipGetLastError() );
   OQCHK( hipEventRecord( e->read, s ) );      // (the slots' reader ends here: the fold reads the entry's scratch)
   c->slotExt[slot].push_back( e->read );
   if( refSlot >= 0 ) { c->slotExt[refSlot].push_back( e->read ); e->refSlot = refSlot; }
   e->state = OQ_FLIGHT; e->queued = true;
-  outTimeBegin( c, s, e->timed2, e->timing2, ssim ? K_OUTPUT_SSIM_SUM : K_OUTPUT_COMPARE_SUM, (double) sizeof( uint32_t ) * ( recWords * blocks + outWords ) * nc );
-  if( ssim ) launch_output_ssim_sum( s, recs, blocks, nc, words );
+  for( int k = 1; k < scales; k++ )      // the deeper levels of an MS-SSIM request: both images from the pyramid, the wide class
+  {
+    CompareParams q = p; MsssimNext from; memset( &from, 0, sizeof( from ) );
+    level( k, from );
+    for( int n = 0; n < nc; n++ ) { q.w[n] = p.w[n] >> k; q.h[n] = p.h[n] >> k; q.src[n] = (const pel_t*) from.x[n]; q.stride[n] = from.stride[n]; q.ref[n] = (const uint8_t*) from.y[n]; q.refStride[n] = sizeof( uint16_t ) * from.stride[n]; }
+    q.refBytes = 2; q.bySample = 0; q.nbx = ( q.w[0] + 63 ) / 64; q.nby = ( q.h[0] + 63 ) / 64;
+    if( k + 1 < scales ) level( k + 1, nx );
+    launch_output_msssim( s, q, c->cfg.bit_depth, recs + fold.recOff[k], k + 1 < scales ? &nx : nullptr );
+    if( e->timed && k + 1 == scales ) hipEventRecord( e->timing.b, s );
+  }
+  outTimeBegin( c, s, e->timed2, e->timing2, ms ? K_OUTPUT_MSSSIM_SUM : ssim ? K_OUTPUT_SSIM_SUM : K_OUTPUT_COMPARE_SUM, ms ? (double) recBytes + crossBytes : (double) sizeof( uint32_t ) * ( recWords * blocks + outWords ) * nc );
+  if( ms ) launch_output_msssim_sum( s, recs, fold, nc, words );
+  else if( ssim ) launch_output_ssim_sum( s, recs, blocks, nc, words );
   else launch_output_compare_sum( s, recs, blocks, nc, words );
   if( e->timed2 ) hipEventRecord( e->timing2.b, s );
   const int ticket = e->ticket;
@@ -1909,6 +2047,21 @@ VVR_API int vvr_ssim_submit( vvr_context* c, const vvr_ssim_request* rq )
   memcpy( &q, rq, sizeof( q ) );
   return compareSubmit( c, &q, "vvr_ssim_submit", true );
 }
+// (a vvr_msssim_request is a vvr_compare_request up to `result`, with `scales` in the first pad byte and no map)
+static_assert( sizeof( vvr_msssim_request ) == 96 && sizeof( vvr_frame_msssim ) == 616 && offsetof( vvr_msssim_request, ref ) == offsetof( vvr_compare_request, ref ) &&
+               offsetof( vvr_msssim_request, result ) == offsetof( vvr_compare_request, result ) && offsetof( vvr_msssim_request, result ) + sizeof( void* ) == sizeof( vvr_msssim_request ) &&
+               VVR_MSSSIM_MAX_SCALES == MSSSIM_MAX_SCALES, "vvr_msssim_request mirrors vvr_compare_request up to result" );
+VVR_API int vvr_msssim_submit( vvr_context* c, const vvr_msssim_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  if( rq->struct_size != sizeof( vvr_msssim_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_msssim_request )", "vvr_msssim_submit" );
+  if( rq->scales < 1 || rq->scales > VVR_MSSSIM_MAX_SCALES ) return outRefuse( c, "scales must be 1 .. 5", "vvr_msssim_submit" );
+  vvr_compare_request q;
+  memset( &q, 0, sizeof( q ) );
+  memcpy( &q, rq, sizeof( *rq ) );
+  q.map = nullptr;
+  return compareSubmit( c, &q, "vvr_msssim_submit", false, rq->scales );
+}
 #undef OQCHK
 
 VVR_API int vvr_output_test( vvr_context* c, int ticket )
@@ -1937,8 +2090,8 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   lk.lock();
   if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
   if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
-  outTimeEnd( c, e->timed, e->timing );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS ...
-  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM; K_OUTPUT_COMPARE and K_OUTPUT_COMPARE_SUM; K_OUTPUT_SSIM and K_OUTPUT_SSIM_SUM)
+  outTimeEnd( c, e->timed, e->timing, e->msScales ? e->msScales : 1 );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS; K_OUTPUT_MSSSIM, a launch per scale ...
+  outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM; K_OUTPUT_COMPARE and K_OUTPUT_COMPARE_SUM; K_OUTPUT_SSIM and K_OUTPUT_SSIM_SUM; K_OUTPUT_MSSSIM_SUM)
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
   if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
   if( e->refSlot >= 0 ) { auto& v = c->slotExt[e->refSlot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }      // (a comparison reads two slots)
@@ -1976,7 +2129,25 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
       for( int k = 0; k < 3; k++ ) { st.max_c[k] = w[2048 + k]; st.min_c[k] = ( ( 1u << c->cfg.bit_depth ) - 1 ) - w[2051 + k]; }
     }
   }
-  if( rc == VVR_OK && e->queued && e->cmp && e->cmpSsim )
+  if( rc == VVR_OK && e->queued && e->cmp && e->msScales )
+  {
+    // the caller's vvr_frame_msssim: the header fields, per level and component the plane, the grid of windows and the two folded sums
+    const uint32_t* w = (const uint32_t*) e->host;
+    vvr_frame_msssim r;
+    memset( &r, 0, sizeof( r ) );
+    r.struct_size = sizeof( r ); r.bit_depth = (uint32_t) c->cfg.bit_depth; r.num_components = (uint32_t) e->cmp; r.scales = (uint32_t) e->msScales;
+    for( int l = 0; l < e->msScales; l++ )
+      for( int k = 0; k < e->cmp; k++ )
+      {
+        const uint32_t* o = w + ( l * e->cmp + k ) * MSSSIM_OUT_WORDS;
+        r.width[l][k] = (uint32_t) ( ( e->cmpW >> ( k ? 1 : 0 ) ) >> l ); r.height[l][k] = (uint32_t) ( ( e->cmpH >> ( k ? 1 : 0 ) ) >> l );
+        r.windows_x[l][k] = r.width[l][k] >= 8 ? ( r.width[l][k] - 8 ) / 4 + 1 : 0; r.windows_y[l][k] = r.height[l][k] >= 8 ? ( r.height[l][k] - 8 ) / 4 + 1 : 0;
+        r.windows[l][k] = (uint64_t) r.windows_x[l][k] * r.windows_y[l][k];
+        r.sum_cs[l][k] = (int64_t) ( o[0] | (uint64_t) o[1] << 32 ); r.sum_v[l][k] = (int64_t) ( o[2] | (uint64_t) o[3] << 32 );
+      }
+    memcpy( (void*) e->cmpOut, &r, sizeof( r ) );
+  }
+  else if( rc == VVR_OK && e->queued && e->cmp && e->cmpSsim )
   {
     // the caller's vvr_frame_ssim: the header fields, the grid of windows, the folded words - the key taken apart into the smallest v and the
     // origin of the first window that has it; the map
