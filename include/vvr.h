@@ -937,7 +937,7 @@ VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_
  *            the output stream; it must stay untouched until vvr_output_wait has returned.  Any other host memory: copied inside vvr_compare_submit
  *            into the entry's pinned staging, as `expected` of a hash request is: the caller's buffers are free again when the call returns.
  *   ticket and ring, ordering   everything said about a hash or statistics request above holds: the ticket comes from the same ticket space and the
- *            same 8 ring entries (VVR_ERR_BUSY counts all six kinds of request); vvr_output_test / vvr_output_wait collect it;
+ *            same 8 ring entries (VVR_ERR_BUSY counts all seven kinds of request); vvr_output_test / vvr_output_wait collect it;
  *            vvr_output_stream_wait means "the words have landed in the context's pinned memory"; vvr_sync waits for it and retires nothing; the
  *            request runs on the output stream behind the picture's completion event ON THE DEVICE (job >= 0) or behind the slot's users (-1);
  *            ref_slot is taken as all work submitted so far leaves it (the job == -1 rule, whatever `job` is); the request is a reader of both slots:
@@ -949,7 +949,7 @@ VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_
  * ref_slot == slot, job < -1, result == NULL, a window outside the picture, empty, or odd in a 4:2:0 context, pictures of different sizes in the two
  * slots; without ref_slot: ref_bytes_per_sample other than 1 or 2, a NULL plane among those the context has, a stride below the row, device planes
  * mixed with host planes, a plane partly inside a device range.
- * Not offered here: SSIM and MS-SSIM are requests of their own (vvr_ssim_submit, vvr_msssim_submit, below); grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
+ * Not offered here: SSIM, MS-SSIM and XPSNR are requests of their own (vvr_ssim_submit, vvr_msssim_submit, vvr_xpsnr_submit, below); grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
  * a reference of another size than the window. */
 typedef struct vvr_frame_compare {
   uint32_t struct_size;            /* sizeof( vvr_frame_compare ), written with the rest */
@@ -1013,7 +1013,7 @@ VVR_API int          vvr_compare_psnr(const vvr_frame_compare* cmp, double peak,
  *   map      NULL, or ceil( w / 64 ) * ceil( h / 64 ) words, row-major: the smallest v over the windows of all components whose ORIGIN sample lies in
  *            that block of 64 x 64 luma samples; a chroma origin ( i, j ) belongs to the block of ( 2 i, 2 j ); 0x7fffffff where no origin falls into
  *            the block (a last block 4 samples wide, for one).
- *   where the reference may lie, ticket and ring, ordering, result   everything said for a comparison request above holds (VVR_ERR_BUSY counts all six
+ *   where the reference may lie, ticket and ring, ordering, result   everything said for a comparison request above holds (VVR_ERR_BUSY counts all seven
  *            kinds of request); the film grain seed chain and the colour description are not touched.
  * Refused (VVR_ERR_PARAMETER with a text that names vvr_ssim_submit, no ring entry taken): everything vvr_compare_submit refuses, struct_size being
  * sizeof( vvr_ssim_request ), and a window with w < 8 or h < 8.
@@ -1055,7 +1055,7 @@ VVR_API int          vvr_compare_ssim(const vvr_frame_ssim* s, double ssim[4]);
 /* MS-SSIM of a picture against a reference frame as a request of the output queue: the third number of a transcoder's quality loop.  The pyramid
  * is built and every level is reduced on the device; scales x components x 4 words cross PCIe.  Everything not said here is exactly as for
  * vvr_ssim_submit: the window and the components' windows in 4:2:0, the reference planes that ARE the window, ref_slot, where the reference may lie,
- * ticket and ring (VVR_ERR_BUSY counts all six kinds of request), ordering, the reader of both slots; a failed job fails the request and leaves
+ * ticket and ring (VVR_ERR_BUSY counts all seven kinds of request), ordering, the reader of both slots; a failed job fails the request and leaves
  * *result untouched.  The result is integers, defined here to the bit:
  *   level 0  x_0 = min( slot word, L ), y_0 = min( reference byte or little-endian word, L ), L = 2^bit_depth - 1; its size is the component's
  *            window, w_0 x h_0.
@@ -1114,6 +1114,107 @@ VVR_API int          vvr_msssim_submit(vvr_context* ctx, const vvr_msssim_reques
  * a struct_size other than sizeof( vvr_frame_msssim ), a bit depth outside 8..10, scales outside 1 .. 5, windows[k][0] == 0 for some k < scales,
  * a weight that is negative or not finite. */
 VVR_API int          vvr_compare_msssim(const vvr_frame_msssim* s, const double* weights, double msssim[4]);
+/* XPSNR of a picture against a reference frame as a request of the output queue: the number the VVC tool chain itself reports (Helmrich et al.,
+ * "XPSNR: a low-complexity extension of PSNR", 2020), a block-wise weighted SSE whose weights come from a spatial high-pass stencil on the reference
+ * luma and a temporal difference against the one or two reference frames before it.  It follows from nothing a comparison returns - that has the
+ * SSE per frame, not per block, and takes one reference frame - so it has a kernel of its own (k_output_xpsnr) and the comparison's plumbing.  This
+ * text follows the structure of XPSNR and is the normative definition; agreement with another implementation's decimals is neither claimed nor
+ * tested.  The result is integers, defined here to the bit:
+ *   samples  x: the slot's 16-bit word; o: the reference's byte or little-endian word; o1, o2: the previous and the one-before-previous reference
+ *            LUMA.  All are read as the unsigned values they are; nothing is clipped or masked, a reference may hold anything up to 65535.
+ *   window   x, y, w, h, the components' windows in 4:2:0, the reference planes that ARE the window, ref_slot: exactly as for vvr_compare_request.
+ *            prev[0] / prev[1] (o1 / o2; the first `temporal` are used) are luma planes of the window's size, with the same ref_bytes_per_sample and
+ *            strides of their own; they are always the caller's memory, also with ref_slot >= 0.  Every plane passed by pointer (ref[] when
+ *            ref_slot == -1, and prev[]) lies in one kind of home: all wholly inside device ranges, or all on the host; the three cases are those
+ *            of vvr_compare_submit: read in place, copied from vvr_host_alloc memory on the output stream, or staged inside the call.
+ *   blocks   B = the request's `block`; for block == 0, B = max( 4, 4 * (int)( 32.0 * sqrt( w * h / 8294400.0 ) + 0.5 ) ) in double: 128 at
+ *            3840 x 2160, 64 at 1920 x 1080, 44 at 1280 x 720, 256 at 8K, 8 at 256 x 128, 4 at 208 x 80.  Block ( bx, by ) covers luma
+ *            [ B bx, min( B bx + B, w ) ) x [ B by, min( B by + B, h ) ) of the window and, in 4:2:0, the chroma samples ( i, j ) with ( 2 i, 2 j )
+ *            inside it.  blocks_x = ceil( w / B ), blocks_y = ceil( h / B ); records are stored row-major.  vvr_xpsnr_blocks gives this geometry.
+ *   filter   filter == 0 resolves to 2 when w * h > 2048 * 1152, else to 1.
+ *            Filter 1, positions ( i, j ) of the luma window with 1 <= i <= w - 2 and 1 <= j <= h - 2:
+ *              f = 12 o(i,j) - 2 [ o(i-1,j) + o(i+1,j) + o(i,j-1) + o(i,j+1) ] - [ o(i-1,j-1) + o(i+1,j-1) + o(i-1,j+1) + o(i+1,j+1) ];
+ *              t = 0 (temporal 0), | o - o1 | (temporal 1), | o - 2 o1 + o2 | (temporal 2), at ( i, j ).
+ *            Filter 2, the same shape on 2 x 2 sums, positions ( i, j ) with i and j even, 2 <= i <= w - 4, 2 <= j <= h - 4: f is the sum over
+ *            di, dj = 0 .. 5 of W[dj][di] * o( i - 2 + di, j - 2 + dj ) with the symmetric weights (their sum is 0)
+ *                 0 -1 -1 -1 -1  0
+ *                -1 -2 -3 -3 -2 -1
+ *                -1 -3 12 12 -3 -1
+ *                -1 -3 12 12 -3 -1
+ *                -1 -2 -3 -3 -2 -1
+ *                 0 -1 -1 -1 -1  0
+ *              and with S(a) = a(i,j) + a(i+1,j) + a(i,j+1) + a(i+1,j+1):  t = 0, | S(o) - S(o1) |, | S(o) - 2 S(o1) + S(o2) |.
+ *            A position belongs to the block that contains ( i, j ); B is a multiple of 4, so a 2 x 2 cell never straddles blocks.
+ *            |f| <= 48 * 65535 < 2^22 and t <= 2^20: every sum is exact in 64 bits for every input (a 32-bit sum over 64 x 64 samples is not, for
+ *            references above the bit depth).
+ *   per block (vvr_xpsnr_block)   sse[c]: the sum of ( x - o )^2 over the block's samples of component c, the d of vvr_compare_submit;
+ *            act_spatial: the sum of |f|, act_temporal: the sum of t, count: the number of positions, all over the block's positions; pad = 0.  The
+ *            entries of the components a 4:0:0 context lacks are 0.
+ *   per frame (vvr_frame_xpsnr)   struct_size, bit_depth, num_components, temporal, filter (resolved: 1 or 2), block (resolved), blocks_x, blocks_y,
+ *            width, height, samples per component, and sse[3], act_spatial, act_temporal, count: the sums over the blocks.
+ *   Three consequences.  (a) sse[c] equals vvr_compare_submit's for the same request.  (b) The frame's sums do not depend on B.  (c) act_spatial,
+ *            act_temporal and count do not depend on the slot.
+ *   ticket and ring, ordering, result   everything said for a comparison request above holds (VVR_ERR_BUSY counts all seven kinds of request); the
+ *            request is a reader of both slots; a request for a job that failed fails with that job's status, *result and blocks untouched.
+ *            vvr_output_wait, when it returns VVR_OK, writes *result and, unless `blocks` is NULL, blocks_x * blocks_y records.
+ * Refused (VVR_ERR_PARAMETER with a text that names vvr_xpsnr_submit, no ring entry taken): everything vvr_compare_submit refuses, struct_size being
+ * sizeof( vvr_xpsnr_request ); w < 8 or h < 8; temporal > 2; filter > 2; a block that is neither 0 nor a multiple of 4; more than 16384 blocks; for
+ * k < temporal a NULL prev[k] or a stride below the row; a prev plane partly inside a device range; pointer planes of mixed homes.
+ * Not offered: minimum-smoothing of the weights between neighbouring blocks at low resolutions; chroma activity; temporal activity from slots;
+ * grained or rescaled frames; results left in device memory; more than 16384 blocks. */
+#define VVR_XPSNR_MAX_BLOCKS 16384
+typedef struct vvr_xpsnr_block {
+  uint64_t sse[3];                 /* sum of ( x - o )^2 per component */
+  uint64_t act_spatial;            /* sum of |f| */
+  uint64_t act_temporal;           /* sum of t */
+  uint32_t count;                  /* positions in the block */
+  uint32_t pad;                    /* 0 */
+} vvr_xpsnr_block;                 /* 48 bytes */
+typedef struct vvr_frame_xpsnr {
+  uint32_t struct_size;            /* sizeof( vvr_frame_xpsnr ), written with the rest */
+  uint32_t bit_depth;              /* the context's */
+  uint32_t num_components;         /* 1 (4:0:0) or 3 */
+  uint32_t temporal;               /* the request's */
+  uint32_t filter;                 /* resolved: 1 or 2 */
+  uint32_t block;                  /* resolved: B */
+  uint32_t blocks_x, blocks_y;
+  uint32_t width[3], height[3];    /* the window per component (chroma: >> 1 in 4:2:0) */
+  uint64_t samples[3];             /* width * height */
+  uint64_t sse[3];                 /* the sums over the blocks */
+  uint64_t act_spatial, act_temporal, count;
+} vvr_frame_xpsnr;                 /* 128 bytes */
+typedef struct vvr_xpsnr_request {
+  uint32_t struct_size;            /* sizeof( vvr_xpsnr_request ) */
+  int32_t  slot;
+  int32_t  job;                    /* as vvr_output_request.job */
+  int32_t  x, y, w, h;             /* window, luma samples (even in 4:2:0), w >= 8 and h >= 8 */
+  int32_t  ref_slot;               /* >= 0: the reference is the same window of that slot; -1: ref[] below */
+  uint8_t  ref_bytes_per_sample;   /* 1 or 2 (little endian), of ref[] and prev[]; ignored with ref_slot: prev[] holds 16-bit words then */
+  uint8_t  blocking;               /* as vvr_output_request.blocking */
+  uint8_t  temporal;               /* 0, 1, 2: how many of prev[] are used */
+  uint8_t  filter;                 /* 0: by the window's size; 1, 2 */
+  uint32_t block;                  /* 0: by the formula; else a multiple of 4 */
+  const void* ref[3];              /* planes of the WINDOW's size (not the picture's); ref[1], ref[2] unused in 4:0:0 */
+  size_t   ref_stride_bytes[3];
+  const void* prev[2];             /* luma of the reference one and two frames earlier, of the window's size; the first `temporal` are used */
+  size_t   prev_stride_bytes[2];
+  vvr_frame_xpsnr* result;         /* written by vvr_output_wait; must stay valid until it has returned */
+  vvr_xpsnr_block* blocks;         /* NULL (totals only), or blocks_x * blocks_y records, written by vvr_output_wait */
+} vvr_xpsnr_request;               /* 136 bytes */
+VVR_API int          vvr_xpsnr_submit(vvr_context* ctx, const vvr_xpsnr_request* req);
+/* the geometry a caller sizes `blocks` with: B, blocks_x and blocks_y of a window of w x h with the request's `block`, by the words above.  A pure
+ * host function.  Refused (VVR_ERR_PARAMETER, outputs untouched): a NULL pointer, w < 8 or h < 8, a block that is neither 0 nor a multiple of 4,
+ * more than 16384 blocks. */
+VVR_API int          vvr_xpsnr_blocks(int w, int h, uint32_t block, uint32_t* resolved_block, uint32_t* blocks_x, uint32_t* blocks_y);
+/* XPSNR from the records of an XPSNR request; a pure host function, no context, everything in double, the blocks in ascending order.  Per block k:
+ * q_k = count_k * ( filter == 2 ? 4 : 1 );  act_k = count_k ? 1 + act_spatial_k / q_k + 2 * act_temporal_k / q_k : 0;  act_k = max( act_k,
+ * 2^( bit_depth - 6 ) );  w_k = sqrt( a_pic ) / act_k, a_pic <= 0 meaning 2^( 2 * bit_depth - 9 ) * sqrt( 3840.0 * 2160.0 / ( width[0] *
+ * height[0] ) ).  wsse_c = the sum over k of w_k * sse_k[c];  xpsnr[c] = 10 log10( peak^2 * samples[c] / wsse_c ), peak <= 0 meaning
+ * 2^bit_depth - 1;  xpsnr[3]: the same formula from the sums of wsse and of samples over the components, as vvr_compare_psnr does.  HUGE_VAL where
+ * wsse is 0; 0 for components that do not exist.  a_pic scales all weights of a frame alike: a caller who matches another tool's normalisation
+ * passes its constant.  Refused (VVR_ERR_PARAMETER, xpsnr untouched): a NULL pointer, a struct_size other than sizeof( vvr_frame_xpsnr ), a bit
+ * depth outside 8..10, samples[0] == 0, blocks_x * blocks_y == 0, filter outside 1..2. */
+VVR_API int          vvr_compare_xpsnr(const vvr_frame_xpsnr* f, const vvr_xpsnr_block* blocks, double a_pic, double peak, double xpsnr[4]);
 /* the finished picture in `slot` (every plane, at the picture's size) into the caller's buffers - what a decoder does with each picture it hands to
  * the application (the planes of a vvdecFrame live in the Picture's own buffers, vvdecimpl.cpp:1058).  Waits for NOTHING: the caller has waited for
  * the picture (vvr_wait); other pictures in flight are not held up (vvr_read_plane drains the context).  Each plane crosses PCIe in one transfer

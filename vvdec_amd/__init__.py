@@ -130,6 +130,12 @@ def lib():
         L.vvr_msssim_submit.argtypes = [C.c_void_p, C.c_void_p]
         L.vvr_compare_msssim.restype = C.c_int
         L.vvr_compare_msssim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vvr_xpsnr_submit.restype = C.c_int
+        L.vvr_xpsnr_submit.argtypes = [C.c_void_p, C.c_void_p]
+        L.vvr_xpsnr_blocks.restype = C.c_int
+        L.vvr_xpsnr_blocks.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vvr_compare_xpsnr.restype = C.c_int
+        L.vvr_compare_xpsnr.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
         L.vvr_output_stream_wait.restype = C.c_int
         L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vvr_device_alloc.restype = C.c_void_p
@@ -151,6 +157,7 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
                     "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit", "vvr_stats_submit", "vvr_light_level",
                     "vvr_compare_submit", "vvr_compare_psnr", "vvr_ssim_submit", "vvr_compare_ssim", "vvr_msssim_submit", "vvr_compare_msssim",
+                    "vvr_xpsnr_submit", "vvr_xpsnr_blocks", "vvr_compare_xpsnr",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
 
 
@@ -673,12 +680,24 @@ class Reconstructor:
         turns it into light levels)"""
         return FrameStats(self.output_wait(ticket))
 
-    def _against_reference(self, what, slot, ref, win, job, request, submit, raw, blocks):
-        """the part compare() and ssim() share: the reference looked at (a slot number, numpy planes, or torch tensors on the device, which are
-        registered with the context for the call's duration), the request made by `request`, submitted with `submit` and waited for; `raw` and
-        `blocks` are written"""
+    def _against_reference(self, what, slot, ref, win, job, request, submit, raw, blocks, prev=None):
+        """the part compare(), ssim(), msssim() and xpsnr() share: the reference looked at (a slot number, numpy planes, or torch tensors on the
+        device, which are registered with the context for the call's duration), the request made by `request`, submitted with `submit` and
+        waited for; `raw` and `blocks` are written.  prev: a list of further luma planes of the window's size (xpsnr), looked at alike and
+        replaced in place by what the request is to point to"""
         nc = 3 if self.chroma_format else 1
         registered = []
+        if prev:
+            if any(tuple(p.shape) != (win[3], win[2]) for p in prev):
+                raise ValueError("%s: prev planes are luma planes of the window's size, %r" % (what, (win[3], win[2])))
+            if all(hasattr(p, "data_ptr") for p in prev):
+                if any(not p.is_cuda or p.device.index != self.cfg.device or p.element_size() not in (1, 2) or (p.shape[1] > 1 and p.stride(1) != 1) or p.stride(0) < 0 for p in prev):
+                    raise ValueError(what + ": prev tensors are row-major 2-D tensors of 1- or 2-byte elements on the context's device")
+            else:
+                prev[:] = [np.asarray(p) for p in prev]
+                if any(p.dtype not in (np.uint8, np.uint16) for p in prev):
+                    raise ValueError(what + ": prev planes are uint8 or uint16 arrays")
+                prev[:] = [p if p.strides[1] == p.itemsize and p.strides[0] > 0 else np.ascontiguousarray(p) for p in prev]
         if not isinstance(ref, int):
             ref = list(ref)[:nc]
             shapes = [(win[3] >> (1 if c else 0), win[2] >> (1 if c else 0)) for c in range(nc)]
@@ -694,8 +713,9 @@ class Reconstructor:
                     raise ValueError(what + ": reference planes are uint8 or uint16 arrays")
                 ref = [p if p.strides[1] == p.itemsize and p.strides[0] > 0 else np.ascontiguousarray(p) for p in ref]
         try:
-            if not isinstance(ref, int) and hasattr(ref[0], "data_ptr"):
-                for t in ref:
+            tensors = [t for t in ([] if isinstance(ref, int) else ref) + list(prev or ()) if hasattr(t, "data_ptr")]
+            if tensors:
+                for t in tensors:
                     ptr, n = t.data_ptr(), (sum((d - 1) * st for d, st in zip(t.shape, t.stride())) + 1) * t.element_size()
                     if any(a <= ptr and ptr + n <= a + m for a, m in self._dev) or ptr in registered:
                         continue
@@ -780,6 +800,38 @@ class Reconstructor:
         out = dict(raw=raw, bit_depth=raw.bit_depth, num_components=raw.num_components, scales=raw.scales, msssim=list(value))
         for name in ("width", "height", "windows", "sum_cs", "sum_v"):
             out[name] = [[int(v) for v in getattr(raw, name)[k]][:nc] for k in range(raw.scales)]
+        return out
+
+    def xpsnr(self, slot, ref, prev=(), window=None, job=None, block=0, filter=0, a_pic=0, peak=0, with_blocks=False):
+        """vvr_xpsnr_submit and vvr_output_wait: XPSNR of the window of `slot` against a reference frame, the block-wise sums taken on the device
+        (integers defined in vvr.h) -> dict: `xpsnr` [Y, Cb, Cr, all components together] as floats (vvr_compare_xpsnr with a_pic and peak; 0:
+        its defaults), the totals sse (per component), act_spatial, act_temporal, count, the geometry block, filter (both resolved), blocks_x,
+        blocks_y, temporal, width, height, samples, bit_depth, num_components, `raw` (the abi.FrameXpsnr) and, with_blocks, `blocks`: a
+        structured array (np.dtype(abi.XPSNR_BLOCK_FIELDS)) of blocks_y x blocks_x records.  prev: the luma planes of the reference one and two frames
+        earlier (0, 1 or 2 of them: `temporal`), of the window's size, numpy arrays or tensors as `ref` is - with a reference given by
+        pointer, of the same kind and element size.  slot, ref, window, job: as compare()."""
+        win = tuple(window or (0, 0, self.width, self.height))
+        nc = 3 if self.chroma_format else 1
+        prev = list(prev)
+        if len(prev) > 2:
+            raise ValueError("xpsnr: at most two prev planes")
+        shape = abi.xpsnr_blocks(win[2], win[3], block)
+        if shape is None:
+            raise ValueError("xpsnr: a window of at least 8 x 8, a block that is 0 or a multiple of 4, at most %d blocks" % abi.XPSNR_MAX_BLOCKS)
+        raw = abi.FrameXpsnr()
+        records = np.zeros((shape[2], shape[1]), np.dtype(abi.XPSNR_BLOCK_FIELDS))
+        self._against_reference("xpsnr", slot, ref, win, job, lambda s, j, w, r, res, b: abi.xpsnr_request(s, j, w, r, res, prev, b, block=block, filter=filter),
+                                self.L.vvr_xpsnr_submit, raw, records, prev)
+        value = (C.c_double * 4)()
+        if self.L.vvr_compare_xpsnr(C.byref(raw), records.ctypes.data, float(a_pic), float(peak), value) != abi.VVR_OK:
+            raise VvrError("vvr_compare_xpsnr: a result of vvr_xpsnr_submit")
+        out = dict(raw=raw, xpsnr=list(value), act_spatial=int(raw.act_spatial), act_temporal=int(raw.act_temporal), count=int(raw.count))
+        for name in ("bit_depth", "num_components", "temporal", "filter", "block", "blocks_x", "blocks_y"):
+            out[name] = int(getattr(raw, name))
+        for name in ("width", "height", "samples", "sse"):
+            out[name] = [int(v) for v in getattr(raw, name)][:nc]
+        if with_blocks:
+            out["blocks"] = records
         return out
 
     def write_picture(self, slot, planes):

@@ -4,6 +4,7 @@ Field names, order and widths follow include/vvr.h one to one; `tests/test_abi.p
 compiled library so the two cannot drift apart silently.
 """
 import ctypes as C
+import math
 
 VVR_ABI_VERSION = 5
 VVR_MAX_REFS = 16
@@ -414,6 +415,66 @@ def msssim_request(slot, job, window, ref, result, scales=5, blocking=True, ref_
     c = compare_request(slot, job, window, ref, result, None, blocking, ref_bytes_per_sample)
     r = MsssimRequest.from_buffer_copy(bytes(c)[:C.sizeof(MsssimRequest)])
     r.struct_size, r.scales = C.sizeof(MsssimRequest), scales
+    return r
+
+
+XPSNR_MAX_BLOCKS = 16384
+
+
+class XpsnrBlock(C.Structure):
+    """vvr_xpsnr_block: the record of one block of an XPSNR request (vvr_xpsnr_submit, vvr.h)"""
+    _fields_ = [("sse", u64 * 3), ("act_spatial", u64), ("act_temporal", u64), ("count", u32), ("pad", u32)]
+
+
+XPSNR_BLOCK_FIELDS = [("sse", "<u8", (3,)), ("act_spatial", "<u8"), ("act_temporal", "<u8"), ("count", "<u4"), ("pad", "<u4")]      # an XpsnrBlock as the fields of a numpy dtype
+
+
+class FrameXpsnr(C.Structure):
+    """vvr_frame_xpsnr: what vvr_output_wait writes for an XPSNR request (vvr_xpsnr_submit, vvr.h): the geometry and the sums over the blocks"""
+    _fields_ = [("struct_size", u32), ("bit_depth", u32), ("num_components", u32), ("temporal", u32), ("filter", u32), ("block", u32),
+                ("blocks_x", u32), ("blocks_y", u32), ("width", u32 * 3), ("height", u32 * 3), ("samples", u64 * 3), ("sse", u64 * 3),
+                ("act_spatial", u64), ("act_temporal", u64), ("count", u64)]
+
+
+class XpsnrRequest(C.Structure):
+    """vvr_xpsnr_request: XPSNR of a picture against a reference frame as a request of the output queue (vvr_xpsnr_submit, vvr.h): a
+    CompareRequest up to the reference's strides, with temporal and filter in its pad bytes and block in pad2, then the prev planes"""
+    _fields_ = [("struct_size", u32), ("slot", i32), ("job", i32), ("x", i32), ("y", i32), ("w", i32), ("h", i32), ("ref_slot", i32),
+                ("ref_bytes_per_sample", u8), ("blocking", u8), ("temporal", u8), ("filter", u8), ("block", u32),
+                ("ref", C.c_void_p * 3), ("ref_stride_bytes", C.c_size_t * 3), ("prev", C.c_void_p * 2), ("prev_stride_bytes", C.c_size_t * 2),
+                ("result", C.c_void_p), ("blocks", C.c_void_p)]
+
+
+def xpsnr_blocks(w, h, block=0):
+    """vvr_xpsnr_blocks restated: (B, blocks_x, blocks_y) of a window of w x h with the request's `block`, or None where the call refuses"""
+    if w < 8 or h < 8 or block < 0 or block & 3:
+        return None
+    b = block or max(4, 4 * int(32.0 * math.sqrt(w * h / 8294400.0) + 0.5))
+    bx, by = (w + b - 1) // b, (h + b - 1) // b
+    return (b, bx, by) if bx * by <= XPSNR_MAX_BLOCKS else None
+
+
+def xpsnr_request(slot, job, window, ref, result, prev=(), blocks=None, block=0, filter=0, blocking=True, ref_bytes_per_sample=2):
+    """an XpsnrRequest that writes into `result` (a FrameXpsnr) and, when given, `blocks` (a C-contiguous array of np.dtype(XPSNR_BLOCK_FIELDS) with
+    blocks_x * blocks_y records); prev: the luma planes o1 (, o2) as compare_request takes the reference's planes, temporal = len(prev);
+    everything else as compare_request"""
+    c = compare_request(slot, job, window, ref, result, None, blocking, ref_bytes_per_sample)
+    r = XpsnrRequest()
+    C.memmove(C.addressof(r), C.addressof(c), XpsnrRequest.prev.offset)
+    r.struct_size, r.temporal, r.filter, r.block = C.sizeof(XpsnrRequest), len(prev), filter, block
+    for k, pl in enumerate(prev):
+        if isinstance(pl, tuple):
+            r.prev[k], r.prev_stride_bytes[k] = pl
+        elif hasattr(pl, "data_ptr"):
+            r.prev[k], r.prev_stride_bytes[k] = pl.data_ptr(), pl.stride(0) * pl.element_size()
+            if isinstance(ref, int):
+                r.ref_bytes_per_sample = pl.element_size()
+        else:
+            r.prev[k], r.prev_stride_bytes[k] = pl.ctypes.data, pl.strides[0]
+            if isinstance(ref, int):
+                r.ref_bytes_per_sample = pl.itemsize
+    r.result = C.addressof(result)
+    r.blocks = None if blocks is None else blocks.ctypes.data
     return r
 
 

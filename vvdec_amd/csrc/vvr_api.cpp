@@ -90,7 +90,7 @@ static double g_wdSum[6]; static uint64_t g_wdJobs; static double g_wdPart[4], g
 
 struct Stat { uint64_t launches = 0; double ms = 0, bytes = 0; };
 struct PendingTiming { hipEvent_t a, b; int kernel; double bytes; };
-const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame", "k_output_rgb", "k_hash_rows", "k_hash_combine", "k_plane_hash_rows", "k_output_stats", "k_output_stats_sum", "k_output_compare", "k_output_compare_sum", "k_output_ssim", "k_output_ssim_sum", "k_output_yuv", "k_output_narrow", "k_output_msssim", "k_output_msssim_sum" };
+const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame", "k_output_rgb", "k_hash_rows", "k_hash_combine", "k_plane_hash_rows", "k_output_stats", "k_output_stats_sum", "k_output_compare", "k_output_compare_sum", "k_output_ssim", "k_output_ssim_sum", "k_output_yuv", "k_output_narrow", "k_output_msssim", "k_output_msssim_sum", "k_output_xpsnr" };
 
 // One slot of the upload ring: pinned staging memory and its image in HBM (grown on demand, never freed while the context lives), the device
 // pointers of the picture that currently sits in it, and the pinned landing area of its DMVR delta MVs.

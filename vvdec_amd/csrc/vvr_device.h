@@ -365,6 +365,15 @@ struct MsssimNext { uint16_t* x[3]; uint16_t* y[3]; int stride[3]; };
 struct MsssimFold { int scales, recOff[MSSSIM_MAX_SCALES], blocks[MSSSIM_MAX_SCALES]; };      // recOff: in words, a multiple of 64
 void launch_output_msssim( hipStream_t s, const CompareParams& p, int bitDepth, uint32_t* recs, const MsssimNext* next );
 void launch_output_msssim_sum( hipStream_t s, const uint32_t* recs, const MsssimFold& f, int numComp, uint32_t* out );
+// XPSNR of a picture against a reference frame (vvr_xpsnr_submit, the definition: vvr.h), on the comparison's parameters and tiles of 64 x 64 luma
+// samples (p.nbx x p.nby of them), one launch.  recs: blocksX * blocksY records of XPSNR_REC_WORDS 64-bit words, row-major, laid out as a
+// vvr_xpsnr_block - sse of the three components, the sum of |f|, the sum of t, then count in the low half of the last word - which the caller has
+// CLEARED: the launch adds to them (integer adds, exact in any order).  block: B, a multiple of 4; filter: 1 or 2; temporal: 0 .. 2 with
+// prev[0 .. temporal - 1], luma planes of the window's size, prevStride in bytes, p.refBytes per sample; p.bySample also stands for their bases
+// and strides.
+#define XPSNR_REC_WORDS 6
+struct XpsnrParams { CompareParams c; const uint8_t* prev[2]; size_t prevStride[2]; int block, blocksX, blocksY, filter, temporal; };
+void launch_output_xpsnr( hipStream_t s, const XpsnrParams& p, unsigned long long* recs );
 // decoded picture hash of the output queue (vvr_hash_submit): CRC (crc != 0) or checksum of every component of a picture, finished on the device.
 // launch_hash_rows: one launch over the rows of all planes, rows[g] = the CRC piece (the row's bytes mod P, register from 0) or the checksum share
 // of row g (the planes' rows one after the other).  launch_hash_combine: out[c] = the component's digest as a number - the checksum, or the CRC

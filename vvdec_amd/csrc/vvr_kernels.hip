@@ -6253,6 +6253,240 @@ void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks,
   hipLaunchKernelGGL( k_output_compare_sum, dim3( numComp ), dim3( 256 ), 0, s, recs, blocks, out );
 }
 
+// k_output_xpsnr — XPSNR of a picture against a reference frame (vvr_xpsnr_submit, the definition: vvr.h), on the tiles of k_output_compare: a
+// workgroup owns 64 x 64 luma samples of the window and the 32 x 32 samples of both chroma components, and in it 16 x 16 cells of 4 x 4 luma
+// samples (2 x 2 of each chroma component).  B is a multiple of 4, so a cell - its samples and its positions - lies in exactly one block.
+// Stage 1 reads as k_output_compare does: a lane loads two luma pieces and one chroma piece of 8 samples (cmp_load, the BYSAMPLE class included),
+// the halo of the reference luma around the tile (FILTER samples on every side: 260 or 528 of them, two or three to a lane, zero outside the
+// window - no position reads those) and, under the uniform `temporal`, the 4 x 4 samples of o1 and o2 of the cell it owns in stage 2; every load
+// is issued before the first value is looked at.  The reference luma goes into LDS as 16-bit words, ( 64 + 2 FILTER )^2 of
+// them, once; the squared differences go into LDS per row and cell - a half piece of luma (four d * d: 34 bits), a quarter piece of chroma - so
+// that no sum crosses a cell.  Stage 2: lane ( tid & 15, tid >> 4 ) owns that cell.  It adds up the cell's rows of squared differences, reads the
+// ( 4 + 2 FILTER )^2 reference samples around its cell from LDS (rows of dwords) and evaluates its 16 (filter 1) or 4 (filter 2) positions:
+// |f| < 2^22 and t <= 2^20, so a cell's sums fit 32 bits; everything beyond a cell is 64 bits.  Reduction per block on chip: a wavefront (4 rows of
+// cells) whose cells all lie in one block - every wavefront when B is a multiple of 64 - folds its six values in registers and lane 0 adds them
+// to the block's accumulator in LDS; otherwise every lane adds its own (ds_add_u64).  The tile meets at most 16 x 16 blocks; after the barrier
+// lane l adds the non-zero words of local block l to the request's cleared records with 64-bit vector atomics.  Integer adds: the result does
+// not depend on the order, hence not on scheduling.  At 4K with B = 128 a tile meets one block: six adds.
+template<int RB, bool BYSAMPLE>
+__device__ __forceinline__ uint32_t xps_sample( const uint8_t* __restrict__ base, size_t stride, int i, int j )
+{
+  const uint8_t* __restrict__ r = base + (size_t) j * stride + (size_t) i * RB;
+  if( RB == 1 ) return r[0];
+  if( BYSAMPLE ) return (uint32_t) r[0] | (uint32_t) r[1] << 8;
+  return *(const uint16_t*) r;
+}
+struct XpsCell { uint2 row[4]; };      // 4 x 4 samples of a plane: RB == 2 two to a dword, RB == 1 the row's four bytes in x
+template<int RB, bool BYSAMPLE>
+__device__ __forceinline__ XpsCell xps_cell( const uint8_t* __restrict__ base, size_t stride, int i0, int j0, int w, int h )
+{
+  XpsCell q;
+#pragma unroll
+  for( int r = 0; r < 4; r++ ) q.row[r] = make_uint2( 0, 0 );
+  if( i0 >= w || j0 >= h ) return q;
+  if( !BYSAMPLE && i0 + 4 <= w && j0 + 4 <= h )
+  {
+#pragma unroll
+    for( int r = 0; r < 4; r++ )
+    {
+      const uint8_t* __restrict__ s = base + (size_t) ( j0 + r ) * stride + (size_t) i0 * RB;
+      if( RB == 2 ) __builtin_memcpy( &q.row[r], s, 8 ); else __builtin_memcpy( &q.row[r].x, s, 4 );
+    }
+    return q;
+  }
+#pragma unroll
+  for( int r = 0; r < 4; r++ )
+  {
+    uint32_t v[4] = { 0, 0, 0, 0 };
+#pragma unroll
+    for( int i = 0; i < 4; i++ ) if( i0 + i < w && j0 + r < h ) v[i] = xps_sample<RB, BYSAMPLE>( base, stride, i0 + i, j0 + r );
+    q.row[r] = RB == 2 ? make_uint2( v[0] | v[1] << 16, v[2] | v[3] << 16 ) : make_uint2( v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24, 0 );
+  }
+  return q;
+}
+template<int RB>
+__device__ __forceinline__ int xps_at( const XpsCell& q, int i, int r )
+{
+  return RB == 2 ? (int) ( ( ( i < 2 ? q.row[r].x : q.row[r].y ) >> ( 16 * ( i & 1 ) ) ) & 0xffff ) : (int) ( ( q.row[r].x >> ( 8 * i ) ) & 0xff );
+}
+template<int RB>
+__device__ __forceinline__ uint64_t xps_sse( const CmpPiece& q, int from, int to )      // the sum of d * d over samples from .. to - 1 of a piece
+{
+  const uint32_t wa[4] = { q.a.x, q.a.y, q.a.z, q.a.w }, wb[4] = { q.b.x, q.b.y, q.b.z, q.b.w };
+  uint64_t sse = 0;
+#pragma unroll
+  for( int i = from; i < to; i++ )
+  {
+    const int a = (int) ( ( wa[i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffff );
+    const int b = RB == 2 ? (int) ( ( wb[i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffff ) : (int) ( ( wb[i >> 2] >> ( 8 * ( i & 3 ) ) ) & 0xff );
+    const uint32_t ad = i < q.n ? (uint32_t) abs( a - b ) : 0u;
+    sse += (uint64_t) ( ad * ad );
+  }
+  return sse;
+}
+template<int RB>
+__device__ __forceinline__ uint32_t xps_ref( const CmpPiece& q, int i )      // reference sample i of a piece; 0 where the piece has none
+{
+  const uint32_t wb[4] = { q.b.x, q.b.y, q.b.z, q.b.w };
+  const uint32_t b = RB == 2 ? ( wb[i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffff : ( wb[i >> 2] >> ( 8 * ( i & 3 ) ) ) & 0xff;
+  return i < q.n ? b : 0u;
+}
+__device__ __forceinline__ uint64_t xps_wave( uint64_t v )      // over the wavefront, in every lane
+{
+#pragma unroll
+  for( int d = 1; d < 64; d <<= 1 )
+  {
+    const uint32_t lo = (uint32_t) __shfl_xor( (int) (uint32_t) v, d ), hi = (uint32_t) __shfl_xor( (int) (uint32_t) ( v >> 32 ), d );
+    v += lo | (uint64_t) hi << 32;
+  }
+  return v;
+}
+template<int RB, bool BYSAMPLE, int FILTER>
+__global__ __launch_bounds__( 256 ) void k_output_xpsnr( XpsnrParams P, unsigned long long* __restrict__ recs )
+{
+  constexpr int HALO = FILTER, T = 64 + 2 * HALO, R = 4 + 2 * HALO, NH = T * T - 64 * 64, HL = ( NH + 255 ) / 256;
+  __shared__ uint16_t tile[T * T];                               // the reference luma: tile ( 0, 0 ) is sample ( X0 - HALO, Y0 - HALO )
+  __shared__ unsigned long long lsse[64][16];                    // luma: d * d summed over the four samples of row r in cell column k
+  __shared__ unsigned long long csse[2][32][16];                 // chroma: the same over two samples
+  __shared__ unsigned long long acc[256][XPSNR_REC_WORDS];       // the tile's local blocks
+  const CompareParams& p = P.c;
+  const int tid = threadIdx.x, cc = 1 + ( tid >> 7 ), ct = tid & 127, cx = tid & 15, cy = tid >> 4;
+  const int X0 = blockIdx.x * 64, Y0 = blockIdx.y * 64, W = p.w[0], H = p.h[0], B = P.block;
+  // ---- stage 1: every load
+  const CmpPiece q0 = cmp_load<RB, BYSAMPLE>( p, 0, X0 + ( tid & 7 ) * 8, Y0 + ( tid >> 3 ) );
+  const CmpPiece q1 = cmp_load<RB, BYSAMPLE>( p, 0, X0 + ( tid & 7 ) * 8, Y0 + 32 + ( tid >> 3 ) );
+  const CmpPiece q2 = cmp_load<RB, BYSAMPLE>( p, cc, ( X0 >> 1 ) + ( ct & 3 ) * 8, ( Y0 >> 1 ) + ( ct >> 2 ) );
+  uint32_t hv[HL]; int hat[HL];
+#pragma unroll
+  for( int n = 0; n < HL; n++ )
+  {
+    // halo sample k: HALO rows above, HALO rows below (T wide), then 2 HALO samples of each of the 64 rows between
+    const int k = tid + 256 * n;
+    int tx, ty;
+    if( k < 2 * HALO * T ) { ty = k / T; tx = k - ty * T; if( ty >= HALO ) ty += 64; }
+    else { const int k3 = k - 2 * HALO * T, s = k3 % ( 2 * HALO ); ty = HALO + k3 / ( 2 * HALO ); tx = s < HALO ? s : 64 + s; }
+    const int gi = X0 - HALO + tx, gj = Y0 - HALO + ty;
+    hat[n] = k < NH ? ty * T + tx : -1; hv[n] = 0;
+    if( k < NH && gi >= 0 && gj >= 0 && gi < W && gj < H ) hv[n] = xps_sample<RB, BYSAMPLE>( p.ref[0], p.refStride[0], gi, gj );
+  }
+  const int gx = X0 + 4 * cx, gy = Y0 + 4 * cy;
+  XpsCell o1, o2;
+#pragma unroll
+  for( int r = 0; r < 4; r++ ) o1.row[r] = o2.row[r] = make_uint2( 0, 0 );
+  if( P.temporal >= 1 ) o1 = xps_cell<RB, BYSAMPLE>( P.prev[0], P.prevStride[0], gx, gy, W, H );
+  if( P.temporal >= 2 ) o2 = xps_cell<RB, BYSAMPLE>( P.prev[1], P.prevStride[1], gx, gy, W, H );
+  // ---- into LDS: the reference luma, the squared differences per row and cell, cleared accumulators
+#pragma unroll
+  for( int i = 0; i < 8; i++ )
+  {
+    tile[( ( tid >> 3 ) + HALO ) * T + ( tid & 7 ) * 8 + HALO + i] = (uint16_t) xps_ref<RB>( q0, i );
+    tile[( ( tid >> 3 ) + 32 + HALO ) * T + ( tid & 7 ) * 8 + HALO + i] = (uint16_t) xps_ref<RB>( q1, i );
+  }
+#pragma unroll
+  for( int n = 0; n < HL; n++ ) if( hat[n] >= 0 ) tile[hat[n]] = (uint16_t) hv[n];
+  lsse[tid >> 3][2 * ( tid & 7 )] = xps_sse<RB>( q0, 0, 4 ); lsse[tid >> 3][2 * ( tid & 7 ) + 1] = xps_sse<RB>( q0, 4, 8 );
+  lsse[32 + ( tid >> 3 )][2 * ( tid & 7 )] = xps_sse<RB>( q1, 0, 4 ); lsse[32 + ( tid >> 3 )][2 * ( tid & 7 ) + 1] = xps_sse<RB>( q1, 4, 8 );
+#pragma unroll
+  for( int k = 0; k < 4; k++ ) csse[cc - 1][ct >> 2][4 * ( ct & 3 ) + k] = xps_sse<RB>( q2, 2 * k, 2 * k + 2 );
+#pragma unroll
+  for( int k = 0; k < XPSNR_REC_WORDS; k++ ) acc[tid][k] = 0;
+  __syncthreads();
+  // ---- stage 2: the cell ( cx, cy )
+  const bool inside = gx < W && gy < H;
+  uint64_t v[XPSNR_REC_WORDS];
+  v[0] = lsse[4 * cy][cx] + lsse[4 * cy + 1][cx] + lsse[4 * cy + 2][cx] + lsse[4 * cy + 3][cx];
+  v[1] = csse[0][2 * cy][cx] + csse[0][2 * cy + 1][cx];
+  v[2] = csse[1][2 * cy][cx] + csse[1][2 * cy + 1][cx];
+  uint32_t rg[R][R / 2];
+  typedef uint32_t __attribute__(( may_alias )) tile_word_t;
+  const tile_word_t* t32 = (const tile_word_t*) tile;
+#pragma unroll
+  for( int r = 0; r < R; r++ )
+#pragma unroll
+    for( int k = 0; k < R / 2; k++ ) rg[r][k] = t32[( ( 4 * cy + r ) * T + 4 * cx ) / 2 + k];      // (T and 4 cx are even)
+  auto o = [&]( int i, int j ) { return (int) ( ( rg[j][i >> 1] >> ( 16 * ( i & 1 ) ) ) & 0xffff ); };      // sample ( gx - HALO + i, gy - HALO + j )
+  uint32_t actS = 0, actT = 0, count = 0;
+  if( FILTER == 1 )
+  {
+#pragma unroll
+    for( int b = 0; b < 4; b++ )
+#pragma unroll
+      for( int a = 0; a < 4; a++ )
+      {
+        const int i = gx + a, j = gy + b;
+        if( i < 1 || j < 1 || i > W - 2 || j > H - 2 ) continue;
+        const int f = 12 * o( a + 1, b + 1 ) - 2 * ( o( a, b + 1 ) + o( a + 2, b + 1 ) + o( a + 1, b ) + o( a + 1, b + 2 ) )
+                      - ( o( a, b ) + o( a + 2, b ) + o( a, b + 2 ) + o( a + 2, b + 2 ) );
+        int t = 0;
+        if( P.temporal == 1 ) t = o( a + 1, b + 1 ) - xps_at<RB>( o1, a, b );
+        else if( P.temporal == 2 ) t = o( a + 1, b + 1 ) - 2 * xps_at<RB>( o1, a, b ) + xps_at<RB>( o2, a, b );
+        actS += (uint32_t) abs( f ); actT += (uint32_t) abs( t ); count++;
+      }
+  }
+  else
+  {
+#pragma unroll
+    for( int b = 0; b < 4; b += 2 )
+#pragma unroll
+      for( int a = 0; a < 4; a += 2 )
+      {
+        const int i = gx + a, j = gy + b;
+        if( i < 2 || j < 2 || i > W - 4 || j > H - 4 ) continue;
+        // the 6 x 6 weights of vvr.h by rings of 2 x 2 sums: 12 x the centre, -3 x its edge neighbours, -2 x the inner corners, -1 x the outer ring
+        const int centre = o( a + 2, b + 2 ) + o( a + 3, b + 2 ) + o( a + 2, b + 3 ) + o( a + 3, b + 3 );
+        const int edges = o( a + 2, b + 1 ) + o( a + 3, b + 1 ) + o( a + 2, b + 4 ) + o( a + 3, b + 4 ) + o( a + 1, b + 2 ) + o( a + 1, b + 3 ) + o( a + 4, b + 2 ) + o( a + 4, b + 3 );
+        const int corners = o( a + 1, b + 1 ) + o( a + 4, b + 1 ) + o( a + 1, b + 4 ) + o( a + 4, b + 4 );
+        const int ring = o( a + 1, b ) + o( a + 2, b ) + o( a + 3, b ) + o( a + 4, b ) + o( a + 1, b + 5 ) + o( a + 2, b + 5 ) + o( a + 3, b + 5 ) + o( a + 4, b + 5 )
+                         + o( a, b + 1 ) + o( a, b + 2 ) + o( a, b + 3 ) + o( a, b + 4 ) + o( a + 5, b + 1 ) + o( a + 5, b + 2 ) + o( a + 5, b + 3 ) + o( a + 5, b + 4 );
+        const int f = 12 * centre - 3 * edges - 2 * corners - ring;
+        int t = 0;
+        if( P.temporal >= 1 )
+        {
+          const int s1 = xps_at<RB>( o1, a, b ) + xps_at<RB>( o1, a + 1, b ) + xps_at<RB>( o1, a, b + 1 ) + xps_at<RB>( o1, a + 1, b + 1 );
+          const int s2 = xps_at<RB>( o2, a, b ) + xps_at<RB>( o2, a + 1, b ) + xps_at<RB>( o2, a, b + 1 ) + xps_at<RB>( o2, a + 1, b + 1 );
+          t = P.temporal == 1 ? centre - s1 : centre - 2 * s1 + s2;
+        }
+        actS += (uint32_t) abs( f ); actT += (uint32_t) abs( t ); count++;
+      }
+  }
+  v[3] = actS; v[4] = actT; v[5] = count;
+  // ---- per block: the cell's local block (a cell outside the window holds zeros and counts with the last block inside)
+  const int lx = min( gx, W - 1 ) / B - X0 / B, ly = min( gy, H - 1 ) / B - Y0 / B, li = ly * 16 + lx;
+  const int li0 = __shfl( li, 0 );
+  if( __all( li == li0 ) )
+  {
+#pragma unroll
+    for( int k = 0; k < XPSNR_REC_WORDS; k++ ) v[k] = xps_wave( v[k] );
+    if( ( tid & 63 ) == 0 )
+#pragma unroll
+      for( int k = 0; k < XPSNR_REC_WORDS; k++ ) if( v[k] ) atomicAdd( &acc[li][k], (unsigned long long) v[k] );
+  }
+  else if( inside )
+  {
+#pragma unroll
+    for( int k = 0; k < XPSNR_REC_WORDS; k++ ) if( v[k] ) atomicAdd( &acc[li][k], (unsigned long long) v[k] );
+  }
+  __syncthreads();
+  const int bx = X0 / B + ( tid & 15 ), by = Y0 / B + ( tid >> 4 );
+  if( bx >= P.blocksX || by >= P.blocksY ) return;
+  unsigned long long* __restrict__ rec = recs + ( (size_t) by * P.blocksX + bx ) * XPSNR_REC_WORDS;
+#pragma unroll
+  for( int k = 0; k < XPSNR_REC_WORDS; k++ ) { const unsigned long long a = acc[tid][k]; if( a ) atomicAdd( rec + k, a ); }
+}
+template<int RB, bool BYSAMPLE>
+static void launch_output_xpsnr_as( hipStream_t s, const XpsnrParams& p, unsigned long long* recs )
+{
+  const dim3 grid( p.c.nbx, p.c.nby );
+  if( p.filter == 2 ) hipLaunchKernelGGL( ( k_output_xpsnr<RB, BYSAMPLE, 2> ), grid, dim3( 256 ), 0, s, p, recs );
+  else hipLaunchKernelGGL( ( k_output_xpsnr<RB, BYSAMPLE, 1> ), grid, dim3( 256 ), 0, s, p, recs );
+}
+void launch_output_xpsnr( hipStream_t s, const XpsnrParams& p, unsigned long long* recs )
+{
+  if( p.c.bySample ) { if( p.c.refBytes == 1 ) launch_output_xpsnr_as<1, true>( s, p, recs ); else launch_output_xpsnr_as<2, true>( s, p, recs ); }
+  else if( p.c.refBytes == 1 ) launch_output_xpsnr_as<1, false>( s, p, recs );
+  else launch_output_xpsnr_as<2, false>( s, p, recs );
+}
+
 // k_output_ssim — SSIM of a picture against a reference frame (vvr_ssim_submit, the definition: vvr.h), on the blocks of k_output_compare: a workgroup
 // owns the SSIM windows (8 x 8 samples at a stride of 4) whose origin lies in its block of 64 x 64 luma samples and in the 32 x 32 samples of both
 // chroma components.  Such a window reaches 4 samples into the blocks to the right and below, so the workgroup reads 68 x 68 luma and 36 x 36 chroma

@@ -689,6 +689,49 @@ void launch_output_msssim_sum( hipStream_t, const uint32_t* recs, const MsssimFo
       o[0] = (uint32_t) cs; o[1] = (uint32_t) ( cs >> 32 ); o[2] = (uint32_t) v; o[3] = (uint32_t) ( v >> 32 );
     }
 }
+
+// ... and launch_output_xpsnr (k_output_xpsnr): the definition of vvr.h sample by sample and position by position, every squared difference and
+// every position added to the record of the block that holds it; the weights of filter 2 as the table vvr.h prints
+void launch_output_xpsnr( hipStream_t, const XpsnrParams& P, unsigned long long* recs )
+{
+  static const int W2[6][6] = { { 0, -1, -1, -1, -1, 0 }, { -1, -2, -3, -3, -2, -1 }, { -1, -3, 12, 12, -3, -1 }, { -1, -3, 12, 12, -3, -1 }, { -1, -2, -3, -3, -2, -1 }, { 0, -1, -1, -1, -1, 0 } };
+  const CompareParams& p = P.c;
+  const int B = P.block, w = p.w[0], h = p.h[0];
+  auto sample = [&]( const uint8_t* base, size_t stride, int i, int j ) { const uint8_t* r = base + (size_t) j * stride + (size_t) i * p.refBytes; return (int64_t) ( p.refBytes == 1 ? r[0] : r[0] | r[1] << 8 ); };
+  auto o = [&]( int i, int j ) { return sample( p.ref[0], p.refStride[0], i, j ); };
+  auto o1 = [&]( int i, int j ) { return sample( P.prev[0], P.prevStride[0], i, j ); };
+  auto o2 = [&]( int i, int j ) { return sample( P.prev[1], P.prevStride[1], i, j ); };
+  for( int c = 0; c < p.numComp; c++ )
+    for( int j = 0; j < p.h[c]; j++ )
+      for( int i = 0; i < p.w[c]; i++ )
+      {
+        const int sh = c ? 1 : 0;
+        const int64_t d = (int64_t) (uint16_t) p.src[c][(size_t) j * p.stride[c] + i] - sample( p.ref[c], p.refStride[c], i, j );
+        recs[( (size_t) ( ( j << sh ) / B ) * P.blocksX + ( i << sh ) / B ) * XPSNR_REC_WORDS + c] += (uint64_t) ( d * d );
+      }
+  const int step = P.filter == 2 ? 2 : 1, first = P.filter == 2 ? 2 : 1, lastX = P.filter == 2 ? w - 4 : w - 2, lastY = P.filter == 2 ? h - 4 : h - 2;
+  for( int j = first; j <= lastY; j += step )
+    for( int i = first; i <= lastX; i += step )
+    {
+      int64_t f = 0, t = 0;
+      if( P.filter == 1 )
+      {
+        f = 12 * o( i, j ) - 2 * ( o( i - 1, j ) + o( i + 1, j ) + o( i, j - 1 ) + o( i, j + 1 ) ) - ( o( i - 1, j - 1 ) + o( i + 1, j - 1 ) + o( i - 1, j + 1 ) + o( i + 1, j + 1 ) );
+        if( P.temporal == 1 ) t = o( i, j ) - o1( i, j );
+        if( P.temporal == 2 ) t = o( i, j ) - 2 * o1( i, j ) + o2( i, j );
+      }
+      else
+      {
+        for( int dj = 0; dj < 6; dj++ )
+          for( int di = 0; di < 6; di++ ) f += W2[dj][di] * o( i - 2 + di, j - 2 + dj );
+        auto S = [&]( auto& a ) { return a( i, j ) + a( i + 1, j ) + a( i, j + 1 ) + a( i + 1, j + 1 ); };
+        if( P.temporal == 1 ) t = S( o ) - S( o1 );
+        if( P.temporal == 2 ) t = S( o ) - 2 * S( o1 ) + S( o2 );
+      }
+      unsigned long long* rec = recs + ( (size_t) ( j / B ) * P.blocksX + i / B ) * XPSNR_REC_WORDS;
+      rec[3] += (uint64_t) ( f < 0 ? -f : f ); rec[4] += (uint64_t) ( t < 0 ? -t : t ); rec[5] += 1;
+    }
+}
 #endif
 
 extern "C" {
@@ -1049,6 +1092,47 @@ VVR_API int vvr_compare_msssim( const vvr_frame_msssim* ms, const double* weight
   return VVR_OK;
 }
 
+// the block size and the grid of blocks of an XPSNR request (vvr_xpsnr_submit), as vvr.h gives them
+VVR_API int vvr_xpsnr_blocks( int w, int h, uint32_t block, uint32_t* resolvedBlock, uint32_t* blocksX, uint32_t* blocksY )
+{
+  if( !resolvedBlock || !blocksX || !blocksY || w < 8 || h < 8 || ( block & 3 ) ) return VVR_ERR_PARAMETER;
+  const uint64_t B = block ? block : (uint64_t) std::max( 4, 4 * (int) ( 32.0 * sqrt( (double) w * (double) h / 8294400.0 ) + 0.5 ) );
+  const uint64_t bx = ( (uint64_t) w + B - 1 ) / B, by = ( (uint64_t) h + B - 1 ) / B;
+  if( bx * by > VVR_XPSNR_MAX_BLOCKS ) return VVR_ERR_PARAMETER;
+  *resolvedBlock = (uint32_t) B; *blocksX = (uint32_t) bx; *blocksY = (uint32_t) by;
+  return VVR_OK;
+}
+
+// XPSNR from the records of an XPSNR request (vvr_xpsnr_submit), the formula as vvr.h gives it, in double, the blocks in ascending order
+VVR_API int vvr_compare_xpsnr( const vvr_frame_xpsnr* f, const vvr_xpsnr_block* blocks, double aPic, double peak, double xpsnr[4] )
+{
+  if( !f || !blocks || !xpsnr || f->struct_size != sizeof( vvr_frame_xpsnr ) || f->bit_depth < 8 || f->bit_depth > 10 || !f->samples[0] ||
+      !( (uint64_t) f->blocks_x * f->blocks_y ) || f->filter < 1 || f->filter > 2 ) return VVR_ERR_PARAMETER;
+  const int nc = f->num_components == 1 ? 1 : 3;
+  if( peak <= 0 ) peak = (double) ( ( 1u << f->bit_depth ) - 1 );
+  if( aPic <= 0 ) aPic = ldexp( 1.0, 2 * (int) f->bit_depth - 9 ) * sqrt( 3840.0 * 2160.0 / ( (double) f->width[0] * (double) f->height[0] ) );
+  const double root = sqrt( aPic ), floorAct = ldexp( 1.0, (int) f->bit_depth - 6 );
+  double wsse[3] = { 0, 0, 0 };
+  for( uint64_t k = 0; k < (uint64_t) f->blocks_x * f->blocks_y; k++ )
+  {
+    const vvr_xpsnr_block& b = blocks[k];
+    const double q = (double) b.count * ( f->filter == 2 ? 4 : 1 );
+    double act = b.count ? 1 + (double) b.act_spatial / q + 2 * (double) b.act_temporal / q : 0;
+    act = std::max( act, floorAct );
+    const double wk = root / act;
+    for( int c = 0; c < nc; c++ ) wsse[c] += wk * (double) b.sse[c];
+  }
+  double out[4] = { 0, 0, 0, 0 }, allW = 0, allN = 0;
+  for( int c = 0; c < nc; c++ )
+  {
+    out[c] = wsse[c] == 0 ? HUGE_VAL : 10 * log10( peak * peak * (double) f->samples[c] / wsse[c] );
+    allW += wsse[c]; allN += (double) f->samples[c];
+  }
+  out[3] = allW == 0 ? HUGE_VAL : 10 * log10( peak * peak * allN / allW );
+  memcpy( xpsnr, out, sizeof( out ) );
+  return VVR_OK;
+}
+
 VVR_API int vvr_read_output_grain( vvr_context* c, int slot, int x, int y, int w, int h, int bytesPerSample, void* const dst[3], const size_t dstStrideBytes[3] )
 {
   if( !c || slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] || !dst || !dstStrideBytes ) return VVR_ERR_PARAMETER;
@@ -1251,7 +1335,9 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // An SSIM request (vvr_ssim_submit) is a comparison request with other kernels (k_output_ssim, k_output_ssim_sum), records and words: both calls
 // go through compareSubmit.  So does an MS-SSIM request (vvr_msssim_submit): a k_output_msssim per scale, each but the last writing the next
 // level of both images into the pyramid that lies behind the records and words in the entry's `dev`, and one k_output_msssim_sum; only level 0
-// reads the slots and the reference, so `read` is recorded behind it.
+// reads the slots and the reference, so `read` is recorded behind it.  And an XPSNR request (vvr_xpsnr_submit): its prev planes take the
+// reference's steps - home, staging behind the reference's planes, devRanges bookkeeping - its records are cleared on the stream and added to
+// by one k_output_xpsnr, and they cross PCIe as they are: vvr_output_wait sums them.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -1262,8 +1348,8 @@ struct OutEntry {
   char* host = nullptr; size_t hostCap = 0;      // pinned: the output (unless it goes straight to the caller's pinned memory), then the words
   hipEvent_t read = nullptr, done = nullptr;     // behind the last kernel; behind the last copy
   bool direct = false, queued = false;           // direct: vvr_output_wait copies nothing (pinned or device destinations); queued: something was enqueued (done has been recorded)
-  bool devDst = false; size_t extent[3] = { 0, 0, 0 };      // the destination planes lie in device memory: dst[k] .. dst[k] + extent[k]
-  int nc = 0, rows[3] = { 0, 0, 0 }; size_t off[3] = { 0, 0, 0 }, rowBytes[3] = { 0, 0, 0 }, dstStride[3] = { 0, 0, 0 }; void* dst[3] = { nullptr, nullptr, nullptr };
+  bool devDst = false; size_t extent[5] = { 0, 0, 0, 0, 0 };      // the destination planes lie in device memory: dst[k] .. dst[k] + extent[k] (five: an XPSNR request's reference and prev planes)
+  int nc = 0, rows[3] = { 0, 0, 0 }; size_t off[3] = { 0, 0, 0 }, rowBytes[3] = { 0, 0, 0 }, dstStride[3] = { 0, 0, 0 }; void* dst[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
   bool timed = false; PendingTiming timing;
   // a hash request: method + 1 (0: an output request); planes of planeBytes[] at off[] in `host` (MD5) or one word per component at its start
   int hash = 0, hashNc = 0; size_t planeBytes[3] = { 0, 0, 0 };
@@ -1280,7 +1366,12 @@ struct OutEntry {
   // ... or an MS-SSIM request (msScales > 0: its number of scales), a comparison request too: MSSSIM_OUT_WORDS words per level and component at the
   // start of `host`, cmpOut pointing to a vvr_frame_msssim, no map; `dev` holds the records of all levels, the words, then the pyramid
   int msScales = 0;
+  // ... or an XPSNR request (xps), a comparison request too: its records - blocks of XPSNR_REC_WORDS 64-bit words, a vvr_xpsnr_block each - at the
+  // start of `dev` (cleared, then added to by k_output_xpsnr) and of `host`; cmpOut points to a vvr_frame_xpsnr; what vvr_output_wait writes
+  bool xps = false; int xpsTemporal = 0, xpsFilter = 0, xpsBlock = 0, xpsBx = 0, xpsBy = 0; vvr_xpsnr_block* xpsBlocks = nullptr;
 };
+// what vvr_xpsnr_submit adds to a comparison request: checked values (temporal 0 .. 2, filter resolved or 0, block 0 or a multiple of 4) and the prev planes
+struct XpsnrAsk { int temporal, filter; uint32_t block; const void* prev[2]; size_t prevStride[2]; vvr_xpsnr_block* blocks; };
 #define CMP_HEAD_WORDS 32      /* 3 x CMP_OUT_WORDS, rounded up: the map starts at a multiple of 128 bytes */
 
 static void destroyOutputQueue( vvr_context* c )
@@ -1385,7 +1476,7 @@ int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blockin
 void outTake( vvr_context* c, OutEntry* e, int slot, int job, int jobFailed )
 {
   e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
-  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0; e->cmp = 0; e->msScales = 0; e->refSlot = -1;
+  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0; e->cmp = 0; e->msScales = 0; e->xps = false; e->refSlot = -1;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
   if( e->timed2 ) { hipEventDestroy( e->timing2.a ); hipEventDestroy( e->timing2.b ); e->timed2 = false; }
 }
@@ -1852,9 +1943,10 @@ VVR_API int vvr_stats_submit( vvr_context* c, const vvr_stats_request* rq )
 // vvr_output_wait writes.  A vvr_ssim_request is a vvr_compare_request field by field (result and map are pointers to other types)
 static_assert( sizeof( vvr_ssim_request ) == sizeof( vvr_compare_request ) && offsetof( vvr_ssim_request, ref ) == offsetof( vvr_compare_request, ref ) &&
                offsetof( vvr_ssim_request, result ) == offsetof( vvr_compare_request, result ) && offsetof( vvr_ssim_request, map ) == offsetof( vvr_compare_request, map ), "vvr_ssim_request mirrors vvr_compare_request" );
-static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const char* who, bool ssim, int scales = 0 )      // scales > 0: vvr_msssim_submit
+static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const char* who, bool ssim, int scales = 0, const XpsnrAsk* xp = nullptr )      // scales > 0: vvr_msssim_submit; xp: vvr_xpsnr_submit
 {
   const bool ms = scales > 0;
+  const int temporal = xp ? xp->temporal : 0;
   // ---- 1. the request (its struct_size has been looked at)
   const int slot = rq->slot, refSlot = rq->ref_slot, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot", who );
@@ -1865,11 +1957,15 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot, not the slot)
   if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, empty, or odd in 4:2:0", who );
   if( ssim && ( w < 8 || h < 8 ) ) return outRefuse( c, "a window below 8 x 8 holds no SSIM window", who );
+  uint32_t xpB = 0, xpBx = 0, xpBy = 0;
+  if( xp && ( w < 8 || h < 8 ) ) return outRefuse( c, "a window below 8 x 8", who );
+  if( xp && vvr_xpsnr_blocks( w, h, xp->block, &xpB, &xpBx, &xpBy ) != VVR_OK ) return outRefuse( c, "more than 16384 blocks", who );
   for( int k = 0; k < nc && ms; k++ )
     if( ( ( w >> ( k ? 1 : 0 ) ) >> ( scales - 1 ) ) < 8 || ( ( h >> ( k ? 1 : 0 ) ) >> ( scales - 1 ) ) < 8 ) return outRefuse( c, "a component has no 8 x 8 window at the last level: the window takes fewer scales", who );
   const int rb = refSlot >= 0 ? 2 : rq->ref_bytes_per_sample;
   CompareParams p; memset( &p, 0, sizeof( p ) );
   size_t rowBytes[3] = { 0, 0, 0 }, extent[3] = { 0, 0, 0 };
+  size_t prevExtent[2] = { 0, 0 };
   for( int k = 0; k < nc; k++ ) { const int sh = k ? 1 : 0; p.w[k] = w >> sh; p.h[k] = h >> sh; p.src[k] = d.p[k] + (size_t) ( y >> sh ) * d.stride[k] + ( x >> sh ); p.stride[k] = d.stride[k]; }
   p.numComp = nc; p.refBytes = rb; p.nbx = ( w + 63 ) / 64; p.nby = ( h + 63 ) / 64;
   if( refSlot >= 0 )
@@ -1887,6 +1983,13 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
       if( !rq->ref[k] || rq->ref_stride_bytes[k] < rowBytes[k] ) return outRefuse( c, "missing reference plane or stride below the window's row", who );
     }
   }
+  if( temporal && rb != 1 && rb != 2 ) return outRefuse( c, "ref_bytes_per_sample must be 1 or 2", who );
+  const size_t prevRow = (size_t) w * rb;      // (the prev planes of an XPSNR request: luma of the window's size, always the caller's memory)
+  for( int k = 0; k < temporal; k++ )
+  {
+    if( !xp->prev[k] || xp->prevStride[k] < prevRow ) return outRefuse( c, "missing prev plane or stride below the window's row", who );
+    prevExtent[k] = (size_t) ( h - 1 ) * xp->prevStride[k] + prevRow;
+  }
   hipSetDevice( c->device );
   std::unique_lock<std::mutex> lk( c->mu );
   // ---- where the reference lies: device memory the context knows (every plane wholly inside a range), or the host
@@ -1900,10 +2003,21 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
       if( b < r.p + r.n && b + extent[k] > r.p ) { c->setError( std::string( who ) + ": a reference plane lies partly inside a device range (vvr_device_alloc / vvr_device_register)" ); return VVR_ERR_PARAMETER; }
     }
   }
-  if( devPlanes && devPlanes != nc ) { c->setError( std::string( who ) + ": reference planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
-  const bool devRef = devPlanes != 0, staged = refSlot < 0 && !devRef;
-  bool pinnedRef = staged;
-  for( int k = 0; k < nc && pinnedRef; k++ ) pinnedRef = c->pinned.contains( rq->ref[k], extent[k] );
+  for( int k = 0; k < temporal; k++ )
+  {
+    const char* b = (const char*) xp->prev[k];
+    for( const DevRange& r : c->devRanges )
+    {
+      if( b >= r.p && b + prevExtent[k] <= r.p + r.n ) { devPlanes++; break; }
+      if( b < r.p + r.n && b + prevExtent[k] > r.p ) { c->setError( std::string( who ) + ": a prev plane lies partly inside a device range (vvr_device_alloc / vvr_device_register)" ); return VVR_ERR_PARAMETER; }
+    }
+  }
+  if( devPlanes && devPlanes != ( refSlot < 0 ? nc : 0 ) + temporal ) { c->setError( std::string( who ) + ": reference planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
+  // (staged: the reference planes go through `tmp`; stagedPrev: the prev planes of an XPSNR request do, behind them - also beside a ref_slot)
+  const bool devRef = devPlanes != 0, staged = refSlot < 0 && !devRef, stagedPrev = temporal && !devRef;
+  bool pinnedRef = staged || stagedPrev;
+  for( int k = 0; k < nc && pinnedRef && staged; k++ ) pinnedRef = c->pinned.contains( rq->ref[k], extent[k] );
+  for( int k = 0; k < temporal && pinnedRef; k++ ) pinnedRef = c->pinned.contains( xp->prev[k], prevExtent[k] );
   // ---- the entry's buffers: the blocks' records, the folded words and the map behind them; a reference from the host packed in `tmp`, rows at a
   // multiple of 16 bytes; pinned: the folded words and the map, then the staging of a reference in pageable memory
   const int blocks = p.nbx * p.nby, recWords = ssim ? SSIM_REC_WORDS : CMP_REC_WORDS, outWords = ssim ? SSIM_OUT_WORDS : CMP_OUT_WORDS;
@@ -1928,14 +2042,18 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
     }
     wordBytes = sizeof( uint32_t ) * MSSSIM_OUT_WORDS * 3 * MSSSIM_MAX_SCALES; crossBytes = sizeof( uint32_t ) * MSSSIM_OUT_WORDS * nc * scales;
   }
+  // XPSNR: the records are the words - cleared on the device, added to by the one launch, copied back whole
+  if( xp ) { recBytes = 0; wordBytes = crossBytes = sizeof( unsigned long long ) * XPSNR_REC_WORDS * xpBx * xpBy; }
   const size_t hostStageOff = alignUp( wordBytes, 256 ), pyrBase = alignUp( recBytes + wordBytes, 256 );
   size_t stageOff[3] = { 0, 0, 0 }, stageStride[3] = { 0, 0, 0 }, stageBytes = 0;
   for( int k = 0; k < nc && staged; k++ ) { stageOff[k] = stageBytes; stageStride[k] = alignUp( rowBytes[k], 16 ); stageBytes += alignUp( stageStride[k] * p.h[k], 256 ); }
+  size_t prevStageOff[2] = { 0, 0 }; const size_t prevStageStride = alignUp( prevRow, 16 );
+  for( int k = 0; k < temporal && stagedPrev; k++ ) { prevStageOff[k] = stageBytes; stageBytes += alignUp( prevStageStride * h, 256 ); }
   // ---- a reference in pageable memory goes into an entry's pinned memory BEFORE the request is ordered: from outAcquire to the registration of the
   // `read` event mu stays held (a picture committed in between that overwrites the slot has to find the event), and a frame's worth of memcpy
   // does not belong under mu.  The entry is this thread's meanwhile and is handed to outAcquire as the one to take
   OutEntry* mine = nullptr;
-  if( staged && !pinnedRef )
+  if( ( staged || stagedPrev ) && !pinnedRef )
   {
     if( !c->outRing ) c->outRing = new OutEntry[VVR_OUT_RING];
     for( int i = 0; i < VVR_OUT_RING && !mine; i++ ) if( c->outRing[i].state == OQ_FREE ) mine = &c->outRing[i];
@@ -1943,8 +2061,10 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
     if( outGrow( mine->host, mine->hostCap, hostStageOff + stageBytes, true ) != VVR_OK ) { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
     mine->state = OQ_WAITING; mine->ticket = -1; mine->devDst = false;
     lk.unlock();
-    for( int k = 0; k < nc; k++ )
+    for( int k = 0; k < nc && staged; k++ )
       for( int r = 0; r < p.h[k]; r++ ) memcpy( mine->host + hostStageOff + stageOff[k] + (size_t) r * stageStride[k], (const char*) rq->ref[k] + (size_t) r * rq->ref_stride_bytes[k], rowBytes[k] );
+    for( int k = 0; k < temporal; k++ )
+      for( int r = 0; r < h; r++ ) memcpy( mine->host + hostStageOff + prevStageOff[k] + (size_t) r * prevStageStride, (const char*) xp->prev[k] + (size_t) r * xp->prevStride[k], prevRow );
     lk.lock();
     mine->state = OQ_FREE;
   }
@@ -1960,6 +2080,7 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   hipStream_t s = c->outQStream;
   outTake( c, e, slot, rq->job, jobFailed );
   e->cmp = nc; e->cmpW = w; e->cmpH = h; e->cmpBlocks = blocks; e->cmpOut = rq->result; e->cmpMap = rq->map; e->cmpSsim = ssim; e->msScales = scales;
+  if( xp ) { e->xps = true; e->xpsTemporal = temporal; e->xpsFilter = xp->filter ? xp->filter : ( (int64_t) w * h > 2048 * 1152 ? 2 : 1 ); e->xpsBlock = (int) xpB; e->xpsBx = (int) xpBx; e->xpsBy = (int) xpBy; e->xpsBlocks = xp->blocks; }
   if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
   if( outGrow( e->dev, e->devCap, ms ? pyrBase + pyrBytes : recBytes + wordBytes, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, stageBytes, false ) != VVR_OK ||
       outGrow( e->host, e->hostCap, hostStageOff, true ) != VVR_OK )      // (a staged reference: grown above, beyond this)
@@ -1972,18 +2093,28 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   // wide loads (vvr_device.h): not from an odd origin of a 4:0:0 window, not from reference planes whose base or stride is odd
   p.bySample = nc == 1 && ( x & 1 );
   for( int k = 0; k < nc; k++ ) if( ( (uintptr_t) p.ref[k] | p.refStride[k] ) & 1 ) p.bySample = 1;
+  XpsnrParams xq; memset( &xq, 0, sizeof( xq ) );
+  for( int k = 0; k < temporal; k++ )
+  {
+    xq.prev[k] = stagedPrev ? (const uint8_t*) ( e->tmp + prevStageOff[k] ) : (const uint8_t*) xp->prev[k];
+    xq.prevStride[k] = stagedPrev ? prevStageStride : xp->prevStride[k];
+    if( ( (uintptr_t) xq.prev[k] | xq.prevStride[k] ) & 1 ) p.bySample = 1;
+  }
   if( devRef )      // (vvr_device_free / vvr_device_unregister see a request in flight that uses the range)
   {
-    e->direct = true; e->devDst = true; e->nc = nc;
-    for( int k = 0; k < nc; k++ ) { e->dst[k] = const_cast<void*>( rq->ref[k] ); e->extent[k] = extent[k]; }
+    e->direct = true; e->devDst = true; e->nc = 0;
+    for( int k = 0; k < nc && refSlot < 0; k++ ) { e->dst[e->nc] = const_cast<void*>( rq->ref[k] ); e->extent[e->nc++] = extent[k]; }
+    for( int k = 0; k < temporal; k++ ) { e->dst[e->nc] = const_cast<void*>( xp->prev[k] ); e->extent[e->nc++] = prevExtent[k]; }
   }
   // ---- 3. behind the picture (or the slot's users) and behind all that uses ref_slot on the device, 4. the reference's copy and the kernels.
   // mu stays held up to the registration of the `read` event (as vvr_output_submit)
   OQCHK( outOrder( c, e, slot, rq->job, jobDone ) );
   if( refSlot >= 0 ) OQCHK( outOrder( c, e, refSlot, -1, nullptr ) );
-  if( staged && !pinnedRef ) OQCHK( hipMemcpyAsync( e->tmp, e->host + hostStageOff, stageBytes, hipMemcpyHostToDevice, s ) );
+  if( ( staged || stagedPrev ) && !pinnedRef ) OQCHK( hipMemcpyAsync( e->tmp, e->host + hostStageOff, stageBytes, hipMemcpyHostToDevice, s ) );
   for( int k = 0; k < nc && staged && pinnedRef; k++ )
     OQCHK( hipMemcpy2DAsync( e->tmp + stageOff[k], stageStride[k], rq->ref[k], rq->ref_stride_bytes[k], rowBytes[k], p.h[k], hipMemcpyHostToDevice, s ) );
+  for( int k = 0; k < temporal && stagedPrev && pinnedRef; k++ )
+    OQCHK( hipMemcpy2DAsync( e->tmp + prevStageOff[k], prevStageStride, xp->prev[k], xp->prevStride[k], prevRow, h, hipMemcpyHostToDevice, s ) );
   uint32_t* recs = (uint32_t*) e->dev; uint32_t* words = (uint32_t*) ( e->dev + recBytes );
   double samples = 0;
   for( int k = 0; k < nc; k++ ) samples += (double) p.w[k] * p.h[k];
@@ -1994,9 +2125,15 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   };
   double msBytes = 0;
   for( int k = 0; k < scales; k++ ) msBytes += samples / (double) ( 1 << 2 * k ) * ( ( k ? 4 : 2 + rb ) + ( k + 1 < scales ? 1 : 0 ) );
-  outTimeBegin( c, s, e->timed, e->timing, ms ? K_OUTPUT_MSSSIM : ssim ? K_OUTPUT_SSIM : K_OUTPUT_COMPARE, ms ? msBytes : samples * ( 2 + rb ) );
+  if( xp ) OQCHK( hipMemsetAsync( e->dev, 0, wordBytes, s ) );      // (the records k_output_xpsnr adds to)
+  outTimeBegin( c, s, e->timed, e->timing, xp ? K_OUTPUT_XPSNR : ms ? K_OUTPUT_MSSSIM : ssim ? K_OUTPUT_SSIM : K_OUTPUT_COMPARE, ms ? msBytes : samples * ( 2 + rb ) + (double) temporal * w * h * rb );
   MsssimNext nx; memset( &nx, 0, sizeof( nx ) );
-  if( ms ) { if( scales > 1 ) level( 1, nx ); launch_output_msssim( s, p, c->cfg.bit_depth, recs, scales > 1 ? &nx : nullptr ); }
+  if( xp )
+  {
+    xq.c = p; xq.block = e->xpsBlock; xq.blocksX = e->xpsBx; xq.blocksY = e->xpsBy; xq.filter = e->xpsFilter; xq.temporal = temporal;
+    launch_output_xpsnr( s, xq, (unsigned long long*) e->dev );
+  }
+  else if( ms ) { if( scales > 1 ) level( 1, nx ); launch_output_msssim( s, p, c->cfg.bit_depth, recs, scales > 1 ? &nx : nullptr ); }
   else if( ssim ) launch_output_ssim( s, p, c->cfg.bit_depth, recs, (int32_t*) ( words + CMP_HEAD_WORDS ) );
   else launch_output_compare( s, p, recs, words + CMP_HEAD_WORDS );
   if( e->timed && scales <= 1 ) hipEventRecord( e->timing.b, s );
@@ -2015,10 +2152,13 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
     launch_output_msssim( s, q, c->cfg.bit_depth, recs + fold.recOff[k], k + 1 < scales ? &nx : nullptr );
     if( e->timed && k + 1 == scales ) hipEventRecord( e->timing.b, s );
   }
-  outTimeBegin( c, s, e->timed2, e->timing2, ms ? K_OUTPUT_MSSSIM_SUM : ssim ? K_OUTPUT_SSIM_SUM : K_OUTPUT_COMPARE_SUM, ms ? (double) recBytes + crossBytes : (double) sizeof( uint32_t ) * ( recWords * blocks + outWords ) * nc );
-  if( ms ) launch_output_msssim_sum( s, recs, fold, nc, words );
-  else if( ssim ) launch_output_ssim_sum( s, recs, blocks, nc, words );
-  else launch_output_compare_sum( s, recs, blocks, nc, words );
+  if( !xp )      // (an XPSNR request has no fold: its blocks are summed on the host)
+  {
+    outTimeBegin( c, s, e->timed2, e->timing2, ms ? K_OUTPUT_MSSSIM_SUM : ssim ? K_OUTPUT_SSIM_SUM : K_OUTPUT_COMPARE_SUM, ms ? (double) recBytes + crossBytes : (double) sizeof( uint32_t ) * ( recWords * blocks + outWords ) * nc );
+    if( ms ) launch_output_msssim_sum( s, recs, fold, nc, words );
+    else if( ssim ) launch_output_ssim_sum( s, recs, blocks, nc, words );
+    else launch_output_compare_sum( s, recs, blocks, nc, words );
+  }
   if( e->timed2 ) hipEventRecord( e->timing2.b, s );
   const int ticket = e->ticket;
   lk.unlock();
@@ -2061,6 +2201,24 @@ VVR_API int vvr_msssim_submit( vvr_context* c, const vvr_msssim_request* rq )
   memcpy( &q, rq, sizeof( *rq ) );
   q.map = nullptr;
   return compareSubmit( c, &q, "vvr_msssim_submit", false, rq->scales );
+}
+// (a vvr_xpsnr_request is a vvr_compare_request up to ref_stride_bytes, with temporal and filter in the pad bytes and block in pad2)
+static_assert( sizeof( vvr_xpsnr_request ) == 136 && sizeof( vvr_frame_xpsnr ) == 128 && sizeof( vvr_xpsnr_block ) == sizeof( unsigned long long ) * XPSNR_REC_WORDS &&
+               offsetof( vvr_xpsnr_request, ref ) == offsetof( vvr_compare_request, ref ) && offsetof( vvr_xpsnr_request, prev ) == offsetof( vvr_compare_request, result ) &&
+               offsetof( vvr_xpsnr_block, act_spatial ) == 24 && offsetof( vvr_xpsnr_block, count ) == 40, "vvr_xpsnr_request mirrors vvr_compare_request up to the reference's strides" );
+VVR_API int vvr_xpsnr_submit( vvr_context* c, const vvr_xpsnr_request* rq )
+{
+  if( !c || !rq ) return VVR_ERR_PARAMETER;
+  if( rq->struct_size != sizeof( vvr_xpsnr_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_xpsnr_request )", "vvr_xpsnr_submit" );
+  if( rq->temporal > 2 ) return outRefuse( c, "temporal must be 0, 1 or 2", "vvr_xpsnr_submit" );
+  if( rq->filter > 2 ) return outRefuse( c, "filter must be 0, 1 or 2", "vvr_xpsnr_submit" );
+  if( rq->block & 3 ) return outRefuse( c, "block must be 0 or a multiple of 4", "vvr_xpsnr_submit" );
+  vvr_compare_request q;
+  memset( &q, 0, sizeof( q ) );
+  memcpy( &q, rq, offsetof( vvr_compare_request, result ) );
+  q.result = (vvr_frame_compare*) rq->result; q.map = nullptr;
+  const XpsnrAsk ask = { rq->temporal, rq->filter, rq->block, { rq->prev[0], rq->prev[1] }, { rq->prev_stride_bytes[0], rq->prev_stride_bytes[1] }, rq->blocks };
+  return compareSubmit( c, &q, "vvr_xpsnr_submit", false, 0, &ask );
 }
 #undef OQCHK
 
@@ -2129,7 +2287,25 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
       for( int k = 0; k < 3; k++ ) { st.max_c[k] = w[2048 + k]; st.min_c[k] = ( ( 1u << c->cfg.bit_depth ) - 1 ) - w[2051 + k]; }
     }
   }
-  if( rc == VVR_OK && e->queued && e->cmp && e->msScales )
+  if( rc == VVR_OK && e->queued && e->cmp && e->xps )
+  {
+    // the caller's vvr_frame_xpsnr: the header fields, the geometry and the sums over the records; the records as they lie
+    const vvr_xpsnr_block* b = (const vvr_xpsnr_block*) e->host;
+    const size_t n = (size_t) e->xpsBx * e->xpsBy;
+    vvr_frame_xpsnr r;
+    memset( &r, 0, sizeof( r ) );
+    r.struct_size = sizeof( r ); r.bit_depth = (uint32_t) c->cfg.bit_depth; r.num_components = (uint32_t) e->cmp; r.temporal = (uint32_t) e->xpsTemporal;
+    r.filter = (uint32_t) e->xpsFilter; r.block = (uint32_t) e->xpsBlock; r.blocks_x = (uint32_t) e->xpsBx; r.blocks_y = (uint32_t) e->xpsBy;
+    for( int k = 0; k < e->cmp; k++ ) { r.width[k] = (uint32_t) ( e->cmpW >> ( k ? 1 : 0 ) ); r.height[k] = (uint32_t) ( e->cmpH >> ( k ? 1 : 0 ) ); r.samples[k] = (uint64_t) r.width[k] * r.height[k]; }
+    for( size_t i = 0; i < n; i++ )
+    {
+      for( int k = 0; k < 3; k++ ) r.sse[k] += b[i].sse[k];
+      r.act_spatial += b[i].act_spatial; r.act_temporal += b[i].act_temporal; r.count += b[i].count;
+    }
+    memcpy( (void*) e->cmpOut, &r, sizeof( r ) );
+    if( e->xpsBlocks ) memcpy( e->xpsBlocks, b, sizeof( vvr_xpsnr_block ) * n );
+  }
+  else if( rc == VVR_OK && e->queued && e->cmp && e->msScales )
   {
     // the caller's vvr_frame_msssim: the header fields, per level and component the plane, the grid of windows and the two folded sums
     const uint32_t* w = (const uint32_t*) e->host;
