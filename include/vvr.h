@@ -949,8 +949,9 @@ VVR_API int          vvr_light_level(const vvr_frame_stats* stats, int transfer_
  * ref_slot == slot, job < -1, result == NULL, a window outside the picture, empty, or odd in a 4:2:0 context, pictures of different sizes in the two
  * slots; without ref_slot: ref_bytes_per_sample other than 1 or 2, a NULL plane among those the context has, a stride below the row, device planes
  * mixed with host planes, a plane partly inside a device range.
- * Not offered here: SSIM, MS-SSIM and XPSNR are requests of their own (vvr_ssim_submit, vvr_msssim_submit, vvr_xpsnr_submit, below); grained or rescaled frames (the decoded picture is what is compared); results left in device memory;
- * a reference of another size than the window. */
+ * Not offered here: SSIM, MS-SSIM and XPSNR are requests of their own (vvr_ssim_submit, vvr_msssim_submit, vvr_xpsnr_submit, below); grained frames; results left in device memory.
+ * A reference of another size than the window: vvr_set_compare_scaling, below - the window is rescaled to the reference's size; ref_slot is not
+ * offered under it, nor is the other direction, a reference scaled to the picture's size. */
 typedef struct vvr_frame_compare {
   uint32_t struct_size;            /* sizeof( vvr_frame_compare ), written with the rest */
   uint32_t bit_depth;              /* the context's */
@@ -1017,7 +1018,8 @@ VVR_API int          vvr_compare_psnr(const vvr_frame_compare* cmp, double peak,
  *            kinds of request); the film grain seed chain and the colour description are not touched.
  * Refused (VVR_ERR_PARAMETER with a text that names vvr_ssim_submit, no ring entry taken): everything vvr_compare_submit refuses, struct_size being
  * sizeof( vvr_ssim_request ), and a window with w < 8 or h < 8.
- * Not offered here: MS-SSIM is a request of its own (vvr_msssim_submit, below).  Not offered: Gaussian windows; grained or rescaled frames; results left in device memory; a reference of another size than the window. */
+ * Not offered here: MS-SSIM is a request of its own (vvr_msssim_submit, below).  Not offered: Gaussian windows; grained frames; results left in device memory;
+ * under vvr_set_compare_scaling (below: a reference of another size than the window) ref_slot, and a reference scaled to the picture's size. */
 typedef struct vvr_frame_ssim {
   uint32_t struct_size;            /* sizeof( vvr_frame_ssim ), written with the rest */
   uint32_t bit_depth;              /* the context's */
@@ -1077,7 +1079,8 @@ VVR_API int          vvr_compare_ssim(const vvr_frame_ssim* s, double ssim[4]);
  * last level: ( w_c >> ( scales - 1 ) ) < 8 or ( h_c >> ( scales - 1 ) ) < 8, with w_c = w >> 1, h_c = h >> 1 for chroma in 4:2:0.  So five scales need
  * a window of 256 x 256 in 4:2:0 and of 128 x 128 in 4:0:0; a smaller window takes fewer scales.
  * Not offered: a map or a minimum (where a picture is worst is vvr_ssim_submit's answer); Gaussian windows; another pyramid filter than the 2 x 2
- * mean; grained or rescaled frames; results left in device memory; a reference of another size than the window. */
+ * mean; grained frames; results left in device memory; under vvr_set_compare_scaling (below: a reference of another size than the window)
+ * ref_slot, and a reference scaled to the picture's size. */
 #define VVR_MSSSIM_MAX_SCALES 5
 typedef struct vvr_frame_msssim {
   uint32_t struct_size;            /* sizeof( vvr_frame_msssim ), written with the rest */
@@ -1161,7 +1164,8 @@ VVR_API int          vvr_compare_msssim(const vvr_frame_msssim* s, const double*
  * sizeof( vvr_xpsnr_request ); w < 8 or h < 8; temporal > 2; filter > 2; a block that is neither 0 nor a multiple of 4; more than 16384 blocks; for
  * k < temporal a NULL prev[k] or a stride below the row; a prev plane partly inside a device range; pointer planes of mixed homes.
  * Not offered: minimum-smoothing of the weights between neighbouring blocks at low resolutions; chroma activity; temporal activity from slots;
- * grained or rescaled frames; results left in device memory; more than 16384 blocks. */
+ * grained frames; results left in device memory; more than 16384 blocks; under vvr_set_compare_scaling (below: a reference of another size than
+ * the window) ref_slot, and a reference scaled to the picture's size. */
 #define VVR_XPSNR_MAX_BLOCKS 16384
 typedef struct vvr_xpsnr_block {
   uint64_t sse[3];                 /* sum of ( x - o )^2 per component */
@@ -1215,6 +1219,33 @@ VVR_API int          vvr_xpsnr_blocks(int w, int h, uint32_t block, uint32_t* re
  * passes its constant.  Refused (VVR_ERR_PARAMETER, xpsnr untouched): a NULL pointer, a struct_size other than sizeof( vvr_frame_xpsnr ), a bit
  * depth outside 8..10, samples[0] == 0, blocks_x * blocks_y == 0, filter outside 1..2. */
 VVR_API int          vvr_compare_xpsnr(const vvr_frame_xpsnr* f, const vvr_xpsnr_block* blocks, double a_pic, double peak, double xpsnr[4]);
+/* A reference of another size than the window, for the four measures above - vvr_compare_submit, vvr_ssim_submit, vvr_msssim_submit,
+ * vvr_xpsnr_submit: the rungs of an adaptive-bitrate ladder below the top one are coded at a reduced size and judged after upscaling to the
+ * source's, and a stream with reference picture resampling changes its picture size mid-sequence while its source does not.  Context state like
+ * the narrowing (vvr_set_output_narrowing): a new context has ( 0, 0 ) - scaling off, every request means what is said above - and the value is
+ * read once, under the context's mutex, when a request is submitted; a request in flight keeps the value it was submitted with.  The request
+ * structs do not change.  out_w, out_h: luma samples; collocated: as vvr_read_output_scaled takes it (bit 0: chroma collocated horizontally,
+ * bit 1: vertically; luma is always collocated).
+ * With scaling on, a request of the four kinds submitted from then on is defined to the bit:
+ *   picture side   component c of the window - x, y, w, h of the request, validated against the picture in the slot as before - rescaled to
+ *            ( out_w >> s ) x ( out_h >> s ), s = 1 for the chroma of a 4:2:0 context: exactly the samples vvr_read_output_scaled delivers for that
+ *            component, that window of its plane, that size and `collocated` with bytes_per_sample == 2.  out_w == w && out_h == h is not special.
+ *   everything downstream of the window   takes out_w x out_h where it took w x h: the reference planes ARE the rescaled window - their rows,
+ *            extents, staging and device-range checks are those of planes of that size; width[], height[], samples[] and windows*[] of the
+ *            results; the blocks of 64 x 64 luma samples of the maps, ceil( out_w / 64 ) * ceil( out_h / 64 ) of them; the 8 x 8 minimum of SSIM and
+ *            XPSNR; the last-level condition of MS-SSIM; XPSNR's block formula, default filter, block count limit (vvr_xpsnr_blocks( out_w, out_h,
+ *            ... )) and prev[] planes; first_x, first_y and min_x, min_y are coordinates of the rescaled window.
+ *   refused at submit (VVR_ERR_PARAMETER, a text that names the submitting function, no ring entry taken), besides all that is refused without
+ *            scaling: out_w outside [ceil( w / 8 ), 8 w] or out_h outside [ceil( h / 8 ), 8 h] - the rule of vvr_read_output_scaled; ref_slot >= 0.
+ * An SSIM, MS-SSIM or XPSNR request keeps the rescaled planes in its ring entry on the device and stops being a reader of the slot when they
+ * are written: a picture submitted afterwards into the slot waits for the rescaling, not for the measure.  A comparison request rescales and
+ * compares in one kernel and stores no rescaled sample; its words are those of the comparison of the rescaled planes.  The film grain seed
+ * chain and the colour description are not touched.
+ * Refused (VVR_ERR_PARAMETER, the text names vvr_set_compare_scaling, the value set before stays in force): exactly one of the two sides 0; a
+ * side outside 1 .. 8192; an odd side in a 4:2:0 context; collocated outside 0 .. 3.
+ * Not offered: grained frames; ref_slot under scaling (two slots of different picture sizes); the other direction, a reference scaled to the
+ * picture's size; results left in device memory. */
+VVR_API int          vvr_set_compare_scaling(vvr_context* ctx, int out_w, int out_h, int collocated);
 /* the finished picture in `slot` (every plane, at the picture's size) into the caller's buffers - what a decoder does with each picture it hands to
  * the application (the planes of a vvdecFrame live in the Picture's own buffers, vvdecimpl.cpp:1058).  Waits for NOTHING: the caller has waited for
  * the picture (vvr_wait); other pictures in flight are not held up (vvr_read_plane drains the context).  Each plane crosses PCIe in one transfer

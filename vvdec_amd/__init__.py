@@ -77,6 +77,7 @@ def lib():
         L.vvr_set_output_colour.restype = C.c_int
         L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
         abi.bind_output_narrowing(L)
+        abi.bind_compare_scaling(L)
         L.vvr_set_output_normalisation.restype = C.c_int
         L.vvr_set_output_normalisation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vvr_set_output_transform.restype = C.c_int
@@ -151,7 +152,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_narrowing", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_set_output_lut3d", "vvr_output_lut3d_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_narrowing", "vvr_set_compare_scaling", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_set_output_lut3d", "vvr_output_lut3d_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
@@ -278,6 +279,7 @@ class Reconstructor:
         self._out = {}
         self._reg = {}      # ticket -> addresses registered for the life of the request (output_submit(into=...))
         self._dev = []      # (address, bytes) of device_array memory: known to the context already
+        self._compare_scaling = None      # (w, h) of set_compare_scaling, None: off
 
     # -- lifetime
     def close(self):
@@ -461,6 +463,20 @@ class Reconstructor:
                 raise ValueError("set_output_narrowing: mode is 0 .. 3 or one of %s" % ", ".join(abi.NARROW_MODES))
             mode = abi.NARROW_MODES[mode]
         self._check(self.L.vvr_set_output_narrowing(self.ctx, int(mode), int(phase)))
+
+    def set_compare_scaling(self, size=None, collocated=(True, False)):
+        """a reference of another size than the window for compare(), ssim(), msssim() and xpsnr() (vvr_set_compare_scaling, the definition:
+        vvr.h): size = (w, h) in luma samples - the window is rescaled to it on the device, exactly as read_output(size=...) delivers it, and
+        measured against a reference of that size; result arrays, maps and XPSNR's prev planes are of that size too.  None: off (a new
+        context).  collocated: (horizontally, vertically), the chroma phase as read_output takes it.  A slot number as `ref` is refused
+        while scaling is on.  A request takes the value that is set when it is submitted."""
+        w, h = (0, 0) if size is None else (int(size[0]), int(size[1]))
+        self._check(self.L.vvr_set_compare_scaling(self.ctx, w, h, (1 if collocated[0] else 0) | (2 if collocated[1] else 0)))
+        self._compare_scaling = (w, h) if w or h else None
+
+    def _measured(self, win):
+        """the window as compare(), ssim(), msssim() and xpsnr() measure it: of the size of set_compare_scaling when that is on"""
+        return win if self._compare_scaling is None else (0, 0) + self._compare_scaling
 
     def set_output_normalisation(self, mean=None, std=None):
         """the per-channel mean and standard deviation the "rgbf32" format of output_submit applies (vvr_set_output_normalisation): three floats
@@ -687,9 +703,10 @@ class Reconstructor:
         replaced in place by what the request is to point to"""
         nc = 3 if self.chroma_format else 1
         registered = []
+        size = self._measured(win)      # (the window's size, or the size it is rescaled to)
         if prev:
-            if any(tuple(p.shape) != (win[3], win[2]) for p in prev):
-                raise ValueError("%s: prev planes are luma planes of the window's size, %r" % (what, (win[3], win[2])))
+            if any(tuple(p.shape) != (size[3], size[2]) for p in prev):
+                raise ValueError("%s: prev planes are luma planes of the window's size, %r" % (what, (size[3], size[2])))
             if all(hasattr(p, "data_ptr") for p in prev):
                 if any(not p.is_cuda or p.device.index != self.cfg.device or p.element_size() not in (1, 2) or (p.shape[1] > 1 and p.stride(1) != 1) or p.stride(0) < 0 for p in prev):
                     raise ValueError(what + ": prev tensors are row-major 2-D tensors of 1- or 2-byte elements on the context's device")
@@ -700,7 +717,7 @@ class Reconstructor:
                 prev[:] = [p if p.strides[1] == p.itemsize and p.strides[0] > 0 else np.ascontiguousarray(p) for p in prev]
         if not isinstance(ref, int):
             ref = list(ref)[:nc]
-            shapes = [(win[3] >> (1 if c else 0), win[2] >> (1 if c else 0)) for c in range(nc)]
+            shapes = [(size[3] >> (1 if c else 0), size[2] >> (1 if c else 0)) for c in range(nc)]
             if len(ref) != nc or any(tuple(p.shape) != s for p, s in zip(ref, shapes)):
                 raise ValueError("%s: the reference needs %d planes of the window's size, %r" % (what, nc, shapes))
             if all(hasattr(p, "data_ptr") for p in ref):
@@ -739,7 +756,7 @@ class Reconstructor:
         win = tuple(window or (0, 0, self.width, self.height))
         nc = 3 if self.chroma_format else 1
         raw = abi.FrameCompare()
-        blocks = np.zeros(abi.compare_map_shape(win), np.uint32) if with_map else None
+        blocks = np.zeros(abi.compare_map_shape(self._measured(win)), np.uint32) if with_map else None
         self._against_reference("compare", slot, ref, win, job, abi.compare_request, self.L.vvr_compare_submit, raw, blocks)
         out = dict(raw=raw, bit_depth=raw.bit_depth, num_components=raw.num_components)
         for name in ("width", "height", "samples", "differing", "sse", "sad", "max_abs"):
@@ -767,7 +784,7 @@ class Reconstructor:
         win = tuple(window or (0, 0, self.width, self.height))
         nc = 3 if self.chroma_format else 1
         raw = abi.FrameSsim()
-        blocks = np.zeros(abi.ssim_map_shape(win), np.int32) if with_map else None
+        blocks = np.zeros(abi.ssim_map_shape(self._measured(win)), np.int32) if with_map else None
         self._against_reference("ssim", slot, ref, win, job, abi.ssim_request, self.L.vvr_ssim_submit, raw, blocks)
         mean = (C.c_double * 4)()
         if self.L.vvr_compare_ssim(C.byref(raw), mean) != abi.VVR_OK:
@@ -815,7 +832,7 @@ class Reconstructor:
         prev = list(prev)
         if len(prev) > 2:
             raise ValueError("xpsnr: at most two prev planes")
-        shape = abi.xpsnr_blocks(win[2], win[3], block)
+        shape = abi.xpsnr_blocks(self._measured(win)[2], self._measured(win)[3], block)
         if shape is None:
             raise ValueError("xpsnr: a window of at least 8 x 8, a block that is 0 or a multiple of 4, at most %d blocks" % abi.XPSNR_MAX_BLOCKS)
         raw = abi.FrameXpsnr()

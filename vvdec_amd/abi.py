@@ -186,6 +186,13 @@ def bind_output_narrowing(L):
     return L
 
 
+def bind_compare_scaling(L):
+    """the ctypes signature of vvr_set_compare_scaling on a loaded library (the product's, or the host build of the tests)"""
+    L.vvr_set_compare_scaling.restype = C.c_int
+    L.vvr_set_compare_scaling.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    return L
+
+
 class OutputRequest(C.Structure):
     """vvr_output_request: one request of the output queue (vvr_output_submit, vvr.h)"""
     _fields_ = [("struct_size", u32), ("slot", i32), ("job", i32), ("x", i32), ("y", i32), ("w", i32), ("h", i32), ("out_w", i32), ("out_h", i32),

@@ -337,6 +337,48 @@ struct CompareParams
 };
 void launch_output_compare( hipStream_t s, const CompareParams& p, uint32_t* recs, uint32_t* map );
 void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks, int numComp, uint32_t* out );
+// ... of a window rescaled on the way (vvr_set_compare_scaling, the definition: vvr.h): k_rescale's tile with the comparison where the store was -
+// the rescaled sample never reaches memory.  rs[c]: the rescaling of component c as launch_rescale takes it (bytesPerSample is not looked at);
+// ref / refStride / refBytes / nbx / nby: as CompareParams, of the RESCALED window; byByte: 2-byte reference samples are read as two bytes (an odd
+// base or stride).  One launch for all components: workgroup g takes tile g - first[c] of component c, first[c] <= g < first[c + 1], tilesX[c]
+// tiles of RS_TW = 64 columns a row, tileH[c] output rows each - a power of two, at most 64 for luma and 32 for chroma, so that a tile lies in one
+// row of blocks; a luma tile lies in one block, a chroma tile in two, a half each.  The tiles of a block meet in its record through integer
+// atomics - 64-bit add, 32-bit add, max, min: the result does not depend on their order - so the launcher first puts every record into the state
+// "nothing differs" (0, 0, 0, 0, 0, 0xffffffff) and every map word to 0: clearWords words in all.  The records and the map are then what
+// launch_output_compare leaves for the rescaled planes, word for word.
+struct CompareScaledParams
+{
+  RescaleParams rs[3];
+  const uint8_t* ref[3]; size_t refStride[3];
+  int numComp, refBytes, nbx, nby, byByte;
+  int tileH[3], rowsCap[3], tilesX[3], first[4];      // (set by compare_scaled_geometry)
+};
+struct CompareScaledGeometry { size_t ldsBytes, clearWords; };
+// the tile height of launch_rescale brought down to a power of two: the source rows of a tile fit RS_ROWS rows of sums; 64- and 32-row tiles only
+// where the component still has about a thousand of them
+inline CompareScaledGeometry compare_scaled_geometry( CompareScaledParams& p )
+{
+  CompareScaledGeometry g = { 0, (size_t) ( CMP_REC_WORDS * p.numComp + 1 ) * p.nbx * p.nby };
+  p.first[0] = 0;
+  for( int c = 0; c < 3; c++ )
+  {
+    p.tileH[c] = p.rowsCap[c] = p.tilesX[c] = 0; p.first[c + 1] = p.first[c];
+    if( c >= p.numComp ) continue;
+    const RescaleParams& r = p.rs[c];
+    const int taps = r.luma ? 8 : 4, fracShift = r.luma ? 4 : 5;
+    auto rows = [&]( int t ) { const int64_t den = (int64_t) 1 << ( r.shiftY + fracShift ); return (int) ( ( (int64_t) ( t - 1 ) * r.stepY + den - 1 ) / den ) + taps; };
+    int tileH = c ? 32 : 64;
+    while( tileH > 1 && rows( tileH ) > 128 /* RS_ROWS */ ) tileH >>= 1;
+    const int tilesX = ( r.outW + 63 ) / 64;
+    while( tileH > 16 && (int64_t) tilesX * ( ( r.outH + tileH - 1 ) / tileH ) < 1000 ) tileH >>= 1;
+    p.tileH[c] = tileH; p.tilesX[c] = tilesX; p.rowsCap[c] = rows( tileH ) < r.h ? rows( tileH ) : r.h;
+    p.first[c + 1] = p.first[c] + tilesX * ( ( r.outH + tileH - 1 ) / tileH );
+    const size_t lds = (size_t) p.rowsCap[c] * 64 * sizeof( int );
+    if( lds > g.ldsBytes ) g.ldsBytes = lds;
+  }
+  return g;
+}
+void launch_output_compare_scaled( hipStream_t s, CompareScaledParams p, uint32_t* recs, uint32_t* map );
 // SSIM of a picture against a reference frame (vvr_ssim_submit, the definition: vvr.h), on the comparison's parameters and blocks: a block owns the
 // SSIM windows (8 x 8 samples at a stride of 4) whose ORIGIN lies in it.  launch_output_ssim: recs[( c * nbx * nby + b ) * SSIM_REC_WORDS ..] = the
 // record of component c in block b - the sum of v (low word, high word), then the smallest v with the first window that has it as ONE 64-bit key,

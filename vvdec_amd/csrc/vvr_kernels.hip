@@ -6253,6 +6253,136 @@ void launch_output_compare_sum( hipStream_t s, const uint32_t* recs, int blocks,
   hipLaunchKernelGGL( k_output_compare_sum, dim3( numComp ), dim3( 256 ), 0, s, recs, blocks, out );
 }
 
+// k_output_compare_scaled — a comparison under vvr_set_compare_scaling (the definition: vvr.h): the window rescaled and compared in one pass, the
+// rescaled frame never stored.  The tile is k_rescale's, restated here so that k_rescale itself stays as it is: 64 output columns x tileH output
+// rows per workgroup, the filter table and the wavefronts' row segments in LDS, the unnormalised horizontal sums in LDS, a lane per output
+// column, an output row per wavefront at a time.  Where k_rescale stores the clipped sample the lane keeps it, subtracts the reference sample of
+// the same position - one load of 1 or 2 bytes a lane, a row of the reference per wavefront, coalesced, issued before the row's sums are read
+// from LDS - and accumulates the comparison's per-lane sums (CmpAcc).  One launch for all components: the workgroup finds its component and
+// tile from first[] / tilesX[] (block-uniform), and the 8-tap and the 4-tap body are the two sides of a block-uniform branch.  tileH is a power of
+// two, at most 64 (luma) or 32 (chroma): a luma tile lies in one block of 64 x 64 luma samples, a chroma tile of 64 columns in two, which its
+// half wavefronts reduce apart.  Wavefront (or half) in registers, the four wavefronts through LDS, then lanes 0 and 1 add the tile's share to the
+// block's record with integer atomics - 64-bit add (sse), 32-bit add (sad, the count, the map word), max, min - into records
+// k_output_compare_clear has put into the state "nothing differs": whatever the order of the tiles, the words are those k_output_compare stores.
+__global__ __launch_bounds__( 256 ) void k_output_compare_clear( uint32_t* __restrict__ recs, int numRecs, uint32_t* __restrict__ map, int blocks )
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if( i < numRecs * CMP_REC_WORDS ) recs[i] = i % CMP_REC_WORDS == 5 ? 0xffffffffu : 0u;
+  if( i < blocks ) map[i] = 0;
+}
+template<int TAPS, int RB, bool BYBYTE>
+__device__ __forceinline__ CmpAcc cmps_tile( const RescaleParams& p, int tileH, int rowsCap, int tx, int ty, const uint8_t* __restrict__ ref, size_t refStride,
+                                             int* __restrict__ rs_sum, pel_t* __restrict__ seg, const int16_t* __restrict__ rs_flt )
+{
+  constexpr int fracShift = TAPS == 8 ? 4 : 5, fracMask = ( 1 << fracShift ) - 1, half = TAPS / 2 - 1;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i0 = tx * RS_TW, iOut = i0 + lane, iLast = min( i0 + RS_TW, p.outW ) - 1, i = min( iOut, iLast );
+  const int j0 = ty * tileH, j1 = min( j0 + tileH, p.outH ) - 1;
+  // the source rows and columns the tile's taps reach, the lane's column: as k_rescale
+  const int rowLo = max( 0, ( ( j0 * p.stepY + p.addY ) >> p.shiftY >> fracShift ) - half );
+  const int rowHi = min( min( p.h - 1, ( ( j1 * p.stepY + p.addY ) >> p.shiftY >> fracShift ) + TAPS - 1 - half ), rowLo + rowsCap - 1 );
+  const int xLo = ( ( i0 * p.stepX + p.addX ) >> p.shiftX >> fracShift ) - half;
+  const int segLen = min( ( ( iLast * p.stepX + p.addX ) >> p.shiftX >> fracShift ) + TAPS - half - xLo, RS_SEG );
+  const int refX = ( i * p.stepX + p.addX ) >> p.shiftX, tap0 = ( refX >> fracShift ) - half - xLo;
+  const int16_t* fh = rs_flt + ( refX & fracMask ) * TAPS;
+  int ch[TAPS], xo[TAPS];
+#pragma unroll
+  for( int k = 0; k < TAPS; k++ ) { ch[k] = fh[k]; xo[k] = min( tap0 + k, RS_SEG - 1 ); }
+  for( int r = rowLo + wave; r <= rowHi; r += 4 )
+  {
+    const pel_t* __restrict__ row = p.src + (size_t) r * p.stride;
+    for( int t = lane; t < segLen; t += 64 ) seg[t] = row[clip3( 0, p.w - 1, xLo + t )];
+    __builtin_amdgcn_wave_barrier();
+    int sum = 0;
+#pragma unroll
+    for( int k = 0; k < TAPS; k++ ) sum += ch[k] * seg[xo[k]];
+    rs_sum[( r - rowLo ) * RS_TW + lane] = sum;
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+  CmpAcc acc = { 0, 0, 0, 0xffffffffu, 0 };
+  const bool inside = iOut < p.outW;
+  const uint8_t* __restrict__ refCol = ref + (size_t) i * RB;      // (a lane beyond the row reads the row's last sample and does not count it)
+  for( int j = j0 + wave; j <= j1; j += 4 )
+  {
+    const uint8_t* __restrict__ r = refCol + (size_t) j * refStride;
+    const int b = RB == 1 ? (int) r[0] : BYBYTE ? (int) ( (uint32_t) r[0] | (uint32_t) r[1] << 8 ) : (int) *(const uint16_t*) r;      // (asked for before the sums are waited for)
+    const int refY = ( j * p.stepY + p.addY ) >> p.shiftY, intY = refY >> fracShift;
+    const int16_t* fv = rs_flt + ( refY & fracMask ) * TAPS;
+    int sum = 0;
+#pragma unroll
+    for( int k = 0; k < TAPS; k++ ) sum += fv[k] * rs_sum[( clip3( rowLo, rowHi, intY + k - half ) - rowLo ) * RS_TW + lane];
+    const int v = clip3( 0, p.maxVal, ( sum + 2048 ) >> 12 );
+    const uint32_t ad = inside ? (uint32_t) abs( v - b ) : 0u;      // (below 2^16: ad * ad fits 32 bits)
+    if( ad ) { acc.n++; acc.first = min( acc.first, (uint32_t) ( j * p.outW + iOut ) ); }
+    acc.sad += ad; acc.top = max( acc.top, ad ); acc.sse += (uint64_t) ( ad * ad );
+  }
+  return acc;
+}
+__device__ __forceinline__ CmpAcc cmps_step( CmpAcc v, int d )
+{
+  v.n += (uint32_t) __shfl_xor( (int) v.n, d ); v.sad += (uint32_t) __shfl_xor( (int) v.sad, d );
+  v.top = max( v.top, (uint32_t) __shfl_xor( (int) v.top, d ) ); v.first = min( v.first, (uint32_t) __shfl_xor( (int) v.first, d ) );
+  const uint32_t lo = (uint32_t) __shfl_xor( (int) (uint32_t) v.sse, d ), hi = (uint32_t) __shfl_xor( (int) (uint32_t) ( v.sse >> 32 ), d );
+  v.sse += lo | (uint64_t) hi << 32;
+  return v;
+}
+template<int RB, bool BYBYTE>
+__global__ __launch_bounds__( 256 ) void k_output_compare_scaled( CompareScaledParams P, uint32_t* __restrict__ recs, uint32_t* __restrict__ map )
+{
+  extern __shared__ int rs_sum[];      // [rowsCap][RS_TW]
+  __shared__ pel_t rs_seg[4][RS_SEG];
+  __shared__ int16_t rs_flt[128];
+  __shared__ uint32_t part[4][2][CMP_REC_WORDS];
+  const int tid = threadIdx.x, wave = tid >> 6, g = blockIdx.x;
+  const int c = g >= P.first[2] ? 2 : g >= P.first[1] ? 1 : 0;      // (block-uniform; values picked one by one, never an index into the arguments)
+  const RescaleParams p = c == 0 ? P.rs[0] : c == 1 ? P.rs[1] : P.rs[2];
+  const int tileH = c == 0 ? P.tileH[0] : c == 1 ? P.tileH[1] : P.tileH[2], rowsCap = c == 0 ? P.rowsCap[0] : c == 1 ? P.rowsCap[1] : P.rowsCap[2];
+  const int tilesX = c == 0 ? P.tilesX[0] : c == 1 ? P.tilesX[1] : P.tilesX[2], t = g - ( c == 0 ? 0 : c == 1 ? P.first[1] : P.first[2] );
+  const uint8_t* __restrict__ ref = c == 0 ? P.ref[0] : c == 1 ? P.ref[1] : P.ref[2];
+  const size_t refStride = c == 0 ? P.refStride[0] : c == 1 ? P.refStride[1] : P.refStride[2];
+  const int tx = t % tilesX, ty = t / tilesX;
+  if( tid < 128 ) rs_flt[tid] = c == 0 ? ( &d_luma_filter[0][0] )[tid] : ( &d_chroma_filter[0][0] )[tid];
+  __syncthreads();
+  CmpAcc acc;
+  if( c == 0 ) acc = cmps_tile<8, RB, BYBYTE>( p, tileH, rowsCap, tx, ty, ref, refStride, rs_sum, rs_seg[wave], rs_flt );
+  else         acc = cmps_tile<4, RB, BYBYTE>( p, tileH, rowsCap, tx, ty, ref, refStride, rs_sum, rs_seg[wave], rs_flt );
+  // the halves of the wavefront (32 columns each: a chroma block), then - luma - the wavefront
+#pragma unroll
+  for( int d = 1; d < 32; d <<= 1 ) acc = cmps_step( acc, d );
+  if( c == 0 ) acc = cmps_step( acc, 32 );
+  if( ( tid & 31 ) == 0 )
+  {
+    uint32_t* v = part[wave][( tid >> 5 ) & 1];
+    v[0] = (uint32_t) acc.sse; v[1] = (uint32_t) ( acc.sse >> 32 ); v[2] = acc.sad; v[3] = acc.n; v[4] = acc.top; v[5] = acc.first;
+  }
+  __syncthreads();
+  // lane h folds half h of the four wavefronts (luma: half 0 is the whole) and adds it to its block's record
+  const int bx = c == 0 ? tx : 2 * tx + tid, by = ( ty * tileH ) >> ( c == 0 ? 6 : 5 );
+  if( tid >= ( c == 0 ? 1 : 2 ) || bx >= P.nbx ) return;
+  uint64_t sse = 0; uint32_t sad = 0, n = 0, top = 0, first = 0xffffffffu;
+  for( int w = 0; w < 4; w++ )
+  {
+    const uint32_t* v = part[w][tid];
+    sse += v[0] | (uint64_t) v[1] << 32; sad += v[2]; n += v[3]; top = max( top, v[4] ); first = min( first, v[5] );
+  }
+  if( !n ) return;      // (nothing differs in the tile: the cleared record says so)
+  const int b = by * P.nbx + bx, blocks = P.nbx * P.nby;
+  uint32_t* rec = recs + ( (size_t) c * blocks + b ) * CMP_REC_WORDS;      // (24 bytes a record: 8-byte aligned)
+  atomicAdd( (unsigned long long*) rec, (unsigned long long) sse ); atomicAdd( rec + 2, sad ); atomicAdd( rec + 3, n ); atomicMax( rec + 4, top ); atomicMin( rec + 5, first );
+  atomicAdd( map + b, n );
+}
+void launch_output_compare_scaled( hipStream_t s, CompareScaledParams p, uint32_t* recs, uint32_t* map )
+{
+  const CompareScaledGeometry g = compare_scaled_geometry( p );
+  const int blocks = p.nbx * p.nby, numRecs = p.numComp * blocks;
+  hipLaunchKernelGGL( k_output_compare_clear, dim3( ( numRecs * CMP_REC_WORDS + 255 ) / 256 ), dim3( 256 ), 0, s, recs, numRecs, map, blocks );
+  const dim3 grid( p.first[3] );
+  if( p.refBytes == 1 ) hipLaunchKernelGGL( ( k_output_compare_scaled<1, false> ), grid, dim3( 256 ), g.ldsBytes, s, p, recs, map );
+  else if( p.byByte ) hipLaunchKernelGGL( ( k_output_compare_scaled<2, true> ), grid, dim3( 256 ), g.ldsBytes, s, p, recs, map );
+  else hipLaunchKernelGGL( ( k_output_compare_scaled<2, false> ), grid, dim3( 256 ), g.ldsBytes, s, p, recs, map );
+}
+
 // k_output_xpsnr — XPSNR of a picture against a reference frame (vvr_xpsnr_submit, the definition: vvr.h), on the tiles of k_output_compare: a
 // workgroup owns 64 x 64 luma samples of the window and the 32 x 32 samples of both chroma components, and in it 16 x 16 cells of 4 x 4 luma
 // samples (2 x 2 of each chroma component).  B is a multiple of 4, so a cell - its samples and its positions - lies in exactly one block.

@@ -568,6 +568,22 @@ void launch_output_compare( hipStream_t, const CompareParams& p, uint32_t* recs,
     }
   }
 }
+// ... and launch_output_compare_scaled (k_output_compare_scaled) as what it stands for: every component rescaled by the loop above, then the
+// comparison's loop over the rescaled planes
+void launch_output_compare_scaled( hipStream_t s, CompareScaledParams q, uint32_t* recs, uint32_t* map )
+{
+  std::vector<uint16_t> planes[3];
+  CompareParams p; memset( &p, 0, sizeof( p ) );
+  for( int k = 0; k < q.numComp; k++ )
+  {
+    RescaleParams r = q.rs[k]; r.bytesPerSample = 2;
+    planes[k].resize( (size_t) r.outW * r.outH );
+    launch_rescale( s, r, planes[k].data() );
+    p.src[k] = (const pel_t*) planes[k].data(); p.stride[k] = r.outW; p.w[k] = r.outW; p.h[k] = r.outH; p.ref[k] = q.ref[k]; p.refStride[k] = q.refStride[k];
+  }
+  p.numComp = q.numComp; p.refBytes = q.refBytes; p.nbx = q.nbx; p.nby = q.nby; p.bySample = 1;
+  launch_output_compare( s, p, recs, map );
+}
 void launch_output_compare_sum( hipStream_t, const uint32_t* recs, int blocks, int numComp, uint32_t* out )
 {
   for( int c = 0; c < numComp; c++ )
@@ -731,6 +747,26 @@ void launch_output_xpsnr( hipStream_t, const XpsnrParams& P, unsigned long long*
       unsigned long long* rec = recs + ( (size_t) ( j / B ) * P.blocksX + i / B ) * XPSNR_REC_WORDS;
       rec[3] += (uint64_t) ( f < 0 ? -f : f ); rec[4] += (uint64_t) ( t < 0 ? -t : t ); rec[5] += 1;
     }
+}
+// the geometry k_output_compare_scaled is launched with (compare_scaled_geometry, vvr_device.h) for a window of w x h luma samples rescaled to
+// outW x outH, for the host tests: out[0 .. 14] = tileH[3], rowsCap[3], tilesX[3], first[4], the bytes of dynamic LDS, the words cleared
+extern "C" __attribute__(( visibility( "default" ) )) void vvt_compare_scaled_geometry( int w, int h, int outW, int outH, int numComp, long long* out )
+{
+  CompareScaledParams p; memset( &p, 0, sizeof( p ) );
+  p.numComp = numComp; p.nbx = ( outW + 63 ) / 64; p.nby = ( outH + 63 ) / 64;
+  for( int k = 0; k < numComp; k++ )
+  {
+    const int cs = k ? 1 : 0, fracShift = k ? 5 : 4;
+    RescaleParams& r = p.rs[k];
+    r.w = w >> cs; r.h = h >> cs; r.outW = outW >> cs; r.outH = outH >> cs; r.luma = k == 0;
+    int scale;
+    rescale_axis( r.w, r.outW, cs, 1, fracShift, scale, r.addX, r.shiftX ); r.stepX = scale << cs;
+    rescale_axis( r.h, r.outH, cs, 1, fracShift, scale, r.addY, r.shiftY ); r.stepY = scale << cs;
+  }
+  const CompareScaledGeometry g = compare_scaled_geometry( p );
+  for( int k = 0; k < 3; k++ ) { out[k] = p.tileH[k]; out[3 + k] = p.rowsCap[k]; out[6 + k] = p.tilesX[k]; }
+  for( int k = 0; k < 4; k++ ) out[9 + k] = p.first[k];
+  out[13] = (long long) g.ldsBytes; out[14] = (long long) g.clearWords;
 }
 #endif
 
@@ -1338,6 +1374,10 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 // reads the slots and the reference, so `read` is recorded behind it.  And an XPSNR request (vvr_xpsnr_submit): its prev planes take the
 // reference's steps - home, staging behind the reference's planes, devRanges bookkeeping - its records are cleared on the stream and added to
 // by one k_output_xpsnr, and they cross PCIe as they are: vvr_output_wait sums them.
+// Under vvr_set_compare_scaling the four measures take a reference of another size: the window is validated as it is, everything behind it is
+// sized by the size that is set.  An SSIM, MS-SSIM or XPSNR request runs k_rescale per component into 16-bit planes at the end of its `dev`
+// and measures those (the `read` event sits behind the last k_rescale); a comparison request is one k_output_compare_scaled, which rescales and
+// compares in one pass into records its launcher has cleared.
 // =====================================================================================================================
 #define VVR_OUT_RING 8
 enum { OQ_FREE = 0, OQ_FLIGHT, OQ_WAITING };
@@ -1355,6 +1395,7 @@ struct OutEntry {
   int hash = 0, hashNc = 0; size_t planeBytes[3] = { 0, 0, 0 };
   uint8_t* digest = nullptr; uint32_t* mismatch = nullptr; bool verify = false; uint8_t expected[48];
   bool timed2 = false; PendingTiming timing2;      // (k_hash_combine; `timing` is k_hash_rows then)
+  bool timed0 = false; PendingTiming timing0; int rescales = 0;      // (the k_rescale launches ahead of a measure under vvr_set_compare_scaling, and how many)
   // a statistics request: mode + 1 (0: none); STATS_WORDS words at the start of `host`; what vvr_output_wait writes besides them
   int stats = 0, statsW = 0, statsH = 0; vvr_frame_stats* statsOut = nullptr;
   // a comparison request: its number of components (0: none); CMP_OUT_WORDS words per component at the start of `host`, the map's words from
@@ -1384,6 +1425,7 @@ static void destroyOutputQueue( vvr_context* c )
       if( e.read ) hipEventDestroy( e.read ); if( e.done ) hipEventDestroy( e.done );
       if( e.timed ) { hipEventDestroy( e.timing.a ); hipEventDestroy( e.timing.b ); }
       if( e.timed2 ) { hipEventDestroy( e.timing2.a ); hipEventDestroy( e.timing2.b ); }
+      if( e.timed0 ) { hipEventDestroy( e.timing0.a ); hipEventDestroy( e.timing0.b ); }
     }
   delete[] c->outRing; c->outRing = nullptr;
   if( c->outQStream ) { hipStreamDestroy( c->outQStream ); c->outQStream = nullptr; }
@@ -1479,6 +1521,8 @@ void outTake( vvr_context* c, OutEntry* e, int slot, int job, int jobFailed )
   e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0; e->cmp = 0; e->msScales = 0; e->xps = false; e->refSlot = -1;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
   if( e->timed2 ) { hipEventDestroy( e->timing2.a ); hipEventDestroy( e->timing2.b ); e->timed2 = false; }
+  if( e->timed0 ) { hipEventDestroy( e->timing0.a ); hipEventDestroy( e->timing0.b ); e->timed0 = false; }
+  e->rescales = 0;
 }
 // outOrder: the output stream behind the picture (or, job < 0, behind the slot's users) and behind the external writers of the slot (readers cost nothing)
 hipError_t outOrder( vvr_context* c, const OutEntry* e, int slot, int job, hipEvent_t jobDone )
@@ -1948,14 +1992,22 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   const bool ms = scales > 0;
   const int temporal = xp ? xp->temporal : 0;
   // ---- 1. the request (its struct_size has been looked at)
-  const int slot = rq->slot, refSlot = rq->ref_slot, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
+  const int slot = rq->slot, refSlot = rq->ref_slot, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, winW = rq->w, winH = rq->h;
+  // the scaling the request takes (vvr_set_compare_scaling): the one that is set now, whatever is set while the request is in flight
+  int scaleW = 0, scaleH = 0, scaleCol = 0;
+  { std::lock_guard<std::mutex> g( c->mu ); scaleW = c->cmpScaleW; scaleH = c->cmpScaleH; scaleCol = c->cmpScaleCollocated; }
+  const bool scaled = scaleW != 0;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot", who );
   if( refSlot < -1 || refSlot >= (int) c->slots.size() || ( refSlot >= 0 && !c->slots[refSlot].p[0] ) ) return outRefuse( c, "no such ref_slot", who );
   if( refSlot == slot ) return outRefuse( c, "ref_slot is the slot itself", who );
   if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1", who );
   if( !rq->result ) return outRefuse( c, "result is NULL", who );
   const DevPlanes d = pictureIn( c, slot );      // (the picture in the slot, not the slot)
-  if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, empty, or odd in 4:2:0", who );
+  if( x < 0 || y < 0 || winW <= 0 || winH <= 0 || x + winW > d.w[0] || y + winH > d.h[0] || ( nc > 1 && ( ( x | y | winW | winH ) & 1 ) ) ) return outRefuse( c, "window outside the picture, empty, or odd in 4:2:0", who );
+  if( scaled && refSlot >= 0 ) return outRefuse( c, "ref_slot while vvr_set_compare_scaling is on (two slots of different picture sizes are not offered)", who );
+  if( scaled && ( winW > 8 * scaleW || scaleW > 8 * winW || winH > 8 * scaleH || scaleH > 8 * winH ) ) return outRefuse( c, "the size of vvr_set_compare_scaling is not within 1/8 .. 8 times the window's", who );
+  // w x h: what is measured - the window, or the window rescaled; everything from here on but the window's origin in the slot takes it
+  const int w = scaled ? scaleW : winW, h = scaled ? scaleH : winH;
   if( ssim && ( w < 8 || h < 8 ) ) return outRefuse( c, "a window below 8 x 8 holds no SSIM window", who );
   uint32_t xpB = 0, xpBx = 0, xpBy = 0;
   if( xp && ( w < 8 || h < 8 ) ) return outRefuse( c, "a window below 8 x 8", who );
@@ -2045,6 +2097,12 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   // XPSNR: the records are the words - cleared on the device, added to by the one launch, copied back whole
   if( xp ) { recBytes = 0; wordBytes = crossBytes = sizeof( unsigned long long ) * XPSNR_REC_WORDS * xpBx * xpBy; }
   const size_t hostStageOff = alignUp( wordBytes, 256 ), pyrBase = alignUp( recBytes + wordBytes, 256 );
+  // the rescaled window (vvr_set_compare_scaling): behind all of that, 16-bit planes as k_rescale stores them - rows back to back - each at a
+  // multiple of 256 bytes.  Not for a comparison: k_output_compare_scaled rescales and compares in one pass (`fused`)
+  const bool fused = scaled && !ssim && !ms && !xp;
+  const size_t scaleBase = alignUp( ms ? pyrBase + pyrBytes : recBytes + wordBytes, 256 );
+  size_t scaleOff[3] = { 0, 0, 0 }, scaleBytes = 0;
+  for( int k = 0; k < nc && scaled && !fused; k++ ) { scaleOff[k] = scaleBytes; scaleBytes += alignUp( sizeof( uint16_t ) * p.w[k] * p.h[k], 256 ); }
   size_t stageOff[3] = { 0, 0, 0 }, stageStride[3] = { 0, 0, 0 }, stageBytes = 0;
   for( int k = 0; k < nc && staged; k++ ) { stageOff[k] = stageBytes; stageStride[k] = alignUp( rowBytes[k], 16 ); stageBytes += alignUp( stageStride[k] * p.h[k], 256 ); }
   size_t prevStageOff[2] = { 0, 0 }; const size_t prevStageStride = alignUp( prevRow, 16 );
@@ -2082,7 +2140,7 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   e->cmp = nc; e->cmpW = w; e->cmpH = h; e->cmpBlocks = blocks; e->cmpOut = rq->result; e->cmpMap = rq->map; e->cmpSsim = ssim; e->msScales = scales;
   if( xp ) { e->xps = true; e->xpsTemporal = temporal; e->xpsFilter = xp->filter ? xp->filter : ( (int64_t) w * h > 2048 * 1152 ? 2 : 1 ); e->xpsBlock = (int) xpB; e->xpsBx = (int) xpBx; e->xpsBy = (int) xpBy; e->xpsBlocks = xp->blocks; }
   if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
-  if( outGrow( e->dev, e->devCap, ms ? pyrBase + pyrBytes : recBytes + wordBytes, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, stageBytes, false ) != VVR_OK ||
+  if( outGrow( e->dev, e->devCap, scaleBase + scaleBytes, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, stageBytes, false ) != VVR_OK ||
       outGrow( e->host, e->hostCap, hostStageOff, true ) != VVR_OK )      // (a staged reference: grown above, beyond this)
   { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
   for( int k = 0; k < nc && refSlot < 0; k++ )
@@ -2092,7 +2150,26 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   }
   // wide loads (vvr_device.h): not from an odd origin of a 4:0:0 window, not from reference planes whose base or stride is odd
   p.bySample = nc == 1 && ( x & 1 );
-  for( int k = 0; k < nc; k++ ) if( ( (uintptr_t) p.ref[k] | p.refStride[k] ) & 1 ) p.bySample = 1;
+  // the rescaled window: k_rescale reads the slot, the measure reads the entry's planes, whose rows lie back to back - a plane of odd width is not
+  // one for wide loads
+  RescaleParams rs[3];
+  for( int k = 0; k < nc && scaled; k++ )
+  {
+    // (as vvr_read_output_scaled: the component's subsampling, luma always collocated)
+    const bool luma = k == 0;
+    const int cs = luma ? 0 : 1, colX = luma ? 1 : scaleCol & 1, colY = luma ? 1 : ( scaleCol >> 1 ) & 1, fracShift = luma ? 4 : 5;
+    RescaleParams& r = rs[k];
+    r.src = p.src[k]; r.stride = p.stride[k]; r.w = winW >> cs; r.h = winH >> cs; r.outW = p.w[k]; r.outH = p.h[k];
+    r.luma = luma; r.maxVal = ( 1 << c->cfg.bit_depth ) - 1; r.bytesPerSample = 2;
+    int scale;
+    rescale_axis( r.w, r.outW, cs, colX, fracShift, scale, r.addX, r.shiftX ); r.stepX = scale << cs;
+    rescale_axis( r.h, r.outH, cs, colY, fracShift, scale, r.addY, r.shiftY ); r.stepY = scale << cs;
+    if( k == 0 ) p.bySample = 0;
+    if( fused ) continue;      // (k_output_compare_scaled reads the slot itself, sample by sample)
+    p.src[k] = (const pel_t*) ( e->dev + scaleBase + scaleOff[k] ); p.stride[k] = p.w[k];
+    if( p.w[k] & 1 ) p.bySample = 1;
+  }
+  for( int k = 0; k < nc; k++ ) if(( (uintptr_t) p.ref[k] | p.refStride[k] ) & 1 ) p.bySample = 1;
   XpsnrParams xq; memset( &xq, 0, sizeof( xq ) );
   for( int k = 0; k < temporal; k++ )
   {
@@ -2110,6 +2187,17 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   // mu stays held up to the registration of the `read` event (as vvr_output_submit)
   OQCHK( outOrder( c, e, slot, rq->job, jobDone ) );
   if( refSlot >= 0 ) OQCHK( outOrder( c, e, refSlot, -1, nullptr ) );
+  if( scaled && !fused )      // (the slot's last reader: the `read` event is recorded behind it, the measure reads the entry's planes)
+  {
+    double rsBytes = 0;
+    for( int k = 0; k < nc; k++ ) rsBytes += sizeof( pel_t ) * ( (double) rs[k].w * rs[k].h + (double) rs[k].outW * rs[k].outH );
+    outTimeBegin( c, s, e->timed0, e->timing0, K_COMPARE_RESCALE, rsBytes );
+    for( int k = 0; k < nc; k++ ) launch_rescale( s, rs[k], e->dev + scaleBase + scaleOff[k] );
+    if( e->timed0 ) hipEventRecord( e->timing0.b, s );
+    e->rescales = nc;
+    OQCHK( hipGetLastError() );
+    OQCHK( hipEventRecord( e->read, s ) );
+  }
   if( ( staged || stagedPrev ) && !pinnedRef ) OQCHK( hipMemcpyAsync( e->tmp, e->host + hostStageOff, stageBytes, hipMemcpyHostToDevice, s ) );
   for( int k = 0; k < nc && staged && pinnedRef; k++ )
     OQCHK( hipMemcpy2DAsync( e->tmp + stageOff[k], stageStride[k], rq->ref[k], rq->ref_stride_bytes[k], rowBytes[k], p.h[k], hipMemcpyHostToDevice, s ) );
@@ -2126,7 +2214,10 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   double msBytes = 0;
   for( int k = 0; k < scales; k++ ) msBytes += samples / (double) ( 1 << 2 * k ) * ( ( k ? 4 : 2 + rb ) + ( k + 1 < scales ? 1 : 0 ) );
   if( xp ) OQCHK( hipMemsetAsync( e->dev, 0, wordBytes, s ) );      // (the records k_output_xpsnr adds to)
-  outTimeBegin( c, s, e->timed, e->timing, xp ? K_OUTPUT_XPSNR : ms ? K_OUTPUT_MSSSIM : ssim ? K_OUTPUT_SSIM : K_OUTPUT_COMPARE, ms ? msBytes : samples * ( 2 + rb ) + (double) temporal * w * h * rb );
+  double fusedBytes = samples * rb;      // (read: the window in the slot and the reference)
+  for( int k = 0; k < nc && fused; k++ ) fusedBytes += sizeof( pel_t ) * (double) rs[k].w * rs[k].h;
+  outTimeBegin( c, s, e->timed, e->timing, fused ? K_OUTPUT_COMPARE_SCALED : xp ? K_OUTPUT_XPSNR : ms ? K_OUTPUT_MSSSIM : ssim ? K_OUTPUT_SSIM : K_OUTPUT_COMPARE,
+                fused ? fusedBytes : ms ? msBytes : samples * ( 2 + rb ) + (double) temporal * w * h * rb );
   MsssimNext nx; memset( &nx, 0, sizeof( nx ) );
   if( xp )
   {
@@ -2135,10 +2226,17 @@ static int compareSubmit( vvr_context* c, const vvr_compare_request* rq, const c
   }
   else if( ms ) { if( scales > 1 ) level( 1, nx ); launch_output_msssim( s, p, c->cfg.bit_depth, recs, scales > 1 ? &nx : nullptr ); }
   else if( ssim ) launch_output_ssim( s, p, c->cfg.bit_depth, recs, (int32_t*) ( words + CMP_HEAD_WORDS ) );
+  else if( fused )
+  {
+    CompareScaledParams sp; memset( &sp, 0, sizeof( sp ) );
+    for( int k = 0; k < nc; k++ ) { sp.rs[k] = rs[k]; sp.ref[k] = p.ref[k]; sp.refStride[k] = p.refStride[k]; }
+    sp.numComp = nc; sp.refBytes = rb; sp.nbx = p.nbx; sp.nby = p.nby; sp.byByte = p.bySample;
+    launch_output_compare_scaled( s, sp, recs, words + CMP_HEAD_WORDS );
+  }
   else launch_output_compare( s, p, recs, words + CMP_HEAD_WORDS );
   if( e->timed && scales <= 1 ) hipEventRecord( e->timing.b, s );
   OQCHK( hipGetLastError() );
-  OQCHK( hipEventRecord( e->read, s ) );      // (the slots' reader ends here: the fold reads the entry's scratch)
+  if( !scaled || fused ) OQCHK( hipEventRecord( e->read, s ) );      // (the slots' reader ends here: the fold reads the entry's scratch)
   c->slotExt[slot].push_back( e->read );
   if( refSlot >= 0 ) { c->slotExt[refSlot].push_back( e->read ); e->refSlot = refSlot; }
   e->state = OQ_FLIGHT; e->queued = true;
@@ -2249,6 +2347,7 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
   if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
   outTimeEnd( c, e->timed, e->timing, e->msScales ? e->msScales : 1 );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS; K_OUTPUT_MSSSIM, a launch per scale ...
+  outTimeEnd( c, e->timed0, e->timing0, e->rescales );      // (K_COMPARE_RESCALE)
   outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM; K_OUTPUT_COMPARE and K_OUTPUT_COMPARE_SUM; K_OUTPUT_SSIM and K_OUTPUT_SSIM_SUM; K_OUTPUT_MSSSIM_SUM)
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
   if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
