@@ -634,7 +634,7 @@ typedef struct vvr_output_request {
   int32_t  job;                /* >= 0: the picture this job reconstructs into `slot`, ordered behind it ON THE DEVICE;
                                   -1: the slot as all work submitted so far leaves it (vvr_stream_wait_slot's rule) */
   int32_t  x, y, w, h;         /* window, luma samples (even in 4:2:0) */
-  int32_t  out_w, out_h;       /* 0, 0: the window's size; else rescaled as vvr_read_output_scaled does it (chroma: >> 1) */
+  int32_t  out_w, out_h;       /* 0, 0: the window's size; else rescaled as vvr_read_output_scaled does it (chroma: >> 1), or resampled by the filter of vvr_set_output_resampling */
   uint8_t  collocated;         /* as vvr_read_output_scaled */
   uint8_t  format;             /* VVR_OUT_* */
   uint8_t  grain;              /* 1: the context's bank is added first, one frame of the seed chain (vvr_read_output_grain's rules) */
@@ -673,6 +673,47 @@ VVR_API int          vvr_set_output_colour(vvr_context* ctx, int matrix_coeffici
  *   blue-noise masks; dither for the RGB formats; P210 / NV16. */
 enum { VVR_NARROW_REFUSE = 0, VVR_NARROW_TRUNCATE = 1, VVR_NARROW_ROUND = 2, VVR_NARROW_DITHER = 3 };
 VVR_API int          vvr_set_output_narrowing(vvr_context* ctx, int mode, int phase);
+/* Antialiased resampling for out_w / out_h - context state, like the narrowing.  filter: VVR_RESAMPLE_REFERENCE (a new context: the rescale
+ * step is vvdec::rescalePlane's DCTIF as ever - same bytes, same refusals, same texts), _AREA, _TRIANGLE (what torch's interpolate( mode =
+ * "bilinear", antialias = True ) and PIL's BILINEAR compute) or _CUBIC (Keys, a = -1/2: torch's "bicubic" with antialias, PIL's BICUBIC).  A
+ * value outside 0 .. 3 is VVR_ERR_PARAMETER with a text, and the value set before stays.  A request takes the value that is set when
+ * vvr_output_submit accepts it; a later call never changes a request in flight.
+ *   With a filter set the rescale step of vvr_output_submit's chain (window -> grain -> rescale -> format) is k_output_resample, for every
+ *   format and every kind of destination; everything behind it reads the resampled 4:2:0 frame exactly as it reads the rescaled one.  The
+ *   accepted range becomes, per plane and axis, n <= 64 m and m <= 8 n with m >= 1 (n source, m output samples; chroma sizes are >> 1 of the
+ *   window's and of the output's; output sides stay 1 .. 8192).  A request outside it is refused with a text naming the limit before a ring
+ *   entry is taken or the seed chain advances.
+ *   Defined to the bit, in integers.  Each plane is resampled on its own, horizontally then vertically.  Per axis: n is the number of source
+ *   samples of the frame being converted (the window, after grain if `grain` is set), m the number of output samples; phi = 2 for luma and
+ *   for chroma whose `collocated` bit of that axis is 0, phi = 1 for chroma whose bit is 1 (the output keeps the siting of the source).  With
+ *   g = gcd( n, m ), n' = n / g, m' = m / g:
+ *     P_k = ( 4 k + phi ) m'      Q_i = ( 4 i + phi ) n'      S = 4 max( n', m' )      N = | P_k - Q_i |
+ *   (the weights do not change under the division by g; it keeps every integer below inside 64 bits: 4 S^3 * 32768 < 2^63 for S <= 32768).
+ *   Numerator of source sample k for output sample i:
+ *     TRIANGLE  S - N where N < S
+ *     CUBIC     3 N^3 - 5 N^2 S + 2 S^3 where N < S;  - N^3 + 5 N^2 S - 8 N S^2 + 4 S^3 where S <= N < 2 S (may be 0 or negative)
+ *     AREA      the length of the overlap of the output footprint [ Q_i - 2 n', Q_i + 2 n' ) with the box of sample k,
+ *               [ P_k - 2 m', P_k + 2 m' ); the box of sample 0 reaches to minus infinity, the box of sample n - 1 to plus infinity, so the
+ *               numerators always sum to 4 n'
+ *   Taps: the samples 0 <= k < n with N < S (TRIANGLE), N < 2 S (CUBIC), a positive overlap (AREA).  They form one run first .. first +
+ *   count - 1 with count <= VVR_RESAMPLE_MAX_TAPS.  Samples beyond the plane are dropped, not clamped - the renormalisation torch and PIL do,
+ *   which is why the edges agree with them.
+ *   Weights: T is the sum of the kept numerators (positive); w_k = floor( ( 2 num_k 16384 + T ) / ( 2 T ) ), the floor towards minus
+ *   infinity; then 16384 - sum( w_k ) is added to the largest w_k, the lowest k among equals.  Every tap list sums to exactly 16384 and a flat
+ *   plane stays flat.
+ *   Horizontal pass, for every source row r:   H[r][i] = ( sum_k wx[i][k] s[r][k] + 512 ) >> 10      (arithmetic shift; four fractional bits, not clipped)
+ *   Vertical pass:                        out[j][i] = clip( ( sum_r wy[j][r] H[r][i] + 131072 ) >> 18, 0, 2^bd - 1 )
+ *   All sums are in int32: integer sums, so any order and any tiling give the same bits; the rounding of H is per sample.
+ *   vvr_resample_taps: a host helper like vvr_xpsnr_blocks - the taps of output sample i of one axis (phase: the phi above, 1 or 2) into
+ *   *first and weights[0 .. count - 1]; returns count, or VVR_ERR_PARAMETER for filter 0 or an unknown filter, sizes outside the accepted range
+ *   (1 <= n, m <= 8192, n <= 64 m, m <= 8 n), a phase other than 1 or 2, i outside 0 .. m - 1, or a NULL pointer.
+ *   Not offered: Lanczos, Mitchell, Gaussian and other kernels; ratios beyond 1/64; the filters for vvr_read_output_scaled and the other
+ *   synchronous calls, for vvr_set_compare_scaling, for statistics and hashes - those keep the reference's DCTIF (or read the picture as it
+ *   lies) whatever is set here. */
+enum { VVR_RESAMPLE_REFERENCE = 0, VVR_RESAMPLE_AREA = 1, VVR_RESAMPLE_TRIANGLE = 2, VVR_RESAMPLE_CUBIC = 3 };
+#define VVR_RESAMPLE_MAX_TAPS 256
+VVR_API int          vvr_set_output_resampling(vvr_context* ctx, int filter);
+VVR_API int          vvr_resample_taps(int filter, int n, int m, int phase, int i, int32_t* first, int16_t weights[VVR_RESAMPLE_MAX_TAPS]);   /* returns count, or VVR_ERR_PARAMETER */
 /* Normalisation of VVR_OUT_RGBF32: a mean and a standard deviation per channel (R, G, B), as a vision model takes them.  Context state like the
  * colour description (copied; NULL, NULL: none; a new context has none): a VVR_OUT_RGBF32 request takes the value that is set when
  * vvr_output_submit accepts it, it travels as kernel arguments, a later call never changes a request in flight.  Every other format -

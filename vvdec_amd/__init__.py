@@ -78,6 +78,7 @@ def lib():
         L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
         abi.bind_output_narrowing(L)
         abi.bind_compare_scaling(L)
+        abi.bind_output_resampling(L)
         L.vvr_set_output_normalisation.restype = C.c_int
         L.vvr_set_output_normalisation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vvr_set_output_transform.restype = C.c_int
@@ -152,7 +153,7 @@ def lib():
 
 
 EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "vvr_wait", "vvr_test", "vvr_sync", "vvr_slot_bytes", "vvr_plane_layout",
-                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_narrowing", "vvr_set_compare_scaling", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_set_output_lut3d", "vvr_output_lut3d_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
+                    "vvr_plane_ptr", "vvr_read_plane", "vvr_read_output", "vvr_read_output_scaled", "vvr_set_film_grain", "vvr_set_film_grain_seed", "vvr_set_output_colour", "vvr_set_output_narrowing", "vvr_set_output_resampling", "vvr_resample_taps", "vvr_set_compare_scaling", "vvr_set_output_normalisation", "vvr_set_output_transform", "vvr_output_transform_preset", "vvr_set_output_lut3d", "vvr_output_lut3d_preset", "vvr_read_output_grain", "vvr_picture_hash", "vvr_write_plane", "vvr_read_dmvr", "vvr_read_col_motion", "vvr_prepare", "vvr_submit_prepared",
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
@@ -160,6 +161,17 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_compare_submit", "vvr_compare_psnr", "vvr_ssim_submit", "vvr_compare_ssim", "vvr_msssim_submit", "vvr_compare_msssim",
                     "vvr_xpsnr_submit", "vvr_xpsnr_blocks", "vvr_compare_xpsnr",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
+
+
+def resample_taps(filter, n, m, phase, i):
+    """vvr_resample_taps: the taps of output sample i of one axis under a filter of Reconstructor.set_output_resampling ("area", "triangle",
+    "cubic" or 1 .. 3), n source and m output samples; phase 2 for luma and for chroma that is not collocated on the axis, 1 for chroma that is
+    -> (first, [weights]): source samples first .. first + len( weights ) - 1, weights that sum to 16384.  A pure host function: no context, no
+    device.  Raises ValueError for what the call refuses (filter 0, sizes outside 1/64 .. 8, i outside 0 .. m - 1)."""
+    got = abi.resample_taps(lib(), filter, n, m, phase, i)
+    if got is None:
+        raise ValueError("resample_taps: refused (filter %r, %r -> %r samples, phase %r, sample %r)" % (filter, n, m, phase, i))
+    return got
 
 
 def output_transform(transfer, primaries, target, src_peak=1000., dst_peak=100., bit_depth=10):
@@ -463,6 +475,18 @@ class Reconstructor:
                 raise ValueError("set_output_narrowing: mode is 0 .. 3 or one of %s" % ", ".join(abi.NARROW_MODES))
             mode = abi.NARROW_MODES[mode]
         self._check(self.L.vvr_set_output_narrowing(self.ctx, int(mode), int(phase)))
+
+    def set_output_resampling(self, filter):
+        """the filter output_submit(size=...) resamples with (vvr_set_output_resampling, the arithmetic: vvr.h): None (a new context: the
+        reference's DCTIF, within 1/8 .. 8 times the window), "area", "triangle" (torch's antialiased "bilinear", PIL's BILINEAR) or "cubic"
+        (torch's antialiased "bicubic", PIL's BICUBIC) - antialiased, support scaled by the ratio, accepted within 1/64 .. 8 times the window
+        in every plane, for every format and destination.  A request takes the value that is set when it is submitted; read_output(size=...),
+        the comparisons under set_compare_scaling, statistics and hashes do not look at it."""
+        if filter is None or isinstance(filter, str):
+            if filter not in abi.RESAMPLE_FILTERS:
+                raise ValueError("set_output_resampling: filter is None, 0 .. 3 or one of %s" % ", ".join(k for k in abi.RESAMPLE_FILTERS if k))
+            filter = abi.RESAMPLE_FILTERS[filter]
+        self._check(self.L.vvr_set_output_resampling(self.ctx, int(filter)))
 
     def set_compare_scaling(self, size=None, collocated=(True, False)):
         """a reference of another size than the window for compare(), ssim(), msssim() and xpsnr() (vvr_set_compare_scaling, the definition:

@@ -186,6 +186,29 @@ def bind_output_narrowing(L):
     return L
 
 
+# vvr_set_output_resampling: the filter out_w / out_h resample with (VVR_RESAMPLE_*); None / "reference": the reference's DCTIF
+RESAMPLE_REFERENCE, RESAMPLE_AREA, RESAMPLE_TRIANGLE, RESAMPLE_CUBIC = 0, 1, 2, 3
+RESAMPLE_FILTERS = {None: RESAMPLE_REFERENCE, "reference": RESAMPLE_REFERENCE, "area": RESAMPLE_AREA, "triangle": RESAMPLE_TRIANGLE, "cubic": RESAMPLE_CUBIC}
+RESAMPLE_MAX_TAPS = 256
+
+
+def bind_output_resampling(L):
+    """the ctypes signatures of vvr_set_output_resampling and vvr_resample_taps on a loaded library (the product's, or the host build of the tests)"""
+    L.vvr_set_output_resampling.restype = C.c_int
+    L.vvr_set_output_resampling.argtypes = [C.c_void_p, C.c_int]
+    L.vvr_resample_taps.restype = C.c_int
+    L.vvr_resample_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return L
+
+
+def resample_taps(L, filter, n, m, phase, i):
+    """vvr_resample_taps: (first, [weights]) of output sample i of an axis of n source and m output samples (phase: 2, or 1 for chroma that is
+    collocated on the axis), or None where the call refuses.  filter: 1 .. 3 or a name of RESAMPLE_FILTERS"""
+    first, w = C.c_int32(0), (C.c_int16 * RESAMPLE_MAX_TAPS)()
+    count = L.vvr_resample_taps(RESAMPLE_FILTERS.get(filter, filter), int(n), int(m), int(phase), int(i), C.byref(first), w)
+    return None if count < 0 else (first.value, list(w[:count]))
+
+
 def bind_compare_scaling(L):
     """the ctypes signature of vvr_set_compare_scaling on a loaded library (the product's, or the host build of the tests)"""
     L.vvr_set_compare_scaling.restype = C.c_int

@@ -90,7 +90,7 @@ static double g_wdSum[6]; static uint64_t g_wdJobs; static double g_wdPart[4], g
 
 struct Stat { uint64_t launches = 0; double ms = 0, bytes = 0; };
 struct PendingTiming { hipEvent_t a, b; int kernel; double bytes; };
-const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame", "k_output_rgb", "k_hash_rows", "k_hash_combine", "k_plane_hash_rows", "k_output_stats", "k_output_stats_sum", "k_output_compare", "k_output_compare_sum", "k_output_ssim", "k_output_ssim_sum", "k_output_yuv", "k_output_narrow", "k_output_msssim", "k_output_msssim_sum", "k_output_xpsnr", "k_rescale", "k_output_compare_scaled" };
+const char* const kKernelNames[K_NUM] = { "k_mc", "k_mc_dmvr", "k_mc_affine", "k_lmcs", "k_itrans", "k_intra", "k_resi_add", "k_deblock_v", "k_deblock_h", "k_sao", "k_alf", "k_copy", "k_output", "k_lf_init", "k_intra_leaf", "k_deblock4", "k_alf_planes", "k_output_frame", "k_output_rgb", "k_hash_rows", "k_hash_combine", "k_plane_hash_rows", "k_output_stats", "k_output_stats_sum", "k_output_compare", "k_output_compare_sum", "k_output_ssim", "k_output_ssim_sum", "k_output_yuv", "k_output_narrow", "k_output_msssim", "k_output_msssim_sum", "k_output_xpsnr", "k_rescale", "k_output_compare_scaled", "k_output_resample" };
 
 // One slot of the upload ring: pinned staging memory and its image in HBM (grown on demand, never freed while the context lives), the device
 // pointers of the picture that currently sits in it, and the pinned landing area of its DMVR delta MVs.
@@ -176,6 +176,10 @@ struct vvr_context {
   int        outMatrix = 0, outFullRange = 0;
   // ... and the narrowing of the byte-per-sample Y'CbCr formats in a context of 9 or 10 bits (vvr_set_output_narrowing): VVR_NARROW_*, the dither's phase
   int        outNarrow = 0, outNarrowPhase = 0;
+  // ... and the filter out_w / out_h resample with (vvr_set_output_resampling): VVR_RESAMPLE_*; the tap tables of the axes it has been used
+  // for, in device memory (vvr_output.inc: resampleTable), and the count their uses are numbered with
+  int        outResample = 0;
+  struct ResampleTable* resampleTabs = nullptr; uint64_t resampleUses = 0;
   // ... and the size the comparison, SSIM, MS-SSIM and XPSNR requests rescale their window to (vvr_set_compare_scaling): luma samples (0, 0: as it
   // lies) and the chroma phase; read once, under mu, where a request is submitted
   int        cmpScaleW = 0, cmpScaleH = 0, cmpScaleCollocated = 0;
@@ -1625,6 +1629,15 @@ VVR_API int vvr_set_output_narrowing( vvr_context* c, int mode, int phase )
   if( mode < VVR_NARROW_REFUSE || mode > VVR_NARROW_DITHER ) { c->setError( "vvr_set_output_narrowing: mode must be 0 (refuse), 1 (truncate), 2 (round) or 3 (dither)" ); return VVR_ERR_PARAMETER; }
   if( phase < 0 || phase > 3 ) { c->setError( "vvr_set_output_narrowing: phase must be 0 .. 3" ); return VVR_ERR_PARAMETER; }
   c->outNarrow = mode; c->outNarrowPhase = phase;
+  return VVR_OK;
+}
+
+VVR_API int vvr_set_output_resampling( vvr_context* c, int filter )
+{
+  if( !c ) return VVR_ERR_PARAMETER;
+  std::lock_guard<std::mutex> lk( c->mu );
+  if( filter < VVR_RESAMPLE_REFERENCE || filter > VVR_RESAMPLE_CUBIC ) { c->setError( "vvr_set_output_resampling: filter must be 0 (the reference's DCTIF), 1 (area), 2 (triangle) or 3 (cubic)" ); return VVR_ERR_PARAMETER; }
+  c->outResample = filter;
   return VVR_OK;
 }
 

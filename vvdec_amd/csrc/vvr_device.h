@@ -233,6 +233,20 @@ struct RescaleParams
   int luma, maxVal, bytesPerSample;
 };
 void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst );
+// antialiased resampling (vvr_set_output_resampling, the definition: vvr.h; k_output_resample): a window of w x h samples to outW x outH, stored
+// like launch_rescale's.  tabX / tabY: the tap table of an axis in device memory, built on the host from the integer definition - m words
+// first | count << 16, one per output sample, then tapsX (tapsY) x m int16 weights tap-major: weight t of output sample i at [ t * m + i ],
+// 0 behind a sample's count.  tapsX / tapsY: the largest count of the axis.  Every tap lies inside the plane (first >= 0, first + count <= n).
+struct ResampleParams
+{
+  const pel_t* src; int stride, w, h, outW, outH;
+  const uint32_t* tabX; const uint32_t* tabY; int tapsX, tapsY;
+  int maxVal, bytesPerSample;
+};
+// a plane that shrinks by more than 4 vertically takes two launches - k_output_resample_h into `scratch`, h x outW 32-bit words, then the vertical
+// pass over those (vvr_kernels.hip) - every other plane one, and no scratch
+static inline bool resample_two_launches( int h, int outH ) { return h > 4 * outH; }
+void launch_output_resample( hipStream_t s, const ResampleParams& p, void* dst, void* scratch );
 // film grain synthesis at the output (FilmGrainImpl::add_grain_block, FilmGrainImpl.cpp:126-324) over a window of every component, packed like
 // launch_output_window into dst + dstOff[c].  words: one random word per 16x16 luma block of the window, nbx per band (vvr_output.inc, grain_words);
 // bank: the device copy of the context's vvr_film_grain_bank

@@ -21,7 +21,8 @@ enum { K_MC, K_MC_DMVR, K_MC_AFFINE, K_LMCS, K_ITRANS, K_INTRA, K_RESI_ADD, K_DE
        K_OUTPUT_MSSSIM, K_OUTPUT_MSSSIM_SUM /* the launches of an MS-SSIM request (vvr_msssim_submit): one k_output_msssim per scale, timed together, then the fold of all levels */,
        K_OUTPUT_XPSNR /* the one launch of an XPSNR request (vvr_xpsnr_submit): it adds to the request's cleared block records */,
        K_COMPARE_RESCALE /* the k_rescale launches, one per component and timed together, ahead of an SSIM, MS-SSIM or XPSNR request under vvr_set_compare_scaling */,
-       K_OUTPUT_COMPARE_SCALED /* a comparison request under vvr_set_compare_scaling (k_output_compare_scaled behind the launch that clears its records): rescaled and compared in one pass */, K_NUM };
+       K_OUTPUT_COMPARE_SCALED /* a comparison request under vvr_set_compare_scaling (k_output_compare_scaled behind the launch that clears its records): rescaled and compared in one pass */,
+       K_OUTPUT_RESAMPLE /* the k_output_resample launches of a request under vvr_set_output_resampling: one per component that changes its size, timed together */, K_NUM };
 
 // A picture description resident in HBM together with its device work lists: every pointer is a device address inside one blob.
 // Streaming submissions (vvr_submit) use the blob of a ring entry owned by the context; vvr_prepare gives the handle a blob of its own.

@@ -4868,6 +4868,123 @@ void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst )
   else         hipLaunchKernelGGL( k_rescale<4>, grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst );
 }
 
+// k_output_resample — antialiased resampling at the output (vvr_set_output_resampling, the definition: vvr.h): area, triangle or Keys cubic with
+// the support scaled by the ratio, down to 1/64.  The taps come from tables the host builds from the integer definition (ResampleParams,
+// vvr_device.h): per output sample of an axis its first source sample and its count, and the weights tap-major, so that the lanes of a
+// wavefront - a lane per output column, as in k_rescale - read neighbouring words.  The count is a run-time value up to 256: the tap loops run
+// over the tables, nothing is kept in register arrays indexed by a tap.
+// One workgroup per tile of 64 output columns x tileH output rows (tileH <= 32: a thread owns column `lane` of the rows j0 + wave + 4 q, one
+// accumulator each).  Nothing in LDS is sized by the ratio: the source rows the tile's vertical taps reach are taken in chunks of RSM_ROWS, and
+// of each row the segment the tile's horizontal taps reach in pieces of RSM_SEG samples.  Per chunk: the four wavefronts take its rows in turn;
+// a wavefront stages a piece of the row with coalesced loads in an LDS row of its own, every lane adds the taps of its column that lie in the
+// piece, and behind the last piece the sum is rounded - ( sum + 512 ) >> 10, per sample, whatever tile computes it - into the chunk's plane of
+// horizontal results; then every thread adds the chunk's rows that its output rows' taps reach to its accumulators.  All sums are integer sums,
+// so the order of the pieces and chunks does not matter.  The results are kept as 32-bit words: the definition does not clip them, and a slot may
+// hold words beyond the bit depth.  Behind the last chunk ( sum + 131072 ) >> 18, the clip and the store, 16-bit words or bytes as k_rescale's.
+#define RSM_TW   64
+#define RSM_ROWS 48      // rows of horizontal results of a chunk: 48 x 64 int32 = 12 KiB
+#define RSM_SEG  1024    // source samples of a piece: 2 KiB per wavefront
+#define RSM_MAXQ 8       // output rows of a thread: tileH <= 4 * RSM_MAXQ
+// the horizontal sum of one source row for the lane's output column i (taps fx .. fx + cx - 1), the row's segment [xLo, xHi] staged piece by piece in `seg`
+__device__ __forceinline__ int rsm_row_sum( const pel_t* __restrict__ row, const int16_t* __restrict__ wx, pel_t* seg, int lane, int i, int outW, int fx, int cx, int xLo, int xHi )
+{
+  int sum = 0;
+  for( int c0 = xLo; c0 <= xHi; c0 += RSM_SEG )
+  {
+    const int len = min( RSM_SEG, xHi - c0 + 1 );
+    for( int t = lane; t < len; t += 64 ) seg[t] = row[c0 + t];
+    __builtin_amdgcn_wave_barrier();
+    const int k1 = min( fx + cx, c0 + len );
+    for( int k = max( fx, c0 ); k < k1; k++ ) sum += wx[(size_t) ( k - fx ) * outW + i] * seg[k - c0];
+    __builtin_amdgcn_wave_barrier();
+  }
+  return sum;
+}
+// FROM_H: the horizontal results come from the plane k_output_resample_h has stored (hsrc: h rows of outW words) instead of being computed here
+template<bool FROM_H>
+__global__ __launch_bounds__( 256 ) void k_output_resample( ResampleParams p, int tileH, const int* __restrict__ hsrc, uint8_t* __restrict__ dst )
+{
+  __shared__ int rsm_h[RSM_ROWS * RSM_TW];
+  __shared__ pel_t rsm_seg[FROM_H ? 1 : 4][FROM_H ? 1 : RSM_SEG];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * RSM_TW, iOut = i0 + lane, iLast = min( i0 + RSM_TW, p.outW ) - 1, i = min( iOut, iLast );
+  const int j0 = blockIdx.y * tileH, j1 = min( j0 + tileH, p.outH ) - 1;
+  const int16_t* __restrict__ wx = (const int16_t*) ( p.tabX + p.outW );
+  const int16_t* __restrict__ wy = (const int16_t*) ( p.tabY + p.outH );
+  // the source columns and rows the tile's taps reach (first and first + count grow with the output sample), the lane's column
+  const uint32_t tx0 = p.tabX[i0], tx1 = p.tabX[iLast], ty0 = p.tabY[j0], ty1 = p.tabY[j1], tx = p.tabX[i];
+  const int xLo = tx0 & 0xffff, xHi = min( (int) ( ( tx1 & 0xffff ) + ( tx1 >> 16 ) ), p.w ) - 1;
+  const int rowLo = ty0 & 0xffff, rowHi = min( (int) ( ( ty1 & 0xffff ) + ( ty1 >> 16 ) ), p.h ) - 1;
+  const int fx = tx & 0xffff, cx = tx >> 16;
+  int acc[RSM_MAXQ], fy[RSM_MAXQ], cy[RSM_MAXQ];
+#pragma unroll
+  for( int q = 0; q < RSM_MAXQ; q++ )
+  {
+    const int j = j0 + wave + 4 * q;
+    const uint32_t ty = j <= j1 ? p.tabY[j] : 0;
+    acc[q] = 0; fy[q] = ty & 0xffff; cy[q] = ty >> 16;
+  }
+  for( int c0r = rowLo; c0r <= rowHi; c0r += RSM_ROWS )
+  {
+    const int c1r = min( c0r + RSM_ROWS - 1, rowHi );
+    for( int r = c0r + wave; r <= c1r; r += 4 )
+    {
+      if( FROM_H ) rsm_h[( r - c0r ) * RSM_TW + lane] = hsrc[(size_t) r * p.outW + i];
+      else rsm_h[( r - c0r ) * RSM_TW + lane] = ( rsm_row_sum( p.src + (size_t) r * p.stride, wx, rsm_seg[FROM_H ? 0 : wave], lane, i, p.outW, fx, cx, xLo, xHi ) + 512 ) >> 10;
+    }
+    __syncthreads();
+#pragma unroll
+    for( int q = 0; q < RSM_MAXQ; q++ )
+    {
+      const int j = j0 + wave + 4 * q, k1 = min( fy[q] + cy[q], c1r + 1 );
+      for( int r = max( fy[q], c0r ); r < k1; r++ ) acc[q] += wy[(size_t) ( r - fy[q] ) * p.outH + j] * rsm_h[( r - c0r ) * RSM_TW + lane];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for( int q = 0; q < RSM_MAXQ; q++ )
+  {
+    const int j = j0 + wave + 4 * q;
+    const int v = clip3( 0, p.maxVal, ( acc[q] + 131072 ) >> 18 );
+    if( j <= j1 && iOut < p.outW )
+    {
+      if( p.bytesPerSample == 2 ) ( (uint16_t*) dst )[(size_t) j * p.outW + iOut] = (uint16_t) v;
+      else dst[(size_t) j * p.outW + iOut] = (uint8_t) v;
+    }
+  }
+}
+// k_output_resample_h — the horizontal pass alone, for the planes that shrink by more than 4 vertically (resample_two_launches, vvr_device.h): there
+// a tile of the one-launch form reads many source rows for few output rows, there are few tiles, and neighbouring tiles compute the same rows
+// again.  A wavefront per source row and 64 output columns - thousands of them at any size - stores the rounded sums as 32-bit words, rows of outW
+// back to back, into the request's scratch; k_output_resample<true> runs the vertical pass over that plane.
+__global__ __launch_bounds__( 256 ) void k_output_resample_h( ResampleParams p, int* __restrict__ hdst )
+{
+  __shared__ pel_t rsm_seg[4][RSM_SEG];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * RSM_TW, iOut = i0 + lane, iLast = min( i0 + RSM_TW, p.outW ) - 1, i = min( iOut, iLast );
+  const int r = blockIdx.y * 4 + wave;
+  if( r >= p.h ) return;      // (no workgroup barrier below)
+  const int16_t* __restrict__ wx = (const int16_t*) ( p.tabX + p.outW );
+  const uint32_t tx0 = p.tabX[i0], tx1 = p.tabX[iLast], tx = p.tabX[i];
+  const int xLo = tx0 & 0xffff, xHi = min( (int) ( ( tx1 & 0xffff ) + ( tx1 >> 16 ) ), p.w ) - 1;
+  const int sum = rsm_row_sum( p.src + (size_t) r * p.stride, wx, rsm_seg[wave], lane, i, p.outW, tx & 0xffff, tx >> 16, xLo, xHi );
+  if( iOut < p.outW ) hdst[(size_t) r * p.outW + iOut] = ( sum + 512 ) >> 10;
+}
+void launch_output_resample( hipStream_t s, const ResampleParams& p, void* dst, void* scratch )
+{
+  // (a small plane - a model's 224 x 224 - in shorter tiles, so that more compute units get a workgroup)
+  const int tilesX = ( p.outW + RSM_TW - 1 ) / RSM_TW;
+  int tileH = 4 * RSM_MAXQ;
+  while( tileH > 4 && (int64_t) tilesX * ( ( p.outH + tileH - 1 ) / tileH ) < 512 ) tileH >>= 1;
+  const dim3 grid( tilesX, ( p.outH + tileH - 1 ) / tileH );
+  if( resample_two_launches( p.h, p.outH ) )
+  {
+    hipLaunchKernelGGL( k_output_resample_h, dim3( tilesX, ( p.h + 3 ) / 4 ), dim3( 256 ), 0, s, p, (int*) scratch );
+    hipLaunchKernelGGL( k_output_resample<true>, grid, dim3( 256 ), 0, s, p, tileH, (const int*) scratch, (uint8_t*) dst );
+  }
+  else hipLaunchKernelGGL( k_output_resample<false>, grid, dim3( 256 ), 0, s, p, tileH, (const int*) nullptr, (uint8_t*) dst );
+}
+
 // k_film_grain — film grain synthesis at the output, the VFGS hardware model of the reference (FilmGrainImpl::add_grain_block ->
 // make_grain_pattern + scale_and_output, FilmGrainImpl.cpp:126-324, line by line as FilmGrain::add_grain_line drives it).  Every sample depends
 // only on its own intensity, on its 16x16 block's random word (8x8 in 4:2:0 chroma; the word of the block above for the overlap rows) and, at a

@@ -106,6 +106,50 @@ void rescale_axis( int src, int dst, int cs, int collocated, int fracShift, int&
   add = ( 1 << ( shift - 1 ) ) + ( ( ( 1 - collocated ) * 8 * ( scale - ( 1 << 14 ) ) + ( 1 << ( 2 + cs ) ) ) >> ( 3 + cs ) );
 }
 
+// the taps of output sample i of an axis of n source and m output samples under a filter of vvr_set_output_resampling, the definition of vvr.h
+// term by term in 64-bit integers (n, m, phi, i checked by the caller: 1 <= n, m <= 8192, n <= 64 m, m <= 8 n).  Returns the count, 0 when
+// the definition gives no tap list (it does not inside the accepted range)
+int64_t floorDiv( int64_t a, int64_t b ) { const int64_t q = a / b; return ( a % b != 0 && ( ( a < 0 ) != ( b < 0 ) ) ) ? q - 1 : q; }      // b > 0 throughout
+int resample_taps_of( int filter, int n, int m, int phi, int i, int& first, int16_t* w )
+{
+  int a = n, b = m; while( b ) { const int t = a % b; a = b; b = t; }
+  const int64_t n1 = n / a, m1 = m / a, S = 4 * std::max( n1, m1 ), Q = ( 4 * (int64_t) i + phi ) * n1;
+  int64_t num[VVR_RESAMPLE_MAX_TAPS], kLo, kHi;
+  if( filter == VVR_RESAMPLE_AREA )
+  {
+    // the boxes tile the line: box k = [ 4 k m' + ( phi - 2 ) m', 4 ( k + 1 ) m' + ( phi - 2 ) m' ); the two outermost take what lies beyond them
+    const int64_t lo = Q - 2 * n1, hi = Q + 2 * n1, base = ( phi - 2 ) * m1;
+    kLo = std::min<int64_t>( std::max<int64_t>( floorDiv( lo - base, 4 * m1 ), 0 ), n - 1 ); kHi = std::max<int64_t>( std::min<int64_t>( floorDiv( hi - 1 - base, 4 * m1 ), n - 1 ), 0 );
+    if( kHi - kLo + 1 > VVR_RESAMPLE_MAX_TAPS ) return 0;
+    for( int64_t k = kLo; k <= kHi; k++ )
+    {
+      const int64_t from = k == 0 ? lo : std::max( lo, 4 * k * m1 + base ), to = k == n - 1 ? hi : std::min( hi, 4 * ( k + 1 ) * m1 + base );
+      num[k - kLo] = to - from;
+    }
+  }
+  else
+  {
+    const int64_t R = filter == VVR_RESAMPLE_CUBIC ? 2 * S : S;      // N < R: Q - R < P_k < Q + R
+    kLo = std::max<int64_t>( -floorDiv( -( Q - R + 1 - phi * m1 ), 4 * m1 ), 0 ); kHi = std::min<int64_t>( floorDiv( Q + R - 1 - phi * m1, 4 * m1 ), n - 1 );
+    if( kHi < kLo || kHi - kLo + 1 > VVR_RESAMPLE_MAX_TAPS ) return 0;
+    for( int64_t k = kLo; k <= kHi; k++ )
+    {
+      const int64_t P = ( 4 * k + phi ) * m1, N = P > Q ? P - Q : Q - P;
+      num[k - kLo] = filter == VVR_RESAMPLE_TRIANGLE ? S - N : N < S ? 3 * N * N * N - 5 * N * N * S + 2 * S * S * S : -N * N * N + 5 * N * N * S - 8 * N * S * S + 4 * S * S * S;
+    }
+  }
+  const int count = (int) ( kHi - kLo + 1 );
+  int64_t T = 0;
+  for( int k = 0; k < count; k++ ) T += num[k];
+  if( T <= 0 ) return 0;
+  int sum = 0, best = 0;
+  for( int k = 0; k < count; k++ ) { w[k] = (int16_t) floorDiv( 2 * num[k] * 16384 + T, 2 * T ); sum += w[k]; if( w[k] > w[best] ) best = k; }
+  w[best] = (int16_t) ( w[best] + 16384 - sum );
+  first = (int) kLo;
+  return count;
+}
+bool resample_axis_ok( int n, int m ) { return n >= 1 && m >= 1 && n <= 8192 && m <= 8192 && n <= 64 * m && m <= 8 * n; }
+
 // the film grain's random generator (prng, FilmGrainImpl.h) and the words of a frame's blocks: FilmGrain::prepareBlockSeeds( w, h ) gives band
 // by (16 luma rows) the seed s[by], s[0] the chain's state and s[by + 1] = s[by] after nbx steps; add_grain_line gives block bx of the band s[by]
 // after bx steps.  words: nby x nbx.  Returns the chain's state after the frame, the seed of its last band (FilmGrain.cpp:794-820).
@@ -179,6 +223,31 @@ void launch_rescale( hipStream_t, const RescaleParams& p, void* dst )
       if( p.bytesPerSample == 2 ) ( (uint16_t*) dst )[(size_t) j * p.outW + i] = (uint16_t) v; else ( (uint8_t*) dst )[(size_t) j * p.outW + i] = (uint8_t) v;
     }
   }
+}
+
+// ... and launch_output_resample (k_output_resample): the two passes of vvr_set_output_resampling (vvr.h) sample by sample over the tap tables
+// as the device takes them
+void launch_output_resample( hipStream_t, const ResampleParams& p, void* dst, void* )
+{
+  const int16_t* wx = (const int16_t*) ( p.tabX + p.outW ); const int16_t* wy = (const int16_t*) ( p.tabY + p.outH );
+  std::vector<int> H( (size_t) p.h * p.outW );
+  for( int r = 0; r < p.h; r++ )
+    for( int i = 0; i < p.outW; i++ )
+    {
+      const int first = p.tabX[i] & 0xffff, count = p.tabX[i] >> 16;
+      int sum = 0;
+      for( int t = 0; t < count; t++ ) sum += wx[(size_t) t * p.outW + i] * p.src[(size_t) r * p.stride + first + t];
+      H[(size_t) r * p.outW + i] = ( sum + 512 ) >> 10;
+    }
+  for( int j = 0; j < p.outH; j++ )
+    for( int i = 0; i < p.outW; i++ )
+    {
+      const int first = p.tabY[j] & 0xffff, count = p.tabY[j] >> 16;
+      int sum = 0;
+      for( int t = 0; t < count; t++ ) sum += wy[(size_t) t * p.outH + j] * H[(size_t) ( first + t ) * p.outW + i];
+      const int v = std::min( std::max( 0, ( sum + 131072 ) >> 18 ), p.maxVal );
+      if( p.bytesPerSample == 2 ) ( (uint16_t*) dst )[(size_t) j * p.outW + i] = (uint16_t) v; else ( (uint8_t*) dst )[(size_t) j * p.outW + i] = (uint8_t) v;
+    }
 }
 
 // ... and launch_film_grain as a plain loop restating FilmGrainImpl::add_grain_block (FilmGrainImpl.cpp:126-324) row by row: the pre-deblock grain
@@ -1139,6 +1208,17 @@ VVR_API int vvr_xpsnr_blocks( int w, int h, uint32_t block, uint32_t* resolvedBl
   return VVR_OK;
 }
 
+// the taps of one output sample of an axis under vvr_set_output_resampling, as vvr.h defines them (what the tables of k_output_resample hold)
+VVR_API int vvr_resample_taps( int filter, int n, int m, int phase, int i, int32_t* first, int16_t* weights )
+{
+  if( !first || !weights || filter < VVR_RESAMPLE_AREA || filter > VVR_RESAMPLE_CUBIC || !resample_axis_ok( n, m ) || phase < 1 || phase > 2 || i < 0 || i >= m ) return VVR_ERR_PARAMETER;
+  int f = 0;
+  const int count = resample_taps_of( filter, n, m, phase, i, f, weights );
+  if( count <= 0 ) return VVR_ERR_PARAMETER;
+  *first = f;
+  return count;
+}
+
 // XPSNR from the records of an XPSNR request (vvr_xpsnr_submit), the formula as vvr.h gives it, in double, the blocks in ascending order
 VVR_API int vvr_compare_xpsnr( const vvr_frame_xpsnr* f, const vvr_xpsnr_block* blocks, double aPic, double peak, double xpsnr[4] )
 {
@@ -1346,7 +1426,7 @@ VVR_API int vvr_picture_hash( vvr_context* c, int slot, int method, uint8_t* dig
 
 // =====================================================================================================================
 // output queue: the output stage as a pipeline.  A request is ordered behind its picture's `done` event on the context's output stream,
-// runs there (k_film_grain, k_rescale, k_output_frame, k_output_narrow, k_output_rgb or k_output_yuv as the request needs them), leaves through a ring entry (device scratch + pinned
+// runs there (k_film_grain, k_rescale - or, under vvr_set_output_resampling, k_output_resample in its place -, k_output_frame, k_output_narrow, k_output_rgb or k_output_yuv as the request needs them), leaves through a ring entry (device scratch + pinned
 // staging) and is collected with its ticket.  Nothing here calls vvr_sync.  The slot is protected the way an external reader's is
 // (vvr_slot_external_event): the entry's `read` event, recorded behind the last kernel of the request, is registered with the slot, so a
 // picture submitted afterwards that overwrites the slot waits for it on the device - not for the copy to the host.
@@ -1395,7 +1475,7 @@ struct OutEntry {
   int hash = 0, hashNc = 0; size_t planeBytes[3] = { 0, 0, 0 };
   uint8_t* digest = nullptr; uint32_t* mismatch = nullptr; bool verify = false; uint8_t expected[48];
   bool timed2 = false; PendingTiming timing2;      // (k_hash_combine; `timing` is k_hash_rows then)
-  bool timed0 = false; PendingTiming timing0; int rescales = 0;      // (the k_rescale launches ahead of a measure under vvr_set_compare_scaling, and how many)
+  bool timed0 = false; PendingTiming timing0; int rescales = 0;      // (the k_rescale launches ahead of a measure under vvr_set_compare_scaling, or the k_output_resample launches of an output request under vvr_set_output_resampling, and how many)
   // a statistics request: mode + 1 (0: none); STATS_WORDS words at the start of `host`; what vvr_output_wait writes besides them
   int stats = 0, statsW = 0, statsH = 0; vvr_frame_stats* statsOut = nullptr;
   // a comparison request: its number of components (0: none); CMP_OUT_WORDS words per component at the start of `host`, the map's words from
@@ -1415,8 +1495,29 @@ struct OutEntry {
 struct XpsnrAsk { int temporal, filter; uint32_t block; const void* prev[2]; size_t prevStride[2]; vvr_xpsnr_block* blocks; };
 #define CMP_HEAD_WORDS 32      /* 3 x CMP_OUT_WORDS, rounded up: the map starts at a multiple of 128 bytes */
 
+// The tap tables of k_output_resample (vvr_set_output_resampling): built on the host from the integer definition (resample_taps_of), one per
+// ( n, m, phi, filter ), laid out as ResampleParams takes them (vvr_device.h), and kept in device memory - eight of them, the least recently
+// used one replaced.  A request needs at most four (luma and chroma, two axes), so a stream of requests of one geometry uploads nothing.  Every
+// table has device and pinned memory of a fixed size of its own, allocated on first use and kept until vvr_destroy: nothing in the request
+// path frees device memory.  A table is uploaded on the output stream, behind the kernels of the requests in flight that read the one it
+// replaces; `uploaded` is recorded behind the copy, and the pinned image is rewritten only once that has completed.
+// Size: count <= 4 n / m + 2, so the weights of an axis are at most 4 n + 2 m <= 49 152 words of 16 bits, behind m <= 8192 words of 32 bits.
+#define VVR_RESAMPLE_TABLES 8
+#define VVR_RESAMPLE_TABLE_BYTES ( 192 << 10 )
+struct ResampleTable {
+  int n = 0, m = 0, phi = 0, filter = 0, taps = 0; uint64_t used = 0;
+  char* dev = nullptr; char* host = nullptr; hipEvent_t uploaded = nullptr;
+};
+
 static void destroyOutputQueue( vvr_context* c )
 {
+  if( c->resampleTabs )
+    for( int i = 0; i < VVR_RESAMPLE_TABLES; i++ )
+    {
+      ResampleTable& t = c->resampleTabs[i];
+      if( t.dev ) hipFree( t.dev ); if( t.host ) hipHostFree( t.host ); if( t.uploaded ) hipEventDestroy( t.uploaded );
+    }
+  delete[] c->resampleTabs; c->resampleTabs = nullptr;
   if( c->outRing )
     for( int i = 0; i < VVR_OUT_RING; i++ )
     {
@@ -1537,6 +1638,44 @@ hipError_t outOrder( vvr_context* c, const OutEntry* e, int slot, int job, hipEv
   for( hipEvent_t ev : c->slotExt[slot] ) if( rc == hipSuccess && ev != e->read ) rc = hipStreamWaitEvent( c->outQStream, ev, 0 );
   return rc;
 }
+// the tap table of an axis in device memory, uploaded on s if the context does not hold it; mu held
+hipError_t resampleTable( vvr_context* c, hipStream_t s, int filter, int n, int m, int phi, const uint32_t*& tab, int& taps )
+{
+  if( !c->resampleTabs ) c->resampleTabs = new ResampleTable[VVR_RESAMPLE_TABLES];
+  ResampleTable* t = nullptr;
+  for( int i = 0; i < VVR_RESAMPLE_TABLES; i++ )
+  {
+    ResampleTable& q = c->resampleTabs[i];
+    if( q.n == n && q.m == m && q.phi == phi && q.filter == filter ) { q.used = ++c->resampleUses; tab = (const uint32_t*) q.dev; taps = q.taps; return hipSuccess; }
+    if( !t || q.used < t->used ) t = &q;
+  }
+  t->n = 0;      // (not a table until it has been enqueued)
+  hipError_t rc = hipSuccess;
+  if( !t->dev ) rc = hipMalloc( (void**) &t->dev, VVR_RESAMPLE_TABLE_BYTES );
+  if( rc == hipSuccess && !t->host ) rc = hipHostMalloc( (void**) &t->host, VVR_RESAMPLE_TABLE_BYTES, hipHostMallocDefault );
+  if( rc == hipSuccess && !t->uploaded ) rc = hipEventCreateWithFlags( &t->uploaded, hipEventDisableTiming );
+  else if( rc == hipSuccess ) rc = hipEventSynchronize( t->uploaded );
+  if( rc != hipSuccess ) return rc;
+  int16_t w[VVR_RESAMPLE_MAX_TAPS]; int first = 0, most = 0;
+  uint32_t* words = (uint32_t*) t->host;
+  for( int i = 0; i < m; i++ )
+  {
+    const int count = resample_taps_of( filter, n, m, phi, i, first, w );
+    if( count <= 0 || first < 0 || first + count > n ) return hipErrorInvalidValue;      // (every tap inside the plane: what the kernel's loads rely on)
+    words[i] = (uint32_t) first | (uint32_t) count << 16; most = std::max( most, count );
+  }
+  const size_t bytes = (size_t) m * 4 + (size_t) most * m * 2;
+  if( bytes > VVR_RESAMPLE_TABLE_BYTES ) return hipErrorInvalidValue;
+  int16_t* wt = (int16_t*) ( words + m );
+  memset( wt, 0, (size_t) most * m * 2 );
+  for( int i = 0; i < m; i++ ) { const int count = resample_taps_of( filter, n, m, phi, i, first, w ); for( int k = 0; k < count; k++ ) wt[(size_t) k * m + i] = w[k]; }
+  rc = hipMemcpyAsync( t->dev, t->host, bytes, hipMemcpyHostToDevice, s );
+  if( rc == hipSuccess ) rc = hipEventRecord( t->uploaded, s );
+  if( rc != hipSuccess ) return rc;
+  t->n = n; t->m = m; t->phi = phi; t->filter = filter; t->taps = most; t->used = ++c->resampleUses;
+  tab = (const uint32_t*) t->dev; taps = most;
+  return hipSuccess;
+}
 }   // namespace
 
 extern "C" {
@@ -1598,13 +1737,18 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     if( bd != 8 && bd != 10 ) return outRefuse( c, "film grain needs a bit depth of 8 or 10 (FilmGrainImpl::set_depth)" );
     if( w <= 128 ) return outRefuse( c, "film grain needs a frame wider than 128 samples (FilmGrainImpl::add_grain_block)" );
   }
+  // the filter out_w / out_h resample with: the one that is set now, read once (0: the reference's DCTIF, k_rescale, and its range)
+  int resample = 0;
+  if( scaled ) { std::lock_guard<std::mutex> lk( c->mu ); resample = c->outResample; }
   int pw[3], ph[3], ow[3], oh[3], outRows[3]; bool resc[3] = { false, false, false }, anyResc = false;
   size_t rowBytes[3] = { 0, 0, 0 };
   for( int k = 0; k < nc; k++ )
   {
     const int s = k ? 1 : 0;
     pw[k] = w >> s; ph[k] = h >> s; ow[k] = scaled ? rq->out_w >> s : pw[k]; oh[k] = scaled ? rq->out_h >> s : ph[k];
-    if( scaled && ( ow[k] <= 0 || oh[k] <= 0 || ow[k] > 8192 || oh[k] > 8192 || pw[k] > 8 * ow[k] || ph[k] > 8 * oh[k] || ow[k] > 8 * pw[k] || oh[k] > 8 * ph[k] ) )
+    if( scaled && resample && ( ow[k] <= 0 || oh[k] <= 0 || !resample_axis_ok( pw[k], ow[k] ) || !resample_axis_ok( ph[k], oh[k] ) ) )
+      return outRefuse( c, "under vvr_set_output_resampling window and output sides must be 1..8192, the output's within 1/64 .. 8 times the window's in every plane" );
+    if( scaled && !resample && ( ow[k] <= 0 || oh[k] <= 0 || ow[k] > 8192 || oh[k] > 8192 || pw[k] > 8 * ow[k] || ph[k] > 8 * oh[k] || ow[k] > 8 * pw[k] || oh[k] > 8 * ph[k] ) )
       return outRefuse( c, "output sides must be 1..8192 and within 1/8 .. 8 times the window's" );
     resc[k] = ow[k] != pw[k] || oh[k] != ph[k]; anyResc |= resc[k];
     if( packed && ( ow[k] & 3 ) ) return outRefuse( c, "packed 10-bit output needs plane widths that are multiples of 4 (four samples in five bytes)" );
@@ -1693,6 +1837,10 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     if( grainTmp ) { offA[k] = tmpBytes; tmpBytes += outRegion( (size_t) pw[k] * ph[k] * 2 ); }
     if( resc[k] && viaTmp ) { offB[k] = tmpBytes; tmpBytes += outRegion( (size_t) ow[k] * oh[k] * 2 ); }
   }
+  // (... and the horizontal results of a plane that k_output_resample takes in two launches: one region, the planes use it in turn on the stream)
+  size_t offH = tmpBytes, bytesH = 0;
+  for( int k = 0; k < nc; k++ ) if( resample && resc[k] && resample_two_launches( ph[k], oh[k] ) ) bytesH = std::max( bytesH, (size_t) ph[k] * ow[k] * sizeof( int ) );
+  tmpBytes += alignUp( bytesH, 256 );
   const int nbx = ( w + 15 ) / 16, nby = ( h + 15 ) / 16;
   const size_t wordsBytes = grain ? (size_t) nbx * nby * sizeof( uint32_t ) : 0, wordsOff = tmpBytes, hostWordsOff = direct ? 0 : total;
   tmpBytes += alignUp( wordsBytes, 256 );
@@ -1733,9 +1881,35 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     for( int k = 0; k < nc; k++ )
       if( grainTmp ) { cur[k].p = (const pel_t*) ( e->tmp + offA[k] ); cur[k].stride = pw[k]; } else cur[k].inOut = true;
   }
+  if( resample && anyResc )
+  {
+    // vvr_set_output_resampling: k_output_resample where k_rescale stands below, with the same two store forms; the tap tables of the axes
+    // from the context's cache (phi: 2 for luma and for chroma whose collocated bit is 0, 1 for chroma whose bit is 1)
+    double bytes = 0; int launches = 0;
+    ResampleParams rp[3];
+    for( int k = 0; k < nc; k++ )
+    {
+      if( !resc[k] ) continue;
+      ResampleParams& p = rp[k];
+      p.src = cur[k].p; p.stride = cur[k].stride; p.w = pw[k]; p.h = ph[k]; p.outW = ow[k]; p.outH = oh[k];
+      p.maxVal = ( 1 << bd ) - 1; p.bytesPerSample = viaTmp ? 2 : bps;
+      OQCHK( resampleTable( c, s, resample, pw[k], ow[k], k && ( rq->collocated & 1 ) ? 1 : 2, p.tabX, p.tapsX ) );
+      OQCHK( resampleTable( c, s, resample, ph[k], oh[k], k && ( rq->collocated & 2 ) ? 1 : 2, p.tabY, p.tapsY ) );
+      bytes += (double) pw[k] * ph[k] * 2 + (double) ow[k] * oh[k] * p.bytesPerSample; launches++;      // (a request's planes count one launch each, in one or two parts)
+    }
+    outTimeBegin( c, s, e->timed0, e->timing0, K_OUTPUT_RESAMPLE, bytes );
+    for( int k = 0; k < nc; k++ )
+    {
+      if( !resc[k] ) continue;
+      launch_output_resample( s, rp[k], viaTmp ? e->tmp + offB[k] : e->dev + e->off[k], e->tmp + offH );
+      if( viaTmp ) { cur[k].p = (const pel_t*) ( e->tmp + offB[k] ); cur[k].stride = ow[k]; } else cur[k].inOut = true;
+    }
+    if( e->timed0 ) hipEventRecord( e->timing0.b, s );
+    e->rescales = launches;
+  }
   for( int k = 0; k < nc; k++ )
   {
-    if( !resc[k] ) continue;
+    if( !resc[k] || resample ) continue;
     // (as vvr_read_output_scaled: the component's subsampling, luma always collocated)
     const bool luma = k == 0;
     const int cs = luma ? 0 : 1, colX = luma ? 1 : rq->collocated & 1, colY = luma ? 1 : ( rq->collocated >> 1 ) & 1, fracShift = luma ? 4 : 5;
@@ -2347,7 +2521,7 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   if( rc == VVR_ERR_DEVICE && e->rc == VVR_OK ) c->setError( "vvr_output_wait: hipEventSynchronize failed" );
   if( rc == VVR_OK ) rc = outJobStatus( c, e->job, lk, true );
   outTimeEnd( c, e->timed, e->timing, e->msScales ? e->msScales : 1 );        // (K_OUTPUT_FRAME or K_OUTPUT_RGB; K_HASH_ROWS; K_OUTPUT_MSSSIM, a launch per scale ...
-  outTimeEnd( c, e->timed0, e->timing0, e->rescales );      // (K_COMPARE_RESCALE)
+  outTimeEnd( c, e->timed0, e->timing0, e->rescales );      // (K_COMPARE_RESCALE; K_OUTPUT_RESAMPLE)
   outTimeEnd( c, e->timed2, e->timing2 );      // ... and K_HASH_COMBINE; K_OUTPUT_STATS and K_OUTPUT_STATS_SUM; K_OUTPUT_COMPARE and K_OUTPUT_COMPARE_SUM; K_OUTPUT_SSIM and K_OUTPUT_SSIM_SUM; K_OUTPUT_MSSSIM_SUM)
   // the slot's reader is gone (the event is complete: a picture that overwrote the slot meanwhile, or a vvr_sync, has dropped it already)
   if( e->slot >= 0 ) { auto& v = c->slotExt[e->slot]; v.erase( std::remove( v.begin(), v.end(), e->read ), v.end() ); }
