@@ -823,6 +823,45 @@ VVR_API int          vvr_set_output_lut3d(vvr_context* ctx, int n, const uint16_
 VVR_API int          vvr_output_lut3d_preset(uint16_t* nodes, int n, int transfer_characteristics, int colour_primaries, int target,
                                              double src_peak_nits, double dst_peak_nits);
 VVR_API int          vvr_output_submit(vvr_context* ctx, const vvr_output_request* req);
+/* Many regions of one picture as a batch in one request: the tiles of a frame for a detector, fixed-size crops around detections, the crops of
+ * test-time augmentation.  One request, one ticket, one ring entry, and one launch per stage whatever `count` is - the region is the third
+ * dimension of the grids of k_rescale, k_output_resample, k_output_resample_h and k_output_rgb.
+ *   definition   region i receives exactly the bytes that vvr_output_submit stores for the same `req` with x, y = origin[2 i], origin[2 i + 1]
+ *            and with dst[k] advanced by i * batch_stride_bytes[k], under the context state in force when the call is accepted: the colour
+ *            description, transform, 3-D LUT, normalisation and resampling filter.  No other byte of the destination changes.
+ *   req      w, h, out_w, out_h, collocated, format, job, slot and blocking mean what they mean for vvr_output_submit; x and y must be 0.  All
+ *            regions have the window's size and the output's size: tap tables, coefficients and tile decomposition are the request's, shared
+ *            by the regions, which differ in a source origin and a destination offset only.
+ *   regions  may overlap in the source, and two may be equal.  The taps see the region's window as the plane, as a single request does:
+ *            samples beyond the window are dropped or clamped exactly as vvr_output_submit does it, even where the picture has samples there.
+ *   origin   count pairs x, y in luma samples (even in 4:2:0); read before the call returns.
+ *   formats  the ten R'G'B' formats: VVR_OUT_RGB8, _RGB16, _RGBF16, _RGBF32, _RGBA8, _BGRA8, _RGB24, _BGR24, _RGB10A2, _RGBA16F.
+ *   resampling   none (out_w = out_h = 0 or the window's size), the reference's DCTIF (no filter set) and the three filters of
+ *            vvr_set_output_resampling, each in its range.
+ *   ticket   one, from the ticket space of vvr_output_submit: vvr_output_test, _wait, _stream_wait and vvr_sync treat it like any other.
+ *   dst      pageable host memory, memory of vvr_host_alloc or device memory, by vvr_output_submit's rules applied to the whole batch: plane k
+ *            of the batch is the span dst[k] .. dst[k] + ( count - 1 ) * batch_stride_bytes[k] + the plane's extent, and every used plane's
+ *            span must lie wholly inside one kind of memory (a span partly inside a device range, and device spans mixed with host spans, are
+ *            refused).  On the device k_output_rgb stores a plane of every region itself, with no copy, when the plane's rows are back to back,
+ *            dst[k] is aligned to 32 bytes and batch_stride_bytes[k] is a multiple of 32 - a contiguous ( N, 3, H, W ) or ( N, H, W, C ) tensor
+ *            at the usual sizes; any other layout goes through the entry's scratch and device-to-device copies.
+ *   refused  VVR_ERR_PARAMETER with a text that names vvr_output_submit_batch, before a ring entry is taken: a struct_size that is not the size of
+ *            its struct (either one); count 0 or above VVR_OUT_BATCH_MAX; origin NULL; req->x | req->y non-zero; an origin whose window leaves the
+ *            picture or is odd in 4:2:0 (the text names the region's index); grain (the seed chain is defined per frame); a format outside the
+ *            ten; a batch_stride_bytes[k] of a used plane below that plane's extent ( rows - 1 ) * dst_stride_bytes[k] + row bytes (regions
+ *            would overlap in the destination); a batch whose device buffers in the entry - outputs not stored directly, resampled 4:2:0 frames,
+ *            horizontal results of the two-launch form - would exceed 512 MiB in total (a stated limit, named in the text); everything
+ *            vvr_output_submit refuses for the same req, with its text behind the new name.  VVR_ERR_BUSY and VVR_NOT_READY as vvr_output_submit.
+ *   not offered   regions of different sizes in one request (submit one batch per size); the Y'CbCr and planar formats; grain; more than 256
+ *            regions; batches for the measures, statistics and hashes. */
+#define VVR_OUT_BATCH_MAX 256
+typedef struct vvr_output_batch {
+  uint32_t       struct_size;            /* sizeof( vvr_output_batch ) */
+  uint32_t       count;                  /* 1 .. VVR_OUT_BATCH_MAX */
+  const int32_t* origin;                 /* count pairs x, y: luma samples, even in 4:2:0; read before the call returns */
+  size_t         batch_stride_bytes[3];  /* region i of plane k starts at (char*) req->dst[k] + i * batch_stride_bytes[k] */
+} vvr_output_batch;                      /* 40 bytes */
+VVR_API int          vvr_output_submit_batch(vvr_context* ctx, const vvr_output_request* req, const vvr_output_batch* batch);
 VVR_API int          vvr_output_test(vvr_context* ctx, int ticket);
 VVR_API int          vvr_output_wait(vvr_context* ctx, int ticket);
 /* Destinations of the output queue in device memory, for a consumer on the same GPU (an encoder, a torch model, the sender of a collective).

@@ -47,7 +47,7 @@ def table(a):
             if m and name:
                 kernels[name][key] = int(m.group(1))
     one = {k: v for k, v in kernels.items() if "k_output_resample" in k or re.match(r"_Z9k_rescaleILi\d", k)}
-    assert len(one) == 5, list(one)      # (k_output_resample<false>, k_output_resample_h, k_output_resample<true>; k_rescale<8>, <4>)
+    assert len(one) == 10, list(one)      # (k_output_resample<false>, k_output_resample_h, k_output_resample<true>; k_rescale<8>, <4> - each for the single request and with the regions of a batch)
     with open(a.table, "w") as f:
         json.dump({"kernels": one}, f, indent=1)
     print(json.dumps(one, indent=1))

@@ -110,6 +110,7 @@ def lib():
         L.vvr_slot_external_event.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.vvr_output_submit.restype = C.c_int
         L.vvr_output_submit.argtypes = [C.c_void_p, C.c_void_p]
+        abi.bind_output_batch(L)
         L.vvr_output_test.restype = C.c_int
         L.vvr_output_test.argtypes = [C.c_void_p, C.c_int]
         L.vvr_output_wait.restype = C.c_int
@@ -157,7 +158,7 @@ EXPORTED_SYMBOLS = ["vvr_version", "vvr_create", "vvr_destroy", "vvr_submit", "v
                     "vvr_free_prepared", "vvr_job_stream", "vvr_last_error", "vvr_enable_stats", "vvr_get_stats", "vvr_resolve_tr_type", "vvr_abi_sizeof",
                     "vvr_inputs_done", "vvr_measure_copy_bandwidth", "vvr_host_alloc", "vvr_host_free",
                     "vvr_stream_wait_job", "vvr_stream_wait_slot", "vvr_slot_external_event", "vvr_slot_picture_size", "vvr_read_picture",
-                    "vvr_output_submit", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit", "vvr_stats_submit", "vvr_light_level",
+                    "vvr_output_submit", "vvr_output_submit_batch", "vvr_output_test", "vvr_output_wait", "vvr_output_stream_wait", "vvr_hash_submit", "vvr_stats_submit", "vvr_light_level",
                     "vvr_compare_submit", "vvr_compare_psnr", "vvr_ssim_submit", "vvr_compare_ssim", "vvr_msssim_submit", "vvr_compare_msssim",
                     "vvr_xpsnr_submit", "vvr_xpsnr_blocks", "vvr_compare_xpsnr",
                     "vvr_device_alloc", "vvr_device_free", "vvr_device_register", "vvr_device_unregister"]
@@ -642,6 +643,56 @@ class Reconstructor:
         if not blocking and ticket == abi.VVR_NOT_READY:
             return None
         self._out[ticket] = planes if whole is None else whole
+        self._reg[ticket] = registered
+        return ticket
+
+    def output_submit_batch(self, slot, origins, window_size, fmt, job=None, size=None, collocated=(True, False), pinned=False, blocking=True, into=None):
+        """vvr_output_submit_batch: the regions of `slot` of window_size = (w, h) at `origins` ((x, y) pairs, up to 256) as one request, one ticket
+        and one launch per stage -> ticket, or None when blocking=False and the job has not been handed to the device yet.  Region i gets exactly
+        what output_submit(slot, window=(x_i, y_i, w, h), fmt=fmt, size=size, collocated=collocated) gives.  fmt: one of abi.OUT_BATCH_FORMATS,
+        the ten R'G'B' formats.  output_wait returns the regions stacked on a leading axis: (N, 3, H, W) for the planar formats, (N, H, W, C)
+        for the interleaved ones, (N, H, W) words for "rgb10a2" - a numpy array (pinned: in memory of the context that the device writes
+        directly), or the tensor given as
+        into: a contiguous torch tensor of that shape on the context's device (rgb10a2: int32), written by the device and registered with the
+        context for the life of the request, as output_submit does it; it must be idle now and stay untouched until the request has completed."""
+        origins = [tuple(int(v) for v in o) for o in origins]
+        n, (w, h) = len(origins), window_size
+        shapes, dt = abi.output_plane_shapes((0, 0, w, h), fmt, size, 3 if self.chroma_format else 1)
+        if fmt not in abi.OUT_BATCH_FORMATS:
+            raise ValueError("output_submit_batch: fmt is one of %r" % (abi.OUT_BATCH_FORMATS,))
+        rows, per_row = shapes[0]
+        inter = abi.OUT_INTERLEAVED.get(fmt)
+        shape = (n, 3, rows, per_row) if inter is None else (n, rows, per_row) if fmt == "rgb10a2" else (n, rows, per_row // inter, inter)
+        item = np.dtype(dt).itemsize
+        plane_bytes, region_bytes = rows * per_row * item, len(shapes) * rows * per_row * item
+        registered = []
+        if into is not None:
+            if not hasattr(into, "is_cuda") or not into.is_cuda or into.device.index != self.cfg.device or tuple(into.shape) != shape or into.element_size() != item or not into.is_contiguous():
+                raise ValueError("output_submit_batch: into is a contiguous tensor on the context's device of shape %r and %d-byte elements" % (shape, item))
+            out, base = into, into.data_ptr()
+            if n and not any(a <= base and base + n * region_bytes <= a + m for a, m in self._dev):
+                self._check(self.L.vvr_device_register(self.ctx, base, n * region_bytes))
+                registered.append(base)
+        else:
+            out = self.host_array(max(1, n * region_bytes // item), dt)[:n * region_bytes // item].reshape(shape) if pinned else np.zeros(shape, dt)
+            base = out.ctypes.data
+        req = abi.OutputRequest()
+        req.struct_size, req.slot, req.job = C.sizeof(abi.OutputRequest), slot, -1 if job is None else job
+        req.x, req.y, req.w, req.h = 0, 0, w, h
+        req.out_w, req.out_h = size or (0, 0)
+        req.collocated = int(bool(collocated[0])) | int(bool(collocated[1])) << 1
+        req.format, req.grain, req.blocking = abi.OUT_FORMATS[fmt], 0, 1 if blocking else 0
+        for k in range(len(shapes)):
+            req.dst[k], req.dst_stride_bytes[k] = base + k * plane_bytes, per_row * item
+        batch, keep = abi.output_batch(origins, [region_bytes] * len(shapes))
+        ticket = self.L.vvr_output_submit_batch(self.ctx, C.byref(req), C.byref(batch))
+        if ticket < 0 or ticket == abi.VVR_NOT_READY:
+            for ptr in registered:
+                self.L.vvr_device_unregister(self.ctx, ptr)
+        self._check(ticket)
+        if not blocking and ticket == abi.VVR_NOT_READY:
+            return None
+        self._out[ticket] = out
         self._reg[ticket] = registered
         return ticket
 

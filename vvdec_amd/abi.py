@@ -239,6 +239,34 @@ def output_request(slot, job, window, fmt, size, collocated, grain, blocking, pl
     return r
 
 
+OUT_BATCH_MAX = 256
+OUT_BATCH_FORMATS = ("rgb8", "rgb16", "rgbf16", "rgbf32", "rgba8", "bgra8", "rgb24", "bgr24", "rgb10a2", "rgba16f")
+
+
+class OutputBatch(C.Structure):
+    """vvr_output_batch: the regions of a batch request (vvr_output_submit_batch, vvr.h)"""
+    _fields_ = [("struct_size", u32), ("count", u32), ("origin", C.POINTER(i32)), ("batch_stride_bytes", C.c_size_t * 3)]
+
+
+def bind_output_batch(L):
+    """the ctypes signature of vvr_output_submit_batch on a loaded library (the product's, or the host build of the tests)"""
+    L.vvr_output_submit_batch.restype = C.c_int
+    L.vvr_output_submit_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
+
+
+def output_batch(origins, batch_stride_bytes):
+    """an OutputBatch of the regions at `origins` ((x, y) pairs) whose planes lie batch_stride_bytes[k] apart -> (the struct, the array it
+    points to: keep it until the call has returned)"""
+    flat = [int(v) for o in origins for v in o]
+    arr = (i32 * max(1, len(flat)))(*flat)
+    b = OutputBatch()
+    b.struct_size, b.count, b.origin = C.sizeof(OutputBatch), len(flat) // 2, C.cast(arr, C.POINTER(i32))
+    for k, v in enumerate(batch_stride_bytes):
+        b.batch_stride_bytes[k] = int(v)
+    return b, arr
+
+
 def output_plane_shapes(window, fmt, size, ncomp):
     """(rows, bytes or samples per row) of every plane a request produces, and the dtype: packed10 rows are w / 4 * 5 bytes; the semi-planar
     formats have two planes, luma and the interleaved CbCr rows of 2 * (w >> 1) samples (nv12: uint8, p010: uint16); the RGB formats three

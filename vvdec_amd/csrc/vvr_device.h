@@ -232,7 +232,17 @@ struct RescaleParams
   int stepX, stepY, addX, addY, shiftX, shiftY;
   int luma, maxVal, bytesPerSample;
 };
-void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst );
+// The regions of a batch (vvr_output_submit_batch): blockIdx.z of k_rescale, k_output_resample and k_output_resample_h.  Region z reads the plane
+// at p.src + srcOff[3 * z + comp] samples (srcOff: a table in device memory, three words per region - the region's origin in the three planes;
+// NULL: p.src), stores its rows at dst + z * dstStep bytes and keeps the horizontal results of the two-launch form at scratch + z * hStep words.
+// The default is the single request: one region, no table, no steps.
+struct PlaneRegions
+{
+  int count = 1, comp = 0;
+  const uint32_t* srcOff = nullptr;
+  size_t dstStep = 0, hStep = 0;
+};
+void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst, const PlaneRegions& rg = PlaneRegions() );
 // antialiased resampling (vvr_set_output_resampling, the definition: vvr.h; k_output_resample): a window of w x h samples to outW x outH, stored
 // like launch_rescale's.  tabX / tabY: the tap table of an axis in device memory, built on the host from the integer definition - m words
 // first | count << 16, one per output sample, then tapsX (tapsY) x m int16 weights tap-major: weight t of output sample i at [ t * m + i ],
@@ -246,7 +256,7 @@ struct ResampleParams
 // a plane that shrinks by more than 4 vertically takes two launches - k_output_resample_h into `scratch`, h x outW 32-bit words, then the vertical
 // pass over those (vvr_kernels.hip) - every other plane one, and no scratch
 static inline bool resample_two_launches( int h, int outH ) { return h > 4 * outH; }
-void launch_output_resample( hipStream_t s, const ResampleParams& p, void* dst, void* scratch );
+void launch_output_resample( hipStream_t s, const ResampleParams& p, void* dst, void* scratch, const PlaneRegions& rg = PlaneRegions() );
 // film grain synthesis at the output (FilmGrainImpl::add_grain_block, FilmGrainImpl.cpp:126-324) over a window of every component, packed like
 // launch_output_window into dst + dstOff[c].  words: one random word per 16x16 luma block of the window, nbx per band (vvr_output.inc, grain_words);
 // bank: the device copy of the context's vvr_film_grain_bank
@@ -306,7 +316,15 @@ struct OutputRgbParams
   // the kernel takes as ( x * lutWiden ) >> 39 with lutWiden = 2^39 / M + 1 (exact for x < 2^26: the error x / 2^39 stays below 1 / M)
   const uint16_t* lut; int lutN, lutShift; uint32_t lutWiden;
 };
-void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst );
+// ... and the regions of a batch for k_output_rgb (blockIdx.z): region z reads plane c at p.src[c] + srcOff[3 * z + c] (the table of PlaneRegions;
+// NULL: none) + z * srcStep[c] samples (the resampled frames of the regions, back to back) and stores plane c at its place + z * dstStep[c] bytes.
+struct RgbRegions
+{
+  int count = 1;
+  const uint32_t* srcOff = nullptr;
+  size_t srcStep[3] = { 0, 0, 0 }, dstStep[3] = { 0, 0, 0 };
+};
+void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst, const RgbRegions& rg = RgbRegions() );
 // a frame of the output queue as Y'CbCr at 4:4:4 or 4:2:2 (VVR_OUT_YUV444P8 ... VVR_OUT_Y410, the definition: vvr.h): one 4:2:0 frame of w x h luma
 // samples (even), the luma as it is, the chroma brought to the luma grid as launch_output_rgb brings it there (4:4:4: bits 0 and 1 of collocated)
 // or to every luma row of its own columns (4:2:2: the vertical 4-tap alone, bit 1 of collocated).  Three planes or one leave, rows back to back,

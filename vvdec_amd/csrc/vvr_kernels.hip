@@ -4799,9 +4799,17 @@ void launch_output_window( hipStream_t s, const pel_t* src, int stride, int w, i
 #define RS_TW   64
 #define RS_ROWS 128      // LDS budget: 128 rows x 64 int32 sums = 32 KiB per workgroup
 #define RS_SEG  576      // source samples a row segment of 64 output columns can span: 63 * 8 + 1 + 8 at 8x down
-template<int TAPS>
-__global__ __launch_bounds__( 256 ) void k_rescale( RescaleParams p, int tileH, int rowsCap, uint8_t* __restrict__ dst )
+// a word of the region table of a batch (PlaneRegions, RgbRegions: vvr_device.h), uniform across the workgroup: kept in a scalar register
+__device__ __forceinline__ size_t region_offset( const uint32_t* __restrict__ tab, unsigned at ) { return tab ? (size_t) (uint32_t) __builtin_amdgcn_readfirstlane( (int) tab[at] ) : 0; }
+// BATCH (k_rescale, k_output_resample, k_output_resample_h): the regions of vvr_output_submit_batch as blockIdx.z - the region's origin in the
+// plane from the table, its rows (and its horizontal results) a step apart.  The single request runs the instantiation without it, which
+// does not look at `rg`: the parent's kernel, instruction for instruction (the one with it measured 2 to 3 % slower at 4K -> 1080p:
+// profiles/output_batch_4k.txt).
+template<int TAPS, bool BATCH>
+__global__ __launch_bounds__( 256 ) void k_rescale( RescaleParams p, int tileH, int rowsCap, uint8_t* __restrict__ dst, PlaneRegions rg )
 {
+  const pel_t* __restrict__ src = p.src;
+  if( BATCH ) { src += region_offset( rg.srcOff, 3 * blockIdx.z + rg.comp ); dst += blockIdx.z * rg.dstStep; }
   extern __shared__ int rs_sum[];      // [rowsCap][RS_TW]
   __shared__ pel_t rs_seg[4][RS_SEG];
   __shared__ int16_t rs_flt[128];      // the filter table (16 x 8 or 32 x 4): the vertical pass reads a row's coefficients from here, not through a global load per row
@@ -4826,7 +4834,7 @@ __global__ __launch_bounds__( 256 ) void k_rescale( RescaleParams p, int tileH, 
   pel_t* seg = rs_seg[wave];
   for( int r = rowLo + wave; r <= rowHi; r += 4 )
   {
-    const pel_t* __restrict__ row = p.src + (size_t) r * p.stride;
+    const pel_t* __restrict__ row = src + (size_t) r * p.stride;
     for( int t = lane; t < segLen; t += 64 ) seg[t] = row[clip3( 0, p.w - 1, xLo + t )];
     __builtin_amdgcn_wave_barrier();
     int sum = 0;
@@ -4851,7 +4859,7 @@ __global__ __launch_bounds__( 256 ) void k_rescale( RescaleParams p, int tileH, 
     }
   }
 }
-void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst )
+void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst, const PlaneRegions& rg )
 {
   const int taps = p.luma ? 8 : 4, fracShift = p.luma ? 4 : 5;
   // source rows of a tile of t output rows <= ceil( ( t - 1 ) * stepY / 2^( shiftY + fracShift ) ) + taps (stepY / 2^( shiftY + fracShift ): source rows per output row)
@@ -4860,12 +4868,13 @@ void launch_rescale( hipStream_t s, const RescaleParams& p, void* dst )
   while( tileH > 1 && rows( tileH ) > RS_ROWS ) tileH--;
   // (a small plane - the chroma of 1080p to 4K - in shorter tiles, so that every compute unit gets several workgroups)
   const int tilesX = ( p.outW + RS_TW - 1 ) / RS_TW;
-  while( tileH > 16 && (int64_t) tilesX * ( ( p.outH + tileH - 1 ) / tileH ) < 1000 ) tileH >>= 1;
+  while( tileH > 16 && (int64_t) tilesX * ( ( p.outH + tileH - 1 ) / tileH ) * rg.count < 1000 ) tileH >>= 1;      // (a batch: the workgroups of all its regions)
   const int rowsCap = std::min( rows( tileH ), p.h );
-  const dim3 grid( tilesX, ( p.outH + tileH - 1 ) / tileH );
+  const dim3 grid( tilesX, ( p.outH + tileH - 1 ) / tileH, rg.count );
   const size_t lds = (size_t) rowsCap * RS_TW * sizeof( int );
-  if( p.luma ) hipLaunchKernelGGL( k_rescale<8>, grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst );
-  else         hipLaunchKernelGGL( k_rescale<4>, grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst );
+  const bool batch = rg.srcOff || rg.count > 1;
+  if( p.luma ) { if( batch ) hipLaunchKernelGGL( ( k_rescale<8, true> ), grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst, rg ); else hipLaunchKernelGGL( ( k_rescale<8, false> ), grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst, rg ); }
+  else         { if( batch ) hipLaunchKernelGGL( ( k_rescale<4, true> ), grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst, rg ); else hipLaunchKernelGGL( ( k_rescale<4, false> ), grid, dim3( 256 ), lds, s, p, tileH, rowsCap, (uint8_t*) dst, rg ); }
 }
 
 // k_output_resample — antialiased resampling at the output (vvr_set_output_resampling, the definition: vvr.h): area, triangle or Keys cubic with
@@ -4901,9 +4910,16 @@ __device__ __forceinline__ int rsm_row_sum( const pel_t* __restrict__ row, const
   return sum;
 }
 // FROM_H: the horizontal results come from the plane k_output_resample_h has stored (hsrc: h rows of outW words) instead of being computed here
-template<bool FROM_H>
-__global__ __launch_bounds__( 256 ) void k_output_resample( ResampleParams p, int tileH, const int* __restrict__ hsrc, uint8_t* __restrict__ dst )
+template<bool FROM_H, bool BATCH>
+__global__ __launch_bounds__( 256 ) void k_output_resample( ResampleParams p, int tileH, const int* __restrict__ hsrc, uint8_t* __restrict__ dst, PlaneRegions rg )
 {
+  // the region of a batch: its origin in the plane or its plane of horizontal results, its rows in dst
+  const pel_t* __restrict__ src = p.src;
+  if( BATCH )
+  {
+    if( FROM_H ) hsrc += blockIdx.z * rg.hStep; else src += region_offset( rg.srcOff, 3 * blockIdx.z + rg.comp );
+    dst += blockIdx.z * rg.dstStep;
+  }
   __shared__ int rsm_h[RSM_ROWS * RSM_TW];
   __shared__ pel_t rsm_seg[FROM_H ? 1 : 4][FROM_H ? 1 : RSM_SEG];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -4930,7 +4946,7 @@ __global__ __launch_bounds__( 256 ) void k_output_resample( ResampleParams p, in
     for( int r = c0r + wave; r <= c1r; r += 4 )
     {
       if( FROM_H ) rsm_h[( r - c0r ) * RSM_TW + lane] = hsrc[(size_t) r * p.outW + i];
-      else rsm_h[( r - c0r ) * RSM_TW + lane] = ( rsm_row_sum( p.src + (size_t) r * p.stride, wx, rsm_seg[FROM_H ? 0 : wave], lane, i, p.outW, fx, cx, xLo, xHi ) + 512 ) >> 10;
+      else rsm_h[( r - c0r ) * RSM_TW + lane] = ( rsm_row_sum( src + (size_t) r * p.stride, wx, rsm_seg[FROM_H ? 0 : wave], lane, i, p.outW, fx, cx, xLo, xHi ) + 512 ) >> 10;
     }
     __syncthreads();
 #pragma unroll
@@ -4957,8 +4973,11 @@ __global__ __launch_bounds__( 256 ) void k_output_resample( ResampleParams p, in
 // a tile of the one-launch form reads many source rows for few output rows, there are few tiles, and neighbouring tiles compute the same rows
 // again.  A wavefront per source row and 64 output columns - thousands of them at any size - stores the rounded sums as 32-bit words, rows of outW
 // back to back, into the request's scratch; k_output_resample<true> runs the vertical pass over that plane.
-__global__ __launch_bounds__( 256 ) void k_output_resample_h( ResampleParams p, int* __restrict__ hdst )
+template<bool BATCH>
+__global__ __launch_bounds__( 256 ) void k_output_resample_h( ResampleParams p, int* __restrict__ hdst, PlaneRegions rg )
 {
+  const pel_t* __restrict__ src = p.src;
+  if( BATCH ) { src += region_offset( rg.srcOff, 3 * blockIdx.z + rg.comp ); hdst += blockIdx.z * rg.hStep; }      // (the region of a batch, as k_output_resample takes it)
   __shared__ pel_t rsm_seg[4][RSM_SEG];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i0 = blockIdx.x * RSM_TW, iOut = i0 + lane, iLast = min( i0 + RSM_TW, p.outW ) - 1, i = min( iOut, iLast );
@@ -4967,22 +4986,26 @@ __global__ __launch_bounds__( 256 ) void k_output_resample_h( ResampleParams p, 
   const int16_t* __restrict__ wx = (const int16_t*) ( p.tabX + p.outW );
   const uint32_t tx0 = p.tabX[i0], tx1 = p.tabX[iLast], tx = p.tabX[i];
   const int xLo = tx0 & 0xffff, xHi = min( (int) ( ( tx1 & 0xffff ) + ( tx1 >> 16 ) ), p.w ) - 1;
-  const int sum = rsm_row_sum( p.src + (size_t) r * p.stride, wx, rsm_seg[wave], lane, i, p.outW, tx & 0xffff, tx >> 16, xLo, xHi );
+  const int sum = rsm_row_sum( src + (size_t) r * p.stride, wx, rsm_seg[wave], lane, i, p.outW, tx & 0xffff, tx >> 16, xLo, xHi );
   if( iOut < p.outW ) hdst[(size_t) r * p.outW + iOut] = ( sum + 512 ) >> 10;
 }
-void launch_output_resample( hipStream_t s, const ResampleParams& p, void* dst, void* scratch )
+void launch_output_resample( hipStream_t s, const ResampleParams& p, void* dst, void* scratch, const PlaneRegions& rg )
 {
   // (a small plane - a model's 224 x 224 - in shorter tiles, so that more compute units get a workgroup)
   const int tilesX = ( p.outW + RSM_TW - 1 ) / RSM_TW;
   int tileH = 4 * RSM_MAXQ;
-  while( tileH > 4 && (int64_t) tilesX * ( ( p.outH + tileH - 1 ) / tileH ) < 512 ) tileH >>= 1;
-  const dim3 grid( tilesX, ( p.outH + tileH - 1 ) / tileH );
+  while( tileH > 4 && (int64_t) tilesX * ( ( p.outH + tileH - 1 ) / tileH ) * rg.count < 512 ) tileH >>= 1;      // (a batch: the workgroups of all its regions, so that small outputs keep full-height tiles)
+  const dim3 grid( tilesX, ( p.outH + tileH - 1 ) / tileH, rg.count );
+  const bool batch = rg.srcOff || rg.count > 1;
   if( resample_two_launches( p.h, p.outH ) )
   {
-    hipLaunchKernelGGL( k_output_resample_h, dim3( tilesX, ( p.h + 3 ) / 4 ), dim3( 256 ), 0, s, p, (int*) scratch );
-    hipLaunchKernelGGL( k_output_resample<true>, grid, dim3( 256 ), 0, s, p, tileH, (const int*) scratch, (uint8_t*) dst );
+    const dim3 gridH( tilesX, ( p.h + 3 ) / 4, rg.count );
+    if( batch ) hipLaunchKernelGGL( k_output_resample_h<true>, gridH, dim3( 256 ), 0, s, p, (int*) scratch, rg ); else hipLaunchKernelGGL( k_output_resample_h<false>, gridH, dim3( 256 ), 0, s, p, (int*) scratch, rg );
+    if( batch ) hipLaunchKernelGGL( ( k_output_resample<true, true> ), grid, dim3( 256 ), 0, s, p, tileH, (const int*) scratch, (uint8_t*) dst, rg );
+    else        hipLaunchKernelGGL( ( k_output_resample<true, false> ), grid, dim3( 256 ), 0, s, p, tileH, (const int*) scratch, (uint8_t*) dst, rg );
   }
-  else hipLaunchKernelGGL( k_output_resample<false>, grid, dim3( 256 ), 0, s, p, tileH, (const int*) nullptr, (uint8_t*) dst );
+  else if( batch ) hipLaunchKernelGGL( ( k_output_resample<false, true> ), grid, dim3( 256 ), 0, s, p, tileH, (const int*) nullptr, (uint8_t*) dst, rg );
+  else             hipLaunchKernelGGL( ( k_output_resample<false, false> ), grid, dim3( 256 ), 0, s, p, tileH, (const int*) nullptr, (uint8_t*) dst, rg );
 }
 
 // k_film_grain — film grain synthesis at the output, the VFGS hardware model of the reference (FilmGrainImpl::add_grain_block ->
@@ -5542,8 +5565,8 @@ __device__ __forceinline__ void stats_flush( const uint32_t* __restrict__ words,
 // the smallest (with equal fractions the choice among the tied axes moves weight 0).  The lane's 8 pixels go in two batches of four: the 16
 // loads of a batch are issued back to back (32 VGPRs of results in flight), then the twelve multiply-adds per pixel; one batch of eight would
 // hold 64 VGPRs, and load-wait-load four dependent round trips to L2 per pixel.
-template<int COL, int FMT, bool WHOLE, int XF>
-__global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_t* __restrict__ dst )
+template<int COL, int FMT, bool WHOLE, int XF, bool BATCH = false>
+__global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_t* __restrict__ dst, RgbRegions rg )
 {
   __shared__ uint16_t rgb_raw[2][RGB_CH][RGB_CW];
   __shared__ __attribute__(( aligned( 16 ) )) int rgb_sum[2][RGB_CH][RGB_SW];
@@ -5554,10 +5577,23 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
   // the lane's 8 luma samples (2-byte aligned in general, as k_output_frame's piece); a row that ends inside them: pair by pair
   const int jj = tid >> 3, xl = ( tid & 7 ) * 8, x = X0 + xl, y = Y0 + jj, n = WHOLE ? 8 : min( 8, p.w - x );
   const bool live = x < p.w && y < p.h;
+  // BATCH: the region of vvr_output_submit_batch (blockIdx.z): where its planes start and where they go - uniform values.  The single
+  // request runs the instantiation without it, which does not look at `rg`: the parent's kernel (four classes of the one with it lost a
+  // wave per SIMD: profiles/output_batch_4k.txt)
+  const unsigned z = BATCH ? blockIdx.z : 0;
+  const pel_t* __restrict__ srcY = p.src[0]; const pel_t* __restrict__ srcU = p.src[1]; const pel_t* __restrict__ srcV = p.src[2];
+  size_t dz[3] = { 0, 0, 0 };
+  if( BATCH )
+  {
+    srcY += region_offset( rg.srcOff, 3 * z ) + z * rg.srcStep[0];
+    srcU += region_offset( rg.srcOff, 3 * z + 1 ) + z * rg.srcStep[1];
+    srcV += region_offset( rg.srcOff, 3 * z + 2 ) + z * rg.srcStep[2];
+    dz[0] = z * rg.dstStep[0]; dz[1] = z * rg.dstStep[1]; dz[2] = z * rg.dstStep[2];
+  }
   uint4 yy = make_uint4( 0, 0, 0, 0 );
   if( live )
   {
-    const pel_t* __restrict__ row = p.src[0] + (size_t) y * p.stride[0] + x;
+    const pel_t* __restrict__ row = srcY + (size_t) y * p.stride[0] + x;
     if( n == 8 ) __builtin_memcpy( &yy, row, 16 );      // (one 16-byte load: unaligned access mode)
     else
     {
@@ -5574,7 +5610,7 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
   for( int i = 0; i < PER_LANE; i++ )      // (all loads in flight before the first LDS store)
   {
     const int t = min( tid + 256 * i, STAGED - 1 ), pl = t / ( RGB_CH * RGB_CW ), rem = t - pl * ( RGB_CH * RGB_CW ), r = rem / RGB_CW, cc = rem - r * RGB_CW;
-    const pel_t* __restrict__ s = pl ? p.src[2] : p.src[1];
+    const pel_t* __restrict__ s = pl ? srcV : srcU;
     staged[i] = (uint16_t) s[(size_t) clip3( 0, ch - 1, cy0 + r ) * ( pl ? p.stride[2] : p.stride[1] ) + clip3( 0, cw - 1, cx0 + cc )];
   }
   // the tables: lane t brings lin[4 t .. 4 t + 3] and the pairs 2 j, 2 j + 1 for j = t, t + 256 (dwords j and j + 1 of enc; dword 512 is
@@ -5748,9 +5784,9 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
   const size_t i0 = (size_t) y * p.w + x;
   if( FMT == VVR_OUT_RGBF32 )
   {
-    rgb_store_f32<WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, p.nscale[0], p.nbias[0], n );
-    rgb_store_f32<WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, G, p.nscale[1], p.nbias[1], n );
-    rgb_store_f32<WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, B, p.nscale[2], p.nbias[2], n );
+    rgb_store_f32<WHOLE>( ( p.direct[0] ? p.direct[0] : dst + p.dstOff[0] ) + dz[0], i0, R, p.nscale[0], p.nbias[0], n );
+    rgb_store_f32<WHOLE>( ( p.direct[1] ? p.direct[1] : dst + p.dstOff[1] ) + dz[1], i0, G, p.nscale[1], p.nbias[1], n );
+    rgb_store_f32<WHOLE>( ( p.direct[2] ? p.direct[2] : dst + p.dstOff[2] ) + dz[2], i0, B, p.nscale[2], p.nbias[2], n );
     return;
   }
   if( FMT >= VVR_OUT_RGBA8 )
@@ -5761,45 +5797,56 @@ __global__ __launch_bounds__( 256 ) void k_output_rgb( OutputRgbParams p, uint8_
 #pragma unroll
       for( int i = 0; i < 8; i++ ) { const int t = R[i]; R[i] = B[i]; B[i] = t; }
     }
-    rgb_store_px<FMT, WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, G, B, p.inv, n );
+    rgb_store_px<FMT, WHOLE>( ( p.direct[0] ? p.direct[0] : dst + p.dstOff[0] ) + dz[0], i0, R, G, B, p.inv, n );
     return;
   }
-  rgb_store<FMT, WHOLE>( p.direct[0] ? p.direct[0] : dst + p.dstOff[0], i0, R, p.inv, n );
-  rgb_store<FMT, WHOLE>( p.direct[1] ? p.direct[1] : dst + p.dstOff[1], i0, G, p.inv, n );
-  rgb_store<FMT, WHOLE>( p.direct[2] ? p.direct[2] : dst + p.dstOff[2], i0, B, p.inv, n );
+  rgb_store<FMT, WHOLE>( ( p.direct[0] ? p.direct[0] : dst + p.dstOff[0] ) + dz[0], i0, R, p.inv, n );
+  rgb_store<FMT, WHOLE>( ( p.direct[1] ? p.direct[1] : dst + p.dstOff[1] ) + dz[1], i0, G, p.inv, n );
+  rgb_store<FMT, WHOLE>( ( p.direct[2] ? p.direct[2] : dst + p.dstOff[2] ) + dz[2], i0, B, p.inv, n );
 }
 template<int FMT, bool WHOLE, int XF>
-static void launch_output_rgb_as( hipStream_t s, const OutputRgbParams& p, void* dst )
+static void launch_output_rgb_as( hipStream_t s, const OutputRgbParams& p, void* dst, const RgbRegions& rg )
 {
-  const dim3 grid( ( p.w + RGB_TW - 1 ) / RGB_TW, ( p.h + RGB_TH - 1 ) / RGB_TH );
+  const dim3 grid( ( p.w + RGB_TW - 1 ) / RGB_TW, ( p.h + RGB_TH - 1 ) / RGB_TH, rg.count );
+  if( rg.srcOff || rg.count > 1 )
+  {
+    switch( p.collocated & 3 )
+    {
+    case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, FMT, WHOLE, XF, true> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
+    case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, FMT, WHOLE, XF, true> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
+    case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, FMT, WHOLE, XF, true> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
+    default: hipLaunchKernelGGL( ( k_output_rgb<3, FMT, WHOLE, XF, true> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
+    }
+    return;
+  }
   switch( p.collocated & 3 )
   {
-  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
-  default: hipLaunchKernelGGL( ( k_output_rgb<3, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst ); break;
+  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
+  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
+  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
+  default: hipLaunchKernelGGL( ( k_output_rgb<3, FMT, WHOLE, XF> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) dst, rg ); break;
   }
 }
 template<int FMT>
-static void launch_output_rgb_fmt( hipStream_t s, const OutputRgbParams& p, void* dst )
+static void launch_output_rgb_fmt( hipStream_t s, const OutputRgbParams& p, void* dst, const RgbRegions& rg )
 {
   const bool whole = ( p.w & 7 ) == 0;      // (rows of a multiple of 8 samples: every lane has 8, at an aligned address)
-  if( p.lut )        { if( whole ) launch_output_rgb_as<FMT, true, 2>( s, p, dst ); else launch_output_rgb_as<FMT, false, 2>( s, p, dst ); }
-  else if( p.xform ) { if( whole ) launch_output_rgb_as<FMT, true, 1>( s, p, dst ); else launch_output_rgb_as<FMT, false, 1>( s, p, dst ); }
-  else               { if( whole ) launch_output_rgb_as<FMT, true, 0>( s, p, dst ); else launch_output_rgb_as<FMT, false, 0>( s, p, dst ); }
+  if( p.lut )        { if( whole ) launch_output_rgb_as<FMT, true, 2>( s, p, dst, rg ); else launch_output_rgb_as<FMT, false, 2>( s, p, dst, rg ); }
+  else if( p.xform ) { if( whole ) launch_output_rgb_as<FMT, true, 1>( s, p, dst, rg ); else launch_output_rgb_as<FMT, false, 1>( s, p, dst, rg ); }
+  else               { if( whole ) launch_output_rgb_as<FMT, true, 0>( s, p, dst, rg ); else launch_output_rgb_as<FMT, false, 0>( s, p, dst, rg ); }
 }
-void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst )
+void launch_output_rgb( hipStream_t s, const OutputRgbParams& p, void* dst, const RgbRegions& rg )
 {
   switch( p.format )
   {
-  case VVR_OUT_RGB8:    launch_output_rgb_fmt<VVR_OUT_RGB8>( s, p, dst ); break;
-  case VVR_OUT_RGB16:   launch_output_rgb_fmt<VVR_OUT_RGB16>( s, p, dst ); break;
-  case VVR_OUT_RGBF16:  launch_output_rgb_fmt<VVR_OUT_RGBF16>( s, p, dst ); break;
-  case VVR_OUT_RGBF32:  launch_output_rgb_fmt<VVR_OUT_RGBF32>( s, p, dst ); break;
-  case VVR_OUT_RGBA8:   launch_output_rgb_fmt<VVR_OUT_RGBA8>( s, p, dst ); break;      // (and BGRA8: p.swapRB)
-  case VVR_OUT_RGB24:   launch_output_rgb_fmt<VVR_OUT_RGB24>( s, p, dst ); break;      // (and BGR24)
-  case VVR_OUT_RGB10A2: launch_output_rgb_fmt<VVR_OUT_RGB10A2>( s, p, dst ); break;
-  case VVR_OUT_RGBA16F: launch_output_rgb_fmt<VVR_OUT_RGBA16F>( s, p, dst ); break;
+  case VVR_OUT_RGB8:    launch_output_rgb_fmt<VVR_OUT_RGB8>( s, p, dst, rg ); break;
+  case VVR_OUT_RGB16:   launch_output_rgb_fmt<VVR_OUT_RGB16>( s, p, dst, rg ); break;
+  case VVR_OUT_RGBF16:  launch_output_rgb_fmt<VVR_OUT_RGBF16>( s, p, dst, rg ); break;
+  case VVR_OUT_RGBF32:  launch_output_rgb_fmt<VVR_OUT_RGBF32>( s, p, dst, rg ); break;
+  case VVR_OUT_RGBA8:   launch_output_rgb_fmt<VVR_OUT_RGBA8>( s, p, dst, rg ); break;      // (and BGRA8: p.swapRB)
+  case VVR_OUT_RGB24:   launch_output_rgb_fmt<VVR_OUT_RGB24>( s, p, dst, rg ); break;      // (and BGR24)
+  case VVR_OUT_RGB10A2: launch_output_rgb_fmt<VVR_OUT_RGB10A2>( s, p, dst, rg ); break;
+  case VVR_OUT_RGBA16F: launch_output_rgb_fmt<VVR_OUT_RGBA16F>( s, p, dst, rg ); break;
   default: break;      // (the request path hands over one of the eight classes)
   }
 }
@@ -6213,10 +6260,10 @@ static void launch_output_stats_as( hipStream_t s, const OutputRgbParams& p, uin
   const dim3 grid( ( p.w + RGB_TW - 1 ) / RGB_TW, ( p.h + RGB_TH - 1 ) / RGB_TH );
   switch( p.collocated & 3 )
   {
-  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
-  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
-  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
-  default: hipLaunchKernelGGL( ( k_output_rgb<3, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards ); break;
+  case 0:  hipLaunchKernelGGL( ( k_output_rgb<0, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards, RgbRegions() ); break;
+  case 1:  hipLaunchKernelGGL( ( k_output_rgb<1, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards, RgbRegions() ); break;
+  case 2:  hipLaunchKernelGGL( ( k_output_rgb<2, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards, RgbRegions() ); break;
+  default: hipLaunchKernelGGL( ( k_output_rgb<3, RGB_FMT_STATS, WHOLE, 0> ), grid, dim3( 256 ), 0, s, p, (uint8_t*) shards, RgbRegions() ); break;
   }
 }
 void launch_output_stats( hipStream_t s, const OutputRgbParams& p, int rgb, uint32_t* shards )

@@ -197,7 +197,18 @@ void rgb_coefficients( int matrix, int fullRange, int bd, int od, OutputRgbParam
 namespace rescale_host_tbl {
 #include "../../tables/vvc_tables.inc"
 }
-void launch_rescale( hipStream_t, const RescaleParams& p, void* dst )
+static void rescale_region( const RescaleParams& p, void* dst );
+// (the regions of a batch, vvr_output_submit_batch: the loop that is blockIdx.z on the device)
+void launch_rescale( hipStream_t, const RescaleParams& p, void* dst, const PlaneRegions& rg )
+{
+  for( int z = 0; z < rg.count; z++ )
+  {
+    RescaleParams q = p;
+    if( rg.srcOff ) q.src += rg.srcOff[3 * z + rg.comp];
+    rescale_region( q, (uint8_t*) dst + (size_t) z * rg.dstStep );
+  }
+}
+static void rescale_region( const RescaleParams& p, void* dst )
 {
   const int taps = p.luma ? 8 : 4, fracShift = p.luma ? 4 : 5, fracMask = ( 1 << fracShift ) - 1;
   auto coef = [&]( int frac, int k ) { return (int) ( p.luma ? rescale_host_tbl::vvc_luma_filter[frac][k] : rescale_host_tbl::vvc_chroma_filter[frac][k] ); };
@@ -227,7 +238,17 @@ void launch_rescale( hipStream_t, const RescaleParams& p, void* dst )
 
 // ... and launch_output_resample (k_output_resample): the two passes of vvr_set_output_resampling (vvr.h) sample by sample over the tap tables
 // as the device takes them
-void launch_output_resample( hipStream_t, const ResampleParams& p, void* dst, void* )
+static void resample_region( const ResampleParams& p, void* dst );
+void launch_output_resample( hipStream_t, const ResampleParams& p, void* dst, void*, const PlaneRegions& rg )
+{
+  for( int z = 0; z < rg.count; z++ )
+  {
+    ResampleParams q = p;
+    if( rg.srcOff ) q.src += rg.srcOff[3 * z + rg.comp];
+    resample_region( q, (uint8_t*) dst + (size_t) z * rg.dstStep );
+  }
+}
+static void resample_region( const ResampleParams& p, void* dst )
 {
   const int16_t* wx = (const int16_t*) ( p.tabX + p.outW ); const int16_t* wy = (const int16_t*) ( p.tabY + p.outH );
   std::vector<int> H( (size_t) p.h * p.outW );
@@ -369,7 +390,21 @@ uint16_t rgb_half_rne( float f )      // 0 or 1 / 65535 <= f <= 1: zero, a subno
   return (uint16_t) h;
 }
 }
-void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst )
+static void rgb_region( const OutputRgbParams& p, void* dst );
+void launch_output_rgb( hipStream_t, const OutputRgbParams& p, void* dst, const RgbRegions& rg )
+{
+  for( int z = 0; z < rg.count; z++ )
+  {
+    OutputRgbParams q = p;
+    for( int c = 0; c < 3; c++ )
+    {
+      q.src[c] += ( rg.srcOff ? rg.srcOff[3 * z + c] : 0 ) + (size_t) z * rg.srcStep[c];
+      if( q.direct[c] ) q.direct[c] += (size_t) z * rg.dstStep[c]; else q.dstOff[c] += (size_t) z * rg.dstStep[c];
+    }
+    rgb_region( q, dst );
+  }
+}
+static void rgb_region( const OutputRgbParams& p, void* dst )
 {
   const int cw = p.w / 2, ch = p.h / 2;
   std::vector<int> sums( (size_t) ch * p.w ), up[2];
@@ -1470,6 +1505,8 @@ struct OutEntry {
   bool direct = false, queued = false;           // direct: vvr_output_wait copies nothing (pinned or device destinations); queued: something was enqueued (done has been recorded)
   bool devDst = false; size_t extent[5] = { 0, 0, 0, 0, 0 };      // the destination planes lie in device memory: dst[k] .. dst[k] + extent[k] (five: an XPSNR request's reference and prev planes)
   int nc = 0, rows[3] = { 0, 0, 0 }; size_t off[3] = { 0, 0, 0 }, rowBytes[3] = { 0, 0, 0 }, dstStride[3] = { 0, 0, 0 }; void* dst[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+  // a batch (vvr_output_submit_batch; a single request: one region): plane k of region i at off[k] + i * step[k] in `dev` / `host` and at dst[k] + i * bstride[k]
+  int count = 1; size_t step[3] = { 0, 0, 0 }, bstride[3] = { 0, 0, 0 };
   bool timed = false; PendingTiming timing;
   // a hash request: method + 1 (0: an output request); planes of planeBytes[] at off[] in `host` (MD5) or one word per component at its start
   int hash = 0, hashNc = 0; size_t planeBytes[3] = { 0, 0, 0 };
@@ -1619,7 +1656,7 @@ int outAcquire( vvr_context* c, const char* who, int slot, int job, bool blockin
 void outTake( vvr_context* c, OutEntry* e, int slot, int job, int jobFailed )
 {
   e->ticket = c->nextTicket; c->nextTicket = c->nextTicket == 0x3fffffff ? 2 : c->nextTicket + 1;
-  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->hash = 0; e->stats = 0; e->cmp = 0; e->msScales = 0; e->xps = false; e->refSlot = -1;
+  e->job = job; e->slot = slot; e->rc = jobFailed; e->queued = false; e->direct = false; e->devDst = false; e->nc = 0; e->count = 1; e->hash = 0; e->stats = 0; e->cmp = 0; e->msScales = 0; e->xps = false; e->refSlot = -1;
   if( e->timed ) { hipEventDestroy( e->timing.a ); hipEventDestroy( e->timing.b ); e->timed = false; }
   if( e->timed2 ) { hipEventDestroy( e->timing2.a ); hipEventDestroy( e->timing2.b ); e->timed2 = false; }
   if( e->timed0 ) { hipEventDestroy( e->timing0.a ); hipEventDestroy( e->timing0.b ); e->timed0 = false; }
@@ -1683,12 +1720,28 @@ extern "C" {
 // (a call that fails while a request is being enqueued: `who` is the submit call, s the output stream - drained, the entry's buffers may be reused at once)
 #define OQCHK( call ) do { hipError_t e_ = ( call ); if( e_ != hipSuccess ) { c->setError( std::string( who ) + ": " #call ": " + hipGetErrorString( e_ ) ); hipStreamSynchronize( s ); return VVR_ERR_DEVICE; } } while( 0 )
 
-VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
+// vvr_output_submit (bt == NULL) and vvr_output_submit_batch: one request path.  A batch is the single request with `count` regions where that has
+// one: the checks, the context state, the tap tables and the launches are the request's; a region adds a row of the table of origins (three words:
+// its sample offset in each plane of the slot, uploaded through the entry's pinned memory on the output stream like the grain's words) and its
+// place in the entry's buffers and in the destination - plane k of region i at i * step from plane k of region 0.
+#define VVR_OUT_BATCH_SCRATCH_MAX ( (size_t) 512 << 20 )
+static_assert( sizeof( vvr_output_batch ) == 40 && offsetof( vvr_output_batch, count ) == 4 && offsetof( vvr_output_batch, origin ) == 8 && offsetof( vvr_output_batch, batch_stride_bytes ) == 16,
+               "vvr_output_batch is part of the ABI" );
+static int outputSubmit( vvr_context* c, const vvr_output_request* rq, const vvr_output_batch* bt, const char* const who )
 {
   if( !c || !rq ) return VVR_ERR_PARAMETER;
-  const char* const who = "vvr_output_submit";
+  auto outRefuse = [who]( vvr_context* c, const std::string& why ) { return ::outRefuse( c, why.c_str(), who ); };
   // ---- 1. the request
   if( rq->struct_size != sizeof( vvr_output_request ) ) return outRefuse( c, "struct_size is not sizeof( vvr_output_request )" );
+  const int count = bt ? (int) bt->count : 1;
+  if( bt )
+  {
+    if( bt->struct_size != sizeof( vvr_output_batch ) ) return outRefuse( c, "struct_size is not sizeof( vvr_output_batch )" );
+    if( bt->count < 1 || bt->count > VVR_OUT_BATCH_MAX ) return outRefuse( c, "count must be 1 .. 256 (VVR_OUT_BATCH_MAX)" );
+    if( !bt->origin ) return outRefuse( c, "origin is NULL" );
+    if( rq->x | rq->y ) return outRefuse( c, "x and y of the request must be 0 (a region's window starts at its origin)" );
+    if( rq->grain ) return outRefuse( c, "grain is not offered for a batch (the seed chain is defined per frame)" );
+  }
   const int slot = rq->slot, bd = c->cfg.bit_depth, nc = c->cfg.chroma_format ? 3 : 1, x = rq->x, y = rq->y, w = rq->w, h = rq->h;
   if( slot < 0 || slot >= (int) c->slots.size() || !c->slots[slot].p[0] ) return outRefuse( c, "no such slot" );
   // the RGB formats: three planes (RGB8, RGB16, RGBF16, RGBF32) or one plane of pixels (`inter`); px: bytes of a sample of a plane, or of a pixel
@@ -1701,6 +1754,7 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   const bool yuv444 = rq->format == VVR_OUT_YUV444P8 || rq->format == VVR_OUT_YUV444P16 || rq->format == VVR_OUT_Y410, yuvOne = yuv && rq->format >= VVR_OUT_UYVY;
   const bool yuv8 = rq->format == VVR_OUT_YUV444P8 || rq->format == VVR_OUT_YUV422P8 || rq->format == VVR_OUT_UYVY || rq->format == VVR_OUT_YUY2;
   if( rq->format > VVR_OUT_PACKED10 && rq->format != VVR_OUT_NV12 && rq->format != VVR_OUT_P010 && !rgb && !yuv ) return outRefuse( c, "unknown format" );
+  if( bt && !rgb ) return outRefuse( c, "a batch takes the ten R'G'B' formats (VVR_OUT_RGB8 ... VVR_OUT_RGBA16F)" );
   if( rq->job < -1 ) return outRefuse( c, "job must be a job id or -1" );
   const bool packed = rq->format == VVR_OUT_PACKED10, semi = rq->format == VVR_OUT_NV12 || rq->format == VVR_OUT_P010, grain = rq->grain != 0, scaled = rq->out_w != 0 || rq->out_h != 0;
   const bool narrow = rq->format == VVR_OUT_PLANAR8 || rq->format == VVR_OUT_NV12 || yuv8;
@@ -1731,6 +1785,12 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   if( yuv && scaled && ( ( rq->out_w | rq->out_h ) & 1 ) ) return outRefuse( c, "4:2:2 / 4:4:4 output needs an even out_w and out_h (one 4:2:0 frame is upsampled)" );
   const DevPlanes d = pictureIn( c, slot );
   if( x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > d.w[0] || y + h > d.h[0] || ( nc > 1 && ( ( x | y | w | h ) & 1 ) ) ) return outRefuse( c, "window outside the picture, or odd in 4:2:0" );
+  for( int i = 0; bt && i < count; i++ )
+  {
+    const int ox = bt->origin[2 * i], oy = bt->origin[2 * i + 1];
+    if( ox < 0 || oy < 0 || ox > d.w[0] - w || oy > d.h[0] - h || ( nc > 1 && ( ( ox | oy ) & 1 ) ) )
+      return outRefuse( c, "region " + std::to_string( i ) + ": window outside the picture, or odd in 4:2:0" );
+  }
   if( grain )
   {
     if( !c->grainBank ) return outRefuse( c, "no film grain bank set" );
@@ -1762,6 +1822,19 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     }
     if( k < nOut && ( !rq->dst[k] || rq->dst_stride_bytes[k] < rowBytes[k] ) ) return outRefuse( c, "missing plane or stride below the output's row" );
   }
+  // a batch: plane k of region i lies i * bstride[k] behind plane k of region 0, regions do not overlap in the destination; span[k]: from the
+  // first byte of plane k of region 0 to the last of the last region (a single request: the plane's extent)
+  size_t extent[3] = { 0, 0, 0 }, span[3] = { 0, 0, 0 }, bstride[3] = { 0, 0, 0 };
+  for( int k = 0; k < nOut; k++ )
+  {
+    extent[k] = (size_t) ( outRows[k] - 1 ) * rq->dst_stride_bytes[k] + rowBytes[k];
+    if( bt )
+    {
+      bstride[k] = bt->batch_stride_bytes[k];
+      if( bstride[k] < extent[k] ) return outRefuse( c, "batch_stride_bytes below the plane's extent ( rows - 1 ) * dst_stride_bytes + row bytes: regions would overlap in the destination" );
+    }
+    span[k] = (size_t) ( count - 1 ) * bstride[k] + extent[k];
+  }
   hipSetDevice( c->device );
   // ---- 2. a ring entry; the picture has been handed to the device
   OutEntry* e = nullptr;
@@ -1770,18 +1843,17 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   { const int rc = outAcquire( c, who, slot, rq->job, rq->blocking != 0, lk, e, jobDone, jobFailed ); if( rc != VVR_OK ) return rc; }
   hipStream_t s = c->outQStream;
   // ---- where the planes go: device memory the context knows (every plane wholly inside a range), or the host
-  size_t extent[3] = { 0, 0, 0 }; int devPlanes = 0;
+  int devPlanes = 0;
   for( int k = 0; k < nOut; k++ )
   {
-    extent[k] = (size_t) ( outRows[k] - 1 ) * rq->dst_stride_bytes[k] + rowBytes[k];
     const char* b = (const char*) rq->dst[k];
     for( const DevRange& r : c->devRanges )
     {
-      if( b >= r.p && b + extent[k] <= r.p + r.n ) { devPlanes++; break; }
-      if( b < r.p + r.n && b + extent[k] > r.p ) { c->setError( "vvr_output_submit: a destination plane lies partly inside a device range (vvr_device_alloc / vvr_device_register)" ); return VVR_ERR_PARAMETER; }
+      if( b >= r.p && b + span[k] <= r.p + r.n ) { devPlanes++; break; }
+      if( b < r.p + r.n && b + span[k] > r.p ) { c->setError( std::string( who ) + ": a destination plane lies partly inside a device range (vvr_device_alloc / vvr_device_register)" ); return VVR_ERR_PARAMETER; }
     }
   }
-  if( devPlanes && devPlanes != nOut ) { c->setError( "vvr_output_submit: destination planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
+  if( devPlanes && devPlanes != nOut ) { c->setError( std::string( who ) + ": destination planes in device memory mixed with planes in host memory" ); return VVR_ERR_PARAMETER; }
   const bool devDst = devPlanes != 0;
   if( rgb ) { outMatrix = c->outMatrix; outFullRange = c->outFullRange; }      // (what is set now, behind the waits above: a description cannot be unset)
   // the narrowing the request takes: the one that is set now (it can be unset: the request is refused then, no entry has been taken); the four
@@ -1818,45 +1890,68 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   }
   int xm[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
   if( xf ) memcpy( xm, c->xform->m, sizeof( xm ) );
-  outTake( c, e, slot, rq->job, jobFailed ); e->nc = nOut;
-  if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
-  // ---- the entry's buffers: the output's planes; the 16-bit planes of a grained frame that goes on (A) and of a rescaled plane that is packed (B); the words
+  // ---- the entry's buffers: the output's planes; the 16-bit planes of a grained frame that goes on (A) and of a rescaled plane that is packed (B); the words.
+  // A batch: plane k of its regions at off[k] + i * step[k] in `dev`, the rescaled planes of its regions back to back at offB[k], the
+  // horizontal results of the two-launch form back to back at offH, the table of origins behind the words
   const bool grainTmp = grain && ( viaTmp || anyResc );
-  size_t total = 0, tmpBytes = 0, offA[3] = { 0, 0, 0 }, offB[3] = { 0, 0, 0 };
+  size_t total = 0, tmpBytes = 0, offA[3] = { 0, 0, 0 }, offB[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
   bool direct = true, kdirect[3] = { false, false, false };      // kdirect: k_output_frame stores the plane straight into the caller's device memory
   for( int k = 0; k < nOut; k++ )
   {
     const bool frameStores = viaTmp || !( ( grain && !grainTmp ) || resc[k] );      // (else k_film_grain / k_rescale store the plane themselves)
-    kdirect[k] = devDst && frameStores && rq->dst_stride_bytes[k] == rowBytes[k] && ( (uintptr_t) rq->dst[k] & 31 ) == 0;
-    e->off[k] = total; e->rowBytes[k] = rowBytes[k]; e->rows[k] = outRows[k]; e->dst[k] = rq->dst[k]; e->dstStride[k] = rq->dst_stride_bytes[k]; e->extent[k] = extent[k];
-    if( !kdirect[k] ) total += outRegion( rowBytes[k] * outRows[k] );
-    direct = direct && ( devDst || c->pinned.contains( rq->dst[k], extent[k] ) );
+    kdirect[k] = devDst && frameStores && rq->dst_stride_bytes[k] == rowBytes[k] && ( (uintptr_t) rq->dst[k] & 31 ) == 0 && ( bstride[k] & 31 ) == 0;
+    e->off[k] = total; e->rowBytes[k] = rowBytes[k]; e->rows[k] = outRows[k]; e->dst[k] = rq->dst[k]; e->dstStride[k] = rq->dst_stride_bytes[k]; e->extent[k] = span[k];
+    step[k] = outRegion( rowBytes[k] * outRows[k] ); e->step[k] = step[k]; e->bstride[k] = bstride[k];
+    if( !kdirect[k] ) total += (size_t) count * step[k];
+    direct = direct && ( devDst || c->pinned.contains( rq->dst[k], span[k] ) );
   }
   for( int k = 0; k < nc; k++ )
   {
     if( grainTmp ) { offA[k] = tmpBytes; tmpBytes += outRegion( (size_t) pw[k] * ph[k] * 2 ); }
-    if( resc[k] && viaTmp ) { offB[k] = tmpBytes; tmpBytes += outRegion( (size_t) ow[k] * oh[k] * 2 ); }
+    if( resc[k] && viaTmp ) { offB[k] = tmpBytes; tmpBytes += outRegion( (size_t) count * ow[k] * oh[k] * 2 ); }
   }
   // (... and the horizontal results of a plane that k_output_resample takes in two launches: one region, the planes use it in turn on the stream)
   size_t offH = tmpBytes, bytesH = 0;
-  for( int k = 0; k < nc; k++ ) if( resample && resc[k] && resample_two_launches( ph[k], oh[k] ) ) bytesH = std::max( bytesH, (size_t) ph[k] * ow[k] * sizeof( int ) );
+  for( int k = 0; k < nc; k++ ) if( resample && resc[k] && resample_two_launches( ph[k], oh[k] ) ) bytesH = std::max( bytesH, (size_t) count * ph[k] * ow[k] * sizeof( int ) );
   tmpBytes += alignUp( bytesH, 256 );
+  if( bt && total + tmpBytes > VVR_OUT_BATCH_SCRATCH_MAX )
+  { c->setError( std::string( who ) + ": the batch's device buffers in the ring entry (outputs not stored directly, resampled frames, horizontal results) would exceed the limit of 512 MiB: submit fewer regions per request" ); return VVR_ERR_PARAMETER; }
+  outTake( c, e, slot, rq->job, jobFailed ); e->nc = nOut; e->count = count;
+  if( jobFailed != VVR_OK ) { e->state = OQ_FLIGHT; return e->ticket; }      // (nothing to run: the request fails with the job's status)
   const int nbx = ( w + 15 ) / 16, nby = ( h + 15 ) / 16;
   const size_t wordsBytes = grain ? (size_t) nbx * nby * sizeof( uint32_t ) : 0, wordsOff = tmpBytes, hostWordsOff = direct ? 0 : total;
   tmpBytes += alignUp( wordsBytes, 256 );
+  const size_t tabBytes = bt ? (size_t) count * 3 * sizeof( uint32_t ) : 0, tabOff = tmpBytes;
+  tmpBytes += alignUp( tabBytes, 256 );
   const size_t hostBankOff = hostWordsOff + alignUp( wordsBytes, 256 );      // (a bank that changed travels through the entry's pinned memory: the context's copy may change while the upload is in flight)
   const size_t hostXformOff = hostBankOff + ( grain && c->grainBankStale ? alignUp( sizeof( vvr_film_grain_bank ), 256 ) : 0 );      // (... and so do the tables of a transform that changed)
   // (... and the nodes of a LUT that changed: up to 2.2 MB more of the entry's pinned staging, grown below once per entry like the staging of a
   // larger output - the device copy is never reallocated, the staging is only ever enlarged)
   const size_t hostLutOff = hostXformOff + ( xfUpload ? alignUp( sizeof( vvr_output_transform ), 256 ) : 0 );
-  if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostLutOff + ( lutUpload ? lutBytes : 0 ), true ) != VVR_OK )
-  { c->setError( "vvr_output_submit: out of device or pinned memory" ); return VVR_ERR_DEVICE; }
+  const size_t hostTabOff = hostLutOff + ( lutUpload ? alignUp( lutBytes, 256 ) : 0 );      // (... and the table of a batch's origins)
+  if( outGrow( e->dev, e->devCap, total, false ) != VVR_OK || outGrow( e->tmp, e->tmpCap, tmpBytes, false ) != VVR_OK || outGrow( e->host, e->hostCap, hostTabOff + tabBytes, true ) != VVR_OK )
+  { c->setError( std::string( who ) + ": out of device or pinned memory" ); return VVR_ERR_DEVICE; }
   e->direct = direct; e->devDst = devDst;
   // ---- 3. behind the picture (or the slot's users) on the device, 4. the kernels.  mu stays held up to the registration of the `read` event: a
   // picture committed meanwhile that overwrites the slot must find it
   OQCHK( outOrder( c, e, slot, rq->job, jobDone ) );
   struct Cur { const pel_t* p; int stride; bool inOut; } cur[3];
   for( int k = 0; k < nc; k++ ) { const int sh = k ? 1 : 0; cur[k].p = d.p[k] + (size_t) ( y >> sh ) * d.stride[k] + ( x >> sh ); cur[k].stride = d.stride[k]; cur[k].inOut = false; }
+  // a batch: the table of origins - per region its sample offset in each plane of the slot - through the entry's pinned memory; the kernels
+  // that read the slot take it (useTab), those behind them read the regions' planes in `tmp` back to back
+  const uint32_t* regionTab = nullptr;
+  if( bt )
+  {
+    uint32_t* tab = (uint32_t*) ( e->host + hostTabOff );
+    for( int i = 0; i < count; i++ )
+      for( int k = 0; k < 3; k++ )
+      {
+        const int sh = k ? 1 : 0, kk = k < nc ? k : 0;
+        tab[3 * i + k] = (uint32_t) ( (size_t) ( bt->origin[2 * i + 1] >> sh ) * d.stride[kk] + ( bt->origin[2 * i] >> sh ) );
+      }
+    OQCHK( hipMemcpyAsync( e->tmp + tabOff, tab, tabBytes, hipMemcpyHostToDevice, s ) );
+    regionTab = (const uint32_t*) ( e->tmp + tabOff );
+  }
   uint32_t nextSeed = c->grainSeed;
   if( grain )
   {
@@ -1895,13 +1990,15 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
       p.maxVal = ( 1 << bd ) - 1; p.bytesPerSample = viaTmp ? 2 : bps;
       OQCHK( resampleTable( c, s, resample, pw[k], ow[k], k && ( rq->collocated & 1 ) ? 1 : 2, p.tabX, p.tapsX ) );
       OQCHK( resampleTable( c, s, resample, ph[k], oh[k], k && ( rq->collocated & 2 ) ? 1 : 2, p.tabY, p.tapsY ) );
-      bytes += (double) pw[k] * ph[k] * 2 + (double) ow[k] * oh[k] * p.bytesPerSample; launches++;      // (a request's planes count one launch each, in one or two parts)
+      bytes += ( (double) pw[k] * ph[k] * 2 + (double) ow[k] * oh[k] * p.bytesPerSample ) * count; launches++;      // (a request's planes count one launch each, in one or two parts - whatever the number of regions)
     }
     outTimeBegin( c, s, e->timed0, e->timing0, K_OUTPUT_RESAMPLE, bytes );
     for( int k = 0; k < nc; k++ )
     {
       if( !resc[k] ) continue;
-      launch_output_resample( s, rp[k], viaTmp ? e->tmp + offB[k] : e->dev + e->off[k], e->tmp + offH );
+      PlaneRegions rg;      // (a batch is an RGB request: its planes go on to k_output_rgb through `tmp`)
+      rg.count = count; rg.comp = k; rg.srcOff = regionTab; rg.dstStep = bt ? (size_t) ow[k] * oh[k] * 2 : 0; rg.hStep = bt ? (size_t) ph[k] * ow[k] : 0;
+      launch_output_resample( s, rp[k], viaTmp ? e->tmp + offB[k] : e->dev + e->off[k], e->tmp + offH, rg );
       if( viaTmp ) { cur[k].p = (const pel_t*) ( e->tmp + offB[k] ); cur[k].stride = ow[k]; } else cur[k].inOut = true;
     }
     if( e->timed0 ) hipEventRecord( e->timing0.b, s );
@@ -1919,7 +2016,9 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     int scale;
     rescale_axis( pw[k], ow[k], cs, colX, fracShift, scale, p.addX, p.shiftX ); p.stepX = scale << cs;
     rescale_axis( ph[k], oh[k], cs, colY, fracShift, scale, p.addY, p.shiftY ); p.stepY = scale << cs;
-    launch_rescale( s, p, viaTmp ? e->tmp + offB[k] : e->dev + e->off[k] );
+    PlaneRegions rg;
+    rg.count = count; rg.comp = k; rg.srcOff = regionTab; rg.dstStep = bt ? (size_t) ow[k] * oh[k] * 2 : 0;
+    launch_rescale( s, p, viaTmp ? e->tmp + offB[k] : e->dev + e->off[k], rg );
     if( viaTmp ) { cur[k].p = (const pel_t*) ( e->tmp + offB[k] ); cur[k].stride = ow[k]; } else cur[k].inOut = true;
   }
   OutputFrameParams fp; memset( &fp, 0, sizeof( fp ) );
@@ -1970,8 +2069,12 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
       rp.lutWiden = (uint32_t) ( ( 1ull << 39 ) / (unsigned) ( ( 1 << bd ) - 1 ) + 1 );
       rp.inv = 1.0f / 65535.0f;
     }
-    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + (double) nOut * px ) );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma; written: the planes, or the pixel)
-    launch_output_rgb( s, rp, e->dev );
+    // the regions of a batch: their windows of the slot through the table, or - every plane is rescaled or none: w, h, out_w, out_h are even -
+    // their rescaled planes in `tmp` back to back; their outputs a step apart in the entry's scratch or in the caller's device memory
+    RgbRegions rg; rg.count = count; rg.srcOff = anyResc ? nullptr : regionTab;
+    for( int k = 0; k < 3; k++ ) { rg.srcStep[k] = bt && anyResc ? (size_t) ow[k] * oh[k] : 0; rg.dstStep[k] = !bt || k >= nOut ? 0 : kdirect[k] ? bstride[k] : step[k]; }
+    outTimeBegin( c, s, e->timed, e->timing, K_OUTPUT_RGB, (double) rp.w * rp.h * ( 3. + (double) nOut * px ) * count );      // (read: 2 bytes of luma, 2 x 2 / 4 of chroma; written: the planes, or the pixel)
+    launch_output_rgb( s, rp, e->dev, rg );
     if( e->timed ) hipEventRecord( e->timing.b, s );
   }
   if( yuv )
@@ -1999,7 +2102,20 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
   lk.unlock();
   // ---- the result's way to the host: exactly the output's bytes
   hipError_t ce = hipSuccess;
-  for( int k = 0; k < nOut && ce == hipSuccess; k++ )
+  for( int k = 0; k < nOut && ce == hipSuccess && bt; k++ )
+  {
+    // a batch: pageable destinations take the entry's planes of all regions as they lie, in one copy (vvr_output_wait moves the rows); a pinned
+    // or device plane whose rows are back to back takes its regions as the rows of one 2-D copy, any other one a 2-D copy per region
+    const hipMemcpyKind kind = devDst ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t planeBytes = rowBytes[k] * outRows[k];
+    if( devDst && kdirect[k] ) continue;
+    if( !devDst && !direct ) ce = hipMemcpyAsync( e->host + e->off[k], e->dev + e->off[k], (size_t) ( count - 1 ) * step[k] + planeBytes, kind, s );
+    else if( rq->dst_stride_bytes[k] == rowBytes[k] ) ce = hipMemcpy2DAsync( rq->dst[k], bstride[k], e->dev + e->off[k], step[k], planeBytes, count, kind, s );
+    else
+      for( int i = 0; i < count && ce == hipSuccess; i++ )
+        ce = hipMemcpy2DAsync( (char*) rq->dst[k] + (size_t) i * bstride[k], rq->dst_stride_bytes[k], e->dev + e->off[k] + (size_t) i * step[k], rowBytes[k], rowBytes[k], outRows[k], kind, s );
+  }
+  for( int k = 0; k < nOut && ce == hipSuccess && !bt; k++ )
   {
     if( devDst )      // (what k_output_frame has not stored itself: rows out of the entry's scratch at the caller's stride, on the device)
     {
@@ -2019,6 +2135,14 @@ VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq )
     lk.lock(); e->rc = VVR_ERR_DEVICE; e->queued = false; c->setError( std::string( who ) + ": copy to the destination: " + hipGetErrorString( ce ) );
   }
   return ticket;
+}
+
+VVR_API int vvr_output_submit( vvr_context* c, const vvr_output_request* rq ) { return outputSubmit( c, rq, nullptr, "vvr_output_submit" ); }
+
+VVR_API int vvr_output_submit_batch( vvr_context* c, const vvr_output_request* rq, const vvr_output_batch* bt )
+{
+  if( !c || !rq || !bt ) return VVR_ERR_PARAMETER;
+  return outputSubmit( c, rq, bt, "vvr_output_submit_batch" );
 }
 
 VVR_API int vvr_hash_submit( vvr_context* c, const vvr_hash_request* rq )
@@ -2529,7 +2653,9 @@ VVR_API int vvr_output_wait( vvr_context* c, int ticket )
   lk.unlock();
   if( rc == VVR_OK && e->queued && !e->direct )
     for( int k = 0; k < e->nc; k++ )
-      for( int r = 0; r < e->rows[k]; r++ ) memcpy( (uint8_t*) e->dst[k] + (size_t) r * e->dstStride[k], e->host + e->off[k] + (size_t) r * e->rowBytes[k], e->rowBytes[k] );
+      for( int i = 0; i < e->count; i++ )
+        for( int r = 0; r < e->rows[k]; r++ )
+          memcpy( (uint8_t*) e->dst[k] + (size_t) i * e->bstride[k] + (size_t) r * e->dstStride[k], e->host + e->off[k] + (size_t) i * e->step[k] + (size_t) r * e->rowBytes[k], e->rowBytes[k] );
   if( rc == VVR_OK && e->queued && e->hash )
   {
     // the digests in vvr_picture_hash's byte order (MD5: the planes' bytes are hashed here, on the waiting thread), then the comparison with the SEI's
