@@ -7,8 +7,7 @@ import numpy as np
 from vvdec_amd import abi, synth, stream
 import test_host_glue as T
 import subprocess, os
-subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-pthread", "-Wl,-Bsymbolic", "-I" + T.HIP_INC, "-D__HIP_PLATFORM_AMD__", "-w", T.SRC, "-o", T.LIB])
-L = C.CDLL(T.LIB)
+L = C.CDLL(T.build_stub())      # (the tests' own build of the stand-in runtime library: one list of flags)
 L.vvr_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; L.vvr_free_prepared.argtypes = [C.c_void_p, C.c_void_p]; L.vvr_destroy.argtypes = [C.c_void_p]
 L.vvr_last_error.restype = C.c_char_p; L.vvr_last_error.argtypes = [C.c_void_p]
 L.vvt_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -109,6 +109,9 @@ typedef struct vvs_params {
                                 // Multiples of 8 inside the picture, ascending, at least one CTU size apart (ph_virtual_boundary_pos_x/y_minus1 and the spacing rule of its semantics)
   float    p_boundary_bt;       // of the square nodes (at most 64 x 64) that cross the right or the bottom picture boundary, not both: split in two in the crossing direction instead of in
                                 // four (both are legal implicit splits) - CUs of 8 x 16 and more in a last column 8 samples wide, where the quad split leaves 8 x 8 only.  0: quad, as before
+  uint8_t  grid_w, grid_h;      // both > 0: no split is drawn; every CTU is cut into a uniform grid of grid_w x grid_h CUs (powers of two, 4 .. 64, at most the CTU size, at least
+                                // the smallest CU side of the picture): quad splits down to the larger side, then binary splits.  Chroma-tree nodes stop at 8 luma samples.  The mode
+                                // constraints of the splits (local dual trees, inter-only sub-trees) and everything inside a CU are drawn as without it.  0: splits are drawn, as before
 } vvs_params;
 
 enum { VVS_SLICES_RASTER = 1, VVS_SLICES_RECT = 2 };
@@ -153,7 +156,7 @@ void vvs_bounds( const vvs_params* P, uint32_t* max_cu, uint32_t* max_tu, uint64
   const uint32_t m = 1u << P->min_cu_log2;
   const uint32_t n = ( ( P->width + m - 1 ) / m ) * ( ( P->height + m - 1 ) / m );
   const uint32_t trees = P->dual_tree >= 2.0f ? 5 : ( P->dual_tree > 0 || P->min_cu_log2 == 2 ) ? 2 : 1;                 // dual tree: luma and chroma CUs (luma down to 4x4: four times as many)
-  *max_cu = n * trees; *max_tu = ( P->p_isp > 0 ? 4 * n : n + n / 4 ) * trees + 16;      // ISP: four TUs per CU
+  *max_cu = n * trees; *max_tu = ( P->p_isp > 0 ? 4 * n : P->p_sbt > 0 ? 2 * n + n / 4 : n + n / 4 ) * trees + 16;      // ISP: four TUs per CU; SBT: two (a picture of smallest CUs that all take it)
   *max_coef = (uint64_t) P->width * P->height * 3 / 2 + 4096;
 }
 
@@ -882,13 +885,19 @@ struct Gen {
       return;
     }
     const int s = std::max( w, h );
+    enum { S_NONE, S_QT, S_BV, S_BH, S_TV, S_TH };
+    int type = S_NONE;
+    if( P.grid_w && P.grid_h )
+    {
+      // uniform grid: no draw.  Quad splits while the node is a square larger than the larger side of the grid (so no quad split follows a binary one), then binary ones
+      const int gw = curTree == VVR_TREE_CHROMA ? std::max<int>( P.grid_w, 8 ) : P.grid_w, gh = curTree == VVR_TREE_CHROMA ? std::max<int>( P.grid_h, 8 ) : P.grid_h;
+      type = ( w == h && w > std::max( gw, gh ) ) ? S_QT : w > gw ? S_BV : h > gh ? S_BH : S_NONE;
+    }
     double ps = s >= 128 ? 0.92 : s >= 64 ? 0.70 : s >= 32 ? 0.45 : s >= 16 ? 0.25 : s >= 8 && minS < 8 ? 0.2 : 0.0;
     ps = std::min( 0.98, ps * P.p_split_scale );
     if( w != h && std::min( w, h ) <= minS ) ps *= 0.5;
     if( curI && s > 64 ) ps = 1.0;   // intra pictures / slices: CUs <= 64
-    enum { S_NONE, S_QT, S_BV, S_BH, S_TV, S_TH };
-    int type = S_NONE;
-    if( rng.p( ps ) )
+    if( !( P.grid_w && P.grid_h ) && rng.p( ps ) )
     {
       const int r = rng.u( 100 );
       // VPDU rules of the standard (every 64x64 region is decoded completely before the next one, or a CU covers whole regions):
@@ -1375,10 +1384,14 @@ struct Gen {
       for( int ry = y; ry < y + ctu && ry < H; ry += R ) for( int rx = x; rx < x + ctu && rx < W; rx += R )
       {
         const bool inside = rx + R <= W && ry + R <= H;
-        const bool nodeQT = R == 64 && inside && rng.p( 0.85 ), nodeNS = R == 64 && inside && !nodeQT;
+        // (uniform grid: the node is left whole for 64 x 64 CUs and quad-split for CUs with both sides below 64; a grid with one side of 64 splits the luma node
+        // in two first, and CCLM stays off)
+        const bool grid = P.grid_w && P.grid_h, grid64 = grid && std::max( P.grid_w, P.grid_h ) == 64;
+        const bool nodeQT = grid ? R == 64 && inside && !grid64 : R == 64 && inside && rng.p( 0.85 );
+        const bool nodeNS = grid ? R == 64 && inside && P.grid_w == 64 && P.grid_h == 64 : R == 64 && inside && !nodeQT;
         for( int tree = VVR_TREE_LUMA; tree <= VVR_TREE_CHROMA; tree++ )
         {
-          curTree = tree; cclmOk = R < 64 || inside;
+          curTree = tree; cclmOk = ( R < 64 || inside ) && !( grid64 && !nodeNS );
           if( nodeNS ) addCu( rx, ry, R, R );
           else if( nodeQT ) { const int hs = R >> 1; split( rx, ry, hs, hs ); split( rx + hs, ry, hs, hs ); split( rx, ry + hs, hs, hs ); split( rx + hs, ry + hs, hs, hs ); }
           else split( rx, ry, R, R );
@@ -1403,6 +1416,11 @@ int vvs_generate( const vvs_params* P, vvs_buffers* B )
 {
   if( P->min_cu_log2 < 2 || P->chroma_format > 1 || P->bit_depth < 8 || P->bit_depth > 10 ) return -1;
   if( P->min_qp_ts < 4 || P->min_qp_ts > 52 || ( P->min_qp_ts - 4 ) % 6 || P->lmcs_shape >= VVS_LMCS_NUM_SHAPES || P->chroma_qp_flavour > 2 ) return -1;
+  if( P->grid_w || P->grid_h )
+  {
+    const int minSide = P->dual_tree >= 2.0f && P->slice_type == 2 && P->chroma_format ? 4 : 1 << P->min_cu_log2;
+    for( int g : { (int) P->grid_w, (int) P->grid_h } ) if( g < 4 || g > 64 || ( g & ( g - 1 ) ) || g > ( 1 << P->log2_ctu ) || g < minSide ) return -1;
+  }
   Gen g( *P, *B );
   return g.run();
 }

@@ -43,7 +43,8 @@ class Params(C.Structure):
                 ("mv_window_ver", C.c_uint16), ("p_mv_limit", C.c_float),
                 ("lmcs_shape", C.c_uint8), ("min_qp_ts", C.c_uint8), ("chroma_qp_flavour", C.c_uint8), ("chroma_qp_model", C.c_uint32),
                 ("tile_col_w", C.c_uint8 * (MAX_TILE_COLS + 1)), ("tile_row_h", C.c_uint8 * (MAX_TILE_ROWS + 1)), ("slice_mode", C.c_uint8),
-                ("slice_map", C.c_void_p), ("slice_map_len", C.c_uint32), ("vb_x", C.c_uint16 * 4), ("vb_y", C.c_uint16 * 4), ("p_boundary_bt", C.c_float)]
+                ("slice_map", C.c_void_p), ("slice_map_len", C.c_uint32), ("vb_x", C.c_uint16 * 4), ("vb_y", C.c_uint16 * 4), ("p_boundary_bt", C.c_float),
+                ("grid_w", C.c_uint8), ("grid_h", C.c_uint8)]      # both > 0: every CTU is cut into a uniform grid of CUs of this size, no split is drawn
 
 
 # Params.lmcs_shape: LMCS models at the ends of what lmcs_data() allows (tools/synth.cpp, genLmcs)
