@@ -23,7 +23,6 @@ NAMES = {R.AREA: "area", R.TRIANGLE: "triangle", R.CUBIC: "cubic"}
 
 def _rec(bd=10):
     rec = vvdec_amd.Reconstructor(B.W, B.H_, bit_depth=bd, chroma_format=1, num_slots=2, num_streams=1)
-    B.bind(rec.L)
     return rec
 
 

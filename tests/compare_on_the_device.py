@@ -10,15 +10,15 @@ import torch                      # first: its HIP runtime is the one the proces
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vvdec_amd                  # noqa: E402
+import output_support as SUP        # noqa: E402
 import compare_ref                # noqa: E402
 import test_output_compare_host as X              # noqa: E402
-import test_output_hash_host as XH                # noqa: E402
 
 
 def tensors_as_the_reference():
     rec = vvdec_amd.Reconstructor(X.W, X.H_, bit_depth=10, num_slots=2, num_streams=1)
     rng = np.random.default_rng(1280)
-    planes = XH.random_planes(rng, X.W, X.H_, 10, 1)
+    planes = SUP.random_planes(rng, X.W, X.H_, 10, 1)
     rec.write_picture(0, planes)
     rec.enable_stats()
     runs = 0

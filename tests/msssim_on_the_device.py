@@ -9,10 +9,10 @@ import torch                      # first: its HIP runtime is the one the proces
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vvdec_amd                  # noqa: E402
+import output_support as SUP        # noqa: E402
 import compare_ref                # noqa: E402
 import msssim_ref                 # noqa: E402
 import test_output_msssim_host as X               # noqa: E402
-import test_output_hash_host as XH                # noqa: E402
 
 
 def agrees(got, want, win, what, weights=None):
@@ -25,7 +25,7 @@ def agrees(got, want, win, what, weights=None):
 def tensors_as_the_reference():
     rec = vvdec_amd.Reconstructor(X.W, X.H_, bit_depth=10, num_slots=2, num_streams=1)
     rng = np.random.default_rng(1580)
-    planes = XH.random_planes(rng, X.W, X.H_, 10, 1)
+    planes = SUP.random_planes(rng, X.W, X.H_, 10, 1)
     rec.write_picture(0, planes)
     rec.enable_stats()
     launches = runs = 0
@@ -52,7 +52,7 @@ def tensors_as_the_reference():
         got = rec.msssim(0, [p.astype(dt) for p in ref], window=win, scales=scales)
         runs, launches = runs + 1, launches + scales
         agrees(got, msssim_ref.msssim(part, ref, 10, scales), win, "numpy planes, %d bytes per sample" % bps)
-    other = X.noisy(planes, 10, 1581)
+    other = SUP.noisy(planes, 10, 1581)
     rec.write_picture(1, other)
     mine = [0.1, 0.2, 0.3, 0.25, 0.15]
     got = rec.msssim(0, 1, weights=mine)

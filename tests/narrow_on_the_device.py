@@ -26,7 +26,6 @@ from vvdec_amd import abi, stream, synth          # noqa: E402
 
 def _rec(bd, cf=1, **kw):
     rec = vvdec_amd.Reconstructor(S.W, S.H_, bit_depth=bd, chroma_format=cf, num_slots=2, num_streams=1, **kw)
-    N.bind(rec.L)
     return rec
 
 

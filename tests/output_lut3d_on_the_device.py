@@ -28,7 +28,6 @@ from vvdec_amd import abi, stream, synth          # noqa: E402
 
 def _setup(bd, seed):
     rec, picture = ID._setup(bd, seed)
-    LH.bind(rec.L)
     return rec, picture
 
 

@@ -26,7 +26,6 @@ YD.TORCH_DT.setdefault(np.float32, torch.float32)
 
 def _rec(bd):
     rec = vvdec_amd.Reconstructor(N.W, N.H_, bit_depth=bd, chroma_format=1, num_slots=2, num_streams=1)
-    N.bind(rec.L)
     return rec
 
 

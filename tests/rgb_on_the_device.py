@@ -56,7 +56,6 @@ class GuardedTensor:
 
 def _rec(bd, **kw):
     rec = vvdec_amd.Reconstructor(S.W, S.H_, bit_depth=bd, chroma_format=1, num_slots=2, num_streams=1, **kw)
-    R.bind(rec.L)
     return rec
 
 

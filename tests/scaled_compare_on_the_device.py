@@ -10,12 +10,12 @@ import torch                      # first: its HIP runtime is the one the proces
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vvdec_amd                  # noqa: E402
+import output_support as SUP        # noqa: E402
 import compare_ref                # noqa: E402
 import msssim_ref                 # noqa: E402
 import ssim_ref                   # noqa: E402
 import xpsnr_ref                  # noqa: E402
 import test_output_compare_host as XC             # noqa: E402
-import test_output_hash_host as XH                # noqa: E402
 import test_output_msssim_host as XM              # noqa: E402
 import test_output_scaled_compare_host as S       # noqa: E402
 import test_output_ssim_host as XS                # noqa: E402
@@ -36,7 +36,7 @@ def tensors_as_the_reference():
     bd = 10
     rec = vvdec_amd.Reconstructor(S.W, S.H_, bit_depth=bd, num_slots=2, num_streams=1)
     rng = np.random.default_rng(2200)
-    planes = XH.random_planes(rng, S.W, S.H_, bd, 1)
+    planes = SUP.random_planes(rng, S.W, S.H_, bd, 1)
     rec.write_picture(0, planes)
     for name, win, size in (S.LADDER, S.UNEVEN):
         rec.set_compare_scaling(size)

@@ -52,7 +52,6 @@ class TensorPlanes:
 
 def _rec(bd, **kw):
     rec = vvdec_amd.Reconstructor(S.W, S.H_, bit_depth=bd, chroma_format=1, num_slots=2, num_streams=1, **kw)
-    S.bind(rec.L)
     return rec
 
 

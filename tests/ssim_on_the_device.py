@@ -9,10 +9,10 @@ import torch                      # first: its HIP runtime is the one the proces
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vvdec_amd                  # noqa: E402
+import output_support as SUP        # noqa: E402
 import compare_ref                # noqa: E402
 import ssim_ref                   # noqa: E402
 import test_output_ssim_host as X                 # noqa: E402
-import test_output_hash_host as XH                # noqa: E402
 
 
 def agrees(got, want, win, what):
@@ -24,7 +24,7 @@ def agrees(got, want, win, what):
 def tensors_as_the_reference():
     rec = vvdec_amd.Reconstructor(X.W, X.H_, bit_depth=10, num_slots=2, num_streams=1)
     rng = np.random.default_rng(1480)
-    planes = XH.random_planes(rng, X.W, X.H_, 10, 1)
+    planes = SUP.random_planes(rng, X.W, X.H_, 10, 1)
     rec.write_picture(0, planes)
     rec.enable_stats()
     runs = 0
@@ -51,7 +51,7 @@ def tensors_as_the_reference():
         got = rec.ssim(0, [p.astype(dt) for p in ref], window=win, with_map=True)
         runs += 1
         agrees(got, ssim_ref.ssim(part, ref, 10), win, "numpy planes, %d bytes per sample" % bps)
-    other = X.noisy(planes, 10, 1481)
+    other = SUP.noisy(planes, 10, 1481)
     rec.write_picture(1, other)
     got = rec.ssim(0, 1, with_map=True)
     runs += 1

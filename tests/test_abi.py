@@ -109,7 +109,6 @@ def test_tr_type_helper(built):
     import vvdec_amd
     from vvdec_amd import abi
     L = vvdec_amd.lib()
-    L.vvr_resolve_tr_type.restype = C.c_uint8
     h = abi.PicHeader(); cu = abi.Cu(); tu = abi.Tu()
     cu.pred_mode = abi.PRED_INTRA; cu.w = cu.h = 16
     tu.w, tu.h = 16, 16
@@ -140,7 +139,6 @@ def test_resolver_matches_reference_checked_streams(built, implicit):
     import vvdec_amd
     from vvdec_amd import abi, synth, stream
     L = vvdec_amd.lib()
-    L.vvr_resolve_tr_type.restype = C.c_uint8
     tools = abi.TOOL_MTS | abi.TOOL_LFNST | abi.TOOL_DEP_QUANT | (abi.TOOL_IMPLICIT_MTS if implicit else 0)
     plans, _ = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     checked = 0
@@ -159,3 +157,16 @@ def test_resolver_matches_reference_checked_streams(built, implicit):
                 assert got == t.tr_type[comp], "CU %dx%d pred %d isp %d sbt %d lfnst %d comp %d: %d != %d" % (cu.w, cu.h, cu.pred_mode, cu.isp_mode, cu.sbt_info, cu.lfnst_idx, comp, got, t.tr_type[comp])
                 checked += 1
     assert checked > 100
+
+
+def test_one_signature_table_covers_every_exported_symbol():
+    """abi.SIGNATURES is what vvdec_amd.lib() and the tests' stand-in library are bound with: one entry per exported symbol, and the functions of
+    include/vvr.h that return a pointer or a size_t (written out here, not parsed) have a return type of that width - ctypes' default int would
+    cut them to 32 bits"""
+    import vvdec_amd
+    from vvdec_amd import abi
+    assert set(abi.SIGNATURES) == set(vvdec_amd.EXPORTED_SYMBOLS)
+    wide = {"vvr_host_alloc": C.c_void_p, "vvr_plane_ptr": C.c_void_p, "vvr_device_alloc": C.c_void_p, "vvr_job_stream": C.c_void_p,
+            "vvr_last_error": C.c_char_p, "vvr_version": C.c_char_p, "vvr_slot_bytes": C.c_size_t, "vvr_abi_sizeof": C.c_size_t}
+    for name, restype in wide.items():
+        assert abi.SIGNATURES[name][0] is restype and C.sizeof(restype) == C.sizeof(C.c_void_p), name

@@ -8,35 +8,12 @@ import numpy as np
 import pytest
 
 import film_grain_ref
+import output_support as SUP
 import test_host_glue as T
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
 need_ref = pytest.mark.skipif(not film_grain_ref.available(), reason="oracle/_ref/libvvref.so not built (needs /root/reference at build time)")
-
-
-def _lib():
-    L = C.CDLL(T.build_stub())
-    L.vvr_last_error.restype = C.c_char_p
-    L.vvr_last_error.argtypes = [C.c_void_p]
-    L.vvr_destroy.argtypes = [C.c_void_p]
-    L.vvr_write_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-    L.vvr_slot_picture_size.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.vvr_set_film_grain.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_set_film_grain_seed.argtypes = [C.c_void_p, C.c_uint32]
-    L.vvr_read_output_grain.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    return L
-
-
-def _ctx(L, W, H, bit_depth, chroma_format, slots=2):
-    cfg = abi.Config()
-    cfg.abi_version = abi.VVR_ABI_VERSION
-    cfg.device, cfg.max_width, cfg.max_height = 0, W, H
-    cfg.chroma_format, cfg.bit_depth, cfg.log2_ctu = chroma_format, bit_depth, 7
-    cfg.num_slots, cfg.num_streams = slots, 1
-    ctx = C.c_void_p()
-    assert L.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    return ctx
 
 
 def read_grain(L, ctx, slot, win, bps, ncomp, pad=(3, 5, 7), call=None):
@@ -72,22 +49,16 @@ def play(set_bank, set_seed, read, steps, banks, want, bd, what):
     assert nf == len(want)
 
 
-def write_picture(L, ctx, slot, planes):
-    for c, p in enumerate(planes):
-        p = np.ascontiguousarray(p, np.uint16)
-        assert L.vvr_write_plane(ctx, slot, c, p.ctypes.data, p.shape[1]) == abi.VVR_OK
-
-
 @need_ref
 @pytest.mark.parametrize("cf", [1, 0])
 @pytest.mark.parametrize("bd", [10, 8])
 def test_sequence_is_the_reference_film_grain(tmp_path, bd, cf):
     """the whole case matrix (film_grain_ref.matrix_sequence) in one sequence on one context, against FilmGrain frame by frame"""
-    L = _lib()
+    L = SUP.stub_lib()
     picture, steps = film_grain_ref.matrix_sequence(bd, cf)
     banks, want = film_grain_ref.expected(picture, steps, bd, cf, str(tmp_path))
-    ctx = _ctx(L, 448, 160, bd, cf)
-    write_picture(L, ctx, 1, picture)
+    ctx = SUP.make_ctx(L, 448, 160, bd, cf)
+    SUP.write_picture(L, ctx, 1, picture)
     keep = []
 
     def set_bank(b):
@@ -105,12 +76,12 @@ def test_sequence_is_the_reference_film_grain(tmp_path, bd, cf):
 @need_ref
 def test_a_picture_smaller_than_its_slot(tmp_path):
     """the window is in samples of the picture in the slot (an RPR picture is smaller than the slot): a window beyond that picture is refused"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(5)
     picture = film_grain_ref.grain_picture(rng, 200, 104, 10, 1)
     sei = film_grain_ref.random_sei(rng, 0, 3, 5)
     banks, want = film_grain_ref.expected(picture, [("fgc", sei), ("frame", (0, 0, 200, 104), 2), ("frame", (4, 2, 160, 96), 2)], 10, 1, str(tmp_path))
-    ctx = _ctx(L, 448, 160, 10, 1)
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
     assert L.vvr_slot_picture_size(ctx, 0, 200, 104) == abi.VVR_OK
     for c, p in enumerate(picture):
         assert L.vvr_write_plane(ctx, 0, c, np.ascontiguousarray(p).ctypes.data, p.shape[1]) == abi.VVR_OK
@@ -132,10 +103,10 @@ def _bank(rng):
 def test_refusals_and_the_chain():
     """every refusal of vvr_set_film_grain / vvr_read_output_grain, with a message; a refused read does not advance the seed chain; the chain
     starts at 0xdeadbeef, vvr_set_film_grain does not touch it and vvr_set_film_grain_seed sets it"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(9)
-    ctx = _ctx(L, 448, 160, 10, 1)
-    write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
+    SUP.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
     win = (2, 4, 200, 64)
     assert read_grain(L, ctx, 0, win, 2, 3)[0] == abi.VVR_ERR_PARAMETER and b"no film grain bank" in L.vvr_last_error(ctx)
     good = _bank(rng)
@@ -163,8 +134,8 @@ def test_refusals_and_the_chain():
     # none of that advanced the chain: the next frame is the first frame of a fresh context
     rc, first = read_grain(L, ctx, 0, win, 2, 3)
     assert rc == abi.VVR_OK
-    ctx2 = _ctx(L, 448, 160, 10, 1)
-    write_picture(L, ctx2, 0, film_grain_ref.grain_picture(np.random.default_rng(9), 448, 160, 10, 1))
+    ctx2 = SUP.make_ctx(L, 448, 160, 10, 1)
+    SUP.write_picture(L, ctx2, 0, film_grain_ref.grain_picture(np.random.default_rng(9), 448, 160, 10, 1))
     assert L.vvr_set_film_grain(ctx2, C.addressof(bank)) == abi.VVR_OK
     rc, again = read_grain(L, ctx2, 0, win, 2, 3)
     assert rc == abi.VVR_OK and all(np.array_equal(a, b) for a, b in zip(first, again))
@@ -179,7 +150,7 @@ def test_refusals_and_the_chain():
     assert read_grain(L, ctx2, 0, win, 2, 3)[0] == abi.VVR_ERR_PARAMETER
     L.vvr_destroy(ctx2)
     # bit depths other than 8 and 10
-    ctx9 = _ctx(L, 448, 160, 9, 1)
+    ctx9 = SUP.make_ctx(L, 448, 160, 9, 1)
     assert L.vvr_set_film_grain(ctx9, C.addressof(bank)) == abi.VVR_OK
     assert read_grain(L, ctx9, 0, win, 2, 3)[0] == abi.VVR_ERR_PARAMETER and b"bit depth" in L.vvr_last_error(ctx9)
     L.vvr_destroy(ctx9)

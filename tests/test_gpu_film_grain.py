@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import film_grain_ref
+import output_support as SUP
 import test_film_grain_host as H
 from vvdec_amd import abi, synth, stream
 
@@ -107,9 +108,9 @@ def test_reconstructed_picture_with_later_pictures_in_flight(built, tmp_path, bd
 
 def _stand_in(bd, cf, picture, cases):
     """(in a child process: the stand-in runtime's library defines the HIP calls it uses) the cases through the stand-in's launch_film_grain"""
-    L = H._lib()
-    ctx = H._ctx(L, 448, 160, bd, cf)
-    H.write_picture(L, ctx, 0, picture)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, 448, 160, bd, cf)
+    SUP.write_picture(L, ctx, 0, picture)
     out, keep = [], []
     for win, bps, bank in cases:
         if bank is not None:

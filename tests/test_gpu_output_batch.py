@@ -13,11 +13,10 @@ import sys
 import numpy as np
 import pytest
 
+import output_support as SUP
 import resample_ref as R
 import rgb_ref
-import test_film_grain_host as H
 import test_gpu_output_compare as GC
-import test_gpu_output_queue as G
 import test_output_batch_host as B
 import test_output_semiplanar_host as S
 from vvdec_amd import stream, synth
@@ -25,18 +24,10 @@ from vvdec_amd import stream, synth
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    return B.bind(G._lib())
-
-
-def _write(L):
-    return lambda ctx, slot, p: G._write(L, ctx, slot, p)
-
-
 def _run(check, bd, *args, **kw):
-    L = _lib()
-    ctx = H._ctx(L, B.W, B.H_, bd, 1)
-    check(L, ctx, _write(L), *args, **kw)
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, B.W, B.H_, bd, 1)
+    check(L, ctx, SUP.writer(L), *args, **kw)
     L.vvr_destroy(ctx)
 
 
@@ -84,8 +75,8 @@ def test_eight_batches_in_flight_collected_out_of_order(built):
 
 
 def test_refusals_leave_the_ring_alone_on_the_device(built):
-    L = _lib()
-    B.check_refusals(L, lambda: H._ctx(L, B.W, B.H_, 10, 1), _write(L))
+    L = SUP.product_lib()
+    B.check_refusals(L, lambda: SUP.make_ctx(L, B.W, B.H_, 10, 1), SUP.writer(L))
 
 
 def test_batches_of_the_pictures_of_a_stream_in_flight(built):
@@ -98,7 +89,6 @@ def test_batches_of_the_pictures_of_a_stream_in_flight(built):
     origins, wsize, size = [(0, 0), (128, 0), (0, 64), (128, 64)], (128, 64), (32, 16)
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     rec = vvdec_amd.Reconstructor(Wd, Hd, num_slots=nslots, num_streams=4, host_threads=3, **GC.GEO)
-    B.bind(rec.L)
     rec.set_output_colour(1, False)
     rec.set_output_resampling("cubic")
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=4714, tool_flags=GC.TOOLS, alloc=rec.host_array, **GC.GEO, **GC.MIX) for pl in plans]

@@ -6,73 +6,51 @@ import numpy as np
 import pytest
 
 import compare_ref
-import test_film_grain_host as H
+import output_support as SUP
 import test_output_compare_host as X
-import test_output_hash_host as XH
 from vvdec_amd import abi, stream, synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    import vvdec_amd
-    return X.bind(vvdec_amd.lib())
-
-
-def _write(L):
-    def write(ctx, slot, planes):
-        for c, p in enumerate(planes):
-            p = np.ascontiguousarray(p, np.uint16)
-            assert L.vvr_write_plane(ctx, slot, c, p.ctypes.data, p.shape[1]) == abi.VVR_OK
-    return write
-
-
-def _ctx_with(L, bd, cf, seed):
-    w, h = (X.W, X.H_) if cf else (X.W400, X.H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    _write(L)(ctx, 0, planes)
-    return ctx, planes
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_window_on_the_device(built, bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1200 + bd + cf)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1200 + bd + cf)
     X.check_contents(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_sums_that_need_64_bits(built, bd, cf):
-    L = _lib()
-    ctx, _ = _ctx_with(L, bd, cf, 1210)
-    X.check_all_ones_reference(L, ctx, _write(L), 3 if cf else 1, bd)
+    L = SUP.product_lib()
+    ctx, _ = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1210)
+    X.check_all_ones_reference(L, ctx, SUP.writer(L), 3 if cf else 1, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_differences_just_outside_the_window_are_not_reported(built, bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1220)
-    X.check_outside(L, ctx, _write(L), planes, bd)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1220)
+    X.check_outside(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_second_slot_as_the_reference(built, bd, cf):
-    L = _lib()
-    ctx, a = _ctx_with(L, bd, cf, 1230)
+    L = SUP.product_lib()
+    ctx, a = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1230)
     b = [np.where(np.random.default_rng(1231 + c).random(p.shape) < 0.3, p ^ 5, p).astype(np.uint16) for c, p in enumerate(a)]
-    X.check_ref_slot(L, ctx, _write(L), a, b, bd)
+    SUP.check_ref_slot("compare", L, ctx, SUP.writer(L), a, b, bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_reference_in_memory_of_vvr_host_alloc(built):
     """copied to the device straight from the caller's pinned planes, at their stride, on the output stream"""
     import ctypes as C
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1250)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1250)
     rng = np.random.default_rng(1251)
     for win in X.WINDOWS:
         part = compare_ref.window_planes(planes, win)
@@ -92,16 +70,16 @@ def test_a_reference_in_memory_of_vvr_host_alloc(built):
 
 
 def test_tickets_are_shared_with_the_other_kinds_of_request(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1260)
-    X.tickets_and_the_ring(L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1260)
+    SUP.tickets_and_the_ring("compare", L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernels(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1261)
-    X.statistics(L, ctx, planes, 10)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1261)
+    SUP.statistics("compare", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
@@ -136,7 +114,7 @@ def test_pictures_of_a_stream_in_flight_are_compared(built):
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     assert plans[-1].slot == plans[0].slot, "a slot has to be reused"
     rec = vvdec_amd.Reconstructor(Wd, Hd, num_slots=nslots, num_streams=4, host_threads=3, **GEO)
-    L = X.bind(rec.L)
+    L = rec.L
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=4714, tool_flags=TOOLS, alloc=rec.host_array, **GEO, **MIX) for pl in plans]
     zeros = [np.zeros((Hd >> s, Wd >> s), np.uint16) for s in (0, 1, 1)]
     cpu, want = {}, []

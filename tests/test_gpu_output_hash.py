@@ -6,39 +6,28 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import output_support as SUP
 import refdrv
-import test_film_grain_host as H
 import test_output_hash_host as X
 from vvdec_amd import abi, stream, synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    import vvdec_amd
-    return X.bind(vvdec_amd.lib())
-
-
-def _write(L, ctx, slot, planes):
-    for c, p in enumerate(planes):
-        p = np.ascontiguousarray(p, np.uint16)
-        assert L.vvr_write_plane(ctx, slot, c, p.ctypes.data, p.shape[1]) == abi.VVR_OK
-
-
 @pytest.mark.parametrize("W,H_,cf,bd", X.SHAPES)
 def test_matrix_on_the_device(built, W, H_, cf, bd):
-    L = _lib()
-    planes = X.random_planes(np.random.default_rng(W + H_ + bd), W, H_, bd, cf)
-    ctx = H._ctx(L, W, H_, bd, cf)
-    _write(L, ctx, 1, planes)
+    L = SUP.product_lib()
+    planes = SUP.random_planes(np.random.default_rng(W + H_ + bd), W, H_, bd, cf)
+    ctx = SUP.make_ctx(L, W, H_, bd, cf)
+    SUP.write_picture(L, ctx, 1, planes)
     X.check_slot(L, ctx, 1, planes, bd, "%dx%d" % (W, H_))
     L.vvr_destroy(ctx)
 
 
 def test_the_picture_in_the_slot_is_hashed_not_the_slot(built):
-    L = _lib()
-    ctx = H._ctx(L, 256, 144, 10, 1)
-    X.small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: _write(L, ctx, slot, p), np.random.default_rng(41))
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, 256, 144, 10, 1)
+    X.small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(41))
     L.vvr_destroy(ctx)
 
 
@@ -46,11 +35,11 @@ def test_a_3840x2160_frame(built):
     """uploaded, not decoded; the three methods.  MD5 and checksum against refdrv.picture_hash; the CRC against refdrv's CRC as numpy computes it row
     by row (test_output_hash_host.crc_by_rows, pinned to refdrv.hash_crc there: refdrv's own byte loop takes six seconds for this frame) and
     against vvr_picture_hash"""
-    L = _lib()
+    L = SUP.product_lib()
     W, H_, bd = 3840, 2160, 10
-    planes = X.random_planes(np.random.default_rng(2160), W, H_, bd, 1)
-    ctx = H._ctx(L, W, H_, bd, 1, slots=1)
-    _write(L, ctx, 0, planes)
+    planes = SUP.random_planes(np.random.default_rng(2160), W, H_, bd, 1)
+    ctx = SUP.make_ctx(L, W, H_, bd, 1, slots=1)
+    SUP.write_picture(L, ctx, 0, planes)
     for method in X.METHODS:
         want = [X.crc_by_rows(p, bd) for p in planes] if method == abi.HASH_CRC else refdrv.picture_hash(planes, bd, method)
         got, mask = X.queued(L, ctx, 0, method, 3, expected=want)
@@ -98,9 +87,9 @@ def test_every_picture_of_a_stream_in_flight_is_verified(built):
 def test_statistics_name_the_kernels(built):
     """vvr_get_stats: one launch of k_hash_rows and one of k_hash_combine per CRC / checksum request, an MD5 request launches neither; the per-plane
     launches of vvr_picture_hash are counted as k_plane_hash_rows"""
-    L = _lib()
-    planes = X.random_planes(np.random.default_rng(5), 200, 72, 10, 1)
-    ctx = H._ctx(L, 200, 72, 10, 1)
-    _write(L, ctx, 0, planes)
-    X.statistics(L, ctx, planes, 10)
+    L = SUP.product_lib()
+    planes = SUP.random_planes(np.random.default_rng(5), 200, 72, 10, 1)
+    ctx = SUP.make_ctx(L, 200, 72, 10, 1)
+    SUP.write_picture(L, ctx, 0, planes)
+    SUP.statistics("hash", L, ctx, planes, 10)
     L.vvr_destroy(ctx)

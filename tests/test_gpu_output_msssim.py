@@ -9,60 +9,43 @@ import pytest
 
 import compare_ref
 import msssim_ref
-import test_film_grain_host as H
+import output_support as SUP
 import test_gpu_output_compare as G
-import test_output_hash_host as XH
 import test_output_msssim_host as X
 from vvdec_amd import stream, synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    import vvdec_amd
-    return X.bind(vvdec_amd.lib())
-
-
-_write = G._write
-
-
-def _ctx_with(L, bd, cf, seed):
-    w, h = (X.W, X.H_) if cf else (X.W400, X.H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    _write(L)(ctx, 0, planes)
-    return ctx, planes
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_window_on_the_device(built, bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1530 + bd + cf)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1530 + bd + cf)
     X.check_contents(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_slot_holding_words_above_the_bit_depth_is_clamped(built, bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1540)
-    X.check_words_above_the_bit_depth(L, ctx, _write(L), planes, bd)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1540)
+    X.check_words_above_the_bit_depth(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_second_slot_as_the_reference(built, bd, cf):
-    L = _lib()
-    ctx, a = _ctx_with(L, bd, cf, 1550)
-    X.check_ref_slot(L, ctx, _write(L), a, X.noisy(a, bd, 1551), bd)
+    L = SUP.product_lib()
+    ctx, a = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1550)
+    SUP.check_ref_slot("msssim", L, ctx, SUP.writer(L), a, SUP.noisy(a, bd, 1551), bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_reference_in_memory_of_vvr_host_alloc(built):
     """copied to the device straight from the caller's pinned planes, at their padded stride, on the output stream"""
     import ctypes as C
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1555)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1555)
     rng = np.random.default_rng(1556)
     for win, scales in X.CASES:
         part = compare_ref.window_planes(planes, win)
@@ -82,16 +65,16 @@ def test_a_reference_in_memory_of_vvr_host_alloc(built):
 
 
 def test_tickets_are_shared_with_the_other_kinds_of_request(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1560)
-    X.tickets_and_the_ring(L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1560)
+    SUP.tickets_and_the_ring("msssim", L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernels(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1561)
-    X.statistics(L, ctx, planes, 10)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1561)
+    SUP.statistics("msssim", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
@@ -121,7 +104,7 @@ def test_msssim_of_the_pictures_of_a_stream_in_flight(built):
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     assert plans[-1].slot == plans[0].slot, "a slot has to be reused"
     rec = vvdec_amd.Reconstructor(Wd, Hd, num_slots=nslots, num_streams=4, host_threads=3, **G.GEO)
-    L = X.bind(rec.L)
+    L = rec.L
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=4714, tool_flags=G.TOOLS, alloc=rec.host_array, **G.GEO, **G.MIX) for pl in plans]
     cpu, want = {}, []
     for n, (pl, d) in enumerate(zip(plans, descs)):

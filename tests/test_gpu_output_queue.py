@@ -2,7 +2,6 @@
 against the synchronous calls and the application's packing, 3840x2160 and 7680x4320 frames, destinations in memory of vvr_host_alloc, requests
 submitted behind pictures that are still being reconstructed, slots that are overwritten while their outputs are on the way (ordered on the
 device: nothing here depends on timing), whole streams against the bytes vvdecapp writes with -o x.pyuv, and the kernel's statistics."""
-import ctypes as C
 import os
 import subprocess
 
@@ -10,26 +9,13 @@ import numpy as np
 import pytest
 
 import film_grain_ref
-import test_film_grain_host as H
+import output_support as SUP
 import test_output_queue_host as Q
 from vvdec_amd import abi, stream, synth
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 APP_REF = os.path.join(HERE, "..", "oracle", "_ref", "vvdecapp_ref")
-
-
-def _lib():
-    import vvdec_amd
-    L = vvdec_amd.lib()
-    L.vvr_slot_picture_size.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    return Q.bind(L)
-
-
-def _write(L, ctx, slot, planes):
-    for c, p in enumerate(planes):
-        p = np.ascontiguousarray(p, np.uint16)
-        assert L.vvr_write_plane(ctx, slot, c, p.ctypes.data, p.shape[1]) == abi.VVR_OK
 
 
 def _ran(L, ctx, name="k_output_frame"):
@@ -41,9 +27,9 @@ def _ran(L, ctx, name="k_output_frame"):
 @pytest.mark.parametrize("cf", [1, 0])
 @pytest.mark.parametrize("bd", [10, 8])
 def test_matrix_on_the_device(built, bd, cf):
-    L = _lib()
-    mk = lambda W, H_: H._ctx(L, W, H_, bd, cf)
-    ctx, bank = Q.setup(L, mk, lambda ctx, slot, p: _write(L, ctx, slot, p), np.random.default_rng(bd + cf), bd, cf)
+    L = SUP.product_lib()
+    mk = lambda W, H_: SUP.make_ctx(L, W, H_, bd, cf)
+    ctx, bank = Q.setup(L, mk, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(bd + cf), bd, cf)
     assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
     Q.check_planar(L, ctx, bd, cf)
     Q.check_packed(L, mk, ctx, bd, cf)
@@ -55,12 +41,12 @@ def test_matrix_on_the_device(built, bd, cf):
 def test_headline_sizes(built, size, bd):
     """whole frames and a window at an offset in every format the bit depth has (8-bit output exists for 8-bit content only), against the
     picture that was written; one request into memory of vvr_host_alloc at a padded stride"""
-    L = _lib()
+    L = SUP.product_lib()
     W, H_ = size
     rng = np.random.default_rng(W + bd)
     planes = [rng.integers(0, 1 << bd, (H_ >> s, W >> s), dtype=np.uint16) for s in (0, 1, 1)]
-    ctx = H._ctx(L, W, H_, bd, 1, slots=1)
-    _write(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, W, H_, bd, 1, slots=1)
+    SUP.write_picture(L, ctx, 0, planes)
     for n, win in enumerate([(0, 0, W, H_), (2, 4, W - 16, H_ - 8)]):
         if n == 0 and W > 4000:         # (7680x4320: the window at an offset only - the checker's packing of a frame takes a second)
             continue

@@ -13,52 +13,43 @@ import sys
 import numpy as np
 import pytest
 
+import output_support as SUP
 import resample_ref as R
 import rgb_ref
-import test_film_grain_host as H
 import test_gpu_output_compare as GC
-import test_gpu_output_queue as G
 import test_output_resample_host as N
 from vvdec_amd import abi, stream, synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    return N.bind(G._lib())
-
-
-def _write(L):
-    return lambda ctx, slot, p: G._write(L, ctx, slot, p)
-
-
 @pytest.mark.parametrize("bd", [10, 8])
 def test_every_filter_geometry_and_content_on_the_device(built, bd):
-    L = _lib()
-    ctx = H._ctx(L, N.W, N.H_, bd, 1)
-    N.check_geometries(L, ctx, _write(L), bd, 3)
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, N.W, N.H_, bd, 1)
+    N.check_geometries(L, ctx, SUP.writer(L), bd, 3)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_400_contexts_on_the_device(built, bd):
-    L = _lib()
-    ctx = H._ctx(L, N.W400, N.H400, bd, 0)
-    N.check_geometries(L, ctx, _write(L), bd, 1)
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, N.W400, N.H400, bd, 0)
+    N.check_geometries(L, ctx, SUP.writer(L), bd, 1)
     L.vvr_destroy(ctx)
 
 
 def test_the_filter_is_context_state_on_the_device(built):
-    L = _lib()
-    ctx = H._ctx(L, N.W, N.H_, 10, 1)
-    N.check_state(L, ctx, _write(L), 10)
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, N.W, N.H_, 10, 1)
+    N.check_state(L, ctx, SUP.writer(L), 10)
     L.vvr_destroy(ctx)
 
 
 def test_eight_requests_in_flight_collected_out_of_order(built):
-    L = _lib()
-    ctx = H._ctx(L, N.W, N.H_, 10, 1)
-    N.check_in_flight(L, ctx, _write(L))
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, N.W, N.H_, 10, 1)
+    N.check_in_flight(L, ctx, SUP.writer(L))
     L.vvr_destroy(ctx)
 
 
@@ -72,7 +63,6 @@ def test_resampled_frames_of_the_pictures_of_a_stream_in_flight(built):
     win, size = (0, 0, Wd, Hd), (64, 32)
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     rec = vvdec_amd.Reconstructor(Wd, Hd, num_slots=nslots, num_streams=4, host_threads=3, **GC.GEO)
-    N.bind(rec.L)
     rec.set_output_colour(1, False)
     rec.set_output_resampling("cubic")
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=4714, tool_flags=GC.TOOLS, alloc=rec.host_array, **GC.GEO, **GC.MIX) for pl in plans]

@@ -8,11 +8,10 @@ import numpy as np
 import pytest
 
 import compare_ref
+import output_support as SUP
 import rescale_ref
 import ssim_ref
-import test_film_grain_host as H
 import test_output_compare_host as XC
-import test_output_hash_host as XH
 import test_output_queue_host as Q
 import test_output_scaled_compare_host as S
 import test_output_ssim_host as XS
@@ -21,82 +20,62 @@ from vvdec_amd import abi, stream, synth
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    import vvdec_amd
-    return S.bind(vvdec_amd.lib())
-
-
-def _write(L, ctx, slot, planes):
-    for c, p in enumerate(planes):
-        p = np.ascontiguousarray(p, np.uint16)
-        assert L.vvr_write_plane(ctx, slot, c, p.ctypes.data, p.shape[1]) == abi.VVR_OK
-
-
-def _ctx_with(L, bd, cf, seed, w=None, h=None):
-    if w is None:
-        w, h = (S.W, S.H_) if cf else (S.W400, S.H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    _write(L, ctx, 0, planes)
-    return ctx, planes
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_case_on_the_device(built, bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 2000 + bd + cf)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(cf), bd, cf, 2000 + bd + cf)
     S.check_comparison(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_collocated_reaches_the_chroma_planes(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2010)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), 10, 1, 2010)
     S.check_collocated(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_ssim_msssim_and_xpsnr_of_the_rescaled_window(built, bd):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, 1, 2020 + bd)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), bd, 1, 2020 + bd)
     S.check_windowed_measures(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_request_keeps_the_value_it_was_submitted_with(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2030)
-    fresh, _ = _ctx_with(L, 10, 1, 2030)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), 10, 1, 2030)
+    fresh, _ = SUP.ctx_with(L, S.picture_size(1), 10, 1, 2030)
     S.check_capture_at_submit(L, ctx, fresh, planes, 10)
     L.vvr_destroy(ctx)
     L.vvr_destroy(fresh)
 
 
 def test_the_homes_of_a_reference_of_the_scaled_size(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 8, 1, 2040)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), 8, 1, 2040)
     S.check_homes(L, ctx, planes, 8)
     L.vvr_destroy(ctx)
 
 
 def test_the_setter_refuses_and_keeps_the_value_set_before(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2050)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), 10, 1, 2050)
     S.check_setter_refusals(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_at_submit_leave_the_ring_alone(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2060)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), 10, 1, 2060)
     S.check_submit_refusals(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_rescaling(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2070)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), 10, 1, 2070)
     S.check_statistics(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
@@ -116,15 +95,15 @@ def test_a_reference_in_torch_tensors_is_read_in_place(built):
 def test_two_picture_sizes_in_one_context_against_one_reference(built):
     """the RPR case: slot 0 holds a picture of 208 x 80, slot 1 one of 104 x 40 (vvr_slot_picture_size); both are measured against the same
     reference of 208 x 80 - comparison and SSIM"""
-    L = _lib()
+    L = SUP.product_lib()
     bd = 10
-    ctx, full = _ctx_with(L, bd, 1, 2090)
-    small = XH.random_planes(np.random.default_rng(2091), 104, 40, bd, 1)
+    ctx, full = SUP.ctx_with(L, S.picture_size(1), bd, 1, 2090)
+    small = SUP.random_planes(np.random.default_rng(2091), 104, 40, bd, 1)
     assert L.vvr_slot_picture_size(ctx, 1, 104, 40) == abi.VVR_OK
-    _write(L, ctx, 1, small)
+    SUP.write_picture(L, ctx, 1, small)
     size = (208, 80)
     ref = [np.random.default_rng(2092 + c).integers(0, 1 << bd, p.shape, dtype=np.int64) for c, p in enumerate(full)]
-    given = XC.forms(ref)[0][1]
+    given = SUP.forms(ref)[0][1]
     S.scaling(L, ctx, size)
     for slot, win in ((0, (0, 0, 208, 80)), (1, (0, 0, 104, 40))):
         part = S.rescaled(L, ctx, slot, win, size, 1, 3)
@@ -154,14 +133,14 @@ def test_pictures_of_a_stream_in_flight_are_measured_at_another_size(built):
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     assert plans[-1].slot == plans[0].slot, "a slot has to be reused"
     rec = vvdec_amd.Reconstructor(Wd, Hd, num_slots=nslots, num_streams=4, host_threads=3, **GEO)
-    L = S.bind(rec.L)
-    aux = H._ctx(L, Wd, Hd, 10, 1)
+    L = rec.L
+    aux = SUP.make_ctx(L, Wd, Hd, 10, 1)
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=4715, tool_flags=TOOLS, alloc=rec.host_array, **GEO, **MIX) for pl in plans]
     zeros = [np.zeros((size[1] >> s, size[0] >> s), np.uint16) for s in (0, 1, 1)]
     cpu, want = {}, []
     for pl, d in zip(plans, descs):
         cpu[pl.slot] = refdrv.oracle_reconstruct(d, cpu)
-        _write(L, aux, 0, cpu[pl.slot])
+        SUP.write_picture(L, aux, 0, cpu[pl.slot])
         want.append(compare_ref.compare(S.rescaled(L, aux, 0, win, size, 1, 3), zeros))
         assert want[-1]["differing"][0] > 0
     rec.set_compare_scaling(size)
@@ -180,18 +159,18 @@ def test_pictures_of_a_stream_in_flight_are_measured_at_another_size(built):
 
 
 def test_eight_requests_of_scaled_and_unscaled_kinds_in_flight(built):
-    L = _lib()
+    L = SUP.product_lib()
     bd = 10
-    ctx, planes = _ctx_with(L, bd, 1, 2100)
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), bd, 1, 2100)
     name, win, size = S.LADDER
     rng = np.random.default_rng(2101)
     S.scaling(L, ctx, size)
     part = S.rescaled(L, ctx, 0, win, size, 1, 3)
     ref = XC.reference("random", rng, part, bd)
-    given = XC.forms(ref)[0][1]
+    given = SUP.forms(ref)[0][1]
     plain = compare_ref.window_planes(planes, win)
     plain_ref = XC.reference("random", rng, plain, bd)
-    plain_given = XC.forms(plain_ref)[0][1]
+    plain_given = SUP.forms(plain_ref)[0][1]
     flight = []
     for n in range(8):
         if n % 4 == 0:
@@ -223,9 +202,9 @@ def test_eight_requests_of_scaled_and_unscaled_kinds_in_flight(built):
 @pytest.mark.parametrize("what,pic,size", [("1080p to 4K", (1920, 1080), (3840, 2160)), ("8x down", (1024, 512), (128, 64))])
 def test_one_comparison_at_a_large_size(built, what, pic, size):
     """the comparison alone: `random` content, with a map"""
-    L = _lib()
+    L = SUP.product_lib()
     bd = 10
-    ctx, planes = _ctx_with(L, bd, 1, 2110, pic[0], pic[1])
+    ctx, planes = SUP.ctx_with(L, pic, bd, 1, 2110)
     win = (0, 0, pic[0], pic[1])
     S.scaling(L, ctx, size)
     part = S.rescaled(L, ctx, 0, win, size, 1, 3)
@@ -240,9 +219,9 @@ def test_one_comparison_at_a_large_size(built, what, pic, size):
 def test_the_picture_side_is_rescale_plane(built, tmp_path):
     """the picture side straight from vvdec::rescalePlane: the comparison of every case against it reports nothing differing"""
     import vvdec_amd
-    L = _lib()
+    L = SUP.product_lib()
     bd = 10
-    ctx, planes = _ctx_with(L, bd, 1, 2080)
+    ctx, planes = SUP.ctx_with(L, S.picture_size(1), bd, 1, 2080)
     cases_ = []
     for name, win, size in S.CASES:
         for c in range(3):

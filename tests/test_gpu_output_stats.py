@@ -5,29 +5,18 @@ numpy's counts over tests/rgb_ref.py; every comparison is exact."""
 import numpy as np
 import pytest
 
+import output_support as SUP
 import refdrv
-import test_film_grain_host as H
 import test_output_stats_host as X
 from vvdec_amd import abi, stream, synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    import vvdec_amd
-    return X.bind(vvdec_amd.lib())
-
-
-def _write(L, ctx, slot, planes):
-    for c, p in enumerate(planes):
-        p = np.ascontiguousarray(p, np.uint16)
-        assert L.vvr_write_plane(ctx, slot, c, p.ctypes.data, p.shape[1]) == abi.VVR_OK
-
-
 def _random_ctx(L, seed, bd=10):
     planes = X.picture("random", np.random.default_rng(seed), X.W, X.H_, bd)
-    ctx = H._ctx(L, X.W, X.H_, bd, 1)
-    _write(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, X.W, X.H_, bd, 1)
+    SUP.write_picture(L, ctx, 0, planes)
     assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
     return ctx, planes
 
@@ -35,81 +24,81 @@ def _random_ctx(L, seed, bd=10):
 @pytest.mark.parametrize("kind", X.CONTENTS)
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_statistics_of_every_case_on_the_device(built, bd, kind):
-    L = _lib()
+    L = SUP.product_lib()
     planes = X.picture(kind, np.random.default_rng(900 + bd), X.W, X.H_, bd)
-    ctx = H._ctx(L, X.W, X.H_, bd, 1)
-    _write(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, X.W, X.H_, bd, 1)
+    SUP.write_picture(L, ctx, 0, planes)
     X.check_content(L, ctx, planes, bd, kind)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_luma_mode_in_a_400_context(built, bd):
-    L = _lib()
+    L = SUP.product_lib()
     planes = X.picture("random", np.random.default_rng(910 + bd), X.W400, X.H400, bd, 0)
-    ctx = H._ctx(L, X.W400, X.H400, bd, 0)
-    _write(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, X.W400, X.H400, bd, 0)
+    SUP.write_picture(L, ctx, 0, planes)
     X.check_400(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_flat_512x256_frame_needs_32_bit_counts(built):
-    L = _lib()
-    ctx = H._ctx(L, 512, 256, 10, 1)
-    X.check_flat_512x256(L, ctx, lambda ctx, slot, p: _write(L, ctx, slot, p))
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, 512, 256, 10, 1)
+    X.check_flat_512x256(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p))
     L.vvr_destroy(ctx)
 
 
 def test_the_picture_in_the_slot_not_the_slot(built):
-    L = _lib()
-    ctx = H._ctx(L, 256, 144, 10, 1)
-    X.small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: _write(L, ctx, slot, p), np.random.default_rng(920))
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, 256, 144, 10, 1)
+    X.small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(920))
     L.vvr_destroy(ctx)
 
 
 def test_tickets_are_shared_with_output_and_hash_requests(built):
-    L = _lib()
+    L = SUP.product_lib()
     ctx, planes = _random_ctx(L, 921)
-    X.tickets_and_the_ring(L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
+    SUP.tickets_and_the_ring("stats", L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernel(built):
-    L = _lib()
+    L = SUP.product_lib()
     ctx, planes = _random_ctx(L, 922)
-    X.statistics(L, ctx, planes, 10)
+    SUP.statistics("stats", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_rgb_requests_around_a_statistics_request_store_the_same_bytes(built):
-    L = _lib()
+    L = SUP.product_lib()
     ctx, planes = _random_ctx(L, 923)
     X.rgb_requests_around_a_statistics_request(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_a_request_takes_the_colour_description_set_when_it_is_submitted(built):
-    L = _lib()
+    L = SUP.product_lib()
     ctx, planes = _random_ctx(L, 924)
     X.colour_snapshot(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_the_loop_from_statistics_to_the_lut(built):
-    L = _lib()
-    ctx = H._ctx(L, X.W, X.H_, 10, 1)
-    X.loop_from_statistics_to_the_lut(L, ctx, lambda ctx, slot, p: _write(L, ctx, slot, p), np.random.default_rng(930))
+    L = SUP.product_lib()
+    ctx = SUP.make_ctx(L, X.W, X.H_, 10, 1)
+    X.loop_from_statistics_to_the_lut(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(930))
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("kind", ["random", "flat"])
 def test_a_3840x2160_frame(built, kind):
     """uploaded, not decoded; both modes against numpy.  The flat frame puts 8 294 400 samples into one bin of each histogram"""
-    L = _lib()
+    L = SUP.product_lib()
     Wf, Hf, bd, win, col, colour = 3840, 2160, 10, (0, 0, 3840, 2160), (True, False), (9, 0)
     planes = X.picture(kind, np.random.default_rng(2160), Wf, Hf, bd)
-    ctx = H._ctx(L, Wf, Hf, bd, 1, slots=1)
-    _write(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, Wf, Hf, bd, 1, slots=1)
+    SUP.write_picture(L, ctx, 0, planes)
     assert L.vvr_set_output_colour(ctx, *colour) == abi.VVR_OK
     want = X.expected(planes, bd, abi.STATS_RGB, colour, col)
     if kind == "flat":

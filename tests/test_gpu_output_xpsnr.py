@@ -9,61 +9,43 @@ import numpy as np
 import pytest
 
 import compare_ref
+import output_support as SUP
 import xpsnr_ref
-import test_film_grain_host as H
 import test_gpu_output_compare as G
-import test_output_hash_host as XH
-import test_output_ssim_host as XS
 import test_output_xpsnr_host as X
 from vvdec_amd import stream, synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _lib():
-    import vvdec_amd
-    return X.bind(vvdec_amd.lib())
-
-
-_write = G._write
-
-
-def _ctx_with(L, bd, cf, seed):
-    w, h = (X.W, X.H_) if cf else (X.W400, X.H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    _write(L)(ctx, 0, planes)
-    return ctx, planes
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_window_on_the_device(built, bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1530 + bd + cf)
-    X.check_contents(L, ctx, _write(L), planes, bd)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1530 + bd + cf)
+    X.check_contents(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_what_follows_from_the_definition(built, bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1540)
-    X.check_consequences(L, ctx, _write(L), planes, bd)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1540)
+    X.check_consequences(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_the_anchor_on_the_device(built):
-    L = _lib()
-    ctx, _ = _ctx_with(L, 10, 1, 1541)
-    X.check_anchor(L, ctx, _write(L))
+    L = SUP.product_lib()
+    ctx, _ = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1541)
+    X.check_anchor(L, ctx, SUP.writer(L))
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_second_slot_as_the_reference_with_prev_planes_on_the_host(built, bd, cf):
-    L = _lib()
-    ctx, a = _ctx_with(L, bd, cf, 1550)
-    X.check_ref_slot(L, ctx, _write(L), a, XS.noisy(a, bd, 1551), bd)
+    L = SUP.product_lib()
+    ctx, a = SUP.ctx_with(L, X.picture_size(cf), bd, cf, 1550)
+    SUP.check_ref_slot("xpsnr", L, ctx, SUP.writer(L), a, SUP.noisy(a, bd, 1551), bd)
     L.vvr_destroy(ctx)
 
 
@@ -71,10 +53,10 @@ def test_planes_in_memory_of_vvr_host_alloc(built):
     """reference and prev planes copied to the device straight from the caller's pinned planes, at their padded strides, on the output stream;
     and prev planes in pinned memory beside a ref_slot"""
     import ctypes as C
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1555)
-    other = XS.noisy(planes, 10, 1557)
-    _write(L)(ctx, 1, other)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1555)
+    other = SUP.noisy(planes, 10, 1557)
+    SUP.writer(L)(ctx, 1, other)
     rng = np.random.default_rng(1556)
     for win in X.WINDOWS:
         part = compare_ref.window_planes(planes, win)
@@ -98,16 +80,16 @@ def test_planes_in_memory_of_vvr_host_alloc(built):
 
 
 def test_tickets_are_shared_with_the_other_kinds_of_request(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1570)
-    X.tickets_and_the_ring(L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1570)
+    SUP.tickets_and_the_ring("xpsnr", L, ctx, planes, 10, None)      # (vvr_output_stream_wait on the null stream)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernel(built):
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1571)
-    X.statistics(L, ctx, planes, 10)
+    L = SUP.product_lib()
+    ctx, planes = SUP.ctx_with(L, X.picture_size(1), 10, 1, 1571)
+    SUP.statistics("xpsnr", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
@@ -135,12 +117,12 @@ def test_xpsnr_of_the_pictures_of_a_stream_in_flight(built):
     win = (0, 0, Wd, Hd)
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     rec = vvdec_amd.Reconstructor(Wd, Hd, num_slots=nslots, num_streams=4, host_threads=3, **G.GEO)
-    L = X.bind(rec.L)
+    L = rec.L
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=4714, tool_flags=G.TOOLS, alloc=rec.host_array, **G.GEO, **G.MIX) for pl in plans]
     cpu, sources, want = {}, [], []
     for n, (pl, d) in enumerate(zip(plans, descs)):
         cpu[pl.slot] = refdrv.oracle_reconstruct(d, cpu)
-        sources.append(XS.noisy(cpu[pl.slot], 10, 1590 + n))
+        sources.append(SUP.noisy(cpu[pl.slot], 10, 1590 + n))
         prev = [s[0] for s in sources[-2::-1][:2]]
         want.append(xpsnr_ref.xpsnr_integers(cpu[pl.slot], sources[-1], prev))
         assert (want[-1]["block"], want[-1]["filter"], want[-1]["temporal"]) == (8, 1, min(n, 2)) and want[-1]["sse"][0] > 0

@@ -47,17 +47,10 @@ def build_stub():
 
 @pytest.fixture(scope="module")
 def stub():
-    L = C.CDLL(build_stub())
-    L.vvr_last_error.restype = C.c_char_p
-    L.vvr_last_error.argtypes = [C.c_void_p]
+    L = abi.bind(C.CDLL(build_stub()))
     L.vvt_sizeof.restype = C.c_size_t
     L.vvt_sync_capacity.restype = C.c_size_t
     L.vvt_sync_capacity.argtypes = [C.c_void_p, C.c_int]
-    L.vvr_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.vvr_submit_prepared.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_free_prepared.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_destroy.argtypes = [C.c_void_p]
-    L.vvr_sync.argtypes = [C.c_void_p]
     L.vvt_intra_tables.argtypes = [C.c_void_p] + [C.c_void_p] * 4
     assert L.vvt_sizeof(0) == UNIT_DT.itemsize and L.vvt_sizeof(1) == ITEM_DT.itemsize
     return L
@@ -579,10 +572,6 @@ def test_external_slot_users_are_ordered_on_the_device(stub):
     cfg.num_slots, cfg.num_streams, cfg.host_threads = nslots, 3, 2
     ctx = C.c_void_p()
     assert stub.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    stub.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    stub.vvr_stream_wait_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    stub.vvr_slot_external_event.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
     ext = C.c_void_p()
     stub.hipStreamCreateWithFlags(C.byref(ext), 0)
     descs = [synth.picture_for_plan(pl, W, H, seed=611, tool_flags=TOOLS) for pl in plans[:3]]
@@ -635,9 +624,6 @@ def test_an_external_event_is_waited_for_whatever_a_query_says(stub):
     W, H = 256, 128
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
     ctx = Ctx(stub, W, H, nslots, streams=3)
-    stub.vvr_stream_wait_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    stub.vvr_slot_external_event.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
     ext = C.c_void_p()
     stub.hipStreamCreateWithFlags(C.byref(ext), 0)
     descs = [synth.picture_for_plan(pl, W, H, seed=612, tool_flags=TOOLS) for pl in plans[:3]]
@@ -678,10 +664,6 @@ def test_job_status_without_waiting(stub):
     cfg.num_slots, cfg.num_streams, cfg.host_threads = nslots, 2, 2
     ctx = C.c_void_p()
     assert stub.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    stub.vvr_test.argtypes = [C.c_void_p, C.c_int]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     d = synth.picture_for_plan(plans[0], W, H, seed=612, tool_flags=TOOLS)
     p = d.c()
     stub.vvt_events_pending(1)                              # the device has not finished anything
@@ -955,8 +937,6 @@ def test_pictures_in_flight_are_ordered_by_their_slots(stub, lanes, frames, gop,
 def test_output_window_and_8bit_frames(stub):
     """vvr_read_output: conformance-window crop and the narrowing to 8-bit frames (VVDecImpl::copyComp), on planes written through the ABI"""
     W, H = 64, 48
-    stub.vvr_read_output.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t]
-    stub.vvr_write_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     rng = np.random.default_rng(3)
     for bd in (8, 10):
         ctx = Ctx(stub, W, H, 2, log2_ctu=5, bit_depth=bd)
@@ -986,8 +966,6 @@ def test_decoded_picture_hash(stub, bd, cf):
     import hashlib
     import refdrv
     W, H = 136, 72                                          # not a multiple of the 32-sample blocks the reference feeds MD5 with
-    stub.vvr_write_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-    stub.vvr_picture_hash.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     rng = np.random.default_rng(bd * 10 + cf)
     ctx = Ctx(stub, W, H, 2, log2_ctu=5, bit_depth=bd, chroma_format=cf)
     planes = [rng.integers(0, 1 << bd, (H >> s, W >> s)).astype(np.uint16) for s in ((0, 1, 1) if cf else (0,))]
@@ -1136,8 +1114,6 @@ def _submit_stream(stub, threads, W=416, H=240, frames=17, gop=8, lanes=3):
     cfg.num_slots, cfg.num_streams, cfg.host_threads = max(nslots, 12), lanes, threads
     ctx = C.c_void_p()
     assert stub.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
     buf = (C.c_int * 60000)()
     stub.vvt_take_trace(buf, len(buf))
     descs = [synth.picture_for_plan(pl, W, H, seed=511, tool_flags=TOOLS | abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE, log2_ctu=5, p_intra=0.15, p_affine=0.1) for pl in plans]
@@ -1169,8 +1145,6 @@ def test_i_pictures_are_prepared_by_the_workers_together(stub):
     picture with inter CUs while the device is short of work: everything that is uploaded for a stream - I pictures of several sizes among B pictures - is
     byte for byte what one thread uploads"""
     stub.vvt_take_h2d_hash.restype = C.c_ulonglong
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
 
     def run(threads, W, H, l2, frames, gop, intra_period, tools, **kw):
         plans, nslots = stream.ra_plan(frames, gop=gop, seed_poc0_is_external=False, pool=12, intra_period=intra_period)
@@ -1231,8 +1205,6 @@ def test_errors_of_queued_pictures_come_back_from_wait(stub):
     cfg.num_slots, cfg.num_streams, cfg.host_threads = nslots, 2, 2
     ctx = C.c_void_p()
     assert stub.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
     mk = lambda pl: synth.picture_for_plan(pl, W, H, seed=509, tool_flags=TOOLS | abi.TOOL_IBC, p_ibc=0.6)
     bad = mk(plans[0])
     k = int(np.nonzero(bad.cu["pred_mode"] == abi.PRED_IBC)[0][0])
@@ -1271,10 +1243,6 @@ def test_a_wait_of_the_intra_stage_that_gave_up_fails_its_own_picture(stub):
     cfg.num_slots, cfg.num_streams, cfg.host_threads = nslots, 2, 2
     ctx = C.c_void_p()
     assert stub.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
-    stub.vvr_test.argtypes = [C.c_void_p, C.c_int]
-    stub.vvr_sync.argtypes = [C.c_void_p]
     descs = [synth.picture_for_plan(pl, W, H, seed=611, tool_flags=TOOLS, p_intra=0.3) for pl in plans]        # (kept alive: the C structs point into their arrays)
     pics = [d.c() for d in descs]
     j0 = stub.vvr_submit(ctx, C.byref(pics[0]))                       # the I picture: the CTU-tile kernel, no such wait
@@ -1307,11 +1275,6 @@ def test_records_in_pinned_memory_are_not_staged(stub):
     cfg.num_slots, cfg.num_streams, cfg.host_threads = nslots, 2, 2
     ctx = C.c_void_p()
     assert stub.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
-    stub.vvr_inputs_done.argtypes = [C.c_void_p, C.c_int]
-    stub.vvr_host_alloc.restype = C.c_void_p
-    stub.vvr_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
     stub.vvt_take_h2d.argtypes = [C.c_void_p, C.c_void_p]
 
     def pinned(n, dt):
@@ -1356,8 +1319,6 @@ def test_pipeline_under_load_does_not_stall(stub):
     cfg.num_slots, cfg.num_streams, cfg.host_threads = max(nslots, 24), 8, 8
     ctx = C.c_void_p()
     assert stub.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
     descs = [synth.picture_for_plan(pl, W, H, seed=513, tool_flags=TOOLS | abi.TOOL_LMCS | abi.TOOL_LMCS_CSCALE, log2_ctu=6, p_intra=0.15) for pl in plans]
     pics = [d.c() for d in descs]
     stub.vvt_set_delay(150)
@@ -1383,9 +1344,6 @@ def test_collocated_motion_host_stage(stub):
     """VVR_TOOL_COL_MOTION against the stand-in runtime (no DMVR kernel runs): what vvr_read_col_motion returns is the motion field at every second
     4x4 unit in both directions, for odd numbers of 4x4 columns / rows too, with worker threads and through prepared handles; asking without a
     motion field is refused"""
-    stub.vvr_read_col_motion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
     for (W, H, threads) in ((200, 136, 0), (416, 240, 2)):
         plans, nslots = stream.ra_plan(3, gop=2, seed_poc0_is_external=False)
         cfg = abi.Config()
@@ -1430,9 +1388,6 @@ def test_pictures_pass_pictures_that_are_still_being_prepared(stub):
     assert nslots >= len(plans)                         # no slot is reused: every stamp can be read at the end
     descs = [synth.picture_for_plan(pl, W, H, seed=531, tool_flags=TOOLS, p_intra=0.1) for pl in plans]
     pics = [d.c() for d in descs]
-    stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_wait.argtypes = [C.c_void_p, C.c_int]
-    stub.vvr_read_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     buf = (C.c_int * 60000)()
     results = {}
     stub.vvt_overtakes.restype = C.c_ulonglong
@@ -1640,8 +1595,6 @@ def test_read_picture_lays_the_rows_out_at_the_callers_strides(stub, threads):
     """vvr_read_picture: every plane of the picture in a slot at the picture's own size (vvr_slot_picture_size), rows at the caller's strides and
     nothing written past them; staging buffers allocated with the context (vvr_config.read_buffers) or with the first call"""
     W, H = 96, 64
-    stub.vvr_write_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-    stub.vvr_read_picture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     rng = np.random.default_rng(5)
     for pre in (0, 2):
         cfg = abi.Config()

@@ -35,14 +35,7 @@ CASES = [
 
 @pytest.fixture(scope="module")
 def stub():
-    L = C.CDLL(build_stub())
-    L.vvr_last_error.restype = C.c_char_p
-    L.vvr_last_error.argtypes = [C.c_void_p]
-    L.vvr_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.vvr_free_prepared.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_destroy.argtypes = [C.c_void_p]
-    L.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_wait.argtypes = [C.c_void_p, C.c_int]
+    L = abi.bind(C.CDLL(build_stub()))
     L.vvt_intra_tables.argtypes = [C.c_void_p] + [C.c_void_p] * 4
     L.vvt_take_h2d_hash.restype = C.c_ulonglong
     L.vvt_sizeof.restype = C.c_size_t

@@ -99,7 +99,6 @@ def test_tables_are_not_uploaded(stub):
         cnt, nbytes = C.c_size_t(), C.c_size_t()
         stub.vvt_take_h2d(C.byref(cnt), C.byref(nbytes))
         pic = d.c()
-        stub.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
         assert stub.vvr_submit(ctx.ctx, C.byref(pic)) >= 0, stub.vvr_last_error(ctx.ctx).decode()
         assert stub.vvr_sync(ctx.ctx) == abi.VVR_OK
         stub.vvt_take_h2d(C.byref(cnt), C.byref(nbytes))

@@ -16,10 +16,10 @@ import pytest
 import colour_transform_ref as X
 import interleaved_ref
 import lut3d_ref as U
+import output_support as SUP
 import resample_ref as R
 import rescale_ref
 import rgb_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_interleaved_host as I
 import test_output_lut3d_host as LH
@@ -32,7 +32,7 @@ from vvdec_amd import abi
 pytestmark = T.pytestmark
 need_ref = pytest.mark.skipif(not rescale_ref.available(), reason="oracle/_ref/libvvdec.so not built (needs /root/reference at build time)")
 W, H_ = N.W, N.H_
-FILL = Q.FILL
+FILL = SUP.FILL
 NORM = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))      # the ImageNet normalisation
 WHO = b"vvr_output_submit_batch: "
 # the geometries of the issue's table: (window size, output size or None, origins)
@@ -42,18 +42,6 @@ WIDE = ((160, 64), (132, 40), [(0, 0), (48, 16), (24, 8)])                    # 
 TWO_LAUNCH = ((64, 80), (16, 8), [(0, 0), (144, 0), (70, 0)])                 # h > 4 * out_h for luma and chroma: the two-launch form
 DCTIF = ((64, 32), (96, 48), [(0, 0), (144, 48), (34, 10)])
 LIMIT = ((16, 16), None, [(16 * (i % 13), 16 * (i // 13 % 5)) for i in range(256)])      # 65 places on a grid, wrapping with duplicates
-
-
-def bind(L):
-    return abi.bind_output_batch(LH.bind(TH.bind(N.bind(S.bind(L)))))
-
-
-def _lib():
-    return bind(H._lib())
-
-
-def _write(L):
-    return lambda ctx, slot, p: H.write_picture(L, ctx, slot, p)
 
 
 def picture(bd, seed=0):
@@ -462,9 +450,9 @@ def check_refusals(L, mk_ctx, write, bd=10):
 # ---- the tests on the stand-in runtime
 
 def _run(check, bd, *args, **kw):
-    L = _lib()
-    ctx = H._ctx(L, W, H_, bd, 1)
-    check(L, ctx, _write(L), *args, **kw)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, bd, 1)
+    check(L, ctx, SUP.writer(L), *args, **kw)
     L.vvr_destroy(ctx)
 
 
@@ -510,13 +498,13 @@ def test_eight_batches_in_flight():
 
 
 def test_refusals_leave_the_ring_alone():
-    L = _lib()
-    check_refusals(L, lambda: H._ctx(L, W, H_, 10, 1), _write(L))
+    L = SUP.stub_lib()
+    check_refusals(L, lambda: SUP.make_ctx(L, W, H_, 10, 1), SUP.writer(L))
 
 
 def test_python_mirror():
     import vvdec_amd
     assert C.sizeof(abi.OutputBatch) == 40 and abi.OutputBatch.count.offset == 4 and abi.OutputBatch.origin.offset == 8 and abi.OutputBatch.batch_stride_bytes.offset == 16
     assert abi.OUT_BATCH_MAX == 256 and len(abi.OUT_BATCH_FORMATS) == 10 and all(f in abi.OUT_FORMATS for f in abi.OUT_BATCH_FORMATS)
-    assert "vvr_output_submit_batch" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(_lib(), "vvr_output_submit_batch")
+    assert "vvr_output_submit_batch" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(SUP.stub_lib(), "vvr_output_submit_batch")
     assert hasattr(vvdec_amd.Reconstructor, "output_submit_batch")

@@ -9,12 +9,10 @@ import numpy as np
 import pytest
 
 import compare_ref
-import test_film_grain_host as H
+import output_support as SUP
 import test_host_glue as T
-import test_output_hash_host as XH
 import test_output_queue_host as Q
-import test_output_stats_host as X
-from vvdec_amd import abi, stream, synth
+from vvdec_amd import abi, synth
 
 pytestmark = T.pytestmark
 W, H_ = 208, 80           # four blocks across with a 16-wide last one, two down with a 16-high last one
@@ -22,51 +20,20 @@ WINDOWS = [(0, 0, 208, 80), (8, 4, 200, 64), (2, 2, 70, 34), (0, 0, 2, 2)]
 W400, H400 = 136, 8
 WINDOWS_400 = [(0, 0, 136, 8), (3, 1, 131, 5), (129, 7, 7, 1), (5, 2, 1, 1)]
 CONTENTS = ["identical", "last", "random", "partial", "two_hits"]
-FILL = 0xaa
 
 
-def bind(L):
-    X.bind(L)
-    Q.bind(L)
-    L.vvr_compare_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_compare_psnr.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
-    L.vvr_device_alloc.restype = C.c_void_p
-    L.vvr_device_alloc.argtypes = [C.c_void_p, C.c_size_t]
-    L.vvr_device_free.restype = None
-    L.vvr_device_free.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_device_register.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.vvr_device_unregister.argtypes = [C.c_void_p, C.c_void_p]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
+def picture_size(cf):
+    return (W, H_) if cf else (W400, H400)
 
 
 def windows(nc):
     return WINDOWS if nc == 3 else WINDOWS_400
 
 
-def padded(plane, dt, pad):
-    """the plane as a view of an array whose rows are `pad` elements longer (filled with a value the plane never compares equal to by accident)"""
-    a = np.full((plane.shape[0], plane.shape[1] + pad), 0x5b, dt)
-    a[:, :plane.shape[1]] = plane
-    return a[:, :plane.shape[1]]
-
-
-def forms(ref):
-    """the forms a reference is given in: 2-byte samples at strides above the row; 1-byte samples, when its values fit, at an odd byte stride"""
-    out = [("16-bit", [padded(p, np.uint16, k) for p, k in zip(ref, (3, 5, 7))])]
-    if all(int(p.max()) <= 255 for p in ref):
-        out.append(("8-bit", [padded(p, np.uint8, 1 if p.shape[1] % 2 == 0 else 2) for p in ref]))
-        assert all(p.strides[0] % 2 == 1 for p in out[-1][1])
-    return out
-
-
 def submit(L, ctx, slot, win, ref, with_map=True, job=None, blocking=True, bps=2):
     """one vvr_compare_submit -> (ticket or error, (the vvr_frame_compare, the map) vvr_output_wait writes, both filled with 0xaa)"""
     raw = abi.FrameCompare()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     blocks = np.full(abi.compare_map_shape(win), 0xaaaaaaaa, np.uint32) if with_map else None
     req = abi.compare_request(slot, job, win, ref, raw, blocks, blocking, bps)
     return L.vvr_compare_submit(ctx, C.byref(req)), (raw, blocks)
@@ -156,7 +123,7 @@ def check_contents(L, ctx, planes, bd):
                 if kind == "two_hits" and want["differing"][0]:
                     met_two_hits += 1
                     assert (want["first_x"][0], want["first_y"][0]) == (69, 0) and want["differing"][0] == 2 and want["map"][0, 0] >= 1 and want["map"][0, 1] >= 1
-                for name, given in [f for f in forms(ref) if (f[0] == "8-bit") == (bps == 1)]:
+                for name, given in [f for f in SUP.forms(ref) if (f[0] == "8-bit") == (bps == 1)]:
                     same(queued(L, ctx, 0, win, given), want, win, bd, "%s at %d bits, window %r, %s reference" % (kind, bd, win, name))
         # (without a map nothing but the result is written)
         want = compare_ref.compare(part, part)
@@ -176,7 +143,7 @@ def check_all_ones_reference(L, ctx, write, nc, bd):
         want = compare_ref.compare(part, ref)
         assert want["sse"][:nc] == [n * 4294836225 for n in want["samples"][:nc]] and want["sad"][:nc] == [n * 65535 for n in want["samples"][:nc]]
         assert win[2] * win[3] < 4096 or want["sse"][0] > 1 << 32
-        for name, given in forms(ref):
+        for name, given in SUP.forms(ref):
             same(queued(L, ctx, 0, win, given), want, win, bd, "zeros against 0xffff, window %r" % (win,))
 
 
@@ -216,75 +183,27 @@ def check_outside(L, ctx, write, planes, bd):
     write(ctx, 0, planes)
 
 
-def check_ref_slot(L, ctx, write, a, b, bd):
-    """two pictures in slots 0 and 1 compared in both directions at every window"""
-    write(ctx, 0, a)
-    write(ctx, 1, b)
-    for win in windows(len(a)):
-        pa, pb = compare_ref.window_planes(a, win), compare_ref.window_planes(b, win)
-        same(queued(L, ctx, 0, win, 1), compare_ref.compare(pa, pb), win, bd, "slot 0 against slot 1, window %r" % (win,))
-        same(queued(L, ctx, 1, win, 0), compare_ref.compare(pb, pa), win, bd, "slot 1 against slot 0, window %r" % (win,))
+def ref_slot_case(L, ctx, slot, ref_slot, win, ps, pr, bd, what):
+    same(queued(L, ctx, slot, win, ref_slot), compare_ref.compare(ps, pr), win, bd, what)
 
 
-def launches(L, ctx):
-    arr = (abi.KernelStat * 32)()
-    L.vvr_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    n = L.vvr_get_stats(ctx, arr, 32)
-    return {arr[i].name.decode(): arr[i].launches for i in range(n)}
-
-
-def statistics(L, ctx, planes, bd):
+def stats_case(L, ctx, planes, bd):
     """vvr_get_stats: one k_output_compare and one k_output_compare_sum per request; none with statistics off"""
-    L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
-    assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
-    win = (8, 4, 200, 64)
+    win = SUP.RING_WIN
     part = compare_ref.window_planes(planes, win)
     ref = reference("random", np.random.default_rng(5), part, bd)
-    for k in range(3):
-        same(queued(L, ctx, 0, win, forms(ref)[0][1]), compare_ref.compare(part, ref), win, bd, "with statistics on")
-    got = launches(L, ctx)
-    assert got == {"k_output_compare": 3, "k_output_compare_sum": 3}, got
-    assert L.vvr_enable_stats(ctx, 0) == abi.VVR_OK
-    queued(L, ctx, 0, win, forms(ref)[0][1])
-    assert not launches(L, ctx)
+
+    def request():
+        same(queued(L, ctx, 0, win, SUP.forms(ref)[0][1]), compare_ref.compare(part, ref), win, bd, "with statistics on")
+
+    def verify(got):
+        assert got == {"k_output_compare": 3, "k_output_compare_sum": 3}, got
+    return [request] * 3, verify, request
 
 
-def tickets_and_the_ring(L, ctx, planes, bd, ext):
-    """eight requests of the four kinds in flight, the ninth of any kind is VVR_ERR_BUSY; vvr_sync retires nothing; ext: a stream of the caller's
-    for vvr_output_stream_wait"""
-    win = (8, 4, 200, 64)
-    part = compare_ref.window_planes(planes, win)
-    ref = reference("random", np.random.default_rng(6), part, bd)
-    want = compare_ref.compare(part, ref)
-    given = forms(ref)[0][1]
-    assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
-    flight = []
-    for n in range(8):
-        if n % 4 == 0:
-            flight.append(("compare",) + submit(L, ctx, 0, win, given))
-        elif n % 4 == 1:
-            flight.append(("out",) + Q.submit(L, ctx, 0, win, "planar16", 3))
-        elif n % 4 == 2:
-            flight.append(("hash",) + XH.submit(L, ctx, 0, abi.HASH_CRC, 3))
-        else:
-            flight.append(("stats",) + X.submit(L, ctx, 0, win, abi.STATS_LUMA))
-    assert all(t >= 2 for _, t, _ in flight) and len(set(t for _, t, _ in flight)) == 8, [t for _, t, _ in flight]
-    for t9 in (submit(L, ctx, 0, win, given)[0], Q.submit(L, ctx, 0, win, "planar16", 3)[0], XH.submit(L, ctx, 0, abi.HASH_CRC, 3)[0], X.submit(L, ctx, 0, win, abi.STATS_LUMA)[0]):
-        assert t9 == abi.VVR_ERR_BUSY and b"in flight" in L.vvr_last_error(ctx)
-    assert L.vvr_sync(ctx) == abi.VVR_OK
-    assert all(L.vvr_output_test(ctx, t) == abi.VVR_OK for _, t, _ in flight)
-    for n, (kind, t, keep) in enumerate(flight):
-        if kind == "compare":
-            assert L.vvr_output_stream_wait(ctx, t, ext) == abi.VVR_OK
-            same(collect(L, ctx, t, keep), want, win, bd, "request %d of eight" % n)
-        elif kind == "out":
-            assert all(np.array_equal(a, b) for a, b in zip(Q.collect(L, ctx, t, keep), part))
-        elif kind == "hash":
-            XH.collect(L, ctx, t, keep)
-        else:
-            X.same(X.collect(L, ctx, t, keep), X.expected(part, bd, abi.STATS_LUMA), win, bd, abi.STATS_LUMA, "request %d of eight" % n)
-    t = flight[0][1]
-    assert L.vvr_output_wait(ctx, t) == abi.VVR_ERR_PARAMETER and b"ticket" in L.vvr_last_error(ctx)
+def ring_request(L, ctx, planes, win, part, ref, bd):
+    given, want = SUP.forms(ref)[0][1], compare_ref.compare(part, ref)
+    return lambda: submit(L, ctx, 0, win, given), lambda t, keep, what: same(collect(L, ctx, t, keep), want, win, bd, what)
 
 
 def c_psnr(L, raw, peak):
@@ -307,81 +226,58 @@ def check_psnr(L, raw, want, bd, what):
 def test_the_structs_mirror_the_header(tmp_path):
     """sizeof / offsetof of the structs as gcc sees include/vvr.h == their ctypes mirrors (vvr_abi_sizeof does not list them: they are guarded by
     their own struct_size)"""
-    import os
-    import subprocess
     names = [("vvr_frame_compare", abi.FrameCompare), ("vvr_compare_request", abi.CompareRequest)]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vvr.h"', 'int main(void){']
-    want = []
-    for cname, mirror in names:
-        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
-        lines += ['printf("%%zu\\n", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_]
-        want += [C.sizeof(mirror)] + [getattr(mirror, f[0]).offset for f in mirror._fields_]
-    lines.append("return 0;}")
-    (tmp_path / "probe.c").write_text("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(os.path.dirname(T.HERE), "include"), str(tmp_path / "probe.c"), "-o", str(tmp_path / "probe")])
-    assert [int(v) for v in subprocess.check_output([str(tmp_path / "probe")]).split()] == want
+    SUP.assert_mirrors(tmp_path, names)
     assert C.sizeof(abi.FrameCompare) == 176
-    L = _lib()
+    L = SUP.stub_lib()
     assert L.vvr_abi_sizeof(18) == 0      # (no new index)
-
-
-def _ctx_with(L, bd, cf, seed):
-    w, h = (W, H_) if cf else (W400, H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    H.write_picture(L, ctx, 0, planes)
-    return ctx, planes
-
-
-def _write(L):
-    return lambda ctx, slot, p: H.write_picture(L, ctx, slot, p)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_window(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1200 + bd + cf)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1200 + bd + cf)
     check_contents(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_sums_that_need_64_bits(bd, cf):
-    L = _lib()
-    ctx, _ = _ctx_with(L, bd, cf, 1210)
-    check_all_ones_reference(L, ctx, _write(L), 3 if cf else 1, bd)
+    L = SUP.stub_lib()
+    ctx, _ = SUP.ctx_with(L, picture_size(cf), bd, cf, 1210)
+    check_all_ones_reference(L, ctx, SUP.writer(L), 3 if cf else 1, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_differences_just_outside_the_window_are_not_reported(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1220)
-    check_outside(L, ctx, _write(L), planes, bd)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1220)
+    check_outside(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_second_slot_as_the_reference(bd, cf):
-    L = _lib()
-    ctx, a = _ctx_with(L, bd, cf, 1230)
+    L = SUP.stub_lib()
+    ctx, a = SUP.ctx_with(L, picture_size(cf), bd, cf, 1230)
     b = [np.where(np.random.default_rng(1231 + c).random(p.shape) < 0.3, p ^ 5, p).astype(np.uint16) for c, p in enumerate(a)]
-    check_ref_slot(L, ctx, _write(L), a, b, bd)
+    SUP.check_ref_slot("compare", L, ctx, SUP.writer(L), a, b, bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_slot_holding_values_above_the_bit_depth_is_read_as_it_lies():
     """16-bit words written from outside: nothing is masked on either side"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(1240)
     planes = [rng.integers(0, 1 << 16, (H_ >> s, W >> s), dtype=np.uint16) for s in (0, 1, 1)]
-    ctx = H._ctx(L, W, H_, 10, 1)
-    H.write_picture(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
+    SUP.write_picture(L, ctx, 0, planes)
     for win in WINDOWS:
         part = compare_ref.window_planes(planes, win)
         for bps in (2, 1):
             ref = reference("random", rng, part, 10, bps)
-            for name, given in [f for f in forms(ref) if (f[0] == "8-bit") == (bps == 1)]:
+            for name, given in [f for f in SUP.forms(ref) if (f[0] == "8-bit") == (bps == 1)]:
                 same(queued(L, ctx, 0, win, given), compare_ref.compare(part, ref), win, 10, "16-bit words in the slot, window %r, %s" % (win, name))
     L.vvr_destroy(ctx)
 
@@ -389,10 +285,9 @@ def test_a_slot_holding_values_above_the_bit_depth_is_read_as_it_lies():
 def test_the_three_homes_of_a_reference():
     """pageable memory (overwritten right after vvr_compare_submit: the result is that of the planes as they were), memory of vvr_host_alloc (no
     staging copy), memory of vvr_device_alloc and a registered range (read in place: nothing is copied to the device)"""
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1250)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1250)
     rng = np.random.default_rng(1251)
-    L.vvt_take_h2d.argtypes = [C.c_void_p, C.c_void_p]
 
     def h2d():
         n, b = C.c_size_t(), C.c_size_t()
@@ -407,7 +302,7 @@ def test_the_three_homes_of_a_reference():
             dt = np.uint16 if bps == 2 else np.uint8
             what = "window %r, %d bytes per sample" % (win, bps)
             # pageable: one copy through the entry's staging; the caller's planes are free at once
-            given = [padded(p, dt, 3) for p in ref]
+            given = [SUP.padded(p, dt, 3) for p in ref]
             h2d()
             t, keep = submit(L, ctx, 0, win, given)
             assert t >= 2 and h2d()[0] == 1
@@ -470,40 +365,30 @@ def test_the_three_homes_of_a_reference():
 
 
 def test_tickets_are_shared_with_the_other_kinds_of_request():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1260)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1260)
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
-    tickets_and_the_ring(L, ctx, planes, 10, ext)
+    SUP.tickets_and_the_ring("compare", L, ctx, planes, 10, ext)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernels():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1261)
-    statistics(L, ctx, planes, 10)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1261)
+    SUP.statistics("compare", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_ring_alone():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1262)
-    H.write_picture(L, ctx, 1, planes)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1262)
+    SUP.write_picture(L, ctx, 1, planes)
     win = (8, 4, 200, 64)
     part = [np.ascontiguousarray(p) for p in compare_ref.window_planes(planes, win)]
     keep = abi.FrameCompare()
 
-    def refused(text, c=ctx, ref=part, w_=win, **kw):
-        req = abi.compare_request(0, None, w_, ref, keep)
-        for k, v in kw.items():
-            if k.startswith("stride"):
-                req.ref_stride_bytes[int(k[6:])] = v
-            elif k.startswith("plane"):
-                req.ref[int(k[5:])] = v
-            else:
-                setattr(req, k, v)
-        rc = L.vvr_compare_submit(c, C.byref(req))
-        assert rc == abi.VVR_ERR_PARAMETER and text in L.vvr_last_error(c) and b"vvr_compare_submit" in L.vvr_last_error(c), (kw, rc, L.vvr_last_error(c))
+    refused = SUP.refuser(L, ctx, "compare", lambda ref=part, w_=win: abi.compare_request(0, None, w_, ref, keep))
 
     refused(b"struct_size", struct_size=C.sizeof(abi.CompareRequest) - 8)
     refused(b"no such slot", slot=7)
@@ -525,33 +410,22 @@ def test_refusals_leave_the_ring_alone():
     refused(b"different sizes", ref=1)
     assert L.vvr_slot_picture_size(ctx, 1, W, H_) == abi.VVR_OK
     # a 4:0:0 context: odd windows are fine, planes 1 and 2 are not looked at
-    ctx400, p400 = _ctx_with(L, 8, 0, 1263)
+    ctx400, p400 = SUP.ctx_with(L, picture_size(0), 8, 0, 1263)
     refused(b"outside the picture", c=ctx400, ref=[p400[0]], w_=(0, 0, W400 + 1, 4))
     L.vvr_destroy(ctx400)
     assert L.vvr_compare_submit(None, None) == abi.VVR_ERR_PARAMETER and L.vvr_compare_submit(ctx, None) == abi.VVR_ERR_PARAMETER
     # the ring is untouched: eight requests still fit
-    flight = [submit(L, ctx, 0, win, part if n % 2 else 1) for n in range(8)]
-    assert all(t >= 2 for t, _ in flight) and len(set(t for t, _ in flight)) == 8, [t for t, _ in flight]
     want = compare_ref.compare(part, part)
-    for t, got in flight:
-        same(collect(L, ctx, t, got), want, win, 10, "behind the refusals")
+    SUP.eight_still_fit(L, ctx, lambda n: submit(L, ctx, 0, win, part if n % 2 else 1), lambda t, got: same(collect(L, ctx, t, got), want, win, 10, "behind the refusals"))
     L.vvr_destroy(ctx)
-
-
-def _stream(L, seed=611, **kw):
-    Wd, Hd = 256, 128
-    plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = Q._stream_ctx(L, Wd, Hd, nslots)
-    descs = [synth.picture_for_plan(pl, Wd, Hd, seed=seed, tool_flags=T.TOOLS, **kw) for pl in plans]
-    return ctx, plans, descs, (0, 0, Wd, Hd)
 
 
 def test_not_ready_while_the_picture_is_with_its_worker():
     """the host stage of a B picture is held on its worker thread (and the stand-in is slowed down): a request without `blocking` comes back
     VVR_NOT_READY and takes no ring entry - for its job, and with ref_slot for any picture still with the workers; with `blocking` it is accepted
     and delivers the comparison of the pictures"""
-    L = _lib()
-    ctx, plans, descs, win = _stream(L)
+    L = SUP.stub_lib()
+    ctx, plans, descs, win = SUP.small_stream(L)
     pics = [d.c() for d in descs[:2]]
     j0 = L.vvr_submit(ctx, C.byref(pics[0]))
     assert j0 >= 0
@@ -582,26 +456,21 @@ def test_not_ready_while_the_picture_is_with_its_worker():
 
 
 def test_a_failed_picture_fails_its_request():
-    L = _lib()
-    ctx, plans, descs, win = _stream(L, p_intra=0.3)
-    pics = [d.c() for d in descs]
-    ref = [np.zeros((win[3] >> s, win[2] >> s), np.uint16) for s in (0, 1, 1)]
-    j0 = L.vvr_submit(ctx, C.byref(pics[0]))
-    t0, k0 = submit(L, ctx, plans[0].slot, win, ref, job=j0)
-    assert t0 >= 2
-    L.vvt_fail_leaf_waits(1)
-    j1 = L.vvr_submit(ctx, C.byref(pics[1]))                         # its intra stage gives up a wait: the job fails when it completes
-    t1, k1 = submit(L, ctx, plans[1].slot, win, ref, job=j1)
-    assert t1 >= 2
-    assert L.vvr_output_test(ctx, t1) == abi.VVR_ERR_DEVICE and L.vvr_output_test(ctx, t0) == abi.VVR_OK
-    assert L.vvr_output_wait(ctx, t1) == abi.VVR_ERR_DEVICE and b"waited for its neighbours" in L.vvr_last_error(ctx)
-    assert bytes(k1[0]) == bytes([FILL]) * C.sizeof(abi.FrameCompare) and (k1[1] == 0xaaaaaaaa).all(), "a request that failed writes nothing"
-    assert collect(L, ctx, t0, k0)[0].samples[0] == win[2] * win[3]
-    t2, k2 = submit(L, ctx, plans[1].slot, win, plans[0].slot, job=j1)      # asked again after the failure is known: accepted, fails the same way
-    assert t2 >= 2 and L.vvr_output_wait(ctx, t2) == abi.VVR_ERR_DEVICE and bytes(k2[0]) == bytes([FILL]) * C.sizeof(abi.FrameCompare) and (k2[1] == 0xaaaaaaaa).all()
-    L.vvt_fail_leaf_waits(0)
-    assert L.vvr_wait(ctx, j1) == abi.VVR_ERR_DEVICE and L.vvr_wait(ctx, j0) == abi.VVR_OK
-    L.vvr_destroy(ctx)
+    SUP.a_failed_picture_fails_its_request("compare", SUP.stub_lib())
+
+
+def zeros_or_slot(win, ref_slot):
+    """the reference of a request on a picture of a stream: planes of zeros, or the slot"""
+    return [np.zeros((win[3] >> s, win[2] >> s), np.uint16) for s in (0, 1, 1)] if ref_slot is None else ref_slot
+
+
+def delivered(keep):
+    assert keep[0].samples[0] == 256 * 128
+
+
+SUP.register("compare", b"vvr_compare_submit", ring_request, stats=stats_case, ref_slot=ref_slot_case, cases=windows,
+             failing=lambda L, ctx, slot, win, job, ref_slot: submit(L, ctx, slot, win, zeros_or_slot(win, ref_slot), job=job),
+             untouched=lambda keep: bytes(keep[0]) == bytes([SUP.FILL]) * C.sizeof(abi.FrameCompare) and (keep[1] == 0xaaaaaaaa).all(), delivered=delivered)
 
 
 def test_later_pictures_into_either_slot_wait_for_the_request():
@@ -609,10 +478,9 @@ def test_later_pictures_into_either_slot_wait_for_the_request():
     request's own event is recorded behind its first kernel; an I picture that later overwrites `slot`, and one that overwrites `ref_slot`, each
     wait for exactly that event on their lane"""
     from dataclasses import replace
-    L = _lib()
-    ctx, plans, descs, win = _stream(L)
+    L = SUP.stub_lib()
+    ctx, plans, descs, win = SUP.small_stream(L)
     Wd, Hd = win[2], win[3]
-    L.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
     s0 = plans[0].slot
@@ -653,7 +521,7 @@ HAND = [("luma only differs", 10, 3, [100, 25, 25], [7, 0, 0]),
 
 @pytest.mark.parametrize("what,bd,nc,samples,sse", HAND)
 def test_psnr_on_sums_built_by_hand(what, bd, nc, samples, sse):
-    L = _lib()
+    L = SUP.stub_lib()
     raw = abi.FrameCompare()
     raw.struct_size, raw.bit_depth, raw.num_components = C.sizeof(abi.FrameCompare), bd, nc
     for c in range(3):
@@ -671,13 +539,13 @@ def test_psnr_on_sums_built_by_hand(what, bd, nc, samples, sse):
 
 
 def test_psnr_of_a_request_and_its_refusals():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1270)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1270)
     win = WINDOWS[0]
     part = compare_ref.window_planes(planes, win)
     ref = reference("random", np.random.default_rng(1271), part, 10)
     want = compare_ref.compare(part, ref)
-    raw, _ = queued(L, ctx, 0, win, forms(ref)[0][1])
+    raw, _ = queued(L, ctx, 0, win, SUP.forms(ref)[0][1])
     check_psnr(L, raw, want, 10, "a request")
     L.vvr_destroy(ctx)
     untouched = [-1.] * 4

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import film_grain_ref
+import output_support as SUP
 import refdrv
 import test_film_grain_host as H
 import test_host_glue as T
@@ -24,26 +25,6 @@ SHAPES = [(200, 72, 1, 10),       # luma rows: 25 chunks, chroma 100 x 36: 12 ch
           (136, 8, 0, 10),        # one component, eight rows
           (200, 72, 1, 9),
           (7680, 16, 1, 10)]      # 122 880 bits per luma row: the CRC's exponent exceeds 2^16; rows of more than one pass (960 chunks)
-
-
-def bind(L):
-    Q.bind(L)
-    L.vvr_hash_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_picture_hash.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.vvr_slot_picture_size.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
-
-
-def random_planes(rng, W, H_, bd, cf):
-    """random over the full range, with 0 and 2^bd - 1 in every plane"""
-    planes = [rng.integers(0, 1 << bd, (H_ >> s, W >> s), dtype=np.uint16) for s in ((0, 1, 1) if cf else (0,))]
-    for p in planes:
-        p[0, 0], p[-1, -1] = 0, (1 << bd) - 1
-    return planes
 
 
 def submit(L, ctx, slot, method, nc, job=None, expected=None, digest=True, blocking=True):
@@ -150,14 +131,7 @@ def crc_by_rows(plane, bit_depth):
 def test_the_request_mirrors_the_header(tmp_path):
     """sizeof / offsetof of vvr_hash_request as gcc sees include/vvr.h == abi.HashRequest (vvr_abi_sizeof does not list the struct: it is guarded by
     its own struct_size)"""
-    import os
-    import subprocess
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vvr.h"', 'int main(void){', 'printf("%zu\\n", sizeof(vvr_hash_request));']
-    lines += ['printf("%%zu\\n", offsetof(vvr_hash_request, %s));' % f[0] for f in abi.HashRequest._fields_] + ["return 0;}"]
-    (tmp_path / "probe.c").write_text("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(os.path.dirname(T.HERE), "include"), str(tmp_path / "probe.c"), "-o", str(tmp_path / "probe")])
-    got = [int(v) for v in subprocess.check_output([str(tmp_path / "probe")]).split()]
-    assert got == [C.sizeof(abi.HashRequest)] + [getattr(abi.HashRequest, f[0]).offset for f in abi.HashRequest._fields_]
+    SUP.assert_mirrors(tmp_path, [("vvr_hash_request", abi.HashRequest)])
 
 
 def test_lane_structure_of_the_kernels_replayed_on_the_cpu(tmp_path):
@@ -175,41 +149,41 @@ def test_lane_structure_of_the_kernels_replayed_on_the_cpu(tmp_path):
 def test_crc_by_rows_is_refdrvs_crc():
     rng = np.random.default_rng(40)
     for W, H_, cf, bd in SHAPES:
-        for p in random_planes(rng, W, H_, bd, cf):
+        for p in SUP.random_planes(rng, W, H_, bd, cf):
             assert crc_by_rows(p, bd) == refdrv.hash_crc(p, bd), (W, H_, bd, p.shape)
 
 
 @pytest.mark.parametrize("W,H_,cf,bd", SHAPES)
 def test_digests_and_verification(W, H_, cf, bd):
-    L = _lib()
-    planes = random_planes(np.random.default_rng(W + H_ + bd), W, H_, bd, cf)
-    ctx = H._ctx(L, W, H_, bd, cf)
-    H.write_picture(L, ctx, 1, planes)
+    L = SUP.stub_lib()
+    planes = SUP.random_planes(np.random.default_rng(W + H_ + bd), W, H_, bd, cf)
+    ctx = SUP.make_ctx(L, W, H_, bd, cf)
+    SUP.write_picture(L, ctx, 1, planes)
     check_slot(L, ctx, 1, planes, bd, "%dx%d" % (W, H_))
     L.vvr_destroy(ctx)
 
 
 def small_picture_in_a_larger_slot(L, ctx, write, rng):
     """a 256x144 context, slot 1 declared to hold a 200x72 picture: the picture is hashed, not the slot"""
-    full = random_planes(rng, 256, 144, 10, 1)
+    full = SUP.random_planes(rng, 256, 144, 10, 1)
     write(ctx, 1, full)
     assert L.vvr_slot_picture_size(ctx, 1, 200, 72) == abi.VVR_OK
     check_slot(L, ctx, 1, [full[0][:72, :200], full[1][:36, :100], full[2][:36, :100]], 10, "200x72 in 256x144")
 
 
 def test_the_picture_in_the_slot_is_hashed_not_the_slot():
-    L = _lib()
-    ctx = H._ctx(L, 256, 144, 10, 1)
-    small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(41))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, 256, 144, 10, 1)
+    small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(41))
     L.vvr_destroy(ctx)
 
 
 def test_refusals_tickets_and_the_ring():
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(42)
-    ctx = H._ctx(L, 448, 160, 10, 1)
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
     picture = film_grain_ref.grain_picture(rng, 448, 160, 10, 1)
-    H.write_picture(L, ctx, 0, picture)
+    SUP.write_picture(L, ctx, 0, picture)
     digest, word = (C.c_uint8 * 48)(), C.c_uint32()
 
     def refused(text, **kw):
@@ -258,46 +232,43 @@ def test_refusals_tickets_and_the_ring():
     L.vvr_destroy(ctx)
 
 
-def launches(L, ctx):
-    """vvr_get_stats -> {kernel name: launches}"""
-    arr = (abi.KernelStat * 24)()
-    L.vvr_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    n = L.vvr_get_stats(ctx, arr, 24)
-    return {arr[i].name.decode(): arr[i].launches for i in range(n)}
-
-
-def statistics(L, ctx, planes, bd):
+def stats_case(L, ctx, planes, bd):
     """one launch of k_hash_rows and of k_hash_combine per CRC / checksum request, none for MD5; vvr_picture_hash counts its per-plane launches as
     k_plane_hash_rows (CRC, checksum) and gives the same digests with statistics on"""
     nc = len(planes)
-    L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
-    assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
-    for method in (abi.HASH_CRC, abi.HASH_CHECKSUM, abi.HASH_MD5, abi.HASH_CRC, abi.HASH_CRC):
-        assert queued(L, ctx, 0, method, nc)[0] == refdrv.picture_hash(planes, bd, method)
-    for method in METHODS:
-        assert sync_hash(L, ctx, 0, method, nc) == refdrv.picture_hash(planes, bd, method)
-    stats = launches(L, ctx)
-    assert stats.get("k_hash_rows") == 4 and stats.get("k_hash_combine") == 4 and stats.get("k_plane_hash_rows") == 2 * nc, stats
-    assert L.vvr_enable_stats(ctx, 0) == abi.VVR_OK
-    assert sync_hash(L, ctx, 0, abi.HASH_CRC, nc) == refdrv.picture_hash(planes, bd, abi.HASH_CRC) and not launches(L, ctx)
+
+    def request(method):
+        def run():
+            assert queued(L, ctx, 0, method, nc)[0] == refdrv.picture_hash(planes, bd, method)
+        return run
+
+    def synchronous(method):
+        def run():
+            assert sync_hash(L, ctx, 0, method, nc) == refdrv.picture_hash(planes, bd, method)
+        return run
+
+    def verify(stats):
+        assert stats.get("k_hash_rows") == 4 and stats.get("k_hash_combine") == 4 and stats.get("k_plane_hash_rows") == 2 * nc, stats
+    return ([request(m) for m in (abi.HASH_CRC, abi.HASH_CHECKSUM, abi.HASH_MD5, abi.HASH_CRC, abi.HASH_CRC)] + [synchronous(m) for m in METHODS],
+            verify, synchronous(abi.HASH_CRC))
 
 
 def test_statistics_name_the_kernels():
-    L = _lib()
-    planes = random_planes(np.random.default_rng(5), 200, 72, 10, 1)
-    ctx = H._ctx(L, 200, 72, 10, 1)
-    H.write_picture(L, ctx, 0, planes)
-    statistics(L, ctx, planes, 10)
+    L = SUP.stub_lib()
+    planes = SUP.random_planes(np.random.default_rng(5), 200, 72, 10, 1)
+    ctx = SUP.make_ctx(L, 200, 72, 10, 1)
+    SUP.write_picture(L, ctx, 0, planes)
+    SUP.statistics("hash", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_hash_requests_leave_the_seed_chain_alone():
     """a grained planar16 request gives the same bytes before and after a run of hash requests started from the same seed: neither the chain's state
     nor the bank moved"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(43)
-    ctx = H._ctx(L, 448, 160, 10, 1)
-    H.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
+    SUP.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
     bank = abi.film_grain_bank(**H._bank(rng))
     assert L.vvr_set_film_grain(ctx, C.addressof(bank)) == abi.VVR_OK
     assert L.vvr_set_film_grain_seed(ctx, 77) == abi.VVR_OK
@@ -318,10 +289,10 @@ def test_requests_are_ordered_on_the_device_not_on_the_host():
     return of vvr_hash_submit the output stream waits for the picture's completion event and records the request's two events, nothing else; the
     picture that overwrites the slot afterwards waits for the first of them on its lane.  Without `blocking`, a picture still with the workers
     gives VVR_NOT_READY and the same request is accepted later."""
-    L = _lib()
+    L = SUP.stub_lib()
     W, H_ = 256, 128
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = Q._stream_ctx(L, W, H_, nslots)
+    ctx = SUP.stream_ctx(L, W, H_, nslots)
     descs = [synth.picture_for_plan(pl, W, H_, seed=611, tool_flags=T.TOOLS) for pl in plans]      # (the records live in the descriptions)
     pics = [d.c() for d in descs]
     L.vvt_set_delay(20000)
@@ -349,7 +320,6 @@ def test_requests_are_ordered_on_the_device_not_on_the_host():
     pa = again.c()
     j1 = L.vvr_submit(ctx, C.byref(pa))         # a second picture into the same slot: its lane waits for the request's read event
     assert j1 >= 0
-    L.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
     assert L.vvr_stream_wait_job(ctx, j1, ext, 1) == abi.VVR_OK      # (handed to the device)
@@ -366,10 +336,10 @@ def test_requests_are_ordered_on_the_device_not_on_the_host():
 def test_not_ready_while_the_picture_is_with_its_worker():
     """the host stage of a B picture is held for 0.3 s on its worker thread (the stand-in runtime's switch): a request without `blocking` made at
     once must come back VVR_NOT_READY, takes no ring entry, and the same request with `blocking` is accepted and delivers"""
-    L = _lib()
+    L = SUP.stub_lib()
     W, H_ = 256, 128
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = Q._stream_ctx(L, W, H_, nslots)
+    ctx = SUP.stream_ctx(L, W, H_, nslots)
     descs = [synth.picture_for_plan(pl, W, H_, seed=611, tool_flags=T.TOOLS) for pl in plans[:2]]
     pics = [d.c() for d in descs]
     assert plans[1].slice_type != abi.SLICE_I
@@ -393,25 +363,28 @@ def test_not_ready_while_the_picture_is_with_its_worker():
 
 
 def test_a_failed_picture_fails_its_request():
-    L = _lib()
-    W, H_ = 256, 128
-    plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = Q._stream_ctx(L, W, H_, nslots)
-    descs = [synth.picture_for_plan(pl, W, H_, seed=611, tool_flags=T.TOOLS, p_intra=0.3) for pl in plans]
-    pics = [d.c() for d in descs]
-    j0 = L.vvr_submit(ctx, C.byref(pics[0]))
-    t0, k0 = submit(L, ctx, plans[0].slot, abi.HASH_CHECKSUM, 3, job=j0)
-    assert t0 >= 2
-    L.vvt_fail_leaf_waits(1)
-    j1 = L.vvr_submit(ctx, C.byref(pics[1]))                         # its intra stage gives up a wait: the job fails when it completes
-    t1, k1 = submit(L, ctx, plans[1].slot, abi.HASH_CHECKSUM, 3, job=j1, expected=[b"\0" * 4] * 3)
-    assert t1 >= 2
-    assert L.vvr_output_test(ctx, t1) == abi.VVR_ERR_DEVICE and L.vvr_output_test(ctx, t0) == abi.VVR_OK
-    assert L.vvr_output_wait(ctx, t1) == abi.VVR_ERR_DEVICE and b"waited for its neighbours" in L.vvr_last_error(ctx)
-    assert k1[1].value == 0xaaaaaaaa and bytes(k1[0]) == b"\xaa" * 12, "a request that failed writes neither digest nor mismatch"
-    collect(L, ctx, t0, k0)
-    t2, k2 = submit(L, ctx, plans[1].slot, abi.HASH_MD5, 3, job=j1)      # asked again after the failure is known: accepted, fails the same way
-    assert t2 >= 2 and L.vvr_output_wait(ctx, t2) == abi.VVR_ERR_DEVICE
-    L.vvt_fail_leaf_waits(0)
-    assert L.vvr_wait(ctx, j1) == abi.VVR_ERR_DEVICE and L.vvr_wait(ctx, j0) == abi.VVR_OK
-    L.vvr_destroy(ctx)
+    SUP.a_failed_picture_fails_its_request("hash", SUP.stub_lib())
+
+
+def ring_request(L, ctx, planes, win, part, ref, bd):
+    def finish(t, keep, what):
+        assert collect(L, ctx, t, keep)[0] == refdrv.picture_hash(planes, bd, abi.HASH_CRC), what
+    return lambda: submit(L, ctx, 0, abi.HASH_CRC, len(planes)), finish
+
+
+def failing(L, ctx, slot, win, job, ref_slot):
+    """the checksum with digests to verify against; asked again: MD5"""
+    if ref_slot is not None:
+        return submit(L, ctx, slot, abi.HASH_MD5, 3, job=job)
+    return submit(L, ctx, slot, abi.HASH_CHECKSUM, 3, job=job, expected=[b"\0" * 4] * 3)
+
+
+def untouched(keep):
+    return (keep[1] is None or keep[1].value == 0xaaaaaaaa) and bytes(keep[0]) == b"\xaa" * len(keep[0])
+
+
+def delivered(keep):
+    assert bytes(keep[0]) != b"\xaa" * len(keep[0]) and keep[1].value != 0xaaaaaaaa, "neither digest nor mismatch"
+
+
+SUP.register("hash", b"vvr_hash_submit", ring_request, stats=stats_case, failing=failing, untouched=untouched, delivered=delivered)

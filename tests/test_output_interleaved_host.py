@@ -12,7 +12,7 @@ import pytest
 
 import colour_transform_ref as X
 import interleaved_ref as IR
-import test_film_grain_host as H
+import output_support as SUP
 import test_host_glue as T
 import test_output_queue_host as Q
 import test_output_semiplanar_host as S
@@ -20,7 +20,7 @@ import test_output_transform_host as XH
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
-FILL = Q.FILL
+FILL = SUP.FILL
 W, H_ = S.W, S.H_
 FORMATS = IR.FORMATS
 # one entry per instantiation of the store: bgra8 runs rgba8's code with R and B exchanged, bgr24 rgb24's
@@ -33,18 +33,8 @@ NORMS = [None, ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225)), ((-3.5, 0., 1000.
 XFORMS = ("none", "pq", "table")
 
 
-def bind(L):
-    XH.bind(L)
-    L.vvr_set_output_normalisation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
-
-
 def _setup(L, bd, seed):
-    return S.setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
+    return S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
 
 
 def transforms(bd, seed=400):
@@ -216,7 +206,7 @@ def test_the_cases_meet_every_instantiation_of_the_store():
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_every_instantiation_straight_from_the_slot(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 410 + bd)
     check_straight(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -224,7 +214,7 @@ def test_every_instantiation_straight_from_the_slot(bd):
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_interleaved_matrix(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 420 + bd)
     check_matrix(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -232,7 +222,7 @@ def test_interleaved_matrix(bd):
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_against_the_planar_formats(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 430 + bd)
     check_against_the_planar_formats(L, ctx, bd, None)
     check_against_the_planar_formats(L, ctx, bd, transforms(bd)["pq"])
@@ -279,14 +269,14 @@ def check_normalisation_state(L, ctx, picture, bd):
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_normalisation_is_taken_when_the_request_is_submitted(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 440 + bd)
     check_normalisation_state(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_ring_and_the_seed_chain_alone():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, 10, 450)
     win = (8, 4, 200, 64)
 
@@ -306,7 +296,7 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
     assert L.vvr_set_film_grain_seed(ctx, 9) == abi.VVR_OK
     first = Q.queued(L, ctx, 0, win, "planar16", 3, grain=True)
     assert L.vvr_set_film_grain_seed(ctx, 9) == abi.VVR_OK
-    ctx400 = H._ctx(L, W, H_, 8, 0)
+    ctx400 = SUP.make_ctx(L, W, H_, 8, 0)
     assert L.vvr_set_output_colour(ctx400, 1, 0) == abi.VVR_OK
     for fmt in FORMATS:
         refused(b"RGB output of a 4:0:0 context: there is no chroma to convert", c=ctx400, fmt=fmt)
@@ -365,7 +355,7 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
 def test_python_mirror_of_the_formats_and_the_symbol():
     import vvdec_amd
     assert {name: abi.OUT_FORMATS[name] for name in FORMATS} == IR.CODES == {"rgbf32": 36, "rgba8": 48, "bgra8": 49, "rgb24": 50, "bgr24": 51, "rgb10a2": 52, "rgba16f": 53}
-    assert "vvr_set_output_normalisation" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(_lib(), "vvr_set_output_normalisation")
+    assert "vvr_set_output_normalisation" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(SUP.stub_lib(), "vvr_set_output_normalisation")
     win = (2, 6, 202, 38)
     assert abi.output_plane_shapes(win, "rgba8", None, 3) == ([(38, 808)], np.uint8) and abi.output_plane_shapes(win, "bgra8", (134, 26), 3) == ([(26, 536)], np.uint8)
     assert abi.output_plane_shapes(win, "rgb24", None, 3) == ([(38, 606)], np.uint8) and abi.output_plane_shapes(win, "bgr24", None, 3) == ([(38, 606)], np.uint8)

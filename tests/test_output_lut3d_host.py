@@ -12,6 +12,7 @@ import pytest
 import colour_transform_ref as X
 import interleaved_ref as IR
 import lut3d_ref as U
+import output_support as SUP
 import rgb_ref
 import test_film_grain_host as H
 import test_host_glue as T
@@ -30,19 +31,8 @@ COLOUR = TH.COLOUR
 same = I.same_planes
 
 
-def bind(L):
-    I.bind(L)
-    L.vvr_set_output_lut3d.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.vvr_output_lut3d_preset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
-
-
 def _setup(L, bd, seed):
-    return S.setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
+    return S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
 
 
 def set_lut(L, ctx, lut):
@@ -247,7 +237,7 @@ def test_the_random_groups_meet_every_instantiation_of_the_kernel():
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_random_luts(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 720 + bd)
     check_random(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -255,7 +245,7 @@ def test_random_luts(bd):
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_extremes(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 730 + bd)
     check_extremes(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -263,22 +253,22 @@ def test_extremes(bd):
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_ties_need_no_rule(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 740 + bd)
-    check_grey(L, ctx, picture, bd, lambda c, slot, p: H.write_picture(L, c, slot, p))
+    check_grey(L, ctx, picture, bd, lambda c, slot, p: SUP.write_picture(L, c, slot, p))
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_snapshot_and_scope(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 750 + bd)
     check_snapshot_and_scope(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_lut_in_force():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, 10, 760)
     win, col = (8, 4, 200, 64), (True, False)
     assert L.vvr_set_output_colour(ctx, *COLOUR) == abi.VVR_OK
@@ -294,7 +284,7 @@ def test_refusals_leave_the_lut_in_force():
         same(Q.queued(L, ctx, 0, win, "rgb16", 3, col=col), want, "after a refused call (n = %d)" % n)
     assert L.vvr_set_output_lut3d(None, 0, None) == abi.VVR_ERR_PARAMETER
     # a LUT in a 4:0:0 context: set, and never met - RGB is refused there as ever
-    ctx400 = H._ctx(L, W, H_, 8, 0)
+    ctx400 = SUP.make_ctx(L, W, H_, 8, 0)
     set_lut(L, ctx400, first)
     assert L.vvr_set_output_colour(ctx400, 1, 0) == abi.VVR_OK
     shapes, dt = abi.output_plane_shapes(win, "rgb16", None, 3)
@@ -319,7 +309,7 @@ def c_preset(L, n, tc, cp, target, src, dst):
 def test_preset_nodes_are_the_standards_formulas(tc, cp, target, src, dst):
     """every node equal to the float64 restatement, or 1 apart where a pow of libm and of numpy differ in their last place and a rounding flips;
     fewer than 1 % of the nodes may differ at all"""
-    L = _lib()
+    L = SUP.stub_lib()
     rc, nodes = c_preset(L, 17, tc, cp, target, src, dst)
     assert rc == abi.VVR_OK
     ref = U.preset(17, tc, cp, target, src, dst)
@@ -342,12 +332,12 @@ def test_pq_preset_on_the_grey_axis_is_the_per_channel_preset():
       BT.2020 primaries to sRGB: within 1 in the 8-bit codes rgb8 stores, and in 16-bit codes within 21.25 + 0.5 - the distance of the
       per-channel integer pipeline from the real-valued one that test_output_transform_host.ACCURACY asserts (the Q14 matrix and the
       interpolated OETF), plus the rounding of the node, which is the real-valued result rounded once"""
-    L = _lib()
+    L = SUP.stub_lib()
     e = np.minimum(np.arange(17) * 4096, 65535) / 65535
     lin = np.floor(X.linear_light(e, 16, 1000., 100.) * 65535 + 0.5).astype(np.int64)      # stage 1 at the nodes' values
     for cp, target, bounds in ((1, X.TO_LINEAR, {"rgb16": 1}), (9, X.TO_SRGB, {"rgb8": 1, "rgb16": TH.ACCURACY[(16, 9, X.TO_SRGB)][1] + 0.5})):
         rc, nodes = c_preset(L, 17, 16, cp, target, 1000., 100.)
-        rc2, t = TH.c_preset(TH.bind(L), 16, cp, target, (1000., 100.), 10)
+        rc2, t = TH.c_preset(L, 16, cp, target, (1000., 100.), 10)
         assert rc == abi.VVR_OK and rc2 == abi.VVR_OK
         _, m, enc = abi.output_transform_arrays(t)
         per_channel = X.stages([np.arange(17)] * 3, lin, m, enc)
@@ -360,7 +350,7 @@ def test_pq_preset_on_the_grey_axis_is_the_per_channel_preset():
 
 
 def test_preset_refuses_what_it_does_not_know():
-    L = _lib()
+    L = SUP.stub_lib()
     for args in [(16, 16, 9, 0, 1000., 100.), (0, 16, 9, 0, 1000., 100.), (129, 16, 9, 0, 1000., 100.), (17, 1, 9, 0, 1000., 100.), (17, 14, 9, 0, 1000., 100.),
                  (17, 16, 5, 0, 1000., 100.), (17, 18, 12, 0, 1000., 100.), (17, 16, 9, 3, 1000., 100.), (17, 16, 9, -1, 1000., 100.), (17, 16, 9, 0, 0., 100.),
                  (17, 16, 9, 0, 1000., -1.), (17, 16, 9, 0, 10001., 100.), (17, 16, 9, 0, float("nan"), 100.), (17, 18, 9, 0, 1000., 0.), (17, 18, 9, 0, 1000., float("nan"))]:
@@ -407,7 +397,7 @@ def test_cube_written_by_hand(tmp_path):
 def test_python_mirror_of_the_symbols():
     import vvdec_amd
     assert "vvr_set_output_lut3d" in vvdec_amd.EXPORTED_SYMBOLS and "vvr_output_lut3d_preset" in vvdec_amd.EXPORTED_SYMBOLS
-    assert hasattr(_lib(), "vvr_set_output_lut3d") and hasattr(_lib(), "vvr_output_lut3d_preset")
+    assert hasattr(SUP.stub_lib(), "vvr_set_output_lut3d") and hasattr(SUP.stub_lib(), "vvr_output_lut3d_preset")
     assert hasattr(vvdec_amd.Reconstructor, "set_output_lut3d") and abi.LUT3D_SIZES == U.SIZES
     assert abi.lut3d_nodes(17, np.zeros((17, 17, 17, 3))).shape == (3 * 17 ** 3,)
     with pytest.raises(AssertionError):

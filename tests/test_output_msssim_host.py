@@ -10,14 +10,11 @@ import pytest
 
 import compare_ref
 import msssim_ref
+import output_support as SUP
 import ssim_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_compare_host as XC
-import test_output_hash_host as XH
-import test_output_queue_host as Q
 import test_output_ssim_host as XS
-import test_output_stats_host as X
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
@@ -29,20 +26,12 @@ CASES = [((0, 0, 304, 272), 5),       # luma 304, 152, 76, 38, 19 by 272, 136, 6
 W400, H400 = 136, 40
 CASES_400 = [((0, 0, 136, 40), 3), ((3, 0, 131, 40), 3)]      # the plain case; an odd origin: the sample-by-sample class at level 0, the wide class below
 CONTENTS = ["identical", "noise", "inverse", "random", "seam", "dead_tail", "deepest"]
-FILL = 0xaa
 ONE = 1 << 24
 FIELDS = ("width", "height", "windows_x", "windows_y", "windows", "sum_cs", "sum_v")
 
 
-def bind(L):
-    XS.bind(L)
-    L.vvr_msssim_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_compare_msssim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
+def picture_size(cf):
+    return (W, H_) if cf else (W400, H400)
 
 
 def cases(nc):
@@ -52,7 +41,7 @@ def cases(nc):
 def submit(L, ctx, slot, win, ref, scales, job=None, blocking=True, bps=2):
     """one vvr_msssim_submit -> (ticket or error, the vvr_frame_msssim vvr_output_wait writes, filled with 0xaa)"""
     raw = abi.FrameMsssim()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     req = abi.msssim_request(slot, job, win, ref, raw, scales, blocking, bps)
     return L.vvr_msssim_submit(ctx, C.byref(req)), raw
 
@@ -175,7 +164,7 @@ def check_contents(L, ctx, planes, bd):
                     at = np.argwhere(xs != ys)
                     assert at.tolist() == [[(xs.shape[0] - 8) // 4 * 4 + 7, (xs.shape[1] - 8) // 4 * 4 + 7]], (what, c, at)
                     assert want["sum_v"][scales - 1][c] != same_want["sum_v"][scales - 1][c] and want["sum_cs"][scales - 1][c] != same_want["sum_cs"][scales - 1][c], what
-            for name, given in XC.forms(ref):
+            for name, given in SUP.forms(ref):
                 met["eight_bit"] += name == "8-bit"
                 raw = queued(L, ctx, 0, win, given, scales)
                 same(raw, want, win, bd, what + ", %s reference" % name)
@@ -184,7 +173,7 @@ def check_contents(L, ctx, planes, bd):
                 if kind == "inverse":
                     assert got == [0.] * 4, what
         # consequence (a): one scale is an SSIM request of the same window, through the library
-        given = XC.forms(reference("noise", rng, part, bd, 1))[0][1]
+        given = SUP.forms(reference("noise", rng, part, bd, 1))[0][1]
         one = queued(L, ctx, 0, win, given, 1)
         ssim = XS.queued(L, ctx, 0, win, given, with_map=False)[0]
         assert [int(v) for v in one.sum_v[0]] == [int(v) for v in ssim.sum] and [int(v) for v in one.windows[0]] == [int(v) for v in ssim.windows], win
@@ -206,109 +195,46 @@ def check_words_above_the_bit_depth(L, ctx, write, planes, bd):
             want = msssim_ref.msssim(held, ref, bd, scales)
             assert want == msssim_ref.msssim([np.minimum(p, top) for p in held], [np.minimum(p, top) for p in ref], bd, scales)
             assert want != msssim_ref.msssim(held, ref, bd, scales, clamp_first=False)
-            same(queued(L, ctx, 0, win, XC.forms(ref)[0][1], scales), want, win, bd, "words above the bit depth in the slot, window %r" % (win,))
+            same(queued(L, ctx, 0, win, SUP.forms(ref)[0][1], scales), want, win, bd, "words above the bit depth in the slot, window %r" % (win,))
     write(ctx, 0, planes)
 
 
-def check_ref_slot(L, ctx, write, a, b, bd):
-    """two pictures in slots 0 and 1, MS-SSIM in both directions at every window"""
-    write(ctx, 0, a)
-    write(ctx, 1, b)
-    for win, scales in cases(len(a)):
-        pa, pb = compare_ref.window_planes(a, win), compare_ref.window_planes(b, win)
-        same(queued(L, ctx, 0, win, 1, scales), msssim_ref.msssim(pa, pb, bd, scales), win, bd, "slot 0 against slot 1, window %r" % (win,))
-        same(queued(L, ctx, 1, win, 0, scales), msssim_ref.msssim(pb, pa, bd, scales), win, bd, "slot 1 against slot 0, window %r" % (win,))
+def ref_slot_case(L, ctx, slot, ref_slot, case, ps, pr, bd, what):
+    win, scales = case
+    same(queued(L, ctx, slot, win, ref_slot, scales), msssim_ref.msssim(ps, pr, bd, scales), win, bd, what)
 
 
-noisy = XS.noisy
-RING_WIN, RING_SCALES = (8, 4, 200, 64), 2
+RING_WIN, RING_SCALES = SUP.RING_WIN, 2
 
 
-def statistics(L, ctx, planes, bd):
+def stats_case(L, ctx, planes, bd):
     """vvr_get_stats: `scales` k_output_msssim and one k_output_msssim_sum per request; none with statistics off"""
-    L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
-    assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
-    total = 0
-    for win, scales in CASES[:2] + CASES[3:]:
-        part = compare_ref.window_planes(planes, win)
-        ref = noisy(part, bd, 5)
-        same(queued(L, ctx, 0, win, XC.forms(ref)[0][1], scales), msssim_ref.msssim(part, ref, bd, scales), win, bd, "with statistics on")
-        total += scales
-    got = XC.launches(L, ctx)
-    assert total == 12 and got == {"k_output_msssim": 12, "k_output_msssim_sum": 3}, got
-    assert L.vvr_enable_stats(ctx, 0) == abi.VVR_OK
-    queued(L, ctx, 0, win, XC.forms(ref)[0][1], scales)
-    assert not XC.launches(L, ctx)
+    asked = CASES[:2] + CASES[3:]
+    assert sum(scales for _, scales in asked) == 12
+
+    def request(win, scales):
+        def run():
+            part = compare_ref.window_planes(planes, win)
+            ref = SUP.noisy(part, bd, 5)
+            same(queued(L, ctx, 0, win, SUP.forms(ref)[0][1], scales), msssim_ref.msssim(part, ref, bd, scales), win, bd, "with statistics on")
+        return run
+
+    def verify(got):
+        assert got == {"k_output_msssim": 12, "k_output_msssim_sum": 3}, got
+    return [request(*case) for case in asked], verify, request(*asked[-1])
 
 
-def tickets_and_the_ring(L, ctx, planes, bd, ext):
-    """eight requests of the six kinds in flight, the ninth of any kind is VVR_ERR_BUSY; vvr_sync retires nothing; ext: a stream of the caller's
-    for vvr_output_stream_wait"""
-    win, scales = RING_WIN, RING_SCALES
-    part = compare_ref.window_planes(planes, win)
-    ref = noisy(part, bd, 6)
-    want, want_ssim, want_cmp = msssim_ref.msssim(part, ref, bd, scales), ssim_ref.ssim(part, ref, bd), compare_ref.compare(part, ref)
-    given = XC.forms(ref)[0][1]
-    assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
-    flight = []
-    for n in range(8):
-        if n % 6 == 0:
-            flight.append(("msssim",) + submit(L, ctx, 0, win, given, scales))
-        elif n % 6 == 1:
-            flight.append(("out",) + Q.submit(L, ctx, 0, win, "planar16", 3))
-        elif n % 6 == 2:
-            flight.append(("hash",) + XH.submit(L, ctx, 0, abi.HASH_CRC, 3))
-        elif n % 6 == 3:
-            flight.append(("stats",) + X.submit(L, ctx, 0, win, abi.STATS_LUMA))
-        elif n % 6 == 4:
-            flight.append(("compare",) + XC.submit(L, ctx, 0, win, given))
-        else:
-            flight.append(("ssim",) + XS.submit(L, ctx, 0, win, given))
-    assert all(t >= 2 for _, t, _ in flight) and len(set(t for _, t, _ in flight)) == 8, [t for _, t, _ in flight]
-    assert [k for k, _, _ in flight].count("msssim") == 2
-    for t9 in (submit(L, ctx, 0, win, given, scales)[0], Q.submit(L, ctx, 0, win, "planar16", 3)[0], XH.submit(L, ctx, 0, abi.HASH_CRC, 3)[0],
-               X.submit(L, ctx, 0, win, abi.STATS_LUMA)[0], XC.submit(L, ctx, 0, win, given)[0], XS.submit(L, ctx, 0, win, given)[0]):
-        assert t9 == abi.VVR_ERR_BUSY and b"in flight" in L.vvr_last_error(ctx)
-    assert b"vvr_ssim_submit" in L.vvr_last_error(ctx)
-    assert submit(L, ctx, 0, win, given, scales)[0] == abi.VVR_ERR_BUSY and b"vvr_msssim_submit" in L.vvr_last_error(ctx)
-    assert L.vvr_sync(ctx) == abi.VVR_OK
-    assert all(L.vvr_output_test(ctx, t) == abi.VVR_OK for _, t, _ in flight)
-    for n, (kind, t, keep) in enumerate(flight):
-        if kind == "msssim":
-            assert L.vvr_output_stream_wait(ctx, t, ext) == abi.VVR_OK
-            same(collect(L, ctx, t, keep), want, win, bd, "request %d of eight" % n)
-        elif kind == "ssim":
-            XS.same(XS.collect(L, ctx, t, keep), want_ssim, win, bd, "request %d of eight" % n)
-        elif kind == "compare":
-            XC.same(XC.collect(L, ctx, t, keep), want_cmp, win, bd, "request %d of eight" % n)
-        elif kind == "out":
-            assert all(np.array_equal(a, b) for a, b in zip(Q.collect(L, ctx, t, keep), part))
-        elif kind == "hash":
-            XH.collect(L, ctx, t, keep)
-        else:
-            X.same(X.collect(L, ctx, t, keep), X.expected(part, bd, abi.STATS_LUMA), win, bd, abi.STATS_LUMA, "request %d of eight" % n)
-    t = flight[0][1]
-    assert L.vvr_output_wait(ctx, t) == abi.VVR_ERR_PARAMETER and b"ticket" in L.vvr_last_error(ctx)
+def ring_request(L, ctx, planes, win, part, ref, bd):
+    given, want = SUP.forms(ref)[0][1], msssim_ref.msssim(part, ref, bd, RING_SCALES)
+    return lambda: submit(L, ctx, 0, win, given, RING_SCALES), lambda t, keep, what: same(collect(L, ctx, t, keep), want, win, bd, what)
 
 
 # ---- tests
 
 def test_the_structs_mirror_the_header(tmp_path):
     """sizeof / offsetof of the structs as gcc sees include/vvr.h == their ctypes mirrors; explicit pads only: the size is the sum of the fields"""
-    import os
-    import subprocess
     names = [("vvr_frame_msssim", abi.FrameMsssim), ("vvr_msssim_request", abi.MsssimRequest)]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vvr.h"', 'int main(void){']
-    want = []
-    for cname, mirror in names:
-        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
-        lines += ['printf("%%zu\\n", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_]
-        want += [C.sizeof(mirror)] + [getattr(mirror, f[0]).offset for f in mirror._fields_]
-    lines.append('printf("%d\\n", VVR_MSSSIM_MAX_SCALES);')
-    lines.append("return 0;}")
-    (tmp_path / "probe.c").write_text("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(os.path.dirname(T.HERE), "include"), str(tmp_path / "probe.c"), "-o", str(tmp_path / "probe")])
-    assert [int(v) for v in subprocess.check_output([str(tmp_path / "probe")]).split()] == want + [abi.MSSSIM_MAX_SCALES]
+    SUP.assert_mirrors(tmp_path, names, [("VVR_MSSSIM_MAX_SCALES", abi.MSSSIM_MAX_SCALES)])
     for mirror in (abi.FrameMsssim, abi.MsssimRequest):
         assert C.sizeof(mirror) == sum(C.sizeof(f[1]) for f in mirror._fields_) and C.sizeof(mirror) % 8 == 0
     assert C.sizeof(abi.FrameMsssim) == 616 and C.sizeof(abi.MsssimRequest) == 96 == C.sizeof(abi.SsimRequest) - 8
@@ -319,7 +245,7 @@ def test_python_mirror_and_symbols():
     import vvdec_amd
     assert "vvr_msssim_submit" in vvdec_amd.EXPORTED_SYMBOLS and "vvr_compare_msssim" in vvdec_amd.EXPORTED_SYMBOLS
     assert hasattr(vvdec_amd.Reconstructor, "msssim")
-    L = _lib()
+    L = SUP.stub_lib()
     assert L.vvr_abi_sizeof(18) == 0      # (no new index)
     assert abi.VVR_ABI_VERSION == 5
     assert abi.MSSSIM_WEIGHTS == msssim_ref.WEIGHTS
@@ -358,77 +284,55 @@ def test_the_restatement_agrees_with_textbook_terms_per_level():
     assert worst[0] > 0 and worst[1] > 0
 
 
-def _ctx_with(L, bd, cf, seed):
-    w, h = (W, H_) if cf else (W400, H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    H.write_picture(L, ctx, 0, planes)
-    return ctx, planes
-
-
-def _write(L):
-    return lambda ctx, slot, p: H.write_picture(L, ctx, slot, p)
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_window(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1530 + bd + cf)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1530 + bd + cf)
     check_contents(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_slot_holding_words_above_the_bit_depth_is_clamped(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1540)
-    check_words_above_the_bit_depth(L, ctx, _write(L), planes, bd)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1540)
+    check_words_above_the_bit_depth(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_second_slot_as_the_reference(bd, cf):
-    L = _lib()
-    ctx, a = _ctx_with(L, bd, cf, 1550)
-    check_ref_slot(L, ctx, _write(L), a, noisy(a, bd, 1551), bd)
+    L = SUP.stub_lib()
+    ctx, a = SUP.ctx_with(L, picture_size(cf), bd, cf, 1550)
+    SUP.check_ref_slot("msssim", L, ctx, SUP.writer(L), a, SUP.noisy(a, bd, 1551), bd)
     L.vvr_destroy(ctx)
 
 
 def test_tickets_are_shared_with_the_other_kinds_of_request():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1560)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1560)
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
-    tickets_and_the_ring(L, ctx, planes, 10, ext)
+    SUP.tickets_and_the_ring("msssim", L, ctx, planes, 10, ext)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernels():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1561)
-    statistics(L, ctx, planes, 10)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1561)
+    SUP.statistics("msssim", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_ring_alone():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1562)
-    H.write_picture(L, ctx, 1, planes)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1562)
+    SUP.write_picture(L, ctx, 1, planes)
     win, scales = RING_WIN, RING_SCALES
     part = [np.ascontiguousarray(p) for p in compare_ref.window_planes(planes, win)]
     keep = abi.FrameMsssim()
 
-    def refused(text, c=ctx, ref=part, w_=win, n=scales, **kw):
-        req = abi.msssim_request(0, None, w_, ref, keep, n)
-        for k, v in kw.items():
-            if k.startswith("stride"):
-                req.ref_stride_bytes[int(k[6:])] = v
-            elif k.startswith("plane"):
-                req.ref[int(k[5:])] = v
-            else:
-                setattr(req, k, v)
-        rc = L.vvr_msssim_submit(c, C.byref(req))
-        assert rc == abi.VVR_ERR_PARAMETER and text in L.vvr_last_error(c) and b"vvr_msssim_submit" in L.vvr_last_error(c), (kw, rc, L.vvr_last_error(c))
+    refused = SUP.refuser(L, ctx, "msssim", lambda ref=part, w_=win, n=scales: abi.msssim_request(0, None, w_, ref, keep, n))
 
     # scales outside 1 .. 5
     for n in (0, 6, 255):
@@ -469,42 +373,29 @@ def test_refusals_leave_the_ring_alone():
     refused(b"different sizes", ref=1)
     assert L.vvr_slot_picture_size(ctx, 1, W, H_) == abi.VVR_OK
     # a 4:0:0 context: odd windows are fine, planes 1 and 2 are not looked at; 128 x 32 takes three scales, not four
-    ctx400, p400 = _ctx_with(L, 8, 0, 1563)
+    ctx400, p400 = SUP.ctx_with(L, picture_size(0), 8, 0, 1563)
     refused(b"outside the picture", c=ctx400, ref=[p400[0]], w_=(0, 0, W400 + 1, 8), n=1)
     refused(b"no 8 x 8 window at the last level", c=ctx400, ref=[p400[0]], w_=(0, 0, W400, 40), n=4)
     refused(b"no 8 x 8 window at the last level", c=ctx400, ref=[p400[0]], w_=(0, 0, W400, 7), n=1)
     L.vvr_destroy(ctx400)
     assert L.vvr_msssim_submit(None, None) == abi.VVR_ERR_PARAMETER and L.vvr_msssim_submit(ctx, None) == abi.VVR_ERR_PARAMETER
     # the ring is untouched: eight requests still fit
-    flight = [submit(L, ctx, 0, win, part if n % 2 else 1, scales) for n in range(8)]
-    assert all(t >= 2 for t, _ in flight) and len(set(t for t, _ in flight)) == 8, [t for t, _ in flight]
     want = msssim_ref.msssim(part, part, 10, scales)
-    for t, got in flight:
-        same(collect(L, ctx, t, got), want, win, 10, "behind the refusals")
+    SUP.eight_still_fit(L, ctx, lambda n: submit(L, ctx, 0, win, part if n % 2 else 1, scales), lambda t, got: same(collect(L, ctx, t, got), want, win, 10, "behind the refusals"))
     L.vvr_destroy(ctx)
 
 
 def test_a_failed_picture_fails_its_request():
-    L = _lib()
-    ctx, plans, descs, win = XC._stream(L, p_intra=0.3)
-    pics = [d.c() for d in descs]
-    ref = [np.zeros((win[3] >> s, win[2] >> s), np.uint16) for s in (0, 1, 1)]
-    j0 = L.vvr_submit(ctx, C.byref(pics[0]))
-    t0, k0 = submit(L, ctx, plans[0].slot, win, ref, 4, job=j0)
-    assert t0 >= 2
-    L.vvt_fail_leaf_waits(1)
-    j1 = L.vvr_submit(ctx, C.byref(pics[1]))                         # its intra stage gives up a wait: the job fails when it completes
-    t1, k1 = submit(L, ctx, plans[1].slot, win, ref, 4, job=j1)
-    assert t1 >= 2
-    assert L.vvr_output_test(ctx, t1) == abi.VVR_ERR_DEVICE and L.vvr_output_test(ctx, t0) == abi.VVR_OK
-    assert L.vvr_output_wait(ctx, t1) == abi.VVR_ERR_DEVICE and b"waited for its neighbours" in L.vvr_last_error(ctx)
-    assert bytes(k1) == bytes([FILL]) * C.sizeof(abi.FrameMsssim), "a request that failed writes nothing"
-    assert fields(collect(L, ctx, t0, k0))["windows"][:4] == [[63 * 31, 31 * 15, 31 * 15], [31 * 15, 15 * 7, 15 * 7], [15 * 7, 7 * 3, 7 * 3], [7 * 3, 3, 3]]
-    t2, k2 = submit(L, ctx, plans[1].slot, win, plans[0].slot, 4, job=j1)      # asked again after the failure is known: accepted, fails the same way
-    assert t2 >= 2 and L.vvr_output_wait(ctx, t2) == abi.VVR_ERR_DEVICE and bytes(k2) == bytes([FILL]) * C.sizeof(abi.FrameMsssim)
-    L.vvt_fail_leaf_waits(0)
-    assert L.vvr_wait(ctx, j1) == abi.VVR_ERR_DEVICE and L.vvr_wait(ctx, j0) == abi.VVR_OK
-    L.vvr_destroy(ctx)
+    SUP.a_failed_picture_fails_its_request("msssim", SUP.stub_lib())
+
+
+def delivered(raw):
+    assert fields(raw)["windows"][:4] == [[63 * 31, 31 * 15, 31 * 15], [31 * 15, 15 * 7, 15 * 7], [15 * 7, 7 * 3, 7 * 3], [7 * 3, 3, 3]]
+
+
+SUP.register("msssim", b"vvr_msssim_submit", ring_request, stats=stats_case, ref_slot=ref_slot_case, cases=cases,
+             failing=lambda L, ctx, slot, win, job, ref_slot: submit(L, ctx, slot, win, XC.zeros_or_slot(win, ref_slot), 4, job=job),
+             untouched=lambda raw: bytes(raw) == bytes([SUP.FILL]) * C.sizeof(abi.FrameMsssim), delivered=delivered)
 
 
 def _hand(bd, nc, scales, windows, sum_cs, sum_v):
@@ -518,7 +409,7 @@ def _hand(bd, nc, scales, windows, sum_cs, sum_v):
 
 
 def test_msssim_on_sums_built_by_hand():
-    L = _lib()
+    L = SUP.stub_lib()
     # every component, three scales: sum_v of the first levels and sum_cs of the last are not looked at
     windows = [[100, 25, 25], [25, 6, 6], [6, 1, 1]]
     cs = [[90 * ONE, 25 * ONE - 7, 20 * ONE], [20 * ONE, 5 * ONE, 3 * ONE], [-(1 << 40), -(1 << 40), -(1 << 40)]]
@@ -551,13 +442,13 @@ def test_msssim_on_sums_built_by_hand():
 
 
 def test_msssim_of_a_request_and_its_refusals():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1570)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1570)
     win, scales = CASES[1]
     part = compare_ref.window_planes(planes, win)
-    ref = noisy(part, 10, 1571)
+    ref = SUP.noisy(part, 10, 1571)
     want = msssim_ref.msssim(part, ref, 10, scales)
-    raw = queued(L, ctx, 0, win, XC.forms(ref)[0][1], scales)
+    raw = queued(L, ctx, 0, win, SUP.forms(ref)[0][1], scales)
     rc, got = c_value(L, raw)
     assert rc == abi.VVR_OK and close(got, msssim_ref.value(want)) and all(0 < v < 1 for v in got)
     mine = [0.1, 0.2, 0.3, 0.25, 0.15]

@@ -13,8 +13,8 @@ import pytest
 
 import film_grain_ref
 import narrow_ref
+import output_support as SUP
 import yuv_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_queue_host as Q
 import test_output_rgb_host as RGB
@@ -22,7 +22,7 @@ import test_output_semiplanar_host as S
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
-FILL = Q.FILL
+FILL = SUP.FILL
 W, H_ = S.W, S.H_
 # luma rows of 18 and chroma rows of 9 samples: shorter than two of a lane's pieces of 16 and of odd length, so one piece spans three rows and
 # the column parity of its samples flips inside it
@@ -33,14 +33,6 @@ FORMATS = narrow_ref.FORMATS
 MODES = narrow_ref.MODES
 REFUSAL = b"8-bit output of a stream with more than 8 bits per sample (only narrowing of 8-bit content, vvdecimpl.cpp:853)"
 ALL_STRIDES = tuple((s, m) for s in S.STRIDES for m in (0, 2))
-
-
-def bind(L):
-    return abi.bind_output_narrowing(RGB.bind(L))
-
-
-def _lib():
-    return bind(H._lib())
 
 
 def set_mode(L, ctx, mode, phase=0):
@@ -249,12 +241,8 @@ def check_out_of_range_words(L, ctx, write, rng):
                     assert (p == 255).all(), (fmt, mode, phase, win)
 
 
-def _write(L):
-    return lambda ctx, slot, p: H.write_picture(L, ctx, slot, p)
-
-
 def _setup(L, bd, seed):
-    return S.setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, plant(p, bd)), np.random.default_rng(seed), bd)
+    return S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, plant(p, bd)), np.random.default_rng(seed), bd)
 
 
 # ---- the restatement and the cases
@@ -308,7 +296,7 @@ def test_the_picture_holds_the_ends_of_the_range(bd):
 
 @pytest.mark.parametrize("bd", [10, 9])
 def test_every_instantiation_straight_from_the_slot(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 182 + bd)
     assert_planted(picture, bd)
     check_instantiations(L, ctx, picture, bd)
@@ -317,7 +305,7 @@ def test_every_instantiation_straight_from_the_slot(bd):
 
 @pytest.mark.parametrize("bd", [10, 9])
 def test_narrow_matrix(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 184 + bd)
     assert_planted(picture, bd)
     check_matrix(L, ctx, picture, bd)
@@ -325,22 +313,22 @@ def test_narrow_matrix(bd):
 
 
 def test_the_bytes_of_a_dithered_cell_add_up_to_the_sample():
-    L = _lib()
-    ctx = H._ctx(L, W, H_, 10, 1)
-    check_cells_add_up(L, ctx, _write(L))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
+    check_cells_add_up(L, ctx, SUP.writer(L))
     L.vvr_destroy(ctx)
 
 
 def test_multiples_of_4_leave_as_their_quarter():
-    L = _lib()
-    ctx = H._ctx(L, W, H_, 10, 1)
-    check_multiples_of_4(L, ctx, _write(L), np.random.default_rng(186))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
+    check_multiples_of_4(L, ctx, SUP.writer(L), np.random.default_rng(186))
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 9])
 def test_truncate_is_a_shift_and_the_luma_is_planar8s(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 187 + bd)
     check_truncate_and_luma(L, ctx, bd, bd == 10)
     L.vvr_destroy(ctx)
@@ -348,9 +336,9 @@ def test_truncate_is_a_shift_and_the_luma_is_planar8s(bd):
 
 @pytest.mark.parametrize("bd", [10, 9])
 def test_out_of_range_words_leave_as_255(bd):
-    L = _lib()
-    ctx = H._ctx(L, W, H_, bd, 1)
-    check_out_of_range_words(L, ctx, _write(L), np.random.default_rng(189))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, bd, 1)
+    check_out_of_range_words(L, ctx, SUP.writer(L), np.random.default_rng(189))
     L.vvr_destroy(ctx)
 
 
@@ -401,14 +389,14 @@ def check_state(L, ctx, picture, bd):
 
 @pytest.mark.parametrize("bd", [10, 9])
 def test_the_mode_is_context_state(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 190 + bd)
     check_state(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_context_of_8_bits_ignores_the_mode():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, 8, 192)
     win = (2, 6, 202, 38)
     before = {fmt: Q.queued(L, ctx, 0, win, fmt, 3) for fmt in FORMATS}
@@ -422,11 +410,11 @@ def test_a_context_of_8_bits_ignores_the_mode():
 
 def test_400_contexts():
     """planar8 of a 4:0:0 context at 10 bits is accepted, luma alone; the formats that need chroma stay refused under a mode"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(193)
-    ctx = H._ctx(L, W, H_, 10, 0)
+    ctx = SUP.make_ctx(L, W, H_, 10, 0)
     luma = plant([rng.integers(0, 1024, (H_, W)).astype(np.uint16)], 10)
-    H.write_picture(L, ctx, 0, luma)
+    SUP.write_picture(L, ctx, 0, luma)
     t, _ = Q.submit(L, ctx, 0, TINY, "planar8", 1)
     assert t == abi.VVR_ERR_PARAMETER and REFUSAL in L.vvr_last_error(ctx)
     for win in (TINY, (2, 6, 202, 38)):
@@ -443,7 +431,7 @@ def test_400_contexts():
 def test_refusals_leave_the_ring_and_the_seed_chain_alone():
     """what vvr_output_submit refuses stays refused under a mode - with its own text - and a refused request takes neither a ring entry nor a
     frame of the seed chain"""
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, 10, 194)
     win = (8, 4, 200, 64)
 
@@ -463,7 +451,7 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
         refused(REFUSAL, fmt=fmt, grain=True)      # (no mode set)
     set_mode(L, ctx, narrow_ref.DITHER, 1)
     # grain at 9 bits
-    ctx9 = H._ctx(L, W, H_, 9, 1)
+    ctx9 = SUP.make_ctx(L, W, H_, 9, 1)
     set_mode(L, ctx9, narrow_ref.ROUND)
     assert L.vvr_set_film_grain(ctx9, C.addressof(bank)) == abi.VVR_OK
     for fmt in FORMATS:
@@ -496,7 +484,7 @@ def test_python_mirror():
     import vvdec_amd
     assert (abi.NARROW_REFUSE, abi.NARROW_TRUNCATE, abi.NARROW_ROUND, abi.NARROW_DITHER) == (0, 1, 2, 3)
     assert abi.NARROW_MODES == {"refuse": 0, "truncate": 1, "round": 2, "dither": 3} and list(abi.OUT_NARROWED) == FORMATS
-    assert "vvr_set_output_narrowing" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(_lib(), "vvr_set_output_narrowing")
+    assert "vvr_set_output_narrowing" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(SUP.stub_lib(), "vvr_set_output_narrowing")
     assert hasattr(vvdec_amd.Reconstructor, "set_output_narrowing")
     # the shapes and dtypes of the six formats do not depend on the bit depth: bytes
     win = (2, 6, 202, 38)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import film_grain_ref
+import output_support as SUP
 import rescale_ref
 import test_film_grain_host as H
 import test_host_glue as T
@@ -19,26 +20,6 @@ pytestmark = T.pytestmark
 need_ref = pytest.mark.skipif(not (film_grain_ref.available() and rescale_ref.available()), reason="oracle/_ref/libvvref.so / libvvdec.so not built (needs /root/reference at build time)")
 
 
-def bind(L):
-    L.vvr_read_output.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t]
-    L.vvr_read_output_scaled.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t]
-    L.vvr_read_output_grain.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.vvr_output_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_output_test.argtypes = [C.c_void_p, C.c_int]
-    L.vvr_output_wait.argtypes = [C.c_void_p, C.c_int]
-    L.vvr_host_alloc.restype = C.c_void_p
-    L.vvr_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
-    L.vvr_sync.argtypes = [C.c_void_p]
-    L.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_wait.argtypes = [C.c_void_p, C.c_int]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
-
-
-FILL = 0xaa
 
 
 def submit(L, ctx, slot, win, fmt, ncomp, size=None, col=(True, False), grain=False, job=None, pad=(3, 5, 7), blocking=True, alloc=None):
@@ -52,7 +33,7 @@ def submit(L, ctx, slot, win, fmt, ncomp, size=None, col=(True, False), grain=Fa
         else:
             nbytes = r * (n + pad[c]) * np.dtype(dt).itemsize
             a = np.frombuffer((C.c_char * nbytes).from_address(alloc(nbytes)), dt).reshape(r, n + pad[c])
-        a.view(np.uint8)[...] = FILL
+        a.view(np.uint8)[...] = SUP.FILL
         outs.append(a)
     req = abi.output_request(slot, job, win, fmt, size, col, grain, blocking, outs)
     return L.vvr_output_submit(ctx, C.byref(req)), outs
@@ -62,8 +43,12 @@ def collect(L, ctx, ticket, outs, pad=(3, 5, 7)):
     """vvr_output_wait; nothing was written past a row -> the planes without their padding"""
     rc = L.vvr_output_wait(ctx, ticket)
     assert rc == abi.VVR_OK, (rc, L.vvr_last_error(ctx))
+    return unpadded(outs, pad)
+
+
+def unpadded(outs, pad=(3, 5, 7)):
     for c, a in enumerate(outs):
-        assert pad[c] == 0 or (a[:, a.shape[1] - pad[c]:].view(np.uint8) == FILL).all(), "wrote beyond the row"
+        assert pad[c] == 0 or (a[:, a.shape[1] - pad[c]:].view(np.uint8) == SUP.FILL).all(), "wrote beyond the row"
     return [a[:, :a.shape[1] - pad[c]] if pad[c] else a for c, a in enumerate(outs)]
 
 
@@ -193,8 +178,8 @@ def check_packed(L, mk_ctx, ctx, bd, cf):
 @pytest.mark.parametrize("cf", [1, 0])
 @pytest.mark.parametrize("bd", [10, 8])
 def test_planar_formats_match_the_synchronous_calls(bd, cf):
-    L = _lib()
-    ctx, bank = setup(L, lambda W, H_: H._ctx(L, W, H_, bd, cf), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(bd + cf), bd, cf)
+    L = SUP.stub_lib()
+    ctx, bank = setup(L, lambda W, H_: SUP.make_ctx(L, W, H_, bd, cf), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(bd + cf), bd, cf)
     check_planar(L, ctx, bd, cf)
     # a window beyond the picture in the slot (inside the slot) is refused
     t, _ = submit(L, ctx, 1, (8, 0, 200, 104), "planar16", 3 if cf else 1)
@@ -205,9 +190,9 @@ def test_planar_formats_match_the_synchronous_calls(bd, cf):
 @pytest.mark.parametrize("cf", [1, 0])
 @pytest.mark.parametrize("bd", [10, 8])
 def test_packed10_matches_the_applications_writer(bd, cf):
-    L = _lib()
-    mk = lambda W, H_: H._ctx(L, W, H_, bd, cf)
-    ctx, bank = setup(L, mk, lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(20 + bd + cf), bd, cf)
+    L = SUP.stub_lib()
+    mk = lambda W, H_: SUP.make_ctx(L, W, H_, bd, cf)
+    ctx, bank = setup(L, mk, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(20 + bd + cf), bd, cf)
     check_packed(L, mk, ctx, bd, cf)
     L.vvr_destroy(ctx)
 
@@ -227,12 +212,12 @@ def reference_chain(picture, sei, cases, backend, tmpdir):
 @need_ref
 def test_grain_then_rescale_is_the_reference_chain(tmp_path):
     """10-bit 4:2:0, ratios 2, 2/3 and 3/2, three collocation settings, one seed chain over the three frames; scale factors below 128"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(31)
     picture = film_grain_ref.grain_picture(rng, 448, 160, 10, 1)
     bank, want = reference_chain(picture, film_grain_ref.random_sei(rng, 1, 3, 5), CHAIN_CASES, T.build_stub(), str(tmp_path))
-    ctx = H._ctx(L, 448, 160, 10, 1)
-    H.write_picture(L, ctx, 0, picture)
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
+    SUP.write_picture(L, ctx, 0, picture)
     keep = abi.film_grain_bank(**bank)
     assert L.vvr_set_film_grain(ctx, C.addressof(keep)) == abi.VVR_OK
     for (win, size, col), w_ in zip(CHAIN_CASES, want):
@@ -246,13 +231,13 @@ def test_grain_then_rescale_is_the_reference_chain(tmp_path):
 def test_the_seed_chain_is_shared(tmp_path):
     """synchronous grained reads and queued grained requests interleaved on one context: the reference's sequence for the same frames; a refused
     request in between does not advance the chain; several requests in flight advance it in submission order"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(32)
     picture = film_grain_ref.grain_picture(rng, 448, 160, 10, 1)
     wins = [(0, 0, 136, 64), (2, 6, 200, 40), (4, 2, 384, 98), (10, 16, 146, 50), (0, 0, 448, 160), (40, 30, 256, 66)]
     banks, want = film_grain_ref.expected(picture, [("fgc", film_grain_ref.random_sei(rng, 0, 3, 4))] + [("frame", w, 2) for w in wins], 10, 1, str(tmp_path))
-    ctx = H._ctx(L, 448, 160, 10, 1)
-    H.write_picture(L, ctx, 0, picture)
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
+    SUP.write_picture(L, ctx, 0, picture)
     keep = abi.film_grain_bank(**banks[0])
     assert L.vvr_set_film_grain(ctx, C.addressof(keep)) == abi.VVR_OK
     got = [sync_read(L, ctx, 0, wins[0], 2, 3, grain=True), queued(L, ctx, 0, wins[1], "planar16", 3, grain=True)]
@@ -270,10 +255,10 @@ def test_the_seed_chain_is_shared(tmp_path):
 
 
 def test_refusals_tickets_and_the_ring():
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(33)
-    ctx = H._ctx(L, 448, 160, 10, 1)
-    H.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
+    SUP.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
     win = (8, 4, 200, 64)
 
     def refused(text, code=abi.VVR_ERR_PARAMETER, c=ctx, **kw):
@@ -303,7 +288,7 @@ def test_refusals_tickets_and_the_ring():
     bank = abi.film_grain_bank(**H._bank(rng))
     assert L.vvr_set_film_grain(ctx, C.addressof(bank)) == abi.VVR_OK
     refused(b"wider than 128", grain=True, win=(0, 0, 128, 64))
-    ctx9 = H._ctx(L, 448, 160, 9, 1)
+    ctx9 = SUP.make_ctx(L, 448, 160, 9, 1)
     refused(b"bit depth of 8 or 10", c=ctx9, fmt="packed10")
     L.vvr_destroy(ctx9)
     # tickets: test leaves the ticket, wait retires it; unknown tickets
@@ -331,10 +316,10 @@ def test_refusals_tickets_and_the_ring():
 def test_destinations_in_pinned_memory_are_written_by_the_copy():
     """every plane in memory of vvr_host_alloc: the rows are in place, at the padded stride, before vvr_output_wait is called (the stand-in's copies
     run at once) and the padding is untouched; pageable destinations: nothing arrives before vvr_output_wait"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(34)
-    ctx = H._ctx(L, 448, 160, 10, 1)
-    H.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
+    ctx = SUP.make_ctx(L, 448, 160, 10, 1)
+    SUP.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, 448, 160, 10, 1))
     win = (8, 4, 200, 64)
     want = sync_read(L, ctx, 0, win, 2, 3)
     for fmt, w_ in (("planar16", want), ("packed10", [pack10(p, 10) for p in want])):
@@ -345,19 +330,9 @@ def test_destinations_in_pinned_memory_are_written_by_the_copy():
         got = collect(L, ctx, t, outs)
         assert all(np.array_equal(a, b) for a, b in zip(got, w_))
     t, outs = submit(L, ctx, 0, win, "planar16", 3)
-    assert t >= 0 and all((a.view(np.uint8) == FILL).all() for a in outs), "pageable destinations are written by vvr_output_wait"
+    assert t >= 0 and all((a.view(np.uint8) == SUP.FILL).all() for a in outs), "pageable destinations are written by vvr_output_wait"
     assert all(np.array_equal(a, b) for a, b in zip(collect(L, ctx, t, outs), want))
     L.vvr_destroy(ctx)
-
-
-def _stream_ctx(L, W, H_, nslots, lanes=2, threads=2):
-    cfg = abi.Config()
-    cfg.abi_version = abi.VVR_ABI_VERSION
-    cfg.device, cfg.max_width, cfg.max_height, cfg.chroma_format, cfg.bit_depth, cfg.log2_ctu = 0, W, H_, 1, 10, 7
-    cfg.num_slots, cfg.num_streams, cfg.host_threads = nslots, lanes, threads
-    ctx = C.c_void_p()
-    assert L.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    return ctx
 
 
 def _trace(L):
@@ -371,10 +346,10 @@ def test_requests_are_ordered_on_the_device_not_on_the_host():
     never waits for the picture; the request's own event is recorded behind its kernels, and the picture that overwrites the slot later waits for
     exactly that event on its lane.  A job whose out_slot is another slot is refused; without `blocking` a picture still with the workers gives
     VVR_NOT_READY."""
-    L = _lib()
+    L = SUP.stub_lib()
     W, H_ = 256, 128
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = _stream_ctx(L, W, H_, nslots)
+    ctx = SUP.stream_ctx(L, W, H_, nslots)
     descs = [synth.picture_for_plan(pl, W, H_, seed=611, tool_flags=T.TOOLS) for pl in plans]
     pics = [d.c() for d in descs]
     win = (0, 0, W, H_)
@@ -404,7 +379,6 @@ def test_requests_are_ordered_on_the_device_not_on_the_host():
     pa = again.c()
     j1 = L.vvr_submit(ctx, C.byref(pa))
     assert j1 >= 0
-    L.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
     assert L.vvr_stream_wait_job(ctx, j1, ext, 1) == abi.VVR_OK      # (handed to the device)
@@ -423,24 +397,16 @@ def test_requests_are_ordered_on_the_device_not_on_the_host():
 
 
 def test_a_failed_picture_fails_its_request():
-    L = _lib()
-    W, H_ = 256, 128
-    plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = _stream_ctx(L, W, H_, nslots)
-    descs = [synth.picture_for_plan(pl, W, H_, seed=611, tool_flags=T.TOOLS, p_intra=0.3) for pl in plans]
-    pics = [d.c() for d in descs]
-    j0 = L.vvr_submit(ctx, C.byref(pics[0]))
-    t0, o0 = submit(L, ctx, plans[0].slot, (0, 0, W, H_), "planar16", 3, job=j0)
-    assert t0 >= 0
-    L.vvt_fail_leaf_waits(1)
-    j1 = L.vvr_submit(ctx, C.byref(pics[1]))                         # its intra stage gives up a wait: the job fails when it completes
-    t1, o1 = submit(L, ctx, plans[1].slot, (0, 0, W, H_), "planar16", 3, job=j1)
-    assert t1 >= 0
-    assert L.vvr_output_test(ctx, t1) == abi.VVR_ERR_DEVICE and L.vvr_output_test(ctx, t0) == abi.VVR_OK
-    assert L.vvr_output_wait(ctx, t1) == abi.VVR_ERR_DEVICE and b"waited for its neighbours" in L.vvr_last_error(ctx)
-    collect(L, ctx, t0, o0)
-    t2, o2 = submit(L, ctx, plans[1].slot, (0, 0, W, H_), "planar16", 3, job=j1)      # asked again after the failure is known: accepted, fails the same way
-    assert t2 >= 0 and L.vvr_output_wait(ctx, t2) == abi.VVR_ERR_DEVICE
-    L.vvt_fail_leaf_waits(0)
-    assert L.vvr_wait(ctx, j1) == abi.VVR_ERR_DEVICE and L.vvr_wait(ctx, j0) == abi.VVR_OK
-    L.vvr_destroy(ctx)
+    SUP.a_failed_picture_fails_its_request("out", SUP.stub_lib())
+
+
+def ring_request(L, ctx, planes, win, part, ref, bd):
+    def finish(t, keep, what):
+        assert all(np.array_equal(a, b) for a, b in zip(collect(L, ctx, t, keep), part)), what
+    return lambda: submit(L, ctx, 0, win, "planar16", 3), finish
+
+
+SUP.register("out", b"vvr_output_submit", ring_request,
+             failing=lambda L, ctx, slot, win, job, ref_slot: submit(L, ctx, slot, win, "planar16", 3, job=job),
+             untouched=lambda outs: all((a.view(np.uint8) == SUP.FILL).all() for a in outs),
+             delivered=unpadded)

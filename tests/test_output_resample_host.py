@@ -13,6 +13,7 @@ import pytest
 
 import interleaved_ref
 import narrow_ref
+import output_support as SUP
 import resample_ref as R
 import rgb_ref
 import yuv_ref
@@ -37,14 +38,6 @@ COLLOCATED = [(False, False), (True, False), (False, True), (True, True)]      #
 REFUSAL = b"under vvr_set_output_resampling window and output sides must be 1..8192, the output's within 1/64 .. 8 times the window's in every plane"
 REFUSAL_REFERENCE = b"output sides must be 1..8192 and within 1/8 .. 8 times the window's"
 SWEEP = [(8191, 128), (8192, 128), (1, 8), (2, 16), (17, 9), (1023, 8184), (208, 56), (104, 28), (70, 50), (35, 25), (16, 128), (208, 210), (208, 4), (128, 2), (64, 1), (136, 17), (131, 262), (3840, 224), (2160, 224), (3840, 1920)]
-
-
-def bind(L):
-    return abi.bind_output_resampling(abi.bind_output_narrowing(I.bind(L)))
-
-
-def _lib():
-    return bind(H._lib())
 
 
 def set_filter(L, ctx, filt):
@@ -185,10 +178,6 @@ def check_in_flight(L, ctx, write, bd=10):
         same(Q.collect(L, ctx, t, outs), want, what)
 
 
-def _write(L):
-    return lambda ctx, slot, p: H.write_picture(L, ctx, slot, p)
-
-
 # ---- the restatement and the helper
 
 def test_the_restatement_on_values_worked_by_hand():
@@ -219,7 +208,7 @@ def sweep_samples(m):
 def test_taps_against_python_integers():
     """vvr_resample_taps over a sweep (8191 -> 128 is the coprime 64-bit worst case), both phi: count <= 256, the weights sum to 16384, the taps
     lie inside the plane and | H | < 32768 at 10 bits - the sum of the positive weights times 1023, rounded, is the largest H there is"""
-    L = _lib()
+    L = SUP.stub_lib()
     most = 0
     for n, m in SWEEP:
         assert R.accepted(n, m)
@@ -238,7 +227,7 @@ def test_taps_against_python_integers():
 
 
 def test_taps_refusals():
-    L = _lib()
+    L = SUP.stub_lib()
     ok = (R.CUBIC, 208, 56, 2, 0)
     assert abi.resample_taps(L, *ok) is not None
     for bad in [(0, 208, 56, 2, 0), (4, 208, 56, 2, 0), (-1, 208, 56, 2, 0), (R.CUBIC, 0, 56, 2, 0), (R.CUBIC, 208, 0, 2, 0), (R.CUBIC, 8193, 8192, 2, 0), (R.CUBIC, 8192, 8193, 2, 0),
@@ -253,51 +242,51 @@ def test_taps_refusals():
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_every_filter_geometry_and_content(bd):
-    L = _lib()
-    ctx = H._ctx(L, W, H_, bd, 1)
-    check_geometries(L, ctx, _write(L), bd, 3)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, bd, 1)
+    check_geometries(L, ctx, SUP.writer(L), bd, 3)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_400_contexts(bd):
-    L = _lib()
-    ctx = H._ctx(L, W400, H400, bd, 0)
-    check_geometries(L, ctx, _write(L), bd, 1)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W400, H400, bd, 0)
+    check_geometries(L, ctx, SUP.writer(L), bd, 1)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_formats_behind_the_resampler(bd):
-    L = _lib()
-    ctx = H._ctx(L, W, H_, bd, 1)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, bd, 1)
     bank = abi.film_grain_bank(**H._bank(np.random.default_rng(510 + bd)))
-    check_formats(L, ctx, _write(L), bd, bank)
+    check_formats(L, ctx, SUP.writer(L), bd, bank)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_the_filter_is_context_state(bd):
-    L = _lib()
-    ctx = H._ctx(L, W, H_, bd, 1)
-    check_state(L, ctx, _write(L), bd)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, bd, 1)
+    check_state(L, ctx, SUP.writer(L), bd)
     L.vvr_destroy(ctx)
 
 
 def test_eight_requests_in_flight():
-    L = _lib()
-    ctx = H._ctx(L, W, H_, 10, 1)
-    check_in_flight(L, ctx, _write(L))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
+    check_in_flight(L, ctx, SUP.writer(L))
     L.vvr_destroy(ctx)
 
 
 def test_a_context_at_filter_0_is_todays():
     """a new context, and one set back to 0: the bytes of the synchronous rescaler (vvdec::rescalePlane's) and the refusal below 1/8 with
     today's text; under a filter the same request is accepted"""
-    L = _lib()
-    ctx = H._ctx(L, W, H_, 10, 1)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
     picture = content("noise", W, H_, 10, 3, 80)
-    H.write_picture(L, ctx, 0, picture)
+    SUP.write_picture(L, ctx, 0, picture)
     win, size = GEOMETRIES[0]
     for turn in range(2):
         same(Q.queued(L, ctx, 0, win, "planar16", 3, size=size), Q.sync_read(L, ctx, 0, win, 2, 3, size=size), "filter 0")
@@ -314,10 +303,10 @@ def test_refusals_per_plane_leave_the_ring_and_the_seed_chain_alone():
     """the limits hold per plane and axis: 130 -> 3 passes the luma test ( 130 <= 64 * 3 ) and fails the chroma one ( 65 > 64 * 1 ); 130 -> 2
     fails both; 128 -> 2 and 128 -> 3 pass.  Upwards 16 -> 128 passes, 16 -> 130 does not.  A refused request takes neither a ring entry nor a
     frame of the seed chain."""
-    L = _lib()
-    ctx = H._ctx(L, W, H_, 10, 1)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
     picture = content("noise", W, H_, 10, 3, 81)
-    H.write_picture(L, ctx, 0, picture)
+    SUP.write_picture(L, ctx, 0, picture)
     bank = abi.film_grain_bank(**H._bank(np.random.default_rng(82)))
     assert L.vvr_set_film_grain(ctx, C.addressof(bank)) == abi.VVR_OK
     set_filter(L, ctx, R.AREA)
@@ -348,10 +337,10 @@ def test_refusals_per_plane_leave_the_ring_and_the_seed_chain_alone():
 
 def test_the_synchronous_call_and_a_scaled_comparison_do_not_look_at_the_filter():
     import test_output_scaled_compare_host as SC
-    L = SC.bind(_lib())
-    ctx = H._ctx(L, W, H_, 10, 1)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
     picture = content("noise", W, H_, 10, 3, 83)
-    H.write_picture(L, ctx, 0, picture)
+    SUP.write_picture(L, ctx, 0, picture)
     win, size = GEOMETRIES[0]
     before = Q.sync_read(L, ctx, 0, win, 2, 3, size=size)
     cmp_before = scaled_comparison(L, ctx, win, size)
@@ -428,5 +417,5 @@ def test_python_mirror():
     import vvdec_amd
     assert (abi.RESAMPLE_REFERENCE, abi.RESAMPLE_AREA, abi.RESAMPLE_TRIANGLE, abi.RESAMPLE_CUBIC) == (0, 1, 2, 3) and abi.RESAMPLE_MAX_TAPS == 256
     assert abi.RESAMPLE_FILTERS == {None: 0, "reference": 0, "area": 1, "triangle": 2, "cubic": 3}
-    assert all(s in vvdec_amd.EXPORTED_SYMBOLS and hasattr(_lib(), s) for s in ("vvr_set_output_resampling", "vvr_resample_taps"))
+    assert all(s in vvdec_amd.EXPORTED_SYMBOLS and hasattr(SUP.stub_lib(), s) for s in ("vvr_set_output_resampling", "vvr_resample_taps"))
     assert hasattr(vvdec_amd.Reconstructor, "set_output_resampling") and hasattr(vvdec_amd, "resample_taps")

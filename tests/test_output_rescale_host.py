@@ -1,37 +1,16 @@
 """CPU: vvr_read_output_scaled, the host half (argument checks, scale factors and positions, packing, the caller's stride) on the stand-in runtime of
 tests/hoststub, whose launch_rescale is a plain loop restating sampleRateConvCore (vvr_output.inc, compiled for the host only).  Ground truth is the
 reference's own vvdec::rescalePlane from the drop-in library, on both of its paths (plain C++ and x86 SIMD, tests/rescale_ref.py)."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
+import output_support as SUP
 import rescale_ref
 import test_host_glue as T
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
-
-
-def _lib():
-    L = C.CDLL(T.build_stub())
-    L.vvr_last_error.restype = C.c_char_p
-    L.vvr_last_error.argtypes = [C.c_void_p]
-    L.vvr_destroy.argtypes = [C.c_void_p]
-    L.vvr_write_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-    L.vvr_read_output_scaled.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t]
-    return L
-
-
-def _ctx(L, W, H, bit_depth, chroma_format):
-    cfg = abi.Config()
-    cfg.abi_version = abi.VVR_ABI_VERSION
-    cfg.device, cfg.max_width, cfg.max_height = 0, W, H
-    cfg.chroma_format, cfg.bit_depth, cfg.log2_ctu = chroma_format, bit_depth, 7
-    cfg.num_slots, cfg.num_streams = 2, 1
-    ctx = C.c_void_p()
-    assert L.vvr_create(C.byref(cfg), C.byref(ctx)) == abi.VVR_OK
-    return ctx
 
 
 def _scaled(L, ctx, slot, comp, win, ow, oh, col, bps, pad=0):
@@ -44,8 +23,8 @@ def _scaled(L, ctx, slot, comp, win, ow, oh, col, bps, pad=0):
 
 
 def test_argument_checks():
-    L = _lib()
-    ctx = _ctx(L, 256, 128, 10, 1)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, 256, 128, 10, 1)
     buf = np.zeros(8192 * 16, np.uint16)
 
     def call(comp=0, x=0, y=0, w=64, h=32, ow=128, oh=64, col=1, bps=2, stride=None):
@@ -69,9 +48,9 @@ def test_argument_checks():
 def test_values_are_rescale_plane(tmp_path, bd, cf):
     """every window of the case matrix against vvdec::rescalePlane, plain C++ and SIMD path; 8-bit content: rescalePlane of the samples widened
     to 16 bits, narrowed (what vvdecapp --upscale would do if it handed the frame's 8-bit samples over right)"""
-    L = _lib()
+    L = SUP.stub_lib()
     W = H = 1024
-    ctx = _ctx(L, W, H, bd, cf)
+    ctx = SUP.make_ctx(L, W, H, bd, cf)
     rng = np.random.default_rng(bd * 10 + cf)
     planes = []
     for c in range(3 if cf else 1):

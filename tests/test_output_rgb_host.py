@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import film_grain_ref
+import output_support as SUP
 import rescale_ref
 import rgb_ref
 import test_film_grain_host as H
@@ -19,22 +20,12 @@ import test_output_semiplanar_host as S
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
-FILL = Q.FILL
+FILL = SUP.FILL
 W, H_ = S.W, S.H_
 FORMATS = ["rgb8", "rgb16", "rgbf16"]
 COLOURS = [(1, 0), (5, 1), (9, 0), (6, 0), (1, 1), (9, 1), (5, 0), (6, 1)]      # (matrix_coefficients, full_range): every accepted pair
 DEPTHS = [(8, 8), (9, 8), (9, 9), (10, 8), (10, 10)]                           # (bd, od)
 BOUND = 0.5 + (1023 + 512 + 512) / 2 ** 15                                     # rounding of the result + of the coefficients, at most 10 bits
-
-
-def bind(L):
-    S.bind(L)
-    L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
 
 
 def cases(bd):
@@ -176,24 +167,24 @@ def test_the_cases_meet_every_instantiation_of_the_kernel():
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_every_instantiation_straight_from_the_slot(bd):
-    L = _lib()
-    ctx, picture, bank = S.setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(85 + bd), bd)
+    L = SUP.stub_lib()
+    ctx, picture, bank = S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(85 + bd), bd)
     check_instantiations(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_rgb_matrix(bd):
-    L = _lib()
-    ctx, picture, bank = S.setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(80 + bd), bd)
+    L = SUP.stub_lib()
+    ctx, picture, bank = S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(80 + bd), bd)
     check_matrix(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_ring_and_the_seed_chain_alone():
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(81)
-    ctx, picture, bank = S.setup(L, lambda w, h: H._ctx(L, w, h, 10, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), rng, 10)
+    ctx, picture, bank = S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, 10, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), rng, 10)
     win = (8, 4, 200, 64)
 
     def refused(text, c=ctx, fmt="rgb16", mutate=None, size=None, grain=False, w_=win):
@@ -217,7 +208,7 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
     assert L.vvr_set_film_grain_seed(ctx, 9) == abi.VVR_OK
     first = Q.queued(L, ctx, 0, win, "planar16", 3, grain=True)
     assert L.vvr_set_film_grain_seed(ctx, 9) == abi.VVR_OK
-    ctx400 = H._ctx(L, W, H_, 8, 0)
+    ctx400 = SUP.make_ctx(L, W, H_, 8, 0)
     assert L.vvr_set_output_colour(ctx400, 1, 0) == abi.VVR_OK
     for fmt in FORMATS:
         refused(b"no chroma", c=ctx400, fmt=fmt)
@@ -236,7 +227,7 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
     refused(b"no such slot", mutate=lambda r: setattr(r, "slot", 7))
     for f in (3, 4, 15, 18, 31, 35, 255):
         refused(b"unknown format", mutate=lambda r, f=f: setattr(r, "format", f))
-    ctx9 = H._ctx(L, W, H_, 9, 1)
+    ctx9 = SUP.make_ctx(L, W, H_, 9, 1)
     assert L.vvr_set_output_colour(ctx9, 1, 0) == abi.VVR_OK
     bank9 = abi.film_grain_bank(**H._bank(rng))
     assert L.vvr_set_film_grain(ctx9, C.addressof(bank9)) == abi.VVR_OK
@@ -264,10 +255,10 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
 
 def test_a_request_takes_the_colour_description_set_when_it_is_submitted():
     """vvr_set_output_colour between two submits changes only the second; a refused call leaves the first value in force"""
-    L = _lib()
-    ctx = H._ctx(L, W, H_, 10, 1)
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
     picture = film_grain_ref.grain_picture(np.random.default_rng(82), W, H_, 10, 1)
-    H.write_picture(L, ctx, 0, picture)
+    SUP.write_picture(L, ctx, 0, picture)
     win, col = (2, 6, 202, 38), (True, False)
     want = {colour: rgb_ref.rgb(S.crop(picture, win), 10, "rgb16", colour[0], bool(colour[1]), col) for colour in [(1, 0), (9, 1)]}
     assert not all(np.array_equal(a, b) for a, b in zip(want[(1, 0)], want[(9, 1)]))

@@ -11,12 +11,11 @@ import pytest
 
 import compare_ref
 import msssim_ref
+import output_support as SUP
 import rescale_ref
 import ssim_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_compare_host as XC
-import test_output_hash_host as XH
 import test_output_msssim_host as XM
 import test_output_ssim_host as XS
 import test_output_xpsnr_host as XX
@@ -34,19 +33,10 @@ CASES = [("2x up", (0, 0, 104, 40), (208, 80)),                 # the plain ladd
          ("equal size", (0, 0, 208, 80), (208, 80))]            # the phase-0 luma filter and the chroma phase of `collocated`
 CASES_400 = [("4:0:0, odd sizes", (3, 1, 131, 5), (77, 9))]     # odd origin and odd scaled width
 LADDER, UNEVEN = CASES[0], CASES[1]
-FILL = 0xaa
 
 
-def bind(L):
-    XX.bind(L)
-    abi.bind_compare_scaling(L)
-    L.vvr_read_output_scaled.restype = C.c_int
-    L.vvr_read_output_scaled.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
+def picture_size(cf):
+    return (W, H_) if cf else (W400, H400)
 
 
 def cases(nc):
@@ -81,7 +71,7 @@ def as_window(size):
 # one request of each kind: the request carries the window, the arrays vvr_output_wait writes are sized by the scaled size
 def submit_compare(L, ctx, slot, win, size, ref, with_map=True, job=None, bps=2):
     raw = abi.FrameCompare()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     blocks = np.full(abi.compare_map_shape(as_window(size)), 0xaaaaaaaa, np.uint32) if with_map else None
     req = abi.compare_request(slot, job, win, ref, raw, blocks, True, bps)
     return L.vvr_compare_submit(ctx, C.byref(req)), (raw, blocks)
@@ -89,7 +79,7 @@ def submit_compare(L, ctx, slot, win, size, ref, with_map=True, job=None, bps=2)
 
 def submit_ssim(L, ctx, slot, win, size, ref, with_map=True, job=None):
     raw = abi.FrameSsim()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     blocks = np.full(abi.ssim_map_shape(as_window(size)), -0x55555556, np.int32) if with_map else None
     req = abi.ssim_request(slot, job, win, ref, raw, blocks, True, 2)
     return L.vvr_ssim_submit(ctx, C.byref(req)), (raw, blocks)
@@ -97,16 +87,16 @@ def submit_ssim(L, ctx, slot, win, size, ref, with_map=True, job=None):
 
 def submit_msssim(L, ctx, slot, win, size, ref, scales, job=None):
     raw = abi.FrameMsssim()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     req = abi.msssim_request(slot, job, win, ref, raw, scales, True, 2)
     return L.vvr_msssim_submit(ctx, C.byref(req)), raw
 
 
 def submit_xpsnr(L, ctx, slot, win, size, ref, prev=(), block=0, job=None):
     raw = abi.FrameXpsnr()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     shape = abi.xpsnr_blocks(size[0], size[1], block)
-    blocks = np.frombuffer(bytearray([FILL]) * (XX.BLOCK_DTYPE.itemsize * shape[1] * shape[2]), XX.BLOCK_DTYPE)
+    blocks = np.frombuffer(bytearray([SUP.FILL]) * (XX.BLOCK_DTYPE.itemsize * shape[1] * shape[2]), XX.BLOCK_DTYPE)
     req = abi.xpsnr_request(slot, job, win, ref, raw, list(prev), blocks, block, 0, True, 2)
     return L.vvr_xpsnr_submit(ctx, C.byref(req)), (raw, blocks)
 
@@ -143,7 +133,7 @@ def check_comparison(L, ctx, planes, bd):
                     c = int(kind[4:])
                     assert sum(want["differing"]) == 1 and (want["first_x"][c], want["first_y"][c]) == (want["width"][c] - 1, want["height"][c] - 1), what
                 blocks_seen.add(want["map"].shape)
-                for form, given in [f for f in XC.forms(ref) if (f[0] == "8-bit") == (bps == 1)]:
+                for form, given in [f for f in SUP.forms(ref) if (f[0] == "8-bit") == (bps == 1)]:
                     for with_map in (True, False):
                         got = queued(L, ctx, submit_compare(L, ctx, 0, win, size, given, with_map))
                         XC.same(got, want, as_window(size), bd, "%s, %s reference, map %d" % (what, form, with_map))
@@ -163,7 +153,7 @@ def check_collocated(L, ctx, planes, bd):
         seen.append(part)
         for kind in ("identical", "random"):
             ref = XC.reference(kind, rng, part, bd)
-            got = queued(L, ctx, submit_compare(L, ctx, 0, win, size, XC.forms(ref)[0][1]))
+            got = queued(L, ctx, submit_compare(L, ctx, 0, win, size, SUP.forms(ref)[0][1]))
             XC.same(got, compare_ref.compare(part, ref), as_window(size), bd, "collocated %d, %s" % (col, kind))
     assert all(np.array_equal(seen[0][0], s[0]) for s in seen)
     assert all(not np.array_equal(seen[a][1], seen[b][1]) for a in range(4) for b in range(a))
@@ -184,7 +174,7 @@ def check_windowed_measures(L, ctx, planes, bd):
         swin = as_window(size)
         for kind, ref in references(rng, part, bd):
             what = "%s: %s at %d bits" % (name, kind, bd)
-            given = [XC.padded(p, np.uint16, k) for p, k in zip(ref, (3, 5, 7))]
+            given = [SUP.padded(p, np.uint16, k) for p, k in zip(ref, (3, 5, 7))]
             XS.same(queued(L, ctx, submit_ssim(L, ctx, 0, win, size, given)), ssim_ref.ssim(part, ref, bd), swin, bd, "SSIM, " + what)
             XS.same(queued(L, ctx, submit_ssim(L, ctx, 0, win, size, given, with_map=False)), ssim_ref.ssim(part, ref, bd), swin, bd, "SSIM without a map, " + what)
             want = msssim_ref.msssim(part, ref, bd, 2)
@@ -195,7 +185,7 @@ def check_windowed_measures(L, ctx, planes, bd):
                 for block in (0, 8):
                     want = xpsnr_ref.xpsnr_integers(part, ref, prev[:temporal], block, 0)
                     assert want["block"] == (block or 4) and want["blocks_x"] == -(-size[0] // want["block"]) and want["temporal"] == temporal
-                    got = queued(L, ctx, submit_xpsnr(L, ctx, 0, win, size, given, [XC.padded(p, np.uint16, 9) for p in prev[:temporal]], block))
+                    got = queued(L, ctx, submit_xpsnr(L, ctx, 0, win, size, given, [SUP.padded(p, np.uint16, 9) for p in prev[:temporal]], block))
                     XX.same(got, want, swin, bd, "XPSNR, temporal %d, block %d, %s" % (temporal, block, what))
     off(L, ctx)
 
@@ -210,14 +200,14 @@ def check_capture_at_submit(L, ctx, fresh, planes, bd):
     ref = XC.reference("random", rng, part, bd)
     plain = compare_ref.window_planes(planes, win)
     plain_ref = XC.reference("random", rng, plain, bd)
-    a = submit_compare(L, ctx, 0, win, size, XC.forms(ref)[0][1])
+    a = submit_compare(L, ctx, 0, win, size, SUP.forms(ref)[0][1])
     off(L, ctx)
-    b = XC.submit(L, ctx, 0, win, XC.forms(plain_ref)[0][1])
+    b = XC.submit(L, ctx, 0, win, SUP.forms(plain_ref)[0][1])
     scaling(L, ctx, (2 * size[0], 2 * size[1]))      # (a request in flight keeps the value it was submitted with)
     XC.same(queued(L, ctx, a), compare_ref.compare(part, ref), as_window(size), bd, "the scaled request")
     got = queued(L, ctx, b)
     XC.same(got, compare_ref.compare(plain, plain_ref), win, bd, "the unscaled request behind it")
-    there = XC.queued(L, fresh, 0, win, XC.forms(plain_ref)[0][1])
+    there = XC.queued(L, fresh, 0, win, SUP.forms(plain_ref)[0][1])
     assert bytes(got[0]) == bytes(there[0]) and np.array_equal(got[1], there[1])
     off(L, ctx)
 
@@ -232,7 +222,7 @@ def check_homes(L, ctx, planes, bd):
     for bps, dt in ((2, np.uint16), (1, np.uint8)):
         ref = XC.reference("random", rng, part, bd, bps)
         want = compare_ref.compare(part, ref)
-        given = [XC.padded(p, dt, 3) for p in ref]
+        given = [SUP.padded(p, dt, 3) for p in ref]
         sub = submit_compare(L, ctx, 0, win, size, given)
         for g in given:
             g.base[...] = 0x33
@@ -277,7 +267,7 @@ def check_setter_refusals(L, ctx, planes, bd):
 def check_submit_refusals(L, ctx, planes, bd):
     """what a submit call refuses under scaling beyond what it refuses without: a size outside 1/8 .. 8 times the window's, ref_slot - each
     kind of request, each with a text that names the call, no ring entry taken: eight further requests are accepted"""
-    H.write_picture(L, ctx, 1, planes)
+    SUP.write_picture(L, ctx, 1, planes)
     zeros = lambda size: [np.zeros((size[1] >> s, size[0] >> s), np.uint16) for s in (0, 1, 1)]
     kinds = [(b"vvr_compare_submit", lambda win, size, ref: submit_compare(L, ctx, 0, win, size, ref)[0]),
              (b"vvr_ssim_submit", lambda win, size, ref: submit_ssim(L, ctx, 0, win, size, ref)[0]),
@@ -325,7 +315,6 @@ def check_submit_refusals(L, ctx, planes, bd):
 def check_statistics(L, ctx, planes, bd):
     """vvr_get_stats: a scaled comparison is one k_output_compare_scaled and the fold; a scaled SSIM request runs k_rescale - one launch per
     component - ahead of its own kernels"""
-    L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
     assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
     name, win, size = LADDER
     scaling(L, ctx, size)
@@ -335,81 +324,73 @@ def check_statistics(L, ctx, planes, bd):
     queued(L, ctx, submit_ssim(L, ctx, 0, win, size, words16(part)))
     off(L, ctx)
     XC.queued(L, ctx, 0, win, words16(compare_ref.window_planes(planes, win)))
-    got = XC.launches(L, ctx)
+    got = SUP.launches(L, ctx)
     assert got == {"k_output_compare_scaled": 2, "k_rescale": 3, "k_output_compare": 1, "k_output_compare_sum": 3, "k_output_ssim": 1, "k_output_ssim_sum": 1}, got
     assert L.vvr_enable_stats(ctx, 0) == abi.VVR_OK
 
 
 # ---- tests
 
-def _ctx_with(L, bd, cf, seed):
-    w, h = (W, H_) if cf else (W400, H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    H.write_picture(L, ctx, 0, planes)
-    return ctx, planes
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_case(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 2000 + bd + cf)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 2000 + bd + cf)
     check_comparison(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_collocated_reaches_the_chroma_planes():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2010)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 2010)
     check_collocated(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_ssim_msssim_and_xpsnr_of_the_rescaled_window(bd):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, 1, 2020 + bd)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), bd, 1, 2020 + bd)
     check_windowed_measures(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_request_keeps_the_value_it_was_submitted_with():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2030)
-    fresh, _ = _ctx_with(L, 10, 1, 2030)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 2030)
+    fresh, _ = SUP.ctx_with(L, picture_size(1), 10, 1, 2030)
     check_capture_at_submit(L, ctx, fresh, planes, 10)
     L.vvr_destroy(ctx)
     L.vvr_destroy(fresh)
 
 
 def test_the_homes_of_a_reference_of_the_scaled_size():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 8, 1, 2040)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 8, 1, 2040)
     check_homes(L, ctx, planes, 8)
     L.vvr_destroy(ctx)
 
 
 def test_the_setter_refuses_and_keeps_the_value_set_before():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2050)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 2050)
     check_setter_refusals(L, ctx, planes, 10)
     # a 4:0:0 context takes odd sides
-    ctx400, _ = _ctx_with(L, 8, 0, 2051)
+    ctx400, _ = SUP.ctx_with(L, picture_size(0), 8, 0, 2051)
     scaling(L, ctx400, (77, 9))
     L.vvr_destroy(ctx400)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_at_submit_leave_the_ring_alone():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2060)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 2060)
     check_submit_refusals(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_rescaling():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 2070)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 2070)
     check_statistics(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
@@ -420,10 +401,9 @@ def test_the_slot_is_free_behind_the_rescaling():
     from dataclasses import replace
     from vvdec_amd import synth
     import test_output_queue_host as Q
-    L = _lib()
-    ctx, plans, descs, win = XC._stream(L)
+    L = SUP.stub_lib()
+    ctx, plans, descs, win = SUP.small_stream(L)
     Wd, Hd = win[2], win[3]
-    L.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
     s0 = plans[0].slot
@@ -457,9 +437,9 @@ def test_the_slot_is_free_behind_the_rescaling():
 def test_the_picture_side_is_rescale_plane(tmp_path):
     """the picture side straight from vvdec::rescalePlane instead of vvr_read_output_scaled: the comparison of every case against it reports
     nothing differing, and against it with one sample changed exactly that sample"""
-    L = _lib()
+    L = SUP.stub_lib()
     bd = 10
-    ctx, planes = _ctx_with(L, bd, 1, 2080)
+    ctx, planes = SUP.ctx_with(L, picture_size(1), bd, 1, 2080)
     cases_ = []
     for name, win, size in CASES:
         for c in range(3):
@@ -479,8 +459,6 @@ def test_the_picture_side_is_rescale_plane(tmp_path):
 
 def geometry(L, win, size, nc):
     out = (C.c_longlong * 15)()
-    L.vvt_compare_scaled_geometry.restype = None
-    L.vvt_compare_scaled_geometry.argtypes = [C.c_int] * 5 + [C.c_void_p]
     L.vvt_compare_scaled_geometry(win[2], win[3], size[0], size[1], nc, out)
     v = [int(x) for x in out]
     return dict(tile_h=v[0:3], rows_cap=v[3:6], tiles_x=v[6:9], first=v[9:13], lds=v[13], clear=v[14])
@@ -490,7 +468,7 @@ def test_the_geometry_of_the_fused_launch():
     """tile height, tile list, LDS and the words cleared ahead of k_output_compare_scaled: worked out by hand for three sizes, and for every
     case what the kernel relies on - a tile height that is a power of two of at most 64 (luma) or 32 (chroma), so that a tile lies in one row of
     blocks; the source rows of a tile within the 128 rows of sums LDS holds; every output row and column in exactly one tile"""
-    L = _lib()
+    L = SUP.stub_lib()
     # 1080p to 4K: a source row for every two output rows, 63 / 2 -> 32 + 8 taps = 40 rows of sums (chroma: 31 / 2 -> 16 + 4); 60 x 34 and
     # 30 x 34 tiles - about a thousand each, so the tiles stay 64 and 32 rows high; ( 6 x 3 + 1 ) words for each of 60 x 34 blocks
     g = geometry(L, (0, 0, 1920, 1080), (3840, 2160), 3)
@@ -530,5 +508,5 @@ def test_the_geometry_of_the_fused_launch():
 
 def test_python_mirror_and_symbols():
     import vvdec_amd
-    assert "vvr_set_compare_scaling" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(_lib(), "vvr_set_compare_scaling")
+    assert "vvr_set_compare_scaling" in vvdec_amd.EXPORTED_SYMBOLS and hasattr(SUP.stub_lib(), "vvr_set_compare_scaling")
     assert hasattr(vvdec_amd.Reconstructor, "set_compare_scaling") and hasattr(abi, "bind_compare_scaling")

@@ -10,34 +10,19 @@ import numpy as np
 import pytest
 
 import film_grain_ref
+import output_support as SUP
 import test_film_grain_host as H
 import test_host_glue as T
 import test_output_queue_host as Q
 from vvdec_amd import abi, stream, synth
 
 pytestmark = T.pytestmark
-FILL = Q.FILL
+FILL = SUP.FILL
 W, H_ = 448, 160
 # (2, 6, 202, 38): chroma rows of 101 samples - odd, rows that straddle a lane's piece, a chroma origin at an odd sample
 WINDOWS = [(0, 0, 448, 160), (8, 4, 200, 64), (2, 6, 202, 38), (6, 2, 144, 34)]
 SIZES = [None, (300, 96), (134, 26)]
 VARIANTS = [(10, "p010"), (8, "p010"), (9, "p010"), (8, "nv12")]
-
-
-def bind(L):
-    Q.bind(L)
-    L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.vvr_device_alloc.restype = C.c_void_p
-    L.vvr_device_alloc.argtypes = [C.c_void_p, C.c_size_t]
-    L.vvr_device_free.restype = None
-    L.vvr_device_free.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_device_register.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.vvr_device_unregister.argtypes = [C.c_void_p, C.c_void_p]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
 
 
 def cases(bd):
@@ -174,8 +159,8 @@ def setup(L, mk_ctx, write, rng, bd):
 
 @pytest.mark.parametrize("bd,fmt", VARIANTS)
 def test_semiplanar_matrix(bd, fmt):
-    L = _lib()
-    ctx, picture, bank = setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(40 + bd), bd)
+    L = SUP.stub_lib()
+    ctx, picture, bank = setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(40 + bd), bd)
     check_matrix(L, ctx, picture, bd, fmt)
     L.vvr_destroy(ctx)
 
@@ -183,9 +168,9 @@ def test_semiplanar_matrix(bd, fmt):
 def test_device_requests_copy_nothing_in_wait():
     """the stand-in's kernels and copies run inside vvr_output_submit: the rows are in place when it returns, and what the test writes over them
     afterwards survives vvr_output_wait; memory of vvr_device_alloc serves like a registered range"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(51)
-    ctx, picture, bank = setup(L, lambda w, h: H._ctx(L, w, h, 10, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), rng, 10)
+    ctx, picture, bank = setup(L, lambda w, h: SUP.make_ctx(L, w, h, 10, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), rng, 10)
     win = (2, 6, 202, 38)
     want = semi(crop(picture, win), "p010", 10)
     for stride_kind in STRIDES:
@@ -218,9 +203,9 @@ def test_device_requests_copy_nothing_in_wait():
 @pytest.mark.parametrize("bd", [10, 8])
 def test_existing_formats_into_device_memory(bd):
     """planar16, planar8 and packed10 into registered ranges: the bytes of the same requests into pageable memory"""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(52 + bd)
-    ctx, picture, bank = setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), rng, bd)
+    ctx, picture, bank = setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), rng, bd)
     n = 0
     for fmt in ["planar16", "packed10"] + (["planar8"] if bd == 8 else []):
         for win in [(0, 0, 448, 160), (8, 4, 200, 64)] + ([(2, 6, 202, 38)] if fmt != "packed10" else []):
@@ -234,10 +219,10 @@ def test_existing_formats_into_device_memory(bd):
 
 
 def test_refusals_of_formats_and_ranges():
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(53)
-    ctx = H._ctx(L, W, H_, 10, 1)
-    H.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, W, H_, 10, 1))
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
+    SUP.write_picture(L, ctx, 0, film_grain_ref.grain_picture(rng, W, H_, 10, 1))
     win = (8, 4, 200, 64)
 
     def refused(text, c=ctx, fmt="p010", mutate=None, ncomp=3, outs=None):
@@ -250,7 +235,7 @@ def test_refusals_of_formats_and_ranges():
         assert rc == abi.VVR_ERR_PARAMETER and text in L.vvr_last_error(c), (text, rc, L.vvr_last_error(c))
 
     refused(b"8-bit output of a stream with more than 8 bits per sample", fmt="nv12")          # (VVR_OUT_PLANAR8's wording)
-    ctx400 = H._ctx(L, W, H_, 8, 0)
+    ctx400 = SUP.make_ctx(L, W, H_, 8, 0)
     for fmt in ("nv12", "p010"):
         refused(b"no chroma to interleave", c=ctx400, fmt=fmt)
     L.vvr_destroy(ctx400)
@@ -318,9 +303,9 @@ def test_stream_wait_is_one_wait_for_the_completion_event():
     """the stand-in's trace: vvr_output_stream_wait puts exactly one wait, for the event the request recorded last on the output stream (behind
     its last kernel or copy), on the caller's stream and nothing else; the request is still not complete for the host afterwards (nothing
     waited for it) and the ticket stays.  Device and host destinations alike.  Eight device requests in flight, the ninth is VVR_ERR_BUSY."""
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(54)
-    ctx, picture, bank = setup(L, lambda w, h: H._ctx(L, w, h, 10, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), rng, 10)
+    ctx, picture, bank = setup(L, lambda w, h: SUP.make_ctx(L, w, h, 10, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), rng, 10)
     win = (2, 6, 202, 38)
     want = semi(crop(picture, win), "p010", 10)
     ext = C.c_void_p()
@@ -369,10 +354,10 @@ def test_stream_wait_is_one_wait_for_the_completion_event():
 
 def test_stream_wait_of_a_request_whose_job_failed():
     """a request submitted after its job is known to have failed: vvr_output_stream_wait gives the job's status and enqueues nothing"""
-    L = _lib()
+    L = SUP.stub_lib()
     Wd, Hd = 256, 128
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = Q._stream_ctx(L, Wd, Hd, nslots)
+    ctx = SUP.stream_ctx(L, Wd, Hd, nslots)
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=611, tool_flags=T.TOOLS, p_intra=0.3) for pl in plans[:2]]
     pics = [d.c() for d in descs]
     j0 = L.vvr_submit(ctx, C.byref(pics[0]))

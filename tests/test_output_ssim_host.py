@@ -9,13 +9,10 @@ import numpy as np
 import pytest
 
 import compare_ref
+import output_support as SUP
 import ssim_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_compare_host as XC
-import test_output_hash_host as XH
-import test_output_queue_host as Q
-import test_output_stats_host as X
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
@@ -29,19 +26,11 @@ WINDOWS = [(0, 0, 208, 80),       # the whole picture
 W400, H400 = 136, 8
 WINDOWS_400 = [(0, 0, 136, 8), (3, 0, 131, 8)]
 CONTENTS = ["identical", "noise", "inverse", "random", "flat", "seam", "last_window", "tail", "two_minima"]
-FILL = 0xaa
 ONE = 1 << 24
 
 
-def bind(L):
-    XC.bind(L)
-    L.vvr_ssim_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_compare_ssim.argtypes = [C.c_void_p, C.c_void_p]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
+def picture_size(cf):
+    return (W, H_) if cf else (W400, H400)
 
 
 def windows(nc):
@@ -51,7 +40,7 @@ def windows(nc):
 def submit(L, ctx, slot, win, ref, with_map=True, job=None, blocking=True, bps=2):
     """one vvr_ssim_submit -> (ticket or error, (the vvr_frame_ssim, the map) vvr_output_wait writes, both filled with 0xaa)"""
     raw = abi.FrameSsim()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     blocks = np.full(abi.ssim_map_shape(win), -0x55555556, np.int32) if with_map else None
     req = abi.ssim_request(slot, job, win, ref, raw, blocks, blocking, bps)
     return L.vvr_ssim_submit(ctx, C.byref(req)), (raw, blocks)
@@ -148,7 +137,7 @@ def periodic(planes, win, rng, bd):
 
 def forms(ref):
     """the forms a reference is given in: 2-byte samples at padded strides; 1-byte samples, when its values fit, at an odd byte stride"""
-    return XC.forms(ref)
+    return SUP.forms(ref)
 
 
 def check_contents(L, ctx, write, planes, bd):
@@ -232,107 +221,43 @@ def check_words_above_the_bit_depth(L, ctx, write, planes, bd):
         for ref in ([np.full(p.shape, top, np.int64) for p in held], [rng.integers(0, 1 << 16, p.shape, dtype=np.int64) for p in held]):
             want = ssim_ref.ssim(held, ref, bd)
             assert want == {**ssim_ref.ssim([np.minimum(p, top) for p in held], [np.minimum(p, top) for p in ref], bd), "map": want["map"]}
-            same(queued(L, ctx, 0, win, XC.forms(ref)[0][1]), want, win, bd, "words above the bit depth in the slot, window %r" % (win,))
+            same(queued(L, ctx, 0, win, SUP.forms(ref)[0][1]), want, win, bd, "words above the bit depth in the slot, window %r" % (win,))
     write(ctx, 0, planes)
 
 
-def check_ref_slot(L, ctx, write, a, b, bd):
-    """two pictures in slots 0 and 1, SSIM in both directions at every window"""
-    write(ctx, 0, a)
-    write(ctx, 1, b)
-    for win in windows(len(a)):
-        pa, pb = compare_ref.window_planes(a, win), compare_ref.window_planes(b, win)
-        same(queued(L, ctx, 0, win, 1), ssim_ref.ssim(pa, pb, bd), win, bd, "slot 0 against slot 1, window %r" % (win,))
-        same(queued(L, ctx, 1, win, 0), ssim_ref.ssim(pb, pa, bd), win, bd, "slot 1 against slot 0, window %r" % (win,))
+def ref_slot_case(L, ctx, slot, ref_slot, win, ps, pr, bd, what):
+    same(queued(L, ctx, slot, win, ref_slot), ssim_ref.ssim(ps, pr, bd), win, bd, what)
 
 
-def noisy(planes, bd, seed):
-    rng = np.random.default_rng(seed)
-    return [np.clip(p.astype(np.int64) + rng.integers(-8, 9, p.shape), 0, (1 << bd) - 1).astype(np.uint16) for p in planes]
-
-
-def statistics(L, ctx, planes, bd):
+def stats_case(L, ctx, planes, bd):
     """vvr_get_stats: one k_output_ssim and one k_output_ssim_sum per request; none with statistics off"""
-    L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
-    assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
-    win = (8, 4, 200, 64)
+    win = SUP.RING_WIN
     part = compare_ref.window_planes(planes, win)
-    ref = noisy(part, bd, 5)
-    for k in range(3):
-        same(queued(L, ctx, 0, win, XC.forms(ref)[0][1]), ssim_ref.ssim(part, ref, bd), win, bd, "with statistics on")
-    got = XC.launches(L, ctx)
-    assert got == {"k_output_ssim": 3, "k_output_ssim_sum": 3}, got
-    assert L.vvr_enable_stats(ctx, 0) == abi.VVR_OK
-    queued(L, ctx, 0, win, XC.forms(ref)[0][1])
-    assert not XC.launches(L, ctx)
+    ref = SUP.noisy(part, bd, 5)
+
+    def request():
+        same(queued(L, ctx, 0, win, SUP.forms(ref)[0][1]), ssim_ref.ssim(part, ref, bd), win, bd, "with statistics on")
+
+    def verify(got):
+        assert got == {"k_output_ssim": 3, "k_output_ssim_sum": 3}, got
+    return [request] * 3, verify, request
 
 
-def tickets_and_the_ring(L, ctx, planes, bd, ext):
-    """eight requests of the five kinds in flight, the ninth of any kind is VVR_ERR_BUSY; vvr_sync retires nothing; ext: a stream of the caller's
-    for vvr_output_stream_wait"""
-    win = (8, 4, 200, 64)
-    part = compare_ref.window_planes(planes, win)
-    ref = noisy(part, bd, 6)
-    want, want_cmp = ssim_ref.ssim(part, ref, bd), compare_ref.compare(part, ref)
-    given = XC.forms(ref)[0][1]
-    assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
-    flight = []
-    for n in range(8):
-        if n % 5 == 0:
-            flight.append(("ssim",) + submit(L, ctx, 0, win, given))
-        elif n % 5 == 1:
-            flight.append(("out",) + Q.submit(L, ctx, 0, win, "planar16", 3))
-        elif n % 5 == 2:
-            flight.append(("hash",) + XH.submit(L, ctx, 0, abi.HASH_CRC, 3))
-        elif n % 5 == 3:
-            flight.append(("stats",) + X.submit(L, ctx, 0, win, abi.STATS_LUMA))
-        else:
-            flight.append(("compare",) + XC.submit(L, ctx, 0, win, given))
-    assert all(t >= 2 for _, t, _ in flight) and len(set(t for _, t, _ in flight)) == 8, [t for _, t, _ in flight]
-    for t9 in (submit(L, ctx, 0, win, given)[0], Q.submit(L, ctx, 0, win, "planar16", 3)[0], XH.submit(L, ctx, 0, abi.HASH_CRC, 3)[0],
-               X.submit(L, ctx, 0, win, abi.STATS_LUMA)[0], XC.submit(L, ctx, 0, win, given)[0]):
-        assert t9 == abi.VVR_ERR_BUSY and b"in flight" in L.vvr_last_error(ctx)
-    assert b"vvr_compare_submit" in L.vvr_last_error(ctx)
-    assert submit(L, ctx, 0, win, given)[0] == abi.VVR_ERR_BUSY and b"vvr_ssim_submit" in L.vvr_last_error(ctx)
-    assert L.vvr_sync(ctx) == abi.VVR_OK
-    assert all(L.vvr_output_test(ctx, t) == abi.VVR_OK for _, t, _ in flight)
-    for n, (kind, t, keep) in enumerate(flight):
-        if kind == "ssim":
-            assert L.vvr_output_stream_wait(ctx, t, ext) == abi.VVR_OK
-            same(collect(L, ctx, t, keep), want, win, bd, "request %d of eight" % n)
-        elif kind == "compare":
-            XC.same(XC.collect(L, ctx, t, keep), want_cmp, win, bd, "request %d of eight" % n)
-        elif kind == "out":
-            assert all(np.array_equal(a, b) for a, b in zip(Q.collect(L, ctx, t, keep), part))
-        elif kind == "hash":
-            XH.collect(L, ctx, t, keep)
-        else:
-            X.same(X.collect(L, ctx, t, keep), X.expected(part, bd, abi.STATS_LUMA), win, bd, abi.STATS_LUMA, "request %d of eight" % n)
-    t = flight[0][1]
-    assert L.vvr_output_wait(ctx, t) == abi.VVR_ERR_PARAMETER and b"ticket" in L.vvr_last_error(ctx)
+def ring_request(L, ctx, planes, win, part, ref, bd):
+    given, want = SUP.forms(ref)[0][1], ssim_ref.ssim(part, ref, bd)
+    return lambda: submit(L, ctx, 0, win, given), lambda t, keep, what: same(collect(L, ctx, t, keep), want, win, bd, what)
 
 
 # ---- tests
 
 def test_the_structs_mirror_the_header(tmp_path):
     """sizeof / offsetof of the structs as gcc sees include/vvr.h == their ctypes mirrors; explicit pads only: the size is the sum of the fields"""
-    import os
-    import subprocess
     names = [("vvr_frame_ssim", abi.FrameSsim), ("vvr_ssim_request", abi.SsimRequest)]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vvr.h"', 'int main(void){']
-    want = []
-    for cname, mirror in names:
-        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
-        lines += ['printf("%%zu\\n", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_]
-        want += [C.sizeof(mirror)] + [getattr(mirror, f[0]).offset for f in mirror._fields_]
-    lines.append("return 0;}")
-    (tmp_path / "probe.c").write_text("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(os.path.dirname(T.HERE), "include"), str(tmp_path / "probe.c"), "-o", str(tmp_path / "probe")])
-    assert [int(v) for v in subprocess.check_output([str(tmp_path / "probe")]).split()] == want
+    SUP.assert_mirrors(tmp_path, names)
     for mirror in (abi.FrameSsim, abi.SsimRequest):
         assert C.sizeof(mirror) == sum(C.sizeof(f[1]) for f in mirror._fields_) and C.sizeof(mirror) % 8 == 0
     assert C.sizeof(abi.FrameSsim) == 152 and C.sizeof(abi.SsimRequest) == C.sizeof(abi.CompareRequest)
-    L = _lib()
+    L = SUP.stub_lib()
     assert L.vvr_abi_sizeof(18) == 0      # (no new index)
     assert abi.VVR_ABI_VERSION == 5
 
@@ -376,77 +301,55 @@ def test_truncation_is_toward_zero():
     assert ssim_ref.trunc_div(a, np.int64(3)).tolist() == [2, -2, 0, 0, (1 << 40) // 3, -((1 << 40) // 3)]
 
 
-def _ctx_with(L, bd, cf, seed):
-    w, h = (W, H_) if cf else (W400, H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    H.write_picture(L, ctx, 0, planes)
-    return ctx, planes
-
-
-def _write(L):
-    return lambda ctx, slot, p: H.write_picture(L, ctx, slot, p)
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_window(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1430 + bd + cf)
-    check_contents(L, ctx, _write(L), planes, bd)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1430 + bd + cf)
+    check_contents(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_slot_holding_words_above_the_bit_depth_is_clamped(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1440)
-    check_words_above_the_bit_depth(L, ctx, _write(L), planes, bd)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1440)
+    check_words_above_the_bit_depth(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_second_slot_as_the_reference(bd, cf):
-    L = _lib()
-    ctx, a = _ctx_with(L, bd, cf, 1450)
-    check_ref_slot(L, ctx, _write(L), a, noisy(a, bd, 1451), bd)
+    L = SUP.stub_lib()
+    ctx, a = SUP.ctx_with(L, picture_size(cf), bd, cf, 1450)
+    SUP.check_ref_slot("ssim", L, ctx, SUP.writer(L), a, SUP.noisy(a, bd, 1451), bd)
     L.vvr_destroy(ctx)
 
 
 def test_tickets_are_shared_with_the_other_kinds_of_request():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1460)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1460)
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
-    tickets_and_the_ring(L, ctx, planes, 10, ext)
+    SUP.tickets_and_the_ring("ssim", L, ctx, planes, 10, ext)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernels():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1461)
-    statistics(L, ctx, planes, 10)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1461)
+    SUP.statistics("ssim", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_ring_alone():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1462)
-    H.write_picture(L, ctx, 1, planes)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1462)
+    SUP.write_picture(L, ctx, 1, planes)
     win = (8, 4, 200, 64)
     part = [np.ascontiguousarray(p) for p in compare_ref.window_planes(planes, win)]
     keep = abi.FrameSsim()
 
-    def refused(text, c=ctx, ref=part, w_=win, **kw):
-        req = abi.ssim_request(0, None, w_, ref, keep)
-        for k, v in kw.items():
-            if k.startswith("stride"):
-                req.ref_stride_bytes[int(k[6:])] = v
-            elif k.startswith("plane"):
-                req.ref[int(k[5:])] = v
-            else:
-                setattr(req, k, v)
-        rc = L.vvr_ssim_submit(c, C.byref(req))
-        assert rc == abi.VVR_ERR_PARAMETER and text in L.vvr_last_error(c) and b"vvr_ssim_submit" in L.vvr_last_error(c), (kw, rc, L.vvr_last_error(c))
+    refused = SUP.refuser(L, ctx, "ssim", lambda ref=part, w_=win: abi.ssim_request(0, None, w_, ref, keep))
 
     # a window below 8 x 8
     for w, h in [(6, 8), (8, 6), (2, 2), (6, 80), (208, 6)]:
@@ -483,41 +386,28 @@ def test_refusals_leave_the_ring_alone():
     refused(b"different sizes", ref=1)
     assert L.vvr_slot_picture_size(ctx, 1, W, H_) == abi.VVR_OK
     # a 4:0:0 context: odd windows are fine, planes 1 and 2 are not looked at
-    ctx400, p400 = _ctx_with(L, 8, 0, 1463)
+    ctx400, p400 = SUP.ctx_with(L, picture_size(0), 8, 0, 1463)
     refused(b"outside the picture", c=ctx400, ref=[p400[0]], w_=(0, 0, W400 + 1, 8))
     refused(b"below 8 x 8", c=ctx400, ref=[p400[0]], w_=(0, 0, W400, 7))
     L.vvr_destroy(ctx400)
     assert L.vvr_ssim_submit(None, None) == abi.VVR_ERR_PARAMETER and L.vvr_ssim_submit(ctx, None) == abi.VVR_ERR_PARAMETER
     # the ring is untouched: eight requests still fit
-    flight = [submit(L, ctx, 0, win, part if n % 2 else 1) for n in range(8)]
-    assert all(t >= 2 for t, _ in flight) and len(set(t for t, _ in flight)) == 8, [t for t, _ in flight]
     want = ssim_ref.ssim(part, part, 10)
-    for t, got in flight:
-        same(collect(L, ctx, t, got), want, win, 10, "behind the refusals")
+    SUP.eight_still_fit(L, ctx, lambda n: submit(L, ctx, 0, win, part if n % 2 else 1), lambda t, got: same(collect(L, ctx, t, got), want, win, 10, "behind the refusals"))
     L.vvr_destroy(ctx)
 
 
 def test_a_failed_picture_fails_its_request():
-    L = _lib()
-    ctx, plans, descs, win = XC._stream(L, p_intra=0.3)
-    pics = [d.c() for d in descs]
-    ref = [np.zeros((win[3] >> s, win[2] >> s), np.uint16) for s in (0, 1, 1)]
-    j0 = L.vvr_submit(ctx, C.byref(pics[0]))
-    t0, k0 = submit(L, ctx, plans[0].slot, win, ref, job=j0)
-    assert t0 >= 2
-    L.vvt_fail_leaf_waits(1)
-    j1 = L.vvr_submit(ctx, C.byref(pics[1]))                         # its intra stage gives up a wait: the job fails when it completes
-    t1, k1 = submit(L, ctx, plans[1].slot, win, ref, job=j1)
-    assert t1 >= 2
-    assert L.vvr_output_test(ctx, t1) == abi.VVR_ERR_DEVICE and L.vvr_output_test(ctx, t0) == abi.VVR_OK
-    assert L.vvr_output_wait(ctx, t1) == abi.VVR_ERR_DEVICE and b"waited for its neighbours" in L.vvr_last_error(ctx)
-    assert bytes(k1[0]) == bytes([FILL]) * C.sizeof(abi.FrameSsim) and (k1[1] == -0x55555556).all(), "a request that failed writes nothing"
-    assert collect(L, ctx, t0, k0)[0].windows[0] == 63 * 31
-    t2, k2 = submit(L, ctx, plans[1].slot, win, plans[0].slot, job=j1)      # asked again after the failure is known: accepted, fails the same way
-    assert t2 >= 2 and L.vvr_output_wait(ctx, t2) == abi.VVR_ERR_DEVICE and bytes(k2[0]) == bytes([FILL]) * C.sizeof(abi.FrameSsim) and (k2[1] == -0x55555556).all()
-    L.vvt_fail_leaf_waits(0)
-    assert L.vvr_wait(ctx, j1) == abi.VVR_ERR_DEVICE and L.vvr_wait(ctx, j0) == abi.VVR_OK
-    L.vvr_destroy(ctx)
+    SUP.a_failed_picture_fails_its_request("ssim", SUP.stub_lib())
+
+
+def delivered(keep):
+    assert keep[0].windows[0] == 63 * 31
+
+
+SUP.register("ssim", b"vvr_ssim_submit", ring_request, stats=stats_case, ref_slot=ref_slot_case, cases=windows,
+             failing=lambda L, ctx, slot, win, job, ref_slot: submit(L, ctx, slot, win, XC.zeros_or_slot(win, ref_slot), job=job),
+             untouched=lambda keep: bytes(keep[0]) == bytes([SUP.FILL]) * C.sizeof(abi.FrameSsim) and (keep[1] == -0x55555556).all(), delivered=delivered)
 
 
 HAND = [("luma only is below one", 10, 3, [100, 25, 25], [100 * ONE - 12345, 25 * ONE, 25 * ONE]),
@@ -529,7 +419,7 @@ HAND = [("luma only is below one", 10, 3, [100, 25, 25], [100 * ONE - 12345, 25 
 
 @pytest.mark.parametrize("what,bd,nc,count,total", HAND)
 def test_mean_ssim_on_sums_built_by_hand(what, bd, nc, count, total):
-    L = _lib()
+    L = SUP.stub_lib()
     raw = abi.FrameSsim()
     raw.struct_size, raw.bit_depth, raw.num_components = C.sizeof(abi.FrameSsim), bd, nc
     for c in range(3):
@@ -547,13 +437,13 @@ def test_mean_ssim_on_sums_built_by_hand(what, bd, nc, count, total):
 
 
 def test_mean_ssim_of_a_request_and_its_refusals():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1470)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1470)
     win = WINDOWS[0]
     part = compare_ref.window_planes(planes, win)
-    ref = noisy(part, 10, 1471)
+    ref = SUP.noisy(part, 10, 1471)
     want = ssim_ref.ssim(part, ref, 10)
-    raw, _ = queued(L, ctx, 0, win, XC.forms(ref)[0][1])
+    raw, _ = queued(L, ctx, 0, win, SUP.forms(ref)[0][1])
     rc, got = c_mean(L, raw)
     assert rc == abi.VVR_OK and got == ssim_ref.mean(want) and all(0 < v < 1 for v in got)
     L.vvr_destroy(ctx)

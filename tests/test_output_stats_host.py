@@ -10,10 +10,9 @@ import pytest
 
 import colour_transform_ref as X
 import lut3d_ref as U
+import output_support as SUP
 import rgb_ref
-import test_film_grain_host as H
 import test_host_glue as T
-import test_output_hash_host as XH
 import test_output_lut3d_host as LH
 import test_output_queue_host as Q
 import test_output_rgb_host as R
@@ -34,19 +33,6 @@ W400, H400 = 136, 8
 WINDOWS_400 = [(0, 0, 136, 8), (3, 1, 131, 5), (129, 7, 7, 1), (5, 2, 1, 1)]
 
 
-def bind(L):
-    R.bind(L)
-    LH.bind(L)
-    XH.bind(L)
-    L.vvr_stats_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_light_level.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
-
-
 def cases():
     """(window, collocated, colour): every window at every chroma position; the colour descriptions alternate"""
     out = []
@@ -64,7 +50,7 @@ def picture(kind, rng, w, h, bd, cf=1):
     top = (1 << bd) - 1
     shapes = [(h >> s, w >> s) for s in ((0, 1, 1) if cf else (0,))]
     if kind == "random":
-        return XH.random_planes(rng, w, h, bd, cf)
+        return SUP.random_planes(rng, w, h, bd, cf)
     if kind == "flat":
         return [np.full(s, v, np.uint16) for s, v in zip(shapes, (3 * (top + 1) // 8 + 1, (top + 1) // 2 - 7, (top + 1) // 2 + 9))]
     if kind == "runs":
@@ -164,7 +150,7 @@ def check_flat_512x256(L, ctx, write):
 
 def small_picture_in_a_larger_slot(L, ctx, write, rng):
     """a 256x144 context, slot 1 declared to hold a 200x72 picture: windows are windows of the picture, its edge is where the taps clamp"""
-    full = XH.random_planes(rng, 256, 144, 10, 1)
+    full = SUP.random_planes(rng, 256, 144, 10, 1)
     write(ctx, 1, full)
     assert L.vvr_slot_picture_size(ctx, 1, 200, 72) == abi.VVR_OK
     assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
@@ -175,22 +161,18 @@ def small_picture_in_a_larger_slot(L, ctx, write, rng):
     assert t == abi.VVR_ERR_PARAMETER and b"outside the picture" in L.vvr_last_error(ctx)
 
 
-def launches(L, ctx):
-    return XH.launches(L, ctx)
-
-
-def statistics(L, ctx, planes, bd):
+def stats_case(L, ctx, planes, bd):
     """vvr_get_stats: one k_output_stats (and one k_output_stats_sum) per request of either mode; none with statistics off"""
-    L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
-    assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
-    win = (8, 4, 200, 64)
-    for mode in (abi.STATS_RGB, abi.STATS_LUMA, abi.STATS_RGB):
-        same(queued(L, ctx, 0, win, mode), expected(crop(planes, win), bd, mode, (1, 0), (True, False)), win, bd, mode, "with statistics on")
-    got = launches(L, ctx)
-    assert got.get("k_output_stats") == 3 and got.get("k_output_stats_sum") == 3 and "k_output_rgb" not in got, got
-    assert L.vvr_enable_stats(ctx, 0) == abi.VVR_OK
-    queued(L, ctx, 0, win, abi.STATS_RGB)
-    assert not launches(L, ctx)
+    win = SUP.RING_WIN
+
+    def request(mode):
+        def run():
+            same(queued(L, ctx, 0, win, mode), expected(crop(planes, win), bd, mode, (1, 0), (True, False)), win, bd, mode, "with statistics on")
+        return run
+
+    def verify(got):
+        assert got.get("k_output_stats") == 3 and got.get("k_output_stats_sum") == 3 and "k_output_rgb" not in got, got
+    return [request(mode) for mode in (abi.STATS_RGB, abi.STATS_LUMA, abi.STATS_RGB)], verify, lambda: queued(L, ctx, 0, win, abi.STATS_RGB)
 
 
 def rgb_requests_around_a_statistics_request(L, ctx, planes, bd):
@@ -220,35 +202,19 @@ def colour_snapshot(L, ctx, planes, bd):
     same(collect(L, ctx, t0, r0), w0, win, bd, abi.STATS_RGB, "first")
 
 
-def tickets_and_the_ring(L, ctx, planes, bd, ext):
-    """eight requests of the three kinds in flight, the ninth of any kind is VVR_ERR_BUSY; vvr_sync retires nothing; ext: a stream of the caller's
-    for vvr_output_stream_wait"""
-    win = (8, 4, 200, 64)
-    assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
-    flight = []
-    for n in range(8):
-        if n % 3 == 0:
-            flight.append(("stats",) + submit(L, ctx, 0, win, n // 3 % 2))
-        elif n % 3 == 1:
-            flight.append(("out",) + Q.submit(L, ctx, 0, win, "planar16", 3))
-        else:
-            flight.append(("hash",) + XH.submit(L, ctx, 0, abi.HASH_CRC, 3))
-    assert all(t >= 2 for _, t, _ in flight) and len(set(t for _, t, _ in flight)) == 8, [t for _, t, _ in flight]
-    for t9 in (submit(L, ctx, 0, win, abi.STATS_RGB)[0], Q.submit(L, ctx, 0, win, "planar16", 3)[0], XH.submit(L, ctx, 0, abi.HASH_CRC, 3)[0]):
-        assert t9 == abi.VVR_ERR_BUSY and b"in flight" in L.vvr_last_error(ctx)
-    assert L.vvr_sync(ctx) == abi.VVR_OK
-    assert all(L.vvr_output_test(ctx, t) == abi.VVR_OK for _, t, _ in flight)
-    for n, (kind, t, keep) in enumerate(flight):
-        if kind == "stats":
-            mode = n // 3 % 2
-            assert L.vvr_output_stream_wait(ctx, t, ext) == abi.VVR_OK
-            same(collect(L, ctx, t, keep), expected(crop(planes, win), bd, mode, (1, 0), (True, False)), win, bd, mode, "request %d of eight" % n)
-        elif kind == "out":
-            assert all(np.array_equal(a, b) for a, b in zip(Q.collect(L, ctx, t, keep), crop(planes, win)))
-        else:
-            XH.collect(L, ctx, t, keep)
-    t = flight[0][1]
-    assert L.vvr_output_wait(ctx, t) == abi.VVR_ERR_PARAMETER and b"ticket" in L.vvr_last_error(ctx)
+def ring_request(L, ctx, planes, win, part, ref, bd):
+    """luma and RGB statistics in turn (the colour description is BT.709, limited range)"""
+    modes = []
+
+    def start():
+        modes.append(len(modes) % 2)
+        t, raw = submit(L, ctx, 0, win, modes[-1])
+        return t, (raw, modes[-1])
+
+    def finish(t, keep, what):
+        raw, mode = keep
+        same(collect(L, ctx, t, raw), expected(part, bd, mode, (1, 0), (True, False)), win, bd, mode, what)
+    return start, finish
 
 
 # ---- the PQ EOTF and vvr_light_level restated
@@ -334,19 +300,8 @@ def loop_from_statistics_to_the_lut(L, ctx, write, rng):
 def test_the_structs_mirror_the_header(tmp_path):
     """sizeof / offsetof of the three structs as gcc sees include/vvr.h == their ctypes mirrors (vvr_abi_sizeof does not list them: they are
     guarded by their own struct_size)"""
-    import os
-    import subprocess
     names = [("vvr_frame_stats", abi.FrameStats), ("vvr_stats_request", abi.StatsRequest), ("struct vvr_light_level", abi.LightLevel)]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vvr.h"', 'int main(void){']
-    want = []
-    for cname, mirror in names:
-        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
-        lines += ['printf("%%zu\\n", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_]
-        want += [C.sizeof(mirror)] + [getattr(mirror, f[0]).offset for f in mirror._fields_]
-    lines.append("return 0;}")
-    (tmp_path / "probe.c").write_text("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(os.path.dirname(T.HERE), "include"), str(tmp_path / "probe.c"), "-o", str(tmp_path / "probe")])
-    assert [int(v) for v in subprocess.check_output([str(tmp_path / "probe")]).split()] == want
+    SUP.assert_mirrors(tmp_path, names)
     assert C.sizeof(abi.FrameStats) == 32 + 8192 + 24
 
 
@@ -365,81 +320,81 @@ def test_the_cases_meet_every_instantiation_of_the_kernel():
 @pytest.mark.parametrize("kind", CONTENTS)
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_statistics_of_every_case(bd, kind):
-    L = _lib()
+    L = SUP.stub_lib()
     planes = picture(kind, np.random.default_rng(900 + bd), W, H_, bd)
-    ctx = H._ctx(L, W, H_, bd, 1)
-    H.write_picture(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, W, H_, bd, 1)
+    SUP.write_picture(L, ctx, 0, planes)
     check_content(L, ctx, planes, bd, kind)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_luma_mode_in_a_400_context(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     planes = picture("random", np.random.default_rng(910 + bd), W400, H400, bd, 0)
-    ctx = H._ctx(L, W400, H400, bd, 0)
-    H.write_picture(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, W400, H400, bd, 0)
+    SUP.write_picture(L, ctx, 0, planes)
     check_400(L, ctx, planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_a_flat_512x256_frame_needs_32_bit_counts():
-    L = _lib()
-    ctx = H._ctx(L, 512, 256, 10, 1)
-    check_flat_512x256(L, ctx, lambda ctx, slot, p: H.write_picture(L, ctx, slot, p))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, 512, 256, 10, 1)
+    check_flat_512x256(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p))
     L.vvr_destroy(ctx)
 
 
 def test_the_picture_in_the_slot_not_the_slot():
-    L = _lib()
-    ctx = H._ctx(L, 256, 144, 10, 1)
-    small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(920))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, 256, 144, 10, 1)
+    small_picture_in_a_larger_slot(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(920))
     L.vvr_destroy(ctx)
 
 
 def _random_ctx(L, seed, bd=10):
     planes = picture("random", np.random.default_rng(seed), W, H_, bd)
-    ctx = H._ctx(L, W, H_, bd, 1)
-    H.write_picture(L, ctx, 0, planes)
+    ctx = SUP.make_ctx(L, W, H_, bd, 1)
+    SUP.write_picture(L, ctx, 0, planes)
     assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
     return ctx, planes
 
 
 def test_tickets_are_shared_with_output_and_hash_requests():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, planes = _random_ctx(L, 921)
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
-    tickets_and_the_ring(L, ctx, planes, 10, ext)
+    SUP.tickets_and_the_ring("stats", L, ctx, planes, 10, ext)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernel():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, planes = _random_ctx(L, 922)
-    statistics(L, ctx, planes, 10)
+    SUP.statistics("stats", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_rgb_requests_around_a_statistics_request_store_the_same_bytes():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, planes = _random_ctx(L, 923)
     rgb_requests_around_a_statistics_request(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_a_request_takes_the_colour_description_set_when_it_is_submitted():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, planes = _random_ctx(L, 924)
     colour_snapshot(L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_ring_the_seed_chain_and_the_colour_state_alone():
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(925)
     Wg, Hg = S.W, S.H_      # (film grain needs a frame wider than 128: the pictures of the grain tests)
-    ctx, pic, bank = S.setup(L, lambda w, h: H._ctx(L, w, h, 10, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), rng, 10)
+    ctx, pic, bank = S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, 10, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), rng, 10)
     win = (8, 4, 200, 64)
     keep = abi.FrameStats()
 
@@ -464,7 +419,7 @@ def test_refusals_leave_the_ring_the_seed_chain_and_the_colour_state_alone():
     refused(b"stats is NULL", stats=None)
     for x, y, w, h in [(Wg - 100, 0, 200, 64), (0, Hg - 2, 8, 4), (-2, 0, 8, 8), (0, 0, 0, 8), (0, 0, 8, 0), (0, 0, 8, -2), (1, 0, 8, 8), (0, 1, 8, 8), (0, 0, 7, 8), (0, 0, 8, 7)]:
         refused(b"outside the picture, empty, or odd", x=x, y=y, w=w, h=h)
-    ctx400 = H._ctx(L, W400, H400, 8, 0)
+    ctx400 = SUP.make_ctx(L, W400, H400, 8, 0)
     assert L.vvr_set_output_colour(ctx400, 1, 0) == abi.VVR_OK
     refused(b"no chroma", c=ctx400, x=0, y=0, w=8, h=8)
     L.vvr_destroy(ctx400)
@@ -482,10 +437,10 @@ def test_refusals_leave_the_ring_the_seed_chain_and_the_colour_state_alone():
 def test_not_ready_while_the_picture_is_with_its_worker():
     """as the hash request's test: the host stage of a B picture is held on its worker thread; a request without `blocking` comes back
     VVR_NOT_READY and takes no ring entry, the same request with `blocking` is accepted and delivers the statistics of the picture"""
-    L = _lib()
+    L = SUP.stub_lib()
     Wd, Hd = 256, 128
     plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = Q._stream_ctx(L, Wd, Hd, nslots)
+    ctx = SUP.stream_ctx(L, Wd, Hd, nslots)
     assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
     descs = [synth.picture_for_plan(pl, Wd, Hd, seed=611, tool_flags=T.TOOLS) for pl in plans[:2]]
     pics = [d.c() for d in descs]
@@ -513,30 +468,17 @@ def test_not_ready_while_the_picture_is_with_its_worker():
 
 
 def test_a_failed_picture_fails_its_request():
-    L = _lib()
-    Wd, Hd = 256, 128
-    plans, nslots = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
-    ctx = Q._stream_ctx(L, Wd, Hd, nslots)
-    assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
-    descs = [synth.picture_for_plan(pl, Wd, Hd, seed=611, tool_flags=T.TOOLS, p_intra=0.3) for pl in plans]
-    pics = [d.c() for d in descs]
-    win = (0, 0, Wd, Hd)
-    j0 = L.vvr_submit(ctx, C.byref(pics[0]))
-    t0, r0 = submit(L, ctx, plans[0].slot, win, abi.STATS_RGB, job=j0)
-    assert t0 >= 2
-    L.vvt_fail_leaf_waits(1)
-    j1 = L.vvr_submit(ctx, C.byref(pics[1]))                         # its intra stage gives up a wait: the job fails when it completes
-    t1, r1 = submit(L, ctx, plans[1].slot, win, abi.STATS_RGB, job=j1)
-    assert t1 >= 2
-    assert L.vvr_output_test(ctx, t1) == abi.VVR_ERR_DEVICE and L.vvr_output_test(ctx, t0) == abi.VVR_OK
-    assert L.vvr_output_wait(ctx, t1) == abi.VVR_ERR_DEVICE and b"waited for its neighbours" in L.vvr_last_error(ctx)
-    assert bytes(r1) == b"\xaa" * C.sizeof(abi.FrameStats), "a request that failed writes no statistics"
-    assert collect(L, ctx, t0, r0).samples == Wd * Hd
-    t2, r2 = submit(L, ctx, plans[1].slot, win, abi.STATS_LUMA, job=j1)      # asked again after the failure is known: accepted, fails the same way
-    assert t2 >= 2 and L.vvr_output_wait(ctx, t2) == abi.VVR_ERR_DEVICE and bytes(r2) == b"\xaa" * C.sizeof(abi.FrameStats)
-    L.vvt_fail_leaf_waits(0)
-    assert L.vvr_wait(ctx, j1) == abi.VVR_ERR_DEVICE and L.vvr_wait(ctx, j0) == abi.VVR_OK
-    L.vvr_destroy(ctx)
+    SUP.a_failed_picture_fails_its_request("stats", SUP.stub_lib())
+
+
+def delivered(raw):
+    assert raw.samples == raw.width * raw.height == 256 * 128
+
+
+SUP.register("stats", b"vvr_stats_submit", ring_request, stats=stats_case,
+             failing=lambda L, ctx, slot, win, job, ref_slot: submit(L, ctx, slot, win, abi.STATS_RGB if ref_slot is None else abi.STATS_LUMA, job=job),
+             untouched=lambda raw: bytes(raw) == b"\xaa" * C.sizeof(abi.FrameStats), delivered=delivered)
+
 
 
 HAND = [("a single bin", {700: 4321}, [700, 650, 12], 10),
@@ -547,7 +489,7 @@ HAND = [("a single bin", {700: 4321}, [700, 650, 12], 10),
 
 @pytest.mark.parametrize("what,bins,max_c,bd", HAND)
 def test_light_level_on_histograms_built_by_hand(what, bins, max_c, bd):
-    L = _lib()
+    L = SUP.stub_lib()
     hist = np.zeros(1024, np.int64)
     for v, n in bins.items():
         hist[v] = n
@@ -570,7 +512,7 @@ def test_pq_checkpoints_of_the_restatement():
 
 
 def test_light_level_refusals_leave_the_result_untouched():
-    L = _lib()
+    L = SUP.stub_lib()
     hist = np.zeros(1024, np.int64)
     hist[100] = 10
     untouched = b"\xaa" * C.sizeof(abi.LightLevel)
@@ -597,9 +539,9 @@ def test_light_level_refusals_leave_the_result_untouched():
 
 
 def test_the_loop_from_statistics_to_the_lut():
-    L = _lib()
-    ctx = H._ctx(L, W, H_, 10, 1)
-    loop_from_statistics_to_the_lut(L, ctx, lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(930))
+    L = SUP.stub_lib()
+    ctx = SUP.make_ctx(L, W, H_, 10, 1)
+    loop_from_statistics_to_the_lut(L, ctx, lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(930))
     L.vvr_destroy(ctx)
 
 
@@ -608,5 +550,5 @@ def test_python_mirror_of_the_modes_and_symbols():
     assert (abi.STATS_LUMA, abi.STATS_RGB) == (0, 1) and abi.STATS_MODES == {"luma": 0, "rgb": 1}
     assert "vvr_stats_submit" in vvdec_amd.EXPORTED_SYMBOLS and "vvr_light_level" in vvdec_amd.EXPORTED_SYMBOLS
     assert all(hasattr(vvdec_amd.Reconstructor, f) for f in ("stats_submit", "stats_wait")) and callable(vvdec_amd.light_level)
-    L = _lib()
+    L = SUP.stub_lib()
     assert L.vvr_abi_sizeof(18) == 0      # (no new index: the structs carry their struct_size)

@@ -12,8 +12,8 @@ import pytest
 
 import colour_transform_ref as X
 import film_grain_ref
+import output_support as SUP
 import rgb_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_queue_host as Q
 import test_output_rgb_host as R
@@ -26,19 +26,8 @@ FORMATS, STRAIGHT = R.FORMATS, R.STRAIGHT
 COLOUR = (9, 0)       # BT.2020 non-constant luminance, limited range: what HDR video is
 
 
-def bind(L):
-    R.bind(L)
-    L.vvr_set_output_transform.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_output_transform_preset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
-
-
 def _setup(L, bd, seed):
-    return S.setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
+    return S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
 
 
 def set_transform(L, ctx, transform):
@@ -174,7 +163,7 @@ def test_python_mirror_of_the_struct():
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_identity_is_plain_rgb16(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 110 + bd)
     check_identity(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -182,7 +171,7 @@ def test_identity_is_plain_rgb16(bd):
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_random_tables(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 120 + bd)
     check_random_tables(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -196,7 +185,7 @@ def test_the_random_cases_meet_every_instantiation_of_the_kernel():
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_extremes_need_64_bits(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 130 + bd)
     check_extremes(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -204,14 +193,14 @@ def test_extremes_need_64_bits(bd):
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_snapshot_and_scope(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 140 + bd)
     check_snapshot_and_scope(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_transform_in_force():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, 10, 150)
     win, col = (8, 4, 200, 64), (True, False)
     assert L.vvr_set_output_colour(ctx, *COLOUR) == abi.VVR_OK
@@ -236,7 +225,7 @@ def test_refusals_leave_the_transform_in_force():
     set_transform(L, ctx, edge)
     R.same_bytes(Q.queued(L, ctx, 0, win, "rgb16", 3, col=col), X.rgb(S.crop(picture, win), 10, "rgb16", COLOUR[0], bool(COLOUR[1]), col, edge), "+-65536")
     # a transform in a 4:0:0 context: set, and never met - RGB is refused there as ever
-    ctx400 = H._ctx(L, W, H_, 8, 0)
+    ctx400 = SUP.make_ctx(L, W, H_, 8, 0)
     set_transform(L, ctx400, first)
     assert L.vvr_set_output_colour(ctx400, 1, 0) == abi.VVR_OK
     shapes, dt = abi.output_plane_shapes(win, "rgb16", None, 3)
@@ -260,7 +249,7 @@ def c_preset(L, tc, cp, target, peaks, bd):
 
 def test_preset_tables_are_the_standards_formulas():
     """every entry of lin and enc within 1 of the float64 restatement (one pow that differs in its last bit can only move a rounding); the matrix equal"""
-    L = _lib()
+    L = SUP.stub_lib()
     for tc, cp, target, peaks, bd in PRESETS:
         rc, t = c_preset(L, tc, cp, target, peaks, bd)
         assert rc == abi.VVR_OK and t.struct_size == C.sizeof(abi.OutputTransform), (tc, cp, target, peaks, bd)
@@ -277,7 +266,7 @@ def test_preset_tables_are_the_standards_formulas():
 
 
 def test_preset_refuses_what_it_does_not_know():
-    L = _lib()
+    L = SUP.stub_lib()
     for args in [(1, 9, 0, 1000., 100., 10), (14, 9, 0, 1000., 100., 10), (16, 5, 0, 1000., 100., 10), (18, 12, 0, 1000., 100., 10), (16, 9, 3, 1000., 100., 10),
                  (16, 9, -1, 1000., 100., 10), (16, 9, 0, 1000., 100., 11), (18, 9, 0, 1000., 100., 7), (16, 9, 0, 0., 100., 10), (16, 9, 0, 1000., -1., 10),
                  (16, 9, 0, 10001., 100., 10), (16, 9, 0, float("nan"), 100., 10)]:

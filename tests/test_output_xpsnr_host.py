@@ -11,14 +11,10 @@ import numpy as np
 import pytest
 
 import compare_ref
+import output_support as SUP
 import xpsnr_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_compare_host as XC
-import test_output_hash_host as XH
-import test_output_queue_host as Q
-import test_output_ssim_host as XS
-import test_output_stats_host as X
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
@@ -34,20 +30,11 @@ WINDOWS_400 = [(0, 0, 136, 8),
 BLOCKS = [0, 4, 44, 64, 128, 256]      # by the formula (4 at these sizes); the smallest; off the tile grid; a tile; larger than a tile; larger than the window
 PARAMS = list(itertools.product(BLOCKS, (1, 2), (0, 1, 2)))      # block, filter (both forced at this size), temporal
 CONTENTS = ["identical", "noise", "random16", "flat", "prev_equal"]
-FILL = 0xaa
 BLOCK_DTYPE = np.dtype(abi.XPSNR_BLOCK_FIELDS)
 
 
-def bind(L):
-    XS.bind(L)
-    L.vvr_xpsnr_submit.argtypes = [C.c_void_p, C.c_void_p]
-    L.vvr_xpsnr_blocks.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.vvr_compare_xpsnr.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
-    return L
-
-
-def _lib():
-    return bind(H._lib())
+def picture_size(cf):
+    return (W, H_) if cf else (W400, H400)
 
 
 def windows(nc):
@@ -57,9 +44,9 @@ def windows(nc):
 def submit(L, ctx, slot, win, ref, prev=(), block=0, filter_=0, with_blocks=True, job=None, blocking=True, bps=2):
     """one vvr_xpsnr_submit -> (ticket or error, (the vvr_frame_xpsnr, the records) vvr_output_wait writes, both filled with 0xaa)"""
     raw = abi.FrameXpsnr()
-    C.memset(C.addressof(raw), FILL, C.sizeof(raw))
+    C.memset(C.addressof(raw), SUP.FILL, C.sizeof(raw))
     shape = abi.xpsnr_blocks(win[2], win[3], block)
-    blocks = np.frombuffer(bytearray([FILL]) * (BLOCK_DTYPE.itemsize * shape[1] * shape[2]), BLOCK_DTYPE) if with_blocks and shape else None
+    blocks = np.frombuffer(bytearray([SUP.FILL]) * (BLOCK_DTYPE.itemsize * shape[1] * shape[2]), BLOCK_DTYPE) if with_blocks and shape else None
     req = abi.xpsnr_request(slot, job, win, ref, raw, list(prev), blocks, block, filter_, blocking, bps)
     return L.vvr_xpsnr_submit(ctx, C.byref(req)), (raw, blocks)
 
@@ -136,7 +123,7 @@ def unaligned(plane):
 def forms(ref, prev):
     """the forms a reference and its prev planes are given in: 2-byte samples at padded strides; 2-byte samples at odd addresses and odd strides;
     1-byte samples, when all values fit, from an odd base at an odd byte stride"""
-    out = [("16-bit", [XC.padded(p, np.uint16, k) for p, k in zip(ref, (3, 5, 7))], [XC.padded(p, np.uint16, k) for p, k in zip(prev, (9, 1))]),
+    out = [("16-bit", [SUP.padded(p, np.uint16, k) for p, k in zip(ref, (3, 5, 7))], [SUP.padded(p, np.uint16, k) for p, k in zip(prev, (9, 1))]),
            ("16-bit at odd addresses", [unaligned(p) for p in ref], [unaligned(p) for p in prev])]
     if all(int(p.max()) <= 255 for p in list(ref) + list(prev)):
         def odd(p):
@@ -197,7 +184,7 @@ def check_consequences(L, ctx, write, planes, bd):
     """sse equals a vvr_compare_submit of the same request; the totals do not depend on the block size; the activity does not depend on the slot"""
     nc = len(planes)
     rng = np.random.default_rng(1510 + bd)
-    other = XS.noisy(planes, bd, 1511)
+    other = SUP.noisy(planes, bd, 1511)
     for win in windows(nc):
         part = compare_ref.window_planes(planes, win)
         ref, prev = reference("random16", rng, part, bd)
@@ -235,98 +222,45 @@ def check_anchor(L, ctx, write):
         assert rc == abi.VVR_OK and all(abs(g - w_) < 5e-7 for g, w_ in zip(db, want)), (db, want)
 
 
-def check_ref_slot(L, ctx, write, a, b, bd):
-    """two pictures in slots 0 and 1, the prev planes in host memory"""
-    write(ctx, 0, a)
-    write(ctx, 1, b)
-    rng = np.random.default_rng(1520)
-    for win in windows(len(a)):
-        pa, pb = compare_ref.window_planes(a, win), compare_ref.window_planes(b, win)
-        prev = [np.ascontiguousarray(rng.integers(0, 1 << bd, pa[0].shape), np.uint16) for _ in range(2)]
-        for (s, r), (ps, pr) in (((0, 1), (pa, pb)), ((1, 0), (pb, pa))):
-            for block, flt, temporal in ((0, 1, 2), (64, 2, 1), (44, 2, 0)):
-                want = xpsnr_ref.xpsnr_integers(ps, pr, prev[:temporal], block, flt)
-                same(queued(L, ctx, s, win, r, prev[:temporal], block=block, filter_=flt), want, win, bd, "slot %d against slot %d, window %r" % (s, r, win))
+def ref_slot_case(L, ctx, slot, ref_slot, win, ps, pr, bd, what):
+    """the prev planes in host memory: the same two for both directions"""
+    prev = [np.ascontiguousarray(np.random.default_rng(1520 + k).integers(0, 1 << bd, ps[0].shape), np.uint16) for k in range(2)]
+    for block, flt, temporal in ((0, 1, 2), (64, 2, 1), (44, 2, 0)):
+        want = xpsnr_ref.xpsnr_integers(ps, pr, prev[:temporal], block, flt)
+        same(queued(L, ctx, slot, win, ref_slot, prev[:temporal], block=block, filter_=flt), want, win, bd, what)
 
 
-def statistics(L, ctx, planes, bd):
+def stats_case(L, ctx, planes, bd):
     """vvr_get_stats: one k_output_xpsnr per request and nothing else; none with statistics off"""
-    L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
-    assert L.vvr_enable_stats(ctx, 1) == abi.VVR_OK
-    win = (8, 4, 200, 64)
+    win = SUP.RING_WIN
     part = compare_ref.window_planes(planes, win)
     ref, prev = reference("noise", np.random.default_rng(5), part, bd)
     r16, p16 = forms(ref, prev)[0][1:]
-    for k in range(3):
-        same(queued(L, ctx, 0, win, r16, p16[:k], filter_=1 + k % 2), xpsnr_ref.xpsnr_integers(part, ref, prev[:k], 0, 1 + k % 2), win, bd, "with statistics on")
-    got = XC.launches(L, ctx)
-    assert got == {"k_output_xpsnr": 3}, got
-    assert L.vvr_enable_stats(ctx, 0) == abi.VVR_OK
-    queued(L, ctx, 0, win, r16, p16)
-    assert not XC.launches(L, ctx)
+
+    def request(k):
+        def run():
+            same(queued(L, ctx, 0, win, r16, p16[:k], filter_=1 + k % 2), xpsnr_ref.xpsnr_integers(part, ref, prev[:k], 0, 1 + k % 2), win, bd, "with statistics on")
+        return run
+
+    def verify(got):
+        assert got == {"k_output_xpsnr": 3}, got
+    return [request(k) for k in range(3)], verify, lambda: queued(L, ctx, 0, win, r16, p16)
 
 
-def tickets_and_the_ring(L, ctx, planes, bd, ext):
-    """eight requests of mixed kinds in flight, the ninth of any kind is VVR_ERR_BUSY; vvr_sync retires nothing; ext: a stream of the caller's
-    for vvr_output_stream_wait"""
-    win = (8, 4, 200, 64)
-    part = compare_ref.window_planes(planes, win)
-    ref, prev = reference("noise", np.random.default_rng(6), part, bd)
+def ring_request(L, ctx, planes, win, part, ref, bd):
+    """against the ring's reference with two prev planes of this request's own, blocks of 44, the second filter"""
+    _, prev = reference("noise", np.random.default_rng(6), part, bd)
     r16, p16 = forms(ref, prev)[0][1:]
-    want, want_cmp = xpsnr_ref.xpsnr_integers(part, ref, prev, 44, 2), compare_ref.compare(part, ref)
-    assert L.vvr_set_output_colour(ctx, 1, 0) == abi.VVR_OK
-    flight = []
-    for n in range(8):
-        if n % 5 == 0:
-            flight.append(("xpsnr",) + submit(L, ctx, 0, win, r16, p16, block=44, filter_=2))
-        elif n % 5 == 1:
-            flight.append(("out",) + Q.submit(L, ctx, 0, win, "planar16", 3))
-        elif n % 5 == 2:
-            flight.append(("hash",) + XH.submit(L, ctx, 0, abi.HASH_CRC, 3))
-        elif n % 5 == 3:
-            flight.append(("stats",) + X.submit(L, ctx, 0, win, abi.STATS_LUMA))
-        else:
-            flight.append(("compare",) + XC.submit(L, ctx, 0, win, r16))
-    assert all(t >= 2 for _, t, _ in flight) and len(set(t for _, t, _ in flight)) == 8, [t for _, t, _ in flight]
-    for t9 in (Q.submit(L, ctx, 0, win, "planar16", 3)[0], XH.submit(L, ctx, 0, abi.HASH_CRC, 3)[0], X.submit(L, ctx, 0, win, abi.STATS_LUMA)[0],
-               XC.submit(L, ctx, 0, win, r16)[0], XS.submit(L, ctx, 0, win, r16)[0], submit(L, ctx, 0, win, r16, p16)[0]):
-        assert t9 == abi.VVR_ERR_BUSY and b"in flight" in L.vvr_last_error(ctx)
-    assert b"vvr_xpsnr_submit" in L.vvr_last_error(ctx)
-    assert L.vvr_sync(ctx) == abi.VVR_OK
-    assert all(L.vvr_output_test(ctx, t) == abi.VVR_OK for _, t, _ in flight)
-    for n, (kind, t, keep) in enumerate(flight):
-        if kind == "xpsnr":
-            assert L.vvr_output_stream_wait(ctx, t, ext) == abi.VVR_OK
-            same(collect(L, ctx, t, keep), want, win, bd, "request %d of eight" % n)
-        elif kind == "compare":
-            XC.same(XC.collect(L, ctx, t, keep), want_cmp, win, bd, "request %d of eight" % n)
-        elif kind == "out":
-            assert all(np.array_equal(a, b) for a, b in zip(Q.collect(L, ctx, t, keep), part))
-        elif kind == "hash":
-            XH.collect(L, ctx, t, keep)
-        else:
-            X.same(X.collect(L, ctx, t, keep), X.expected(part, bd, abi.STATS_LUMA), win, bd, abi.STATS_LUMA, "request %d of eight" % n)
-    t = flight[0][1]
-    assert L.vvr_output_wait(ctx, t) == abi.VVR_ERR_PARAMETER and b"ticket" in L.vvr_last_error(ctx)
+    want = xpsnr_ref.xpsnr_integers(part, ref, prev, 44, 2)
+    return lambda: submit(L, ctx, 0, win, r16, p16, block=44, filter_=2), lambda t, keep, what: same(collect(L, ctx, t, keep), want, win, bd, what)
 
 
 # ---- tests
 
 def test_the_structs_mirror_the_header(tmp_path):
     """sizeof / offsetof of the structs as gcc sees include/vvr.h == their ctypes mirrors; explicit pads only: the size is the sum of the fields"""
-    import os
-    import subprocess
     names = [("vvr_xpsnr_block", abi.XpsnrBlock), ("vvr_frame_xpsnr", abi.FrameXpsnr), ("vvr_xpsnr_request", abi.XpsnrRequest)]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vvr.h"', 'int main(void){']
-    want = []
-    for cname, mirror in names:
-        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
-        lines += ['printf("%%zu\\n", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_]
-        want += [C.sizeof(mirror)] + [getattr(mirror, f[0]).offset for f in mirror._fields_]
-    lines.append("return 0;}")
-    (tmp_path / "probe.c").write_text("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(os.path.dirname(T.HERE), "include"), str(tmp_path / "probe.c"), "-o", str(tmp_path / "probe")])
-    assert [int(v) for v in subprocess.check_output([str(tmp_path / "probe")]).split()] == want
+    SUP.assert_mirrors(tmp_path, names)
     for _, mirror in names:
         assert C.sizeof(mirror) == sum(C.sizeof(f[1]) for f in mirror._fields_) and C.sizeof(mirror) % 8 == 0
     assert (C.sizeof(abi.XpsnrBlock), C.sizeof(abi.FrameXpsnr), C.sizeof(abi.XpsnrRequest)) == (48, 128, 136) and BLOCK_DTYPE.itemsize == 48
@@ -348,7 +282,7 @@ def test_the_anchor_comes_out_of_the_restatement():
 
 
 def test_block_sizes_and_the_geometry_call():
-    L = _lib()
+    L = SUP.stub_lib()
     for (w, h), b in (((3840, 2160), 128), ((1920, 1080), 64), ((1280, 720), 44), ((7680, 4320), 256), ((256, 128), 8), ((208, 80), 4)):
         assert xpsnr_ref.resolve_block(w, h) == b and abi.xpsnr_blocks(w, h)[0] == b
     out = [C.c_uint32(77) for _ in range(3)]
@@ -370,46 +304,34 @@ def test_block_sizes_and_the_geometry_call():
     assert xpsnr_ref.resolve_filter(2048, 1152) == 1 and xpsnr_ref.resolve_filter(2048, 1154) == 2 and xpsnr_ref.resolve_filter(3840, 2160) == 2
 
 
-def _ctx_with(L, bd, cf, seed):
-    w, h = (W, H_) if cf else (W400, H400)
-    planes = XH.random_planes(np.random.default_rng(seed), w, h, bd, cf)
-    ctx = H._ctx(L, w, h, bd, cf)
-    H.write_picture(L, ctx, 0, planes)
-    return ctx, planes
-
-
-def _write(L):
-    return lambda ctx, slot, p: H.write_picture(L, ctx, slot, p)
-
-
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 1), (8, 0), (10, 0)])
 def test_every_content_at_every_window(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1530 + bd + cf)
-    check_contents(L, ctx, _write(L), planes, bd)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1530 + bd + cf)
+    check_contents(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_what_follows_from_the_definition(bd, cf):
-    L = _lib()
-    ctx, planes = _ctx_with(L, bd, cf, 1540)
-    check_consequences(L, ctx, _write(L), planes, bd)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(cf), bd, cf, 1540)
+    check_consequences(L, ctx, SUP.writer(L), planes, bd)
     L.vvr_destroy(ctx)
 
 
 def test_the_anchor_on_the_stand_in_runtime():
-    L = _lib()
-    ctx, _ = _ctx_with(L, 10, 1, 1541)
-    check_anchor(L, ctx, _write(L))
+    L = SUP.stub_lib()
+    ctx, _ = SUP.ctx_with(L, picture_size(1), 10, 1, 1541)
+    check_anchor(L, ctx, SUP.writer(L))
     L.vvr_destroy(ctx)
 
 
 @pytest.mark.parametrize("bd,cf", [(10, 1), (8, 0)])
 def test_a_second_slot_as_the_reference_with_prev_planes_on_the_host(bd, cf):
-    L = _lib()
-    ctx, a = _ctx_with(L, bd, cf, 1550)
-    check_ref_slot(L, ctx, _write(L), a, XS.noisy(a, bd, 1551), bd)
+    L = SUP.stub_lib()
+    ctx, a = SUP.ctx_with(L, picture_size(cf), bd, cf, 1550)
+    SUP.check_ref_slot("xpsnr", L, ctx, SUP.writer(L), a, SUP.noisy(a, bd, 1551), bd)
     L.vvr_destroy(ctx)
 
 
@@ -417,11 +339,10 @@ def test_the_three_homes_of_the_planes():
     """pageable memory (overwritten right after vvr_xpsnr_submit; one staging copy for the reference and the prev planes together), memory of
     vvr_host_alloc (no staging copy), a registered range (read in place); prev planes beside a ref_slot likewise; mixed homes and a prev plane
     partly inside a range are refused"""
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1560)
-    H.write_picture(L, ctx, 1, XS.noisy(planes, 10, 1561))
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1560)
+    SUP.write_picture(L, ctx, 1, SUP.noisy(planes, 10, 1561))
     rng = np.random.default_rng(1562)
-    L.vvt_take_h2d.argtypes = [C.c_void_p, C.c_void_p]
 
     def h2d():
         n, b = C.c_size_t(), C.c_size_t()
@@ -435,7 +356,7 @@ def test_the_three_homes_of_the_planes():
             ref, prev = reference("random16", rng, part, 10, 8 * bps)
             want = xpsnr_ref.xpsnr_integers(part, ref, prev, 44, 1)
             what = "window %r, %d bytes per sample" % (win, bps)
-            given, gprev = [XC.padded(p, dt, 3) for p in ref], [XC.padded(p, dt, 5) for p in prev]
+            given, gprev = [SUP.padded(p, dt, 3) for p in ref], [SUP.padded(p, dt, 5) for p in prev]
             h2d()
             t, keep = submit(L, ctx, 0, win, given, gprev, block=44, filter_=1)
             assert t >= 2 and h2d()[0] == 1
@@ -470,7 +391,7 @@ def test_the_three_homes_of_the_planes():
                 assert h2d()[0] == 0, "planes in pinned or device memory are not staged"
                 same(collect(L, ctx, t, keep), want, win, 10, "%s, %s" % (home, what))
                 if bps == 2:      # (a slot holds 16-bit words, and so do the prev planes beside it)
-                    other = compare_ref.window_planes(XS.noisy(planes, 10, 1561), win)
+                    other = compare_ref.window_planes(SUP.noisy(planes, 10, 1561), win)
                     t, keep = submit(L, ctx, 0, win, 1, placed[3:4], block=44, filter_=1)
                     assert t >= 2, L.vvr_last_error(ctx)
                     same(collect(L, ctx, t, keep), xpsnr_ref.xpsnr_integers(part, other, prev[:1], 44, 1), win, 10, "ref_slot with prev in %s, %s" % (home, what))
@@ -490,45 +411,31 @@ def test_the_three_homes_of_the_planes():
 
 
 def test_tickets_are_shared_with_the_other_kinds_of_request():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1570)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1570)
     ext = C.c_void_p()
     L.hipStreamCreateWithFlags(C.byref(ext), 0)
-    tickets_and_the_ring(L, ctx, planes, 10, ext)
+    SUP.tickets_and_the_ring("xpsnr", L, ctx, planes, 10, ext)
     L.vvr_destroy(ctx)
 
 
 def test_statistics_name_the_kernel():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1571)
-    statistics(L, ctx, planes, 10)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1571)
+    SUP.statistics("xpsnr", L, ctx, planes, 10)
     L.vvr_destroy(ctx)
 
 
 def test_refusals_leave_the_ring_alone():
-    L = _lib()
-    ctx, planes = _ctx_with(L, 10, 1, 1572)
-    H.write_picture(L, ctx, 1, planes)
+    L = SUP.stub_lib()
+    ctx, planes = SUP.ctx_with(L, picture_size(1), 10, 1, 1572)
+    SUP.write_picture(L, ctx, 1, planes)
     win = (8, 4, 200, 64)
     part = [np.ascontiguousarray(p) for p in compare_ref.window_planes(planes, win)]
     prev = [part[0].copy(), part[0].copy()]
     keep = abi.FrameXpsnr()
 
-    def refused(text, c=ctx, ref=part, w_=win, prev_=prev, **kw):
-        req = abi.xpsnr_request(0, None, w_, ref, keep, prev_)
-        for k, v in kw.items():
-            if k.startswith("stride"):
-                req.ref_stride_bytes[int(k[6:])] = v
-            elif k.startswith("plane"):
-                req.ref[int(k[5:])] = v
-            elif k.startswith("pstride"):
-                req.prev_stride_bytes[int(k[7:])] = v
-            elif k.startswith("pplane"):
-                req.prev[int(k[6:])] = v
-            else:
-                setattr(req, k, v)
-        rc = L.vvr_xpsnr_submit(c, C.byref(req))
-        assert rc == abi.VVR_ERR_PARAMETER and text in L.vvr_last_error(c) and b"vvr_xpsnr_submit" in L.vvr_last_error(c), (kw, rc, L.vvr_last_error(c))
+    refused = SUP.refuser(L, ctx, "xpsnr", lambda ref=part, w_=win, prev_=prev: abi.xpsnr_request(0, None, w_, ref, keep, prev_))
 
     # what only this request is refused for
     for w, h in [(6, 8), (8, 6), (2, 2), (6, 80), (208, 6)]:
@@ -577,52 +484,40 @@ def test_refusals_leave_the_ring_alone():
     refused(b"different sizes", ref=1)
     assert L.vvr_slot_picture_size(ctx, 1, W, H_) == abi.VVR_OK
     # a 4:0:0 context: odd windows are fine, planes 1 and 2 are not looked at
-    ctx400, p400 = _ctx_with(L, 8, 0, 1573)
+    ctx400, p400 = SUP.ctx_with(L, picture_size(0), 8, 0, 1573)
     refused(b"outside the picture", c=ctx400, ref=[p400[0]], w_=(0, 0, W400 + 1, 8), prev_=[])
     refused(b"below 8 x 8", c=ctx400, ref=[p400[0]], w_=(0, 0, W400, 7), prev_=[])
     L.vvr_destroy(ctx400)
     # more than 16384 blocks: 516 x 512 at B = 4 is 129 x 128 of them; 512 x 512 is accepted
-    big = H._ctx(L, 520, 512, 8, 0)
+    big = SUP.make_ctx(L, 520, 512, 8, 0)
     flat = [np.zeros((512, 520), np.uint16)]
-    H.write_picture(L, big, 0, flat)
+    SUP.write_picture(L, big, 0, flat)
     refused(b"more than 16384 blocks", c=big, ref=[flat[0][:, :516]], w_=(0, 0, 516, 512), prev_=[], block=4)
     got = queued(L, big, 0, (0, 0, 512, 512), [flat[0][:, :512]], block=4, filter_=1)
     assert (got[0].blocks_x, got[0].blocks_y, int(got[0].count)) == (128, 128, 510 * 510) and got[1].shape == (16384,)
     L.vvr_destroy(big)
     assert L.vvr_xpsnr_submit(None, None) == abi.VVR_ERR_PARAMETER and L.vvr_xpsnr_submit(ctx, None) == abi.VVR_ERR_PARAMETER
     # the ring is untouched: eight requests still fit
-    flight = [submit(L, ctx, 0, win, part if n % 2 else 1, prev) for n in range(8)]
-    assert all(t >= 2 for t, _ in flight) and len(set(t for t, _ in flight)) == 8, [t for t, _ in flight]
     want = xpsnr_ref.xpsnr_integers(part, part, prev)
-    for t, got in flight:
-        same(collect(L, ctx, t, got), want, win, 10, "behind the refusals")
+    SUP.eight_still_fit(L, ctx, lambda n: submit(L, ctx, 0, win, part if n % 2 else 1, prev), lambda t, got: same(collect(L, ctx, t, got), want, win, 10, "behind the refusals"))
     L.vvr_destroy(ctx)
 
 
 def test_a_failed_picture_fails_its_request():
-    L = _lib()
-    ctx, plans, descs, win = XC._stream(L, p_intra=0.3)
-    bind(L)
-    pics = [d.c() for d in descs]
-    ref = [np.zeros((win[3] >> s, win[2] >> s), np.uint16) for s in (0, 1, 1)]
-    j0 = L.vvr_submit(ctx, C.byref(pics[0]))
-    t0, k0 = submit(L, ctx, plans[0].slot, win, ref, ref[:1], job=j0)
-    assert t0 >= 2
-    L.vvt_fail_leaf_waits(1)
-    j1 = L.vvr_submit(ctx, C.byref(pics[1]))                         # its intra stage gives up a wait: the job fails when it completes
-    t1, k1 = submit(L, ctx, plans[1].slot, win, ref, ref[:1], job=j1)
-    assert t1 >= 2
-    assert L.vvr_output_test(ctx, t1) == abi.VVR_ERR_DEVICE and L.vvr_output_test(ctx, t0) == abi.VVR_OK
-    assert L.vvr_output_wait(ctx, t1) == abi.VVR_ERR_DEVICE and b"waited for its neighbours" in L.vvr_last_error(ctx)
-    untouched = lambda k: bytes(k[0]) == bytes([FILL]) * C.sizeof(abi.FrameXpsnr) and k[1].tobytes() == bytes([FILL]) * k[1].nbytes
-    assert untouched(k1), "a request that failed writes nothing"
-    got = collect(L, ctx, t0, k0)
-    assert (got[0].block, got[0].blocks_x, got[0].blocks_y, int(got[0].count)) == (8, 32, 16, 254 * 126)
-    t2, k2 = submit(L, ctx, plans[1].slot, win, plans[0].slot, ref[:1], job=j1)      # asked again after the failure is known: accepted, fails the same way
-    assert t2 >= 2 and L.vvr_output_wait(ctx, t2) == abi.VVR_ERR_DEVICE and untouched(k2)
-    L.vvt_fail_leaf_waits(0)
-    assert L.vvr_wait(ctx, j1) == abi.VVR_ERR_DEVICE and L.vvr_wait(ctx, j0) == abi.VVR_OK
-    L.vvr_destroy(ctx)
+    SUP.a_failed_picture_fails_its_request("xpsnr", SUP.stub_lib())
+
+
+def failing(L, ctx, slot, win, job, ref_slot):
+    zeros = XC.zeros_or_slot(win, None)
+    return submit(L, ctx, slot, win, zeros if ref_slot is None else ref_slot, zeros[:1], job=job)
+
+
+def delivered(keep):
+    assert (keep[0].block, keep[0].blocks_x, keep[0].blocks_y, int(keep[0].count)) == (8, 32, 16, 254 * 126)
+
+
+SUP.register("xpsnr", b"vvr_xpsnr_submit", ring_request, stats=stats_case, ref_slot=ref_slot_case, cases=windows, failing=failing,
+             untouched=lambda k: bytes(k[0]) == bytes([SUP.FILL]) * C.sizeof(abi.FrameXpsnr) and k[1].tobytes() == bytes([SUP.FILL]) * k[1].nbytes, delivered=delivered)
 
 
 def _hand(bd, nc, flt, w, h, records):
@@ -639,7 +534,7 @@ def _hand(bd, nc, flt, w, h, records):
 
 
 def test_decibels_from_records_built_by_hand_and_the_overrides():
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(1580)
     many = [([int(v) for v in rng.integers(0, 1 << 40, 3)], int(rng.integers(0, 1 << 36)), int(rng.integers(0, 1 << 34)), int(rng.integers(1, 1 << 14))) for _ in range(300)]
     cases = [("one block at the floor", 10, 3, 1, 128, 64, [([9, 4, 1], 0, 0, 100)]),

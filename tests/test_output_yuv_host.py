@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 import film_grain_ref
+import output_support as SUP
 import rgb_ref
 import yuv_ref
-import test_film_grain_host as H
 import test_host_glue as T
 import test_output_queue_host as Q
 import test_output_rgb_host as RGB
@@ -21,18 +21,10 @@ import test_output_semiplanar_host as S
 from vvdec_amd import abi
 
 pytestmark = T.pytestmark
-FILL = Q.FILL
+FILL = SUP.FILL
 W, H_ = S.W, S.H_
 PER_CASE = 3
 ALL_STRIDES = tuple((s, m) for s in S.STRIDES for m in (0, 2))
-
-
-def bind(L):
-    return RGB.bind(L)
-
-
-def _lib():
-    return bind(H._lib())
 
 
 def cases(bd):
@@ -121,7 +113,7 @@ def check_phase_0_is_the_identity(L, ctx, picture, wins=RGB.STRAIGHT):
 
 
 def _setup(L, bd, seed):
-    return S.setup(L, lambda w, h: H._ctx(L, w, h, bd, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
+    return S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, bd, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), np.random.default_rng(seed), bd)
 
 
 # ---- the restatement itself
@@ -173,7 +165,7 @@ def test_the_cases_meet_every_instantiation_of_the_kernel():
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_every_instantiation_straight_from_the_slot(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 125 + bd)
     check_instantiations(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -181,7 +173,7 @@ def test_every_instantiation_straight_from_the_slot(bd):
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_yuv_matrix(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 130 + bd)
     check_matrix(L, ctx, picture, bd)
     L.vvr_destroy(ctx)
@@ -189,7 +181,7 @@ def test_yuv_matrix(bd):
 
 @pytest.mark.parametrize("bd", [10, 8, 9])
 def test_the_444_planes_are_the_ones_the_rgb_formats_convert(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 140 + bd)
     check_the_planes_are_the_ones_rgb_converts(L, ctx, bd)
     L.vvr_destroy(ctx)
@@ -197,14 +189,14 @@ def test_the_444_planes_are_the_ones_the_rgb_formats_convert(bd):
 
 @pytest.mark.parametrize("bd", [10, 8])
 def test_phase_0_of_422_is_the_identity(bd):
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, bd, 150 + bd)
     check_phase_0_is_the_identity(L, ctx, picture)
     L.vvr_destroy(ctx)
 
 
 def test_one_plane_formats_ignore_the_other_planes():
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, 8, 160)
     win = (8, 4, 200, 64)
     for fmt in yuv_ref.ONE_PLANE:
@@ -219,9 +211,9 @@ def test_one_plane_formats_ignore_the_other_planes():
 
 
 def test_refusals_leave_the_ring_and_the_seed_chain_alone():
-    L = _lib()
+    L = SUP.stub_lib()
     rng = np.random.default_rng(161)
-    ctx, picture, bank = S.setup(L, lambda w, h: H._ctx(L, w, h, 10, 1), lambda ctx, slot, p: H.write_picture(L, ctx, slot, p), rng, 10)
+    ctx, picture, bank = S.setup(L, lambda w, h: SUP.make_ctx(L, w, h, 10, 1), lambda ctx, slot, p: SUP.write_picture(L, ctx, slot, p), rng, 10)
     win = (8, 4, 200, 64)
 
     def refused(text, c=ctx, fmt="yuv444p16", mutate=None, size=None, grain=False, w_=win):
@@ -238,14 +230,14 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
     first = Q.queued(L, ctx, 0, win, "planar16", 3, grain=True)
     assert L.vvr_set_film_grain_seed(ctx, 9) == abi.VVR_OK
     # a 4:0:0 context: no chroma to upsample
-    ctx400 = H._ctx(L, W, H_, 8, 0)
+    ctx400 = SUP.make_ctx(L, W, H_, 8, 0)
     for fmt in yuv_ref.FORMATS:
         refused(b"no chroma to upsample", c=ctx400, fmt=fmt)
     L.vvr_destroy(ctx400)
     # the 8-bit formats in a context of more than 8 bits: VVR_OUT_PLANAR8's wording
     for fmt in yuv_ref.BYTES:
         refused(b"8-bit output of a stream with more than 8 bits per sample", fmt=fmt, grain=True)
-    ctx9 = H._ctx(L, W, H_, 9, 1)
+    ctx9 = SUP.make_ctx(L, W, H_, 9, 1)
     for fmt in yuv_ref.BYTES:
         refused(b"8-bit output of a stream with more than 8 bits per sample", c=ctx9, fmt=fmt)
     L.vvr_destroy(ctx9)
@@ -290,7 +282,7 @@ def test_refusals_leave_the_ring_and_the_seed_chain_alone():
 
 def test_an_accepted_grained_request_advances_the_chain_once():
     """a grained y210 request takes one frame of the seed chain, as a grained planar16 request does: the request after it gets the next frame"""
-    L = _lib()
+    L = SUP.stub_lib()
     ctx, picture, bank = _setup(L, 10, 162)
     win = (8, 4, 200, 64)
     assert L.vvr_set_film_grain_seed(ctx, 33) == abi.VVR_OK

@@ -9,11 +9,10 @@ import torch                      # first: its HIP runtime is the one the proces
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vvdec_amd                  # noqa: E402
+import output_support as SUP        # noqa: E402
 import compare_ref                # noqa: E402
 import xpsnr_ref                  # noqa: E402
 import test_output_xpsnr_host as X                # noqa: E402
-import test_output_ssim_host as XS                # noqa: E402
-import test_output_hash_host as XH                # noqa: E402
 
 
 def agrees(got, want, win, what):
@@ -27,7 +26,7 @@ def agrees(got, want, win, what):
 def tensors_as_the_planes():
     rec = vvdec_amd.Reconstructor(X.W, X.H_, bit_depth=10, num_slots=2, num_streams=1)
     rng = np.random.default_rng(1580)
-    planes = XH.random_planes(rng, X.W, X.H_, 10, 1)
+    planes = SUP.random_planes(rng, X.W, X.H_, 10, 1)
     rec.write_picture(0, planes)
     rec.enable_stats()
     runs = 0
@@ -54,9 +53,9 @@ def tensors_as_the_planes():
         got = rec.xpsnr(0, [p.astype(dt) for p in ref], [p.astype(dt) for p in prev], window=win, with_blocks=True)
         runs += 1
         agrees(got, xpsnr_ref.xpsnr_integers(part, ref, prev), win, "numpy planes, %d bytes per sample" % bps)
-    other = XS.noisy(planes, 10, 1581)
+    other = SUP.noisy(planes, 10, 1581)
     rec.write_picture(1, other)
-    prev = [XS.noisy(planes, 10, 1582)[0]]
+    prev = [SUP.noisy(planes, 10, 1582)[0]]
     got = rec.xpsnr(0, 1, prev, with_blocks=True, a_pic=1000., peak=1020.)
     runs += 1
     want = xpsnr_ref.xpsnr_integers(planes, other, prev)

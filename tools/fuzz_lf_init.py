@@ -15,10 +15,7 @@ plans, _ = stream.ra_plan(5, gop=4, seed_poc0_is_external=False)
 
 
 def sweep(seed, seconds):
-    stub = C.CDLL(T.build_stub())
-    stub.vvr_last_error.restype = C.c_char_p; stub.vvr_last_error.argtypes = [C.c_void_p]
-    stub.vvr_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; stub.vvr_submit_prepared.argtypes = [C.c_void_p, C.c_void_p]
-    stub.vvr_free_prepared.argtypes = [C.c_void_p, C.c_void_p]; stub.vvr_destroy.argtypes = [C.c_void_p]; stub.vvr_sync.argtypes = [C.c_void_p]
+    stub = abi.bind(C.CDLL(T.build_stub()))
     rnd = random.Random(seed)
     t_end = time.time() + seconds
     n = bad = 0

@@ -23,8 +23,7 @@ lib, log = os.path.join(tmp, "hoststub_o3.so"), os.path.join(tmp, "stderr.txt")
 subprocess.check_call(["g++", "-std=c++17", "-O3", "-fPIC", "-shared", "-pthread", "-Wl,-Bsymbolic", "-I" + T.HIP_INC, "-D__HIP_PLATFORM_AMD__", "-DVVR_DEV_ENV", "-DVVT_NO_LF_STANDIN", "-w",
                        os.path.join(a.root, "tests", "hoststub", "vvr_host_stub.cpp"), "-o", lib])
 os.environ["VVR_PHASES"] = "1"
-L = C.CDLL(lib)
-L.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]; L.vvr_wait.argtypes = [C.c_void_p, C.c_int]; L.vvr_destroy.argtypes = [C.c_void_p]
+L = abi.bind(C.CDLL(lib))
 W, H, mix, _, _ = bench.CONFIGS["4k"]
 plans, nslots = stream.ra_plan(1, gop=1, seed_poc0_is_external=False)
 d = synth.picture_for_plan(plans[0], W, H, seed=1234, tool_flags=bench._tools(abi), **mix)

@@ -8,8 +8,7 @@ import bench
 import test_host_glue as T
 lib = "/tmp/vvr_hoststub_o3.so"
 subprocess.check_call(["g++", "-std=c++17", "-O3", "-fPIC", "-shared", "-pthread", "-Wl,-Bsymbolic", "-I" + T.HIP_INC, "-D__HIP_PLATFORM_AMD__", "-w", T.SRC, "-o", lib])
-L = C.CDLL(lib)
-L.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]; L.vvr_sync.argtypes = [C.c_void_p]; L.vvr_destroy.argtypes = [C.c_void_p]
+L = abi.bind(C.CDLL(lib))
 W, H = 3840, 2160
 plans, nslots = stream.ra_plan(17, gop=16, seed_poc0_is_external=False, pool=24)
 descs = [synth.picture_for_plan(pl, W, H, seed=1234, tool_flags=bench._tools(abi), **bench.MIX) for pl in plans[1:9]]

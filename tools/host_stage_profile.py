@@ -32,8 +32,7 @@ import bench
 import test_host_glue as T
 lib = "/tmp/vvr_hoststub_prof.so"
 subprocess.check_call(["g++", "-std=c++17", "-O3", "-g", "-fno-omit-frame-pointer", "-fPIC", "-shared", "-pthread", "-Wl,-Bsymbolic", "-I" + T.HIP_INC, "-D__HIP_PLATFORM_AMD__", "-DVVT_NO_LF_STANDIN", "-w", T.SRC, "-o", lib])
-L = C.CDLL(lib); P = C.CDLL("/tmp/libpcprof.so")
-L.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]; L.vvr_sync.argtypes = [C.c_void_p]
+L = abi.bind(C.CDLL(lib)); P = C.CDLL("/tmp/libpcprof.so")
 W, H = 3840, 2160
 plans, nslots = stream.ra_plan(17, gop=16, seed_poc0_is_external=False, pool=24)
 tools = bench._tools(abi) | abi.TOOL_LFP_ON_DEVICE | abi.TOOL_AFFINE_MV_ON_DEVICE

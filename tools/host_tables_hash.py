@@ -7,9 +7,7 @@ import numpy as np
 from vvdec_amd import abi, synth, stream
 import test_host_glue as T
 import subprocess, os
-L = C.CDLL(T.build_stub())      # (the tests' own build of the stand-in runtime library: one list of flags)
-L.vvr_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; L.vvr_free_prepared.argtypes = [C.c_void_p, C.c_void_p]; L.vvr_destroy.argtypes = [C.c_void_p]
-L.vvr_last_error.restype = C.c_char_p; L.vvr_last_error.argtypes = [C.c_void_p]
+L = abi.bind(C.CDLL(T.build_stub()))      # (the tests' own build of the stand-in runtime library: one list of flags)
 L.vvt_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
 out = {}
 extra = [("wp_sl", 256, 128, 5, 4, 520, T.TOOLS | abi.TOOL_WP | abi.TOOL_SCALING_LIST, dict(p_intra=0.2, p_affine=0.2, p_sbtmvp=0.2, p_geo=0.1, p_sbt=0.2)),

@@ -9,28 +9,16 @@ slot's and the reference's samples over the kernel's time - stand against vvr_me
 second of the library's copy kernel).
 --table FILE: the compiler's resource table (tools/kernel_resources.sh); the lines of the kernels measured here are quoted in the note.
 Usage: python tools/output_compare_cost.py [--repeats 30] [--rounds 5] [--table FILE] [--out profiles/output_compare_4k.txt] [--json FILE]"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-W, H = 3840, 2160
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from output_cost_common import W, H, picture, noisy, summary, timed, take_turns, main      # noqa: E402
+
 KERNELS = ("k_output_compare", "k_output_compare_sum", "k_output_stats", "k_output_stats_sum")
-
-
-def picture(rng):
-    yy, xx = np.mgrid[0:H, 0:W]
-    luma = (512 + 380 * np.sin(xx / 97.) * np.cos(yy / 61.) + rng.integers(-12, 13, (H, W))).clip(0, 1023).astype(np.uint16)
-    return [luma, (512 + (luma[::2, ::2].astype(np.int64) - 512) // 3 + rng.integers(-6, 7, (H // 2, W // 2))).clip(0, 1023).astype(np.uint16),
-            (512 - (luma[::2, ::2].astype(np.int64) - 512) // 4 + rng.integers(-6, 7, (H // 2, W // 2))).clip(0, 1023).astype(np.uint16)]
-
-
-def summary(v):
-    return {"round_medians": [round(float(x), 2) for x in v], "median": round(float(np.median(v)), 2), "spread": round(float(np.max(v) - np.min(v)), 2)}
 
 
 def measure(a):
@@ -40,7 +28,7 @@ def measure(a):
     rng = np.random.default_rng(7)
     planes = picture(rng)
     # the reference: the picture with coding-noise-like differences in a quarter of the samples
-    other = [np.where(rng.random(p.shape) < 0.25, (p.astype(np.int64) + rng.integers(-3, 4, p.shape)).clip(0, 1023), p).astype(np.uint16) for p in planes]
+    other = [noisy(rng, p) for p in planes]
     rec = vvdec_amd.Reconstructor(W, H, bit_depth=10, num_slots=2, num_streams=1)
     rec.write_picture(0, planes)
     rec.write_picture(1, other)
@@ -58,25 +46,13 @@ def measure(a):
                ("reference in device memory, 8-bit", dev8, 3), ("luma-mode statistics of the same frame (k_output_stats)", None, 2)]
     samples = W * H * 3 // 2
 
-    def kernel_ms():
-        st = {s["name"]: s["total_ms"] for s in rec.stats()}
-        return [st.get(k, 0.) for k in KERNELS]
+    def request(config):
+        name, ref, _b = config
+        if ref is None:
+            return timed(rec, KERNELS, lambda: rec.stats_wait(rec.stats_submit(0, window=(0, 0, W, H), mode="luma")))
+        return timed(rec, KERNELS, lambda: rec.compare(0, ref, window=(0, 0, W, H), with_map=True))
 
-    medians = {c[0]: [] for c in configs}
-    for _ in range(a.rounds):
-        times = {c[0]: [] for c in configs}
-        for k in range(3 + a.repeats):
-            for name, ref, _b in configs:
-                k0, t0 = kernel_ms(), time.perf_counter()
-                if ref is None:
-                    rec.stats_wait(rec.stats_submit(0, window=(0, 0, W, H), mode="luma"))
-                else:
-                    rec.compare(0, ref, window=(0, 0, W, H), with_map=True)
-                wall = time.perf_counter() - t0
-                if k >= 3:
-                    times[name].append([y - x for x, y in zip(k0, kernel_ms())] + [wall * 1000])
-        for name, _r, _b in configs:
-            medians[name].append([float(v) for v in np.median(np.array(times[name]), axis=0)])
+    medians = take_turns(configs, a.rounds, a.repeats, request)
     first = rec.compare(0, dev16, window=(0, 0, W, H))
     rec.close()
     res = {"size": [W, H], "bit_depth": 10, "repeats": a.repeats, "rounds": a.rounds, "library": vvdec_amd.lib().vvr_version().decode(),
@@ -87,14 +63,7 @@ def measure(a):
         nbytes = W * H * 2 if ref is None else samples * bps
         res["configs"][name] = {"kernel_us": summary(main), "fold_us": summary(fold), "request_wall_us": summary(m[:, 4]), "bytes_read": nbytes,
                                 "read_GBps": round(nbytes / (float(np.median(main)) * 1e-6) / 1e9, 1)}
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
-    text = compose(res, a.table)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text)
+    return res
 
 
 def compose(res, table):
@@ -122,15 +91,5 @@ def compose(res, table):
     return "\n".join(out) + "\n"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--table", default="")
-    ap.add_argument("--out", default="")
-    ap.add_argument("--json", default="")
-    measure(ap.parse_args())
-
-
 if __name__ == "__main__":
-    main()
+    main(measure, compose, table_only=False)

@@ -10,17 +10,14 @@ the launches, vvr_enable_stats / vvr_get_stats); the wall time is vvr_msssim_sub
 --table FILE: the compiler's resource table (tools/kernel_resources.sh); the lines of the kernels measured here are quoted in the note.
 --table-only: no GPU: the note holds the compiler's table and says that the times are NOT YET measured.
 Usage: python tools/output_msssim_cost.py [--repeats 30] [--rounds 5] [--table FILE] [--table-only] [--out profiles/output_msssim_4k.txt] [--json FILE]"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from output_compare_cost import W, H, picture, summary      # noqa: E402  (the same frame and the same reduction of the rounds)
+from output_cost_common import W, H, picture, noisy, summary, timed, take_turns, main      # noqa: E402
 
 KERNELS = ("k_output_msssim", "k_output_msssim_sum", "k_output_ssim", "k_output_ssim_sum")
 YARDSTICK = "SSIM request of the same frame (k_output_ssim), reference in device memory, 16-bit"
@@ -34,7 +31,7 @@ def measure(a):
     rng = np.random.default_rng(7)
     planes = picture(rng)
     # the reference: the picture with coding-noise-like differences in a quarter of the samples
-    other = [np.where(rng.random(p.shape) < 0.25, (p.astype(np.int64) + rng.integers(-3, 4, p.shape)).clip(0, 1023), p).astype(np.uint16) for p in planes]
+    other = [noisy(rng, p) for p in planes]
     rec = vvdec_amd.Reconstructor(W, H, bit_depth=10, num_slots=2, num_streams=1)
     rec.write_picture(0, planes)
     rec.write_picture(1, other)
@@ -46,25 +43,13 @@ def measure(a):
     configs = [("reference in device memory, 16-bit", dev16, SCALES), ("reference in another slot", 1, SCALES), (YARDSTICK, dev16, 0)]
     configs += [("%d scale%s, reference in device memory, 16-bit" % (n, "s" if n > 1 else ""), dev16, n) for n in range(1, SCALES)]
 
-    def kernel_ms():
-        st = {s["name"]: s["total_ms"] for s in rec.stats()}
-        return [st.get(k, 0.) for k in KERNELS]
+    def request(config):
+        name, ref, scales = config
+        if scales:
+            return timed(rec, KERNELS, lambda: rec.msssim(0, ref, window=(0, 0, W, H), scales=scales))
+        return timed(rec, KERNELS, lambda: rec.ssim(0, ref, window=(0, 0, W, H)))
 
-    medians = {c[0]: [] for c in configs}
-    for _ in range(a.rounds):
-        times = {c[0]: [] for c in configs}
-        for k in range(3 + a.repeats):
-            for name, ref, scales in configs:
-                k0, t0 = kernel_ms(), time.perf_counter()
-                if scales:
-                    rec.msssim(0, ref, window=(0, 0, W, H), scales=scales)
-                else:
-                    rec.ssim(0, ref, window=(0, 0, W, H))
-                wall = time.perf_counter() - t0
-                if k >= 3:
-                    times[name].append([y - x for x, y in zip(k0, kernel_ms())] + [wall * 1000])
-        for c in configs:
-            medians[c[0]].append([float(v) for v in np.median(np.array(times[c[0]]), axis=0)])
+    medians = take_turns(configs, a.rounds, a.repeats, request)
     first = rec.msssim(0, dev16, window=(0, 0, W, H), scales=SCALES)
     rec.close()
     res = {"size": [W, H], "bit_depth": 10, "scales": SCALES, "repeats": a.repeats, "rounds": a.rounds, "library": vvdec_amd.lib().vvr_version().decode(),
@@ -73,9 +58,6 @@ def measure(a):
         m = np.array(medians[name]) * 1000      # microseconds
         main, fold = (m[:, 0], m[:, 1]) if scales else (m[:, 2], m[:, 3])
         res["configs"][name] = {"scales": scales, "kernel_us": summary(main), "fold_us": summary(fold), "request_wall_us": summary(m[:, 4])}
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
     return res
 
 
@@ -114,21 +96,5 @@ def compose(res, table):
     return "\n".join(out) + "\n"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--table", default="")
-    ap.add_argument("--table-only", action="store_true")
-    ap.add_argument("--out", default="")
-    ap.add_argument("--json", default="")
-    a = ap.parse_args()
-    text = compose(None if a.table_only else measure(a), a.table)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text)
-
-
 if __name__ == "__main__":
-    main()
+    main(measure, compose)

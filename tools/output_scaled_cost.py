@@ -10,29 +10,18 @@ vvr_get_stats).  The condition the fused kernel has to meet: the median of (1) i
 round medians.  vvr_measure_copy_bandwidth of the same run is the ceiling the bytes stand against.
 --table FILE: the compiler's resource table (tools/kernel_resources.sh); the lines of the kernels measured here are quoted in the note.
 Usage: python tools/output_scaled_cost.py [--repeats 30] [--rounds 5] [--table FILE] [--out profiles/output_scaled_4k.txt] [--json FILE]"""
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-W, H = 3840, 2160
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from output_cost_common import W, H, picture, noisy, summary, timed, take_turns, main      # noqa: E402
+
 PW, PH = 1920, 1080
 KERNELS = ("k_output_compare_scaled", "k_rescale", "k_output_compare", "k_output_ssim", "k_output_msssim", "k_output_xpsnr")
 FUSED, RESCALE, COMPARE = 0, 1, 2
-
-
-def picture(rng, w, h):
-    yy, xx = np.mgrid[0:h, 0:w]
-    luma = (512 + 380 * np.sin(xx * (W / w) / 97.) * np.cos(yy * (H / h) / 61.) + rng.integers(-12, 13, (h, w))).clip(0, 1023).astype(np.uint16)
-    return [luma, (512 + (luma[::2, ::2].astype(np.int64) - 512) // 3 + rng.integers(-6, 7, (h // 2, w // 2))).clip(0, 1023).astype(np.uint16),
-            (512 - (luma[::2, ::2].astype(np.int64) - 512) // 4 + rng.integers(-6, 7, (h // 2, w // 2))).clip(0, 1023).astype(np.uint16)]
-
-
-def summary(v):
-    return {"round_medians": [round(float(x), 2) for x in v], "median": round(float(np.median(v)), 2), "spread": round(float(np.max(v) - np.min(v)), 2)}
 
 
 def measure(a):
@@ -41,7 +30,7 @@ def measure(a):
     import vvdec_amd
     rng = np.random.default_rng(11)
     rec = vvdec_amd.Reconstructor(W, H, bit_depth=10, num_slots=2, num_streams=1)
-    rec.write_picture(0, picture(rng, W, H))
+    rec.write_picture(0, picture(rng))
     rec._check(rec.L.vvr_slot_picture_size(rec.ctx, 1, PW, PH))
     for c, p in enumerate(picture(rng, PW, PH)):
         rec._check(rec.L.vvr_write_plane(rec.ctx, 1, c, p.ctypes.data, p.shape[1]))
@@ -49,7 +38,7 @@ def measure(a):
     small, full = (0, 0, PW, PH), (0, 0, W, H)
     # the reference: the rescaled picture with coding-noise-like differences in a quarter of the samples
     up = rec.read_output(1, small, 2, size=(W, H))
-    other = [np.where(rng.random(p.shape) < 0.25, (p.astype(np.int64) + rng.integers(-3, 4, p.shape)).clip(0, 1023), p).astype(np.uint16) for p in up]
+    other = [noisy(rng, p) for p in up]
     ref = [torch.from_numpy(p.view(np.int16)).cuda() for p in other]
     prev = [torch.from_numpy(np.roll(other[0], 3, 1).view(np.int16)).cuda()]
     torch.cuda.synchronize()
@@ -60,26 +49,19 @@ def measure(a):
                 ("XPSNR, temporal 1", lambda slot, win: rec.xpsnr(slot, ref, prev, window=win))]
     configs = [("%s, %s" % (name, how), call, scaled) for name, call in requests for how, scaled in (("1080p rescaled to 4K", True), ("4K picture", False))]
 
-    def kernel_ms():
-        st = {s["name"]: s["total_ms"] for s in rec.stats()}
-        return [st.get(k, 0.) for k in KERNELS]
+    def request(config):
+        name, call, scaled = config
+        rec.set_compare_scaling((W, H) if scaled else None)
+        return timed(rec, KERNELS, lambda: call(1 if scaled else 0, small if scaled else full))[:-1]
 
-    medians = {c[0]: [] for c in configs}
     unfused = []
-    for _ in range(a.rounds):
-        times = {c[0]: [] for c in configs}
-        for k in range(3 + a.repeats):
-            for name, call, scaled in configs:
-                rec.set_compare_scaling((W, H) if scaled else None)
-                k0 = kernel_ms()
-                call(1 if scaled else 0, small if scaled else full)
-                if k >= 3:
-                    times[name].append([y - x for x, y in zip(k0, kernel_ms())])
-        for name, _c, _s in configs:
-            medians[name].append([float(v) for v in np.median(np.array(times[name]), axis=0)])
-        # the unfused sequence, request by request: k_rescale of this turn's scaled SSIM request + k_output_compare of this turn's 4K comparison
+
+    def unfused_pairs(times):
+        """the unfused sequence, request by request: k_rescale of this turn's scaled SSIM request + k_output_compare of this turn's 4K comparison"""
         pairs = np.array(times["SSIM, 1080p rescaled to 4K"])[:, RESCALE] + np.array(times["comparison, 4K picture"])[:, COMPARE]
         unfused.append(float(np.median(pairs)))
+
+    medians = take_turns(configs, a.rounds, a.repeats, request, unfused_pairs)
     rec.set_compare_scaling((W, H))
     first = rec.compare(1, ref, window=small)
     rec.close()
@@ -92,14 +74,7 @@ def measure(a):
     res["fused_us"] = fused
     res["unfused_us"] = summary(np.array(unfused) * 1000)
     res["condition_met"] = bool(fused["median"] <= res["unfused_us"]["median"] + res["unfused_us"]["spread"])
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
-    text = compose(res, a.table)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text)
+    return res
 
 
 def compose(res, table):
@@ -129,15 +104,5 @@ def compose(res, table):
     return "\n".join(out) + "\n"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--table", default="")
-    ap.add_argument("--out", default="")
-    ap.add_argument("--json", default="")
-    measure(ap.parse_args())
-
-
 if __name__ == "__main__":
-    main()
+    main(measure, compose, table_only=False)

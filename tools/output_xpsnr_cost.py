@@ -9,17 +9,14 @@ vvr_xpsnr_submit .. vvr_output_wait on the host.
 --table FILE: the compiler's resource table (tools/kernel_resources.sh); the lines of the kernels measured here are quoted in the note.
 --table-only: no GPU: the note holds the compiler's table and says that the times are unmeasured.
 Usage: python tools/output_xpsnr_cost.py [--repeats 30] [--rounds 5] [--table FILE] [--table-only] [--out profiles/output_xpsnr_4k.txt] [--json FILE]"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from output_compare_cost import W, H, picture, summary      # noqa: E402  (the same frame and the same reduction of the rounds)
+from output_cost_common import W, H, picture, noisy, summary, timed, take_turns, main      # noqa: E402
 
 KERNELS = ("k_output_xpsnr", "k_output_compare")
 YARDSTICK = "comparison request of the same frame (k_output_compare), reference in device memory, 16-bit"
@@ -32,10 +29,8 @@ def measure(a):
     rng = np.random.default_rng(7)
     planes = picture(rng)
     # the reference ("source"): the picture with coding-noise-like differences in a quarter of the samples; its two predecessors: the same again
-    def noisy(p):
-        return np.where(rng.random(p.shape) < 0.25, (p.astype(np.int64) + rng.integers(-3, 4, p.shape)).clip(0, 1023), p).astype(np.uint16)
-    other = [noisy(p) for p in planes]
-    before = [noisy(other[0]), noisy(other[0])]
+    other = [noisy(rng, p) for p in planes]
+    before = [noisy(rng, other[0]), noisy(rng, other[0])]
     rec = vvdec_amd.Reconstructor(W, H, bit_depth=10, num_slots=2, num_streams=1)
     rec.write_picture(0, planes)
     ceiling = rec.copy_bandwidth(20)
@@ -50,25 +45,13 @@ def measure(a):
                ("temporal 2, planes in device memory, 8-bit", dev8, prev8, samples * 3 + 2 * luma),
                (YARDSTICK, dev16, None, samples * 4)]
 
-    def kernel_ms():
-        st = {s["name"]: s["total_ms"] for s in rec.stats()}
-        return [st.get(k, 0.) for k in KERNELS]
+    def request(config):
+        name, ref, prev, _b = config
+        if prev is None:
+            return timed(rec, KERNELS, lambda: rec.compare(0, ref, window=(0, 0, W, H), with_map=True))
+        return timed(rec, KERNELS, lambda: rec.xpsnr(0, ref, prev, window=(0, 0, W, H)))
 
-    medians = {c[0]: [] for c in configs}
-    for _ in range(a.rounds):
-        times = {c[0]: [] for c in configs}
-        for k in range(3 + a.repeats):
-            for name, ref, prev, _b in configs:
-                k0, t0 = kernel_ms(), time.perf_counter()
-                if prev is None:
-                    rec.compare(0, ref, window=(0, 0, W, H), with_map=True)
-                else:
-                    rec.xpsnr(0, ref, prev, window=(0, 0, W, H))
-                wall = time.perf_counter() - t0
-                if k >= 3:
-                    times[name].append([y - x for x, y in zip(k0, kernel_ms())] + [wall * 1000])
-        for c in configs:
-            medians[c[0]].append([float(v) for v in np.median(np.array(times[c[0]]), axis=0)])
+    medians = take_turns(configs, a.rounds, a.repeats, request)
     first = rec.xpsnr(0, dev16, prev16, window=(0, 0, W, H))
     rec.close()
     res = {"size": [W, H], "bit_depth": 10, "repeats": a.repeats, "rounds": a.rounds, "library": vvdec_amd.lib().vvr_version().decode(),
@@ -79,9 +62,6 @@ def measure(a):
         main = m[:, 1] if prev is None else m[:, 0]
         res["configs"][name] = {"kernel_us": summary(main), "request_wall_us": summary(m[:, 2]), "bytes_read": nbytes,
                                 "read_GBps": round(nbytes / (float(np.median(main)) * 1e-6) / 1e9, 1)}
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
     return res
 
 
@@ -120,21 +100,5 @@ def compose(res, table):
     return "\n".join(out) + "\n"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--table", default="")
-    ap.add_argument("--table-only", action="store_true")
-    ap.add_argument("--out", default="")
-    ap.add_argument("--json", default="")
-    a = ap.parse_args()
-    text = compose(None if a.table_only else measure(a), a.table)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text)
-
-
 if __name__ == "__main__":
-    main()
+    main(measure, compose)

@@ -41,115 +41,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(_LIBPATH):
             raise VvrError("libvvdec_amd.so is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
-        L = C.CDLL(_LIBPATH)
-        L.vvr_version.restype = C.c_char_p
-        L.vvr_last_error.restype = C.c_char_p
-        L.vvr_last_error.argtypes = [C.c_void_p]
-        L.vvr_slot_bytes.restype = C.c_size_t
-        L.vvr_abi_sizeof.restype = C.c_size_t
-        L.vvr_plane_ptr.restype = C.c_void_p
-        L.vvr_plane_ptr.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.vvr_job_stream.restype = C.c_void_p
-        L.vvr_job_stream.argtypes = [C.c_void_p, C.c_int]
-        for f in ("vvr_create", "vvr_submit", "vvr_wait", "vvr_sync", "vvr_read_plane", "vvr_write_plane", "vvr_prepare",
-                  "vvr_submit_prepared", "vvr_enable_stats", "vvr_get_stats", "vvr_plane_layout"):
-            getattr(L, f).restype = C.c_int
-        L.vvr_destroy.argtypes = [C.c_void_p]
-        L.vvr_wait.argtypes = [C.c_void_p, C.c_int]
-        L.vvr_test.argtypes = [C.c_void_p, C.c_int]
-        L.vvr_sync.argtypes = [C.c_void_p]
-        L.vvr_submit.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vvr_submit_prepared.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_free_prepared.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_read_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-        L.vvr_write_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-        L.vvr_picture_hash.restype = C.c_int
-        L.vvr_picture_hash.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.vvr_read_output.restype = C.c_int
-        L.vvr_read_output.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_size_t]
-        L.vvr_read_output_scaled.restype = C.c_int
-        L.vvr_read_output_scaled.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t]
-        L.vvr_set_film_grain.restype = C.c_int
-        L.vvr_set_film_grain.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_set_film_grain_seed.restype = C.c_int
-        L.vvr_set_film_grain_seed.argtypes = [C.c_void_p, C.c_uint32]
-        L.vvr_set_output_colour.restype = C.c_int
-        L.vvr_set_output_colour.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        abi.bind_output_narrowing(L)
-        abi.bind_compare_scaling(L)
-        abi.bind_output_resampling(L)
-        L.vvr_set_output_normalisation.restype = C.c_int
-        L.vvr_set_output_normalisation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vvr_set_output_transform.restype = C.c_int
-        L.vvr_set_output_transform.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_output_transform_preset.restype = C.c_int
-        L.vvr_output_transform_preset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
-        L.vvr_set_output_lut3d.restype = C.c_int
-        L.vvr_set_output_lut3d.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.vvr_output_lut3d_preset.restype = C.c_int
-        L.vvr_output_lut3d_preset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
-        L.vvr_read_output_grain.restype = C.c_int
-        L.vvr_read_output_grain.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-        L.vvr_read_dmvr.restype = C.c_int
-        L.vvr_read_dmvr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-        L.vvr_read_col_motion.restype = C.c_int
-        L.vvr_read_col_motion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-        L.vvr_enable_stats.argtypes = [C.c_void_p, C.c_int]
-        L.vvr_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.vvr_plane_layout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vvr_inputs_done.restype = C.c_int
-        L.vvr_inputs_done.argtypes = [C.c_void_p, C.c_int]
-        L.vvr_host_alloc.restype = C.c_void_p
-        L.vvr_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
-        L.vvr_host_free.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_measure_copy_bandwidth.restype = C.c_double
-        L.vvr_measure_copy_bandwidth.argtypes = [C.c_void_p, C.c_int]
-        L.vvr_stream_wait_job.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.vvr_stream_wait_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.vvr_slot_external_event.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.vvr_output_submit.restype = C.c_int
-        L.vvr_output_submit.argtypes = [C.c_void_p, C.c_void_p]
-        abi.bind_output_batch(L)
-        L.vvr_output_test.restype = C.c_int
-        L.vvr_output_test.argtypes = [C.c_void_p, C.c_int]
-        L.vvr_output_wait.restype = C.c_int
-        L.vvr_output_wait.argtypes = [C.c_void_p, C.c_int]
-        L.vvr_hash_submit.restype = C.c_int
-        L.vvr_hash_submit.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_stats_submit.restype = C.c_int
-        L.vvr_stats_submit.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_light_level.restype = C.c_int
-        L.vvr_light_level.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
-        L.vvr_compare_submit.restype = C.c_int
-        L.vvr_compare_submit.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_compare_psnr.restype = C.c_int
-        L.vvr_compare_psnr.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
-        L.vvr_ssim_submit.restype = C.c_int
-        L.vvr_ssim_submit.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_compare_ssim.restype = C.c_int
-        L.vvr_compare_ssim.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_msssim_submit.restype = C.c_int
-        L.vvr_msssim_submit.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_compare_msssim.restype = C.c_int
-        L.vvr_compare_msssim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vvr_xpsnr_submit.restype = C.c_int
-        L.vvr_xpsnr_submit.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_xpsnr_blocks.restype = C.c_int
-        L.vvr_xpsnr_blocks.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vvr_compare_xpsnr.restype = C.c_int
-        L.vvr_compare_xpsnr.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
-        L.vvr_output_stream_wait.restype = C.c_int
-        L.vvr_output_stream_wait.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.vvr_device_alloc.restype = C.c_void_p
-        L.vvr_device_alloc.argtypes = [C.c_void_p, C.c_size_t]
-        L.vvr_device_free.restype = None
-        L.vvr_device_free.argtypes = [C.c_void_p, C.c_void_p]
-        L.vvr_device_register.restype = C.c_int
-        L.vvr_device_register.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.vvr_device_unregister.restype = C.c_int
-        L.vvr_device_unregister.argtypes = [C.c_void_p, C.c_void_p]
-        _lib = L
+        _lib = abi.bind(C.CDLL(_LIBPATH))
     return _lib
 
 
@@ -432,7 +324,6 @@ class Reconstructor:
         arrs = [np.full((size[1] >> (1 if c else 0), (size[0] >> (1 if c else 0)) + pad), 0xffff, np.uint16) for c in range(ncomp)]
         dst = (C.c_void_p * 3)(*[a.ctypes.data for a in arrs] + [None] * (3 - ncomp))
         strides = (C.c_size_t * 3)(*[a.shape[1] for a in arrs] + [0] * (3 - ncomp))
-        self.L.vvr_read_picture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         self._check(self.L.vvr_read_picture(self.ctx, slot, dst, strides, threads))
         for c, a in enumerate(arrs):
             assert pad == 0 or (a[:, a.shape[1] - pad:] == 0xffff).all(), "vvr_read_picture wrote outside the picture"

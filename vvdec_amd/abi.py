@@ -179,26 +179,10 @@ NARROW_MODES = {"refuse": NARROW_REFUSE, "truncate": NARROW_TRUNCATE, "round": N
 OUT_NARROWED = ("planar8", "nv12", "yuv444p8", "yuv422p8", "uyvy", "yuy2")
 
 
-def bind_output_narrowing(L):
-    """the ctypes signature of vvr_set_output_narrowing on a loaded library (the product's, or the host build of the tests)"""
-    L.vvr_set_output_narrowing.restype = C.c_int
-    L.vvr_set_output_narrowing.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    return L
-
-
 # vvr_set_output_resampling: the filter out_w / out_h resample with (VVR_RESAMPLE_*); None / "reference": the reference's DCTIF
 RESAMPLE_REFERENCE, RESAMPLE_AREA, RESAMPLE_TRIANGLE, RESAMPLE_CUBIC = 0, 1, 2, 3
 RESAMPLE_FILTERS = {None: RESAMPLE_REFERENCE, "reference": RESAMPLE_REFERENCE, "area": RESAMPLE_AREA, "triangle": RESAMPLE_TRIANGLE, "cubic": RESAMPLE_CUBIC}
 RESAMPLE_MAX_TAPS = 256
-
-
-def bind_output_resampling(L):
-    """the ctypes signatures of vvr_set_output_resampling and vvr_resample_taps on a loaded library (the product's, or the host build of the tests)"""
-    L.vvr_set_output_resampling.restype = C.c_int
-    L.vvr_set_output_resampling.argtypes = [C.c_void_p, C.c_int]
-    L.vvr_resample_taps.restype = C.c_int
-    L.vvr_resample_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    return L
 
 
 def resample_taps(L, filter, n, m, phase, i):
@@ -207,13 +191,6 @@ def resample_taps(L, filter, n, m, phase, i):
     first, w = C.c_int32(0), (C.c_int16 * RESAMPLE_MAX_TAPS)()
     count = L.vvr_resample_taps(RESAMPLE_FILTERS.get(filter, filter), int(n), int(m), int(phase), int(i), C.byref(first), w)
     return None if count < 0 else (first.value, list(w[:count]))
-
-
-def bind_compare_scaling(L):
-    """the ctypes signature of vvr_set_compare_scaling on a loaded library (the product's, or the host build of the tests)"""
-    L.vvr_set_compare_scaling.restype = C.c_int
-    L.vvr_set_compare_scaling.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    return L
 
 
 class OutputRequest(C.Structure):
@@ -246,13 +223,6 @@ OUT_BATCH_FORMATS = ("rgb8", "rgb16", "rgbf16", "rgbf32", "rgba8", "bgra8", "rgb
 class OutputBatch(C.Structure):
     """vvr_output_batch: the regions of a batch request (vvr_output_submit_batch, vvr.h)"""
     _fields_ = [("struct_size", u32), ("count", u32), ("origin", C.POINTER(i32)), ("batch_stride_bytes", C.c_size_t * 3)]
-
-
-def bind_output_batch(L):
-    """the ctypes signature of vvr_output_submit_batch on a loaded library (the product's, or the host build of the tests)"""
-    L.vvr_output_submit_batch.restype = C.c_int
-    L.vvr_output_submit_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
 
 
 def output_batch(origins, batch_stride_bytes):
@@ -538,3 +508,111 @@ def xpsnr_request(slot, job, window, ref, result, prev=(), blocks=None, block=0,
 
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", u64), ("total_ms", C.c_double), ("algo_bytes", C.c_double)]
+
+
+# The C signatures of include/vvr.h, name -> (restype, argtypes): the one place they are written down.  Pointers to structs, arrays and
+# opaque handles are c_void_p (byref(), addresses, arrays and None all pass); the two arrays of vvr_read_output_grain keep their element types.
+_int, _p, _sz, _dbl = C.c_int, C.c_void_p, C.c_size_t, C.c_double
+_submit = (_int, [_p, _p])
+SIGNATURES = {
+    "vvr_create": (_int, [_p, _p]),
+    "vvr_destroy": (None, [_p]),
+    "vvr_submit": _submit,
+    "vvr_inputs_done": (_int, [_p, _int]),
+    "vvr_host_alloc": (_p, [_p, _sz]),
+    "vvr_host_free": (None, [_p, _p]),
+    "vvr_wait": (_int, [_p, _int]),
+    "vvr_test": (_int, [_p, _int]),
+    "vvr_sync": (_int, [_p]),
+    "vvr_slot_bytes": (_sz, [_p]),
+    "vvr_plane_layout": (_int, [_p, _int, _p, _p, _p, _p]),
+    "vvr_plane_ptr": (_p, [_p, _int, _int]),
+    "vvr_read_plane": (_int, [_p, _int, _int, _p, _sz]),
+    "vvr_read_output": (_int, [_p] + [_int] * 7 + [_p, _sz]),
+    "vvr_read_output_scaled": (_int, [_p] + [_int] * 10 + [_p, _sz]),
+    "vvr_set_film_grain": _submit,
+    "vvr_set_film_grain_seed": (_int, [_p, u32]),
+    "vvr_read_output_grain": (_int, [_p] + [_int] * 6 + [C.POINTER(_p), C.POINTER(_sz)]),
+    "vvr_set_output_colour": (_int, [_p, _int, _int]),
+    "vvr_set_output_narrowing": (_int, [_p, _int, _int]),
+    "vvr_set_output_resampling": (_int, [_p, _int]),
+    "vvr_resample_taps": (_int, [_int] * 5 + [_p, _p]),
+    "vvr_set_output_normalisation": (_int, [_p, _p, _p]),
+    "vvr_set_output_transform": _submit,
+    "vvr_output_transform_preset": (_int, [_p, _int, _int, _int, _dbl, _dbl, _int]),
+    "vvr_set_output_lut3d": (_int, [_p, _int, _p]),
+    "vvr_output_lut3d_preset": (_int, [_p, _int, _int, _int, _int, _dbl, _dbl]),
+    "vvr_output_submit": _submit,
+    "vvr_output_submit_batch": (_int, [_p, _p, _p]),
+    "vvr_output_test": (_int, [_p, _int]),
+    "vvr_output_wait": (_int, [_p, _int]),
+    "vvr_device_alloc": (_p, [_p, _sz]),
+    "vvr_device_free": (None, [_p, _p]),
+    "vvr_device_register": (_int, [_p, _p, _sz]),
+    "vvr_device_unregister": _submit,
+    "vvr_output_stream_wait": (_int, [_p, _int, _p]),
+    "vvr_picture_hash": (_int, [_p, _int, _int, _p, _p]),
+    "vvr_hash_submit": _submit,
+    "vvr_stats_submit": _submit,
+    "vvr_light_level": (_int, [_p, _int, u32, _p]),
+    "vvr_compare_submit": _submit,
+    "vvr_compare_psnr": (_int, [_p, _dbl, _p]),
+    "vvr_ssim_submit": _submit,
+    "vvr_compare_ssim": (_int, [_p, _p]),
+    "vvr_msssim_submit": _submit,
+    "vvr_compare_msssim": (_int, [_p, _p, _p]),
+    "vvr_xpsnr_submit": _submit,
+    "vvr_xpsnr_blocks": (_int, [_int, _int, u32, _p, _p, _p]),
+    "vvr_compare_xpsnr": (_int, [_p, _p, _dbl, _dbl, _p]),
+    "vvr_set_compare_scaling": (_int, [_p, _int, _int, _int]),
+    "vvr_read_picture": (_int, [_p, _int, _p, _p, _int]),
+    "vvr_write_plane": (_int, [_p, _int, _int, _p, _sz]),
+    "vvr_slot_picture_size": (_int, [_p, _int, _int, _int]),
+    "vvr_read_dmvr": (_int, [_p, _int, _p, _sz]),
+    "vvr_read_col_motion": (_int, [_p, _int, _p, _sz]),
+    "vvr_prepare": (_int, [_p, _p, _p]),
+    "vvr_submit_prepared": _submit,
+    "vvr_free_prepared": (None, [_p, _p]),
+    "vvr_job_stream": (_p, [_p, _int]),
+    "vvr_stream_wait_job": (_int, [_p, _int, _p, _int]),
+    "vvr_stream_wait_slot": (_int, [_p, _int, _p, _int]),
+    "vvr_slot_external_event": (_int, [_p, _int, _p, _int]),
+    "vvr_last_error": (C.c_char_p, [_p]),
+    "vvr_version": (C.c_char_p, []),
+    "vvr_abi_sizeof": (_sz, [_int]),
+    "vvr_enable_stats": (_int, [_p, _int]),
+    "vvr_get_stats": (_int, [_p, _p, _int]),
+    "vvr_measure_copy_bandwidth": (_dbl, [_p, _int]),
+    "vvr_resolve_tr_type": (u8, [_p, _p, _p, _int, _int, _int, _int]),
+}
+
+
+def bind(L):
+    """the signatures of SIGNATURES on a loaded library (the product's, or the host build of the tests, which exports the same vvr_* names); a
+    missing symbol is an AttributeError"""
+    return _bind_names(L, *SIGNATURES)
+
+
+def _bind_names(L, *names):
+    for name in names:
+        f = getattr(L, name)
+        f.restype, f.argtypes = SIGNATURES[name][0], list(SIGNATURES[name][1])
+    return L
+
+
+# the per-feature helpers of earlier callers: the same table, a few names at a time
+def bind_output_narrowing(L):
+    return _bind_names(L, "vvr_set_output_narrowing")
+
+
+def bind_output_resampling(L):
+    return _bind_names(L, "vvr_set_output_resampling", "vvr_resample_taps")
+
+
+def bind_compare_scaling(L):
+    return _bind_names(L, "vvr_set_compare_scaling")
+
+
+def bind_output_batch(L):
+    return _bind_names(L, "vvr_output_submit_batch")
+
